@@ -65,6 +65,38 @@ def test_config5_at_the_bench_shape(tmp_path):
     pset.close()
 
 
+def test_bench_dump_outputs_are_the_timed_batch_pcm(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the PCM a caller of the timed batch reads (all of it for an output this
+    small), and the line reports the --steps it timed."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parent.parent
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--batch", "3", "--frames", "600",
+                        "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--dump-outputs",
+                        str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    pcm, idx, lens = (np.load(tmp_path / f"{n}.npy") for n in ("pcm", "pcm_index", "pcm_lengths"))
+    assert pcm.dtype == idx.dtype == lens.dtype == np.float64
+    eng = J.Engine.load([VOICE])
+    tab, vi = synth.VoiceTables(eng), eng.voice_info()
+    vi.beta = 0.0  # bench.py --beta default
+    utt = synth.synth_utterance(tab, 600, 0)
+    with J.Batch(vi, [utt] * 3) as b:
+        b.run()
+        b.sync()
+        want = [b.pcm(i) for i in range(3)]
+    assert lens.tolist() == [len(w) for w in want]
+    assert idx.tolist() == [[i, k] for i, w in enumerate(want) for k in range(len(w))]
+    for i, w in enumerate(want):
+        got = pcm[idx[:, 0] == i]
+        assert np.abs(got).max() > 1.0 and rel_rms(got, w) <= PCM_TOL, i
+
+
 def test_one_pass_of_the_config3_job():
     eng = J.Engine.load([VOICE])
     tab, vi = synth.VoiceTables(eng), eng.voice_info()

@@ -70,6 +70,28 @@ def test_bench_launcher_spawns_ranks_and_plans_config3():
     assert "error" not in plan
 
 
+def test_bench_dump_sample_points():
+    """bench.py --dump-outputs: the sample of a batch's PCM is the same from run to run, lies inside every
+    utterance, comes in order, takes all of a small output and keeps the files within 64 MB."""
+    import numpy as np
+
+    import bench
+
+    lens = [0, 5, 3, 0, 7]
+    u, p = bench.pcm_sample_points(lens, 100)
+    assert list(zip(u.tolist(), p.tolist())) == [(i, k) for i, n in enumerate(lens) for k in range(n)]
+    big = [synth.T_128S * 240] * 256  # config 2
+    u, p = bench.pcm_sample_points(big, bench.DUMP_POINTS)
+    u2, p2 = bench.pcm_sample_points(big, bench.DUMP_POINTS)
+    assert np.array_equal(u, u2) and np.array_equal(p, p2)
+    assert 0.99 * bench.DUMP_POINTS < len(u) <= bench.DUMP_POINTS
+    assert set(u.tolist()) == set(range(256)) and p.min() >= 0 and p.max() < big[0]
+    flat = u * big[0] + p
+    assert (np.diff(flat) > 0).all()
+    assert len(u) * (8 + 16) + len(big) * 8 <= 64 << 20  # pcm, pcm_index, pcm_lengths (float64)
+    assert bench.pcm_sample_points([], 10)[0].size == 0
+
+
 def _children_of(pid):
     out = subprocess.run(["ps", "-o", "pid=", "--ppid", str(pid)], capture_output=True, text=True).stdout.split()
     return [int(x) for x in out]
