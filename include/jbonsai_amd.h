@@ -187,6 +187,21 @@ int jb_batch_create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t
 /* Same from row indices into device-resident pdf tables (gather + blend on the GPU). */
 int jb_batch_create_indexed(const jb_voice_desc *voice, const jb_pdf_set *set, const jb_index_utt *utts,
                             size_t n_utts, const jb_batch_opts *opts, jb_batch **out);
+/* Vocoder condition of one utterance: the Vocoder::new arguments alpha, beta and volume (src/vocoder/mod.rs:45-55;
+ * Condition::alpha / beta / volume, src/engine.rs:46-80) that jb_voice_desc otherwise holds for the whole batch.
+ * volume is linear, as jb_voice_desc.volume.  The beta rule is the batch's: stage 0 filters with beta only where
+ * nmcp > 2 (cepstrum.rs:24), stage > 0 hands it to postfilter_lsp (lsp.rs:113-139). */
+typedef struct jb_utt_voc {
+    double alpha, beta, volume;
+} jb_utt_voc;
+/* jb_batch_create / jb_batch_create_indexed with one jb_utt_voc per utterance (voc[n_utts]): utterance u is vocoded
+ * as Vocoder::new(..., voc[u].alpha, voc[u].beta, voc[u].volume) would (new entry: the reference has no batch).
+ * voc == NULL: every utterance takes voice->alpha / beta / volume, i.e. jb_batch_create[_indexed].  Entries are
+ * checked like jb_voice_desc's (beta >= 0; alpha, beta, volume finite): JB_ERR_INVALID naming the entry. */
+int jb_batch_create_voc(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n_utts, const jb_utt_voc *voc,
+                        const jb_batch_opts *opts, jb_batch **out);
+int jb_batch_create_indexed_voc(const jb_voice_desc *voice, const jb_pdf_set *set, const jb_index_utt *utts,
+                                size_t n_utts, const jb_utt_voc *voc, const jb_batch_opts *opts, jb_batch **out);
 /* Enqueue the whole hot path (MLPG+GV x3 -> frame prologue -> pulse schedule ->
  * excitation + MLSA) on the batch's HIP stream.  Inputs are already resident. */
 int jb_batch_run(jb_batch *b);
@@ -433,6 +448,18 @@ int jb_synthesize_batch_i16(const jb_engine *e, const char *const *label_lines,
                             const size_t *line_off, size_t n_utts, int32_t device,
                             int16_t **pcm, size_t *n_samples);
 void jb_pcm_i16_free(int16_t *pcm);
+/* jb_synthesize_batch with one engine per utterance: utterance u is Engine::synthesize (src/engine.rs:250-266) of
+ * engines[u], under engines[u]'s whole Condition (speed, alignment flag, half tone, volume, alpha, beta, GV weights,
+ * MSD thresholds, the three kinds of interpolation weight), in one batch.  New entry (the reference has no batch).
+ * The engines share one voice set -- engines made from one another with jb_engine_new (Engine::clone) -- and agree
+ * on sampling_frequency, fperiod, stage, use_log_gain and the batch-invariant flag; otherwise JB_ERR_INVALID, with
+ * jb_last_error naming what differs, before any device is touched.  pcm[u] library-owned (jb_pcm_free each). */
+int jb_synthesize_batch_each(const jb_engine *const *engines, const char *const *label_lines, const size_t *line_off,
+                             size_t n_utts, int32_t device, double **pcm, size_t *n_samples);
+/* Same with the 16-bit sink (jb_synthesize_batch_i16); pcm[u]: jb_pcm_i16_free each. */
+int jb_synthesize_batch_each_i16(const jb_engine *const *engines, const char *const *label_lines,
+                                 const size_t *line_off, size_t n_utts, int32_t device, int16_t **pcm,
+                                 size_t *n_samples);
 /* The same two over a device list: the utterances are split by LPT on their label counts (the frame
  * counts are known only after the front half), one host thread per device runs jb_synthesize_batch's
  * path on its share (front half on that thread's workers, GPU work on that device). */
@@ -537,6 +564,8 @@ JB_LAYOUT_ASSERT(sizeof(jb_index_utt) == 360 && offsetof(jb_index_utt, stream) =
                      offsetof(jb_index_utt, lf0_offset) == 352, "jb_index_utt");
 JB_LAYOUT_ASSERT(sizeof(jb_track_utt) == 64 && offsetof(jb_track_utt, spectrum_width) == 24 &&
                      offsetof(jb_track_utt, spectrum) == 40, "jb_track_utt");
+JB_LAYOUT_ASSERT(sizeof(jb_utt_voc) == 24 && offsetof(jb_utt_voc, beta) == 8 && offsetof(jb_utt_voc, volume) == 16,
+                 "jb_utt_voc");
 #undef JB_LAYOUT_ASSERT
 #endif
 #endif /* JBONSAI_AMD_H */

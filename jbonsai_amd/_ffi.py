@@ -122,6 +122,11 @@ class TrackUtt(C.Structure):
     ]
 
 
+class UttVoc(C.Structure):
+    """jb_utt_voc: one utterance's vocoder condition (volume linear, as VoiceDesc.volume)."""
+    _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("volume", C.c_double)]
+
+
 class BatchOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32), ("chunk_frames", C.c_uint32),
                 ("warmup_frames", C.c_uint32), ("verify_tol", C.c_double), ("reserved0", C.c_uint32), ("reserved", C.c_uint32)]
@@ -153,6 +158,7 @@ SYMBOLS = [
     "jb_gathered_samples", "jb_gathered_sample_bytes", "jb_gathered_device", "jb_gathered_read", "jb_gathered_free",
     "jb_lpt_partition", "jb_paramgen_vocode_batch_multi", "jb_synthesize_batch_multi", "jb_synthesize_batch_i16_multi",
     "jb_states_duration_params", "jb_last_error", "jb_device_count", "jb_device_arch", "jb_device_pci_bus_id", "jb_version", "jb_default_verify_tol",
+    "jb_batch_create_voc", "jb_batch_create_indexed_voc", "jb_synthesize_batch_each", "jb_synthesize_batch_each_i16",
 ]
 
 
@@ -194,6 +200,10 @@ def lib():
     L.jb_pdf_set_free.restype = None
     L.jb_batch_create_indexed.argtypes = [C.POINTER(VoiceDesc), vp, C.POINTER(IndexUtt), sz, C.POINTER(BatchOpts),
                                           C.POINTER(vp)]
+    L.jb_batch_create_voc.argtypes = [C.POINTER(VoiceDesc), C.POINTER(StateUtt), sz, C.POINTER(UttVoc),
+                                      C.POINTER(BatchOpts), C.POINTER(vp)]
+    L.jb_batch_create_indexed_voc.argtypes = [C.POINTER(VoiceDesc), vp, C.POINTER(IndexUtt), sz, C.POINTER(UttVoc),
+                                              C.POINTER(BatchOpts), C.POINTER(vp)]
     L.jb_batch_run.argtypes = [vp]
     L.jb_batch_sync.argtypes = [vp]
     L.jb_batch_run_timed.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]

@@ -219,6 +219,11 @@ class TrackUtterance:
         return u
 
 
+# Batch(voc=VOC_NULL): jb_batch_create[_indexed]_voc with voc = NULL -- every utterance under the voice's own alpha,
+# beta and volume, through the per-utterance entry
+VOC_NULL = object()
+
+
 class Batch:
     """A batch of utterances resident in HBM (jb_batch_*).  `utts` are state-level utterances
     (Utterance), or -- with `pdf_set` -- pdf row indices (IndexUtterance: the per-state Gaussians are
@@ -231,7 +236,7 @@ class Batch:
                  chunk_frames: int = 0, warmup_frames: int = 0, verify_tol: float = 0.0,
                  kernel: str = "auto", serial_gv: bool = False, pcm_i16: bool = False,
                  pdf_set: Optional[PdfSet] = None, mlpg_only: bool = False,
-                 test_gang_timeout: bool = False, no_exc_table: bool = False):
+                 test_gang_timeout: bool = False, no_exc_table: bool = False, voc=None):
         L = F.lib()
         self._L = L
         self.voice = voice
@@ -253,7 +258,24 @@ class Batch:
         opts.chunk_frames, opts.warmup_frames, opts.verify_tol = chunk_frames, warmup_frames, verify_tol
         self.flags, self.device = opts.flags | (F.BATCH_KEEP_TRACKS if mlpg_only else 0), device
         h = C.c_void_p()
-        if from_tracks:
+        if voc is not None:
+            # per-utterance vocoder conditions (jb_batch_create[_indexed]_voc): UttVoc or (alpha, beta, volume) each
+            if from_tracks:
+                raise ValueError("voc= takes state-level or indexed utterances")
+            if voc is VOC_NULL:
+                va = None
+            elif len(voc) != len(self._utts):
+                raise ValueError("voc= needs one entry per utterance")
+            else:
+                va = (F.UttVoc * max(1, len(voc)))()
+                for i, v in enumerate(voc):
+                    va[i] = v if isinstance(v, F.UttVoc) else F.UttVoc(*[float(x) for x in v])
+            if pdf_set is not None:
+                F.check(L.jb_batch_create_indexed_voc(C.byref(vd), pdf_set._h, arr, len(utts), va, C.byref(opts),
+                                                      C.byref(h)))
+            else:
+                F.check(L.jb_batch_create_voc(C.byref(vd), arr, len(utts), va, C.byref(opts), C.byref(h)))
+        elif from_tracks:
             F.check(L.jb_batch_create_from_tracks(C.byref(vd), arr, len(utts), C.byref(opts), C.byref(h)))
         elif pdf_set is not None:
             F.check(L.jb_batch_create_indexed(C.byref(vd), pdf_set._h, arr, len(utts), C.byref(opts), C.byref(h)))

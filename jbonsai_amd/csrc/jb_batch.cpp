@@ -801,13 +801,42 @@ static int check_voice(const jb_voice_desc *v, bool need_windows = true, bool vo
     return JB_OK;
 }
 
+// Vocoder condition of one utterance under voice v: alpha, volume and beta of `c` (null: those of v), with the beta
+// rule of the batch (postfilter_mcp acts only for beta > 0, more than two coefficients and stage 0, cepstrum.rs:24;
+// with stage > 0 beta goes to postfilter_lsp, lsp.rs:113-139)
+static VocUtt voc_utt(const jb_voice_desc *v, const jb_utt_voc *c)
+{
+    const double alpha = c ? c->alpha : v->alpha, beta = c ? c->beta : v->beta, volume = c ? c->volume : v->volume;
+    VocUtt u{};
+    u.alpha = alpha;
+    u.volume = volume;
+    u.beta = (beta > 0.0 && v->stream[0].vector_length > 2 && v->stage == 0) ? beta : 0.0;
+    u.beta_stage = v->stage ? beta : 0.0;
+    return u;
+}
+static bool same_voc(const VocUtt &a, const VocUtt &b)
+{
+    return a.alpha == b.alpha && a.volume == b.volume && a.beta == b.beta && a.beta_stage == b.beta_stage;
+}
+
 int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n, const jb_batch_opts *opts,
-                  Batch **out, const IndexSrc *idx, const TrackSrc *trk)
+                  Batch **out, const IndexSrc *idx, const TrackSrc *trk, const jb_utt_voc *voc)
 {
     *out = nullptr;
     int rc = check_voice(voice, trk == nullptr, trk && trk->vocoder_level);
     if (rc)
         return rc;
+    // per-utterance vocoder conditions: checked like the voice's own (check_voice), alpha and volume finite
+    for (size_t i = 0; voc && i < n; i++) {
+        if (!(voc[i].beta >= 0.0)) {
+            set_error("jb_utt_voc[" + std::to_string(i) + "]: beta must be >= 0");
+            return JB_ERR_INVALID;
+        }
+        if (!std::isfinite(voc[i].alpha) || !std::isfinite(voc[i].volume) || !std::isfinite(voc[i].beta)) {
+            set_error("jb_utt_voc[" + std::to_string(i) + "]: alpha, beta and volume must be finite");
+            return JB_ERR_INVALID;
+        }
+    }
     // JB_CREATE_TRACE=1: where the creation of a batch spends its time (stderr)
     const bool ctrace = getenv("JB_CREATE_TRACE") != nullptr;
     const auto tc0 = std::chrono::steady_clock::now();
@@ -1195,13 +1224,53 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
     }
     vd.bs = bs;
     vd.nblk = (vd.fperiod + bs - 1) / bs;
-    vd.alpha = voice->alpha;
-    vd.volume = voice->volume;
-    // postfilter_mcp acts only for beta > 0 and more than two coefficients (cepstrum.rs:24)
-    vd.beta = (voice->beta > 0.0 && vd.nmcp > 2 && voice->stage == 0) ? voice->beta : 0.0;
+    // The vocoder condition (voc_utt).  One for the whole batch -- no jb_utt_voc, or every entry the same -- stands
+    // in vd.alpha / volume / beta / beta_stage, and the kernels run as they always have.  Otherwise vd.uvoc holds each
+    // utterance's; vd.beta / beta_stage then say only whether SOME utterance has a post-filter (what is allocated and
+    // launched), and the lane kernel's launch permutation keeps the condition classes apart (build_work).
+    std::vector<double> pf_alphas; // the alpha of each post-filter operator (vd.pf_table)
+    {
+        const VocUtt v0 = voc_utt(voice, (voc && n) ? &voc[0] : nullptr);
+        bool mixed = false;
+        for (size_t i = 1; voc && i < n && !mixed; i++)
+            mixed = !same_voc(voc_utt(voice, &voc[i]), v0);
+        vd.alpha = v0.alpha;
+        vd.volume = v0.volume;
+        vd.beta = v0.beta;
+        vd.beta_stage = v0.beta_stage;
+        if (v0.beta > 0.0)
+            pf_alphas.push_back(v0.alpha);
+        if (mixed) {
+            b->uvoc.resize(n);
+            b->voc_class.resize(n);
+            std::vector<std::pair<double, double>> cls; // (alpha, volume) of each class
+            for (size_t i = 0; i < n; i++) {
+                VocUtt &u = b->uvoc[i];
+                u = voc_utt(voice, &voc[i]);
+                const auto key = std::make_pair(u.alpha, u.volume);
+                const size_t c = std::find(cls.begin(), cls.end(), key) - cls.begin();
+                if (c == cls.size())
+                    cls.push_back(key);
+                b->voc_class[i] = (uint32_t)c;
+                if (u.beta > 0.0) {
+                    const size_t k = std::find(pf_alphas.begin(), pf_alphas.end(), u.alpha) - pf_alphas.begin();
+                    if (k == pf_alphas.size())
+                        pf_alphas.push_back(u.alpha);
+                    u.pf = (uint32_t)k;
+                }
+                vd.beta = std::max(vd.beta, u.beta);
+                vd.beta_stage = std::max(vd.beta_stage, u.beta_stage);
+            }
+            b->n_classes = (uint32_t)cls.size();
+            VocUtt *dev_uvoc = nullptr;
+            if ((rc = b->stage(b->uvoc.data(), n, &dev_uvoc)))
+                return rc;
+            vd.uvoc = dev_uvoc;
+        }
+        vd.n_pf = (uint32_t)pf_alphas.size();
+    }
     vd.stage = (int)voice->stage;
     vd.use_log_gain = voice->use_log_gain ? 1 : 0;
-    vd.beta_stage = voice->stage ? voice->beta : 0.0; // postfilter_lsp (lsp.rs:113-139)
     vd.voiced = b->sd[1].voiced;
     vd.run_list = b->sd[1].run_list;
     vd.nruns = b->sd[1].nruns;
@@ -1223,7 +1292,8 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
         return rc;
     if (vd.beta > 0.0) {
         if ((rc = b->dalloc(&vd.bfirst, (size_t)std::max<size_t>(n, 1) * (size_t)vd.nmcp, true)) ||
-            (rc = b->dalloc(&vd.pf_table, (size_t)vd.nmcp * 576, false)) || (rc = b->dalloc(&vd.pf_rcp, 576, false)))
+            (rc = b->dalloc(&vd.pf_table, (size_t)vd.n_pf * vd.nmcp * 576, false)) ||
+            (rc = b->dalloc(&vd.pf_rcp, 576, false)))
             return rc;
     }
     if (b->flags & JB_BATCH_PCM_I16)
@@ -1281,7 +1351,7 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
         return rc;
     vd.noise = b->noise->ptr;
     vd.noise_len = b->noise->len;
-    if (vd.beta > 0.0 && (e = launch_pf_table(vd, b->stream)) != hipSuccess)
+    if (vd.beta > 0.0 && (e = launch_pf_table(vd, pf_alphas.data(), b->stream)) != hipSuccess)
         return hip_fail(e, "k_pf_table");
     cmark("vocoder buffers allocated");
     if ((rc = b->build_work(opts)))
@@ -1506,13 +1576,36 @@ int Batch::build_work(const jb_batch_opts *opts)
     if ((rc = stage(work.data(), n_items, &work_dev))) // (with the arena's next flush: create() ends with one)
         return rc;
     if (lp_mode) {
-        // launch permutation: equal-length chunks share a wave (lanes run in lock step)
+        // launch permutation: equal-length chunks share a wave (lanes run in lock step).  With several condition
+        // classes (per-utterance alpha / volume) the chunks go by class first, and each class is padded to whole
+        // waves with slots that hold no chunk: a wave's chunks then share the alpha and volume it keeps in scalar
+        // registers.  One class: the plain permutation.
         std::vector<uint32_t> ord(n_items);
         std::iota(ord.begin(), ord.end(), 0u);
-        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
-            return (work[x].t_end - work[x].t_start) > (work[y].t_end - work[y].t_start);
-        });
-        if ((rc = stage(ord.data(), n_items, &order_dev)))
+        if (uvoc.empty()) {
+            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
+                return (work[x].t_end - work[x].t_start) > (work[y].t_end - work[y].t_start);
+            });
+        } else {
+            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
+                const uint32_t cx = voc_class[work[x].utt], cy = voc_class[work[y].utt];
+                if (cx != cy)
+                    return cx < cy;
+                return (work[x].t_end - work[x].t_start) > (work[y].t_end - work[y].t_start);
+            });
+            const uint32_t per_wave = (uint32_t)vocoder_ls_chunks_per_wave(vd.nmcp);
+            std::vector<uint32_t> padded;
+            padded.reserve(n_items + (size_t)n_classes * per_wave);
+            for (uint32_t k = 0; k < n_items; k++) {
+                padded.push_back(ord[k]);
+                const bool class_ends = k + 1 == n_items || voc_class[work[ord[k + 1]].utt] != voc_class[work[ord[k]].utt];
+                while (class_ends && padded.size() % per_wave)
+                    padded.push_back(0xffffffffu); // (kLtNoItem of the kernel)
+            }
+            ord.swap(padded);
+        }
+        n_slots = (uint32_t)ord.size();
+        if ((rc = stage(ord.data(), ord.size(), &order_dev)))
             return rc;
     }
     return JB_OK;
@@ -1544,7 +1637,7 @@ int Batch::enqueue_vocoder()
 {
     hipError_t e;
     if (lp_mode)
-        e = launch_vocoder_ls(bd, vd, work_dev, order_dev, n_items, lt_waves_per_simd, stream_voc);
+        e = launch_vocoder_ls(bd, vd, work_dev, order_dev, n_slots, lt_waves_per_simd, stream_voc);
     else
         e = launch_vocoder(bd, vd, work_dev, n_items, stream_voc);
     if (e != hipSuccess)
@@ -2333,10 +2426,16 @@ int jb_device_pci_bus_id(int dev, char *buf, size_t cap)
 int jb_batch_create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n_utts,
                     const jb_batch_opts *opts, jb_batch **out)
 {
+    return jb_batch_create_voc(voice, utts, n_utts, nullptr, opts, out);
+}
+
+int jb_batch_create_voc(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n_utts, const jb_utt_voc *voc,
+                        const jb_batch_opts *opts, jb_batch **out)
+{
     if (!out)
         return JB_ERR_INVALID;
     Batch *b = nullptr;
-    int rc = Batch::create(voice, utts, n_utts, opts, &b);
+    int rc = Batch::create(voice, utts, n_utts, opts, &b, nullptr, nullptr, voc);
     *out = (jb_batch *)b;
     return rc;
 }
@@ -2399,8 +2498,8 @@ int jb_pdf_set_create(const jb_pdf_table *tables, uint32_t n_voices, uint32_t ns
 
 void jb_pdf_set_free(jb_pdf_set *s) { delete (PdfSet *)s; }
 
-int jb_batch_create_indexed(const jb_voice_desc *voice, const jb_pdf_set *set, const jb_index_utt *utts,
-                            size_t n_utts, const jb_batch_opts *opts, jb_batch **out)
+int jb_batch_create_indexed_voc(const jb_voice_desc *voice, const jb_pdf_set *set, const jb_index_utt *utts,
+                                size_t n_utts, const jb_utt_voc *voc, const jb_batch_opts *opts, jb_batch **out)
 {
     if (!out)
         return JB_ERR_INVALID;
@@ -2424,9 +2523,15 @@ int jb_batch_create_indexed(const jb_voice_desc *voice, const jb_pdf_set *set, c
     }
     IndexSrc idx{(const PdfSet *)set, utts};
     Batch *b = nullptr;
-    int rc = Batch::create(voice, su.data(), n_utts, opts, &b, &idx);
+    int rc = Batch::create(voice, su.data(), n_utts, opts, &b, &idx, nullptr, voc);
     *out = (jb_batch *)b;
     return rc;
+}
+
+int jb_batch_create_indexed(const jb_voice_desc *voice, const jb_pdf_set *set, const jb_index_utt *utts,
+                            size_t n_utts, const jb_batch_opts *opts, jb_batch **out)
+{
+    return jb_batch_create_indexed_voc(voice, set, utts, n_utts, nullptr, opts, out);
 }
 
 int jb_batch_run(jb_batch *b) { return b ? ((Batch *)b)->run(true) : JB_ERR_INVALID; }

@@ -153,9 +153,20 @@ static_assert(sizeof(GvGang) == 128 + sizeof(unsigned long long) * 2 * kGvGangMa
                                     (JB_GG_PROFILE ? sizeof(unsigned long long) * 2 * 8 * 96 : 0),
               "GvGang layout (host offsets in jb_batch.cpp and the kernel must agree)");
 
+// Vocoder condition of one utterance (jb_utt_voc after the beta rule of Batch::create): what VocDev::alpha / volume /
+// beta / beta_stage hold for a batch with one condition.  pf: which freqt operator of VocDev::pf_table (beta > 0).
+struct VocUtt {
+    double alpha, volume, beta, beta_stage;
+    uint32_t pf, pad;
+};
+
 struct VocDev {
     int fs, fperiod, nmcp, nlpf, bs, nblk; // bs = samples per block (divides fperiod, <=64)
     double alpha, volume;
+    // per-utterance conditions [B], or nullptr: every utterance runs under alpha / volume / beta / beta_stage here.
+    // Only a batch whose utterances differ has the table; the kernels then read the utterance's own values (wave-
+    // uniform: a wave works on one chunk, one frame, or -- k_vocoder_lt -- chunks of one condition class).
+    const VocUtt *uvoc;
     const double *mcp;    // [sumT][nmcp] (MLPG out of stream 0)
     const double *lf0;    // [sumT]
     const double *lpf;    // [sumT][nlpf]
@@ -166,7 +177,9 @@ struct VocDev {
     int stage, use_log_gain;
     double beta_stage;
     double *bfirst;       // [B][nmcp] un-filtered bcoef of each utterance's first frame, or nullptr (beta == 0)
-    double *pf_table;     // [nmcp][576] freqt(575, -alpha) as a linear operator (k_pf_table), or nullptr
+    double *pf_table;     // [n_pf][nmcp][576] freqt(575, -alpha) as a linear operator (k_pf_table), one per distinct
+                          // alpha among the utterances with beta > 0 (n_pf = 1 without uvoc), or nullptr
+    uint32_t n_pf;
     double *pf_rcp;       // [576] 1/n
     double *pitch;        // [sumT]  period in samples, 0 = unvoiced
     double *cur_start;    // [sumT]  pitch_of_curr_point at frame start
@@ -214,6 +227,29 @@ struct VocDev {
     uint32_t ckpt_frames; // checkpoint position inside a chunk (frames past t_out); 0 = no checkpoints
     uint32_t ckpt2_frames; // second checkpoint (long chunks only), 0 = none
 };
+
+// The vocoder condition of utterance b
+__device__ __forceinline__ double voc_alpha(const VocDev &vd, uint32_t b)
+{
+    return vd.uvoc ? vd.uvoc[b].alpha : vd.alpha;
+}
+__device__ __forceinline__ double voc_volume(const VocDev &vd, uint32_t b)
+{
+    return vd.uvoc ? vd.uvoc[b].volume : vd.volume;
+}
+__device__ __forceinline__ double voc_beta_stage(const VocDev &vd, uint32_t b)
+{
+    return vd.uvoc ? vd.uvoc[b].beta_stage : vd.beta_stage;
+}
+// a value every lane of the wave holds, made provably wave-uniform (SGPRs): the vocoder kernels keep alpha and volume
+// there, and the lane kernel hands them to its asm as "s" operands
+__device__ __forceinline__ double wave_uniform(double v)
+{
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+    const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // The row of LPF taps of frame f (index in the concatenated arrays), NL taps per row
 __device__ __forceinline__ const double *lpf_row(const VocDev &vd, uint64_t f, int NL)
@@ -355,7 +391,8 @@ bool excite_is_split(const VocDev &vd);
 hipError_t launch_excite_noise(const BatchDev &bd, const VocDev &vd, hipStream_t stream);
 hipError_t launch_excite(const BatchDev &bd, const VocDev &vd, hipStream_t stream);
 // X1 post-filter (cepstrum.rs:23-37): constant tables once, then bcoef in place for every frame
-hipError_t launch_pf_table(const VocDev &vd, hipStream_t stream);
+// (alphas[k]: the alpha of operator k of vd.pf_table, k < vd.n_pf)
+hipError_t launch_pf_table(const VocDev &vd, const double *alphas, hipStream_t stream);
 hipError_t launch_postfilter(const BatchDev &bd, const VocDev &vd, uint64_t nframes, hipStream_t stream);
 hipError_t launch_vocoder(const BatchDev &bd, const VocDev &vd, const VocWork *work_dev, uint32_t n_items,
                           hipStream_t stream);

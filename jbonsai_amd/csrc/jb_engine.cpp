@@ -403,9 +403,12 @@ static unsigned host_threads_default()
     return nt;
 }
 
+// indexed: row indices into the concatenated pdf tables of `tables` (default e; what Engine::pdf_set_for built them
+// for -- engines that share one voice set share the layout)
 static int build_states(const Engine &e, const char *const *lines, size_t n, States &st, bool indexed = false,
-                        unsigned label_threads = 1)
+                        unsigned label_threads = 1, const Engine *tables = nullptr)
 {
+    const std::vector<Engine::CatTable> &cat = (tables ? tables : &e)->cat;
     const Condition &c = e.cond;
     const Voice &v0 = *e.voices[0];
     // JB_FRONT_TRACE=1: phases of the front half of one utterance on stderr (like JB_CREATE_TRACE / JB_REDO_TRACE)
@@ -469,7 +472,7 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
                                 m.get_index((int)(2 + s), pl.labels[i], tp, pi, &memo);
                                 if (tp < 0 || pi < 1 || pi > m.npdf[(size_t)tp])
                                     throw ModelError("index not found"); // reference: todo!() (voice/model.rs:76-79)
-                                st.rows[si][v][row] = e.cat[v * nsx + si].tree_off[(size_t)tp] + (uint32_t)(pi - 1);
+                                st.rows[si][v][row] = cat[v * nsx + si].tree_off[(size_t)tp] + (uint32_t)(pi - 1);
                             }
                         } else {
                             blend(e, c.w_param[si], plen, buf.data(), [&](const Voice &v) {
@@ -949,8 +952,10 @@ int jb_write_wav_f64(const char *path, const double *pcm, size_t n, uint32_t fs)
 
 // elem = 8: f64 PCM (Engine::synthesize's Vec<f64>); elem = 2: the fused 16-bit sink
 int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                              int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads)
+                              int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads,
+                              const jb_engine *const *each)
 {
+    auto eng = [&](size_t u) { return CENG(each ? each[u] : e); }; // the engine of utterance u
     if (!e || !pcm || !n_samples || (n_utts && !line_off))
         return JB_ERR_INVALID;
     for (size_t u = 0; u < n_utts; u++) {
@@ -1026,8 +1031,8 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         const unsigned per_utt = (unsigned)std::max<size_t>(1, nt / std::max<size_t>(1, hi - lo));
         auto work = [&]() {
             for (size_t u; (u = next.fetch_add(1)) < hi;) {
-                rcs[u - lo] = build_states(*CENG(e), lines + line_off[u], line_off[u + 1] - line_off[u], *sts[u], indexed,
-                                           per_utt);
+                rcs[u - lo] = build_states(*eng(u), lines + line_off[u], line_off[u + 1] - line_off[u], *sts[u], indexed,
+                                           per_utt, CENG(e));
                 if (rcs[u - lo])
                     errs[u - lo] = jb::g_err; // the worker's thread-local message
             }
@@ -1058,16 +1063,22 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         opts.flags = (elem == 2 ? JB_BATCH_PCM_I16 : 0) | (CENG(e)->cond.batch_invariant ? (JB_BATCH_SERIAL | JB_BATCH_SERIAL_GV) : 0);
         jb::Batch *b = nullptr;
         int rc;
+        // one engine per utterance: the vocoder conditions of the utterances (a batch whose entries are all the
+        // same runs as one made without them)
+        std::vector<jb_utt_voc> voc(each ? hi - lo : 0);
+        for (size_t u = lo; each && u < hi; u++)
+            voc[u - lo] = jb_utt_voc{eng(u)->cond.alpha, eng(u)->cond.beta, eng(u)->cond.volume};
+        const jb_utt_voc *vp = each ? voc.data() : nullptr;
         if (indexed) {
             std::vector<jb_index_utt> iu(hi - lo);
             for (size_t u = lo; u < hi; u++)
                 iu[u - lo] = sts[u]->iutt;
-            rc = jb_batch_create_indexed(&CENG(e)->desc, pset, iu.data(), hi - lo, &opts, (jb_batch **)&b);
+            rc = jb_batch_create_indexed_voc(&CENG(e)->desc, pset, iu.data(), hi - lo, vp, &opts, (jb_batch **)&b);
         } else {
             std::vector<jb_state_utt> su(hi - lo);
             for (size_t u = lo; u < hi; u++)
                 su[u - lo] = sts[u]->utt;
-            rc = jb::Batch::create(&CENG(e)->desc, su.data(), hi - lo, &opts, &b);
+            rc = jb::Batch::create(&CENG(e)->desc, su.data(), hi - lo, &opts, &b, nullptr, nullptr, vp);
         }
         if (rc)
             return rc;
@@ -1208,6 +1219,73 @@ int jb_synthesize_batch_i16(const jb_engine *e, const char *const *lines, const 
 }
 
 void jb_pcm_i16_free(int16_t *p) { free(p); }
+
+} // extern "C"
+
+// The engines of jb_synthesize_batch_each: one voice set (the same Voice objects: jb_engine_new / Engine::clone) and
+// the Condition fields one batch cannot vary.  Host-side only, before any device is touched.
+static int check_engines(const jb_engine *const *engines, size_t n)
+{
+    if (!engines) {
+        jb::set_error("jb_synthesize_batch_each: engines is NULL");
+        return JB_ERR_INVALID;
+    }
+    for (size_t u = 0; u < n; u++)
+        if (!engines[u]) {
+            jb::set_error("jb_synthesize_batch_each: engines[" + std::to_string(u) + "] is NULL");
+            return JB_ERR_INVALID;
+        }
+    const jb::Engine &e0 = *CENG(engines[0]);
+    for (size_t u = 1; u < n; u++) {
+        const jb::Engine &e = *CENG(engines[u]);
+        const char *field = nullptr;
+        if (e.voices != e0.voices)
+            field = "voice set (engines must be made from one another with jb_engine_new)";
+        else if (e.cond.sampling_frequency != e0.cond.sampling_frequency)
+            field = "sampling_frequency";
+        else if (e.cond.fperiod != e0.cond.fperiod)
+            field = "fperiod";
+        else if (e.cond.stage != e0.cond.stage)
+            field = "stage";
+        else if (e.cond.use_log_gain != e0.cond.use_log_gain)
+            field = "use_log_gain";
+        else if (e.cond.batch_invariant != e0.cond.batch_invariant)
+            field = "batch_invariant";
+        if (field) {
+            jb::set_error("jb_synthesize_batch_each: engines[" + std::to_string(u) + "] differs from engines[0] in " +
+                          field);
+            return JB_ERR_INVALID;
+        }
+    }
+    return JB_OK;
+}
+
+static int synthesize_each(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                           size_t n_utts, int32_t device, size_t elem, void **pcm, size_t *n_samples)
+{
+    if (!pcm || !n_samples || (n_utts && !line_off))
+        return JB_ERR_INVALID;
+    if (n_utts == 0)
+        return JB_OK;
+    const int rc = check_engines(engines, n_utts);
+    if (rc)
+        return rc;
+    return jb::synthesize_batch_impl(engines[0], lines, line_off, n_utts, device, elem, pcm, n_samples, 0, engines);
+}
+
+extern "C" {
+
+int jb_synthesize_batch_each(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                             size_t n_utts, int32_t device, double **pcm, size_t *n_samples)
+{
+    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(double), (void **)pcm, n_samples);
+}
+
+int jb_synthesize_batch_each_i16(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                                 size_t n_utts, int32_t device, int16_t **pcm, size_t *n_samples)
+{
+    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)pcm, n_samples);
+}
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)
 {

@@ -25,9 +25,12 @@ struct NoiseDev {
 int noise_table(int device, size_t need, std::shared_ptr<NoiseDev> *out);
 void release_cached_memory(); // empties the per-device pools of finished batches' memory
 void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE_POOL_MB at start)
-// jb_synthesize_batch[_i16] on one device (jb_engine.cpp); host_threads = 0: default front-half thread count
+// jb_synthesize_batch[_i16] on one device (jb_engine.cpp); host_threads = 0: default front-half thread count;
+// each != null (jb_synthesize_batch_each[_i16], engines checked by the caller): utterance u under each[u]'s Condition,
+// e = each[0] for what the engines share
 int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                          int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0);
+                          int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0,
+                          const jb_engine *const *each = nullptr);
 // static LPT partition (jb_multi.cpp): part_of[i] = bin of item i
 void lpt_partition(const uint64_t *weights, size_t n, size_t n_parts, uint32_t *part_of);
 
@@ -92,6 +95,13 @@ struct Batch {
     bool lp_mode = false;            // lane-triple throughput kernel
     int lt_waves_per_simd = 2;       // its waves per SIMD: 2 (eight-wave workgroups) or 1 (build_work)
     uint32_t *order_dev = nullptr;   // its launch permutation
+    uint32_t n_slots = 0;            // ... and its length: n_items, plus the padding of condition classes (build_work)
+    // per-utterance vocoder conditions (jb_batch_create_voc): the host copy of vd.uvoc -- empty when every utterance
+    // has the same, which then stands in vd.alpha / volume / beta / beta_stage -- and each utterance's condition
+    // class: utterances with equal (alpha, volume), numbered in order of first appearance
+    std::vector<VocUtt> uvoc;
+    std::vector<uint32_t> voc_class;
+    uint32_t n_classes = 1;
     VocWork *redo_dev = nullptr;
     VocWork *gen_work_dev = nullptr; // one item per frame of utterance 0 (streaming generator)
     std::vector<std::pair<void *, size_t>> allocs; // device blocks (pointer, pooled size)
@@ -148,7 +158,7 @@ struct Batch {
     uint32_t gang_fallbacks = 0;     // times the resident GV kernel timed out in formation and the sweeps took over
     static int create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n,
                       const jb_batch_opts *opts, Batch **out, const IndexSrc *idx = nullptr,
-                      const TrackSrc *trk = nullptr);
+                      const TrackSrc *trk = nullptr, const jb_utt_voc *voc = nullptr);
     int enqueue_mlpg_only();
     int enqueue_from_tracks();
     int gather_states(const jb_voice_desc *voice, const IndexSrc &idx, size_t n,

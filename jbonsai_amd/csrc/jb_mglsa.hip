@@ -217,12 +217,13 @@ __global__ __launch_bounds__(64) void k_stage_coef(BatchDev bd, VocDev vd)
     const uint64_t f = u->frame_off + t;
     SgScratch w;
     double cc[kSgMaxN];
-    sg_frame_coef(vd.mcp + f * (uint64_t)n, n, vd.alpha, vd.beta_stage, vd.use_log_gain, vd.stage, true, cc, w);
+    const double alpha = voc_alpha(vd, (uint32_t)b), beta = voc_beta_stage(vd, (uint32_t)b);
+    sg_frame_coef(vd.mcp + f * (uint64_t)n, n, alpha, beta, vd.use_log_gain, vd.stage, true, cc, w);
     for (int i = 0; i < n; i++)
         vd.bcoef[f * (uint64_t)n + i] = cc[i];
     if (t == 0) {
         // the first frame starts from the coefficients of the un-filtered spectrum (mod.rs:92-106)
-        sg_frame_coef(vd.mcp + f * (uint64_t)n, n, vd.alpha, vd.beta_stage, vd.use_log_gain, vd.stage, false, cc, w);
+        sg_frame_coef(vd.mcp + f * (uint64_t)n, n, alpha, beta, vd.use_log_gain, vd.stage, false, cc, w);
         for (int i = 0; i < n; i++)
             vd.bfirst[(uint64_t)b * (uint64_t)n + i] = cc[i];
     }
@@ -280,7 +281,8 @@ __global__ __launch_bounds__(256) void k_vocoder_mglsa(BatchDev bd, VocDev vd, c
     const int lane = threadIdx.x & 63;
     const uint64_t base = bd.utt[b].frame_off;
     const int n = vd.nmcp, fp = vd.fperiod, bs = vd.bs, nblk = vd.nblk;
-    const double a = vd.alpha, na = -a, aa = 1.0 - a * a, vol = vd.volume;
+    const double a = wave_uniform(voc_alpha(vd, (uint32_t)b)), na = -a, aa = 1.0 - a * a,
+                 vol = wave_uniform(voc_volume(vd, (uint32_t)b));
     // scan weights: lane i folds lane i - s with (-a)^s where that lane exists (recurrence over taps 0..n-2)
     auto pw = [&](int s) {
         double r = 1.0;

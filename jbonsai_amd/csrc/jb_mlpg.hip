@@ -2432,11 +2432,12 @@ __global__ __launch_bounds__(256) void k_mc2b_mt(BatchDev bd, StreamDev sd, VocD
         for (int e = threadIdx.x; e < (int)nt * L; e += blockDim.x)
             sd.out[o0 + (uint64_t)e] = tile[(e % L) * 65 + e / L];
     __syncthreads();
-    if (threadIdx.x < nt && vd.alpha != 0.0) {
+    const double alpha = voc_alpha(vd, (uint32_t)b);
+    if (threadIdx.x < nt && alpha != 0.0) {
         const int tl = threadIdx.x;
         double prev = tile[(L - 1) * 65 + tl];
         for (int i = L - 2; i >= 0; i--) {
-            prev = tile[i * 65 + tl] - vd.alpha * prev;
+            prev = tile[i * 65 + tl] - alpha * prev;
             tile[i * 65 + tl] = prev;
         }
     }

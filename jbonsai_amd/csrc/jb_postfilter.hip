@@ -124,7 +124,7 @@ __device__ __forceinline__ double pf_wave_sum(double v)
     return v;
 }
 
-__global__ __launch_bounds__(64 * kPfWaves) void k_postfilter(VocDev vd, uint64_t nframes)
+__global__ __launch_bounds__(64 * kPfWaves) void k_postfilter(BatchDev bd, VocDev vd, uint64_t nframes)
 {
     extern __shared__ double pf_lds[]; // per wave: pad|kg0[576] | pad|kg1[576] | fin0[64] | fin1[64]
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -134,11 +134,29 @@ __global__ __launch_bounds__(64 * kPfWaves) void k_postfilter(VocDev vd, uint64_
     kg0[lane - kPfPad] = 0.0;
     kg1[lane - kPfPad] = 0.0;
     const int nm = vd.nmcp;
-    const double alpha = vd.alpha, beta = vd.beta;
+    double alpha = vd.alpha, beta = vd.beta;
     const double *__restrict__ table = vd.pf_table;
     const double *__restrict__ rcp = vd.pf_rcp;
     const uint64_t stride = (uint64_t)gridDim.x * kPfWaves;
     for (uint64_t f = (uint64_t)blockIdx.x * kPfWaves + (uint64_t)w; f < nframes; f += stride) {
+        if (vd.uvoc) {
+            // the frame's utterance (the last one whose frames start at or before f) and its condition: frames of
+            // utterances with beta = 0 stay un-filtered
+            uint32_t lo = 0, hi = (uint32_t)bd.B;
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) / 2;
+                if (bd.utt[mid].frame_off <= f)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            const uint32_t ub = wave_uniform(lo);
+            beta = wave_uniform(vd.uvoc[ub].beta);
+            if (beta == 0.0)
+                continue;
+            alpha = wave_uniform(vd.uvoc[ub].alpha);
+            table = vd.pf_table + (size_t)wave_uniform(vd.uvoc[ub].pf) * (size_t)nm * kIrLen;
+        }
         double *bp = vd.bcoef + f * (uint64_t)nm;
         // ---- b (= mc2b(c), k_mc2b*) and the emphasised b' (cepstrum.rs:28-31) ----
         const double b0 = lane < nm ? bp[lane] : 0.0;
@@ -258,11 +276,17 @@ __global__ __launch_bounds__(64 * kPfWaves) void k_postfilter(VocDev vd, uint64_
     }
 }
 
-hipError_t launch_pf_table(const VocDev &vd, hipStream_t stream)
+hipError_t launch_pf_table(const VocDev &vd, const double *alphas, hipStream_t stream)
 {
-    // postfilter_mcp's transform uses -alpha (coefficients.rs:76)
-    hipLaunchKernelGGL(k_pf_table, dim3(1), dim3(64), 0, stream, vd.pf_table, vd.pf_rcp, vd.nmcp, -vd.alpha);
-    return hipGetLastError();
+    // postfilter_mcp's transform uses -alpha (coefficients.rs:76); one operator per distinct alpha (VocDev::n_pf)
+    for (uint32_t k = 0; k < vd.n_pf; k++) {
+        hipLaunchKernelGGL(k_pf_table, dim3(1), dim3(64), 0, stream, vd.pf_table + (size_t)k * vd.nmcp * kIrLen,
+                           vd.pf_rcp, vd.nmcp, -alphas[k]);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_postfilter(const BatchDev &bd, const VocDev &vd, uint64_t nframes, hipStream_t stream)
@@ -291,7 +315,7 @@ hipError_t launch_postfilter(const BatchDev &bd, const VocDev &vd, uint64_t nfra
     uint64_t blocks = (nframes + kPfWaves - 1) / kPfWaves;
     if (blocks > (uint64_t)ncu * (uint64_t)per_cu)
         blocks = (uint64_t)ncu * (uint64_t)per_cu;
-    hipLaunchKernelGGL(k_postfilter, dim3((unsigned)blocks), dim3(64 * kPfWaves), lds, stream, vd, nframes);
+    hipLaunchKernelGGL(k_postfilter, dim3((unsigned)blocks), dim3(64 * kPfWaves), lds, stream, bd, vd, nframes);
     return hipGetLastError();
 }
 

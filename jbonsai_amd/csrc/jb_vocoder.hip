@@ -82,10 +82,11 @@ __global__ __launch_bounds__(kMc2bFrames) void k_mc2b(BatchDev bd, VocDev vd)
     for (uint32_t e = tid; e < tot; e += kMc2bFrames)
         tile[e % n][e / n] = vd.mcp[off + e];
     __syncthreads();
-    if ((uint32_t)tid < nf && vd.alpha != 0.0) {
+    const double alpha = voc_alpha(vd, (uint32_t)b);
+    if ((uint32_t)tid < nf && alpha != 0.0) {
         double prev = tile[n - 1][tid];
         for (int i = n - 2; i >= 0; i--) {
-            prev = tile[i][tid] - vd.alpha * prev;
+            prev = tile[i][tid] - alpha * prev;
             tile[i][tid] = prev;
         }
     }
@@ -1257,7 +1258,8 @@ __global__ __launch_bounds__(256) void k_vocoder(BatchDev bd, VocDev vd, const V
     const uint64_t base = bd.utt[b].frame_off;
     const int nmcp = vd.nmcp, fp = vd.fperiod, bs = vd.bs, nblk = vd.nblk;
     const int M = nmcp - 1; // live taps 1..M
-    const double a = vd.alpha, iaa = 1.0 - a * a, vol = vd.volume;
+    const double a = wave_uniform(voc_alpha(vd, (uint32_t)b)), iaa = 1.0 - a * a,
+                 vol = wave_uniform(voc_volume(vd, (uint32_t)b));
 
     // ---- lane roles ----
     const int s = lane / kGroups, g = lane % kGroups;
@@ -1491,7 +1493,8 @@ __global__ __launch_bounds__(128 * ITEMS) void k_vocoder_pair(BatchDev bd, VocDe
     for (int j = 0; j < ITEMS; j++)
         NBmax = max(NBmax, nblocks_sh[j]);
     const uint64_t base = NB ? bd.utt[b].frame_off : 0;
-    const double a = vd.alpha, iaa = 1.0 - a * a, vol = vd.volume;
+    const double a = wave_uniform(voc_alpha(vd, (uint32_t)b)), iaa = 1.0 - a * a,
+                 vol = wave_uniform(voc_volume(vd, (uint32_t)b));
     double *const xb = &xbuf[slot][0][0];
     double *const ob = &obuf[slot][0][0];
 
@@ -1751,6 +1754,7 @@ __device__ __forceinline__ double fold5(double s)
     return t2 + dpp_f64<DPP_ROW_SHL4>(s);
 }
 __host__ __device__ constexpr int lt_chunks(int lpc) { return lpc == 3 ? 21 : 12; } // chunks per wave
+constexpr uint32_t kLtNoItem = 0xffffffffu; // a slot of the launch permutation without a chunk (class padding)
 constexpr int kLtPf = 4; // coefficient reads in flight ahead of their use (2, 3 or 4 measure the same)
 // Waves per workgroup.  EIGHT = a whole CU (two waves of 256 VGPRs per SIMD): waves w and w + 4 of a workgroup land on
 // the same SIMD, so the two waves that share a SIMD can see each other's progress in LDS.  The issue arbiter serves
@@ -1804,9 +1808,12 @@ __global__ __launch_bounds__(64 * kLtWaves, 2) void k_vocoder_lt(BatchDev bd, Vo
     const int pos = LPC == 3 ? (idle ? 2 : lane % 3) : (idle ? 4 : (lane & 15) % 5);
     const int ci = LPC == 3 ? (idle ? 20 : lane / 3) : (lane >> 4) * 3 + (idle ? 2 : (lane & 15) / 5); // chunk slot
     const uint32_t slot = (blockIdx.x * (uint32_t)kLtWaves + (uint32_t)wv) * (uint32_t)kLtChunks + (uint32_t)ci;
-    const bool has = !idle && slot < n_items;
+    // (n_items counts the slots of the permutation: with several condition classes each class is padded to whole
+    // waves by kLtNoItem entries, slots without a chunk)
+    const uint32_t oslot = (!idle && slot < n_items) ? order[slot] : kLtNoItem;
+    const bool has = oslot != kLtNoItem;
     const bool lead = has && pos == 0;
-    const uint32_t item = has ? order[slot] : 0u;
+    const uint32_t item = has ? oslot : 0u;
     struct {
         uint32_t utt, t_start, t_out, t_end;
         const double *load_state;
@@ -1852,7 +1859,15 @@ __global__ __launch_bounds__(64 * kLtWaves, 2) void k_vocoder_lt(BatchDev bd, Vo
 #endif
     const uint64_t base = has ? bd.utt[wk.utt].frame_off : 0;
     const int fp = vd.fperiod;
-    const double a = vd.alpha, na = -a, iaa = 1.0 - a * a, vol = vd.volume;
+    // alpha and volume stay wave-uniform scalars: the chunks of a wave share a condition class (Batch::build_work),
+    // whose values are those of the wave's first chunk (slot 0 of a wave that works is never padding)
+    double a = vd.alpha, vol = vd.volume;
+    if (vd.uvoc) {
+        const uint32_t u0 = wave_uniform(wk.utt);
+        a = wave_uniform(vd.uvoc[u0].alpha);
+        vol = wave_uniform(vd.uvoc[u0].volume);
+    }
+    const double na = -a, iaa = 1.0 - a * a;
     const int s0 = NS * pos; // first stage of this lane
     // Pade weights of the two slots: stage s -> PPADE[s+1]; slot 0 (odd i) enters the
     // alternating sum with +, slot 1 (even i) with -; the inert slot has weight 0

@@ -64,6 +64,10 @@ def _bind(L):
                                             C.POINTER(sz)]
     L.jb_synthesize_batch_i16_multi.argtypes = [vp, cpp, C.POINTER(sz), sz, C.POINTER(C.c_int32), sz,
                                                 C.POINTER(C.POINTER(C.c_int16)), C.POINTER(sz)]
+    L.jb_synthesize_batch_each.argtypes = [C.POINTER(vp), cpp, C.POINTER(sz), sz, C.c_int32, C.POINTER(dp),
+                                           C.POINTER(sz)]
+    L.jb_synthesize_batch_each_i16.argtypes = [C.POINTER(vp), cpp, C.POINTER(sz), sz, C.c_int32,
+                                               C.POINTER(C.POINTER(C.c_int16)), C.POINTER(sz)]
     L.jb_pcm_i16_free.argtypes = [C.POINTER(C.c_int16)]
     L.jb_pcm_i16_free.restype = None
     L.jb_engine_states.argtypes = [vp, cpp, sz, C.POINTER(vp)]
@@ -309,21 +313,49 @@ class Engine:
         else:
             fn = self._L.jb_synthesize_batch_i16 if i16 else self._L.jb_synthesize_batch
             F.check(fn(self._h, _lines(flat), offs, B, device, pcm, ns))
-        out = []
-        for i in range(B):
-            if not ns[i]:
-                out.append(np.zeros(0, dtype=np.int16 if i16 else np.float64))
-                continue
-            buf = (ety * ns[i]).from_address(C.addressof(pcm[i].contents))
-            arr = np.frombuffer(buf, dtype=np.int16 if i16 else np.float64)
-            weakref.finalize(buf, free, C.cast(C.addressof(pcm[i].contents), C.POINTER(ety)))
-            out.append(arr)
-        return out
+        return _pcm_arrays(pcm, ns, B, i16, free)
 
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
         F.check(self._L.jb_generator_new(self._h, _lines(labels), len(labels), C.byref(h)))
         return SpeechGenerator(h, self._L)
+
+
+def _pcm_arrays(pcm, ns, B, i16, free):
+    """numpy views of library-owned PCM buffers, each released with `free` when its array dies."""
+    ety = C.c_int16 if i16 else C.c_double
+    out = []
+    for i in range(B):
+        if not ns[i]:
+            out.append(np.zeros(0, dtype=np.int16 if i16 else np.float64))
+            continue
+        buf = (ety * ns[i]).from_address(C.addressof(pcm[i].contents))
+        arr = np.frombuffer(buf, dtype=np.int16 if i16 else np.float64)
+        weakref.finalize(buf, free, C.cast(C.addressof(pcm[i].contents), C.POINTER(ety)))
+        out.append(arr)
+    return out
+
+
+def synthesize_batch_each(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]], i16: bool = False,
+                          device: int = -1) -> List[np.ndarray]:
+    """jb_synthesize_batch_each[_i16]: utterance u under engines[u]'s Condition, all in one batch.  The engines
+    share one voice set (Engine.new / clone of one another) and agree on sampling frequency, fperiod, stage,
+    log gain and the batch-invariant flag."""
+    if len(engines) != len(utterances):
+        raise ValueError("one engine per utterance")
+    B = len(utterances)
+    L = engines[0]._L if B and engines[0] is not None else F.lib()
+    _bind(L)
+    flat = [l for u in utterances for l in u]
+    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
+    ety = C.c_int16 if i16 else C.c_double
+    pcm = (C.POINTER(ety) * max(1, B))()
+    ns = (C.c_size_t * max(1, B))()
+    fn = L.jb_synthesize_batch_each_i16 if i16 else L.jb_synthesize_batch_each
+    F.check(fn(hs, _lines(flat), offs, B, device, pcm, ns))
+    return _pcm_arrays(pcm, ns, B, i16, L.jb_pcm_i16_free if i16 else L.jb_pcm_free)
 
 
 class SpeechGenerator:
