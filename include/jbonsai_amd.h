@@ -130,6 +130,26 @@ typedef struct jb_batch_opts {
                                     read from the table all utterances share where their taps are the batch's
                                     canonical ones; same bits either way */
 
+#define JB_BATCH_INVARIANT 1024u /* fast batch-invariant mode: every choice the default mode makes from the whole batch
+                                    is made from the utterance and the voice alone, with the throughput kernels.
+                                    The output bits are a function of the voice, the utterance's inputs (states or
+                                    tracks, its jb_utt_voc), verify_tol, the library build and the GPU architecture;
+                                    they do not depend on the other utterances of the batch, the utterance's position
+                                    in it, the device list of a _multi entry, the entry point, the number of batches
+                                    in flight, or whether the resident GV kernel formed.  They differ from the default
+                                    mode's and from JB_BATCH_SERIAL's (both stay within the hand-off tolerance of the
+                                    serial recursion).  Combined with chunk_frames, warmup_frames,
+                                    JB_BATCH_WAVE_KERNEL or JB_BATCH_LANE_KERNEL: JB_ERR_INVALID before any device is
+                                    touched.  With JB_BATCH_SERIAL (already invariant) the serial mode runs and this
+                                    flag has no effect.  How: per utterance of T frames, chunks of
+                                    clamp(ceil(T / 96), 16, 153) frames behind 18 frames of warm-up, checkpoints at
+                                    48 / 96 frames into chunks long enough for them, the lane-triple kernel wherever
+                                    the voice supports it (else one fixed wave-kernel form), redo rounds on one fixed
+                                    wave-kernel form, the GV by the resident kernel or, wherever it does not run (rows
+                                    of more than 64 of its tiles, too few CUs, a formation timeout), by its
+                                    multi-launch form k_mlpg_gv_gsweep with the same sums bit for bit, and no
+                                    serially served head in the generator */
+
 #define JB_BATCH_TEST_GANG_TIMEOUT 256u /* test aid: the first run behaves as if the resident GV kernel had timed
                                     out in formation (possible without a fault when several such launches share a
                                     device), which makes jb_batch_sync redo the step with the multi-launch GV
@@ -253,7 +273,8 @@ int jb_batch_read_excitation(jb_batch *b, size_t utt, double *dst, size_t cap);
 void *jb_batch_device_pcm(jb_batch *b, size_t *n_samples);
 size_t jb_batch_pcm_offset(const jb_batch *b, size_t utt);
 /* Execution facts of the last run: chunk length / warm-up actually used, number of
- * vocoder work items, and how many chunks failed the hand-off check and were redone. */
+ * vocoder work items, and how many chunks failed the hand-off check and were redone.
+ * (JB_BATCH_INVARIANT: every utterance has a chunk length of its own; this is the longest.) */
 int jb_batch_info(const jb_batch *b, uint32_t *chunk_frames, uint32_t *warmup_frames,
                   uint32_t *n_items, uint32_t *n_redo);
 /* Of the chunks that failed the hand-off check in the last run: how many were settled by
@@ -403,6 +424,15 @@ int jb_engine_get_phoneme_alignment_flag(const jb_engine *e);
  * generator and on any device count; throughput drops to one SIMD per utterance. */
 int jb_engine_set_batch_invariant(jb_engine *e, int flag);
 int jb_engine_get_batch_invariant(const jb_engine *e);
+/* New.  Fast batch-invariant mode: every batch of the engine carries JB_BATCH_INVARIANT (see there), so the same
+ * labels give the SAME BITS alone, in any batch (jb_synthesize_batch[_each|_multi], the 16-bit sink) and through
+ * jb_generator_new, at close to the throughput of the default mode.  The bits are a function of the voice set, the
+ * Condition, the labels, the library build and the GPU architecture; they differ from the default mode's and from
+ * jb_engine_set_batch_invariant's, and stay within the same tolerance of the serial recursion.
+ * jb_engine_set_batch_invariant, when also set, takes precedence (its bits, its speed).  jb_engine_new copies the
+ * flag with the rest of the Condition; the engines of jb_synthesize_batch_each must agree on it. */
+int jb_engine_set_fast_invariant(jb_engine *e, int flag);
+int jb_engine_get_fast_invariant(const jb_engine *e);
 int jb_engine_set_speed(jb_engine *e, double v);
 double jb_engine_get_speed(const jb_engine *e);
 int jb_engine_set_alpha(jb_engine *e, double v);
@@ -452,7 +482,7 @@ void jb_pcm_i16_free(int16_t *pcm);
  * engines[u], under engines[u]'s whole Condition (speed, alignment flag, half tone, volume, alpha, beta, GV weights,
  * MSD thresholds, the three kinds of interpolation weight), in one batch.  New entry (the reference has no batch).
  * The engines share one voice set -- engines made from one another with jb_engine_new (Engine::clone) -- and agree
- * on sampling_frequency, fperiod, stage, use_log_gain and the batch-invariant flag; otherwise JB_ERR_INVALID, with
+ * on sampling_frequency, fperiod, stage, use_log_gain, the batch-invariant and the fast-invariant flags; otherwise JB_ERR_INVALID, with
  * jb_last_error naming what differs, before any device is touched.  pcm[u] library-owned (jb_pcm_free each). */
 int jb_synthesize_batch_each(const jb_engine *const *engines, const char *const *label_lines, const size_t *line_off,
                              size_t n_utts, int32_t device, double **pcm, size_t *n_samples);
@@ -518,7 +548,8 @@ long jb_generator_step(jb_generator *g, double *buf, size_t buf_len);
  * path of jb_synthesize: nothing a SpeechGenerator holds can change between steps) and the call returns
  * without waiting; steps hand out the finished PCM.  While the utterance is still in flight the first 8
  * single-frame steps are served by the serial recursion with persistent state on a side stream, so the
- * first frame does not wait for the last. */
+ * first frame does not wait for the last (not with jb_engine_set_fast_invariant: those frames would not have the
+ * bits of jb_synthesize, and the first step waits for the whole utterance). */
 long jb_generator_step_n(jb_generator *g, double *buf, size_t buf_len, size_t max_frames);
 void jb_generator_free(jb_generator *g);
 

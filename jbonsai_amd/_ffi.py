@@ -31,6 +31,7 @@ BATCH_PCM_I16 = 64
 BATCH_MLPG_ONLY = 128
 BATCH_TEST_GANG_TIMEOUT = 256
 BATCH_NO_EXC_TABLE = 512
+BATCH_INVARIANT = 1024
 
 
 class JbError(RuntimeError):
@@ -145,6 +146,7 @@ SYMBOLS = [
     "jb_engine_set_msd_threshold", "jb_engine_get_msd_threshold", "jb_engine_set_gv_weight",
     "jb_engine_get_gv_weight", "jb_engine_set_phoneme_alignment_flag",
     "jb_engine_get_phoneme_alignment_flag", "jb_engine_set_batch_invariant", "jb_engine_get_batch_invariant",
+    "jb_engine_set_fast_invariant", "jb_engine_get_fast_invariant",
     "jb_engine_set_speed", "jb_engine_get_speed",
     "jb_engine_set_alpha", "jb_engine_get_alpha", "jb_engine_set_beta", "jb_engine_get_beta",
     "jb_engine_set_additional_half_tone", "jb_engine_get_additional_half_tone",

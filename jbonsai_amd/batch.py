@@ -229,14 +229,16 @@ class Batch:
     (Utterance), or -- with `pdf_set` -- pdf row indices (IndexUtterance: the per-state Gaussians are
     gathered and blended on the device, jb_batch_create_indexed), or parameter tracks (TrackUtterance:
     jb_batch_create_from_tracks, the run starts at the vocoder's frame prologue).  mlpg_only=True: the run
-    ends with the parameter tracks (JB_BATCH_MLPG_ONLY; read them with track())."""
+    ends with the parameter tracks (JB_BATCH_MLPG_ONLY; read them with track()).  fast_invariant=True: each
+    utterance's output bits depend on the utterance alone, not on the rest of the batch (JB_BATCH_INVARIANT)."""
 
     def __init__(self, voice: VoiceInfo, utts: Sequence[Utterance], device: int = -1,
                  keep_tracks: bool = False, generic_mlpg: bool = False, serial: bool = False,
                  chunk_frames: int = 0, warmup_frames: int = 0, verify_tol: float = 0.0,
                  kernel: str = "auto", serial_gv: bool = False, pcm_i16: bool = False,
                  pdf_set: Optional[PdfSet] = None, mlpg_only: bool = False,
-                 test_gang_timeout: bool = False, no_exc_table: bool = False, voc=None):
+                 test_gang_timeout: bool = False, no_exc_table: bool = False, voc=None,
+                 fast_invariant: bool = False):
         L = F.lib()
         self._L = L
         self.voice = voice
@@ -254,6 +256,7 @@ class Batch:
                       | (F.BATCH_PCM_I16 if pcm_i16 else 0) | (F.BATCH_MLPG_ONLY if mlpg_only else 0)
                       | (F.BATCH_TEST_GANG_TIMEOUT if test_gang_timeout else 0)
                       | (F.BATCH_NO_EXC_TABLE if no_exc_table else 0)
+                      | (F.BATCH_INVARIANT if fast_invariant else 0)
                       | {"auto": 0, "wave": F.BATCH_WAVE_KERNEL, "triple": F.BATCH_LANE_KERNEL}[kernel])
         opts.chunk_frames, opts.warmup_frames, opts.verify_tol = chunk_frames, warmup_frames, verify_tol
         self.flags, self.device = opts.flags | (F.BATCH_KEEP_TRACKS if mlpg_only else 0), device

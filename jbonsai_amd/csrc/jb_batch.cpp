@@ -819,11 +819,28 @@ static bool same_voc(const VocUtt &a, const VocUtt &b)
     return a.alpha == b.alpha && a.volume == b.volume && a.beta == b.beta && a.beta_stage == b.beta_stage;
 }
 
+int check_invariant_opts(const jb_batch_opts *opts)
+{
+    if (!opts || !(opts->flags & JB_BATCH_INVARIANT))
+        return JB_OK;
+    const char *what = opts->chunk_frames ? "chunk_frames"
+                       : opts->warmup_frames ? "warmup_frames"
+                       : (opts->flags & JB_BATCH_WAVE_KERNEL) ? "JB_BATCH_WAVE_KERNEL"
+                       : (opts->flags & JB_BATCH_LANE_KERNEL) ? "JB_BATCH_LANE_KERNEL" : nullptr;
+    if (!what)
+        return JB_OK;
+    set_error(std::string("JB_BATCH_INVARIANT fixes the vocoder geometry itself: it cannot be combined with ") + what);
+    return JB_ERR_INVALID;
+}
+
 int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n, const jb_batch_opts *opts,
                   Batch **out, const IndexSrc *idx, const TrackSrc *trk, const jb_utt_voc *voc)
 {
     *out = nullptr;
-    int rc = check_voice(voice, trk == nullptr, trk && trk->vocoder_level);
+    int rc = check_invariant_opts(opts);
+    if (rc)
+        return rc;
+    rc = check_voice(voice, trk == nullptr, trk && trk->vocoder_level);
     if (rc)
         return rc;
     // per-utterance vocoder conditions: checked like the voice's own (check_voice), alpha and volume finite
@@ -929,6 +946,7 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
         return hip_fail(e, "hipSetDevice");
     b->device = dev;
     b->flags = opts ? opts->flags : 0;
+    b->invariant = (b->flags & JB_BATCH_INVARIANT) && !(b->flags & JB_BATCH_SERIAL);
     if (b->flags & JB_BATCH_MLPG_ONLY)
         b->flags |= JB_BATCH_KEEP_TRACKS; // the [frame][dim] tracks are the result
     if (trk && (b->flags & JB_BATCH_MLPG_ONLY)) {
@@ -1161,6 +1179,10 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
                 // resident GV (one persistent launch, jb_gv_gang.hip) unless the CUs are partitioned (its
                 // grid is sized for the whole device) or a row has more tiles than a gang can hold
                 int tiles = 0, gangs = 0;
+                // (JB_BATCH_INVARIANT: whether the resident kernel takes a batch depends on its longest row, and
+                // whether it forms on what else runs on the device; wherever it does not run, its multi-launch form
+                // k_mlpg_gv_gsweep does, with the same sums, instead of k_mlpg_gv_tp)
+                sd.gv_gsweep = b->invariant ? 1 : 0;
                 if (maxT > 0 &&
                     gv_gang_plan(dev, maxT, (uint32_t)nbl, &tiles, &gangs)) {
                     uint8_t *ctl;
@@ -1411,7 +1433,28 @@ int Batch::build_work(const jb_batch_opts *opts)
     lp_mode = !serial && !(flags & JB_BATCH_WAVE_KERNEL) && vd.stage == 0 && vocoder_ls_supported(vd.nmcp) &&
               (vd.fperiod & 1) == 0 &&
               (sumT >= lp_min || (flags & JB_BATCH_LANE_KERNEL));
-    if (serial) {
+    // JB_BATCH_INVARIANT: every choice below that the default makes from the whole batch -- chunk length, warm-up,
+    // kernel, its waves per SIMD, checkpoints -- is made from the utterance (and the voice) alone.  Chunks of
+    // clamp(ceil(T / 96), 16, 153) frames behind 18 of warm-up: 153 is what config 2 (256 x 25,546 frames) gets by
+    // default, so that an utterance of more than 14,592 frames keeps the default's chunk-with-warm-up of 171 frames
+    // (12 % of the frames computed twice) and config 2 its work list; shorter utterances get ~96 chunks each, which
+    // keeps a batch of a few of them spread over the chip (64 x 2,000 frames: 21-frame chunks, 6,144 items; the
+    // default gives that batch 16-frame chunks) at the price of more warm-up where many of them fill it anyway
+    // (1024 x 6,386 frames: 67-frame chunks, 27 % of the frames twice against 12 %).  18 frames of warm-up: the
+    // default's for batches with few hand-off positions (14 pays only where a redo round is certain anyway, which
+    // is a property of the batch).  The lane-triple kernel wherever the voice supports it, in its eight-wave form.
+    auto inv_chunk = [](uint32_t Ti) -> uint32_t {
+        constexpr uint32_t kInvChunks = 96, kInvMin = 16, kInvMax = 153;
+        return std::min(std::max((Ti + kInvChunks - 1) / kInvChunks, kInvMin), kInvMax);
+    };
+    if (invariant) {
+        warmup_frames = 18;
+        lp_mode = vd.stage == 0 && vocoder_ls_supported(vd.nmcp) && (vd.fperiod & 1) == 0;
+        lt_waves_per_simd = 2;
+        ch = 0;
+        for (int i = 0; i < B; i++)
+            ch = std::max(ch, inv_chunk(T[(size_t)i])); // (what jb_batch_info reports: the longest of the batch)
+    } else if (serial) {
         ch = 0;
     } else if (ch == 0 && lp_mode) {
         // two waves on every SIMD: 8 XCDs x 32 CUs x 4 SIMDs x 2 -- or ONE, while the batch is too small to give
@@ -1487,7 +1530,7 @@ int Batch::build_work(const jb_batch_opts *opts)
             ch = (ch + 7) / 8 * 8;
     }
     chunk_frames = ch;
-    if (!warmup_given && ch != 0) {
+    if (!warmup_given && ch != 0 && !invariant) {
         warmup_frames = 18;
         uint64_t positions = 0;
         for (int i = 0; i < B; i++)
@@ -1508,13 +1551,16 @@ int Batch::build_work(const jb_batch_opts *opts)
     // chunks of 36 and more, 16 into chunks of 24 and more (a single 128 s utterance, 799 chunks of 32 frames: all six
     // failing hand-offs settle there and the redo is one round of 16 frames, 10.2 -> 9.2 ms per call; 8 frames into
     // 16-frame chunks settle three in four but the rest still take their rounds: same time, not done)
-    vd.ckpt_frames = ch >= 2 * kVocCkptFrames ? kVocCkptFrames
+    // (JB_BATCH_INVARIANT: the positions are constants, and each chunk has them or not by its own length -- a chunk of
+    // 60 frames and more the first, of 108 and more the second; shorter chunks are recomputed to their end)
+    vd.ckpt_frames = invariant ? kVocCkptFrames
+                     : ch >= 2 * kVocCkptFrames ? kVocCkptFrames
                      : ch >= kVocCkptFramesShort + 12 ? kVocCkptFramesShort
                      : ch >= kVocCkptFramesTiny + 8 ? kVocCkptFramesTiny : 0;
-    vd.ckpt2_frames = (vd.ckpt_frames == kVocCkptFrames && ch >= kVocCkpt2Frames + 48) ? kVocCkpt2Frames : 0;
+    vd.ckpt2_frames = invariant || (vd.ckpt_frames == kVocCkptFrames && ch >= kVocCkpt2Frames + 48) ? kVocCkpt2Frames : 0;
 #ifdef JB_DBG_GATES
     if (const char *c1 = getenv("JB_DBG_CKPT1")) // measurement aid: another first checkpoint for long chunks
-        if (vd.ckpt2_frames && atoi(c1) >= 16 && atoi(c1) + 12 <= (int)vd.ckpt2_frames)
+        if (!invariant && vd.ckpt2_frames && atoi(c1) >= 16 && atoi(c1) + 12 <= (int)vd.ckpt2_frames)
             vd.ckpt_frames = (uint32_t)atoi(c1);
 #endif
     work.clear();
@@ -1523,16 +1569,17 @@ int Batch::build_work(const jb_batch_opts *opts)
         const uint32_t Ti = T[(size_t)i];
         if (Ti == 0)
             continue;
-        if (ch == 0 || Ti <= ch + warmup_frames) {
+        const uint32_t ci = invariant ? inv_chunk(Ti) : ch;
+        if (ci == 0 || Ti <= ci + warmup_frames) {
             work.push_back(VocWork{(uint32_t)i, 0, 0, Ti, nullptr, nullptr, nullptr});
             continue;
         }
-        for (uint32_t t0 = 0; t0 < Ti; t0 += ch) {
+        for (uint32_t t0 = 0; t0 < Ti; t0 += ci) {
             VocWork w{};
             w.utt = (uint32_t)i;
             w.t_out = t0;
             w.t_start = t0 > warmup_frames ? t0 - warmup_frames : 0;
-            w.t_end = std::min(Ti, t0 + ch);
+            w.t_end = std::min(Ti, t0 + ci);
             work.push_back(w);
         }
     }
@@ -1639,7 +1686,7 @@ int Batch::enqueue_vocoder()
     if (lp_mode)
         e = launch_vocoder_ls(bd, vd, work_dev, order_dev, n_slots, lt_waves_per_simd, stream_voc);
     else
-        e = launch_vocoder(bd, vd, work_dev, n_items, stream_voc);
+        e = launch_vocoder(bd, vd, work_dev, n_items, stream_voc, invariant);
     if (e != hipSuccess)
         return hip_fail(e, "k_vocoder");
     return JB_OK;
@@ -1906,7 +1953,7 @@ int Batch::finish_verify()
             hipSuccess)
             return hip_fail(he, "hipMemcpy(redo)");
         const double t_b = since();
-        if ((he = launch_vocoder(bd, vd, redo_dev, (uint32_t)round.size(), stream_voc)) != hipSuccess)
+        if ((he = launch_vocoder(bd, vd, redo_dev, (uint32_t)round.size(), stream_voc, invariant)) != hipSuccess)
             return hip_fail(he, "k_vocoder(redo)");
         const double t_c = since();
         if ((he = hipStreamSynchronize(stream_voc)) != hipSuccess)

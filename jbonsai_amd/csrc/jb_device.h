@@ -78,6 +78,8 @@ struct StreamDev {
     // this batch; null = the multi-launch sweeps (k_mlpg_gv_tp)
     void *gv_gang_ctl;
     int gv_gang_n, gv_gang_tiles;
+    int gv_gsweep; // 1 (JB_BATCH_INVARIANT): without the resident kernel, its multi-launch form k_mlpg_gv_gsweep
+                   // (the resident kernel's sums bit for bit) instead of k_mlpg_gv_tp
     // rows of several SHORT utterances share one pass of a gang (round 4): a bin = utterances whose tiles fit the
     // gang's, entry [bin][tile] = which utterance and which of its tiles that workgroup works on; the queue hands
     // out (bin, dim) groups.  (A ragged batch -- BASELINE config 3 -- took 16.4 ms where equal lengths take 8.)
@@ -374,6 +376,8 @@ void gv_gang_bins(const uint32_t *T, const uint8_t *has_gv, const uint32_t *orde
                   std::vector<GvBinEntry> &out);
 size_t gv_gang_ctl_bytes(int n_gangs);
 hipError_t launch_gv_gang(const BatchDev &bd, const StreamDev &sd, int si, hipStream_t stream);
+// the same GV as seven ordinary launches with the resident kernel's tiles and sum shape (bit-identical tracks)
+hipError_t launch_gv_gsweep(const BatchDev &bd, const StreamDev &sd, int si, hipStream_t stream);
 int mlpg_mt_max_dim();      // largest vector length served by the [dim][frame] fast path
 int mlpg_gv_tile_frames();  // frames per block of the time-parallel GV sweeps
 hipError_t launch_pitch(const BatchDev &bd, const VocDev &vd, hipStream_t stream);
@@ -394,8 +398,9 @@ hipError_t launch_excite(const BatchDev &bd, const VocDev &vd, hipStream_t strea
 // (alphas[k]: the alpha of operator k of vd.pf_table, k < vd.n_pf)
 hipError_t launch_pf_table(const VocDev &vd, const double *alphas, hipStream_t stream);
 hipError_t launch_postfilter(const BatchDev &bd, const VocDev &vd, uint64_t nframes, hipStream_t stream);
+// fixed_form: always k_vocoder<tpl_for(nmcp)> (no pair forms chosen by item and CU count): JB_BATCH_INVARIANT
 hipError_t launch_vocoder(const BatchDev &bd, const VocDev &vd, const VocWork *work_dev, uint32_t n_items,
-                          hipStream_t stream);
+                          hipStream_t stream, bool fixed_form = false);
 // lane-serial throughput kernel (one chunk per lane); order_dev = launch permutation of items
 bool vocoder_ls_supported(int nmcp);
 int vocoder_ls_chunks_per_wave(int nmcp); // 21 (lane triples: orders up to 34) or 12 (one stage per lane)

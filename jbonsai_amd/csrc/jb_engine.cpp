@@ -40,6 +40,11 @@ struct Condition {
     std::vector<double> msd_threshold, gv_weight;
     bool phoneme_alignment = false;
     bool batch_invariant = false; // jb_engine_set_batch_invariant: JB_BATCH_SERIAL | JB_BATCH_SERIAL_GV for every batch of this engine
+    bool fast_invariant = false;  // jb_engine_set_fast_invariant: JB_BATCH_INVARIANT for every batch of this engine
+    uint32_t batch_flags() const
+    {
+        return (batch_invariant ? (JB_BATCH_SERIAL | JB_BATCH_SERIAL_GV) : 0u) | (fast_invariant ? JB_BATCH_INVARIANT : 0u);
+    }
     double speed = 1.0;
     size_t stage = 0;
     bool use_log_gain = false;
@@ -740,6 +745,12 @@ int jb_engine_set_batch_invariant(jb_engine *e, int f)
     return JB_OK;
 }
 int jb_engine_get_batch_invariant(const jb_engine *e) { return CENG(e)->cond.batch_invariant; }
+int jb_engine_set_fast_invariant(jb_engine *e, int f)
+{
+    ENG(e)->cond.fast_invariant = f != 0;
+    return JB_OK;
+}
+int jb_engine_get_fast_invariant(const jb_engine *e) { return CENG(e)->cond.fast_invariant; }
 int jb_engine_set_speed(jb_engine *e, double v)
 {
     ENG(e)->cond.speed = std::max(v, 1.0E-06);
@@ -1060,7 +1071,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         const size_t lo = glo[g], hi = glo[g + 1];
         jb_batch_opts opts{};
         opts.device = device;
-        opts.flags = (elem == 2 ? JB_BATCH_PCM_I16 : 0) | (CENG(e)->cond.batch_invariant ? (JB_BATCH_SERIAL | JB_BATCH_SERIAL_GV) : 0);
+        opts.flags = (elem == 2 ? JB_BATCH_PCM_I16 : 0) | CENG(e)->cond.batch_flags();
         jb::Batch *b = nullptr;
         int rc;
         // one engine per utterance: the vocoder conditions of the utterances (a batch whose entries are all the
@@ -1251,6 +1262,8 @@ static int check_engines(const jb_engine *const *engines, size_t n)
             field = "use_log_gain";
         else if (e.cond.batch_invariant != e0.cond.batch_invariant)
             field = "batch_invariant";
+        else if (e.cond.fast_invariant != e0.cond.fast_invariant)
+            field = "fast_invariant";
         if (field) {
             jb::set_error("jb_synthesize_batch_each: engines[" + std::to_string(u) + "] differs from engines[0] in " +
                           field);
@@ -1308,7 +1321,7 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     std::unique_ptr<jb::Generator> g(new jb::Generator());
     jb_batch_opts opts{};
     opts.device = -1;
-    opts.flags = CENG(e)->cond.batch_invariant ? (JB_BATCH_SERIAL | JB_BATCH_SERIAL_GV) : 0;
+    opts.flags = CENG(e)->cond.batch_flags();
     if (const char *ev = getenv("JB_GENERATOR_TEST_GANG_TIMEOUT")) // test aid, as JB_BATCH_TEST_GANG_TIMEOUT
         if (atoi(ev) != 0)
             opts.flags |= JB_BATCH_TEST_GANG_TIMEOUT;
@@ -1320,7 +1333,7 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     g->total = b->T[0];
     // Engine::generator runs all three MLPGs before returning (src/engine.rs:333-357); here they are
     // enqueued, with the vocoder behind them, and the call returns while the device works
-    if ((rc = b->build_generator_work()) || (rc = b->run(false)))
+    if ((!b->invariant && (rc = b->build_generator_work())) || (rc = b->run(false)))
         return rc;
     *out = (jb_generator *)g.release();
     return JB_OK;
@@ -1349,7 +1362,7 @@ int jb_generator_new_from_tracks(const jb_voice_desc *voice, const jb_track_utt 
     g->batch.reset(b);
     g->fperiod = b->voice.fperiod;
     g->total = b->T[0];
-    if ((rc = b->build_generator_work()) || (rc = b->run(false)))
+    if ((!b->invariant && (rc = b->build_generator_work())) || (rc = b->run(false)))
         return rc;
     *out = (jb_generator *)g.release();
     return JB_OK;
@@ -1389,7 +1402,9 @@ long jb_generator_step(jb_generator *hg, double *buf, size_t buf_len)
     if (hipSetDevice(b->device) != hipSuccess)
         return JB_ERR_DEVICE;
     int rc;
-    if (!g->ahead_ready && (g->next >= kGenSerialFrames || hipEventQuery(b->ev_voc_done) == hipSuccess) &&
+    // (no serial head in the fast batch-invariant mode: its frames would not have the bits of jb_synthesize)
+    if (!g->ahead_ready &&
+        (g->next >= kGenSerialFrames || !b->gen_work_dev || hipEventQuery(b->ev_voc_done) == hipSuccess) &&
         (rc = generator_finish(g)))
         return rc;
     if (!g->ahead_ready) {

@@ -249,6 +249,77 @@ __device__ __forceinline__ void gg_turn(double (&r)[kGgFPT], double *xs, int lan
     }
 }
 
+// ---- the arithmetic of a phase, shared by k_mlpg_gv_gang and its multi-launch form k_mlpg_gv_gsweep, so that the
+// two cannot drift apart: the reference's expressions in the reference's order (FP contraction off) ----
+// statistics of an owned, switched-on frame (sums shifted by K, the previous phase's mean)
+__device__ __forceinline__ void gg_stat(double pf, double K, double &s1, double &s2)
+{
+    const double dlt = pf - K;
+    s1 += dlt;
+    s2 += dlt * dlt;
+}
+// band product (W'U^-1W par) at frame f of the lane (calc_hmmobj_derivative, mlpg.rs:205-229), the reference's
+// order of additions; o1, o2: par of the frames f-1, f-2; pr1, pr2: of the two frames after the lane's last
+__device__ __forceinline__ double gg_band(int f, const double (&p)[kGgFPT], double a0f, const double (&a1)[kGgFPT],
+                                          const double (&a2)[kGgFPT], double a1m, double a2m, double a2mm, double o1,
+                                          double o2, double pr1, double pr2)
+{
+    const double pf = p[f];
+    const double pp1 = f + 1 < kGgFPT ? p[f + 1 < kGgFPT ? f + 1 : 0] : pr1;
+    const double pp2 = f + 2 < kGgFPT ? p[f + 2 < kGgFPT ? f + 2 : 0] : (f + 2 == kGgFPT ? pr1 : pr2);
+    const double am1 = f >= 1 ? a1[f >= 1 ? f - 1 : 0] : a1m;
+    const double am2 = f >= 2 ? a2[f >= 2 ? f - 2 : 0] : (f == 1 ? a2m : a2mm);
+    double gg = a0f * pf;
+    gg += a1[f] * pp1;
+    gg += am1 * o1;
+    gg += a2[f] * pp2;
+    gg += am2 * o2;
+    return gg;
+}
+// the HMM objective's term of an owned frame
+__device__ __forceinline__ double gg_hmm_term(double wgt, double pf, double bf, double gg)
+{
+    return 1.0 * wgt * pf * (bf - 0.5 * gg);
+}
+// mean and variance of a phase from its three sums
+__device__ __forceinline__ void gg_moments(double K, double S1, double S2, double glen, double &mean, double &vari)
+{
+    mean = K + S1 / glen;
+    vari = (S2 - S1 * S1 / glen) / glen;
+}
+// conv_gv (mlpg.rs:195-203)
+__device__ __forceinline__ double gg_conv(double ratio, double pf, double mean) { return ratio * (pf - mean) + mean; }
+// objective, step control and the GV gradient factor of ascent iteration it >= 1 (mlpg.rs:230-292)
+__device__ __forceinline__ double gg_ascent(int it, double H, double vari, double gv_vari, double gv_mean, double length,
+                                            double &step, double &prev)
+{
+    const double gvobj = -0.5 * 1.0 * vari * gv_vari * (vari - 2.0 * gv_mean);
+    const double obj = -(H + gvobj);
+    if (it > 1) {
+        if (obj > prev)
+            step *= 0.5; // STEPDEC
+        else if (obj < prev)
+            step *= 1.2; // STEPINC
+    }
+    prev = obj;
+    return -2.0 * gv_vari * (vari - gv_mean) / length; // dv
+}
+// next_step (mlpg.rs:230-258) of one frame: the new par
+__device__ __forceinline__ double gg_next(double pf, double gg, double bf, double a0f, bool on, double wgt, double ll,
+                                          double lm1, double gv_vari, double vari, double gv_mean, double mean, double dv,
+                                          double step)
+{
+    const double h = -1.0 * wgt * a0f -
+                     1.0 * 2.0 / ll * (lm1 * gv_vari * (vari - gv_mean) + 2.0 * gv_vari * (pf - mean) * (pf - mean));
+    const double rh = gg_recip(h);
+    double next_g;
+    if (on)
+        next_g = rh * (1.0 * wgt * (-gg + bf) + 1.0 * dv * (pf - mean));
+    else
+        next_g = rh * (1.0 * wgt * (-gg + bf));
+    return pf + step * next_g;
+}
+
 __global__ __launch_bounds__(kGgNT, JB_GG_WPS) void k_mlpg_gv_gang(BatchDev bd, StreamDev sd, int si, GvGangCtl *ctl,
                                                             GvGang *gangs, int NTg, int n_gangs)
 {
@@ -664,29 +735,16 @@ __global__ __launch_bounds__(kGgNT, JB_GG_WPS) void k_mlpg_gv_gang(BatchDev bd, 
                 for (int f = 0; f < kGgFPT; f++) {
                     const double pf = p[f];
                     const bool own = ownbits >> f & 1u;
-                    if (own && (onbits >> f & 1u)) {
-                        const double dlt = pf - K;
-                        s1 += dlt;
-                        s2 += dlt * dlt;
-                    }
+                    if (own && (onbits >> f & 1u))
+                        gg_stat(pf, K, s1, s2);
                     if (it > 0 && (own || JB_GG_KEEPG)) {
-                        // calc_hmmobj_derivative (mlpg.rs:205-229), the reference's order of additions;
                         // operands outside [0, n) are zeros, which leaves the sum bit-identical
-                        const double pp1 = f + 1 < kGgFPT ? p[f + 1 < kGgFPT ? f + 1 : 0] : pr1;
-                        const double pp2 =
-                            f + 2 < kGgFPT ? p[f + 2 < kGgFPT ? f + 2 : 0] : (f + 2 == kGgFPT ? pr1 : pr2);
-                        const double am1 = f >= 1 ? a1[f >= 1 ? f - 1 : 0] : a1m;
-                        const double am2 = f >= 2 ? a2[f >= 2 ? f - 2 : 0] : (f == 1 ? a2m : a2mm);
-                        double gg = GG_A0(f) * pf;
-                        gg += a1[f] * pp1;
-                        gg += am1 * o1;
-                        gg += a2[f] * pp2;
-                        gg += am2 * o2;
+                        const double gg = gg_band(f, p, GG_A0(f), a1, a2, a1m, a2m, a2mm, o1, o2, pr1, pr2);
 #if JB_GG_KEEPG
                         g[f] = gg;
 #endif
                         if (own)
-                            hh += 1.0 * wgt * pf * (GG_B(f) - 0.5 * gg);
+                            hh += gg_hmm_term(wgt, pf, GG_B(f), gg);
                     }
                     o2 = o1;
                     o1 = pf;
@@ -709,28 +767,19 @@ __global__ __launch_bounds__(kGgNT, JB_GG_WPS) void k_mlpg_gv_gang(BatchDev bd, 
             }
             double S1, S2, H;
             gather(S1, S2, H);
-            const double mean = K + S1 / glen;
-            const double vari = (S2 - S1 * S1 / glen) / glen;
+            double mean, vari;
+            gg_moments(K, S1, S2, glen, mean, vari);
             if (it == 0) {
                 const double ratio = sqrt(gv_mean / vari);
 #pragma unroll
                 for (int f = 0; f < kGgFPT; f++)
                     if (onbits >> f & 1u)
-                        p[f] = ratio * (p[f] - mean) + mean;
+                        p[f] = gg_conv(ratio, p[f], mean);
             } else {
-                const double gvobj = -0.5 * 1.0 * vari * gv_vari * (vari - 2.0 * gv_mean);
-                const double obj = -(H + gvobj);
-                if (it > 1) {
-                    if (obj > prev)
-                        step *= 0.5; // STEPDEC
-                    else if (obj < prev)
-                        step *= 1.2; // STEPINC
-                }
-                prev = obj;
                 // next_step (mlpg.rs:230-258); the band product again (cheaper than keeping it in 16
                 // VGPRs across the exchange), in place and ascending: the two old values to the left of
                 // frame f are carried along (o2, o1), the ones to its right have not been touched yet
-                const double dv = -2.0 * gv_vari * (vari - gv_mean) / length;
+                const double dv = gg_ascent(it, H, vari, gv_vari, gv_mean, length, step, prev);
                 if (busy) {
 #if !JB_GG_KEEPG
                     double o2 = pl2, o1 = pl1;
@@ -741,33 +790,15 @@ __global__ __launch_bounds__(kGgNT, JB_GG_WPS) void k_mlpg_gv_gang(BatchDev bd, 
 #if JB_GG_KEEPG
                         const double gg = g[f];
 #else
-                        const double pp1 = f + 1 < kGgFPT ? p[f + 1 < kGgFPT ? f + 1 : 0] : pr1;
-                        const double pp2 =
-                            f + 2 < kGgFPT ? p[f + 2 < kGgFPT ? f + 2 : 0] : (f + 2 == kGgFPT ? pr1 : pr2);
-                        const double am1 = f >= 1 ? a1[f >= 1 ? f - 1 : 0] : a1m;
-                        const double am2 = f >= 2 ? a2[f >= 2 ? f - 2 : 0] : (f == 1 ? a2m : a2mm);
-                        double gg = GG_A0(f) * pf;
-                        gg += a1[f] * pp1;
-                        gg += am1 * o1;
-                        gg += a2[f] * pp2;
-                        gg += am2 * o2;
+                        const double gg = gg_band(f, p, GG_A0(f), a1, a2, a1m, a2m, a2mm, o1, o2, pr1, pr2);
 #endif
-                        const double bf = GG_B(f);
-                        const double h = -1.0 * wgt * GG_A0(f) -
-                                         1.0 * 2.0 / ll *
-                                             (lm1 * gv_vari * (vari - gv_mean) +
-                                              2.0 * gv_vari * (pf - mean) * (pf - mean));
-                        const double rh = gg_recip(h);
-                        double next_g;
-                        if (onbits >> f & 1u)
-                            next_g = rh * (1.0 * wgt * (-gg + bf) + 1.0 * dv * (pf - mean));
-                        else
-                            next_g = rh * (1.0 * wgt * (-gg + bf));
+                        const double nf = gg_next(pf, gg, GG_B(f), GG_A0(f), (onbits >> f & 1u) != 0, wgt, ll, lm1,
+                                                  gv_vari, vari, gv_mean, mean, dv, step);
 #if !JB_GG_KEEPG
                         o2 = o1;
                         o1 = pf;
 #endif
-                        p[f] = pf + step * next_g;
+                        p[f] = nf;
                         JB_GG_FRAME_FENCE;
                     }
                 }
@@ -801,6 +832,204 @@ __global__ __launch_bounds__(kGgNT, JB_GG_WPS) void k_mlpg_gv_gang(BatchDev bd, 
         for (int k = 0; k < 8; k++)
             atomicAdd(&ctl->prof[k], (unsigned long long)prof_[k]);
 #endif
+}
+
+// ---- the same computation as seven ordinary launches (JB_BATCH_INVARIANT, wherever the resident kernel does not
+// run: a row of more than kGvGangMaxTiles tiles, a gang capacity too small, a formation timeout) ----
+// Workgroup (tile k, dim m, utterance b) owns the frames k_mlpg_gv_gang's tile k owns, and its wave wv the same 488
+// frames in the same 512-frame window, 8 frames per lane; the sums have the gang's shape (lanes ascending, the DPP
+// tree, waves in order, tiles in order) and every frame the gang's expressions (the gg_* functions above), so the
+// tracks are those of the resident kernel bit for bit.  Launch j (0..6) loads the track the previous launch left
+// (halos included: nothing is carried between launches but the track and the sums), applies phase j-1's transform
+// with the scalars it recomputes from the sums of phases 0..j-1 (gv_part, one record per tile: the recurrence of
+// mean, step and objective is a few dozen additions), then takes the sums of phase j on the new track and writes
+// its owned frames.  par -> g -> par ... : six writing launches, result back in par.
+__global__ __launch_bounds__(kGgNT) void k_mlpg_gv_gsweep(BatchDev bd, StreamDev sd, int si, int j,
+                                                          const double *__restrict__ src, double *__restrict__ dst)
+{
+    __shared__ double xs_all[kGgWaves][kGgXs];
+    __shared__ double red[kGgWaves][4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int k = blockIdx.x, m = blockIdx.y, b = blockIdx.z;
+    const UttDev *up = bd.utt + b;
+    const StreamStatesDev st = up->st[si];
+    const int n_i = (int)sd.Tv[b];
+    const uint32_t gvl = sd.gvlen[b];
+    if (!st.gv_mean || n_i <= 0 || gvl == 0 || k * kGgBlockOwn >= n_i)
+        return; // (uniform over the workgroup: no barrier has been passed yet)
+    const int L = sd.L;
+    const uint64_t rowoff = mt_row0(up, L) + (uint64_t)m * (uint64_t)up->mt_rs;
+    const double *A0 = sd.A[0] + rowoff, *A1 = sd.A[1] + rowoff, *A2 = sd.A[2] + rowoff, *Bv = sd.bvec + rowoff;
+    const double *P = src + rowoff;
+    const uint8_t *sw = sd.vsw + up->frame_off;
+    const uint64_t bl = (uint64_t)b * (uint64_t)L + (uint64_t)m;
+    auto rec = [&](int ph, int t) { return sd.gv_part + (((uint64_t)ph * bd.B * L + bl) * sd.gv_ntile + t) * 4; };
+    const int ntr = (n_i + kGgBlockOwn - 1) / kGgBlockOwn; // the row's tiles
+
+    const double gv_mean = st.gv_mean[m] * st.gv_weight; // mlpg.rs:135-137
+    const double gv_vari = st.gv_var[m];
+    const uint32_t n = (uint32_t)n_i;
+    const double glen = (double)gvl;
+    const double wgt = 1.0 / (double)((uint64_t)sd.W * (uint64_t)n);
+    const double length = (double)n;
+    const double ll = (double)((uint64_t)n * (uint64_t)n);
+    const double lm1 = (double)(n - 1);
+
+    // the scalars of phases 0..j-1, in the gang's order: K of phase 0 is the solved track's first frame
+    double K = j == 0 ? P[0] : rec(0, 0)[3];
+    double step = 0.1, prev = 0.0, mean = 0.0, vari = 0.0, dv = 0.0, ratio = 0.0; // STEPINIT
+    for (int ph = 0; ph < j; ph++) {
+        double S1 = 0.0, S2 = 0.0, H = 0.0;
+        for (int t = 0; t < ntr; t++) {
+            const double *r = rec(ph, t);
+            S1 += r[0];
+            S2 += r[1];
+            H += r[2];
+        }
+        gg_moments(K, S1, S2, glen, mean, vari);
+        if (ph == 0)
+            ratio = sqrt(gv_mean / vari);
+        else
+            dv = gg_ascent(ph, H, vari, gv_vari, gv_mean, length, step, prev);
+        K = mean;
+    }
+
+    double *xs = xs_all[wv];
+    const int own_lo = k * kGgBlockOwn + wv * kGgOwn;
+    const bool busy = own_lo < n_i;
+    const int ws = own_lo - kGgHalo;
+    const int t0 = ws + kGgFPT * lane;
+    const int own_hi = own_lo + kGgOwn < n_i ? own_lo + kGgOwn : n_i;
+    double a0[kGgFPT], a1[kGgFPT], a2[kGgFPT], p[kGgFPT], bb[kGgFPT];
+    double a1m = 0.0, a2m = 0.0, a2mm = 0.0;
+    uint32_t onbits = 0, ownbits = 0;
+#pragma unroll
+    for (int f = 0; f < kGgFPT; f++)
+        p[f] = 0.0; // (an idle wave of the row's last tile: its lanes' zeros go into the sums, as in the gang)
+    if (busy) {
+        if (ws >= 0 && ws + kGgWin <= n_i) {
+            gg_fetch<true>(a0, A0, ws, n_i, lane);
+            gg_fetch<true>(a1, A1, ws, n_i, lane);
+            gg_fetch<true>(a2, A2, ws, n_i, lane);
+            gg_fetch<true>(p, P, ws, n_i, lane);
+            gg_fetch<true>(bb, Bv, ws, n_i, lane);
+        } else {
+            gg_fetch<false>(a0, A0, ws, n_i, lane);
+            gg_fetch<false>(a1, A1, ws, n_i, lane);
+            gg_fetch<false>(a2, A2, ws, n_i, lane);
+            gg_fetch<false>(p, P, ws, n_i, lane);
+            gg_fetch<false>(bb, Bv, ws, n_i, lane);
+        }
+        gg_turn(a0, xs, lane);
+        gg_turn(a1, xs, lane);
+        gg_turn(a2, xs, lane);
+        gg_turn(p, xs, lane);
+        gg_turn(bb, xs, lane);
+        a1m = gg_dpp<GG_WAVE_SHR1>(a1[kGgFPT - 1]);
+        a2m = gg_dpp<GG_WAVE_SHR1>(a2[kGgFPT - 1]);
+        a2mm = gg_dpp<GG_WAVE_SHR1>(a2[kGgFPT - 2]);
+#pragma unroll
+        for (int f = 0; f < kGgFPT; f++) {
+            const int t = t0 + f;
+            const bool in = t >= 0 && t < n_i;
+            if (in && sw[t] != 0)
+                onbits |= 1u << f;
+            if (t >= own_lo && t < own_hi)
+                ownbits |= 1u << f;
+        }
+        // ---- phase j-1's transform ----
+        if (j == 1) {
+#pragma unroll
+            for (int f = 0; f < kGgFPT; f++)
+                if (onbits >> f & 1u)
+                    p[f] = gg_conv(ratio, p[f], mean);
+        } else if (j >= 2) {
+            const double pl2 = gg_dpp<GG_WAVE_SHR1>(p[kGgFPT - 2]), pl1 = gg_dpp<GG_WAVE_SHR1>(p[kGgFPT - 1]);
+            const double pr1 = gg_dpp<GG_WAVE_SHL1>(p[0]), pr2 = gg_dpp<GG_WAVE_SHL1>(p[1]);
+            double o2 = pl2, o1 = pl1;
+#pragma unroll
+            for (int f = 0; f < kGgFPT; f++) {
+                const double pf = p[f];
+                const double gg = gg_band(f, p, a0[f], a1, a2, a1m, a2m, a2mm, o1, o2, pr1, pr2);
+                const double nf = gg_next(pf, gg, bb[f], a0[f], (onbits >> f & 1u) != 0, wgt, ll, lm1, gv_vari, vari,
+                                          gv_mean, mean, dv, step);
+                o2 = o1;
+                o1 = pf;
+                p[f] = nf;
+            }
+        }
+    }
+    // ---- phase j's sums on the new track ----
+    if (j <= 5) {
+        double s1 = 0.0, s2 = 0.0, hh = 0.0;
+        const double pl2 = gg_dpp<GG_WAVE_SHR1>(p[kGgFPT - 2]), pl1 = gg_dpp<GG_WAVE_SHR1>(p[kGgFPT - 1]);
+        const double pr1 = gg_dpp<GG_WAVE_SHL1>(p[0]), pr2 = gg_dpp<GG_WAVE_SHL1>(p[1]);
+        if (busy) {
+            double o2 = pl2, o1 = pl1;
+#pragma unroll
+            for (int f = 0; f < kGgFPT; f++) {
+                const double pf = p[f];
+                const bool own = ownbits >> f & 1u;
+                if (own && (onbits >> f & 1u))
+                    gg_stat(pf, K, s1, s2);
+                if (j > 0 && own)
+                    hh += gg_hmm_term(wgt, pf, bb[f], gg_band(f, p, a0[f], a1, a2, a1m, a2m, a2mm, o1, o2, pr1, pr2));
+                o2 = o1;
+                o1 = pf;
+            }
+        }
+        s1 = gg_wave_sum63(s1);
+        s2 = gg_wave_sum63(s2);
+        hh = gg_wave_sum63(hh);
+        if (lane == 63) {
+            red[wv][0] = s1;
+            red[wv][1] = s2;
+            red[wv][2] = hh;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double v0 = red[0][0], v1 = red[0][1], v2 = red[0][2];
+#pragma unroll
+            for (int w = 1; w < kGgWaves; w++) {
+                v0 += red[w][0];
+                v1 += red[w][1];
+                v2 += red[w][2];
+            }
+            double *r = rec(j, k);
+            r[0] = v0;
+            r[1] = v1;
+            r[2] = v2;
+            r[3] = K; // (phase 0: the shift every later launch starts its recurrence from)
+        }
+    }
+    // ---- the owned frames of the new track ----
+    if (j >= 1 && busy) {
+        double *Q = dst + rowoff;
+        gg_wave_sync();
+        double2 *q = reinterpret_cast<double2 *>(xs);
+#pragma unroll
+        for (int jj = 0; jj < kGgFPT / 2; jj++)
+            q[gg_gran(lane, jj)] = make_double2(p[2 * jj], p[2 * jj + 1]);
+        gg_wave_sync();
+#pragma unroll
+        for (int jj = 0; jj < kGgFPT; jj++) {
+            const int t = ws + 64 * jj + lane;
+            if (t >= own_lo && t < own_hi)
+                Q[t] = xs[gg_idx(64 * jj + lane)];
+        }
+    }
+}
+
+hipError_t launch_gv_gsweep(const BatchDev &bd, const StreamDev &sd, int si, hipStream_t stream)
+{
+    // (the records of a row: ceil(n / 3,904) tiles within the gv_ntile slots of 2,048 frames per row and phase)
+    const dim3 grid((unsigned)((bd.maxT + kGgBlockOwn - 1) / kGgBlockOwn), (unsigned)sd.L, (unsigned)bd.B);
+    for (int j = 0; j <= 6; j++) {
+        const double *src = j == 0 || (j & 1) ? sd.par : sd.g;
+        double *dst = j == 0 ? nullptr : (j & 1) ? sd.g : sd.par;
+        hipLaunchKernelGGL(k_mlpg_gv_gsweep, grid, dim3(kGgNT), 0, stream, bd, sd, si, j, src, dst);
+    }
+    return hipGetLastError();
 }
 
 // Workgroups that fit the device at once for this kernel (what the register budget of its launch

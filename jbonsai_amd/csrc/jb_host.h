@@ -15,6 +15,9 @@ namespace jb {
 extern thread_local std::string g_err;
 void set_error(const std::string &s);
 int hip_fail(hipError_t e, const char *what);
+// JB_BATCH_INVARIANT fixes the geometry itself: with an explicit chunk_frames / warmup_frames or a forced vocoder
+// kernel, JB_ERR_INVALID (set_error names the conflict); touches no device
+int check_invariant_opts(const jb_batch_opts *opts);
 // Device copy of the shared Gaussian noise stream; a Batch keeps the table it was created with alive
 struct NoiseDev {
     int device = -1;
@@ -92,6 +95,7 @@ struct Batch {
     uint32_t *nbad_dev = nullptr;
     bool verify_pending = false;
     std::vector<uint8_t> first_of_kind; // [B] 1: no earlier utterance of the batch was made from the same arrays
+    bool invariant = false;          // JB_BATCH_INVARIANT without JB_BATCH_SERIAL: geometry from each utterance alone
     bool lp_mode = false;            // lane-triple throughput kernel
     int lt_waves_per_simd = 2;       // its waves per SIMD: 2 (eight-wave workgroups) or 1 (build_work)
     uint32_t *order_dev = nullptr;   // its launch permutation

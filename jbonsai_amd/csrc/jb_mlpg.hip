@@ -2347,6 +2347,10 @@ static hipError_t launch_mlpg_bw(const BatchDev &bd, const StreamDev &sd, int si
             JB_DBG_SKIP_IF(16, he = launch_gv_gang(bd, sd, si, stream));
             if (he != hipSuccess)
                 return he;
+        } else if (tp && sd.gv_gsweep) {
+            hipError_t he = launch_gv_gsweep(bd, sd, si, stream);
+            if (he != hipSuccess)
+                return he;
         } else if (tp) {
             // par -> g -> par -> ... : conv_gv + five iterations = six writes, result back in par
             dim3 gg(sd.gv_ntile, sd.L, bd.B), gb(kGvNT);

@@ -172,7 +172,10 @@ int jb_paramgen_vocode_batch_multi(const jb_voice_desc *voice, const jb_state_ut
 {
     if (!voice || (n_utts && !utts))
         return JB_ERR_INVALID;
-    int rc = jb::check_devices(devices, n_devices);
+    int rc = jb::check_invariant_opts(opts);
+    if (rc)
+        return rc;
+    rc = jb::check_devices(devices, n_devices);
     if (rc)
         return rc;
     // weights: frames per utterance (the cost of every kernel of the path is linear in them)

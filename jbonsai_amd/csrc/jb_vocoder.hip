@@ -2641,7 +2641,7 @@ hipError_t launch_vocoder_ls(const BatchDev &bd, const VocDev &vd, const VocWork
 }
 
 hipError_t launch_vocoder(const BatchDev &bd, const VocDev &vd, const VocWork *work_dev, uint32_t n_items,
-                          hipStream_t stream)
+                          hipStream_t stream, bool fixed_form)
 {
     if (n_items == 0)
         return hipSuccess;
@@ -2649,7 +2649,7 @@ hipError_t launch_vocoder(const BatchDev &bd, const VocDev &vd, const VocWork *w
         return launch_vocoder_mglsa(bd, vd, work_dev, n_items, stream);
     dim3 grid((n_items + 3) / 4), block(256);
     // two waves per item while that still leaves every wave a SIMD of its own (k_vocoder_pair)
-    const int cus = current_device_cus();
+    const int cus = fixed_form ? 0 : current_device_cus(); // (0: neither pair form)
     const char *nop = getenv("JB_NO_PAIR_KERNEL"); // (unset: both forms; "1": neither; "8": not the eight-wave form)
     if (cus > 0 && n_items <= 2u * (uint32_t)cus && !(nop && nop[0] == '1')) {
         const dim3 gp((n_items + 1) / 2);
