@@ -14,7 +14,7 @@ import jbonsai_amd as J
 from jbonsai_amd import shard, synth
 from tests.conftest import VOICE
 from tests.golden.make_permuted_voice import permuted_voice_path
-from tests.helpers import rel_rms, PCM_TOL
+from tests.helpers import PCM_TOL, assert_pcm_close, rel_rms
 from tests.test_gpu_configs import oracle_pcm
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +43,7 @@ def test_config4_at_the_bench_shape():
     print("config 4 at the bench shape:", info)
     for i in PICKS:
         ref, _ = oracle_pcm(vi, synth.synth_utterance(tab, FRAMES, 4000 + i))
-        assert len(got[i]) == len(ref) and rel_rms(got[i], ref) <= PCM_TOL, i
+        assert_pcm_close(got[i], ref, 240, what=i)
     pset.close()
 
 
@@ -61,7 +61,7 @@ def test_config5_at_the_bench_shape(tmp_path):
         got = {i: b.pcm(i) for i in PICKS}
     for i in PICKS:
         ref, _ = oracle_pcm(vi, synth.synth_utterance_voices(tabs, half, FRAMES, 5000 + i))
-        assert len(got[i]) == len(ref) and rel_rms(got[i], ref) <= PCM_TOL, i
+        assert_pcm_close(got[i], ref, 240, what=i)
     pset.close()
 
 
@@ -94,6 +94,7 @@ def test_bench_dump_outputs_are_the_timed_batch_pcm(tmp_path):
     assert idx.tolist() == [[i, k] for i, w in enumerate(want) for k in range(len(w))]
     for i, w in enumerate(want):
         got = pcm[idx[:, 0] == i]
+        # (bench.py's dump against the library's own batch of the same utterances, not the oracle: the plain gate)
         assert np.abs(got).max() > 1.0 and rel_rms(got, w) <= PCM_TOL, i
 
 
@@ -122,7 +123,7 @@ def test_one_pass_of_the_config3_job():
             assert np.isfinite(a).all() and np.abs(a).max() > 1.0, ids[q]
         q = int(order[1])  # one of the shortest: the oracle takes ~0.15 s per 1000 frames
         ref, _ = oracle_pcm(vi, synth.synth_utterance(tab, lens[ids[q]], 2000 + ids[q]))
-        assert len(pcm[q]) == len(ref) and rel_rms(pcm[q], ref) <= PCM_TOL, ids[q]
+        assert_pcm_close(pcm[q], ref, 240, what=ids[q])
         checked += 1
     assert checked == len(subs) >= 8
     pset.close()

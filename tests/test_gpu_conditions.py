@@ -15,7 +15,7 @@ from oracle import oracle as O
 from tests.conftest import VOICE
 from tests.golden.labels import SAMPLE_SENTENCE_1, SAMPLE_SENTENCE_2, label_pool_utterances
 from tests.golden.make_permuted_voice import permuted_voice_path
-from tests.helpers import PCM_TOL, VERIFY_TOL, rel_rms
+from tests.helpers import VERIFY_TOL, assert_pcm_close, rel_rms
 
 pytestmark = pytest.mark.gpu
 DMAX = 1.7976931348623157e308
@@ -120,7 +120,7 @@ def test_mixed_conditions_vs_oracle(ctx, nmcp):
         if kw.get("kernel") == "triple":
             assert kinfo[0] == "k_vocoder_lt"
         for i, (g, r) in enumerate(zip(got, refs)):
-            assert len(g) == len(r) and rel_rms(g, r) <= PCM_TOL, (nmcp, kw, i, voc[i], rel_rms(g, r))
+            assert_pcm_close(g, r, 240, what=(nmcp, kw, i, voc[i]))
 
 
 def test_mixed_conditions_indexed_path(ctx):
@@ -138,7 +138,7 @@ def test_mixed_conditions_indexed_path(ctx):
         ps.close()
     for i in range(len(iutts)):
         ref = oracle_voc(vi, tracks[i], voc[i])
-        assert len(got[i]) == len(ref) and rel_rms(got[i], ref) <= PCM_TOL, (i, voc[i])
+        assert_pcm_close(got[i], ref, 240, what=(i, voc[i]))
 
 
 # ---- 3. an utterance of a mixed batch is the utterance alone ---------------------------------------------------
@@ -166,7 +166,7 @@ def test_mixed_alpha_redo_path_vs_oracle(ctx, kernel):
     assert info["n_redo"] > 0 and n_part + n_full > 0, info
     for i, u in enumerate(utts):
         ref = oracle_voc(vi, oracle_tracks(vi, u), voc[i])
-        assert len(got[i]) == len(ref) and rel_rms(got[i], ref) <= PCM_TOL, (kernel, i)
+        assert_pcm_close(got[i], ref, 240, what=(kernel, i))
 
 
 # ---- 5. as many classes as utterances in the lane kernel --------------------------------------------------------
@@ -180,7 +180,7 @@ def test_lane_kernel_one_class_per_utterance(ctx, nmcp):
     assert kinfo[0] == "k_vocoder_lt"
     for i, u in enumerate(utts):
         ref = oracle_voc(vi2, oracle_tracks(vi2, u), voc[i])
-        assert len(got[i]) == len(ref) and rel_rms(got[i], ref) <= PCM_TOL, (nmcp, i)
+        assert_pcm_close(got[i], ref, 240, what=(nmcp, i))
 
 
 # ---- 6. Stage::NonZero (MGLSA) -----------------------------------------------------------------------------------
@@ -226,7 +226,7 @@ def test_stage_mixed_alpha_beta(ctx):
             ref = oracle_voc(v2, tr, voc[i], stage=stage)
         same = oracle_voc(v2, tr, voc[i], stage=stage, coef=coef[i], cfirst=first[i])
         assert len(got[i]) == len(ref) and np.all(np.isfinite(ref))
-        assert rel_rms(got[i], same) <= PCM_TOL, i
+        assert_pcm_close(got[i], same, 240, what=i)
         want = np.stack([O.stage_coefficients(tr[0][t], alpha, beta, False, stage) for t in range(len(tr[0]))])
         assert np.abs(coef[i] - want).max() / np.abs(want).max() <= 1e-6, i
         assert rel_rms(got[i], ref) <= 1e-4, i
@@ -269,12 +269,12 @@ def _check_each(engines, labels, oracle=None):
         alone = e.synthesize(lab)
         assert len(got[i]) == len(alone), i
         if len(alone):
-            assert rel_rms(got[i], alone) <= PCM_TOL, i
+            assert_pcm_close(got[i], alone, 240, what=i)
         want16 = np.clip(got[i], -32768.0, 32767.0).astype(np.int16)
         assert got16[i].dtype == np.int16 and np.array_equal(got16[i], want16), i
         if oracle is not None and oracle[i] is not None:
             ref = oracle[i]()
-            assert len(ref) == len(got[i]) and rel_rms(got[i], ref) <= PCM_TOL, i
+            assert_pcm_close(got[i], ref, 240, what=i)
     return got
 
 

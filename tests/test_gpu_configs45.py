@@ -24,7 +24,7 @@ from oracle import oracle as O
 from tests.conftest import VOICE
 from tests.golden.labels import BENCH_LETTER, GENJI, label_pool_utterances
 from tests.golden.make_permuted_voice import permuted_voice_path
-from tests.helpers import rel_rms, PCM_TOL
+from tests.helpers import assert_pcm_close, rel_rms
 from tests.test_gpu_configs import oracle_pcm
 
 pytestmark = pytest.mark.gpu
@@ -71,7 +71,7 @@ def test_config4_labels_batch_1024(pool, oracle_voice):
     for i in PICKS:
         ref = oracle_voice.synthesize(pool[i])
         assert len(outs[i]) == len(ref)
-        assert rel_rms(outs[i], ref) <= PCM_TOL, i
+        assert_pcm_close(outs[i], ref, 240, what=i)
     total = sum(len(o) for o in outs)
     print("config 4 labels: 1024 utterances,", total / 48000.0, "s of audio")
 
@@ -89,7 +89,7 @@ def test_config5_labels_batch_1024_two_different_voices(pool, voice2, weights):
     for i in PICKS:
         ref = vs.synthesize(pool[i])
         assert len(outs[i]) == len(ref), i
-        assert rel_rms(outs[i], ref) <= PCM_TOL, i
+        assert_pcm_close(outs[i], ref, 240, what=i)
     # the blend is a real one: neither voice alone gives this audio, nor does the swapped order
     one = O.Voice(VOICE).synthesize(pool[0])
     assert len(one) != len(outs[0]) or rel_rms(outs[0], one) > 1e-3
@@ -107,9 +107,9 @@ def test_two_voice_single_utterance_entries(voice2):
     vs = O.VoiceSet([VOICE, voice2], W_REF)
     ref = vs.synthesize(BENCH_LETTER, speed=1.2, half_tone=1.5)
     got = e.synthesize(BENCH_LETTER)
-    assert len(got) == len(ref) and rel_rms(got, ref) <= PCM_TOL
+    assert_pcm_close(got, ref, 240)
     g = e.generator(BENCH_LETTER)
-    assert rel_rms(g.generate_all(), ref) <= PCM_TOL
+    assert_pcm_close(g.generate_all(), ref, 240)
 
 
 # ---- state level (what bench.py's config4 / config5 records run) ------------------------------------
@@ -131,7 +131,8 @@ def test_config4_state_level_batch_1024():
     print("config 4 state level:", info, sum(lens), "frames")
     for i in PICKS:
         ref, _ = oracle_pcm(vi, synth.synth_utterance(tab, lens[i], 4000 + i))
-        assert len(got[i]) == lens[i] * 240 and rel_rms(got[i], ref) <= PCM_TOL, i
+        assert len(got[i]) == lens[i] * 240
+        assert_pcm_close(got[i], ref, 240, what=i)
     pset.close()
 
 
@@ -154,7 +155,8 @@ def test_config5_state_level_batch_1024_two_different_voices(voice2, weights):
     for i in PICKS:
         u = synth.synth_utterance_voices(tabs, weights, lens[i], 5000 + i)
         ref, tr = oracle_pcm(vi, u)
-        assert len(got[i]) == lens[i] * 240 and rel_rms(got[i], ref) <= PCM_TOL, i
+        assert len(got[i]) == lens[i] * 240
+        assert_pcm_close(got[i], ref, 240, what=i)
         if i in trk:
             for s in range(3):
                 np.testing.assert_allclose(trk[i][s], tr[s], rtol=1e-12, atol=1e-13)
@@ -174,17 +176,19 @@ def test_genji_1456_labels(oracle_voice):
     ref = oracle_voice.synthesize(GENJI)
     assert len(ref) == 32865 * 240
     got = e.synthesize(GENJI)
-    assert len(got) == len(ref) and rel_rms(got, ref) <= PCM_TOL
+    assert_pcm_close(got, ref, 240)
     ref43 = oracle_voice.synthesize(BENCH_LETTER)
     outs = e.synthesize_batch([BENCH_LETTER, GENJI, [], GENJI[:700], BENCH_LETTER])
     assert [len(o) for o in outs][:3] == [len(ref43), len(ref), 0]
-    assert rel_rms(outs[0], ref43) <= PCM_TOL and rel_rms(outs[1], ref) <= PCM_TOL
+    assert_pcm_close(outs[0], ref43, 240)
+    assert_pcm_close(outs[1], ref, 240)
     assert np.array_equal(outs[0], outs[4])
-    assert rel_rms(outs[3], oracle_voice.synthesize(GENJI[:700])) <= PCM_TOL
+    assert_pcm_close(outs[3], oracle_voice.synthesize(GENJI[:700]), 240)
 
 
 def test_bench_letter_43_labels(oracle_voice):
     e = J.Engine.load([VOICE])
     ref = oracle_voice.synthesize(BENCH_LETTER)
     got = e.synthesize(BENCH_LETTER)
-    assert len(got) == len(ref) == 742 * 240 and rel_rms(got, ref) <= PCM_TOL
+    assert len(got) == len(ref) == 742 * 240
+    assert_pcm_close(got, ref, 240)

@@ -10,7 +10,7 @@ import pytest
 import jbonsai_amd as J
 from oracle import oracle as O
 from tests.golden.labels import SAMPLE_SENTENCE_1, SAMPLE_SENTENCE_2
-from tests.helpers import oracle_run, oracle_states, rel_rms, to_utt, voice_info, PCM_TOL
+from tests.helpers import assert_pcm_close, oracle_run, oracle_states, to_utt, voice_info
 
 pytestmark = pytest.mark.gpu
 
@@ -62,7 +62,7 @@ def test_table_and_per_frame_pass_same_bits_and_oracle(oracle_voice, mode):
     for i in range(2):
         assert np.array_equal(tab[i], gen[i])
         assert np.array_equal(tab[i], tap[i])
-        assert rel_rms(tab[i], refs[i]) <= PCM_TOL
+        assert_pcm_close(tab[i], refs[i], 240)
         np.testing.assert_allclose(gexc[i], excs[i], rtol=0, atol=1e-9)
 
 

@@ -11,7 +11,7 @@ import pytest
 import jbonsai_amd as J
 from oracle import oracle as O
 from tests.golden.labels import SAMPLE_SENTENCE_1, SAMPLE_SENTENCE_2
-from tests.helpers import oracle_run, oracle_states, rel_rms, to_utt, voice_info, PCM_TOL, VERIFY_TOL
+from tests.helpers import VERIFY_TOL, assert_pcm_close, oracle_run, oracle_states, rel_rms, to_utt, voice_info
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +41,7 @@ def test_bonsai_tracks_excitation_pcm(oracle_voice, have_gpu):
         gexc = b.excitation(0)
         np.testing.assert_allclose(gexc, exc, rtol=0, atol=1e-9)
         got = b.pcm(0)
-    assert rel_rms(got, pcm) <= PCM_TOL
+    assert_pcm_close(got, pcm, 240)
     # the reference's own goldens (src/lib.rs:44-46), through the GPU
     assert abs(got[2000] - 19.35141137623778) < 1e-6
     assert abs(got[30000] - -980.6757547598129) < 1e-6
@@ -57,7 +57,7 @@ def test_is_this_bonsai_and_speed(oracle_voice, have_gpu):
     got = J.paramgen_vocode_batch(voice_info(v), utts)
     assert [len(g) for g in got] == [100800, 72000]
     for g, r in zip(got, refs):
-        assert rel_rms(g, r) <= PCM_TOL
+        assert_pcm_close(g, r, 240)
     assert abs(got[0][70000] - -1898.2890228814217) < 1e-6
     assert abs(got[1][71199] - 7.840225089163972) < 1e-6
 
@@ -74,7 +74,8 @@ def test_batch_mixed_and_empty(oracle_voice, have_gpu):
     got = J.paramgen_vocode_batch(voice_info(v), [u1, empty, u2, u1, u2])
     r1, r2 = oracle_run(v, d1, s1)[1], oracle_run(v, d2, s2)[1]
     assert len(got[1]) == 0
-    assert rel_rms(got[0], r1) <= PCM_TOL and rel_rms(got[2], r2) <= PCM_TOL
+    assert_pcm_close(got[0], r1, 240)
+    assert_pcm_close(got[2], r2, 240)
     assert np.array_equal(got[0], got[3]) and np.array_equal(got[2], got[4])
 
 
@@ -83,7 +84,7 @@ def test_volume_and_gv_weight(oracle_voice, have_gpu):
     dur, sts = oracle_states(v, SAMPLE_SENTENCE_1, gv_weight=(0.7, 1.3, 1.0), msd_threshold=(0.5, 0.3, 0.5))
     ref = oracle_run(v, dur, sts, volume=0.5)[1]
     got = J.paramgen_vocode_batch(voice_info(v, volume=0.5), [to_utt(dur, sts)])[0]
-    assert len(got) == len(ref) and rel_rms(got, ref) <= PCM_TOL
+    assert_pcm_close(got, ref, 240)
 
 
 def test_fused_mlpg_equals_generic_bitwise(oracle_voice, have_gpu):
@@ -181,7 +182,8 @@ def test_chunked_equals_serial(oracle_voice, have_gpu):
     for i in range(2):
         assert rel_rms(chk[i], ser[i]) <= 1e-12
         assert rel_rms(dflt[i], ser[i]) <= 1e-12
-        assert rel_rms(chk[i], ref[i]) <= PCM_TOL and rel_rms(ser[i], ref[i]) <= PCM_TOL
+        assert_pcm_close(chk[i], ref[i], 240)
+        assert_pcm_close(ser[i], ref[i], 240)
         print("chunked vs serial rel RMS", rel_rms(chk[i], ser[i]), "max abs", np.abs(chk[i] - ser[i]).max())
 
 
@@ -219,7 +221,7 @@ def test_partial_redo_at_checkpoint(ctx_long, have_gpu):
         e = rel_rms(out[0], ser[0])
         print(kern, "hand-offs failing", info["n_redo"], "settled at checkpoint", n_part, "to the end", n_full,
               "rel RMS vs serial", e)
-        assert e <= PCM_TOL
+        assert_pcm_close(out[0], ser[0], 240, what=kern, chunk=160)
     # the second checkpoint (96 frames into chunks of 144 and more): with a 2-frame warm-up and a tolerance of 1e-12
     # some chunks have not converged 48 frames in and go on to the second checkpoint (JB_REDO_TRACE=1 shows them);
     # with a tolerance below the rounding differences of the two kernels nothing ever settles and every chunk is
@@ -242,14 +244,15 @@ def test_partial_redo_at_checkpoint(ctx_long, have_gpu):
             b.sync()
             info, (n_part, n_full) = b.info(), b.redo_stats()
             e = rel_rms(b.pcm(0), ser[0])
+            assert_pcm_close(b.pcm(0), ser[0], 240, what=chunk, chunk=chunk)
         print("chunk", chunk, "hand-offs failing", info["n_redo"], "settled at checkpoint", n_part, "to the end", n_full,
               "rel RMS vs serial", e)
-        assert info["n_redo"] >= 5 and n_part >= 1 and n_part + n_full == info["n_redo"] and e <= PCM_TOL
+        assert info["n_redo"] >= 5 and n_part >= 1 and n_part + n_full == info["n_redo"]
     # 32-frame warm-up, the default-like case: whatever fails, the result stays certified
     with J.Batch(vi, [u], chunk_frames=136, warmup_frames=32, kernel="triple") as b:
         b.run()
         b.sync()
-        assert rel_rms(b.pcm(0), ser[0]) <= PCM_TOL
+        assert_pcm_close(b.pcm(0), ser[0], 240)
 
 
 def test_pair_kernel_equals_wave_kernel_and_oracle(oracle_voice, have_gpu):
@@ -268,7 +271,8 @@ def test_pair_kernel_equals_wave_kernel_and_oracle(oracle_voice, have_gpu):
     for i in range(3):
         assert rel_rms(par[i], ser[i]) <= 1e-12, i
         assert rel_rms(par[i], wav[i]) <= 1e-12, i
-    assert rel_rms(par[0], ref[0]) <= PCM_TOL and rel_rms(par[1], ref[1]) <= PCM_TOL
+    assert_pcm_close(par[0], ref[0], 240)
+    assert_pcm_close(par[1], ref[1], 240)
     assert np.array_equal(par[0], par[2])
     print("pair vs serial rel RMS", rel_rms(par[0], ser[0]), rel_rms(par[1], ser[1]))
     redo, info2 = _run(v, utts, chunk_frames=64, warmup_frames=1, verify_tol=VERIFY_TOL, kernel="triple")

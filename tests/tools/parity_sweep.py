@@ -41,7 +41,7 @@ def main():
     import jbonsai_amd as J
     from jbonsai_amd import synth
     from tests.conftest import VOICE
-    from tests.helpers import EXC_TOL, PCM_TOL
+    from tests.helpers import EXC_TOL, LOCAL_TOL, PCM_TOL, frame_err
 
     eng = J.Engine.load([VOICE])
     tab = synth.VoiceTables(eng)
@@ -67,26 +67,33 @@ def main():
             got = [(b.pcm(i), b.excitation(i)) for i in range(len(utts))]
         refs = list(fut)
     t1 = time.perf_counter()
-    rel, exc_abs, pulses, bad_pulse = [], [], 0, 0
+    rel, loc, exc_abs, pulses, bad_pulse = [], [], [], 0, 0
     for (g, gx), (r, rx, rp), T in zip(got, refs, lens):
         assert len(g) == len(r) == T * vi.fperiod
         den = np.sqrt(np.mean(r * r))
         rel.append(float(np.sqrt(np.mean((g - r) ** 2)) / (den if den > 0 else 1.0)))
+        loc.append(frame_err(g, r, vi.fperiod))
         exc_abs.append(float(np.abs(gx - rx).max()))
         # a pulse of the oracle is a sample where the excitation stands out by sqrt(pitch): positions are compared
         # through the excitation itself (its max |delta| above would be ~1 for a pulse a sample off)
         pulses += len(rp)
         bad_pulse += int(np.sum(np.abs(gx[rp] - rx[rp]) > 1e-6))
-    rel, exc_abs = np.array(rel), np.array(exc_abs)
+    rel, exc_abs, fe = np.array(rel), np.array(exc_abs), np.array([x[0] for x in loc])
     print(f"{a.n} utterances of {min(lens)}..{max(lens)} frames ({sum(lens)} frames, {sum(lens) * vi.fperiod / vi.sampling_frequency:.0f} s of"
           f" audio) as one ragged batch: {kern[0]}, chunk {info['chunk_frames']} frames,"
           f" {info['n_items']} chunks, {info['n_redo']} redone; oracle on {a.procs} processes; {t1 - t0:.1f} s wall")
     print(f"PCM relative RMS vs oracle: max {rel.max():.3e}  median {np.median(rel):.3e}  (gate {PCM_TOL:g}; north_star 1e-4)")
+    print(f"PCM worst frame vs oracle (frame_err): max {fe.max():.3e}  p99 {np.quantile(fe, 0.99):.3e}  median {np.median(fe):.3e}"
+          f"  (gate {LOCAL_TOL:g})")
     print(f"excitation max |delta|:     max {exc_abs.max():.3e}  median {np.median(exc_abs):.3e}  (gate {EXC_TOL:g})")
     print(f"pulses: {pulses} on the oracle's samples, {bad_pulse} off")
     worst = int(np.argmax(rel))
     print(f"worst utterance: #{worst}, {lens[worst]} frames, rel RMS {rel[worst]:.3e}")
-    ok = rel.max() <= PCM_TOL and exc_abs.max() <= EXC_TOL and bad_pulse == 0
+    wl = int(np.argmax(fe))
+    c = info["chunk_frames"]
+    print(f"worst frame: utterance #{wl}, {lens[wl]} frames, frame {loc[wl][1]} (offset {loc[wl][1] % c} in its {c}-frame"
+          f" chunk), frame_err {fe[wl]:.3e}, rel RMS {rel[wl]:.3e}")
+    ok = rel.max() <= PCM_TOL and fe.max() <= LOCAL_TOL and exc_abs.max() <= EXC_TOL and bad_pulse == 0
     print("PARITY GREEN" if ok else "PARITY RED")
     sys.exit(0 if ok else 1)
 
