@@ -287,6 +287,24 @@ int jb_batch_kernel_info(const jb_batch *b, uint32_t *lane_triple, uint32_t *wav
 /* Times the resident GV kernel of this batch gave up in formation and the step was redone with the
  * multi-launch sweeps (0 in normal operation; see jb_gv_gang.hip "Liveness"). */
 uint32_t jb_batch_gang_fallbacks(const jb_batch *b);
+/* New (the reference only emits the voice's own rate; Condition::set_sampling_frequency changes the rate the vocoder
+ * converts pitch with, not the rate of the audio).  Output rate of the batch's PCM: out_hz[0] for every utterance
+ * (n == 1) or out_hz[u] for utterance u (n == jb_batch_size(b)); 0, or the voice's rate, = native.  Only before the
+ * batch's first run, and not on a JB_BATCH_MLPG_ONLY batch: JB_ERR_INVALID.  A pair whose ratio reduces to L/M with
+ * L or M above 2048: JB_ERR_UNSUPPORTED (jb_last_error says why).  With some utterance at another rate, the run
+ * converts the certified PCM on the device (jb_resample_filter's table) and jb_batch_num_samples / total_samples /
+ * pcm_offset, jb_batch_read_pcm[_all], jb_batch_read_pcm_i16[_all], jb_batch_device_pcm and so jb_gather_pcm all
+ * report the output: ceil(N L / M) samples for N at the voice's rate, f64 or 16-bit by the batch's flags (the 16-bit
+ * conversion then follows the conversion of the rate; native utterances of such a batch are copied, values
+ * unchanged).  Excitation, coefficient and track reads stay at the voice's rate.  With every entry native nothing
+ * runs and nothing is allocated: the batch is the one created. */
+int jb_batch_set_output_rate(jb_batch *b, const uint32_t *out_hz, size_t n);
+/* Rate of utterance utt's PCM as the read entries hand it out (the voice's rate when native); 0 for no such utterance. */
+uint32_t jb_batch_output_rate(const jb_batch *b, size_t utt);
+/* The vocoder's f64 PCM of utterance utt at the voice's rate, jb_batch_num_frames * fperiod samples (what
+ * jb_batch_read_pcm reads without an output rate).  Readable whenever an output rate is set, with JB_BATCH_PCM_I16
+ * as well; a JB_BATCH_PCM_I16 batch without one has no f64 PCM: JB_ERR_INVALID. */
+int jb_batch_read_pcm_native(jb_batch *b, size_t utt, double *dst, size_t cap);
 void jb_batch_free(jb_batch *b);
 
 /* One-shot convenience: create + run + read + free.  pcm[i] must hold
@@ -335,6 +353,25 @@ int jb_vocode_tracks_batch(const jb_voice_desc *voice, const jb_track_utt *utts,
  * and lf0-width mismatches stay JB_ERR_INVALID.  Same buffers as jb_vocode_tracks_batch. */
 int jb_vocoder_synthesize_batch(const jb_voice_desc *voice, const jb_track_utt *utts, size_t n_utts,
                                 const jb_batch_opts *opts, double *const *pcm, size_t *n_samples);
+
+/* ---- output rate (new: no reference counterpart) -----------------------------------------------------------------
+ * Rational polyphase resampling with a Kaiser-windowed sinc, in f64: g = gcd(in_hz, out_hz), L = out_hz / g,
+ * M = in_hz / g, r = min(1, L/M), cutoff fc = 0.45 r cycles per input sample, half-width H = 32 / (2 fc) input
+ * samples, C = ceil(H), ntaps = 2 C; h(t) = 2 fc sinc(2 fc t) I0(10 sqrt(1 - (t/H)^2)) / I0(10) for |t| < H, else 0.
+ * Output k of N input samples: q = floor(k M / L), p = k M mod L, y[k] = sum_{j=0}^{ntaps-1} h[p][j] x[q - C + 1 + j]
+ * with h[p][j] = h(p/L + C - 1 - j), x = 0 outside [0, N) (every utterance alone), n_out = ceil(N L / M).  The device
+ * sums in ascending j with explicit FMAs: each output is a function of x and h alone.  L and M up to 2048 (every pair
+ * of 8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000, 96000 Hz); else JB_ERR_UNSUPPORTED. */
+/* The library's phase table, host only (no GPU needed): *L, *M, *ntaps (each may be NULL) and, when taps is not NULL,
+ * the [L][ntaps] taps h[p][j] (JB_ERR_BUFFER if cap < L * ntaps).  in_hz == out_hz is the pair L = M = 1 of the
+ * formula; the batch entries never filter it. */
+int jb_resample_filter(uint32_t in_hz, uint32_t out_hz, uint32_t *L, uint32_t *M, uint32_t *ntaps, double *taps,
+                       size_t cap);
+/* The converter on PCM the caller holds (the seam of jb_vocoder_synthesize_batch's kind): in[u] of n_in[u] samples at
+ * in_hz -> out[u] of n_out[u] = ceil(n_in[u] L / M) samples at out_hz, library-owned (jb_pcm_free each), on `device`
+ * (-1 = current). */
+int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t in_hz, uint32_t out_hz,
+                          int32_t device, double **out, size_t *n_out);
 
 /* ---- multi-GPU (SURVEY 8b "device_ids[] / n_devices", 8e) ----------------------------------
  * Utterances are independent, so a batch shards over the GPUs of a node with no data-path
@@ -433,6 +470,14 @@ int jb_engine_get_batch_invariant(const jb_engine *e);
  * flag with the rest of the Condition; the engines of jb_synthesize_batch_each must agree on it. */
 int jb_engine_set_fast_invariant(jb_engine *e, int flag);
 int jb_engine_get_fast_invariant(const jb_engine *e);
+/* New.  Rate of the audio the engine's entries return: jb_synthesize, jb_synthesize_batch[_i16], _each[_i16] (each
+ * engine's own rate for its utterance: it is not among the fields the engines must agree on), _multi and the
+ * generator convert the voice-rate PCM on the device before it is copied out (jb_batch_set_output_rate).  0 (the
+ * default) or the voice's rate = native: unchanged output.  jb_engine_new copies it with the Condition.  Unlike
+ * jb_engine_set_sampling_frequency (Condition::set_sampling_frequency, the rate the vocoder converts pitch with),
+ * this resamples.  A pair the converter does not support fails at synthesis with JB_ERR_UNSUPPORTED. */
+int jb_engine_set_output_sampling_frequency(jb_engine *e, size_t hz);
+size_t jb_engine_get_output_sampling_frequency(const jb_engine *e);
 int jb_engine_set_speed(jb_engine *e, double v);
 double jb_engine_get_speed(const jb_engine *e);
 int jb_engine_set_alpha(jb_engine *e, double v);
@@ -539,11 +584,16 @@ size_t jb_generator_fperiod(const jb_generator *g);
 size_t jb_generator_synthesized_frames(const jb_generator *g);
 size_t jb_generator_total_frames(const jb_generator *g);
 /* generate_step: writes fperiod samples to buf, returns fperiod, 0 when exhausted,
- * or a negative jb_status (JB_ERR_BUFFER where the reference panics). */
+ * or a negative jb_status (JB_ERR_BUFFER where the reference panics).
+ * With an output rate (jb_engine_set_output_sampling_frequency, L/M of the voice's rate): step k writes the output
+ * samples [ceil(k F L / M), ceil((k + 1) F L / M)), F = fperiod, and returns their count (at 22.05 kHz from 48 kHz
+ * with F = 240: 110 or 111); buf must hold ceil(F L / M) samples, else JB_ERR_BUFFER.  The steps concatenate to
+ * jb_synthesize's output at that rate; the first step waits for the whole utterance (no serially served head). */
 long jb_generator_step(jb_generator *g, double *buf, size_t buf_len);
 /* Up to max_frames generate_step calls in one: writes n * fperiod samples to buf, n = min(max_frames,
  * frames left, buf_len / fperiod), and returns that sample count (0 when exhausted, JB_ERR_BUFFER if buf
- * cannot hold one frame).  One device-to-host copy for the n frames.
+ * cannot hold one frame).  With an output rate: the samples of the n steps by jb_generator_step's rule, n the most
+ * frames whose samples fit buf_len (JB_ERR_BUFFER if not one step's ceil(F L / M) fit).  One device-to-host copy for the n frames.
  * How the generator works: the whole utterance is enqueued on the device when the generator is made (the
  * path of jb_synthesize: nothing a SpeechGenerator holds can change between steps) and the call returns
  * without waiting; steps hand out the finished PCM.  While the utterance is still in flight the first 8

@@ -161,6 +161,8 @@ SYMBOLS = [
     "jb_lpt_partition", "jb_paramgen_vocode_batch_multi", "jb_synthesize_batch_multi", "jb_synthesize_batch_i16_multi",
     "jb_states_duration_params", "jb_last_error", "jb_device_count", "jb_device_arch", "jb_device_pci_bus_id", "jb_version", "jb_default_verify_tol",
     "jb_batch_create_voc", "jb_batch_create_indexed_voc", "jb_synthesize_batch_each", "jb_synthesize_batch_each_i16",
+    "jb_batch_set_output_rate", "jb_batch_output_rate", "jb_batch_read_pcm_native", "jb_resample_filter",
+    "jb_resample_pcm_batch", "jb_engine_set_output_sampling_frequency", "jb_engine_get_output_sampling_frequency",
 ]
 
 
@@ -265,6 +267,19 @@ def lib():
     L.jb_lpt_partition.argtypes = [C.POINTER(C.c_uint64), sz, sz, C.POINTER(C.c_uint32)]
     L.jb_paramgen_vocode_batch_multi.argtypes = [C.POINTER(VoiceDesc), C.POINTER(StateUtt), sz, C.POINTER(BatchOpts),
                                                  C.POINTER(C.c_int32), sz, C.POINTER(dp), C.POINTER(sz)]
+    L.jb_pcm_free.argtypes = [dp]
+    L.jb_pcm_free.restype = None
+    L.jb_batch_set_output_rate.argtypes = [vp, C.POINTER(C.c_uint32), sz]
+    L.jb_batch_output_rate.argtypes = [vp, sz]
+    L.jb_batch_output_rate.restype = C.c_uint32
+    L.jb_batch_read_pcm_native.argtypes = [vp, sz, vp, sz]
+    L.jb_resample_filter.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32), dp, sz]
+    L.jb_resample_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, C.c_uint32, C.c_uint32, C.c_int32,
+                                        C.POINTER(dp), C.POINTER(sz)]
+    L.jb_engine_set_output_sampling_frequency.argtypes = [vp, sz]
+    L.jb_engine_get_output_sampling_frequency.argtypes = [vp]
+    L.jb_engine_get_output_sampling_frequency.restype = sz
     L.jb_write_wav_i16.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     L.jb_write_wav_f64.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     _lib = L
@@ -282,6 +297,41 @@ def write_wav(path, pcm, sampling_frequency: int) -> None:
     else:
         a = np.ascontiguousarray(a, dtype=np.float64)
         check(lib().jb_write_wav_f64(str(path).encode(), a.ctypes.data, a.size, sampling_frequency))
+
+
+def resample_filter(in_hz: int, out_hz: int):
+    """The library's polyphase table for in_hz -> out_hz (include/jbonsai_amd.h jb_resample_filter; host only):
+    (L, M, taps) with taps a float64 array [L][ntaps]."""
+    import numpy as np
+
+    L = lib()
+    l_, m_, nt = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(L.jb_resample_filter(in_hz, out_hz, C.byref(l_), C.byref(m_), C.byref(nt), None, 0))
+    taps = np.zeros((l_.value, nt.value), dtype=np.float64)
+    check(L.jb_resample_filter(in_hz, out_hz, C.byref(l_), C.byref(m_), C.byref(nt),
+                               taps.ctypes.data_as(C.POINTER(C.c_double)), taps.size))
+    return l_.value, m_.value, taps
+
+
+def resample(pcms, in_hz: int, out_hz: int, device: int = -1):
+    """jb_resample_pcm_batch: each float64 array of `pcms` (or one array) converted from in_hz to out_hz on the GPU."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
+    n = len(arrs)
+    L = lib()
+    dp = C.POINTER(C.c_double)
+    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    outs = (dp * max(n, 1))()
+    nout = (C.c_size_t * max(n, 1))()
+    check(L.jb_resample_pcm_batch(ins, nin, n, in_hz, out_hz, device, outs, nout))
+    res = []
+    for u in range(n):
+        res.append(np.ctypeslib.as_array(outs[u], shape=(nout[u],)).copy() if nout[u] else np.zeros(0))
+        L.jb_pcm_free(outs[u])
+    return res[0] if single else res
 
 
 def check(rc):

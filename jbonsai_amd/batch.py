@@ -356,6 +356,25 @@ class Batch:
         F.check(fn(self._h, ptrs))
         return out
 
+    def set_output_rate(self, out_hz):
+        """jb_batch_set_output_rate: one rate (int) for the whole batch or one per utterance; 0 or the voice's rate =
+        native.  Before the first run only.  The PCM reads (pcm, pcm_i16, pcm_all, num_samples, device_pcm...) then
+        hand out the converted audio."""
+        rates = [int(out_hz)] if np.isscalar(out_hz) else [int(r) for r in out_hz]
+        arr = (C.c_uint32 * max(1, len(rates)))(*rates)
+        F.check(self._L.jb_batch_set_output_rate(self._h, arr, len(rates)))
+
+    def output_rate(self, i) -> int:
+        """Rate of utterance i's PCM as the read entries hand it out (the voice's rate when native)."""
+        return self._L.jb_batch_output_rate(self._h, i)
+
+    def pcm_native(self, i) -> np.ndarray:
+        """The vocoder's f64 PCM of utterance i at the voice's rate (jb_batch_read_pcm_native)."""
+        n = self.num_frames(i) * self.voice.fperiod
+        out = np.empty(n, dtype=np.float64)
+        F.check(self._L.jb_batch_read_pcm_native(self._h, i, out.ctypes.data, n))
+        return out
+
     def track(self, i, stream) -> np.ndarray:
         T, Lv = self.num_frames(i), self.voice.streams[stream].vector_length
         out = np.empty((T, Lv), dtype=np.float64)
@@ -377,7 +396,7 @@ class Batch:
         return out
 
     def excitation(self, i) -> np.ndarray:
-        n = self.num_samples(i)
+        n = self.num_frames(i) * self.voice.fperiod  # at the voice's rate, output rate or not
         out = np.empty(n, dtype=np.float64)
         F.check(self._L.jb_batch_read_excitation(self._h, i, out.ctypes.data, n))
         return out

@@ -1866,6 +1866,7 @@ int Batch::run(bool timed)
     // a previous run's vocoder may still read what this run's parameter generation rewrites
     hipStreamWaitEvent(stream, ev_voc_done, 0);
     last_run_timed = timed;
+    has_run = true;
     for (int si = 0; si < kMaxStream; si++)
         if (sd[si].gv_gang_ctl && !from_tracks)
             gang_check_pending = true;
@@ -1902,6 +1903,10 @@ int Batch::run(bool timed)
             return hip_fail(e, "k_voc_verify");
         verify_pending = true;
     }
+    // behind the check: a batch whose hand-offs all pass pays no host round trip for its output rate (finish_verify
+    // converts again what a redo round rewrites)
+    if ((rc = enqueue_resample()))
+        return rc;
     if (timed)
         hipEventRecord(ev3, stream_voc);
     hipEventRecord(ev_voc_done, stream_voc);
@@ -1964,6 +1969,7 @@ int Batch::finish_verify()
     };
     std::vector<uint8_t> pending(bad);
     pending[0] = 0;
+    std::vector<uint8_t> touched((size_t)B, 0); // utterances a redo round rewrote PCM of: converted again at the end
     const bool redo_trace = getenv("JB_REDO_TRACE") != nullptr; // debugging aid: one line per redo round on stderr
     if (redo_trace)
         fprintf(stderr, "redo: lists and scratch ready after %.3f ms\n", since());
@@ -1990,6 +1996,8 @@ int Batch::finish_verify()
         }
         if (ids.empty())
             break;
+        for (uint32_t k : ids)
+            touched[work[k].utt] = 1;
         // stage A: up to the checkpoint (or the whole chunk where there is none)
         std::vector<VocWork> round;
         std::vector<uint32_t> part; // positions in ids whose recomputed state is compared: with a checkpoint, or
@@ -2170,8 +2178,173 @@ int Batch::finish_verify()
                 }
         }
     }
+    // output rate: what run() converted behind the check came in part from PCM these rounds replaced
+    return enqueue_resample(&touched);
+}
+
+// ---- output rate (jb_batch_set_output_rate) ----
+int Batch::set_output_rate(const uint32_t *hz, size_t n)
+{
+    if (flags & JB_BATCH_MLPG_ONLY) {
+        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_INVALID;
+    }
+    if (has_run) {
+        set_error("jb_batch_set_output_rate: the output rate is set before the batch's first run");
+        return JB_ERR_INVALID;
+    }
+    if (!hz || (n != 1 && n != (size_t)B)) {
+        set_error("jb_batch_set_output_rate: give one rate, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    const uint32_t in = voice.sampling_frequency;
+    std::vector<uint32_t> want((size_t)B);
+    bool any = false;
+    int rc;
+    for (size_t u = 0; u < (size_t)B; u++) {
+        const uint32_t h = hz[n == 1 ? 0 : u];
+        want[u] = h == in ? 0 : h;
+        if (want[u] && (rc = resample_design(in, want[u], nullptr, nullptr)))
+            return rc;
+        any = any || want[u];
+    }
+    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0;
+    if (!any) { // (again) all native: the batch as created
+        if (i16 && rs_on) {
+            vd.pcm16 = rs_sink16;
+            vd.pcm = nullptr;
+        }
+        out_hz = want;
+        rs_on = false;
+        return JB_OK;
+    }
+    // Everything is built in locals first and committed at the end: a failure leaves the batch as it was (a 16-bit
+    // batch keeps its sink)
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipSetDevice");
+    // one table per distinct rate; native utterances go through the identity table (a copy / the 16-bit conversion)
+    std::vector<ResampleTable> tables;
+    std::vector<uint32_t> rate_of_table, table_of((size_t)B);
+    for (size_t u = 0; u < (size_t)B; u++) {
+        const uint32_t h = want[u] ? want[u] : in;
+        size_t t = std::find(rate_of_table.begin(), rate_of_table.end(), h) - rate_of_table.begin();
+        if (t == rate_of_table.size()) {
+            ResampleTable tb{};
+            if ((rc = resample_table(device, in, h, &tb)))
+                return rc;
+            rate_of_table.push_back(h);
+            tables.push_back(tb);
+        }
+        table_of[u] = (uint32_t)t;
+    }
+    std::vector<uint64_t> off((size_t)B + 1, 0);
+    for (size_t u = 0; u < (size_t)B; u++) {
+        const ResampleTable &tb = tables[table_of[u]];
+        off[u + 1] = off[u] + resample_out_len((uint64_t)T[u] * voice.fperiod, tb.L, tb.M);
+    }
+    const size_t n_out = (size_t)off[(size_t)B];
+    // the converter reads f64: a 16-bit batch's vocoder writes an f64 slab of its own from now on, and the 16-bit
+    // conversion moves into k_resample
+    double *f64 = vd.pcm;
+    if (!f64 && !rs_vpcm && (rc = dalloc(&rs_vpcm, std::max<size_t>(total_samples, 1), false)))
+        return rc;
+    if (!f64)
+        f64 = rs_vpcm;
+    int16_t *sink = rs_on ? rs_sink16 : vd.pcm16;
+    double *out64 = nullptr;
+    int16_t *out16 = nullptr;
+    if (i16) {
+        // the 16-bit slab the batch was made with is big enough when the rates go down
+        out16 = sink;
+        if (n_out > total_samples && (rc = dalloc(&out16, std::max<size_t>(n_out, 1), false)))
+            return rc;
+    } else if ((rc = dalloc(&out64, std::max<size_t>(n_out, 1), false))) {
+        return rc;
+    }
+    void *slab = i16 ? (void *)out16 : (void *)out64;
+    const size_t elem = i16 ? sizeof(int16_t) : sizeof(double);
+    std::vector<ResampleTile> tiles;
+    std::vector<uint32_t> tile_lo((size_t)B + 1, 0);
+    for (size_t u = 0; u < (size_t)B; u++) {
+        tile_lo[u] = (uint32_t)tiles.size();
+        resample_tiles(tables[table_of[u]], table_of[u], f64 + (size_t)frame_off[u] * voice.fperiod,
+                       (uint64_t)T[u] * voice.fperiod, (char *)slab + off[u] * elem, off[u + 1] - off[u], tiles);
+    }
+    tile_lo[(size_t)B] = (uint32_t)tiles.size();
+    size_t lds = 0;
+    for (const ResampleTable &tb : tables)
+        lds = std::max<size_t>(lds, tb.lds_bytes);
+    ResampleTable *tables_dev = nullptr;
+    ResampleTile *tiles_dev = nullptr;
+    if ((rc = dalloc(&tables_dev, tables.size(), false)) ||
+        (rc = dalloc(&tiles_dev, std::max<size_t>(tiles.size(), 1), false)))
+        return rc;
+    if ((e = hipMemcpy(tables_dev, tables.data(), sizeof(ResampleTable) * tables.size(), hipMemcpyHostToDevice)) !=
+            hipSuccess ||
+        (!tiles.empty() &&
+         (e = hipMemcpy(tiles_dev, tiles.data(), sizeof(ResampleTile) * tiles.size(), hipMemcpyHostToDevice)) !=
+             hipSuccess))
+        return hip_fail(e, "resample work list");
+    // commit
+    out_hz = want;
+    rs_tables = std::move(tables);
+    rs_off = std::move(off);
+    rs_tiles = std::move(tiles);
+    rs_tile_lo = std::move(tile_lo);
+    rs_lds = lds;
+    rs_tables_dev = tables_dev;
+    rs_tiles_dev = tiles_dev;
+    rs_pcm = out64;
+    rs_pcm16 = out16;
+    if (i16) {
+        rs_sink16 = sink;
+        vd.pcm = f64;
+        vd.pcm16 = nullptr;
+    }
+    rs_on = true;
     return JB_OK;
 }
+
+int Batch::enqueue_resample(const std::vector<uint8_t> *only)
+{
+    if (!rs_on)
+        return JB_OK;
+    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0;
+    hipError_t e;
+    if (!only) {
+        if ((e = launch_resample(rs_tables_dev, rs_tiles_dev, (uint32_t)rs_tiles.size(), i16, rs_lds, stream_voc)) !=
+            hipSuccess)
+            return hip_fail(e, "k_resample");
+        return JB_OK;
+    }
+    std::vector<ResampleTile> sub;
+    for (size_t u = 0; u < (size_t)B; u++)
+        if ((*only)[u])
+            sub.insert(sub.end(), rs_tiles.begin() + rs_tile_lo[u], rs_tiles.begin() + rs_tile_lo[u + 1]);
+    if (sub.empty())
+        return JB_OK;
+    // the list of a redo's tiles, allocated when a redo first needs it (most steps redo nothing)
+    if (sub.size() > rs_redo_cap) {
+        int rc = dalloc(&rs_redo_dev, sub.size(), false);
+        if (rc)
+            return rc;
+        rs_redo_cap = sub.size();
+    }
+    if ((e = hipMemcpy(rs_redo_dev, sub.data(), sizeof(ResampleTile) * sub.size(), hipMemcpyHostToDevice)) !=
+            hipSuccess ||
+        (e = launch_resample(rs_tables_dev, rs_redo_dev, (uint32_t)sub.size(), i16, rs_lds, stream_voc)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
+        return hip_fail(e, "k_resample(redo)");
+    return JB_OK;
+}
+
+size_t Batch::out_samples(size_t u) const
+{
+    return rs_on ? (size_t)(rs_off[u + 1] - rs_off[u]) : (size_t)T[u] * voice.fperiod;
+}
+size_t Batch::out_offset(size_t u) const { return rs_on ? (size_t)rs_off[u] : (size_t)frame_off[u] * voice.fperiod; }
+size_t Batch::out_total() const { return rs_on ? (size_t)rs_off[(size_t)B] : total_samples; }
 
 int Batch::sync()
 {
@@ -2323,7 +2496,8 @@ int stage_ring(int device, StageRing **out)
 
 int Batch::read_pcm_split(void *const *dst, size_t elem)
 {
-    const char *slab = elem == 2 ? (const char *)vd.pcm16 : (const char *)vd.pcm;
+    const char *slab = rs_on ? (elem == 2 ? (const char *)rs_pcm16 : (const char *)rs_pcm)
+                             : (elem == 2 ? (const char *)vd.pcm16 : (const char *)vd.pcm);
     if (flags & JB_BATCH_MLPG_ONLY) {
         set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
@@ -2332,7 +2506,7 @@ int Batch::read_pcm_split(void *const *dst, size_t elem)
         set_error(elem == 2 ? "16-bit PCM needs JB_BATCH_PCM_I16" : "f64 PCM was replaced by the 16-bit sink");
         return JB_ERR_INVALID;
     }
-    const size_t total = total_samples * elem;
+    const size_t total = out_total() * elem;
     if (total == 0)
         return JB_OK;
     int rc = sync();
@@ -2346,7 +2520,7 @@ int Batch::read_pcm_split(void *const *dst, size_t elem)
     // byte offset of every utterance in the slab (utterances are contiguous, in batch order)
     std::vector<size_t> uoff((size_t)B + 1);
     for (int u = 0; u <= B; u++)
-        uoff[u] = (size_t)frame_off[u] * voice.fperiod * elem;
+        uoff[u] = out_offset((size_t)u) * elem;
     const size_t nchunks = (total + kStageSlot - 1) / kStageSlot;
     if (nchunks <= 4 && nchunks <= (size_t)kStageSlots) {
         // a small request (one sentence: 0.5 MB; a 21 s text: 8 MB): its few copies issued at once and scattered on
@@ -2624,13 +2798,51 @@ size_t jb_batch_num_frames(const jb_batch *hb, size_t i)
 size_t jb_batch_num_samples(const jb_batch *hb, size_t i)
 {
     const Batch *b = (const Batch *)hb;
-    return (b && i < (size_t)b->B) ? (size_t)b->T[i] * b->voice.fperiod : 0;
+    return (b && i < (size_t)b->B) ? b->out_samples(i) : 0;
 }
-size_t jb_batch_total_samples(const jb_batch *b) { return b ? ((const Batch *)b)->total_samples : 0; }
+size_t jb_batch_total_samples(const jb_batch *b) { return b ? ((const Batch *)b)->out_total() : 0; }
 size_t jb_batch_pcm_offset(const jb_batch *hb, size_t i)
 {
     const Batch *b = (const Batch *)hb;
-    return (b && i <= (size_t)b->B) ? (size_t)b->frame_off[i] * b->voice.fperiod : 0;
+    return (b && i <= (size_t)b->B) ? b->out_offset(i) : 0;
+}
+
+int jb_batch_set_output_rate(jb_batch *hb, const uint32_t *out_hz, size_t n)
+{
+    return hb ? ((Batch *)hb)->set_output_rate(out_hz, n) : JB_ERR_INVALID;
+}
+
+uint32_t jb_batch_output_rate(const jb_batch *hb, size_t i)
+{
+    const Batch *b = (const Batch *)hb;
+    if (!b || i >= (size_t)b->B)
+        return 0;
+    return (b->rs_on && b->out_hz[i]) ? b->out_hz[i] : b->voice.sampling_frequency;
+}
+
+int jb_batch_read_pcm_native(jb_batch *hb, size_t i, double *dst, size_t cap)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || i >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    if (b->flags & JB_BATCH_MLPG_ONLY) {
+        jb::set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_INVALID;
+    }
+    if (!b->vd.pcm) {
+        jb::set_error("a JB_BATCH_PCM_I16 batch without an output rate has no f64 PCM");
+        return JB_ERR_INVALID;
+    }
+    const size_t ns = (size_t)b->T[i] * b->voice.fperiod;
+    if (cap < ns) {
+        jb::set_error("pcm buffer too small");
+        return JB_ERR_BUFFER;
+    }
+    if (ns == 0)
+        return JB_OK;
+    if (!dst)
+        return JB_ERR_INVALID;
+    return b->read(b->vd.pcm + (size_t)b->frame_off[i] * b->voice.fperiod, dst, ns * sizeof(double));
 }
 void *jb_batch_device_pcm(jb_batch *hb, size_t *n)
 {
@@ -2638,9 +2850,11 @@ void *jb_batch_device_pcm(jb_batch *hb, size_t *n)
     if (!b)
         return nullptr;
     if (n)
-        *n = b->total_samples;
+        *n = b->out_total();
     if ((b->flags & JB_BATCH_MLPG_ONLY) || b->sync()) // the slab is handed out finished and certified
         return nullptr;
+    if (b->rs_on) // output rate: the converted slab
+        return b->rs_pcm ? (void *)b->rs_pcm : (void *)b->rs_pcm16;
     return b->vd.pcm ? (void *)b->vd.pcm : (void *)b->vd.pcm16; // i16 slab for JB_BATCH_PCM_I16 batches
 }
 
@@ -2653,7 +2867,7 @@ int jb_batch_read_pcm(jb_batch *hb, size_t i, double *dst, size_t cap)
         jb::set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
     }
-    size_t ns = (size_t)b->T[i] * b->voice.fperiod;
+    size_t ns = b->out_samples(i);
     if (cap < ns) {
         jb::set_error("pcm buffer too small");
         return JB_ERR_BUFFER;
@@ -2662,11 +2876,12 @@ int jb_batch_read_pcm(jb_batch *hb, size_t i, double *dst, size_t cap)
         return JB_OK;
     if (!dst)
         return JB_ERR_INVALID;
-    if (!b->vd.pcm) {
+    const double *slab = b->rs_on ? b->rs_pcm : b->vd.pcm;
+    if (!slab) {
         jb::set_error("batch was created with JB_BATCH_PCM_I16: use jb_batch_read_pcm_i16");
         return JB_ERR_INVALID;
     }
-    return b->read(b->vd.pcm + (size_t)b->frame_off[i] * b->voice.fperiod, dst, ns * sizeof(double));
+    return b->read(slab + b->out_offset(i), dst, ns * sizeof(double));
 }
 
 int jb_batch_read_pcm_i16(jb_batch *hb, size_t i, int16_t *dst, size_t cap)
@@ -2678,11 +2893,12 @@ int jb_batch_read_pcm_i16(jb_batch *hb, size_t i, int16_t *dst, size_t cap)
         jb::set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
     }
-    if (!b->vd.pcm16) {
+    const int16_t *slab = b->rs_on ? b->rs_pcm16 : b->vd.pcm16;
+    if (!slab) {
         jb::set_error("batch was created without JB_BATCH_PCM_I16");
         return JB_ERR_INVALID;
     }
-    size_t ns = (size_t)b->T[i] * b->voice.fperiod;
+    size_t ns = b->out_samples(i);
     if (cap < ns) {
         jb::set_error("pcm buffer too small");
         return JB_ERR_BUFFER;
@@ -2691,7 +2907,7 @@ int jb_batch_read_pcm_i16(jb_batch *hb, size_t i, int16_t *dst, size_t cap)
         return JB_OK;
     if (!dst)
         return JB_ERR_INVALID;
-    return b->read(b->vd.pcm16 + (size_t)b->frame_off[i] * b->voice.fperiod, dst, ns * sizeof(int16_t));
+    return b->read(slab + b->out_offset(i), dst, ns * sizeof(int16_t));
 }
 
 int jb_batch_read_pcm_all(jb_batch *hb, double *const *dst)

@@ -45,6 +45,7 @@ struct Condition {
     {
         return (batch_invariant ? (JB_BATCH_SERIAL | JB_BATCH_SERIAL_GV) : 0u) | (fast_invariant ? JB_BATCH_INVARIANT : 0u);
     }
+    size_t output_rate = 0;       // jb_engine_set_output_sampling_frequency: 0 = the voice's rate
     double speed = 1.0;
     size_t stage = 0;
     bool use_log_gain = false;
@@ -607,6 +608,11 @@ struct Generator {
     bool serial_armed = false;  // the side stream waits for parameter generation
     std::vector<double> cache;  // PCM of frames [cache_first, cache_first + cache_frames)
     size_t cache_first = 0, cache_frames = 0;
+    // output rate L/M of the voice's (batch->rs_on): step k hands out samples [ceil(k F L / M), ceil((k+1) F L / M))
+    // of the converted utterance, read whole into `cache` by the first step
+    uint64_t L = 1, M = 1;
+    size_t out_start(size_t k) const { return (size_t)(((uint64_t)k * fperiod * L + M - 1) / M); }
+    size_t out_step_max() const { return (size_t)(((uint64_t)fperiod * L + M - 1) / M); }
 };
 constexpr size_t kGenSerialFrames = 8;  // steps that may be served serially while the utterance is in flight
 constexpr size_t kGenBlockFrames = 256; // frames per D2H block of the cache (480 KB at 240 samples per frame)
@@ -751,6 +757,14 @@ int jb_engine_set_fast_invariant(jb_engine *e, int f)
     return JB_OK;
 }
 int jb_engine_get_fast_invariant(const jb_engine *e) { return CENG(e)->cond.fast_invariant; }
+int jb_engine_set_output_sampling_frequency(jb_engine *e, size_t hz)
+{
+    if (!e || hz > UINT32_MAX)
+        return JB_ERR_INVALID;
+    ENG(e)->cond.output_rate = hz;
+    return JB_OK;
+}
+size_t jb_engine_get_output_sampling_frequency(const jb_engine *e) { return e ? CENG(e)->cond.output_rate : 0; }
 int jb_engine_set_speed(jb_engine *e, double v)
 {
     ENG(e)->cond.speed = std::max(v, 1.0E-06);
@@ -1094,6 +1108,15 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         if (rc)
             return rc;
         batches[g].reset(b);
+        // output rate: each utterance's engine's own (a batch whose utterances are all native converts nothing)
+        std::vector<uint32_t> rates(hi - lo);
+        bool any_rate = false;
+        for (size_t u = lo; u < hi; u++) {
+            rates[u - lo] = (uint32_t)eng(u)->cond.output_rate;
+            any_rate = any_rate || rates[u - lo];
+        }
+        if (any_rate && (rc = b->set_output_rate(rates.data(), rates.size())))
+            return rc;
         rc = b->run(false);
         t_create += ms(t0, now());
         return rc;
@@ -1110,7 +1133,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         int rc = JB_OK;
         const auto t0 = now();
         for (size_t u = lo; u < hi; u++) {
-            const size_t ns = (size_t)b->T[u - lo] * b->voice.fperiod;
+            const size_t ns = b->out_samples(u - lo);
             n_samples[u] = ns;
             if (!ns)
                 continue;
@@ -1331,9 +1354,22 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     g->batch.reset(b);
     g->fperiod = b->voice.fperiod;
     g->total = b->T[0];
+    if (CENG(e)->cond.output_rate) {
+        const uint32_t hz = (uint32_t)CENG(e)->cond.output_rate;
+        ResampleSpec sp{};
+        if ((rc = b->set_output_rate(&hz, 1)))
+            return rc;
+        if (b->rs_on && (rc = resample_design(b->voice.sampling_frequency, hz, &sp, nullptr)) == JB_OK) {
+            g->L = sp.L;
+            g->M = sp.M;
+        }
+        if (rc)
+            return rc;
+    }
     // Engine::generator runs all three MLPGs before returning (src/engine.rs:333-357); here they are
     // enqueued, with the vocoder behind them, and the call returns while the device works
-    if ((!b->invariant && (rc = b->build_generator_work())) || (rc = b->run(false)))
+    // (no serially served head with an output rate either: the converted samples of a frame need its successors)
+    if ((!b->invariant && !b->rs_on && (rc = b->build_generator_work())) || (rc = b->run(false)))
         return rc;
     *out = (jb_generator *)g.release();
     return JB_OK;
@@ -1387,6 +1423,35 @@ static int generator_finish(jb::Generator *g)
     return JB_OK;
 }
 
+// Output rate: the converted utterance, read whole by the first step, handed out by the steps' ceil rule
+static long generator_out(jb::Generator *g, double *buf, size_t buf_len, size_t max_frames)
+{
+    if (buf_len < g->out_step_max() || !buf) {
+        set_error("The length of speech buffer must be at least ceil(fperiod * output rate / voice rate).");
+        return JB_ERR_BUFFER;
+    }
+    jb::Batch *b = g->batch.get();
+    if (hipSetDevice(b->device) != hipSuccess)
+        return JB_ERR_DEVICE;
+    int rc = generator_finish(g);
+    if (rc)
+        return rc;
+    if (g->cache.empty() && b->out_samples(0)) {
+        g->cache.resize(b->out_samples(0));
+        if ((rc = b->read(b->rs_pcm + b->out_offset(0), g->cache.data(), g->cache.size() * sizeof(double), false)))
+            return rc;
+    }
+    const size_t lo = g->out_start(g->next);
+    size_t nf = 0;
+    while (nf < max_frames && g->next + nf < g->total && g->out_start(g->next + nf + 1) - lo <= buf_len)
+        nf++;
+    const size_t hi = std::min(g->out_start(g->next + nf), g->cache.size());
+    if (hi > lo)
+        memcpy(buf, g->cache.data() + lo, (hi - lo) * sizeof(double));
+    g->next += nf;
+    return (long)(hi > lo ? hi - lo : 0);
+}
+
 long jb_generator_step(jb_generator *hg, double *buf, size_t buf_len)
 {
     jb::Generator *g = (jb::Generator *)hg;
@@ -1394,6 +1459,8 @@ long jb_generator_step(jb_generator *hg, double *buf, size_t buf_len)
         return JB_ERR_INVALID;
     if (g->total <= g->next)
         return 0;
+    if (g->batch->rs_on)
+        return generator_out(g, buf, buf_len, 1);
     if (buf_len < g->fperiod || !buf) {
         set_error("The length of speech buffer must be larger than fperiod.");
         return JB_ERR_BUFFER;
@@ -1463,6 +1530,8 @@ long jb_generator_step_n(jb_generator *hg, double *buf, size_t buf_len, size_t m
         return JB_ERR_INVALID;
     if (g->total <= g->next || max_frames == 0)
         return 0;
+    if (g->batch->rs_on)
+        return generator_out(g, buf, buf_len, max_frames);
     if (buf_len < g->fperiod || !buf) {
         set_error("The length of speech buffer must be larger than fperiod.");
         return JB_ERR_BUFFER;

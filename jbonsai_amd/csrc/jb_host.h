@@ -37,6 +37,43 @@ int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const si
 // static LPT partition (jb_multi.cpp): part_of[i] = bin of item i
 void lpt_partition(const uint64_t *weights, size_t n, size_t n_parts, uint32_t *part_of);
 
+// Output-rate conversion (jb_resample.hip): the polyphase filter of one (in_hz, out_hz) pair
+constexpr uint64_t kResampleMaxLM = 2048;
+struct ResampleSpec {
+    uint32_t L, M, C, ntaps;
+};
+// in_hz -> out_hz reduced to L/M; taps ([L][ntaps], may be null) by the definition in jb_resample.hip.
+// JB_ERR_UNSUPPORTED (set_error says why) for L or M above 2048
+int resample_design(uint32_t in_hz, uint32_t out_hz, ResampleSpec *spec, std::vector<double> *taps);
+// A pair's device table and its launch geometry, built once per (device, in_hz, out_hz) and kept for the process;
+// in_hz == out_hz gives the identity (one tap 1.0: a copy, or the 16-bit conversion alone)
+struct ResampleTable {
+    const double *h;    // [L][ntaps] device
+    uint32_t L, M, C, ntaps;
+    uint32_t rows;      // output rows (of L outputs each) per tile
+    uint32_t row_waves; // waves a tile's rows are spread over (1, 2, 4); the others split the phases
+    uint32_t lds;       // 1: the tile's input window is staged in LDS; 0: read from global memory
+    uint32_t pad;       // > 0: the LDS window carries one pad double per 2^pad (bank spread for even M)
+    uint32_t lds_bytes; // LDS of a full tile's window (0 without LDS): a launch allocates its tables' largest
+    uint32_t identity;  // 1: in == out, a copy; a tile is `rows` outputs (L = 1)
+};
+// One workgroup's work: rows [m0, m0 + rows) of one utterance (tiles never cross utterances)
+struct ResampleTile {
+    const double *x; // the utterance's input (f64)
+    void *y;         // its output (f64 or i16, by the launch)
+    uint64_t n_in, n_out;
+    uint64_t m0;
+    uint32_t rows;
+    uint32_t table;  // index into the launch's table list
+};
+int resample_table(int device, uint32_t in_hz, uint32_t out_hz, ResampleTable *out);
+uint64_t resample_out_len(uint64_t n_in, uint32_t L, uint32_t M); // ceil(n_in L / M)
+void resample_tiles(const ResampleTable &t, uint32_t table, const double *x, uint64_t n_in, void *y, uint64_t n_out,
+                    std::vector<ResampleTile> &tiles);
+// lds_bytes: the largest lds_bytes of the launch's tables
+hipError_t launch_resample(const ResampleTable *tables_dev, const ResampleTile *tiles_dev, uint32_t n_tiles, bool i16,
+                           size_t lds_bytes, hipStream_t stream);
+
 // Device-resident pdf tables of a voice set (jb_pdf_set) and an indexed batch source
 struct PdfSet {
     int device = -1;
@@ -158,6 +195,29 @@ struct Batch {
     // the caller has waited for ev_mlpg_done
     int gang_timeout_seen(bool *seen);
     double *gen_pcm = nullptr;       // PCM of the streaming generator's serially served frames (its own buffer)
+    // Output rate (jb_batch_set_output_rate).  rs_on: some utterance is converted; then the vocoder writes its f64
+    // slab (vd.pcm) whatever the flags, k_resample fills the output slab (rs_pcm, or rs_pcm16 with JB_BATCH_PCM_I16)
+    // behind the hand-off check, and every PCM read entry but jb_batch_read_pcm_native reads the output slab
+    bool rs_on = false;
+    bool has_run = false;
+    std::vector<uint32_t> out_hz;    // [B] 0 = native; empty until a rate is set
+    std::vector<uint64_t> rs_off;    // [B + 1] first output sample of each utterance
+    double *rs_pcm = nullptr;
+    int16_t *rs_pcm16 = nullptr;
+    int16_t *rs_sink16 = nullptr;    // the 16-bit slab the batch was created with (JB_BATCH_PCM_I16)
+    double *rs_vpcm = nullptr;       // the f64 slab the vocoder of a 16-bit batch writes while a rate is set
+    size_t rs_redo_cap = 0;          // tiles rs_redo_dev holds (allocated by the first redo that needs it)
+    std::vector<ResampleTable> rs_tables;
+    ResampleTable *rs_tables_dev = nullptr;
+    std::vector<ResampleTile> rs_tiles; // sorted by utterance: utterance u owns [rs_tile_lo[u], rs_tile_lo[u + 1])
+    std::vector<uint32_t> rs_tile_lo;
+    size_t rs_lds = 0;               // dynamic LDS of its launches
+    ResampleTile *rs_tiles_dev = nullptr, *rs_redo_dev = nullptr;
+    int set_output_rate(const uint32_t *hz, size_t n);
+    int enqueue_resample(const std::vector<uint8_t> *only = nullptr); // only: [B] 1 = utterances to redo (synchronous)
+    size_t out_samples(size_t u) const;  // what the PCM read entries hand out for utterance u
+    size_t out_offset(size_t u) const;   // ... and where it starts in the slab they read
+    size_t out_total() const;
     bool last_run_timed = false;
     uint32_t gang_fallbacks = 0;     // times the resident GV kernel timed out in formation and the sweeps took over
     static int create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n,

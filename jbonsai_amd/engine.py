@@ -44,6 +44,9 @@ def _bind(L):
     L.jb_engine_get_phoneme_alignment_flag.argtypes = [vp]
     L.jb_engine_set_batch_invariant.argtypes = [vp, C.c_int]
     L.jb_engine_get_batch_invariant.argtypes = [vp]
+    L.jb_engine_set_output_sampling_frequency.argtypes = [vp, sz]
+    L.jb_engine_get_output_sampling_frequency.argtypes = [vp]
+    L.jb_engine_get_output_sampling_frequency.restype = sz
     L.jb_engine_set_fast_invariant.argtypes = [vp, C.c_int]
     L.jb_engine_get_fast_invariant.argtypes = [vp]
     for n in ("num_voices", "num_streams", "num_states"):
@@ -131,6 +134,9 @@ class _Condition:
     def get_batch_invariant(self): return bool(self._L().jb_engine_get_batch_invariant(self._h()))
     def set_fast_invariant(self, b): F.check(self._L().jb_engine_set_fast_invariant(self._h(), int(bool(b))))
     def get_fast_invariant(self): return bool(self._L().jb_engine_get_fast_invariant(self._h()))
+    def set_output_sampling_frequency(self, hz):
+        F.check(self._L().jb_engine_set_output_sampling_frequency(self._h(), int(hz)))
+    def get_output_sampling_frequency(self): return self._L().jb_engine_get_output_sampling_frequency(self._h())
     def set_alpha(self, f): F.check(self._L().jb_engine_set_alpha(self._h(), float(f)))
     def get_alpha(self): return self._L().jb_engine_get_alpha(self._h())
     def set_beta(self, f): F.check(self._L().jb_engine_set_beta(self._h(), float(f)))
@@ -322,7 +328,8 @@ class Engine:
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
         F.check(self._L.jb_generator_new(self._h, _lines(labels), len(labels), C.byref(h)))
-        return SpeechGenerator(h, self._L)
+        return SpeechGenerator(h, self._L, self.condition.get_output_sampling_frequency(),
+                               self.condition.get_sampling_frequency())
 
 
 def _pcm_arrays(pcm, ns, B, i16, free):
@@ -365,15 +372,19 @@ def synthesize_batch_each(engines: Sequence["Engine"], utterances: Sequence[Sequ
 class SpeechGenerator:
     """jbonsai::speech::SpeechGenerator (src/speech.rs:9-96)."""
 
-    def __init__(self, handle, L):
+    def __init__(self, handle, L, output_rate: int = 0, voice_rate: int = 0):
         self._h, self._L = handle, L
+        self.output_rate = output_rate if output_rate and output_rate != voice_rate else 0  # 0: native
+        self.voice_rate = voice_rate
 
     def fperiod(self): return self._L.jb_generator_fperiod(self._h)
     def synthesized_frames(self): return self._L.jb_generator_synthesized_frames(self._h)
     def total_frames(self): return self._L.jb_generator_total_frames(self._h)
 
     def generate_step(self, speech: np.ndarray) -> int:
-        """Writes fperiod samples to speech[0:fperiod]; returns fperiod, or 0 when exhausted."""
+        """Writes fperiod samples to speech[0:fperiod]; returns fperiod, or 0 when exhausted.  With an output rate
+        (L/M of the voice's) step k writes samples [ceil(k F L / M), ceil((k + 1) F L / M)) of the converted
+        utterance and returns their count: a variable length."""
         assert speech.dtype == np.float64 and speech.flags["C_CONTIGUOUS"]
         r = self._L.jb_generator_step(self._h, speech.ctypes.data_as(C.POINTER(C.c_double)), speech.size)
         if r < 0:
@@ -393,6 +404,16 @@ class SpeechGenerator:
         """generate_all (src/speech.rs:87-96): the frames not yet synthesized."""
         fp = self.fperiod()
         left = self.total_frames() - self.synthesized_frames()
+        if self.output_rate:
+            # variable-length steps: a buffer for the most one step of this rate pair writes, the steps concatenated
+            step_max = -(-fp * self.output_rate // self.voice_rate)
+            buf, parts = np.zeros(max(step_max, 1)), []
+            while True:
+                n = self.generate_step(buf)
+                if n == 0:
+                    break
+                parts.append(buf[:n].copy())
+            return np.concatenate(parts) if parts else np.zeros(0)
         buf = np.zeros(left * fp)
         if left:
             got = self.generate_steps(buf, left)
