@@ -8,6 +8,8 @@
 //     so that "lane = vector dim" (MLPG) and "lane = sample" (PCM) accesses are
 //     coalesced.
 #pragma once
+#include "jb_plan.h"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
@@ -291,21 +293,8 @@ struct VocWork {
     double *save_ckpt;        // state on entering frame t_out + VocDev::ckpt_frames, or nullptr (partial redo)
     double *save_ckpt2;       // state on entering frame t_out + VocDev::ckpt2_frames, or nullptr
 };
-// A failing chunk is first recomputed only up to VocDev::ckpt_frames frames past its start; if the
-// recomputed state meets the checkpoint the original chunk left there, the rest of the chunk stands.
-// 48 frames into chunks of 96 frames and more, 24 into chunks of 36 to 95, 16 into chunks of 24 to 35, none below
-// (Batch::build_work).  A redo round lasts as long as the frames to the checkpoint (0.06 ms per frame, one wave per
-// chunk) and ALL of a round's chunks wait for the one that goes furthest.  A hand-off that failed behind 18 frames
-// of warm-up settles at the checkpoint if 18 + 48 frames from zero state are enough.  Tried in round 4: 32 frames
-// (-1 ms per round) -- but about 1 % of the failing hand-offs have not converged there, and a batch of 512 or 1024
-// distinct utterances (BASELINE configs 3 to 5: ~300 failing hand-offs) then nearly always has one and pays the
-// second stage: 2.0 + 3.0 ms instead of 2.9 (tools/ckpt_sweep.sh: 1024 x 6,386 frames 86.6 / 86.3 / 83.9 / 84.6 ms
-// per step with the first checkpoint at 32 / 40 / 48 / 56).
-// Chunks of 144 frames and more leave a SECOND checkpoint 96 frames in: the rare chunk that has not converged at
-// the first one is recomputed 48 frames further and compared again, instead of to its end (105 frames = 6.4 ms).
 // chunk hand-off check: max|state diff| <= tol * max|state| (jb_batch_opts.verify_tol = 0; jb_default_verify_tol())
 constexpr double kDefaultVerifyTol = 1e-9;
-constexpr uint32_t kVocCkptFrames = 48, kVocCkptFramesShort = 24, kVocCkptFramesTiny = 16, kVocCkpt2Frames = 96;
 
 // Timing experiments only (library built with -DJB_DBG_GATES, never the product): JB_DBG_SKIP is a bit mask of
 // launches to leave out once a launcher has been called JB_DBG_SKIP_AFTER times (default 2: bench.py's warm-up
@@ -402,8 +391,6 @@ hipError_t launch_postfilter(const BatchDev &bd, const VocDev &vd, uint64_t nfra
 hipError_t launch_vocoder(const BatchDev &bd, const VocDev &vd, const VocWork *work_dev, uint32_t n_items,
                           hipStream_t stream, bool fixed_form = false);
 // lane-serial throughput kernel (one chunk per lane); order_dev = launch permutation of items
-bool vocoder_ls_supported(int nmcp);
-int vocoder_ls_chunks_per_wave(int nmcp); // 21 (lane triples: orders up to 34) or 12 (one stage per lane)
 // waves_per_simd: 2 = eight-wave workgroups (a whole CU), 1 = four-wave workgroups
 hipError_t launch_vocoder_ls(const BatchDev &bd, const VocDev &vd, const VocWork *work_dev,
                              const uint32_t *order_dev, uint32_t n_items, int waves_per_simd, hipStream_t stream);

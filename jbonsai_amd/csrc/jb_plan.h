@@ -1,0 +1,71 @@
+#pragma once
+// jb_plan.h -- the vocoder's work geometry: chunk length, warm-up, checkpoints, kernel and waves per SIMD, the work
+// items and the lane kernel's launch order, decided from the batch's shape alone (plan_vocoder_work, jb_plan.cpp).
+// Plain C++17 without HIP: the planner runs and is tested on any host; the kernels read the constants below too.
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+
+namespace jb {
+
+// The code an order runs on: its own for nitech's two (35, 25: the EXACT instantiations), else the next of
+// {25, 31, 35} as lane triples or of {41, 51, 61} with one stage per lane, the taps above the voice's own at coefficient
+// zero (an order-39 voice pays for 40 taps, an order-49 voice for 50).  Orders below 6 stay with the wave kernels.
+constexpr int lt_code_nm(int nmcp)
+{
+    return nmcp <= 25 ? 25 : nmcp <= 31 ? 31 : nmcp <= 35 ? 35
+         : nmcp <= 41 ? 41 : nmcp <= 51 ? 51 : nmcp <= 61 ? 61 : 0;
+}
+constexpr int lt_chunks(int lpc) { return lpc == 3 ? 21 : 12; } // chunks per wave
+constexpr bool vocoder_ls_supported(int nmcp) { return nmcp >= 7 && lt_code_nm(nmcp) != 0; }
+// 21 (lane triples: orders up to 34) or 12 (one stage per lane)
+constexpr int vocoder_ls_chunks_per_wave(int nmcp) { return lt_chunks(lt_code_nm(nmcp) <= 35 ? 3 : 5); }
+constexpr uint32_t kLtNoItem = 0xffffffffu; // a slot of the launch permutation without a chunk (class padding)
+
+// A failing chunk is first recomputed only up to VocDev::ckpt_frames frames past its start; if the
+// recomputed state meets the checkpoint the original chunk left there, the rest of the chunk stands.
+// 48 frames into chunks of 96 frames and more, 24 into chunks of 36 to 95, 16 into chunks of 24 to 35, none below
+// (plan_vocoder_work).  A redo round lasts as long as the frames to the checkpoint (0.06 ms per frame, one wave per
+// chunk) and ALL of a round's chunks wait for the one that goes furthest.  A hand-off that failed behind 18 frames
+// of warm-up settles at the checkpoint if 18 + 48 frames from zero state are enough.  Tried in round 4: 32 frames
+// (-1 ms per round) -- but about 1 % of the failing hand-offs have not converged there, and a batch of 512 or 1024
+// distinct utterances (BASELINE configs 3 to 5: ~300 failing hand-offs) then nearly always has one and pays the
+// second stage: 2.0 + 3.0 ms instead of 2.9 (profiles/r04_ckpt_sweep.txt: 1024 x 6,386 frames 86.6 / 86.3 / 83.9 /
+// 84.6 ms per step with the first checkpoint at 32 / 40 / 48 / 56).
+// Chunks of 144 frames and more leave a SECOND checkpoint 96 frames in: the rare chunk that has not converged at
+// the first one is recomputed 48 frames further and compared again, instead of to its end (105 frames = 6.4 ms).
+constexpr uint32_t kVocCkptFrames = 48, kVocCkptFramesShort = 24, kVocCkptFramesTiny = 16, kVocCkpt2Frames = 96;
+
+// What the plan reads: the batch's shape and the caller's options, as plain values.
+struct VocPlanIn {
+    const uint32_t *T = nullptr;            // [B] frames of each utterance (zeros allowed)
+    size_t B = 0;
+    const uint8_t *first_of_kind = nullptr; // [B] 1: no earlier utterance is a copy of this one; nullptr: all distinct
+    const uint32_t *voc_class = nullptr;    // [B] condition class of each utterance; nullptr: one class
+    int nmcp = 0, fperiod = 0, stage = 0;   // the voice's vocoder
+    uint32_t flags = 0;                     // JB_BATCH_* of the batch
+    uint32_t chunk_frames = 0, warmup_frames = 0; // jb_batch_opts: 0 = the library's choice
+};
+
+// VocPlanItem::saves: the states a chunk leaves for the hand-off check and the partial redo
+enum : uint8_t { kSaveEnd = 1, kSaveWarm = 2, kSaveCkpt = 4, kSaveCkpt2 = 8 };
+
+struct VocPlanItem {
+    uint32_t utt, t_start, t_out, t_end; // as VocWork: warm-up from t_start, output [t_out, t_end)
+    uint8_t saves;                       // kSave* bits
+};
+
+struct VocPlan {
+    bool lane_kernel = false;    // k_vocoder_lt (else the wave kernel k_vocoder)
+    int waves_per_simd = 2;      // the lane kernel's: 1 (four-wave workgroups) or 2 (eight-wave)
+    uint32_t chunk_frames = 0;   // 0: serial (one item per utterance); JB_BATCH_INVARIANT: the longest of the batch
+    uint32_t warmup_frames = 0;
+    uint32_t ckpt_frames = 0, ckpt2_frames = 0; // VocDev::ckpt_frames / ckpt2_frames
+    std::vector<VocPlanItem> items;
+    std::vector<uint32_t> order; // the lane kernel's launch permutation of items, kLtNoItem slots included
+};
+
+// Pure: no globals, no environment.
+VocPlan plan_vocoder_work(const VocPlanIn &in);
+
+} // namespace jb

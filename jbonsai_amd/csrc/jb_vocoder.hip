@@ -1753,8 +1753,6 @@ __device__ __forceinline__ double fold5(double s)
     const double t2 = t1 + dpp_f64<DPP_ROW_SHL2>(t1);
     return t2 + dpp_f64<DPP_ROW_SHL4>(s);
 }
-__host__ __device__ constexpr int lt_chunks(int lpc) { return lpc == 3 ? 21 : 12; } // chunks per wave
-constexpr uint32_t kLtNoItem = 0xffffffffu; // a slot of the launch permutation without a chunk (class padding)
 constexpr int kLtPf = 4; // coefficient reads in flight ahead of their use (2, 3 or 4 measure the same)
 // Waves per workgroup.  EIGHT = a whole CU (two waves of 256 VGPRs per SIMD): waves w and w + 4 of a workgroup land on
 // the same SIMD, so the two waves that share a SIMD can see each other's progress in LDS.  The issue arbiter serves
@@ -2546,20 +2544,6 @@ hipError_t launch_voc_verify_pairs(const double *const *pairs_dev, uint32_t n_pa
                        ntaps < 0 ? state_doubles : state_doubles - 4, ntaps, tol, bad, n_bad);
     return hipGetLastError();
 }
-
-// The code an order runs on: its own for nitech's two (35, 25: the EXACT instantiations), else the next of
-// {25, 31, 35} as lane triples or of {41, 51, 61} with one stage per lane, the taps above the voice's own at coefficient
-// zero (an order-39 voice pays for 40 taps, an order-49 voice for 50).  Orders below 6 stay with the wave kernels.
-static int lt_code_nm(int nmcp)
-{
-    for (int c : {25, 31, 35, 41, 51, 61})
-        if (nmcp <= c)
-            return c;
-    return 0;
-}
-bool vocoder_ls_supported(int nmcp) { return nmcp >= 7 && lt_code_nm(nmcp) != 0; }
-
-int vocoder_ls_chunks_per_wave(int nmcp) { return lt_chunks(lt_code_nm(nmcp) <= 35 ? 3 : 5); }
 
 hipError_t launch_vocoder_ls(const BatchDev &bd, const VocDev &vd, const VocWork *work_dev,
                              const uint32_t *order_dev, uint32_t n_items, int waves_per_simd, hipStream_t stream)

@@ -2,7 +2,8 @@
 single-item / chunked boundary, the fast invariant mode's chunk, checkpoint and cap boundaries, the MLPG / GV tiles
 and the resident GV kernel's row limit.  The PCM goes through the local gate (tests/helpers.py assert_pcm_close): an
 error after one seam shows there at its own size.  Each case asserts that it reaches the path it names (info(),
-redo_stats(), kernel_info(), gang_fallbacks())."""
+redo_stats(), kernel_info(), gang_fallbacks()); the vocoder's geometry is also what the host planner
+(tests/test_vocoder_plan.py) computes for the same shape."""
 import dataclasses
 
 import numpy as np
@@ -10,10 +11,12 @@ import pytest
 
 import jbonsai_amd as J
 from jbonsai_amd import synth
+from jbonsai_amd._ffi import BATCH_INVARIANT, BATCH_LANE_KERNEL, BATCH_WAVE_KERNEL
 from oracle import oracle as O
 from tests.conftest import VOICE
 from tests.helpers import assert_pcm_close
 from tests.test_gpu_configs import DMAX, oracle_pcm
+from tests.test_vocoder_plan import build_probe, run_probe, summary
 
 pytestmark = pytest.mark.gpu
 FP = 240
@@ -66,6 +69,22 @@ def run(vi, utts, pcm=True, tracks=False, **kw):
     return out
 
 
+@pytest.fixture(scope="module")
+def plan_probe(tmp_path_factory):
+    return build_probe(tmp_path_factory.mktemp("plan"))
+
+
+def planned(exe, lens, **kw):
+    """(info, kernel_info) of a batch of these lengths as the host planner has them (info without n_redo)."""
+    s = summary(run_probe(exe, lens, **kw))
+    return (dict(chunk_frames=s["chunk"], warmup_frames=s["warmup"], n_items=s["n_items"]),
+            ("k_vocoder_lt" if s["lane"] else "k_vocoder", s["waves"]))
+
+
+def geometry(r):
+    return {k: r["info"][k] for k in ("chunk_frames", "warmup_frames", "n_items")}, tuple(r["kernel"])
+
+
 def _same(a, b, what=""):
     assert a.dtype == b.dtype and a.shape == b.shape, what
     assert a.tobytes() == b.tobytes(), what
@@ -90,7 +109,7 @@ def default_lengths(C):
 
 @pytest.mark.parametrize("kernel", ["wave", "triple"])
 @pytest.mark.parametrize("C", sorted(CKPT))
-def test_default_checkpoint_lengths(ctx, C, kernel):
+def test_default_checkpoint_lengths(ctx, plan_probe, C, kernel):
     eng, tab, vi = ctx
     lens = default_lengths(C)
     utts = [synth.synth_utterance(tab, T, 9100 + T) for T in lens]
@@ -101,6 +120,8 @@ def test_default_checkpoint_lengths(ctx, C, kernel):
     assert r["info"]["chunk_frames"] == C and r["info"]["warmup_frames"] == W, r["info"]
     assert r["info"]["n_items"] == items(lens + lens[:1], C, W), r["info"]
     assert r["kernel"][0] == {"wave": "k_vocoder", "triple": "k_vocoder_lt"}[kernel], r["kernel"]
+    assert geometry(r) == planned(plan_probe, lens + lens[:1], chunk=C, first_of_kind=[1] * len(lens) + [0],
+                                  flags={"wave": BATCH_WAVE_KERNEL, "triple": BATCH_LANE_KERNEL}[kernel])
     _same(r["pcm"][0], r["pcm"][-1])
     print(f"chunk {C} {kernel}: lengths {lens}, {r['info']}, redo {r['redo']}")
     for i, (u, T) in enumerate(zip(utts, lens)):
@@ -136,7 +157,7 @@ def inv_chunk(T):
 INV_LENGTHS = [34, 35, 1536, 1537, 5664, 5665, 10272, 10273, 14592, 14593]
 
 
-def test_fast_invariant_geometry(ctx):
+def test_fast_invariant_geometry(ctx, plan_probe):
     """One item or chunked (34 / 35), chunks of 16 / 17, 59 / 60 (the first checkpoint), 107 / 108 (the second),
     152 / 153 (the cap): alone and inside a batch whose longest utterance sets another chunk length, the same bytes."""
     eng, tab, vi = ctx
@@ -148,6 +169,7 @@ def test_fast_invariant_geometry(ctx):
     assert inside["info"]["chunk_frames"] == inv_chunk(30000) == 153
     assert inside["info"]["warmup_frames"] == W
     assert inside["info"]["n_items"] == sum(items([T], inv_chunk(T), W) for T in INV_LENGTHS + [30000, 700, 20000, 3])
+    assert geometry(inside) == planned(plan_probe, [30000, 700] + INV_LENGTHS + [20000, 3], flags=BATCH_INVARIANT)
     for i, (u, T) in enumerate(zip(utts, INV_LENGTHS)):
         alone = run(vi, [u], fast_invariant=True)
         c = inv_chunk(T)
@@ -178,6 +200,31 @@ def test_fast_invariant_partial_settles(ctx):
         _same(alone["pcm"][0], inside["pcm"][1], T)
         want, _ = oracle(vi, u, ("inv", T))
         assert_pcm_close(alone["pcm"][0], want, FP, what=T, chunk=inv_chunk(T))
+
+
+# ---- the library's own choice of geometry, against the host planner -------------------------------------------------
+
+@pytest.mark.parametrize("case", ["sentences", "4x2000_copies", "4x2000_distinct", "64x2000", "64x2000_invariant"])
+def test_planner_matches_batch(ctx, plan_probe, case):
+    """Chunk length, warm-up, items, kernel and waves per SIMD as the library chooses them for a batch (copies of one
+    utterance count once towards the warm-up rule) are what the host planner computes from the same shape."""
+    eng, tab, vi = ctx
+    if case == "sentences":
+        utts = [synth.synth_utterance(tab, T, 9900 + i) for i, T in enumerate((277, 420, 742))]
+    elif case == "4x2000_copies":
+        utts = [synth.synth_utterance(tab, 2000, 9910)] * 4
+    elif case == "4x2000_distinct":
+        utts = [synth.synth_utterance(tab, 2000, 9910 + i) for i in range(4)]
+    else:
+        utts = [synth.synth_utterance(tab, 2000, 9920 + i) for i in range(64)]
+    invariant = case.endswith("_invariant")
+    with J.Batch(vi, utts, fast_invariant=invariant) as b:
+        lens = [b.num_frames(i) for i in range(len(utts))]
+        got = geometry(dict(info=b.info(), kernel=b.kernel_info()))
+    first = [1] + [0] * 3 if case == "4x2000_copies" else None
+    want = planned(plan_probe, lens, first_of_kind=first, flags=BATCH_INVARIANT if invariant else 0)
+    print(case, lens[:4], got)
+    assert got == want, (case, got, want)
 
 
 # ---- MLPG and GV tiles -----------------------------------------------------------------------------------------------
