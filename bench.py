@@ -13,8 +13,13 @@ Workloads (--job):
   config3: BASELINE config 3 as ONE job -- the seed-fixed list of 4096 mixed-length utterances
       (synth.mixed_lengths) is built once, LPT-partitioned over the N ranks (jbonsai_amd/shard.py)
       and every rank synthesises its share in sub-batches that fit HBM (strong scaling: total work
-      fixed).  At N > 1 a short config-3 pass is also appended to the default run and reported
-      under "config3_strong" (outside `value`).
+      fixed).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line.
+Everything else the benchmark measures or checks -- the CPU baseline and the error figure against the
+oracle, the secondary records of the N = 1 line (other configs, orders, precisions, modes), the config-3
+job beside the config-2 headline and the N = 1 reference of a multi-rank config-3 job -- runs only with
+--full; none of it enters `value`.
 Utterances are independent, so there is no data-path collective; RCCL carries the barrier, the
 max-over-ranks of the timed region and -- with --gather -- the PCM gather onto rank 0.
 
@@ -64,11 +69,15 @@ def parse_args():
     ap.add_argument("--batch", type=int, default=256, help="utterances per GPU (config2 job)")
     ap.add_argument("--frames", type=int, default=0, help="frames per utterance (0 = 25,546 = ~128 s)")
     ap.add_argument("--utts", type=int, default=CONFIG3_UTTS, help="utterances of the config3 job (whole job)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement after the headline: the CPU baseline and the error "
+                         "figure against the oracle, the extras of the N = 1 line (distinct utterances, D2H-inclusive, "
+                         "labels -> PCM, configs 4 and 5 at batch 1024, order 49, batch-invariant), the config-3 job "
+                         "beside the config-2 headline and the N = 1 reference of a multi-rank config-3 job; none of "
+                         "them enters `value`.  Off by default: a plain run times the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements appended to the default line (distinct utterances, "
-                         "D2H-inclusive, labels -> PCM, configs 4 and 5 at batch 1024, the config-3 job); none of "
-                         "them enters `value`")
+                    help="with --full: skip the extras and the config-3 job beside the headline")
     ap.add_argument("--distinct", type=int, default=1,
                     help="number of DISTINCT synthetic utterances tiled over the batch (default 1 = BASELINE "
                          "config 2's copies of one utterance); >1 shows the cost of real hand-off failures")
@@ -209,7 +218,7 @@ def cpu_baseline(utt, vi, batch_size, gpu=None):
     as the checker build), on the same synthetic utterance as the GPU batch:
       (a) single thread: one utterance, median of 5 runs after 1 warm-up;
       (b) all host cores: one utterance per thread at a time until the batch is done or ~12 s have
-          passed (a bounded sample of the batch: the default run must finish within minutes)."""
+          passed (a bounded sample of the batch: the --full run must finish within minutes)."""
     import numpy as np
     from oracle import oracle as O
 
@@ -1216,7 +1225,7 @@ def config3_n1_reference(R, J, tab, vi, pset, args):
 def run_rank(args):
     # the config-3 job keeps two sub-batches alive (one running, the next being created): let the
     # library's device-memory pool hold both sets of blocks between passes (default cap 64 GB).  Not for
-    # the single-GPU default run: its secondary measurements create differently shaped batches, and a
+    # the config-2 job: the secondary measurements of --full create differently shaped batches, and a
     # pool that fills the device turns their allocations into out-of-memory retries
     if args.job == "config3":
         os.environ.setdefault("JB_DEVICE_POOL_MB", "160000")
@@ -1247,7 +1256,7 @@ def run_rank(args):
         pset = tab.pdf_set(R.local_rank)
         ranks, n_cards = R.identities(J)
         rec = run_config3(R, J, tab, vi, pset, args, args.steps, args.warmup)
-        n1 = config3_n1_reference(R, J, tab, vi, pset, args)
+        n1 = config3_n1_reference(R, J, tab, vi, pset, args) if args.full else None
         if R.rank == 0:
             out = {
                 "metric": "48 kHz PCM samples/sec (whole node), batched utterances",
@@ -1273,6 +1282,8 @@ def run_rank(args):
 
     # ---- config 2 (headline): every utterance of the batch is the same sequence ("256 copies"),
     # uploaded once and aliased; outputs / workspace / filter state are per utterance
+    extras = args.full and not args.no_extras
+    cpu_base = args.full and not args.no_cpu_baseline and R.world == 1
     utt = synth.synth_utterance(tab, frames, args.seed)
     nd = max(1, min(args.distinct, args.batch))
     utts = [utt] + [synth.synth_utterance(tab, frames, 1000 + i) for i in range(1, nd)]
@@ -1366,7 +1377,7 @@ def run_rank(args):
             "kernel_sources_sha16": kernel_sources_sha16(),
         }
     gpu_out = None
-    if R.rank == 0 and R.world == 1 and not args.no_cpu_baseline and not args.mixed and nd == 1:
+    if R.rank == 0 and cpu_base and not args.mixed and nd == 1:
         # what the error figure compares: PCM of the first and the last utterance of the timed batch, and the
         # excitation of the same utterance from a one-utterance batch with the debug tap
         gpu_out = {"pcm": [batch.pcm(0), batch.pcm(args.batch - 1)], "exc": None}
@@ -1377,12 +1388,12 @@ def run_rank(args):
                 gpu_out["exc"] = bt.excitation(0)
         except Exception as e:  # the figure then lacks the excitation part
             print(f"excitation tap failed: {e!r}", file=sys.stderr)
-    if R.world == 1 and not args.no_extras:
+    if R.world == 1 and extras:
         ex = extras_single_gpu(J, eng, tab, vi, args, batch, batch_utts, frames, ms_per_step, R)
         if out is not None:
             out.update(ex)
     batch.close()
-    if not args.no_extras:
+    if extras:
         # BASELINE config 3 as ONE job beside the headline: the 4096-utterance list, this rank's share walked
         # in sub-batches: one warm-up pass and two timed passes ("config3_strong" at N > 1, "config3_job" at
         # N = 1: ~0.9 s per pass).  The job keeps two sub-batches alive: let the memory pool hold both
@@ -1405,7 +1416,7 @@ def run_rank(args):
                 if n1.get("value") and rec.get("value"):
                     out["config3_strong"]["speedup_over_n1"] = rec["value"] / n1["value"]
     if R.rank == 0:
-        if R.world == 1 and not args.no_cpu_baseline:
+        if cpu_base:
             out["cpu_baseline"] = cpu_baseline(utt, vi, args.batch, gpu_out)
             # the metric's error figure, at the top level of the line (it is part of the metric)
             out["error_vs_oracle"] = out["cpu_baseline"].pop("error_vs_oracle")

@@ -65,6 +65,30 @@ def test_config5_at_the_bench_shape(tmp_path):
     pset.close()
 
 
+def test_bench_plain_run_prints_the_headline_alone():
+    """A run without --full times the headline and nothing else: the line carries the headline's keys, and none of
+    the records that only --full measures (CPU baseline, error against the oracle, extras, the config-3 job)."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parent.parent
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--batch", "3", "--frames", "600",
+                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(d["config"]["samples_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3))
+    for key in ("cpu_baseline", "error_vs_oracle", "two_batches_in_flight", "d2h_inclusive", "host_visible",
+                "copies_over_seeds", "distinct_64", "labels_to_pcm", "config4", "config5", "order49",
+                "batch_invariant", "config3_job", "config3_strong", "config3_job_n1"):
+        assert key not in d, key
+
+
 def test_bench_dump_outputs_are_the_timed_batch_pcm(tmp_path):
     """`bench.py --dump-outputs DIR` writes the PCM a caller of the timed batch reads (all of it for an output this
     small), and the line reports the --steps it timed."""

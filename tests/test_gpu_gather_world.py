@@ -61,14 +61,14 @@ def test_bench_rehearsal_line_is_self_verifying(double):
     carry one identity record per rank -- the PCI bus id of its card and the communicator size RCCL itself reports
     (ncclCommCount through jb_comm_size) -- so that the driver's real N-GPU run proves by itself that N ranks ran
     on N distinct cards (VERDICT r5 "next" 7).  Here: two ranks, ONE card, size 2, and the gather keyed by its type;
-    the config-3 job carries its own N = 1 reference."""
+    with --full, the config-3 job carries its own N = 1 reference."""
     import json
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(JB_BENCH_REHEARSE="1", JB_RCCL_LIBRARY=double, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--batch", "8", "--frames", "3000",
-                        "--steps", "2", "--warmup", "1", "--utts", "64", "--gather", "--no-cpu-baseline"], env=env,
-                       capture_output=True, text=True, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--utts", "64", "--gather", "--full", "--no-cpu-baseline"],
+                       env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["distinct_gpus"] == 1

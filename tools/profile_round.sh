@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 # copy them from $out to profiles/ after the call: only gpurun_out/ comes back from the box)
 JSON=profiles/${R}_pmc_sq_k_vocoder_lt.json bash tools/pmc_voc.sh > $out/${R}_pmc_sq_k_vocoder_lt.txt 2>&1 && cp profiles/${R}_pmc_sq_k_vocoder_lt.json $out/
 bash tools/traffic.sh $R > $out/traffic.log 2>&1 && cp profiles/${R}_traffic.json $out/${R}_traffic.json
-python bench.py --steps 20 --warmup 5 > $out/${R}_bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+python bench.py --steps 20 --warmup 5 --full > $out/${R}_bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 STEPS=4 bash tools/kstats.sh > $out/${R}_kernel_ms_per_step.txt 2>&1
 cp gpurun_out/kstats/k_kernel_stats.csv $out/${R}_kernel_stats.csv
 python tools/timeline.py > $out/${R}_timeline_one_step.txt
