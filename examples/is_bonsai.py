@@ -1,10 +1,13 @@
 """The reference's `examples/is-bonsai` on the GPU path: full-context labels -> PCM -> 16-bit WAV.
 
-    python examples/is_bonsai.py [voice.htsvoice] [out.wav]
+    python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
+With --loudness the audio is normalized on the GPU to that integrated loudness (BS.1770-4), its sample peak kept at or
+under --ceiling (dBFS, default 0).
 """
+import argparse
 import os
 import sys
 
@@ -12,13 +15,24 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import jbonsai_amd as J  # noqa: E402
 from tests.golden.labels import SAMPLE_SENTENCE_2  # the label lines of the reference's example  # noqa: E402
 
-voice = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
-    os.path.dirname(__file__), "..", "tests", "golden", "voice", "nitech_jp_atr503_m001.htsvoice")
-out = sys.argv[2] if len(sys.argv) > 2 else "is-bonsai.wav"
+ap = argparse.ArgumentParser()
+ap.add_argument("voice", nargs="?", default=os.path.join(
+    os.path.dirname(__file__), "..", "tests", "golden", "voice", "nitech_jp_atr503_m001.htsvoice"))
+ap.add_argument("out", nargs="?", default="is-bonsai.wav")
+ap.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="target integrated loudness")
+ap.add_argument("--ceiling", type=float, default=0.0, metavar="DBFS", help="sample-peak ceiling (with --loudness)")
+args = ap.parse_args()
+voice, out = args.voice, args.out
 
 engine = J.Engine.load([voice])
+if args.loudness is not None:
+    engine.condition.set_loudness_target(args.loudness)
+    engine.condition.set_peak_ceiling(args.ceiling)
 speech = engine.synthesize(SAMPLE_SENTENCE_2)
 print(f"The synthesized voice has {len(speech)} samples in total.")
+if args.loudness is not None:
+    lufs, peak = J.loudness(speech, engine.condition.get_sampling_frequency())
+    print(f"normalized: {lufs:.2f} LUFS, sample peak {peak:.2f} dBFS")
 J.write_wav(out, speech, engine.condition.get_sampling_frequency())
 print(f"wrote {out}")
 

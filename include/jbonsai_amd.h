@@ -302,9 +302,24 @@ int jb_batch_set_output_rate(jb_batch *b, const uint32_t *out_hz, size_t n);
 /* Rate of utterance utt's PCM as the read entries hand it out (the voice's rate when native); 0 for no such utterance. */
 uint32_t jb_batch_output_rate(const jb_batch *b, size_t utt);
 /* The vocoder's f64 PCM of utterance utt at the voice's rate, jb_batch_num_frames * fperiod samples (what
- * jb_batch_read_pcm reads without an output rate).  Readable whenever an output rate is set, with JB_BATCH_PCM_I16
- * as well; a JB_BATCH_PCM_I16 batch without one has no f64 PCM: JB_ERR_INVALID. */
+ * jb_batch_read_pcm reads without an output rate or a loudness target: never normalized).  Readable whenever an
+ * output rate or a loudness target is set, with JB_BATCH_PCM_I16 as well; a JB_BATCH_PCM_I16 batch without either has
+ * no f64 PCM: JB_ERR_INVALID. */
 int jb_batch_read_pcm_native(jb_batch *b, size_t utt, double *dst, size_t cap);
+/* New (the reference's only level control is the fixed `volume` gain).  Loudness normalization ("loudness" below):
+ * target_lufs[0] for every utterance (n == 1) or target_lufs[u] for utterance u (n == jb_batch_size(b)), and one peak
+ * ceiling (dBFS; +INFINITY: none).  A NaN target: the utterance is measured and gets gain 0 dB unless its peak is above
+ * the ceiling.  Only before the batch's first run, and not on a JB_BATCH_MLPG_ONLY batch: JB_ERR_INVALID.  Together
+ * with an output rate, in either order: the measurement is taken at the output rate.  The run measures the output
+ * f64 on the device and writes x * g to a slab of its own, f64 or 16-bit by the flags: jb_batch_read_pcm[_all],
+ * jb_batch_read_pcm_i16[_all], jb_batch_device_pcm and so jb_gather_pcm hand that out (lengths and offsets
+ * unchanged); jb_batch_read_pcm_native does not.  Without a call nothing runs and nothing is allocated.  An output
+ * rate whose hop is outside 1..61439 samples fails at the run with JB_ERR_UNSUPPORTED. */
+int jb_batch_set_loudness_target(jb_batch *b, const double *target_lufs, size_t n, double ceiling_dbfs);
+/* What the last run measured and applied for utterance utt (each pointer may be NULL): L (LUFS, -INFINITY when no
+ * block survives the gates), P (dBFS, -INFINITY for silence) and gain_dB.  Waits for the run like the read entries;
+ * a batch without a target or not yet run: JB_ERR_INVALID. */
+int jb_batch_loudness(jb_batch *b, size_t utt, double *lufs, double *peak_dbfs, double *gain_db);
 void jb_batch_free(jb_batch *b);
 
 /* One-shot convenience: create + run + read + free.  pcm[i] must hold
@@ -372,6 +387,33 @@ int jb_resample_filter(uint32_t in_hz, uint32_t out_hz, uint32_t *L, uint32_t *M
  * (-1 = current). */
 int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t in_hz, uint32_t out_hz,
                           int32_t device, double **out, size_t *n_out);
+
+/* ---- loudness (new: no reference counterpart; ITU-R BS.1770-4 / EBU R128 integrated loudness) -------------------
+ * PCM in the library's 16-bit units (full scale 32768); x = an utterance's output as the read entries hand it out
+ * before any 16-bit conversion (the vocoder's certified f64, or the converter's f64 with an output rate), N samples
+ * at its output rate fs.
+ * 1. K-weighting: y = HP(SHELF(x / 32768)), two biquads (transposed direct form II), each utterance alone from zero
+ *    state.  K = tan(pi fc / fs), a0 = 1 + K/Q + K^2, a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0];
+ *    shelf: fc = 1681.974450955533, Q = 0.7071752369554196, Vh = 10^(3.999843853973347 / 20),
+ *    Vb = Vh^0.4996667741545416, b = [(Vh + Vb K/Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K/Q + K^2) / a0];
+ *    high-pass: fc = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1].
+ * 2. Hop H = (fs + 5) / 10 (integer division); z_j = sum of y^2 over [jH, (j + 1)H); block i (hops i..i+3, counted
+ *    only when (i + 4)H <= N) has l_i = -0.691 + 10 log10((z_i + ... + z_(i+3)) / 4H).
+ * 3. Gates: keep l_i > -70; G = -0.691 + 10 log10(mean of their block mean squares) - 10; keep l_i > G as well;
+ *    L = -0.691 + 10 log10(mean of the block mean squares left); -INFINITY if none is left (or N < 4H).
+ * 4. P = 20 log10(max |x| / 32768) (sample peak; -INFINITY for silence).  gain_dB = min(T - L, C - P) over the terms
+ *    that are finite (0 if neither is), T the target, C the ceiling; output x * 10^(gain_dB / 20), one f64 product
+ *    per sample, then the 16-bit sink's clamp and truncation on a 16-bit batch.  A quiet or silent utterance is never
+ *    amplified past C.  The ceiling bounds the sample peak only: true-peak (oversampled) limiting is not done.
+ * L, P and gain_dB are functions of the utterance's samples alone (not of the batch, its order, the entry or the
+ * devices); the device sums in fixed orders, so JB_BATCH_INVARIANT output stays invariant with a target. */
+/* Host only (no GPU): the coefficients of step 1 at hz, b[6] = b of the shelf then of the high-pass, a[6] likewise
+ * (a[0] = a[3] = 1), and *hop = H; each pointer may be NULL.  hz == 0: JB_ERR_INVALID. */
+int jb_loudness_filter(uint32_t hz, double *b, double *a, uint32_t *hop);
+/* The measurement on PCM the caller holds (jb_resample_pcm_batch's twin): lufs[u] = L and peak_dbfs[u] = P of in[u]
+ * (n_in[u] samples at hz), on `device` (-1 = current).  A hop outside 1..61439 samples: JB_ERR_UNSUPPORTED. */
+int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
+                          double *lufs, double *peak_dbfs);
 
 /* ---- multi-GPU (SURVEY 8b "device_ids[] / n_devices", 8e) ----------------------------------
  * Utterances are independent, so a batch shards over the GPUs of a node with no data-path
@@ -478,6 +520,16 @@ int jb_engine_get_fast_invariant(const jb_engine *e);
  * this resamples.  A pair the converter does not support fails at synthesis with JB_ERR_UNSUPPORTED. */
 int jb_engine_set_output_sampling_frequency(jb_engine *e, size_t hz);
 size_t jb_engine_get_output_sampling_frequency(const jb_engine *e);
+/* New.  Loudness target (LUFS) of the audio the engine's entries return: jb_synthesize, jb_synthesize_batch[_i16],
+ * _each[_i16] (each engine's own target and ceiling for its utterance: they are not among the fields the engines
+ * must agree on), _multi and the generator normalize on the device (jb_batch_set_loudness_target).  NaN (the
+ * default) = off: nothing is measured and the output is unchanged, whatever the ceiling.  jb_engine_new copies both
+ * with the Condition. */
+int jb_engine_set_loudness_target(jb_engine *e, double lufs);
+double jb_engine_get_loudness_target(const jb_engine *e);
+/* New.  Peak ceiling (dBFS) that goes with the loudness target: default 0; +INFINITY = none. */
+int jb_engine_set_peak_ceiling(jb_engine *e, double dbfs);
+double jb_engine_get_peak_ceiling(const jb_engine *e);
 int jb_engine_set_speed(jb_engine *e, double v);
 double jb_engine_get_speed(const jb_engine *e);
 int jb_engine_set_alpha(jb_engine *e, double v);
@@ -588,7 +640,9 @@ size_t jb_generator_total_frames(const jb_generator *g);
  * With an output rate (jb_engine_set_output_sampling_frequency, L/M of the voice's rate): step k writes the output
  * samples [ceil(k F L / M), ceil((k + 1) F L / M)), F = fperiod, and returns their count (at 22.05 kHz from 48 kHz
  * with F = 240: 110 or 111); buf must hold ceil(F L / M) samples, else JB_ERR_BUFFER.  The steps concatenate to
- * jb_synthesize's output at that rate; the first step waits for the whole utterance (no serially served head). */
+ * jb_synthesize's output at that rate; the first step waits for the whole utterance (no serially served head).
+ * With a loudness target (jb_engine_set_loudness_target) the first step waits for the whole utterance as well (the
+ * gain needs every sample), and the steps hand out the normalized output. */
 long jb_generator_step(jb_generator *g, double *buf, size_t buf_len);
 /* Up to max_frames generate_step calls in one: writes n * fperiod samples to buf, n = min(max_frames,
  * frames left, buf_len / fperiod), and returns that sample count (0 when exhausted, JB_ERR_BUFFER if buf

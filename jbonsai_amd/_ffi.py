@@ -163,6 +163,9 @@ SYMBOLS = [
     "jb_batch_create_voc", "jb_batch_create_indexed_voc", "jb_synthesize_batch_each", "jb_synthesize_batch_each_i16",
     "jb_batch_set_output_rate", "jb_batch_output_rate", "jb_batch_read_pcm_native", "jb_resample_filter",
     "jb_resample_pcm_batch", "jb_engine_set_output_sampling_frequency", "jb_engine_get_output_sampling_frequency",
+    "jb_batch_set_loudness_target", "jb_batch_loudness", "jb_loudness_filter", "jb_loudness_pcm_batch",
+    "jb_engine_set_loudness_target", "jb_engine_get_loudness_target", "jb_engine_set_peak_ceiling",
+    "jb_engine_get_peak_ceiling",
 ]
 
 
@@ -280,6 +283,14 @@ def lib():
     L.jb_engine_set_output_sampling_frequency.argtypes = [vp, sz]
     L.jb_engine_get_output_sampling_frequency.argtypes = [vp]
     L.jb_engine_get_output_sampling_frequency.restype = sz
+    L.jb_batch_set_loudness_target.argtypes = [vp, dp, sz, C.c_double]
+    L.jb_batch_loudness.argtypes = [vp, sz, dp, dp, dp]
+    L.jb_loudness_filter.argtypes = [C.c_uint32, dp, dp, C.POINTER(C.c_uint32)]
+    L.jb_loudness_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, C.c_uint32, C.c_int32, dp, dp]
+    for n in ("loudness_target", "peak_ceiling"):
+        getattr(L, "jb_engine_set_" + n).argtypes = [vp, C.c_double]
+        getattr(L, "jb_engine_get_" + n).argtypes = [vp]
+        getattr(L, "jb_engine_get_" + n).restype = C.c_double
     L.jb_write_wav_i16.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     L.jb_write_wav_f64.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     _lib = L
@@ -311,6 +322,33 @@ def resample_filter(in_hz: int, out_hz: int):
     check(L.jb_resample_filter(in_hz, out_hz, C.byref(l_), C.byref(m_), C.byref(nt),
                                taps.ctypes.data_as(C.POINTER(C.c_double)), taps.size))
     return l_.value, m_.value, taps
+
+
+def loudness_filter(hz: int):
+    """The library's K-weighting at hz (include/jbonsai_amd.h jb_loudness_filter; host only): (b, a, hop) with b and a
+    float64 arrays [2][3] (shelf, then high-pass)."""
+    import numpy as np
+
+    b, a, hop = np.zeros(6), np.zeros(6), C.c_uint32()
+    dp = C.POINTER(C.c_double)
+    check(lib().jb_loudness_filter(hz, b.ctypes.data_as(dp), a.ctypes.data_as(dp), C.byref(hop)))
+    return b.reshape(2, 3), a.reshape(2, 3), hop.value
+
+
+def loudness(pcms, hz: int, device: int = -1):
+    """jb_loudness_pcm_batch: (lufs, peak_dbfs) of each float64 array of `pcms` (or of one array) at hz, on the GPU."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
+    n = len(arrs)
+    dp = C.POINTER(C.c_double)
+    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    lufs, peak = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    check(lib().jb_loudness_pcm_batch(ins, nin, n, hz, device, lufs.ctypes.data_as(dp), peak.ctypes.data_as(dp)))
+    res = [(float(lufs[u]), float(peak[u])) for u in range(n)]
+    return res[0] if single else res
 
 
 def resample(pcms, in_hz: int, out_hz: int, device: int = -1):

@@ -364,6 +364,19 @@ class Batch:
         arr = (C.c_uint32 * max(1, len(rates)))(*rates)
         F.check(self._L.jb_batch_set_output_rate(self._h, arr, len(rates)))
 
+    def set_loudness_target(self, target_lufs, ceiling_dbfs=float("inf")):
+        """jb_batch_set_loudness_target: one target (float) for the whole batch or one per utterance (NaN: measured,
+        gain 0 dB unless above the ceiling).  Before the first run only.  The PCM reads then hand out x * gain."""
+        ts = [float(target_lufs)] if np.isscalar(target_lufs) else [float(t) for t in target_lufs]
+        arr = (C.c_double * max(1, len(ts)))(*ts)
+        F.check(self._L.jb_batch_set_loudness_target(self._h, arr, len(ts), float(ceiling_dbfs)))
+
+    def loudness(self, i):
+        """(lufs, peak_dbfs, gain_db) the last run measured and applied for utterance i (jb_batch_loudness)."""
+        v = [C.c_double(), C.c_double(), C.c_double()]
+        F.check(self._L.jb_batch_loudness(self._h, i, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def output_rate(self, i) -> int:
         """Rate of utterance i's PCM as the read entries hand it out (the voice's rate when native)."""
         return self._L.jb_batch_output_rate(self._h, i)

@@ -1660,13 +1660,16 @@ int Batch::run(bool timed)
     hipStreamWaitEvent(stream, ev_voc_done, 0);
     last_run_timed = timed;
     has_run = true;
+    int rc = prepare_loudness();
+    if (rc)
+        return rc;
     for (int si = 0; si < kMaxStream; si++)
         if (sd[si].gv_gang_ctl && !from_tracks)
             gang_check_pending = true;
     const bool inject_timeout = (flags & JB_BATCH_TEST_GANG_TIMEOUT) && gang_check_pending && gang_fallbacks == 0;
     if (timed)
         hipEventRecord(ev0, stream);
-    int rc = enqueue_paramgen();
+    rc = enqueue_paramgen();
     if (rc)
         return rc;
     if (inject_timeout) // test aid: as if the resident GV kernel had given up in formation
@@ -1699,6 +1702,10 @@ int Batch::run(bool timed)
     // behind the check: a batch whose hand-offs all pass pays no host round trip for its output rate (finish_verify
     // converts again what a redo round rewrites)
     if ((rc = enqueue_resample()))
+        return rc;
+    // loudness: measured on the output f64 and applied behind the converter (finish_verify does both again for what
+    // a redo round rewrites)
+    if ((rc = enqueue_loudness()))
         return rc;
     if (timed)
         hipEventRecord(ev3, stream_voc);
@@ -1972,8 +1979,160 @@ int Batch::finish_verify()
         }
     }
     // output rate: what run() converted behind the check came in part from PCM these rounds replaced
-    return enqueue_resample(&touched);
+    rc = enqueue_resample(&touched);
+    if (rc)
+        return rc;
+    // loudness: the gain is a function of the final PCM
+    return enqueue_loudness(&touched);
 }
+
+// ---- loudness target (jb_batch_set_loudness_target) ----
+int Batch::set_loudness(const double *target, const double *ceiling, size_t n)
+{
+    if (flags & JB_BATCH_MLPG_ONLY) {
+        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_INVALID;
+    }
+    if (has_run) {
+        set_error("jb_batch_set_loudness_target: the target is set before the batch's first run");
+        return JB_ERR_INVALID;
+    }
+    if (!target || !ceiling || (n != 1 && n != (size_t)B)) {
+        set_error("jb_batch_set_loudness_target: give one target, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    ln_target.assign((size_t)B, 0.0);
+    ln_ceiling.assign((size_t)B, 0.0);
+    for (size_t u = 0; u < (size_t)B; u++) {
+        ln_target[u] = target[n == 1 ? 0 : u];
+        ln_ceiling[u] = ceiling[n == 1 ? 0 : u];
+    }
+    ln_on = true;
+    return JB_OK;
+}
+
+// At the first run, when the output rate is settled: the f64 the measurement reads (the vocoder's or the
+// converter's, made f64 where the flags asked for 16 bits), the output slab, the per-rate tables and the lists
+int Batch::prepare_loudness()
+{
+    if (!ln_on || ln_ready)
+        return JB_OK;
+    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0;
+    int rc;
+    hipError_t e;
+    const double *src = nullptr;
+    if (rs_on) {
+        if (i16) {
+            // the converter writes f64 for the measurement; the apply pass writes the 16-bit slab it wrote before
+            if ((rc = dalloc(&ln_src64, std::max<size_t>(out_total(), 1), false)))
+                return rc;
+            for (size_t u = 0; u < (size_t)B; u++)
+                for (uint32_t t = rs_tile_lo[u]; t < rs_tile_lo[u + 1]; t++)
+                    rs_tiles[t].y = ln_src64 + rs_off[u];
+            if (!rs_tiles.empty() && (e = hipMemcpy(rs_tiles_dev, rs_tiles.data(), sizeof(ResampleTile) * rs_tiles.size(),
+                                                    hipMemcpyHostToDevice)) != hipSuccess)
+                return hip_fail(e, "resample work list");
+            src = ln_src64;
+            ln_pcm16 = rs_pcm16;
+        } else {
+            src = rs_pcm;
+        }
+    } else if (i16) {
+        // the vocoder writes f64 for the measurement; the apply pass writes the batch's 16-bit slab
+        if ((rc = dalloc(&ln_src64, std::max<size_t>(total_samples, 1), false)))
+            return rc;
+        ln_pcm16 = vd.pcm16;
+        vd.pcm = ln_src64;
+        vd.pcm16 = nullptr;
+        src = ln_src64;
+    } else {
+        src = vd.pcm;
+    }
+    if (!i16 && (rc = dalloc(&ln_pcm, std::max<size_t>(out_total(), 1), false)))
+        return rc;
+    std::vector<LoudnessRate> rates;
+    ln_utts.assign((size_t)B, LoudnessUtt{});
+    uint64_t tiles = 0, atiles = 0;
+    for (size_t u = 0; u < (size_t)B; u++) {
+        const uint32_t hz = (rs_on && out_hz[u]) ? out_hz[u] : voice.sampling_frequency;
+        size_t r = 0;
+        while (r < rates.size() && rates[r].hz != hz)
+            r++;
+        if (r == rates.size()) {
+            LoudnessRate lr{};
+            if ((rc = loudness_rate(hz, &lr)))
+                return rc;
+            rates.push_back(lr);
+        }
+        LoudnessUtt &w = ln_utts[u];
+        const size_t off = out_offset(u);
+        w.x = src + off;
+        w.y = i16 ? (void *)(ln_pcm16 + off) : (void *)(ln_pcm + off);
+        w.n = out_samples(u);
+        w.ntiles = loudness_tiles(rates[r], w.n);
+        w.tile0 = w.lt0 = tiles;
+        w.at0 = atiles;
+        w.rate = (uint32_t)r;
+        w.slot = (uint32_t)u;
+        w.target = ln_target[u];
+        w.ceiling = ln_ceiling[u];
+        tiles += w.ntiles;
+        atiles += (w.n + kLnApplyTile - 1) / kLnApplyTile;
+    }
+    if ((rc = dalloc(&ln_rates_dev, rates.size(), false)) || (rc = dalloc(&ln_utts_dev, (size_t)B, false)) ||
+        (rc = dalloc(&ln_redo_dev, (size_t)B, false)) || (rc = dalloc(&ln_st, 4 * std::max<uint64_t>(tiles, 1), false)) ||
+        (rc = dalloc(&ln_pk, std::max<uint64_t>(tiles, 1), false)) ||
+        (rc = dalloc(&ln_z, std::max<uint64_t>(tiles, 1), false)) || (rc = dalloc(&ln_res, (size_t)B, false)))
+        return rc;
+    if ((e = hipMemcpy(ln_rates_dev, rates.data(), sizeof(LoudnessRate) * rates.size(), hipMemcpyHostToDevice)) !=
+            hipSuccess ||
+        (B > 0 && (e = hipMemcpy(ln_utts_dev, ln_utts.data(), sizeof(LoudnessUtt) * (size_t)B, hipMemcpyHostToDevice)) !=
+                      hipSuccess))
+        return hip_fail(e, "loudness work list");
+    ln_tiles = tiles;
+    ln_atiles = atiles;
+    ln_ready = true;
+    return JB_OK;
+}
+
+int Batch::enqueue_loudness(const std::vector<uint8_t> *only)
+{
+    if (!ln_on || !ln_ready)
+        return JB_OK;
+    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0;
+    hipError_t e;
+    if (!only) {
+        if ((e = launch_loudness_measure(ln_rates_dev, ln_utts_dev, (uint32_t)B, ln_tiles, ln_st, ln_pk, ln_z, ln_res,
+                                         stream_voc)) != hipSuccess ||
+            (e = launch_loudness_apply(ln_utts_dev, (uint32_t)B, ln_atiles, ln_res, i16, stream_voc)) != hipSuccess)
+            return hip_fail(e, "loudness");
+        return JB_OK;
+    }
+    // the utterances a redo touched, renumbered (their scratch stays where it is)
+    std::vector<LoudnessUtt> sub;
+    uint64_t tiles = 0, atiles = 0;
+    for (size_t u = 0; u < (size_t)B; u++)
+        if ((*only)[u]) {
+            LoudnessUtt w = ln_utts[u];
+            w.lt0 = tiles;
+            w.at0 = atiles;
+            tiles += w.ntiles;
+            atiles += (w.n + kLnApplyTile - 1) / kLnApplyTile;
+            sub.push_back(w);
+        }
+    if (sub.empty())
+        return JB_OK;
+    if ((e = hipMemcpy(ln_redo_dev, sub.data(), sizeof(LoudnessUtt) * sub.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = launch_loudness_measure(ln_rates_dev, ln_redo_dev, (uint32_t)sub.size(), tiles, ln_st, ln_pk, ln_z, ln_res,
+                                     stream_voc)) != hipSuccess ||
+        (e = launch_loudness_apply(ln_redo_dev, (uint32_t)sub.size(), atiles, ln_res, i16, stream_voc)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
+        return hip_fail(e, "loudness(redo)");
+    return JB_OK;
+}
+
+const double *Batch::out_pcm64() const { return ln_on ? ln_pcm : rs_on ? rs_pcm : vd.pcm; }
+const int16_t *Batch::out_pcm16() const { return ln_on ? ln_pcm16 : rs_on ? rs_pcm16 : vd.pcm16; }
 
 // ---- output rate (jb_batch_set_output_rate) ----
 int Batch::set_output_rate(const uint32_t *hz, size_t n)
@@ -2103,7 +2262,8 @@ int Batch::enqueue_resample(const std::vector<uint8_t> *only)
 {
     if (!rs_on)
         return JB_OK;
-    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0;
+    // (with a loudness target the converter writes f64 for the measurement, and the apply pass the 16 bits)
+    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0 && !ln_on;
     hipError_t e;
     if (!only) {
         if ((e = launch_resample(rs_tables_dev, rs_tiles_dev, (uint32_t)rs_tiles.size(), i16, rs_lds, stream_voc)) !=
@@ -2289,8 +2449,7 @@ int stage_ring(int device, StageRing **out)
 
 int Batch::read_pcm_split(void *const *dst, size_t elem)
 {
-    const char *slab = rs_on ? (elem == 2 ? (const char *)rs_pcm16 : (const char *)rs_pcm)
-                             : (elem == 2 ? (const char *)vd.pcm16 : (const char *)vd.pcm);
+    const char *slab = elem == 2 ? (const char *)out_pcm16() : (const char *)out_pcm64();
     if (flags & JB_BATCH_MLPG_ONLY) {
         set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
@@ -2613,6 +2772,36 @@ uint32_t jb_batch_output_rate(const jb_batch *hb, size_t i)
     return (b->rs_on && b->out_hz[i]) ? b->out_hz[i] : b->voice.sampling_frequency;
 }
 
+int jb_batch_set_loudness_target(jb_batch *hb, const double *target_lufs, size_t n, double ceiling_dbfs)
+{
+    if (!hb)
+        return JB_ERR_INVALID;
+    std::vector<double> ceil(n ? n : 1, ceiling_dbfs);
+    return ((Batch *)hb)->set_loudness(target_lufs, ceil.data(), n);
+}
+
+int jb_batch_loudness(jb_batch *hb, size_t utt, double *lufs, double *peak_dbfs, double *gain_db)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    if (!b->ln_on || !b->ln_ready) {
+        jb::set_error(b->ln_on ? "jb_batch_loudness: the batch has not run" : "jb_batch_loudness: no loudness target is set");
+        return JB_ERR_INVALID;
+    }
+    jb::LoudnessResult r{};
+    int rc = b->read(b->ln_res + utt, &r, sizeof r);
+    if (rc)
+        return rc;
+    if (lufs)
+        *lufs = r.lufs;
+    if (peak_dbfs)
+        *peak_dbfs = r.peak_dbfs;
+    if (gain_db)
+        *gain_db = r.gain_db;
+    return JB_OK;
+}
+
 int jb_batch_read_pcm_native(jb_batch *hb, size_t i, double *dst, size_t cap)
 {
     Batch *b = (Batch *)hb;
@@ -2623,7 +2812,7 @@ int jb_batch_read_pcm_native(jb_batch *hb, size_t i, double *dst, size_t cap)
         return JB_ERR_INVALID;
     }
     if (!b->vd.pcm) {
-        jb::set_error("a JB_BATCH_PCM_I16 batch without an output rate has no f64 PCM");
+        jb::set_error("a JB_BATCH_PCM_I16 batch without an output rate or a loudness target has no f64 PCM");
         return JB_ERR_INVALID;
     }
     const size_t ns = (size_t)b->T[i] * b->voice.fperiod;
@@ -2646,8 +2835,8 @@ void *jb_batch_device_pcm(jb_batch *hb, size_t *n)
         *n = b->out_total();
     if ((b->flags & JB_BATCH_MLPG_ONLY) || b->sync()) // the slab is handed out finished and certified
         return nullptr;
-    if (b->rs_on) // output rate: the converted slab
-        return b->rs_pcm ? (void *)b->rs_pcm : (void *)b->rs_pcm16;
+    if (b->ln_on || b->rs_on) // loudness target / output rate: the slab the read entries hand out
+        return b->out_pcm64() ? (void *)b->out_pcm64() : (void *)b->out_pcm16();
     return b->vd.pcm ? (void *)b->vd.pcm : (void *)b->vd.pcm16; // i16 slab for JB_BATCH_PCM_I16 batches
 }
 
@@ -2669,7 +2858,7 @@ int jb_batch_read_pcm(jb_batch *hb, size_t i, double *dst, size_t cap)
         return JB_OK;
     if (!dst)
         return JB_ERR_INVALID;
-    const double *slab = b->rs_on ? b->rs_pcm : b->vd.pcm;
+    const double *slab = b->out_pcm64();
     if (!slab) {
         jb::set_error("batch was created with JB_BATCH_PCM_I16: use jb_batch_read_pcm_i16");
         return JB_ERR_INVALID;
@@ -2686,7 +2875,7 @@ int jb_batch_read_pcm_i16(jb_batch *hb, size_t i, int16_t *dst, size_t cap)
         jb::set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
     }
-    const int16_t *slab = b->rs_on ? b->rs_pcm16 : b->vd.pcm16;
+    const int16_t *slab = b->out_pcm16();
     if (!slab) {
         jb::set_error("batch was created without JB_BATCH_PCM_I16");
         return JB_ERR_INVALID;

@@ -46,6 +46,8 @@ struct Condition {
         return (batch_invariant ? (JB_BATCH_SERIAL | JB_BATCH_SERIAL_GV) : 0u) | (fast_invariant ? JB_BATCH_INVARIANT : 0u);
     }
     size_t output_rate = 0;       // jb_engine_set_output_sampling_frequency: 0 = the voice's rate
+    double loudness_target = NAN; // jb_engine_set_loudness_target: NaN = off
+    double peak_ceiling = 0.0;    // jb_engine_set_peak_ceiling (dBFS), with a target only
     double speed = 1.0;
     size_t stage = 0;
     bool use_log_gain = false;
@@ -765,6 +767,22 @@ int jb_engine_set_output_sampling_frequency(jb_engine *e, size_t hz)
     return JB_OK;
 }
 size_t jb_engine_get_output_sampling_frequency(const jb_engine *e) { return e ? CENG(e)->cond.output_rate : 0; }
+int jb_engine_set_loudness_target(jb_engine *e, double lufs)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    ENG(e)->cond.loudness_target = lufs;
+    return JB_OK;
+}
+double jb_engine_get_loudness_target(const jb_engine *e) { return e ? CENG(e)->cond.loudness_target : NAN; }
+int jb_engine_set_peak_ceiling(jb_engine *e, double dbfs)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    ENG(e)->cond.peak_ceiling = dbfs;
+    return JB_OK;
+}
+double jb_engine_get_peak_ceiling(const jb_engine *e) { return e ? CENG(e)->cond.peak_ceiling : NAN; }
 int jb_engine_set_speed(jb_engine *e, double v)
 {
     ENG(e)->cond.speed = std::max(v, 1.0E-06);
@@ -1117,6 +1135,18 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         }
         if (any_rate && (rc = b->set_output_rate(rates.data(), rates.size())))
             return rc;
+        // loudness: each utterance's engine's own target and ceiling; an engine without a target leaves its
+        // utterance as it is (measured, gain 0 dB: bit for bit the same) when another engine of the batch has one
+        std::vector<double> targets(hi - lo), ceilings(hi - lo);
+        bool any_target = false;
+        for (size_t u = lo; u < hi; u++) {
+            const bool on = !std::isnan(eng(u)->cond.loudness_target);
+            targets[u - lo] = on ? eng(u)->cond.loudness_target : NAN;
+            ceilings[u - lo] = on ? eng(u)->cond.peak_ceiling : INFINITY;
+            any_target = any_target || on;
+        }
+        if (any_target && (rc = b->set_loudness(targets.data(), ceilings.data(), targets.size())))
+            return rc;
         rc = b->run(false);
         t_create += ms(t0, now());
         return rc;
@@ -1366,10 +1396,16 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
         if (rc)
             return rc;
     }
+    if (!std::isnan(CENG(e)->cond.loudness_target)) {
+        const double t = CENG(e)->cond.loudness_target, c = CENG(e)->cond.peak_ceiling;
+        if ((rc = b->set_loudness(&t, &c, 1)))
+            return rc;
+    }
     // Engine::generator runs all three MLPGs before returning (src/engine.rs:333-357); here they are
     // enqueued, with the vocoder behind them, and the call returns while the device works
     // (no serially served head with an output rate either: the converted samples of a frame need its successors)
-    if ((!b->invariant && !b->rs_on && (rc = b->build_generator_work())) || (rc = b->run(false)))
+    // (nor with a loudness target: the gain needs every sample)
+    if ((!b->invariant && !b->rs_on && !b->ln_on && (rc = b->build_generator_work())) || (rc = b->run(false)))
         return rc;
     *out = (jb_generator *)g.release();
     return JB_OK;
@@ -1423,7 +1459,7 @@ static int generator_finish(jb::Generator *g)
     return JB_OK;
 }
 
-// Output rate: the converted utterance, read whole by the first step, handed out by the steps' ceil rule
+// Output rate / loudness target: the converted (normalized) utterance, read whole by the first step, handed out by the steps' ceil rule
 static long generator_out(jb::Generator *g, double *buf, size_t buf_len, size_t max_frames)
 {
     if (buf_len < g->out_step_max() || !buf) {
@@ -1438,7 +1474,7 @@ static long generator_out(jb::Generator *g, double *buf, size_t buf_len, size_t 
         return rc;
     if (g->cache.empty() && b->out_samples(0)) {
         g->cache.resize(b->out_samples(0));
-        if ((rc = b->read(b->rs_pcm + b->out_offset(0), g->cache.data(), g->cache.size() * sizeof(double), false)))
+        if ((rc = b->read(b->out_pcm64() + b->out_offset(0), g->cache.data(), g->cache.size() * sizeof(double), false)))
             return rc;
     }
     const size_t lo = g->out_start(g->next);
@@ -1459,7 +1495,7 @@ long jb_generator_step(jb_generator *hg, double *buf, size_t buf_len)
         return JB_ERR_INVALID;
     if (g->total <= g->next)
         return 0;
-    if (g->batch->rs_on)
+    if (g->batch->rs_on || g->batch->ln_on)
         return generator_out(g, buf, buf_len, 1);
     if (buf_len < g->fperiod || !buf) {
         set_error("The length of speech buffer must be larger than fperiod.");
@@ -1530,7 +1566,7 @@ long jb_generator_step_n(jb_generator *hg, double *buf, size_t buf_len, size_t m
         return JB_ERR_INVALID;
     if (g->total <= g->next || max_frames == 0)
         return 0;
-    if (g->batch->rs_on)
+    if (g->batch->rs_on || g->batch->ln_on)
         return generator_out(g, buf, buf_len, max_frames);
     if (buf_len < g->fperiod || !buf) {
         set_error("The length of speech buffer must be larger than fperiod.");

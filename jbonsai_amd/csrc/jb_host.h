@@ -74,6 +74,42 @@ void resample_tiles(const ResampleTable &t, uint32_t table, const double *x, uin
 hipError_t launch_resample(const ResampleTable *tables_dev, const ResampleTile *tiles_dev, uint32_t n_tiles, bool i16,
                            size_t lds_bytes, hipStream_t stream);
 
+// Loudness normalization (jb_loudness.hip): BS.1770-4 K-weighting, measured per utterance in tiles of at most
+// 256 segments of S samples; tiles never cross a hop (H samples), a hop has tph of them
+constexpr uint32_t kLnLanes = 256;
+struct LoudnessRate {
+    double b[6], a[6];     // stage 1 (shelf) then stage 2 (high-pass): b0 b1 b2 / 1 a1 a2
+    double P[8][16];       // A^(S 2^k), k = 0..7: the state transition over 2^k segments (4x4, row-major)
+    double Pt[16], Pr[16]; // A^G (a hop's tiles but its last), A^(H - (tph - 1) G) (a hop's last tile)
+    double Ph[16];         // A^H (a hop)
+    uint32_t hz, H, S, G, tph, pad_;
+};
+// One utterance of a loudness launch.  Launch lists are in utterance order; lt0 / at0 are prefix sums over the
+// list (measure tiles / apply tiles), tile0 the utterance's place in the per-tile scratch (fixed per batch)
+struct LoudnessUtt {
+    const double *x; // f64 PCM measured
+    void *y;         // output (f64 or i16, by the launch); null: measure only
+    uint64_t n, tile0, lt0, at0;
+    uint32_t ntiles, rate, slot, pad_;
+    double target, ceiling;
+};
+struct LoudnessResult {
+    double lufs, peak_dbfs, gain_db, g;
+};
+constexpr uint32_t kLnApplyTile = 8192; // samples per workgroup of the apply pass
+// K-weighting coefficients and the hop of `hz`; JB_ERR_INVALID for hz == 0
+int loudness_filter(uint32_t hz, double b[6], double a[6], uint32_t *hop);
+// The device table of one rate (host-built); JB_ERR_UNSUPPORTED where the tiling does not reach (H == 0, H > 61439)
+int loudness_rate(uint32_t hz, LoudnessRate *out);
+uint32_t loudness_tiles(const LoudnessRate &r, uint64_t n); // measure tiles of an utterance of n samples
+// measure: utts_dev[0..n) of total tiles; st: 4 doubles per tile, pk / z: one; res[slot] of each utterance
+hipError_t launch_loudness_measure(const LoudnessRate *rates_dev, const LoudnessUtt *utts_dev, uint32_t n,
+                                   uint64_t tiles, double *st, double *pk, double *z, LoudnessResult *res,
+                                   hipStream_t stream);
+// y = x * res[slot].g for every utterance of the list (apply tiles in all)
+hipError_t launch_loudness_apply(const LoudnessUtt *utts_dev, uint32_t n, uint64_t atiles, const LoudnessResult *res,
+                                 bool i16, hipStream_t stream);
+
 // Device-resident pdf tables of a voice set (jb_pdf_set) and an indexed batch source
 struct PdfSet {
     int device = -1;
@@ -218,6 +254,26 @@ struct Batch {
     size_t out_samples(size_t u) const;  // what the PCM read entries hand out for utterance u
     size_t out_offset(size_t u) const;   // ... and where it starts in the slab they read
     size_t out_total() const;
+    // Loudness target (jb_batch_set_loudness_target).  ln_on: the run measures the output f64 (vd.pcm, or the
+    // converter's f64 with an output rate: both written whatever the flags) and writes x * g to a slab of its own
+    // (ln_pcm, or the batch's 16-bit slab), which every PCM read entry but jb_batch_read_pcm_native reads
+    bool ln_on = false, ln_ready = false;
+    std::vector<double> ln_target, ln_ceiling; // [B]
+    double *ln_pcm = nullptr;        // f64 output
+    int16_t *ln_pcm16 = nullptr;     // 16-bit output (the slab the read entries would hand out without a target)
+    double *ln_src64 = nullptr;      // f64 the measurement reads where the flags asked for 16 bits
+    std::vector<LoudnessUtt> ln_utts;
+    LoudnessUtt *ln_utts_dev = nullptr, *ln_redo_dev = nullptr;
+    LoudnessRate *ln_rates_dev = nullptr;
+    double *ln_st = nullptr, *ln_pk = nullptr, *ln_z = nullptr;
+    LoudnessResult *ln_res = nullptr;
+    uint64_t ln_tiles = 0, ln_atiles = 0;
+    // target / ceiling: n == 1 or B entries each
+    int set_loudness(const double *target, const double *ceiling, size_t n);
+    int prepare_loudness(); // at the first run: slabs, lists, tables
+    int enqueue_loudness(const std::vector<uint8_t> *only = nullptr); // only: as enqueue_resample's
+    const double *out_pcm64() const;
+    const int16_t *out_pcm16() const;
     bool last_run_timed = false;
     uint32_t gang_fallbacks = 0;     // times the resident GV kernel timed out in formation and the sweeps took over
     static int create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n,

@@ -1,0 +1,683 @@
+// Loudness normalization of synthesized PCM (new surface: the reference's only level control is the fixed
+// `volume` gain).  The definition is in include/jbonsai_amd.h ("loudness"); in short: K-weighting (two biquads,
+// BS.1770-4) of x / 32768 from zero state per utterance, hop sums z_j of y^2 over [jH, (j+1)H), H = (fs + 5) / 10,
+// four-hop gating blocks, the -70 LUFS absolute and the -10 LU relative gate, the sample peak, and
+// gain_dB = min(T - L, C - P) over the finite terms.
+//
+// The filter is linear and time-invariant, so a recursion cut into pieces is exact up to rounding: a piece filtered
+// from zero state ends in e, and the state s at its start carries over as s -> A^len s + e (A: the 4x4 transition of
+// one sample with x = 0, len: the piece's length).  Four kernels measure, one applies:
+//   k_ln_tiles<false>  one workgroup per tile (<= 256 segments of S <= 16 samples, inside one hop): the tile is staged
+//                      through LDS with coalesced loads (the sample peak on the way), every lane filters its segment
+//                      from zero, a Hillis-Steele scan of the affine maps across the 256 lanes (matrices A^(S 2^k),
+//                      wave-uniform) gives each segment's start state for a zero tile start, and the last lane
+//                      filters its segment again: the tile's zero-state end state.
+//   k_ln_scan          one wave per utterance: tiles fold into hops (A^G, A^r), hops into 64 lane chunks (A^H), a
+//                      shuffle scan across the lanes (powers of A^(H c)), then each lane walks its chunk again and
+//                      leaves every tile's true start state where its end state was.
+//   k_ln_tiles<true>   the tile again, the same zero-state pass and scan, now from the tile's true start state;
+//                      every lane filters its segment from its start state and sums y^2; a fixed tree gives the
+//                      tile's share of its hop's z (tiles of the tail hop, in no block, are skipped).
+//   k_ln_gate          one workgroup per utterance: z_j, the blocks, both gates, L, P and the gain, every sum in a
+//                      fixed order over a fixed thread count.
+//   k_ln_apply         y = x * g, f64 or the 16-bit sink's rule (clamp, then truncate).
+// Each sample is read from HBM twice to measure (both tile passes) and once to apply.  Every result is a function of
+// the utterance's samples and rate alone: the tiling depends on nothing else (the fast invariant mode stays
+// invariant).
+#include "jb_host.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace jb {
+
+namespace {
+constexpr uint32_t kLnMaxS = 16; // samples per segment at most (tiles of at most 4096 samples)
+constexpr uint32_t kLnMaxHop = 61439; // tph = ceil(H / 4096) <= 15: the hop's last tile is never empty
+using M4 = double[16];
+
+// One sample through both stages (transposed direct form II); c: b0 b1 b2 a1 a2 of stage 1, then of stage 2
+inline double host_step(const double *c, double *s, double x)
+{
+    const double w = std::fma(c[0], x, s[0]);
+    s[0] = std::fma(c[1], x, std::fma(-c[3], w, s[1]));
+    s[1] = std::fma(c[2], x, -c[4] * w);
+    const double y = std::fma(c[5], w, s[2]);
+    s[2] = std::fma(c[6], w, std::fma(-c[8], y, s[3]));
+    s[3] = std::fma(c[7], w, -c[9] * y);
+    return y;
+}
+
+void mat_mul(const double *a, const double *b, double *out)
+{
+    double t[16];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double acc = 0.0;
+            for (int k = 0; k < 4; k++)
+                acc += a[i * 4 + k] * b[k * 4 + j];
+            t[i * 4 + j] = acc;
+        }
+    std::copy(t, t + 16, out);
+}
+
+void mat_pow(const double *a, uint64_t n, double *out)
+{
+    double r[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, p[16];
+    std::copy(a, a + 16, p);
+    for (; n; n >>= 1) {
+        if (n & 1)
+            mat_mul(r, p, r);
+        mat_mul(p, p, p);
+    }
+    std::copy(r, r + 16, out);
+}
+} // namespace
+
+int loudness_filter(uint32_t hz, double b[6], double a[6], uint32_t *hop)
+{
+    if (hz == 0) {
+        set_error("loudness: a rate of 0 Hz");
+        return JB_ERR_INVALID;
+    }
+    const double fs = (double)hz;
+    auto stage = [&](double fc, double Q, double *bb, double *aa, bool shelf) {
+        const double K = std::tan(M_PI * fc / fs);
+        const double a0 = 1.0 + K / Q + K * K;
+        if (shelf) {
+            const double Vh = std::pow(10.0, 3.999843853973347 / 20.0);
+            const double Vb = std::pow(Vh, 0.4996667741545416);
+            bb[0] = (Vh + Vb * K / Q + K * K) / a0;
+            bb[1] = 2.0 * (K * K - Vh) / a0;
+            bb[2] = (Vh - Vb * K / Q + K * K) / a0;
+        } else {
+            bb[0] = 1.0;
+            bb[1] = -2.0;
+            bb[2] = 1.0;
+        }
+        aa[0] = 1.0;
+        aa[1] = 2.0 * (K * K - 1.0) / a0;
+        aa[2] = (1.0 - K / Q + K * K) / a0;
+    };
+    double bb[6], aa[6];
+    stage(1681.974450955533, 0.7071752369554196, bb, aa, true);
+    stage(38.13547087602444, 0.5003270373238773, bb + 3, aa + 3, false);
+    if (b)
+        std::copy(bb, bb + 6, b);
+    if (a)
+        std::copy(aa, aa + 6, a);
+    if (hop)
+        *hop = (hz + 5) / 10;
+    return JB_OK;
+}
+
+int loudness_rate(uint32_t hz, LoudnessRate *out)
+{
+    LoudnessRate r{};
+    uint32_t H = 0;
+    int rc = loudness_filter(hz, r.b, r.a, &H);
+    if (rc)
+        return rc;
+    if (H == 0 || H > kLnMaxHop) {
+        set_error("loudness: " + std::to_string(hz) + " Hz gives a hop of " + std::to_string(H) +
+                  " samples (1.." + std::to_string(kLnMaxHop) + " are measured)");
+        return JB_ERR_UNSUPPORTED;
+    }
+    r.hz = hz;
+    r.H = H;
+    r.tph = (H + 4095) / 4096;
+    r.S = (H + kLnLanes * r.tph - 1) / (kLnLanes * r.tph);
+    r.G = kLnLanes * r.S;
+    const uint64_t last = (uint64_t)H - (uint64_t)(r.tph - 1) * r.G;
+    if (r.S > kLnMaxS || (uint64_t)(r.tph - 1) * r.G >= H || last > r.G) {
+        set_error("loudness: no tiling for a hop of " + std::to_string(H));
+        return JB_ERR_UNSUPPORTED;
+    }
+    // A: one sample with x = 0, column j from the unit state e_j -- the device's recursion, term for term
+    const double c[10] = {r.b[0], r.b[1], r.b[2], r.a[1], r.a[2], r.b[3], r.b[4], r.b[5], r.a[4], r.a[5]};
+    double A[16];
+    for (int j = 0; j < 4; j++) {
+        double s[4] = {0, 0, 0, 0};
+        s[j] = 1.0;
+        host_step(c, s, 0.0);
+        for (int i = 0; i < 4; i++)
+            A[i * 4 + j] = s[i];
+    }
+    for (int k = 0; k < 8; k++)
+        mat_pow(A, (uint64_t)r.S << k, r.P[k]);
+    mat_pow(A, r.G, r.Pt);
+    mat_pow(A, last, r.Pr);
+    mat_pow(A, H, r.Ph);
+    *out = r;
+    return JB_OK;
+}
+
+uint32_t loudness_tiles(const LoudnessRate &r, uint64_t n)
+{
+    if (n == 0)
+        return 0;
+    const uint64_t nh = (n + r.H - 1) / r.H;   // hops, the tail's included
+    const uint64_t rem = n - (nh - 1) * r.H;   // samples of the last hop, 1..H
+    return (uint32_t)((nh - 1) * r.tph + (rem + r.G - 1) / r.G);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) double cdouble;
+
+__device__ __forceinline__ double ln_step(const double *c, double *s, double x)
+{
+    const double w = __builtin_fma(c[0], x, s[0]);
+    s[0] = __builtin_fma(c[1], x, __builtin_fma(-c[3], w, s[1]));
+    s[1] = __builtin_fma(c[2], x, -c[4] * w);
+    const double y = __builtin_fma(c[5], w, s[2]);
+    s[2] = __builtin_fma(c[6], w, __builtin_fma(-c[8], y, s[3]));
+    s[3] = __builtin_fma(c[7], w, -c[9] * y);
+    return y;
+}
+
+// v += P w (P wave-uniform: scalar operands)
+__device__ __forceinline__ void ln_mv_add(cdouble *P, const double *w, double *v)
+{
+    for (int i = 0; i < 4; i++) {
+        double acc = v[i];
+        for (int k = 0; k < 4; k++)
+            acc = __builtin_fma(P[i * 4 + k], w[k], acc);
+        v[i] = acc;
+    }
+}
+
+// largest u with utts[u].lt0 (kApply: at0) <= idx; utterances without tiles share their successor's prefix
+template <bool kApply>
+__device__ __forceinline__ uint32_t ln_find(const LoudnessUtt *utts, uint32_t n, uint64_t idx)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((kApply ? utts[mid].at0 : utts[mid].lt0) <= idx)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void ln_coefs(const LoudnessRate *R, double *c)
+{
+    cdouble *b = (cdouble *)R->b, *a = (cdouble *)R->a;
+    c[0] = b[0], c[1] = b[1], c[2] = b[2], c[3] = a[1], c[4] = a[2];
+    c[5] = b[3], c[6] = b[4], c[7] = b[5], c[8] = a[4], c[9] = a[5];
+}
+
+template <bool kZ>
+__global__ __launch_bounds__(kLnLanes) void k_ln_tiles(const LoudnessRate *__restrict__ rates,
+                                                       const LoudnessUtt *__restrict__ utts, uint32_t n_utts,
+                                                       double *__restrict__ st, double *__restrict__ pk,
+                                                       double *__restrict__ z)
+{
+    __shared__ double xs[kLnLanes * (kLnMaxS + 1)]; // lane l's segment at l * (S | 1): odd strides, no bank conflict
+    __shared__ double sc[kLnLanes * 4];
+    __shared__ double red[kLnLanes];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t u = ln_find<false>(utts, n_utts, blockIdx.x);
+    const LoudnessUtt U = utts[u];
+    const LoudnessRate *R = rates + U.rate;
+    const uint32_t H = R->H, S = R->S, G = R->G, tph = R->tph;
+    const uint64_t t = blockIdx.x - U.lt0;
+    const uint64_t j = t / tph;
+    const uint32_t k = (uint32_t)(t % tph);
+    const uint64_t start = j * H + (uint64_t)k * G;
+    if (t >= U.ntiles || start >= U.n)
+        return;
+    if (kZ && (j + 1) * (uint64_t)H > U.n) // the tail hop: in no gating block
+        return;
+    const uint32_t len = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(G, H - k * G), U.n - start);
+    const uint32_t Sp = S | 1u;
+    const double *x = U.x + start;
+    // stage: element e to slot (e / S) * Sp + e % S, quotient and remainder carried along.  All of a thread's loads
+    // (len <= 256 S: at most kLnMaxS) are issued before the first store, so they are in flight together
+    double peak = 0.0;
+    {
+        double xv[kLnMaxS];
+#pragma unroll
+        for (uint32_t i = 0; i < kLnMaxS; i++) {
+            const uint32_t e = tid + i * kLnLanes;
+            xv[i] = e < len ? x[e] : 0.0;
+        }
+        uint32_t q = tid / S, r = tid % S;
+        const uint32_t dq = kLnLanes / S, dr = kLnLanes % S;
+#pragma unroll
+        for (uint32_t i = 0; i < kLnMaxS; i++) {
+            const uint32_t e = tid + i * kLnLanes;
+            if (e >= len)
+                break;
+            const double v = xv[i];
+            xs[q * Sp + r] = v;
+            peak = fmax(peak, fabs(v));
+            q += dq;
+            r += dr;
+            if (r >= S) {
+                r -= S;
+                q++;
+            }
+        }
+    }
+    __syncthreads();
+    double c[10];
+    ln_coefs(R, c);
+    const double inv = 1.0 / 32768.0;
+    const uint32_t seg0 = tid * S;
+    const uint32_t sl = seg0 < len ? std::min(S, len - seg0) : 0u;
+    const double *xl = xs + tid * Sp;
+    // every segment from zero state: its end state
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (uint32_t i = 0; i < sl; i++)
+        ln_step(c, v, xl[i] * inv);
+    for (int i = 0; i < 4; i++)
+        sc[tid * 4 + i] = v[i];
+    __syncthreads();
+    // inclusive scan of v_0 = tile start state, v_l = e_(l-1): s_l = sum_(m <= l) A^(S (l - m)) v_m
+    for (int i = 0; i < 4; i++) {
+        double s0 = 0.0;
+        if (kZ)
+            s0 = st[(U.tile0 + t) * 4 + i];
+        v[i] = tid == 0 ? s0 : sc[(tid - 1) * 4 + i];
+    }
+    const uint32_t nact = (len + S - 1) / S;
+    for (uint32_t kk = 0; (1u << kk) < nact; kk++) {
+        const uint32_t d = 1u << kk;
+        __syncthreads();
+        for (int i = 0; i < 4; i++)
+            sc[tid * 4 + i] = v[i];
+        __syncthreads();
+        if (tid >= d) {
+            double w[4];
+            for (int i = 0; i < 4; i++)
+                w[i] = sc[(tid - d) * 4 + i];
+            ln_mv_add((cdouble *)R->P[kk], w, v);
+        }
+    }
+    // v: the state at the start of this lane's segment
+    double acc = 0.0;
+    if (kZ) {
+        for (uint32_t i = 0; i < sl; i++) {
+            const double y = ln_step(c, v, xl[i] * inv);
+            acc = __builtin_fma(y, y, acc);
+        }
+    } else {
+        if (tid == nact - 1) {
+            for (uint32_t i = 0; i < sl; i++)
+                ln_step(c, v, xl[i] * inv);
+            for (int i = 0; i < 4; i++)
+                st[(U.tile0 + t) * 4 + i] = v[i];
+        }
+        acc = peak;
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (uint32_t w = kLnLanes / 2; w > 0; w >>= 1) {
+        if (tid < w)
+            red[tid] = kZ ? red[tid] + red[tid + w] : fmax(red[tid], red[tid + w]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (kZ)
+            z[U.tile0 + t] = red[0];
+        else
+            pk[U.tile0 + t] = red[0];
+    }
+}
+
+__device__ __forceinline__ void ln_mat_mul(const double *a, const double *b, double *out)
+{
+    double r[16];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double acc = 0.0;
+            for (int k = 0; k < 4; k++)
+                acc = __builtin_fma(a[i * 4 + k], b[k * 4 + j], acc);
+            r[i * 4 + j] = acc;
+        }
+    for (int i = 0; i < 16; i++)
+        out[i] = r[i];
+}
+
+// One wave per utterance: every tile of a full hop gets its true start state (in place of its zero-state end state)
+__global__ __launch_bounds__(64) void k_ln_scan(const LoudnessRate *__restrict__ rates,
+                                                const LoudnessUtt *__restrict__ utts, double *__restrict__ st)
+{
+    const LoudnessUtt U = utts[blockIdx.x];
+    const LoudnessRate *R = rates + U.rate;
+    const uint32_t H = R->H, tph = R->tph;
+    const uint64_t nh = U.n / H; // full hops
+    if (nh == 0)
+        return;
+    const uint32_t lane = threadIdx.x;
+    const uint64_t cl = (nh + 63) / 64; // hops per lane
+    const uint64_t h0 = std::min<uint64_t>(lane * cl, nh), h1 = std::min<uint64_t>(h0 + cl, nh);
+    double *sb = st + U.tile0 * 4;
+    cdouble *Pt = (cdouble *)R->Pt, *Pr = (cdouble *)R->Pr, *Ph = (cdouble *)R->Ph;
+    // the chunk's end state from zero
+    double F[4] = {0.0, 0.0, 0.0, 0.0};
+    for (uint64_t h = h0; h < h1; h++) {
+        double e[4];
+        for (int i = 0; i < 4; i++)
+            e[i] = sb[(h * tph) * 4 + i];
+        for (uint32_t k = 1; k < tph; k++) {
+            double n[4];
+            for (int i = 0; i < 4; i++)
+                n[i] = sb[(h * tph + k) * 4 + i];
+            ln_mv_add(k + 1 < tph ? Pt : Pr, e, n);
+            for (int i = 0; i < 4; i++)
+                e[i] = n[i];
+        }
+        ln_mv_add(Ph, F, e);
+        for (int i = 0; i < 4; i++)
+            F[i] = e[i];
+    }
+    // Q = A^(H cl), the transition over a full chunk
+    double Q[16], p[16];
+    for (int i = 0; i < 16; i++) {
+        Q[i] = (i % 5) == 0 ? 1.0 : 0.0;
+        p[i] = Ph[i];
+    }
+    for (uint64_t m = cl; m; m >>= 1) {
+        if (m & 1)
+            ln_mat_mul(Q, p, Q);
+        if (m > 1)
+            ln_mat_mul(p, p, p);
+    }
+    // inclusive scan across the lanes, then each lane's chunk start is its predecessor's value
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        double w[4];
+        for (int i = 0; i < 4; i++)
+            w[i] = __shfl_up(F[i], d, 64);
+        if (lane >= d)
+            for (int i = 0; i < 4; i++) {
+                double acc = F[i];
+                for (int k = 0; k < 4; k++)
+                    acc = __builtin_fma(Q[i * 4 + k], w[k], acc);
+                F[i] = acc;
+            }
+        ln_mat_mul(Q, Q, Q);
+    }
+    double s[4];
+    for (int i = 0; i < 4; i++) {
+        const double w = __shfl_up(F[i], 1, 64);
+        s[i] = lane == 0 ? 0.0 : w;
+    }
+    for (uint64_t h = h0; h < h1; h++)
+        for (uint32_t k = 0; k < tph; k++) {
+            double *p4 = sb + (h * tph + k) * 4;
+            double e[4];
+            for (int i = 0; i < 4; i++) {
+                e[i] = p4[i];
+                p4[i] = s[i];
+            }
+            ln_mv_add(k + 1 < tph ? Pt : Pr, s, e);
+            for (int i = 0; i < 4; i++)
+                s[i] = e[i];
+        }
+}
+
+// One workgroup per utterance: z_j, blocks, gates, L, P, gain -- fixed orders over a fixed thread count
+__global__ __launch_bounds__(kLnLanes) void k_ln_gate(const LoudnessRate *__restrict__ rates,
+                                                      const LoudnessUtt *__restrict__ utts,
+                                                      const double *__restrict__ pk, const double *__restrict__ z,
+                                                      LoudnessResult *__restrict__ res)
+{
+    __shared__ double rs[kLnLanes];
+    __shared__ uint32_t rn[kLnLanes];
+    const uint32_t tid = threadIdx.x;
+    const LoudnessUtt U = utts[blockIdx.x];
+    const LoudnessRate *R = rates + U.rate;
+    const uint32_t H = R->H, tph = R->tph;
+    double m = 0.0;
+    for (uint32_t t = tid; t < U.ntiles; t += kLnLanes)
+        m = fmax(m, pk[U.tile0 + t]);
+    rs[tid] = m;
+    __syncthreads();
+    for (uint32_t w = kLnLanes / 2; w > 0; w >>= 1) {
+        if (tid < w)
+            rs[tid] = fmax(rs[tid], rs[tid + w]);
+        __syncthreads();
+    }
+    const double peak = rs[0];
+    __syncthreads();
+    const uint64_t nh = U.n / H, nb = nh >= 4 ? nh - 3 : 0;
+    const double *zu = z + U.tile0;
+    auto hop_z = [&](uint64_t h) {
+        double s = zu[h * tph];
+        for (uint32_t k = 1; k < tph; k++)
+            s += zu[h * tph + k];
+        return s;
+    };
+    const double den = 4.0 * (double)H;
+    // pass 0: the absolute gate; pass 1: both gates
+    double gamma = -INFINITY, L = -INFINITY;
+    for (int pass = 0; pass < 2; pass++) {
+        double sum = 0.0;
+        uint32_t cnt = 0;
+        for (uint64_t i = tid; i < nb; i += kLnLanes) {
+            const double ms = (((hop_z(i) + hop_z(i + 1)) + hop_z(i + 2)) + hop_z(i + 3)) / den;
+            const double l = -0.691 + 10.0 * log10(ms);
+            if (l > -70.0 && (pass == 0 || l > gamma)) {
+                sum += ms;
+                cnt++;
+            }
+        }
+        rs[tid] = sum;
+        rn[tid] = cnt;
+        __syncthreads();
+        for (uint32_t w = kLnLanes / 2; w > 0; w >>= 1) {
+            if (tid < w) {
+                rs[tid] += rs[tid + w];
+                rn[tid] += rn[tid + w];
+            }
+            __syncthreads();
+        }
+        sum = rs[0];
+        cnt = rn[0];
+        __syncthreads();
+        if (cnt == 0)
+            break;
+        const double lk = -0.691 + 10.0 * log10(sum / (double)cnt);
+        if (pass == 0)
+            gamma = lk - 10.0;
+        else
+            L = lk;
+    }
+    if (tid == 0) {
+        const double P = 20.0 * log10(peak / 32768.0);
+        double gain = 0.0;
+        bool any = false;
+        const double tl = U.target - L, cp = U.ceiling - P;
+        if (isfinite(tl)) {
+            gain = tl;
+            any = true;
+        }
+        if (isfinite(cp)) {
+            gain = any ? fmin(gain, cp) : cp;
+            any = true;
+        }
+        LoudnessResult r;
+        r.lufs = L;
+        r.peak_dbfs = P;
+        r.gain_db = gain;
+        r.g = pow(10.0, gain / 20.0);
+        res[U.slot] = r;
+    }
+}
+
+// the vocoder's 16-bit sink rule (jb_vocoder.hip pcm_i16): clamp, then truncate toward zero
+__device__ __forceinline__ int16_t ln_i16(double v)
+{
+    v = fmin(v, 32767.0);
+    v = fmax(v, -32768.0);
+    return (int16_t)(int)v;
+}
+
+template <class T>
+__global__ __launch_bounds__(kLnLanes) void k_ln_apply(const LoudnessUtt *__restrict__ utts, uint32_t n_utts,
+                                                       const LoudnessResult *__restrict__ res)
+{
+    const uint32_t u = ln_find<true>(utts, n_utts, blockIdx.x);
+    const LoudnessUtt U = utts[u];
+    const uint64_t k0 = (blockIdx.x - U.at0) * (uint64_t)kLnApplyTile;
+    if (k0 >= U.n || !U.y)
+        return;
+    const uint64_t k1 = std::min<uint64_t>(k0 + kLnApplyTile, U.n);
+    const double g = res[U.slot].g;
+    T *y = (T *)U.y;
+#pragma unroll 8
+    for (uint64_t k = k0 + threadIdx.x; k < k1; k += kLnLanes) {
+        const double v = U.x[k] * g;
+        if constexpr (sizeof(T) == 2)
+            y[k] = ln_i16(v);
+        else
+            y[k] = v;
+    }
+}
+
+hipError_t launch_loudness_measure(const LoudnessRate *rates_dev, const LoudnessUtt *utts_dev, uint32_t n,
+                                   uint64_t tiles, double *st, double *pk, double *z, LoudnessResult *res,
+                                   hipStream_t stream)
+{
+    if (n == 0)
+        return hipSuccess;
+    if (tiles > 0x7fffffffull)
+        return hipErrorInvalidValue;
+    if (tiles) {
+        hipLaunchKernelGGL(k_ln_tiles<false>, dim3((uint32_t)tiles), dim3(kLnLanes), 0, stream, rates_dev, utts_dev, n,
+                           st, pk, z);
+        hipLaunchKernelGGL(k_ln_scan, dim3(n), dim3(64), 0, stream, rates_dev, utts_dev, st);
+        hipLaunchKernelGGL(k_ln_tiles<true>, dim3((uint32_t)tiles), dim3(kLnLanes), 0, stream, rates_dev, utts_dev, n,
+                           st, pk, z);
+    }
+    hipLaunchKernelGGL(k_ln_gate, dim3(n), dim3(kLnLanes), 0, stream, rates_dev, utts_dev, pk, z, res);
+    return hipGetLastError();
+}
+
+hipError_t launch_loudness_apply(const LoudnessUtt *utts_dev, uint32_t n, uint64_t atiles, const LoudnessResult *res,
+                                 bool i16, hipStream_t stream)
+{
+    if (n == 0 || atiles == 0)
+        return hipSuccess;
+    if (atiles > 0x7fffffffull)
+        return hipErrorInvalidValue;
+    if (i16)
+        hipLaunchKernelGGL(k_ln_apply<int16_t>, dim3((uint32_t)atiles), dim3(kLnLanes), 0, stream, utts_dev, n, res);
+    else
+        hipLaunchKernelGGL(k_ln_apply<double>, dim3((uint32_t)atiles), dim3(kLnLanes), 0, stream, utts_dev, n, res);
+    return hipGetLastError();
+}
+
+} // namespace jb
+
+using namespace jb;
+
+extern "C" {
+
+int jb_loudness_filter(uint32_t hz, double *b, double *a, uint32_t *hop) { return loudness_filter(hz, b, a, hop); }
+
+int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
+                          double *lufs, double *peak_dbfs)
+{
+    if (n && (!in || !n_in || !lufs || !peak_dbfs))
+        return JB_ERR_INVALID;
+    if (hz == 0) {
+        set_error("loudness: a rate of 0 Hz");
+        return JB_ERR_INVALID;
+    }
+    if (n > 0x7fffffffu)
+        return JB_ERR_INVALID;
+    for (size_t u = 0; u < n; u++)
+        if (n_in[u] && !in[u])
+            return JB_ERR_INVALID;
+    LoudnessRate rate{};
+    int rc = loudness_rate(hz, &rate);
+    if (rc)
+        return rc;
+    int dev = device, prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
+        set_error("no HIP device");
+        return JB_ERR_DEVICE;
+    }
+    if (dev != prev && hipSetDevice(dev) != hipSuccess) {
+        set_error("hipSetDevice failed");
+        return JB_ERR_DEVICE;
+    }
+    std::vector<LoudnessUtt> utts(n);
+    uint64_t tiles = 0, samples = 0;
+    for (size_t u = 0; u < n; u++) {
+        LoudnessUtt &w = utts[u];
+        w = LoudnessUtt{};
+        w.n = n_in[u];
+        w.ntiles = loudness_tiles(rate, w.n);
+        w.tile0 = w.lt0 = tiles;
+        w.slot = (uint32_t)u;
+        w.target = NAN;
+        w.ceiling = INFINITY;
+        tiles += w.ntiles;
+        samples += w.n;
+    }
+    double *dx = nullptr, *dst = nullptr, *dpk = nullptr, *dz = nullptr;
+    LoudnessRate *dr = nullptr;
+    LoudnessUtt *du = nullptr;
+    LoudnessResult *dres = nullptr;
+    hipStream_t s = nullptr;
+    std::vector<LoudnessResult> out(n);
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&dx, sizeof(double) * std::max<uint64_t>(samples, 1));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&dst, sizeof(double) * 4 * std::max<uint64_t>(tiles, 1));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&dpk, sizeof(double) * std::max<uint64_t>(tiles, 1));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&dz, sizeof(double) * std::max<uint64_t>(tiles, 1));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&dr, sizeof rate);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&du, sizeof(LoudnessUtt) * std::max<size_t>(n, 1));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&dres, sizeof(LoudnessResult) * std::max<size_t>(n, 1));
+    uint64_t off = 0;
+    for (size_t u = 0; u < n && e == hipSuccess; u++) {
+        utts[u].x = dx + off;
+        if (n_in[u])
+            e = hipMemcpyAsync(dx + off, in[u], sizeof(double) * n_in[u], hipMemcpyHostToDevice, s);
+        off += n_in[u];
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(dr, &rate, sizeof rate, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n)
+        e = hipMemcpyAsync(du, utts.data(), sizeof(LoudnessUtt) * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = launch_loudness_measure(dr, du, (uint32_t)n, tiles, dst, dpk, dz, dres, s);
+    if (e == hipSuccess && n)
+        e = hipMemcpyAsync(out.data(), dres, sizeof(LoudnessResult) * n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (s)
+        (void)hipStreamSynchronize(s);
+    hipFree(dx);
+    hipFree(dst);
+    hipFree(dpk);
+    hipFree(dz);
+    hipFree(dr);
+    hipFree(du);
+    hipFree(dres);
+    if (s)
+        hipStreamDestroy(s);
+    if (dev != prev)
+        (void)hipSetDevice(prev);
+    if (e != hipSuccess)
+        return hip_fail(e, "jb_loudness_pcm_batch");
+    for (size_t u = 0; u < n; u++) {
+        lufs[u] = out[u].lufs;
+        peak_dbfs[u] = out[u].peak_dbfs;
+    }
+    return JB_OK;
+}
+
+} // extern "C"

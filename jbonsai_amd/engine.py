@@ -47,6 +47,10 @@ def _bind(L):
     L.jb_engine_set_output_sampling_frequency.argtypes = [vp, sz]
     L.jb_engine_get_output_sampling_frequency.argtypes = [vp]
     L.jb_engine_get_output_sampling_frequency.restype = sz
+    for n in ("loudness_target", "peak_ceiling"):
+        getattr(L, "jb_engine_set_" + n).argtypes = [vp, C.c_double]
+        getattr(L, "jb_engine_get_" + n).argtypes = [vp]
+        getattr(L, "jb_engine_get_" + n).restype = C.c_double
     L.jb_engine_set_fast_invariant.argtypes = [vp, C.c_int]
     L.jb_engine_get_fast_invariant.argtypes = [vp]
     for n in ("num_voices", "num_streams", "num_states"):
@@ -137,6 +141,14 @@ class _Condition:
     def set_output_sampling_frequency(self, hz):
         F.check(self._L().jb_engine_set_output_sampling_frequency(self._h(), int(hz)))
     def get_output_sampling_frequency(self): return self._L().jb_engine_get_output_sampling_frequency(self._h())
+    def set_loudness_target(self, lufs):
+        """Target loudness (LUFS) of every entry's output; NaN (the default) = off."""
+        F.check(self._L().jb_engine_set_loudness_target(self._h(), float(lufs)))
+    def get_loudness_target(self): return self._L().jb_engine_get_loudness_target(self._h())
+    def set_peak_ceiling(self, dbfs):
+        """Sample-peak ceiling (dBFS) that goes with the target: default 0, inf = none."""
+        F.check(self._L().jb_engine_set_peak_ceiling(self._h(), float(dbfs)))
+    def get_peak_ceiling(self): return self._L().jb_engine_get_peak_ceiling(self._h())
     def set_alpha(self, f): F.check(self._L().jb_engine_set_alpha(self._h(), float(f)))
     def get_alpha(self): return self._L().jb_engine_get_alpha(self._h())
     def set_beta(self, f): F.check(self._L().jb_engine_set_beta(self._h(), float(f)))
