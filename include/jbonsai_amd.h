@@ -96,6 +96,16 @@ typedef struct jb_state_utt {
     jb_stream_states stream[JB_MAX_STREAM];
 } jb_state_utt;
 
+/* FLAC options (jb_batch_set_flac, jb_flac_encode_pcm_batch, jb_synthesize*_flac).  All zero (or a NULL pointer) =
+ * the defaults: block_size 4096, max_lpc_order 8 (what `flac -5` uses for mono).  block_size 16..4608 (0: 4096);
+ * max_lpc_order 0..12, 0 with a nonzero block_size = CONSTANT, VERBATIM and FIXED subframes only; reserved 0.
+ * Anything else: JB_ERR_INVALID before any device is touched. */
+typedef struct jb_flac_opts {
+    uint32_t block_size;
+    uint32_t max_lpc_order;
+    uint32_t reserved[2];
+} jb_flac_opts;
+
 typedef struct jb_batch_opts {
     int32_t device;         /* HIP device ordinal; -1 = current */
     uint32_t flags;         /* JB_BATCH_* */
@@ -320,6 +330,19 @@ int jb_batch_set_loudness_target(jb_batch *b, const double *target_lufs, size_t 
  * block survives the gates), P (dBFS, -INFINITY for silence) and gain_dB.  Waits for the run like the read entries;
  * a batch without a target or not yet run: JB_ERR_INVALID. */
 int jb_batch_loudness(jb_batch *b, size_t utt, double *lufs, double *peak_dbfs, double *gain_db);
+/* New.  FLAC output (see "FLAC" below): the run encodes each utterance's 16-bit PCM as the read entries hand it out
+ * (after the output rate and the loudness target) into one FLAC stream per utterance, on the device.  opts: NULL or
+ * zeros = the defaults.  Only before the batch's first run, on a JB_BATCH_PCM_I16 batch that is not
+ * JB_BATCH_MLPG_ONLY; otherwise JB_ERR_INVALID.  An output rate with no frame-header code fails at the run with
+ * JB_ERR_UNSUPPORTED.  The PCM read entries keep working.  Without a call nothing runs and nothing is allocated. */
+int jb_batch_set_flac(jb_batch *b, const jb_flac_opts *opts);
+/* Bytes of utterance utt's stream; waits for the run like the read entries.  No FLAC or no such utterance:
+ * JB_ERR_INVALID. */
+int jb_batch_flac_size(jb_batch *b, size_t utt, size_t *n_bytes);
+/* The stream of utterance utt into dst; cap below jb_batch_flac_size: JB_ERR_BUFFER. */
+int jb_batch_read_flac(jb_batch *b, size_t utt, uint8_t *dst, size_t cap);
+/* Every stream: dst[u] must hold jb_batch_flac_size(b, u) bytes (one device-to-host copy for the batch). */
+int jb_batch_read_flac_all(jb_batch *b, uint8_t *const *dst);
 void jb_batch_free(jb_batch *b);
 
 /* One-shot convenience: create + run + read + free.  pcm[i] must hold
@@ -414,6 +437,36 @@ int jb_loudness_filter(uint32_t hz, double *b, double *a, uint32_t *hop);
  * (n_in[u] samples at hz), on `device` (-1 = current).  A hop outside 1..61439 samples: JB_ERR_UNSUPPORTED. */
 int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
                           double *lufs, double *peak_dbfs);
+
+/* ---- FLAC (new: the reference writes WAV only; RFC 9639) ---------------------------------------------------------
+ * Each utterance's 16-bit output (exactly what jb_batch_read_pcm_i16 hands out: after the converter, the loudness
+ * apply pass or the fused sink) becomes one complete FLAC stream; decoding it gives those samples bit for bit.
+ * - Layout: "fLaC", one STREAMINFO block (marked last), then frames.  Mono, 16 bits, at the utterance's output rate
+ *   (jb_batch_output_rate).  Fixed block size with frame-number headers: every frame has block_size samples but the
+ *   last, which may be shorter.
+ * - STREAMINFO: min = max block size = block_size; min / max frame size the true values of the stream (0 with no
+ *   frames); total samples exact; MD5 all zero ("not computed", which the format allows: it is serial per stream).
+ * - Every stream is in the streamable subset: block size <= 4608, LPC order <= 12, Rice partition order <= 8, and
+ *   the sample rate and bit depth coded in every frame header.  A rate without a code of its own uses the kHz,
+ *   16-bit-Hz or tens-of-Hz form; a rate none of them can express is JB_ERR_UNSUPPORTED when FLAC is requested
+ *   (every rate up to 65,535 Hz has a code, and so do 88.2, 96, 176.4 and 192 kHz).
+ * - Subframes: a block of equal samples is CONSTANT; otherwise the cheapest of VERBATIM, FIXED orders 0-4 and LPC
+ *   at the orders 2, 4, 8 and max_lpc_order (those <= max_lpc_order and below the block length; Tukey(0.5) window,
+ *   autocorrelation, Levinson-Durbin, precision 7..12 bits by block length, shift 0..15) with partitioned Rice
+ *   residuals (4- or 5-bit parameters, chosen by libFLAC's estimate; the winner priced exactly).  A frame is never
+ *   larger than its VERBATIM encoding.  Wasted-bits flag 0.  An LPC candidate whose residual does not fit in 32
+ *   bits is dropped.
+ * - Determinism: a stream's bytes depend only on its samples, its rate, the options and the library build (every
+ *   f64 step runs in a fixed order and ties break by a fixed rule), not on the batch, the utterance's position, the
+ *   entry point or redo rounds; JB_BATCH_INVARIANT output stays invariant.
+ * Not covered: the generator (it hands out f64), the _multi entries and jb_gather_pcm, f64 batches, 24-bit or
+ * stereo, MD5, SEEKTABLE and other metadata, variable block size, Ogg encapsulation, lossy codecs. */
+/* The encoder on PCM the caller holds (jb_resample_pcm_batch's twin): out[u] = the stream of in[u] (n_in[u] samples
+ * at hz), n_out[u] bytes, library-owned (jb_flac_free each), on `device` (-1 = current).  The same samples and
+ * options give the same bytes as the batch path. */
+int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, uint32_t hz,
+                             const jb_flac_opts *opts, int32_t device, uint8_t **out, size_t *n_out);
+void jb_flac_free(uint8_t *p);
 
 /* ---- multi-GPU (SURVEY 8b "device_ids[] / n_devices", 8e) ----------------------------------
  * Utterances are independent, so a batch shards over the GPUs of a node with no data-path
@@ -587,6 +640,17 @@ int jb_synthesize_batch_each(const jb_engine *const *engines, const char *const 
 int jb_synthesize_batch_each_i16(const jb_engine *const *engines, const char *const *label_lines,
                                  const size_t *line_off, size_t n_utts, int32_t device, int16_t **pcm,
                                  size_t *n_samples);
+/* New.  FLAC forms of jb_synthesize (one utterance, current device), jb_synthesize_batch_i16 and
+ * jb_synthesize_batch_each_i16: flac[u] is the stream of what the _i16 entry returns (each engine's output rate and
+ * loudness target honoured the same way), n_bytes[u] bytes, library-owned (jb_flac_free each).  opts as
+ * jb_batch_set_flac's. */
+int jb_synthesize_flac(const jb_engine *e, const char *const *label_lines, size_t n_lines, const jb_flac_opts *opts,
+                       uint8_t **flac, size_t *n_bytes);
+int jb_synthesize_batch_flac(const jb_engine *e, const char *const *label_lines, const size_t *line_off, size_t n_utts,
+                             int32_t device, const jb_flac_opts *opts, uint8_t **flac, size_t *n_bytes);
+int jb_synthesize_batch_each_flac(const jb_engine *const *engines, const char *const *label_lines,
+                                  const size_t *line_off, size_t n_utts, int32_t device, const jb_flac_opts *opts,
+                                  uint8_t **flac, size_t *n_bytes);
 /* The same two over a device list: the utterances are split by LPT on their label counts (the frame
  * counts are known only after the front half), one host thread per device runs jb_synthesize_batch's
  * path on its share (front half on that thread's workers, GPU work on that device). */
@@ -701,6 +765,8 @@ JB_LAYOUT_ASSERT(sizeof(jb_track_utt) == 64 && offsetof(jb_track_utt, spectrum_w
                      offsetof(jb_track_utt, spectrum) == 40, "jb_track_utt");
 JB_LAYOUT_ASSERT(sizeof(jb_utt_voc) == 24 && offsetof(jb_utt_voc, beta) == 8 && offsetof(jb_utt_voc, volume) == 16,
                  "jb_utt_voc");
+JB_LAYOUT_ASSERT(sizeof(jb_flac_opts) == 16 && offsetof(jb_flac_opts, max_lpc_order) == 4 &&
+                     offsetof(jb_flac_opts, reserved) == 8, "jb_flac_opts");
 #undef JB_LAYOUT_ASSERT
 #endif
 #endif /* JBONSAI_AMD_H */

@@ -4,16 +4,16 @@ MLSA-vocoder hot path behind a C ABI (include/jbonsai_amd.h).
 The HIP shared library `libjbonsai_amd.so` is the product; this package is the
 thin host-side mirror of the reference's API used by tests and the benchmark.
 """
-from ._ffi import (JbError, LIB_PATH, NODATA, UttVoc, build, lib, loudness, loudness_filter, resample,  # noqa: F401
-                   resample_filter, write_wav)
+from ._ffi import (JbError, LIB_PATH, NODATA, UttVoc, build, flac_encode, lib, loudness, loudness_filter,  # noqa: F401
+                   resample, resample_filter, write_wav)
 from .batch import (Batch, IndexStreamStates, IndexUtterance, PdfSet, StreamInfo, StreamStates, TrackUtterance,  # noqa: F401
                     Utterance, VoiceInfo, generator_from_tracks, mlpg_batch, paramgen_vocode_batch, vocode_tracks_batch,
                     vocoder_synthesize_batch)
 
-from .engine import Engine, SpeechGenerator, synthesize_batch_each  # noqa: F401,E402
+from .engine import Engine, SpeechGenerator, synthesize_batch_each, synthesize_batch_each_flac  # noqa: F401,E402
 from . import comm  # noqa: F401,E402
 
 __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build", "lib", "write_wav", "Batch", "StreamInfo", "StreamStates",
            "Utterance", "VoiceInfo", "paramgen_vocode_batch", "mlpg_batch", "vocode_tracks_batch", "vocoder_synthesize_batch", "generator_from_tracks", "TrackUtterance", "PdfSet", "IndexUtterance", "IndexStreamStates",
            "UttVoc", "synthesize_batch_each", "resample", "resample_filter",
-           "loudness", "loudness_filter"]
+           "loudness", "loudness_filter", "flac_encode", "synthesize_batch_each_flac"]

@@ -128,6 +128,23 @@ class UttVoc(C.Structure):
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("volume", C.c_double)]
 
 
+class FlacOpts(C.Structure):
+    """jb_flac_opts: all zero = the defaults (block size 4096, LPC order up to 8)."""
+    _fields_ = [("block_size", C.c_uint32), ("max_lpc_order", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def flac_opts(block_size: int = 0, max_lpc_order=None):
+    """FlacOpts for (block_size, max_lpc_order); None / 0 keep the defaults (max_lpc_order=0 with a block size: no
+    LPC)."""
+    o = FlacOpts()
+    o.block_size = int(block_size)
+    if max_lpc_order is not None:
+        o.max_lpc_order = int(max_lpc_order)
+        if not o.block_size and o.max_lpc_order == 0:
+            o.block_size = 4096  # "FIXED only" needs a nonzero block size: all zeros are the defaults
+    return o
+
+
 class BatchOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32), ("chunk_frames", C.c_uint32),
                 ("warmup_frames", C.c_uint32), ("verify_tol", C.c_double), ("reserved0", C.c_uint32), ("reserved", C.c_uint32)]
@@ -166,6 +183,9 @@ SYMBOLS = [
     "jb_batch_set_loudness_target", "jb_batch_loudness", "jb_loudness_filter", "jb_loudness_pcm_batch",
     "jb_engine_set_loudness_target", "jb_engine_get_loudness_target", "jb_engine_set_peak_ceiling",
     "jb_engine_get_peak_ceiling",
+    "jb_batch_set_flac", "jb_batch_flac_size", "jb_batch_read_flac", "jb_batch_read_flac_all",
+    "jb_flac_encode_pcm_batch", "jb_flac_free", "jb_synthesize_flac", "jb_synthesize_batch_flac",
+    "jb_synthesize_batch_each_flac",
 ]
 
 
@@ -291,6 +311,20 @@ def lib():
         getattr(L, "jb_engine_set_" + n).argtypes = [vp, C.c_double]
         getattr(L, "jb_engine_get_" + n).argtypes = [vp]
         getattr(L, "jb_engine_get_" + n).restype = C.c_double
+    u8p, fop = C.POINTER(C.c_uint8), C.POINTER(FlacOpts)
+    L.jb_batch_set_flac.argtypes = [vp, fop]
+    L.jb_batch_flac_size.argtypes = [vp, sz, C.POINTER(sz)]
+    L.jb_batch_read_flac.argtypes = [vp, sz, u8p, sz]
+    L.jb_batch_read_flac_all.argtypes = [vp, C.POINTER(u8p)]
+    L.jb_flac_encode_pcm_batch.argtypes = [C.POINTER(C.POINTER(C.c_int16)), C.POINTER(sz), sz, C.c_uint32, fop,
+                                           C.c_int32, C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_flac_free.argtypes = [u8p]
+    L.jb_flac_free.restype = None
+    L.jb_synthesize_flac.argtypes = [vp, C.POINTER(C.c_char_p), sz, fop, C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_synthesize_batch_flac.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, fop,
+                                           C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_synthesize_batch_each_flac.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
+                                                fop, C.POINTER(u8p), C.POINTER(sz)]
     L.jb_write_wav_i16.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     L.jb_write_wav_f64.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     _lib = L
@@ -349,6 +383,32 @@ def loudness(pcms, hz: int, device: int = -1):
     check(lib().jb_loudness_pcm_batch(ins, nin, n, hz, device, lufs.ctypes.data_as(dp), peak.ctypes.data_as(dp)))
     res = [(float(lufs[u]), float(peak[u])) for u in range(n)]
     return res[0] if single else res
+
+
+def take_flac(L, bufs, ns, n):
+    """bytes of n library-owned FLAC streams, each released with jb_flac_free."""
+    out = []
+    for u in range(n):
+        out.append(C.string_at(bufs[u], ns[u]) if ns[u] else b"")
+        if bufs[u]:
+            L.jb_flac_free(bufs[u])
+    return out
+
+
+def flac_encode(pcms, hz: int, block_size: int = 0, max_lpc_order=None, device: int = -1):
+    """jb_flac_encode_pcm_batch: one FLAC stream (bytes) per int16 array of `pcms` at hz, encoded on the GPU."""
+    import numpy as np
+
+    arrs = [np.ascontiguousarray(a, dtype=np.int16) for a in pcms]
+    n = len(arrs)
+    L = lib()
+    i16p, u8p = C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
+    ins = (i16p * max(n, 1))(*[a.ctypes.data_as(i16p) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    opts = flac_opts(block_size, max_lpc_order)
+    check(L.jb_flac_encode_pcm_batch(ins, nin, n, hz, C.byref(opts), device, bufs, ns))
+    return take_flac(L, bufs, ns, n)
 
 
 def resample(pcms, in_hz: int, out_hz: int, device: int = -1):

@@ -377,6 +377,34 @@ class Batch:
         F.check(self._L.jb_batch_loudness(self._h, i, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def set_flac(self, block_size: int = 0, max_lpc_order=None):
+        """jb_batch_set_flac: the run also encodes each utterance's 16-bit output as a FLAC stream (pcm_i16=True,
+        not mlpg_only; before the first run only).  Defaults: block size 4096, LPC order up to 8."""
+        opts = F.flac_opts(block_size, max_lpc_order)
+        F.check(self._L.jb_batch_set_flac(self._h, C.byref(opts)))
+
+    def flac(self, i) -> bytes:
+        """Utterance i's FLAC stream (jb_batch_flac_size + jb_batch_read_flac)."""
+        n = C.c_size_t()
+        F.check(self._L.jb_batch_flac_size(self._h, i, C.byref(n)))
+        buf = bytearray(max(1, n.value))
+        F.check(self._L.jb_batch_read_flac(self._h, i, (C.c_uint8 * len(buf)).from_buffer(buf), n.value))
+        return bytes(buf[:n.value])
+
+    def flac_all(self) -> List[bytes]:
+        """Every utterance's FLAC stream through one device-to-host copy (jb_batch_read_flac_all)."""
+        B = len(self)
+        ns = []
+        for i in range(B):
+            n = C.c_size_t()
+            F.check(self._L.jb_batch_flac_size(self._h, i, C.byref(n)))
+            ns.append(n.value)
+        bufs = [bytearray(max(1, n)) for n in ns]
+        u8p = C.POINTER(C.c_uint8)
+        arr = (u8p * max(1, B))(*[C.cast((C.c_uint8 * len(b)).from_buffer(b), u8p) for b in bufs])
+        F.check(self._L.jb_batch_read_flac_all(self._h, arr))
+        return [bytes(b[:n]) for b, n in zip(bufs, ns)]
+
     def output_rate(self, i) -> int:
         """Rate of utterance i's PCM as the read entries hand it out (the voice's rate when native)."""
         return self._L.jb_batch_output_rate(self._h, i)

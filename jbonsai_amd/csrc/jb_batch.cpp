@@ -1661,7 +1661,7 @@ int Batch::run(bool timed)
     last_run_timed = timed;
     has_run = true;
     int rc = prepare_loudness();
-    if (rc)
+    if (rc || (rc = prepare_flac()))
         return rc;
     for (int si = 0; si < kMaxStream; si++)
         if (sd[si].gv_gang_ctl && !from_tracks)
@@ -1706,6 +1706,9 @@ int Batch::run(bool timed)
     // loudness: measured on the output f64 and applied behind the converter (finish_verify does both again for what
     // a redo round rewrites)
     if ((rc = enqueue_loudness()))
+        return rc;
+    // FLAC: the 16-bit output encoded (finish_verify encodes again what a redo round rewrote)
+    if ((rc = enqueue_flac()))
         return rc;
     if (timed)
         hipEventRecord(ev3, stream_voc);
@@ -1983,7 +1986,117 @@ int Batch::finish_verify()
     if (rc)
         return rc;
     // loudness: the gain is a function of the final PCM
-    return enqueue_loudness(&touched);
+    rc = enqueue_loudness(&touched);
+    if (rc)
+        return rc;
+    // FLAC: the streams of the utterances these rounds rewrote, then every stream's place
+    return enqueue_flac(&touched);
+}
+
+// ---- FLAC (jb_batch_set_flac) ----
+int Batch::set_flac(const jb_flac_opts *opts)
+{
+    FlacParams p{};
+    int rc = flac_check_opts(opts, &p);
+    if (rc)
+        return rc;
+    if (flags & JB_BATCH_MLPG_ONLY) {
+        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_INVALID;
+    }
+    if (!(flags & JB_BATCH_PCM_I16)) {
+        set_error("jb_batch_set_flac: FLAC encodes the 16-bit output (JB_BATCH_PCM_I16)");
+        return JB_ERR_INVALID;
+    }
+    if (has_run) {
+        set_error("jb_batch_set_flac: FLAC is set before the batch's first run");
+        return JB_ERR_INVALID;
+    }
+    fl_p = p;
+    fl_on = true;
+    return JB_OK;
+}
+
+// At the first run, when the output rate and the loudness slabs are settled
+int Batch::prepare_flac()
+{
+    if (!fl_on || fl_ready)
+        return JB_OK;
+    std::vector<const int16_t *> xs((size_t)B);
+    std::vector<uint64_t> ns((size_t)B);
+    std::vector<uint32_t> hz((size_t)B);
+    for (size_t u = 0; u < (size_t)B; u++) {
+        xs[u] = out_pcm16() + out_offset(u);
+        ns[u] = out_samples(u);
+        hz[u] = (rs_on && out_hz[u]) ? out_hz[u] : voice.sampling_frequency;
+    }
+    uint64_t slot_bytes = 0, bound = 0;
+    int rc = flac_plan(fl_p, xs.data(), ns.data(), hz.data(), (size_t)B, &fl_utts, &fl_work, &slot_bytes, &bound);
+    if (rc)
+        return rc;
+    const size_t nf = std::max<size_t>(fl_work.size(), 1);
+    if ((rc = dalloc(&fl_slots, std::max<uint64_t>(slot_bytes, 4), false)) ||
+        (rc = dalloc(&fl_out, std::max<uint64_t>(bound, 4), false)) ||
+        (rc = dalloc(&fl_utts_dev, std::max<size_t>((size_t)B, 1), false)) || (rc = dalloc(&fl_work_dev, nf, false)) ||
+        (rc = dalloc(&fl_redo_dev, nf, false)) || (rc = dalloc(&fl_fsize, nf, false)) ||
+        (rc = dalloc(&fl_foff, nf, false)) || (rc = dalloc(&fl_res, std::max<size_t>((size_t)B, 1), false)) ||
+        (rc = dalloc(&fl_total, 1, false)))
+        return rc;
+    flac_bind(&fl_utts, fl_slots);
+    hipError_t e = hipSuccess;
+    if ((B > 0 && (e = hipMemcpy(fl_utts_dev, fl_utts.data(), sizeof(FlacUtt) * (size_t)B, hipMemcpyHostToDevice)) !=
+                      hipSuccess) ||
+        (!fl_work.empty() && (e = hipMemcpy(fl_work_dev, fl_work.data(), sizeof(FlacWork) * fl_work.size(),
+                                            hipMemcpyHostToDevice)) != hipSuccess))
+        return hip_fail(e, "FLAC work list");
+    fl_ready = true;
+    return JB_OK;
+}
+
+int Batch::enqueue_flac(const std::vector<uint8_t> *only)
+{
+    if (!fl_on || !fl_ready)
+        return JB_OK;
+    hipError_t e;
+    const uint32_t nw = (uint32_t)fl_work.size();
+    if (!only) {
+        if ((e = launch_flac_encode(fl_p, fl_utts_dev, fl_work_dev, nw, fl_fsize, stream_voc)) != hipSuccess ||
+            (e = launch_flac_pack(fl_p, fl_utts_dev, (uint32_t)B, fl_work_dev, nw, fl_fsize, fl_foff, fl_res, fl_total,
+                                  fl_out, stream_voc)) != hipSuccess)
+            return hip_fail(e, "FLAC");
+        return JB_OK;
+    }
+    // the blocks of the utterances a redo touched; then every stream's offsets and place again
+    std::vector<FlacWork> sub;
+    for (const FlacWork &w : fl_work)
+        if ((*only)[w.utt])
+            sub.push_back(w);
+    if (sub.empty())
+        return JB_OK;
+    if ((e = hipMemcpy(fl_redo_dev, sub.data(), sizeof(FlacWork) * sub.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = launch_flac_encode(fl_p, fl_utts_dev, fl_redo_dev, (uint32_t)sub.size(), fl_fsize, stream_voc)) !=
+            hipSuccess ||
+        (e = launch_flac_pack(fl_p, fl_utts_dev, (uint32_t)B, fl_work_dev, nw, fl_fsize, fl_foff, fl_res, fl_total,
+                              fl_out, stream_voc)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
+        return hip_fail(e, "FLAC(redo)");
+    return JB_OK;
+}
+
+int Batch::read_flac_index(std::vector<FlacOut> *res, uint64_t *total)
+{
+    if (!fl_on || !fl_ready) {
+        set_error(fl_on ? "FLAC: the batch has not run" : "FLAC: jb_batch_set_flac was not called");
+        return JB_ERR_INVALID;
+    }
+    res->assign((size_t)B, FlacOut{});
+    int rc = B > 0 ? read(fl_res, res->data(), sizeof(FlacOut) * (size_t)B) : sync();
+    if (rc)
+        return rc;
+    *total = 0;
+    for (const FlacOut &o : *res)
+        *total = std::max<uint64_t>(*total, o.off + o.bytes);
+    return JB_OK;
 }
 
 // ---- loudness target (jb_batch_set_loudness_target) ----
@@ -2799,6 +2912,76 @@ int jb_batch_loudness(jb_batch *hb, size_t utt, double *lufs, double *peak_dbfs,
         *peak_dbfs = r.peak_dbfs;
     if (gain_db)
         *gain_db = r.gain_db;
+    return JB_OK;
+}
+
+int jb_batch_set_flac(jb_batch *hb, const jb_flac_opts *opts)
+{
+    if (!hb)
+        return JB_ERR_INVALID;
+    return ((Batch *)hb)->set_flac(opts);
+}
+
+int jb_batch_flac_size(jb_batch *hb, size_t utt, size_t *n_bytes)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !n_bytes || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    if (!b->fl_on || !b->fl_ready) {
+        jb::set_error(b->fl_on ? "FLAC: the batch has not run" : "FLAC: jb_batch_set_flac was not called");
+        return JB_ERR_INVALID;
+    }
+    jb::FlacOut o{};
+    int rc = b->read(b->fl_res + utt, &o, sizeof o);
+    if (rc)
+        return rc;
+    *n_bytes = (size_t)o.bytes;
+    return JB_OK;
+}
+
+int jb_batch_read_flac(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    if (!b->fl_on || !b->fl_ready) {
+        jb::set_error(b->fl_on ? "FLAC: the batch has not run" : "FLAC: jb_batch_set_flac was not called");
+        return JB_ERR_INVALID;
+    }
+    jb::FlacOut o{};
+    int rc = b->read(b->fl_res + utt, &o, sizeof o);
+    if (rc)
+        return rc;
+    if (cap < o.bytes)
+        return JB_ERR_BUFFER;
+    if (!dst)
+        return JB_ERR_INVALID;
+    return b->read(b->fl_out + o.off, dst, (size_t)o.bytes, false);
+}
+
+int jb_batch_read_flac_all(jb_batch *hb, uint8_t *const *dst)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || (!dst && b->B))
+        return JB_ERR_INVALID;
+    std::vector<jb::FlacOut> res;
+    uint64_t total = 0;
+    int rc = b->read_flac_index(&res, &total);
+    if (rc)
+        return rc;
+    for (size_t u = 0; u < (size_t)b->B; u++)
+        if (!dst[u] && res[u].bytes)
+            return JB_ERR_INVALID;
+    // one copy of the used bytes (not zero-filled first), then the streams into the callers' buffers
+    std::unique_ptr<uint8_t[]> host(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
+    if (!host) {
+        jb::set_error("out of host memory");
+        return JB_ERR_INVALID;
+    }
+    if (total && (rc = b->read(b->fl_out, host.get(), (size_t)total, false)))
+        return rc;
+    for (size_t u = 0; u < (size_t)b->B; u++)
+        memcpy(dst[u], host.get() + res[u].off, (size_t)res[u].bytes);
     return JB_OK;
 }
 

@@ -996,7 +996,7 @@ int jb_write_wav_f64(const char *path, const double *pcm, size_t n, uint32_t fs)
 // elem = 8: f64 PCM (Engine::synthesize's Vec<f64>); elem = 2: the fused 16-bit sink
 int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                               int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads,
-                              const jb_engine *const *each)
+                              const jb_engine *const *each, bool flac, const jb_flac_opts *flac_opts)
 {
     auto eng = [&](size_t u) { return CENG(each ? each[u] : e); }; // the engine of utterance u
     if (!e || !pcm || !n_samples || (n_utts && !line_off))
@@ -1147,6 +1147,8 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         }
         if (any_target && (rc = b->set_loudness(targets.data(), ceilings.data(), targets.size())))
             return rc;
+        if (flac && (rc = b->set_flac(flac_opts)))
+            return rc;
         rc = b->run(false);
         t_create += ms(t0, now());
         return rc;
@@ -1162,6 +1164,32 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         jb::Batch *b = batches[g].get();
         int rc = JB_OK;
         const auto t0 = now();
+        if (flac) {
+            // the streams' sizes and places (one small copy), then the used bytes of the compact slab in one copy
+            std::vector<jb::FlacOut> res;
+            uint64_t total = 0;
+            if ((rc = b->read_flac_index(&res, &total)))
+                return rc;
+            std::unique_ptr<uint8_t[]> host(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
+            if (!host) {
+                jb::set_error("out of host memory");
+                return JB_ERR_INVALID;
+            }
+            if (total && (rc = b->read(b->fl_out, host.get(), (size_t)total, false)))
+                return rc;
+            for (size_t u = lo; u < hi; u++) {
+                const jb::FlacOut &o = res[u - lo];
+                if (!(pcm[u] = malloc(std::max<size_t>((size_t)o.bytes, 1)))) {
+                    jb::set_error("out of host memory");
+                    return JB_ERR_INVALID;
+                }
+                memcpy(pcm[u], host.get() + o.off, (size_t)o.bytes);
+                n_samples[u] = (size_t)o.bytes;
+            }
+            batches[g].reset();
+            t_d2h += ms(t0, now());
+            return JB_OK;
+        }
         for (size_t u = lo; u < hi; u++) {
             const size_t ns = b->out_samples(u - lo);
             n_samples[u] = ns;
@@ -1327,7 +1355,8 @@ static int check_engines(const jb_engine *const *engines, size_t n)
 }
 
 static int synthesize_each(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
-                           size_t n_utts, int32_t device, size_t elem, void **pcm, size_t *n_samples)
+                           size_t n_utts, int32_t device, size_t elem, void **pcm, size_t *n_samples,
+                           bool flac = false, const jb_flac_opts *flac_opts = nullptr)
 {
     if (!pcm || !n_samples || (n_utts && !line_off))
         return JB_ERR_INVALID;
@@ -1336,7 +1365,8 @@ static int synthesize_each(const jb_engine *const *engines, const char *const *l
     const int rc = check_engines(engines, n_utts);
     if (rc)
         return rc;
-    return jb::synthesize_batch_impl(engines[0], lines, line_off, n_utts, device, elem, pcm, n_samples, 0, engines);
+    return jb::synthesize_batch_impl(engines[0], lines, line_off, n_utts, device, elem, pcm, n_samples, 0, engines,
+                                     flac, flac_opts);
 }
 
 extern "C" {
@@ -1351,6 +1381,36 @@ int jb_synthesize_batch_each_i16(const jb_engine *const *engines, const char *co
                                  size_t n_utts, int32_t device, int16_t **pcm, size_t *n_samples)
 {
     return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)pcm, n_samples);
+}
+
+int jb_synthesize_batch_flac(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                             int32_t device, const jb_flac_opts *opts, uint8_t **flac, size_t *n_bytes)
+{
+    int rc = jb::flac_check_opts(opts, nullptr);
+    if (rc)
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, 0,
+                                     nullptr, true, opts);
+}
+
+int jb_synthesize_batch_each_flac(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_flac_opts *opts, uint8_t **flac,
+                                  size_t *n_bytes)
+{
+    int rc = jb::flac_check_opts(opts, nullptr);
+    if (rc)
+        return rc;
+    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, true,
+                           opts);
+}
+
+int jb_synthesize_flac(const jb_engine *e, const char *const *lines, size_t n, const jb_flac_opts *opts,
+                       uint8_t **flac, size_t *n_bytes)
+{
+    if (!flac || !n_bytes)
+        return JB_ERR_INVALID;
+    size_t off[2] = {0, n};
+    return jb_synthesize_batch_flac(e, lines, off, 1, -1, opts, flac, n_bytes);
 }
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)

@@ -30,10 +30,12 @@ void release_cached_memory(); // empties the per-device pools of finished batche
 void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE_POOL_MB at start)
 // jb_synthesize_batch[_i16] on one device (jb_engine.cpp); host_threads = 0: default front-half thread count;
 // each != null (jb_synthesize_batch_each[_i16], engines checked by the caller): utterance u under each[u]'s Condition,
-// e = each[0] for what the engines share
+// e = each[0] for what the engines share; flac (elem 2): pcm[u] / n_samples[u] receive utterance u's FLAC stream
+// and its byte count instead (jb_synthesize*_flac)
 int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                           int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0,
-                          const jb_engine *const *each = nullptr);
+                          const jb_engine *const *each = nullptr, bool flac = false,
+                          const jb_flac_opts *flac_opts = nullptr);
 // static LPT partition (jb_multi.cpp): part_of[i] = bin of item i
 void lpt_partition(const uint64_t *weights, size_t n, size_t n_parts, uint32_t *part_of);
 
@@ -109,6 +111,44 @@ hipError_t launch_loudness_measure(const LoudnessRate *rates_dev, const Loudness
 // y = x * res[slot].g for every utterance of the list (apply tiles in all)
 hipError_t launch_loudness_apply(const LoudnessUtt *utts_dev, uint32_t n, uint64_t atiles, const LoudnessResult *res,
                                  bool i16, hipStream_t stream);
+
+// FLAC encoding of the 16-bit output (jb_flac.hip).  One stream per utterance: a 42-byte header, then frames of
+// block_size samples (the last may be shorter), each encoded into its block's slot (the VERBATIM bound apart), then
+// packed at byte offsets into one compact slab, utterance after utterance
+constexpr uint32_t kFlacMaxBlock = 4608, kFlacMaxLpc = 12, kFlacDefaultBlock = 4096, kFlacDefaultLpc = 8;
+constexpr uint32_t kFlacHeaderBytes = 42; // fLaC + STREAMINFO
+struct FlacParams {
+    uint32_t block_size, max_order, slot_bytes, pad_;
+};
+struct FlacUtt {
+    const int16_t *x; // the utterance's 16-bit PCM
+    uint8_t *slots;   // frame f at slots + f * slot_bytes
+    uint64_t n, frame0; // samples; first frame's index in the per-frame arrays
+    uint32_t nframes, hz, rate_code, rate_bits, rate_val, pad_;
+};
+struct FlacWork { // one block of an encode launch (a pack launch: every frame of the batch, in order)
+    uint32_t utt, frame;
+};
+struct FlacOut { // per utterance: the stream's size and offset in the compact slab, min / max frame size
+    uint64_t bytes, off;
+    uint32_t min_frame, max_frame;
+};
+// opts (NULL: defaults) -> p; JB_ERR_INVALID (set_error says why) for values outside the contract
+int flac_check_opts(const jb_flac_opts *opts, FlacParams *p);
+uint32_t flac_slot_bytes(uint32_t block_size);
+// The frame-header rate code of hz (and its 8- or 16-bit extra field); JB_ERR_UNSUPPORTED where none exists
+int flac_rate_code(uint32_t hz, uint32_t *code, uint32_t *bits, uint32_t *val);
+// The lists of a batch of n_utts streams; slots are offsets (total *slot_bytes) until flac_bind adds the slab's
+// base; *out_bound bounds the compact slab
+int flac_plan(const FlacParams &p, const int16_t *const *x, const uint64_t *n, const uint32_t *hz, size_t n_utts,
+              std::vector<FlacUtt> *utts, std::vector<FlacWork> *work, uint64_t *slot_bytes, uint64_t *out_bound);
+void flac_bind(std::vector<FlacUtt> *utts, uint8_t *slots);
+hipError_t launch_flac_encode(const FlacParams &p, const FlacUtt *utts, const FlacWork *work, uint32_t n_work,
+                              uint32_t *fsize, hipStream_t stream);
+// every utterance: frame offsets, sizes, places, headers, and every frame (work: all of them) into dst
+hipError_t launch_flac_pack(const FlacParams &p, const FlacUtt *utts, uint32_t n_utts, const FlacWork *work,
+                            uint32_t n_frames, const uint32_t *fsize, uint64_t *foff, FlacOut *out, uint64_t *total,
+                            uint8_t *dst, hipStream_t stream);
 
 // Device-resident pdf tables of a voice set (jb_pdf_set) and an indexed batch source
 struct PdfSet {
@@ -274,6 +314,22 @@ struct Batch {
     int enqueue_loudness(const std::vector<uint8_t> *only = nullptr); // only: as enqueue_resample's
     const double *out_pcm64() const;
     const int16_t *out_pcm16() const;
+    // FLAC (jb_batch_set_flac): the run encodes out_pcm16() into fl_out, one stream per utterance
+    bool fl_on = false, fl_ready = false;
+    FlacParams fl_p{};
+    std::vector<FlacUtt> fl_utts;
+    std::vector<FlacWork> fl_work;
+    FlacUtt *fl_utts_dev = nullptr;
+    FlacWork *fl_work_dev = nullptr, *fl_redo_dev = nullptr;
+    uint8_t *fl_slots = nullptr, *fl_out = nullptr;
+    uint32_t *fl_fsize = nullptr;
+    uint64_t *fl_foff = nullptr, *fl_total = nullptr;
+    FlacOut *fl_res = nullptr;
+    int set_flac(const jb_flac_opts *opts);
+    int prepare_flac(); // at the first run, after prepare_loudness: lists and slabs
+    int enqueue_flac(const std::vector<uint8_t> *only = nullptr); // only: re-encode those utterances, pack all
+    // after sync: every stream's size and place (FlacOut) and the compact slab's used bytes
+    int read_flac_index(std::vector<FlacOut> *res, uint64_t *total);
     bool last_run_timed = false;
     uint32_t gang_fallbacks = 0;     // times the resident GV kernel timed out in formation and the sweeps took over
     static int create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n,
