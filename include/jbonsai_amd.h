@@ -307,7 +307,9 @@ uint32_t jb_batch_gang_fallbacks(const jb_batch *b);
  * report the output: ceil(N L / M) samples for N at the voice's rate, f64 or 16-bit by the batch's flags (the 16-bit
  * conversion then follows the conversion of the rate; native utterances of such a batch are copied, values
  * unchanged).  Excitation, coefficient and track reads stay at the voice's rate.  With every entry native nothing
- * runs and nothing is allocated: the batch is the one created. */
+ * runs and nothing is allocated: the batch is the one created.  The call records the request and answers the
+ * geometry at once; the converter's slabs and tables are allocated by the first jb_batch_run, as the loudness and
+ * FLAC ones are, so a device allocation failure for them surfaces there and not from this call. */
 int jb_batch_set_output_rate(jb_batch *b, const uint32_t *out_hz, size_t n);
 /* Rate of utterance utt's PCM as the read entries hand it out (the voice's rate when native); 0 for no such utterance. */
 uint32_t jb_batch_output_rate(const jb_batch *b, size_t utt);

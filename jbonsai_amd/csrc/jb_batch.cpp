@@ -341,24 +341,22 @@ Batch::~Batch()
         stream_release(device, stream);
 }
 
-template <class T> int Batch::dalloc(T **p, size_t n, bool zero)
+int Batch::dalloc_bytes(void **p, size_t bytes, bool zero)
 {
     *p = nullptr;
-    if (n == 0)
-        n = 1;
     void *v = nullptr;
     size_t got = 0;
-    hipError_t e = pool_alloc(device, n * sizeof(T), &v, &got);
+    hipError_t e = pool_alloc(device, bytes, &v, &got);
     if (e != hipSuccess) {
         char msg[128];
-        snprintf(msg, sizeof msg, "hipMalloc(%zu bytes)", n * sizeof(T));
+        snprintf(msg, sizeof msg, "hipMalloc(%zu bytes)", bytes);
         return hip_fail(e, msg);
     }
     allocs.emplace_back(v, got);
-    bytes_alloc += n * sizeof(T);
+    bytes_alloc += bytes;
     if (zero)
-        zero_list.emplace_back(v, std::min(got, (n * sizeof(T) + 15) / 16 * 16));
-    *p = (T *)v;
+        zero_list.emplace_back(v, std::min(got, (bytes + 15) / 16 * 16));
+    *p = v;
     return JB_OK;
 }
 
@@ -1324,6 +1322,7 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
         rc = b->dalloc(&vd.pcm, mlpg_only ? 1 : b->total_samples, false);
     if (rc)
         return rc;
+    b->out.init();
     if ((b->flags & JB_BATCH_KEEP_TRACKS) && !mlpg_only)
         if ((rc = b->dalloc(&vd.exc, b->total_samples, false)))
             return rc;
@@ -1659,9 +1658,8 @@ int Batch::run(bool timed)
     // a previous run's vocoder may still read what this run's parameter generation rewrites
     hipStreamWaitEvent(stream, ev_voc_done, 0);
     last_run_timed = timed;
-    has_run = true;
-    int rc = prepare_loudness();
-    if (rc || (rc = prepare_flac()))
+    int rc = out.prepare();
+    if (rc)
         return rc;
     for (int si = 0; si < kMaxStream; si++)
         if (sd[si].gv_gang_ctl && !from_tracks)
@@ -1699,16 +1697,9 @@ int Batch::run(bool timed)
             return hip_fail(e, "k_voc_verify");
         verify_pending = true;
     }
-    // behind the check: a batch whose hand-offs all pass pays no host round trip for its output rate (finish_verify
-    // converts again what a redo round rewrites)
-    if ((rc = enqueue_resample()))
-        return rc;
-    // loudness: measured on the output f64 and applied behind the converter (finish_verify does both again for what
-    // a redo round rewrites)
-    if ((rc = enqueue_loudness()))
-        return rc;
-    // FLAC: the 16-bit output encoded (finish_verify encodes again what a redo round rewrote)
-    if ((rc = enqueue_flac()))
+    // output rate, loudness, FLAC behind the check: a batch whose hand-offs all pass pays no host round trip for
+    // them (finish_verify does again what a redo round rewrites)
+    if ((rc = out.enqueue()))
         return rc;
     if (timed)
         hipEventRecord(ev3, stream_voc);
@@ -1981,436 +1972,10 @@ int Batch::finish_verify()
                 }
         }
     }
-    // output rate: what run() converted behind the check came in part from PCM these rounds replaced
-    rc = enqueue_resample(&touched);
-    if (rc)
-        return rc;
-    // loudness: the gain is a function of the final PCM
-    rc = enqueue_loudness(&touched);
-    if (rc)
-        return rc;
-    // FLAC: the streams of the utterances these rounds rewrote, then every stream's place
-    return enqueue_flac(&touched);
+    // what run() converted, measured and encoded behind the check came in part from PCM these rounds replaced (the
+    // gain is a function of an utterance's final PCM; the FLAC pack places every stream again)
+    return out.enqueue(&touched);
 }
-
-// ---- FLAC (jb_batch_set_flac) ----
-int Batch::set_flac(const jb_flac_opts *opts)
-{
-    FlacParams p{};
-    int rc = flac_check_opts(opts, &p);
-    if (rc)
-        return rc;
-    if (flags & JB_BATCH_MLPG_ONLY) {
-        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
-        return JB_ERR_INVALID;
-    }
-    if (!(flags & JB_BATCH_PCM_I16)) {
-        set_error("jb_batch_set_flac: FLAC encodes the 16-bit output (JB_BATCH_PCM_I16)");
-        return JB_ERR_INVALID;
-    }
-    if (has_run) {
-        set_error("jb_batch_set_flac: FLAC is set before the batch's first run");
-        return JB_ERR_INVALID;
-    }
-    fl_p = p;
-    fl_on = true;
-    return JB_OK;
-}
-
-// At the first run, when the output rate and the loudness slabs are settled
-int Batch::prepare_flac()
-{
-    if (!fl_on || fl_ready)
-        return JB_OK;
-    std::vector<const int16_t *> xs((size_t)B);
-    std::vector<uint64_t> ns((size_t)B);
-    std::vector<uint32_t> hz((size_t)B);
-    for (size_t u = 0; u < (size_t)B; u++) {
-        xs[u] = out_pcm16() + out_offset(u);
-        ns[u] = out_samples(u);
-        hz[u] = (rs_on && out_hz[u]) ? out_hz[u] : voice.sampling_frequency;
-    }
-    uint64_t slot_bytes = 0, bound = 0;
-    int rc = flac_plan(fl_p, xs.data(), ns.data(), hz.data(), (size_t)B, &fl_utts, &fl_work, &slot_bytes, &bound);
-    if (rc)
-        return rc;
-    const size_t nf = std::max<size_t>(fl_work.size(), 1);
-    if ((rc = dalloc(&fl_slots, std::max<uint64_t>(slot_bytes, 4), false)) ||
-        (rc = dalloc(&fl_out, std::max<uint64_t>(bound, 4), false)) ||
-        (rc = dalloc(&fl_utts_dev, std::max<size_t>((size_t)B, 1), false)) || (rc = dalloc(&fl_work_dev, nf, false)) ||
-        (rc = dalloc(&fl_redo_dev, nf, false)) || (rc = dalloc(&fl_fsize, nf, false)) ||
-        (rc = dalloc(&fl_foff, nf, false)) || (rc = dalloc(&fl_res, std::max<size_t>((size_t)B, 1), false)) ||
-        (rc = dalloc(&fl_total, 1, false)))
-        return rc;
-    flac_bind(&fl_utts, fl_slots);
-    hipError_t e = hipSuccess;
-    if ((B > 0 && (e = hipMemcpy(fl_utts_dev, fl_utts.data(), sizeof(FlacUtt) * (size_t)B, hipMemcpyHostToDevice)) !=
-                      hipSuccess) ||
-        (!fl_work.empty() && (e = hipMemcpy(fl_work_dev, fl_work.data(), sizeof(FlacWork) * fl_work.size(),
-                                            hipMemcpyHostToDevice)) != hipSuccess))
-        return hip_fail(e, "FLAC work list");
-    fl_ready = true;
-    return JB_OK;
-}
-
-int Batch::enqueue_flac(const std::vector<uint8_t> *only)
-{
-    if (!fl_on || !fl_ready)
-        return JB_OK;
-    hipError_t e;
-    const uint32_t nw = (uint32_t)fl_work.size();
-    if (!only) {
-        if ((e = launch_flac_encode(fl_p, fl_utts_dev, fl_work_dev, nw, fl_fsize, stream_voc)) != hipSuccess ||
-            (e = launch_flac_pack(fl_p, fl_utts_dev, (uint32_t)B, fl_work_dev, nw, fl_fsize, fl_foff, fl_res, fl_total,
-                                  fl_out, stream_voc)) != hipSuccess)
-            return hip_fail(e, "FLAC");
-        return JB_OK;
-    }
-    // the blocks of the utterances a redo touched; then every stream's offsets and place again
-    std::vector<FlacWork> sub;
-    for (const FlacWork &w : fl_work)
-        if ((*only)[w.utt])
-            sub.push_back(w);
-    if (sub.empty())
-        return JB_OK;
-    if ((e = hipMemcpy(fl_redo_dev, sub.data(), sizeof(FlacWork) * sub.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = launch_flac_encode(fl_p, fl_utts_dev, fl_redo_dev, (uint32_t)sub.size(), fl_fsize, stream_voc)) !=
-            hipSuccess ||
-        (e = launch_flac_pack(fl_p, fl_utts_dev, (uint32_t)B, fl_work_dev, nw, fl_fsize, fl_foff, fl_res, fl_total,
-                              fl_out, stream_voc)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
-        return hip_fail(e, "FLAC(redo)");
-    return JB_OK;
-}
-
-int Batch::read_flac_index(std::vector<FlacOut> *res, uint64_t *total)
-{
-    if (!fl_on || !fl_ready) {
-        set_error(fl_on ? "FLAC: the batch has not run" : "FLAC: jb_batch_set_flac was not called");
-        return JB_ERR_INVALID;
-    }
-    res->assign((size_t)B, FlacOut{});
-    int rc = B > 0 ? read(fl_res, res->data(), sizeof(FlacOut) * (size_t)B) : sync();
-    if (rc)
-        return rc;
-    *total = 0;
-    for (const FlacOut &o : *res)
-        *total = std::max<uint64_t>(*total, o.off + o.bytes);
-    return JB_OK;
-}
-
-// ---- loudness target (jb_batch_set_loudness_target) ----
-int Batch::set_loudness(const double *target, const double *ceiling, size_t n)
-{
-    if (flags & JB_BATCH_MLPG_ONLY) {
-        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
-        return JB_ERR_INVALID;
-    }
-    if (has_run) {
-        set_error("jb_batch_set_loudness_target: the target is set before the batch's first run");
-        return JB_ERR_INVALID;
-    }
-    if (!target || !ceiling || (n != 1 && n != (size_t)B)) {
-        set_error("jb_batch_set_loudness_target: give one target, or one per utterance");
-        return JB_ERR_INVALID;
-    }
-    ln_target.assign((size_t)B, 0.0);
-    ln_ceiling.assign((size_t)B, 0.0);
-    for (size_t u = 0; u < (size_t)B; u++) {
-        ln_target[u] = target[n == 1 ? 0 : u];
-        ln_ceiling[u] = ceiling[n == 1 ? 0 : u];
-    }
-    ln_on = true;
-    return JB_OK;
-}
-
-// At the first run, when the output rate is settled: the f64 the measurement reads (the vocoder's or the
-// converter's, made f64 where the flags asked for 16 bits), the output slab, the per-rate tables and the lists
-int Batch::prepare_loudness()
-{
-    if (!ln_on || ln_ready)
-        return JB_OK;
-    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0;
-    int rc;
-    hipError_t e;
-    const double *src = nullptr;
-    if (rs_on) {
-        if (i16) {
-            // the converter writes f64 for the measurement; the apply pass writes the 16-bit slab it wrote before
-            if ((rc = dalloc(&ln_src64, std::max<size_t>(out_total(), 1), false)))
-                return rc;
-            for (size_t u = 0; u < (size_t)B; u++)
-                for (uint32_t t = rs_tile_lo[u]; t < rs_tile_lo[u + 1]; t++)
-                    rs_tiles[t].y = ln_src64 + rs_off[u];
-            if (!rs_tiles.empty() && (e = hipMemcpy(rs_tiles_dev, rs_tiles.data(), sizeof(ResampleTile) * rs_tiles.size(),
-                                                    hipMemcpyHostToDevice)) != hipSuccess)
-                return hip_fail(e, "resample work list");
-            src = ln_src64;
-            ln_pcm16 = rs_pcm16;
-        } else {
-            src = rs_pcm;
-        }
-    } else if (i16) {
-        // the vocoder writes f64 for the measurement; the apply pass writes the batch's 16-bit slab
-        if ((rc = dalloc(&ln_src64, std::max<size_t>(total_samples, 1), false)))
-            return rc;
-        ln_pcm16 = vd.pcm16;
-        vd.pcm = ln_src64;
-        vd.pcm16 = nullptr;
-        src = ln_src64;
-    } else {
-        src = vd.pcm;
-    }
-    if (!i16 && (rc = dalloc(&ln_pcm, std::max<size_t>(out_total(), 1), false)))
-        return rc;
-    std::vector<LoudnessRate> rates;
-    ln_utts.assign((size_t)B, LoudnessUtt{});
-    uint64_t tiles = 0, atiles = 0;
-    for (size_t u = 0; u < (size_t)B; u++) {
-        const uint32_t hz = (rs_on && out_hz[u]) ? out_hz[u] : voice.sampling_frequency;
-        size_t r = 0;
-        while (r < rates.size() && rates[r].hz != hz)
-            r++;
-        if (r == rates.size()) {
-            LoudnessRate lr{};
-            if ((rc = loudness_rate(hz, &lr)))
-                return rc;
-            rates.push_back(lr);
-        }
-        LoudnessUtt &w = ln_utts[u];
-        const size_t off = out_offset(u);
-        w.x = src + off;
-        w.y = i16 ? (void *)(ln_pcm16 + off) : (void *)(ln_pcm + off);
-        w.n = out_samples(u);
-        w.ntiles = loudness_tiles(rates[r], w.n);
-        w.tile0 = w.lt0 = tiles;
-        w.at0 = atiles;
-        w.rate = (uint32_t)r;
-        w.slot = (uint32_t)u;
-        w.target = ln_target[u];
-        w.ceiling = ln_ceiling[u];
-        tiles += w.ntiles;
-        atiles += (w.n + kLnApplyTile - 1) / kLnApplyTile;
-    }
-    if ((rc = dalloc(&ln_rates_dev, rates.size(), false)) || (rc = dalloc(&ln_utts_dev, (size_t)B, false)) ||
-        (rc = dalloc(&ln_redo_dev, (size_t)B, false)) || (rc = dalloc(&ln_st, 4 * std::max<uint64_t>(tiles, 1), false)) ||
-        (rc = dalloc(&ln_pk, std::max<uint64_t>(tiles, 1), false)) ||
-        (rc = dalloc(&ln_z, std::max<uint64_t>(tiles, 1), false)) || (rc = dalloc(&ln_res, (size_t)B, false)))
-        return rc;
-    if ((e = hipMemcpy(ln_rates_dev, rates.data(), sizeof(LoudnessRate) * rates.size(), hipMemcpyHostToDevice)) !=
-            hipSuccess ||
-        (B > 0 && (e = hipMemcpy(ln_utts_dev, ln_utts.data(), sizeof(LoudnessUtt) * (size_t)B, hipMemcpyHostToDevice)) !=
-                      hipSuccess))
-        return hip_fail(e, "loudness work list");
-    ln_tiles = tiles;
-    ln_atiles = atiles;
-    ln_ready = true;
-    return JB_OK;
-}
-
-int Batch::enqueue_loudness(const std::vector<uint8_t> *only)
-{
-    if (!ln_on || !ln_ready)
-        return JB_OK;
-    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0;
-    hipError_t e;
-    if (!only) {
-        if ((e = launch_loudness_measure(ln_rates_dev, ln_utts_dev, (uint32_t)B, ln_tiles, ln_st, ln_pk, ln_z, ln_res,
-                                         stream_voc)) != hipSuccess ||
-            (e = launch_loudness_apply(ln_utts_dev, (uint32_t)B, ln_atiles, ln_res, i16, stream_voc)) != hipSuccess)
-            return hip_fail(e, "loudness");
-        return JB_OK;
-    }
-    // the utterances a redo touched, renumbered (their scratch stays where it is)
-    std::vector<LoudnessUtt> sub;
-    uint64_t tiles = 0, atiles = 0;
-    for (size_t u = 0; u < (size_t)B; u++)
-        if ((*only)[u]) {
-            LoudnessUtt w = ln_utts[u];
-            w.lt0 = tiles;
-            w.at0 = atiles;
-            tiles += w.ntiles;
-            atiles += (w.n + kLnApplyTile - 1) / kLnApplyTile;
-            sub.push_back(w);
-        }
-    if (sub.empty())
-        return JB_OK;
-    if ((e = hipMemcpy(ln_redo_dev, sub.data(), sizeof(LoudnessUtt) * sub.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = launch_loudness_measure(ln_rates_dev, ln_redo_dev, (uint32_t)sub.size(), tiles, ln_st, ln_pk, ln_z, ln_res,
-                                     stream_voc)) != hipSuccess ||
-        (e = launch_loudness_apply(ln_redo_dev, (uint32_t)sub.size(), atiles, ln_res, i16, stream_voc)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
-        return hip_fail(e, "loudness(redo)");
-    return JB_OK;
-}
-
-const double *Batch::out_pcm64() const { return ln_on ? ln_pcm : rs_on ? rs_pcm : vd.pcm; }
-const int16_t *Batch::out_pcm16() const { return ln_on ? ln_pcm16 : rs_on ? rs_pcm16 : vd.pcm16; }
-
-// ---- output rate (jb_batch_set_output_rate) ----
-int Batch::set_output_rate(const uint32_t *hz, size_t n)
-{
-    if (flags & JB_BATCH_MLPG_ONLY) {
-        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
-        return JB_ERR_INVALID;
-    }
-    if (has_run) {
-        set_error("jb_batch_set_output_rate: the output rate is set before the batch's first run");
-        return JB_ERR_INVALID;
-    }
-    if (!hz || (n != 1 && n != (size_t)B)) {
-        set_error("jb_batch_set_output_rate: give one rate, or one per utterance");
-        return JB_ERR_INVALID;
-    }
-    const uint32_t in = voice.sampling_frequency;
-    std::vector<uint32_t> want((size_t)B);
-    bool any = false;
-    int rc;
-    for (size_t u = 0; u < (size_t)B; u++) {
-        const uint32_t h = hz[n == 1 ? 0 : u];
-        want[u] = h == in ? 0 : h;
-        if (want[u] && (rc = resample_design(in, want[u], nullptr, nullptr)))
-            return rc;
-        any = any || want[u];
-    }
-    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0;
-    if (!any) { // (again) all native: the batch as created
-        if (i16 && rs_on) {
-            vd.pcm16 = rs_sink16;
-            vd.pcm = nullptr;
-        }
-        out_hz = want;
-        rs_on = false;
-        return JB_OK;
-    }
-    // Everything is built in locals first and committed at the end: a failure leaves the batch as it was (a 16-bit
-    // batch keeps its sink)
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess)
-        return hip_fail(e, "hipSetDevice");
-    // one table per distinct rate; native utterances go through the identity table (a copy / the 16-bit conversion)
-    std::vector<ResampleTable> tables;
-    std::vector<uint32_t> rate_of_table, table_of((size_t)B);
-    for (size_t u = 0; u < (size_t)B; u++) {
-        const uint32_t h = want[u] ? want[u] : in;
-        size_t t = std::find(rate_of_table.begin(), rate_of_table.end(), h) - rate_of_table.begin();
-        if (t == rate_of_table.size()) {
-            ResampleTable tb{};
-            if ((rc = resample_table(device, in, h, &tb)))
-                return rc;
-            rate_of_table.push_back(h);
-            tables.push_back(tb);
-        }
-        table_of[u] = (uint32_t)t;
-    }
-    std::vector<uint64_t> off((size_t)B + 1, 0);
-    for (size_t u = 0; u < (size_t)B; u++) {
-        const ResampleTable &tb = tables[table_of[u]];
-        off[u + 1] = off[u] + resample_out_len((uint64_t)T[u] * voice.fperiod, tb.L, tb.M);
-    }
-    const size_t n_out = (size_t)off[(size_t)B];
-    // the converter reads f64: a 16-bit batch's vocoder writes an f64 slab of its own from now on, and the 16-bit
-    // conversion moves into k_resample
-    double *f64 = vd.pcm;
-    if (!f64 && !rs_vpcm && (rc = dalloc(&rs_vpcm, std::max<size_t>(total_samples, 1), false)))
-        return rc;
-    if (!f64)
-        f64 = rs_vpcm;
-    int16_t *sink = rs_on ? rs_sink16 : vd.pcm16;
-    double *out64 = nullptr;
-    int16_t *out16 = nullptr;
-    if (i16) {
-        // the 16-bit slab the batch was made with is big enough when the rates go down
-        out16 = sink;
-        if (n_out > total_samples && (rc = dalloc(&out16, std::max<size_t>(n_out, 1), false)))
-            return rc;
-    } else if ((rc = dalloc(&out64, std::max<size_t>(n_out, 1), false))) {
-        return rc;
-    }
-    void *slab = i16 ? (void *)out16 : (void *)out64;
-    const size_t elem = i16 ? sizeof(int16_t) : sizeof(double);
-    std::vector<ResampleTile> tiles;
-    std::vector<uint32_t> tile_lo((size_t)B + 1, 0);
-    for (size_t u = 0; u < (size_t)B; u++) {
-        tile_lo[u] = (uint32_t)tiles.size();
-        resample_tiles(tables[table_of[u]], table_of[u], f64 + (size_t)frame_off[u] * voice.fperiod,
-                       (uint64_t)T[u] * voice.fperiod, (char *)slab + off[u] * elem, off[u + 1] - off[u], tiles);
-    }
-    tile_lo[(size_t)B] = (uint32_t)tiles.size();
-    size_t lds = 0;
-    for (const ResampleTable &tb : tables)
-        lds = std::max<size_t>(lds, tb.lds_bytes);
-    ResampleTable *tables_dev = nullptr;
-    ResampleTile *tiles_dev = nullptr;
-    if ((rc = dalloc(&tables_dev, tables.size(), false)) ||
-        (rc = dalloc(&tiles_dev, std::max<size_t>(tiles.size(), 1), false)))
-        return rc;
-    if ((e = hipMemcpy(tables_dev, tables.data(), sizeof(ResampleTable) * tables.size(), hipMemcpyHostToDevice)) !=
-            hipSuccess ||
-        (!tiles.empty() &&
-         (e = hipMemcpy(tiles_dev, tiles.data(), sizeof(ResampleTile) * tiles.size(), hipMemcpyHostToDevice)) !=
-             hipSuccess))
-        return hip_fail(e, "resample work list");
-    // commit
-    out_hz = want;
-    rs_tables = std::move(tables);
-    rs_off = std::move(off);
-    rs_tiles = std::move(tiles);
-    rs_tile_lo = std::move(tile_lo);
-    rs_lds = lds;
-    rs_tables_dev = tables_dev;
-    rs_tiles_dev = tiles_dev;
-    rs_pcm = out64;
-    rs_pcm16 = out16;
-    if (i16) {
-        rs_sink16 = sink;
-        vd.pcm = f64;
-        vd.pcm16 = nullptr;
-    }
-    rs_on = true;
-    return JB_OK;
-}
-
-int Batch::enqueue_resample(const std::vector<uint8_t> *only)
-{
-    if (!rs_on)
-        return JB_OK;
-    // (with a loudness target the converter writes f64 for the measurement, and the apply pass the 16 bits)
-    const bool i16 = (flags & JB_BATCH_PCM_I16) != 0 && !ln_on;
-    hipError_t e;
-    if (!only) {
-        if ((e = launch_resample(rs_tables_dev, rs_tiles_dev, (uint32_t)rs_tiles.size(), i16, rs_lds, stream_voc)) !=
-            hipSuccess)
-            return hip_fail(e, "k_resample");
-        return JB_OK;
-    }
-    std::vector<ResampleTile> sub;
-    for (size_t u = 0; u < (size_t)B; u++)
-        if ((*only)[u])
-            sub.insert(sub.end(), rs_tiles.begin() + rs_tile_lo[u], rs_tiles.begin() + rs_tile_lo[u + 1]);
-    if (sub.empty())
-        return JB_OK;
-    // the list of a redo's tiles, allocated when a redo first needs it (most steps redo nothing)
-    if (sub.size() > rs_redo_cap) {
-        int rc = dalloc(&rs_redo_dev, sub.size(), false);
-        if (rc)
-            return rc;
-        rs_redo_cap = sub.size();
-    }
-    if ((e = hipMemcpy(rs_redo_dev, sub.data(), sizeof(ResampleTile) * sub.size(), hipMemcpyHostToDevice)) !=
-            hipSuccess ||
-        (e = launch_resample(rs_tables_dev, rs_redo_dev, (uint32_t)sub.size(), i16, rs_lds, stream_voc)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
-        return hip_fail(e, "k_resample(redo)");
-    return JB_OK;
-}
-
-size_t Batch::out_samples(size_t u) const
-{
-    return rs_on ? (size_t)(rs_off[u + 1] - rs_off[u]) : (size_t)T[u] * voice.fperiod;
-}
-size_t Batch::out_offset(size_t u) const { return rs_on ? (size_t)rs_off[u] : (size_t)frame_off[u] * voice.fperiod; }
-size_t Batch::out_total() const { return rs_on ? (size_t)rs_off[(size_t)B] : total_samples; }
 
 int Batch::sync()
 {
@@ -2562,7 +2127,7 @@ int stage_ring(int device, StageRing **out)
 
 int Batch::read_pcm_split(void *const *dst, size_t elem)
 {
-    const char *slab = elem == 2 ? (const char *)out_pcm16() : (const char *)out_pcm64();
+    const char *slab = elem == 2 ? (const char *)out.pcm16() : (const char *)out.pcm64();
     if (flags & JB_BATCH_MLPG_ONLY) {
         set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
@@ -2571,7 +2136,7 @@ int Batch::read_pcm_split(void *const *dst, size_t elem)
         set_error(elem == 2 ? "16-bit PCM needs JB_BATCH_PCM_I16" : "f64 PCM was replaced by the 16-bit sink");
         return JB_ERR_INVALID;
     }
-    const size_t total = out_total() * elem;
+    const size_t total = out.total() * elem;
     if (total == 0)
         return JB_OK;
     int rc = sync();
@@ -2585,7 +2150,7 @@ int Batch::read_pcm_split(void *const *dst, size_t elem)
     // byte offset of every utterance in the slab (utterances are contiguous, in batch order)
     std::vector<size_t> uoff((size_t)B + 1);
     for (int u = 0; u <= B; u++)
-        uoff[u] = out_offset((size_t)u) * elem;
+        uoff[u] = out.offset((size_t)u) * elem;
     const size_t nchunks = (total + kStageSlot - 1) / kStageSlot;
     if (nchunks <= 4 && nchunks <= (size_t)kStageSlots) {
         // a small request (one sentence: 0.5 MB; a 21 s text: 8 MB): its few copies issued at once and scattered on
@@ -2863,18 +2428,18 @@ size_t jb_batch_num_frames(const jb_batch *hb, size_t i)
 size_t jb_batch_num_samples(const jb_batch *hb, size_t i)
 {
     const Batch *b = (const Batch *)hb;
-    return (b && i < (size_t)b->B) ? b->out_samples(i) : 0;
+    return (b && i < (size_t)b->B) ? b->out.samples(i) : 0;
 }
-size_t jb_batch_total_samples(const jb_batch *b) { return b ? ((const Batch *)b)->out_total() : 0; }
+size_t jb_batch_total_samples(const jb_batch *b) { return b ? ((const Batch *)b)->out.total() : 0; }
 size_t jb_batch_pcm_offset(const jb_batch *hb, size_t i)
 {
     const Batch *b = (const Batch *)hb;
-    return (b && i <= (size_t)b->B) ? b->out_offset(i) : 0;
+    return (b && i <= (size_t)b->B) ? b->out.offset(i) : 0;
 }
 
 int jb_batch_set_output_rate(jb_batch *hb, const uint32_t *out_hz, size_t n)
 {
-    return hb ? ((Batch *)hb)->set_output_rate(out_hz, n) : JB_ERR_INVALID;
+    return hb ? ((Batch *)hb)->out.set_output_rate(out_hz, n) : JB_ERR_INVALID;
 }
 
 uint32_t jb_batch_output_rate(const jb_batch *hb, size_t i)
@@ -2882,7 +2447,7 @@ uint32_t jb_batch_output_rate(const jb_batch *hb, size_t i)
     const Batch *b = (const Batch *)hb;
     if (!b || i >= (size_t)b->B)
         return 0;
-    return (b->rs_on && b->out_hz[i]) ? b->out_hz[i] : b->voice.sampling_frequency;
+    return b->out.utt(i).hz;
 }
 
 int jb_batch_set_loudness_target(jb_batch *hb, const double *target_lufs, size_t n, double ceiling_dbfs)
@@ -2890,7 +2455,7 @@ int jb_batch_set_loudness_target(jb_batch *hb, const double *target_lufs, size_t
     if (!hb)
         return JB_ERR_INVALID;
     std::vector<double> ceil(n ? n : 1, ceiling_dbfs);
-    return ((Batch *)hb)->set_loudness(target_lufs, ceil.data(), n);
+    return ((Batch *)hb)->out.set_loudness(target_lufs, ceil.data(), n);
 }
 
 int jb_batch_loudness(jb_batch *hb, size_t utt, double *lufs, double *peak_dbfs, double *gain_db)
@@ -2898,12 +2463,8 @@ int jb_batch_loudness(jb_batch *hb, size_t utt, double *lufs, double *peak_dbfs,
     Batch *b = (Batch *)hb;
     if (!b || utt >= (size_t)b->B)
         return JB_ERR_INVALID;
-    if (!b->ln_on || !b->ln_ready) {
-        jb::set_error(b->ln_on ? "jb_batch_loudness: the batch has not run" : "jb_batch_loudness: no loudness target is set");
-        return JB_ERR_INVALID;
-    }
     jb::LoudnessResult r{};
-    int rc = b->read(b->ln_res + utt, &r, sizeof r);
+    int rc = b->out.read_loudness(utt, &r);
     if (rc)
         return rc;
     if (lufs)
@@ -2919,7 +2480,7 @@ int jb_batch_set_flac(jb_batch *hb, const jb_flac_opts *opts)
 {
     if (!hb)
         return JB_ERR_INVALID;
-    return ((Batch *)hb)->set_flac(opts);
+    return ((Batch *)hb)->out.set_flac(opts);
 }
 
 int jb_batch_flac_size(jb_batch *hb, size_t utt, size_t *n_bytes)
@@ -2927,12 +2488,8 @@ int jb_batch_flac_size(jb_batch *hb, size_t utt, size_t *n_bytes)
     Batch *b = (Batch *)hb;
     if (!b || !n_bytes || utt >= (size_t)b->B)
         return JB_ERR_INVALID;
-    if (!b->fl_on || !b->fl_ready) {
-        jb::set_error(b->fl_on ? "FLAC: the batch has not run" : "FLAC: jb_batch_set_flac was not called");
-        return JB_ERR_INVALID;
-    }
     jb::FlacOut o{};
-    int rc = b->read(b->fl_res + utt, &o, sizeof o);
+    int rc = b->out.read_flac_index(utt, &o);
     if (rc)
         return rc;
     *n_bytes = (size_t)o.bytes;
@@ -2944,19 +2501,15 @@ int jb_batch_read_flac(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
     Batch *b = (Batch *)hb;
     if (!b || utt >= (size_t)b->B)
         return JB_ERR_INVALID;
-    if (!b->fl_on || !b->fl_ready) {
-        jb::set_error(b->fl_on ? "FLAC: the batch has not run" : "FLAC: jb_batch_set_flac was not called");
-        return JB_ERR_INVALID;
-    }
     jb::FlacOut o{};
-    int rc = b->read(b->fl_res + utt, &o, sizeof o);
+    int rc = b->out.read_flac_index(utt, &o);
     if (rc)
         return rc;
     if (cap < o.bytes)
         return JB_ERR_BUFFER;
     if (!dst)
         return JB_ERR_INVALID;
-    return b->read(b->fl_out + o.off, dst, (size_t)o.bytes, false);
+    return b->out.read_flac(o, dst);
 }
 
 int jb_batch_read_flac_all(jb_batch *hb, uint8_t *const *dst)
@@ -2965,21 +2518,13 @@ int jb_batch_read_flac_all(jb_batch *hb, uint8_t *const *dst)
     if (!b || (!dst && b->B))
         return JB_ERR_INVALID;
     std::vector<jb::FlacOut> res;
-    uint64_t total = 0;
-    int rc = b->read_flac_index(&res, &total);
+    std::unique_ptr<uint8_t[]> host;
+    int rc = b->out.read_flac_all(&res, &host);
     if (rc)
         return rc;
     for (size_t u = 0; u < (size_t)b->B; u++)
         if (!dst[u] && res[u].bytes)
             return JB_ERR_INVALID;
-    // one copy of the used bytes (not zero-filled first), then the streams into the callers' buffers
-    std::unique_ptr<uint8_t[]> host(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
-    if (!host) {
-        jb::set_error("out of host memory");
-        return JB_ERR_INVALID;
-    }
-    if (total && (rc = b->read(b->fl_out, host.get(), (size_t)total, false)))
-        return rc;
     for (size_t u = 0; u < (size_t)b->B; u++)
         memcpy(dst[u], host.get() + res[u].off, (size_t)res[u].bytes);
     return JB_OK;
@@ -2994,7 +2539,8 @@ int jb_batch_read_pcm_native(jb_batch *hb, size_t i, double *dst, size_t cap)
         jb::set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
     }
-    if (!b->vd.pcm) {
+    const double *native = b->out.native64();
+    if (!native) {
         jb::set_error("a JB_BATCH_PCM_I16 batch without an output rate or a loudness target has no f64 PCM");
         return JB_ERR_INVALID;
     }
@@ -3007,7 +2553,7 @@ int jb_batch_read_pcm_native(jb_batch *hb, size_t i, double *dst, size_t cap)
         return JB_OK;
     if (!dst)
         return JB_ERR_INVALID;
-    return b->read(b->vd.pcm + (size_t)b->frame_off[i] * b->voice.fperiod, dst, ns * sizeof(double));
+    return b->read(native + (size_t)b->frame_off[i] * b->voice.fperiod, dst, ns * sizeof(double));
 }
 void *jb_batch_device_pcm(jb_batch *hb, size_t *n)
 {
@@ -3015,12 +2561,10 @@ void *jb_batch_device_pcm(jb_batch *hb, size_t *n)
     if (!b)
         return nullptr;
     if (n)
-        *n = b->out_total();
+        *n = b->out.total();
     if ((b->flags & JB_BATCH_MLPG_ONLY) || b->sync()) // the slab is handed out finished and certified
         return nullptr;
-    if (b->ln_on || b->rs_on) // loudness target / output rate: the slab the read entries hand out
-        return b->out_pcm64() ? (void *)b->out_pcm64() : (void *)b->out_pcm16();
-    return b->vd.pcm ? (void *)b->vd.pcm : (void *)b->vd.pcm16; // i16 slab for JB_BATCH_PCM_I16 batches
+    return (void *)b->out.pcm(); // the slab the read entries hand out: f64, or 16-bit for JB_BATCH_PCM_I16 batches
 }
 
 int jb_batch_read_pcm(jb_batch *hb, size_t i, double *dst, size_t cap)
@@ -3032,7 +2576,7 @@ int jb_batch_read_pcm(jb_batch *hb, size_t i, double *dst, size_t cap)
         jb::set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
     }
-    size_t ns = b->out_samples(i);
+    size_t ns = b->out.samples(i);
     if (cap < ns) {
         jb::set_error("pcm buffer too small");
         return JB_ERR_BUFFER;
@@ -3041,12 +2585,12 @@ int jb_batch_read_pcm(jb_batch *hb, size_t i, double *dst, size_t cap)
         return JB_OK;
     if (!dst)
         return JB_ERR_INVALID;
-    const double *slab = b->out_pcm64();
+    const double *slab = b->out.pcm64();
     if (!slab) {
         jb::set_error("batch was created with JB_BATCH_PCM_I16: use jb_batch_read_pcm_i16");
         return JB_ERR_INVALID;
     }
-    return b->read(slab + b->out_offset(i), dst, ns * sizeof(double));
+    return b->read(slab + b->out.offset(i), dst, ns * sizeof(double));
 }
 
 int jb_batch_read_pcm_i16(jb_batch *hb, size_t i, int16_t *dst, size_t cap)
@@ -3058,12 +2602,12 @@ int jb_batch_read_pcm_i16(jb_batch *hb, size_t i, int16_t *dst, size_t cap)
         jb::set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
         return JB_ERR_INVALID;
     }
-    const int16_t *slab = b->out_pcm16();
+    const int16_t *slab = b->out.pcm16();
     if (!slab) {
         jb::set_error("batch was created without JB_BATCH_PCM_I16");
         return JB_ERR_INVALID;
     }
-    size_t ns = b->out_samples(i);
+    size_t ns = b->out.samples(i);
     if (cap < ns) {
         jb::set_error("pcm buffer too small");
         return JB_ERR_BUFFER;
@@ -3072,7 +2616,7 @@ int jb_batch_read_pcm_i16(jb_batch *hb, size_t i, int16_t *dst, size_t cap)
         return JB_OK;
     if (!dst)
         return JB_ERR_INVALID;
-    return b->read(slab + b->out_offset(i), dst, ns * sizeof(int16_t));
+    return b->read(slab + b->out.offset(i), dst, ns * sizeof(int16_t));
 }
 
 int jb_batch_read_pcm_all(jb_batch *hb, double *const *dst)

@@ -610,7 +610,7 @@ struct Generator {
     bool serial_armed = false;  // the side stream waits for parameter generation
     std::vector<double> cache;  // PCM of frames [cache_first, cache_first + cache_frames)
     size_t cache_first = 0, cache_frames = 0;
-    // output rate L/M of the voice's (batch->rs_on): step k hands out samples [ceil(k F L / M), ceil((k+1) F L / M))
+    // output rate L/M of the voice's (the batch converts): step k hands out samples [ceil(k F L / M), ceil((k+1) F L / M))
     // of the converted utterance, read whole into `cache` by the first step
     uint64_t L = 1, M = 1;
     size_t out_start(size_t k) const { return (size_t)(((uint64_t)k * fperiod * L + M - 1) / M); }
@@ -1133,7 +1133,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             rates[u - lo] = (uint32_t)eng(u)->cond.output_rate;
             any_rate = any_rate || rates[u - lo];
         }
-        if (any_rate && (rc = b->set_output_rate(rates.data(), rates.size())))
+        if (any_rate && (rc = b->out.set_output_rate(rates.data(), rates.size())))
             return rc;
         // loudness: each utterance's engine's own target and ceiling; an engine without a target leaves its
         // utterance as it is (measured, gain 0 dB: bit for bit the same) when another engine of the batch has one
@@ -1145,9 +1145,9 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             ceilings[u - lo] = on ? eng(u)->cond.peak_ceiling : INFINITY;
             any_target = any_target || on;
         }
-        if (any_target && (rc = b->set_loudness(targets.data(), ceilings.data(), targets.size())))
+        if (any_target && (rc = b->out.set_loudness(targets.data(), ceilings.data(), targets.size())))
             return rc;
-        if (flac && (rc = b->set_flac(flac_opts)))
+        if (flac && (rc = b->out.set_flac(flac_opts)))
             return rc;
         rc = b->run(false);
         t_create += ms(t0, now());
@@ -1167,15 +1167,8 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         if (flac) {
             // the streams' sizes and places (one small copy), then the used bytes of the compact slab in one copy
             std::vector<jb::FlacOut> res;
-            uint64_t total = 0;
-            if ((rc = b->read_flac_index(&res, &total)))
-                return rc;
-            std::unique_ptr<uint8_t[]> host(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
-            if (!host) {
-                jb::set_error("out of host memory");
-                return JB_ERR_INVALID;
-            }
-            if (total && (rc = b->read(b->fl_out, host.get(), (size_t)total, false)))
+            std::unique_ptr<uint8_t[]> host;
+            if ((rc = b->out.read_flac_all(&res, &host)))
                 return rc;
             for (size_t u = lo; u < hi; u++) {
                 const jb::FlacOut &o = res[u - lo];
@@ -1191,7 +1184,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             return JB_OK;
         }
         for (size_t u = lo; u < hi; u++) {
-            const size_t ns = b->out_samples(u - lo);
+            const size_t ns = b->out.samples(u - lo);
             n_samples[u] = ns;
             if (!ns)
                 continue;
@@ -1446,26 +1439,21 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     g->total = b->T[0];
     if (CENG(e)->cond.output_rate) {
         const uint32_t hz = (uint32_t)CENG(e)->cond.output_rate;
-        ResampleSpec sp{};
-        if ((rc = b->set_output_rate(&hz, 1)))
+        if ((rc = b->out.set_output_rate(&hz, 1)))
             return rc;
-        if (b->rs_on && (rc = resample_design(b->voice.sampling_frequency, hz, &sp, nullptr)) == JB_OK) {
-            g->L = sp.L;
-            g->M = sp.M;
-        }
-        if (rc)
-            return rc;
+        g->L = b->out.utt(0).L;
+        g->M = b->out.utt(0).M;
     }
     if (!std::isnan(CENG(e)->cond.loudness_target)) {
         const double t = CENG(e)->cond.loudness_target, c = CENG(e)->cond.peak_ceiling;
-        if ((rc = b->set_loudness(&t, &c, 1)))
+        if ((rc = b->out.set_loudness(&t, &c, 1)))
             return rc;
     }
     // Engine::generator runs all three MLPGs before returning (src/engine.rs:333-357); here they are
     // enqueued, with the vocoder behind them, and the call returns while the device works
     // (no serially served head with an output rate either: the converted samples of a frame need its successors)
     // (nor with a loudness target: the gain needs every sample)
-    if ((!b->invariant && !b->rs_on && !b->ln_on && (rc = b->build_generator_work())) || (rc = b->run(false)))
+    if ((!b->invariant && !b->out.active() && (rc = b->build_generator_work())) || (rc = b->run(false)))
         return rc;
     *out = (jb_generator *)g.release();
     return JB_OK;
@@ -1532,9 +1520,9 @@ static long generator_out(jb::Generator *g, double *buf, size_t buf_len, size_t 
     int rc = generator_finish(g);
     if (rc)
         return rc;
-    if (g->cache.empty() && b->out_samples(0)) {
-        g->cache.resize(b->out_samples(0));
-        if ((rc = b->read(b->out_pcm64() + b->out_offset(0), g->cache.data(), g->cache.size() * sizeof(double), false)))
+    if (g->cache.empty() && b->out.samples(0)) {
+        g->cache.resize(b->out.samples(0));
+        if ((rc = b->read(b->out.pcm64() + b->out.offset(0), g->cache.data(), g->cache.size() * sizeof(double), false)))
             return rc;
     }
     const size_t lo = g->out_start(g->next);
@@ -1555,7 +1543,7 @@ long jb_generator_step(jb_generator *hg, double *buf, size_t buf_len)
         return JB_ERR_INVALID;
     if (g->total <= g->next)
         return 0;
-    if (g->batch->rs_on || g->batch->ln_on)
+    if (g->batch->out.active())
         return generator_out(g, buf, buf_len, 1);
     if (buf_len < g->fperiod || !buf) {
         set_error("The length of speech buffer must be larger than fperiod.");
@@ -1626,7 +1614,7 @@ long jb_generator_step_n(jb_generator *hg, double *buf, size_t buf_len, size_t m
         return JB_ERR_INVALID;
     if (g->total <= g->next || max_frames == 0)
         return 0;
-    if (g->batch->rs_on || g->batch->ln_on)
+    if (g->batch->out.active())
         return generator_out(g, buf, buf_len, max_frames);
     if (buf_len < g->fperiod || !buf) {
         set_error("The length of speech buffer must be larger than fperiod.");

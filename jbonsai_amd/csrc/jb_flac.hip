@@ -888,7 +888,8 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
         set_error("no HIP device");
         return JB_ERR_DEVICE;
     }
-    if (dev != prev && hipSetDevice(dev) != hipSuccess) {
+    DeviceScratch scratch;
+    if (scratch.enter(dev) != hipSuccess) {
         set_error("hipSetDevice failed");
         return JB_ERR_DEVICE;
     }
@@ -905,7 +906,7 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
     std::vector<FlacOut> res(n);
     std::vector<uint8_t> host;
     uint64_t slot_bytes = 0, bound = 0, total = 0;
-    hipError_t e = hipMalloc((void **)&dx, sizeof(int16_t) * std::max<uint64_t>(samples, 1));
+    hipError_t e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
     uint64_t off = 0;
     for (size_t u = 0; u < n && e == hipSuccess; u++) {
         xs[u] = dx + off;
@@ -913,24 +914,26 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
     }
     if (e == hipSuccess && (rc = flac_plan(p, xs.data(), ns.data(), hzs.data(), n, &utts, &work, &slot_bytes, &bound)))
         e = hipErrorInvalidValue;
+    if (e == hipSuccess) {
+        e = scratch.open_stream();
+        s = scratch.stream;
+    }
     if (e == hipSuccess)
-        e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        e = scratch.alloc(&dslots, std::max<uint64_t>(slot_bytes, 4));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dslots, std::max<uint64_t>(slot_bytes, 4));
+        e = scratch.alloc(&dout, std::max<uint64_t>(bound, 4));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dout, std::max<uint64_t>(bound, 4));
+        e = scratch.alloc(&du, std::max<size_t>(n, 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&du, sizeof(FlacUtt) * std::max<size_t>(n, 1));
+        e = scratch.alloc(&dw, std::max<size_t>(work.size(), 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dw, sizeof(FlacWork) * std::max<size_t>(work.size(), 1));
+        e = scratch.alloc(&dfs, std::max<size_t>(work.size(), 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dfs, sizeof(uint32_t) * std::max<size_t>(work.size(), 1));
+        e = scratch.alloc(&dfo, std::max<size_t>(work.size(), 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dfo, sizeof(uint64_t) * std::max<size_t>(work.size(), 1));
+        e = scratch.alloc(&dres, std::max<size_t>(n, 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dres, sizeof(FlacOut) * std::max<size_t>(n, 1));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&dtot, sizeof(uint64_t));
+        e = scratch.alloc(&dtot, 1);
     off = 0;
     for (size_t u = 0; u < n && e == hipSuccess; u++) {
         if (n_in[u])
@@ -958,21 +961,6 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
         host.resize(total);
         e = hipMemcpy(host.data(), dout, total, hipMemcpyDeviceToHost);
     }
-    if (s)
-        (void)hipStreamSynchronize(s);
-    hipFree(dx);
-    hipFree(dslots);
-    hipFree(dout);
-    hipFree(du);
-    hipFree(dw);
-    hipFree(dfs);
-    hipFree(dfo);
-    hipFree(dres);
-    hipFree(dtot);
-    if (s)
-        hipStreamDestroy(s);
-    if (dev != prev)
-        (void)hipSetDevice(prev);
     if (rc)
         return rc;
     if (e != hipSuccess)

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/jbonsai_amd.h"
 #include "jb_device.h"
+#include "jb_output.h"
 
 #include <map>
 #include <memory>
@@ -69,7 +70,6 @@ struct ResampleTile {
     uint32_t table;  // index into the launch's table list
 };
 int resample_table(int device, uint32_t in_hz, uint32_t out_hz, ResampleTable *out);
-uint64_t resample_out_len(uint64_t n_in, uint32_t L, uint32_t M); // ceil(n_in L / M)
 void resample_tiles(const ResampleTable &t, uint32_t table, const double *x, uint64_t n_in, void *y, uint64_t n_out,
                     std::vector<ResampleTile> &tiles);
 // lds_bytes: the largest lds_bytes of the launch's tables
@@ -171,6 +171,123 @@ struct TrackSrc {
     bool vocoder_level = false;
 };
 
+// What an entry that works on PCM the caller holds needs on the device for the length of the call: makes a device
+// current and gives the caller its own back, owns a non-blocking stream and the device blocks it hands out
+struct DeviceScratch {
+    int prev = -1;
+    bool changed = false;
+    hipStream_t stream = nullptr;
+    std::vector<void *> blocks;
+    DeviceScratch() = default;
+    DeviceScratch(const DeviceScratch &) = delete;
+    DeviceScratch &operator=(const DeviceScratch &) = delete;
+    hipError_t enter(int device)
+    {
+        hipError_t e = hipGetDevice(&prev);
+        if (e == hipSuccess && prev != device) {
+            e = hipSetDevice(device);
+            changed = e == hipSuccess;
+        }
+        return e;
+    }
+    hipError_t open_stream() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
+    template <class T> hipError_t alloc(T **p, size_t n)
+    {
+        hipError_t e = hipMalloc((void **)p, sizeof(T) * n);
+        if (e == hipSuccess)
+            blocks.push_back((void *)*p);
+        return e;
+    }
+    ~DeviceScratch()
+    {
+        if (stream)
+            (void)hipStreamSynchronize(stream); // nothing of the call stays in flight into the blocks
+        for (void *p : blocks)
+            (void)hipFree(p);
+        if (stream)
+            (void)hipStreamDestroy(stream);
+        if (changed)
+            (void)hipSetDevice(prev);
+    }
+};
+
+struct Batch;
+// The stages behind the vocoder of one batch -- output rate (jb_batch_set_output_rate), loudness target
+// (jb_batch_set_loudness_target), FLAC (jb_batch_set_flac) -- and all their device state.  The setters record a
+// request and plan again (jb_output.h); the first run carries the plan out (prepare); every run enqueues the chain
+// once behind the hand-off check, and finish_verify once more for the utterances its redo rounds rewrote.
+// Without a request the chain holds no device memory and enqueues nothing
+struct OutputChain {
+    explicit OutputChain(Batch &batch) : b(batch) {}
+    // Each setter refuses after the first run; the last request before it wins
+    int set_output_rate(const uint32_t *hz, size_t n); // n == 1 or B entries, 0 = native
+    int set_loudness(const double *target, const double *ceiling, size_t n); // n == 1 or B entries each
+    int set_flac(const jb_flac_opts *opts);
+    void init();   // Batch::create: the slabs the batch was made with, the plan of no request
+    int prepare(); // at the first run: every slab, table and list of the plan; points the vocoder at its slab
+    // only: [B] 1 = the utterances a redo rewrote: their part of every stage again (the FLAC pack: every stream),
+    // then one wait
+    int enqueue(const std::vector<uint8_t> *only = nullptr);
+
+    bool active() const { return plan.active(); } // the PCM is converted or normalized behind the vocoder
+    // what the PCM read entries hand out: utterance u's samples, rate and place in the slab, the slab by type
+    size_t samples(size_t u) const { return (size_t)plan.utt[u].n; }
+    size_t offset(size_t u) const { return u < plan.utt.size() ? (size_t)plan.utt[u].off : (size_t)plan.total; }
+    size_t total() const { return (size_t)plan.total; }
+    const OutUtt &utt(size_t u) const { return plan.utt[u]; }
+    const double *pcm64() const { return plan.final.i16 ? nullptr : (const double *)slab[(size_t)plan.final.slab]; }
+    const int16_t *pcm16() const { return plan.final.i16 ? (const int16_t *)slab[(size_t)plan.final.slab] : nullptr; }
+    const void *pcm() const { return slab[(size_t)plan.final.slab]; }
+    const double *native64() const { return (const double *)slab[(size_t)plan.native64]; } // null: there is none
+    // after sync (each reports a stage that was not set, or a batch that has not run, as JB_ERR_INVALID)
+    int read_loudness(size_t u, LoudnessResult *r);
+    int read_flac_index(size_t u, FlacOut *o);
+    int read_flac(const FlacOut &o, uint8_t *dst);
+    // every stream's size and place, and the compact slab's used bytes in one copy
+    int read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_t[]> *host);
+
+private:
+    Batch &b;
+    OutPlan plan;
+    std::vector<uint32_t> want_hz;             // [B] 0 = native; empty: no rate requested
+    bool ln_on = false, flac_on = false;       // a loudness target / FLAC is requested
+    std::vector<double> ln_target, ln_ceiling; // [B]
+    FlacParams flac_p{};
+    bool frozen = false, ready = false; // the first run has begun: no more requests / its prepare() succeeded
+    void *slab[(size_t)OutSlab::Count] = {};
+    struct { // converter
+        ResampleTable *tables_dev = nullptr;
+        std::vector<ResampleTile> tiles; // sorted by utterance: utterance u owns [tile_lo[u], tile_lo[u + 1])
+        std::vector<uint32_t> tile_lo;
+        ResampleTile *tiles_dev = nullptr, *redo_dev = nullptr;
+        size_t lds = 0;                  // dynamic LDS of its launches
+    } rs;
+    struct { // loudness
+        std::vector<LoudnessUtt> utts;
+        LoudnessUtt *utts_dev = nullptr, *redo_dev = nullptr;
+        LoudnessRate *rates_dev = nullptr;
+        double *st = nullptr, *pk = nullptr, *z = nullptr;
+        LoudnessResult *res = nullptr;
+        uint64_t tiles = 0, atiles = 0;
+    } ln;
+    struct { // FLAC
+        std::vector<FlacWork> work;
+        FlacUtt *utts_dev = nullptr;
+        FlacWork *work_dev = nullptr, *redo_dev = nullptr;
+        uint8_t *out = nullptr;
+        uint32_t *fsize = nullptr;
+        uint64_t *foff = nullptr, *total = nullptr;
+        FlacOut *res = nullptr;
+    } fl;
+    void replan(); // host geometry and routing of the present requests
+    int check_settable(const char *after_run) const;
+    int prepare_resample();
+    int prepare_loudness();
+    int prepare_flac();
+    int check_ready(bool requested, const char *not_run, const char *not_set) const;
+    int flac_ready() const;
+};
+
 struct Batch {
     int device = -1;
     uint32_t flags = 0;
@@ -255,7 +372,14 @@ struct Batch {
     int flush_uploads();
 
     ~Batch();
-    template <class T> int dalloc(T **p, size_t n, bool zero);
+    int dalloc_bytes(void **p, size_t bytes, bool zero); // a pool block the batch owns until it is destroyed
+    template <class T> int dalloc(T **p, size_t n, bool zero) // n elements (0: one)
+    {
+        void *v = nullptr;
+        const int rc = dalloc_bytes(&v, (n ? n : 1) * sizeof(T), zero);
+        *p = (T *)v;
+        return rc;
+    }
     // blocks that must start out zeroed: cleared by ONE launch when the batch has been put together (flush_zero),
     // not by a fill of its own each -- two dozen 5 us launches were 0.13 ms of the 2.4 ms of a one-sentence request
     std::vector<std::pair<void *, size_t>> zero_list;
@@ -271,65 +395,7 @@ struct Batch {
     // the caller has waited for ev_mlpg_done
     int gang_timeout_seen(bool *seen);
     double *gen_pcm = nullptr;       // PCM of the streaming generator's serially served frames (its own buffer)
-    // Output rate (jb_batch_set_output_rate).  rs_on: some utterance is converted; then the vocoder writes its f64
-    // slab (vd.pcm) whatever the flags, k_resample fills the output slab (rs_pcm, or rs_pcm16 with JB_BATCH_PCM_I16)
-    // behind the hand-off check, and every PCM read entry but jb_batch_read_pcm_native reads the output slab
-    bool rs_on = false;
-    bool has_run = false;
-    std::vector<uint32_t> out_hz;    // [B] 0 = native; empty until a rate is set
-    std::vector<uint64_t> rs_off;    // [B + 1] first output sample of each utterance
-    double *rs_pcm = nullptr;
-    int16_t *rs_pcm16 = nullptr;
-    int16_t *rs_sink16 = nullptr;    // the 16-bit slab the batch was created with (JB_BATCH_PCM_I16)
-    double *rs_vpcm = nullptr;       // the f64 slab the vocoder of a 16-bit batch writes while a rate is set
-    size_t rs_redo_cap = 0;          // tiles rs_redo_dev holds (allocated by the first redo that needs it)
-    std::vector<ResampleTable> rs_tables;
-    ResampleTable *rs_tables_dev = nullptr;
-    std::vector<ResampleTile> rs_tiles; // sorted by utterance: utterance u owns [rs_tile_lo[u], rs_tile_lo[u + 1])
-    std::vector<uint32_t> rs_tile_lo;
-    size_t rs_lds = 0;               // dynamic LDS of its launches
-    ResampleTile *rs_tiles_dev = nullptr, *rs_redo_dev = nullptr;
-    int set_output_rate(const uint32_t *hz, size_t n);
-    int enqueue_resample(const std::vector<uint8_t> *only = nullptr); // only: [B] 1 = utterances to redo (synchronous)
-    size_t out_samples(size_t u) const;  // what the PCM read entries hand out for utterance u
-    size_t out_offset(size_t u) const;   // ... and where it starts in the slab they read
-    size_t out_total() const;
-    // Loudness target (jb_batch_set_loudness_target).  ln_on: the run measures the output f64 (vd.pcm, or the
-    // converter's f64 with an output rate: both written whatever the flags) and writes x * g to a slab of its own
-    // (ln_pcm, or the batch's 16-bit slab), which every PCM read entry but jb_batch_read_pcm_native reads
-    bool ln_on = false, ln_ready = false;
-    std::vector<double> ln_target, ln_ceiling; // [B]
-    double *ln_pcm = nullptr;        // f64 output
-    int16_t *ln_pcm16 = nullptr;     // 16-bit output (the slab the read entries would hand out without a target)
-    double *ln_src64 = nullptr;      // f64 the measurement reads where the flags asked for 16 bits
-    std::vector<LoudnessUtt> ln_utts;
-    LoudnessUtt *ln_utts_dev = nullptr, *ln_redo_dev = nullptr;
-    LoudnessRate *ln_rates_dev = nullptr;
-    double *ln_st = nullptr, *ln_pk = nullptr, *ln_z = nullptr;
-    LoudnessResult *ln_res = nullptr;
-    uint64_t ln_tiles = 0, ln_atiles = 0;
-    // target / ceiling: n == 1 or B entries each
-    int set_loudness(const double *target, const double *ceiling, size_t n);
-    int prepare_loudness(); // at the first run: slabs, lists, tables
-    int enqueue_loudness(const std::vector<uint8_t> *only = nullptr); // only: as enqueue_resample's
-    const double *out_pcm64() const;
-    const int16_t *out_pcm16() const;
-    // FLAC (jb_batch_set_flac): the run encodes out_pcm16() into fl_out, one stream per utterance
-    bool fl_on = false, fl_ready = false;
-    FlacParams fl_p{};
-    std::vector<FlacUtt> fl_utts;
-    std::vector<FlacWork> fl_work;
-    FlacUtt *fl_utts_dev = nullptr;
-    FlacWork *fl_work_dev = nullptr, *fl_redo_dev = nullptr;
-    uint8_t *fl_slots = nullptr, *fl_out = nullptr;
-    uint32_t *fl_fsize = nullptr;
-    uint64_t *fl_foff = nullptr, *fl_total = nullptr;
-    FlacOut *fl_res = nullptr;
-    int set_flac(const jb_flac_opts *opts);
-    int prepare_flac(); // at the first run, after prepare_loudness: lists and slabs
-    int enqueue_flac(const std::vector<uint8_t> *only = nullptr); // only: re-encode those utterances, pack all
-    // after sync: every stream's size and place (FlacOut) and the compact slab's used bytes
-    int read_flac_index(std::vector<FlacOut> *res, uint64_t *total);
+    OutputChain out{*this};          // the stages behind the vocoder: output rate, loudness, FLAC
     bool last_run_timed = false;
     uint32_t gang_fallbacks = 0;     // times the resident GV kernel timed out in formation and the sweeps took over
     static int create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n,

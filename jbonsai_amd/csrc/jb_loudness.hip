@@ -602,7 +602,8 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
         set_error("no HIP device");
         return JB_ERR_DEVICE;
     }
-    if (dev != prev && hipSetDevice(dev) != hipSuccess) {
+    DeviceScratch scratch;
+    if (scratch.enter(dev) != hipSuccess) {
         set_error("hipSetDevice failed");
         return JB_ERR_DEVICE;
     }
@@ -624,23 +625,23 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
     LoudnessRate *dr = nullptr;
     LoudnessUtt *du = nullptr;
     LoudnessResult *dres = nullptr;
-    hipStream_t s = nullptr;
     std::vector<LoudnessResult> out(n);
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipError_t e = scratch.open_stream();
+    hipStream_t s = scratch.stream;
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dx, sizeof(double) * std::max<uint64_t>(samples, 1));
+        e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dst, sizeof(double) * 4 * std::max<uint64_t>(tiles, 1));
+        e = scratch.alloc(&dst, 4 * std::max<uint64_t>(tiles, 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dpk, sizeof(double) * std::max<uint64_t>(tiles, 1));
+        e = scratch.alloc(&dpk, std::max<uint64_t>(tiles, 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dz, sizeof(double) * std::max<uint64_t>(tiles, 1));
+        e = scratch.alloc(&dz, std::max<uint64_t>(tiles, 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dr, sizeof rate);
+        e = scratch.alloc(&dr, 1);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&du, sizeof(LoudnessUtt) * std::max<size_t>(n, 1));
+        e = scratch.alloc(&du, std::max<size_t>(n, 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dres, sizeof(LoudnessResult) * std::max<size_t>(n, 1));
+        e = scratch.alloc(&dres, std::max<size_t>(n, 1));
     uint64_t off = 0;
     for (size_t u = 0; u < n && e == hipSuccess; u++) {
         utts[u].x = dx + off;
@@ -658,19 +659,6 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
         e = hipMemcpyAsync(out.data(), dres, sizeof(LoudnessResult) * n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
-    if (s)
-        (void)hipStreamSynchronize(s);
-    hipFree(dx);
-    hipFree(dst);
-    hipFree(dpk);
-    hipFree(dz);
-    hipFree(dr);
-    hipFree(du);
-    hipFree(dres);
-    if (s)
-        hipStreamDestroy(s);
-    if (dev != prev)
-        (void)hipSetDevice(prev);
     if (e != hipSuccess)
         return hip_fail(e, "jb_loudness_pcm_batch");
     for (size_t u = 0; u < n; u++) {

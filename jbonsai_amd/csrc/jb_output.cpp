@@ -1,0 +1,66 @@
+// jb_output.cpp -- plan_output: the routing table of the output stages (jb_output.h).
+#include "jb_output.h"
+
+#include <algorithm>
+#include <numeric>
+
+namespace jb {
+
+void resample_ratio(uint32_t in_hz, uint32_t out_hz, uint64_t *L, uint64_t *M)
+{
+    const uint64_t g = std::gcd((uint64_t)in_hz, (uint64_t)out_hz);
+    *L = out_hz / g;
+    *M = in_hz / g;
+}
+
+uint64_t resample_out_len(uint64_t n_in, uint64_t L, uint64_t M) { return (n_in * L + M - 1) / M; }
+
+OutPlan plan_output(const OutPlanIn &in)
+{
+    OutPlan p;
+    p.utt.resize(in.B);
+    for (size_t u = 0; u < in.B; u++) {
+        OutUtt &w = p.utt[u];
+        w.hz = (in.want_hz && in.want_hz[u]) ? in.want_hz[u] : in.voice_hz;
+        uint64_t L = 1, M = 1;
+        if (w.hz != in.voice_hz) {
+            resample_ratio(in.voice_hz, w.hz, &L, &M);
+            p.convert = true;
+        }
+        w.L = (uint32_t)L;
+        w.M = (uint32_t)M;
+        p.native_total += in.n_native[u];
+    }
+    // a converting batch packs its output utterance after utterance; without conversion the native slab is the output
+    for (size_t u = 0; u < in.B; u++) {
+        OutUtt &w = p.utt[u];
+        w.n = p.convert ? resample_out_len(in.n_native[u], w.L, w.M) : in.n_native[u];
+        w.off = p.convert ? p.total : in.off_native[u];
+        p.total += w.n;
+    }
+    // Every stage but the last writes f64 (the converter and the measurement read f64); the last one writes what the
+    // flags asked for.  A 16-bit output goes to the slab the batch was created with where it fits
+    const OutSlab out16 = p.total <= p.native_total ? OutSlab::S16 : OutSlab::New16;
+    if (in.i16 && !p.convert && !in.loudness)
+        p.vocoder = {OutSlab::S16, true};
+    else
+        p.vocoder = {in.i16 ? OutSlab::Voc64 : OutSlab::V64, false};
+    p.final = p.vocoder;
+    if (p.convert) {
+        p.converter = (in.i16 && !in.loudness) ? OutWrite{out16, true} : OutWrite{OutSlab::Conv64, false};
+        p.final = p.converter;
+    }
+    if (in.loudness) {
+        p.measure = p.final.slab;
+        p.apply = in.i16 ? OutWrite{out16, true} : OutWrite{OutSlab::Apply64, false};
+        p.final = p.apply;
+    }
+    p.native64 = p.vocoder.i16 ? OutSlab::None : p.vocoder.slab;
+    p.flac = (in.flac && p.final.i16) ? p.final.slab : OutSlab::None;
+    for (const OutWrite &w : {p.vocoder, p.converter, p.apply})
+        if (w.slab != OutSlab::None && w.slab != OutSlab::V64 && w.slab != OutSlab::S16)
+            p.alloc[(size_t)w.slab] = std::max<uint64_t>(w.slab == OutSlab::Voc64 ? p.native_total : p.total, 1);
+    return p;
+}
+
+} // namespace jb

@@ -1,0 +1,69 @@
+#pragma once
+// jb_output.h -- the routing of the stages behind the vocoder (output rate, loudness, FLAC): which slab each stage
+// reads and writes, in f64 or in 16 bits, which slab the read entries hand out, and each utterance's output geometry,
+// decided from the batch's shape and the three requests alone (plan_output, jb_output.cpp).
+// Plain C++17 without HIP: the plan is made and tested on any host; OutputChain (jb_host.h) carries it out.
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+
+namespace jb {
+
+// The PCM slabs of a batch, by name.  The first two are made with the batch (one of them: by JB_BATCH_PCM_I16);
+// the others are allocated at the first run where the plan lists them
+enum class OutSlab : uint8_t {
+    None,
+    V64,     // the vocoder's f64 slab of the batch as created
+    S16,     // the 16-bit slab of the batch as created
+    Voc64,   // f64 the vocoder of a 16-bit batch writes for a stage that reads f64
+    Conv64,  // f64 the converter writes
+    Apply64, // f64 the loudness apply pass writes
+    New16,   // 16-bit output longer than S16
+    Count
+};
+constexpr size_t out_slab_elem(OutSlab s) { return s == OutSlab::S16 || s == OutSlab::New16 ? 2 : 8; } // bytes
+
+// in_hz -> out_hz reduced by their gcd (rates above 0)
+void resample_ratio(uint32_t in_hz, uint32_t out_hz, uint64_t *L, uint64_t *M);
+uint64_t resample_out_len(uint64_t n_in, uint64_t L, uint64_t M); // ceil(n_in L / M)
+
+// What the plan reads, as plain values
+struct OutPlanIn {
+    size_t B = 0;
+    const uint64_t *n_native = nullptr;   // [B] samples of each utterance at the voice's rate
+    const uint64_t *off_native = nullptr; // [B] its first sample in the native slab
+    uint32_t voice_hz = 0;
+    bool i16 = false;                     // JB_BATCH_PCM_I16
+    const uint32_t *want_hz = nullptr;    // [B] requested rate, 0 or voice_hz = native; nullptr: none requested
+    bool loudness = false, flac = false;
+};
+
+struct OutUtt {
+    uint32_t hz, L, M; // output rate = voice_hz L / M
+    uint64_t n, off;   // samples and first sample in the slabs behind the converter (the native ones without it)
+};
+
+struct OutWrite { // what a stage writes; slab None: the stage does not run
+    OutSlab slab = OutSlab::None;
+    bool i16 = false;
+};
+
+struct OutPlan {
+    std::vector<OutUtt> utt;  // [B]
+    uint64_t total = 0;       // samples of the slabs behind the converter
+    uint64_t native_total = 0;
+    bool convert = false;     // some utterance is not native; the native ones then go through the identity table
+    OutWrite vocoder, converter, apply;
+    OutSlab measure = OutSlab::None;  // f64 the loudness measurement reads (never scaled in place)
+    OutSlab flac = OutSlab::None;     // 16 bits FLAC encodes: the slab handed out
+    OutWrite final;                   // what the PCM read entries hand out
+    OutSlab native64 = OutSlab::None; // f64 at the voice's rate (jb_batch_read_pcm_native)
+    uint64_t alloc[(size_t)OutSlab::Count] = {}; // elements to allocate of each slab, at least 1 (0: none; V64 / S16 exist)
+    bool normalize() const { return apply.slab != OutSlab::None; }
+    bool active() const { return convert || normalize(); } // a stage rewrites the PCM behind the vocoder
+};
+
+// Pure: no globals, no environment.
+OutPlan plan_output(const OutPlanIn &in);
+
+} // namespace jb

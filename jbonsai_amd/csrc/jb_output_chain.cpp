@@ -1,0 +1,394 @@
+// jb_output_chain.cpp -- OutputChain (jb_host.h): the stages behind the vocoder of one batch.  The setters record a
+// request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() launches
+// k_resample, the loudness measurement and apply pass and the FLAC encoder and pack, in that order, on the
+// vocoder's stream.
+#include "jb_host.h"
+
+#include <algorithm>
+#include <new>
+
+namespace jb {
+
+void OutputChain::init()
+{
+    slab[(size_t)OutSlab::V64] = b.vd.pcm;
+    slab[(size_t)OutSlab::S16] = b.vd.pcm16;
+    replan();
+}
+
+void OutputChain::replan()
+{
+    const size_t B = (size_t)b.B;
+    std::vector<uint64_t> n(B), off(B);
+    for (size_t u = 0; u < B; u++) {
+        n[u] = (uint64_t)b.T[u] * b.voice.fperiod;
+        off[u] = b.frame_off[u] * b.voice.fperiod;
+    }
+    OutPlanIn in;
+    in.B = B;
+    in.n_native = n.data();
+    in.off_native = off.data();
+    in.voice_hz = b.voice.sampling_frequency;
+    in.i16 = (b.flags & JB_BATCH_PCM_I16) != 0;
+    in.want_hz = want_hz.empty() ? nullptr : want_hz.data();
+    in.loudness = ln_on;
+    in.flac = flac_on;
+    plan = plan_output(in);
+}
+
+// what every setter refuses
+int OutputChain::check_settable(const char *after_run) const
+{
+    if (b.flags & JB_BATCH_MLPG_ONLY) {
+        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_INVALID;
+    }
+    if (frozen) {
+        set_error(after_run);
+        return JB_ERR_INVALID;
+    }
+    return JB_OK;
+}
+
+int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
+{
+    int rc = check_settable("jb_batch_set_output_rate: the output rate is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!hz || (n != 1 && n != (size_t)b.B)) {
+        set_error("jb_batch_set_output_rate: give one rate, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    const uint32_t in = b.voice.sampling_frequency;
+    std::vector<uint32_t> want((size_t)b.B);
+    for (size_t u = 0; u < want.size(); u++) {
+        const uint32_t h = hz[n == 1 ? 0 : u];
+        want[u] = h == in ? 0 : h;
+        if (want[u] && (rc = resample_design(in, want[u], nullptr, nullptr)))
+            return rc;
+    }
+    want_hz = std::move(want);
+    replan();
+    return JB_OK;
+}
+
+int OutputChain::set_loudness(const double *target, const double *ceiling, size_t n)
+{
+    int rc = check_settable("jb_batch_set_loudness_target: the target is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!target || !ceiling || (n != 1 && n != (size_t)b.B)) {
+        set_error("jb_batch_set_loudness_target: give one target, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    ln_target.assign((size_t)b.B, 0.0);
+    ln_ceiling.assign((size_t)b.B, 0.0);
+    for (size_t u = 0; u < (size_t)b.B; u++) {
+        ln_target[u] = target[n == 1 ? 0 : u];
+        ln_ceiling[u] = ceiling[n == 1 ? 0 : u];
+    }
+    ln_on = true;
+    replan();
+    return JB_OK;
+}
+
+int OutputChain::set_flac(const jb_flac_opts *opts)
+{
+    FlacParams p{};
+    int rc = flac_check_opts(opts, &p);
+    if (rc)
+        return rc;
+    // (a JB_BATCH_MLPG_ONLY batch is told that it has no PCM, not which flag its PCM lacks)
+    if (!(b.flags & (JB_BATCH_MLPG_ONLY | JB_BATCH_PCM_I16))) {
+        set_error("jb_batch_set_flac: FLAC encodes the 16-bit output (JB_BATCH_PCM_I16)");
+        return JB_ERR_INVALID;
+    }
+    if ((rc = check_settable("jb_batch_set_flac: FLAC is set before the batch's first run")))
+        return rc;
+    flac_p = p;
+    flac_on = true;
+    replan();
+    return JB_OK;
+}
+
+// At the first run (a second one, or the step done again behind a resident-GV formation timeout, finds it done).
+// The vocoder is pointed at its slab last: a failure leaves the batch as it was created, its blocks the batch's own
+int OutputChain::prepare()
+{
+    if (ready)
+        return JB_OK;
+    frozen = true;
+    int rc;
+    for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
+        if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
+            return rc;
+    if ((rc = prepare_resample()) || (rc = prepare_loudness()) || (rc = prepare_flac()))
+        return rc;
+    if (plan.active()) {
+        void *voc = slab[(size_t)plan.vocoder.slab];
+        b.vd.pcm = plan.vocoder.i16 ? nullptr : (double *)voc;
+        b.vd.pcm16 = plan.vocoder.i16 ? (int16_t *)voc : nullptr;
+    }
+    ready = true;
+    return JB_OK;
+}
+
+// One table per distinct rate (native utterances go through the identity table: a copy, or the 16-bit conversion
+// alone) and the tiles, reading the vocoder's f64 and writing the converter's slab
+int OutputChain::prepare_resample()
+{
+    if (!plan.convert)
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    const uint32_t in = b.voice.sampling_frequency;
+    const double *src = (const double *)slab[(size_t)plan.vocoder.slab];
+    char *dst = (char *)slab[(size_t)plan.converter.slab];
+    const size_t elem = plan.converter.i16 ? sizeof(int16_t) : sizeof(double);
+    std::vector<ResampleTable> tables;
+    std::vector<uint32_t> rate_of_table;
+    int rc;
+    rs.tiles.clear();
+    rs.tile_lo.assign(B + 1, 0);
+    for (size_t u = 0; u < B; u++) {
+        const OutUtt &w = plan.utt[u];
+        const size_t t = std::find(rate_of_table.begin(), rate_of_table.end(), w.hz) - rate_of_table.begin();
+        if (t == rate_of_table.size()) {
+            ResampleTable tb{};
+            if ((rc = resample_table(b.device, in, w.hz, &tb)))
+                return rc;
+            rate_of_table.push_back(w.hz);
+            tables.push_back(tb);
+            rs.lds = std::max<size_t>(rs.lds, tb.lds_bytes);
+        }
+        rs.tile_lo[u] = (uint32_t)rs.tiles.size();
+        resample_tiles(tables[t], (uint32_t)t, src + (size_t)b.frame_off[u] * b.voice.fperiod,
+                       (uint64_t)b.T[u] * b.voice.fperiod, dst + w.off * elem, w.n, rs.tiles);
+    }
+    rs.tile_lo[B] = (uint32_t)rs.tiles.size();
+    const size_t nt = std::max<size_t>(rs.tiles.size(), 1);
+    if ((rc = b.dalloc(&rs.tables_dev, tables.size(), false)) || (rc = b.dalloc(&rs.tiles_dev, nt, false)) ||
+        (rc = b.dalloc(&rs.redo_dev, nt, false)))
+        return rc;
+    hipError_t e;
+    if ((e = hipMemcpy(rs.tables_dev, tables.data(), sizeof(ResampleTable) * tables.size(), hipMemcpyHostToDevice)) !=
+            hipSuccess ||
+        (!rs.tiles.empty() && (e = hipMemcpy(rs.tiles_dev, rs.tiles.data(), sizeof(ResampleTile) * rs.tiles.size(),
+                                             hipMemcpyHostToDevice)) != hipSuccess))
+        return hip_fail(e, "resample work list");
+    return JB_OK;
+}
+
+// The per-rate tables and the utterance list: the measurement reads the f64 of the stage in front, the apply pass
+// writes x * g to its own slab
+int OutputChain::prepare_loudness()
+{
+    if (!plan.normalize())
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    const double *src = (const double *)slab[(size_t)plan.measure];
+    char *dst = (char *)slab[(size_t)plan.apply.slab];
+    const size_t elem = plan.apply.i16 ? sizeof(int16_t) : sizeof(double);
+    std::vector<LoudnessRate> rates;
+    ln.utts.assign(B, LoudnessUtt{});
+    uint64_t tiles = 0, atiles = 0;
+    int rc;
+    for (size_t u = 0; u < B; u++) {
+        const OutUtt &o = plan.utt[u];
+        size_t r = 0;
+        while (r < rates.size() && rates[r].hz != o.hz)
+            r++;
+        if (r == rates.size()) {
+            LoudnessRate lr{};
+            if ((rc = loudness_rate(o.hz, &lr)))
+                return rc;
+            rates.push_back(lr);
+        }
+        LoudnessUtt &w = ln.utts[u];
+        w.x = src + o.off;
+        w.y = dst + o.off * elem;
+        w.n = o.n;
+        w.ntiles = loudness_tiles(rates[r], w.n);
+        w.tile0 = w.lt0 = tiles;
+        w.at0 = atiles;
+        w.rate = (uint32_t)r;
+        w.slot = (uint32_t)u;
+        w.target = ln_target[u];
+        w.ceiling = ln_ceiling[u];
+        tiles += w.ntiles;
+        atiles += (w.n + kLnApplyTile - 1) / kLnApplyTile;
+    }
+    const size_t nt = (size_t)std::max<uint64_t>(tiles, 1);
+    if ((rc = b.dalloc(&ln.rates_dev, rates.size(), false)) || (rc = b.dalloc(&ln.utts_dev, B, false)) ||
+        (rc = b.dalloc(&ln.redo_dev, B, false)) || (rc = b.dalloc(&ln.st, 4 * nt, false)) ||
+        (rc = b.dalloc(&ln.pk, nt, false)) || (rc = b.dalloc(&ln.z, nt, false)) || (rc = b.dalloc(&ln.res, B, false)))
+        return rc;
+    hipError_t e;
+    if ((e = hipMemcpy(ln.rates_dev, rates.data(), sizeof(LoudnessRate) * rates.size(), hipMemcpyHostToDevice)) !=
+            hipSuccess ||
+        (B > 0 && (e = hipMemcpy(ln.utts_dev, ln.utts.data(), sizeof(LoudnessUtt) * B, hipMemcpyHostToDevice)) !=
+                      hipSuccess))
+        return hip_fail(e, "loudness work list");
+    ln.tiles = tiles;
+    ln.atiles = atiles;
+    return JB_OK;
+}
+
+// The streams' lists and slabs: one stream per utterance of the 16-bit slab handed out, at its output rate
+int OutputChain::prepare_flac()
+{
+    if (!flac_on)
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    std::vector<const int16_t *> xs(B);
+    std::vector<uint64_t> ns(B);
+    std::vector<uint32_t> hz(B);
+    for (size_t u = 0; u < B; u++) {
+        xs[u] = (const int16_t *)slab[(size_t)plan.flac] + plan.utt[u].off;
+        ns[u] = plan.utt[u].n;
+        hz[u] = plan.utt[u].hz;
+    }
+    std::vector<FlacUtt> utts;
+    uint64_t slot_bytes = 0, bound = 0;
+    int rc = flac_plan(flac_p, xs.data(), ns.data(), hz.data(), B, &utts, &fl.work, &slot_bytes, &bound);
+    if (rc)
+        return rc;
+    const size_t nf = std::max<size_t>(fl.work.size(), 1);
+    uint8_t *slots = nullptr;
+    if ((rc = b.dalloc(&slots, std::max<uint64_t>(slot_bytes, 4), false)) ||
+        (rc = b.dalloc(&fl.out, std::max<uint64_t>(bound, 4), false)) || (rc = b.dalloc(&fl.utts_dev, B, false)) ||
+        (rc = b.dalloc(&fl.work_dev, nf, false)) || (rc = b.dalloc(&fl.redo_dev, nf, false)) ||
+        (rc = b.dalloc(&fl.fsize, nf, false)) || (rc = b.dalloc(&fl.foff, nf, false)) ||
+        (rc = b.dalloc(&fl.res, B, false)) || (rc = b.dalloc(&fl.total, 1, false)))
+        return rc;
+    flac_bind(&utts, slots);
+    hipError_t e = hipSuccess;
+    if ((B > 0 && (e = hipMemcpy(fl.utts_dev, utts.data(), sizeof(FlacUtt) * B, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (!fl.work.empty() && (e = hipMemcpy(fl.work_dev, fl.work.data(), sizeof(FlacWork) * fl.work.size(),
+                                            hipMemcpyHostToDevice)) != hipSuccess))
+        return hip_fail(e, "FLAC work list");
+    return JB_OK;
+}
+
+int OutputChain::enqueue(const std::vector<uint8_t> *only)
+{
+    if (!ready || !(plan.active() || flac_on))
+        return JB_OK;
+    const uint32_t B = (uint32_t)b.B;
+    hipStream_t st = b.stream_voc;
+    // the lists of a run: the batch's own
+    const ResampleTile *tiles = rs.tiles_dev;
+    const LoudnessUtt *utts = ln.utts_dev;
+    const FlacWork *work = fl.work_dev;
+    const uint32_t n_all_work = (uint32_t)fl.work.size();
+    uint32_t n_tiles = (uint32_t)rs.tiles.size(), n_utts = B, n_work = n_all_work;
+    uint64_t lt = ln.tiles, at = ln.atiles;
+    hipError_t e = hipSuccess;
+    if (only) {
+        // of a redo: the tiles, the utterances (renumbered: their scratch stays where it is) and the FLAC blocks of
+        // the utterances it rewrote, uploaded before the first launch
+        std::vector<ResampleTile> rs_sub;
+        std::vector<LoudnessUtt> ln_sub;
+        std::vector<FlacWork> fl_sub;
+        lt = at = 0;
+        for (size_t u = 0; u < B; u++) {
+            if (!(*only)[u])
+                continue;
+            if (plan.convert)
+                rs_sub.insert(rs_sub.end(), rs.tiles.begin() + rs.tile_lo[u], rs.tiles.begin() + rs.tile_lo[u + 1]);
+            if (plan.normalize()) {
+                LoudnessUtt w = ln.utts[u];
+                w.lt0 = lt;
+                w.at0 = at;
+                lt += w.ntiles;
+                at += (w.n + kLnApplyTile - 1) / kLnApplyTile;
+                ln_sub.push_back(w);
+            }
+        }
+        for (const FlacWork &w : fl.work)
+            if ((*only)[w.utt])
+                fl_sub.push_back(w);
+        tiles = rs.redo_dev;
+        utts = ln.redo_dev;
+        work = fl.redo_dev;
+        n_tiles = (uint32_t)rs_sub.size();
+        n_utts = (uint32_t)ln_sub.size();
+        n_work = (uint32_t)fl_sub.size();
+        if (!n_tiles && !n_utts && !n_work)
+            return JB_OK;
+        if ((n_tiles && (e = hipMemcpy(rs.redo_dev, rs_sub.data(), sizeof(ResampleTile) * n_tiles,
+                                       hipMemcpyHostToDevice)) != hipSuccess) ||
+            (n_utts && (e = hipMemcpy(ln.redo_dev, ln_sub.data(), sizeof(LoudnessUtt) * n_utts,
+                                      hipMemcpyHostToDevice)) != hipSuccess) ||
+            (n_work && (e = hipMemcpy(fl.redo_dev, fl_sub.data(), sizeof(FlacWork) * n_work, hipMemcpyHostToDevice)) !=
+                           hipSuccess))
+            return hip_fail(e, "output chain(redo lists)");
+    }
+    // a run launches every stage of the plan; a redo those that have something to do again
+    if (plan.convert && (!only || n_tiles) &&
+        (e = launch_resample(rs.tables_dev, tiles, n_tiles, plan.converter.i16, rs.lds, st)) != hipSuccess)
+        return hip_fail(e, only ? "k_resample(redo)" : "k_resample");
+    if (plan.normalize() && (!only || n_utts) &&
+        ((e = launch_loudness_measure(ln.rates_dev, utts, n_utts, lt, ln.st, ln.pk, ln.z, ln.res, st)) != hipSuccess ||
+         (e = launch_loudness_apply(utts, n_utts, at, ln.res, plan.apply.i16, st)) != hipSuccess))
+        return hip_fail(e, only ? "loudness(redo)" : "loudness");
+    // FLAC: the blocks of the list, then every stream's offsets and place (all of fl.work_dev, redo or not)
+    if (flac_on && (!only || n_work) &&
+        ((e = launch_flac_encode(flac_p, fl.utts_dev, work, n_work, fl.fsize, st)) != hipSuccess ||
+         (e = launch_flac_pack(flac_p, fl.utts_dev, B, fl.work_dev, n_all_work, fl.fsize, fl.foff, fl.res, fl.total,
+                               fl.out, st)) != hipSuccess))
+        return hip_fail(e, only ? "FLAC(redo)" : "FLAC");
+    if (only && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "output chain(redo)");
+    return JB_OK;
+}
+
+int OutputChain::check_ready(bool requested, const char *not_run, const char *not_set) const
+{
+    if (requested && ready)
+        return JB_OK;
+    set_error(requested ? not_run : not_set);
+    return JB_ERR_INVALID;
+}
+
+int OutputChain::read_loudness(size_t u, LoudnessResult *r)
+{
+    int rc = check_ready(plan.normalize(), "jb_batch_loudness: the batch has not run",
+                         "jb_batch_loudness: no loudness target is set");
+    return rc ? rc : b.read(ln.res + u, r, sizeof *r);
+}
+
+int OutputChain::flac_ready() const
+{
+    return check_ready(flac_on, "FLAC: the batch has not run", "FLAC: jb_batch_set_flac was not called");
+}
+
+int OutputChain::read_flac_index(size_t u, FlacOut *o)
+{
+    int rc = flac_ready();
+    return rc ? rc : b.read(fl.res + u, o, sizeof *o);
+}
+
+int OutputChain::read_flac(const FlacOut &o, uint8_t *dst) { return b.read(fl.out + o.off, dst, (size_t)o.bytes, false); }
+
+int OutputChain::read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_t[]> *host)
+{
+    int rc = flac_ready();
+    if (rc)
+        return rc;
+    const size_t B = (size_t)b.B;
+    res->assign(B, FlacOut{});
+    if ((rc = B > 0 ? b.read(fl.res, res->data(), sizeof(FlacOut) * B) : b.sync()))
+        return rc;
+    uint64_t total = 0;
+    for (const FlacOut &o : *res)
+        total = std::max<uint64_t>(total, o.off + o.bytes);
+    // one copy of the used bytes (not zero-filled first)
+    host->reset(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
+    if (!*host) {
+        set_error("out of host memory");
+        return JB_ERR_INVALID;
+    }
+    return total ? b.read(fl.out, host->get(), (size_t)total, false) : JB_OK;
+}
+
+} // namespace jb

@@ -42,25 +42,6 @@ constexpr int kRsThreads = 256;          // four waves
 constexpr uint32_t kRsLdsDoubles = 8192;
 constexpr uint32_t kRsCopyRows = 16384; // outputs per tile of the identity table (a copy: no window, no taps)
 
-// Makes a device current for the scope and gives the caller its own back
-struct DeviceScope {
-    int prev = -1;
-    bool changed = false;
-    hipError_t enter(int device)
-    {
-        hipError_t e = hipGetDevice(&prev);
-        if (e == hipSuccess && prev != device) {
-            e = hipSetDevice(device);
-            changed = e == hipSuccess;
-        }
-        return e;
-    }
-    ~DeviceScope()
-    {
-        if (changed)
-            (void)hipSetDevice(prev);
-    }
-};
 constexpr size_t kRsLdsMaxBytes = sizeof(double) * kRsLdsDoubles;
 
 // pad shift of a window: slot(e) = e + (e >> shift) spreads the bank pairs (slot mod 32) of a half-wave's 32 lanes,
@@ -101,8 +82,8 @@ int resample_design(uint32_t in_hz, uint32_t out_hz, ResampleSpec *spec, std::ve
         set_error("resample: a rate of 0 Hz");
         return JB_ERR_INVALID;
     }
-    const uint64_t g = std::gcd((uint64_t)in_hz, (uint64_t)out_hz);
-    const uint64_t L = out_hz / g, M = in_hz / g;
+    uint64_t L, M;
+    resample_ratio(in_hz, out_hz, &L, &M);
     if (L > kResampleMaxLM || M > kResampleMaxLM) {
         set_error("resample: " + std::to_string(in_hz) + " Hz -> " + std::to_string(out_hz) + " Hz reduces to L/M = " +
                   std::to_string(L) + "/" + std::to_string(M) + "; supported are L <= 2048 and M <= 2048");
@@ -210,7 +191,7 @@ int resample_table(int device, uint32_t in_hz, uint32_t out_hz, ResampleTable *o
         t.lds_bytes = (uint32_t)(sizeof(double) * (t.pad ? wlen + (wlen >> t.pad) + 1 : wlen));
     }
     // on `device`, whatever the calling thread has current (and that stays current afterwards)
-    DeviceScope scope;
+    DeviceScratch scope;
     hipError_t e = scope.enter(device);
     if (e == hipSuccess)
         e = hipMalloc((void **)&t.h, sizeof(double) * taps.size());
@@ -225,8 +206,6 @@ int resample_table(int device, uint32_t in_hz, uint32_t out_hz, ResampleTable *o
     *out = t;
     return JB_OK;
 }
-
-uint64_t resample_out_len(uint64_t n_in, uint32_t L, uint32_t M) { return (n_in * L + M - 1) / M; }
 
 void resample_tiles(const ResampleTable &t, uint32_t table, const double *x, uint64_t n_in, void *y, uint64_t n_out,
                     std::vector<ResampleTile> &tiles)
@@ -401,8 +380,8 @@ int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
         return JB_ERR_DEVICE;
     }
     // everything below (stream, allocations, launch) on `dev`, where the table lives; the caller keeps its device
-    DeviceScope scope;
-    if (hipError_t se = scope.enter(dev); se != hipSuccess)
+    DeviceScratch scratch;
+    if (hipError_t se = scratch.enter(dev); se != hipSuccess)
         return hip_fail(se, "hipSetDevice");
     ResampleTable t{};
     int rc = resample_table(dev, in_hz, out_hz, &t);
@@ -431,24 +410,24 @@ int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
     double *dx = nullptr, *dy = nullptr;
     ResampleTable *dt = nullptr;
     ResampleTile *dtl = nullptr;
-    hipStream_t st = nullptr;
     std::vector<ResampleTile> tiles;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    hipError_t e = scratch.open_stream();
+    hipStream_t st = scratch.stream;
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dx, sizeof(double) * std::max<uint64_t>(ioff[n], 1));
+        e = scratch.alloc(&dx, std::max<uint64_t>(ioff[n], 1));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dy, sizeof(double) * std::max<uint64_t>(ooff[n], 1));
+        e = scratch.alloc(&dy, std::max<uint64_t>(ooff[n], 1));
     for (size_t u = 0; u < n && e == hipSuccess; u++) {
         if (n_in[u])
             e = hipMemcpyAsync(dx + ioff[u], in[u], sizeof(double) * n_in[u], hipMemcpyHostToDevice, st);
         resample_tiles(t, 0, dx + ioff[u], n_in[u], dy + ooff[u], ooff[u + 1] - ooff[u], tiles);
     }
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dt, sizeof t);
+        e = scratch.alloc(&dt, 1);
     if (e == hipSuccess)
         e = hipMemcpyAsync(dt, &t, sizeof t, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && !tiles.empty()) {
-        e = hipMalloc((void **)&dtl, sizeof(ResampleTile) * tiles.size());
+        e = scratch.alloc(&dtl, tiles.size());
         if (e == hipSuccess)
             e = hipMemcpyAsync(dtl, tiles.data(), sizeof(ResampleTile) * tiles.size(), hipMemcpyHostToDevice, st);
     }
@@ -459,14 +438,6 @@ int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
             e = hipMemcpyAsync(out[u], dy + ooff[u], sizeof(double) * n_out[u], hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
-    if (st)
-        (void)hipStreamSynchronize(st);
-    hipFree(dx);
-    hipFree(dy);
-    hipFree(dt);
-    hipFree(dtl);
-    if (st)
-        hipStreamDestroy(st);
     if (e != hipSuccess) {
         for (size_t u = 0; u < n; u++) {
             free(out[u]);

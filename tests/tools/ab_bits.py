@@ -1,10 +1,17 @@
 """Bitwise A/B aid: SHA-256 of the MCP/LF0 tracks and the PCM of fixed batches, to compare two builds of the
 library (swap jbonsai_amd/libjbonsai_amd.so between runs): a mid-size batch of label utterances (wave
 kernel), and 8 x the 25,546-frame synthetic utterance + 3 distinct ones (lane-triple kernel, resident GV,
-LDS-staged band solve, split excitation: the kernels of BASELINE config 2), f64 and the 16-bit sink."""
+LDS-staged band solve, split excitation: the kernels of BASELINE config 2), f64 and the 16-bit sink.  Then the
+stages behind the vocoder: all eight rows of the output routing table (f64 / 16-bit sink x output
+rate x loudness target; FLAC on the 16-bit rows) on three ragged utterances, with the default geometry and with the
+redo-heavy one of the redo tests, and the three entries on caller-held PCM on seeded input.
+
+    python tests/tools/ab_bits.py               every hash (what tools/ab_bits.sh compares between two libraries)
+    python tests/tools/ab_bits.py --redo-time N  no hash: run() + sync() of the redo-heavy rows, wall ms, N times each"""
 import hashlib
 import os
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np  # noqa: E402
@@ -14,6 +21,80 @@ from oracle import oracle as O  # noqa: E402
 from tests.conftest import VOICE  # noqa: E402
 from tests.golden.labels import SAMPLE_SENTENCE_1, SAMPLE_SENTENCE_2  # noqa: E402
 from tests.helpers import oracle_states, to_utt, voice_info  # noqa: E402
+
+redo_time = int(sys.argv[sys.argv.index("--redo-time") + 1]) if "--redo-time" in sys.argv else 0
+
+
+def digest(arrs):
+    h = hashlib.sha256()
+    for a in arrs:
+        h.update(a if isinstance(a, bytes) else np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()[:16]
+
+
+def output_rows(vi, utts, geometry, label):
+    """Every row of the routing table: what the read entries return (per utterance and _all), pcm_native where there
+    is one, jb_batch_loudness' values, the FLAC streams (non-default block size and LPC order)."""
+    B = len(utts)
+    for i16 in (False, True):
+        for rates in (None, [22050, 16000, 0], [96000] * B):
+            for target in (None, [-20.0, -26.0, float("nan")]):
+                name = f"{label} {'i16' if i16 else 'f64'} rate={rates} target={target}"
+                with J.Batch(vi, utts, pcm_i16=i16, **geometry) as b:
+                    if rates:
+                        b.set_output_rate(rates)
+                    if target:
+                        b.set_loudness_target(target, -1.0)
+                    if i16:
+                        b.set_flac(block_size=1152, max_lpc_order=12)
+                    if redo_time:
+                        ms = []
+                        for _ in range(redo_time):
+                            t0 = time.perf_counter()
+                            b.run()
+                            b.sync()
+                            ms.append(1e3 * (time.perf_counter() - t0))
+                        print(name, "n_redo", b.info()["n_redo"], "run+sync ms", " ".join(f"{x:.3f}" for x in ms))
+                        continue
+                    b.run()
+                    b.sync()
+                    read = b.pcm_i16 if i16 else b.pcm
+                    out = [name, "n_redo", b.info()["n_redo"], "n", [b.num_samples(i) for i in range(B)],
+                           "hz", [b.output_rate(i) for i in range(B)], "off", [b.pcm_offset(i) for i in range(B + 1)],
+                           "pcm", digest([read(i) for i in range(B)]), "all", digest(b.pcm_all())]
+                    if not i16 or rates or target:
+                        out += ["native", digest([b.pcm_native(i) for i in range(B)])]
+                    if target:
+                        out += ["loudness", digest([np.array(b.loudness(i)) for i in range(B)])]
+                    if i16:
+                        out += ["flac", digest([b.flac(i) for i in range(B)]), "flac_all", digest(b.flac_all())]
+                    print(*out)
+
+
+def output_stages():
+    eng = J.Engine.load([VOICE])
+    tab, vi = synth.VoiceTables(eng), eng.voice_info()
+    utts = [synth.synth_utterance(tab, T, 40 + T) for T in (600, 1100, 37)]
+    if not redo_time:
+        output_rows(vi, utts, {}, "default")
+    output_rows(vi, utts, dict(chunk_frames=96, warmup_frames=2, verify_tol=1e-12), "redo")
+    if redo_time:
+        return
+    rng = np.random.default_rng(20240)
+    pcm = [8000.0 * rng.standard_normal(n) * np.sin(np.arange(n) * 0.01) for n in (48000, 0, 131071, 777)]
+    for hz in (16000, 22050, 96000):
+        print("resample_pcm_batch", hz, digest(J.resample(pcm, 48000, hz)))
+    print("loudness_pcm_batch", digest([np.array(J.loudness(pcm, 48000))]))
+    pcm16 = [np.clip(x, -32768, 32767).astype(np.int16) for x in pcm]
+    print("flac_encode_pcm_batch", digest(J.flac_encode(pcm16, 48000)),
+          digest(J.flac_encode(pcm16, 22050, block_size=1152, max_lpc_order=12)))
+
+
+from jbonsai_amd import synth  # noqa: E402
+
+if redo_time:
+    output_stages()
+    sys.exit(0)
 
 v = O.Voice(VOICE)
 utts = []
@@ -29,8 +110,6 @@ with J.Batch(voice_info(v), utts * 3, keep_tracks=True) as b:
         for a in arrs:
             h.update(np.ascontiguousarray(a).tobytes())
         print(name, h.hexdigest()[:16])
-
-from jbonsai_amd import synth  # noqa: E402
 
 eng = J.Engine.load([VOICE])
 tab, vi = synth.VoiceTables(eng), eng.voice_info()
@@ -53,3 +132,4 @@ with J.Batch(vi, big, pcm_i16=True) as b:
     for i in (0, 8, 10):
         h.update(b.pcm_i16(i).tobytes())
     print("big pcm_i16", h.hexdigest()[:16])
+output_stages()

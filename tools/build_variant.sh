@@ -9,8 +9,10 @@ out=tools/_ab_$name; mkdir -p $out/obj
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Wno-unused-value $*"
 pids=()
-for f in jb_mlpg.hip jb_gv_gang.hip jb_vocoder.hip jb_mglsa.hip jb_postfilter.hip jb_batch.cpp jb_voice.cpp jb_engine.cpp jb_multi.cpp; do
-  $HIPCC $FLAGS -x hip -c jbonsai_amd/csrc/$f -o $out/obj/${f%.*}.o &
+rm -f $out/obj/*.o
+for src in jbonsai_amd/csrc/*.hip jbonsai_amd/csrc/*.cpp; do # every source of the library, as jbonsai_amd/csrc/build.sh lists them
+  f=$(basename $src)
+  $HIPCC $FLAGS -x hip -c $src -o $out/obj/${f%.*}.o &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
