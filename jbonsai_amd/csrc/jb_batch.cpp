@@ -799,24 +799,6 @@ static int check_voice(const jb_voice_desc *v, bool need_windows = true, bool vo
     return JB_OK;
 }
 
-// Vocoder condition of one utterance under voice v: alpha, volume and beta of `c` (null: those of v), with the beta
-// rule of the batch (postfilter_mcp acts only for beta > 0, more than two coefficients and stage 0, cepstrum.rs:24;
-// with stage > 0 beta goes to postfilter_lsp, lsp.rs:113-139)
-static VocUtt voc_utt(const jb_voice_desc *v, const jb_utt_voc *c)
-{
-    const double alpha = c ? c->alpha : v->alpha, beta = c ? c->beta : v->beta, volume = c ? c->volume : v->volume;
-    VocUtt u{};
-    u.alpha = alpha;
-    u.volume = volume;
-    u.beta = (beta > 0.0 && v->stream[0].vector_length > 2 && v->stage == 0) ? beta : 0.0;
-    u.beta_stage = v->stage ? beta : 0.0;
-    return u;
-}
-static bool same_voc(const VocUtt &a, const VocUtt &b)
-{
-    return a.alpha == b.alpha && a.volume == b.volume && a.beta == b.beta && a.beta_stage == b.beta_stage;
-}
-
 int check_invariant_opts(const jb_batch_opts *opts)
 {
     if (!opts || !(opts->flags & JB_BATCH_INVARIANT))
@@ -831,104 +813,128 @@ int check_invariant_opts(const jb_batch_opts *opts)
     return JB_ERR_INVALID;
 }
 
-int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n, const jb_batch_opts *opts,
-                  Batch **out, const IndexSrc *idx, const TrackSrc *trk, const jb_utt_voc *voc)
+namespace {
+
+// What the steps of Batch::create share: the call's arguments, the batch being made, and the host-side temporaries
+// that one step fills and a later one reads.  Lives for the call alone.
+struct CreateCtx {
+    const jb_voice_desc *voice;
+    const jb_state_utt *utts; // the caller's, or `pseudo` (tracks as the source)
+    size_t n;
+    const jb_batch_opts *opts;
+    const IndexSrc *idx;
+    const TrackSrc *trk;
+    const jb_utt_voc *voc;
+    Batch *b = nullptr;
+    // tracks as the source: the LF0 track's voiced / unvoiced runs as pseudo-states (track_pseudo_states)
+    std::vector<jb_state_utt> pseudo;
+    std::vector<std::vector<uint32_t>> pseudo_dur;
+    std::vector<std::vector<double>> pseudo_msd;
+    std::vector<StreamStatesDev> gathered; // indexed source: per-state Gaussians produced on the device
+    std::vector<UttDev> hu;                // the descriptor table as uploaded (layout_utterances)
+    uint64_t sumS = 0, sum_mt = 0;         // sum_mt: frames of the [dim][frame] workspace, rows padded to 16
+    uint32_t maxS = 0;
+    std::vector<uint32_t> order;   // launch order: longest utterance first (stage_descriptors)
+    std::vector<double> pf_alphas; // the alpha of each post-filter operator (vd.pf_table)
+    // JB_CREATE_TRACE=1: where the creation of a batch spends its time (stderr)
+    const bool ctrace = getenv("JB_CREATE_TRACE") != nullptr;
+    const std::chrono::steady_clock::time_point tc0 = std::chrono::steady_clock::now();
+    void mark(const char *what) const
+    {
+        if (ctrace)
+            fprintf(stderr, "  create: %-28s at %.3f ms\n", what,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count());
+    }
+};
+
+// Everything that can be refused from the voice, the options and the per-utterance conditions alone
+int check_create_args(const CreateCtx &c)
 {
-    *out = nullptr;
-    int rc = check_invariant_opts(opts);
+    int rc = check_invariant_opts(c.opts);
     if (rc)
         return rc;
-    rc = check_voice(voice, trk == nullptr, trk && trk->vocoder_level);
+    rc = check_voice(c.voice, c.trk == nullptr, c.trk && c.trk->vocoder_level);
     if (rc)
         return rc;
     // per-utterance vocoder conditions: checked like the voice's own (check_voice), alpha and volume finite
-    for (size_t i = 0; voc && i < n; i++) {
-        if (!(voc[i].beta >= 0.0)) {
+    for (size_t i = 0; c.voc && i < c.n; i++) {
+        const jb_utt_voc &v = c.voc[i];
+        if (!(v.beta >= 0.0)) {
             set_error("jb_utt_voc[" + std::to_string(i) + "]: beta must be >= 0");
             return JB_ERR_INVALID;
         }
-        if (!std::isfinite(voc[i].alpha) || !std::isfinite(voc[i].volume) || !std::isfinite(voc[i].beta)) {
+        if (!std::isfinite(v.alpha) || !std::isfinite(v.volume) || !std::isfinite(v.beta)) {
             set_error("jb_utt_voc[" + std::to_string(i) + "]: alpha, beta and volume must be finite");
             return JB_ERR_INVALID;
         }
     }
-    // JB_CREATE_TRACE=1: where the creation of a batch spends its time (stderr)
-    const bool ctrace = getenv("JB_CREATE_TRACE") != nullptr;
-    const auto tc0 = std::chrono::steady_clock::now();
-    auto cmark = [&](const char *what) {
-        if (ctrace)
-            fprintf(stderr, "  create: %-28s at %.3f ms\n", what,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count());
-    };
-    // Parameter tracks as the source (SpeechGenerator::new, src/speech.rs:25-50).  The kernels behind the
-    // frame prologue want the LF0 stream's voiced flags and voiced runs, which the state walk of that
-    // stream produces: give it the track's runs of voiced / unvoiced frames (a frame is voiced where
-    // lf0 != NODATA, vocoder/mod.rs:73-77) as pseudo-states (msd 1 / 0, threshold 0.5).
-    std::vector<jb_state_utt> pseudo;
-    std::vector<std::vector<uint32_t>> pseudo_dur;
-    std::vector<std::vector<double>> pseudo_msd;
-    if (trk) {
-        if (n && !trk->utts)
-            return JB_ERR_INVALID;
-        pseudo.resize(n);
-        pseudo_dur.resize(n);
-        pseudo_msd.resize(n);
-        for (size_t i = 0; i < n; i++) {
-            const jb_track_utt &t = trk->utts[i];
-            if (t.n_spectrum != t.n_lf0 || t.n_spectrum != t.n_lpf) {
-                set_error("The length of spectrum, lf0, and lpf must be the same."); // speech.rs:32-34
-                return JB_ERR_INVALID;
-            }
-            if (t.n_lf0 && t.lf0_width != 1) {
-                set_error("The size of lf0 static vector must be 1."); // speech.rs:35-37
-                return JB_ERR_INVALID;
-            }
-            if (t.n_lpf && t.lpf_width % 2 == 0 && !trk->vocoder_level) {
-                set_error("The number of low-pass filter coefficient must be odd numbers."); // speech.rs:38-40
-                return JB_ERR_INVALID;
-            }
-            if (t.n_lf0 && (t.spectrum_width != voice->stream[0].vector_length ||
-                            t.lpf_width != voice->stream[2].vector_length)) {
-                set_error("track widths differ from the vocoder's nmcp / nlpf (Vocoder::new, vocoder/mod.rs:45-55)");
-                return JB_ERR_INVALID;
-            }
-            if (t.n_lf0 && (!t.spectrum || !t.lf0 || !t.lpf))
-                return JB_ERR_INVALID;
-            if (t.n_lf0 > 0xffffffffull / voice->fperiod) {
-                set_error("utterance too long");
-                return JB_ERR_INVALID;
-            }
-            std::vector<uint32_t> &d = pseudo_dur[i];
-            std::vector<double> &m = pseudo_msd[i];
-            for (size_t f = 0; f < t.n_lf0; f++) {
-                const double v = t.lf0[f] != kNoData ? 1.0 : 0.0;
-                if (m.empty() || m.back() != v) {
-                    m.push_back(v);
-                    d.push_back(0);
-                }
-                d.back()++;
-            }
-            jb_state_utt &u = pseudo[i];
-            memset(&u, 0, sizeof u);
-            u.num_states = (uint32_t)d.size();
-            u.durations = d.data();
-            u.stream[1].msd = m.data();
-            for (int si = 0; si < JB_MAX_STREAM; si++) {
-                u.stream[si].msd_threshold = 0.5;
-                u.stream[si].gv_weight = 1.0;
-            }
-        }
-        utts = pseudo.data();
-    }
-    if (n && !utts)
+    return JB_OK;
+}
+
+// Parameter tracks as the source (SpeechGenerator::new, src/speech.rs:25-50).  The kernels behind the
+// frame prologue want the LF0 stream's voiced flags and voiced runs, which the state walk of that
+// stream produces: give it the track's runs of voiced / unvoiced frames (plan_voiced_runs) as pseudo-states
+// (msd 1 / 0, threshold 0.5).  c.utts then points at them.
+int track_pseudo_states(CreateCtx &c)
+{
+    const TrackSrc *trk = c.trk;
+    const size_t n = c.n;
+    if (n && !trk->utts)
         return JB_ERR_INVALID;
+    c.pseudo.resize(n);
+    c.pseudo_dur.resize(n);
+    c.pseudo_msd.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const jb_track_utt &t = trk->utts[i];
+        if (t.n_spectrum != t.n_lf0 || t.n_spectrum != t.n_lpf) {
+            set_error("The length of spectrum, lf0, and lpf must be the same."); // speech.rs:32-34
+            return JB_ERR_INVALID;
+        }
+        if (t.n_lf0 && t.lf0_width != 1) {
+            set_error("The size of lf0 static vector must be 1."); // speech.rs:35-37
+            return JB_ERR_INVALID;
+        }
+        if (t.n_lpf && t.lpf_width % 2 == 0 && !trk->vocoder_level) {
+            set_error("The number of low-pass filter coefficient must be odd numbers."); // speech.rs:38-40
+            return JB_ERR_INVALID;
+        }
+        if (t.n_lf0 && (t.spectrum_width != c.voice->stream[0].vector_length ||
+                        t.lpf_width != c.voice->stream[2].vector_length)) {
+            set_error("track widths differ from the vocoder's nmcp / nlpf (Vocoder::new, vocoder/mod.rs:45-55)");
+            return JB_ERR_INVALID;
+        }
+        if (t.n_lf0 && (!t.spectrum || !t.lf0 || !t.lpf))
+            return JB_ERR_INVALID;
+        if (t.n_lf0 > 0xffffffffull / c.voice->fperiod) {
+            set_error("utterance too long");
+            return JB_ERR_INVALID;
+        }
+        plan_voiced_runs(t.lf0, t.n_lf0, c.pseudo_dur[i], c.pseudo_msd[i]);
+        jb_state_utt &u = c.pseudo[i];
+        memset(&u, 0, sizeof u);
+        u.num_states = (uint32_t)c.pseudo_dur[i].size();
+        u.durations = c.pseudo_dur[i].data();
+        u.stream[1].msd = c.pseudo_msd[i].data();
+        for (int si = 0; si < JB_MAX_STREAM; si++) {
+            u.stream[si].msd_threshold = 0.5;
+            u.stream[si].gv_weight = 1.0;
+        }
+    }
+    c.utts = c.pseudo.data();
+    return JB_OK;
+}
+
+// The device, the batch's flags, its streams and events
+int open_device(CreateCtx &c)
+{
+    Batch *b = c.b;
+    const jb_batch_opts *opts = c.opts;
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0) {
         set_error("no HIP device available (this library has no CPU path)");
         return JB_ERR_DEVICE;
     }
-    std::unique_ptr<Batch> b(new Batch());
     int dev = opts ? opts->device : -1;
     if (dev < 0) {
         e = hipGetDevice(&dev);
@@ -947,12 +953,12 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
     b->invariant = (b->flags & JB_BATCH_INVARIANT) && !(b->flags & JB_BATCH_SERIAL);
     if (b->flags & JB_BATCH_MLPG_ONLY)
         b->flags |= JB_BATCH_KEEP_TRACKS; // the [frame][dim] tracks are the result
-    if (trk && (b->flags & JB_BATCH_MLPG_ONLY)) {
+    if (c.trk && (b->flags & JB_BATCH_MLPG_ONLY)) {
         set_error("JB_BATCH_MLPG_ONLY needs state-level input");
         return JB_ERR_INVALID;
     }
-    b->from_tracks = trk != nullptr;
-    b->voice = *voice;
+    b->from_tracks = c.trk != nullptr;
+    b->voice = *c.voice;
     // (stream priorities were tried for the critical path and made every latency-bound kernel
     // 2-4x slower on this stack; ordering is done with events instead)
     if (opts && opts->reserved0) {
@@ -972,122 +978,138 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
                (e = stream_acquire(b->device, &b->stream_lpf)) != hipSuccess)
         return hip_fail(e, "hipStreamCreate");
     b->stream_voc = b->stream;
-    hipEventCreateWithFlags(&b->ev_mlpg_done, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_voc_done, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_lf0, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_lpf, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_prep, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_build, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_mcpbuild, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_ivar, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_fb, hipEventDisableTiming);
-    hipEventCreate(&b->ev0);
-    hipEventCreate(&b->ev1);
-    hipEventCreate(&b->ev2);
-    hipEventCreate(&b->ev3);
+    // the ordering events carry no time stamps; ev0..ev3 are the ones run(timed) reads times from
+    static const struct {
+        hipEvent_t Batch::*ev;
+        unsigned flags;
+    } events[] = {
+        {&Batch::ev_mlpg_done, hipEventDisableTiming}, {&Batch::ev_voc_done, hipEventDisableTiming},
+        {&Batch::ev_fork, hipEventDisableTiming},      {&Batch::ev_lf0, hipEventDisableTiming},
+        {&Batch::ev_lpf, hipEventDisableTiming},       {&Batch::ev_prep, hipEventDisableTiming},
+        {&Batch::ev_build, hipEventDisableTiming},     {&Batch::ev_mcpbuild, hipEventDisableTiming},
+        {&Batch::ev_ivar, hipEventDisableTiming},      {&Batch::ev_fb, hipEventDisableTiming},
+        {&Batch::ev0, hipEventDefault},                {&Batch::ev1, hipEventDefault},
+        {&Batch::ev2, hipEventDefault},                {&Batch::ev3, hipEventDefault},
+    };
+    for (const auto &t : events) // (~Batch destroys the ones that were made)
+        if ((e = hipEventCreateWithFlags(&(b->*t.ev), t.flags)) != hipSuccess)
+            return hip_fail(e, "hipEventCreate");
+    b->B = (int)c.n;
+    return JB_OK;
+}
 
-    const int B = (int)n;
-    b->B = B;
-    std::vector<StreamStatesDev> gathered; // indexed source: per-state Gaussians produced on the device
-    cmark("streams and events made");
-    if (idx && (rc = b->gather_states(voice, *idx, n, gathered)))
+// n elements of a host array into the upload arena, which de-duplicates by host pointer: utterances that alias each
+// other's arrays share one copy (what first_of_kind and ivar_owner go by)
+template <class T> int upload_to(Batch *b, const T *host, size_t n, const T *&dev)
+{
+    const void *dp = nullptr;
+    const int rc = b->upload(host, sizeof(T) * n, &dp);
+    dev = (const T *)dp;
+    return rc;
+}
+
+// The state arrays of stream si of utterance i: taken from the gather (indexed source), or uploaded
+int upload_stream_states(CreateCtx &c, size_t i, uint32_t si)
+{
+    Batch *b = c.b;
+    const jb_stream_states &hs = c.utts[i].stream[si];
+    const jb_stream_desc &sd = c.voice->stream[si];
+    const size_t S = c.utts[i].num_states, WL = (size_t)sd.vector_length * sd.num_windows;
+    StreamStatesDev &ds = c.hu[i].st[si];
+    int rc;
+    if (c.idx) {
+        const StreamStatesDev &g = c.gathered[i * c.voice->nstream + si];
+        ds.mean = g.mean;
+        ds.var = g.var;
+        ds.msd = g.msd;
+    } else if (c.trk) {
+        ds.mean = ds.var = nullptr; // no MLPG: the tracks are given
+        if ((rc = upload_to(b, hs.msd, S, ds.msd)))
+            return rc;
+    } else {
+        if (S && (!hs.mean || !hs.var)) {
+            set_error("stream mean/var missing");
+            return JB_ERR_INVALID;
+        }
+        if ((rc = upload_to(b, hs.mean, WL * S, ds.mean)) || (rc = upload_to(b, hs.var, WL * S, ds.var)) ||
+            (rc = upload_to(b, hs.msd, S, ds.msd)))
+            return rc;
+    }
+    ds.gv_mean = ds.gv_var = nullptr;
+    ds.gv_switch = nullptr;
+    if (sd.use_gv && hs.gv_mean && hs.gv_var && hs.gv_switch &&
+        ((rc = upload_to(b, hs.gv_mean, sd.vector_length, ds.gv_mean)) ||
+         (rc = upload_to(b, hs.gv_var, sd.vector_length, ds.gv_var)) || (rc = upload_to(b, hs.gv_switch, S, ds.gv_switch))))
         return rc;
-    cmark("states gathered on the device");
+    ds.gv_weight = hs.gv_weight;
+    ds.msd_threshold = hs.msd_threshold;
+    return JB_OK;
+}
+
+// Each utterance's frames and its place in the concatenated frame, state and [dim][frame] arrays; its inputs staged
+int layout_utterances(CreateCtx &c)
+{
+    Batch *b = c.b;
+    const size_t n = c.n;
     b->T.resize(n);
     b->frame_off.resize(n + 1);
-    std::vector<UttDev> hu(n);
-    uint64_t sumT = 0, sumS = 0, sum_mt = 0; // sum_mt: frames of the [dim][frame] workspace, rows padded to 16
-    uint32_t maxT = 0, maxS = 0;
+    c.hu.resize(n);
+    uint64_t sumT = 0;
+    uint32_t maxT = 0;
+    int rc;
     for (size_t i = 0; i < n; i++) {
-        const jb_state_utt &u = utts[i];
+        const jb_state_utt &u = c.utts[i];
+        UttDev &h = c.hu[i];
         if (u.num_states && !u.durations)
             return JB_ERR_INVALID;
         uint64_t T = 0;
         for (uint32_t s = 0; s < u.num_states; s++)
             T += u.durations[s];
-        if (T > 0xffffffffull / voice->fperiod) {
+        if (T > 0xffffffffull / c.voice->fperiod) {
             set_error("utterance too long");
             return JB_ERR_INVALID;
         }
         b->T[i] = (uint32_t)T;
         b->frame_off[i] = sumT;
-        hu[i].S = u.num_states;
-        hu[i].T = (uint32_t)T;
-        hu[i].frame_off = sumT;
-        hu[i].state_off = sumS;
-        hu[i].mt_rs = (uint32_t)((T + 15) / 16 * 16);
-        hu[i].mt_off = sum_mt;
-        sum_mt += hu[i].mt_rs;
+        h.S = u.num_states;
+        h.T = (uint32_t)T;
+        h.frame_off = sumT;
+        h.state_off = c.sumS;
+        h.mt_rs = (uint32_t)((T + 15) / 16 * 16);
+        h.mt_off = c.sum_mt;
+        c.sum_mt += h.mt_rs;
         sumT += T;
-        sumS += u.num_states;
+        c.sumS += u.num_states;
         maxT = std::max(maxT, (uint32_t)T);
-        maxS = std::max(maxS, u.num_states);
-        const void *dp;
-        if ((rc = b->upload(u.durations, sizeof(uint32_t) * u.num_states, &dp)))
+        c.maxS = std::max(c.maxS, u.num_states);
+        if ((rc = upload_to(b, u.durations, u.num_states, h.dur)))
             return rc;
-        hu[i].dur = (const uint32_t *)dp;
-        for (uint32_t si = 0; si < voice->nstream; si++) {
-            const jb_stream_states &hs = u.stream[si];
-            const jb_stream_desc &sd = voice->stream[si];
-            const size_t WL = (size_t)sd.vector_length * sd.num_windows;
-            StreamStatesDev &ds = hu[i].st[si];
-            if (idx) {
-                const StreamStatesDev &g = gathered[i * voice->nstream + si];
-                ds.mean = g.mean;
-                ds.var = g.var;
-                ds.msd = g.msd;
-            } else if (trk) {
-                ds.mean = ds.var = nullptr; // no MLPG: the tracks are given
-                if ((rc = b->upload(hs.msd, sizeof(double) * u.num_states, &dp)))
-                    return rc;
-                ds.msd = (const double *)dp;
-            } else {
-                if (u.num_states && (!hs.mean || !hs.var)) {
-                    set_error("stream mean/var missing");
-                    return JB_ERR_INVALID;
-                }
-                if ((rc = b->upload(hs.mean, sizeof(double) * WL * u.num_states, &dp)))
-                    return rc;
-                ds.mean = (const double *)dp;
-                if ((rc = b->upload(hs.var, sizeof(double) * WL * u.num_states, &dp)))
-                    return rc;
-                ds.var = (const double *)dp;
-                if ((rc = b->upload(hs.msd, sizeof(double) * u.num_states, &dp)))
-                    return rc;
-                ds.msd = (const double *)dp;
-            }
-            ds.gv_mean = ds.gv_var = nullptr;
-            ds.gv_switch = nullptr;
-            if (sd.use_gv && hs.gv_mean && hs.gv_var && hs.gv_switch) {
-                if ((rc = b->upload(hs.gv_mean, sizeof(double) * sd.vector_length, &dp)))
-                    return rc;
-                ds.gv_mean = (const double *)dp;
-                if ((rc = b->upload(hs.gv_var, sizeof(double) * sd.vector_length, &dp)))
-                    return rc;
-                ds.gv_var = (const double *)dp;
-                if ((rc = b->upload(hs.gv_switch, u.num_states, &dp)))
-                    return rc;
-                ds.gv_switch = (const uint8_t *)dp;
-            }
-            ds.gv_weight = hs.gv_weight;
-            ds.msd_threshold = hs.msd_threshold;
-        }
+        for (uint32_t si = 0; si < c.voice->nstream; si++)
+            if ((rc = upload_stream_states(c, i, si)))
+                return rc;
     }
     b->frame_off[n] = sumT;
     b->sumT = sumT;
     b->maxT = maxT;
-    // distinct utterances (copies share their uploaded / gathered arrays): what the vocoder's warm-up length goes by
-    {
-        std::set<std::tuple<const void *, uint32_t, const void *, const void *>> seen_utts;
-        b->first_of_kind.assign(n, 0);
-        for (size_t i = 0; i < n; i++)
-            b->first_of_kind[i] = seen_utts.emplace((const void *)hu[i].dur, hu[i].S, (const void *)hu[i].st[0].mean,
-                                                    (const void *)(voice->nstream > 1 ? hu[i].st[1].mean : nullptr)).second;
-    }
+    return JB_OK;
+}
+
+// Copies of an utterance share their uploaded / gathered arrays: found by those pointers
+void share_copies(CreateCtx &c)
+{
+    Batch *b = c.b;
+    const size_t n = c.n;
+    const uint32_t ns = c.voice->nstream;
+    std::vector<UttDev> &hu = c.hu;
+    // distinct utterances: what the vocoder's warm-up length goes by
+    std::set<std::tuple<const void *, uint32_t, const void *, const void *>> seen_utts;
+    b->first_of_kind.assign(n, 0);
+    for (size_t i = 0; i < n; i++)
+        b->first_of_kind[i] = seen_utts.emplace((const void *)hu[i].dur, hu[i].S, (const void *)hu[i].st[0].mean,
+                                                (const void *)(ns > 1 ? hu[i].st[1].mean : nullptr)).second;
     // one inverse-variance table per distinct variance array (256 copies of an utterance: one table of 2.5 MB that
     // stays in L2 instead of 256 of them, 640 MB, behind the build's gathers)
-    for (uint32_t si = 0; si < voice->nstream; si++) {
+    for (uint32_t si = 0; si < ns; si++) {
         std::map<std::pair<const void *, uint32_t>, size_t> first;
         for (size_t i = 0; i < n; i++) {
             auto it = first.emplace(std::make_pair((const void *)hu[i].st[si].var, hu[i].S), i).first;
@@ -1096,210 +1118,238 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
             hu[i].ivar_owner[si] = shared ? 0 : 1;
         }
     }
+}
 
-    cmark("descriptors, uploads staged");
-    if ((rc = b->flush_uploads()))
-        return rc;
-    cmark("uploads flushed");
+// The descriptor table and the launch order, staged; BatchDev
+int stage_descriptors(CreateCtx &c)
+{
+    Batch *b = c.b;
+    const size_t n = c.n;
+    int rc;
     UttDev *dutt;
-    if ((rc = b->stage(hu.data(), n, &dutt)))
+    if ((rc = b->stage(c.hu.data(), n, &dutt)))
         return rc;
     // launch order: longest utterance first (LPT within the GPU)
-    std::vector<uint32_t> order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t a, uint32_t c) { return b->T[a] > b->T[c]; });
+    c.order.resize(n);
+    std::iota(c.order.begin(), c.order.end(), 0u);
+    std::stable_sort(c.order.begin(), c.order.end(), [&](uint32_t x, uint32_t y) { return b->T[x] > b->T[y]; });
     uint32_t *dord;
-    if ((rc = b->stage(order.data(), n, &dord)))
+    if ((rc = b->stage(c.order.data(), n, &dord)))
         return rc;
-    b->bd.B = B;
+    b->bd.B = b->B;
     b->bd.utt = dutt;
     b->bd.order = dord;
-    b->bd.maxT = maxT;
-    b->bd.maxS = maxS;
+    b->bd.maxT = b->maxT;
+    b->bd.maxS = c.maxS;
+    return JB_OK;
+}
 
-    // ---- per-stream scratch + MLPG workspace ----
-    for (uint32_t si = 0; si < voice->nstream; si++) {
-        const jb_stream_desc &hs = voice->stream[si];
-        StreamDev &sd = b->sd[si];
-        memset(&sd, 0, sizeof sd);
-        sd.L = (int)hs.vector_length;
-        sd.W = (int)hs.num_windows;
-        sd.is_msd = trk ? (si == 1) : (int)hs.is_msd;
-        sd.use_gv = trk ? 0 : (int)hs.use_gv;
-        if (trk)
-            sd.W = 1; // the window description is not read without MLPG (and may be absent)
-        int off = 0, maxw = trk ? 1 : 0;
-        for (int w = 0; !trk && w < sd.W; w++) {
-            sd.win_width[w] = (int)hs.win_width[w];
-            sd.win_off[w] = off;
-            for (int k = 0; k < sd.win_width[w]; k++)
-                sd.win_coef[off + k] = hs.win_coef[off + k];
-            off += sd.win_width[w];
-            maxw = std::max(maxw, sd.win_width[w]);
-        }
-        sd.BW = (maxw / 2) * 2 + 1; // Windows::max_width()*2+1 (window.rs:19-21, mlpg.rs:27)
-        sd.generic_solver = (b->flags & JB_BATCH_GENERIC_MLPG) ? 1 : 0;
-        sd.serial_gv = (b->flags & JB_BATCH_SERIAL_GV) ? 1 : 0;
-        // [dim][frame] workspace with the fused kernels: band width 3, up to three windows (the sliding-window
-        // build), 3..60 dims; everything else takes the generic reference-shaped kernels
-        sd.mt = (sd.BW == 3 && sd.W <= 3 && !sd.generic_solver && sd.L > 2 && sd.L <= mlpg_mt_max_dim()) ? 1 : 0;
-        // MCP, non-MSD, [dim][frame]: its transpose is fused with mc2b (enqueue_paramgen)
-        // (Stage::NonZero reads the [frame][dim] track itself: k_stage_coef)
-        sd.defer_out = (si == 0 && sd.mt && !sd.is_msd && voice->stage == 0 && !trk) ? 1 : 0;
-        const size_t nf = (size_t)sumT, nfl = std::max((size_t)sumT, (size_t)sum_mt) * (size_t)sd.L, nst = (size_t)sumS;
-        if ((rc = b->dalloc(&sd.s_start, nst, false)) || (rc = b->dalloc(&sd.s_vpre, nst, false)) ||
-            (rc = b->dalloc(&sd.s_rstart, nst, false)) || (rc = b->dalloc(&sd.s_rend, nst, false)) ||
-            (rc = b->dalloc(&sd.s_voiced, nst, false)) || (rc = b->dalloc(&sd.run_list, nst, false)) ||
-            (rc = b->dalloc(&sd.nruns, n, true)))
-            return rc;
-        if ((rc = b->dalloc(&sd.fstate, nf, false)) || (rc = b->dalloc(&sd.voiced, nf, false)) ||
-            (rc = b->dalloc(&sd.fl, nf, false)) || (rc = b->dalloc(&sd.fr, nf, false)) ||
-            (rc = b->dalloc(&sd.vidx, nf, false)) || (rc = b->dalloc(&sd.vsw, nf, false)) ||
-            (rc = b->dalloc(&sd.Tv, n, true)) || (rc = b->dalloc(&sd.gvlen, n, true)))
-            return rc;
-        const bool is_static = sd.BW == 1 && sd.W == 1 && !sd.use_gv && !sd.generic_solver;
-        if (!is_static && !trk) {
-            for (int j = 0; j < sd.BW; j++)
-                if ((rc = b->dalloc(&sd.A[j], nfl, false)) || (rc = b->dalloc(&sd.F[j], nfl, false)))
-                    return rc;
-            if ((rc = b->dalloc(&sd.bvec, nfl, false)) || (rc = b->dalloc(&sd.g, nfl, false)) ||
-                (rc = b->dalloc(&sd.par, nfl, false)))
-                return rc;
-            if (sd.mt && (rc = b->dalloc(&sd.ivar, nst * (size_t)sd.W * (size_t)sd.L, false)))
-                return rc;
-            if (sd.mt && sd.use_gv && !sd.serial_gv) {
-                sd.gv_ntile = (maxT + (uint32_t)mlpg_gv_tile_frames() - 1) / (uint32_t)mlpg_gv_tile_frames();
-                const size_t nbl = n * (size_t)sd.L;
-                if ((rc = b->dalloc(&sd.gv_part, 7 * nbl * (size_t)sd.gv_ntile * 4, false)) ||
-                    (rc = b->dalloc(&sd.gv_scal, 6 * nbl * 4, false)))
-                    return rc;
-                // resident GV (one persistent launch, jb_gv_gang.hip) unless the CUs are partitioned (its
-                // grid is sized for the whole device) or a row has more tiles than a gang can hold
-                int tiles = 0, gangs = 0;
-                // (JB_BATCH_INVARIANT: whether the resident kernel takes a batch depends on its longest row, and
-                // whether it forms on what else runs on the device; wherever it does not run, its multi-launch form
-                // k_mlpg_gv_gsweep does, with the same sums, instead of k_mlpg_gv_tp)
-                sd.gv_gsweep = b->invariant ? 1 : 0;
-                if (maxT > 0 &&
-                    gv_gang_plan(dev, maxT, (uint32_t)nbl, &tiles, &gangs)) {
-                    uint8_t *ctl;
-                    if ((rc = b->dalloc(&ctl, gv_gang_ctl_bytes(gangs), true)))
-                        return rc;
-                    // bins of utterances whose rows share a pass of a gang (the frames of an MSD stream's rows are
-                    // counted on the device: its utterances keep a pass each, tiles by their upper bound)
-                    std::vector<uint8_t> has_gv(n);
-                    std::vector<uint32_t> Tb(n);
-                    for (size_t i = 0; i < n; i++) {
-                        has_gv[i] = hu[i].st[si].gv_mean != nullptr;
-                        Tb[i] = sd.is_msd ? maxT : b->T[i];
-                    }
-                    std::vector<GvBinEntry> bins;
-                    gv_gang_bins(Tb.data(), has_gv.data(), order.data(), n, tiles, bins);
-                    GvBinEntry *dbins;
-                    if ((rc = b->stage(bins.data(), bins.size(), &dbins)))
-                        return rc;
-                    sd.gv_bins = dbins;
-                    sd.gv_nbins = (uint32_t)(bins.size() / (size_t)tiles);
-                    if ((uint32_t)gangs > sd.gv_nbins * (uint32_t)sd.L)
-                        gangs = (int)(sd.gv_nbins * (uint32_t)sd.L);
-                    sd.gv_gang_ctl = ctl;
-                    sd.gv_gang_n = gangs;
-                    sd.gv_gang_tiles = tiles;
-                }
-            }
-        }
-        if ((rc = b->dalloc(&sd.out, nfl, false)))
-            return rc;
-        if (trk) // the tracks themselves: [frame][dim] per utterance at frame_off * L
-            for (size_t i = 0; i < n; i++) {
-                const jb_track_utt &t = trk->utts[i];
-                const double *src = si == 0 ? t.spectrum : si == 1 ? t.lf0 : t.lpf;
-                const size_t ne = (size_t)b->T[i] * (size_t)sd.L;
-                if (ne && (e = hipMemcpy(sd.out + (size_t)b->frame_off[i] * (size_t)sd.L, src, ne * sizeof(double),
-                                         hipMemcpyHostToDevice)) != hipSuccess)
-                    return hip_fail(e, "hipMemcpy(H2D tracks)");
-            }
+// Time-parallel GV of stream si: its partial sums, and the resident kernel's control block and bins where it can run
+int alloc_resident_gv(CreateCtx &c, uint32_t si)
+{
+    Batch *b = c.b;
+    StreamDev &sd = b->sd[si];
+    const size_t n = c.n;
+    const uint32_t maxT = b->maxT;
+    int rc;
+    sd.gv_ntile = (maxT + (uint32_t)mlpg_gv_tile_frames() - 1) / (uint32_t)mlpg_gv_tile_frames();
+    const size_t nbl = n * (size_t)sd.L;
+    if ((rc = b->dalloc(&sd.gv_part, 7 * nbl * (size_t)sd.gv_ntile * 4, false)) ||
+        (rc = b->dalloc(&sd.gv_scal, 6 * nbl * 4, false)))
+        return rc;
+    // resident GV (one persistent launch, jb_gv_gang.hip) unless the CUs are partitioned (its
+    // grid is sized for the whole device) or a row has more tiles than a gang can hold
+    int tiles = 0, gangs = 0;
+    // (JB_BATCH_INVARIANT: whether the resident kernel takes a batch depends on its longest row, and
+    // whether it forms on what else runs on the device; wherever it does not run, its multi-launch form
+    // k_mlpg_gv_gsweep does, with the same sums, instead of k_mlpg_gv_tp)
+    sd.gv_gsweep = b->invariant ? 1 : 0;
+    if (maxT == 0 || !gv_gang_plan(b->device, maxT, (uint32_t)nbl, &tiles, &gangs))
+        return JB_OK;
+    uint8_t *ctl;
+    if ((rc = b->dalloc(&ctl, gv_gang_ctl_bytes(gangs), true)))
+        return rc;
+    // bins of utterances whose rows share a pass of a gang (the frames of an MSD stream's rows are
+    // counted on the device: its utterances keep a pass each, tiles by their upper bound)
+    std::vector<uint8_t> has_gv(n);
+    std::vector<uint32_t> Tb(n);
+    for (size_t i = 0; i < n; i++) {
+        has_gv[i] = c.hu[i].st[si].gv_mean != nullptr;
+        Tb[i] = sd.is_msd ? maxT : b->T[i];
     }
+    std::vector<GvBinEntry> bins;
+    gv_gang_bins(Tb.data(), has_gv.data(), c.order.data(), n, tiles, bins);
+    GvBinEntry *dbins;
+    if ((rc = b->stage(bins.data(), bins.size(), &dbins)))
+        return rc;
+    sd.gv_bins = dbins;
+    sd.gv_nbins = (uint32_t)(bins.size() / (size_t)tiles);
+    if ((uint32_t)gangs > sd.gv_nbins * (uint32_t)sd.L)
+        gangs = (int)(sd.gv_nbins * (uint32_t)sd.L);
+    sd.gv_gang_ctl = ctl;
+    sd.gv_gang_n = gangs;
+    sd.gv_gang_tiles = tiles;
+    return JB_OK;
+}
 
-    cmark("stream workspaces allocated");
-    // ---- vocoder ----
+// Stream si: its mode (plan_stream_mode), windows, per-state and per-frame scratch, MLPG workspace and track
+int make_stream(CreateCtx &c, uint32_t si)
+{
+    Batch *b = c.b;
+    const TrackSrc *trk = c.trk;
+    const size_t n = c.n;
+    const jb_stream_desc &hs = c.voice->stream[si];
+    StreamDev &sd = b->sd[si];
+    memset(&sd, 0, sizeof sd);
+    const StreamMode m = plan_stream_mode(hs, si, b->flags, c.voice->stage, trk != nullptr, mlpg_mt_max_dim());
+    sd.L = (int)hs.vector_length;
+    sd.W = m.W;
+    sd.is_msd = m.is_msd;
+    sd.use_gv = m.use_gv;
+    sd.BW = m.BW;
+    sd.mt = m.mt;
+    sd.defer_out = m.defer_out;
+    int off = 0;
+    for (int w = 0; !trk && w < sd.W; w++) { // (the window description is not read without MLPG, and may be absent)
+        sd.win_width[w] = (int)hs.win_width[w];
+        sd.win_off[w] = off;
+        for (int k = 0; k < sd.win_width[w]; k++)
+            sd.win_coef[off + k] = hs.win_coef[off + k];
+        off += sd.win_width[w];
+    }
+    sd.generic_solver = (b->flags & JB_BATCH_GENERIC_MLPG) ? 1 : 0;
+    sd.serial_gv = (b->flags & JB_BATCH_SERIAL_GV) ? 1 : 0;
+    const size_t nf = (size_t)b->sumT, nfl = std::max((size_t)b->sumT, (size_t)c.sum_mt) * (size_t)sd.L,
+                 nst = (size_t)c.sumS;
+    int rc;
+    if ((rc = b->dalloc(&sd.s_start, nst, false)) || (rc = b->dalloc(&sd.s_vpre, nst, false)) ||
+        (rc = b->dalloc(&sd.s_rstart, nst, false)) || (rc = b->dalloc(&sd.s_rend, nst, false)) ||
+        (rc = b->dalloc(&sd.s_voiced, nst, false)) || (rc = b->dalloc(&sd.run_list, nst, false)) ||
+        (rc = b->dalloc(&sd.nruns, n, true)))
+        return rc;
+    if ((rc = b->dalloc(&sd.fstate, nf, false)) || (rc = b->dalloc(&sd.voiced, nf, false)) ||
+        (rc = b->dalloc(&sd.fl, nf, false)) || (rc = b->dalloc(&sd.fr, nf, false)) ||
+        (rc = b->dalloc(&sd.vidx, nf, false)) || (rc = b->dalloc(&sd.vsw, nf, false)) ||
+        (rc = b->dalloc(&sd.Tv, n, true)) || (rc = b->dalloc(&sd.gvlen, n, true)))
+        return rc;
+    if (!sd.is_static() && !trk) {
+        for (int j = 0; j < sd.BW; j++)
+            if ((rc = b->dalloc(&sd.A[j], nfl, false)) || (rc = b->dalloc(&sd.F[j], nfl, false)))
+                return rc;
+        if ((rc = b->dalloc(&sd.bvec, nfl, false)) || (rc = b->dalloc(&sd.g, nfl, false)) ||
+            (rc = b->dalloc(&sd.par, nfl, false)))
+            return rc;
+        if (sd.mt && (rc = b->dalloc(&sd.ivar, nst * (size_t)sd.W * (size_t)sd.L, false)))
+            return rc;
+        if (sd.mt && sd.use_gv && !sd.serial_gv && (rc = alloc_resident_gv(c, si)))
+            return rc;
+    }
+    if ((rc = b->dalloc(&sd.out, nfl, false)))
+        return rc;
+    for (size_t i = 0; trk && i < n; i++) { // the tracks themselves: [frame][dim] per utterance at frame_off * L
+        const jb_track_utt &t = trk->utts[i];
+        const double *src = si == 0 ? t.spectrum : si == 1 ? t.lf0 : t.lpf;
+        const size_t ne = (size_t)b->T[i] * (size_t)sd.L;
+        hipError_t e;
+        if (ne && (e = hipMemcpy(sd.out + (size_t)b->frame_off[i] * (size_t)sd.L, src, ne * sizeof(double),
+                                 hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_fail(e, "hipMemcpy(H2D tracks)");
+    }
+    return JB_OK;
+}
+
+// VocDev's scalars: the voice's vocoder, the frame blocks (plan_frame_blocks), the vocoder conditions
+// (plan_voc_conditions; a batch whose utterances differ has them in vd.uvoc, staged here)
+int set_vocoder_shape(CreateCtx &c)
+{
+    Batch *b = c.b;
+    const jb_voice_desc *voice = c.voice;
     VocDev &vd = b->vd;
     memset(&vd, 0, sizeof vd);
     vd.fs = (int)voice->sampling_frequency;
     vd.fperiod = (int)voice->fperiod;
     vd.nmcp = (int)voice->stream[0].vector_length;
     vd.nlpf = (int)voice->stream[2].vector_length;
-    // A frame's samples in blocks of bs <= 64 (one pulse-mask word and one wave pass of lane = sample per block).
-    // The largest divisor of the frame period that is <= 64 where there is a useful one (every BASELINE shape: 240 ->
-    // 4 x 60; the split excitation kernels and the lane-triple vocoder are built on equal blocks); otherwise -- a
-    // prime frame period, 75 = 3 x 25 under a 31-tap filter -- blocks of ceil(fperiod / nblk) samples with a shorter
-    // LAST block (block q = samples [q bs, min(fperiod, (q + 1) bs)): sample i is bit i % bs of word i / bs either way).
-    int bs = std::min(64, vd.fperiod);
-    while (vd.fperiod % bs)
-        bs--;
-    if ((bs < vd.nlpf - 1 || bs < 16) && bs < std::min(64, vd.fperiod)) {
-        const int nblk = (vd.fperiod + 63) / 64;
-        bs = (vd.fperiod + nblk - 1) / nblk;
+    const FrameBlocks fb = plan_frame_blocks(vd.fperiod, vd.nlpf);
+    vd.bs = fb.bs;
+    vd.nblk = fb.nblk;
+    VocCondPlan cp = plan_voc_conditions(jb_utt_voc{voice->alpha, voice->beta, voice->volume}, (uint32_t)vd.nmcp,
+                                         voice->stage, c.voc, c.n);
+    vd.alpha = cp.batch.alpha;
+    vd.volume = cp.batch.volume;
+    vd.beta = cp.batch.beta;
+    vd.beta_stage = cp.batch.beta_stage;
+    if (cp.mixed) {
+        b->uvoc = std::move(cp.utt);
+        b->voc_class = std::move(cp.cls);
+        b->n_classes = cp.n_classes;
+        VocUtt *dev_uvoc = nullptr;
+        int rc;
+        if ((rc = b->stage(b->uvoc.data(), c.n, &dev_uvoc)))
+            return rc;
+        vd.uvoc = dev_uvoc;
     }
-    vd.bs = bs;
-    vd.nblk = (vd.fperiod + bs - 1) / bs;
-    // The vocoder condition (voc_utt).  One for the whole batch -- no jb_utt_voc, or every entry the same -- stands
-    // in vd.alpha / volume / beta / beta_stage, and the kernels run as they always have.  Otherwise vd.uvoc holds each
-    // utterance's; vd.beta / beta_stage then say only whether SOME utterance has a post-filter (what is allocated and
-    // launched), and the lane kernel's launch permutation keeps the condition classes apart (build_work).
-    std::vector<double> pf_alphas; // the alpha of each post-filter operator (vd.pf_table)
-    {
-        const VocUtt v0 = voc_utt(voice, (voc && n) ? &voc[0] : nullptr);
-        bool mixed = false;
-        for (size_t i = 1; voc && i < n && !mixed; i++)
-            mixed = !same_voc(voc_utt(voice, &voc[i]), v0);
-        vd.alpha = v0.alpha;
-        vd.volume = v0.volume;
-        vd.beta = v0.beta;
-        vd.beta_stage = v0.beta_stage;
-        if (v0.beta > 0.0)
-            pf_alphas.push_back(v0.alpha);
-        if (mixed) {
-            b->uvoc.resize(n);
-            b->voc_class.resize(n);
-            std::vector<std::pair<double, double>> cls; // (alpha, volume) of each class
-            for (size_t i = 0; i < n; i++) {
-                VocUtt &u = b->uvoc[i];
-                u = voc_utt(voice, &voc[i]);
-                const auto key = std::make_pair(u.alpha, u.volume);
-                const size_t c = std::find(cls.begin(), cls.end(), key) - cls.begin();
-                if (c == cls.size())
-                    cls.push_back(key);
-                b->voc_class[i] = (uint32_t)c;
-                if (u.beta > 0.0) {
-                    const size_t k = std::find(pf_alphas.begin(), pf_alphas.end(), u.alpha) - pf_alphas.begin();
-                    if (k == pf_alphas.size())
-                        pf_alphas.push_back(u.alpha);
-                    u.pf = (uint32_t)k;
-                }
-                vd.beta = std::max(vd.beta, u.beta);
-                vd.beta_stage = std::max(vd.beta_stage, u.beta_stage);
-            }
-            b->n_classes = (uint32_t)cls.size();
-            VocUtt *dev_uvoc = nullptr;
-            if ((rc = b->stage(b->uvoc.data(), n, &dev_uvoc)))
-                return rc;
-            vd.uvoc = dev_uvoc;
-        }
-        vd.n_pf = (uint32_t)pf_alphas.size();
-    }
+    c.pf_alphas = std::move(cp.pf_alphas);
+    vd.n_pf = (uint32_t)c.pf_alphas.size();
     vd.stage = (int)voice->stage;
     vd.use_log_gain = voice->use_log_gain ? 1 : 0;
     vd.voiced = b->sd[1].voiced;
     vd.run_list = b->sd[1].run_list;
     vd.nruns = b->sd[1].nruns;
-    if ((rc = b->dalloc(&vd.run_base, n + 1, true)) || (rc = b->dalloc(&vd.run_counter, 1, true)))
-        return rc;
     vd.mcp = b->sd[0].out;
     vd.lf0 = b->sd[1].out;
     vd.lpf = b->sd[2].out;
-    const size_t nf = (size_t)sumT;
+    return JB_OK;
+}
+
+// Shared pulse-free excitation (jb_device.h): the table, the per-frame source codes, the work list of the
+// per-frame pass.  With the debug tap (every sample wanted as computed per utterance) and on request
+// (JB_BATCH_NO_EXC_TABLE: A/B tests) every frame goes through the per-frame pass.
+int alloc_excitation_table(CreateCtx &c)
+{
+    Batch *b = c.b;
+    VocDev &vd = b->vd;
+    const size_t n = c.n, nf = (size_t)b->sumT;
+    int rc;
+    vd.exc_no_table = (vd.exc || (b->flags & JB_BATCH_NO_EXC_TABLE)) ? 1 : 0;
+    // which frames carry the canonical taps: tracked by the LPF MLPG itself where that is the one-window
+    // kernel (a byte per frame instead of a second pass over the track); else k_exc_classify compares rows
+    StreamDev &sl = b->sd[2];
+    if (!c.trk && sl.is_static() && !vd.exc_no_table && nf) {
+        if ((rc = b->dalloc(&sl.canon, nf, false)))
+            return rc;
+        sl.canon_n = nf;
+        sl.canon_ref_utt = 0;
+        for (size_t i = 0; i < n; i++)
+            if (b->T[i] > 0) {
+                sl.canon_ref_utt = (uint32_t)i; // owns the batch's first frame (frame_off 0)
+                break;
+            }
+        vd.lpf_canon = sl.canon;
+        // the canonical rows themselves need not be stored unless the track is a result
+        if (sl.L <= 32 && !(b->flags & JB_BATCH_KEEP_TRACKS)) {
+            sl.canon_skip_rows = 1;
+            vd.lpf_sparse = 1;
+        }
+    }
+    if ((rc = b->dalloc(&vd.exc_tab, std::max<size_t>((size_t)b->maxT * (size_t)vd.fperiod, 1), false)) ||
+        (rc = b->dalloc(&vd.exc_src, std::max<size_t>(nf, 1), true)) ||
+        (rc = b->dalloc(&vd.exc_gen, 2 * std::max<size_t>(nf, 1), false)) ||
+        (rc = b->dalloc(&vd.exc_gen_count, 1, true)))
+        return rc;
+    return JB_OK;
+}
+
+// The vocoder's buffers: coefficients, pitch and pulses, excitation, PCM, filter state, the noise stream, the
+// post-filter operators
+int alloc_vocoder(CreateCtx &c)
+{
+    Batch *b = c.b;
+    VocDev &vd = b->vd;
+    const size_t n = c.n, nf = (size_t)b->sumT;
+    int rc;
+    if ((rc = b->dalloc(&vd.run_base, n + 1, true)) || (rc = b->dalloc(&vd.run_counter, 1, true)))
+        return rc;
     const bool mlpg_only = (b->flags & JB_BATCH_MLPG_ONLY) != 0; // no excitation, no PCM: no slabs for them
     b->total_samples = nf * (size_t)vd.fperiod;
     if ((rc = b->dalloc(&vd.bcoef, nf * (size_t)vd.nmcp, false)) ||
@@ -1331,67 +1381,78 @@ int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n
     vd.skip_unvoiced = (!vd.exc && excite_is_split(vd)) ? 1 : 0;
     if (vd.nlpf == 0 && !mlpg_only && (rc = b->dalloc(&vd.uv_before, std::max<size_t>(nf, 1), false)))
         return rc; // ring-buffer-less excitation: unvoiced frames before each frame = its place in the noise stream
-    if (excite_is_split(vd) && !mlpg_only) {
-        // shared pulse-free excitation (jb_device.h): the table, the per-frame source codes, the work list of the
-        // per-frame pass.  With the debug tap (every sample wanted as computed per utterance) and on request
-        // (JB_BATCH_NO_EXC_TABLE: A/B tests) every frame goes through the per-frame pass.
-        vd.exc_no_table = (vd.exc || (b->flags & JB_BATCH_NO_EXC_TABLE)) ? 1 : 0;
-        {
-            // which frames carry the canonical taps: tracked by the LPF MLPG itself where that is the one-window
-            // kernel (a byte per frame instead of a second pass over the track); else k_exc_classify compares rows
-            StreamDev &sl = b->sd[2];
-            const bool is_static = sl.BW == 1 && sl.W == 1 && !sl.use_gv && !sl.generic_solver;
-            if (!trk && is_static && !vd.exc_no_table && nf) {
-                if ((rc = b->dalloc(&sl.canon, nf, false)))
-                    return rc;
-                sl.canon_n = nf;
-                sl.canon_ref_utt = 0;
-                for (size_t i = 0; i < n; i++)
-                    if (b->T[i] > 0) {
-                        sl.canon_ref_utt = (uint32_t)i; // owns the batch's first frame (frame_off 0)
-                        break;
-                    }
-                vd.lpf_canon = sl.canon;
-                // the canonical rows themselves need not be stored unless the track is a result
-                if (sl.L <= 32 && !(b->flags & JB_BATCH_KEEP_TRACKS)) {
-                    sl.canon_skip_rows = 1;
-                    vd.lpf_sparse = 1;
-                }
-            }
-        }
-        if ((rc = b->dalloc(&vd.exc_tab, std::max<size_t>((size_t)maxT * (size_t)vd.fperiod, 1), false)) ||
-            (rc = b->dalloc(&vd.exc_src, std::max<size_t>(nf, 1), true)) ||
-            (rc = b->dalloc(&vd.exc_gen, 2 * std::max<size_t>(nf, 1), false)) ||
-            (rc = b->dalloc(&vd.exc_gen_count, 1, true)))
-            return rc;
-    }
+    if (excite_is_split(vd) && !mlpg_only && (rc = alloc_excitation_table(c)))
+        return rc;
     vd.state_stride = vd.stage > 0 ? mglsa_state_doubles(vd.stage) : vocoder_state_doubles(vd.nmcp);
     if ((rc = b->dalloc(&vd.state, (size_t)vd.state_stride * n, true)))
         return rc;
-    if ((rc = noise_table(dev, (size_t)maxT * (size_t)vd.fperiod, &b->noise)))
+    if ((rc = noise_table(b->device, (size_t)b->maxT * (size_t)vd.fperiod, &b->noise)))
         return rc;
     vd.noise = b->noise->ptr;
     vd.noise_len = b->noise->len;
-    if (vd.beta > 0.0 && (e = launch_pf_table(vd, pf_alphas.data(), b->stream)) != hipSuccess)
+    hipError_t e;
+    if (vd.beta > 0.0 && (e = launch_pf_table(vd, c.pf_alphas.data(), b->stream)) != hipSuccess)
         return hip_fail(e, "k_pf_table");
-    cmark("vocoder buffers allocated");
+    return JB_OK;
+}
+
+} // namespace
+
+// A batch is put together in these steps, in this order (the arena and the device pool see the same sequence of
+// uploads and allocations whatever the source): checks -- everything that can be decided without a device comes
+// first --, a track's pseudo-states, device / streams / events, the gather of an indexed source, the utterances'
+// layout and uploads, the per-stream workspaces, the vocoder's buffers, the work list, and the flushes.
+int Batch::create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n, const jb_batch_opts *opts,
+                  Batch **out, const IndexSrc *idx, const TrackSrc *trk, const jb_utt_voc *voc)
+{
+    *out = nullptr;
+    CreateCtx c{voice, utts, n, opts, idx, trk, voc};
+    int rc;
+    if ((rc = check_create_args(c)) || (trk && (rc = track_pseudo_states(c))))
+        return rc;
+    if (n && !c.utts)
+        return JB_ERR_INVALID;
+    std::unique_ptr<Batch> b(new Batch());
+    c.b = b.get();
+    if ((rc = open_device(c)))
+        return rc;
+    c.mark("streams and events made");
+    if (idx && (rc = b->gather_states(voice, *idx, n, c.gathered)))
+        return rc;
+    c.mark("states gathered on the device");
+    if ((rc = layout_utterances(c)))
+        return rc;
+    share_copies(c);
+    c.mark("descriptors, uploads staged");
+    if ((rc = b->flush_uploads()))
+        return rc;
+    c.mark("uploads flushed");
+    if ((rc = stage_descriptors(c)))
+        return rc;
+    for (uint32_t si = 0; si < voice->nstream; si++)
+        if ((rc = make_stream(c, si)))
+            return rc;
+    c.mark("stream workspaces allocated");
+    if ((rc = set_vocoder_shape(c)) || (rc = alloc_vocoder(c)))
+        return rc;
+    c.mark("vocoder buffers allocated");
     if ((rc = b->build_work(opts)))
         return rc;
     if ((rc = b->flush_zero())) // (legacy stream, like the uploads: in order with them)
         return rc;
     if ((rc = b->flush_uploads()))
         return rc;
-    for (auto &c : b->up_chunks)
-        c.host.reset(); // staging copies are not needed any more
+    for (auto &ch : b->up_chunks)
+        ch.host.reset(); // staging copies are not needed any more
     // uploads and memsets ran on the legacy stream, the gather and the constant tables on the batch's
     // own: wait for those two, not for the device (another batch may be running a step)
-    cmark("work list built");
-    e = hipStreamSynchronize(nullptr);
+    c.mark("work list built");
+    hipError_t e = hipStreamSynchronize(nullptr);
     if (e == hipSuccess)
         e = hipStreamSynchronize(b->stream);
     if (e != hipSuccess)
         return hip_fail(e, "upload");
-    cmark("synchronised");
+    c.mark("synchronised");
     *out = b.release();
     return JB_OK;
 }
@@ -2754,20 +2815,18 @@ uint32_t jb_batch_gang_fallbacks(const jb_batch *b) { return b ? ((const Batch *
 
 void jb_batch_free(jb_batch *b) { delete (Batch *)b; }
 
-int jb_paramgen_vocode_batch(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n,
-                             const jb_batch_opts *opts, double *const *pcm, size_t *n_samples)
+// The one-shot PCM entries behind their create call: report the lengths, run once, read each utterance
+static int run_once_read_pcm(Batch *b, size_t n, double *const *pcm, size_t *n_samples)
 {
-    jb_batch *hb = nullptr;
-    int rc = jb_batch_create(voice, utts, n, opts, &hb);
-    if (rc)
-        return rc;
-    std::unique_ptr<Batch> guard((Batch *)hb);
+    std::unique_ptr<Batch> guard(b);
+    jb_batch *hb = (jb_batch *)b;
+    int rc;
     if (n_samples)
         for (size_t i = 0; i < n; i++)
             n_samples[i] = jb_batch_num_samples(hb, i);
     if (!pcm)
         return JB_OK;
-    if ((rc = guard->run(false)) || (rc = guard->sync()))
+    if ((rc = b->run(false)) || (rc = b->sync()))
         return rc;
     for (size_t i = 0; i < n; i++) {
         size_t ns = jb_batch_num_samples(hb, i);
@@ -2777,27 +2836,20 @@ int jb_paramgen_vocode_batch(const jb_voice_desc *voice, const jb_state_utt *utt
     return JB_OK;
 }
 
+int jb_paramgen_vocode_batch(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n,
+                             const jb_batch_opts *opts, double *const *pcm, size_t *n_samples)
+{
+    jb_batch *hb = nullptr;
+    const int rc = jb_batch_create(voice, utts, n, opts, &hb);
+    return rc ? rc : run_once_read_pcm((Batch *)hb, n, pcm, n_samples);
+}
+
 int jb_vocode_tracks_batch(const jb_voice_desc *voice, const jb_track_utt *utts, size_t n, const jb_batch_opts *opts,
                            double *const *pcm, size_t *n_samples)
 {
     jb_batch *hb = nullptr;
-    int rc = jb_batch_create_from_tracks(voice, utts, n, opts, &hb);
-    if (rc)
-        return rc;
-    std::unique_ptr<Batch> guard((Batch *)hb);
-    if (n_samples)
-        for (size_t i = 0; i < n; i++)
-            n_samples[i] = jb_batch_num_samples(hb, i);
-    if (!pcm)
-        return JB_OK;
-    if ((rc = guard->run(false)) || (rc = guard->sync()))
-        return rc;
-    for (size_t i = 0; i < n; i++) {
-        size_t ns = jb_batch_num_samples(hb, i);
-        if (ns && (rc = jb_batch_read_pcm(hb, i, pcm[i], ns)))
-            return rc;
-    }
-    return JB_OK;
+    const int rc = jb_batch_create_from_tracks(voice, utts, n, opts, &hb);
+    return rc ? rc : run_once_read_pcm((Batch *)hb, n, pcm, n_samples);
 }
 
 int jb_vocoder_synthesize_batch(const jb_voice_desc *voice, const jb_track_utt *utts, size_t n,
@@ -2806,24 +2858,8 @@ int jb_vocoder_synthesize_batch(const jb_voice_desc *voice, const jb_track_utt *
     Batch *b = nullptr;
     jb::TrackSrc src{utts};
     src.vocoder_level = true;
-    int rc = Batch::create(voice, nullptr, n, opts, &b, nullptr, &src);
-    if (rc)
-        return rc;
-    std::unique_ptr<Batch> guard(b);
-    jb_batch *hb = (jb_batch *)b;
-    if (n_samples)
-        for (size_t i = 0; i < n; i++)
-            n_samples[i] = jb_batch_num_samples(hb, i);
-    if (!pcm)
-        return JB_OK;
-    if ((rc = guard->run(false)) || (rc = guard->sync()))
-        return rc;
-    for (size_t i = 0; i < n; i++) {
-        size_t ns = jb_batch_num_samples(hb, i);
-        if (ns && (rc = jb_batch_read_pcm(hb, i, pcm[i], ns)))
-            return rc;
-    }
-    return JB_OK;
+    const int rc = Batch::create(voice, nullptr, n, opts, &b, nullptr, &src);
+    return rc ? rc : run_once_read_pcm(b, n, pcm, n_samples);
 }
 
 int jb_mlpg_batch(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n, const jb_batch_opts *opts,

@@ -24,7 +24,6 @@ constexpr int kPade = 5;          // MelLogSpectrumApproximation<6>: 5 stages (s
 constexpr int kGroups = 12;       // lane groups per Pade stage: 5*12 = 60 lanes of a wave64
 constexpr int kMaxTPL = 6;        // taps per lane of the wave kernels => nmcp-1 <= 72
 constexpr int kMaxNmcp = 64;      // ... and the 64-lane kernels (mc2b tile, post-filter, MGLSA): nmcp <= 64
-constexpr double kNoData = -1e10; // src/constants.rs:13
 
 struct StreamStatesDev {
     const double *mean;   // [S][W*L]
@@ -119,6 +118,8 @@ struct StreamDev {
     // 1: k_mlpg_static does not STORE a canonical row (but the batch's first): its readers take row 0 instead
     // (VocDev::lpf_sparse).  Not with JB_BATCH_KEEP_TRACKS: then the track is a result.
     int canon_skip_rows;
+    // the one-window case (k_mlpg_static): no MLPG workspace is allocated, and launch_mlpg takes that kernel
+    bool is_static() const { return mlpg_is_static(BW, W, use_gv, generic_solver); }
 };
 
 // One workgroup's share of a bin (above): utterance b (0xffffffff: none), tile k of its nt tiles, which stand at
@@ -157,15 +158,10 @@ static_assert(sizeof(GvGang) == 128 + sizeof(unsigned long long) * 2 * kGvGangMa
                                     (JB_GG_PROFILE ? sizeof(unsigned long long) * 2 * 8 * 96 : 0),
               "GvGang layout (host offsets in jb_batch.cpp and the kernel must agree)");
 
-// Vocoder condition of one utterance (jb_utt_voc after the beta rule of Batch::create): what VocDev::alpha / volume /
-// beta / beta_stage hold for a batch with one condition.  pf: which freqt operator of VocDev::pf_table (beta > 0).
-struct VocUtt {
-    double alpha, volume, beta, beta_stage;
-    uint32_t pf, pad;
-};
-
 struct VocDev {
-    int fs, fperiod, nmcp, nlpf, bs, nblk; // bs = samples per block (divides fperiod, <=64)
+    // bs = samples per block (<= 64), nblk = ceil(fperiod / bs) blocks per frame: bs divides fperiod wherever a useful
+    // divisor exists, else the last block is shorter (plan_frame_blocks, jb_plan.h)
+    int fs, fperiod, nmcp, nlpf, bs, nblk;
     double alpha, volume;
     // per-utterance conditions [B], or nullptr: every utterance runs under alpha / volume / beta / beta_stage here.
     // Only a batch whose utterances differ has the table; the kernels then read the utterance's own values (wave-

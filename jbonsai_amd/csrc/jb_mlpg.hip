@@ -2526,7 +2526,7 @@ static hipError_t launch_mlpg_inner(const BatchDev &bd, const StreamDev &sd, int
 {
     if (after_ivar && !(sd.BW == 3 && sd.mt)) // no inverse-variance pass on this path: "done" from the start
         (void)hipEventRecord(after_ivar, stream);
-    if (sd.BW == 1 && sd.W == 1 && !sd.use_gv && !sd.generic_solver) {
+    if (sd.is_static()) {
         const uint64_t work = (uint64_t)bd.maxT * (uint64_t)sd.L;
         if (work == 0 || bd.B == 0)
             return hipSuccess;

@@ -1,12 +1,11 @@
 // jb_plan.cpp -- the vocoder's work list (jb_plan.h): serial = one item per utterance; chunked = items of
 // chunk_frames output frames that start warmup_frames early from zero state.  Batch::build_work allocates and
-// uploads what this decides.
+// uploads what this decides.  Behind it, the shape rules of Batch::create.
 #include "jb_plan.h"
-
-#include "../../include/jbonsai_amd.h"
 
 #include <algorithm>
 #include <numeric>
+#include <utility>
 
 namespace jb {
 namespace {
@@ -230,6 +229,98 @@ VocPlan plan_vocoder_work(const VocPlanIn &in)
         }
     }
     return p;
+}
+
+FrameBlocks plan_frame_blocks(int fperiod, int nlpf)
+{
+    int bs = std::min(64, fperiod);
+    while (fperiod % bs)
+        bs--;
+    if ((bs < nlpf - 1 || bs < 16) && bs < std::min(64, fperiod)) {
+        const int nblk = (fperiod + 63) / 64;
+        bs = (fperiod + nblk - 1) / nblk;
+    }
+    return FrameBlocks{bs, (fperiod + bs - 1) / bs};
+}
+
+void plan_voiced_runs(const double *lf0, size_t n, std::vector<uint32_t> &durations, std::vector<double> &msd)
+{
+    for (size_t f = 0; f < n; f++) {
+        const double v = lf0[f] != kNoData ? 1.0 : 0.0;
+        if (msd.empty() || msd.back() != v) {
+            msd.push_back(v);
+            durations.push_back(0);
+        }
+        durations.back()++;
+    }
+}
+
+VocCondPlan plan_voc_conditions(const jb_utt_voc &voice, uint32_t nmcp, uint32_t stage, const jb_utt_voc *utt, size_t n)
+{
+    auto cond = [&](const jb_utt_voc &c) {
+        VocUtt u{};
+        u.alpha = c.alpha;
+        u.volume = c.volume;
+        u.beta = (c.beta > 0.0 && nmcp > 2 && stage == 0) ? c.beta : 0.0;
+        u.beta_stage = stage ? c.beta : 0.0;
+        return u;
+    };
+    auto same = [](const VocUtt &a, const VocUtt &b) {
+        return a.alpha == b.alpha && a.volume == b.volume && a.beta == b.beta && a.beta_stage == b.beta_stage;
+    };
+    VocCondPlan p;
+    p.batch = cond((utt && n) ? utt[0] : voice);
+    for (size_t i = 1; utt && i < n && !p.mixed; i++)
+        p.mixed = !same(cond(utt[i]), p.batch);
+    if (p.batch.beta > 0.0)
+        p.pf_alphas.push_back(p.batch.alpha);
+    if (!p.mixed)
+        return p;
+    p.utt.resize(n);
+    p.cls.resize(n);
+    std::vector<std::pair<double, double>> cls; // (alpha, volume) of each class
+    for (size_t i = 0; i < n; i++) {
+        VocUtt &u = p.utt[i];
+        u = cond(utt[i]);
+        const auto key = std::make_pair(u.alpha, u.volume);
+        const size_t c = std::find(cls.begin(), cls.end(), key) - cls.begin();
+        if (c == cls.size())
+            cls.push_back(key);
+        p.cls[i] = (uint32_t)c;
+        if (u.beta > 0.0) {
+            const size_t k = std::find(p.pf_alphas.begin(), p.pf_alphas.end(), u.alpha) - p.pf_alphas.begin();
+            if (k == p.pf_alphas.size())
+                p.pf_alphas.push_back(u.alpha);
+            u.pf = (uint32_t)k;
+        }
+        p.batch.beta = std::max(p.batch.beta, u.beta);
+        p.batch.beta_stage = std::max(p.batch.beta_stage, u.beta_stage);
+    }
+    p.n_classes = (uint32_t)cls.size();
+    return p;
+}
+
+StreamMode plan_stream_mode(const jb_stream_desc &s, uint32_t si, uint32_t flags, uint32_t stage, bool from_tracks,
+                            int mt_max_dim)
+{
+    StreamMode m{};
+    const int L = (int)s.vector_length;
+    const int generic = (flags & JB_BATCH_GENERIC_MLPG) ? 1 : 0;
+    m.W = from_tracks ? 1 : (int)s.num_windows;
+    m.is_msd = from_tracks ? (si == 1) : (int)s.is_msd;
+    m.use_gv = from_tracks ? 0 : (int)s.use_gv;
+    int maxw = from_tracks ? 1 : 0;
+    for (int w = 0; !from_tracks && w < m.W; w++)
+        maxw = std::max(maxw, (int)s.win_width[w]);
+    m.BW = (maxw / 2) * 2 + 1;
+    // [dim][frame] workspace with the fused kernels: band width 3, up to three windows (the sliding-window
+    // build), 3..60 dims; everything else takes the generic reference-shaped kernels
+    m.mt = (m.BW == 3 && m.W <= 3 && !generic && L > 2 && L <= mt_max_dim) ? 1 : 0;
+    // MCP, non-MSD, [dim][frame]: its transpose is fused with mc2b (enqueue_paramgen)
+    // (Stage::NonZero reads the [frame][dim] track itself: k_stage_coef)
+    m.defer_out = (si == 0 && m.mt && !m.is_msd && stage == 0 && !from_tracks) ? 1 : 0;
+    m.is_static = mlpg_is_static(m.BW, m.W, m.use_gv, generic);
+    return m;
 }
 
 } // namespace jb

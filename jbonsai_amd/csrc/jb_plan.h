@@ -1,7 +1,11 @@
 #pragma once
 // jb_plan.h -- the vocoder's work geometry: chunk length, warm-up, checkpoints, kernel and waves per SIMD, the work
 // items and the lane kernel's launch order, decided from the batch's shape alone (plan_vocoder_work, jb_plan.cpp).
-// Plain C++17 without HIP: the planner runs and is tested on any host; the kernels read the constants below too.
+// Below it, the shape rules of Batch::create: frame blocks, the voiced runs of an LF0 track, the vocoder conditions and
+// each stream's MLPG mode.  Plain C++17 without HIP: the planners run and are tested on any host; the kernels read the
+// constants below too.
+#include "../../include/jbonsai_amd.h"
+
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
@@ -67,5 +71,70 @@ struct VocPlan {
 
 // Pure: no globals, no environment.
 VocPlan plan_vocoder_work(const VocPlanIn &in);
+
+// ---- the shape rules of Batch::create (each pure: plain values in, no globals, no environment) ----
+
+constexpr double kNoData = -1e10; // src/constants.rs:13
+
+// A frame's samples in blocks of bs <= 64 (one pulse-mask word and one wave pass of lane = sample per block).
+// The largest divisor of the frame period that is <= 64 where there is a useful one (every BASELINE shape: 240 ->
+// 4 x 60; the split excitation kernels and the lane-triple vocoder are built on equal blocks); otherwise -- a
+// prime frame period, 75 = 3 x 25 under a 31-tap filter -- blocks of ceil(fperiod / nblk) samples with a shorter
+// LAST block (block q = samples [q bs, min(fperiod, (q + 1) bs)): sample i is bit i % bs of word i / bs either way).
+struct FrameBlocks {
+    int bs, nblk;
+};
+FrameBlocks plan_frame_blocks(int fperiod, int nlpf);
+
+// Parameter tracks as the source: the runs of voiced / unvoiced frames of an LF0 track (a frame is voiced where
+// lf0 != NODATA, vocoder/mod.rs:73-77) as the pseudo-states of the LF0 stream's state walk: durations[k] frames of
+// msd[k] = 1 (voiced) or 0, alternating.
+void plan_voiced_runs(const double *lf0, size_t n, std::vector<uint32_t> &durations, std::vector<double> &msd);
+
+// Vocoder condition of one utterance (jb_utt_voc after the beta rule below): what VocDev::alpha / volume / beta /
+// beta_stage hold for a batch with one condition.  pf: which freqt operator of VocDev::pf_table (beta > 0).
+struct VocUtt {
+    double alpha, volume, beta, beta_stage;
+    uint32_t pf, pad;
+};
+
+// The vocoder conditions of a batch.  One for the whole batch -- no jb_utt_voc, or every entry the same -- stands in
+// `batch`, and the kernels run as they always have.  Otherwise `utt` holds each utterance's; batch.beta / beta_stage
+// are then the maxima over the utterances: they say only whether SOME utterance has a post-filter (what is allocated
+// and launched), and the lane kernel's launch permutation keeps the condition classes apart (plan_vocoder_work).
+struct VocCondPlan {
+    VocUtt batch{};
+    bool mixed = false;
+    std::vector<VocUtt> utt;        // [n], mixed only (VocDev::uvoc)
+    std::vector<uint32_t> cls;      // [n], mixed only: utterances with equal (alpha, volume), by first appearance
+    uint32_t n_classes = 1;
+    std::vector<double> pf_alphas;  // the alpha of each post-filter operator (VocDev::pf_table): the batch-wide
+                                    // condition's first where its beta > 0, then by first appearance among the
+                                    // utterances with beta > 0
+};
+// voice: the voice's own alpha / beta / volume; utt: [n] per-utterance triples, or nullptr.  The beta rule:
+// postfilter_mcp acts only for beta > 0, more than two coefficients and stage 0 (cepstrum.rs:24); with stage > 0 beta
+// goes to postfilter_lsp (lsp.rs:113-139).
+VocCondPlan plan_voc_conditions(const jb_utt_voc &voice, uint32_t nmcp, uint32_t stage, const jb_utt_voc *utt, size_t n);
+
+// "The one-window case": a width-1 window alone, no GV -- the track is the state means (k_mlpg_static), and no MLPG
+// workspace is allocated for the stream
+constexpr bool mlpg_is_static(int BW, int W, int use_gv, int generic_solver)
+{
+    return BW == 1 && W == 1 && !use_gv && !generic_solver;
+}
+
+// How stream si of a batch is generated: what StreamDev's fields of the same names hold.
+struct StreamMode {
+    int W, BW;      // windows read; band width = Windows::max_width() * 2 + 1 (window.rs:19-21, mlpg.rs:27)
+    int is_msd, use_gv;
+    int mt;         // [dim][frame] workspace with the fused kernels
+    int defer_out;  // the MCP stream's transpose is fused with mc2b (enqueue_paramgen)
+    bool is_static; // mlpg_is_static
+};
+// flags: JB_BATCH_* of the batch; from_tracks: parameter tracks are the source (no MLPG: the window description is not
+// read and may be absent); mt_max_dim: mlpg_mt_max_dim()
+StreamMode plan_stream_mode(const jb_stream_desc &s, uint32_t si, uint32_t flags, uint32_t stage, bool from_tracks,
+                            int mt_max_dim);
 
 } // namespace jb
