@@ -1,11 +1,11 @@
 """The reference's `examples/is-bonsai` on the GPU path: full-context labels -> PCM -> 16-bit WAV.
 
-    python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS]]
+    python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
 With --loudness the audio is normalized on the GPU to that integrated loudness (BS.1770-4), its sample peak kept at or
-under --ceiling (dBFS, default 0).
+under --ceiling (dBFS, default 0); with --true-peak the ceiling bounds the true peak (dBTP, BS.1770-4 Annex 2) instead.
 """
 import argparse
 import os
@@ -21,6 +21,7 @@ ap.add_argument("voice", nargs="?", default=os.path.join(
 ap.add_argument("out", nargs="?", default="is-bonsai.wav")
 ap.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="target integrated loudness")
 ap.add_argument("--ceiling", type=float, default=0.0, metavar="DBFS", help="sample-peak ceiling (with --loudness)")
+ap.add_argument("--true-peak", action="store_true", help="the ceiling bounds the true peak (dBTP), not the sample peak")
 args = ap.parse_args()
 voice, out = args.voice, args.out
 
@@ -28,11 +29,13 @@ engine = J.Engine.load([voice])
 if args.loudness is not None:
     engine.condition.set_loudness_target(args.loudness)
     engine.condition.set_peak_ceiling(args.ceiling)
+    engine.condition.set_peak_mode(J.PEAK_TRUE if args.true_peak else J.PEAK_SAMPLE)
 speech = engine.synthesize(SAMPLE_SENTENCE_2)
 print(f"The synthesized voice has {len(speech)} samples in total.")
 if args.loudness is not None:
     lufs, peak = J.loudness(speech, engine.condition.get_sampling_frequency())
-    print(f"normalized: {lufs:.2f} LUFS, sample peak {peak:.2f} dBFS")
+    tp = J.true_peak(speech, engine.condition.get_sampling_frequency())
+    print(f"normalized: {lufs:.2f} LUFS, sample peak {peak:.2f} dBFS, true peak {tp:.2f} dBTP")
 J.write_wav(out, speech, engine.condition.get_sampling_frequency())
 print(f"wrote {out}")
 

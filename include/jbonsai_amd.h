@@ -332,6 +332,22 @@ int jb_batch_set_loudness_target(jb_batch *b, const double *target_lufs, size_t 
  * block survives the gates), P (dBFS, -INFINITY for silence) and gain_dB.  Waits for the run like the read entries;
  * a batch without a target or not yet run: JB_ERR_INVALID. */
 int jb_batch_loudness(jb_batch *b, size_t utt, double *lufs, double *peak_dbfs, double *gain_db);
+/* New.  What the ceiling of jb_batch_set_loudness_target bounds ("loudness" below, step 5): the sample peak
+ * (JB_PEAK_SAMPLE, the default) or the true peak (JB_PEAK_TRUE, dBTP).  mode[0] for every utterance (n == 1) or
+ * mode[u] for utterance u (n == jb_batch_size(b)); any other value, or another n: JB_ERR_INVALID.  Only before the
+ * batch's first run, and not on a JB_BATCH_MLPG_ONLY batch: JB_ERR_INVALID.  In either order with the target; without
+ * a target it has no effect.  A batch with every utterance in sample mode launches and allocates nothing more. */
+#define JB_PEAK_SAMPLE 0
+#define JB_PEAK_TRUE 1
+int jb_batch_set_peak_mode(jb_batch *b, const uint32_t *mode, size_t n);
+/* jb_batch_loudness with the true peak: TP (NaN for an utterance in sample mode), the utterance's mode and the
+ * oversampling factor F its TP was taken with (1 in sample mode).  gain_db is the gain applied, by the rule of the
+ * utterance's mode.  Readiness rules of jb_batch_loudness. */
+typedef struct jb_loudness_report {
+    double lufs, sample_peak_dbfs, true_peak_dbtp, gain_db;
+    uint32_t peak_mode, oversampling;
+} jb_loudness_report;
+int jb_batch_loudness_report(jb_batch *b, size_t utt, jb_loudness_report *out);
 /* New.  FLAC output (see "FLAC" below): the run encodes each utterance's 16-bit PCM as the read entries hand it out
  * (after the output rate and the loudness target) into one FLAC stream per utterance, on the device.  opts: NULL or
  * zeros = the defaults.  Only before the batch's first run, on a JB_BATCH_PCM_I16 batch that is not
@@ -429,8 +445,20 @@ int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
  * 4. P = 20 log10(max |x| / 32768) (sample peak; -INFINITY for silence).  gain_dB = min(T - L, C - P) over the terms
  *    that are finite (0 if neither is), T the target, C the ceiling; output x * 10^(gain_dB / 20), one f64 product
  *    per sample, then the 16-bit sink's clamp and truncation on a 16-bit batch.  A quiet or silent utterance is never
- *    amplified past C.  The ceiling bounds the sample peak only: true-peak (oversampled) limiting is not done.
- * L, P and gain_dB are functions of the utterance's samples alone (not of the batch, its order, the entry or the
+ *    amplified past C.
+ * 5. True peak (BS.1770-4 Annex 2), on the same f64 x, x = 0 outside [0, N).  Oversampling factor
+ *    F = min(64, ceil(192000 / fs)): 48 k -> 4, 44.1 k -> 5, 96 k -> 2, 192 k and above -> 1, 32 k -> 6, 24 k -> 8,
+ *    22.05 k -> 9, 16 k -> 12, 11.025 k -> 18, 8 k -> 24.  Interpolator h(t) = sinc(t) I0(8 sqrt(1 - (t/6)^2)) / I0(8)
+ *    for |t| < 6, else 0, sinc(t) = sin(pi t) / (pi t); 12 taps per phase, h[p][j] = h(p/F + 5 - j), j = 0..11 (the size
+ *    of the Annex 2 example filter); phases p = 1..F-1 are tabled, phase 0 is the samples themselves.
+ *    y_p[n] = sum_{j=0}^{11} h[p][j] x[n - 5 + j] for n = 0..N-1, summed as h[p][0] x[n-5] and then FMAs in ascending
+ *    j (the resampler's rule): each y is a function of x and h alone.  TPlin = max(max |x[n]|, max_{p,n} |y_p[n]|),
+ *    TP = 20 log10(TPlin / 32768) dBTP, -INFINITY for silence; TP >= P by construction, and with F = 1 TP = P and
+ *    nothing extra runs.  In true-peak mode (JB_PEAK_TRUE) the gain rule is step 4 with TP in place of P:
+ *    gain_dB = min(T - L, C - TP) over the finite terms; the reported P stays the sample peak.  Sample mode is the
+ *    default.  TP is measured on the f64 before any 16-bit conversion: what the 16-bit sink's clamp and truncation
+ *    do to the waveform is not measured again.  One gain per utterance: no look-ahead limiting.
+ * L, P, TP and gain_dB are functions of the utterance's samples alone (not of the batch, its order, the entry or the
  * devices); the device sums in fixed orders, so JB_BATCH_INVARIANT output stays invariant with a target. */
 /* Host only (no GPU): the coefficients of step 1 at hz, b[6] = b of the shelf then of the high-pass, a[6] likewise
  * (a[0] = a[3] = 1), and *hop = H; each pointer may be NULL.  hz == 0: JB_ERR_INVALID. */
@@ -439,6 +467,13 @@ int jb_loudness_filter(uint32_t hz, double *b, double *a, uint32_t *hop);
  * (n_in[u] samples at hz), on `device` (-1 = current).  A hop outside 1..61439 samples: JB_ERR_UNSUPPORTED. */
 int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
                           double *lufs, double *peak_dbfs);
+/* Host only (no GPU): the interpolator of step 5 at hz: *F, *ntaps = 12 (each may be NULL) and, when taps is not NULL,
+ * the [F - 1][12] taps h[p][j] of phases p = 1..F-1 (JB_ERR_BUFFER if cap < (F - 1) * 12).  hz == 0: JB_ERR_INVALID. */
+int jb_true_peak_filter(uint32_t hz, uint32_t *F, uint32_t *ntaps, double *taps, size_t cap);
+/* jb_loudness_pcm_batch's twin for step 5: true_peak_dbtp[u] = TP of in[u] (n_in[u] samples at hz), on `device`
+ * (-1 = current).  The tiling is the measurement's: a hop outside 1..61439 samples is JB_ERR_UNSUPPORTED. */
+int jb_true_peak_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
+                           double *true_peak_dbtp);
 
 /* ---- FLAC (new: the reference writes WAV only; RFC 9639) ---------------------------------------------------------
  * Each utterance's 16-bit output (exactly what jb_batch_read_pcm_i16 hands out: after the converter, the loudness
@@ -585,6 +620,12 @@ double jb_engine_get_loudness_target(const jb_engine *e);
 /* New.  Peak ceiling (dBFS) that goes with the loudness target: default 0; +INFINITY = none. */
 int jb_engine_set_peak_ceiling(jb_engine *e, double dbfs);
 double jb_engine_get_peak_ceiling(const jb_engine *e);
+/* New.  What that ceiling bounds: JB_PEAK_SAMPLE (the default) or JB_PEAK_TRUE (dBTP, jb_batch_set_peak_mode); any
+ * other value: JB_ERR_INVALID.  jb_engine_new copies it with the Condition.  Honoured where the target is: by
+ * jb_synthesize, _batch[_i16], _each[_i16] (each utterance's engine's own mode, like its target and ceiling), the
+ * _flac and _multi entries and the generator. */
+int jb_engine_set_peak_mode(jb_engine *e, uint32_t mode);
+uint32_t jb_engine_get_peak_mode(const jb_engine *e);
 int jb_engine_set_speed(jb_engine *e, double v);
 double jb_engine_get_speed(const jb_engine *e);
 int jb_engine_set_alpha(jb_engine *e, double v);
@@ -769,6 +810,9 @@ JB_LAYOUT_ASSERT(sizeof(jb_utt_voc) == 24 && offsetof(jb_utt_voc, beta) == 8 && 
                  "jb_utt_voc");
 JB_LAYOUT_ASSERT(sizeof(jb_flac_opts) == 16 && offsetof(jb_flac_opts, max_lpc_order) == 4 &&
                      offsetof(jb_flac_opts, reserved) == 8, "jb_flac_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_loudness_report) == 40 && offsetof(jb_loudness_report, gain_db) == 24 &&
+                     offsetof(jb_loudness_report, peak_mode) == 32 && offsetof(jb_loudness_report, oversampling) == 36,
+                 "jb_loudness_report");
 #undef JB_LAYOUT_ASSERT
 #endif
 #endif /* JBONSAI_AMD_H */

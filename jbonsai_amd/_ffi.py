@@ -32,6 +32,8 @@ BATCH_MLPG_ONLY = 128
 BATCH_TEST_GANG_TIMEOUT = 256
 BATCH_NO_EXC_TABLE = 512
 BATCH_INVARIANT = 1024
+PEAK_SAMPLE = 0
+PEAK_TRUE = 1
 
 
 class JbError(RuntimeError):
@@ -145,6 +147,12 @@ def flac_opts(block_size: int = 0, max_lpc_order=None):
     return o
 
 
+class LoudnessReport(C.Structure):
+    """jb_loudness_report: what a run measured and applied for one utterance."""
+    _fields_ = [("lufs", C.c_double), ("sample_peak_dbfs", C.c_double), ("true_peak_dbtp", C.c_double),
+                ("gain_db", C.c_double), ("peak_mode", C.c_uint32), ("oversampling", C.c_uint32)]
+
+
 class BatchOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32), ("chunk_frames", C.c_uint32),
                 ("warmup_frames", C.c_uint32), ("verify_tol", C.c_double), ("reserved0", C.c_uint32), ("reserved", C.c_uint32)]
@@ -186,6 +194,8 @@ SYMBOLS = [
     "jb_batch_set_flac", "jb_batch_flac_size", "jb_batch_read_flac", "jb_batch_read_flac_all",
     "jb_flac_encode_pcm_batch", "jb_flac_free", "jb_synthesize_flac", "jb_synthesize_batch_flac",
     "jb_synthesize_batch_each_flac",
+    "jb_batch_set_peak_mode", "jb_batch_loudness_report", "jb_true_peak_filter", "jb_true_peak_pcm_batch",
+    "jb_engine_set_peak_mode", "jb_engine_get_peak_mode",
 ]
 
 
@@ -311,6 +321,13 @@ def lib():
         getattr(L, "jb_engine_set_" + n).argtypes = [vp, C.c_double]
         getattr(L, "jb_engine_get_" + n).argtypes = [vp]
         getattr(L, "jb_engine_get_" + n).restype = C.c_double
+    L.jb_batch_set_peak_mode.argtypes = [vp, C.POINTER(C.c_uint32), sz]
+    L.jb_batch_loudness_report.argtypes = [vp, sz, C.POINTER(LoudnessReport)]
+    L.jb_true_peak_filter.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), dp, sz]
+    L.jb_true_peak_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, C.c_uint32, C.c_int32, dp]
+    L.jb_engine_set_peak_mode.argtypes = [vp, C.c_uint32]
+    L.jb_engine_get_peak_mode.argtypes = [vp]
+    L.jb_engine_get_peak_mode.restype = C.c_uint32
     u8p, fop = C.POINTER(C.c_uint8), C.POINTER(FlacOpts)
     L.jb_batch_set_flac.argtypes = [vp, fop]
     L.jb_batch_flac_size.argtypes = [vp, sz, C.POINTER(sz)]
@@ -382,6 +399,36 @@ def loudness(pcms, hz: int, device: int = -1):
     lufs, peak = np.zeros(max(n, 1)), np.zeros(max(n, 1))
     check(lib().jb_loudness_pcm_batch(ins, nin, n, hz, device, lufs.ctypes.data_as(dp), peak.ctypes.data_as(dp)))
     res = [(float(lufs[u]), float(peak[u])) for u in range(n)]
+    return res[0] if single else res
+
+
+def true_peak_filter(hz: int):
+    """The library's true-peak interpolator at hz (include/jbonsai_amd.h jb_true_peak_filter; host only): (F, taps)
+    with taps a float64 array [F - 1][12], the phases 1..F-1."""
+    import numpy as np
+
+    L = lib()
+    f, nt = C.c_uint32(), C.c_uint32()
+    check(L.jb_true_peak_filter(hz, C.byref(f), C.byref(nt), None, 0))
+    taps = np.zeros((f.value - 1, nt.value), dtype=np.float64)
+    check(L.jb_true_peak_filter(hz, C.byref(f), C.byref(nt), taps.ctypes.data_as(C.POINTER(C.c_double)), taps.size))
+    return f.value, taps
+
+
+def true_peak(pcms, hz: int, device: int = -1):
+    """jb_true_peak_pcm_batch: the true peak (dBTP) of each float64 array of `pcms` (or of one array) at hz, on the
+    GPU."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
+    n = len(arrs)
+    dp = C.POINTER(C.c_double)
+    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    tp = np.zeros(max(n, 1))
+    check(lib().jb_true_peak_pcm_batch(ins, nin, n, hz, device, tp.ctypes.data_as(dp)))
+    res = [float(tp[u]) for u in range(n)]
     return res[0] if single else res
 
 

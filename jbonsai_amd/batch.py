@@ -377,6 +377,20 @@ class Batch:
         F.check(self._L.jb_batch_loudness(self._h, i, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def set_peak_mode(self, mode):
+        """jb_batch_set_peak_mode: what the ceiling bounds, F.PEAK_SAMPLE (0, the default) or F.PEAK_TRUE (1, dBTP);
+        one mode (int) for the whole batch or one per utterance.  Before the first run only."""
+        ms = [int(mode)] if np.isscalar(mode) else [int(m) for m in mode]
+        arr = (C.c_uint32 * max(1, len(ms)))(*ms)
+        F.check(self._L.jb_batch_set_peak_mode(self._h, arr, len(ms)))
+
+    def loudness_report(self, i):
+        """jb_batch_loudness_report for utterance i: a dict of lufs, sample_peak_dbfs, true_peak_dbtp (NaN in sample
+        mode), gain_db, peak_mode and oversampling."""
+        r = F.LoudnessReport()
+        F.check(self._L.jb_batch_loudness_report(self._h, i, C.byref(r)))
+        return {k: getattr(r, k) for k, _ in F.LoudnessReport._fields_}
+
     def set_flac(self, block_size: int = 0, max_lpc_order=None):
         """jb_batch_set_flac: the run also encodes each utterance's 16-bit output as a FLAC stream (pcm_i16=True,
         not mlpg_only; before the first run only).  Defaults: block size 4096, LPC order up to 8."""

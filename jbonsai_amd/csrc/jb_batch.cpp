@@ -2537,6 +2537,31 @@ int jb_batch_loudness(jb_batch *hb, size_t utt, double *lufs, double *peak_dbfs,
     return JB_OK;
 }
 
+int jb_batch_set_peak_mode(jb_batch *hb, const uint32_t *mode, size_t n)
+{
+    return hb ? ((Batch *)hb)->out.set_peak_mode(mode, n) : JB_ERR_INVALID;
+}
+
+int jb_batch_loudness_report(jb_batch *hb, size_t utt, jb_loudness_report *out)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !out || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    jb::LoudnessResult r{};
+    int rc = b->out.read_loudness(utt, &r);
+    if (rc)
+        return rc;
+    out->lufs = r.lufs;
+    out->sample_peak_dbfs = r.peak_dbfs;
+    out->true_peak_dbtp = r.true_peak_dbtp;
+    out->gain_db = r.gain_db;
+    out->peak_mode = b->out.peak_mode(utt);
+    out->oversampling = 1;
+    if (out->peak_mode == JB_PEAK_TRUE && (rc = jb::true_peak_table(b->out.utt(utt).hz, &out->oversampling, nullptr)))
+        return rc;
+    return JB_OK;
+}
+
 int jb_batch_set_flac(jb_batch *hb, const jb_flac_opts *opts)
 {
     if (!hb)

@@ -48,6 +48,7 @@ struct Condition {
     size_t output_rate = 0;       // jb_engine_set_output_sampling_frequency: 0 = the voice's rate
     double loudness_target = NAN; // jb_engine_set_loudness_target: NaN = off
     double peak_ceiling = 0.0;    // jb_engine_set_peak_ceiling (dBFS), with a target only
+    uint32_t peak_mode = JB_PEAK_SAMPLE; // jb_engine_set_peak_mode: what the ceiling bounds, with a target only
     double speed = 1.0;
     size_t stage = 0;
     bool use_log_gain = false;
@@ -783,6 +784,14 @@ int jb_engine_set_peak_ceiling(jb_engine *e, double dbfs)
     return JB_OK;
 }
 double jb_engine_get_peak_ceiling(const jb_engine *e) { return e ? CENG(e)->cond.peak_ceiling : NAN; }
+int jb_engine_set_peak_mode(jb_engine *e, uint32_t mode)
+{
+    if (!e || (mode != JB_PEAK_SAMPLE && mode != JB_PEAK_TRUE))
+        return JB_ERR_INVALID;
+    ENG(e)->cond.peak_mode = mode;
+    return JB_OK;
+}
+uint32_t jb_engine_get_peak_mode(const jb_engine *e) { return e ? CENG(e)->cond.peak_mode : JB_PEAK_SAMPLE; }
 int jb_engine_set_speed(jb_engine *e, double v)
 {
     ENG(e)->cond.speed = std::max(v, 1.0E-06);
@@ -1138,14 +1147,19 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         // loudness: each utterance's engine's own target and ceiling; an engine without a target leaves its
         // utterance as it is (measured, gain 0 dB: bit for bit the same) when another engine of the batch has one
         std::vector<double> targets(hi - lo), ceilings(hi - lo);
-        bool any_target = false;
+        std::vector<uint32_t> modes(hi - lo);
+        bool any_target = false, any_true = false;
         for (size_t u = lo; u < hi; u++) {
             const bool on = !std::isnan(eng(u)->cond.loudness_target);
             targets[u - lo] = on ? eng(u)->cond.loudness_target : NAN;
             ceilings[u - lo] = on ? eng(u)->cond.peak_ceiling : INFINITY;
+            modes[u - lo] = on ? eng(u)->cond.peak_mode : JB_PEAK_SAMPLE;
             any_target = any_target || on;
+            any_true = any_true || modes[u - lo] == JB_PEAK_TRUE;
         }
         if (any_target && (rc = b->out.set_loudness(targets.data(), ceilings.data(), targets.size())))
+            return rc;
+        if (any_true && (rc = b->out.set_peak_mode(modes.data(), modes.size())))
             return rc;
         if (flac && (rc = b->out.set_flac(flac_opts)))
             return rc;
@@ -1446,7 +1460,8 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     }
     if (!std::isnan(CENG(e)->cond.loudness_target)) {
         const double t = CENG(e)->cond.loudness_target, c = CENG(e)->cond.peak_ceiling;
-        if ((rc = b->out.set_loudness(&t, &c, 1)))
+        const uint32_t mode = CENG(e)->cond.peak_mode;
+        if ((rc = b->out.set_loudness(&t, &c, 1)) || (rc = b->out.set_peak_mode(&mode, 1)))
             return rc;
     }
     // Engine::generator runs all three MLPGs before returning (src/engine.rs:333-357); here they are

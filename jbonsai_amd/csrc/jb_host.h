@@ -79,12 +79,15 @@ hipError_t launch_resample(const ResampleTable *tables_dev, const ResampleTile *
 // Loudness normalization (jb_loudness.hip): BS.1770-4 K-weighting, measured per utterance in tiles of at most
 // 256 segments of S samples; tiles never cross a hop (H samples), a hop has tph of them
 constexpr uint32_t kLnLanes = 256;
+constexpr uint32_t kTpMaxF = 64, kTpTaps = 12; // true peak: oversampling factor at most, taps per phase
 struct LoudnessRate {
     double b[6], a[6];     // stage 1 (shelf) then stage 2 (high-pass): b0 b1 b2 / 1 a1 a2
     double P[8][16];       // A^(S 2^k), k = 0..7: the state transition over 2^k segments (4x4, row-major)
     double Pt[16], Pr[16]; // A^G (a hop's tiles but its last), A^(H - (tph - 1) G) (a hop's last tile)
     double Ph[16];         // A^H (a hop)
-    uint32_t hz, H, S, G, tph, pad_;
+    uint32_t hz, H, S, G, tph;
+    uint32_t F;                                  // true-peak oversampling factor, 1..64 (true_peak_table)
+    double tp[(kTpMaxF - 1) * kTpTaps];          // its phases 1..F-1, [F - 1][12]
 };
 // One utterance of a loudness launch.  Launch lists are in utterance order; lt0 / at0 are prefix sums over the
 // list (measure tiles / apply tiles), tile0 the utterance's place in the per-tile scratch (fixed per batch)
@@ -92,22 +95,28 @@ struct LoudnessUtt {
     const double *x; // f64 PCM measured
     void *y;         // output (f64 or i16, by the launch); null: measure only
     uint64_t n, tile0, lt0, at0;
-    uint32_t ntiles, rate, slot, pad_;
+    uint32_t ntiles, rate, slot;
+    uint32_t mode; // JB_PEAK_SAMPLE / JB_PEAK_TRUE: what the ceiling bounds
     double target, ceiling;
 };
 struct LoudnessResult {
     double lufs, peak_dbfs, gain_db, g;
+    double true_peak_dbtp; // NaN in sample mode
 };
 constexpr uint32_t kLnApplyTile = 8192; // samples per workgroup of the apply pass
 // K-weighting coefficients and the hop of `hz`; JB_ERR_INVALID for hz == 0
 int loudness_filter(uint32_t hz, double b[6], double a[6], uint32_t *hop);
+// The true-peak interpolator of `hz` (pure): *F = min(64, ceil(192000 / hz)) and, when taps is not null, the
+// [F - 1][12] taps of phases 1..F-1 (room for (kTpMaxF - 1) * kTpTaps always suffices); JB_ERR_INVALID for hz == 0
+int true_peak_table(uint32_t hz, uint32_t *F, double *taps);
 // The device table of one rate (host-built); JB_ERR_UNSUPPORTED where the tiling does not reach (H == 0, H > 61439)
 int loudness_rate(uint32_t hz, LoudnessRate *out);
 uint32_t loudness_tiles(const LoudnessRate &r, uint64_t n); // measure tiles of an utterance of n samples
-// measure: utts_dev[0..n) of total tiles; st: 4 doubles per tile, pk / z: one; res[slot] of each utterance
+// measure: utts_dev[0..n) of total tiles; st: 4 doubles per tile, pk / tp / z: one; res[slot] of each utterance.
+// true_peak: some utterance of the list is in JB_PEAK_TRUE mode (without one the oversampled pass is not launched)
 hipError_t launch_loudness_measure(const LoudnessRate *rates_dev, const LoudnessUtt *utts_dev, uint32_t n,
-                                   uint64_t tiles, double *st, double *pk, double *z, LoudnessResult *res,
-                                   hipStream_t stream);
+                                   uint64_t tiles, double *st, double *pk, double *tp, double *z, LoudnessResult *res,
+                                   bool true_peak, hipStream_t stream);
 // y = x * res[slot].g for every utterance of the list (apply tiles in all)
 hipError_t launch_loudness_apply(const LoudnessUtt *utts_dev, uint32_t n, uint64_t atiles, const LoudnessResult *res,
                                  bool i16, hipStream_t stream);
@@ -222,6 +231,7 @@ struct OutputChain {
     // Each setter refuses after the first run; the last request before it wins
     int set_output_rate(const uint32_t *hz, size_t n); // n == 1 or B entries, 0 = native
     int set_loudness(const double *target, const double *ceiling, size_t n); // n == 1 or B entries each
+    int set_peak_mode(const uint32_t *mode, size_t n);                       // n == 1 or B entries; needs no target
     int set_flac(const jb_flac_opts *opts);
     void init();   // Batch::create: the slabs the batch was made with, the plan of no request
     int prepare(); // at the first run: every slab, table and list of the plan; points the vocoder at its slab
@@ -241,6 +251,7 @@ struct OutputChain {
     const double *native64() const { return (const double *)slab[(size_t)plan.native64]; } // null: there is none
     // after sync (each reports a stage that was not set, or a batch that has not run, as JB_ERR_INVALID)
     int read_loudness(size_t u, LoudnessResult *r);
+    uint32_t peak_mode(size_t u) const { return u < ln_mode.size() ? ln_mode[u] : 0u; }
     int read_flac_index(size_t u, FlacOut *o);
     int read_flac(const FlacOut &o, uint8_t *dst);
     // every stream's size and place, and the compact slab's used bytes in one copy
@@ -252,6 +263,7 @@ private:
     std::vector<uint32_t> want_hz;             // [B] 0 = native; empty: no rate requested
     bool ln_on = false, flac_on = false;       // a loudness target / FLAC is requested
     std::vector<double> ln_target, ln_ceiling; // [B]
+    std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
     FlacParams flac_p{};
     bool frozen = false, ready = false; // the first run has begun: no more requests / its prepare() succeeded
     void *slab[(size_t)OutSlab::Count] = {};
@@ -266,9 +278,10 @@ private:
         std::vector<LoudnessUtt> utts;
         LoudnessUtt *utts_dev = nullptr, *redo_dev = nullptr;
         LoudnessRate *rates_dev = nullptr;
-        double *st = nullptr, *pk = nullptr, *z = nullptr;
+        double *st = nullptr, *pk = nullptr, *tp = nullptr, *z = nullptr;
         LoudnessResult *res = nullptr;
         uint64_t tiles = 0, atiles = 0;
+        bool true_peak = false; // some utterance is in JB_PEAK_TRUE mode
     } ln;
     struct { // FLAC
         std::vector<FlacWork> work;

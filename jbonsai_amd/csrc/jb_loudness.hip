@@ -2,11 +2,12 @@
 // `volume` gain).  The definition is in include/jbonsai_amd.h ("loudness"); in short: K-weighting (two biquads,
 // BS.1770-4) of x / 32768 from zero state per utterance, hop sums z_j of y^2 over [jH, (j+1)H), H = (fs + 5) / 10,
 // four-hop gating blocks, the -70 LUFS absolute and the -10 LU relative gate, the sample peak, and
-// gain_dB = min(T - L, C - P) over the finite terms.
+// gain_dB = min(T - L, C - P) over the finite terms; in true-peak mode (JB_PEAK_TRUE) the true peak TP, the largest
+// magnitude of x and of its F - 1 interpolated phases (12 taps each), stands in for P in that rule.
 //
 // The filter is linear and time-invariant, so a recursion cut into pieces is exact up to rounding: a piece filtered
 // from zero state ends in e, and the state s at its start carries over as s -> A^len s + e (A: the 4x4 transition of
-// one sample with x = 0, len: the piece's length).  Four kernels measure, one applies:
+// one sample with x = 0, len: the piece's length).  Five kernels measure, one applies:
 //   k_ln_tiles<false>  one workgroup per tile (<= 256 segments of S <= 16 samples, inside one hop): the tile is staged
 //                      through LDS with coalesced loads (the sample peak on the way), every lane filters its segment
 //                      from zero, a Hillis-Steele scan of the affine maps across the 256 lanes (matrices A^(S 2^k),
@@ -18,10 +19,16 @@
 //   k_ln_tiles<true>   the tile again, the same zero-state pass and scan, now from the tile's true start state;
 //                      every lane filters its segment from its start state and sums y^2; a fixed tree gives the
 //                      tile's share of its hop's z (tiles of the tail hop, in no block, are skipped).
-//   k_ln_gate          one workgroup per utterance: z_j, the blocks, both gates, L, P and the gain, every sum in a
-//                      fixed order over a fixed thread count.
+//   k_ln_true_peak     (launched only with an utterance in true-peak mode; others' tiles return at once) the tile
+//                      and a halo of 5 samples before and 6 after in LDS, zero outside the utterance; a lane takes
+//                      samples l, l + 256, ..., holds the 12-sample window in registers and runs the phases with
+//                      wave-uniform taps (scalar operands), each y one fixed FMA chain; a fixed fmax tree gives the
+//                      tile's largest |y|.
+//   k_ln_gate          one workgroup per utterance: z_j, the blocks, both gates, L, P, TP and the gain, every sum in
+//                      a fixed order over a fixed thread count.
 //   k_ln_apply         y = x * g, f64 or the 16-bit sink's rule (clamp, then truncate).
-// Each sample is read from HBM twice to measure (both tile passes) and once to apply.  Every result is a function of
+// Each sample is read from HBM twice to measure (both tile passes; a third time in true-peak mode) and once to apply.
+// Every result is a function of
 // the utterance's samples and rate alone: the tiling depends on nothing else (the fast invariant mode stays
 // invariant).
 #include "jb_host.h"
@@ -72,7 +79,41 @@ void mat_pow(const double *a, uint64_t n, double *out)
     }
     std::copy(r, r + 16, out);
 }
+
+double tp_bessel_i0(double x)
+{
+    // power series sum_k ((x/2)^k / k!)^2, as the resampler's table: 60 terms reach the rounding floor for x <= 10
+    double sum = 1.0, term = 1.0;
+    const double h = 0.25 * x * x;
+    for (int k = 1; k < 60; k++) {
+        term *= h / ((double)k * (double)k);
+        sum += term;
+    }
+    return sum;
+}
 } // namespace
+
+int true_peak_table(uint32_t hz, uint32_t *F, double *taps)
+{
+    if (hz == 0) {
+        set_error("true peak: a rate of 0 Hz");
+        return JB_ERR_INVALID;
+    }
+    const uint32_t f = std::min<uint32_t>(kTpMaxF, (192000u + hz - 1) / hz);
+    if (F)
+        *F = f;
+    if (!taps)
+        return JB_OK;
+    const double i0b = tp_bessel_i0(8.0), pi = 3.14159265358979323846;
+    for (uint32_t p = 1; p < f; p++)
+        for (uint32_t j = 0; j < kTpTaps; j++) {
+            const double t = (double)p / (double)f + 5.0 - (double)j; // never 0, always inside (-6, 6)
+            const double u = t / 6.0;
+            taps[(size_t)(p - 1) * kTpTaps + j] =
+                std::sin(pi * t) / (pi * t) * tp_bessel_i0(8.0 * std::sqrt(1.0 - u * u)) / i0b;
+        }
+    return JB_OK;
+}
 
 int loudness_filter(uint32_t hz, double b[6], double a[6], uint32_t *hop)
 {
@@ -123,6 +164,8 @@ int loudness_rate(uint32_t hz, LoudnessRate *out)
                   " samples (1.." + std::to_string(kLnMaxHop) + " are measured)");
         return JB_ERR_UNSUPPORTED;
     }
+    if ((rc = true_peak_table(hz, &r.F, r.tp)))
+        return rc;
     r.hz = hz;
     r.H = H;
     r.tph = (H + 4095) / 4096;
@@ -419,11 +462,72 @@ __global__ __launch_bounds__(64) void k_ln_scan(const LoudnessRate *__restrict__
         }
 }
 
-// One workgroup per utterance: z_j, blocks, gates, L, P, gain -- fixed orders over a fixed thread count
+constexpr uint32_t kTpBefore = 5, kTpAfter = 6; // the halo of a 12-tap window around sample n: x[n - 5 .. n + 6]
+
+// True peak of the measure tiles (the tail hop's included): tp[tile] = max over the tile's samples n and the phases
+// p = 1..F-1 of |y_p[n]|, y_p[n] = h[p][0] x[n - 5] and then FMAs in ascending j.  Tiles of an utterance in sample
+// mode, or at a rate with F = 1, return at once: k_ln_gate does not read their slot
+__global__ __launch_bounds__(kLnLanes) void k_ln_true_peak(const LoudnessRate *__restrict__ rates,
+                                                           const LoudnessUtt *__restrict__ utts, uint32_t n_utts,
+                                                           double *__restrict__ tp)
+{
+    __shared__ double xs[kLnLanes * kLnMaxS + kTpBefore + kTpAfter]; // slot i: sample start - 5 + i
+    __shared__ double red[kLnLanes];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t u = ln_find<false>(utts, n_utts, blockIdx.x);
+    const LoudnessUtt U = utts[u];
+    if (U.mode != JB_PEAK_TRUE)
+        return;
+    const LoudnessRate *R = rates + U.rate;
+    const uint32_t H = R->H, G = R->G, tph = R->tph, F = R->F;
+    if (F < 2)
+        return;
+    const uint64_t t = blockIdx.x - U.lt0;
+    const uint64_t j = t / tph;
+    const uint32_t k = (uint32_t)(t % tph);
+    const uint64_t start = j * H + (uint64_t)k * G;
+    if (t >= U.ntiles || start >= U.n)
+        return;
+    const uint32_t len = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(G, H - k * G), U.n - start);
+    // stage x[start - 5, start + len + 6), zero outside [0, n): len + 11 <= 4096 + 11 slots, coalesced
+    for (uint32_t i = tid; i < len + kTpBefore + kTpAfter; i += kLnLanes) {
+        const uint64_t g = start + i; // sample g - 5
+        xs[i] = (g >= kTpBefore && g - kTpBefore < U.n) ? U.x[g - kTpBefore] : 0.0;
+    }
+    __syncthreads();
+    cdouble *h = (cdouble *)R->tp;
+    double m = 0.0;
+    for (uint32_t s = tid; s < len; s += kLnLanes) {
+        double w[kTpTaps];
+#pragma unroll
+        for (uint32_t q = 0; q < kTpTaps; q++)
+            w[q] = xs[s + q];
+#pragma unroll 3
+        for (uint32_t p = 0; p + 1 < F; p++) {
+            cdouble *hp = h + p * kTpTaps;
+            double y = hp[0] * w[0];
+#pragma unroll
+            for (uint32_t q = 1; q < kTpTaps; q++)
+                y = __builtin_fma(hp[q], w[q], y);
+            m = fmax(m, fabs(y));
+        }
+    }
+    red[tid] = m;
+    __syncthreads();
+    for (uint32_t w = kLnLanes / 2; w > 0; w >>= 1) {
+        if (tid < w)
+            red[tid] = fmax(red[tid], red[tid + w]);
+        __syncthreads();
+    }
+    if (tid == 0)
+        tp[U.tile0 + t] = red[0];
+}
+
+// One workgroup per utterance: z_j, blocks, gates, L, P, TP, gain -- fixed orders over a fixed thread count
 __global__ __launch_bounds__(kLnLanes) void k_ln_gate(const LoudnessRate *__restrict__ rates,
                                                       const LoudnessUtt *__restrict__ utts,
-                                                      const double *__restrict__ pk, const double *__restrict__ z,
-                                                      LoudnessResult *__restrict__ res)
+                                                      const double *__restrict__ pk, const double *__restrict__ tp,
+                                                      const double *__restrict__ z, LoudnessResult *__restrict__ res)
 {
     __shared__ double rs[kLnLanes];
     __shared__ uint32_t rn[kLnLanes];
@@ -443,6 +547,23 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_gate(const LoudnessRate *__rest
     }
     const double peak = rs[0];
     __syncthreads();
+    // true-peak mode: the tiles' oversampled maxima folded the same way, then with the sample peak (phase 0)
+    const bool tmode = U.mode == JB_PEAK_TRUE;
+    double tpeak = peak;
+    if (tmode && R->F > 1) {
+        m = 0.0;
+        for (uint32_t t = tid; t < U.ntiles; t += kLnLanes)
+            m = fmax(m, tp[U.tile0 + t]);
+        rs[tid] = m;
+        __syncthreads();
+        for (uint32_t w = kLnLanes / 2; w > 0; w >>= 1) {
+            if (tid < w)
+                rs[tid] = fmax(rs[tid], rs[tid + w]);
+            __syncthreads();
+        }
+        tpeak = fmax(peak, rs[0]);
+        __syncthreads();
+    }
     const uint64_t nh = U.n / H, nb = nh >= 4 ? nh - 3 : 0;
     const double *zu = z + U.tile0;
     auto hop_z = [&](uint64_t h) {
@@ -490,7 +611,8 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_gate(const LoudnessRate *__rest
         const double P = 20.0 * log10(peak / 32768.0);
         double gain = 0.0;
         bool any = false;
-        const double tl = U.target - L, cp = U.ceiling - P;
+        const double TP = tmode ? 20.0 * log10(tpeak / 32768.0) : NAN;
+        const double tl = U.target - L, cp = U.ceiling - (tmode ? TP : P);
         if (isfinite(tl)) {
             gain = tl;
             any = true;
@@ -504,6 +626,7 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_gate(const LoudnessRate *__rest
         r.peak_dbfs = P;
         r.gain_db = gain;
         r.g = pow(10.0, gain / 20.0);
+        r.true_peak_dbtp = TP;
         res[U.slot] = r;
     }
 }
@@ -539,8 +662,8 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_apply(const LoudnessUtt *__rest
 }
 
 hipError_t launch_loudness_measure(const LoudnessRate *rates_dev, const LoudnessUtt *utts_dev, uint32_t n,
-                                   uint64_t tiles, double *st, double *pk, double *z, LoudnessResult *res,
-                                   hipStream_t stream)
+                                   uint64_t tiles, double *st, double *pk, double *tp, double *z, LoudnessResult *res,
+                                   bool true_peak, hipStream_t stream)
 {
     if (n == 0)
         return hipSuccess;
@@ -552,8 +675,11 @@ hipError_t launch_loudness_measure(const LoudnessRate *rates_dev, const Loudness
         hipLaunchKernelGGL(k_ln_scan, dim3(n), dim3(64), 0, stream, rates_dev, utts_dev, st);
         hipLaunchKernelGGL(k_ln_tiles<true>, dim3((uint32_t)tiles), dim3(kLnLanes), 0, stream, rates_dev, utts_dev, n,
                            st, pk, z);
+        if (true_peak)
+            hipLaunchKernelGGL(k_ln_true_peak, dim3((uint32_t)tiles), dim3(kLnLanes), 0, stream, rates_dev, utts_dev,
+                               n, tp);
     }
-    hipLaunchKernelGGL(k_ln_gate, dim3(n), dim3(kLnLanes), 0, stream, rates_dev, utts_dev, pk, z, res);
+    hipLaunchKernelGGL(k_ln_gate, dim3(n), dim3(kLnLanes), 0, stream, rates_dev, utts_dev, pk, tp, z, res);
     return hipGetLastError();
 }
 
@@ -571,18 +697,11 @@ hipError_t launch_loudness_apply(const LoudnessUtt *utts_dev, uint32_t n, uint64
     return hipGetLastError();
 }
 
-} // namespace jb
-
-using namespace jb;
-
-extern "C" {
-
-int jb_loudness_filter(uint32_t hz, double *b, double *a, uint32_t *hop) { return loudness_filter(hz, b, a, hop); }
-
-int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
-                          double *lufs, double *peak_dbfs)
+// The measurement on PCM the caller holds: out[u] of in[u]; mode: what every utterance's ceiling term would read
+int measure_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
+                      uint32_t mode, const char *what, std::vector<LoudnessResult> *res)
 {
-    if (n && (!in || !n_in || !lufs || !peak_dbfs))
+    if (n && (!in || !n_in))
         return JB_ERR_INVALID;
     if (hz == 0) {
         set_error("loudness: a rate of 0 Hz");
@@ -616,16 +735,18 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
         w.ntiles = loudness_tiles(rate, w.n);
         w.tile0 = w.lt0 = tiles;
         w.slot = (uint32_t)u;
+        w.mode = mode;
         w.target = NAN;
         w.ceiling = INFINITY;
         tiles += w.ntiles;
         samples += w.n;
     }
-    double *dx = nullptr, *dst = nullptr, *dpk = nullptr, *dz = nullptr;
+    double *dx = nullptr, *dst = nullptr, *dpk = nullptr, *dtp = nullptr, *dz = nullptr;
     LoudnessRate *dr = nullptr;
     LoudnessUtt *du = nullptr;
     LoudnessResult *dres = nullptr;
-    std::vector<LoudnessResult> out(n);
+    std::vector<LoudnessResult> &out = *res;
+    out.assign(n, LoudnessResult{});
     hipError_t e = scratch.open_stream();
     hipStream_t s = scratch.stream;
     if (e == hipSuccess)
@@ -634,6 +755,8 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
         e = scratch.alloc(&dst, 4 * std::max<uint64_t>(tiles, 1));
     if (e == hipSuccess)
         e = scratch.alloc(&dpk, std::max<uint64_t>(tiles, 1));
+    if (e == hipSuccess)
+        e = scratch.alloc(&dtp, std::max<uint64_t>(tiles, 1));
     if (e == hipSuccess)
         e = scratch.alloc(&dz, std::max<uint64_t>(tiles, 1));
     if (e == hipSuccess)
@@ -654,17 +777,74 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
     if (e == hipSuccess && n)
         e = hipMemcpyAsync(du, utts.data(), sizeof(LoudnessUtt) * n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
-        e = launch_loudness_measure(dr, du, (uint32_t)n, tiles, dst, dpk, dz, dres, s);
+        e = launch_loudness_measure(dr, du, (uint32_t)n, tiles, dst, dpk, dtp, dz, dres, mode == JB_PEAK_TRUE, s);
     if (e == hipSuccess && n)
         e = hipMemcpyAsync(out.data(), dres, sizeof(LoudnessResult) * n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
     if (e != hipSuccess)
-        return hip_fail(e, "jb_loudness_pcm_batch");
+        return hip_fail(e, what);
+    return JB_OK;
+}
+
+} // namespace jb
+
+using namespace jb;
+
+extern "C" {
+
+int jb_loudness_filter(uint32_t hz, double *b, double *a, uint32_t *hop) { return loudness_filter(hz, b, a, hop); }
+
+int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
+                          double *lufs, double *peak_dbfs)
+{
+    if (n && (!lufs || !peak_dbfs))
+        return JB_ERR_INVALID;
+    std::vector<LoudnessResult> out;
+    int rc = measure_pcm_batch(in, n_in, n, hz, device, JB_PEAK_SAMPLE, "jb_loudness_pcm_batch", &out);
+    if (rc)
+        return rc;
     for (size_t u = 0; u < n; u++) {
         lufs[u] = out[u].lufs;
         peak_dbfs[u] = out[u].peak_dbfs;
     }
+    return JB_OK;
+}
+
+int jb_true_peak_filter(uint32_t hz, uint32_t *F, uint32_t *ntaps, double *taps, size_t cap)
+{
+    uint32_t f = 0;
+    int rc = true_peak_table(hz, &f, nullptr);
+    if (rc)
+        return rc;
+    if (F)
+        *F = f;
+    if (ntaps)
+        *ntaps = kTpTaps;
+    if (!taps)
+        return JB_OK;
+    if (cap < (size_t)(f - 1) * kTpTaps) {
+        set_error("jb_true_peak_filter: the buffer holds fewer than (F - 1) * 12 taps");
+        return JB_ERR_BUFFER;
+    }
+    double all[(kTpMaxF - 1) * kTpTaps];
+    if ((rc = true_peak_table(hz, nullptr, all)))
+        return rc;
+    std::copy(all, all + (size_t)(f - 1) * kTpTaps, taps);
+    return JB_OK;
+}
+
+int jb_true_peak_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
+                           double *true_peak_dbtp)
+{
+    if (n && !true_peak_dbtp)
+        return JB_ERR_INVALID;
+    std::vector<LoudnessResult> out;
+    int rc = measure_pcm_batch(in, n_in, n, hz, device, JB_PEAK_TRUE, "jb_true_peak_pcm_batch", &out);
+    if (rc)
+        return rc;
+    for (size_t u = 0; u < n; u++)
+        true_peak_dbtp[u] = out[u].true_peak_dbtp;
     return JB_OK;
 }
 

@@ -92,6 +92,27 @@ int OutputChain::set_loudness(const double *target, const double *ceiling, size_
     return JB_OK;
 }
 
+// The mode is kept with or without a target (either order); it takes effect where a target makes the chain measure
+int OutputChain::set_peak_mode(const uint32_t *mode, size_t n)
+{
+    int rc = check_settable("jb_batch_set_peak_mode: the peak mode is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!mode || (n != 1 && n != (size_t)b.B)) {
+        set_error("jb_batch_set_peak_mode: give one mode, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    for (size_t u = 0; u < n; u++)
+        if (mode[u] != JB_PEAK_SAMPLE && mode[u] != JB_PEAK_TRUE) {
+            set_error("jb_batch_set_peak_mode: a mode is JB_PEAK_SAMPLE or JB_PEAK_TRUE");
+            return JB_ERR_INVALID;
+        }
+    ln_mode.assign((size_t)b.B, JB_PEAK_SAMPLE);
+    for (size_t u = 0; u < (size_t)b.B; u++)
+        ln_mode[u] = mode[n == 1 ? 0 : u];
+    return JB_OK;
+}
+
 int OutputChain::set_flac(const jb_flac_opts *opts)
 {
     FlacParams p{};
@@ -214,13 +235,16 @@ int OutputChain::prepare_loudness()
         w.slot = (uint32_t)u;
         w.target = ln_target[u];
         w.ceiling = ln_ceiling[u];
+        w.mode = peak_mode(u);
+        ln.true_peak = ln.true_peak || w.mode == JB_PEAK_TRUE;
         tiles += w.ntiles;
         atiles += (w.n + kLnApplyTile - 1) / kLnApplyTile;
     }
     const size_t nt = (size_t)std::max<uint64_t>(tiles, 1);
     if ((rc = b.dalloc(&ln.rates_dev, rates.size(), false)) || (rc = b.dalloc(&ln.utts_dev, B, false)) ||
         (rc = b.dalloc(&ln.redo_dev, B, false)) || (rc = b.dalloc(&ln.st, 4 * nt, false)) ||
-        (rc = b.dalloc(&ln.pk, nt, false)) || (rc = b.dalloc(&ln.z, nt, false)) || (rc = b.dalloc(&ln.res, B, false)))
+        (rc = b.dalloc(&ln.pk, nt, false)) || (rc = b.dalloc(&ln.z, nt, false)) ||
+        (rc = b.dalloc(&ln.res, B, false)) || (ln.true_peak && (rc = b.dalloc(&ln.tp, nt, false))))
         return rc;
     hipError_t e;
     if ((e = hipMemcpy(ln.rates_dev, rates.data(), sizeof(LoudnessRate) * rates.size(), hipMemcpyHostToDevice)) !=
@@ -328,7 +352,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         (e = launch_resample(rs.tables_dev, tiles, n_tiles, plan.converter.i16, rs.lds, st)) != hipSuccess)
         return hip_fail(e, only ? "k_resample(redo)" : "k_resample");
     if (plan.normalize() && (!only || n_utts) &&
-        ((e = launch_loudness_measure(ln.rates_dev, utts, n_utts, lt, ln.st, ln.pk, ln.z, ln.res, st)) != hipSuccess ||
+        ((e = launch_loudness_measure(ln.rates_dev, utts, n_utts, lt, ln.st, ln.pk, ln.tp, ln.z, ln.res, ln.true_peak,
+                                      st)) != hipSuccess ||
          (e = launch_loudness_apply(utts, n_utts, at, ln.res, plan.apply.i16, st)) != hipSuccess))
         return hip_fail(e, only ? "loudness(redo)" : "loudness");
     // FLAC: the blocks of the list, then every stream's offsets and place (all of fl.work_dev, redo or not)

@@ -51,6 +51,9 @@ def _bind(L):
         getattr(L, "jb_engine_set_" + n).argtypes = [vp, C.c_double]
         getattr(L, "jb_engine_get_" + n).argtypes = [vp]
         getattr(L, "jb_engine_get_" + n).restype = C.c_double
+    L.jb_engine_set_peak_mode.argtypes = [vp, C.c_uint32]
+    L.jb_engine_get_peak_mode.argtypes = [vp]
+    L.jb_engine_get_peak_mode.restype = C.c_uint32
     L.jb_engine_set_fast_invariant.argtypes = [vp, C.c_int]
     L.jb_engine_get_fast_invariant.argtypes = [vp]
     for n in ("num_voices", "num_streams", "num_states"):
@@ -149,6 +152,10 @@ class _Condition:
         """Sample-peak ceiling (dBFS) that goes with the target: default 0, inf = none."""
         F.check(self._L().jb_engine_set_peak_ceiling(self._h(), float(dbfs)))
     def get_peak_ceiling(self): return self._L().jb_engine_get_peak_ceiling(self._h())
+    def set_peak_mode(self, mode):
+        """What the ceiling bounds: 0 = the sample peak (the default), 1 = the true peak (dBTP)."""
+        F.check(self._L().jb_engine_set_peak_mode(self._h(), int(mode)))
+    def get_peak_mode(self): return self._L().jb_engine_get_peak_mode(self._h())
     def set_alpha(self, f): F.check(self._L().jb_engine_set_alpha(self._h(), float(f)))
     def get_alpha(self): return self._L().jb_engine_get_alpha(self._h())
     def set_beta(self, f): F.check(self._L().jb_engine_set_beta(self._h(), float(f)))
