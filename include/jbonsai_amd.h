@@ -626,6 +626,22 @@ double jb_engine_get_peak_ceiling(const jb_engine *e);
  * _flac and _multi entries and the generator. */
 int jb_engine_set_peak_mode(jb_engine *e, uint32_t mode);
 uint32_t jb_engine_get_peak_mode(const jb_engine *e);
+/* New.  Where the per-label decision-tree search of the front half runs (Model::get_index for the duration model and
+ * every stream model, state and voice, and the GV switch question).  The default is the host, as before: nothing new
+ * runs and nothing is allocated.  On the device one wave searches one label (jb_treesearch.hip); label parsing, the
+ * duration estimate, the GV pdf of the first label and batch creation stay on the host, and the results are bit for
+ * bit the host's, errors included.  A request holding a label above 1023 bytes is searched on the host.  Any other
+ * value: JB_ERR_INVALID.  jb_engine_new copies the mode with the Condition; the engines of an _each call must agree
+ * on it.  Honoured by jb_synthesize, _batch[_i16], _each[_i16], the _flac and _multi entries (each device thread with
+ * its own device's tables), jb_generator_new and jb_engine_states (those two on the current device). */
+#define JB_SEARCH_HOST 0   /* default: the host threads search */
+#define JB_SEARCH_AUTO 1   /* device when the request has at least the measured number of label lines (1,024), else host */
+#define JB_SEARCH_DEVICE 2 /* device for every request with at least one label */
+int jb_engine_set_tree_search(jb_engine *e, uint32_t mode);
+uint32_t jb_engine_get_tree_search(const jb_engine *e);
+/* labels whose trees were searched on a device for this engine so far (0 in host mode); utterance u of an _each call
+ * counts for engines[u] */
+uint64_t jb_engine_device_searched_labels(const jb_engine *e);
 int jb_engine_set_speed(jb_engine *e, double v);
 double jb_engine_get_speed(const jb_engine *e);
 int jb_engine_set_alpha(jb_engine *e, double v);
@@ -675,7 +691,7 @@ void jb_pcm_i16_free(int16_t *pcm);
  * engines[u], under engines[u]'s whole Condition (speed, alignment flag, half tone, volume, alpha, beta, GV weights,
  * MSD thresholds, the three kinds of interpolation weight), in one batch.  New entry (the reference has no batch).
  * The engines share one voice set -- engines made from one another with jb_engine_new (Engine::clone) -- and agree
- * on sampling_frequency, fperiod, stage, use_log_gain, the batch-invariant and the fast-invariant flags; otherwise JB_ERR_INVALID, with
+ * on sampling_frequency, fperiod, stage, use_log_gain, the batch-invariant and the fast-invariant flags and the tree-search mode; otherwise JB_ERR_INVALID, with
  * jb_last_error naming what differs, before any device is touched.  pcm[u] library-owned (jb_pcm_free each). */
 int jb_synthesize_batch_each(const jb_engine *const *engines, const char *const *label_lines, const size_t *line_off,
                              size_t n_utts, int32_t device, double **pcm, size_t *n_samples);
@@ -728,6 +744,19 @@ int jb_engine_pdf_table(const jb_engine *e, size_t voice, int kind, size_t tree,
  * (or -1 when none has that state index), pdf_index 1-based. */
 int jb_engine_tree_index(const jb_engine *e, size_t voice, int kind, int state_index,
                          const char *label, int *tree_state, int *pdf_index);
+
+/* New.  The device tree search on labels the caller holds (jb_resample_pcm_batch's kind): bare label strings, no
+ * times, no shape check, on `device` (-1 = current).  tree_state / pdf_index: [n_labels][n_voices][1 + nstream][nstate];
+ * kind k = 0 is the duration model (entry s = 0 is state_index 2; its entries s > 0 are -1 / 0), kind 1 + si stream
+ * si with entry s = state_index 2 + s: exactly the two values jb_engine_tree_index(e, voice, k, state_index, label)
+ * returns, out-of-range leaves included (no error is raised for them here).  gv_on[n_labels] = 1 unless the voice's
+ * GV_OFF_CONTEXT question matches the label.  Each output may be NULL.  A label above 1023 bytes:
+ * JB_ERR_UNSUPPORTED naming it.  Not counted by jb_engine_device_searched_labels. */
+int jb_tree_search_batch(const jb_engine *e, const char *const *labels, size_t n_labels, int32_t device,
+                         int32_t *tree_state, int32_t *pdf_index, uint8_t *gv_on);
+/* Same outputs from the scalar walker over the same flattened tables (any label length); no GPU is touched. */
+int jb_tree_search_flat_host(const jb_engine *e, const char *const *labels, size_t n_labels, int32_t *tree_state,
+                             int32_t *pdf_index, uint8_t *gv_on);
 
 /* Engine::generator (src/engine.rs:301) + SpeechGenerator (src/speech.rs:25-96). */
 int jb_generator_new(const jb_engine *e, const char *const *label_lines, size_t n_lines,

@@ -34,6 +34,9 @@ BATCH_NO_EXC_TABLE = 512
 BATCH_INVARIANT = 1024
 PEAK_SAMPLE = 0
 PEAK_TRUE = 1
+SEARCH_HOST = 0
+SEARCH_AUTO = 1
+SEARCH_DEVICE = 2
 
 
 class JbError(RuntimeError):
@@ -196,6 +199,8 @@ SYMBOLS = [
     "jb_synthesize_batch_each_flac",
     "jb_batch_set_peak_mode", "jb_batch_loudness_report", "jb_true_peak_filter", "jb_true_peak_pcm_batch",
     "jb_engine_set_peak_mode", "jb_engine_get_peak_mode",
+    "jb_engine_set_tree_search", "jb_engine_get_tree_search", "jb_engine_device_searched_labels",
+    "jb_tree_search_batch", "jb_tree_search_flat_host",
 ]
 
 
@@ -328,6 +333,14 @@ def lib():
     L.jb_engine_set_peak_mode.argtypes = [vp, C.c_uint32]
     L.jb_engine_get_peak_mode.argtypes = [vp]
     L.jb_engine_get_peak_mode.restype = C.c_uint32
+    L.jb_engine_set_tree_search.argtypes = [vp, C.c_uint32]
+    L.jb_engine_get_tree_search.argtypes = [vp]
+    L.jb_engine_get_tree_search.restype = C.c_uint32
+    L.jb_engine_device_searched_labels.argtypes = [vp]
+    L.jb_engine_device_searched_labels.restype = C.c_uint64
+    i32p = C.POINTER(C.c_int32)
+    L.jb_tree_search_batch.argtypes = [vp, C.POINTER(C.c_char_p), sz, C.c_int32, i32p, i32p, C.POINTER(C.c_uint8)]
+    L.jb_tree_search_flat_host.argtypes = [vp, C.POINTER(C.c_char_p), sz, i32p, i32p, C.POINTER(C.c_uint8)]
     u8p, fop = C.POINTER(C.c_uint8), C.POINTER(FlacOpts)
     L.jb_batch_set_flac.argtypes = [vp, fop]
     L.jb_batch_flac_size.argtypes = [vp, sz, C.POINTER(sz)]

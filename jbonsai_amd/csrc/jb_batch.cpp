@@ -270,6 +270,11 @@ void stream_release(int device, hipStream_t st)
 
 } // namespace
 
+hipError_t pooled_stream_acquire(int device, hipStream_t *st) { return stream_acquire(device, st); }
+void pooled_stream_release(int device, hipStream_t st) { stream_release(device, st); }
+hipError_t pooled_block_alloc(int device, size_t bytes, void **out, size_t *got) { return pool_alloc(device, bytes, out, got); }
+void pooled_block_free(int device, void *p, size_t got) { pool_free(device, p, got); }
+
 static void release_pinned_chunks();
 void release_cached_memory()
 {

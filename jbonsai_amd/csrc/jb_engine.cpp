@@ -11,6 +11,7 @@
 // Everything from the state level down (MLPG, GV, excitation, MLSA) is handed to
 // the HIP batch (jb_batch.cpp); nothing here synthesises audio.
 #include "jb_host.h"
+#include "jb_treesearch.h"
 #include "jb_voice.h"
 
 #include <algorithm>
@@ -49,6 +50,7 @@ struct Condition {
     double loudness_target = NAN; // jb_engine_set_loudness_target: NaN = off
     double peak_ceiling = 0.0;    // jb_engine_set_peak_ceiling (dBFS), with a target only
     uint32_t peak_mode = JB_PEAK_SAMPLE; // jb_engine_set_peak_mode: what the ceiling bounds, with a target only
+    uint32_t tree_search = JB_SEARCH_HOST; // jb_engine_set_tree_search: where the per-label tree search runs
     double speed = 1.0;
     size_t stage = 0;
     bool use_log_gain = false;
@@ -76,10 +78,24 @@ struct Engine {
     mutable std::map<int, jb_pdf_set *> pdf_sets;
     mutable std::mutex pdf_mu;
     int pdf_set_for(int device, const jb_pdf_set **out) const;
+    // device tree search (jb_engine_set_tree_search): the flat tables of the voices' trees, built at the first use,
+    // their device copies per GPU (one block each), and the labels searched there so far
+    struct TsDevCopy {
+        void *block = nullptr;
+        TsDev d{};
+    };
+    mutable std::unique_ptr<TsTables> ts;
+    mutable std::map<int, TsDevCopy> ts_dev;
+    mutable std::mutex ts_mu;
+    mutable std::atomic<uint64_t> dev_searched{0};
+    const TsTables &tables() const;
+    int ts_dev_for(int device, TsDev *out) const;
     ~Engine()
     {
         for (auto &kv : pdf_sets)
             jb_pdf_set_free(kv.second);
+        for (auto &kv : ts_dev)
+            (void)hipFree(kv.second.block);
     }
 };
 
@@ -354,22 +370,28 @@ struct States {
     std::vector<uint8_t> gsw[kMaxStream];
 };
 
-// VoiceSet::weighted (voice_set.rs:80-95): first*w0, then += w_i * param_i, in order.
+// VoiceSet::weighted (voice_set.rs:80-95): first*w0, then += w_i * param_i, in order; get(v) = voice v's parameter.
 template <class F>
 static void blend(const Engine &e, const std::vector<double> &w, size_t len, double *out, F get)
 {
-    const float *p0 = get(*e.voices[0]);
+    const float *p0 = get((size_t)0);
     for (size_t k = 0; k < len; k++)
         out[k] = (double)p0[k] * w[0];
     for (size_t v = 1; v < e.voices.size(); v++) {
-        const float *p = get(*e.voices[v]);
+        const float *p = get(v);
         for (size_t k = 0; k < len; k++)
             out[k] += w[v] * (double)p[k];
     }
 }
 
-// indexed == true: the stream Gaussians are NOT blended on the host; st.iutt carries the pdf rows
-// (tree search result) of every state and voice for the device-side gather (needs Engine::cat).
+// Model::get_parameter from a search result: the row of (tree position, 1-based pdf index)
+static const float *pdf_row(const Model &m, int tp, int pi)
+{
+    if (tp < 0 || pi < 1 || pi > m.npdf[(size_t)tp])
+        throw ModelError("index not found"); // reference: todo!() (voice/model.rs:76-79)
+    return m.pdf[(size_t)tp].data() + (size_t)(pi - 1) * (size_t)m.pdf_len;
+}
+
 // Runs fn(lo, hi) over [0, n) in `nt` contiguous pieces on host threads (in the calling thread when nt == 1);
 // a ModelError thrown by a piece is rethrown here.  The per-label work of the front half (tree searches with
 // string-predicate questions, pdf blend) is independent per label and read-only on the engine.
@@ -412,31 +434,255 @@ static unsigned host_threads_default()
     return nt;
 }
 
-// indexed: row indices into the concatenated pdf tables of `tables` (default e; what Engine::pdf_set_for built them
-// for -- engines that share one voice set share the layout)
-static int build_states(const Engine &e, const char *const *lines, size_t n, States &st, bool indexed = false,
-                        unsigned label_threads = 1, const Engine *tables = nullptr)
+// The front half of one utterance goes in three steps: parse (label lines -> labels and times), search (every
+// label's trees -> FrontUtt::tp / pi / gv_on) and finish (pdf rows or blended Gaussians, durations, GV).  The search
+// runs on the host threads -- then inside the finish step's one pass over the labels, label by label, as it always
+// has -- or beforehand on the device (device_tree_search), which fills the same block.
+struct FrontUtt {
+    ParsedLabels pl;
+    // per label [nv][1 + nstream][nstate]: what Model::get_index returns (tree position, 1-based pdf index), laid
+    // out as ts_walk_label's; gv_on per label: !gv_off.test(label)
+    std::vector<int32_t> tp, pi;
+    std::vector<uint8_t> gv_on;
+    // the block as the device filled it: the utterance's part of its request's DeviceIndex (null: not searched yet)
+    // (dev_tp: [entries], the same for every label)
+    const int32_t *dev_tp = nullptr, *dev_pi = nullptr;
+    const uint8_t *dev_gv = nullptr;
+};
+// Results of one device search, all labels of the request in order; the request's FrontUtts point into it
+struct DeviceIndex {
+    std::unique_ptr<int32_t[]> pi;
+    std::unique_ptr<uint8_t[]> gv;
+};
+
+const TsTables &Engine::tables() const
+{
+    std::lock_guard<std::mutex> lk(ts_mu);
+    if (!ts) {
+        ts.reset(new TsTables());
+        ts_flatten(voices, std::min(voices[0]->streams.size(), (size_t)kMaxStream), ts.get());
+    }
+    return *ts;
+}
+
+// the caller has made `device` current
+int Engine::ts_dev_for(int device, TsDev *out) const
+{
+    const TsTables &t = tables();
+    std::lock_guard<std::mutex> lk(ts_mu);
+    auto it = ts_dev.find(device);
+    if (it == ts_dev.end()) {
+        auto al = [](size_t b) { return (b + 15) / 16 * 16; };
+        const size_t sizes[7] = {t.pool.size(),
+                                 t.patterns.size() * sizeof(TsPattern),
+                                 t.questions.size() * sizeof(TsQuestion),
+                                 t.nodes.size() * sizeof(TsNode),
+                                 t.trees.size() * sizeof(TsTree),
+                                 t.models.size() * sizeof(TsModel),
+                                 t.state_tree.size() * sizeof(int32_t)};
+        const void *src[7] = {t.pool.data(),  t.patterns.data(), t.questions.data(),  t.nodes.data(),
+                              t.trees.data(), t.models.data(),   t.state_tree.data()};
+        size_t offs[7], total = 0;
+        for (int k = 0; k < 7; k++) {
+            offs[k] = total;
+            total += al(std::max<size_t>(sizes[k], 1));
+        }
+        std::vector<uint8_t> host(total, 0);
+        for (int k = 0; k < 7; k++)
+            if (sizes[k])
+                memcpy(host.data() + offs[k], src[k], sizes[k]);
+        TsDevCopy c;
+        hipError_t he = hipMalloc(&c.block, total);
+        if (he == hipSuccess && (he = hipMemcpy(c.block, host.data(), total, hipMemcpyHostToDevice)) != hipSuccess) {
+            (void)hipFree(c.block);
+            c.block = nullptr;
+        }
+        if (he != hipSuccess)
+            return hip_fail(he, "tree-search tables");
+        const uint8_t *b = (const uint8_t *)c.block;
+        c.d.pool = b + offs[0];
+        c.d.patterns = (const TsPattern *)(b + offs[1]);
+        c.d.questions = (const TsQuestion *)(b + offs[2]);
+        c.d.nodes = (const TsNode *)(b + offs[3]);
+        c.d.trees = (const TsTree *)(b + offs[4]);
+        c.d.models = (const TsModel *)(b + offs[5]);
+        c.d.state_tree = (const int32_t *)(b + offs[6]);
+        c.d.nv = t.nv;
+        c.d.nkind = t.nkind;
+        c.d.nstate = t.nstate;
+        c.d.gv_question = t.gv_question;
+        c.d.memo_words = tree_search_memo_words(t.questions.size());
+        it = ts_dev.emplace(device, c).first;
+    }
+    *out = it->second.d;
+    return JB_OK;
+}
+
+// Whether the device search takes these labels: each at most kTsMaxLabel bytes, 32-bit offsets into their slab.
+// *too_long (optional): the first label above the limit
+static bool device_searchable(const std::vector<std::string_view> &labels, size_t *too_long = nullptr)
+{
+    uint64_t bytes = 0;
+    for (size_t i = 0; i < labels.size(); i++) {
+        if (labels[i].size() > kTsMaxLabel) {
+            if (too_long)
+                *too_long = i;
+            return false;
+        }
+        bytes += labels[i].size();
+    }
+    if (too_long)
+        *too_long = labels.size();
+    return bytes < 0xffffffffull && labels.size() < 0xffffffffull;
+}
+
+// One launch for all `labels` (device_searchable) on `device` (< 0: the current one), with the tables of `te`: one
+// slab up, the results back once the search's own stream has finished.  tp / pi: [n][entries], gv: [n]
+static int device_tree_search(const Engine &te, int device, const std::vector<std::string_view> &labels, int32_t *tp,
+                              int32_t *pi, uint8_t *gv)
+{
+    const size_t n = labels.size();
+    if (n == 0)
+        return JB_OK;
+    // JB_FRONT_TRACE=1: the steps of one search on stderr (it then waits for the kernel before the read-back)
+    static const bool trace = getenv("JB_FRONT_TRACE") && atoi(getenv("JB_FRONT_TRACE")) != 0;
+    auto t_prev = std::chrono::steady_clock::now();
+    double t_step[4] = {0, 0, 0, 0};
+    auto mark = [&](int k) {
+        const auto t = std::chrono::steady_clock::now();
+        t_step[k] = std::chrono::duration<double, std::milli>(t - t_prev).count();
+        t_prev = t;
+    };
+    hipError_t he;
+    if (device < 0 && (he = hipGetDevice(&device)) != hipSuccess)
+        return hip_fail(he, "no HIP device");
+    DeviceScratch ds; // makes the device current for the call
+    if ((he = ds.enter(device)) != hipSuccess)
+        return hip_fail(he, "hipSetDevice");
+    TsDev d;
+    int rc = te.ts_dev_for(device, &d);
+    if (rc)
+        return rc;
+    const size_t E = te.tables().entries();
+    auto al = [](size_t b) { return (b + 15) / 16 * 16; };
+    size_t slab_bytes = 0;
+    for (const std::string_view &l : labels)
+        slab_bytes += l.size();
+    const size_t off_bytes = al((n + 1) * sizeof(uint32_t)), in_bytes = off_bytes + al(std::max<size_t>(slab_bytes, 1));
+    const size_t idx_bytes = al(n * E * sizeof(int32_t)), out_bytes = 2 * idx_bytes + al(n);
+    std::unique_ptr<uint8_t[]> in(new uint8_t[in_bytes]); // (not cleared: tens of MB for a large request)
+    uint32_t *off = (uint32_t *)in.get();
+    uint32_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = at;
+        memcpy(in.get() + off_bytes + at, labels[i].data(), labels[i].size());
+        at += (uint32_t)labels[i].size();
+    }
+    off[n] = at;
+    mark(0);
+    void *blk = nullptr;
+    size_t got = 0;
+    if ((he = pooled_block_alloc(device, in_bytes + out_bytes, &blk, &got)) != hipSuccess)
+        return hip_fail(he, "tree search: device memory");
+    hipStream_t st = nullptr;
+    if ((he = pooled_stream_acquire(device, &st)) != hipSuccess) {
+        pooled_block_free(device, blk, got);
+        return hip_fail(he, "tree search: stream");
+    }
+    uint8_t *b = (uint8_t *)blk;
+    int32_t *tp_dev = (int32_t *)(b + in_bytes), *pi_dev = (int32_t *)(b + in_bytes + idx_bytes);
+    uint8_t *gv_dev = b + in_bytes + 2 * idx_bytes;
+    const char *what = "tree search: upload";
+    if ((he = hipMemcpyAsync(b, in.get(), in_bytes, hipMemcpyHostToDevice, st)) == hipSuccess) {
+        what = "k_tree_search";
+        mark(1);
+        he = launch_tree_search(d, b + off_bytes, (const uint32_t *)b, (uint32_t)n, tp ? tp_dev : nullptr, pi_dev,
+                                gv_dev, st);
+        if (trace && he == hipSuccess) {
+            he = hipStreamSynchronize(st);
+            mark(2);
+        }
+    }
+    if (he == hipSuccess && tp) {
+        what = "tree search: read-back";
+        he = hipMemcpyAsync(tp, tp_dev, n * E * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    }
+    if (he == hipSuccess && pi)
+        he = hipMemcpyAsync(pi, pi_dev, n * E * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && gv)
+        he = hipMemcpyAsync(gv, gv_dev, n, hipMemcpyDeviceToHost, st);
+    const hipError_t hs = hipStreamSynchronize(st); // nothing stays in flight into the block or the host buffers
+    if (he == hipSuccess && hs != hipSuccess) {
+        what = "tree search";
+        he = hs;
+    }
+    mark(3);
+    pooled_stream_release(device, st);
+    pooled_block_free(device, blk, got);
+    if (trace)
+        fprintf(stderr, "tree search on the device: %zu labels, %zu bytes; slab %.2f ms, block + upload %.2f ms, kernel "
+                        "%.2f ms, read-back %.2f ms\n",
+                n, slab_bytes, t_step[0], t_step[1], t_step[2], t_step[3]);
+    return he == hipSuccess ? JB_OK : hip_fail(he, what);
+}
+
+// The label-line count of a request from which JB_SEARCH_AUTO searches on the device: the crossover that
+// tools/front_half.py measured (profiles/r11_tree_search.txt: device mode wins front half and wall time in every shape
+// from 1,024 labels on, and in none of 512 or fewer), rounded up to a power of two.
+constexpr size_t kAutoSearchLines = 1024;
+
+// Whether a request of n_lines label lines under e's mode asks for the device search
+static bool wants_device_search(const Engine &e, size_t n_lines)
+{
+    const uint32_t mode = e.cond.tree_search;
+    return n_lines > 0 && (mode == JB_SEARCH_DEVICE || (mode == JB_SEARCH_AUTO && n_lines >= kAutoSearchLines));
+}
+
+// Step 2 on the device for the utterances fu[0 .. n) of one request: one slab, one launch.  A request that holds a
+// label the kernel does not take is left to the host search (nothing is counted).  count[u]: the engine utterance
+// u's labels are counted for; out: what the FrontUtts then point into
+static int front_search_device(const Engine &te, int device, FrontUtt *fu, size_t n, const Engine *const *count,
+                               DeviceIndex *out)
+{
+    std::vector<std::string_view> labels;
+    for (size_t u = 0; u < n; u++)
+        for (const std::string &l : fu[u].pl.labels)
+            labels.emplace_back(l);
+    if (labels.empty() || !device_searchable(labels))
+        return JB_OK;
+    const size_t E = te.tables().entries();
+    // (a tree's position does not depend on the label: TsTables::state_tree has it, and only the pdf indices and
+    // the GV bytes come back)
+    out->pi.reset(new int32_t[labels.size() * E]);
+    out->gv.reset(new uint8_t[labels.size()]);
+    const int rc = device_tree_search(te, device, labels, nullptr, out->pi.get(), out->gv.get());
+    if (rc)
+        return rc;
+    size_t at = 0;
+    for (size_t u = 0; u < n; u++) {
+        const size_t nl = fu[u].pl.labels.size();
+        fu[u].dev_tp = te.tables().state_tree.data();
+        fu[u].dev_pi = out->pi.get() + at * E;
+        fu[u].dev_gv = out->gv.get() + at;
+        count[u]->dev_searched.fetch_add(nl, std::memory_order_relaxed);
+        at += nl;
+    }
+    return JB_OK;
+}
+
+// Step 3.  indexed == true: the stream Gaussians are NOT blended on the host; st.iutt carries the pdf rows (tree
+// search result) of every state and voice for the device-side gather: row indices into the concatenated pdf tables
+// of `tables` (default e; what Engine::pdf_set_for built them for -- engines that share one voice set share the
+// layout).  Labels whose trees have not been searched yet (no device block) are searched here, each on the host
+// thread that finishes it.
+static int front_finish(const Engine &e, FrontUtt &fu, States &st, bool indexed, unsigned label_threads,
+                        const Engine *tables)
 {
     const std::vector<Engine::CatTable> &cat = (tables ? tables : &e)->cat;
     const Condition &c = e.cond;
     const Voice &v0 = *e.voices[0];
-    // JB_FRONT_TRACE=1: phases of the front half of one utterance on stderr (like JB_CREATE_TRACE / JB_REDO_TRACE)
-    static const bool trace = getenv("JB_FRONT_TRACE") && atoi(getenv("JB_FRONT_TRACE")) != 0;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto fmark = [&](const char *what) {
-        if (!trace)
-            return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "front half: %-28s %8.3f ms (%zu labels, %u threads)\n", what,
-                std::chrono::duration<double, std::milli>(t - t_prev).count(), n, label_threads);
-        t_prev = t;
-    };
-    ParsedLabels pl;
-    int rc = parse_labels(c, lines, n, pl);
-    if (rc)
-        return rc;
-    fmark("labels parsed");
-    const size_t nl = pl.labels.size(), ns = (size_t)v0.meta.num_states, S = nl * ns;
+    const ParsedLabels &pl = fu.pl;
+    const size_t nl = pl.labels.size(), ns = (size_t)v0.meta.num_states, S = nl * ns, nv = e.voices.size();
     st.dur.assign(S, 0);
     try {
         // Models::duration (model/mod.rs:80-92) and Models::stream (:98-118) of every label in ONE parallel pass
@@ -444,13 +690,16 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
         // 200-label text -- 1.2 ms, of which the tree searches are 0.2 on six threads)
         std::vector<MV> dp(S);
         const size_t nsx = std::min(v0.streams.size(), (size_t)kMaxStream);
+        const size_t nk = 1 + nsx, E = nv * nk * ns;
         size_t plen_max = 0;
+        bool any_gv = false;
         for (size_t si = 0; si < nsx; si++) {
             const StreamModel &sm = v0.streams[si];
             const size_t WL = (size_t)sm.vector_length * (size_t)sm.num_windows;
             plen_max = std::max(plen_max, 2 * WL + (sm.is_msd ? 1 : 0));
+            any_gv = any_gv || sm.use_gv;
             if (indexed) {
-                for (size_t v = 0; v < e.voices.size(); v++)
+                for (size_t v = 0; v < nv; v++)
                     st.rows[si][v].assign(S, 0);
                 st.weights[si] = c.w_param[si];
             } else {
@@ -459,13 +708,41 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
                 st.msd[si].assign(S, DBL_MAX);
             }
         }
+        const bool search_here = !fu.dev_tp;
+        if (search_here) {
+            fu.tp.assign(nl * E, -1);
+            fu.pi.assign(nl * E, 0);
+            fu.gv_on.assign(nl, 1);
+        }
+        const int32_t *const tp_all = search_here ? fu.tp.data() : fu.dev_tp;
+        const int32_t *const pi_all = search_here ? fu.pi.data() : fu.dev_pi;
+        const uint8_t *const gv_all = search_here ? fu.gv_on.data() : fu.dev_gv;
         parallel_labels(nl, label_threads, [&](size_t lo, size_t hi) {
             std::vector<double> tmp(2 * ns), buf(plen_max);
             QuestionMemo memo; // question results of the current label, per model
             for (size_t i = lo; i < hi; i++) {
-                memo.reset();
-                blend(e, c.w_duration, 2 * ns, tmp.data(),
-                      [&](const Voice &v) { return v.duration.get_parameter(2, pl.labels[i], &memo); });
+                const int32_t *tp = tp_all + (search_here ? i * E : 0), *pi = pi_all + i * E;
+                if (search_here) {
+                    int32_t *wt = fu.tp.data() + i * E, *wp = fu.pi.data() + i * E;
+                    memo.reset();
+                    for (size_t v = 0; v < nv; v++) {
+                        int a, b;
+                        e.voices[v]->duration.get_index(2, pl.labels[i], a, b, &memo);
+                        wt[v * nk * ns] = a;
+                        wp[v * nk * ns] = b;
+                        for (size_t si = 0; si < nsx; si++)
+                            for (size_t s = 0; s < ns; s++) {
+                                e.voices[v]->streams[si].stream.get_index((int)(2 + s), pl.labels[i], a, b, &memo);
+                                wt[(v * nk + 1 + si) * ns + s] = a;
+                                wp[(v * nk + 1 + si) * ns + s] = b;
+                            }
+                    }
+                    if (any_gv)
+                        fu.gv_on[i] = !v0.gv_off.test(pl.labels[i]);
+                }
+                blend(e, c.w_duration, 2 * ns, tmp.data(), [&](size_t v) {
+                    return pdf_row(e.voices[v]->duration, tp[v * nk * ns], pi[v * nk * ns]);
+                });
                 for (size_t s = 0; s < ns; s++)
                     dp[i * ns + s] = {tmp[s], tmp[s + ns]};
                 for (size_t si = 0; si < nsx; si++) {
@@ -475,17 +752,17 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
                     for (size_t s = 0; s < ns; s++) {
                         const size_t row = i * ns + s;
                         if (indexed) {
-                            for (size_t v = 0; v < e.voices.size(); v++) {
+                            for (size_t v = 0; v < nv; v++) {
                                 const Model &m = e.voices[v]->streams[si].stream;
-                                int tp, pi;
-                                m.get_index((int)(2 + s), pl.labels[i], tp, pi, &memo);
-                                if (tp < 0 || pi < 1 || pi > m.npdf[(size_t)tp])
+                                const int t = tp[(v * nk + 1 + si) * ns + s], p = pi[(v * nk + 1 + si) * ns + s];
+                                if (t < 0 || p < 1 || p > m.npdf[(size_t)t])
                                     throw ModelError("index not found"); // reference: todo!() (voice/model.rs:76-79)
-                                st.rows[si][v][row] = cat[v * nsx + si].tree_off[(size_t)tp] + (uint32_t)(pi - 1);
+                                st.rows[si][v][row] = cat[v * nsx + si].tree_off[(size_t)t] + (uint32_t)(p - 1);
                             }
                         } else {
-                            blend(e, c.w_param[si], plen, buf.data(), [&](const Voice &v) {
-                                return v.streams[si].stream.get_parameter((int)(2 + s), pl.labels[i], &memo);
+                            blend(e, c.w_param[si], plen, buf.data(), [&](size_t v) {
+                                return pdf_row(e.voices[v]->streams[si].stream, tp[(v * nk + 1 + si) * ns + s],
+                                               pi[(v * nk + 1 + si) * ns + s]);
                             });
                             std::copy(buf.begin(), buf.begin() + WL, st.mean[si].begin() + row * WL);
                             std::copy(buf.begin() + WL, buf.begin() + 2 * WL, st.var[si].begin() + row * WL);
@@ -496,7 +773,6 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
                 }
             }
         });
-        fmark("pdfs of all models");
         st.dur_pdf.resize(2 * S);
         for (size_t s = 0; s < S; s++) {
             st.dur_pdf[2 * s] = dp[s].mean;
@@ -531,7 +807,6 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
                 }
             }
         }
-        fmark("durations");
         st.utt.num_states = (uint32_t)S;
         st.utt.durations = st.dur.data();
         // Models::stream / gv (model/mod.rs:98-146)
@@ -539,7 +814,7 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
             const StreamModel &sm = v0.streams[si];
             if (indexed) {
                 jb_index_stream &io = st.iutt.stream[si];
-                for (size_t v = 0; v < e.voices.size(); v++)
+                for (size_t v = 0; v < nv; v++)
                     io.row[v] = st.rows[si][v].data();
                 io.weight = st.weights[si].data();
             }
@@ -552,22 +827,20 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
             if (sm.use_gv && nl > 0) {
                 const size_t L = (size_t)sm.vector_length;
                 std::vector<double> g(2 * L);
-                blend(e, c.w_gv[si], 2 * L, g.data(), [&](const Voice &v) {
-                    return v.streams[si].gv->get_parameter(2, pl.labels[0]); // first label only
+                blend(e, c.w_gv[si], 2 * L, g.data(), [&](size_t v) {
+                    return e.voices[v]->streams[si].gv->get_parameter(2, pl.labels[0]); // first label only
                 });
                 st.gvm[si].assign(g.begin(), g.begin() + L);
                 st.gvv[si].assign(g.begin() + L, g.end());
                 st.gsw[si].assign(S, 0);
-                for (size_t i = 0; i < nl; i++) {
-                    uint8_t sw = !v0.gv_off.test(pl.labels[i]);
+                for (size_t i = 0; i < nl; i++)
                     for (size_t s = 0; s < ns; s++)
-                        st.gsw[si][i * ns + s] = sw;
-                }
+                        st.gsw[si][i * ns + s] = gv_all[i];
                 o.gv_mean = st.gvm[si].data();
                 o.gv_var = st.gvv[si].data();
                 o.gv_switch = st.gsw[si].data();
             }
-                    if (indexed) {
+            if (indexed) {
                 jb_index_stream &io = st.iutt.stream[si];
                 io.gv_mean = o.gv_mean;
                 io.gv_var = o.gv_var;
@@ -594,6 +867,39 @@ static int build_states(const Engine &e, const char *const *lines, size_t n, Sta
         return JB_ERR_MODEL;
     }
     return JB_OK;
+}
+
+// The three steps for one utterance.  search_device: -2 = host search; otherwise the device (-1: the current one)
+// whose tables search the labels when e's mode asks for it
+static int build_states(const Engine &e, const char *const *lines, size_t n, States &st, bool indexed = false,
+                        unsigned label_threads = 1, const Engine *tables = nullptr, int search_device = -2)
+{
+    // JB_FRONT_TRACE=1: phases of the front half of one utterance on stderr (like JB_CREATE_TRACE / JB_REDO_TRACE)
+    static const bool trace = getenv("JB_FRONT_TRACE") && atoi(getenv("JB_FRONT_TRACE")) != 0;
+    auto t_prev = std::chrono::steady_clock::now();
+    auto fmark = [&](const char *what) {
+        if (!trace)
+            return;
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "front half: %-28s %8.3f ms (%zu labels, %u threads)\n", what,
+                std::chrono::duration<double, std::milli>(t - t_prev).count(), n, label_threads);
+        t_prev = t;
+    };
+    FrontUtt fu;
+    DeviceIndex dix;
+    int rc = parse_labels(e.cond, lines, n, fu.pl);
+    if (rc)
+        return rc;
+    fmark("labels parsed");
+    if (search_device != -2 && wants_device_search(e, n)) {
+        const Engine *count = &e;
+        if ((rc = front_search_device(tables ? *tables : e, search_device, &fu, 1, &count, &dix)))
+            return rc;
+        fmark("trees searched on the device");
+    }
+    rc = front_finish(e, fu, st, indexed, label_threads, tables);
+    fmark("pdfs, durations, GV");
+    return rc;
 }
 
 // SpeechGenerator (src/speech.rs:9-96).  The reference's generator owns its three parameter tracks and a
@@ -792,6 +1098,18 @@ int jb_engine_set_peak_mode(jb_engine *e, uint32_t mode)
     return JB_OK;
 }
 uint32_t jb_engine_get_peak_mode(const jb_engine *e) { return e ? CENG(e)->cond.peak_mode : JB_PEAK_SAMPLE; }
+int jb_engine_set_tree_search(jb_engine *e, uint32_t mode)
+{
+    if (!e || (mode != JB_SEARCH_HOST && mode != JB_SEARCH_AUTO && mode != JB_SEARCH_DEVICE))
+        return JB_ERR_INVALID;
+    ENG(e)->cond.tree_search = mode;
+    return JB_OK;
+}
+uint32_t jb_engine_get_tree_search(const jb_engine *e) { return e ? CENG(e)->cond.tree_search : JB_SEARCH_HOST; }
+uint64_t jb_engine_device_searched_labels(const jb_engine *e)
+{
+    return e ? CENG(e)->dev_searched.load(std::memory_order_relaxed) : 0;
+}
 int jb_engine_set_speed(jb_engine *e, double v)
 {
     ENG(e)->cond.speed = std::max(v, 1.0E-06);
@@ -934,6 +1252,70 @@ int jb_engine_tree_index(const jb_engine *e, size_t voice, int kind, int state_i
     return JB_OK;
 }
 
+// tree positions of a search -> the trees' states, as jb_engine_tree_index reports them
+static void positions_to_states(const jb::TsTables &t, size_t n_labels, int32_t *tree_state)
+{
+    const size_t E = t.entries();
+    for (size_t i = 0; i < n_labels; i++)
+        for (size_t k = 0; k < E; k++) {
+            int32_t &v = tree_state[i * E + k];
+            if (v >= 0)
+                v = t.trees[t.models[k / t.nstate].tree0 + (uint32_t)v].state;
+        }
+}
+
+int jb_tree_search_flat_host(const jb_engine *e, const char *const *labels, size_t n_labels, int32_t *tree_state,
+                             int32_t *pdf_index, uint8_t *gv_on)
+{
+    if (!e || (n_labels && !labels))
+        return JB_ERR_INVALID;
+    for (size_t i = 0; i < n_labels; i++)
+        if (!labels[i])
+            return JB_ERR_INVALID;
+    const jb::TsTables &t = CENG(e)->tables();
+    const size_t E = t.entries();
+    std::vector<int32_t> tp(E), pi(E);
+    std::vector<int8_t> memo;
+    for (size_t i = 0; i < n_labels; i++) {
+        uint8_t g = 0;
+        jb::ts_walk_label(t, labels[i], tp.data(), pi.data(), &g, memo);
+        if (tree_state)
+            std::copy(tp.begin(), tp.end(), tree_state + i * E);
+        if (pdf_index)
+            std::copy(pi.begin(), pi.end(), pdf_index + i * E);
+        if (gv_on)
+            gv_on[i] = g;
+    }
+    if (tree_state)
+        positions_to_states(t, n_labels, tree_state);
+    return JB_OK;
+}
+
+int jb_tree_search_batch(const jb_engine *e, const char *const *labels, size_t n_labels, int32_t device,
+                         int32_t *tree_state, int32_t *pdf_index, uint8_t *gv_on)
+{
+    if (!e || (n_labels && !labels))
+        return JB_ERR_INVALID;
+    std::vector<std::string_view> views(n_labels);
+    for (size_t i = 0; i < n_labels; i++) {
+        if (!labels[i])
+            return JB_ERR_INVALID;
+        views[i] = labels[i];
+    }
+    size_t bad = 0;
+    if (!device_searchable(views, &bad)) {
+        set_error(bad < n_labels ? "jb_tree_search_batch: labels[" + std::to_string(bad) + "] has " +
+                                       std::to_string(views[bad].size()) + " bytes; the device search takes at most " +
+                                       std::to_string(jb::kTsMaxLabel)
+                                 : std::string("jb_tree_search_batch: the labels exceed 4 GiB"));
+        return JB_ERR_UNSUPPORTED;
+    }
+    const int rc = device_tree_search(*CENG(e), device, views, tree_state, pdf_index, gv_on);
+    if (!rc && tree_state)
+        positions_to_states(CENG(e)->tables(), n_labels, tree_state);
+    return rc;
+}
+
 // ---- states ----
 int jb_engine_states(const jb_engine *e, const char *const *lines, size_t n, jb_states **out)
 {
@@ -941,7 +1323,7 @@ int jb_engine_states(const jb_engine *e, const char *const *lines, size_t n, jb_
         return JB_ERR_INVALID;
     *out = nullptr;
     std::unique_ptr<jb::States> st(new jb::States());
-    int rc = build_states(*CENG(e), lines, n, *st, false, host_threads_default());
+    int rc = build_states(*CENG(e), lines, n, *st, false, host_threads_default(), nullptr, -1);
     if (rc)
         return rc;
     *out = (jb_states *)st.release();
@@ -1077,35 +1459,66 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         const auto t0 = now();
         std::vector<int> rcs(hi - lo, JB_OK);
         std::vector<std::string> errs(hi - lo);
-        std::atomic<size_t> next{lo};
         // fewer utterances than threads (a single long text through jb_synthesize): the spare threads split
         // each utterance's labels
         const unsigned per_utt = (unsigned)std::max<size_t>(1, nt / std::max<size_t>(1, hi - lo));
-        auto work = [&]() {
-            for (size_t u; (u = next.fetch_add(1)) < hi;) {
-                rcs[u - lo] = build_states(*eng(u), lines + line_off[u], line_off[u + 1] - line_off[u], *sts[u], indexed,
-                                           per_utt, CENG(e));
-                if (rcs[u - lo])
-                    errs[u - lo] = jb::g_err; // the worker's thread-local message
+        // fn(u) for every utterance of the group on the host threads; the first failure in utterance order
+        auto each_utt = [&](auto fn) -> int {
+            std::atomic<size_t> next{lo};
+            auto work = [&]() {
+                for (size_t u; (u = next.fetch_add(1)) < hi;) {
+                    rcs[u - lo] = fn(u);
+                    if (rcs[u - lo])
+                        errs[u - lo] = jb::g_err; // the worker's thread-local message
+                }
+            };
+            const unsigned n = (unsigned)std::min<size_t>(nt, hi - lo);
+            if (n <= 1) {
+                work();
+            } else {
+                std::vector<std::thread> pool;
+                for (unsigned k = 0; k < n; k++)
+                    pool.emplace_back(work);
+                for (auto &t : pool)
+                    t.join();
             }
+            for (size_t u = lo; u < hi; u++)
+                if (rcs[u - lo]) {
+                    jb::set_error(errs[u - lo]);
+                    return rcs[u - lo];
+                }
+            return JB_OK;
         };
-        const unsigned n = (unsigned)std::min<size_t>(nt, hi - lo);
-        if (n <= 1) {
-            work();
+        int rc;
+        if (wants_device_search(*CENG(e), line_off[hi] - line_off[lo])) {
+            // the group's labels through one launch: parse on the host threads, one slab up, the indices back,
+            // finish on the host threads
+            std::vector<jb::FrontUtt> fu(hi - lo);
+            jb::DeviceIndex dix;
+            std::vector<const jb::Engine *> count(hi - lo);
+            for (size_t u = lo; u < hi; u++)
+                count[u - lo] = eng(u);
+            rc = each_utt([&](size_t u) {
+                return parse_labels(eng(u)->cond, lines + line_off[u], line_off[u + 1] - line_off[u], fu[u - lo].pl);
+            });
+            const auto t1 = now();
+            if (!rc)
+                rc = front_search_device(*CENG(e), device, fu.data(), fu.size(), count.data(), &dix);
+            const auto t2 = now();
+            if (!rc)
+                rc = each_utt(
+                    [&](size_t u) { return front_finish(*eng(u), fu[u - lo], *sts[u], indexed, per_utt, CENG(e)); });
+            if (timing)
+                fprintf(stderr, "front half of %zu utterance(s): parse %.2f ms, device search %.2f ms, finish %.2f ms\n",
+                        hi - lo, ms(t0, t1), ms(t1, t2), ms(t2, now()));
         } else {
-            std::vector<std::thread> pool;
-            for (unsigned k = 0; k < n; k++)
-                pool.emplace_back(work);
-            for (auto &t : pool)
-                t.join();
+            rc = each_utt([&](size_t u) {
+                return build_states(*eng(u), lines + line_off[u], line_off[u + 1] - line_off[u], *sts[u], indexed, per_utt,
+                                    CENG(e));
+            });
         }
         t_front += ms(t0, now());
-        for (size_t u = lo; u < hi; u++)
-            if (rcs[u - lo]) {
-                jb::set_error(errs[u - lo]);
-                return rcs[u - lo];
-            }
-        return JB_OK;
+        return rc;
     };
     auto launch = [&](size_t g) -> int {
         const auto t0 = now();
@@ -1352,6 +1765,8 @@ static int check_engines(const jb_engine *const *engines, size_t n)
             field = "batch_invariant";
         else if (e.cond.fast_invariant != e0.cond.fast_invariant)
             field = "fast_invariant";
+        else if (e.cond.tree_search != e0.cond.tree_search)
+            field = "tree_search";
         if (field) {
             jb::set_error("jb_synthesize_batch_each: engines[" + std::to_string(u) + "] differs from engines[0] in " +
                           field);
@@ -1435,7 +1850,7 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
         return JB_ERR_INVALID;
     *out = nullptr;
     jb::States st;
-    int rc = build_states(*CENG(e), lines, n, st, false, host_threads_default());
+    int rc = build_states(*CENG(e), lines, n, st, false, host_threads_default(), nullptr, -1);
     if (rc)
         return rc;
     std::unique_ptr<jb::Generator> g(new jb::Generator());

@@ -37,6 +37,19 @@ int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const si
                           int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0,
                           const jb_engine *const *each = nullptr, bool flac = false,
                           const jb_flac_opts *flac_opts = nullptr);
+// A stream / a device block from the per-device pools that batches draw from (jb_batch.cpp), for work outside a
+// batch; *got is the block's pooled size, which pooled_block_free takes back
+hipError_t pooled_stream_acquire(int device, hipStream_t *st);
+void pooled_stream_release(int device, hipStream_t st);
+hipError_t pooled_block_alloc(int device, size_t bytes, void **out, size_t *got);
+void pooled_block_free(int device, void *p, size_t got);
+// Decision-tree search of the front half on the device (jb_treesearch.hip): labels are slab[off[i] .. off[i + 1]),
+// each at most kTsMaxLabel bytes; outputs as ts_walk_label's, [n_labels][entries] and [n_labels] (tree_pos may be
+// null: a tree's position does not depend on the label)
+struct TsDev;
+uint32_t tree_search_memo_words(size_t n_questions); // TsDev::memo_words for that many questions (0: no memo fits)
+hipError_t launch_tree_search(const TsDev &d, const uint8_t *slab, const uint32_t *off, uint32_t n_labels,
+                              int32_t *tree_pos, int32_t *pdf_index, uint8_t *gv_on, hipStream_t stream);
 // static LPT partition (jb_multi.cpp): part_of[i] = bin of item i
 void lpt_partition(const uint64_t *weights, size_t n, size_t n_parts, uint32_t *part_of);
 

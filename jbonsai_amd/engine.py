@@ -156,6 +156,11 @@ class _Condition:
         """What the ceiling bounds: 0 = the sample peak (the default), 1 = the true peak (dBTP)."""
         F.check(self._L().jb_engine_set_peak_mode(self._h(), int(mode)))
     def get_peak_mode(self): return self._L().jb_engine_get_peak_mode(self._h())
+    def set_tree_search(self, mode):
+        """Where the per-label tree search runs: 0 = host threads (the default), 1 = the device from the measured
+        request size on, 2 = the device always (_ffi.SEARCH_*)."""
+        F.check(self._L().jb_engine_set_tree_search(self._h(), int(mode)))
+    def get_tree_search(self): return self._L().jb_engine_get_tree_search(self._h())
     def set_alpha(self, f): F.check(self._L().jb_engine_set_alpha(self._h(), float(f)))
     def get_alpha(self): return self._L().jb_engine_get_alpha(self._h())
     def set_beta(self, f): F.check(self._L().jb_engine_set_beta(self._h(), float(f)))
@@ -257,6 +262,27 @@ class Engine:
         F.check(self._L.jb_engine_tree_index(self._h, voice, kind, state_index, label.encode(),
                                              C.byref(ts), C.byref(pi)))
         return (None if ts.value < 0 else ts.value, pi.value)
+
+    @property
+    def device_searched_labels(self) -> int:
+        """Labels whose trees were searched on a device for this engine so far (0 in host mode)."""
+        return int(self._L.jb_engine_device_searched_labels(self._h))
+
+    def tree_search(self, labels: Sequence[str], device: int = -1, host: bool = False):
+        """jb_tree_search_batch (host=True: jb_tree_search_flat_host, no GPU): (tree_state, pdf_index, gv_on) with
+        the first two int32 [n_labels][num_voices][1 + num_streams][num_states] -- what tree_index returns for kind k
+        and state index 2 + s, tree_state -1 for None -- and gv_on uint8 [n_labels]."""
+        n = len(labels)
+        shape = (n, self.num_voices, 1 + min(self.num_streams, F.MAX_STREAM), self.num_states)
+        ts, pi = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+        gv = np.zeros(n, np.uint8)
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        args = (ts.ctypes.data_as(i32p), pi.ctypes.data_as(i32p), gv.ctypes.data_as(u8p))
+        if host:
+            F.check(self._L.jb_tree_search_flat_host(self._h, _lines(labels), n, *args))
+        else:
+            F.check(self._L.jb_tree_search_batch(self._h, _lines(labels), n, device, *args))
+        return ts, pi, gv
 
     def voice_info(self) -> VoiceInfo:
         d = self._L.jb_engine_voice_desc(self._h).contents

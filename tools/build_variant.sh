@@ -12,7 +12,7 @@ pids=()
 rm -f $out/obj/*.o
 for src in jbonsai_amd/csrc/*.hip jbonsai_amd/csrc/*.cpp; do # every source of the library, as jbonsai_amd/csrc/build.sh lists them
   f=$(basename $src)
-  $HIPCC $FLAGS -x hip -c $src -o $out/obj/${f%.*}.o &
+  $HIPCC $FLAGS -x hip -c $src -o $out/obj/$f.o & # (the whole name: jb_treesearch.hip and .cpp are two objects)
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
