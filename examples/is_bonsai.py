@@ -1,11 +1,14 @@
 """The reference's `examples/is-bonsai` on the GPU path: full-context labels -> PCM -> 16-bit WAV.
 
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak]]
+                                 [--format f32|s16|s24|ulaw|alaw [--dither]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
 With --loudness the audio is normalized on the GPU to that integrated loudness (BS.1770-4), its sample peak kept at or
 under --ceiling (dBFS, default 0); with --true-peak the ceiling bounds the true peak (dBTP, BS.1770-4 Annex 2) instead.
+With --format the samples are converted to that format on the GPU (ulaw and alaw at 8 kHz, the telephony rate; --dither:
+TPDF dither for s16 and s24) and the WAV file carries them as they are.
 """
 import argparse
 import os
@@ -22,6 +25,9 @@ ap.add_argument("out", nargs="?", default="is-bonsai.wav")
 ap.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="target integrated loudness")
 ap.add_argument("--ceiling", type=float, default=0.0, metavar="DBFS", help="sample-peak ceiling (with --loudness)")
 ap.add_argument("--true-peak", action="store_true", help="the ceiling bounds the true peak (dBTP), not the sample peak")
+ap.add_argument("--format", choices=["f32", "s16", "s24", "ulaw", "alaw"], default=None,
+                help="sample format of the WAV file, converted on the GPU")
+ap.add_argument("--dither", action="store_true", help="TPDF dither (with --format s16 or s24)")
 args = ap.parse_args()
 voice, out = args.voice, args.out
 
@@ -30,6 +36,14 @@ if args.loudness is not None:
     engine.condition.set_loudness_target(args.loudness)
     engine.condition.set_peak_ceiling(args.ceiling)
     engine.condition.set_peak_mode(J.PEAK_TRUE if args.true_peak else J.PEAK_SAMPLE)
+if args.format is not None:
+    if args.format in ("ulaw", "alaw"):
+        engine.condition.set_output_sampling_frequency(8000)
+    hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
+    data = engine.synthesize_formatted(SAMPLE_SENTENCE_2, args.format, dither=args.dither, seed=1)
+    J.write_wav_formatted(out, data, hz, args.format)
+    print(f"wrote {out}: {len(data)} bytes of {args.format} at {hz} Hz")
+    sys.exit(0)
 speech = engine.synthesize(SAMPLE_SENTENCE_2)
 print(f"The synthesized voice has {len(speech)} samples in total.")
 if args.loudness is not None:

@@ -106,6 +106,23 @@ typedef struct jb_flac_opts {
     uint32_t reserved[2];
 } jb_flac_opts;
 
+/* Output sample format (jb_batch_set_format, jb_format_pcm_batch, jb_format_pcm_host, jb_synthesize*_formatted; see
+ * "Output sample formats" below).  dither: JB_DITHER_TPDF with JB_FMT_S16 and JB_FMT_S24 only; seed: the dither's,
+ * one per batch.  An unknown format or dither, or dither with another format: JB_ERR_INVALID before any device is
+ * touched. */
+#define JB_FMT_F32 1u  /* float32 in +-1.0, 4 bytes little-endian */
+#define JB_FMT_S16 2u  /* 16-bit PCM, 2 bytes */
+#define JB_FMT_S24 3u  /* 24-bit PCM, 3 bytes packed, little-endian */
+#define JB_FMT_ULAW 4u /* G.711 mu-law, 1 byte */
+#define JB_FMT_ALAW 5u /* G.711 A-law, 1 byte */
+#define JB_DITHER_NONE 0u
+#define JB_DITHER_TPDF 1u
+typedef struct jb_format_opts {
+    uint32_t format; /* JB_FMT_* */
+    uint32_t dither; /* JB_DITHER_* */
+    uint64_t seed;
+} jb_format_opts;
+
 typedef struct jb_batch_opts {
     int32_t device;         /* HIP device ordinal; -1 = current */
     uint32_t flags;         /* JB_BATCH_* */
@@ -361,6 +378,20 @@ int jb_batch_flac_size(jb_batch *b, size_t utt, size_t *n_bytes);
 int jb_batch_read_flac(jb_batch *b, size_t utt, uint8_t *dst, size_t cap);
 /* Every stream: dst[u] must hold jb_batch_flac_size(b, u) bytes (one device-to-host copy for the batch). */
 int jb_batch_read_flac_all(jb_batch *b, uint8_t *const *dst);
+/* New.  Output sample format (see "Output sample formats" below): the run also writes each utterance's final f64
+ * PCM -- what jb_batch_read_pcm hands out, after the output rate and the loudness target -- as bytes of opts->format,
+ * on the device.  Only before the batch's first run, on a batch that is neither JB_BATCH_PCM_I16 (the stage reads
+ * f64; FLAC, which needs the 16-bit batch, is therefore never in the same batch) nor JB_BATCH_MLPG_ONLY; otherwise
+ * JB_ERR_INVALID.  The f64 read entries keep working.  Without a call nothing runs and nothing is allocated. */
+int jb_batch_set_format(jb_batch *b, const jb_format_opts *opts);
+/* Bytes of utterance utt in the format: jb_batch_num_samples x jb_format_bytes_per_sample.  No format or no such
+ * utterance: JB_ERR_INVALID. */
+int jb_batch_formatted_size(jb_batch *b, size_t utt, size_t *n_bytes);
+/* The bytes of utterance utt into dst; waits for the run like the read entries; cap below jb_batch_formatted_size:
+ * JB_ERR_BUFFER. */
+int jb_batch_read_formatted(jb_batch *b, size_t utt, uint8_t *dst, size_t cap);
+/* Every utterance: dst[u] must hold jb_batch_formatted_size(b, u) bytes (one device-to-host copy for the batch). */
+int jb_batch_read_formatted_all(jb_batch *b, uint8_t *const *dst);
 void jb_batch_free(jb_batch *b);
 
 /* One-shot convenience: create + run + read + free.  pcm[i] must hold
@@ -504,6 +535,32 @@ int jb_true_peak_pcm_batch(const double *const *in, const size_t *n_in, size_t n
 int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, uint32_t hz,
                              const jb_flac_opts *opts, int32_t device, uint8_t **out, size_t *n_out);
 void jb_flac_free(uint8_t *p);
+
+/* ---- Output sample formats (new: the reference hands out f64 and its examples clamp and truncate to 16 bits) -------
+ * v is the final f64 sample in 16-bit scale (what jb_batch_read_pcm hands out).
+ * - JB_FMT_F32: (float)(v * 2^-15); the product is exact, one round-to-nearest-even f64 -> f32; no clamp.
+ * - JB_FMT_S16: q(v) in [-32768, 32767].  JB_FMT_S24: q(256 v) in [-8388608, 8388607], little-endian, packed.
+ * - JB_FMT_ULAW / JB_FMT_ALAW: G.711 of s = q(v) at 16 bits without dither, with the semantics of the common C
+ *   implementation (14-bit mu-law with the clip at 8159 and the bias 33, 13-bit A-law): mu-law never emits 0x7F.
+ * - q(x) without dither is the 16-bit sink's rule: fmin to the upper bound, fmax to the lower, truncate toward zero;
+ *   JB_FMT_S16 is then bit for bit what a JB_BATCH_PCM_I16 batch hands out, and S24 truncated by 256 equals S16.
+ *   With JB_DITHER_TPDF: floor((x + d) + 0.5) (two f64 additions in that order), then the clamp.
+ * - d = ((double)(r >> 32) - (double)(r & 0xffffffff)) * 2^-32, triangular in (-1, 1) LSB; r = mix(mix(seed) ^ k),
+ *   k the sample's 0-based index within its utterance's output, mix the splitmix64 finaliser (z += 0x9E3779B97F4A7C15;
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31).  An utterance's
+ *   bytes depend on its samples, the options and the seed, not on the batch, its position in it or redo rounds.
+ * Not covered: the generator (it hands out f64), the _multi entries and jb_gather_pcm, per-utterance formats within
+ * one batch, S32, U8 and big-endian, noise shaping (a serial nonlinear recursion), dither on the fused 16-bit sink. */
+size_t jb_format_bytes_per_sample(uint32_t format); /* 0 for an unknown format */
+/* The stage on PCM the caller holds (jb_resample_pcm_batch's twin): out[u] = the bytes of in[u], n_bytes[u] of them,
+ * library-owned (jb_format_free each), on `device` (-1 = current). */
+int jb_format_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_format_opts *opts,
+                        int32_t device, uint8_t **out, size_t *n_bytes);
+void jb_format_free(uint8_t *p);
+/* The same rules in plain C++ on the host; no GPU is touched.  out must hold n x jb_format_bytes_per_sample bytes
+ * (cap below that: JB_ERR_BUFFER).  The same samples and options give the same bytes from both seams and from the
+ * batch path. */
+int jb_format_pcm_host(const double *in, size_t n, const jb_format_opts *opts, uint8_t *out, size_t cap);
 
 /* ---- multi-GPU (SURVEY 8b "device_ids[] / n_devices", 8e) ----------------------------------
  * Utterances are independent, so a batch shards over the GPUs of a node with no data-path
@@ -673,6 +730,11 @@ void jb_pcm_free(double *pcm);
 int jb_write_wav_i16(const char *path, const int16_t *pcm, size_t n_samples, uint32_t sampling_frequency);
 /* Same from f64 samples, converting like jb's i16 sink: value.min(32767).max(-32768) as i16. */
 int jb_write_wav_f64(const char *path, const double *pcm, size_t n_samples, uint32_t sampling_frequency);
+/* Mono RIFF/WAVE of formatted bytes (n_samples x jb_format_bytes_per_sample of them): format tag 1 for JB_FMT_S16 and
+ * _S24, 3 for _F32, 7 for _ULAW, 6 for _ALAW; the non-PCM tags carry cbSize = 0 and a fact chunk; a data chunk of odd
+ * length is padded. */
+int jb_write_wav_formatted(const char *path, const uint8_t *bytes, size_t n_samples, uint32_t sampling_frequency,
+                           uint32_t format);
 
 /* Batched synthesize: utterance u has lines [line_off[u], line_off[u+1]).  New
  * entry (the reference is single-utterance); a Rust `Engine::synthesize_batch`
@@ -710,6 +772,18 @@ int jb_synthesize_batch_flac(const jb_engine *e, const char *const *label_lines,
 int jb_synthesize_batch_each_flac(const jb_engine *const *engines, const char *const *label_lines,
                                   const size_t *line_off, size_t n_utts, int32_t device, const jb_flac_opts *opts,
                                   uint8_t **flac, size_t *n_bytes);
+/* New.  Formatted forms of jb_synthesize (one utterance, current device), jb_synthesize_batch and
+ * jb_synthesize_batch_each: bytes[u] is what the f64 entry returns (each engine's output rate, loudness target,
+ * ceiling and peak mode honoured the same way) in opts->format, n_bytes[u] bytes, library-owned (jb_format_free
+ * each). */
+int jb_synthesize_formatted(const jb_engine *e, const char *const *label_lines, size_t n_lines,
+                            const jb_format_opts *opts, uint8_t **bytes, size_t *n_bytes);
+int jb_synthesize_batch_formatted(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_format_opts *opts, uint8_t **bytes,
+                                  size_t *n_bytes);
+int jb_synthesize_batch_each_formatted(const jb_engine *const *engines, const char *const *label_lines,
+                                       const size_t *line_off, size_t n_utts, int32_t device,
+                                       const jb_format_opts *opts, uint8_t **bytes, size_t *n_bytes);
 /* The same two over a device list: the utterances are split by LPT on their label counts (the frame
  * counts are known only after the front half), one host thread per device runs jb_synthesize_batch's
  * path on its share (front half on that thread's workers, GPU work on that device). */
@@ -839,6 +913,8 @@ JB_LAYOUT_ASSERT(sizeof(jb_utt_voc) == 24 && offsetof(jb_utt_voc, beta) == 8 && 
                  "jb_utt_voc");
 JB_LAYOUT_ASSERT(sizeof(jb_flac_opts) == 16 && offsetof(jb_flac_opts, max_lpc_order) == 4 &&
                      offsetof(jb_flac_opts, reserved) == 8, "jb_flac_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_format_opts) == 16 && offsetof(jb_format_opts, dither) == 4 &&
+                     offsetof(jb_format_opts, seed) == 8, "jb_format_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_loudness_report) == 40 && offsetof(jb_loudness_report, gain_db) == 24 &&
                      offsetof(jb_loudness_report, peak_mode) == 32 && offsetof(jb_loudness_report, oversampling) == 36,
                  "jb_loudness_report");

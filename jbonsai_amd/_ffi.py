@@ -34,6 +34,9 @@ BATCH_NO_EXC_TABLE = 512
 BATCH_INVARIANT = 1024
 PEAK_SAMPLE = 0
 PEAK_TRUE = 1
+FMT_F32, FMT_S16, FMT_S24, FMT_ULAW, FMT_ALAW = 1, 2, 3, 4, 5
+DITHER_NONE, DITHER_TPDF = 0, 1
+FORMATS = {"f32": FMT_F32, "s16": FMT_S16, "s24": FMT_S24, "ulaw": FMT_ULAW, "alaw": FMT_ALAW}
 SEARCH_HOST = 0
 SEARCH_AUTO = 1
 SEARCH_DEVICE = 2
@@ -150,6 +153,20 @@ def flac_opts(block_size: int = 0, max_lpc_order=None):
     return o
 
 
+class FormatOpts(C.Structure):
+    """jb_format_opts: the output sample format, its dither and the dither's seed."""
+    _fields_ = [("format", C.c_uint32), ("dither", C.c_uint32), ("seed", C.c_uint64)]
+
+
+def format_opts(fmt, dither=False, seed: int = 0):
+    """FormatOpts for a format ("f32", "s16", "s24", "ulaw", "alaw" or a JB_FMT_* value), TPDF dither or none."""
+    o = FormatOpts()
+    o.format = FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+    o.dither = int(dither)
+    o.seed = int(seed) & (2 ** 64 - 1)
+    return o
+
+
 class LoudnessReport(C.Structure):
     """jb_loudness_report: what a run measured and applied for one utterance."""
     _fields_ = [("lufs", C.c_double), ("sample_peak_dbfs", C.c_double), ("true_peak_dbtp", C.c_double),
@@ -201,6 +218,10 @@ SYMBOLS = [
     "jb_engine_set_peak_mode", "jb_engine_get_peak_mode",
     "jb_engine_set_tree_search", "jb_engine_get_tree_search", "jb_engine_device_searched_labels",
     "jb_tree_search_batch", "jb_tree_search_flat_host",
+    "jb_format_bytes_per_sample", "jb_batch_set_format", "jb_batch_formatted_size", "jb_batch_read_formatted",
+    "jb_batch_read_formatted_all", "jb_format_pcm_batch", "jb_format_pcm_host", "jb_format_free",
+    "jb_synthesize_formatted", "jb_synthesize_batch_formatted", "jb_synthesize_batch_each_formatted",
+    "jb_write_wav_formatted",
 ]
 
 
@@ -355,6 +376,23 @@ def lib():
                                            C.POINTER(u8p), C.POINTER(sz)]
     L.jb_synthesize_batch_each_flac.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
                                                 fop, C.POINTER(u8p), C.POINTER(sz)]
+    mop = C.POINTER(FormatOpts)
+    L.jb_format_bytes_per_sample.argtypes = [C.c_uint32]
+    L.jb_format_bytes_per_sample.restype = sz
+    L.jb_batch_set_format.argtypes = [vp, mop]
+    L.jb_batch_formatted_size.argtypes = [vp, sz, C.POINTER(sz)]
+    L.jb_batch_read_formatted.argtypes = [vp, sz, vp, sz]
+    L.jb_batch_read_formatted_all.argtypes = [vp, C.POINTER(vp)]
+    L.jb_format_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, mop, C.c_int32, C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_format_pcm_host.argtypes = [vp, sz, mop, vp, sz]
+    L.jb_format_free.argtypes = [u8p]
+    L.jb_format_free.restype = None
+    L.jb_synthesize_formatted.argtypes = [vp, C.POINTER(C.c_char_p), sz, mop, C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_synthesize_batch_formatted.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, mop,
+                                                C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_synthesize_batch_each_formatted.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz,
+                                                     C.c_int32, mop, C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_write_wav_formatted.argtypes = [C.c_char_p, vp, sz, C.c_uint32, C.c_uint32]
     L.jb_write_wav_i16.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     L.jb_write_wav_f64.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     _lib = L
@@ -469,6 +507,59 @@ def flac_encode(pcms, hz: int, block_size: int = 0, max_lpc_order=None, device: 
     opts = flac_opts(block_size, max_lpc_order)
     check(L.jb_flac_encode_pcm_batch(ins, nin, n, hz, C.byref(opts), device, bufs, ns))
     return take_flac(L, bufs, ns, n)
+
+
+def take_formatted(L, bufs, ns, n):
+    """bytes of n library-owned formatted outputs, each released with jb_format_free."""
+    out = []
+    for u in range(n):
+        out.append(C.string_at(bufs[u], ns[u]) if ns[u] else b"")
+        if bufs[u]:
+            L.jb_format_free(bufs[u])
+    return out
+
+
+def format_pcm(pcms, fmt, dither=False, seed: int = 0, device: int = -1):
+    """jb_format_pcm_batch: the bytes of each float64 array of `pcms` (or of one array) in the sample format, on the
+    GPU."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
+    n = len(arrs)
+    L = lib()
+    dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    opts = format_opts(fmt, dither, seed)
+    check(L.jb_format_pcm_batch(ins, nin, n, C.byref(opts), device, bufs, ns))
+    res = take_formatted(L, bufs, ns, n)
+    return res[0] if single else res
+
+
+def format_pcm_host(pcm, fmt, dither=False, seed: int = 0) -> bytes:
+    """jb_format_pcm_host: the same rules in plain C++ on the host (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    opts = format_opts(fmt, dither, seed)
+    L = lib()
+    out = np.empty(max(1, a.size * L.jb_format_bytes_per_sample(opts.format)), dtype=np.uint8)
+    check(L.jb_format_pcm_host(a.ctypes.data, a.size, C.byref(opts), out.ctypes.data, out.size))
+    return out[:a.size * L.jb_format_bytes_per_sample(opts.format)].tobytes()
+
+
+def write_wav_formatted(path, data: bytes, sampling_frequency: int, fmt) -> None:
+    """jb_write_wav_formatted: a mono WAV file of formatted bytes (format tag 1, 3, 7 or 6 by the format)."""
+    f = FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+    L = lib()
+    nb = L.jb_format_bytes_per_sample(f)
+    if nb and len(data) % nb:
+        raise ValueError("the bytes are no whole number of samples")
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    check(L.jb_write_wav_formatted(str(path).encode(), C.cast(buf, C.c_void_p), len(data) // nb if nb else 0,
+                                   sampling_frequency, f))
 
 
 def resample(pcms, in_hz: int, out_hz: int, device: int = -1):

@@ -419,6 +419,34 @@ class Batch:
         F.check(self._L.jb_batch_read_flac_all(self._h, arr))
         return [bytes(b[:n]) for b, n in zip(bufs, ns)]
 
+    def set_format(self, fmt, dither=False, seed: int = 0):
+        """jb_batch_set_format: the run also writes each utterance's final f64 PCM as bytes of a sample format --
+        "f32", "s16", "s24", "ulaw" or "alaw"; dither=True: TPDF (s16 and s24) with `seed` -- on the GPU.  An f64
+        batch (not pcm_i16, not mlpg_only), before the first run only."""
+        opts = F.format_opts(fmt, dither, seed)
+        F.check(self._L.jb_batch_set_format(self._h, C.byref(opts)))
+
+    def formatted(self, i) -> bytes:
+        """Utterance i's bytes in the batch's sample format (jb_batch_formatted_size + jb_batch_read_formatted)."""
+        n = C.c_size_t()
+        F.check(self._L.jb_batch_formatted_size(self._h, i, C.byref(n)))
+        buf = np.empty(max(1, n.value), dtype=np.uint8)
+        F.check(self._L.jb_batch_read_formatted(self._h, i, buf.ctypes.data, n.value))
+        return buf[:n.value].tobytes()
+
+    def formatted_all(self) -> List[bytes]:
+        """Every utterance's formatted bytes through one device-to-host copy (jb_batch_read_formatted_all)."""
+        B = len(self)
+        ns = []
+        for i in range(B):
+            n = C.c_size_t()
+            F.check(self._L.jb_batch_formatted_size(self._h, i, C.byref(n)))
+            ns.append(n.value)
+        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
+        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
+        F.check(self._L.jb_batch_read_formatted_all(self._h, arr))
+        return [b[:n].tobytes() for b, n in zip(bufs, ns)]
+
     def output_rate(self, i) -> int:
         """Rate of utterance i's PCM as the read entries hand it out (the voice's rate when native)."""
         return self._L.jb_batch_output_rate(self._h, i)

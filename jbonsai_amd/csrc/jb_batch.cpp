@@ -2621,6 +2621,59 @@ int jb_batch_read_flac_all(jb_batch *hb, uint8_t *const *dst)
     return JB_OK;
 }
 
+int jb_batch_set_format(jb_batch *hb, const jb_format_opts *opts)
+{
+    if (!hb)
+        return JB_ERR_INVALID;
+    return ((Batch *)hb)->out.set_format(opts);
+}
+
+int jb_batch_formatted_size(jb_batch *hb, size_t utt, size_t *n_bytes)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !n_bytes || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    return b->out.format_size(utt, n_bytes);
+}
+
+int jb_batch_read_formatted(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    size_t nb = 0;
+    int rc = b->out.format_size(utt, &nb);
+    if (rc)
+        return rc;
+    if (cap < nb) {
+        jb::set_error("jb_batch_read_formatted: the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (!dst && nb)
+        return JB_ERR_INVALID;
+    return b->out.read_formatted(utt, dst);
+}
+
+int jb_batch_read_formatted_all(jb_batch *hb, uint8_t *const *dst)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || (!dst && b->B))
+        return JB_ERR_INVALID;
+    std::unique_ptr<uint8_t[]> host;
+    int rc = b->out.read_formatted_all(&host);
+    if (rc)
+        return rc;
+    for (size_t u = 0; u < (size_t)b->B; u++)
+        if (!dst[u] && b->out.format_place(u).bytes)
+            return JB_ERR_INVALID;
+    for (size_t u = 0; u < (size_t)b->B; u++) {
+        const jb::OutFmtUtt &w = b->out.format_place(u);
+        if (w.bytes)
+            memcpy(dst[u], host.get() + w.off, (size_t)w.bytes);
+    }
+    return JB_OK;
+}
+
 int jb_batch_read_pcm_native(jb_batch *hb, size_t i, double *dst, size_t cap)
 {
     Batch *b = (Batch *)hb;

@@ -1387,7 +1387,8 @@ int jb_write_wav_f64(const char *path, const double *pcm, size_t n, uint32_t fs)
 // elem = 8: f64 PCM (Engine::synthesize's Vec<f64>); elem = 2: the fused 16-bit sink
 int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                               int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads,
-                              const jb_engine *const *each, bool flac, const jb_flac_opts *flac_opts)
+                              const jb_engine *const *each, bool flac, const jb_flac_opts *flac_opts,
+                              const jb_format_opts *fmt_opts)
 {
     auto eng = [&](size_t u) { return CENG(each ? each[u] : e); }; // the engine of utterance u
     if (!e || !pcm || !n_samples || (n_utts && !line_off))
@@ -1576,6 +1577,8 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             return rc;
         if (flac && (rc = b->out.set_flac(flac_opts)))
             return rc;
+        if (fmt_opts && (rc = b->out.set_format(fmt_opts)))
+            return rc;
         rc = b->run(false);
         t_create += ms(t0, now());
         return rc;
@@ -1610,6 +1613,24 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             t_d2h += ms(t0, now());
             return JB_OK;
         }
+        if (fmt_opts) {
+            // the used bytes of the format slab in one copy, then each utterance's share
+            std::unique_ptr<uint8_t[]> host;
+            if ((rc = b->out.read_formatted_all(&host)))
+                return rc;
+            for (size_t u = lo; u < hi; u++) {
+                const jb::OutFmtUtt &w = b->out.format_place(u - lo);
+                if (!(pcm[u] = malloc(std::max<size_t>((size_t)w.bytes, 1)))) {
+                    jb::set_error("out of host memory");
+                    return JB_ERR_INVALID;
+                }
+                memcpy(pcm[u], host.get() + w.off, (size_t)w.bytes);
+                n_samples[u] = (size_t)w.bytes;
+            }
+            batches[g].reset();
+            t_d2h += ms(t0, now());
+            return JB_OK;
+        }
         for (size_t u = lo; u < hi; u++) {
             const size_t ns = b->out.samples(u - lo);
             n_samples[u] = ns;
@@ -1639,7 +1660,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
     };
     // f64 in groups (JB_SYNTH_GROUPS only): all groups' GPU work first, then the read-backs, so that no
     // read-back runs beside kernels
-    const bool d2h_last = elem == 8;
+    const bool d2h_last = elem == 8 && !fmt_opts;
 
     int rc = JB_OK;
     if (ngroups == 1) {
@@ -1778,7 +1799,8 @@ static int check_engines(const jb_engine *const *engines, size_t n)
 
 static int synthesize_each(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
                            size_t n_utts, int32_t device, size_t elem, void **pcm, size_t *n_samples,
-                           bool flac = false, const jb_flac_opts *flac_opts = nullptr)
+                           bool flac = false, const jb_flac_opts *flac_opts = nullptr,
+                           const jb_format_opts *fmt_opts = nullptr)
 {
     if (!pcm || !n_samples || (n_utts && !line_off))
         return JB_ERR_INVALID;
@@ -1788,7 +1810,7 @@ static int synthesize_each(const jb_engine *const *engines, const char *const *l
     if (rc)
         return rc;
     return jb::synthesize_batch_impl(engines[0], lines, line_off, n_utts, device, elem, pcm, n_samples, 0, engines,
-                                     flac, flac_opts);
+                                     flac, flac_opts, fmt_opts);
 }
 
 extern "C" {
@@ -1833,6 +1855,45 @@ int jb_synthesize_flac(const jb_engine *e, const char *const *lines, size_t n, c
         return JB_ERR_INVALID;
     size_t off[2] = {0, n};
     return jb_synthesize_batch_flac(e, lines, off, 1, -1, opts, flac, n_bytes);
+}
+
+static int check_format_entry(const jb_format_opts *opts, const char *who)
+{
+    if (!opts) {
+        jb::set_error(std::string(who) + ": opts is NULL");
+        return JB_ERR_INVALID;
+    }
+    return jb::format_check_opts(opts->format, opts->dither, who);
+}
+
+int jb_synthesize_batch_formatted(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                  int32_t device, const jb_format_opts *opts, uint8_t **bytes, size_t *n_bytes)
+{
+    int rc = check_format_entry(opts, "jb_synthesize_batch_formatted");
+    if (rc)
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(double), (void **)bytes, n_bytes, 0,
+                                     nullptr, false, nullptr, opts);
+}
+
+int jb_synthesize_batch_each_formatted(const jb_engine *const *engines, const char *const *lines,
+                                       const size_t *line_off, size_t n_utts, int32_t device,
+                                       const jb_format_opts *opts, uint8_t **bytes, size_t *n_bytes)
+{
+    int rc = check_format_entry(opts, "jb_synthesize_batch_each_formatted");
+    if (rc)
+        return rc;
+    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(double), (void **)bytes, n_bytes, false,
+                           nullptr, opts);
+}
+
+int jb_synthesize_formatted(const jb_engine *e, const char *const *lines, size_t n, const jb_format_opts *opts,
+                            uint8_t **bytes, size_t *n_bytes)
+{
+    if (!bytes || !n_bytes)
+        return JB_ERR_INVALID;
+    size_t off[2] = {0, n};
+    return jb_synthesize_batch_formatted(e, lines, off, 1, -1, opts, bytes, n_bytes);
 }
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)

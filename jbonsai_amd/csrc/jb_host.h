@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/jbonsai_amd.h"
 #include "jb_device.h"
+#include "jb_format.h"
 #include "jb_output.h"
 
 #include <map>
@@ -32,11 +33,12 @@ void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE
 // jb_synthesize_batch[_i16] on one device (jb_engine.cpp); host_threads = 0: default front-half thread count;
 // each != null (jb_synthesize_batch_each[_i16], engines checked by the caller): utterance u under each[u]'s Condition,
 // e = each[0] for what the engines share; flac (elem 2): pcm[u] / n_samples[u] receive utterance u's FLAC stream
-// and its byte count instead (jb_synthesize*_flac)
+// and its byte count instead (jb_synthesize*_flac); fmt_opts (elem 8): its bytes in that sample format and their
+// count (jb_synthesize*_formatted)
 int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                           int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0,
                           const jb_engine *const *each = nullptr, bool flac = false,
-                          const jb_flac_opts *flac_opts = nullptr);
+                          const jb_flac_opts *flac_opts = nullptr, const jb_format_opts *fmt_opts = nullptr);
 // A stream / a device block from the per-device pools that batches draw from (jb_batch.cpp), for work outside a
 // batch; *got is the block's pooled size, which pooled_block_free takes back
 hipError_t pooled_stream_acquire(int device, hipStream_t *st);
@@ -172,6 +174,10 @@ hipError_t launch_flac_pack(const FlacParams &p, const FlacUtt *utts, uint32_t n
                             uint32_t n_frames, const uint32_t *fsize, uint64_t *foff, FlacOut *out, uint64_t *total,
                             uint8_t *dst, hipStream_t stream);
 
+// Output sample formats (jb_format.hip; the rules and FormatUtt: jb_format.h): utts_dev[0..n) of `tiles` tiles in all
+hipError_t launch_format(uint32_t format, uint32_t dither, uint64_t seed, const FormatUtt *utts_dev, uint32_t n,
+                         uint64_t tiles, hipStream_t stream);
+
 // Device-resident pdf tables of a voice set (jb_pdf_set) and an indexed batch source
 struct PdfSet {
     int device = -1;
@@ -235,7 +241,8 @@ struct DeviceScratch {
 
 struct Batch;
 // The stages behind the vocoder of one batch -- output rate (jb_batch_set_output_rate), loudness target
-// (jb_batch_set_loudness_target), FLAC (jb_batch_set_flac) -- and all their device state.  The setters record a
+// (jb_batch_set_loudness_target), FLAC (jb_batch_set_flac), sample format (jb_batch_set_format) -- and all their
+// device state.  The setters record a
 // request and plan again (jb_output.h); the first run carries the plan out (prepare); every run enqueues the chain
 // once behind the hand-off check, and finish_verify once more for the utterances its redo rounds rewrote.
 // Without a request the chain holds no device memory and enqueues nothing
@@ -246,6 +253,7 @@ struct OutputChain {
     int set_loudness(const double *target, const double *ceiling, size_t n); // n == 1 or B entries each
     int set_peak_mode(const uint32_t *mode, size_t n);                       // n == 1 or B entries; needs no target
     int set_flac(const jb_flac_opts *opts);
+    int set_format(const jb_format_opts *opts); // an f64 batch only
     void init();   // Batch::create: the slabs the batch was made with, the plan of no request
     int prepare(); // at the first run: every slab, table and list of the plan; points the vocoder at its slab
     // only: [B] 1 = the utterances a redo rewrote: their part of every stage again (the FLAC pack: every stream),
@@ -269,12 +277,20 @@ struct OutputChain {
     int read_flac(const FlacOut &o, uint8_t *dst);
     // every stream's size and place, and the compact slab's used bytes in one copy
     int read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_t[]> *host);
+    // the formatted bytes: utterance u's count (known once a format is set), its bytes, or the used part of the
+    // slab in one copy (utterance u at host + format_place(u).off)
+    int format_size(size_t u, size_t *n_bytes) const;
+    int read_formatted(size_t u, uint8_t *dst);
+    int read_formatted_all(std::unique_ptr<uint8_t[]> *host);
+    const OutFmtUtt &format_place(size_t u) const { return plan.fmt[u]; }
 
 private:
     Batch &b;
     OutPlan plan;
     std::vector<uint32_t> want_hz;             // [B] 0 = native; empty: no rate requested
     bool ln_on = false, flac_on = false;       // a loudness target / FLAC is requested
+    bool fmt_on = false;                       // a sample format is requested
+    jb_format_opts fmt_p{};
     std::vector<double> ln_target, ln_ceiling; // [B]
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
     FlacParams flac_p{};
@@ -305,11 +321,18 @@ private:
         uint64_t *foff = nullptr, *total = nullptr;
         FlacOut *res = nullptr;
     } fl;
+    struct { // sample format
+        std::vector<FormatUtt> utts;
+        FormatUtt *utts_dev = nullptr, *redo_dev = nullptr;
+        uint64_t tiles = 0;
+    } fm;
     void replan(); // host geometry and routing of the present requests
     int check_settable(const char *after_run) const;
     int prepare_resample();
     int prepare_loudness();
     int prepare_flac();
+    int prepare_format();
+    int format_ready() const;
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
     int flac_ready() const;
 };

@@ -60,6 +60,17 @@ OutPlan plan_output(const OutPlanIn &in)
     for (const OutWrite &w : {p.vocoder, p.converter, p.apply})
         if (w.slab != OutSlab::None && w.slab != OutSlab::V64 && w.slab != OutSlab::S16)
             p.alloc[(size_t)w.slab] = std::max<uint64_t>(w.slab == OutSlab::Voc64 ? p.native_total : p.total, 1);
+    // the format stage behind all of them: the final f64 to bytes, utterance after utterance on 16-byte boundaries
+    if (in.fmt_bytes && !p.final.i16) {
+        p.fmt_src = p.final.slab;
+        p.fmt.resize(in.B);
+        uint64_t bytes = 0;
+        for (size_t u = 0; u < in.B; u++) {
+            p.fmt[u] = {bytes, p.utt[u].n * in.fmt_bytes};
+            bytes += (p.fmt[u].bytes + 15) & ~(uint64_t)15;
+        }
+        p.alloc[(size_t)OutSlab::Fmt] = std::max<uint64_t>(bytes, 16);
+    }
     return p;
 }
 

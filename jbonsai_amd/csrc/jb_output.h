@@ -1,7 +1,8 @@
 #pragma once
 // jb_output.h -- the routing of the stages behind the vocoder (output rate, loudness, FLAC): which slab each stage
 // reads and writes, in f64 or in 16 bits, which slab the read entries hand out, and each utterance's output geometry,
-// decided from the batch's shape and the three requests alone (plan_output, jb_output.cpp).
+// decided from the batch's shape and the requests alone (plan_output, jb_output.cpp); with a sample format, the f64
+// slab the format stage reads and each utterance's place in its byte slab.
 // Plain C++17 without HIP: the plan is made and tested on any host; OutputChain (jb_host.h) carries it out.
 #include <stddef.h>
 #include <stdint.h>
@@ -19,9 +20,13 @@ enum class OutSlab : uint8_t {
     Conv64,  // f64 the converter writes
     Apply64, // f64 the loudness apply pass writes
     New16,   // 16-bit output longer than S16
+    Fmt,     // bytes the format stage writes
     Count
 };
-constexpr size_t out_slab_elem(OutSlab s) { return s == OutSlab::S16 || s == OutSlab::New16 ? 2 : 8; } // bytes
+constexpr size_t out_slab_elem(OutSlab s) // bytes
+{
+    return s == OutSlab::Fmt ? 1 : s == OutSlab::S16 || s == OutSlab::New16 ? 2 : 8;
+}
 
 // in_hz -> out_hz reduced by their gcd (rates above 0)
 void resample_ratio(uint32_t in_hz, uint32_t out_hz, uint64_t *L, uint64_t *M);
@@ -36,11 +41,16 @@ struct OutPlanIn {
     bool i16 = false;                     // JB_BATCH_PCM_I16
     const uint32_t *want_hz = nullptr;    // [B] requested rate, 0 or voice_hz = native; nullptr: none requested
     bool loudness = false, flac = false;
+    uint32_t fmt_bytes = 0;               // bytes per sample of the requested sample format; 0: none requested
 };
 
 struct OutUtt {
     uint32_t hz, L, M; // output rate = voice_hz L / M
     uint64_t n, off;   // samples and first sample in the slabs behind the converter (the native ones without it)
+};
+
+struct OutFmtUtt { // an utterance's place in the format slab
+    uint64_t off, bytes; // byte offset (16-byte aligned) and n * bytes per sample
 };
 
 struct OutWrite { // what a stage writes; slab None: the stage does not run
@@ -58,6 +68,8 @@ struct OutPlan {
     OutSlab flac = OutSlab::None;     // 16 bits FLAC encodes: the slab handed out
     OutWrite final;                   // what the PCM read entries hand out
     OutSlab native64 = OutSlab::None; // f64 at the voice's rate (jb_batch_read_pcm_native)
+    OutSlab fmt_src = OutSlab::None;  // f64 the format stage reads: what `final` names (None: no format, or no f64)
+    std::vector<OutFmtUtt> fmt;       // [B] with a format stage, else empty
     uint64_t alloc[(size_t)OutSlab::Count] = {}; // elements to allocate of each slab, at least 1 (0: none; V64 / S16 exist)
     bool normalize() const { return apply.slab != OutSlab::None; }
     bool active() const { return convert || normalize(); } // a stage rewrites the PCM behind the vocoder

@@ -1,7 +1,7 @@
 // jb_output_chain.cpp -- OutputChain (jb_host.h): the stages behind the vocoder of one batch.  The setters record a
 // request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() launches
-// k_resample, the loudness measurement and apply pass and the FLAC encoder and pack, in that order, on the
-// vocoder's stream.
+// k_resample, the loudness measurement and apply pass, the FLAC encoder and pack and the sample format, in that order,
+// on the vocoder's stream.
 #include "jb_host.h"
 
 #include <algorithm>
@@ -33,6 +33,7 @@ void OutputChain::replan()
     in.want_hz = want_hz.empty() ? nullptr : want_hz.data();
     in.loudness = ln_on;
     in.flac = flac_on;
+    in.fmt_bytes = fmt_on ? (uint32_t)format_bytes(fmt_p.format) : 0;
     plan = plan_output(in);
 }
 
@@ -132,6 +133,27 @@ int OutputChain::set_flac(const jb_flac_opts *opts)
     return JB_OK;
 }
 
+int OutputChain::set_format(const jb_format_opts *opts)
+{
+    if (!opts) {
+        set_error("jb_batch_set_format: opts is NULL");
+        return JB_ERR_INVALID;
+    }
+    int rc = format_check_opts(opts->format, opts->dither, "jb_batch_set_format");
+    if (rc)
+        return rc;
+    if ((rc = check_settable("jb_batch_set_format: the format is set before the batch's first run")))
+        return rc;
+    if (b.flags & JB_BATCH_PCM_I16) {
+        set_error("jb_batch_set_format: the format stage reads the f64 output (a batch without JB_BATCH_PCM_I16)");
+        return JB_ERR_INVALID;
+    }
+    fmt_p = *opts;
+    fmt_on = true;
+    replan();
+    return JB_OK;
+}
+
 // At the first run (a second one, or the step done again behind a resident-GV formation timeout, finds it done).
 // The vocoder is pointed at its slab last: a failure leaves the batch as it was created, its blocks the batch's own
 int OutputChain::prepare()
@@ -143,7 +165,8 @@ int OutputChain::prepare()
     for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
-    if ((rc = prepare_resample()) || (rc = prepare_loudness()) || (rc = prepare_flac()))
+    if ((rc = prepare_resample()) || (rc = prepare_loudness()) || (rc = prepare_flac()) ||
+        (rc = prepare_format()))
         return rc;
     if (plan.active()) {
         void *voc = slab[(size_t)plan.vocoder.slab];
@@ -293,9 +316,37 @@ int OutputChain::prepare_flac()
     return JB_OK;
 }
 
+// The utterance list: the final f64 of the plan in, each utterance's bytes at its 16-byte aligned place out
+int OutputChain::prepare_format()
+{
+    if (plan.fmt_src == OutSlab::None)
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    const double *src = (const double *)slab[(size_t)plan.fmt_src];
+    uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Fmt];
+    fm.utts.assign(B, FormatUtt{});
+    fm.tiles = 0;
+    for (size_t u = 0; u < B; u++) {
+        FormatUtt &w = fm.utts[u];
+        w.x = src + plan.utt[u].off;
+        w.y = dst + plan.fmt[u].off;
+        w.n = plan.utt[u].n;
+        w.ft0 = fm.tiles;
+        fm.tiles += (w.n + kFmtTile - 1) / kFmtTile;
+    }
+    int rc;
+    if ((rc = b.dalloc(&fm.utts_dev, B, false)) || (rc = b.dalloc(&fm.redo_dev, B, false)))
+        return rc;
+    hipError_t e;
+    if (B > 0 && (e = hipMemcpy(fm.utts_dev, fm.utts.data(), sizeof(FormatUtt) * B, hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_fail(e, "format work list");
+    return JB_OK;
+}
+
 int OutputChain::enqueue(const std::vector<uint8_t> *only)
 {
-    if (!ready || !(plan.active() || flac_on))
+    const bool fmt = plan.fmt_src != OutSlab::None;
+    if (!ready || !(plan.active() || flac_on || fmt))
         return JB_OK;
     const uint32_t B = (uint32_t)b.B;
     hipStream_t st = b.stream_voc;
@@ -303,6 +354,9 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const ResampleTile *tiles = rs.tiles_dev;
     const LoudnessUtt *utts = ln.utts_dev;
     const FlacWork *work = fl.work_dev;
+    const FormatUtt *futts = fm.utts_dev;
+    uint32_t n_futts = fmt ? B : 0;
+    uint64_t ft = fm.tiles;
     const uint32_t n_all_work = (uint32_t)fl.work.size();
     uint32_t n_tiles = (uint32_t)rs.tiles.size(), n_utts = B, n_work = n_all_work;
     uint64_t lt = ln.tiles, at = ln.atiles;
@@ -313,7 +367,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         std::vector<ResampleTile> rs_sub;
         std::vector<LoudnessUtt> ln_sub;
         std::vector<FlacWork> fl_sub;
-        lt = at = 0;
+        std::vector<FormatUtt> fm_sub;
+        lt = at = ft = 0;
         for (size_t u = 0; u < B; u++) {
             if (!(*only)[u])
                 continue;
@@ -327,6 +382,12 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
                 at += (w.n + kLnApplyTile - 1) / kLnApplyTile;
                 ln_sub.push_back(w);
             }
+            if (fmt) {
+                FormatUtt w = fm.utts[u];
+                w.ft0 = ft;
+                ft += (w.n + kFmtTile - 1) / kFmtTile;
+                fm_sub.push_back(w);
+            }
         }
         for (const FlacWork &w : fl.work)
             if ((*only)[w.utt])
@@ -334,17 +395,21 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         tiles = rs.redo_dev;
         utts = ln.redo_dev;
         work = fl.redo_dev;
+        futts = fm.redo_dev;
+        n_futts = (uint32_t)fm_sub.size();
         n_tiles = (uint32_t)rs_sub.size();
         n_utts = (uint32_t)ln_sub.size();
         n_work = (uint32_t)fl_sub.size();
-        if (!n_tiles && !n_utts && !n_work)
+        if (!n_tiles && !n_utts && !n_work && !n_futts)
             return JB_OK;
         if ((n_tiles && (e = hipMemcpy(rs.redo_dev, rs_sub.data(), sizeof(ResampleTile) * n_tiles,
                                        hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_utts && (e = hipMemcpy(ln.redo_dev, ln_sub.data(), sizeof(LoudnessUtt) * n_utts,
                                       hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_work && (e = hipMemcpy(fl.redo_dev, fl_sub.data(), sizeof(FlacWork) * n_work, hipMemcpyHostToDevice)) !=
-                           hipSuccess))
+                           hipSuccess) ||
+            (n_futts && (e = hipMemcpy(fm.redo_dev, fm_sub.data(), sizeof(FormatUtt) * n_futts,
+                                       hipMemcpyHostToDevice)) != hipSuccess))
             return hip_fail(e, "output chain(redo lists)");
     }
     // a run launches every stage of the plan; a redo those that have something to do again
@@ -362,6 +427,10 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
          (e = launch_flac_pack(flac_p, fl.utts_dev, B, fl.work_dev, n_all_work, fl.fsize, fl.foff, fl.res, fl.total,
                                fl.out, st)) != hipSuccess))
         return hip_fail(e, only ? "FLAC(redo)" : "FLAC");
+    // the sample format last: behind the apply pass, the converter or the hand-off check, whichever wrote last
+    if (fmt && (!only || n_futts) &&
+        (e = launch_format(fmt_p.format, fmt_p.dither, fmt_p.seed, futts, n_futts, ft, st)) != hipSuccess)
+        return hip_fail(e, only ? "k_format(redo)" : "k_format");
     if (only && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "output chain(redo)");
     return JB_OK;
@@ -414,6 +483,47 @@ int OutputChain::read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_
         return JB_ERR_INVALID;
     }
     return total ? b.read(fl.out, host->get(), (size_t)total, false) : JB_OK;
+}
+
+int OutputChain::format_ready() const
+{
+    return check_ready(fmt_on, "format: the batch has not run", "format: jb_batch_set_format was not called");
+}
+
+int OutputChain::format_size(size_t u, size_t *n_bytes) const
+{
+    if (!fmt_on) {
+        set_error("format: jb_batch_set_format was not called");
+        return JB_ERR_INVALID;
+    }
+    *n_bytes = (size_t)plan.fmt[u].bytes;
+    return JB_OK;
+}
+
+int OutputChain::read_formatted(size_t u, uint8_t *dst)
+{
+    int rc = format_ready();
+    if (rc)
+        return rc;
+    const OutFmtUtt &w = plan.fmt[u];
+    return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Fmt] + w.off, dst, (size_t)w.bytes) : b.sync();
+}
+
+int OutputChain::read_formatted_all(std::unique_ptr<uint8_t[]> *host)
+{
+    int rc = format_ready();
+    if (rc)
+        return rc;
+    uint64_t total = 0;
+    for (const OutFmtUtt &w : plan.fmt)
+        total = std::max<uint64_t>(total, w.off + w.bytes);
+    // one copy of the used bytes (not zero-filled first)
+    host->reset(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
+    if (!*host) {
+        set_error("out of host memory");
+        return JB_ERR_INVALID;
+    }
+    return total ? b.read(slab[(size_t)OutSlab::Fmt], host->get(), (size_t)total) : b.sync();
 }
 
 } // namespace jb

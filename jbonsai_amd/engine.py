@@ -390,6 +390,28 @@ class Engine:
         F.check(self._L.jb_synthesize_batch_flac(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
         return F.take_flac(self._L, bufs, ns, B)
 
+    def synthesize_formatted(self, labels: Sequence[str], fmt, dither=False, seed: int = 0) -> bytes:
+        """jb_synthesize_formatted: what synthesize(labels) returns as bytes of a sample format ("f32", "s16", "s24",
+        "ulaw", "alaw"; dither=True: TPDF with `seed`), formatted on the GPU."""
+        buf, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+        opts = F.format_opts(fmt, dither, seed)
+        F.check(self._L.jb_synthesize_formatted(self._h, _lines(labels), len(labels), C.byref(opts), C.byref(buf),
+                                                C.byref(n)))
+        return F.take_formatted(self._L, [buf], [n.value], 1)[0]
+
+    def synthesize_batch_formatted(self, utterances: Sequence[Sequence[str]], fmt, dither=False, seed: int = 0,
+                                   device: int = -1) -> List[bytes]:
+        """jb_synthesize_batch_formatted: the bytes of each utterance of synthesize_batch(...) in the format."""
+        flat = [l for u in utterances for l in u]
+        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+        B = len(utterances)
+        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+        bufs, ns = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))()
+        opts = F.format_opts(fmt, dither, seed)
+        F.check(self._L.jb_synthesize_batch_formatted(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs,
+                                                      ns))
+        return F.take_formatted(self._L, bufs, ns, B)
+
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
         F.check(self._L.jb_generator_new(self._h, _lines(labels), len(labels), C.byref(h)))
@@ -432,6 +454,24 @@ def synthesize_batch_each(engines: Sequence["Engine"], utterances: Sequence[Sequ
     fn = L.jb_synthesize_batch_each_i16 if i16 else L.jb_synthesize_batch_each
     F.check(fn(hs, _lines(flat), offs, B, device, pcm, ns))
     return _pcm_arrays(pcm, ns, B, i16, L.jb_pcm_i16_free if i16 else L.jb_pcm_free)
+
+
+def synthesize_batch_each_formatted(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]], fmt,
+                                    dither=False, seed: int = 0, device: int = -1) -> List[bytes]:
+    """jb_synthesize_batch_each_formatted: the bytes of synthesize_batch_each(...) in the sample format."""
+    if len(engines) != len(utterances):
+        raise ValueError("one engine per utterance")
+    B = len(utterances)
+    L = engines[0]._L if B and engines[0] is not None else F.lib()
+    _bind(L)
+    flat = [l for u in utterances for l in u]
+    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
+    bufs, ns = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))()
+    opts = F.format_opts(fmt, dither, seed)
+    F.check(L.jb_synthesize_batch_each_formatted(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
+    return F.take_formatted(L, bufs, ns, B)
 
 
 def synthesize_batch_each_flac(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]], device: int = -1,
