@@ -2382,14 +2382,15 @@ static hipError_t launch_mlpg_bw(const BatchDev &bd, const StreamDev &sd, int si
             dim3 gvgrid(sd.L, bd.B);
             if (sd.is_msd) {
                 if (gv_vt) {
-                    // L == 1: [frame][1] is [1][frame]; one lane per voiced run (the compacted system is block
-                    // diagonal: same bits as a sweep over the whole utterance)
-                    if (sd.L == 1 && bd.maxS > 0) {
+                    // L == 1: one lane per voiced run (the compacted system is block diagonal: same bits as a sweep
+                    // over the whole utterance).  Block diagonal BECAUSE every window that reaches a neighbour has
+                    // its inverse variance zeroed at an MSD boundary, which the first window never has (mod.rs:74):
+                    // a first window of more than one tap couples the runs, and the whole-utterance sweep takes it.
+                    // (bd.maxS > 0 wherever there is work: no other L == 1 case)
+                    if (sd.L == 1 && sd.win_width[0] == 1) {
                         dim3 rg((bd.maxS + 63) / 64, bd.B);
                         JB_DBG_SKIP_IF(128, hipLaunchKernelGGL(k_mlpg_fb_runs, rg, dim3(64), 0, stream, bd, sd, si));
-                    } else if (sd.L == 1)
-                        launch_fb(bd, sd, si, stream);
-                    else
+                    } else
                         hipLaunchKernelGGL((k_mlpg_solve3<false, false>), grid, block, 0, stream, bd, sd, si);
                     JB_DBG_SKIP_IF(32, hipLaunchKernelGGL(k_mlpg_gv_vt<false>, gvgrid, block, 0, stream, bd, sd, si));
                 } else {
