@@ -1,7 +1,7 @@
 """The reference's `examples/is-bonsai` on the GPU path: full-context labels -> PCM -> 16-bit WAV.
 
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak]]
-                                 [--format f32|s16|s24|ulaw|alaw [--dither]]
+                                 [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
@@ -9,6 +9,8 @@ With --loudness the audio is normalized on the GPU to that integrated loudness (
 under --ceiling (dBFS, default 0); with --true-peak the ceiling bounds the true peak (dBTP, BS.1770-4 Annex 2) instead.
 With --format the samples are converted to that format on the GPU (ulaw and alaw at 8 kHz, the telephony rate; --dither:
 TPDF dither for s16 and s24) and the WAV file carries them as they are.
+With --adpcm the audio is encoded as IMA ADPCM (WAV format tag 0x11, half a byte per sample) on the GPU, at --rate if
+given, with the block size that goes with the rate.
 """
 import argparse
 import os
@@ -28,6 +30,8 @@ ap.add_argument("--true-peak", action="store_true", help="the ceiling bounds the
 ap.add_argument("--format", choices=["f32", "s16", "s24", "ulaw", "alaw"], default=None,
                 help="sample format of the WAV file, converted on the GPU")
 ap.add_argument("--dither", action="store_true", help="TPDF dither (with --format s16 or s24)")
+ap.add_argument("--adpcm", action="store_true", help="IMA ADPCM (4-bit) WAV file, encoded on the GPU")
+ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm)")
 args = ap.parse_args()
 voice, out = args.voice, args.out
 
@@ -36,6 +40,14 @@ if args.loudness is not None:
     engine.condition.set_loudness_target(args.loudness)
     engine.condition.set_peak_ceiling(args.ceiling)
     engine.condition.set_peak_mode(J.PEAK_TRUE if args.true_peak else J.PEAK_SAMPLE)
+if args.adpcm:
+    if args.rate:
+        engine.condition.set_output_sampling_frequency(args.rate)
+    stream = engine.synthesize_adpcm(SAMPLE_SENTENCE_2)
+    stream.write_wav(out)
+    print(f"wrote {out}: {stream.n_samples} samples at {stream.hz} Hz in {len(stream.data)} bytes of IMA ADPCM "
+          f"(blocks of {stream.block_align}, {len(stream.data) / max(stream.n_samples, 1):.3f} bytes per sample)")
+    sys.exit(0)
 if args.format is not None:
     if args.format in ("ulaw", "alaw"):
         engine.condition.set_output_sampling_frequency(8000)

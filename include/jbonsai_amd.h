@@ -123,6 +123,15 @@ typedef struct jb_format_opts {
     uint64_t seed;
 } jb_format_opts;
 
+/* IMA ADPCM options (jb_batch_set_adpcm, jb_adpcm_encode_pcm_batch, jb_adpcm_encode_host, jb_synthesize*_adpcm; see
+ * "IMA ADPCM" below).  block_align 0 = by each utterance's output rate (256 below 22,050 Hz, 512 below 44,100 Hz, 1024
+ * otherwise: the Microsoft convention); otherwise a multiple of 4 in 32..8192; reserved 0.  Anything else:
+ * JB_ERR_INVALID before any device is touched. */
+typedef struct jb_adpcm_opts {
+    uint32_t block_align;
+    uint32_t reserved[3];
+} jb_adpcm_opts;
+
 typedef struct jb_batch_opts {
     int32_t device;         /* HIP device ordinal; -1 = current */
     uint32_t flags;         /* JB_BATCH_* */
@@ -392,6 +401,22 @@ int jb_batch_formatted_size(jb_batch *b, size_t utt, size_t *n_bytes);
 int jb_batch_read_formatted(jb_batch *b, size_t utt, uint8_t *dst, size_t cap);
 /* Every utterance: dst[u] must hold jb_batch_formatted_size(b, u) bytes (one device-to-host copy for the batch). */
 int jb_batch_read_formatted_all(jb_batch *b, uint8_t *const *dst);
+/* New.  IMA ADPCM output (see "IMA ADPCM" below): the run also encodes each utterance's final PCM -- what the PCM read
+ * entries hand out, after the output rate and the loudness target; the f64 of an f64 batch quantised by the 16-bit
+ * sink's rule, the 16-bit samples of a JB_BATCH_PCM_I16 batch -- as 4-bit WAV blocks, on the device.  Only before the
+ * batch's first run, on a batch that is not JB_BATCH_MLPG_ONLY; otherwise JB_ERR_INVALID.  Independent of FLAC and of
+ * the sample format: it may be requested with either.  The PCM read entries keep working.  Without a call nothing runs
+ * and nothing is allocated. */
+int jb_batch_set_adpcm(jb_batch *b, const jb_adpcm_opts *opts);
+/* Bytes of utterance utt's blocks (known from the geometry once the request is made) and its block size A.  No
+ * request or no such utterance: JB_ERR_INVALID. */
+int jb_batch_adpcm_size(jb_batch *b, size_t utt, size_t *n_bytes);
+int jb_batch_adpcm_block_align(jb_batch *b, size_t utt, uint32_t *block_align);
+/* The blocks of utterance utt into dst; waits for the run like the read entries; cap below jb_batch_adpcm_size:
+ * JB_ERR_BUFFER. */
+int jb_batch_read_adpcm(jb_batch *b, size_t utt, uint8_t *dst, size_t cap);
+/* Every utterance: dst[u] must hold jb_batch_adpcm_size(b, u) bytes (one device-to-host copy for the batch). */
+int jb_batch_read_adpcm_all(jb_batch *b, uint8_t *const *dst);
 void jb_batch_free(jb_batch *b);
 
 /* One-shot convenience: create + run + read + free.  pcm[i] must hold
@@ -561,6 +586,48 @@ void jb_format_free(uint8_t *p);
  * (cap below that: JB_ERR_BUFFER).  The same samples and options give the same bytes from both seams and from the
  * batch path. */
 int jb_format_pcm_host(const double *in, size_t n, const jb_format_opts *opts, uint8_t *out, size_t cap);
+
+/* ---- IMA ADPCM (new: the reference writes 16-bit WAV only; WAV format tag 0x0011, mono) --------------------------------
+ * Half a byte per sample at any rate.  A WAV ADPCM block carries its own predictor and step index, and here every
+ * block picks its start index from its own first samples instead of carrying it from the block before (as the serial
+ * encoders do), so blocks are independent: one GPU lane encodes one block.
+ * - Geometry: block size A bytes (jb_adpcm_opts); samples per block spb = 2 (A - 4) + 1; ceil(n / spb) blocks of A
+ *   bytes for n samples, 0 bytes for n = 0.  The last block is padded by repeating the last sample.
+ * - Input: s[k] = the 16-bit sink's rule on the final f64 (fmin to 32767, fmax to -32768, truncate toward zero; no
+ *   dither), or the 16-bit sample itself on a JB_BATCH_PCM_I16 batch; the two are equal.
+ * - Block header: bytes 0-1 the block's first sample b[0] (little-endian int16), byte 2 the start index i0, byte 3
+ *   zero.  i0 is the smallest i with STEP[i] >= d, d = floor((sum_{k=1..8} |b[k] - b[k-1]|) / 8), and 88 if none.
+ * - Each further sample b[k], from pred = b[0], idx = i0: step = STEP[idx]; diff = b[k] - pred; sign = diff < 0 ? 8 : 0;
+ *   diff = |diff|; delta = 0; vp = step >> 3; three times {if (diff >= step) set the bit (4, 2, 1), diff -= step,
+ *   vp += step; step >>= 1}; pred = clamp(pred -/+ vp to int16); idx = clamp(idx + IDX[delta], 0, 88);
+ *   code = delta | sign.  IDX = {-1, -1, -1, -1, 2, 4, 6, 8}; STEP is the standard 89-entry IMA table (7 .. 32767).
+ *   Byte 4 + j holds the code of sample 2j + 1 in its low nibble and that of sample 2j + 2 in its high nibble.  The
+ *   decoder builds the same vp from the code's bits (jb_adpcm_decode_host; any WAV player).
+ * - Determinism: a stream's bytes depend only on its samples, its rate and A, not on the batch, the utterance's
+ *   position in it, the entry point or redo rounds; JB_BATCH_INVARIANT output stays invariant.
+ * - Cost on 256 x 128 s (profiles/r14_adpcm.txt): 0.502 bytes per sample at A = 1024; the encoder takes 1.67 ms of
+ *   device time from the 16-bit slab and 4.19 ms from f64 (a 16-bit format pass of the same batch: 2.64 ms); run + read
+ *   of everything 292 ms at 48 kHz (16-bit PCM: 151 ms) and 140 ms at 8 kHz (mu-law: 191 ms): the read is one
+ *   pageable copy.
+ * Not covered: the generator (it hands out f64), the _multi entries and jb_gather_pcm, stereo, Microsoft ADPCM
+ * (tag 2), a trial search over start indices, reading through the pinned ring (the read is one pageable copy). */
+/* A (block_align 0: by hz), samples per block, blocks and bytes of n samples; any out pointer may be NULL.  A bad
+ * block_align: JB_ERR_INVALID. */
+int jb_adpcm_geometry(uint32_t hz, uint32_t block_align, size_t n, uint32_t *A, uint32_t *spb, size_t *n_blocks,
+                      size_t *n_bytes);
+/* The encoder in plain C++ on the host; no GPU is touched.  out must hold the geometry's bytes (cap below that:
+ * JB_ERR_BUFFER).  The same samples, rate and options give the same bytes from the host, the seam and the batch. */
+int jb_adpcm_encode_host(const double *in, size_t n, uint32_t hz, const jb_adpcm_opts *opts, uint8_t *out, size_t cap);
+int jb_adpcm_encode_i16_host(const int16_t *in, size_t n, uint32_t hz, const jb_adpcm_opts *opts, uint8_t *out,
+                             size_t cap);
+/* The decoder on the host: the first n_samples samples of n_bytes bytes of blocks of A bytes (cap below n_samples:
+ * JB_ERR_BUFFER; fewer blocks than n_samples need, or a bad A: JB_ERR_INVALID). */
+int jb_adpcm_decode_host(const uint8_t *bytes, size_t n_bytes, uint32_t A, size_t n_samples, int16_t *out, size_t cap);
+/* The stage on PCM the caller holds (jb_format_pcm_batch's twin): out[u] = the blocks of in[u] (n_in[u] f64 samples at
+ * hz[u]), n_bytes[u] of them, library-owned (jb_adpcm_free each), on `device` (-1 = current). */
+int jb_adpcm_encode_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                              const jb_adpcm_opts *opts, int32_t device, uint8_t **out, size_t *n_bytes);
+void jb_adpcm_free(uint8_t *p);
 
 /* ---- multi-GPU (SURVEY 8b "device_ids[] / n_devices", 8e) ----------------------------------
  * Utterances are independent, so a batch shards over the GPUs of a node with no data-path
@@ -736,6 +803,11 @@ int jb_write_wav_f64(const char *path, const double *pcm, size_t n_samples, uint
 int jb_write_wav_formatted(const char *path, const uint8_t *bytes, size_t n_samples, uint32_t sampling_frequency,
                            uint32_t format);
 
+/* Mono RIFF/WAVE of IMA ADPCM blocks: fmt chunk with tag 0x11, 1 channel, nAvgBytesPerSec = floor(hz A / spb),
+ * nBlockAlign A, 4 bits, cbSize 2, wSamplesPerBlock spb; a fact chunk holding n_samples; the data chunk. */
+int jb_write_wav_adpcm(const char *path, const uint8_t *bytes, size_t n_bytes, size_t n_samples,
+                       uint32_t sampling_frequency, uint32_t block_align);
+
 /* Batched synthesize: utterance u has lines [line_off[u], line_off[u+1]).  New
  * entry (the reference is single-utterance); a Rust `Engine::synthesize_batch`
  * would sit on it.  pcm[u] library-owned (jb_pcm_free each). */
@@ -784,6 +856,18 @@ int jb_synthesize_batch_formatted(const jb_engine *e, const char *const *label_l
 int jb_synthesize_batch_each_formatted(const jb_engine *const *engines, const char *const *label_lines,
                                        const size_t *line_off, size_t n_utts, int32_t device,
                                        const jb_format_opts *opts, uint8_t **bytes, size_t *n_bytes);
+/* New.  IMA ADPCM forms of jb_synthesize (one utterance, current device), jb_synthesize_batch_i16 and
+ * jb_synthesize_batch_each_i16: bytes[u] holds the blocks of what the PCM entry returns (each engine's output rate,
+ * loudness target, ceiling and peak mode honoured the same way; with block_align 0 each utterance's A follows its own
+ * rate), n_bytes[u] bytes, library-owned (jb_adpcm_free each); n_samples[u] (may be NULL) the samples they encode. */
+int jb_synthesize_adpcm(const jb_engine *e, const char *const *label_lines, size_t n_lines, const jb_adpcm_opts *opts,
+                        uint8_t **bytes, size_t *n_bytes, size_t *n_samples);
+int jb_synthesize_batch_adpcm(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                              size_t n_utts, int32_t device, const jb_adpcm_opts *opts, uint8_t **bytes,
+                              size_t *n_bytes, size_t *n_samples);
+int jb_synthesize_batch_each_adpcm(const jb_engine *const *engines, const char *const *label_lines,
+                                   const size_t *line_off, size_t n_utts, int32_t device, const jb_adpcm_opts *opts,
+                                   uint8_t **bytes, size_t *n_bytes, size_t *n_samples);
 /* The same two over a device list: the utterances are split by LPT on their label counts (the frame
  * counts are known only after the front half), one host thread per device runs jb_synthesize_batch's
  * path on its share (front half on that thread's workers, GPU work on that device). */
@@ -915,6 +999,7 @@ JB_LAYOUT_ASSERT(sizeof(jb_flac_opts) == 16 && offsetof(jb_flac_opts, max_lpc_or
                      offsetof(jb_flac_opts, reserved) == 8, "jb_flac_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_format_opts) == 16 && offsetof(jb_format_opts, dither) == 4 &&
                      offsetof(jb_format_opts, seed) == 8, "jb_format_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_adpcm_opts) == 16 && offsetof(jb_adpcm_opts, reserved) == 4, "jb_adpcm_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_loudness_report) == 40 && offsetof(jb_loudness_report, gain_db) == 24 &&
                      offsetof(jb_loudness_report, peak_mode) == 32 && offsetof(jb_loudness_report, oversampling) == 36,
                  "jb_loudness_report");

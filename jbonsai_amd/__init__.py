@@ -6,13 +6,14 @@ thin host-side mirror of the reference's API used by tests and the benchmark.
 """
 from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, build, flac_encode, lib, loudness,  # noqa: F401
                    loudness_filter, resample, resample_filter, true_peak, true_peak_filter, write_wav,
-                   format_pcm, format_pcm_host, write_wav_formatted)
+                   format_pcm, format_pcm_host, write_wav_formatted, AdpcmStream, adpcm_decode_host, adpcm_encode,
+                   adpcm_encode_host, adpcm_geometry, write_wav_adpcm)
 from .batch import (Batch, IndexStreamStates, IndexUtterance, PdfSet, StreamInfo, StreamStates, TrackUtterance,  # noqa: F401
                     Utterance, VoiceInfo, generator_from_tracks, mlpg_batch, paramgen_vocode_batch, vocode_tracks_batch,
                     vocoder_synthesize_batch)
 
 from .engine import (Engine, SpeechGenerator, synthesize_batch_each, synthesize_batch_each_flac,  # noqa: F401,E402
-                     synthesize_batch_each_formatted)
+                     synthesize_batch_each_adpcm, synthesize_batch_each_formatted)
 from . import comm  # noqa: F401,E402
 
 __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build", "lib", "write_wav", "Batch", "StreamInfo", "StreamStates",
@@ -20,4 +21,6 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "UttVoc", "synthesize_batch_each", "resample", "resample_filter",
            "loudness", "loudness_filter", "flac_encode", "synthesize_batch_each_flac",
            "true_peak", "true_peak_filter", "PEAK_SAMPLE", "PEAK_TRUE",
-           "format_pcm", "format_pcm_host", "write_wav_formatted", "synthesize_batch_each_formatted"]
+           "format_pcm", "format_pcm_host", "write_wav_formatted", "synthesize_batch_each_formatted",
+           "AdpcmStream", "adpcm_decode_host", "adpcm_encode", "adpcm_encode_host", "adpcm_geometry", "write_wav_adpcm",
+           "synthesize_batch_each_adpcm"]

@@ -5,6 +5,7 @@ fails loudly when the HIP library is missing -- there is no CPU fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import subprocess
 from pathlib import Path
@@ -167,6 +168,17 @@ def format_opts(fmt, dither=False, seed: int = 0):
     return o
 
 
+class AdpcmOpts(C.Structure):
+    """jb_adpcm_opts: the IMA ADPCM block size (0: by each utterance's output rate)."""
+    _fields_ = [("block_align", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+def adpcm_opts(block_align: int = 0):
+    o = AdpcmOpts()
+    o.block_align = int(block_align)
+    return o
+
+
 class LoudnessReport(C.Structure):
     """jb_loudness_report: what a run measured and applied for one utterance."""
     _fields_ = [("lufs", C.c_double), ("sample_peak_dbfs", C.c_double), ("true_peak_dbtp", C.c_double),
@@ -222,6 +234,10 @@ SYMBOLS = [
     "jb_batch_read_formatted_all", "jb_format_pcm_batch", "jb_format_pcm_host", "jb_format_free",
     "jb_synthesize_formatted", "jb_synthesize_batch_formatted", "jb_synthesize_batch_each_formatted",
     "jb_write_wav_formatted",
+    "jb_batch_set_adpcm", "jb_batch_adpcm_size", "jb_batch_adpcm_block_align", "jb_batch_read_adpcm",
+    "jb_batch_read_adpcm_all", "jb_adpcm_geometry", "jb_adpcm_encode_host", "jb_adpcm_encode_i16_host",
+    "jb_adpcm_decode_host", "jb_adpcm_encode_pcm_batch", "jb_adpcm_free", "jb_write_wav_adpcm",
+    "jb_synthesize_adpcm", "jb_synthesize_batch_adpcm", "jb_synthesize_batch_each_adpcm",
 ]
 
 
@@ -393,6 +409,27 @@ def lib():
     L.jb_synthesize_batch_each_formatted.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz,
                                                      C.c_int32, mop, C.POINTER(u8p), C.POINTER(sz)]
     L.jb_write_wav_formatted.argtypes = [C.c_char_p, vp, sz, C.c_uint32, C.c_uint32]
+    aop, u32p = C.POINTER(AdpcmOpts), C.POINTER(C.c_uint32)
+    L.jb_batch_set_adpcm.argtypes = [vp, aop]
+    L.jb_batch_adpcm_size.argtypes = [vp, sz, C.POINTER(sz)]
+    L.jb_batch_adpcm_block_align.argtypes = [vp, sz, u32p]
+    L.jb_batch_read_adpcm.argtypes = [vp, sz, vp, sz]
+    L.jb_batch_read_adpcm_all.argtypes = [vp, C.POINTER(vp)]
+    L.jb_adpcm_geometry.argtypes = [C.c_uint32, C.c_uint32, sz, u32p, u32p, C.POINTER(sz), C.POINTER(sz)]
+    L.jb_adpcm_encode_host.argtypes = [vp, sz, C.c_uint32, aop, vp, sz]
+    L.jb_adpcm_encode_i16_host.argtypes = [vp, sz, C.c_uint32, aop, vp, sz]
+    L.jb_adpcm_decode_host.argtypes = [vp, sz, C.c_uint32, sz, vp, sz]
+    L.jb_adpcm_encode_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, u32p, aop, C.c_int32, C.POINTER(u8p),
+                                            C.POINTER(sz)]
+    L.jb_adpcm_free.argtypes = [u8p]
+    L.jb_adpcm_free.restype = None
+    L.jb_write_wav_adpcm.argtypes = [C.c_char_p, vp, sz, sz, C.c_uint32, C.c_uint32]
+    L.jb_synthesize_adpcm.argtypes = [vp, C.POINTER(C.c_char_p), sz, aop, C.POINTER(u8p), C.POINTER(sz),
+                                      C.POINTER(sz)]
+    L.jb_synthesize_batch_adpcm.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, aop,
+                                            C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_batch_each_adpcm.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
+                                                 aop, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
     L.jb_write_wav_i16.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     L.jb_write_wav_f64.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     _lib = L
@@ -560,6 +597,98 @@ def write_wav_formatted(path, data: bytes, sampling_frequency: int, fmt) -> None
     buf = C.create_string_buffer(bytes(data), max(1, len(data)))
     check(L.jb_write_wav_formatted(str(path).encode(), C.cast(buf, C.c_void_p), len(data) // nb if nb else 0,
                                    sampling_frequency, f))
+
+
+class AdpcmStream(collections.namedtuple("AdpcmStream", "data n_samples hz block_align")):
+    """One utterance as IMA ADPCM: its blocks, the samples they encode, its rate and its block size."""
+
+    def write_wav(self, path) -> None:
+        write_wav_adpcm(path, self.data, self.n_samples, self.hz, self.block_align)
+
+    def decode(self):
+        return adpcm_decode_host(self.data, self.block_align, self.n_samples)
+
+
+def adpcm_streams(L, bufs, ns, nsamp, rates, block_align, n):
+    """AdpcmStream of n library-owned outputs at their rates (released here)."""
+    datas = take_adpcm(L, bufs, ns, n)
+    return [AdpcmStream(datas[u], nsamp[u], rates[u], adpcm_geometry(rates[u], 0, block_align)[0]) for u in range(n)]
+
+
+def take_adpcm(L, bufs, ns, n):
+    """bytes of n library-owned ADPCM outputs, each released with jb_adpcm_free."""
+    out = []
+    for u in range(n):
+        out.append(C.string_at(bufs[u], ns[u]) if ns[u] else b"")
+        if bufs[u]:
+            L.jb_adpcm_free(bufs[u])
+    return out
+
+
+def adpcm_geometry(hz: int, n: int, block_align: int = 0):
+    """jb_adpcm_geometry: (A, samples per block, blocks, bytes) of n samples at hz."""
+    A, spb, nb, nby = C.c_uint32(), C.c_uint32(), C.c_size_t(), C.c_size_t()
+    check(lib().jb_adpcm_geometry(hz, block_align, n, C.byref(A), C.byref(spb), C.byref(nb), C.byref(nby)))
+    return A.value, spb.value, nb.value, nby.value
+
+
+def adpcm_encode_host(pcm, hz: int, block_align: int = 0) -> bytes:
+    """jb_adpcm_encode_host / jb_adpcm_encode_i16_host (by the array's dtype): IMA ADPCM blocks of float64 samples in
+    16-bit scale, or of int16 samples, in plain C++ on the host (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm)
+    i16 = a.dtype == np.int16
+    if not i16:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+    L = lib()
+    opts = adpcm_opts(block_align)
+    nby = adpcm_geometry(hz, a.size, block_align)[3]
+    out = np.empty(max(1, nby), dtype=np.uint8)
+    fn = L.jb_adpcm_encode_i16_host if i16 else L.jb_adpcm_encode_host
+    check(fn(a.ctypes.data, a.size, hz, C.byref(opts), out.ctypes.data, nby))
+    return out[:nby].tobytes()
+
+
+def adpcm_decode_host(data: bytes, block_align: int, n_samples: int):
+    """jb_adpcm_decode_host: the first n_samples int16 samples of IMA ADPCM blocks of block_align bytes."""
+    import numpy as np
+
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.empty(max(1, n_samples), dtype=np.int16)
+    check(lib().jb_adpcm_decode_host(buf.ctypes.data if buf.size else None, buf.size, block_align, n_samples,
+                                     out.ctypes.data, n_samples))
+    return out[:n_samples]
+
+
+def adpcm_encode(pcms, hz, block_align: int = 0, device: int = -1):
+    """jb_adpcm_encode_pcm_batch: the IMA ADPCM blocks of each float64 array of `pcms` (or of one array) on the GPU;
+    hz: one rate, or one per array."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
+    n = len(arrs)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    L = lib()
+    dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    opts = adpcm_opts(block_align)
+    check(L.jb_adpcm_encode_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, bufs, ns))
+    res = take_adpcm(L, bufs, ns, n)
+    return res[0] if single else res
+
+
+def write_wav_adpcm(path, data: bytes, n_samples: int, sampling_frequency: int, block_align: int) -> None:
+    """jb_write_wav_adpcm: a mono WAV file (format tag 0x11) of IMA ADPCM blocks."""
+    buf = C.create_string_buffer(bytes(data), max(1, len(data)))
+    check(lib().jb_write_wav_adpcm(str(path).encode(), C.cast(buf, C.c_void_p), len(data), n_samples,
+                                   sampling_frequency, block_align))
 
 
 def resample(pcms, in_hz: int, out_hz: int, device: int = -1):

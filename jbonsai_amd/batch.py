@@ -447,6 +447,40 @@ class Batch:
         F.check(self._L.jb_batch_read_formatted_all(self._h, arr))
         return [b[:n].tobytes() for b, n in zip(bufs, ns)]
 
+    def set_adpcm(self, block_align: int = 0):
+        """jb_batch_set_adpcm: the run also encodes each utterance's final PCM as IMA ADPCM blocks (WAV tag 0x11) on
+        the GPU.  block_align 0: by each utterance's output rate (256 / 512 / 1024), else a multiple of 4 in 32..8192.
+        An f64 or a pcm_i16 batch (not mlpg_only), before the first run only."""
+        opts = F.adpcm_opts(block_align)
+        F.check(self._L.jb_batch_set_adpcm(self._h, C.byref(opts)))
+
+    def adpcm_block_align(self, i) -> int:
+        """Utterance i's block size A (jb_batch_adpcm_block_align)."""
+        a = C.c_uint32()
+        F.check(self._L.jb_batch_adpcm_block_align(self._h, i, C.byref(a)))
+        return a.value
+
+    def adpcm_size(self, i) -> int:
+        n = C.c_size_t()
+        F.check(self._L.jb_batch_adpcm_size(self._h, i, C.byref(n)))
+        return n.value
+
+    def read_adpcm(self, i) -> bytes:
+        """Utterance i's IMA ADPCM blocks (jb_batch_adpcm_size + jb_batch_read_adpcm)."""
+        n = self.adpcm_size(i)
+        buf = np.empty(max(1, n), dtype=np.uint8)
+        F.check(self._L.jb_batch_read_adpcm(self._h, i, buf.ctypes.data, n))
+        return buf[:n].tobytes()
+
+    def read_adpcm_all(self) -> List[bytes]:
+        """Every utterance's blocks through one device-to-host copy (jb_batch_read_adpcm_all)."""
+        B = len(self)
+        ns = [self.adpcm_size(i) for i in range(B)]
+        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
+        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
+        F.check(self._L.jb_batch_read_adpcm_all(self._h, arr))
+        return [b[:n].tobytes() for b, n in zip(bufs, ns)]
+
     def output_rate(self, i) -> int:
         """Rate of utterance i's PCM as the read entries hand it out (the voice's rate when native)."""
         return self._L.jb_batch_output_rate(self._h, i)

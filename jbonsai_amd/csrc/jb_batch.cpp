@@ -2674,6 +2674,74 @@ int jb_batch_read_formatted_all(jb_batch *hb, uint8_t *const *dst)
     return JB_OK;
 }
 
+int jb_batch_set_adpcm(jb_batch *hb, const jb_adpcm_opts *opts)
+{
+    if (!hb)
+        return JB_ERR_INVALID;
+    return ((Batch *)hb)->out.set_adpcm(opts);
+}
+
+int jb_batch_adpcm_size(jb_batch *hb, size_t utt, size_t *n_bytes)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !n_bytes || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
+    if (!w)
+        return JB_ERR_INVALID;
+    *n_bytes = (size_t)w->bytes;
+    return JB_OK;
+}
+
+int jb_batch_adpcm_block_align(jb_batch *hb, size_t utt, uint32_t *block_align)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !block_align || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
+    if (!w)
+        return JB_ERR_INVALID;
+    *block_align = w->A;
+    return JB_OK;
+}
+
+int jb_batch_read_adpcm(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
+    if (!w)
+        return JB_ERR_INVALID;
+    if (cap < w->bytes) {
+        jb::set_error("jb_batch_read_adpcm: the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (!dst && w->bytes)
+        return JB_ERR_INVALID;
+    return b->out.read_adpcm(utt, dst);
+}
+
+int jb_batch_read_adpcm_all(jb_batch *hb, uint8_t *const *dst)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || (!dst && b->B))
+        return JB_ERR_INVALID;
+    std::unique_ptr<uint8_t[]> host;
+    int rc = b->out.read_adpcm_all(&host);
+    if (rc)
+        return rc;
+    for (size_t u = 0; u < (size_t)b->B; u++)
+        if (!dst[u] && b->out.adpcm_place(u)->bytes)
+            return JB_ERR_INVALID;
+    for (size_t u = 0; u < (size_t)b->B; u++) {
+        const jb::OutAdpcmUtt *w = b->out.adpcm_place(u);
+        if (w->bytes)
+            memcpy(dst[u], host.get() + w->off, (size_t)w->bytes);
+    }
+    return JB_OK;
+}
+
 int jb_batch_read_pcm_native(jb_batch *hb, size_t i, double *dst, size_t cap)
 {
     Batch *b = (Batch *)hb;

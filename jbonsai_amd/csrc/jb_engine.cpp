@@ -1388,7 +1388,7 @@ int jb_write_wav_f64(const char *path, const double *pcm, size_t n, uint32_t fs)
 int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                               int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads,
                               const jb_engine *const *each, bool flac, const jb_flac_opts *flac_opts,
-                              const jb_format_opts *fmt_opts)
+                              const jb_format_opts *fmt_opts, const jb_adpcm_opts *adpcm_opts, size_t *adpcm_samples)
 {
     auto eng = [&](size_t u) { return CENG(each ? each[u] : e); }; // the engine of utterance u
     if (!e || !pcm || !n_samples || (n_utts && !line_off))
@@ -1579,6 +1579,8 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             return rc;
         if (fmt_opts && (rc = b->out.set_format(fmt_opts)))
             return rc;
+        if (adpcm_opts && (rc = b->out.set_adpcm(adpcm_opts)))
+            return rc;
         rc = b->run(false);
         t_create += ms(t0, now());
         return rc;
@@ -1626,6 +1628,26 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
                 }
                 memcpy(pcm[u], host.get() + w.off, (size_t)w.bytes);
                 n_samples[u] = (size_t)w.bytes;
+            }
+            batches[g].reset();
+            t_d2h += ms(t0, now());
+            return JB_OK;
+        }
+        if (adpcm_opts) {
+            // the used bytes of the ADPCM slab in one copy, then each utterance's blocks
+            std::unique_ptr<uint8_t[]> host;
+            if ((rc = b->out.read_adpcm_all(&host)))
+                return rc;
+            for (size_t u = lo; u < hi; u++) {
+                const jb::OutAdpcmUtt &w = *b->out.adpcm_place(u - lo);
+                if (!(pcm[u] = malloc(std::max<size_t>((size_t)w.bytes, 1)))) {
+                    jb::set_error("out of host memory");
+                    return JB_ERR_INVALID;
+                }
+                memcpy(pcm[u], host.get() + w.off, (size_t)w.bytes);
+                n_samples[u] = (size_t)w.bytes;
+                if (adpcm_samples)
+                    adpcm_samples[u] = b->out.samples(u - lo);
             }
             batches[g].reset();
             t_d2h += ms(t0, now());
@@ -1800,7 +1822,8 @@ static int check_engines(const jb_engine *const *engines, size_t n)
 static int synthesize_each(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
                            size_t n_utts, int32_t device, size_t elem, void **pcm, size_t *n_samples,
                            bool flac = false, const jb_flac_opts *flac_opts = nullptr,
-                           const jb_format_opts *fmt_opts = nullptr)
+                           const jb_format_opts *fmt_opts = nullptr, const jb_adpcm_opts *adpcm_opts = nullptr,
+                           size_t *adpcm_samples = nullptr)
 {
     if (!pcm || !n_samples || (n_utts && !line_off))
         return JB_ERR_INVALID;
@@ -1810,7 +1833,7 @@ static int synthesize_each(const jb_engine *const *engines, const char *const *l
     if (rc)
         return rc;
     return jb::synthesize_batch_impl(engines[0], lines, line_off, n_utts, device, elem, pcm, n_samples, 0, engines,
-                                     flac, flac_opts, fmt_opts);
+                                     flac, flac_opts, fmt_opts, adpcm_opts, adpcm_samples);
 }
 
 extern "C" {
@@ -1894,6 +1917,37 @@ int jb_synthesize_formatted(const jb_engine *e, const char *const *lines, size_t
         return JB_ERR_INVALID;
     size_t off[2] = {0, n};
     return jb_synthesize_batch_formatted(e, lines, off, 1, -1, opts, bytes, n_bytes);
+}
+
+int jb_synthesize_batch_adpcm(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                              int32_t device, const jb_adpcm_opts *opts, uint8_t **bytes, size_t *n_bytes,
+                              size_t *n_samples)
+{
+    int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_batch_adpcm");
+    if (rc)
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)bytes, n_bytes, 0,
+                                     nullptr, false, nullptr, nullptr, opts, n_samples);
+}
+
+int jb_synthesize_batch_each_adpcm(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                                   size_t n_utts, int32_t device, const jb_adpcm_opts *opts, uint8_t **bytes,
+                                   size_t *n_bytes, size_t *n_samples)
+{
+    int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_batch_each_adpcm");
+    if (rc)
+        return rc;
+    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)bytes, n_bytes, false,
+                           nullptr, nullptr, opts, n_samples);
+}
+
+int jb_synthesize_adpcm(const jb_engine *e, const char *const *lines, size_t n, const jb_adpcm_opts *opts,
+                        uint8_t **bytes, size_t *n_bytes, size_t *n_samples)
+{
+    if (!bytes || !n_bytes)
+        return JB_ERR_INVALID;
+    size_t off[2] = {0, n};
+    return jb_synthesize_batch_adpcm(e, lines, off, 1, -1, opts, bytes, n_bytes, n_samples);
 }
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/jbonsai_amd.h"
 #include "jb_device.h"
+#include "jb_adpcm.h"
 #include "jb_format.h"
 #include "jb_output.h"
 
@@ -34,11 +35,13 @@ void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE
 // each != null (jb_synthesize_batch_each[_i16], engines checked by the caller): utterance u under each[u]'s Condition,
 // e = each[0] for what the engines share; flac (elem 2): pcm[u] / n_samples[u] receive utterance u's FLAC stream
 // and its byte count instead (jb_synthesize*_flac); fmt_opts (elem 8): its bytes in that sample format and their
-// count (jb_synthesize*_formatted)
+// count (jb_synthesize*_formatted); adpcm_opts (elem 2): its IMA ADPCM blocks and their byte count, the samples they
+// encode in adpcm_samples[u] where that is not null (jb_synthesize*_adpcm)
 int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                           int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0,
                           const jb_engine *const *each = nullptr, bool flac = false,
-                          const jb_flac_opts *flac_opts = nullptr, const jb_format_opts *fmt_opts = nullptr);
+                          const jb_flac_opts *flac_opts = nullptr, const jb_format_opts *fmt_opts = nullptr,
+                          const jb_adpcm_opts *adpcm_opts = nullptr, size_t *adpcm_samples = nullptr);
 // A stream / a device block from the per-device pools that batches draw from (jb_batch.cpp), for work outside a
 // batch; *got is the block's pooled size, which pooled_block_free takes back
 hipError_t pooled_stream_acquire(int device, hipStream_t *st);
@@ -178,6 +181,10 @@ hipError_t launch_flac_pack(const FlacParams &p, const FlacUtt *utts, uint32_t n
 hipError_t launch_format(uint32_t format, uint32_t dither, uint64_t seed, const FormatUtt *utts_dev, uint32_t n,
                          uint64_t tiles, hipStream_t stream);
 
+// IMA ADPCM (jb_adpcm.hip; the rules and AdpcmUtt: jb_adpcm.h): utts_dev[0..n) of `groups` workgroups in all, their
+// x f64 or 16-bit samples by i16
+hipError_t launch_adpcm(bool i16, const AdpcmUtt *utts_dev, uint32_t n, uint64_t groups, hipStream_t stream);
+
 // Device-resident pdf tables of a voice set (jb_pdf_set) and an indexed batch source
 struct PdfSet {
     int device = -1;
@@ -241,7 +248,8 @@ struct DeviceScratch {
 
 struct Batch;
 // The stages behind the vocoder of one batch -- output rate (jb_batch_set_output_rate), loudness target
-// (jb_batch_set_loudness_target), FLAC (jb_batch_set_flac), sample format (jb_batch_set_format) -- and all their
+// (jb_batch_set_loudness_target), FLAC (jb_batch_set_flac), sample format (jb_batch_set_format), IMA ADPCM
+// (jb_batch_set_adpcm) -- and all their
 // device state.  The setters record a
 // request and plan again (jb_output.h); the first run carries the plan out (prepare); every run enqueues the chain
 // once behind the hand-off check, and finish_verify once more for the utterances its redo rounds rewrote.
@@ -254,6 +262,7 @@ struct OutputChain {
     int set_peak_mode(const uint32_t *mode, size_t n);                       // n == 1 or B entries; needs no target
     int set_flac(const jb_flac_opts *opts);
     int set_format(const jb_format_opts *opts); // an f64 batch only
+    int set_adpcm(const jb_adpcm_opts *opts);   // an f64 or a 16-bit batch
     void init();   // Batch::create: the slabs the batch was made with, the plan of no request
     int prepare(); // at the first run: every slab, table and list of the plan; points the vocoder at its slab
     // only: [B] 1 = the utterances a redo rewrote: their part of every stage again (the FLAC pack: every stream),
@@ -283,6 +292,11 @@ struct OutputChain {
     int read_formatted(size_t u, uint8_t *dst);
     int read_formatted_all(std::unique_ptr<uint8_t[]> *host);
     const OutFmtUtt &format_place(size_t u) const { return plan.fmt[u]; }
+    // the ADPCM blocks: utterance u's place, byte count and block size (known once the request is made; null without
+    // one), its bytes, or the used part of the slab in one copy (utterance u at host + adpcm_place(u)->off)
+    const OutAdpcmUtt *adpcm_place(size_t u) const;
+    int read_adpcm(size_t u, uint8_t *dst);
+    int read_adpcm_all(std::unique_ptr<uint8_t[]> *host);
 
 private:
     Batch &b;
@@ -291,6 +305,8 @@ private:
     bool ln_on = false, flac_on = false;       // a loudness target / FLAC is requested
     bool fmt_on = false;                       // a sample format is requested
     jb_format_opts fmt_p{};
+    bool ad_on = false;                        // IMA ADPCM is requested
+    uint32_t ad_align = 0;                     // its block_align (0: by the rate)
     std::vector<double> ln_target, ln_ceiling; // [B]
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
     FlacParams flac_p{};
@@ -326,12 +342,18 @@ private:
         FormatUtt *utts_dev = nullptr, *redo_dev = nullptr;
         uint64_t tiles = 0;
     } fm;
+    struct { // IMA ADPCM
+        std::vector<AdpcmUtt> utts;
+        AdpcmUtt *utts_dev = nullptr, *redo_dev = nullptr;
+        uint64_t groups = 0;
+    } ad;
     void replan(); // host geometry and routing of the present requests
     int check_settable(const char *after_run) const;
     int prepare_resample();
     int prepare_loudness();
     int prepare_flac();
     int prepare_format();
+    int prepare_adpcm();
     int format_ready() const;
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
     int flac_ready() const;

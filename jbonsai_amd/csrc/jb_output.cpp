@@ -1,5 +1,6 @@
 // jb_output.cpp -- plan_output: the routing table of the output stages (jb_output.h).
 #include "jb_output.h"
+#include "jb_adpcm.h"
 
 #include <algorithm>
 #include <numeric>
@@ -70,6 +71,18 @@ OutPlan plan_output(const OutPlanIn &in)
             bytes += (p.fmt[u].bytes + 15) & ~(uint64_t)15;
         }
         p.alloc[(size_t)OutSlab::Fmt] = std::max<uint64_t>(bytes, 16);
+    }
+    // IMA ADPCM beside it: the final PCM, f64 or 16-bit, to blocks of each utterance's own size
+    if (in.adpcm) {
+        p.adpcm_src = p.final;
+        p.adpcm.resize(in.B);
+        uint64_t bytes = 0;
+        for (size_t u = 0; u < in.B; u++) {
+            const uint32_t A = adpcm_block_align(p.utt[u].hz, in.adpcm_align);
+            p.adpcm[u] = {bytes, adpcm_bytes(p.utt[u].n, A), A};
+            bytes += (p.adpcm[u].bytes + 15) & ~(uint64_t)15;
+        }
+        p.alloc[(size_t)OutSlab::Adpcm] = std::max<uint64_t>(bytes, 16);
     }
     return p;
 }

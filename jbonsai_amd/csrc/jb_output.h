@@ -2,7 +2,8 @@
 // jb_output.h -- the routing of the stages behind the vocoder (output rate, loudness, FLAC): which slab each stage
 // reads and writes, in f64 or in 16 bits, which slab the read entries hand out, and each utterance's output geometry,
 // decided from the batch's shape and the requests alone (plan_output, jb_output.cpp); with a sample format, the f64
-// slab the format stage reads and each utterance's place in its byte slab.
+// slab the format stage reads and each utterance's place in its byte slab; with an IMA ADPCM request, the slab that
+// stage reads (f64 or 16-bit) and each utterance's blocks in its byte slab.
 // Plain C++17 without HIP: the plan is made and tested on any host; OutputChain (jb_host.h) carries it out.
 #include <stddef.h>
 #include <stdint.h>
@@ -21,11 +22,12 @@ enum class OutSlab : uint8_t {
     Apply64, // f64 the loudness apply pass writes
     New16,   // 16-bit output longer than S16
     Fmt,     // bytes the format stage writes
+    Adpcm,   // IMA ADPCM blocks
     Count
 };
 constexpr size_t out_slab_elem(OutSlab s) // bytes
 {
-    return s == OutSlab::Fmt ? 1 : s == OutSlab::S16 || s == OutSlab::New16 ? 2 : 8;
+    return s == OutSlab::Fmt || s == OutSlab::Adpcm ? 1 : s == OutSlab::S16 || s == OutSlab::New16 ? 2 : 8;
 }
 
 // in_hz -> out_hz reduced by their gcd (rates above 0)
@@ -42,6 +44,8 @@ struct OutPlanIn {
     const uint32_t *want_hz = nullptr;    // [B] requested rate, 0 or voice_hz = native; nullptr: none requested
     bool loudness = false, flac = false;
     uint32_t fmt_bytes = 0;               // bytes per sample of the requested sample format; 0: none requested
+    bool adpcm = false;                   // IMA ADPCM is requested
+    uint32_t adpcm_align = 0;             // its block_align: 0 = by each utterance's output rate (jb_adpcm.h)
 };
 
 struct OutUtt {
@@ -51,6 +55,11 @@ struct OutUtt {
 
 struct OutFmtUtt { // an utterance's place in the format slab
     uint64_t off, bytes; // byte offset (16-byte aligned) and n * bytes per sample
+};
+
+struct OutAdpcmUtt { // an utterance's blocks in the ADPCM slab
+    uint64_t off, bytes; // byte offset (16-byte aligned) and blocks * A
+    uint32_t A;          // its block size
 };
 
 struct OutWrite { // what a stage writes; slab None: the stage does not run
@@ -70,6 +79,8 @@ struct OutPlan {
     OutSlab native64 = OutSlab::None; // f64 at the voice's rate (jb_batch_read_pcm_native)
     OutSlab fmt_src = OutSlab::None;  // f64 the format stage reads: what `final` names (None: no format, or no f64)
     std::vector<OutFmtUtt> fmt;       // [B] with a format stage, else empty
+    OutWrite adpcm_src;               // what the ADPCM stage reads: what `final` names, f64 or 16-bit (None: no ADPCM)
+    std::vector<OutAdpcmUtt> adpcm;   // [B] with an ADPCM stage, else empty
     uint64_t alloc[(size_t)OutSlab::Count] = {}; // elements to allocate of each slab, at least 1 (0: none; V64 / S16 exist)
     bool normalize() const { return apply.slab != OutSlab::None; }
     bool active() const { return convert || normalize(); } // a stage rewrites the PCM behind the vocoder

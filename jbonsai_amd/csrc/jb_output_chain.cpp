@@ -1,6 +1,7 @@
 // jb_output_chain.cpp -- OutputChain (jb_host.h): the stages behind the vocoder of one batch.  The setters record a
 // request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() launches
-// k_resample, the loudness measurement and apply pass, the FLAC encoder and pack and the sample format, in that order,
+// k_resample, the loudness measurement and apply pass, the FLAC encoder and pack, the sample format and IMA ADPCM, in
+// that order,
 // on the vocoder's stream.
 #include "jb_host.h"
 
@@ -34,6 +35,8 @@ void OutputChain::replan()
     in.loudness = ln_on;
     in.flac = flac_on;
     in.fmt_bytes = fmt_on ? (uint32_t)format_bytes(fmt_p.format) : 0;
+    in.adpcm = ad_on;
+    in.adpcm_align = ad_align;
     plan = plan_output(in);
 }
 
@@ -154,6 +157,19 @@ int OutputChain::set_format(const jb_format_opts *opts)
     return JB_OK;
 }
 
+int OutputChain::set_adpcm(const jb_adpcm_opts *opts)
+{
+    int rc = adpcm_check_opts((const AdpcmOpts *)opts, "jb_batch_set_adpcm");
+    if (rc)
+        return rc;
+    if ((rc = check_settable("jb_batch_set_adpcm: IMA ADPCM is set before the batch's first run")))
+        return rc;
+    ad_align = opts->block_align;
+    ad_on = true;
+    replan();
+    return JB_OK;
+}
+
 // At the first run (a second one, or the step done again behind a resident-GV formation timeout, finds it done).
 // The vocoder is pointed at its slab last: a failure leaves the batch as it was created, its blocks the batch's own
 int OutputChain::prepare()
@@ -166,7 +182,7 @@ int OutputChain::prepare()
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
     if ((rc = prepare_resample()) || (rc = prepare_loudness()) || (rc = prepare_flac()) ||
-        (rc = prepare_format()))
+        (rc = prepare_format()) || (rc = prepare_adpcm()))
         return rc;
     if (plan.active()) {
         void *voc = slab[(size_t)plan.vocoder.slab];
@@ -343,10 +359,42 @@ int OutputChain::prepare_format()
     return JB_OK;
 }
 
+// The utterance list: the final PCM of the plan in (f64 or 16-bit), each utterance's blocks at their 16-byte aligned
+// place out
+int OutputChain::prepare_adpcm()
+{
+    if (plan.adpcm_src.slab == OutSlab::None)
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    const char *src = (const char *)slab[(size_t)plan.adpcm_src.slab];
+    const size_t elem = plan.adpcm_src.i16 ? sizeof(int16_t) : sizeof(double);
+    uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Adpcm];
+    ad.utts.assign(B, AdpcmUtt{});
+    ad.groups = 0;
+    for (size_t u = 0; u < B; u++) {
+        AdpcmUtt &w = ad.utts[u];
+        w.x = src + plan.utt[u].off * elem;
+        w.y = dst + plan.adpcm[u].off;
+        w.n = plan.utt[u].n;
+        w.g0 = ad.groups;
+        w.A = plan.adpcm[u].A;
+        w.spb = adpcm_spb(w.A);
+        ad.groups += (adpcm_blocks(w.n, w.A) + kAdpcmLanes - 1) / kAdpcmLanes;
+    }
+    int rc;
+    if ((rc = b.dalloc(&ad.utts_dev, B, false)) || (rc = b.dalloc(&ad.redo_dev, B, false)))
+        return rc;
+    hipError_t e;
+    if (B > 0 && (e = hipMemcpy(ad.utts_dev, ad.utts.data(), sizeof(AdpcmUtt) * B, hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_fail(e, "ADPCM work list");
+    return JB_OK;
+}
+
 int OutputChain::enqueue(const std::vector<uint8_t> *only)
 {
     const bool fmt = plan.fmt_src != OutSlab::None;
-    if (!ready || !(plan.active() || flac_on || fmt))
+    const bool adp = plan.adpcm_src.slab != OutSlab::None;
+    if (!ready || !(plan.active() || flac_on || fmt || adp))
         return JB_OK;
     const uint32_t B = (uint32_t)b.B;
     hipStream_t st = b.stream_voc;
@@ -357,6 +405,9 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const FormatUtt *futts = fm.utts_dev;
     uint32_t n_futts = fmt ? B : 0;
     uint64_t ft = fm.tiles;
+    const AdpcmUtt *autts = ad.utts_dev;
+    uint32_t n_autts = adp ? B : 0;
+    uint64_t ag = ad.groups;
     const uint32_t n_all_work = (uint32_t)fl.work.size();
     uint32_t n_tiles = (uint32_t)rs.tiles.size(), n_utts = B, n_work = n_all_work;
     uint64_t lt = ln.tiles, at = ln.atiles;
@@ -368,7 +419,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         std::vector<LoudnessUtt> ln_sub;
         std::vector<FlacWork> fl_sub;
         std::vector<FormatUtt> fm_sub;
-        lt = at = ft = 0;
+        std::vector<AdpcmUtt> ad_sub;
+        lt = at = ft = ag = 0;
         for (size_t u = 0; u < B; u++) {
             if (!(*only)[u])
                 continue;
@@ -388,6 +440,12 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
                 ft += (w.n + kFmtTile - 1) / kFmtTile;
                 fm_sub.push_back(w);
             }
+            if (adp) {
+                AdpcmUtt w = ad.utts[u];
+                w.g0 = ag;
+                ag += (adpcm_blocks(w.n, w.A) + kAdpcmLanes - 1) / kAdpcmLanes;
+                ad_sub.push_back(w);
+            }
         }
         for (const FlacWork &w : fl.work)
             if ((*only)[w.utt])
@@ -397,10 +455,12 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         work = fl.redo_dev;
         futts = fm.redo_dev;
         n_futts = (uint32_t)fm_sub.size();
+        autts = ad.redo_dev;
+        n_autts = (uint32_t)ad_sub.size();
         n_tiles = (uint32_t)rs_sub.size();
         n_utts = (uint32_t)ln_sub.size();
         n_work = (uint32_t)fl_sub.size();
-        if (!n_tiles && !n_utts && !n_work && !n_futts)
+        if (!n_tiles && !n_utts && !n_work && !n_futts && !n_autts)
             return JB_OK;
         if ((n_tiles && (e = hipMemcpy(rs.redo_dev, rs_sub.data(), sizeof(ResampleTile) * n_tiles,
                                        hipMemcpyHostToDevice)) != hipSuccess) ||
@@ -409,6 +469,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
             (n_work && (e = hipMemcpy(fl.redo_dev, fl_sub.data(), sizeof(FlacWork) * n_work, hipMemcpyHostToDevice)) !=
                            hipSuccess) ||
             (n_futts && (e = hipMemcpy(fm.redo_dev, fm_sub.data(), sizeof(FormatUtt) * n_futts,
+                                       hipMemcpyHostToDevice)) != hipSuccess) ||
+            (n_autts && (e = hipMemcpy(ad.redo_dev, ad_sub.data(), sizeof(AdpcmUtt) * n_autts,
                                        hipMemcpyHostToDevice)) != hipSuccess))
             return hip_fail(e, "output chain(redo lists)");
     }
@@ -431,6 +493,10 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     if (fmt && (!only || n_futts) &&
         (e = launch_format(fmt_p.format, fmt_p.dither, fmt_p.seed, futts, n_futts, ft, st)) != hipSuccess)
         return hip_fail(e, only ? "k_format(redo)" : "k_format");
+    // IMA ADPCM beside it, of the same final PCM
+    if (adp && (!only || n_autts) &&
+        (e = launch_adpcm(plan.adpcm_src.i16, autts, n_autts, ag, st)) != hipSuccess)
+        return hip_fail(e, only ? "k_adpcm(redo)" : "k_adpcm");
     if (only && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "output chain(redo)");
     return JB_OK;
@@ -483,6 +549,41 @@ int OutputChain::read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_
         return JB_ERR_INVALID;
     }
     return total ? b.read(fl.out, host->get(), (size_t)total, false) : JB_OK;
+}
+
+const OutAdpcmUtt *OutputChain::adpcm_place(size_t u) const
+{
+    if (!ad_on) {
+        set_error("ADPCM: jb_batch_set_adpcm was not called");
+        return nullptr;
+    }
+    return &plan.adpcm[u];
+}
+
+int OutputChain::read_adpcm(size_t u, uint8_t *dst)
+{
+    int rc = check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called");
+    if (rc)
+        return rc;
+    const OutAdpcmUtt &w = plan.adpcm[u];
+    return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Adpcm] + w.off, dst, (size_t)w.bytes) : b.sync();
+}
+
+int OutputChain::read_adpcm_all(std::unique_ptr<uint8_t[]> *host)
+{
+    int rc = check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called");
+    if (rc)
+        return rc;
+    uint64_t total = 0;
+    for (const OutAdpcmUtt &w : plan.adpcm)
+        total = std::max<uint64_t>(total, w.off + w.bytes);
+    // one copy of the used bytes (not zero-filled first)
+    host->reset(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
+    if (!*host) {
+        set_error("out of host memory");
+        return JB_ERR_INVALID;
+    }
+    return total ? b.read(slab[(size_t)OutSlab::Adpcm], host->get(), (size_t)total) : b.sync();
 }
 
 int OutputChain::format_ready() const

@@ -412,6 +412,31 @@ class Engine:
                                                       ns))
         return F.take_formatted(self._L, bufs, ns, B)
 
+    def _out_hz(self) -> int:
+        return self.condition.get_output_sampling_frequency() or self.condition.get_sampling_frequency()
+
+    def synthesize_adpcm(self, labels: Sequence[str], block_align: int = 0) -> "F.AdpcmStream":
+        """jb_synthesize_adpcm: what synthesize(labels) returns, quantised to 16 bits and encoded as IMA ADPCM blocks
+        (WAV tag 0x11) on the GPU.  block_align 0: by the output rate."""
+        buf, n, ns = C.POINTER(C.c_uint8)(), C.c_size_t(), C.c_size_t()
+        opts = F.adpcm_opts(block_align)
+        F.check(self._L.jb_synthesize_adpcm(self._h, _lines(labels), len(labels), C.byref(opts), C.byref(buf),
+                                            C.byref(n), C.byref(ns)))
+        return F.adpcm_streams(self._L, [buf], [n.value], [ns.value], [self._out_hz()], block_align, 1)[0]
+
+    def synthesize_adpcm_batch(self, utterances: Sequence[Sequence[str]], block_align: int = 0,
+                               device: int = -1) -> List["F.AdpcmStream"]:
+        """jb_synthesize_batch_adpcm: each utterance of synthesize_batch(...) as IMA ADPCM blocks."""
+        flat = [l for u in utterances for l in u]
+        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+        B = len(utterances)
+        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+        bufs, ns, nsamp = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
+        opts = F.adpcm_opts(block_align)
+        F.check(self._L.jb_synthesize_batch_adpcm(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns,
+                                                  nsamp))
+        return F.adpcm_streams(self._L, bufs, ns, nsamp, [self._out_hz()] * B, block_align, B)
+
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
         F.check(self._L.jb_generator_new(self._h, _lines(labels), len(labels), C.byref(h)))
@@ -472,6 +497,25 @@ def synthesize_batch_each_formatted(engines: Sequence["Engine"], utterances: Seq
     opts = F.format_opts(fmt, dither, seed)
     F.check(L.jb_synthesize_batch_each_formatted(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
     return F.take_formatted(L, bufs, ns, B)
+
+
+def synthesize_batch_each_adpcm(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]],
+                                block_align: int = 0, device: int = -1) -> List["F.AdpcmStream"]:
+    """jb_synthesize_batch_each_adpcm: synthesize_batch_each(...) as IMA ADPCM blocks, each utterance at its engine's
+    output rate (and, with block_align 0, at that rate's block size)."""
+    if len(engines) != len(utterances):
+        raise ValueError("one engine per utterance")
+    B = len(utterances)
+    L = engines[0]._L if B and engines[0] is not None else F.lib()
+    _bind(L)
+    flat = [l for u in utterances for l in u]
+    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
+    bufs, ns, nsamp = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
+    opts = F.adpcm_opts(block_align)
+    F.check(L.jb_synthesize_batch_each_adpcm(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns, nsamp))
+    return F.adpcm_streams(L, bufs, ns, nsamp, [e._out_hz() for e in engines], block_align, B)
 
 
 def synthesize_batch_each_flac(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]], device: int = -1,
