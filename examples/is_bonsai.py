@@ -1,7 +1,7 @@
 """The reference's `examples/is-bonsai` on the GPU path: full-context labels -> PCM -> 16-bit WAV.
 
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak]]
-                                 [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
+                                 [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]] [--flac]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
@@ -11,6 +11,8 @@ With --format the samples are converted to that format on the GPU (ulaw and alaw
 TPDF dither for s16 and s24) and the WAV file carries them as they are.
 With --adpcm the audio is encoded as IMA ADPCM (WAV format tag 0x11, half a byte per sample) on the GPU, at --rate if
 given, with the block size that goes with the rate.
+With --flac the 16-bit audio is encoded as a FLAC stream on the GPU, with the MD5 of its samples in STREAMINFO and a
+SEEKTABLE with a point about every second, and written as it is.
 """
 import argparse
 import os
@@ -32,6 +34,7 @@ ap.add_argument("--format", choices=["f32", "s16", "s24", "ulaw", "alaw"], defau
 ap.add_argument("--dither", action="store_true", help="TPDF dither (with --format s16 or s24)")
 ap.add_argument("--adpcm", action="store_true", help="IMA ADPCM (4-bit) WAV file, encoded on the GPU")
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm)")
+ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
 args = ap.parse_args()
 voice, out = args.voice, args.out
 
@@ -47,6 +50,12 @@ if args.adpcm:
     stream.write_wav(out)
     print(f"wrote {out}: {stream.n_samples} samples at {stream.hz} Hz in {len(stream.data)} bytes of IMA ADPCM "
           f"(blocks of {stream.block_align}, {len(stream.data) / max(stream.n_samples, 1):.3f} bytes per sample)")
+    sys.exit(0)
+if args.flac:
+    data = engine.synthesize_flac(SAMPLE_SENTENCE_2, md5=True, seek_interval_ms=1000)
+    with open(out, "wb") as f:
+        f.write(data)
+    print(f"wrote {out}: {len(data)} bytes of FLAC, MD5 {data[26:42].hex()}")
     sys.exit(0)
 if args.format is not None:
     if args.format in ("ulaw", "alaw"):

@@ -105,6 +105,16 @@ typedef struct jb_flac_opts {
     uint32_t max_lpc_order;
     uint32_t reserved[2];
 } jb_flac_opts;
+/* New.  FLAC metadata that needs the samples or the frame offsets (jb_batch_set_flac_meta, the *_flac_meta entries;
+ * see "FLAC" below).  All zero (or a NULL pointer) = neither: the stream of jb_flac_opts alone, byte for byte.
+ * flags: JB_FLAC_MD5 puts the MD5 of the samples into STREAMINFO; any other bit is JB_ERR_INVALID.
+ * seek_interval_ms > 0 adds a SEEKTABLE with one point about every seek_interval_ms of audio.  reserved must be 0. */
+#define JB_FLAC_MD5 1u
+typedef struct jb_flac_meta {
+    uint32_t flags;
+    uint32_t seek_interval_ms;
+    uint32_t reserved[2];
+} jb_flac_meta;
 
 /* Output sample format (jb_batch_set_format, jb_format_pcm_batch, jb_format_pcm_host, jb_synthesize*_formatted; see
  * "Output sample formats" below).  dither: JB_DITHER_TPDF with JB_FMT_S16 and JB_FMT_S24 only; seed: the dither's,
@@ -380,6 +390,10 @@ int jb_batch_loudness_report(jb_batch *b, size_t utt, jb_loudness_report *out);
  * JB_BATCH_MLPG_ONLY; otherwise JB_ERR_INVALID.  An output rate with no frame-header code fails at the run with
  * JB_ERR_UNSUPPORTED.  The PCM read entries keep working.  Without a call nothing runs and nothing is allocated. */
 int jb_batch_set_flac(jb_batch *b, const jb_flac_opts *opts);
+/* New.  The streams' MD5 and SEEKTABLE (jb_flac_meta): after jb_batch_set_flac and before the batch's first run;
+ * otherwise, or with unknown flag bits or non-zero reserved words, JB_ERR_INVALID.  NULL or zeros withdraw the
+ * request.  jb_batch_flac_size and the read entries work as before (a table adds its bytes to the size). */
+int jb_batch_set_flac_meta(jb_batch *b, const jb_flac_meta *m);
 /* Bytes of utterance utt's stream; waits for the run like the read entries.  No FLAC or no such utterance:
  * JB_ERR_INVALID. */
 int jb_batch_flac_size(jb_batch *b, size_t utt, size_t *n_bytes);
@@ -534,11 +548,24 @@ int jb_true_peak_pcm_batch(const double *const *in, const size_t *n_in, size_t n
 /* ---- FLAC (new: the reference writes WAV only; RFC 9639) ---------------------------------------------------------
  * Each utterance's 16-bit output (exactly what jb_batch_read_pcm_i16 hands out: after the converter, the loudness
  * apply pass or the fused sink) becomes one complete FLAC stream; decoding it gives those samples bit for bit.
- * - Layout: "fLaC", one STREAMINFO block (marked last), then frames.  Mono, 16 bits, at the utterance's output rate
- *   (jb_batch_output_rate).  Fixed block size with frame-number headers: every frame has block_size samples but the
+ * - Layout: "fLaC", one STREAMINFO block (marked last unless a SEEKTABLE follows), then frames.  Mono, 16 bits, at
+ *   the utterance's output rate (jb_batch_output_rate).  Fixed block size with frame-number headers: every frame has block_size samples but the
  *   last, which may be shorter.
  * - STREAMINFO: min = max block size = block_size; min / max frame size the true values of the stream (0 with no
- *   frames); total samples exact; MD5 all zero ("not computed", which the format allows: it is serial per stream).
+ *   frames); total samples exact; MD5 all zero ("not computed", which the format allows) unless JB_FLAC_MD5 asks for
+ *   it.
+ * - MD5 (JB_FLAC_MD5; RFC 1321): of the utterance's 16-bit samples as little-endian bytes, 2 N of them -- FLAC's
+ *   definition for mono 16-bit -- in STREAMINFO bytes 18..33 in RFC 1321's output order.  Computed on the device from
+ *   the PCM the stream encodes (in FLAC mode the host never holds it), one chain per utterance, the batch in
+ *   parallel; a redo round's utterances are hashed again from their final PCM.
+ * - SEEKTABLE (seek_interval_ms > 0): with block size bs and rate hz the step in frames is
+ *   max(1, (seek_interval_ms hz + 500 bs) / (1000 bs)) in integer division, raised to ceil(frames / 65535) where that
+ *   is larger; the points are the frames 0, step, 2 step, ... (ceil(frames / step) of them, ascending, no
+ *   placeholders), each 18 bytes big-endian: u64 first sample f bs, u64 byte offset of frame f's header from the first
+ *   frame's header, u16 samples of the frame.  The stream is then "fLaC", STREAMINFO (not marked last), one
+ *   SEEKTABLE block (type 3, marked last, 18 bytes per point), the frames; a stream without frames has no table.
+ *   The header is 42 + (points ? 4 + 18 points : 0) bytes (jb_flac_seek_geometry).  The frames' bytes are the same
+ *   with and without either request.
  * - Every stream is in the streamable subset: block size <= 4608, LPC order <= 12, Rice partition order <= 8, and
  *   the sample rate and bit depth coded in every frame header.  A rate without a code of its own uses the kHz,
  *   16-bit-Hz or tens-of-Hz form; a rate none of them can express is JB_ERR_UNSUPPORTED when FLAC is requested
@@ -553,12 +580,26 @@ int jb_true_peak_pcm_batch(const double *const *in, const size_t *n_in, size_t n
  *   f64 step runs in a fixed order and ties break by a fixed rule), not on the batch, the utterance's position, the
  *   entry point or redo rounds; JB_BATCH_INVARIANT output stays invariant.
  * Not covered: the generator (it hands out f64), the _multi entries and jb_gather_pcm, f64 batches, 24-bit or
- * stereo, MD5, SEEKTABLE and other metadata, variable block size, Ogg encapsulation, lossy codecs. */
+ * stereo, VORBIS_COMMENT and ReplayGain tags, PADDING and other metadata, variable block size, Ogg encapsulation,
+ * lossy codecs. */
 /* The encoder on PCM the caller holds (jb_resample_pcm_batch's twin): out[u] = the stream of in[u] (n_in[u] samples
  * at hz), n_out[u] bytes, library-owned (jb_flac_free each), on `device` (-1 = current).  The same samples and
  * options give the same bytes as the batch path. */
 int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, uint32_t hz,
                              const jb_flac_opts *opts, int32_t device, uint8_t **out, size_t *n_out);
+/* New.  The same with a metadata request (meta NULL or zeros: jb_flac_encode_pcm_batch itself). */
+int jb_flac_encode_pcm_batch_meta(const int16_t *const *in, const size_t *n_in, size_t n, uint32_t hz,
+                                  const jb_flac_opts *opts, const jb_flac_meta *meta, int32_t device, uint8_t **out,
+                                  size_t *n_out);
+/* New.  The device's MD5 alone: digests[16 u ..] = MD5 of in[u]'s n_in[u] samples as little-endian bytes, on
+ * `device` (-1 = current). */
+int jb_flac_md5_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, int32_t device, uint8_t *digests);
+/* New.  The same rules in plain C++ on the host, no GPU touched: MD5 (RFC 1321) of n_bytes bytes, and the SEEKTABLE
+ * geometry of a stream of n_samples at block_size (0: 4096) and hz: frames between two points (0 without a table),
+ * points, bytes in front of the first frame.  Any output pointer of the geometry may be NULL. */
+int jb_md5_host(const void *data, size_t n_bytes, uint8_t digest[16]);
+int jb_flac_seek_geometry(uint64_t n_samples, uint32_t block_size, uint32_t hz, uint32_t seek_interval_ms,
+                          uint32_t *step_frames, uint32_t *n_points, uint32_t *header_bytes);
 void jb_flac_free(uint8_t *p);
 
 /* ---- Output sample formats (new: the reference hands out f64 and its examples clamp and truncate to 16 bits) -------
@@ -844,6 +885,15 @@ int jb_synthesize_batch_flac(const jb_engine *e, const char *const *label_lines,
 int jb_synthesize_batch_each_flac(const jb_engine *const *engines, const char *const *label_lines,
                                   const size_t *line_off, size_t n_utts, int32_t device, const jb_flac_opts *opts,
                                   uint8_t **flac, size_t *n_bytes);
+/* New.  The same with a metadata request (jb_flac_meta; NULL or zeros: the entries above). */
+int jb_synthesize_flac_meta(const jb_engine *e, const char *const *label_lines, size_t n_lines,
+                            const jb_flac_opts *opts, const jb_flac_meta *meta, uint8_t **flac, size_t *n_bytes);
+int jb_synthesize_batch_flac_meta(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta,
+                                  uint8_t **flac, size_t *n_bytes);
+int jb_synthesize_batch_each_flac_meta(const jb_engine *const *engines, const char *const *label_lines,
+                                       const size_t *line_off, size_t n_utts, int32_t device, const jb_flac_opts *opts,
+                                       const jb_flac_meta *meta, uint8_t **flac, size_t *n_bytes);
 /* New.  Formatted forms of jb_synthesize (one utterance, current device), jb_synthesize_batch and
  * jb_synthesize_batch_each: bytes[u] is what the f64 entry returns (each engine's output rate, loudness target,
  * ceiling and peak mode honoured the same way) in opts->format, n_bytes[u] bytes, library-owned (jb_format_free
@@ -997,6 +1047,8 @@ JB_LAYOUT_ASSERT(sizeof(jb_utt_voc) == 24 && offsetof(jb_utt_voc, beta) == 8 && 
                  "jb_utt_voc");
 JB_LAYOUT_ASSERT(sizeof(jb_flac_opts) == 16 && offsetof(jb_flac_opts, max_lpc_order) == 4 &&
                      offsetof(jb_flac_opts, reserved) == 8, "jb_flac_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_flac_meta) == 16 && offsetof(jb_flac_meta, seek_interval_ms) == 4 &&
+                     offsetof(jb_flac_meta, reserved) == 8, "jb_flac_meta");
 JB_LAYOUT_ASSERT(sizeof(jb_format_opts) == 16 && offsetof(jb_format_opts, dither) == 4 &&
                      offsetof(jb_format_opts, seed) == 8, "jb_format_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_adpcm_opts) == 16 && offsetof(jb_adpcm_opts, reserved) == 4, "jb_adpcm_opts");

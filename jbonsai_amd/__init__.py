@@ -4,7 +4,8 @@ MLSA-vocoder hot path behind a C ABI (include/jbonsai_amd.h).
 The HIP shared library `libjbonsai_amd.so` is the product; this package is the
 thin host-side mirror of the reference's API used by tests and the benchmark.
 """
-from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, build, flac_encode, lib, loudness,  # noqa: F401
+from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, build, flac_encode, flac_md5, flac_seek_geometry, lib, loudness,  # noqa: F401
+                   md5_host,
                    loudness_filter, resample, resample_filter, true_peak, true_peak_filter, write_wav,
                    format_pcm, format_pcm_host, write_wav_formatted, AdpcmStream, adpcm_decode_host, adpcm_encode,
                    adpcm_encode_host, adpcm_geometry, write_wav_adpcm)
@@ -19,7 +20,7 @@ from . import comm  # noqa: F401,E402
 __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build", "lib", "write_wav", "Batch", "StreamInfo", "StreamStates",
            "Utterance", "VoiceInfo", "paramgen_vocode_batch", "mlpg_batch", "vocode_tracks_batch", "vocoder_synthesize_batch", "generator_from_tracks", "TrackUtterance", "PdfSet", "IndexUtterance", "IndexStreamStates",
            "UttVoc", "synthesize_batch_each", "resample", "resample_filter",
-           "loudness", "loudness_filter", "flac_encode", "synthesize_batch_each_flac",
+           "loudness", "loudness_filter", "flac_encode", "synthesize_batch_each_flac", "flac_md5", "flac_seek_geometry", "md5_host",
            "true_peak", "true_peak_filter", "PEAK_SAMPLE", "PEAK_TRUE",
            "format_pcm", "format_pcm_host", "write_wav_formatted", "synthesize_batch_each_formatted",
            "AdpcmStream", "adpcm_decode_host", "adpcm_encode", "adpcm_encode_host", "adpcm_geometry", "write_wav_adpcm",

@@ -154,6 +154,24 @@ def flac_opts(block_size: int = 0, max_lpc_order=None):
     return o
 
 
+FLAC_MD5 = 1
+
+
+class FlacMeta(C.Structure):
+    """jb_flac_meta: all zero = no MD5 and no SEEKTABLE (the stream of jb_flac_opts alone)."""
+    _fields_ = [("flags", C.c_uint32), ("seek_interval_ms", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def flac_meta(md5: bool = False, seek_interval_ms: int = 0):
+    """FlacMeta for (md5, seek_interval_ms); None where neither is asked for (the entries without _meta)."""
+    if not md5 and not seek_interval_ms:
+        return None
+    m = FlacMeta()
+    m.flags = FLAC_MD5 if md5 else 0
+    m.seek_interval_ms = int(seek_interval_ms)
+    return m
+
+
 class FormatOpts(C.Structure):
     """jb_format_opts: the output sample format, its dither and the dither's seed."""
     _fields_ = [("format", C.c_uint32), ("dither", C.c_uint32), ("seed", C.c_uint64)]
@@ -226,6 +244,9 @@ SYMBOLS = [
     "jb_batch_set_flac", "jb_batch_flac_size", "jb_batch_read_flac", "jb_batch_read_flac_all",
     "jb_flac_encode_pcm_batch", "jb_flac_free", "jb_synthesize_flac", "jb_synthesize_batch_flac",
     "jb_synthesize_batch_each_flac",
+    "jb_batch_set_flac_meta", "jb_flac_encode_pcm_batch_meta", "jb_flac_md5_pcm_batch", "jb_md5_host",
+    "jb_flac_seek_geometry", "jb_synthesize_flac_meta", "jb_synthesize_batch_flac_meta",
+    "jb_synthesize_batch_each_flac_meta",
     "jb_batch_set_peak_mode", "jb_batch_loudness_report", "jb_true_peak_filter", "jb_true_peak_pcm_batch",
     "jb_engine_set_peak_mode", "jb_engine_get_peak_mode",
     "jb_engine_set_tree_search", "jb_engine_get_tree_search", "jb_engine_device_searched_labels",
@@ -392,6 +413,18 @@ def lib():
                                            C.POINTER(u8p), C.POINTER(sz)]
     L.jb_synthesize_batch_each_flac.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
                                                 fop, C.POINTER(u8p), C.POINTER(sz)]
+    fmp, i16pp = C.POINTER(FlacMeta), C.POINTER(C.POINTER(C.c_int16))
+    L.jb_batch_set_flac_meta.argtypes = [vp, fmp]
+    L.jb_flac_encode_pcm_batch_meta.argtypes = [i16pp, C.POINTER(sz), sz, C.c_uint32, fop, fmp, C.c_int32,
+                                                C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_flac_md5_pcm_batch.argtypes = [i16pp, C.POINTER(sz), sz, C.c_int32, vp]
+    L.jb_md5_host.argtypes = [vp, sz, vp]
+    L.jb_flac_seek_geometry.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
+    L.jb_synthesize_flac_meta.argtypes = [vp, C.POINTER(C.c_char_p), sz, fop, fmp, C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_synthesize_batch_flac_meta.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, fop, fmp,
+                                                C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_synthesize_batch_each_flac_meta.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz,
+                                                     C.c_int32, fop, fmp, C.POINTER(u8p), C.POINTER(sz)]
     mop = C.POINTER(FormatOpts)
     L.jb_format_bytes_per_sample.argtypes = [C.c_uint32]
     L.jb_format_bytes_per_sample.restype = sz
@@ -530,8 +563,10 @@ def take_flac(L, bufs, ns, n):
     return out
 
 
-def flac_encode(pcms, hz: int, block_size: int = 0, max_lpc_order=None, device: int = -1):
-    """jb_flac_encode_pcm_batch: one FLAC stream (bytes) per int16 array of `pcms` at hz, encoded on the GPU."""
+def flac_encode(pcms, hz: int, block_size: int = 0, max_lpc_order=None, device: int = -1, md5: bool = False,
+                seek_interval_ms: int = 0):
+    """jb_flac_encode_pcm_batch[_meta]: one FLAC stream (bytes) per int16 array of `pcms` at hz, encoded on the GPU;
+    md5: the samples' MD5 in STREAMINFO; seek_interval_ms > 0: a SEEKTABLE with a point about that often."""
     import numpy as np
 
     arrs = [np.ascontiguousarray(a, dtype=np.int16) for a in pcms]
@@ -541,9 +576,45 @@ def flac_encode(pcms, hz: int, block_size: int = 0, max_lpc_order=None, device: 
     ins = (i16p * max(n, 1))(*[a.ctypes.data_as(i16p) for a in arrs])
     nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
     bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-    opts = flac_opts(block_size, max_lpc_order)
-    check(L.jb_flac_encode_pcm_batch(ins, nin, n, hz, C.byref(opts), device, bufs, ns))
+    opts, meta = flac_opts(block_size, max_lpc_order), flac_meta(md5, seek_interval_ms)
+    if meta is None:
+        check(L.jb_flac_encode_pcm_batch(ins, nin, n, hz, C.byref(opts), device, bufs, ns))
+    else:
+        check(L.jb_flac_encode_pcm_batch_meta(ins, nin, n, hz, C.byref(opts), C.byref(meta), device, bufs, ns))
     return take_flac(L, bufs, ns, n)
+
+
+def flac_md5(pcms, device: int = -1):
+    """jb_flac_md5_pcm_batch: the MD5 digest (16 bytes) of each int16 array of `pcms` as little-endian bytes, on the
+    GPU."""
+    import numpy as np
+
+    arrs = [np.ascontiguousarray(a, dtype=np.int16) for a in pcms]
+    n = len(arrs)
+    i16p = C.POINTER(C.c_int16)
+    ins = (i16p * max(n, 1))(*[a.ctypes.data_as(i16p) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    out = C.create_string_buffer(16 * max(n, 1))
+    check(lib().jb_flac_md5_pcm_batch(ins, nin, n, device, C.cast(out, C.c_void_p)))
+    return [out.raw[16 * u:16 * u + 16] for u in range(n)]
+
+
+def md5_host(data) -> bytes:
+    """jb_md5_host: MD5 (RFC 1321) of bytes in plain C++ on the host (no GPU)."""
+    data = bytes(data)
+    buf = C.create_string_buffer(data, max(1, len(data)))
+    out = C.create_string_buffer(16)
+    check(lib().jb_md5_host(C.cast(buf, C.c_void_p), len(data), C.cast(out, C.c_void_p)))
+    return out.raw
+
+
+def flac_seek_geometry(n_samples: int, block_size: int, hz: int, seek_interval_ms: int):
+    """jb_flac_seek_geometry: (frames between two seek points, points, bytes in front of the first frame) of a
+    stream (host only)."""
+    step, pts, hdr = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().jb_flac_seek_geometry(n_samples, block_size, hz, seek_interval_ms, C.byref(step), C.byref(pts),
+                                      C.byref(hdr)))
+    return step.value, pts.value, hdr.value
 
 
 def take_formatted(L, bufs, ns, n):

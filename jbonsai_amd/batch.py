@@ -391,11 +391,20 @@ class Batch:
         F.check(self._L.jb_batch_loudness_report(self._h, i, C.byref(r)))
         return {k: getattr(r, k) for k, _ in F.LoudnessReport._fields_}
 
-    def set_flac(self, block_size: int = 0, max_lpc_order=None):
+    def set_flac(self, block_size: int = 0, max_lpc_order=None, md5: bool = False, seek_interval_ms: int = 0):
         """jb_batch_set_flac: the run also encodes each utterance's 16-bit output as a FLAC stream (pcm_i16=True,
-        not mlpg_only; before the first run only).  Defaults: block size 4096, LPC order up to 8."""
+        not mlpg_only; before the first run only).  Defaults: block size 4096, LPC order up to 8.  md5 /
+        seek_interval_ms: set_flac_meta behind it."""
         opts = F.flac_opts(block_size, max_lpc_order)
         F.check(self._L.jb_batch_set_flac(self._h, C.byref(opts)))
+        if md5 or seek_interval_ms:
+            self.set_flac_meta(md5, seek_interval_ms)
+
+    def set_flac_meta(self, md5: bool = False, seek_interval_ms: int = 0):
+        """jb_batch_set_flac_meta: the streams carry the MD5 of their samples and / or a SEEKTABLE with a point about
+        every seek_interval_ms (after set_flac, before the first run)."""
+        meta = F.flac_meta(md5, seek_interval_ms) or F.FlacMeta()
+        F.check(self._L.jb_batch_set_flac_meta(self._h, C.byref(meta)))
 
     def flac(self, i) -> bytes:
         """Utterance i's FLAC stream (jb_batch_flac_size + jb_batch_read_flac)."""

@@ -2574,6 +2574,13 @@ int jb_batch_set_flac(jb_batch *hb, const jb_flac_opts *opts)
     return ((Batch *)hb)->out.set_flac(opts);
 }
 
+int jb_batch_set_flac_meta(jb_batch *hb, const jb_flac_meta *m)
+{
+    if (!hb)
+        return JB_ERR_INVALID;
+    return ((Batch *)hb)->out.set_flac_meta(m);
+}
+
 int jb_batch_flac_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 {
     Batch *b = (Batch *)hb;

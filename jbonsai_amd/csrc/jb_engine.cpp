@@ -1388,7 +1388,8 @@ int jb_write_wav_f64(const char *path, const double *pcm, size_t n, uint32_t fs)
 int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                               int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads,
                               const jb_engine *const *each, bool flac, const jb_flac_opts *flac_opts,
-                              const jb_format_opts *fmt_opts, const jb_adpcm_opts *adpcm_opts, size_t *adpcm_samples)
+                              const jb_format_opts *fmt_opts, const jb_adpcm_opts *adpcm_opts, size_t *adpcm_samples,
+                              const jb_flac_meta *flac_meta)
 {
     auto eng = [&](size_t u) { return CENG(each ? each[u] : e); }; // the engine of utterance u
     if (!e || !pcm || !n_samples || (n_utts && !line_off))
@@ -1575,7 +1576,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             return rc;
         if (any_true && (rc = b->out.set_peak_mode(modes.data(), modes.size())))
             return rc;
-        if (flac && (rc = b->out.set_flac(flac_opts)))
+        if (flac && ((rc = b->out.set_flac(flac_opts)) || (flac_meta && (rc = b->out.set_flac_meta(flac_meta)))))
             return rc;
         if (fmt_opts && (rc = b->out.set_format(fmt_opts)))
             return rc;
@@ -1823,7 +1824,7 @@ static int synthesize_each(const jb_engine *const *engines, const char *const *l
                            size_t n_utts, int32_t device, size_t elem, void **pcm, size_t *n_samples,
                            bool flac = false, const jb_flac_opts *flac_opts = nullptr,
                            const jb_format_opts *fmt_opts = nullptr, const jb_adpcm_opts *adpcm_opts = nullptr,
-                           size_t *adpcm_samples = nullptr)
+                           size_t *adpcm_samples = nullptr, const jb_flac_meta *flac_meta = nullptr)
 {
     if (!pcm || !n_samples || (n_utts && !line_off))
         return JB_ERR_INVALID;
@@ -1833,7 +1834,7 @@ static int synthesize_each(const jb_engine *const *engines, const char *const *l
     if (rc)
         return rc;
     return jb::synthesize_batch_impl(engines[0], lines, line_off, n_utts, device, elem, pcm, n_samples, 0, engines,
-                                     flac, flac_opts, fmt_opts, adpcm_opts, adpcm_samples);
+                                     flac, flac_opts, fmt_opts, adpcm_opts, adpcm_samples, flac_meta);
 }
 
 extern "C" {
@@ -1850,34 +1851,54 @@ int jb_synthesize_batch_each_i16(const jb_engine *const *engines, const char *co
     return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)pcm, n_samples);
 }
 
+int jb_synthesize_batch_flac_meta(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                  int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta, uint8_t **flac,
+                                  size_t *n_bytes)
+{
+    int rc = jb::flac_check_opts(opts, nullptr);
+    if (rc || (rc = jb::flac_check_meta(meta, nullptr)))
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, 0,
+                                     nullptr, true, opts, nullptr, nullptr, nullptr, meta);
+}
+
 int jb_synthesize_batch_flac(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                              int32_t device, const jb_flac_opts *opts, uint8_t **flac, size_t *n_bytes)
 {
+    return jb_synthesize_batch_flac_meta(e, lines, line_off, n_utts, device, opts, nullptr, flac, n_bytes);
+}
+
+int jb_synthesize_batch_each_flac_meta(const jb_engine *const *engines, const char *const *lines,
+                                       const size_t *line_off, size_t n_utts, int32_t device, const jb_flac_opts *opts,
+                                       const jb_flac_meta *meta, uint8_t **flac, size_t *n_bytes)
+{
     int rc = jb::flac_check_opts(opts, nullptr);
-    if (rc)
+    if (rc || (rc = jb::flac_check_meta(meta, nullptr)))
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, 0,
-                                     nullptr, true, opts);
+    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, true,
+                           opts, nullptr, nullptr, nullptr, meta);
 }
 
 int jb_synthesize_batch_each_flac(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
                                   size_t n_utts, int32_t device, const jb_flac_opts *opts, uint8_t **flac,
                                   size_t *n_bytes)
 {
-    int rc = jb::flac_check_opts(opts, nullptr);
-    if (rc)
-        return rc;
-    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, true,
-                           opts);
+    return jb_synthesize_batch_each_flac_meta(engines, lines, line_off, n_utts, device, opts, nullptr, flac, n_bytes);
+}
+
+int jb_synthesize_flac_meta(const jb_engine *e, const char *const *lines, size_t n, const jb_flac_opts *opts,
+                            const jb_flac_meta *meta, uint8_t **flac, size_t *n_bytes)
+{
+    if (!flac || !n_bytes)
+        return JB_ERR_INVALID;
+    size_t off[2] = {0, n};
+    return jb_synthesize_batch_flac_meta(e, lines, off, 1, -1, opts, meta, flac, n_bytes);
 }
 
 int jb_synthesize_flac(const jb_engine *e, const char *const *lines, size_t n, const jb_flac_opts *opts,
                        uint8_t **flac, size_t *n_bytes)
 {
-    if (!flac || !n_bytes)
-        return JB_ERR_INVALID;
-    size_t off[2] = {0, n};
-    return jb_synthesize_batch_flac(e, lines, off, 1, -1, opts, flac, n_bytes);
+    return jb_synthesize_flac_meta(e, lines, n, opts, nullptr, flac, n_bytes);
 }
 
 static int check_format_entry(const jb_format_opts *opts, const char *who)

@@ -1,8 +1,10 @@
 // FLAC encoding of the 16-bit output (new surface: the reference writes WAV only).  The contract is in
 // include/jbonsai_amd.h ("FLAC"); in short: one complete mono 16-bit FLAC stream per utterance, fixed block size,
-// streamable subset, MD5 left zero, decode(stream) == the 16-bit PCM bit for bit.
+// streamable subset, decode(stream) == the 16-bit PCM bit for bit; on request the MD5 of the samples in STREAMINFO
+// and a SEEKTABLE (the rules: jb_md5.h).
 //
-// Five kernels (launch_flac_encode, then launch_flac_pack):
+// Five kernels (launch_flac_encode, then launch_flac_pack), and two more on request (launch_flac_md5 in front of
+// the pack, k_flac_seektable inside it):
 //   k_flac_encode   one workgroup per block (<= 4608 samples, staged in LDS): CONSTANT test; FIXED 0-4 and LPC at
 //                   a fixed set of orders (Tukey(0.5) window, autocorrelation, Levinson-Durbin and coefficient
 //                   quantization in f64, every sum in a fixed order) each priced by partitioned Rice on the
@@ -12,11 +14,18 @@
 //                   code touches more than two words).  The CRC-16 is parallel: every thread's byte segment from
 //                   zero state, joined by multiplication with x^(8 len) mod the polynomial (the CRC is linear:
 //                   zero init, no final xor).  The frame goes to its block's slot (the VERBATIM bound apart).
+//   k_flac_md5      one lane per utterance (a chain cannot be split: the batch is the parallelism), the launch list
+//                   longest first so that a wave's 64 chains have similar lengths.  A lane reads its 64-byte blocks
+//                   as aligned dwords, shifted by a half-word where the utterance starts on an odd sample, one block
+//                   ahead of the one it hashes; the last one or two blocks (the samples left, 0x80, zeros, the bit
+//                   count) are built in registers from guarded 16-bit loads: nothing behind sample n - 1 is read.
 //   k_flac_scan     one workgroup per utterance: frame offsets, stream size, min and max frame size.
 //   k_flac_place    one workgroup: each utterance's place in the compact slab (a scan in utterance order).
-//   k_flac_header / k_flac_compact: the 42-byte stream header (fLaC + STREAMINFO) and one workgroup per frame
-//                   copying it from its slot to its byte offset: whole words inside, byte stores at a head and a
-//                   tail that may share a word with a neighbour.
+//   k_flac_header / k_flac_compact: the 42-byte stream header (fLaC + STREAMINFO, the digest in it on request) and
+//                   one workgroup per frame copying it from its slot to its byte offset: whole words inside, byte
+//                   stores at a head and a tail that may share a word with a neighbour.
+//   k_flac_seektable  one thread per seek point (launched only where some utterance has points): sample number,
+//                   byte offset from the first frame's header, samples of the frame, from k_flac_scan's offsets.
 // A stream's bytes are a function of its samples, its rate and the options alone (the fast invariant mode stays
 // invariant): the block is the unit of every choice, and no result depends on the batch.
 #include "jb_host.h"
@@ -621,7 +630,7 @@ __global__ __launch_bounds__(kT) void k_flac_encode(FlacParams P, const FlacUtt 
         slot[w] = __builtin_bswap32(bits[w]);
 }
 
-// Per utterance: frame offsets in its stream (after the 42-byte header), size, min and max frame size
+// Per utterance: frame offsets in its stream (after its header), size, min and max frame size
 __global__ __launch_bounds__(kT) void k_flac_scan(const FlacUtt *__restrict__ utts, const uint32_t *__restrict__ fsize,
                                                   uint64_t *__restrict__ foff, FlacOut *__restrict__ out)
 {
@@ -648,13 +657,13 @@ __global__ __launch_bounds__(kT) void k_flac_scan(const FlacUtt *__restrict__ ut
         atomicMax(&mx, lmx);
     }
     uint64_t tot;
-    uint64_t off = kFlacHeaderBytes + block_excl_scan<uint64_t>(acc, wsum, &tot);
+    uint64_t off = U.header_bytes + block_excl_scan<uint64_t>(acc, wsum, &tot);
     for (uint32_t f = lo; f < hi; f++) {
         foff[U.frame0 + f] = off;
         off += fsize[U.frame0 + f];
     }
     if (t == 0) {
-        out[blockIdx.x].bytes = kFlacHeaderBytes + tot;
+        out[blockIdx.x].bytes = U.header_bytes + tot;
         out[blockIdx.x].min_frame = nf ? mn : 0;
         out[blockIdx.x].max_frame = nf ? mx : 0;
     }
@@ -679,10 +688,12 @@ __global__ __launch_bounds__(kT) void k_flac_place(FlacOut *__restrict__ out, ui
         *total = tot;
 }
 
-// fLaC, the STREAMINFO block header (last, type 0, 34 bytes) and STREAMINFO; byte stores (the first frame may share
-// the last word)
+// fLaC, the STREAMINFO block header (type 0, 34 bytes; last unless a SEEKTABLE follows) and STREAMINFO, its MD5 from
+// digests (null: zeros, "not computed"), then the SEEKTABLE's block header (last, type 3) where the utterance has
+// points; byte stores (the first frame may share the last word)
 __global__ __launch_bounds__(kT) void k_flac_header(FlacParams P, const FlacUtt *__restrict__ utts, uint32_t n,
-                                                    const FlacOut *__restrict__ out, uint8_t *__restrict__ dst)
+                                                    const FlacOut *__restrict__ out, const uint32_t *__restrict__ digests,
+                                                    uint8_t *__restrict__ dst)
 {
     const uint32_t u = blockIdx.x * kT + threadIdx.x;
     if (u >= n)
@@ -692,16 +703,67 @@ __global__ __launch_bounds__(kT) void k_flac_header(FlacParams P, const FlacUtt 
     // 20 bits rate, 3 bits channels - 1, 5 bits depth - 1, 36 bits total samples
     const uint64_t v = ((uint64_t)U.hz << 44) | (15ull << 36) | (U.n & 0xfffffffffull);
     const uint64_t bs = P.block_size, mn = o.min_frame, mx = o.max_frame;
-    const uint64_t w[4] = {0x664C614380000022ull, // fLaC, last block, type 0, 34 bytes
+    const uint64_t w[4] = {U.n_points ? 0x664C614300000022ull : 0x664C614380000022ull, // fLaC, (last,) type 0, 34 bytes
                            (bs << 48) | (bs << 32) | (mn << 8) | (mx >> 16), ((mx & 0xffffull) << 48) | (v >> 16),
                            (v & 0xffffull) << 48};
     uint8_t *d = dst + o.off;
 #pragma unroll
     for (int k = 0; k < 32; k++)
         d[k] = (uint8_t)(w[k >> 3] >> (56 - 8 * (k & 7)));
+    // bytes 26..41: A, B, C, D of the digest, each little-endian
 #pragma unroll
-    for (int k = 32; k < (int)kFlacHeaderBytes; k++)
-        d[k] = 0; // MD5: not computed
+    for (int k = 0; k < 16; k++)
+        d[26 + k] = digests ? (uint8_t)(digests[4 * (size_t)u + (k >> 2)] >> (8 * (k & 3))) : 0;
+    if (U.n_points) {
+        const uint32_t len = kFlacSeekPointBytes * U.n_points;
+        d[42] = 0x83;
+        d[43] = (uint8_t)(len >> 16);
+        d[44] = (uint8_t)(len >> 8);
+        d[45] = (uint8_t)len;
+    }
+}
+
+// Seek point p of utterance blockIdx.x: frame p * seek_step
+__global__ __launch_bounds__(kT) void k_flac_seektable(FlacParams P, const FlacUtt *__restrict__ utts,
+                                                       const uint64_t *__restrict__ foff,
+                                                       const FlacOut *__restrict__ out, uint8_t *__restrict__ dst)
+{
+    const FlacUtt &U = utts[blockIdx.x];
+    const uint32_t p = blockIdx.y * kT + threadIdx.x;
+    if (p >= U.n_points)
+        return;
+    const uint64_t f = (uint64_t)p * U.seek_step, s0 = f * P.block_size;
+    const uint64_t off = foff[U.frame0 + f] - U.header_bytes;
+    const uint32_t cnt = (uint32_t)std::min<uint64_t>(P.block_size, U.n - s0);
+    uint8_t *d = dst + out[blockIdx.x].off + kFlacStreamInfoBytes + 4 + (uint64_t)kFlacSeekPointBytes * p;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        d[k] = (uint8_t)(s0 >> (56 - 8 * k));
+        d[8 + k] = (uint8_t)(off >> (56 - 8 * k));
+    }
+    d[16] = (uint8_t)(cnt >> 8);
+    d[17] = (uint8_t)cnt;
+}
+
+#define JB_FLAC_GLOBAL __attribute__((address_space(1)))
+
+// One lane per utterance of the list: the chain of jb_md5.h over its samples, the digest by plain stores
+__global__ __launch_bounds__(64) void k_flac_md5(const FlacUtt *__restrict__ utts, const uint32_t *__restrict__ order,
+                                                 uint32_t n_order, uint32_t *__restrict__ digests)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_order)
+        return;
+    const uint32_t u = order[i];
+    const JB_FLAC_GLOBAL int16_t *x = (const JB_FLAC_GLOBAL int16_t *)utts[u].x;
+    const JB_FLAC_GLOBAL uint32_t *w = (const JB_FLAC_GLOBAL uint32_t *)((uintptr_t)x & ~(uintptr_t)3);
+    uint32_t st[4];
+    md5_samples(
+        utts[u].n, ((uintptr_t)x & 2u) != 0, [&](uint64_t k) { return w[k]; }, [&](uint64_t k) { return x[k]; }, st);
+    JB_FLAC_GLOBAL uint32_t *d = (JB_FLAC_GLOBAL uint32_t *)digests + 4 * (size_t)u;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        d[j] = st[j];
 }
 
 __global__ __launch_bounds__(kT) void k_flac_compact(FlacParams P, const FlacUtt *__restrict__ utts,
@@ -731,100 +793,6 @@ __global__ __launch_bounds__(kT) void k_flac_compact(FlacParams P, const FlacUtt
 }
 } // namespace
 
-uint32_t flac_slot_bytes(uint32_t bs) { return ((16u + 1u + 2u * bs + 2u + 3u) & ~3u) + 4u; }
-
-int flac_check_opts(const jb_flac_opts *o, FlacParams *p)
-{
-    FlacParams r{};
-    r.block_size = kFlacDefaultBlock;
-    r.max_order = kFlacDefaultLpc;
-    if (o) {
-        if (o->reserved[0] || o->reserved[1]) {
-            set_error("jb_flac_opts: reserved fields must be 0");
-            return JB_ERR_INVALID;
-        }
-        if (o->block_size && (o->block_size < 16 || o->block_size > kFlacMaxBlock)) {
-            set_error("jb_flac_opts: block_size must be 16..4608 (0: 4096)");
-            return JB_ERR_INVALID;
-        }
-        if (o->max_lpc_order > kFlacMaxLpc) {
-            set_error("jb_flac_opts: max_lpc_order must be 0..12");
-            return JB_ERR_INVALID;
-        }
-        if (o->block_size)
-            r.block_size = o->block_size;
-        // zeros: the defaults; a block size alone keeps the default order (max_lpc_order 0 with a block size: none)
-        if (o->block_size || o->max_lpc_order)
-            r.max_order = o->max_lpc_order;
-    }
-    r.slot_bytes = flac_slot_bytes(r.block_size);
-    if (p)
-        *p = r;
-    return JB_OK;
-}
-
-int flac_rate_code(uint32_t hz, uint32_t *code, uint32_t *bits, uint32_t *val)
-{
-    static const uint32_t table[][2] = {{88200, 1}, {176400, 2}, {192000, 3}, {8000, 4},   {16000, 5}, {22050, 6},
-                                        {24000, 7}, {32000, 8},   {44100, 9},  {48000, 10}, {96000, 11}};
-    *bits = 0;
-    *val = 0;
-    for (const auto &e : table)
-        if (e[0] == hz) {
-            *code = e[1];
-            return JB_OK;
-        }
-    if (hz % 1000 == 0 && hz / 1000 <= 255 && hz) {
-        *code = 12, *bits = 8, *val = hz / 1000;
-    } else if (hz && hz <= 65535) {
-        *code = 13, *bits = 16, *val = hz;
-    } else if (hz && hz % 10 == 0 && hz / 10 <= 65535) {
-        *code = 14, *bits = 16, *val = hz / 10;
-    } else {
-        set_error("FLAC: a rate of " + std::to_string(hz) + " Hz has no frame-header code");
-        return JB_ERR_UNSUPPORTED;
-    }
-    return JB_OK;
-}
-
-int flac_plan(const FlacParams &p, const int16_t *const *x, const uint64_t *n, const uint32_t *hz, size_t n_utts,
-              std::vector<FlacUtt> *utts, std::vector<FlacWork> *work, uint64_t *slot_bytes, uint64_t *out_bound)
-{
-    utts->assign(n_utts, FlacUtt{});
-    work->clear();
-    uint64_t frames = 0, slots = 0, bound = 0;
-    for (size_t u = 0; u < n_utts; u++) {
-        FlacUtt &w = (*utts)[u];
-        int rc = flac_rate_code(hz[u], &w.rate_code, &w.rate_bits, &w.rate_val);
-        if (rc)
-            return rc;
-        if (n[u] > 0xfffffffffull) {
-            set_error("FLAC: an utterance longer than 2^36 samples");
-            return JB_ERR_UNSUPPORTED;
-        }
-        w.x = x[u];
-        w.n = n[u];
-        w.hz = hz[u];
-        w.nframes = (uint32_t)((n[u] + p.block_size - 1) / p.block_size);
-        w.frame0 = frames;
-        w.slots = (uint8_t *)(uintptr_t)slots; // an offset until the slab exists (flac_bind)
-        for (uint32_t f = 0; f < w.nframes; f++)
-            work->push_back(FlacWork{(uint32_t)u, f});
-        frames += w.nframes;
-        slots += (uint64_t)w.nframes * p.slot_bytes;
-        bound += kFlacHeaderBytes + (uint64_t)w.nframes * p.slot_bytes;
-    }
-    *slot_bytes = slots;
-    *out_bound = bound;
-    return JB_OK;
-}
-
-void flac_bind(std::vector<FlacUtt> *utts, uint8_t *slots)
-{
-    for (auto &w : *utts)
-        w.slots = slots + (uintptr_t)w.slots;
-}
-
 hipError_t launch_flac_encode(const FlacParams &p, const FlacUtt *utts, const FlacWork *work, uint32_t n_work,
                               uint32_t *fsize, hipStream_t stream)
 {
@@ -833,15 +801,27 @@ hipError_t launch_flac_encode(const FlacParams &p, const FlacUtt *utts, const Fl
     return hipGetLastError();
 }
 
+hipError_t launch_flac_md5(const FlacUtt *utts, const uint32_t *order, uint32_t n_order, uint32_t *digests,
+                           hipStream_t stream)
+{
+    if (n_order)
+        hipLaunchKernelGGL(k_flac_md5, dim3((n_order + 63) / 64), dim3(64), 0, stream, utts, order, n_order, digests);
+    return hipGetLastError();
+}
+
 hipError_t launch_flac_pack(const FlacParams &p, const FlacUtt *utts, uint32_t n_utts, const FlacWork *work,
                             uint32_t n_frames, const uint32_t *fsize, uint64_t *foff, FlacOut *out, uint64_t *total,
-                            uint8_t *dst, hipStream_t stream)
+                            uint8_t *dst, hipStream_t stream, const uint32_t *digests, uint32_t max_points)
 {
     if (!n_utts)
         return hipSuccess;
     hipLaunchKernelGGL(k_flac_scan, dim3(n_utts), dim3(kT), 0, stream, utts, fsize, foff, out);
     hipLaunchKernelGGL(k_flac_place, dim3(1), dim3(kT), 0, stream, out, n_utts, total);
-    hipLaunchKernelGGL(k_flac_header, dim3((n_utts + kT - 1) / kT), dim3(kT), 0, stream, p, utts, n_utts, out, dst);
+    hipLaunchKernelGGL(k_flac_header, dim3((n_utts + kT - 1) / kT), dim3(kT), 0, stream, p, utts, n_utts, out,
+                       digests, dst);
+    if (max_points)
+        hipLaunchKernelGGL(k_flac_seektable, dim3(n_utts, (max_points + kT - 1) / kT), dim3(kT), 0, stream, p, utts,
+                           foff, out, dst);
     if (n_frames)
         hipLaunchKernelGGL(k_flac_compact, dim3(n_frames), dim3(kT), 0, stream, p, utts, work, fsize, foff, out, dst);
     return hipGetLastError();
@@ -853,13 +833,16 @@ using namespace jb;
 
 extern "C" {
 
-int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, uint32_t hz,
-                             const jb_flac_opts *opts, int32_t device, uint8_t **out, size_t *n_out)
+int jb_flac_encode_pcm_batch_meta(const int16_t *const *in, const size_t *n_in, size_t n, uint32_t hz,
+                                  const jb_flac_opts *opts, const jb_flac_meta *meta, int32_t device, uint8_t **out,
+                                  size_t *n_out)
 {
     FlacParams p{};
+    FlacMeta m{};
     int rc = flac_check_opts(opts, &p);
-    if (rc)
+    if (rc || (rc = flac_check_meta(meta, &m)))
         return rc;
+    const bool md5 = (m.flags & kFlacMetaMd5) != 0;
     if (n && (!in || !n_in || !out || !n_out))
         return JB_ERR_INVALID;
     if (n > 0x7fffffffu)
@@ -899,10 +882,13 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
     FlacWork *dw = nullptr;
     uint32_t *dfs = nullptr;
     uint64_t *dfo = nullptr, *dtot = nullptr;
+    uint32_t *dord = nullptr, *ddig = nullptr;
     FlacOut *dres = nullptr;
     hipStream_t s = nullptr;
     std::vector<FlacUtt> utts;
     std::vector<FlacWork> work;
+    std::vector<uint32_t> order;
+    uint32_t max_points = 0;
     std::vector<FlacOut> res(n);
     std::vector<uint8_t> host;
     uint64_t slot_bytes = 0, bound = 0, total = 0;
@@ -912,8 +898,16 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
         xs[u] = dx + off;
         off += n_in[u];
     }
-    if (e == hipSuccess && (rc = flac_plan(p, xs.data(), ns.data(), hzs.data(), n, &utts, &work, &slot_bytes, &bound)))
+    if (e == hipSuccess &&
+        (rc = flac_plan(p, m, xs.data(), ns.data(), hzs.data(), n, &utts, &work, &slot_bytes, &bound)))
         e = hipErrorInvalidValue;
+    for (const FlacUtt &w : utts)
+        max_points = std::max(max_points, w.n_points);
+    if (e == hipSuccess && md5) {
+        flac_md5_order(utts, nullptr, &order);
+        if ((e = scratch.alloc(&dord, std::max<size_t>(n, 1))) == hipSuccess)
+            e = scratch.alloc(&ddig, 4 * std::max<size_t>(n, 1));
+    }
     if (e == hipSuccess) {
         e = scratch.open_stream();
         s = scratch.stream;
@@ -947,10 +941,15 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
     }
     if (e == hipSuccess && !work.empty())
         e = hipMemcpyAsync(dw, work.data(), sizeof(FlacWork) * work.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && !order.empty())
+        e = hipMemcpyAsync(dord, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
         e = launch_flac_encode(p, du, dw, (uint32_t)work.size(), dfs, s);
+    if (e == hipSuccess && md5)
+        e = launch_flac_md5(du, dord, (uint32_t)order.size(), ddig, s);
     if (e == hipSuccess)
-        e = launch_flac_pack(p, du, (uint32_t)n, dw, (uint32_t)work.size(), dfs, dfo, dres, dtot, dout, s);
+        e = launch_flac_pack(p, du, (uint32_t)n, dw, (uint32_t)work.size(), dfs, dfo, dres, dtot, dout, s,
+                             md5 ? ddig : nullptr, max_points);
     if (e == hipSuccess && n)
         e = hipMemcpyAsync(res.data(), dres, sizeof(FlacOut) * n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && n)
@@ -979,6 +978,77 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
         memcpy(out[u], host.data() + res[u].off, res[u].bytes);
         n_out[u] = res[u].bytes;
     }
+    return JB_OK;
+}
+
+int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, uint32_t hz,
+                             const jb_flac_opts *opts, int32_t device, uint8_t **out, size_t *n_out)
+{
+    return jb_flac_encode_pcm_batch_meta(in, n_in, n, hz, opts, nullptr, device, out, n_out);
+}
+
+int jb_flac_md5_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, int32_t device, uint8_t *digests)
+{
+    if (n && (!in || !n_in || !digests))
+        return JB_ERR_INVALID;
+    if (n > 0x7fffffffu)
+        return JB_ERR_INVALID;
+    uint64_t samples = 0;
+    for (size_t u = 0; u < n; u++) {
+        if (n_in[u] && !in[u])
+            return JB_ERR_INVALID;
+        samples += n_in[u];
+    }
+    if (!n)
+        return JB_OK;
+    int dev = device, prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
+        set_error("no HIP device");
+        return JB_ERR_DEVICE;
+    }
+    DeviceScratch scratch;
+    if (scratch.enter(dev) != hipSuccess) {
+        set_error("hipSetDevice failed");
+        return JB_ERR_DEVICE;
+    }
+    // the inputs packed one after the other, as a batch's 16-bit slab has them: a start is only 2-byte aligned
+    int16_t *dx = nullptr;
+    FlacUtt *du = nullptr;
+    uint32_t *dord = nullptr, *ddig = nullptr;
+    std::vector<FlacUtt> utts(n);
+    std::vector<uint32_t> order, dig(4 * n);
+    hipError_t e = scratch.open_stream();
+    hipStream_t s = scratch.stream;
+    if (e == hipSuccess)
+        e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
+    if (e == hipSuccess)
+        e = scratch.alloc(&du, n);
+    if (e == hipSuccess)
+        e = scratch.alloc(&dord, n);
+    if (e == hipSuccess)
+        e = scratch.alloc(&ddig, 4 * n);
+    uint64_t off = 0;
+    for (size_t u = 0; u < n && e == hipSuccess; u++) {
+        utts[u].x = dx + off;
+        utts[u].n = n_in[u];
+        if (n_in[u])
+            e = hipMemcpyAsync(dx + off, in[u], sizeof(int16_t) * n_in[u], hipMemcpyHostToDevice, s);
+        off += n_in[u];
+    }
+    flac_md5_order(utts, nullptr, &order);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(du, utts.data(), sizeof(FlacUtt) * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(dord, order.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = launch_flac_md5(du, dord, (uint32_t)n, ddig, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(dig.data(), ddig, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (e != hipSuccess)
+        return hip_fail(e, "jb_flac_md5_pcm_batch");
+    memcpy(digests, dig.data(), 16 * n); // A, B, C, D little-endian: the digest's byte order (a little-endian host)
     return JB_OK;
 }
 

@@ -4,6 +4,7 @@
 #include "jb_device.h"
 #include "jb_adpcm.h"
 #include "jb_format.h"
+#include "jb_md5.h"
 #include "jb_output.h"
 
 #include <map>
@@ -36,12 +37,14 @@ void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE
 // e = each[0] for what the engines share; flac (elem 2): pcm[u] / n_samples[u] receive utterance u's FLAC stream
 // and its byte count instead (jb_synthesize*_flac); fmt_opts (elem 8): its bytes in that sample format and their
 // count (jb_synthesize*_formatted); adpcm_opts (elem 2): its IMA ADPCM blocks and their byte count, the samples they
-// encode in adpcm_samples[u] where that is not null (jb_synthesize*_adpcm)
+// encode in adpcm_samples[u] where that is not null (jb_synthesize*_adpcm); flac_meta: the streams' MD5 / SEEKTABLE
+// request (jb_synthesize*_flac_meta; null: none)
 int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                           int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0,
                           const jb_engine *const *each = nullptr, bool flac = false,
                           const jb_flac_opts *flac_opts = nullptr, const jb_format_opts *fmt_opts = nullptr,
-                          const jb_adpcm_opts *adpcm_opts = nullptr, size_t *adpcm_samples = nullptr);
+                          const jb_adpcm_opts *adpcm_opts = nullptr, size_t *adpcm_samples = nullptr,
+                          const jb_flac_meta *flac_meta = nullptr);
 // A stream / a device block from the per-device pools that batches draw from (jb_batch.cpp), for work outside a
 // batch; *got is the block's pooled size, which pooled_block_free takes back
 hipError_t pooled_stream_acquire(int device, hipStream_t *st);
@@ -139,11 +142,11 @@ hipError_t launch_loudness_measure(const LoudnessRate *rates_dev, const Loudness
 hipError_t launch_loudness_apply(const LoudnessUtt *utts_dev, uint32_t n, uint64_t atiles, const LoudnessResult *res,
                                  bool i16, hipStream_t stream);
 
-// FLAC encoding of the 16-bit output (jb_flac.hip).  One stream per utterance: a 42-byte header, then frames of
+// FLAC encoding of the 16-bit output (jb_flac.hip; the host half: jb_flac.cpp).  One stream per utterance: its header
+// (42 bytes: fLaC + STREAMINFO; with a SEEKTABLE request that block behind it, jb_md5.h), then frames of
 // block_size samples (the last may be shorter), each encoded into its block's slot (the VERBATIM bound apart), then
 // packed at byte offsets into one compact slab, utterance after utterance
 constexpr uint32_t kFlacMaxBlock = 4608, kFlacMaxLpc = 12, kFlacDefaultBlock = 4096, kFlacDefaultLpc = 8;
-constexpr uint32_t kFlacHeaderBytes = 42; // fLaC + STREAMINFO
 struct FlacParams {
     uint32_t block_size, max_order, slot_bytes, pad_;
 };
@@ -151,7 +154,9 @@ struct FlacUtt {
     const int16_t *x; // the utterance's 16-bit PCM
     uint8_t *slots;   // frame f at slots + f * slot_bytes
     uint64_t n, frame0; // samples; first frame's index in the per-frame arrays
-    uint32_t nframes, hz, rate_code, rate_bits, rate_val, pad_;
+    uint32_t nframes, hz, rate_code, rate_bits, rate_val;
+    uint32_t header_bytes;        // bytes in front of the first frame: 42, or 46 + 18 n_points
+    uint32_t seek_step, n_points; // SEEKTABLE: frames between two points, points (0: no table)
 };
 struct FlacWork { // one block of an encode launch (a pack launch: every frame of the batch, in order)
     uint32_t utt, frame;
@@ -162,20 +167,31 @@ struct FlacOut { // per utterance: the stream's size and offset in the compact s
 };
 // opts (NULL: defaults) -> p; JB_ERR_INVALID (set_error says why) for values outside the contract
 int flac_check_opts(const jb_flac_opts *opts, FlacParams *p);
+// meta (NULL: no request) -> m; JB_ERR_INVALID for unknown flag bits or non-zero reserved words
+int flac_check_meta(const jb_flac_meta *meta, FlacMeta *m);
 uint32_t flac_slot_bytes(uint32_t block_size);
 // The frame-header rate code of hz (and its 8- or 16-bit extra field); JB_ERR_UNSUPPORTED where none exists
 int flac_rate_code(uint32_t hz, uint32_t *code, uint32_t *bits, uint32_t *val);
 // The lists of a batch of n_utts streams; slots are offsets (total *slot_bytes) until flac_bind adds the slab's
-// base; *out_bound bounds the compact slab
-int flac_plan(const FlacParams &p, const int16_t *const *x, const uint64_t *n, const uint32_t *hz, size_t n_utts,
-              std::vector<FlacUtt> *utts, std::vector<FlacWork> *work, uint64_t *slot_bytes, uint64_t *out_bound);
+// base; *out_bound bounds the compact slab; meta fills each utterance's seek step, points and header bytes
+int flac_plan(const FlacParams &p, const FlacMeta &meta, const int16_t *const *x, const uint64_t *n,
+              const uint32_t *hz, size_t n_utts, std::vector<FlacUtt> *utts, std::vector<FlacWork> *work,
+              uint64_t *slot_bytes, uint64_t *out_bound);
 void flac_bind(std::vector<FlacUtt> *utts, uint8_t *slots);
+// The MD5 launch list of the utterances `only` marks (null: all): their indices, longest first, so that the 64
+// lanes of a wave walk chains of similar length
+void flac_md5_order(const std::vector<FlacUtt> &utts, const std::vector<uint8_t> *only, std::vector<uint32_t> *order);
 hipError_t launch_flac_encode(const FlacParams &p, const FlacUtt *utts, const FlacWork *work, uint32_t n_work,
                               uint32_t *fsize, hipStream_t stream);
-// every utterance: frame offsets, sizes, places, headers, and every frame (work: all of them) into dst
+// digests[4 u ..] = MD5 of utterance u = order[i]'s samples, one lane per utterance
+hipError_t launch_flac_md5(const FlacUtt *utts, const uint32_t *order, uint32_t n_order, uint32_t *digests,
+                           hipStream_t stream);
+// every utterance: frame offsets, sizes, places, headers, and every frame (work: all of them) into dst; digests
+// (null: zeros) go into STREAMINFO; the SEEKTABLE of every utterance that has points (max_points: the most of one)
 hipError_t launch_flac_pack(const FlacParams &p, const FlacUtt *utts, uint32_t n_utts, const FlacWork *work,
                             uint32_t n_frames, const uint32_t *fsize, uint64_t *foff, FlacOut *out, uint64_t *total,
-                            uint8_t *dst, hipStream_t stream);
+                            uint8_t *dst, hipStream_t stream, const uint32_t *digests = nullptr,
+                            uint32_t max_points = 0);
 
 // Output sample formats (jb_format.hip; the rules and FormatUtt: jb_format.h): utts_dev[0..n) of `tiles` tiles in all
 hipError_t launch_format(uint32_t format, uint32_t dither, uint64_t seed, const FormatUtt *utts_dev, uint32_t n,
@@ -261,6 +277,7 @@ struct OutputChain {
     int set_loudness(const double *target, const double *ceiling, size_t n); // n == 1 or B entries each
     int set_peak_mode(const uint32_t *mode, size_t n);                       // n == 1 or B entries; needs no target
     int set_flac(const jb_flac_opts *opts);
+    int set_flac_meta(const jb_flac_meta *meta); // behind set_flac
     int set_format(const jb_format_opts *opts); // an f64 batch only
     int set_adpcm(const jb_adpcm_opts *opts);   // an f64 or a 16-bit batch
     void init();   // Batch::create: the slabs the batch was made with, the plan of no request
@@ -310,6 +327,7 @@ private:
     std::vector<double> ln_target, ln_ceiling; // [B]
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
     FlacParams flac_p{};
+    FlacMeta flac_m{}; // MD5 / SEEKTABLE request (zeros: none)
     bool frozen = false, ready = false; // the first run has begun: no more requests / its prepare() succeeded
     void *slab[(size_t)OutSlab::Count] = {};
     struct { // converter
@@ -330,8 +348,11 @@ private:
     } ln;
     struct { // FLAC
         std::vector<FlacWork> work;
+        std::vector<FlacUtt> utts; // (kept with an MD5 request: the redo's launch list is ordered by their lengths)
         FlacUtt *utts_dev = nullptr;
         FlacWork *work_dev = nullptr, *redo_dev = nullptr;
+        uint32_t *md5_order_dev = nullptr, *md5_redo_dev = nullptr, *digests = nullptr; // with an MD5 request
+        uint32_t n_md5 = 0, max_points = 0;
         uint8_t *out = nullptr;
         uint32_t *fsize = nullptr;
         uint64_t *foff = nullptr, *total = nullptr;

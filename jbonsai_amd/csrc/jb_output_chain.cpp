@@ -136,6 +136,22 @@ int OutputChain::set_flac(const jb_flac_opts *opts)
     return JB_OK;
 }
 
+int OutputChain::set_flac_meta(const jb_flac_meta *meta)
+{
+    FlacMeta m{};
+    int rc = flac_check_meta(meta, &m);
+    if (rc)
+        return rc;
+    if (!flac_on) {
+        set_error("jb_batch_set_flac_meta: call jb_batch_set_flac first");
+        return JB_ERR_INVALID;
+    }
+    if ((rc = check_settable("jb_batch_set_flac_meta: the metadata is set before the batch's first run")))
+        return rc;
+    flac_m = m; // (the plan of the slabs does not depend on it: the FLAC slabs are sized at the first run)
+    return JB_OK;
+}
+
 int OutputChain::set_format(const jb_format_opts *opts)
 {
     if (!opts) {
@@ -312,23 +328,38 @@ int OutputChain::prepare_flac()
     }
     std::vector<FlacUtt> utts;
     uint64_t slot_bytes = 0, bound = 0;
-    int rc = flac_plan(flac_p, xs.data(), ns.data(), hz.data(), B, &utts, &fl.work, &slot_bytes, &bound);
+    int rc = flac_plan(flac_p, flac_m, xs.data(), ns.data(), hz.data(), B, &utts, &fl.work, &slot_bytes, &bound);
     if (rc)
         return rc;
+    const bool md5 = (flac_m.flags & kFlacMetaMd5) != 0;
+    std::vector<uint32_t> order;
+    if (md5)
+        flac_md5_order(utts, nullptr, &order);
+    fl.n_md5 = (uint32_t)order.size();
+    fl.max_points = 0;
+    for (const FlacUtt &w : utts)
+        fl.max_points = std::max(fl.max_points, w.n_points);
     const size_t nf = std::max<size_t>(fl.work.size(), 1);
     uint8_t *slots = nullptr;
     if ((rc = b.dalloc(&slots, std::max<uint64_t>(slot_bytes, 4), false)) ||
         (rc = b.dalloc(&fl.out, std::max<uint64_t>(bound, 4), false)) || (rc = b.dalloc(&fl.utts_dev, B, false)) ||
         (rc = b.dalloc(&fl.work_dev, nf, false)) || (rc = b.dalloc(&fl.redo_dev, nf, false)) ||
         (rc = b.dalloc(&fl.fsize, nf, false)) || (rc = b.dalloc(&fl.foff, nf, false)) ||
-        (rc = b.dalloc(&fl.res, B, false)) || (rc = b.dalloc(&fl.total, 1, false)))
+        (rc = b.dalloc(&fl.res, B, false)) || (rc = b.dalloc(&fl.total, 1, false)) ||
+        (md5 && ((rc = b.dalloc(&fl.md5_order_dev, std::max<size_t>(B, 1), false)) ||
+                 (rc = b.dalloc(&fl.md5_redo_dev, std::max<size_t>(B, 1), false)) ||
+                 (rc = b.dalloc(&fl.digests, 4 * std::max<size_t>(B, 1), false)))))
         return rc;
     flac_bind(&utts, slots);
     hipError_t e = hipSuccess;
     if ((B > 0 && (e = hipMemcpy(fl.utts_dev, utts.data(), sizeof(FlacUtt) * B, hipMemcpyHostToDevice)) != hipSuccess) ||
         (!fl.work.empty() && (e = hipMemcpy(fl.work_dev, fl.work.data(), sizeof(FlacWork) * fl.work.size(),
-                                            hipMemcpyHostToDevice)) != hipSuccess))
+                                            hipMemcpyHostToDevice)) != hipSuccess) ||
+        (!order.empty() && (e = hipMemcpy(fl.md5_order_dev, order.data(), sizeof(uint32_t) * order.size(),
+                                          hipMemcpyHostToDevice)) != hipSuccess))
         return hip_fail(e, "FLAC work list");
+    if (md5)
+        fl.utts = std::move(utts);
     return JB_OK;
 }
 
@@ -402,6 +433,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const ResampleTile *tiles = rs.tiles_dev;
     const LoudnessUtt *utts = ln.utts_dev;
     const FlacWork *work = fl.work_dev;
+    const uint32_t *md5_order = fl.md5_order_dev;
+    uint32_t n_md5 = fl.n_md5;
     const FormatUtt *futts = fm.utts_dev;
     uint32_t n_futts = fmt ? B : 0;
     uint64_t ft = fm.tiles;
@@ -418,6 +451,7 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         std::vector<ResampleTile> rs_sub;
         std::vector<LoudnessUtt> ln_sub;
         std::vector<FlacWork> fl_sub;
+        std::vector<uint32_t> md5_sub;
         std::vector<FormatUtt> fm_sub;
         std::vector<AdpcmUtt> ad_sub;
         lt = at = ft = ag = 0;
@@ -450,9 +484,13 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         for (const FlacWork &w : fl.work)
             if ((*only)[w.utt])
                 fl_sub.push_back(w);
+        if (fl.digests)
+            flac_md5_order(fl.utts, only, &md5_sub); // (an utterance without frames keeps its digest of no samples)
         tiles = rs.redo_dev;
         utts = ln.redo_dev;
         work = fl.redo_dev;
+        md5_order = fl.md5_redo_dev;
+        n_md5 = (uint32_t)md5_sub.size();
         futts = fm.redo_dev;
         n_futts = (uint32_t)fm_sub.size();
         autts = ad.redo_dev;
@@ -468,6 +506,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
                                       hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_work && (e = hipMemcpy(fl.redo_dev, fl_sub.data(), sizeof(FlacWork) * n_work, hipMemcpyHostToDevice)) !=
                            hipSuccess) ||
+            (n_md5 && (e = hipMemcpy(fl.md5_redo_dev, md5_sub.data(), sizeof(uint32_t) * n_md5,
+                                     hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_futts && (e = hipMemcpy(fm.redo_dev, fm_sub.data(), sizeof(FormatUtt) * n_futts,
                                        hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_autts && (e = hipMemcpy(ad.redo_dev, ad_sub.data(), sizeof(AdpcmUtt) * n_autts,
@@ -483,11 +523,13 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
                                       st)) != hipSuccess ||
          (e = launch_loudness_apply(utts, n_utts, at, ln.res, plan.apply.i16, st)) != hipSuccess))
         return hip_fail(e, only ? "loudness(redo)" : "loudness");
-    // FLAC: the blocks of the list, then every stream's offsets and place (all of fl.work_dev, redo or not)
+    // FLAC: the blocks of the list, the digests of its utterances' now final PCM (on request), then every stream's
+    // offsets, place and header (all of fl.work_dev, redo or not): the pack never sees a digest of replaced PCM
     if (flac_on && (!only || n_work) &&
         ((e = launch_flac_encode(flac_p, fl.utts_dev, work, n_work, fl.fsize, st)) != hipSuccess ||
+         (fl.digests && (e = launch_flac_md5(fl.utts_dev, md5_order, n_md5, fl.digests, st)) != hipSuccess) ||
          (e = launch_flac_pack(flac_p, fl.utts_dev, B, fl.work_dev, n_all_work, fl.fsize, fl.foff, fl.res, fl.total,
-                               fl.out, st)) != hipSuccess))
+                               fl.out, st, fl.digests, fl.max_points)) != hipSuccess))
         return hip_fail(e, only ? "FLAC(redo)" : "FLAC");
     // the sample format last: behind the apply pass, the converter or the hand-off check, whichever wrote last
     if (fmt && (!only || n_futts) &&

@@ -370,24 +370,34 @@ class Engine:
             F.check(fn(self._h, _lines(flat), offs, B, device, pcm, ns))
         return _pcm_arrays(pcm, ns, B, i16, free)
 
-    def synthesize_flac(self, labels: Sequence[str], block_size: int = 0, max_lpc_order=None) -> bytes:
-        """jb_synthesize_flac: the FLAC stream of what synthesize_batch([labels], i16=True) returns."""
+    def synthesize_flac(self, labels: Sequence[str], block_size: int = 0, max_lpc_order=None, md5: bool = False,
+                        seek_interval_ms: int = 0) -> bytes:
+        """jb_synthesize_flac[_meta]: the FLAC stream of what synthesize_batch([labels], i16=True) returns; md5 /
+        seek_interval_ms as Batch.set_flac's."""
         buf, n = C.POINTER(C.c_uint8)(), C.c_size_t()
-        opts = F.flac_opts(block_size, max_lpc_order)
-        F.check(self._L.jb_synthesize_flac(self._h, _lines(labels), len(labels), C.byref(opts), C.byref(buf),
-                                           C.byref(n)))
+        opts, meta = F.flac_opts(block_size, max_lpc_order), F.flac_meta(md5, seek_interval_ms)
+        if meta is None:
+            F.check(self._L.jb_synthesize_flac(self._h, _lines(labels), len(labels), C.byref(opts), C.byref(buf),
+                                               C.byref(n)))
+        else:
+            F.check(self._L.jb_synthesize_flac_meta(self._h, _lines(labels), len(labels), C.byref(opts),
+                                                    C.byref(meta), C.byref(buf), C.byref(n)))
         return F.take_flac(self._L, [buf], [n.value], 1)[0]
 
     def synthesize_batch_flac(self, utterances: Sequence[Sequence[str]], device: int = -1, block_size: int = 0,
-                              max_lpc_order=None) -> List[bytes]:
-        """jb_synthesize_batch_flac: one FLAC stream per utterance of synthesize_batch(..., i16=True)."""
+                              max_lpc_order=None, md5: bool = False, seek_interval_ms: int = 0) -> List[bytes]:
+        """jb_synthesize_batch_flac[_meta]: one FLAC stream per utterance of synthesize_batch(..., i16=True)."""
         flat = [l for u in utterances for l in u]
         off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
         B = len(utterances)
         offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
         bufs, ns = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))()
-        opts = F.flac_opts(block_size, max_lpc_order)
-        F.check(self._L.jb_synthesize_batch_flac(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
+        opts, meta = F.flac_opts(block_size, max_lpc_order), F.flac_meta(md5, seek_interval_ms)
+        if meta is None:
+            F.check(self._L.jb_synthesize_batch_flac(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
+        else:
+            F.check(self._L.jb_synthesize_batch_flac_meta(self._h, _lines(flat), offs, B, device, C.byref(opts),
+                                                          C.byref(meta), bufs, ns))
         return F.take_flac(self._L, bufs, ns, B)
 
     def synthesize_formatted(self, labels: Sequence[str], fmt, dither=False, seed: int = 0) -> bytes:
@@ -519,8 +529,9 @@ def synthesize_batch_each_adpcm(engines: Sequence["Engine"], utterances: Sequenc
 
 
 def synthesize_batch_each_flac(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]], device: int = -1,
-                               block_size: int = 0, max_lpc_order=None) -> List[bytes]:
-    """jb_synthesize_batch_each_flac: the FLAC streams of synthesize_batch_each(..., i16=True)."""
+                               block_size: int = 0, max_lpc_order=None, md5: bool = False,
+                               seek_interval_ms: int = 0) -> List[bytes]:
+    """jb_synthesize_batch_each_flac[_meta]: the FLAC streams of synthesize_batch_each(..., i16=True)."""
     if len(engines) != len(utterances):
         raise ValueError("one engine per utterance")
     B = len(utterances)
@@ -531,8 +542,12 @@ def synthesize_batch_each_flac(engines: Sequence["Engine"], utterances: Sequence
     offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
     hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
     bufs, ns = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))()
-    opts = F.flac_opts(block_size, max_lpc_order)
-    F.check(L.jb_synthesize_batch_each_flac(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
+    opts, meta = F.flac_opts(block_size, max_lpc_order), F.flac_meta(md5, seek_interval_ms)
+    if meta is None:
+        F.check(L.jb_synthesize_batch_each_flac(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
+    else:
+        F.check(L.jb_synthesize_batch_each_flac_meta(hs, _lines(flat), offs, B, device, C.byref(opts), C.byref(meta),
+                                                     bufs, ns))
     return F.take_flac(L, bufs, ns, B)
 
 
