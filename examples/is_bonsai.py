@@ -1,12 +1,17 @@
 """The reference's `examples/is-bonsai` on the GPU path: full-context labels -> PCM -> 16-bit WAV.
 
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak]]
-                                 [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]] [--flac]
+                                 [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
+                                 [--flac]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
 With --loudness the audio is normalized on the GPU to that integrated loudness (BS.1770-4), its sample peak kept at or
 under --ceiling (dBFS, default 0); with --true-peak the ceiling bounds the true peak (dBTP, BS.1770-4 Annex 2) instead.
+With --programme (and --loudness) the reference's two sample sentences are synthesized side by side as sentence
+utterances under ONE programme gain (per-request loudness scope: one gated measurement over both, one peak, one gain), so
+the level between them is kept as synthesized; they are written back to back, and the programme's loudness, loudness
+range and largest momentary and short-term loudness are printed.
 With --format the samples are converted to that format on the GPU (ulaw and alaw at 8 kHz, the telephony rate; --dither:
 TPDF dither for s16 and s24) and the WAV file carries them as they are.
 With --adpcm the audio is encoded as IMA ADPCM (WAV format tag 0x11, half a byte per sample) on the GPU, at --rate if
@@ -20,7 +25,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import jbonsai_amd as J  # noqa: E402
-from tests.golden.labels import SAMPLE_SENTENCE_2  # the label lines of the reference's example  # noqa: E402
+from tests.golden.labels import SAMPLE_SENTENCE_1, SAMPLE_SENTENCE_2  # the reference's example label lines  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("voice", nargs="?", default=os.path.join(
@@ -29,6 +34,8 @@ ap.add_argument("out", nargs="?", default="is-bonsai.wav")
 ap.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="target integrated loudness")
 ap.add_argument("--ceiling", type=float, default=0.0, metavar="DBFS", help="sample-peak ceiling (with --loudness)")
 ap.add_argument("--true-peak", action="store_true", help="the ceiling bounds the true peak (dBTP), not the sample peak")
+ap.add_argument("--programme", action="store_true",
+                help="two sentences as one programme under one gain (with --loudness)")
 ap.add_argument("--format", choices=["f32", "s16", "s24", "ulaw", "alaw"], default=None,
                 help="sample format of the WAV file, converted on the GPU")
 ap.add_argument("--dither", action="store_true", help="TPDF dither (with --format s16 or s24)")
@@ -43,6 +50,23 @@ if args.loudness is not None:
     engine.condition.set_loudness_target(args.loudness)
     engine.condition.set_peak_ceiling(args.ceiling)
     engine.condition.set_peak_mode(J.PEAK_TRUE if args.true_peak else J.PEAK_SAMPLE)
+if args.programme:
+    if args.loudness is None:
+        ap.error("--programme goes with --loudness")
+    import numpy as np
+
+    engine.set_loudness_scope(J.LOUDNESS_PER_REQUEST)
+    hz = engine.condition.get_sampling_frequency()
+    parts = [np.asarray(x) for x in engine.synthesize_batch([SAMPLE_SENTENCE_1, SAMPLE_SENTENCE_2])]
+    rep = J.loudness_groups(parts, hz, [0, 0], mode=J.PEAK_TRUE if args.true_peak else J.PEAK_SAMPLE)
+    g, r = rep["groups"][0], rep["groups"][0]["r128"]
+    print(f"programme of {len(parts)} sentences: {g['lufs']:.2f} LUFS, sample peak {g['sample_peak_dbfs']:.2f} dBFS, "
+          f"LRA {r['lra_lu']:.2f} LU, max momentary {r['max_momentary_lufs']:.2f}, "
+          f"max short-term {r['max_short_term_lufs']:.2f} LUFS")
+    print("each sentence alone: " + ", ".join(f"{v:.2f} LUFS" for v in rep["lufs"]))
+    J.write_wav(out, np.concatenate(parts), hz)
+    print(f"wrote {out}")
+    sys.exit(0)
 if args.adpcm:
     if args.rate:
         engine.condition.set_output_sampling_frequency(args.rate)

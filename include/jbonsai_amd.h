@@ -384,6 +384,47 @@ typedef struct jb_loudness_report {
     uint32_t peak_mode, oversampling;
 } jb_loudness_report;
 int jb_batch_loudness_report(jb_batch *b, size_t utt, jb_loudness_report *out);
+/* New.  Programme loudness ("loudness" below, step 6): one measurement, one peak and one gain for a group of
+ * utterances, so that their relative levels survive -- libebur128's ebur128_loudness_global_multiple, ReplayGain's
+ * album gain.  group[u] is a group id below jb_batch_size(b), or JB_LOUDNESS_NO_GROUP for an utterance of its own;
+ * n == jb_batch_size(b).  group == NULL with n == 0 withdraws the request.  The members of one group must agree on
+ * target, ceiling, peak mode and output rate (two NaN targets agree): this call, jb_batch_set_loudness_target,
+ * jb_batch_set_peak_mode and jb_batch_set_output_rate each check the combined request, and a call that would leave a
+ * group mixed is refused with JB_ERR_INVALID (jb_last_error names the group and the field) and changes nothing.
+ * Only before the batch's first run.  In either order with the target; without a target it has no effect.  The
+ * per-utterance entries (jb_batch_loudness, jb_batch_loudness_report) keep reporting each utterance's own L, P and
+ * TP; their gain_db is the gain applied, the group's.  Without a call nothing more runs and nothing is allocated. */
+#define JB_LOUDNESS_NO_GROUP 0xffffffffu
+int jb_batch_set_loudness_groups(jb_batch *b, const uint32_t *group, size_t n);
+/* The group of utterance utt, numbered densely in the order of the groups' first members (an utterance of its own
+ * counts as a group of one); -1 without a group request or for no such utterance. */
+int32_t jb_batch_loudness_group_of(const jb_batch *b, size_t utt);
+/* New.  The R128 report ("loudness" below, steps 7 and 8): with JB_LOUDNESS_R128 the run also takes the largest
+ * momentary and short-term loudness and the loudness range of every utterance and of every group; 0 withdraws the
+ * request.  Only before the batch's first run; without a target it has no effect.  Changes no sample. */
+#define JB_LOUDNESS_R128 1u
+int jb_batch_set_loudness_report(jb_batch *b, uint32_t flags);
+typedef struct jb_loudness_r128 {
+    double max_momentary_lufs;  /* over every 400 ms block, no gate; -INFINITY without a block */
+    double max_short_term_lufs; /* over every 3 s window; -INFINITY without a window */
+    double lra_lu;              /* loudness range; 0 when n_windows == 0 */
+    double lra_low_lufs, lra_high_lufs; /* the 10 % and 95 % windows; NaN when n_windows == 0 */
+    uint64_t n_windows;         /* windows above both gates of step 8 */
+} jb_loudness_r128;
+/* What the last run measured for utterance utt; needs JB_LOUDNESS_R128 and a target.  Readiness rules of
+ * jb_batch_loudness. */
+int jb_batch_loudness_r128(jb_batch *b, size_t utt, jb_loudness_r128 *out);
+/* What the last run measured and applied for the group of utterance utt: L_G, P_G, TP_G (NaN in sample mode), the
+ * one gain, the group's peak mode and oversampling factor, its member count, and, when flags has JB_LOUDNESS_R128,
+ * the group's R128 fields (zeros otherwise).  Needs a group request and a target.  Readiness rules of
+ * jb_batch_loudness. */
+typedef struct jb_loudness_group_report {
+    double lufs, sample_peak_dbfs, true_peak_dbtp, gain_db;
+    uint32_t peak_mode, oversampling; /* oversampling: 1 in sample mode, 0 where the rate is not known */
+    uint32_t members, flags;
+    jb_loudness_r128 r128;
+} jb_loudness_group_report;
+int jb_batch_loudness_group(jb_batch *b, size_t utt, jb_loudness_group_report *out);
 /* New.  FLAC output (see "FLAC" below): the run encodes each utterance's 16-bit PCM as the read entries hand it out
  * (after the output rate and the loudness target) into one FLAC stream per utterance, on the device.  opts: NULL or
  * zeros = the defaults.  Only before the batch's first run, on a JB_BATCH_PCM_I16 batch that is not
@@ -528,6 +569,26 @@ int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
  *    gain_dB = min(T - L, C - TP) over the finite terms; the reported P stays the sample peak.  Sample mode is the
  *    default.  TP is measured on the f64 before any 16-bit conversion: what the 16-bit sink's clamp and truncation
  *    do to the waveform is not measured again.  One gain per utterance: no look-ahead limiting.
+ * 6. Groups (jb_batch_set_loudness_groups).  The blocks of a group are the union of its members' own blocks (a
+ *    block never straddles two members: this is libebur128's ebur128_loudness_global_multiple, not the loudness of
+ *    the concatenated file).  With l_i of step 2: keep l_i > -70; G_G = the loudness of the mean of their mean
+ *    squares, minus 10; keep l_i > G_G as well; L_G = the loudness of the mean of the mean squares left, -INFINITY
+ *    when none is.  P_G (TP_G in true-peak mode) is the largest of the members' peaks.  gain_dB is step 4's rule,
+ *    min(T - L_G, C - P_G) over the finite terms, and every member is multiplied by the same g, the identical f64.
+ *    Fixed order: a member's partial (sum, count) of each gate pass is formed as for an utterance alone (256 lanes,
+ *    lane t adding blocks t, t + 256, ...; then a tree, lane t taking lane t + w for w = 128, 64, ..., 1), and the
+ *    members' partials are added one after the other in ascending utterance index.  So a group of one member gives
+ *    the ungrouped result bit for bit, and a group's result depends on its members' samples, rate and relative order
+ *    only -- not on the batch, the members' positions or what else runs: JB_BATCH_INVARIANT output stays invariant for
+ *    a whole group.
+ * 7. Momentary maximum: max_i l_i over all blocks of step 2, no gate; -INFINITY without a block.  Short-term:
+ *    s_i = (z_i + ... + z_(i+29)) / (30 H) for i = 0 .. nh - 30 (nh = N / H full hops), added in ascending hop order:
+ *    a 3 s window at every 100 ms hop, none for nh < 30; the maximum is reported as loudness, -0.691 + 10 log10(s).
+ * 8. Loudness range (EBU Tech 3342): of the s_i with loudness above -70, G_r = the loudness of their mean, minus 20;
+ *    keep those above G_r as well, n values in ascending order; lo = element floor((n - 1) 0.10 + 0.5),
+ *    hi = element floor((n - 1) 0.95 + 0.5) (libebur128's nearest-rank rule); LRA = 10 log10(hi / lo), 0.0 for n = 0.
+ *    For a group the s_i are the union of the members' windows (none straddles two members) and the mean is taken in
+ *    the order of step 6.  The two order statistics are exact for any n.
  * L, P, TP and gain_dB are functions of the utterance's samples alone (not of the batch, its order, the entry or the
  * devices); the device sums in fixed orders, so JB_BATCH_INVARIANT output stays invariant with a target. */
 /* Host only (no GPU): the coefficients of step 1 at hz, b[6] = b of the shelf then of the high-pass, a[6] likewise
@@ -537,6 +598,24 @@ int jb_loudness_filter(uint32_t hz, double *b, double *a, uint32_t *hop);
  * (n_in[u] samples at hz), on `device` (-1 = current).  A hop outside 1..61439 samples: JB_ERR_UNSUPPORTED. */
 int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
                           double *lufs, double *peak_dbfs);
+/* The group measurement on PCM the caller holds (jb_loudness_pcm_batch's twin for steps 6 to 8): in[u] (n_in[u]
+ * samples at hz) in the groups of group[u] (ids below n or JB_LOUDNESS_NO_GROUP; NULL: every utterance its own),
+ * measured on `device` (-1 = current) in peak mode `mode` against target_lufs and ceiling_db.  group_of[u] (may be
+ * NULL) = the dense group of utterance u, numbered by first member; groups[g] for g < *n_groups (at most groups_cap
+ * are written; JB_ERR_BUFFER if there are more), each with its R128 fields; utt_r128[u] (may be NULL) = each
+ * utterance's own R128 fields; utt_lufs[u] (may be NULL) = its own L.  No sample is changed. */
+int jb_loudness_groups_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *group,
+                                 uint32_t hz, int32_t device, uint32_t mode, double target_lufs, double ceiling_db,
+                                 uint32_t *group_of, jb_loudness_group_report *groups, size_t groups_cap,
+                                 size_t *n_groups, jb_loudness_r128 *utt_r128, double *utt_lufs);
+/* Host only (no GPU): steps 6 to 8 by the library's rule text, on hop energies the caller holds.  Member m has
+ * n_hops[m] full hops of `hop` samples with energies z[m][j] (step 2's z_j), sample peak peak[m] and, in true-peak
+ * mode, true_peak[m] (largest magnitudes in 16-bit units; true_peak == NULL: sample mode).  *group = the set's report
+ * with its R128 fields (oversampling 0 in true-peak mode: no rate is given); member_r128 (may be NULL) = each
+ * member's own R128 fields. */
+int jb_loudness_gate_host(const double *const *z, const size_t *n_hops, size_t n, uint32_t hop, const double *peak,
+                          const double *true_peak, double target_lufs, double ceiling_db,
+                          jb_loudness_group_report *group, jb_loudness_r128 *member_r128);
 /* Host only (no GPU): the interpolator of step 5 at hz: *F, *ntaps = 12 (each may be NULL) and, when taps is not NULL,
  * the [F - 1][12] taps h[p][j] of phases p = 1..F-1 (JB_ERR_BUFFER if cap < (F - 1) * 12).  hz == 0: JB_ERR_INVALID. */
 int jb_true_peak_filter(uint32_t hz, uint32_t *F, uint32_t *ntaps, double *taps, size_t cap);
@@ -791,6 +870,18 @@ double jb_engine_get_peak_ceiling(const jb_engine *e);
  * _flac and _multi entries and the generator. */
 int jb_engine_set_peak_mode(jb_engine *e, uint32_t mode);
 uint32_t jb_engine_get_peak_mode(const jb_engine *e);
+/* New.  What one gain of the loudness target covers: each utterance (JB_LOUDNESS_PER_UTTERANCE, the default) or the
+ * whole request (JB_LOUDNESS_PER_REQUEST): all utterances of one jb_synthesize_batch* call -- the f64, _i16,
+ * _flac[_meta], _formatted, _adpcm and _each* forms -- are one loudness group (jb_batch_set_loudness_groups), so
+ * their relative levels survive; such a request runs as one batch.  In the _each forms the engines must then agree
+ * on scope, target, ceiling, peak mode and output rate: JB_ERR_INVALID naming the field, before any device is
+ * touched.  jb_synthesize and the generator are a group of one: their output is unchanged.  The _multi entries
+ * refuse an engine with per-request scope (a group does not span devices): JB_ERR_INVALID.  Any other value:
+ * JB_ERR_INVALID.  Without a target the scope has no effect. */
+#define JB_LOUDNESS_PER_UTTERANCE 0
+#define JB_LOUDNESS_PER_REQUEST 1
+int jb_engine_set_loudness_scope(jb_engine *e, uint32_t scope);
+uint32_t jb_engine_get_loudness_scope(const jb_engine *e);
 /* New.  Where the per-label decision-tree search of the front half runs (Model::get_index for the duration model and
  * every stream model, state and voice, and the GV switch question).  The default is the host, as before: nothing new
  * runs and nothing is allocated.  On the device one wave searches one label (jb_treesearch.hip); label parsing, the
@@ -1055,6 +1146,12 @@ JB_LAYOUT_ASSERT(sizeof(jb_adpcm_opts) == 16 && offsetof(jb_adpcm_opts, reserved
 JB_LAYOUT_ASSERT(sizeof(jb_loudness_report) == 40 && offsetof(jb_loudness_report, gain_db) == 24 &&
                      offsetof(jb_loudness_report, peak_mode) == 32 && offsetof(jb_loudness_report, oversampling) == 36,
                  "jb_loudness_report");
+JB_LAYOUT_ASSERT(sizeof(jb_loudness_r128) == 48 && offsetof(jb_loudness_r128, lra_lu) == 16 &&
+                     offsetof(jb_loudness_r128, n_windows) == 40,
+                 "jb_loudness_r128");
+JB_LAYOUT_ASSERT(sizeof(jb_loudness_group_report) == 96 && offsetof(jb_loudness_group_report, peak_mode) == 32 &&
+                     offsetof(jb_loudness_group_report, members) == 40 && offsetof(jb_loudness_group_report, r128) == 48,
+                 "jb_loudness_group_report");
 #undef JB_LAYOUT_ASSERT
 #endif
 #endif /* JBONSAI_AMD_H */

@@ -203,6 +203,29 @@ class LoudnessReport(C.Structure):
                 ("gain_db", C.c_double), ("peak_mode", C.c_uint32), ("oversampling", C.c_uint32)]
 
 
+class LoudnessR128(C.Structure):
+    """jb_loudness_r128: largest momentary and short-term loudness and the loudness range of an utterance or a group."""
+    _fields_ = [("max_momentary_lufs", C.c_double), ("max_short_term_lufs", C.c_double), ("lra_lu", C.c_double),
+                ("lra_low_lufs", C.c_double), ("lra_high_lufs", C.c_double), ("n_windows", C.c_uint64)]
+
+
+class LoudnessGroupReport(C.Structure):
+    """jb_loudness_group_report: what a run measured and applied for one loudness group."""
+    _fields_ = [("lufs", C.c_double), ("sample_peak_dbfs", C.c_double), ("true_peak_dbtp", C.c_double),
+                ("gain_db", C.c_double), ("peak_mode", C.c_uint32), ("oversampling", C.c_uint32),
+                ("members", C.c_uint32), ("flags", C.c_uint32), ("r128", LoudnessR128)]
+
+
+LOUDNESS_PER_UTTERANCE, LOUDNESS_PER_REQUEST = 0, 1
+LOUDNESS_NO_GROUP = 0xFFFFFFFF
+LOUDNESS_R128 = 1
+
+
+def _struct_dict(r):
+    return {k: (_struct_dict(getattr(r, k)) if isinstance(getattr(r, k), C.Structure) else getattr(r, k))
+            for k, _ in r._fields_}
+
+
 class BatchOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32), ("chunk_frames", C.c_uint32),
                 ("warmup_frames", C.c_uint32), ("verify_tol", C.c_double), ("reserved0", C.c_uint32), ("reserved", C.c_uint32)]
@@ -259,6 +282,9 @@ SYMBOLS = [
     "jb_batch_read_adpcm_all", "jb_adpcm_geometry", "jb_adpcm_encode_host", "jb_adpcm_encode_i16_host",
     "jb_adpcm_decode_host", "jb_adpcm_encode_pcm_batch", "jb_adpcm_free", "jb_write_wav_adpcm",
     "jb_synthesize_adpcm", "jb_synthesize_batch_adpcm", "jb_synthesize_batch_each_adpcm",
+    "jb_batch_set_loudness_groups", "jb_batch_loudness_group_of", "jb_batch_loudness_group",
+    "jb_batch_set_loudness_report", "jb_batch_loudness_r128", "jb_loudness_groups_pcm_batch",
+    "jb_loudness_gate_host", "jb_engine_set_loudness_scope", "jb_engine_get_loudness_scope",
 ]
 
 
@@ -385,10 +411,26 @@ def lib():
         getattr(L, "jb_engine_get_" + n).argtypes = [vp]
         getattr(L, "jb_engine_get_" + n).restype = C.c_double
     L.jb_batch_set_peak_mode.argtypes = [vp, C.POINTER(C.c_uint32), sz]
+    u32p = C.POINTER(C.c_uint32)
+    L.jb_batch_set_loudness_groups.argtypes = [vp, u32p, sz]
+    L.jb_batch_loudness_group_of.argtypes = [vp, sz]
+    L.jb_batch_loudness_group_of.restype = C.c_int32
+    L.jb_batch_loudness_group.argtypes = [vp, sz, C.POINTER(LoudnessGroupReport)]
+    L.jb_batch_set_loudness_report.argtypes = [vp, C.c_uint32]
+    L.jb_batch_loudness_r128.argtypes = [vp, sz, C.POINTER(LoudnessR128)]
+    L.jb_loudness_groups_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, u32p, C.c_uint32, C.c_int32,
+                                               C.c_uint32, C.c_double, C.c_double, u32p,
+                                               C.POINTER(LoudnessGroupReport), sz, C.POINTER(sz),
+                                               C.POINTER(LoudnessR128), dp]
+    L.jb_loudness_gate_host.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, C.c_uint32, dp, dp, C.c_double, C.c_double,
+                                        C.POINTER(LoudnessGroupReport), C.POINTER(LoudnessR128)]
     L.jb_batch_loudness_report.argtypes = [vp, sz, C.POINTER(LoudnessReport)]
     L.jb_true_peak_filter.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), dp, sz]
     L.jb_true_peak_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, C.c_uint32, C.c_int32, dp]
     L.jb_engine_set_peak_mode.argtypes = [vp, C.c_uint32]
+    L.jb_engine_set_loudness_scope.argtypes = [vp, C.c_uint32]
+    L.jb_engine_get_loudness_scope.argtypes = [vp]
+    L.jb_engine_get_loudness_scope.restype = C.c_uint32
     L.jb_engine_get_peak_mode.argtypes = [vp]
     L.jb_engine_get_peak_mode.restype = C.c_uint32
     L.jb_engine_set_tree_search.argtypes = [vp, C.c_uint32]
@@ -521,6 +563,60 @@ def loudness(pcms, hz: int, device: int = -1):
     check(lib().jb_loudness_pcm_batch(ins, nin, n, hz, device, lufs.ctypes.data_as(dp), peak.ctypes.data_as(dp)))
     res = [(float(lufs[u]), float(peak[u])) for u in range(n)]
     return res[0] if single else res
+
+
+def _group_ids(group, n):
+    """A ctypes array of n group ids: None entries (or group None) are JB_LOUDNESS_NO_GROUP."""
+    ids = [LOUDNESS_NO_GROUP] * n if group is None else [LOUDNESS_NO_GROUP if g is None else int(g) for g in group]
+    if len(ids) != n:
+        raise ValueError("one group per utterance")
+    return (C.c_uint32 * max(n, 1))(*ids)
+
+
+def loudness_groups(pcms, hz: int, group=None, device: int = -1, mode: int = 0, target=float("nan"),
+                    ceiling=float("inf")):
+    """jb_loudness_groups_pcm_batch: the float64 arrays of `pcms` at hz, measured on the GPU in the groups of `group`
+    (ids below len(pcms); None = an utterance of its own).  Returns a dict: group_of (the dense group of each
+    utterance), groups (a dict per group: lufs, sample_peak_dbfs, true_peak_dbtp, gain_db, peak_mode, oversampling,
+    members, flags, r128), r128 (a dict per utterance) and lufs (each utterance's own L)."""
+    import numpy as np
+
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in pcms]
+    n = len(arrs)
+    dp = C.POINTER(C.c_double)
+    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    ids = _group_ids(group, n)
+    of = (C.c_uint32 * max(n, 1))()
+    reps = (LoudnessGroupReport * max(n, 1))()
+    r128 = (LoudnessR128 * max(n, 1))()
+    lufs = np.zeros(max(n, 1))
+    ng = C.c_size_t()
+    check(lib().jb_loudness_groups_pcm_batch(ins, nin, n, ids, hz, device, mode, float(target), float(ceiling), of,
+                                             reps, n, C.byref(ng), r128, lufs.ctypes.data_as(dp)))
+    return {"group_of": [int(of[u]) for u in range(n)], "groups": [_struct_dict(reps[g]) for g in range(ng.value)],
+            "r128": [_struct_dict(r128[u]) for u in range(n)], "lufs": [float(lufs[u]) for u in range(n)]}
+
+
+def loudness_gate_host(z, hop: int, peak, true_peak=None, target=float("nan"), ceiling=float("inf")):
+    """jb_loudness_gate_host (host only): the group rules on hop energies the caller holds.  z: one float64 array of
+    hop energies per member; peak / true_peak: their largest magnitudes in 16-bit units.  Returns (group, members):
+    the set's report as a dict (r128 included) and each member's own R128 fields."""
+    import numpy as np
+
+    zs = [np.ascontiguousarray(a, dtype=np.float64) for a in z]
+    n = len(zs)
+    dp = C.POINTER(C.c_double)
+    zp = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in zs])
+    nh = (C.c_size_t * max(n, 1))(*[a.size for a in zs])
+    pk = np.ascontiguousarray(peak, dtype=np.float64)
+    tp = None if true_peak is None else np.ascontiguousarray(true_peak, dtype=np.float64)
+    rep = LoudnessGroupReport()
+    mr = (LoudnessR128 * max(n, 1))()
+    check(lib().jb_loudness_gate_host(zp, nh, n, hop, pk.ctypes.data_as(dp),
+                                      None if tp is None else tp.ctypes.data_as(dp), float(target), float(ceiling),
+                                      C.byref(rep), mr))
+    return _struct_dict(rep), [_struct_dict(mr[m]) for m in range(n)]
 
 
 def true_peak_filter(hz: int):

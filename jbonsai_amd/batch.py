@@ -384,6 +384,37 @@ class Batch:
         arr = (C.c_uint32 * max(1, len(ms)))(*ms)
         F.check(self._L.jb_batch_set_peak_mode(self._h, arr, len(ms)))
 
+    def set_loudness_groups(self, group):
+        """jb_batch_set_loudness_groups: one group id (below the batch size) per utterance, None for an utterance of
+        its own; group None withdraws the request.  The members of a group share one measurement and one gain."""
+        if group is None:
+            F.check(self._L.jb_batch_set_loudness_groups(self._h, None, 0))
+            return
+        ids = F._group_ids(group, len(group))
+        F.check(self._L.jb_batch_set_loudness_groups(self._h, ids, len(group)))
+
+    def loudness_group_of(self, i):
+        """The dense group of utterance i (numbered by first member), -1 without a group request."""
+        return int(self._L.jb_batch_loudness_group_of(self._h, i))
+
+    def loudness_group(self, i):
+        """jb_batch_loudness_group for the group of utterance i: a dict of lufs, sample_peak_dbfs, true_peak_dbtp,
+        gain_db, peak_mode, oversampling, members, flags and r128 (filled with a report request)."""
+        r = F.LoudnessGroupReport()
+        F.check(self._L.jb_batch_loudness_group(self._h, i, C.byref(r)))
+        return F._struct_dict(r)
+
+    def set_loudness_report(self, flags=F.LOUDNESS_R128):
+        """jb_batch_set_loudness_report: F.LOUDNESS_R128 asks for the R128 fields, 0 withdraws the request."""
+        F.check(self._L.jb_batch_set_loudness_report(self._h, int(flags)))
+
+    def loudness_r128(self, i):
+        """jb_batch_loudness_r128 for utterance i: a dict of max_momentary_lufs, max_short_term_lufs, lra_lu,
+        lra_low_lufs, lra_high_lufs and n_windows."""
+        r = F.LoudnessR128()
+        F.check(self._L.jb_batch_loudness_r128(self._h, i, C.byref(r)))
+        return F._struct_dict(r)
+
     def loudness_report(self, i):
         """jb_batch_loudness_report for utterance i: a dict of lufs, sample_peak_dbfs, true_peak_dbtp (NaN in sample
         mode), gain_db, peak_mode and oversampling."""

@@ -2567,6 +2567,55 @@ int jb_batch_loudness_report(jb_batch *hb, size_t utt, jb_loudness_report *out)
     return JB_OK;
 }
 
+int jb_batch_set_loudness_groups(jb_batch *hb, const uint32_t *group, size_t n)
+{
+    return hb ? ((Batch *)hb)->out.set_loudness_groups(group, n) : JB_ERR_INVALID;
+}
+
+int32_t jb_batch_loudness_group_of(const jb_batch *hb, size_t utt)
+{
+    const Batch *b = (const Batch *)hb;
+    return (b && utt < (size_t)b->B) ? b->out.group_of(utt) : -1;
+}
+
+int jb_batch_set_loudness_report(jb_batch *hb, uint32_t flags)
+{
+    return hb ? ((Batch *)hb)->out.set_loudness_report(flags) : JB_ERR_INVALID;
+}
+
+int jb_batch_loudness_r128(jb_batch *hb, size_t utt, jb_loudness_r128 *out)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !out || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    jb::LoudnessRange r{};
+    int rc = b->out.read_loudness_range(utt, false, &r);
+    if (rc)
+        return rc;
+    jb::loudness_r128_out(r, out);
+    return JB_OK;
+}
+
+int jb_batch_loudness_group(jb_batch *hb, size_t utt, jb_loudness_group_report *out)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !out || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    jb::LoudnessGroupResult g{};
+    int rc = b->out.read_loudness_group(utt, &g);
+    if (rc)
+        return rc;
+    jb::LoudnessRange r{};
+    if (b->out.report_on() && (rc = b->out.read_loudness_range(utt, true, &r)))
+        return rc;
+    const uint32_t mode = b->out.peak_mode(utt);
+    uint32_t F = 1;
+    if (mode == JB_PEAK_TRUE && (rc = jb::true_peak_table(b->out.utt(utt).hz, &F, nullptr)))
+        return rc;
+    jb::loudness_group_report(g, mode, F, b->out.group_members(utt), b->out.report_on() ? &r : nullptr, out);
+    return JB_OK;
+}
+
 int jb_batch_set_flac(jb_batch *hb, const jb_flac_opts *opts)
 {
     if (!hb)

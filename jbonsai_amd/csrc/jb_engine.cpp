@@ -50,6 +50,7 @@ struct Condition {
     double loudness_target = NAN; // jb_engine_set_loudness_target: NaN = off
     double peak_ceiling = 0.0;    // jb_engine_set_peak_ceiling (dBFS), with a target only
     uint32_t peak_mode = JB_PEAK_SAMPLE; // jb_engine_set_peak_mode: what the ceiling bounds, with a target only
+    uint32_t loudness_scope = JB_LOUDNESS_PER_UTTERANCE; // jb_engine_set_loudness_scope: what one gain covers
     uint32_t tree_search = JB_SEARCH_HOST; // jb_engine_set_tree_search: where the per-label tree search runs
     double speed = 1.0;
     size_t stage = 0;
@@ -1098,6 +1099,17 @@ int jb_engine_set_peak_mode(jb_engine *e, uint32_t mode)
     return JB_OK;
 }
 uint32_t jb_engine_get_peak_mode(const jb_engine *e) { return e ? CENG(e)->cond.peak_mode : JB_PEAK_SAMPLE; }
+int jb_engine_set_loudness_scope(jb_engine *e, uint32_t scope)
+{
+    if (!e || (scope != JB_LOUDNESS_PER_UTTERANCE && scope != JB_LOUDNESS_PER_REQUEST))
+        return JB_ERR_INVALID;
+    ENG(e)->cond.loudness_scope = scope;
+    return JB_OK;
+}
+uint32_t jb_engine_get_loudness_scope(const jb_engine *e)
+{
+    return e ? CENG(e)->cond.loudness_scope : JB_LOUDNESS_PER_UTTERANCE;
+}
 int jb_engine_set_tree_search(jb_engine *e, uint32_t mode)
 {
     if (!e || (mode != JB_SEARCH_HOST && mode != JB_SEARCH_AUTO && mode != JB_SEARCH_DEVICE))
@@ -1445,6 +1457,11 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
         ngroups = 2;
     if (const char *ev = getenv("JB_SYNTH_GROUPS"))
         ngroups = (size_t)std::max(1, atoi(ev));
+    // per-request loudness scope: the request is one loudness group, and a group lives in one batch
+    const bool one_gain = CENG(e)->cond.loudness_scope == JB_LOUDNESS_PER_REQUEST &&
+                          !std::isnan(CENG(e)->cond.loudness_target);
+    if (one_gain)
+        ngroups = 1;
     ngroups = std::max<size_t>(1, std::min(ngroups, n_utts));
     std::vector<size_t> glo(ngroups + 1, n_utts);
     glo[0] = 0;
@@ -1576,6 +1593,11 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             return rc;
         if (any_true && (rc = b->out.set_peak_mode(modes.data(), modes.size())))
             return rc;
+        if (one_gain) {
+            const std::vector<uint32_t> group(hi - lo, 0u);
+            if ((rc = b->out.set_loudness_groups(group.data(), group.size())))
+                return rc;
+        }
         if (flac && ((rc = b->out.set_flac(flac_opts)) || (flac_meta && (rc = b->out.set_flac_meta(flac_meta)))))
             return rc;
         if (fmt_opts && (rc = b->out.set_format(fmt_opts)))
@@ -1811,6 +1833,20 @@ static int check_engines(const jb_engine *const *engines, size_t n)
             field = "fast_invariant";
         else if (e.cond.tree_search != e0.cond.tree_search)
             field = "tree_search";
+        else if (e.cond.loudness_scope != e0.cond.loudness_scope)
+            field = "loudness_scope";
+        else if (e0.cond.loudness_scope == JB_LOUDNESS_PER_REQUEST) {
+            // one gain for the request: what the members of a loudness group must share
+            const double a = e.cond.loudness_target, b = e0.cond.loudness_target;
+            if (!(a == b || (std::isnan(a) && std::isnan(b))))
+                field = "loudness_target (per-request loudness scope)";
+            else if (e.cond.peak_ceiling != e0.cond.peak_ceiling)
+                field = "peak_ceiling (per-request loudness scope)";
+            else if (e.cond.peak_mode != e0.cond.peak_mode)
+                field = "peak_mode (per-request loudness scope)";
+            else if (e.cond.output_rate != e0.cond.output_rate)
+                field = "output_sampling_frequency (per-request loudness scope)";
+        }
         if (field) {
             jb::set_error("jb_synthesize_batch_each: engines[" + std::to_string(u) + "] differs from engines[0] in " +
                           field);

@@ -4,6 +4,7 @@
 #include "jb_device.h"
 #include "jb_adpcm.h"
 #include "jb_format.h"
+#include "jb_loudness_rules.h"
 #include "jb_md5.h"
 #include "jb_output.h"
 
@@ -99,7 +100,7 @@ hipError_t launch_resample(const ResampleTable *tables_dev, const ResampleTile *
 
 // Loudness normalization (jb_loudness.hip): BS.1770-4 K-weighting, measured per utterance in tiles of at most
 // 256 segments of S samples; tiles never cross a hop (H samples), a hop has tph of them
-constexpr uint32_t kLnLanes = 256;
+// (kLnLanes, the threads of a loudness workgroup: jb_loudness_rules.h)
 constexpr uint32_t kTpMaxF = 64, kTpTaps = 12; // true peak: oversampling factor at most, taps per phase
 struct LoudnessRate {
     double b[6], a[6];     // stage 1 (shelf) then stage 2 (high-pass): b0 b1 b2 / 1 a1 a2
@@ -141,6 +142,62 @@ hipError_t launch_loudness_measure(const LoudnessRate *rates_dev, const Loudness
 // y = x * res[slot].g for every utterance of the list (apply tiles in all)
 hipError_t launch_loudness_apply(const LoudnessUtt *utts_dev, uint32_t n, uint64_t atiles, const LoudnessResult *res,
                                  bool i16, hipStream_t stream);
+// Loudness groups and the R128 report (jb_output.h: LnGroups; the rules: jb_loudness_rules.h).  A set is what one
+// workgroup walks: the members of a group, or one utterance; members[m0 .. m0 + nm) index the batch's utterance list
+struct LoudnessSet {
+    uint32_t m0, nm;
+    uint32_t slot;  // its place in the group results (a group) or the utterance's slot (an utterance)
+    uint32_t rslot; // its place in the R128 results
+};
+struct LoudnessGroupResult {
+    double lufs, peak_dbfs, true_peak_dbtp, gain_db, g;
+};
+using LoudnessRange = LnRangeOut;
+// k_ln_gate_group behind the measure passes: sets_dev[0..n) are groups; utts_all is the batch's list by utterance
+// index (its res entries hold what k_ln_gate left); gres[slot] gets the group's result and every member's gain_db and
+// g in res are overwritten with the group's
+hipError_t launch_loudness_groups(const LoudnessRate *rates_dev, const LoudnessUtt *utts_all, const LoudnessSet *sets_dev,
+                                  uint32_t n, const uint32_t *members, const double *z, LoudnessResult *res,
+                                  LoudnessGroupResult *gres, hipStream_t stream);
+// The R128 report: k_ln_windows over utts_dev[0..n_utts) (each utterance's short-term windows into sw, at its tile0,
+// and its largest momentary loudness into mm[slot]), then k_ln_range over sets_dev[0..n_sets) into r128[rslot]
+hipError_t launch_loudness_range(const LoudnessRate *rates_dev, const LoudnessUtt *utts_dev, uint32_t n_utts,
+                                 const LoudnessUtt *utts_all, const LoudnessSet *sets_dev, uint32_t n_sets,
+                                 const uint32_t *members, const double *z, double *sw, double *mm,
+                                 LoudnessRange *r128, hipStream_t stream);
+// the public structs of a result
+inline void loudness_r128_out(const LoudnessRange &r, jb_loudness_r128 *out)
+{
+    out->max_momentary_lufs = r.max_momentary;
+    out->max_short_term_lufs = r.max_short_term;
+    out->lra_lu = r.lra;
+    out->lra_low_lufs = r.lra_low;
+    out->lra_high_lufs = r.lra_high;
+    out->n_windows = r.n;
+}
+// oversampling: the factor of the group's rate in true-peak mode (0: not known); range: null without a report
+inline void loudness_group_report(const LoudnessGroupResult &g, uint32_t mode, uint32_t oversampling, uint32_t members,
+                                  const LoudnessRange *range, jb_loudness_group_report *out)
+{
+    *out = jb_loudness_group_report{};
+    out->lufs = g.lufs;
+    out->sample_peak_dbfs = g.peak_dbfs;
+    out->true_peak_dbtp = g.true_peak_dbtp;
+    out->gain_db = g.gain_db;
+    out->peak_mode = mode;
+    out->oversampling = mode == JB_PEAK_TRUE ? oversampling : 1;
+    out->members = members;
+    if (range) {
+        out->flags = JB_LOUDNESS_R128;
+        loudness_r128_out(*range, &out->r128);
+    }
+}
+// The host statement of the same rules (jb_loudness.cpp; no GPU): z[m][0..nh[m]) the hop energies of member m, peak /
+// true_peak (null: sample mode) their largest magnitudes in 16-bit units; *group the set's result, *range its R128
+// fields, member_range (null or [n]) each member's own
+void loudness_gate_host(const double *const *z, const size_t *nh, size_t n, uint32_t hop, const double *peak,
+                        const double *true_peak, double target, double ceiling, LoudnessGroupResult *group,
+                        LoudnessRange *range, LoudnessRange *member_range);
 
 // FLAC encoding of the 16-bit output (jb_flac.hip; the host half: jb_flac.cpp).  One stream per utterance: its header
 // (42 bytes: fLaC + STREAMINFO; with a SEEKTABLE request that block behind it, jb_md5.h), then frames of
@@ -276,6 +333,10 @@ struct OutputChain {
     int set_output_rate(const uint32_t *hz, size_t n); // n == 1 or B entries, 0 = native
     int set_loudness(const double *target, const double *ceiling, size_t n); // n == 1 or B entries each
     int set_peak_mode(const uint32_t *mode, size_t n);                       // n == 1 or B entries; needs no target
+    // group[u]: a group id below B or kLnNoGroup, n == B (nullptr, 0: the request is withdrawn); every setter that
+    // could leave a group's members disagreeing (this one, target, peak mode, output rate) checks the combined request
+    int set_loudness_groups(const uint32_t *group, size_t n);
+    int set_loudness_report(uint32_t flags); // JB_LOUDNESS_R128 or 0
     int set_flac(const jb_flac_opts *opts);
     int set_flac_meta(const jb_flac_meta *meta); // behind set_flac
     int set_format(const jb_format_opts *opts); // an f64 batch only
@@ -299,6 +360,13 @@ struct OutputChain {
     // after sync (each reports a stage that was not set, or a batch that has not run, as JB_ERR_INVALID)
     int read_loudness(size_t u, LoudnessResult *r);
     uint32_t peak_mode(size_t u) const { return u < ln_mode.size() ? ln_mode[u] : 0u; }
+    // the dense group of utterance u (-1 without a group request), its members, its result and the R128 fields of an
+    // utterance or of utterance u's group
+    int32_t group_of(size_t u) const { return ln_groups.group_of.empty() ? -1 : (int32_t)ln_groups.group_of[u]; }
+    uint32_t group_members(size_t u) const;
+    int read_loudness_group(size_t u, LoudnessGroupResult *r);
+    bool report_on() const { return ln_report != 0; }
+    int read_loudness_range(size_t u, bool of_group, LoudnessRange *r);
     int read_flac_index(size_t u, FlacOut *o);
     int read_flac(const FlacOut &o, uint8_t *dst);
     // every stream's size and place, and the compact slab's used bytes in one copy
@@ -326,6 +394,9 @@ private:
     uint32_t ad_align = 0;                     // its block_align (0: by the rate)
     std::vector<double> ln_target, ln_ceiling; // [B]
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
+    std::vector<uint32_t> ln_group_req;        // [B] the caller's ids; empty: no group request
+    LnGroups ln_groups;                        // the request planned (empty without one)
+    uint32_t ln_report = 0;                    // JB_LOUDNESS_R128: the report is requested
     FlacParams flac_p{};
     FlacMeta flac_m{}; // MD5 / SEEKTABLE request (zeros: none)
     bool frozen = false, ready = false; // the first run has begun: no more requests / its prepare() succeeded
@@ -345,6 +416,14 @@ private:
         LoudnessResult *res = nullptr;
         uint64_t tiles = 0, atiles = 0;
         bool true_peak = false; // some utterance is in JB_PEAK_TRUE mode
+        // with a group or a report request only
+        std::vector<LoudnessSet> sets;  // [B] the utterances, then [G] the groups
+        LoudnessSet *sets_dev = nullptr, *sets_redo_dev = nullptr;
+        LoudnessUtt *apply_redo_dev = nullptr; // grouped: a redo applies to every member of a touched group
+        uint32_t *members_dev = nullptr; // [B] the identity, then [B] the groups' members
+        LoudnessGroupResult *gres = nullptr; // [G]
+        double *sw = nullptr, *mm = nullptr; // the report's windows (per tile slot) and momentary maxima (per utterance)
+        LoudnessRange *r128 = nullptr;       // [B + G]
     } ln;
     struct { // FLAC
         std::vector<FlacWork> work;
@@ -369,6 +448,11 @@ private:
         uint64_t groups = 0;
     } ad;
     void replan(); // host geometry and routing of the present requests
+    // the group request `group` ([B], empty: none) against these targets, modes and rates: JB_ERR_INVALID naming the
+    // group and the field where members would disagree; *out (may be null) gets the plan
+    int check_groups(const std::vector<uint32_t> &group, const std::vector<double> &target,
+                     const std::vector<double> &ceiling, const std::vector<uint32_t> &mode,
+                     const std::vector<uint32_t> &want, const char *who, LnGroups *out) const;
     int check_settable(const char *after_run) const;
     int prepare_resample();
     int prepare_loudness();

@@ -35,6 +35,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <string>
 
 namespace jb {
 
@@ -523,6 +524,51 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_true_peak(const LoudnessRate *_
         tp[U.tile0 + t] = red[0];
 }
 
+// z of hop h of one utterance: its tiles' shares added in ascending order
+struct LnHopZ {
+    const double *zu;
+    uint32_t tph;
+    __device__ __forceinline__ double operator()(uint64_t h) const
+    {
+        double s = zu[h * tph];
+        for (uint32_t k = 1; k < tph; k++)
+            s += zu[h * tph + k];
+        return s;
+    }
+};
+
+// ln_tree (jb_loudness_rules.h) over the workgroup's lanes in LDS; every lane gets lane 0's result
+__device__ __forceinline__ void ln_tree_lds(double *rs, uint32_t *rn, uint32_t tid, double *sum, uint32_t *cnt)
+{
+    rs[tid] = *sum;
+    rn[tid] = *cnt;
+    __syncthreads();
+    for (uint32_t w = kLnLanes / 2; w > 0; w >>= 1) {
+        if (tid < w) {
+            rs[tid] += rs[tid + w];
+            rn[tid] += rn[tid + w];
+        }
+        __syncthreads();
+    }
+    *sum = rs[0];
+    *cnt = rn[0];
+    __syncthreads();
+}
+
+__device__ __forceinline__ double ln_max_lds(double *rs, uint32_t tid, double v)
+{
+    rs[tid] = v;
+    __syncthreads();
+    for (uint32_t w = kLnLanes / 2; w > 0; w >>= 1) {
+        if (tid < w)
+            rs[tid] = fmax(rs[tid], rs[tid + w]);
+        __syncthreads();
+    }
+    v = rs[0];
+    __syncthreads();
+    return v;
+}
+
 // One workgroup per utterance: z_j, blocks, gates, L, P, TP, gain -- fixed orders over a fixed thread count
 __global__ __launch_bounds__(kLnLanes) void k_ln_gate(const LoudnessRate *__restrict__ rates,
                                                       const LoudnessUtt *__restrict__ utts,
@@ -564,63 +610,28 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_gate(const LoudnessRate *__rest
         tpeak = fmax(peak, rs[0]);
         __syncthreads();
     }
-    const uint64_t nh = U.n / H, nb = nh >= 4 ? nh - 3 : 0;
-    const double *zu = z + U.tile0;
-    auto hop_z = [&](uint64_t h) {
-        double s = zu[h * tph];
-        for (uint32_t k = 1; k < tph; k++)
-            s += zu[h * tph + k];
-        return s;
-    };
-    const double den = 4.0 * (double)H;
+    const uint64_t nh = U.n / H, nb = ln_blocks(nh);
+    const LnHopZ hop_z{z + U.tile0, tph};
+    auto ms = [&](uint64_t i) { return ln_block_ms(hop_z, i, H); };
     // pass 0: the absolute gate; pass 1: both gates
     double gamma = -INFINITY, L = -INFINITY;
     for (int pass = 0; pass < 2; pass++) {
-        double sum = 0.0;
-        uint32_t cnt = 0;
-        for (uint64_t i = tid; i < nb; i += kLnLanes) {
-            const double ms = (((hop_z(i) + hop_z(i + 1)) + hop_z(i + 2)) + hop_z(i + 3)) / den;
-            const double l = -0.691 + 10.0 * log10(ms);
-            if (l > -70.0 && (pass == 0 || l > gamma)) {
-                sum += ms;
-                cnt++;
-            }
-        }
-        rs[tid] = sum;
-        rn[tid] = cnt;
-        __syncthreads();
-        for (uint32_t w = kLnLanes / 2; w > 0; w >>= 1) {
-            if (tid < w) {
-                rs[tid] += rs[tid + w];
-                rn[tid] += rn[tid + w];
-            }
-            __syncthreads();
-        }
-        sum = rs[0];
-        cnt = rn[0];
-        __syncthreads();
+        double sum;
+        uint32_t cnt;
+        ln_lane_partial(ms, nb, tid, pass, gamma, &sum, &cnt);
+        ln_tree_lds(rs, rn, tid, &sum, &cnt);
         if (cnt == 0)
             break;
-        const double lk = -0.691 + 10.0 * log10(sum / (double)cnt);
+        const double lk = ln_loudness(sum / (double)cnt);
         if (pass == 0)
-            gamma = lk - 10.0;
+            gamma = lk + kLnRelGate;
         else
             L = lk;
     }
     if (tid == 0) {
         const double P = 20.0 * log10(peak / 32768.0);
-        double gain = 0.0;
-        bool any = false;
         const double TP = tmode ? 20.0 * log10(tpeak / 32768.0) : NAN;
-        const double tl = U.target - L, cp = U.ceiling - (tmode ? TP : P);
-        if (isfinite(tl)) {
-            gain = tl;
-            any = true;
-        }
-        if (isfinite(cp)) {
-            gain = any ? fmin(gain, cp) : cp;
-            any = true;
-        }
+        const double gain = ln_gain_db(U.target, L, U.ceiling, tmode ? TP : P);
         LoudnessResult r;
         r.lufs = L;
         r.peak_dbfs = P;
@@ -628,6 +639,202 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_gate(const LoudnessRate *__rest
         r.g = pow(10.0, gain / 20.0);
         r.true_peak_dbtp = TP;
         res[U.slot] = r;
+    }
+}
+
+// One workgroup per group: the members' blocks through both gates as one set.  A member's partial of a pass is
+// k_ln_gate's (the lanes' strided sums, the tree); the members' partials are added in the list's order, ascending
+// utterance index.  P_G / TP_G: the largest of what k_ln_gate left for the members (log10 is monotone: the dB of the
+// largest magnitude).  Every member's gain_db and g become the group's
+__global__ __launch_bounds__(kLnLanes) void k_ln_gate_group(const LoudnessRate *__restrict__ rates,
+                                                            const LoudnessUtt *__restrict__ utts,
+                                                            const LoudnessSet *__restrict__ sets,
+                                                            const uint32_t *__restrict__ members,
+                                                            const double *__restrict__ z, LoudnessResult *res,
+                                                            LoudnessGroupResult *__restrict__ gres)
+{
+    __shared__ double rs[kLnLanes];
+    __shared__ uint32_t rn[kLnLanes];
+    const uint32_t tid = threadIdx.x;
+    const LoudnessSet S = sets[blockIdx.x];
+    const uint32_t *mem = members + S.m0;
+    double gamma = -INFINITY, L = -INFINITY;
+    for (int pass = 0; pass < 2; pass++) {
+        double gsum = 0.0;
+        uint64_t gcnt = 0;
+        for (uint32_t m = 0; m < S.nm; m++) {
+            const LoudnessUtt U = utts[mem[m]];
+            const LoudnessRate *R = rates + U.rate;
+            const uint32_t H = R->H;
+            const LnHopZ hop_z{z + U.tile0, R->tph};
+            auto ms = [&](uint64_t i) { return ln_block_ms(hop_z, i, H); };
+            double sum;
+            uint32_t cnt;
+            ln_lane_partial(ms, ln_blocks(U.n / H), tid, pass, gamma, &sum, &cnt);
+            ln_tree_lds(rs, rn, tid, &sum, &cnt);
+            gsum += sum;
+            gcnt += cnt;
+        }
+        if (gcnt == 0)
+            break;
+        const double lk = ln_loudness(gsum / (double)gcnt);
+        if (pass == 0)
+            gamma = lk + kLnRelGate;
+        else
+            L = lk;
+    }
+    // the peaks: a max is exact in any order
+    double p = -INFINITY, t = -INFINITY;
+    for (uint32_t m = tid; m < S.nm; m += kLnLanes) {
+        const LoudnessResult r = res[utts[mem[m]].slot];
+        p = fmax(p, r.peak_dbfs);
+        t = fmax(t, r.true_peak_dbtp); // (NaN in sample mode: fmax keeps -INFINITY, not used)
+    }
+    p = ln_max_lds(rs, tid, p);
+    t = ln_max_lds(rs, tid, t);
+    const LoudnessUtt U0 = utts[mem[0]];
+    const bool tmode = U0.mode == JB_PEAK_TRUE;
+    const double TP = tmode ? t : NAN;
+    const double gain = ln_gain_db(U0.target, L, U0.ceiling, tmode ? TP : p);
+    const double g = pow(10.0, gain / 20.0);
+    if (tid == 0) {
+        LoudnessGroupResult r;
+        r.lufs = L;
+        r.peak_dbfs = p;
+        r.true_peak_dbtp = TP;
+        r.gain_db = gain;
+        r.g = g;
+        gres[S.slot] = r;
+    }
+    for (uint32_t m = tid; m < S.nm; m += kLnLanes) {
+        LoudnessResult *r = res + utts[mem[m]].slot;
+        r->gain_db = gain;
+        r->g = g;
+    }
+}
+
+// One workgroup per utterance: short-term window i (hops i..i+29, ascending) to sw[tile0 + i] -- an utterance has no
+// more windows than tiles -- and its largest momentary loudness, over every block without a gate, to mm[slot]
+__global__ __launch_bounds__(kLnLanes) void k_ln_windows(const LoudnessRate *__restrict__ rates,
+                                                         const LoudnessUtt *__restrict__ utts,
+                                                         const double *__restrict__ z, double *__restrict__ sw,
+                                                         double *__restrict__ mm)
+{
+    __shared__ double rs[kLnLanes];
+    const uint32_t tid = threadIdx.x;
+    const LoudnessUtt U = utts[blockIdx.x];
+    const LoudnessRate *R = rates + U.rate;
+    const uint32_t H = R->H;
+    const uint64_t nh = U.n / H, nb = ln_blocks(nh), nw = ln_windows(nh);
+    const LnHopZ hop_z{z + U.tile0, R->tph};
+    for (uint64_t i = tid; i < nw; i += kLnLanes)
+        sw[U.tile0 + i] = ln_window_ms(hop_z, i, H);
+    double m = 0.0;
+    for (uint64_t i = tid; i < nb; i += kLnLanes)
+        m = fmax(m, ln_block_ms(hop_z, i, H));
+    m = ln_max_lds(rs, tid, m);
+    if (tid == 0)
+        mm[U.slot] = ln_loudness(m); // (no block: log10(0), -INFINITY)
+}
+
+// One workgroup per set (an utterance, or a group's members): the largest momentary and short-term loudness and the
+// loudness range.  The range's gate is a mean in the fixed order of k_ln_gate_group; its two order statistics come
+// from a radix selection over the bit patterns of the kept windows' mean squares (positive doubles: their order is
+// the integer order), 8 bits a pass into LDS histograms by integer atomics, both ranks through the same passes
+__global__ __launch_bounds__(kLnLanes) void k_ln_range(const LoudnessRate *__restrict__ rates,
+                                                       const LoudnessUtt *__restrict__ utts,
+                                                       const LoudnessSet *__restrict__ sets,
+                                                       const uint32_t *__restrict__ members,
+                                                       const double *__restrict__ sw, const double *__restrict__ mm,
+                                                       LoudnessRange *__restrict__ out)
+{
+    __shared__ double rs[kLnLanes];
+    __shared__ uint32_t rn[kLnLanes];
+    __shared__ uint32_t hist[2][256];
+    const uint32_t tid = threadIdx.x;
+    const LoudnessSet S = sets[blockIdx.x];
+    const uint32_t *mem = members + S.m0;
+    double mom = -INFINITY, st = 0.0;
+    for (uint32_t m = tid; m < S.nm; m += kLnLanes)
+        mom = fmax(mom, mm[utts[mem[m]].slot]);
+    mom = ln_max_lds(rs, tid, mom);
+    // the windows of member m: nw values at w
+    auto windows = [&](uint32_t m, const double **w) {
+        const LoudnessUtt U = utts[mem[m]];
+        *w = sw + U.tile0;
+        return ln_windows(U.n / rates[U.rate].H);
+    };
+    for (uint32_t m = 0; m < S.nm; m++) {
+        const double *w;
+        const uint64_t nw = windows(m, &w);
+        for (uint64_t i = tid; i < nw; i += kLnLanes)
+            st = fmax(st, w[i]);
+    }
+    st = ln_max_lds(rs, tid, st);
+    // pass 0: the absolute gate and the relative gate's level; pass 1: the count of what both keep
+    double gamma = -INFINITY;
+    uint64_t n = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        double gsum = 0.0;
+        uint64_t gcnt = 0;
+        for (uint32_t m = 0; m < S.nm; m++) {
+            const double *w;
+            const uint64_t nw = windows(m, &w);
+            auto ms = [&](uint64_t i) { return w[i]; };
+            double sum;
+            uint32_t cnt;
+            ln_lane_partial(ms, nw, tid, pass, gamma, &sum, &cnt);
+            ln_tree_lds(rs, rn, tid, &sum, &cnt);
+            gsum += sum;
+            gcnt += cnt;
+        }
+        if (gcnt == 0)
+            break;
+        if (pass == 0)
+            gamma = ln_loudness(gsum / (double)gcnt) + kLnRangeGate;
+        else
+            n = gcnt;
+    }
+    uint64_t rank[2] = {0, 0}, prefix[2] = {0, 0};
+    if (n) {
+        rank[0] = ln_rank(n, kLnRangeLo);
+        rank[1] = ln_rank(n, kLnRangeHi);
+    }
+    for (uint32_t pass = 0; n && pass < 8; pass++) {
+        hist[0][tid] = 0;
+        hist[1][tid] = 0;
+        __syncthreads();
+        for (uint32_t m = 0; m < S.nm; m++) {
+            const double *w;
+            const uint64_t nw = windows(m, &w);
+            for (uint64_t i = tid; i < nw; i += kLnLanes) {
+                const double v = w[i];
+                if (!ln_keep(ln_loudness(v), 1, gamma))
+                    continue;
+                const uint64_t bits = ln_bits(v);
+                const uint32_t d = ln_radix_digit(bits, pass);
+                if (ln_radix_in(bits, prefix[0], pass))
+                    atomicAdd(&hist[0][d], 1u);
+                if (ln_radix_in(bits, prefix[1], pass))
+                    atomicAdd(&hist[1][d], 1u);
+            }
+        }
+        __syncthreads();
+        // (every thread walks the bins itself: the same answer everywhere, no broadcast)
+        for (int k = 0; k < 2; k++)
+            prefix[k] = (prefix[k] << 8) | ln_radix_pick(hist[k], &rank[k]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        LoudnessRange r;
+        r.max_momentary = mom;
+        r.max_short_term = ln_loudness(st); // (no window: -INFINITY)
+        r.n = n;
+        const double lo = ln_from_bits(prefix[0]), hi = ln_from_bits(prefix[1]);
+        r.lra = n ? 10.0 * log10(hi / lo) : 0.0;
+        r.lra_low = n ? ln_loudness(lo) : NAN;
+        r.lra_high = n ? ln_loudness(hi) : NAN;
+        out[S.rslot] = r;
     }
 }
 
@@ -697,9 +904,41 @@ hipError_t launch_loudness_apply(const LoudnessUtt *utts_dev, uint32_t n, uint64
     return hipGetLastError();
 }
 
+hipError_t launch_loudness_groups(const LoudnessRate *rates_dev, const LoudnessUtt *utts_all, const LoudnessSet *sets_dev,
+                                  uint32_t n, const uint32_t *members, const double *z, LoudnessResult *res,
+                                  LoudnessGroupResult *gres, hipStream_t stream)
+{
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_ln_gate_group, dim3(n), dim3(kLnLanes), 0, stream, rates_dev, utts_all, sets_dev, members, z,
+                       res, gres);
+    return hipGetLastError();
+}
+
+hipError_t launch_loudness_range(const LoudnessRate *rates_dev, const LoudnessUtt *utts_dev, uint32_t n_utts,
+                                 const LoudnessUtt *utts_all, const LoudnessSet *sets_dev, uint32_t n_sets,
+                                 const uint32_t *members, const double *z, double *sw, double *mm,
+                                 LoudnessRange *r128, hipStream_t stream)
+{
+    if (n_utts)
+        hipLaunchKernelGGL(k_ln_windows, dim3(n_utts), dim3(kLnLanes), 0, stream, rates_dev, utts_dev, z, sw, mm);
+    if (n_sets)
+        hipLaunchKernelGGL(k_ln_range, dim3(n_sets), dim3(kLnLanes), 0, stream, rates_dev, utts_all, sets_dev, members,
+                           sw, mm, r128);
+    return hipGetLastError();
+}
+
 // The measurement on PCM the caller holds: out[u] of in[u]; mode: what every utterance's ceiling term would read
+// gr (null: none): the utterances in these groups against one target and ceiling, with the R128 fields
+struct PcmGroups {
+    LnGroups plan;
+    double target = NAN, ceiling = INFINITY;
+    std::vector<LoudnessGroupResult> gres; // [G]
+    std::vector<LoudnessRange> r128;       // [n] the utterances, then [G] the groups
+};
+
 int measure_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
-                      uint32_t mode, const char *what, std::vector<LoudnessResult> *res)
+                      uint32_t mode, const char *what, std::vector<LoudnessResult> *res, PcmGroups *gr = nullptr)
 {
     if (n && (!in || !n_in))
         return JB_ERR_INVALID;
@@ -736,8 +975,8 @@ int measure_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uin
         w.tile0 = w.lt0 = tiles;
         w.slot = (uint32_t)u;
         w.mode = mode;
-        w.target = NAN;
-        w.ceiling = INFINITY;
+        w.target = gr ? gr->target : NAN;
+        w.ceiling = gr ? gr->ceiling : INFINITY;
         tiles += w.ntiles;
         samples += w.n;
     }
@@ -778,6 +1017,49 @@ int measure_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uin
         e = hipMemcpyAsync(du, utts.data(), sizeof(LoudnessUtt) * n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
         e = launch_loudness_measure(dr, du, (uint32_t)n, tiles, dst, dpk, dtp, dz, dres, mode == JB_PEAK_TRUE, s);
+    if (gr && n && e == hipSuccess) {
+        // the sets: every utterance (members: the identity), then every group
+        const size_t G = gr->plan.size();
+        std::vector<LoudnessSet> sets(n + G);
+        std::vector<uint32_t> members(2 * n);
+        for (size_t u = 0; u < n; u++) {
+            sets[u] = LoudnessSet{(uint32_t)u, 1, (uint32_t)u, (uint32_t)u};
+            members[u] = (uint32_t)u;
+            members[n + u] = gr->plan.members[u];
+        }
+        for (size_t g = 0; g < G; g++)
+            sets[n + g] = LoudnessSet{(uint32_t)n + gr->plan.first[g], gr->plan.first[g + 1] - gr->plan.first[g],
+                                      (uint32_t)g, (uint32_t)(n + g)};
+        LoudnessSet *dsets = nullptr;
+        uint32_t *dmem = nullptr;
+        LoudnessGroupResult *dgres = nullptr;
+        LoudnessRange *dr128 = nullptr;
+        double *dsw = nullptr, *dmm = nullptr;
+        gr->gres.assign(G, LoudnessGroupResult{});
+        gr->r128.assign(n + G, LoudnessRange{});
+        if ((e = scratch.alloc(&dsets, n + G)) == hipSuccess && (e = scratch.alloc(&dmem, 2 * n)) == hipSuccess &&
+            (e = scratch.alloc(&dgres, G)) == hipSuccess && (e = scratch.alloc(&dr128, n + G)) == hipSuccess &&
+            (e = scratch.alloc(&dsw, std::max<uint64_t>(tiles, 1))) == hipSuccess &&
+            (e = scratch.alloc(&dmm, n)) == hipSuccess &&
+            (e = hipMemcpyAsync(dsets, sets.data(), sizeof(LoudnessSet) * (n + G), hipMemcpyHostToDevice, s)) ==
+                hipSuccess &&
+            (e = hipMemcpyAsync(dmem, members.data(), sizeof(uint32_t) * 2 * n, hipMemcpyHostToDevice, s)) ==
+                hipSuccess &&
+            (e = launch_loudness_groups(dr, du, dsets + n, (uint32_t)G, dmem, dz, dres, dgres, s)) == hipSuccess &&
+            (e = launch_loudness_range(dr, du, (uint32_t)n, du, dsets, (uint32_t)(n + G), dmem, dz, dsw, dmm, dr128,
+                                       s)) == hipSuccess &&
+            (e = hipMemcpyAsync(gr->gres.data(), dgres, sizeof(LoudnessGroupResult) * G, hipMemcpyDeviceToHost, s)) ==
+                hipSuccess)
+            e = hipMemcpyAsync(gr->r128.data(), dr128, sizeof(LoudnessRange) * (n + G), hipMemcpyDeviceToHost, s);
+        // (the sources of the asynchronous copies live to the wait below)
+        if (e == hipSuccess && n)
+            e = hipMemcpyAsync(out.data(), dres, sizeof(LoudnessResult) * n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (e != hipSuccess)
+            return hip_fail(e, what);
+        return JB_OK;
+    }
     if (e == hipSuccess && n)
         e = hipMemcpyAsync(out.data(), dres, sizeof(LoudnessResult) * n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
@@ -808,6 +1090,60 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
         lufs[u] = out[u].lufs;
         peak_dbfs[u] = out[u].peak_dbfs;
     }
+    return JB_OK;
+}
+
+int jb_loudness_groups_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *group,
+                                 uint32_t hz, int32_t device, uint32_t mode, double target_lufs, double ceiling_db,
+                                 uint32_t *group_of, jb_loudness_group_report *groups, size_t groups_cap,
+                                 size_t *n_groups, jb_loudness_r128 *utt_r128, double *utt_lufs)
+{
+    if (mode != JB_PEAK_SAMPLE && mode != JB_PEAK_TRUE) {
+        set_error("jb_loudness_groups_pcm_batch: a mode is JB_PEAK_SAMPLE or JB_PEAK_TRUE");
+        return JB_ERR_INVALID;
+    }
+    if (n > 0x7fffffffu || (groups_cap && !groups))
+        return JB_ERR_INVALID;
+    PcmGroups gr;
+    gr.target = target_lufs;
+    gr.ceiling = ceiling_db;
+    std::vector<uint32_t> own(n, kLnNoGroup);
+    LnGroupsIn gi;
+    gi.B = n;
+    gi.group = group ? group : own.data();
+    uint32_t bad = 0;
+    const char *field = "";
+    if (!plan_loudness_groups(gi, &gr.plan, &bad, &field)) {
+        set_error("jb_loudness_groups_pcm_batch: " + std::string(field) + " " + std::to_string(bad) +
+                  " (an id is below n, or JB_LOUDNESS_NO_GROUP)");
+        return JB_ERR_INVALID;
+    }
+    const size_t G = gr.plan.size();
+    if (n_groups)
+        *n_groups = G;
+    if (G > groups_cap && groups) {
+        set_error("jb_loudness_groups_pcm_batch: " + std::to_string(G) + " groups, room for " +
+                  std::to_string(groups_cap));
+        return JB_ERR_BUFFER;
+    }
+    std::vector<LoudnessResult> out;
+    int rc = measure_pcm_batch(in, n_in, n, hz, device, mode, "jb_loudness_groups_pcm_batch", &out, &gr);
+    if (rc)
+        return rc;
+    uint32_t F = 1;
+    if ((rc = true_peak_table(hz, &F, nullptr)))
+        return rc;
+    for (size_t u = 0; u < n; u++) {
+        if (group_of)
+            group_of[u] = gr.plan.group_of[u];
+        if (utt_r128)
+            loudness_r128_out(gr.r128[u], &utt_r128[u]);
+        if (utt_lufs)
+            utt_lufs[u] = out[u].lufs;
+    }
+    for (size_t g = 0; groups && g < G; g++)
+        loudness_group_report(gr.gres[g], mode, F, gr.plan.first[g + 1] - gr.plan.first[g], &gr.r128[n + g],
+                              &groups[g]);
     return JB_OK;
 }
 

@@ -97,6 +97,11 @@ static int synthesize_multi(const jb_engine *e, const char *const *lines, const 
     int rc = check_devices(devices, n_devices);
     if (rc)
         return rc;
+    if (jb_engine_get_loudness_scope(e) == JB_LOUDNESS_PER_REQUEST) {
+        set_error("jb_synthesize_batch_multi: per-request loudness scope needs the request on one device (a loudness "
+                  "group does not span devices); use jb_synthesize_batch, or JB_LOUDNESS_PER_UTTERANCE");
+        return JB_ERR_INVALID;
+    }
     for (size_t u = 0; u < n_utts; u++) {
         pcm[u] = nullptr;
         n_samples[u] = 0;

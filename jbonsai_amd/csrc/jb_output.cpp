@@ -87,4 +87,73 @@ OutPlan plan_output(const OutPlanIn &in)
     return p;
 }
 
+bool plan_loudness_groups(const LnGroupsIn &in, LnGroups *out, uint32_t *bad_group, const char **bad_field)
+{
+    const size_t B = in.B;
+    auto refuse = [&](uint32_t id, const char *field) {
+        if (bad_group)
+            *bad_group = id;
+        if (bad_field)
+            *bad_field = field;
+        return false;
+    };
+    LnGroups g;
+    g.group_of.assign(B, 0);
+    std::vector<uint32_t> dense_of(B, kLnNoGroup); // caller's id -> dense id
+    std::vector<uint32_t> first_member;            // dense id -> its first member
+    for (size_t u = 0; u < B; u++) {
+        const uint32_t id = in.group[u];
+        if (id != kLnNoGroup && id >= B)
+            return refuse(id, "group id");
+        uint32_t d = id == kLnNoGroup ? kLnNoGroup : dense_of[id];
+        if (d == kLnNoGroup) {
+            d = (uint32_t)first_member.size();
+            first_member.push_back((uint32_t)u);
+            if (id != kLnNoGroup)
+                dense_of[id] = d;
+        }
+        g.group_of[u] = d;
+        // a member agrees with its group's first member
+        const size_t f = first_member[d];
+        if (f == u)
+            continue;
+        if (in.target) {
+            const double a = in.target[f], b = in.target[u];
+            if (!(a == b || (a != a && b != b)))
+                return refuse(id, "target");
+            if (in.ceiling && in.ceiling[f] != in.ceiling[u])
+                return refuse(id, "ceiling");
+        }
+        if (in.mode && in.mode[f] != in.mode[u])
+            return refuse(id, "peak mode");
+        if (in.hz && in.hz[f] != in.hz[u])
+            return refuse(id, "output rate");
+    }
+    const size_t G = first_member.size();
+    g.first.assign(G + 1, 0);
+    for (size_t u = 0; u < B; u++)
+        g.first[g.group_of[u] + 1]++;
+    for (size_t d = 0; d < G; d++)
+        g.first[d + 1] += g.first[d];
+    g.members.assign(B, 0);
+    std::vector<uint32_t> fill(g.first.begin(), g.first.end() - 1);
+    for (size_t u = 0; u < B; u++)
+        g.members[fill[g.group_of[u]]++] = (uint32_t)u;
+    *out = std::move(g);
+    return true;
+}
+
+void loudness_groups_closure(const LnGroups &g, const std::vector<uint8_t> &touched, std::vector<uint8_t> *groups,
+                             std::vector<uint8_t> *members)
+{
+    const size_t B = g.group_of.size();
+    groups->assign(g.size(), 0);
+    members->assign(B, 0);
+    for (size_t u = 0; u < B; u++)
+        if (touched[u])
+            (*groups)[g.group_of[u]] = 1;
+    for (size_t u = 0; u < B; u++)
+        (*members)[u] = (*groups)[g.group_of[u]];
+}
+
 } // namespace jb

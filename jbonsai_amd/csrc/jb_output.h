@@ -89,4 +89,36 @@ struct OutPlan {
 // Pure: no globals, no environment.
 OutPlan plan_output(const OutPlanIn &in);
 
+// Loudness groups (jb_batch_set_loudness_groups): one measurement and one gain for the members of a group.
+constexpr uint32_t kLnNoGroup = 0xffffffffu; // JB_LOUDNESS_NO_GROUP: the utterance is a group of its own
+
+// What the group bookkeeping reads.  An entry of `group` is a caller's id below B or kLnNoGroup
+struct LnGroupsIn {
+    size_t B = 0;
+    const uint32_t *group = nullptr;  // [B]
+    const double *target = nullptr;   // [B] (NaN: measured only); nullptr: no target set yet, nothing to compare
+    const double *ceiling = nullptr;  // [B], with target
+    const uint32_t *mode = nullptr;   // [B] JB_PEAK_*; nullptr: the sample peak everywhere
+    const uint32_t *hz = nullptr;     // [B] output rate
+};
+
+// Groups numbered densely in the order of their first member (an ungrouped utterance: a group of one, numbered the
+// same way); group g owns members[first[g] .. first[g + 1]), ascending utterance indices
+struct LnGroups {
+    std::vector<uint32_t> group_of; // [B]
+    std::vector<uint32_t> first;    // [G + 1]
+    std::vector<uint32_t> members;  // [B]
+    size_t size() const { return first.empty() ? 0 : first.size() - 1; }
+};
+
+// Pure.  false: the request is refused; *bad_group is the caller's id of the first offending group (kLnNoGroup for
+// an entry that is no id) and *bad_field names what its members disagree on ("target", "ceiling", "peak mode",
+// "output rate") or says "group id" for an id of B or above.  Two NaN targets agree
+bool plan_loudness_groups(const LnGroupsIn &in, LnGroups *out, uint32_t *bad_group, const char **bad_field);
+
+// The redo closure.  touched: [B] 1 = an utterance a redo round rewrote.  groups: [G] 1 = a group with a touched
+// member; members: [B] 1 = a member of such a group (a superset of touched)
+void loudness_groups_closure(const LnGroups &g, const std::vector<uint8_t> &touched, std::vector<uint8_t> *groups,
+                             std::vector<uint8_t> *members);
+
 } // namespace jb

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <new>
+#include <string>
 
 namespace jb {
 
@@ -71,8 +72,84 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
         if (want[u] && (rc = resample_design(in, want[u], nullptr, nullptr)))
             return rc;
     }
+    if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)))
+        return rc;
     want_hz = std::move(want);
     replan();
+    return JB_OK;
+}
+
+// The combined request: the groups of `group` under these targets, ceilings, modes and rates (each empty: not set)
+int OutputChain::check_groups(const std::vector<uint32_t> &group, const std::vector<double> &target,
+                              const std::vector<double> &ceiling, const std::vector<uint32_t> &mode,
+                              const std::vector<uint32_t> &want, const char *who, LnGroups *out) const
+{
+    if (group.empty())
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    std::vector<uint32_t> hz(B, b.voice.sampling_frequency);
+    for (size_t u = 0; u < want.size(); u++)
+        if (want[u])
+            hz[u] = want[u];
+    LnGroupsIn in;
+    in.B = B;
+    in.group = group.data();
+    in.target = target.empty() ? nullptr : target.data();
+    in.ceiling = ceiling.empty() ? nullptr : ceiling.data();
+    in.mode = mode.empty() ? nullptr : mode.data();
+    in.hz = hz.data();
+    LnGroups plan;
+    uint32_t bad = 0;
+    const char *field = "";
+    if (!plan_loudness_groups(in, &plan, &bad, &field)) {
+        if (std::string(field) == "group id")
+            set_error(std::string(who) + ": group id " + std::to_string(bad) +
+                      " (an id is below the batch size, or JB_LOUDNESS_NO_GROUP)");
+        else
+            set_error(std::string(who) + ": the members of loudness group " + std::to_string(bad) +
+                      " would disagree on the " + field);
+        return JB_ERR_INVALID;
+    }
+    if (out)
+        *out = std::move(plan);
+    return JB_OK;
+}
+
+int OutputChain::set_loudness_groups(const uint32_t *group, size_t n)
+{
+    int rc = check_settable("jb_batch_set_loudness_groups: the groups are set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!group && n == 0) {
+        ln_group_req.clear();
+        ln_groups = LnGroups{};
+        return JB_OK;
+    }
+    if (!group || n != (size_t)b.B) {
+        set_error("jb_batch_set_loudness_groups: give one group per utterance");
+        return JB_ERR_INVALID;
+    }
+    std::vector<uint32_t> req(group, group + n);
+    LnGroups plan;
+    if ((rc = check_groups(req, ln_target, ln_ceiling, ln_mode, want_hz, "jb_batch_set_loudness_groups", &plan)))
+        return rc;
+    if (req.empty()) // (an empty batch: nothing to group)
+        return JB_OK;
+    ln_group_req = std::move(req);
+    ln_groups = std::move(plan);
+    return JB_OK;
+}
+
+int OutputChain::set_loudness_report(uint32_t flags)
+{
+    int rc = check_settable("jb_batch_set_loudness_report: the report is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (flags & ~(uint32_t)JB_LOUDNESS_R128) {
+        set_error("jb_batch_set_loudness_report: flags are JB_LOUDNESS_R128 or 0");
+        return JB_ERR_INVALID;
+    }
+    ln_report = flags;
     return JB_OK;
 }
 
@@ -85,12 +162,15 @@ int OutputChain::set_loudness(const double *target, const double *ceiling, size_
         set_error("jb_batch_set_loudness_target: give one target, or one per utterance");
         return JB_ERR_INVALID;
     }
-    ln_target.assign((size_t)b.B, 0.0);
-    ln_ceiling.assign((size_t)b.B, 0.0);
+    std::vector<double> t((size_t)b.B, 0.0), c((size_t)b.B, 0.0);
     for (size_t u = 0; u < (size_t)b.B; u++) {
-        ln_target[u] = target[n == 1 ? 0 : u];
-        ln_ceiling[u] = ceiling[n == 1 ? 0 : u];
+        t[u] = target[n == 1 ? 0 : u];
+        c[u] = ceiling[n == 1 ? 0 : u];
     }
+    if ((rc = check_groups(ln_group_req, t, c, ln_mode, want_hz, "jb_batch_set_loudness_target", nullptr)))
+        return rc;
+    ln_target = std::move(t);
+    ln_ceiling = std::move(c);
     ln_on = true;
     replan();
     return JB_OK;
@@ -111,9 +191,12 @@ int OutputChain::set_peak_mode(const uint32_t *mode, size_t n)
             set_error("jb_batch_set_peak_mode: a mode is JB_PEAK_SAMPLE or JB_PEAK_TRUE");
             return JB_ERR_INVALID;
         }
-    ln_mode.assign((size_t)b.B, JB_PEAK_SAMPLE);
+    std::vector<uint32_t> m((size_t)b.B, JB_PEAK_SAMPLE);
     for (size_t u = 0; u < (size_t)b.B; u++)
-        ln_mode[u] = mode[n == 1 ? 0 : u];
+        m[u] = mode[n == 1 ? 0 : u];
+    if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, m, want_hz, "jb_batch_set_peak_mode", nullptr)))
+        return rc;
+    ln_mode = std::move(m);
     return JB_OK;
 }
 
@@ -309,6 +392,33 @@ int OutputChain::prepare_loudness()
         return hip_fail(e, "loudness work list");
     ln.tiles = tiles;
     ln.atiles = atiles;
+    // with a group or a report request: the sets (every utterance, then every group) and what their kernels write
+    const bool grouped = !ln_group_req.empty();
+    if ((!grouped && !ln_report) || B == 0)
+        return JB_OK;
+    const size_t G = ln_groups.size();
+    ln.sets.assign(B + G, LoudnessSet{});
+    std::vector<uint32_t> members(grouped ? 2 * B : B);
+    for (size_t u = 0; u < B; u++) {
+        ln.sets[u] = LoudnessSet{(uint32_t)u, 1, (uint32_t)u, (uint32_t)u};
+        members[u] = (uint32_t)u;
+        if (grouped)
+            members[B + u] = ln_groups.members[u];
+    }
+    for (size_t g = 0; g < G; g++)
+        ln.sets[B + g] = LoudnessSet{(uint32_t)B + ln_groups.first[g], ln_groups.first[g + 1] - ln_groups.first[g],
+                                     (uint32_t)g, (uint32_t)(B + g)};
+    if ((rc = b.dalloc(&ln.sets_dev, B + G, false)) || (rc = b.dalloc(&ln.sets_redo_dev, B + G, false)) ||
+        (rc = b.dalloc(&ln.members_dev, members.size(), false)) ||
+        (grouped && ((rc = b.dalloc(&ln.gres, G, false)) || (rc = b.dalloc(&ln.apply_redo_dev, B, false)))) ||
+        (ln_report && ((rc = b.dalloc(&ln.sw, nt, false)) || (rc = b.dalloc(&ln.mm, B, false)) ||
+                       (rc = b.dalloc(&ln.r128, B + G, false)))))
+        return rc;
+    if ((e = hipMemcpy(ln.sets_dev, ln.sets.data(), sizeof(LoudnessSet) * (B + G), hipMemcpyHostToDevice)) !=
+            hipSuccess ||
+        (e = hipMemcpy(ln.members_dev, members.data(), sizeof(uint32_t) * members.size(), hipMemcpyHostToDevice)) !=
+            hipSuccess)
+        return hip_fail(e, "loudness group list");
     return JB_OK;
 }
 
@@ -444,7 +554,21 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const uint32_t n_all_work = (uint32_t)fl.work.size();
     uint32_t n_tiles = (uint32_t)rs.tiles.size(), n_utts = B, n_work = n_all_work;
     uint64_t lt = ln.tiles, at = ln.atiles;
+    // loudness groups and the R128 report (with a target only): the utterances the apply pass takes, the groups, the
+    // report's sets
+    const bool grouped = plan.normalize() && ln.gres, report = plan.normalize() && ln.r128;
+    const size_t G = grouped ? ln_groups.size() : 0;
+    const LoudnessUtt *apply_utts = ln.utts_dev;
+    uint32_t n_apply = B, n_gsets = (uint32_t)G, n_rsets = report ? (uint32_t)(B + G) : 0;
+    const LoudnessSet *gsets = grouped ? ln.sets_dev + B : nullptr, *rsets = ln.sets_dev;
+    // behind the apply pass a group's gain reaches every member: the stages there run again for all of them
+    std::vector<uint8_t> touched_groups, group_members;
+    const std::vector<uint8_t> *post = only;
     hipError_t e = hipSuccess;
+    if (only && grouped) {
+        loudness_groups_closure(ln_groups, *only, &touched_groups, &group_members);
+        post = &group_members;
+    }
     if (only) {
         // of a redo: the tiles, the utterances (renumbered: their scratch stays where it is) and the FLAC blocks of
         // the utterances it rewrote, uploaded before the first launch
@@ -454,19 +578,33 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         std::vector<uint32_t> md5_sub;
         std::vector<FormatUtt> fm_sub;
         std::vector<AdpcmUtt> ad_sub;
+        std::vector<LoudnessUtt> ap_sub; // grouped: the apply pass's own list
+        std::vector<LoudnessSet> set_sub;
         lt = at = ft = ag = 0;
+        uint64_t mat = 0; // apply tiles of the measured list (its at0 is not read when the apply pass has its own)
         for (size_t u = 0; u < B; u++) {
-            if (!(*only)[u])
+            if ((*only)[u]) {
+                if (plan.convert)
+                    rs_sub.insert(rs_sub.end(), rs.tiles.begin() + rs.tile_lo[u],
+                                  rs.tiles.begin() + rs.tile_lo[u + 1]);
+                if (plan.normalize()) {
+                    LoudnessUtt w = ln.utts[u];
+                    w.lt0 = lt;
+                    w.at0 = mat;
+                    lt += w.ntiles;
+                    mat += (w.n + kLnApplyTile - 1) / kLnApplyTile;
+                    ln_sub.push_back(w);
+                    if (report)
+                        set_sub.push_back(ln.sets[u]);
+                }
+            }
+            if (!(*post)[u])
                 continue;
-            if (plan.convert)
-                rs_sub.insert(rs_sub.end(), rs.tiles.begin() + rs.tile_lo[u], rs.tiles.begin() + rs.tile_lo[u + 1]);
-            if (plan.normalize()) {
+            if (grouped) {
                 LoudnessUtt w = ln.utts[u];
-                w.lt0 = lt;
                 w.at0 = at;
-                lt += w.ntiles;
                 at += (w.n + kLnApplyTile - 1) / kLnApplyTile;
-                ln_sub.push_back(w);
+                ap_sub.push_back(w);
             }
             if (fmt) {
                 FormatUtt w = fm.utts[u];
@@ -481,11 +619,23 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
                 ad_sub.push_back(w);
             }
         }
+        if (!grouped)
+            at = mat;
+        const uint32_t n_usets = (uint32_t)set_sub.size();
+        for (size_t g = 0; g < G; g++)
+            if (touched_groups[g])
+                set_sub.push_back(ln.sets[B + g]);
+        n_gsets = (uint32_t)set_sub.size() - n_usets;
+        n_rsets = report ? (uint32_t)set_sub.size() : 0;
+        rsets = ln.sets_redo_dev;
+        gsets = ln.sets_redo_dev + n_usets;
+        n_apply = grouped ? (uint32_t)ap_sub.size() : (uint32_t)ln_sub.size();
+        apply_utts = grouped ? ln.apply_redo_dev : ln.redo_dev;
         for (const FlacWork &w : fl.work)
-            if ((*only)[w.utt])
+            if ((*post)[w.utt])
                 fl_sub.push_back(w);
         if (fl.digests)
-            flac_md5_order(fl.utts, only, &md5_sub); // (an utterance without frames keeps its digest of no samples)
+            flac_md5_order(fl.utts, post, &md5_sub); // (an utterance without frames keeps its digest of no samples)
         tiles = rs.redo_dev;
         utts = ln.redo_dev;
         work = fl.redo_dev;
@@ -498,12 +648,16 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         n_tiles = (uint32_t)rs_sub.size();
         n_utts = (uint32_t)ln_sub.size();
         n_work = (uint32_t)fl_sub.size();
-        if (!n_tiles && !n_utts && !n_work && !n_futts && !n_autts)
+        if (!n_tiles && !n_utts && !n_work && !n_futts && !n_autts && !n_apply)
             return JB_OK;
         if ((n_tiles && (e = hipMemcpy(rs.redo_dev, rs_sub.data(), sizeof(ResampleTile) * n_tiles,
                                        hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_utts && (e = hipMemcpy(ln.redo_dev, ln_sub.data(), sizeof(LoudnessUtt) * n_utts,
                                       hipMemcpyHostToDevice)) != hipSuccess) ||
+            (!ap_sub.empty() && (e = hipMemcpy(ln.apply_redo_dev, ap_sub.data(), sizeof(LoudnessUtt) * ap_sub.size(),
+                                               hipMemcpyHostToDevice)) != hipSuccess) ||
+            (!set_sub.empty() && (e = hipMemcpy(ln.sets_redo_dev, set_sub.data(), sizeof(LoudnessSet) * set_sub.size(),
+                                                hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_work && (e = hipMemcpy(fl.redo_dev, fl_sub.data(), sizeof(FlacWork) * n_work, hipMemcpyHostToDevice)) !=
                            hipSuccess) ||
             (n_md5 && (e = hipMemcpy(fl.md5_redo_dev, md5_sub.data(), sizeof(uint32_t) * n_md5,
@@ -521,7 +675,12 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     if (plan.normalize() && (!only || n_utts) &&
         ((e = launch_loudness_measure(ln.rates_dev, utts, n_utts, lt, ln.st, ln.pk, ln.tp, ln.z, ln.res, ln.true_peak,
                                       st)) != hipSuccess ||
-         (e = launch_loudness_apply(utts, n_utts, at, ln.res, plan.apply.i16, st)) != hipSuccess))
+         // the groups' gate over the measured members' scratch, the report, then one gain for every member
+         (grouped && (e = launch_loudness_groups(ln.rates_dev, ln.utts_dev, gsets, n_gsets, ln.members_dev, ln.z,
+                                                 ln.res, ln.gres, st)) != hipSuccess) ||
+         (report && (e = launch_loudness_range(ln.rates_dev, utts, n_utts, ln.utts_dev, rsets, n_rsets, ln.members_dev,
+                                               ln.z, ln.sw, ln.mm, ln.r128, st)) != hipSuccess) ||
+         (e = launch_loudness_apply(apply_utts, n_apply, at, ln.res, plan.apply.i16, st)) != hipSuccess))
         return hip_fail(e, only ? "loudness(redo)" : "loudness");
     // FLAC: the blocks of the list, the digests of its utterances' now final PCM (on request), then every stream's
     // offsets, place and header (all of fl.work_dev, redo or not): the pack never sees a digest of replaced PCM
@@ -557,6 +716,27 @@ int OutputChain::read_loudness(size_t u, LoudnessResult *r)
     int rc = check_ready(plan.normalize(), "jb_batch_loudness: the batch has not run",
                          "jb_batch_loudness: no loudness target is set");
     return rc ? rc : b.read(ln.res + u, r, sizeof *r);
+}
+
+uint32_t OutputChain::group_members(size_t u) const
+{
+    const uint32_t g = ln_groups.group_of[u];
+    return ln_groups.first[g + 1] - ln_groups.first[g];
+}
+
+int OutputChain::read_loudness_group(size_t u, LoudnessGroupResult *r)
+{
+    int rc = check_ready(plan.normalize() && !ln_group_req.empty(), "jb_batch_loudness_group: the batch has not run",
+                         "jb_batch_loudness_group: needs a loudness target and jb_batch_set_loudness_groups");
+    return rc ? rc : b.read(ln.gres + ln_groups.group_of[u], r, sizeof *r);
+}
+
+int OutputChain::read_loudness_range(size_t u, bool of_group, LoudnessRange *r)
+{
+    int rc = check_ready(plan.normalize() && ln_report && (!of_group || !ln_group_req.empty()),
+                         "loudness report: the batch has not run",
+                         "loudness report: needs a loudness target and jb_batch_set_loudness_report");
+    return rc ? rc : b.read(ln.r128 + (of_group ? (size_t)b.B + ln_groups.group_of[u] : u), r, sizeof *r);
 }
 
 int OutputChain::flac_ready() const

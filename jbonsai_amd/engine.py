@@ -156,6 +156,12 @@ class _Condition:
         """What the ceiling bounds: 0 = the sample peak (the default), 1 = the true peak (dBTP)."""
         F.check(self._L().jb_engine_set_peak_mode(self._h(), int(mode)))
     def get_peak_mode(self): return self._L().jb_engine_get_peak_mode(self._h())
+    def set_loudness_scope(self, scope):
+        """What one gain of the target covers: 0 = each utterance (the default), 1 = the whole request
+        (_ffi.LOUDNESS_PER_UTTERANCE / LOUDNESS_PER_REQUEST): the utterances of one synthesize_batch call keep
+        their relative levels."""
+        F.check(self._L().jb_engine_set_loudness_scope(self._h(), int(scope)))
+    def get_loudness_scope(self): return self._L().jb_engine_get_loudness_scope(self._h())
     def set_tree_search(self, mode):
         """Where the per-label tree search runs: 0 = host threads (the default), 1 = the device from the measured
         request size on, 2 = the device always (_ffi.SEARCH_*)."""
@@ -226,6 +232,14 @@ class Engine:
 
     def clone(self) -> "Engine":
         return Engine.new(self, self)
+
+    def set_loudness_scope(self, scope):
+        """jb_engine_set_loudness_scope (the Condition's setter, on the engine): _ffi.LOUDNESS_PER_UTTERANCE or
+        _ffi.LOUDNESS_PER_REQUEST."""
+        self.condition.set_loudness_scope(scope)
+
+    def get_loudness_scope(self):
+        return self.condition.get_loudness_scope()
 
     def close(self):
         if getattr(self, "_h", None):
