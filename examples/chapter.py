@@ -1,0 +1,58 @@
+"""A chapter as one file: several label files in, ONE FLAC stream or WAV file out -- sentence, pause, sentence.
+
+    python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
+                               [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
+                               [--loudness LUFS [--ceiling DBFS]] [--rate HZ]
+
+Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
+batch and joined on the GPU (Engine.synthesize_programme) in front of the encoder, so a .flac output is one stream whose
+frame numbers, STREAMINFO, MD5 and SEEKTABLE (a point about every second) cover the whole chapter; any other name is
+written as a 16-bit WAV file.  With --loudness the chapter gets ONE gain (per-request loudness scope), so the sentences
+keep their relative levels.  The cue list -- each sentence's first sample and time within the chapter -- is printed.
+Needs an MI355X: the library has no CPU path.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import jbonsai_amd as J  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("voice")
+ap.add_argument("labels", nargs="+", help="one label file per sentence")
+ap.add_argument("-o", "--out", default="chapter.flac")
+ap.add_argument("--lead-ms", type=float, default=0.0, help="silence in front of the first sentence")
+ap.add_argument("--gap-ms", type=float, default=500.0, help="silence between two sentences")
+ap.add_argument("--trail-ms", type=float, default=0.0, help="silence behind the last sentence")
+ap.add_argument("--fade-ms", type=float, default=5.0, help="fade at both edges of every sentence")
+ap.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="target loudness of the chapter")
+ap.add_argument("--ceiling", type=float, default=-1.0, metavar="DBFS", help="sample-peak ceiling (with --loudness)")
+ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate")
+args = ap.parse_args()
+
+sentences = []
+for path in args.labels:
+    with open(path) as f:
+        sentences.append([ln for ln in f.read().split("\n") if ln and not ln.startswith("#")])
+
+engine = J.Engine.load([args.voice])
+if args.rate:
+    engine.condition.set_output_sampling_frequency(args.rate)
+if args.loudness is not None:
+    engine.condition.set_loudness_target(args.loudness)
+    engine.condition.set_peak_ceiling(args.ceiling)
+    engine.set_loudness_scope(J.LOUDNESS_PER_REQUEST)
+hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
+join = dict(lead_ms=args.lead_ms, gap_ms=args.gap_ms, trail_ms=args.trail_ms, fade_ms=args.fade_ms)
+if args.out.endswith(".flac"):
+    data, starts = engine.synthesize_programme(sentences, sink="flac", md5=True, seek_interval_ms=1000, **join)
+    with open(args.out, "wb") as f:
+        f.write(data)
+    print(f"wrote {args.out}: {len(data)} bytes of FLAC at {hz} Hz, MD5 {data[26:42].hex()}")
+else:
+    pcm, starts = engine.synthesize_programme(sentences, sink="i16", **join)
+    J.write_wav(args.out, pcm, hz)
+    print(f"wrote {args.out}: {pcm.size} samples at {hz} Hz")
+for k, (s, path) in enumerate(zip(starts, args.labels)):
+    print(f"cue {k} {s} {s / hz:.3f} {path}")

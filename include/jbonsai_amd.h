@@ -141,6 +141,22 @@ typedef struct jb_adpcm_opts {
     uint32_t block_align;
     uint32_t reserved[3];
 } jb_adpcm_opts;
+/* The join request of one utterance (see "Join" below): the programme it belongs to, the zero samples before and
+ * after it and the lengths of its edge fades.  reserved must be 0. */
+#define JB_JOIN_NONE 0xffffffffu
+typedef struct jb_join_utt {
+    uint32_t programme;             /* id below jb_batch_size(b), or JB_JOIN_NONE: a programme of its own */
+    uint32_t fade_in, fade_out;     /* samples at the output rate; 0: none */
+    uint32_t reserved;              /* 0 */
+    uint64_t pad_before, pad_after; /* zero samples at the output rate */
+} jb_join_utt;
+/* The join of a jb_synthesize_programme* call: all its utterances are one programme.  lead_ms of zeros in front of the
+ * first, gap_ms between neighbours, trail_ms behind the last, a fade of fade_ms at both edges of every utterance; each
+ * in samples at the output rate by jb_join_ms_to_samples.  Finite and not negative; reserved 0. */
+typedef struct jb_join_opts {
+    double lead_ms, gap_ms, trail_ms, fade_ms;
+    uint32_t reserved[2];
+} jb_join_opts;
 
 typedef struct jb_batch_opts {
     int32_t device;         /* HIP device ordinal; -1 = current */
@@ -472,6 +488,35 @@ int jb_batch_adpcm_block_align(jb_batch *b, size_t utt, uint32_t *block_align);
 int jb_batch_read_adpcm(jb_batch *b, size_t utt, uint8_t *dst, size_t cap);
 /* Every utterance: dst[u] must hold jb_batch_adpcm_size(b, u) bytes (one device-to-host copy for the batch). */
 int jb_batch_read_adpcm_all(jb_batch *b, uint8_t *const *dst);
+/* New (none: no reference counterpart).  Join (see "Join" below): the run also gathers the utterances' final PCM --
+ * what the PCM read entries hand out, after the output rate and the loudness target -- into programmes, on the
+ * device: each programme its members in ascending utterance index, each between its pads and under its fades.  FLAC,
+ * the sample format and IMA ADPCM then encode programmes instead of utterances: the index `utt` of
+ * jb_batch_flac_size / _read_flac, jb_batch_formatted_size / _read_formatted and jb_batch_adpcm_size /
+ * _adpcm_block_align / _read_adpcm is then a programme (jb_batch_num_outputs of them; one of that number or above:
+ * JB_ERR_INVALID), and their _all forms take jb_batch_num_outputs pointers.  n == jb_batch_size(b); req == NULL with
+ * n == 0 withdraws the request.  The members of one programme must agree on the output rate: this call and
+ * jb_batch_set_output_rate each check the combined request, and a call that would leave a programme mixed is refused
+ * with JB_ERR_INVALID (jb_last_error names the programme and the field) and changes nothing.  Only before the batch's
+ * first run, on a batch that is not JB_BATCH_MLPG_ONLY; an id of jb_batch_size or above (JB_JOIN_NONE apart) or a
+ * non-zero reserved word: JB_ERR_INVALID.  The per-utterance PCM entries, jb_batch_device_pcm and jb_gather_pcm keep
+ * handing out utterances.  Without a call nothing more runs, nothing is allocated and no output byte changes. */
+int jb_batch_set_join(jb_batch *b, const jb_join_utt *req, size_t n);
+/* New (none).  What the encoders' entries index: the programmes with a join request, else the utterances. */
+size_t jb_batch_num_outputs(const jb_batch *b);
+/* New (none).  The programme of utterance utt, numbered densely in the order of the programmes' first members (a
+ * JB_JOIN_NONE utterance counts as a programme of one); -1 without a join request or for no such utterance. */
+int32_t jb_batch_programme_of(const jb_batch *b, size_t utt);
+/* New (none).  Members, samples and rate of programme p, known from the geometry once the request is made (any out
+ * pointer may be NULL).  No request or no such programme: JB_ERR_INVALID. */
+int jb_batch_programme_layout(const jb_batch *b, size_t p, size_t *n_members, uint64_t *n_samples, uint32_t *hz);
+/* New (none).  The first sample of utterance utt within its programme, behind its pad_before: the cue list that maps
+ * sentences to times.  No request or no such utterance: JB_ERR_INVALID. */
+int jb_batch_member_start(const jb_batch *b, size_t utt, uint64_t *start_sample);
+/* New (none).  The PCM of programme p, f64 or 16-bit by the batch's flags as jb_batch_read_pcm / _i16; waits for the
+ * run like the read entries; cap below the programme's samples: JB_ERR_BUFFER. */
+int jb_batch_read_programme_pcm(jb_batch *b, size_t p, double *dst, size_t cap);
+int jb_batch_read_programme_pcm_i16(jb_batch *b, size_t p, int16_t *dst, size_t cap);
 void jb_batch_free(jb_batch *b);
 
 /* One-shot convenience: create + run + read + free.  pcm[i] must hold
@@ -748,6 +793,52 @@ int jb_adpcm_decode_host(const uint8_t *bytes, size_t n_bytes, uint32_t A, size_
 int jb_adpcm_encode_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
                               const jb_adpcm_opts *opts, int32_t device, uint8_t **out, size_t *n_bytes);
 void jb_adpcm_free(uint8_t *p);
+
+/* ---- Join (new: the reference synthesises one utterance into one buffer; none of these entries has a counterpart) ------
+ * A programme is "sentence, pause, sentence" as ONE stream: FLAC frame numbers, STREAMINFO, MD5 and SEEKTABLE, ADPCM
+ * blocks and the dither index then run over the whole, which the host cannot make from per-utterance outputs.
+ * - Numbering: programmes are numbered densely in the order of their first member; an utterance of JB_JOIN_NONE is a
+ *   programme of one and still gets its pads and fades.  Members stand in ascending utterance index.
+ * - Geometry: a programme's length is the sum over its members of pad_before + n + pad_after; a member starts at the
+ *   running sum plus its own pad_before.  All of it is known on the host once the request is made.
+ * - Fade weight: sample k < fade_in of a member is multiplied by s(t), t = (double)(2k + 1) / (double)(2 fade_in),
+ *   s = (t * t) * (3.0 - 2.0 * t) (a smoothstep, evaluated as written in f64 without contraction: bit-exact on the host
+ *   and the device); the fade-out the same with k' = n - 1 - k < fade_out.  Where both reach one sample (fade_in +
+ *   fade_out > n is allowed): x * s_in * s_out in that order.  From f64 the product stays f64; from 16 bits it is
+ *   truncated toward zero to int16 (the weights are in [0, 1]: no clamp).  Samples outside both fades are copied bit
+ *   for bit; pads are zeros.
+ * - Independence: a member's samples in the programme depend on its own samples and its two fade lengths alone, not on
+ *   the batch, the programme, its position or redo rounds; JB_BATCH_INVARIANT output stays invariant.
+ * - Loudness is measured on the members, in front of the pads; with jb_batch_set_loudness_groups over the same
+ *   members the programme has one gain.
+ * - Cost: not measured yet.
+ * Not covered: the generator, the _multi entries and jb_gather_pcm, the _each forms at engine level, overlapping members (a
+ * crossfade, i.e. negative pads), a caller-chosen member order, FLAC CUESHEET / VORBIS_COMMENT blocks and seek points
+ * at member starts, loudness measured over the joined programme, reading through the pinned ring. */
+/* New (none).  floor(ms * hz / 1000.0 + 0.5): a duration in samples at hz (0 for a negative or NaN duration). */
+uint64_t jb_join_ms_to_samples(double ms, uint32_t hz);
+/* New (none).  The geometry of a request over n members of n_in[u] samples at hz[u] (hz NULL: not compared):
+ * programme_of[u] and member_start[u] ([n] each), *n_programmes = P and programme_samples[p] ([n], the first P are
+ * written); any out pointer may be NULL.  A bad id, a non-zero reserved word or a programme of mixed rates:
+ * JB_ERR_INVALID. */
+int jb_join_geometry(const jb_join_utt *req, const size_t *n_in, const uint32_t *hz, size_t n, uint32_t *programme_of,
+                     uint64_t *member_start, size_t *n_programmes, uint64_t *programme_samples);
+/* New (none).  The rules in plain C++ on the host; no GPU is touched.  out[p] must hold programme p's samples
+ * (cap[p] below that: JB_ERR_BUFFER); p runs over the geometry's P programmes.  The same samples and request give the
+ * same programmes from the host, the seam and the batch. */
+int jb_join_host(const double *const *in, const size_t *n_in, size_t n, const jb_join_utt *req, double *const *out,
+                 const size_t *cap);
+int jb_join_i16_host(const int16_t *const *in, const size_t *n_in, size_t n, const jb_join_utt *req,
+                     int16_t *const *out, const size_t *cap);
+/* New (none).  The stage on PCM the caller holds (jb_format_pcm_batch's twin), on `device` (-1 = current): the members
+ * are packed one after the other on the device, as a batch's slab has them (member u starts n_in[0] + .. + n_in[u-1]
+ * samples into it), and joined there.  out and n_out have n entries; the first *n_programmes are written: out[p] =
+ * programme p, n_out[p] samples, library-owned (jb_join_free each). */
+int jb_join_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_join_utt *req, int32_t device,
+                      double **out, size_t *n_out, size_t *n_programmes);
+int jb_join_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n, const jb_join_utt *req,
+                          int32_t device, int16_t **out, size_t *n_out, size_t *n_programmes);
+void jb_join_free(void *p);
 
 /* ---- multi-GPU (SURVEY 8b "device_ids[] / n_devices", 8e) ----------------------------------
  * Utterances are independent, so a batch shards over the GPUs of a node with no data-path
@@ -1092,6 +1183,28 @@ long jb_generator_step(jb_generator *g, double *buf, size_t buf_len);
 long jb_generator_step_n(jb_generator *g, double *buf, size_t buf_len, size_t max_frames);
 void jb_generator_free(jb_generator *g);
 
+/* New (none: no reference counterpart).  The utterances of one call as ONE programme ("Join" above): the arguments of
+ * the jb_synthesize_batch* entry of the same sink plus the join options; one output (*pcm / *bytes, library-owned, freed
+ * as the batch entry's outputs are) instead of n_utts.  The engine's output rate, loudness target, ceiling, peak mode
+ * and scope hold as in the batch entries: with JB_LOUDNESS_PER_REQUEST the programme has one gain.  The _flac_meta and
+ * _adpcm forms join the 16-bit samples (what jb_synthesize_programme_i16 returns), the _formatted form the f64 ones.  starts (NULL or
+ * n_utts entries) receives each utterance's first sample within the programme.  n_utts == 0, a NULL join, a negative or
+ * non-finite duration or non-zero reserved words: JB_ERR_INVALID before any device is touched. */
+int jb_synthesize_programme(const jb_engine *e, const char *const *label_lines, const size_t *line_off, size_t n_utts,
+                            int32_t device, const jb_join_opts *join, double **pcm, size_t *n_samples, uint64_t *starts);
+int jb_synthesize_programme_i16(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                size_t n_utts, int32_t device, const jb_join_opts *join, int16_t **pcm,
+                                size_t *n_samples, uint64_t *starts);
+int jb_synthesize_programme_flac_meta(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                      size_t n_utts, int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta,
+                                      const jb_join_opts *join, uint8_t **flac, size_t *n_bytes, uint64_t *starts);
+int jb_synthesize_programme_formatted(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                      size_t n_utts, int32_t device, const jb_format_opts *opts,
+                                      const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, uint64_t *starts);
+int jb_synthesize_programme_adpcm(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_adpcm_opts *opts, const jb_join_opts *join,
+                                  uint8_t **bytes, size_t *n_bytes, size_t *n_samples, uint64_t *starts);
+
 /* ------------------------------------------------------------------------ */
 const char *jb_last_error(void);
 int jb_device_count(void);
@@ -1143,6 +1256,11 @@ JB_LAYOUT_ASSERT(sizeof(jb_flac_meta) == 16 && offsetof(jb_flac_meta, seek_inter
 JB_LAYOUT_ASSERT(sizeof(jb_format_opts) == 16 && offsetof(jb_format_opts, dither) == 4 &&
                      offsetof(jb_format_opts, seed) == 8, "jb_format_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_adpcm_opts) == 16 && offsetof(jb_adpcm_opts, reserved) == 4, "jb_adpcm_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_join_utt) == 32 && offsetof(jb_join_utt, fade_out) == 8 &&
+                     offsetof(jb_join_utt, pad_before) == 16 && offsetof(jb_join_utt, pad_after) == 24,
+                 "jb_join_utt");
+JB_LAYOUT_ASSERT(sizeof(jb_join_opts) == 40 && offsetof(jb_join_opts, fade_ms) == 24 &&
+                     offsetof(jb_join_opts, reserved) == 32, "jb_join_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_loudness_report) == 40 && offsetof(jb_loudness_report, gain_db) == 24 &&
                      offsetof(jb_loudness_report, peak_mode) == 32 && offsetof(jb_loudness_report, oversampling) == 36,
                  "jb_loudness_report");

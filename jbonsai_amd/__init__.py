@@ -9,7 +9,8 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    loudness_filter, resample, resample_filter, true_peak, true_peak_filter, write_wav,
                    format_pcm, format_pcm_host, write_wav_formatted, AdpcmStream, adpcm_decode_host, adpcm_encode,
                    adpcm_encode_host, adpcm_geometry, write_wav_adpcm, loudness_groups, loudness_gate_host,
-                   LOUDNESS_NO_GROUP, LOUDNESS_R128, LOUDNESS_PER_UTTERANCE, LOUDNESS_PER_REQUEST)
+                   LOUDNESS_NO_GROUP, LOUDNESS_R128, LOUDNESS_PER_UTTERANCE, LOUDNESS_PER_REQUEST,
+                   JOIN_NONE, JoinUtt, join_geometry, join_host, join_ms_to_samples, join_pcm)
 from .batch import (Batch, IndexStreamStates, IndexUtterance, PdfSet, StreamInfo, StreamStates, TrackUtterance,  # noqa: F401
                     Utterance, VoiceInfo, generator_from_tracks, mlpg_batch, paramgen_vocode_batch, vocode_tracks_batch,
                     vocoder_synthesize_batch)
@@ -26,4 +27,5 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "format_pcm", "format_pcm_host", "write_wav_formatted", "synthesize_batch_each_formatted",
            "AdpcmStream", "adpcm_decode_host", "adpcm_encode", "adpcm_encode_host", "adpcm_geometry", "write_wav_adpcm",
            "synthesize_batch_each_adpcm", "loudness_groups", "loudness_gate_host", "LOUDNESS_NO_GROUP", "LOUDNESS_R128", "LOUDNESS_PER_UTTERANCE",
-           "LOUDNESS_PER_REQUEST"]
+           "LOUDNESS_PER_REQUEST", "JOIN_NONE", "JoinUtt", "join_geometry", "join_host", "join_ms_to_samples",
+           "join_pcm"]

@@ -197,6 +197,44 @@ def adpcm_opts(block_align: int = 0):
     return o
 
 
+JOIN_NONE = 0xFFFFFFFF
+
+
+class JoinUtt(C.Structure):
+    """jb_join_utt: an utterance's programme, its edge fades and its pads of zero samples."""
+    _fields_ = [("programme", C.c_uint32), ("fade_in", C.c_uint32), ("fade_out", C.c_uint32), ("reserved", C.c_uint32),
+                ("pad_before", C.c_uint64), ("pad_after", C.c_uint64)]
+
+
+class JoinOpts(C.Structure):
+    """jb_join_opts: lead, gap, trail and fade of a jb_synthesize_programme* call, in milliseconds."""
+    _fields_ = [("lead_ms", C.c_double), ("gap_ms", C.c_double), ("trail_ms", C.c_double), ("fade_ms", C.c_double),
+                ("reserved", C.c_uint32 * 2)]
+
+
+def join_opts(lead_ms: float = 0.0, gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0):
+    o = JoinOpts()
+    o.lead_ms, o.gap_ms, o.trail_ms, o.fade_ms = float(lead_ms), float(gap_ms), float(trail_ms), float(fade_ms)
+    return o
+
+
+def join_request(req):
+    """A (JoinUtt * n) array of `req`: JoinUtt entries, or tuples / dicts of (programme, pad_before, pad_after,
+    fade_in, fade_out) with programme None for an utterance of its own and the rest 0 by default."""
+    arr = (JoinUtt * max(1, len(req)))()
+    for i, r in enumerate(req):
+        if isinstance(r, JoinUtt):
+            arr[i] = r
+            continue
+        if isinstance(r, dict):
+            r = (r.get("programme"), r.get("pad_before", 0), r.get("pad_after", 0), r.get("fade_in", 0),
+                 r.get("fade_out", 0))
+        r = tuple(r) + (0,) * (5 - len(r))
+        arr[i].programme = JOIN_NONE if r[0] is None else int(r[0])
+        arr[i].pad_before, arr[i].pad_after, arr[i].fade_in, arr[i].fade_out = (int(v) for v in r[1:5])
+    return arr
+
+
 class LoudnessReport(C.Structure):
     """jb_loudness_report: what a run measured and applied for one utterance."""
     _fields_ = [("lufs", C.c_double), ("sample_peak_dbfs", C.c_double), ("true_peak_dbtp", C.c_double),
@@ -285,6 +323,12 @@ SYMBOLS = [
     "jb_batch_set_loudness_groups", "jb_batch_loudness_group_of", "jb_batch_loudness_group",
     "jb_batch_set_loudness_report", "jb_batch_loudness_r128", "jb_loudness_groups_pcm_batch",
     "jb_loudness_gate_host", "jb_engine_set_loudness_scope", "jb_engine_get_loudness_scope",
+    "jb_batch_set_join", "jb_batch_num_outputs", "jb_batch_programme_of", "jb_batch_programme_layout",
+    "jb_batch_member_start", "jb_batch_read_programme_pcm", "jb_batch_read_programme_pcm_i16",
+    "jb_join_ms_to_samples", "jb_join_geometry", "jb_join_host", "jb_join_i16_host", "jb_join_pcm_batch",
+    "jb_join_pcm_batch_i16", "jb_join_free",
+    "jb_synthesize_programme", "jb_synthesize_programme_i16", "jb_synthesize_programme_flac_meta",
+    "jb_synthesize_programme_formatted", "jb_synthesize_programme_adpcm",
 ]
 
 
@@ -505,6 +549,35 @@ def lib():
                                             C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
     L.jb_synthesize_batch_each_adpcm.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
                                                  aop, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    jup, jop, u64p = C.POINTER(JoinUtt), C.POINTER(JoinOpts), C.POINTER(C.c_uint64)
+    L.jb_batch_set_join.argtypes = [vp, jup, sz]
+    L.jb_batch_num_outputs.argtypes = [vp]
+    L.jb_batch_num_outputs.restype = sz
+    L.jb_batch_programme_of.argtypes = [vp, sz]
+    L.jb_batch_programme_of.restype = C.c_int32
+    L.jb_batch_programme_layout.argtypes = [vp, sz, C.POINTER(sz), u64p, u32p]
+    L.jb_batch_member_start.argtypes = [vp, sz, u64p]
+    L.jb_batch_read_programme_pcm.argtypes = [vp, sz, vp, sz]
+    L.jb_batch_read_programme_pcm_i16.argtypes = [vp, sz, vp, sz]
+    L.jb_join_ms_to_samples.argtypes = [C.c_double, C.c_uint32]
+    L.jb_join_ms_to_samples.restype = C.c_uint64
+    L.jb_join_geometry.argtypes = [jup, C.POINTER(sz), u32p, sz, u32p, u64p, C.POINTER(sz), u64p]
+    L.jb_join_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, jup, C.POINTER(vp), C.POINTER(sz)]
+    L.jb_join_i16_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, jup, C.POINTER(vp), C.POINTER(sz)]
+    L.jb_join_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, jup, C.c_int32, C.POINTER(vp), C.POINTER(sz),
+                                    C.POINTER(sz)]
+    L.jb_join_pcm_batch_i16.argtypes = L.jb_join_pcm_batch.argtypes
+    L.jb_join_free.argtypes = [vp]
+    L.jb_join_free.restype = None
+    lines, szp = C.POINTER(C.c_char_p), C.POINTER(sz)
+    L.jb_synthesize_programme.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
+    L.jb_synthesize_programme_i16.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
+    L.jb_synthesize_programme_flac_meta.argtypes = [vp, lines, szp, sz, C.c_int32, C.POINTER(FlacOpts),
+                                                    C.POINTER(FlacMeta), jop, C.POINTER(u8p), szp, u64p]
+    L.jb_synthesize_programme_formatted.argtypes = [vp, lines, szp, sz, C.c_int32, mop, jop, C.POINTER(u8p), szp,
+                                                    u64p]
+    L.jb_synthesize_programme_adpcm.argtypes = [vp, lines, szp, sz, C.c_int32, aop, jop, C.POINTER(u8p), szp, szp,
+                                                u64p]
     L.jb_write_wav_i16.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     L.jb_write_wav_f64.argtypes = [C.c_char_p, vp, sz, C.c_uint32]
     _lib = L
@@ -856,6 +929,72 @@ def write_wav_adpcm(path, data: bytes, n_samples: int, sampling_frequency: int, 
     buf = C.create_string_buffer(bytes(data), max(1, len(data)))
     check(lib().jb_write_wav_adpcm(str(path).encode(), C.cast(buf, C.c_void_p), len(data), n_samples,
                                    sampling_frequency, block_align))
+
+
+def join_ms_to_samples(ms: float, hz: int) -> int:
+    """jb_join_ms_to_samples: floor(ms * hz / 1000.0 + 0.5)."""
+    return int(lib().jb_join_ms_to_samples(float(ms), int(hz)))
+
+
+def join_geometry(req, lengths, hz=None):
+    """jb_join_geometry: (programme_of [n], member_start [n], programme_samples [P]) of a request (join_request's
+    forms) over members of `lengths` samples; hz: one rate per member to compare, or None."""
+    n = len(lengths)
+    arr = join_request(req)
+    nin = (C.c_size_t * max(n, 1))(*[int(x) for x in lengths])
+    hzs = None if hz is None else (C.c_uint32 * max(n, 1))(*[int(h) for h in hz])
+    po, ms = (C.c_uint32 * max(n, 1))(), (C.c_uint64 * max(n, 1))()
+    P, ps = C.c_size_t(), (C.c_uint64 * max(n, 1))()
+    check(lib().jb_join_geometry(arr, nin, hzs, n, po, ms, C.byref(P), ps))
+    return list(po[:n]), list(ms[:n]), list(ps[:P.value])
+
+
+def _join_inputs(pcms):
+    import numpy as np
+
+    i16 = len(pcms) > 0 and all(np.asarray(a).dtype == np.int16 for a in pcms)
+    arrs = [np.ascontiguousarray(a, dtype=np.int16 if i16 else np.float64) for a in pcms]
+    n = len(arrs)
+    ins = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    return i16, arrs, n, ins, nin
+
+
+def join_host(pcms, req):
+    """jb_join_host / jb_join_i16_host (by the arrays' dtype): the programmes of the members `pcms` under the request
+    `req`, in plain C++ on the host (no GPU).  Every output buffer holds exactly its programme's samples."""
+    import numpy as np
+
+    i16, arrs, n, ins, nin = _join_inputs(pcms)
+    arr = join_request(req)
+    _, _, ps = join_geometry(arr[:n], [a.size for a in arrs])
+    outs = [np.empty(int(k), dtype=np.int16 if i16 else np.float64) for k in ps]
+    P = len(outs)
+    optr = (C.c_void_p * max(P, 1))(*[o.ctypes.data if o.size else None for o in outs])
+    caps = (C.c_size_t * max(P, 1))(*[o.size for o in outs])
+    L = lib()
+    check((L.jb_join_i16_host if i16 else L.jb_join_host)(ins, nin, n, arr, optr, caps))
+    return outs
+
+
+def join_pcm(pcms, req, device: int = -1):
+    """jb_join_pcm_batch / _i16 (by the arrays' dtype): the same programmes, joined on the GPU."""
+    import numpy as np
+
+    i16, arrs, n, ins, nin = _join_inputs(pcms)
+    arr = join_request(req)
+    outs, ns, P = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), C.c_size_t()
+    L = lib()
+    check((L.jb_join_pcm_batch_i16 if i16 else L.jb_join_pcm_batch)(ins, nin, n, arr, device, outs, ns, C.byref(P)))
+    res = []
+    ety = C.c_int16 if i16 else C.c_double
+    for p in range(P.value):
+        if ns[p]:
+            res.append(np.frombuffer((ety * ns[p]).from_address(outs[p]), dtype=np.int16 if i16 else np.float64).copy())
+        else:
+            res.append(np.zeros(0, dtype=np.int16 if i16 else np.float64))
+        L.jb_join_free(outs[p])
+    return res
 
 
 def resample(pcms, in_hz: int, out_hz: int, device: int = -1):

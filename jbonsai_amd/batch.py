@@ -446,8 +446,9 @@ class Batch:
         return bytes(buf[:n.value])
 
     def flac_all(self) -> List[bytes]:
-        """Every utterance's FLAC stream through one device-to-host copy (jb_batch_read_flac_all)."""
-        B = len(self)
+        """Every utterance's (with a join: every programme's) FLAC stream through one device-to-host copy
+        (jb_batch_read_flac_all)."""
+        B = self.num_outputs()
         ns = []
         for i in range(B):
             n = C.c_size_t()
@@ -475,8 +476,9 @@ class Batch:
         return buf[:n.value].tobytes()
 
     def formatted_all(self) -> List[bytes]:
-        """Every utterance's formatted bytes through one device-to-host copy (jb_batch_read_formatted_all)."""
-        B = len(self)
+        """Every utterance's (with a join: every programme's) formatted bytes through one device-to-host copy
+        (jb_batch_read_formatted_all)."""
+        B = self.num_outputs()
         ns = []
         for i in range(B):
             n = C.c_size_t()
@@ -513,13 +515,53 @@ class Batch:
         return buf[:n].tobytes()
 
     def read_adpcm_all(self) -> List[bytes]:
-        """Every utterance's blocks through one device-to-host copy (jb_batch_read_adpcm_all)."""
-        B = len(self)
+        """Every utterance's (with a join: every programme's) blocks through one device-to-host copy
+        (jb_batch_read_adpcm_all)."""
+        B = self.num_outputs()
         ns = [self.adpcm_size(i) for i in range(B)]
         bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
         arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
         F.check(self._L.jb_batch_read_adpcm_all(self._h, arr))
         return [b[:n].tobytes() for b, n in zip(bufs, ns)]
+
+    def set_join(self, req):
+        """jb_batch_set_join: one request per utterance -- F.JoinUtt entries, or (programme, pad_before, pad_after,
+        fade_in, fade_out) tuples with programme None for an utterance of its own, in samples at the output rate; None
+        withdraws the request.  The run then gathers the final PCM into programmes on the GPU, and flac(i),
+        formatted(i) and read_adpcm(i) (and their _all forms) index programmes.  Before the first run only."""
+        if req is None:
+            F.check(self._L.jb_batch_set_join(self._h, None, 0))
+            return
+        F.check(self._L.jb_batch_set_join(self._h, F.join_request(req), len(req)))
+
+    def num_outputs(self) -> int:
+        """What the encoders' entries index: the programmes with a join request, else the utterances."""
+        return self._L.jb_batch_num_outputs(self._h)
+
+    def programme_of(self, i) -> int:
+        """The programme of utterance i (numbered by first member), -1 without a join request."""
+        return int(self._L.jb_batch_programme_of(self._h, i))
+
+    def programme_layout(self, p):
+        """(members, samples, rate) of programme p (jb_batch_programme_layout)."""
+        m, n, hz = C.c_size_t(), C.c_uint64(), C.c_uint32()
+        F.check(self._L.jb_batch_programme_layout(self._h, p, C.byref(m), C.byref(n), C.byref(hz)))
+        return m.value, n.value, hz.value
+
+    def member_start(self, i) -> int:
+        """The first sample of utterance i within its programme (jb_batch_member_start): the cue list."""
+        k = C.c_uint64()
+        F.check(self._L.jb_batch_member_start(self._h, i, C.byref(k)))
+        return k.value
+
+    def programme_pcm(self, p) -> np.ndarray:
+        """The PCM of programme p: float64, or int16 on a pcm_i16 batch (jb_batch_read_programme_pcm / _i16)."""
+        i16 = bool(self.flags & F.BATCH_PCM_I16)
+        n = self.programme_layout(p)[1]
+        out = np.empty(n, dtype=np.int16 if i16 else np.float64)
+        fn = self._L.jb_batch_read_programme_pcm_i16 if i16 else self._L.jb_batch_read_programme_pcm
+        F.check(fn(self._h, p, out.ctypes.data, n))
+        return out
 
     def output_rate(self, i) -> int:
         """Rate of utterance i's PCM as the read entries hand it out (the voice's rate when native)."""

@@ -2633,7 +2633,7 @@ int jb_batch_set_flac_meta(jb_batch *hb, const jb_flac_meta *m)
 int jb_batch_flac_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 {
     Batch *b = (Batch *)hb;
-    if (!b || !n_bytes || utt >= (size_t)b->B)
+    if (!b || !n_bytes || utt >= b->out.num_outputs())
         return JB_ERR_INVALID;
     jb::FlacOut o{};
     int rc = b->out.read_flac_index(utt, &o);
@@ -2646,7 +2646,7 @@ int jb_batch_flac_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 int jb_batch_read_flac(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
 {
     Batch *b = (Batch *)hb;
-    if (!b || utt >= (size_t)b->B)
+    if (!b || utt >= b->out.num_outputs())
         return JB_ERR_INVALID;
     jb::FlacOut o{};
     int rc = b->out.read_flac_index(utt, &o);
@@ -2669,10 +2669,10 @@ int jb_batch_read_flac_all(jb_batch *hb, uint8_t *const *dst)
     int rc = b->out.read_flac_all(&res, &host);
     if (rc)
         return rc;
-    for (size_t u = 0; u < (size_t)b->B; u++)
+    for (size_t u = 0; u < res.size(); u++)
         if (!dst[u] && res[u].bytes)
             return JB_ERR_INVALID;
-    for (size_t u = 0; u < (size_t)b->B; u++)
+    for (size_t u = 0; u < res.size(); u++)
         memcpy(dst[u], host.get() + res[u].off, (size_t)res[u].bytes);
     return JB_OK;
 }
@@ -2687,7 +2687,7 @@ int jb_batch_set_format(jb_batch *hb, const jb_format_opts *opts)
 int jb_batch_formatted_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 {
     Batch *b = (Batch *)hb;
-    if (!b || !n_bytes || utt >= (size_t)b->B)
+    if (!b || !n_bytes || utt >= b->out.num_outputs())
         return JB_ERR_INVALID;
     return b->out.format_size(utt, n_bytes);
 }
@@ -2695,7 +2695,7 @@ int jb_batch_formatted_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 int jb_batch_read_formatted(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
 {
     Batch *b = (Batch *)hb;
-    if (!b || utt >= (size_t)b->B)
+    if (!b || utt >= b->out.num_outputs())
         return JB_ERR_INVALID;
     size_t nb = 0;
     int rc = b->out.format_size(utt, &nb);
@@ -2719,10 +2719,10 @@ int jb_batch_read_formatted_all(jb_batch *hb, uint8_t *const *dst)
     int rc = b->out.read_formatted_all(&host);
     if (rc)
         return rc;
-    for (size_t u = 0; u < (size_t)b->B; u++)
+    for (size_t u = 0; u < b->out.num_outputs(); u++)
         if (!dst[u] && b->out.format_place(u).bytes)
             return JB_ERR_INVALID;
-    for (size_t u = 0; u < (size_t)b->B; u++) {
+    for (size_t u = 0; u < b->out.num_outputs(); u++) {
         const jb::OutFmtUtt &w = b->out.format_place(u);
         if (w.bytes)
             memcpy(dst[u], host.get() + w.off, (size_t)w.bytes);
@@ -2740,7 +2740,7 @@ int jb_batch_set_adpcm(jb_batch *hb, const jb_adpcm_opts *opts)
 int jb_batch_adpcm_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 {
     Batch *b = (Batch *)hb;
-    if (!b || !n_bytes || utt >= (size_t)b->B)
+    if (!b || !n_bytes || utt >= b->out.num_outputs())
         return JB_ERR_INVALID;
     const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
     if (!w)
@@ -2752,7 +2752,7 @@ int jb_batch_adpcm_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 int jb_batch_adpcm_block_align(jb_batch *hb, size_t utt, uint32_t *block_align)
 {
     Batch *b = (Batch *)hb;
-    if (!b || !block_align || utt >= (size_t)b->B)
+    if (!b || !block_align || utt >= b->out.num_outputs())
         return JB_ERR_INVALID;
     const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
     if (!w)
@@ -2764,7 +2764,7 @@ int jb_batch_adpcm_block_align(jb_batch *hb, size_t utt, uint32_t *block_align)
 int jb_batch_read_adpcm(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
 {
     Batch *b = (Batch *)hb;
-    if (!b || utt >= (size_t)b->B)
+    if (!b || utt >= b->out.num_outputs())
         return JB_ERR_INVALID;
     const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
     if (!w)
@@ -2787,15 +2787,91 @@ int jb_batch_read_adpcm_all(jb_batch *hb, uint8_t *const *dst)
     int rc = b->out.read_adpcm_all(&host);
     if (rc)
         return rc;
-    for (size_t u = 0; u < (size_t)b->B; u++)
+    for (size_t u = 0; u < b->out.num_outputs(); u++)
         if (!dst[u] && b->out.adpcm_place(u)->bytes)
             return JB_ERR_INVALID;
-    for (size_t u = 0; u < (size_t)b->B; u++) {
+    for (size_t u = 0; u < b->out.num_outputs(); u++) {
         const jb::OutAdpcmUtt *w = b->out.adpcm_place(u);
         if (w->bytes)
             memcpy(dst[u], host.get() + w->off, (size_t)w->bytes);
     }
     return JB_OK;
+}
+
+int jb_batch_set_join(jb_batch *hb, const jb_join_utt *req, size_t n)
+{
+    return hb ? ((Batch *)hb)->out.set_join(req, n) : JB_ERR_INVALID;
+}
+
+size_t jb_batch_num_outputs(const jb_batch *hb) { return hb ? ((const Batch *)hb)->out.num_outputs() : 0; }
+
+int32_t jb_batch_programme_of(const jb_batch *hb, size_t utt)
+{
+    const Batch *b = (const Batch *)hb;
+    return (b && utt < (size_t)b->B) ? b->out.programme_of(utt) : -1;
+}
+
+int jb_batch_programme_layout(const jb_batch *hb, size_t p, size_t *n_members, uint64_t *n_samples, uint32_t *hz)
+{
+    const Batch *b = (const Batch *)hb;
+    if (!b)
+        return JB_ERR_INVALID;
+    if (!b->out.joined() || p >= b->out.num_outputs()) {
+        jb::set_error(b->out.joined() ? "jb_batch_programme_layout: no such programme"
+                                      : "join: jb_batch_set_join was not called");
+        return JB_ERR_INVALID;
+    }
+    if (n_members)
+        *n_members = b->out.programme_members(p);
+    if (n_samples)
+        *n_samples = b->out.programme(p).n;
+    if (hz)
+        *hz = b->out.programme(p).hz;
+    return JB_OK;
+}
+
+int jb_batch_member_start(const jb_batch *hb, size_t utt, uint64_t *start_sample)
+{
+    const Batch *b = (const Batch *)hb;
+    if (!b || !start_sample)
+        return JB_ERR_INVALID;
+    if (!b->out.joined() || utt >= (size_t)b->B) {
+        jb::set_error(b->out.joined() ? "jb_batch_member_start: no such utterance"
+                                      : "join: jb_batch_set_join was not called");
+        return JB_ERR_INVALID;
+    }
+    *start_sample = b->out.member_start(utt);
+    return JB_OK;
+}
+
+static int read_programme(jb_batch *hb, size_t p, void *dst, size_t cap, bool i16)
+{
+    Batch *b = (Batch *)hb;
+    if (!b)
+        return JB_ERR_INVALID;
+    if (!b->out.joined() || p >= b->out.num_outputs()) {
+        jb::set_error(b->out.joined() ? "jb_batch_read_programme_pcm: no such programme"
+                                      : "join: jb_batch_set_join was not called");
+        return JB_ERR_INVALID;
+    }
+    const size_t ns = (size_t)b->out.programme(p).n;
+    if (cap < ns) {
+        jb::set_error("pcm buffer too small");
+        return JB_ERR_BUFFER;
+    }
+    if (!dst && ns)
+        return JB_ERR_INVALID;
+    return b->out.read_programme(p, i16, dst);
+}
+
+int jb_batch_read_programme_pcm(jb_batch *hb, size_t p, double *dst, size_t cap)
+{
+    return read_programme(hb, p, dst, cap, false);
+}
+
+int jb_batch_read_programme_pcm_i16(jb_batch *hb, size_t p, int16_t *dst, size_t cap)
+{
+    return read_programme(hb, p, dst, cap, true);
 }
 
 int jb_batch_read_pcm_native(jb_batch *hb, size_t i, double *dst, size_t cap)

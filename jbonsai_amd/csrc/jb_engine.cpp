@@ -1401,12 +1401,14 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
                               int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads,
                               const jb_engine *const *each, bool flac, const jb_flac_opts *flac_opts,
                               const jb_format_opts *fmt_opts, const jb_adpcm_opts *adpcm_opts, size_t *adpcm_samples,
-                              const jb_flac_meta *flac_meta)
+                              const jb_flac_meta *flac_meta, const jb_join_opts *join, uint64_t *join_starts)
 {
     auto eng = [&](size_t u) { return CENG(each ? each[u] : e); }; // the engine of utterance u
     if (!e || !pcm || !n_samples || (n_utts && !line_off))
         return JB_ERR_INVALID;
-    for (size_t u = 0; u < n_utts; u++) {
+    // with a join the call hands out ONE output, the programme of all its utterances
+    const size_t n_outs = join ? 1 : n_utts;
+    for (size_t u = 0; u < n_outs; u++) {
         pcm[u] = nullptr;
         n_samples[u] = 0;
     }
@@ -1460,7 +1462,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
     // per-request loudness scope: the request is one loudness group, and a group lives in one batch
     const bool one_gain = CENG(e)->cond.loudness_scope == JB_LOUDNESS_PER_REQUEST &&
                           !std::isnan(CENG(e)->cond.loudness_target);
-    if (one_gain)
+    if (one_gain || join) // (a programme lives in one batch too)
         ngroups = 1;
     ngroups = std::max<size_t>(1, std::min(ngroups, n_utts));
     std::vector<size_t> glo(ngroups + 1, n_utts);
@@ -1604,6 +1606,23 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             return rc;
         if (adpcm_opts && (rc = b->out.set_adpcm(adpcm_opts)))
             return rc;
+        if (join) {
+            // one programme: the lead in front of the first member, the gap behind every member but the last, the
+            // trail behind the last, the fade at both edges of each, in samples at the output rate
+            const uint32_t hz = b->out.utt(0).hz;
+            std::vector<jb_join_utt> req(hi - lo, jb_join_utt{});
+            for (size_t u = 0; u < req.size(); u++) {
+                req[u].programme = 0;
+                req[u].fade_in = req[u].fade_out = (uint32_t)std::min<uint64_t>(jb::join_ms_to_samples(join->fade_ms, hz),
+                                                                               0xffffffffu);
+                req[u].pad_before = u == 0 ? jb::join_ms_to_samples(join->lead_ms, hz) : 0;
+                req[u].pad_after = jb::join_ms_to_samples(u + 1 == req.size() ? join->trail_ms : join->gap_ms, hz);
+            }
+            if ((rc = b->out.set_join(req.data(), req.size())))
+                return rc;
+            for (size_t u = 0; join_starts && u < req.size(); u++)
+                join_starts[lo + u] = b->out.member_start(u);
+        }
         rc = b->run(false);
         t_create += ms(t0, now());
         return rc;
@@ -1625,7 +1644,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             std::unique_ptr<uint8_t[]> host;
             if ((rc = b->out.read_flac_all(&res, &host)))
                 return rc;
-            for (size_t u = lo; u < hi; u++) {
+            for (size_t u = lo; u < lo + b->out.num_outputs(); u++) {
                 const jb::FlacOut &o = res[u - lo];
                 if (!(pcm[u] = malloc(std::max<size_t>((size_t)o.bytes, 1)))) {
                     jb::set_error("out of host memory");
@@ -1643,7 +1662,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             std::unique_ptr<uint8_t[]> host;
             if ((rc = b->out.read_formatted_all(&host)))
                 return rc;
-            for (size_t u = lo; u < hi; u++) {
+            for (size_t u = lo; u < lo + b->out.num_outputs(); u++) {
                 const jb::OutFmtUtt &w = b->out.format_place(u - lo);
                 if (!(pcm[u] = malloc(std::max<size_t>((size_t)w.bytes, 1)))) {
                     jb::set_error("out of host memory");
@@ -1661,7 +1680,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             std::unique_ptr<uint8_t[]> host;
             if ((rc = b->out.read_adpcm_all(&host)))
                 return rc;
-            for (size_t u = lo; u < hi; u++) {
+            for (size_t u = lo; u < lo + b->out.num_outputs(); u++) {
                 const jb::OutAdpcmUtt &w = *b->out.adpcm_place(u - lo);
                 if (!(pcm[u] = malloc(std::max<size_t>((size_t)w.bytes, 1)))) {
                     jb::set_error("out of host memory");
@@ -1670,11 +1689,24 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
                 memcpy(pcm[u], host.get() + w.off, (size_t)w.bytes);
                 n_samples[u] = (size_t)w.bytes;
                 if (adpcm_samples)
-                    adpcm_samples[u] = b->out.samples(u - lo);
+                    adpcm_samples[u] = join ? (size_t)b->out.programme(u - lo).n : b->out.samples(u - lo);
             }
             batches[g].reset();
             t_d2h += ms(t0, now());
             return JB_OK;
+        }
+        if (join) {
+            // the programme's PCM in one copy
+            const size_t ns = (size_t)b->out.programme(0).n;
+            if (!(pcm[0] = malloc(std::max<size_t>(ns, 1) * elem))) {
+                jb::set_error("out of host memory");
+                return JB_ERR_INVALID;
+            }
+            n_samples[0] = ns;
+            rc = b->out.read_programme(0, elem == 2, pcm[0]);
+            batches[g].reset();
+            t_d2h += ms(t0, now());
+            return rc;
         }
         for (size_t u = lo; u < hi; u++) {
             const size_t ns = b->out.samples(u - lo);
@@ -1767,7 +1799,7 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
     }
     if (rc) {
         batches.clear();
-        for (size_t u = 0; u < n_utts; u++) {
+        for (size_t u = 0; u < n_outs; u++) {
             free(pcm[u]);
             pcm[u] = nullptr;
             n_samples[u] = 0;
@@ -2005,6 +2037,84 @@ int jb_synthesize_adpcm(const jb_engine *e, const char *const *lines, size_t n, 
         return JB_ERR_INVALID;
     size_t off[2] = {0, n};
     return jb_synthesize_batch_adpcm(e, lines, off, 1, -1, opts, bytes, n_bytes, n_samples);
+}
+
+// jb_synthesize_programme*: the options checked before any device is touched
+static int check_join_entry(const jb_join_opts *j, size_t n_utts, const char *who)
+{
+    if (!j) {
+        jb::set_error(std::string(who) + ": join is NULL");
+        return JB_ERR_INVALID;
+    }
+    for (double ms : {j->lead_ms, j->gap_ms, j->trail_ms, j->fade_ms})
+        if (!(ms >= 0.0) || !std::isfinite(ms)) {
+            jb::set_error(std::string(who) + ": lead_ms, gap_ms, trail_ms and fade_ms are finite and not negative");
+            return JB_ERR_INVALID;
+        }
+    if (j->reserved[0] || j->reserved[1]) {
+        jb::set_error(std::string(who) + ": reserved must be 0");
+        return JB_ERR_INVALID;
+    }
+    if (n_utts == 0) {
+        jb::set_error(std::string(who) + ": a programme has at least one utterance");
+        return JB_ERR_INVALID;
+    }
+    return JB_OK;
+}
+
+int jb_synthesize_programme(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                            int32_t device, const jb_join_opts *join, double **pcm, size_t *n_samples, uint64_t *starts)
+{
+    int rc = check_join_entry(join, n_utts, "jb_synthesize_programme");
+    if (rc)
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(double), (void **)pcm, n_samples, 0,
+                                     nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr, join, starts);
+}
+
+int jb_synthesize_programme_i16(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                int32_t device, const jb_join_opts *join, int16_t **pcm, size_t *n_samples,
+                                uint64_t *starts)
+{
+    int rc = check_join_entry(join, n_utts, "jb_synthesize_programme_i16");
+    if (rc)
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)pcm, n_samples, 0,
+                                     nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr, join, starts);
+}
+
+int jb_synthesize_programme_flac_meta(const jb_engine *e, const char *const *lines, const size_t *line_off,
+                                      size_t n_utts, int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta,
+                                      const jb_join_opts *join, uint8_t **flac, size_t *n_bytes, uint64_t *starts)
+{
+    int rc = jb::flac_check_opts(opts, nullptr);
+    if (rc || (rc = jb::flac_check_meta(meta, nullptr)) ||
+        (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_flac_meta")))
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, 0,
+                                     nullptr, true, opts, nullptr, nullptr, nullptr, meta, join, starts);
+}
+
+int jb_synthesize_programme_formatted(const jb_engine *e, const char *const *lines, const size_t *line_off,
+                                      size_t n_utts, int32_t device, const jb_format_opts *opts,
+                                      const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, uint64_t *starts)
+{
+    int rc = check_format_entry(opts, "jb_synthesize_programme_formatted");
+    if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_formatted")))
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(double), (void **)bytes, n_bytes, 0,
+                                     nullptr, false, nullptr, opts, nullptr, nullptr, nullptr, join, starts);
+}
+
+int jb_synthesize_programme_adpcm(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                  int32_t device, const jb_adpcm_opts *opts, const jb_join_opts *join, uint8_t **bytes,
+                                  size_t *n_bytes, size_t *n_samples, uint64_t *starts)
+{
+    int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_programme_adpcm");
+    if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_adpcm")))
+        return rc;
+    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)bytes, n_bytes, 0,
+                                     nullptr, false, nullptr, nullptr, opts, n_samples, nullptr, join, starts);
 }
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)

@@ -39,13 +39,15 @@ void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE
 // and its byte count instead (jb_synthesize*_flac); fmt_opts (elem 8): its bytes in that sample format and their
 // count (jb_synthesize*_formatted); adpcm_opts (elem 2): its IMA ADPCM blocks and their byte count, the samples they
 // encode in adpcm_samples[u] where that is not null (jb_synthesize*_adpcm); flac_meta: the streams' MD5 / SEEKTABLE
-// request (jb_synthesize*_flac_meta; null: none)
+// request (jb_synthesize*_flac_meta; null: none); join (jb_synthesize_programme*): all utterances are one programme
+// and pcm[0] / n_samples[0] alone receive it, join_starts[u] (may be null) each member's first sample
 int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                           int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0,
                           const jb_engine *const *each = nullptr, bool flac = false,
                           const jb_flac_opts *flac_opts = nullptr, const jb_format_opts *fmt_opts = nullptr,
                           const jb_adpcm_opts *adpcm_opts = nullptr, size_t *adpcm_samples = nullptr,
-                          const jb_flac_meta *flac_meta = nullptr);
+                          const jb_flac_meta *flac_meta = nullptr, const jb_join_opts *join = nullptr,
+                          uint64_t *join_starts = nullptr);
 // A stream / a device block from the per-device pools that batches draw from (jb_batch.cpp), for work outside a
 // batch; *got is the block's pooled size, which pooled_block_free takes back
 hipError_t pooled_stream_acquire(int device, hipStream_t *st);
@@ -258,6 +260,18 @@ hipError_t launch_format(uint32_t format, uint32_t dither, uint64_t seed, const 
 // x f64 or 16-bit samples by i16
 hipError_t launch_adpcm(bool i16, const AdpcmUtt *utts_dev, uint32_t n, uint64_t groups, hipStream_t stream);
 
+// The join stage (jb_join.hip; the rules, JoinMember and JoinSpan: jb_join.h; the layout: jb_output.h)
+// join_layout with the request's reserved words checked and set_error naming what is wrong (JB_ERR_INVALID)
+int join_layout_checked(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
+                        JoinLayout *out, const char *who);
+// The lists of a run: members[i] for the layout's members[i] (utterance u's samples at x + xoff[u] elements), one
+// span per programme (programme p at y + units[p].off elements)
+void join_lists(const JoinLayout &lay, const JoinUtt *req, const uint64_t *n, const uint64_t *xoff, const void *x,
+                void *y, size_t elem, std::vector<JoinMember> *members, std::vector<JoinSpan> *spans);
+// spans_dev[0..n) of `tiles` tiles in all, their samples f64 or 16-bit by i16
+hipError_t launch_join(bool i16, const JoinSpan *spans_dev, uint32_t n, uint64_t tiles, const JoinMember *members_dev,
+                       hipStream_t stream);
+
 // Device-resident pdf tables of a voice set (jb_pdf_set) and an indexed batch source
 struct PdfSet {
     int device = -1;
@@ -341,6 +355,9 @@ struct OutputChain {
     int set_flac_meta(const jb_flac_meta *meta); // behind set_flac
     int set_format(const jb_format_opts *opts); // an f64 batch only
     int set_adpcm(const jb_adpcm_opts *opts);   // an f64 or a 16-bit batch
+    // req[u]: utterance u's programme, pads and fades, n == B (nullptr, 0: the request is withdrawn); this setter and
+    // set_output_rate check that a programme's members agree on the rate
+    int set_join(const jb_join_utt *req, size_t n);
     void init();   // Batch::create: the slabs the batch was made with, the plan of no request
     int prepare(); // at the first run: every slab, table and list of the plan; points the vocoder at its slab
     // only: [B] 1 = the utterances a redo rewrote: their part of every stage again (the FLAC pack: every stream),
@@ -382,6 +399,15 @@ struct OutputChain {
     const OutAdpcmUtt *adpcm_place(size_t u) const;
     int read_adpcm(size_t u, uint8_t *dst);
     int read_adpcm_all(std::unique_ptr<uint8_t[]> *host);
+    // the join: what the encoders' entries index (the programmes, or the utterances without a request), an
+    // utterance's programme (-1 without a request) and start, a programme's place, members and PCM
+    bool joined() const { return plan.join.slab != OutSlab::None; }
+    size_t num_outputs() const { return joined() ? plan.units.size() : plan.utt.size(); }
+    int32_t programme_of(size_t u) const { return joined() ? (int32_t)plan.prog_of[u] : -1; }
+    uint64_t member_start(size_t u) const { return plan.prog_start[u]; }
+    const OutUnit &programme(size_t p) const { return plan.units[p]; }
+    size_t programme_members(size_t p) const { return plan.prog_first[p + 1] - plan.prog_first[p]; }
+    int read_programme(size_t p, bool i16, void *dst);
 
 private:
     Batch &b;
@@ -392,6 +418,7 @@ private:
     jb_format_opts fmt_p{};
     bool ad_on = false;                        // IMA ADPCM is requested
     uint32_t ad_align = 0;                     // its block_align (0: by the rate)
+    std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
     std::vector<double> ln_target, ln_ceiling; // [B]
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
     std::vector<uint32_t> ln_group_req;        // [B] the caller's ids; empty: no group request
@@ -447,6 +474,22 @@ private:
         AdpcmUtt *utts_dev = nullptr, *redo_dev = nullptr;
         uint64_t groups = 0;
     } ad;
+    struct { // join
+        std::vector<JoinMember> members; // in programme order: programme p owns [prog_first[p], prog_first[p + 1])
+        std::vector<uint32_t> member_at; // [B] utterance -> its place in `members`
+        std::vector<JoinSpan> spans;     // [P] every programme whole
+        JoinMember *members_dev = nullptr;
+        JoinSpan *spans_dev = nullptr, *redo_dev = nullptr;
+        uint64_t tiles = 0;
+    } jn;
+    // the units the encoders take: the programmes in the join slab, or the utterances in the slab `utt_slab`
+    struct EncUnit {
+        uint64_t off, n;
+        uint32_t hz;
+    };
+    std::vector<EncUnit> enc_units() const;
+    int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
+    int prepare_join();
     void replan(); // host geometry and routing of the present requests
     // the group request `group` ([B], empty: none) against these targets, modes and rates: JB_ERR_INVALID naming the
     // group and the field where members would disagree; *out (may be null) gets the plan

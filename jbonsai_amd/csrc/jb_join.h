@@ -1,0 +1,129 @@
+#pragma once
+// jb_join.h -- the join stage (include/jbonsai_amd.h "Join"): a programme's PCM is its members one after the other, each
+// between its own pads of zero samples and under its own edge fades.  The rules of one sample and of the geometry,
+// stated once for the kernel (jb_join.hip), for the host seam (jb_join.cpp) and for the output plan (jb_output.cpp),
+// and the stage's work lists.
+// Plain C++17 and header-only; under hipcc the rules compile for the host and the device alike.
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __HIPCC__
+// (spelt without the HIP runtime header: jb_output.cpp includes this file without it)
+#define JB_JOIN_HD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
+#else
+#define JB_JOIN_HD inline
+#endif
+
+namespace jb {
+
+// jb_join_utt of the public header, restated (this header stands without it; jb_join.cpp asserts the two agree)
+struct JoinUtt {
+    uint32_t programme;         // a caller's id below B, or kJoinNone
+    uint32_t fade_in, fade_out; // samples at the output rate
+    uint32_t reserved;
+    uint64_t pad_before, pad_after;
+};
+static_assert(sizeof(JoinUtt) == 32 && offsetof(JoinUtt, pad_before) == 16, "jb_join_utt is 32 bytes");
+constexpr uint32_t kJoinNone = 0xffffffffu; // JB_JOIN_NONE: the utterance is a programme of its own
+
+constexpr uint32_t kJoinLanes = 256;
+constexpr uint32_t kJoinTileBytes = 16384; // destination bytes per workgroup: four 16-byte groups per lane
+constexpr uint32_t kJoinGroupBytes = 16;   // what one store writes; programmes start on such a boundary in their slab
+
+// One member of a join launch, in the order of its programme
+struct JoinMember {
+    const void *x;  // its final PCM: f64 or 16-bit samples (by the launch)
+    uint64_t start; // its first sample within the programme (behind its pad_before)
+    uint64_t n;
+    uint32_t fade_in, fade_out;
+};
+
+// One span of a join launch: samples [k0, k1) of one programme, k0 a multiple of a group's samples, k1 one too or the
+// programme's end.  A run lists every programme whole; a redo the spans of the members that changed.  t0 is the
+// prefix sum of the list's tiles (tiles never cross spans); the programme owns members[m0 .. m0 + nm), nm >= 1
+struct JoinSpan {
+    void *y;    // the programme's first sample in the join slab, 16-byte aligned
+    uint64_t n; // the programme's samples
+    uint64_t k0, k1, t0;
+    uint32_t m0, nm;
+};
+
+// tiles of a span [k0, k1) of 16-bit or f64 samples
+constexpr uint64_t join_tiles(uint64_t k0, uint64_t k1, bool i16)
+{
+    return k1 > k0 ? (k1 - k0 + kJoinTileBytes / (i16 ? 2 : 8) - 1) / (kJoinTileBytes / (i16 ? 2 : 8)) : 0;
+}
+
+// floor(ms hz / 1000 + 0.5); 0 for a negative or NaN duration
+JB_JOIN_HD uint64_t join_ms_to_samples(double ms, uint32_t hz)
+{
+    const double v = ms * (double)hz / 1000.0 + 0.5;
+    return v >= 1.0 ? (uint64_t)v : 0; // (the conversion truncates: the floor of a positive value)
+}
+
+// The smoothstep weight of sample k < fade of a fade of `fade` samples, counted from the edge: evaluated as written,
+// without contraction (the library is built with -ffp-contract=off), so that the host and the device agree bit for bit
+JB_JOIN_HD double join_fade(uint64_t k, uint32_t fade)
+{
+    const double t = (double)(2 * k + 1) / (double)(2 * (uint64_t)fade);
+    return (t * t) * (3.0 - 2.0 * t);
+}
+
+// samples [ka, kb] of a member of n samples lie outside both fades: they are copied
+JB_JOIN_HD bool join_plain(uint64_t ka, uint64_t kb, uint64_t n, uint32_t fade_in, uint32_t fade_out)
+{
+    return ka >= fade_in && n - 1 - kb >= fade_out;
+}
+
+// Sample k of a member of n samples: x * s_in * s_out in that order, each factor only where its fade reaches; a sample
+// outside both is returned as it came.  From f64 the product stays f64
+JB_JOIN_HD double join_sample(double x, uint64_t k, uint64_t n, uint32_t fade_in, uint32_t fade_out)
+{
+    if (k < fade_in)
+        x = x * join_fade(k, fade_in);
+    const uint64_t kr = n - 1 - k;
+    if (kr < fade_out)
+        x = x * join_fade(kr, fade_out);
+    return x;
+}
+
+// From 16 bits the product is truncated toward zero (the weights are in [0, 1]: no clamp)
+JB_JOIN_HD int16_t join_sample(int16_t x, uint64_t k, uint64_t n, uint32_t fade_in, uint32_t fade_out)
+{
+    if (join_plain(k, k, n, fade_in, fade_out))
+        return x;
+    return (int16_t)(int32_t)join_sample((double)x, k, n, fade_in, fade_out);
+}
+
+// The member that holds sample k of a programme, among members[0 .. nm) ascending by start: the last one with
+// start <= k searched in [lo, hi], or -1 where k lies in front of the first.  *inside: k is one of its samples (else
+// k lies in a pad)
+JB_JOIN_HD int32_t join_find(const JoinMember *members, int32_t lo, int32_t hi, uint64_t k, bool *inside)
+{
+    if (members[lo].start > k) {
+        *inside = false;
+        return lo - 1;
+    }
+    while (hi > lo) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (members[mid].start <= k)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    *inside = k - members[lo].start < members[lo].n;
+    return lo;
+}
+
+// Sample k of a programme by the rules above: a member's sample, or the zero of a pad
+template <class T> JB_JOIN_HD T join_value(const JoinMember *members, int32_t lo, int32_t hi, uint64_t k)
+{
+    bool inside;
+    const int32_t j = join_find(members, lo, hi, k, &inside);
+    if (!inside)
+        return (T)0;
+    const JoinMember m = members[j];
+    return join_sample(((const T *)m.x)[k - m.start], k - m.start, m.n, m.fade_in, m.fade_out);
+}
+
+} // namespace jb

@@ -61,30 +61,109 @@ OutPlan plan_output(const OutPlanIn &in)
     for (const OutWrite &w : {p.vocoder, p.converter, p.apply})
         if (w.slab != OutSlab::None && w.slab != OutSlab::V64 && w.slab != OutSlab::S16)
             p.alloc[(size_t)w.slab] = std::max<uint64_t>(w.slab == OutSlab::Voc64 ? p.native_total : p.total, 1);
-    // the format stage behind all of them: the final f64 to bytes, utterance after utterance on 16-byte boundaries
+    // the join behind all of them: the final PCM gathered into programmes in a slab of its own, which the encoders
+    // then read; their units are the programmes (a request the chain has checked; one that does not lay out: no join)
+    std::vector<OutUnit> units;
+    OutWrite enc = p.final; // what the encoders read
+    if (in.join) {
+        std::vector<uint64_t> n(in.B);
+        for (size_t u = 0; u < in.B; u++)
+            n[u] = p.utt[u].n;
+        JoinLayout lay;
+        if (join_layout(in.join, n.data(), nullptr, in.B, p.final.i16 ? 2 : 8, &lay, nullptr, nullptr)) {
+            p.join_src = p.final;
+            p.join = {p.final.i16 ? OutSlab::Join16 : OutSlab::Join64, p.final.i16};
+            for (size_t g = 0; g < lay.units.size(); g++)
+                lay.units[g].hz = p.utt[lay.progs.members[lay.progs.first[g]]].hz;
+            p.units = lay.units;
+            p.prog_of = std::move(lay.progs.group_of);
+            p.prog_first = std::move(lay.progs.first);
+            p.prog_members = std::move(lay.progs.members);
+            p.prog_start = std::move(lay.start);
+            p.alloc[(size_t)p.join.slab] = std::max<uint64_t>(lay.total, 1);
+            enc = p.join;
+            if (p.flac != OutSlab::None)
+                p.flac = p.join.slab;
+        }
+    }
+    const bool joined = p.join.slab != OutSlab::None;
+    if (joined)
+        units = p.units;
+    else
+        for (size_t u = 0; u < in.B; u++)
+            units.push_back({p.utt[u].hz, p.utt[u].n, p.utt[u].off});
+    // the format stage behind all of them: the final f64 to bytes, unit after unit (an utterance; with a join a
+    // programme) on 16-byte boundaries
     if (in.fmt_bytes && !p.final.i16) {
-        p.fmt_src = p.final.slab;
-        p.fmt.resize(in.B);
+        p.fmt_src = enc.slab;
+        p.fmt.resize(units.size());
         uint64_t bytes = 0;
-        for (size_t u = 0; u < in.B; u++) {
-            p.fmt[u] = {bytes, p.utt[u].n * in.fmt_bytes};
+        for (size_t u = 0; u < units.size(); u++) {
+            p.fmt[u] = {bytes, units[u].n * in.fmt_bytes};
             bytes += (p.fmt[u].bytes + 15) & ~(uint64_t)15;
         }
         p.alloc[(size_t)OutSlab::Fmt] = std::max<uint64_t>(bytes, 16);
     }
-    // IMA ADPCM beside it: the final PCM, f64 or 16-bit, to blocks of each utterance's own size
+    // IMA ADPCM beside it: the final PCM, f64 or 16-bit, to blocks of each unit's own size
     if (in.adpcm) {
-        p.adpcm_src = p.final;
-        p.adpcm.resize(in.B);
+        p.adpcm_src = enc;
+        p.adpcm.resize(units.size());
         uint64_t bytes = 0;
-        for (size_t u = 0; u < in.B; u++) {
-            const uint32_t A = adpcm_block_align(p.utt[u].hz, in.adpcm_align);
-            p.adpcm[u] = {bytes, adpcm_bytes(p.utt[u].n, A), A};
+        for (size_t u = 0; u < units.size(); u++) {
+            const uint32_t A = adpcm_block_align(units[u].hz, in.adpcm_align);
+            p.adpcm[u] = {bytes, adpcm_bytes(units[u].n, A), A};
             bytes += (p.adpcm[u].bytes + 15) & ~(uint64_t)15;
         }
         p.alloc[(size_t)OutSlab::Adpcm] = std::max<uint64_t>(bytes, 16);
     }
     return p;
+}
+
+bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, JoinLayout *out,
+                 uint32_t *bad, const char **field)
+{
+    // the numbering and the agreement on the rate are the loudness groups' (kJoinNone == kLnNoGroup)
+    static_assert(kJoinNone == kLnNoGroup, "one numbering for groups and programmes");
+    std::vector<uint32_t> ids(B);
+    for (size_t u = 0; u < B; u++)
+        ids[u] = req[u].programme;
+    LnGroupsIn gi;
+    gi.B = B;
+    gi.group = ids.data();
+    gi.hz = hz;
+    JoinLayout lay;
+    const char *f = "";
+    if (!plan_loudness_groups(gi, &lay.progs, bad, &f)) {
+        if (field)
+            *field = f[0] == 'g' ? "programme id" : f; // ("group id")
+        return false;
+    }
+    const size_t P = lay.progs.size();
+    const uint64_t align = kJoinGroupBytes / elem;
+    lay.units.assign(P, OutUnit{});
+    lay.start.assign(B, 0);
+    for (size_t g = 0; g < P; g++) {
+        OutUnit &w = lay.units[g];
+        w.off = lay.total;
+        for (uint32_t i = lay.progs.first[g]; i < lay.progs.first[g + 1]; i++) {
+            const uint32_t u = lay.progs.members[i];
+            lay.start[u] = w.n + req[u].pad_before;
+            w.n = lay.start[u] + n[u] + req[u].pad_after;
+        }
+        w.hz = hz ? hz[lay.progs.members[lay.progs.first[g]]] : 0;
+        lay.total = (w.off + w.n + align - 1) / align * align;
+    }
+    *out = std::move(lay);
+    return true;
+}
+
+void join_closure(const std::vector<uint32_t> &prog_of, size_t P, const std::vector<uint8_t> &post,
+                  std::vector<uint8_t> *programmes)
+{
+    programmes->assign(P, 0);
+    for (size_t u = 0; u < prog_of.size(); u++)
+        if (post[u])
+            (*programmes)[prog_of[u]] = 1;
 }
 
 bool plan_loudness_groups(const LnGroupsIn &in, LnGroups *out, uint32_t *bad_group, const char **bad_field)

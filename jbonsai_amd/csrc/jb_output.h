@@ -3,11 +3,15 @@
 // reads and writes, in f64 or in 16 bits, which slab the read entries hand out, and each utterance's output geometry,
 // decided from the batch's shape and the requests alone (plan_output, jb_output.cpp); with a sample format, the f64
 // slab the format stage reads and each utterance's place in its byte slab; with an IMA ADPCM request, the slab that
-// stage reads (f64 or 16-bit) and each utterance's blocks in its byte slab.
+// stage reads (f64 or 16-bit) and each utterance's blocks in its byte slab; with a join request (jb_join.h), the
+// programmes: their numbering, each one's place in the join slab and each member's start, and then the encoders'
+// geometry by programme instead of by utterance.
 // Plain C++17 without HIP: the plan is made and tested on any host; OutputChain (jb_host.h) carries it out.
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
+
+#include "jb_join.h"
 
 namespace jb {
 
@@ -23,11 +27,15 @@ enum class OutSlab : uint8_t {
     New16,   // 16-bit output longer than S16
     Fmt,     // bytes the format stage writes
     Adpcm,   // IMA ADPCM blocks
+    Join64,  // f64 the join stage writes: the programmes
+    Join16,  // the same in 16 bits
     Count
 };
 constexpr size_t out_slab_elem(OutSlab s) // bytes
 {
-    return s == OutSlab::Fmt || s == OutSlab::Adpcm ? 1 : s == OutSlab::S16 || s == OutSlab::New16 ? 2 : 8;
+    return s == OutSlab::Fmt || s == OutSlab::Adpcm                            ? 1
+           : s == OutSlab::S16 || s == OutSlab::New16 || s == OutSlab::Join16 ? 2
+                                                                               : 8;
 }
 
 // in_hz -> out_hz reduced by their gcd (rates above 0)
@@ -46,6 +54,7 @@ struct OutPlanIn {
     uint32_t fmt_bytes = 0;               // bytes per sample of the requested sample format; 0: none requested
     bool adpcm = false;                   // IMA ADPCM is requested
     uint32_t adpcm_align = 0;             // its block_align: 0 = by each utterance's output rate (jb_adpcm.h)
+    const JoinUtt *join = nullptr;        // [B] the join request (jb_join.h); nullptr: none
 };
 
 struct OutUtt {
@@ -60,6 +69,11 @@ struct OutFmtUtt { // an utterance's place in the format slab
 struct OutAdpcmUtt { // an utterance's blocks in the ADPCM slab
     uint64_t off, bytes; // byte offset (16-byte aligned) and blocks * A
     uint32_t A;          // its block size
+};
+
+struct OutUnit { // a programme in the join slab: what the encoders behind a join take for an utterance
+    uint32_t hz;
+    uint64_t n, off; // samples and first sample in the join slab (a 16-byte boundary)
 };
 
 struct OutWrite { // what a stage writes; slab None: the stage does not run
@@ -81,6 +95,13 @@ struct OutPlan {
     std::vector<OutFmtUtt> fmt;       // [B] with a format stage, else empty
     OutWrite adpcm_src;               // what the ADPCM stage reads: what `final` names, f64 or 16-bit (None: no ADPCM)
     std::vector<OutAdpcmUtt> adpcm;   // [B] with an ADPCM stage, else empty
+    // With a join request: the stage reads what `final` names and writes the programmes to a slab of its own; flac,
+    // fmt_src and adpcm_src then name that slab, and fmt and adpcm have [P] entries laid out from `units`
+    OutWrite join_src, join;          // None: no join
+    std::vector<OutUnit> units;       // [P] the programmes
+    std::vector<uint32_t> prog_of;    // [B] each utterance's programme
+    std::vector<uint64_t> prog_start; // [B] its first sample within it
+    std::vector<uint32_t> prog_first, prog_members; // programme p owns prog_members[prog_first[p] .. prog_first[p + 1])
     uint64_t alloc[(size_t)OutSlab::Count] = {}; // elements to allocate of each slab, at least 1 (0: none; V64 / S16 exist)
     bool normalize() const { return apply.slab != OutSlab::None; }
     bool active() const { return convert || normalize(); } // a stage rewrites the PCM behind the vocoder
@@ -120,5 +141,25 @@ bool plan_loudness_groups(const LnGroupsIn &in, LnGroups *out, uint32_t *bad_gro
 // member; members: [B] 1 = a member of such a group (a superset of touched)
 void loudness_groups_closure(const LnGroups &g, const std::vector<uint8_t> &touched, std::vector<uint8_t> *groups,
                              std::vector<uint8_t> *members);
+
+// The join request laid out (jb_join.h): programmes numbered densely in the order of their first member, as the
+// loudness groups are (an utterance of kJoinNone: a programme of one); programme p is its members in ascending
+// utterance index, each between its pads, and starts on a 16-byte boundary of a slab of `elem`-byte samples
+struct JoinLayout {
+    LnGroups progs;              // group_of: [B] the programme of each utterance; first / members: [P + 1] / [B]
+    std::vector<OutUnit> units;  // [P]
+    std::vector<uint64_t> start; // [B] each member's first sample within its programme
+    uint64_t total = 0;          // samples of the slab
+};
+// Pure.  n: [B] each utterance's samples; hz: [B] its output rate (nullptr: not compared, the units' rate is 0).
+// false: the request is refused; *bad is the caller's id of the offending programme and *field says "programme id"
+// for an id of B or above, or "output rate" where its members disagree
+bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, JoinLayout *out,
+                 uint32_t *bad, const char **field);
+
+// The redo closure behind the join.  post: [B] 1 = an utterance whose final PCM changed (behind
+// loudness_groups_closure); programmes: [P] 1 = a programme with such a member
+void join_closure(const std::vector<uint32_t> &prog_of, size_t P, const std::vector<uint8_t> &post,
+                  std::vector<uint8_t> *programmes);
 
 } // namespace jb

@@ -1,8 +1,7 @@
 // jb_output_chain.cpp -- OutputChain (jb_host.h): the stages behind the vocoder of one batch.  The setters record a
 // request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() launches
-// k_resample, the loudness measurement and apply pass, the FLAC encoder and pack, the sample format and IMA ADPCM, in
-// that order,
-// on the vocoder's stream.
+// k_resample, the loudness measurement and apply pass, the join, the FLAC encoder and pack, the sample format and IMA
+// ADPCM, in that order, on the vocoder's stream.
 #include "jb_host.h"
 
 #include <algorithm>
@@ -38,6 +37,7 @@ void OutputChain::replan()
     in.fmt_bytes = fmt_on ? (uint32_t)format_bytes(fmt_p.format) : 0;
     in.adpcm = ad_on;
     in.adpcm_align = ad_align;
+    in.join = join_req.empty() ? nullptr : join_req.data();
     plan = plan_output(in);
 }
 
@@ -72,7 +72,8 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
         if (want[u] && (rc = resample_design(in, want[u], nullptr, nullptr)))
             return rc;
     }
-    if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)))
+    if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)) ||
+        (rc = check_join(join_req, want, "jb_batch_set_output_rate")))
         return rc;
     want_hz = std::move(want);
     replan();
@@ -269,6 +270,43 @@ int OutputChain::set_adpcm(const jb_adpcm_opts *opts)
     return JB_OK;
 }
 
+// The join request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming what is wrong
+int OutputChain::check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const
+{
+    if (req.empty())
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    std::vector<uint32_t> hz(B, b.voice.sampling_frequency);
+    for (size_t u = 0; u < want.size(); u++)
+        if (want[u])
+            hz[u] = want[u];
+    std::vector<uint64_t> n(B, 0); // (the lengths do not bear on the check)
+    JoinLayout lay;
+    return join_layout_checked(req.data(), n.data(), hz.data(), B, sizeof(double), &lay, who);
+}
+
+int OutputChain::set_join(const jb_join_utt *req, size_t n)
+{
+    int rc = check_settable("jb_batch_set_join: the join is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!req && n == 0) {
+        join_req.clear();
+        replan();
+        return JB_OK;
+    }
+    if (!req || n != (size_t)b.B) {
+        set_error("jb_batch_set_join: give one request per utterance");
+        return JB_ERR_INVALID;
+    }
+    std::vector<JoinUtt> r((const JoinUtt *)req, (const JoinUtt *)req + n);
+    if ((rc = check_join(r, want_hz, "jb_batch_set_join")))
+        return rc;
+    join_req = std::move(r);
+    replan();
+    return JB_OK;
+}
+
 // At the first run (a second one, or the step done again behind a resident-GV formation timeout, finds it done).
 // The vocoder is pointed at its slab last: a failure leaves the batch as it was created, its blocks the batch's own
 int OutputChain::prepare()
@@ -280,7 +318,7 @@ int OutputChain::prepare()
     for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
-    if ((rc = prepare_resample()) || (rc = prepare_loudness()) || (rc = prepare_flac()) ||
+    if ((rc = prepare_resample()) || (rc = prepare_loudness()) || (rc = prepare_join()) || (rc = prepare_flac()) ||
         (rc = prepare_format()) || (rc = prepare_adpcm()))
         return rc;
     if (plan.active()) {
@@ -422,19 +460,72 @@ int OutputChain::prepare_loudness()
     return JB_OK;
 }
 
-// The streams' lists and slabs: one stream per utterance of the 16-bit slab handed out, at its output rate
+// The units the encoders take, in the slab each of them reads: the programmes behind a join, else the utterances
+std::vector<OutputChain::EncUnit> OutputChain::enc_units() const
+{
+    std::vector<EncUnit> units;
+    if (joined())
+        for (const OutUnit &w : plan.units)
+            units.push_back({w.off, w.n, w.hz});
+    else
+        for (const OutUtt &w : plan.utt)
+            units.push_back({w.off, w.n, w.hz});
+    return units;
+}
+
+// The members in programme order and one span per programme: the final PCM of the plan in, the join slab out
+int OutputChain::prepare_join()
+{
+    if (!joined())
+        return JB_OK;
+    const size_t B = (size_t)b.B, P = plan.units.size();
+    const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
+    const char *src = (const char *)slab[(size_t)plan.join_src.slab];
+    char *dst = (char *)slab[(size_t)plan.join.slab];
+    jn.members.assign(B, JoinMember{});
+    jn.member_at.assign(B, 0);
+    jn.spans.assign(P, JoinSpan{});
+    jn.tiles = 0;
+    for (size_t p = 0; p < P; p++) {
+        const uint32_t m0 = plan.prog_first[p], m1 = plan.prog_first[p + 1];
+        for (uint32_t i = m0; i < m1; i++) {
+            const uint32_t u = plan.prog_members[i];
+            jn.member_at[u] = i;
+            jn.members[i] = {src + plan.utt[u].off * elem, plan.prog_start[u], plan.utt[u].n, join_req[u].fade_in,
+                             join_req[u].fade_out};
+        }
+        jn.spans[p] = {dst + plan.units[p].off * elem, plan.units[p].n, 0, plan.units[p].n, jn.tiles, m0, m1 - m0};
+        jn.tiles += join_tiles(0, plan.units[p].n, plan.join.i16);
+    }
+    int rc;
+    // (a redo lists at most one span per member)
+    if ((rc = b.dalloc(&jn.members_dev, B, false)) || (rc = b.dalloc(&jn.spans_dev, P, false)) ||
+        (rc = b.dalloc(&jn.redo_dev, B, false)))
+        return rc;
+    hipError_t e;
+    if (B > 0 && ((e = hipMemcpy(jn.members_dev, jn.members.data(), sizeof(JoinMember) * B, hipMemcpyHostToDevice)) !=
+                      hipSuccess ||
+                  (e = hipMemcpy(jn.spans_dev, jn.spans.data(), sizeof(JoinSpan) * P, hipMemcpyHostToDevice)) !=
+                      hipSuccess))
+        return hip_fail(e, "join work list");
+    return JB_OK;
+}
+
+// The streams' lists and slabs: one stream per unit (an utterance; behind a join a programme) of the 16-bit slab
+// FLAC reads, at its output rate
 int OutputChain::prepare_flac()
 {
     if (!flac_on)
         return JB_OK;
-    const size_t B = (size_t)b.B;
+    const std::vector<EncUnit> units = enc_units();
+    const size_t B = units.size();
     std::vector<const int16_t *> xs(B);
     std::vector<uint64_t> ns(B);
     std::vector<uint32_t> hz(B);
     for (size_t u = 0; u < B; u++) {
-        xs[u] = (const int16_t *)slab[(size_t)plan.flac] + plan.utt[u].off;
-        ns[u] = plan.utt[u].n;
-        hz[u] = plan.utt[u].hz;
+        xs[u] = (const int16_t *)slab[(size_t)plan.flac] + units[u].off;
+        ns[u] = units[u].n;
+        hz[u] = units[u].hz;
     }
     std::vector<FlacUtt> utts;
     uint64_t slot_bytes = 0, bound = 0;
@@ -478,16 +569,17 @@ int OutputChain::prepare_format()
 {
     if (plan.fmt_src == OutSlab::None)
         return JB_OK;
-    const size_t B = (size_t)b.B;
+    const std::vector<EncUnit> units = enc_units();
+    const size_t B = units.size();
     const double *src = (const double *)slab[(size_t)plan.fmt_src];
     uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Fmt];
     fm.utts.assign(B, FormatUtt{});
     fm.tiles = 0;
     for (size_t u = 0; u < B; u++) {
         FormatUtt &w = fm.utts[u];
-        w.x = src + plan.utt[u].off;
+        w.x = src + units[u].off;
         w.y = dst + plan.fmt[u].off;
-        w.n = plan.utt[u].n;
+        w.n = units[u].n;
         w.ft0 = fm.tiles;
         fm.tiles += (w.n + kFmtTile - 1) / kFmtTile;
     }
@@ -506,7 +598,8 @@ int OutputChain::prepare_adpcm()
 {
     if (plan.adpcm_src.slab == OutSlab::None)
         return JB_OK;
-    const size_t B = (size_t)b.B;
+    const std::vector<EncUnit> units = enc_units();
+    const size_t B = units.size();
     const char *src = (const char *)slab[(size_t)plan.adpcm_src.slab];
     const size_t elem = plan.adpcm_src.i16 ? sizeof(int16_t) : sizeof(double);
     uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Adpcm];
@@ -514,9 +607,9 @@ int OutputChain::prepare_adpcm()
     ad.groups = 0;
     for (size_t u = 0; u < B; u++) {
         AdpcmUtt &w = ad.utts[u];
-        w.x = src + plan.utt[u].off * elem;
+        w.x = src + units[u].off * elem;
         w.y = dst + plan.adpcm[u].off;
-        w.n = plan.utt[u].n;
+        w.n = units[u].n;
         w.g0 = ad.groups;
         w.A = plan.adpcm[u].A;
         w.spb = adpcm_spb(w.A);
@@ -535,9 +628,10 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
 {
     const bool fmt = plan.fmt_src != OutSlab::None;
     const bool adp = plan.adpcm_src.slab != OutSlab::None;
-    if (!ready || !(plan.active() || flac_on || fmt || adp))
+    if (!ready || !(plan.active() || flac_on || fmt || adp || joined()))
         return JB_OK;
     const uint32_t B = (uint32_t)b.B;
+    const uint32_t U = (uint32_t)num_outputs(); // the encoders' units: the programmes behind a join, else B
     hipStream_t st = b.stream_voc;
     // the lists of a run: the batch's own
     const ResampleTile *tiles = rs.tiles_dev;
@@ -546,10 +640,10 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const uint32_t *md5_order = fl.md5_order_dev;
     uint32_t n_md5 = fl.n_md5;
     const FormatUtt *futts = fm.utts_dev;
-    uint32_t n_futts = fmt ? B : 0;
+    uint32_t n_futts = fmt ? U : 0;
     uint64_t ft = fm.tiles;
     const AdpcmUtt *autts = ad.utts_dev;
-    uint32_t n_autts = adp ? B : 0;
+    uint32_t n_autts = adp ? U : 0;
     uint64_t ag = ad.groups;
     const uint32_t n_all_work = (uint32_t)fl.work.size();
     uint32_t n_tiles = (uint32_t)rs.tiles.size(), n_utts = B, n_work = n_all_work;
@@ -564,10 +658,21 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     // behind the apply pass a group's gain reaches every member: the stages there run again for all of them
     std::vector<uint8_t> touched_groups, group_members;
     const std::vector<uint8_t> *post = only;
+    // behind the join a member's samples reach its programme: the encoders run again for every programme of `post`
+    std::vector<uint8_t> touched_units;
+    const std::vector<uint8_t> *upost = only; // [U]
+    const JoinSpan *jspans = jn.spans_dev;
+    uint32_t n_jspans = joined() ? U : 0;
+    uint64_t jt = jn.tiles;
     hipError_t e = hipSuccess;
     if (only && grouped) {
         loudness_groups_closure(ln_groups, *only, &touched_groups, &group_members);
         post = &group_members;
+    }
+    upost = post;
+    if (only && joined()) {
+        join_closure(plan.prog_of, U, *post, &touched_units);
+        upost = &touched_units;
     }
     if (only) {
         // of a redo: the tiles, the utterances (renumbered: their scratch stays where it is) and the FLAC blocks of
@@ -580,7 +685,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         std::vector<AdpcmUtt> ad_sub;
         std::vector<LoudnessUtt> ap_sub; // grouped: the apply pass's own list
         std::vector<LoudnessSet> set_sub;
-        lt = at = ft = ag = 0;
+        std::vector<JoinSpan> jn_sub;
+        lt = at = ft = ag = jt = 0;
         uint64_t mat = 0; // apply tiles of the measured list (its at0 is not read when the apply pass has its own)
         for (size_t u = 0; u < B; u++) {
             if ((*only)[u]) {
@@ -606,6 +712,22 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
                 at += (w.n + kLnApplyTile - 1) / kLnApplyTile;
                 ap_sub.push_back(w);
             }
+            if (joined() && plan.utt[u].n) {
+                // the member's span alone, widened to whole groups (the samples around it are what they were: its
+                // neighbours' current ones, and pads)
+                const uint64_t gs = kJoinGroupBytes / (plan.join.i16 ? sizeof(int16_t) : sizeof(double));
+                JoinSpan w = jn.spans[plan.prog_of[u]];
+                const JoinMember &m = jn.members[jn.member_at[u]];
+                w.k0 = m.start / gs * gs;
+                w.k1 = std::min<uint64_t>((m.start + m.n + gs - 1) / gs * gs, w.n);
+                w.t0 = jt;
+                jt += join_tiles(w.k0, w.k1, plan.join.i16);
+                jn_sub.push_back(w);
+            }
+        }
+        for (size_t u = 0; u < U; u++) {
+            if (!(*upost)[u])
+                continue;
             if (fmt) {
                 FormatUtt w = fm.utts[u];
                 w.ft0 = ft;
@@ -632,10 +754,10 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         n_apply = grouped ? (uint32_t)ap_sub.size() : (uint32_t)ln_sub.size();
         apply_utts = grouped ? ln.apply_redo_dev : ln.redo_dev;
         for (const FlacWork &w : fl.work)
-            if ((*post)[w.utt])
+            if ((*upost)[w.utt])
                 fl_sub.push_back(w);
         if (fl.digests)
-            flac_md5_order(fl.utts, post, &md5_sub); // (an utterance without frames keeps its digest of no samples)
+            flac_md5_order(fl.utts, upost, &md5_sub); // (an utterance without frames keeps its digest of no samples)
         tiles = rs.redo_dev;
         utts = ln.redo_dev;
         work = fl.redo_dev;
@@ -648,7 +770,9 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         n_tiles = (uint32_t)rs_sub.size();
         n_utts = (uint32_t)ln_sub.size();
         n_work = (uint32_t)fl_sub.size();
-        if (!n_tiles && !n_utts && !n_work && !n_futts && !n_autts && !n_apply)
+        jspans = jn.redo_dev;
+        n_jspans = (uint32_t)jn_sub.size();
+        if (!n_tiles && !n_utts && !n_work && !n_futts && !n_autts && !n_apply && !n_jspans)
             return JB_OK;
         if ((n_tiles && (e = hipMemcpy(rs.redo_dev, rs_sub.data(), sizeof(ResampleTile) * n_tiles,
                                        hipMemcpyHostToDevice)) != hipSuccess) ||
@@ -658,6 +782,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
                                                hipMemcpyHostToDevice)) != hipSuccess) ||
             (!set_sub.empty() && (e = hipMemcpy(ln.sets_redo_dev, set_sub.data(), sizeof(LoudnessSet) * set_sub.size(),
                                                 hipMemcpyHostToDevice)) != hipSuccess) ||
+            (n_jspans && (e = hipMemcpy(jn.redo_dev, jn_sub.data(), sizeof(JoinSpan) * n_jspans,
+                                        hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_work && (e = hipMemcpy(fl.redo_dev, fl_sub.data(), sizeof(FlacWork) * n_work, hipMemcpyHostToDevice)) !=
                            hipSuccess) ||
             (n_md5 && (e = hipMemcpy(fl.md5_redo_dev, md5_sub.data(), sizeof(uint32_t) * n_md5,
@@ -682,12 +808,16 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
                                                ln.z, ln.sw, ln.mm, ln.r128, st)) != hipSuccess) ||
          (e = launch_loudness_apply(apply_utts, n_apply, at, ln.res, plan.apply.i16, st)) != hipSuccess))
         return hip_fail(e, only ? "loudness(redo)" : "loudness");
+    // the join: behind everything that writes the final PCM, in front of everything that encodes it
+    if (joined() && (!only || n_jspans) &&
+        (e = launch_join(plan.join.i16, jspans, n_jspans, jt, jn.members_dev, st)) != hipSuccess)
+        return hip_fail(e, only ? "k_join(redo)" : "k_join");
     // FLAC: the blocks of the list, the digests of its utterances' now final PCM (on request), then every stream's
     // offsets, place and header (all of fl.work_dev, redo or not): the pack never sees a digest of replaced PCM
     if (flac_on && (!only || n_work) &&
         ((e = launch_flac_encode(flac_p, fl.utts_dev, work, n_work, fl.fsize, st)) != hipSuccess ||
          (fl.digests && (e = launch_flac_md5(fl.utts_dev, md5_order, n_md5, fl.digests, st)) != hipSuccess) ||
-         (e = launch_flac_pack(flac_p, fl.utts_dev, B, fl.work_dev, n_all_work, fl.fsize, fl.foff, fl.res, fl.total,
+         (e = launch_flac_pack(flac_p, fl.utts_dev, U, fl.work_dev, n_all_work, fl.fsize, fl.foff, fl.res, fl.total,
                                fl.out, st, fl.digests, fl.max_points)) != hipSuccess))
         return hip_fail(e, only ? "FLAC(redo)" : "FLAC");
     // the sample format last: behind the apply pass, the converter or the hand-off check, whichever wrote last
@@ -757,7 +887,7 @@ int OutputChain::read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_
     int rc = flac_ready();
     if (rc)
         return rc;
-    const size_t B = (size_t)b.B;
+    const size_t B = num_outputs();
     res->assign(B, FlacOut{});
     if ((rc = B > 0 ? b.read(fl.res, res->data(), sizeof(FlacOut) * B) : b.sync()))
         return rc;
@@ -771,6 +901,21 @@ int OutputChain::read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_
         return JB_ERR_INVALID;
     }
     return total ? b.read(fl.out, host->get(), (size_t)total, false) : JB_OK;
+}
+
+int OutputChain::read_programme(size_t p, bool i16, void *dst)
+{
+    int rc = check_ready(joined(), "join: the batch has not run", "join: jb_batch_set_join was not called");
+    if (rc)
+        return rc;
+    if (i16 != plan.join.i16) {
+        set_error(i16 ? "batch was created without JB_BATCH_PCM_I16"
+                      : "batch was created with JB_BATCH_PCM_I16: use jb_batch_read_programme_pcm_i16");
+        return JB_ERR_INVALID;
+    }
+    const OutUnit &w = plan.units[p];
+    const size_t elem = i16 ? sizeof(int16_t) : sizeof(double);
+    return w.n ? b.read((const char *)slab[(size_t)plan.join.slab] + w.off * elem, dst, (size_t)w.n * elem) : b.sync();
 }
 
 const OutAdpcmUtt *OutputChain::adpcm_place(size_t u) const

@@ -461,6 +461,59 @@ class Engine:
                                                   nsamp))
         return F.adpcm_streams(self._L, bufs, ns, nsamp, [self._out_hz()] * B, block_align, B)
 
+    def synthesize_programme(self, utterances: Sequence[Sequence[str]], sink: str = "f64", lead_ms: float = 0.0,
+                             gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0, device: int = -1,
+                             **sink_opts):
+        """jb_synthesize_programme*: the utterances as ONE programme -- lead_ms of zeros, the first utterance, gap_ms,
+        the next, ..., trail_ms, a fade of fade_ms at both edges of each -- joined on the GPU in front of the sink.
+        sink: "f64" or "i16" (PCM arrays), "flac" (bytes; block_size, max_lpc_order, md5, seek_interval_ms),
+        "formatted" (bytes; fmt, dither, seed) or "adpcm" (an AdpcmStream; block_align).  Returns (output, starts):
+        starts[u] is utterance u's first sample within the programme."""
+        flat = [l for u in utterances for l in u]
+        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+        B = len(utterances)
+        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+        join = F.join_opts(lead_ms, gap_ms, trail_ms, fade_ms)
+        starts = (C.c_uint64 * max(1, B))()
+        out, n = C.c_void_p(), C.c_size_t()
+        L = self._L
+        if sink in ("f64", "i16"):
+            if sink_opts:
+                raise TypeError(f"unknown options {sorted(sink_opts)}")
+            fn = L.jb_synthesize_programme_i16 if sink == "i16" else L.jb_synthesize_programme
+            F.check(fn(self._h, _lines(flat), offs, B, device, C.byref(join), C.byref(out), C.byref(n), starts))
+            ety, dt = (C.c_int16, np.int16) if sink == "i16" else (C.c_double, np.float64)
+            res = np.frombuffer((ety * n.value).from_address(out.value), dtype=dt).copy() if n.value else np.zeros(0, dt)
+            L.jb_join_free(out)  # (malloc'ed by the library, as every output is)
+            return res, list(starts[:B])
+        buf = C.POINTER(C.c_uint8)()
+        if sink == "flac":
+            opts = F.flac_opts(sink_opts.pop("block_size", 0), sink_opts.pop("max_lpc_order", None))
+            meta = F.flac_meta(sink_opts.pop("md5", False), sink_opts.pop("seek_interval_ms", 0))
+            if sink_opts:
+                raise TypeError(f"unknown options {sorted(sink_opts)}")
+            F.check(L.jb_synthesize_programme_flac_meta(self._h, _lines(flat), offs, B, device, C.byref(opts),
+                                                        C.byref(meta) if meta is not None else None, C.byref(join),
+                                                        C.byref(buf), C.byref(n), starts))
+            return F.take_flac(L, [buf], [n.value], 1)[0], list(starts[:B])
+        if sink == "formatted":
+            opts = F.format_opts(sink_opts.pop("fmt"), sink_opts.pop("dither", False), sink_opts.pop("seed", 0))
+            if sink_opts:
+                raise TypeError(f"unknown options {sorted(sink_opts)}")
+            F.check(L.jb_synthesize_programme_formatted(self._h, _lines(flat), offs, B, device, C.byref(opts),
+                                                        C.byref(join), C.byref(buf), C.byref(n), starts))
+            return F.take_formatted(L, [buf], [n.value], 1)[0], list(starts[:B])
+        if sink == "adpcm":
+            block_align = sink_opts.pop("block_align", 0)
+            if sink_opts:
+                raise TypeError(f"unknown options {sorted(sink_opts)}")
+            opts, ns = F.adpcm_opts(block_align), C.c_size_t()
+            F.check(L.jb_synthesize_programme_adpcm(self._h, _lines(flat), offs, B, device, C.byref(opts),
+                                                    C.byref(join), C.byref(buf), C.byref(n), C.byref(ns), starts))
+            return (F.adpcm_streams(L, [buf], [n.value], [ns.value], [self._out_hz()], block_align, 1)[0],
+                    list(starts[:B]))
+        raise ValueError('sink is "f64", "i16", "flac", "formatted" or "adpcm"')
+
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
         F.check(self._L.jb_generator_new(self._h, _lines(labels), len(labels), C.byref(h)))
