@@ -2,13 +2,14 @@
 
     python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
-                               [--loudness LUFS [--ceiling DBFS]] [--rate HZ]
+                               [--loudness LUFS [--ceiling DBFS]] [--rate HZ] [--highpass HZ]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
 batch and joined on the GPU (Engine.synthesize_programme) in front of the encoder, so a .flac output is one stream whose
 frame numbers, STREAMINFO, MD5 and SEEKTABLE (a point about every second) cover the whole chapter; any other name is
 written as a 16-bit WAV file.  With --loudness the chapter gets ONE gain (per-request loudness scope), so the sentences
-keep their relative levels.  The cue list -- each sentence's first sample and time within the chapter -- is printed.
+keep their relative levels.  With --highpass a rumble and DC high-pass at that corner runs on the GPU in front of the
+loudness measurement and the encoder (Engine.set_filter).  The cue list -- each sentence's first sample and time within the chapter -- is printed.
 Needs an MI355X: the library has no CPU path.
 """
 import argparse
@@ -29,6 +30,7 @@ ap.add_argument("--fade-ms", type=float, default=5.0, help="fade at both edges o
 ap.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="target loudness of the chapter")
 ap.add_argument("--ceiling", type=float, default=-1.0, metavar="DBFS", help="sample-peak ceiling (with --loudness)")
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate")
+ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner (50 to 80 Hz removes rumble and DC)")
 args = ap.parse_args()
 
 sentences = []
@@ -39,6 +41,8 @@ for path in args.labels:
 engine = J.Engine.load([args.voice])
 if args.rate:
     engine.condition.set_output_sampling_frequency(args.rate)
+if args.highpass is not None:
+    engine.set_filter(J.highpass(args.highpass))
 if args.loudness is not None:
     engine.condition.set_loudness_target(args.loudness)
     engine.condition.set_peak_ceiling(args.ceiling)

@@ -2,7 +2,7 @@
 
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
-                                 [--flac]
+                                 [--flac] [--highpass HZ]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
@@ -18,6 +18,8 @@ With --adpcm the audio is encoded as IMA ADPCM (WAV format tag 0x11, half a byte
 given, with the block size that goes with the rate.
 With --flac the 16-bit audio is encoded as a FLAC stream on the GPU, with the MD5 of its samples in STREAMINFO and a
 SEEKTABLE with a point about every second, and written as it is.
+With --highpass the audio passes a second-order high-pass at that corner on the GPU (Engine.set_filter), behind the
+output rate and in front of the loudness measurement and every encoder above.
 """
 import argparse
 import os
@@ -42,10 +44,13 @@ ap.add_argument("--dither", action="store_true", help="TPDF dither (with --forma
 ap.add_argument("--adpcm", action="store_true", help="IMA ADPCM (4-bit) WAV file, encoded on the GPU")
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm)")
 ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
+ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
 args = ap.parse_args()
 voice, out = args.voice, args.out
 
 engine = J.Engine.load([voice])
+if args.highpass is not None:
+    engine.set_filter(J.highpass(args.highpass))
 if args.loudness is not None:
     engine.condition.set_loudness_target(args.loudness)
     engine.condition.set_peak_ceiling(args.ceiling)

@@ -158,6 +158,34 @@ typedef struct jb_join_opts {
     uint32_t reserved[2];
 } jb_join_opts;
 
+/* The output filter (see "Filter" below): a cascade of up to JB_FILTER_MAX_SECTIONS second-order sections at the
+ * output rate, applied in order.  A section is a kind with f0_hz, q and gain_db (gain_db: peaking and the shelves
+ * only, but finite everywhere), or JB_FILTER_RAW with b0 b1 b2 a1 a2 (a0 = 1), used as given at any rate.  reserved 0.
+ * n_sections 0: no filter. */
+#define JB_FILTER_MAX_SECTIONS 4
+#define JB_FILTER_HIGHPASS 1u
+#define JB_FILTER_LOWPASS 2u
+#define JB_FILTER_PEAKING 3u
+#define JB_FILTER_LOWSHELF 4u
+#define JB_FILTER_HIGHSHELF 5u
+#define JB_FILTER_NOTCH 6u
+#define JB_FILTER_RAW 7u
+typedef struct jb_filter_section {
+    uint32_t kind; /* JB_FILTER_* */
+    uint32_t reserved;
+    double f0_hz, q, gain_db;
+    double b0, b1, b2, a1, a2; /* JB_FILTER_RAW only */
+} jb_filter_section;
+typedef struct jb_filter {
+    jb_filter_section section[JB_FILTER_MAX_SECTIONS];
+    uint32_t n_sections;
+    uint32_t reserved;
+} jb_filter;
+/* One designed section: y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2]. */
+typedef struct jb_biquad {
+    double b0, b1, b2, a1, a2;
+} jb_biquad;
+
 typedef struct jb_batch_opts {
     int32_t device;         /* HIP device ordinal; -1 = current */
     uint32_t flags;         /* JB_BATCH_* */
@@ -840,6 +868,51 @@ int jb_join_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n
                           int32_t device, int16_t **out, size_t *n_out, size_t *n_programmes);
 void jb_join_free(void *p);
 
+/* ---- Filter (new: the reference has no such control) ---------------------------------------------------------------
+ * A caller-chosen cascade of up to four second-order sections shapes the PCM on the device, at the output rate: behind
+ * the converter (or the vocoder at the native rate) and in front of the loudness measurement, so that the target, the
+ * ceiling, the groups, the join and every encoder see the filtered audio.
+ * - Design (host only, once per distinct filter and output rate): the Audio EQ Cookbook forms with w0 = 2 pi f0 / fs and
+ *   alpha = sin(w0) / (2 q) for every kind, the shelves with the same alpha and A = 10^(gain_db / 40), normalised by a0.
+ * - Refused (JB_ERR_INVALID; jb_last_error names the utterance, the section and the field): more than four sections, an
+ *   unknown kind, f0 <= 0, f0 >= rate / 2 at that utterance's output rate, q <= 0, a field that is not finite, and any
+ *   section, designed or raw, whose poles are not strictly inside the unit circle (|a2| < 1 and |a1| < 1 + a2).
+ * - One sample: transposed direct form II, per section y = fma(b0, x, s0); s0 = fma(b1, x, fma(-a1, y, s1));
+ *   s1 = fma(b2, x, -a2 * y); the next section's x is y.  States start at zero.  Input and output are f64 in 16-bit
+ *   units; a 16-bit batch's output is the 16-bit sink's rule (fmin to 32767, fmax to -32768, truncate) on the same y.
+ * - The device filters tiles of 4,096 samples from zero state, carries their states with a scan of the affine maps
+ *   s -> A^len s + e and filters the tiles again from their true start states: the serial recursion up to rounding.
+ *   The tiling depends on the utterance's length alone: an utterance's output depends on its samples, its filter and
+ *   its rate, not on the batch, its position in it or redo rounds; JB_BATCH_INVARIANT output stays invariant.
+ * - jb_batch_read_pcm_native stays the unfiltered vocoder PCM.
+ * - Cost on 256 x 128 s (profiles/r18_filter.txt): a one-section high-pass takes 6.70 ms of device time (each sample read
+ *   twice and written once: 37.7 GB), four sections 12.20 ms; the loudness measurement and apply pass of the same batch:
+ *   16.89 ms.  Against a serial cascade in extended precision the device's largest error is 4.4e-12 of the utterance's
+ *   largest sample (a serial f64 cascade: 1.4e-12).
+ * Not covered: FIR sections, time-varying filters, more than four sections, one-pole sections, a filter in front of
+ * the converter, filters on the native-rate reads, a limiter, serving a generator head early, reading through the
+ * pinned ring. */
+/* New (none).  f[0..n): one filter for the batch (n == 1) or one per utterance (n == jb_batch_size); NULL, 0 withdraws
+ * the request.  Before the first run only.  Checked against each utterance's output rate, here and again by a later
+ * jb_batch_set_output_rate. */
+int jb_batch_set_filter(jb_batch *b, const jb_filter *f, size_t n);
+/* New (none).  What the device runs for utterance utt at its output rate: *n sections (0 without a filter) in out. */
+int jb_batch_filter_coefficients(const jb_batch *b, size_t utt, jb_biquad out[JB_FILTER_MAX_SECTIONS], uint32_t *n);
+/* New (none).  The host design of f at hz: f->n_sections sections into out (out may be NULL: the check alone). */
+int jb_filter_design(const jb_filter *f, uint32_t hz, jb_biquad out[JB_FILTER_MAX_SECTIONS]);
+/* New (none).  The serial recursion in plain C++ on the host; no GPU is touched.  out must hold n samples (cap below
+ * that: JB_ERR_BUFFER).  A filter without sections returns the input bit for bit. */
+int jb_filter_pcm_host(const double *in, size_t n, const jb_filter *f, uint32_t hz, double *out, size_t cap);
+/* New (none).  The stage on PCM the caller holds (jb_format_pcm_batch's twin), on `device` (-1 = current): utterance u
+ * is n_in[u] f64 samples at hz[u] under f[u]; out[u] = its n_out[u] = n_in[u] filtered samples, f64 or by the 16-bit
+ * sink's rule, library-owned (jb_filter_free each).  The same samples, filter and rate give the same bits from this
+ * seam and from the batch path. */
+int jb_filter_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_filter *f, const uint32_t *hz,
+                        int32_t device, double **out, size_t *n_out);
+int jb_filter_pcm_batch_i16(const double *const *in, const size_t *n_in, size_t n, const jb_filter *f,
+                            const uint32_t *hz, int32_t device, int16_t **out, size_t *n_out);
+void jb_filter_free(void *p);
+
 /* ---- multi-GPU (SURVEY 8b "device_ids[] / n_devices", 8e) ----------------------------------
  * Utterances are independent, so a batch shards over the GPUs of a node with no data-path
  * collective: static LPT partition by length, one host thread per device, results in the caller's
@@ -973,6 +1046,14 @@ uint32_t jb_engine_get_peak_mode(const jb_engine *e);
 #define JB_LOUDNESS_PER_REQUEST 1
 int jb_engine_set_loudness_scope(jb_engine *e, uint32_t scope);
 uint32_t jb_engine_get_loudness_scope(const jb_engine *e);
+/* New.  The output filter of the audio the engine's entries return (see "Filter"): jb_synthesize, every
+ * jb_synthesize_batch* and jb_synthesize_programme* form, _each* (each engine's own filter for its utterance: it is
+ * not among the fields the engines must agree on), _multi and the generator filter on the device
+ * (jb_batch_set_filter), behind the output rate and in front of the loudness target.  NULL or a filter without
+ * sections (the default) = off: the output is unchanged.  Checked here at the engine's present output rate and again
+ * at synthesis.  jb_engine_new copies it with the Condition. */
+int jb_engine_set_filter(jb_engine *e, const jb_filter *f);
+int jb_engine_get_filter(const jb_engine *e, jb_filter *out);
 /* New.  Where the per-label decision-tree search of the front half runs (Model::get_index for the duration model and
  * every stream model, state and voice, and the GV switch question).  The default is the host, as before: nothing new
  * runs and nothing is allocated.  On the device one wave searches one label (jb_treesearch.hip); label parsing, the
@@ -1270,6 +1351,11 @@ JB_LAYOUT_ASSERT(sizeof(jb_loudness_r128) == 48 && offsetof(jb_loudness_r128, lr
 JB_LAYOUT_ASSERT(sizeof(jb_loudness_group_report) == 96 && offsetof(jb_loudness_group_report, peak_mode) == 32 &&
                      offsetof(jb_loudness_group_report, members) == 40 && offsetof(jb_loudness_group_report, r128) == 48,
                  "jb_loudness_group_report");
+JB_LAYOUT_ASSERT(sizeof(jb_filter_section) == 72 && offsetof(jb_filter_section, f0_hz) == 8 &&
+                     offsetof(jb_filter_section, gain_db) == 24 && offsetof(jb_filter_section, b0) == 32,
+                 "jb_filter_section");
+JB_LAYOUT_ASSERT(sizeof(jb_filter) == 296 && offsetof(jb_filter, n_sections) == 288, "jb_filter");
+JB_LAYOUT_ASSERT(sizeof(jb_biquad) == 40 && offsetof(jb_biquad, a1) == 24, "jb_biquad");
 #undef JB_LAYOUT_ASSERT
 #endif
 #endif /* JBONSAI_AMD_H */

@@ -10,7 +10,9 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    format_pcm, format_pcm_host, write_wav_formatted, AdpcmStream, adpcm_decode_host, adpcm_encode,
                    adpcm_encode_host, adpcm_geometry, write_wav_adpcm, loudness_groups, loudness_gate_host,
                    LOUDNESS_NO_GROUP, LOUDNESS_R128, LOUDNESS_PER_UTTERANCE, LOUDNESS_PER_REQUEST,
-                   JOIN_NONE, JoinUtt, join_geometry, join_host, join_ms_to_samples, join_pcm)
+                   JOIN_NONE, JoinUtt, join_geometry, join_host, join_ms_to_samples, join_pcm,
+                   Filter, FilterSection, Biquad, filter_design, filter_sos, filter_pcm, filter_pcm_host, highpass,
+                   lowpass, peaking, lowshelf, highshelf, notch, raw_filter, telephone_band, no_filter)
 from .batch import (Batch, IndexStreamStates, IndexUtterance, PdfSet, StreamInfo, StreamStates, TrackUtterance,  # noqa: F401
                     Utterance, VoiceInfo, generator_from_tracks, mlpg_batch, paramgen_vocode_batch, vocode_tracks_batch,
                     vocoder_synthesize_batch)
@@ -28,4 +30,6 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "AdpcmStream", "adpcm_decode_host", "adpcm_encode", "adpcm_encode_host", "adpcm_geometry", "write_wav_adpcm",
            "synthesize_batch_each_adpcm", "loudness_groups", "loudness_gate_host", "LOUDNESS_NO_GROUP", "LOUDNESS_R128", "LOUDNESS_PER_UTTERANCE",
            "LOUDNESS_PER_REQUEST", "JOIN_NONE", "JoinUtt", "join_geometry", "join_host", "join_ms_to_samples",
-           "join_pcm"]
+           "join_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",
+           "filter_pcm_host", "highpass", "lowpass", "peaking", "lowshelf", "highshelf", "notch", "raw_filter",
+           "telephone_band", "no_filter"]

@@ -235,6 +235,91 @@ def join_request(req):
     return arr
 
 
+FILTER_MAX_SECTIONS = 4
+FILTER_HIGHPASS, FILTER_LOWPASS, FILTER_PEAKING, FILTER_LOWSHELF, FILTER_HIGHSHELF, FILTER_NOTCH, FILTER_RAW = range(1, 8)
+
+
+class FilterSection(C.Structure):
+    """jb_filter_section: a kind with f0_hz, q and gain_db, or FILTER_RAW with b0 b1 b2 a1 a2 (a0 = 1)."""
+    _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("f0_hz", C.c_double), ("q", C.c_double),
+                ("gain_db", C.c_double), ("b0", C.c_double), ("b1", C.c_double), ("b2", C.c_double),
+                ("a1", C.c_double), ("a2", C.c_double)]
+
+
+class Filter(C.Structure):
+    """jb_filter: up to four sections applied in order.  `a + b` is the cascade of a's sections, then b's."""
+    _fields_ = [("section", FilterSection * FILTER_MAX_SECTIONS), ("n_sections", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __add__(self, other):
+        out = Filter()
+        # (a cascade of more than four sections keeps its count: the library refuses it, naming n_sections)
+        out.n_sections = self.n_sections + other.n_sections
+        secs = [self.section[i] for i in range(min(self.n_sections, FILTER_MAX_SECTIONS))] + \
+            [other.section[i] for i in range(min(other.n_sections, FILTER_MAX_SECTIONS))]
+        for i, sec in enumerate(secs[:FILTER_MAX_SECTIONS]):
+            C.memmove(C.byref(out.section[i]), C.byref(sec), C.sizeof(FilterSection))
+        return out
+
+
+class Biquad(C.Structure):
+    """jb_biquad: one designed section."""
+    _fields_ = [("b0", C.c_double), ("b1", C.c_double), ("b2", C.c_double), ("a1", C.c_double), ("a2", C.c_double)]
+
+
+def filter_section(kind: int, f0: float, q: float = 0.7071067811865476, gain_db: float = 0.0):
+    """A Filter of one designed section."""
+    f = Filter()
+    f.n_sections = 1
+    f.section[0].kind, f.section[0].f0_hz, f.section[0].q, f.section[0].gain_db = int(kind), float(f0), float(q), \
+        float(gain_db)
+    return f
+
+
+def no_filter():
+    return Filter()
+
+
+def highpass(f0, q=0.7071067811865476): return filter_section(FILTER_HIGHPASS, f0, q)
+def lowpass(f0, q=0.7071067811865476): return filter_section(FILTER_LOWPASS, f0, q)
+def peaking(f0, gain_db, q=0.7071067811865476): return filter_section(FILTER_PEAKING, f0, q, gain_db)
+def lowshelf(f0, gain_db, q=0.7071067811865476): return filter_section(FILTER_LOWSHELF, f0, q, gain_db)
+def highshelf(f0, gain_db, q=0.7071067811865476): return filter_section(FILTER_HIGHSHELF, f0, q, gain_db)
+def notch(f0, q=0.7071067811865476): return filter_section(FILTER_NOTCH, f0, q)
+
+
+def telephone_band():
+    """The G.712 voice band in front of G.711: high-pass 300 Hz, low-pass 3400 Hz."""
+    return highpass(300.0) + lowpass(3400.0)
+
+
+def raw_filter(sos):
+    """A Filter of FILTER_RAW sections from rows of b0 b1 b2 a1 a2, or of scipy's b0 b1 b2 1 a1 a2."""
+    f = Filter()
+    rows = [list(map(float, r)) for r in sos]
+    f.n_sections = len(rows)
+    for i, r in enumerate(rows[:FILTER_MAX_SECTIONS]):
+        if len(r) == 6:
+            if r[3] != 1.0:
+                raise ValueError("raw_filter: a0 must be 1")
+            r = r[:3] + r[4:]
+        sec = f.section[i]
+        sec.kind = FILTER_RAW
+        sec.b0, sec.b1, sec.b2, sec.a1, sec.a2 = r
+    return f
+
+
+def filter_array(filters, n=None):
+    """A (Filter * n) array of Filter entries (None: no sections); one entry stands for all n."""
+    fs = [filters] if isinstance(filters, Filter) or filters is None else list(filters)
+    if n is not None and len(fs) == 1:
+        fs = fs * n
+    arr = (Filter * max(1, len(fs)))()
+    for i, f in enumerate(fs):
+        if f is not None:
+            C.memmove(C.byref(arr[i]), C.byref(f), C.sizeof(Filter))
+    return arr, len(fs)
+
+
 class LoudnessReport(C.Structure):
     """jb_loudness_report: what a run measured and applied for one utterance."""
     _fields_ = [("lufs", C.c_double), ("sample_peak_dbfs", C.c_double), ("true_peak_dbtp", C.c_double),
@@ -327,6 +412,8 @@ SYMBOLS = [
     "jb_batch_member_start", "jb_batch_read_programme_pcm", "jb_batch_read_programme_pcm_i16",
     "jb_join_ms_to_samples", "jb_join_geometry", "jb_join_host", "jb_join_i16_host", "jb_join_pcm_batch",
     "jb_join_pcm_batch_i16", "jb_join_free",
+    "jb_batch_set_filter", "jb_batch_filter_coefficients", "jb_filter_design", "jb_filter_pcm_host",
+    "jb_filter_pcm_batch", "jb_filter_pcm_batch_i16", "jb_filter_free", "jb_engine_set_filter", "jb_engine_get_filter",
     "jb_synthesize_programme", "jb_synthesize_programme_i16", "jb_synthesize_programme_flac_meta",
     "jb_synthesize_programme_formatted", "jb_synthesize_programme_adpcm",
 ]
@@ -569,6 +656,18 @@ def lib():
     L.jb_join_pcm_batch_i16.argtypes = L.jb_join_pcm_batch.argtypes
     L.jb_join_free.argtypes = [vp]
     L.jb_join_free.restype = None
+    flp, bqp = C.POINTER(Filter), C.POINTER(Biquad)
+    L.jb_batch_set_filter.argtypes = [vp, flp, sz]
+    L.jb_batch_filter_coefficients.argtypes = [vp, sz, bqp, u32p]
+    L.jb_filter_design.argtypes = [flp, C.c_uint32, bqp]
+    L.jb_filter_pcm_host.argtypes = [dp, sz, flp, C.c_uint32, dp, sz]
+    L.jb_filter_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, flp, u32p, C.c_int32, C.POINTER(vp),
+                                      C.POINTER(sz)]
+    L.jb_filter_pcm_batch_i16.argtypes = L.jb_filter_pcm_batch.argtypes
+    L.jb_filter_free.argtypes = [vp]
+    L.jb_filter_free.restype = None
+    L.jb_engine_set_filter.argtypes = [vp, flp]
+    L.jb_engine_get_filter.argtypes = [vp, flp]
     lines, szp = C.POINTER(C.c_char_p), C.POINTER(sz)
     L.jb_synthesize_programme.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
     L.jb_synthesize_programme_i16.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
@@ -994,6 +1093,65 @@ def join_pcm(pcms, req, device: int = -1):
         else:
             res.append(np.zeros(0, dtype=np.int16 if i16 else np.float64))
         L.jb_join_free(outs[p])
+    return res
+
+
+def _biquads(arr, n):
+    import numpy as np
+    return np.array([[arr[i].b0, arr[i].b1, arr[i].b2, arr[i].a1, arr[i].a2] for i in range(n)],
+                    dtype=np.float64).reshape(n, 5)
+
+
+def filter_design(f, hz: int):
+    """jb_filter_design: the coefficients [n_sections, 5] (b0 b1 b2 a1 a2, a0 = 1) of Filter `f` at `hz`."""
+    out = (Biquad * FILTER_MAX_SECTIONS)()
+    check(lib().jb_filter_design(C.byref(f), int(hz), out))
+    return _biquads(out, f.n_sections)
+
+
+def filter_sos(f, hz: int):
+    """The same as rows of b0 b1 b2 1 a1 a2, as scipy.signal takes them."""
+    import numpy as np
+    c = filter_design(f, hz)
+    return np.concatenate([c[:, :3], np.ones((c.shape[0], 1)), c[:, 3:]], axis=1)
+
+
+def filter_pcm_host(pcm, f, hz: int):
+    """jb_filter_pcm_host: the serial recursion on the host (no GPU), f64 in and out."""
+    import numpy as np
+    x = np.ascontiguousarray(pcm, dtype=np.float64)
+    y = np.empty_like(x)
+    dp = C.POINTER(C.c_double)
+    check(lib().jb_filter_pcm_host(x.ctypes.data_as(dp), x.size, C.byref(f if f is not None else Filter()), int(hz),
+                                   y.ctypes.data_as(dp), y.size))
+    return y
+
+
+def filter_pcm(pcms, filters, hz, device: int = -1, i16: bool = False):
+    """jb_filter_pcm_batch / _i16: the f64 utterances `pcms` filtered on the GPU, utterance u under filters[u] (a
+    Filter, or None) at hz[u]; one Filter or one rate stands for all.  f64 out, or int16 by the 16-bit sink's rule."""
+    import numpy as np
+    L = lib()
+    arrs = [np.ascontiguousarray(p, dtype=np.float64) for p in pcms]
+    n = len(arrs)
+    farr, nf = filter_array(filters, n)
+    if nf != n:
+        raise ValueError("filter_pcm: one filter, or one per utterance")
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("filter_pcm: one rate, or one per utterance")
+    ins = (C.c_void_p * max(1, n))(*[a.ctypes.data for a in arrs])
+    nin = (C.c_size_t * max(1, n))(*[a.size for a in arrs])
+    hzs = (C.c_uint32 * max(1, n))(*rates)
+    outs = (C.c_void_p * max(1, n))()
+    ns = (C.c_size_t * max(1, n))()
+    check((L.jb_filter_pcm_batch_i16 if i16 else L.jb_filter_pcm_batch)(ins, nin, n, farr, hzs, device, outs, ns))
+    res = []
+    for u in range(n):
+        ct = C.c_int16 if i16 else C.c_double
+        buf = C.cast(outs[u], C.POINTER(ct))
+        res.append(np.ctypeslib.as_array(buf, shape=(max(int(ns[u]), 1),))[:int(ns[u])].copy())
+        L.jb_filter_free(outs[u])
     return res
 
 

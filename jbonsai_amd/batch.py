@@ -364,6 +364,24 @@ class Batch:
         arr = (C.c_uint32 * max(1, len(rates)))(*rates)
         F.check(self._L.jb_batch_set_output_rate(self._h, arr, len(rates)))
 
+    def set_filter(self, filters):
+        """jb_batch_set_filter: one F.Filter for the whole batch or one per utterance (None in a list: no sections);
+        None withdraws the request.  Before the first run only.  The stage runs behind the output rate and in front of
+        the loudness target; pcm_native stays the unfiltered vocoder PCM."""
+        if filters is None:
+            F.check(self._L.jb_batch_set_filter(self._h, None, 0))
+            return
+        arr, n = F.filter_array(filters)
+        F.check(self._L.jb_batch_set_filter(self._h, arr, n))
+
+    def filter_coefficients(self, i) -> np.ndarray:
+        """jb_batch_filter_coefficients: [n_sections, 5] (b0 b1 b2 a1 a2) of what the device runs for utterance i at
+        its output rate; [0, 5] without a filter."""
+        out = (F.Biquad * F.FILTER_MAX_SECTIONS)()
+        n = C.c_uint32()
+        F.check(self._L.jb_batch_filter_coefficients(self._h, i, out, C.byref(n)))
+        return F._biquads(out, n.value)
+
     def set_loudness_target(self, target_lufs, ceiling_dbfs=float("inf")):
         """jb_batch_set_loudness_target: one target (float) for the whole batch or one per utterance (NaN: measured,
         gain 0 dB unless above the ceiling).  Before the first run only.  The PCM reads then hand out x * gain."""

@@ -2508,6 +2508,19 @@ int jb_batch_set_output_rate(jb_batch *hb, const uint32_t *out_hz, size_t n)
     return hb ? ((Batch *)hb)->out.set_output_rate(out_hz, n) : JB_ERR_INVALID;
 }
 
+int jb_batch_set_filter(jb_batch *hb, const jb_filter *f, size_t n)
+{
+    return hb ? ((Batch *)hb)->out.set_filter(f, n) : JB_ERR_INVALID;
+}
+
+int jb_batch_filter_coefficients(const jb_batch *hb, size_t utt, jb_biquad out[JB_FILTER_MAX_SECTIONS], uint32_t *n)
+{
+    const Batch *b = (const Batch *)hb;
+    if (!b || !out || !n || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    return b->out.filter_coefficients(utt, out, n);
+}
+
 uint32_t jb_batch_output_rate(const jb_batch *hb, size_t i)
 {
     const Batch *b = (const Batch *)hb;

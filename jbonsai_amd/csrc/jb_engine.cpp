@@ -51,6 +51,7 @@ struct Condition {
     double peak_ceiling = 0.0;    // jb_engine_set_peak_ceiling (dBFS), with a target only
     uint32_t peak_mode = JB_PEAK_SAMPLE; // jb_engine_set_peak_mode: what the ceiling bounds, with a target only
     uint32_t loudness_scope = JB_LOUDNESS_PER_UTTERANCE; // jb_engine_set_loudness_scope: what one gain covers
+    jb_filter filter{};           // jb_engine_set_filter: n_sections 0 = off
     uint32_t tree_search = JB_SEARCH_HOST; // jb_engine_set_tree_search: where the per-label tree search runs
     double speed = 1.0;
     size_t stage = 0;
@@ -1091,6 +1092,29 @@ int jb_engine_set_peak_ceiling(jb_engine *e, double dbfs)
     return JB_OK;
 }
 double jb_engine_get_peak_ceiling(const jb_engine *e) { return e ? CENG(e)->cond.peak_ceiling : NAN; }
+int jb_engine_set_filter(jb_engine *e, const jb_filter *f)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    if (!f) {
+        ENG(e)->cond.filter = jb_filter{};
+        return JB_OK;
+    }
+    const jb::Condition &c = CENG(e)->cond;
+    const size_t hz = c.output_rate ? c.output_rate : c.sampling_frequency;
+    int rc = jb::filter_design_checked(f, (uint32_t)hz, 0, nullptr, "jb_engine_set_filter");
+    if (rc)
+        return rc;
+    ENG(e)->cond.filter = *f;
+    return JB_OK;
+}
+int jb_engine_get_filter(const jb_engine *e, jb_filter *out)
+{
+    if (!e || !out)
+        return JB_ERR_INVALID;
+    *out = CENG(e)->cond.filter;
+    return JB_OK;
+}
 int jb_engine_set_peak_mode(jb_engine *e, uint32_t mode)
 {
     if (!e || (mode != JB_PEAK_SAMPLE && mode != JB_PEAK_TRUE))
@@ -1591,6 +1615,15 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
             any_target = any_target || on;
             any_true = any_true || modes[u - lo] == JB_PEAK_TRUE;
         }
+        // the filter: each utterance's engine's own (a batch whose engines all have none filters nothing)
+        std::vector<jb_filter> filters(hi - lo);
+        bool any_filter = false;
+        for (size_t u = lo; u < hi; u++) {
+            filters[u - lo] = eng(u)->cond.filter;
+            any_filter = any_filter || filters[u - lo].n_sections;
+        }
+        if (any_filter && (rc = b->out.set_filter(filters.data(), filters.size())))
+            return rc;
         if (any_target && (rc = b->out.set_loudness(targets.data(), ceilings.data(), targets.size())))
             return rc;
         if (any_true && (rc = b->out.set_peak_mode(modes.data(), modes.size())))
@@ -2155,6 +2188,8 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
         g->L = b->out.utt(0).L;
         g->M = b->out.utt(0).M;
     }
+    if (CENG(e)->cond.filter.n_sections && (rc = b->out.set_filter(&CENG(e)->cond.filter, 1)))
+        return rc;
     if (!std::isnan(CENG(e)->cond.loudness_target)) {
         const double t = CENG(e)->cond.loudness_target, c = CENG(e)->cond.peak_ceiling;
         const uint32_t mode = CENG(e)->cond.peak_mode;
@@ -2164,7 +2199,7 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     // Engine::generator runs all three MLPGs before returning (src/engine.rs:333-357); here they are
     // enqueued, with the vocoder behind them, and the call returns while the device works
     // (no serially served head with an output rate either: the converted samples of a frame need its successors)
-    // (nor with a loudness target: the gain needs every sample)
+    // (nor with a loudness target: the gain needs every sample; nor with a filter: the chain rewrites the PCM)
     if ((!b->invariant && !b->out.active() && (rc = b->build_generator_work())) || (rc = b->run(false)))
         return rc;
     *out = (jb_generator *)g.release();

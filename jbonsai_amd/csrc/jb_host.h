@@ -3,6 +3,7 @@
 #include "../../include/jbonsai_amd.h"
 #include "jb_device.h"
 #include "jb_adpcm.h"
+#include "jb_filter.h"
 #include "jb_format.h"
 #include "jb_loudness_rules.h"
 #include "jb_md5.h"
@@ -272,6 +273,29 @@ void join_lists(const JoinLayout &lay, const JoinUtt *req, const uint64_t *n, co
 hipError_t launch_join(bool i16, const JoinSpan *spans_dev, uint32_t n, uint64_t tiles, const JoinMember *members_dev,
                        hipStream_t stream);
 
+// The filter stage (jb_filter.hip; the rules, FilterClass and FilterUtt: jb_filter.h; the host half: jb_filter.cpp)
+// f at `hz`: its coefficients into c ([n_sections][5], may be null), or JB_ERR_INVALID with set_error naming the
+// utterance `utt`, the section and the field
+int filter_design_checked(const jb_filter *f, uint32_t hz, size_t utt, double *c, const char *who);
+void filter_class_build(const double *c, uint32_t ns, FilterClass *out); // the device table of designed coefficients
+// The distinct (filter, rate) pairs of f[0..nf) (nf == 1: one filter for all) over hz[0..B): their tables and each
+// utterance's class; every utterance without sections shares one identity class
+int filter_classes(const jb_filter *f, size_t nf, const uint32_t *hz, size_t B, std::vector<FilterClass> *classes,
+                   std::vector<uint32_t> *cls_of, const char *who);
+// A launch list: the utterances `only` marks (null: all) sorted by their classes' section count, t0 filled in;
+// count[ns] / tiles[ns]: the utterances and tiles of each count
+struct FilterLaunch {
+    std::vector<FilterUtt> utts;
+    uint32_t count[kFiltMaxSections + 1] = {};
+    uint64_t tiles[kFiltMaxSections + 1] = {};
+};
+int filter_launch_list(const std::vector<FilterClass> &classes, const std::vector<FilterUtt> &utts,
+                       const std::vector<uint8_t> *only, FilterLaunch *out);
+// utts_dev: a launch list on the device; st: kFiltMaxD doubles per tile of the batch; per section count present the
+// three launches (zero-state tiles, the utterance scan, the tiles again from their start states), a copy for count 0
+hipError_t launch_filter(const FilterClass *classes_dev, const FilterUtt *utts_dev, const FilterLaunch &l, double *st,
+                         bool i16, hipStream_t stream);
+
 // Device-resident pdf tables of a voice set (jb_pdf_set) and an indexed batch source
 struct PdfSet {
     int device = -1;
@@ -334,8 +358,8 @@ struct DeviceScratch {
 };
 
 struct Batch;
-// The stages behind the vocoder of one batch -- output rate (jb_batch_set_output_rate), loudness target
-// (jb_batch_set_loudness_target), FLAC (jb_batch_set_flac), sample format (jb_batch_set_format), IMA ADPCM
+// The stages behind the vocoder of one batch -- output rate (jb_batch_set_output_rate), filter (jb_batch_set_filter),
+// loudness target (jb_batch_set_loudness_target), FLAC (jb_batch_set_flac), sample format (jb_batch_set_format), IMA ADPCM
 // (jb_batch_set_adpcm) -- and all their
 // device state.  The setters record a
 // request and plan again (jb_output.h); the first run carries the plan out (prepare); every run enqueues the chain
@@ -358,6 +382,11 @@ struct OutputChain {
     // req[u]: utterance u's programme, pads and fades, n == B (nullptr, 0: the request is withdrawn); this setter and
     // set_output_rate check that a programme's members agree on the rate
     int set_join(const jb_join_utt *req, size_t n);
+    // f[0..n): n == 1 or B filters (nullptr, 0: the request is withdrawn), each checked at its utterance's output
+    // rate; set_output_rate checks the combined request again
+    int set_filter(const jb_filter *f, size_t n);
+    // the coefficients the device runs for utterance u at its output rate (*n = 0 without a filter)
+    int filter_coefficients(size_t u, jb_biquad *out, uint32_t *n) const;
     void init();   // Batch::create: the slabs the batch was made with, the plan of no request
     int prepare(); // at the first run: every slab, table and list of the plan; points the vocoder at its slab
     // only: [B] 1 = the utterances a redo rewrote: their part of every stage again (the FLAC pack: every stream),
@@ -419,6 +448,8 @@ private:
     bool ad_on = false;                        // IMA ADPCM is requested
     uint32_t ad_align = 0;                     // its block_align (0: by the rate)
     std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
+    std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
+    std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
     std::vector<double> ln_target, ln_ceiling; // [B]
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
     std::vector<uint32_t> ln_group_req;        // [B] the caller's ids; empty: no group request
@@ -464,6 +495,14 @@ private:
         uint64_t *foff = nullptr, *total = nullptr;
         FlacOut *res = nullptr;
     } fl;
+    struct { // filter
+        std::vector<FilterClass> classes;
+        std::vector<FilterUtt> utts; // [B] by utterance index
+        FilterLaunch all;            // the launch list of a run
+        FilterClass *classes_dev = nullptr;
+        FilterUtt *utts_dev = nullptr, *redo_dev = nullptr;
+        double *st = nullptr;        // kFiltMaxD doubles per tile
+    } fil;
     struct { // sample format
         std::vector<FormatUtt> utts;
         FormatUtt *utts_dev = nullptr, *redo_dev = nullptr;
@@ -490,6 +529,8 @@ private:
     std::vector<EncUnit> enc_units() const;
     int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
     int prepare_join();
+    int check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const;
+    int prepare_filter();
     void replan(); // host geometry and routing of the present requests
     // the group request `group` ([B], empty: none) against these targets, modes and rates: JB_ERR_INVALID naming the
     // group and the field where members would disagree; *out (may be null) gets the plan

@@ -42,14 +42,24 @@ OutPlan plan_output(const OutPlanIn &in)
     // Every stage but the last writes f64 (the converter and the measurement read f64); the last one writes what the
     // flags asked for.  A 16-bit output goes to the slab the batch was created with where it fits
     const OutSlab out16 = p.total <= p.native_total ? OutSlab::S16 : OutSlab::New16;
-    if (in.i16 && !p.convert && !in.loudness)
+    // (a request whose utterances all have no section is no request: every field as without one)
+    bool filt = false;
+    for (size_t u = 0; in.filter && u < in.B; u++)
+        filt = filt || in.filter[u];
+    if (in.i16 && !p.convert && !in.loudness && !filt)
         p.vocoder = {OutSlab::S16, true};
     else
         p.vocoder = {in.i16 ? OutSlab::Voc64 : OutSlab::V64, false};
     p.final = p.vocoder;
     if (p.convert) {
-        p.converter = (in.i16 && !in.loudness) ? OutWrite{out16, true} : OutWrite{OutSlab::Conv64, false};
+        p.converter = (in.i16 && !in.loudness && !filt) ? OutWrite{out16, true} : OutWrite{OutSlab::Conv64, false};
         p.final = p.converter;
+    }
+    // the filter behind the converter and in front of the measurement: f64 in; the last stage's rule out
+    if (filt) {
+        p.filter_src = p.final.slab;
+        p.filter = (in.i16 && !in.loudness) ? OutWrite{out16, true} : OutWrite{OutSlab::Filt64, false};
+        p.final = p.filter;
     }
     if (in.loudness) {
         p.measure = p.final.slab;
@@ -58,7 +68,7 @@ OutPlan plan_output(const OutPlanIn &in)
     }
     p.native64 = p.vocoder.i16 ? OutSlab::None : p.vocoder.slab;
     p.flac = (in.flac && p.final.i16) ? p.final.slab : OutSlab::None;
-    for (const OutWrite &w : {p.vocoder, p.converter, p.apply})
+    for (const OutWrite &w : {p.vocoder, p.converter, p.filter, p.apply})
         if (w.slab != OutSlab::None && w.slab != OutSlab::V64 && w.slab != OutSlab::S16)
             p.alloc[(size_t)w.slab] = std::max<uint64_t>(w.slab == OutSlab::Voc64 ? p.native_total : p.total, 1);
     // the join behind all of them: the final PCM gathered into programmes in a slab of its own, which the encoders

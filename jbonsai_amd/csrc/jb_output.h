@@ -1,6 +1,7 @@
 #pragma once
 // jb_output.h -- the routing of the stages behind the vocoder (output rate, loudness, FLAC): which slab each stage
 // reads and writes, in f64 or in 16 bits, which slab the read entries hand out, and each utterance's output geometry,
+// with a filter request the stage between the converter and the measurement,
 // decided from the batch's shape and the requests alone (plan_output, jb_output.cpp); with a sample format, the f64
 // slab the format stage reads and each utterance's place in its byte slab; with an IMA ADPCM request, the slab that
 // stage reads (f64 or 16-bit) and each utterance's blocks in its byte slab; with a join request (jb_join.h), the
@@ -29,6 +30,7 @@ enum class OutSlab : uint8_t {
     Adpcm,   // IMA ADPCM blocks
     Join64,  // f64 the join stage writes: the programmes
     Join16,  // the same in 16 bits
+    Filt64,  // f64 the filter stage writes
     Count
 };
 constexpr size_t out_slab_elem(OutSlab s) // bytes
@@ -55,6 +57,7 @@ struct OutPlanIn {
     bool adpcm = false;                   // IMA ADPCM is requested
     uint32_t adpcm_align = 0;             // its block_align: 0 = by each utterance's output rate (jb_adpcm.h)
     const JoinUtt *join = nullptr;        // [B] the join request (jb_join.h); nullptr: none
+    const uint8_t *filter = nullptr;      // [B] 1 = the utterance's filter has at least one section; nullptr: no request
 };
 
 struct OutUtt {
@@ -87,6 +90,11 @@ struct OutPlan {
     uint64_t native_total = 0;
     bool convert = false;     // some utterance is not native; the native ones then go through the identity table
     OutWrite vocoder, converter, apply;
+    // The filter stage (jb_filter.h): behind the converter (or the vocoder), in front of the measurement; it reads the
+    // f64 of the stage in front (filter_src) and every stage behind it reads what it writes.  None: no utterance of
+    // the request has a section
+    OutWrite filter;
+    OutSlab filter_src = OutSlab::None;
     OutSlab measure = OutSlab::None;  // f64 the loudness measurement reads (never scaled in place)
     OutSlab flac = OutSlab::None;     // 16 bits FLAC encodes: the slab handed out
     OutWrite final;                   // what the PCM read entries hand out
@@ -104,7 +112,8 @@ struct OutPlan {
     std::vector<uint32_t> prog_first, prog_members; // programme p owns prog_members[prog_first[p] .. prog_first[p + 1])
     uint64_t alloc[(size_t)OutSlab::Count] = {}; // elements to allocate of each slab, at least 1 (0: none; V64 / S16 exist)
     bool normalize() const { return apply.slab != OutSlab::None; }
-    bool active() const { return convert || normalize(); } // a stage rewrites the PCM behind the vocoder
+    bool filtered() const { return filter.slab != OutSlab::None; }
+    bool active() const { return convert || normalize() || filtered(); } // a stage rewrites the PCM behind the vocoder
 };
 
 // Pure: no globals, no environment.

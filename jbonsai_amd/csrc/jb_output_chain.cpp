@@ -1,6 +1,6 @@
 // jb_output_chain.cpp -- OutputChain (jb_host.h): the stages behind the vocoder of one batch.  The setters record a
 // request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() launches
-// k_resample, the loudness measurement and apply pass, the join, the FLAC encoder and pack, the sample format and IMA
+// k_resample, the filter, the loudness measurement and apply pass, the join, the FLAC encoder and pack, the sample format and IMA
 // ADPCM, in that order, on the vocoder's stream.
 #include "jb_host.h"
 
@@ -38,6 +38,7 @@ void OutputChain::replan()
     in.adpcm = ad_on;
     in.adpcm_align = ad_align;
     in.join = join_req.empty() ? nullptr : join_req.data();
+    in.filter = filt_any.empty() ? nullptr : filt_any.data();
     plan = plan_output(in);
 }
 
@@ -73,7 +74,8 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
             return rc;
     }
     if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)) ||
-        (rc = check_join(join_req, want, "jb_batch_set_output_rate")))
+        (rc = check_join(join_req, want, "jb_batch_set_output_rate")) ||
+        (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")))
         return rc;
     want_hz = std::move(want);
     replan();
@@ -307,6 +309,103 @@ int OutputChain::set_join(const jb_join_utt *req, size_t n)
     return JB_OK;
 }
 
+// The filter request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming the utterance, the section
+// and the field
+int OutputChain::check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const
+{
+    int rc;
+    for (size_t u = 0; u < req.size(); u++) {
+        const uint32_t hz = (u < want.size() && want[u]) ? want[u] : b.voice.sampling_frequency;
+        if ((rc = filter_design_checked(&req[u], hz, u, nullptr, who)))
+            return rc;
+    }
+    return JB_OK;
+}
+
+int OutputChain::set_filter(const jb_filter *f, size_t n)
+{
+    int rc = check_settable("jb_batch_set_filter: the filter is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!f && n == 0) {
+        filt_req.clear();
+        filt_any.clear();
+        replan();
+        return JB_OK;
+    }
+    if (!f || (n != 1 && n != (size_t)b.B)) {
+        set_error("jb_batch_set_filter: give one filter, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    std::vector<jb_filter> r((size_t)b.B);
+    for (size_t u = 0; u < r.size(); u++)
+        r[u] = f[n == 1 ? 0 : u];
+    if ((rc = check_filter(r, want_hz, "jb_batch_set_filter")))
+        return rc;
+    filt_any.assign(r.size(), 0);
+    for (size_t u = 0; u < r.size(); u++)
+        filt_any[u] = r[u].n_sections != 0;
+    filt_req = std::move(r);
+    replan();
+    return JB_OK;
+}
+
+int OutputChain::filter_coefficients(size_t u, jb_biquad *out, uint32_t *n) const
+{
+    *n = 0;
+    if (!plan.filtered() || u >= filt_req.size())
+        return JB_OK;
+    double c[kFiltMaxSections * kFiltCoefs] = {};
+    int rc = filter_design_checked(&filt_req[u], plan.utt[u].hz, u, c, "jb_batch_filter_coefficients");
+    if (rc)
+        return rc;
+    *n = filt_req[u].n_sections;
+    std::copy(c, c + *n * kFiltCoefs, (double *)out);
+    return JB_OK;
+}
+
+// The classes (one table per distinct filter and rate; utterances without sections share the identity), the
+// utterance list sorted by section count and the per-tile state scratch: the f64 of the stage in front in, the
+// filter's slab out
+int OutputChain::prepare_filter()
+{
+    if (!plan.filtered())
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    const double *src = (const double *)slab[(size_t)plan.filter_src];
+    char *dst = (char *)slab[(size_t)plan.filter.slab];
+    const size_t elem = plan.filter.i16 ? sizeof(int16_t) : sizeof(double);
+    std::vector<uint32_t> hz(B), cls_of;
+    for (size_t u = 0; u < B; u++)
+        hz[u] = plan.utt[u].hz;
+    int rc = filter_classes(filt_req.data(), B, hz.data(), B, &fil.classes, &cls_of, "jb_batch_set_filter");
+    if (rc)
+        return rc;
+    fil.utts.assign(B, FilterUtt{});
+    uint64_t tiles = 0;
+    for (size_t u = 0; u < B; u++) {
+        const OutUtt &o = plan.utt[u];
+        if (filter_tiles(o.n) > kFiltMaxTiles) {
+            set_error("filter: utterance " + std::to_string(u) + " is too long");
+            return JB_ERR_UNSUPPORTED;
+        }
+        fil.utts[u] = {src + o.off, dst + o.off * elem, o.n, tiles, 0, (uint32_t)filter_tiles(o.n), cls_of[u]};
+        tiles += fil.utts[u].ntiles;
+    }
+    if ((rc = filter_launch_list(fil.classes, fil.utts, nullptr, &fil.all)))
+        return rc;
+    if ((rc = b.dalloc(&fil.classes_dev, fil.classes.size(), false)) || (rc = b.dalloc(&fil.utts_dev, B, false)) ||
+        (rc = b.dalloc(&fil.redo_dev, B, false)) || (rc = b.dalloc(&fil.st, (size_t)tiles * kFiltMaxD, false)))
+        return rc;
+    hipError_t e;
+    if ((!fil.classes.empty() && (e = hipMemcpy(fil.classes_dev, fil.classes.data(), sizeof(FilterClass) * fil.classes.size(),
+                                               hipMemcpyHostToDevice)) != hipSuccess) ||
+        (B > 0 && (e = hipMemcpy(fil.utts_dev, fil.all.utts.data(), sizeof(FilterUtt) * B, hipMemcpyHostToDevice)) !=
+                      hipSuccess))
+        return hip_fail(e, "filter work list");
+    return JB_OK;
+}
+
 // At the first run (a second one, or the step done again behind a resident-GV formation timeout, finds it done).
 // The vocoder is pointed at its slab last: a failure leaves the batch as it was created, its blocks the batch's own
 int OutputChain::prepare()
@@ -318,7 +417,7 @@ int OutputChain::prepare()
     for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
-    if ((rc = prepare_resample()) || (rc = prepare_loudness()) || (rc = prepare_join()) || (rc = prepare_flac()) ||
+    if ((rc = prepare_resample()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_join()) || (rc = prepare_flac()) ||
         (rc = prepare_format()) || (rc = prepare_adpcm()))
         return rc;
     if (plan.active()) {
@@ -664,6 +763,10 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const JoinSpan *jspans = jn.spans_dev;
     uint32_t n_jspans = joined() ? U : 0;
     uint64_t jt = jn.tiles;
+    const bool filt = plan.filtered();
+    FilterLaunch flt_sub;
+    const FilterLaunch *flt = &fil.all;
+    const FilterUtt *flt_utts = fil.utts_dev;
     hipError_t e = hipSuccess;
     if (only && grouped) {
         loudness_groups_closure(ln_groups, *only, &touched_groups, &group_members);
@@ -686,6 +789,14 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         std::vector<LoudnessUtt> ap_sub; // grouped: the apply pass's own list
         std::vector<LoudnessSet> set_sub;
         std::vector<JoinSpan> jn_sub;
+        // a recursive filter carries a changed sample to the utterance's end: every touched utterance whole
+        if (filt) {
+            int rc = filter_launch_list(fil.classes, fil.utts, only, &flt_sub);
+            if (rc)
+                return rc;
+            flt = &flt_sub;
+            flt_utts = fil.redo_dev;
+        }
         lt = at = ft = ag = jt = 0;
         uint64_t mat = 0; // apply tiles of the measured list (its at0 is not read when the apply pass has its own)
         for (size_t u = 0; u < B; u++) {
@@ -772,9 +883,12 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         n_work = (uint32_t)fl_sub.size();
         jspans = jn.redo_dev;
         n_jspans = (uint32_t)jn_sub.size();
-        if (!n_tiles && !n_utts && !n_work && !n_futts && !n_autts && !n_apply && !n_jspans)
+        if (!n_tiles && !n_utts && !n_work && !n_futts && !n_autts && !n_apply && !n_jspans && flt_sub.utts.empty())
             return JB_OK;
-        if ((n_tiles && (e = hipMemcpy(rs.redo_dev, rs_sub.data(), sizeof(ResampleTile) * n_tiles,
+        if ((!flt_sub.utts.empty() && (e = hipMemcpy(fil.redo_dev, flt_sub.utts.data(),
+                                                     sizeof(FilterUtt) * flt_sub.utts.size(), hipMemcpyHostToDevice)) !=
+                                          hipSuccess) ||
+            (n_tiles && (e = hipMemcpy(rs.redo_dev, rs_sub.data(), sizeof(ResampleTile) * n_tiles,
                                        hipMemcpyHostToDevice)) != hipSuccess) ||
             (n_utts && (e = hipMemcpy(ln.redo_dev, ln_sub.data(), sizeof(LoudnessUtt) * n_utts,
                                       hipMemcpyHostToDevice)) != hipSuccess) ||
@@ -798,6 +912,10 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     if (plan.convert && (!only || n_tiles) &&
         (e = launch_resample(rs.tables_dev, tiles, n_tiles, plan.converter.i16, rs.lds, st)) != hipSuccess)
         return hip_fail(e, only ? "k_resample(redo)" : "k_resample");
+    // the filter: behind the converter (its second pass too), in front of the measurement
+    if (filt && (!only || !flt->utts.empty()) &&
+        (e = launch_filter(fil.classes_dev, flt_utts, *flt, fil.st, plan.filter.i16, st)) != hipSuccess)
+        return hip_fail(e, only ? "filter(redo)" : "filter");
     if (plan.normalize() && (!only || n_utts) &&
         ((e = launch_loudness_measure(ln.rates_dev, utts, n_utts, lt, ln.st, ln.pk, ln.tp, ln.z, ln.res, ln.true_peak,
                                       st)) != hipSuccess ||

@@ -156,6 +156,14 @@ class _Condition:
         """What the ceiling bounds: 0 = the sample peak (the default), 1 = the true peak (dBTP)."""
         F.check(self._L().jb_engine_set_peak_mode(self._h(), int(mode)))
     def get_peak_mode(self): return self._L().jb_engine_get_peak_mode(self._h())
+    def set_filter(self, f):
+        """The output filter (an _ffi.Filter: J.highpass(70), J.telephone_band(), ...) of every entry's output, behind
+        the output rate and in front of the loudness target; None (the default) = off."""
+        F.check(self._L().jb_engine_set_filter(self._h(), None if f is None else C.byref(f)))
+    def get_filter(self):
+        f = F.Filter()
+        F.check(self._L().jb_engine_get_filter(self._h(), C.byref(f)))
+        return f
     def set_loudness_scope(self, scope):
         """What one gain of the target covers: 0 = each utterance (the default), 1 = the whole request
         (_ffi.LOUDNESS_PER_UTTERANCE / LOUDNESS_PER_REQUEST): the utterances of one synthesize_batch call keep
@@ -240,6 +248,13 @@ class Engine:
 
     def get_loudness_scope(self):
         return self.condition.get_loudness_scope()
+
+    def set_filter(self, f):
+        """jb_engine_set_filter (the Condition's setter, on the engine): an _ffi.Filter, or None for none."""
+        self.condition.set_filter(f)
+
+    def get_filter(self):
+        return self.condition.get_filter()
 
     def close(self):
         if getattr(self, "_h", None):
