@@ -358,12 +358,49 @@ struct DeviceScratch {
 };
 
 struct Batch;
-// The stages behind the vocoder of one batch -- output rate (jb_batch_set_output_rate), filter (jb_batch_set_filter),
-// loudness target (jb_batch_set_loudness_target), FLAC (jb_batch_set_flac), sample format (jb_batch_set_format), IMA ADPCM
-// (jb_batch_set_adpcm) -- and all their
-// device state.  The setters record a
-// request and plan again (jb_output.h); the first run carries the plan out (prepare); every run enqueues the chain
-// once behind the hand-off check, and finish_verify once more for the utterances its redo rounds rewrote.
+
+// n elements to the device, synchronously (an empty list: nothing)
+template <class T> int upload_list(T *dst, const std::vector<T> &v, const char *what)
+{
+    const hipError_t e =
+        v.empty() ? hipSuccess : hipMemcpy(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+    return e == hipSuccess ? JB_OK : hip_fail(e, what);
+}
+
+// A work list of an output stage: the list of a full run on the host and on the device, a second device block for
+// the list of a redo, and what the next launch takes of the two (take_all / upload_redo)
+template <class T> struct DevList {
+    std::vector<T> host;
+    T *dev = nullptr, *redo = nullptr;
+    const T *list = nullptr; // of the next launch
+    uint32_t n = 0;          // its entries
+    uint64_t total = 0;      // its tiles (or groups of blocks), where the entries number them
+    template <class Alloc> int alloc(Alloc &b, size_t n_dev, size_t n_redo) // (Batch is declared below)
+    {
+        const int rc = b.dalloc(&dev, n_dev, false);
+        return rc ? rc : b.dalloc(&redo, n_redo, false);
+    }
+    int upload(const char *what) { return upload_list(dev, host, what); }
+    int take_all(uint64_t all = 0) // JB_OK
+    {
+        list = dev, n = (uint32_t)host.size(), total = all;
+        return JB_OK;
+    }
+    int upload_redo(const std::vector<T> &v, const char *what, uint64_t of_v = 0)
+    {
+        list = redo, n = (uint32_t)v.size(), total = of_v;
+        return upload_list(redo, v, what);
+    }
+};
+
+// The stages behind the vocoder of one batch, in their order -- the converter (jb_batch_set_output_rate), the filter
+// (jb_batch_set_filter), loudness (jb_batch_set_loudness_target, with peak mode, groups and the R128 report), the
+// join (jb_batch_set_join), then the encoders of the final PCM side by side: FLAC (jb_batch_set_flac, _flac_meta),
+// the sample format (jb_batch_set_format) and IMA ADPCM (jb_batch_set_adpcm) -- and all their device state.
+// The setters record a request and plan again (jb_output.h); the first run carries the plan out (prepare); every run
+// enqueues the chain once behind the hand-off check, and finish_verify once more for the utterances its redo rounds
+// rewrote.  Each stage has the same three steps: prepare_X (its lists and scratch), select_X (what the next launch
+// takes: the run's lists, or those of a redo by the one mask of the RedoScope the stage follows) and launch_X.
 // Without a request the chain holds no device memory and enqueues nothing
 struct OutputChain {
     explicit OutputChain(Batch &batch) : b(batch) {}
@@ -459,93 +496,102 @@ private:
     FlacMeta flac_m{}; // MD5 / SEEKTABLE request (zeros: none)
     bool frozen = false, ready = false; // the first run has begun: no more requests / its prepare() succeeded
     void *slab[(size_t)OutSlab::Count] = {};
-    struct { // converter
+    struct Converter { // follows `measured`
         ResampleTable *tables_dev = nullptr;
-        std::vector<ResampleTile> tiles; // sorted by utterance: utterance u owns [tile_lo[u], tile_lo[u + 1])
+        DevList<ResampleTile> tiles; // sorted by utterance: utterance u owns [tile_lo[u], tile_lo[u + 1])
         std::vector<uint32_t> tile_lo;
-        ResampleTile *tiles_dev = nullptr, *redo_dev = nullptr;
-        size_t lds = 0;                  // dynamic LDS of its launches
+        size_t lds = 0;              // dynamic LDS of its launches
     } rs;
-    struct { // loudness
-        std::vector<LoudnessUtt> utts;
-        LoudnessUtt *utts_dev = nullptr, *redo_dev = nullptr;
+    struct Filter { // follows `measured`
+        std::vector<FilterClass> classes;
+        DevList<FilterUtt> utts;             // host: [B] by utterance index; on the device: a launch list
+        FilterLaunch all, sub;               // the launch list of a run, of the last redo
+        const FilterLaunch *take = nullptr;  // of the next launch
+        FilterClass *classes_dev = nullptr;
+        double *st = nullptr;                // kFiltMaxD doubles per tile
+    } fil;
+    struct Loudness { // measurement and an utterance's report set: `measured`; the apply pass with groups: `post`
+        DevList<LoudnessUtt> utts;             // [B]; total: the measurement's tiles
+        DevList<LoudnessUtt> apply;            // what the apply pass takes: `utts`, or on a redo with groups a list
+                                               // of its own (only `redo` is a block of its own); total: its tiles
+        std::vector<uint64_t> ntiles, natiles; // [B] each utterance's measurement and apply tiles
         LoudnessRate *rates_dev = nullptr;
         double *st = nullptr, *pk = nullptr, *tp = nullptr, *z = nullptr;
         LoudnessResult *res = nullptr;
-        uint64_t tiles = 0, atiles = 0;
-        bool true_peak = false; // some utterance is in JB_PEAK_TRUE mode
+        uint64_t tiles = 0, atiles = 0; // of the batch
+        bool true_peak = false;         // some utterance is in JB_PEAK_TRUE mode
         // with a group or a report request only
-        std::vector<LoudnessSet> sets;  // [B] the utterances, then [G] the groups
-        LoudnessSet *sets_dev = nullptr, *sets_redo_dev = nullptr;
-        LoudnessUtt *apply_redo_dev = nullptr; // grouped: a redo applies to every member of a touched group
+        DevList<LoudnessSet> sets;       // [B] the utterances, then [G] the groups (a redo: the measured, the touched)
+        uint32_t n_usets = 0;            // the utterances' sets of the next launch: the groups' follow them
         uint32_t *members_dev = nullptr; // [B] the identity, then [B] the groups' members
         LoudnessGroupResult *gres = nullptr; // [G]
         double *sw = nullptr, *mm = nullptr; // the report's windows (per tile slot) and momentary maxima (per utterance)
         LoudnessRange *r128 = nullptr;       // [B + G]
     } ln;
-    struct { // FLAC
-        std::vector<FlacWork> work;
+    struct Join { // follows `post`
+        std::vector<JoinMember> members; // in programme order: programme p owns [prog_first[p], prog_first[p + 1])
+        std::vector<uint32_t> member_at; // [B] utterance -> its place in `members`
+        DevList<JoinSpan> spans;         // [P] every programme whole (a redo: one span per member)
+        JoinMember *members_dev = nullptr;
+        uint64_t tiles = 0;
+    } jn;
+    struct Flac { // follows `units`, by work item; the pack takes every stream
+        DevList<FlacWork> work;
+        DevList<uint32_t> md5;     // with an MD5 request: the units in launch order
         std::vector<FlacUtt> utts; // (kept with an MD5 request: the redo's launch list is ordered by their lengths)
         FlacUtt *utts_dev = nullptr;
-        FlacWork *work_dev = nullptr, *redo_dev = nullptr;
-        uint32_t *md5_order_dev = nullptr, *md5_redo_dev = nullptr, *digests = nullptr; // with an MD5 request
-        uint32_t n_md5 = 0, max_points = 0;
+        uint32_t *digests = nullptr; // with an MD5 request
+        uint32_t max_points = 0;
         uint8_t *out = nullptr;
         uint32_t *fsize = nullptr;
         uint64_t *foff = nullptr, *total = nullptr;
         FlacOut *res = nullptr;
     } fl;
-    struct { // filter
-        std::vector<FilterClass> classes;
-        std::vector<FilterUtt> utts; // [B] by utterance index
-        FilterLaunch all;            // the launch list of a run
-        FilterClass *classes_dev = nullptr;
-        FilterUtt *utts_dev = nullptr, *redo_dev = nullptr;
-        double *st = nullptr;        // kFiltMaxD doubles per tile
-    } fil;
-    struct { // sample format
-        std::vector<FormatUtt> utts;
-        FormatUtt *utts_dev = nullptr, *redo_dev = nullptr;
+    struct Format { // follows `units`
+        DevList<FormatUtt> utts;
+        std::vector<uint64_t> ntiles; // [U]
         uint64_t tiles = 0;
     } fm;
-    struct { // IMA ADPCM
-        std::vector<AdpcmUtt> utts;
-        AdpcmUtt *utts_dev = nullptr, *redo_dev = nullptr;
+    struct Adpcm { // follows `units`
+        DevList<AdpcmUtt> utts;
+        std::vector<uint64_t> ngroups; // [U] each unit's groups of kAdpcmLanes blocks
         uint64_t groups = 0;
     } ad;
-    struct { // join
-        std::vector<JoinMember> members; // in programme order: programme p owns [prog_first[p], prog_first[p + 1])
-        std::vector<uint32_t> member_at; // [B] utterance -> its place in `members`
-        std::vector<JoinSpan> spans;     // [P] every programme whole
-        JoinMember *members_dev = nullptr;
-        JoinSpan *spans_dev = nullptr, *redo_dev = nullptr;
-        uint64_t tiles = 0;
-    } jn;
-    // the units the encoders take: the programmes in the join slab, or the utterances in the slab `utt_slab`
+    // the units the encoders take: the programmes in the join slab, or the utterances
     struct EncUnit {
         uint64_t off, n;
         uint32_t hz;
     };
     std::vector<EncUnit> enc_units() const;
-    int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
-    int prepare_join();
-    int check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const;
-    int prepare_filter();
+    bool grouped() const { return plan.normalize() && ln.gres; } // the chain runs loudness groups
+    bool formatted() const { return plan.fmt_src != OutSlab::None; }
+    bool adpcm() const { return plan.adpcm_src.slab != OutSlab::None; }
     void replan(); // host geometry and routing of the present requests
+    // v[0..n), n == 1 or B, as [B] values; false (set_error(err)) for anything else
+    template <class T> bool broadcast(const T *v, size_t n, std::vector<T> *out, const char *err) const;
+    std::vector<uint32_t> rates_under(const std::vector<uint32_t> &want) const; // [B] the output rates a request gives
     // the group request `group` ([B], empty: none) against these targets, modes and rates: JB_ERR_INVALID naming the
     // group and the field where members would disagree; *out (may be null) gets the plan
     int check_groups(const std::vector<uint32_t> &group, const std::vector<double> &target,
                      const std::vector<double> &ceiling, const std::vector<uint32_t> &mode,
                      const std::vector<uint32_t> &want, const char *who, LnGroups *out) const;
+    int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
+    int check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const;
     int check_settable(const char *after_run) const;
-    int prepare_resample();
-    int prepare_loudness();
-    int prepare_flac();
-    int prepare_format();
-    int prepare_adpcm();
+    // the stages, in the order enqueue() runs them.  scope null: a full run
+    int prepare_resample(), select_resample(const RedoScope *scope), launch_resample(bool redo);
+    int prepare_filter(), select_filter(const RedoScope *scope), launch_filter(bool redo);
+    int prepare_loudness(), select_loudness(const RedoScope *scope), launch_loudness(bool redo);
+    int prepare_join(), select_join(const RedoScope *scope), launch_join(bool redo);
+    JoinSpan join_span(size_t p, uint64_t k0, uint64_t k1, uint64_t *tiles) const;
+    int prepare_flac(), select_flac(const RedoScope *scope), launch_flac(bool redo);
+    int prepare_format(), select_format(const RedoScope *scope), launch_format(bool redo);
+    int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);
     int format_ready() const;
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
     int flac_ready() const;
+    // the used bytes of a byte slab in one copy (wait: for the batch first, as Batch::read does)
+    int read_used(const void *src, uint64_t bytes, bool wait, std::unique_ptr<uint8_t[]> *host);
 };
 
 struct Batch {
@@ -655,7 +701,7 @@ struct Batch {
     // the caller has waited for ev_mlpg_done
     int gang_timeout_seen(bool *seen);
     double *gen_pcm = nullptr;       // PCM of the streaming generator's serially served frames (its own buffer)
-    OutputChain out{*this};          // the stages behind the vocoder: output rate, loudness, FLAC
+    OutputChain out{*this};          // the stages behind the vocoder: rate, filter, loudness, join, the encoders
     bool last_run_timed = false;
     uint32_t gang_fallbacks = 0;     // times the resident GV kernel timed out in formation and the sweeps took over
     static int create(const jb_voice_desc *voice, const jb_state_utt *utts, size_t n,

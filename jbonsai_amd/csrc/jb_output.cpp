@@ -245,4 +245,29 @@ void loudness_groups_closure(const LnGroups &g, const std::vector<uint8_t> &touc
         (*members)[u] = (*groups)[g.group_of[u]];
 }
 
+RedoScope redo_scope(const std::vector<uint32_t> &prog_of, size_t P, const LnGroups &groups,
+                     const std::vector<uint8_t> &only)
+{
+    RedoScope s;
+    s.measured = s.post = only;
+    if (groups.size())
+        loudness_groups_closure(groups, only, &s.touched_groups, &s.post);
+    s.units = s.post;
+    if (!prog_of.empty())
+        join_closure(prog_of, P, s.post, &s.units);
+    return s;
+}
+
+Picked pick_renumbered(const std::vector<uint8_t> &mask, const std::vector<uint64_t> &count)
+{
+    Picked p;
+    for (size_t i = 0; i < count.size(); i++)
+        if (mask[i]) {
+            p.index.push_back((uint32_t)i);
+            p.base.push_back(p.total);
+            p.total += count[i];
+        }
+    return p;
+}
+
 } // namespace jb

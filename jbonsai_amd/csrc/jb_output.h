@@ -1,13 +1,13 @@
 #pragma once
-// jb_output.h -- the routing of the stages behind the vocoder (output rate, loudness, FLAC): which slab each stage
-// reads and writes, in f64 or in 16 bits, which slab the read entries hand out, and each utterance's output geometry,
-// with a filter request the stage between the converter and the measurement,
-// decided from the batch's shape and the requests alone (plan_output, jb_output.cpp); with a sample format, the f64
-// slab the format stage reads and each utterance's place in its byte slab; with an IMA ADPCM request, the slab that
-// stage reads (f64 or 16-bit) and each utterance's blocks in its byte slab; with a join request (jb_join.h), the
-// programmes: their numbering, each one's place in the join slab and each member's start, and then the encoders'
-// geometry by programme instead of by utterance.
-// Plain C++17 without HIP: the plan is made and tested on any host; OutputChain (jb_host.h) carries it out.
+// jb_output.h -- the routing of the stages behind the vocoder, in their order: converter (output rate), filter,
+// loudness (measurement, groups, report, apply pass), join, then the encoders side by side: FLAC, sample format, IMA
+// ADPCM.  plan_output (jb_output.cpp) decides from the batch's shape and the requests alone which slab each stage
+// reads and writes, in f64 or in 16 bits, which slab the read entries hand out, each utterance's output geometry and
+// its place in the encoders' byte slabs, and with a join request (jb_join.h) the programmes: their numbering, each
+// one's place in the join slab, each member's start, and the encoders' geometry by programme instead of by utterance.
+// The loudness groups' bookkeeping is here too, and what a redo round runs again: the three masks the stages follow
+// (redo_scope) and the renumbering of the items a mask picks (pick_renumbered).
+// Plain C++17 without HIP: all of it is made and tested on any host; OutputChain (jb_host.h) carries it out.
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
@@ -170,5 +170,28 @@ bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size
 // loudness_groups_closure); programmes: [P] 1 = a programme with such a member
 void join_closure(const std::vector<uint32_t> &prog_of, size_t P, const std::vector<uint8_t> &post,
                   std::vector<uint8_t> *programmes);
+
+// What a redo round runs again, from the utterances it rewrote.  Each stage of the chain follows one of the masks
+struct RedoScope {
+    std::vector<uint8_t> measured;       // [B] = only: converter, filter, measurement, per-utterance report sets
+    std::vector<uint8_t> post;           // [B] the members of every touched group (= only without groups): behind the
+                                         // apply pass a group's gain reaches every member; the join spans
+    std::vector<uint8_t> units;          // [P] the programmes of `post` (= post, [B], without a join): the encoders
+    std::vector<uint8_t> touched_groups; // [G] a group with a member in `only` (empty without groups)
+};
+// Pure: loudness_groups_closure, then join_closure.  prog_of: [B] each utterance's programme of P (empty: no join);
+// groups: the loudness groups the chain runs (empty: none); only: [B] 1 = an utterance the round rewrote
+RedoScope redo_scope(const std::vector<uint32_t> &prog_of, size_t P, const LnGroups &groups,
+                     const std::vector<uint8_t> &only);
+
+// The items a mask picks, renumbered: a redo launch packs their tiles (or groups, or blocks) from 0, while their
+// scratch stays where the full run's numbering put it.  An item of count 0 is picked like any other
+struct Picked {
+    std::vector<uint32_t> index; // the picked items, ascending
+    std::vector<uint64_t> base;  // the sum of the counts of the picked items in front of each
+    uint64_t total = 0;
+};
+// Pure.  mask, count: one entry per item
+Picked pick_renumbered(const std::vector<uint8_t> &mask, const std::vector<uint64_t> &count);
 
 } // namespace jb

@@ -1,7 +1,8 @@
 // jb_output_chain.cpp -- OutputChain (jb_host.h): the stages behind the vocoder of one batch.  The setters record a
-// request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() launches
-// k_resample, the filter, the loudness measurement and apply pass, the join, the FLAC encoder and pack, the sample format and IMA
-// ADPCM, in that order, on the vocoder's stream.
+// request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() selects what each
+// stage takes (everything, or a redo's part: redo_scope, jb_output.h) and launches, in this order and on the
+// vocoder's stream: the converter (k_resample), the filter, loudness (measurement, groups, report, apply pass), the
+// join, then the encoders of the final PCM: FLAC (blocks, MD5, pack), the sample format and IMA ADPCM.
 #include "jb_host.h"
 
 #include <algorithm>
@@ -56,21 +57,40 @@ int OutputChain::check_settable(const char *after_run) const
     return JB_OK;
 }
 
+template <class T> bool OutputChain::broadcast(const T *v, size_t n, std::vector<T> *out, const char *err) const
+{
+    const size_t B = (size_t)b.B;
+    if (!v || (n != 1 && n != B)) {
+        set_error(err);
+        return false;
+    }
+    out->resize(B);
+    for (size_t u = 0; u < B; u++)
+        (*out)[u] = v[n == 1 ? 0 : u];
+    return true;
+}
+
+std::vector<uint32_t> OutputChain::rates_under(const std::vector<uint32_t> &want) const
+{
+    std::vector<uint32_t> hz((size_t)b.B, b.voice.sampling_frequency);
+    for (size_t u = 0; u < want.size(); u++)
+        if (want[u])
+            hz[u] = want[u];
+    return hz;
+}
+
 int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
 {
     int rc = check_settable("jb_batch_set_output_rate: the output rate is set before the batch's first run");
     if (rc)
         return rc;
-    if (!hz || (n != 1 && n != (size_t)b.B)) {
-        set_error("jb_batch_set_output_rate: give one rate, or one per utterance");
+    std::vector<uint32_t> want;
+    if (!broadcast(hz, n, &want, "jb_batch_set_output_rate: give one rate, or one per utterance"))
         return JB_ERR_INVALID;
-    }
     const uint32_t in = b.voice.sampling_frequency;
-    std::vector<uint32_t> want((size_t)b.B);
-    for (size_t u = 0; u < want.size(); u++) {
-        const uint32_t h = hz[n == 1 ? 0 : u];
-        want[u] = h == in ? 0 : h;
-        if (want[u] && (rc = resample_design(in, want[u], nullptr, nullptr)))
+    for (uint32_t &w : want) {
+        w = w == in ? 0 : w;
+        if (w && (rc = resample_design(in, w, nullptr, nullptr)))
             return rc;
     }
     if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)) ||
@@ -89,13 +109,9 @@ int OutputChain::check_groups(const std::vector<uint32_t> &group, const std::vec
 {
     if (group.empty())
         return JB_OK;
-    const size_t B = (size_t)b.B;
-    std::vector<uint32_t> hz(B, b.voice.sampling_frequency);
-    for (size_t u = 0; u < want.size(); u++)
-        if (want[u])
-            hz[u] = want[u];
+    const std::vector<uint32_t> hz = rates_under(want);
     LnGroupsIn in;
-    in.B = B;
+    in.B = hz.size();
     in.group = group.data();
     in.target = target.empty() ? nullptr : target.data();
     in.ceiling = ceiling.empty() ? nullptr : ceiling.data();
@@ -161,15 +177,10 @@ int OutputChain::set_loudness(const double *target, const double *ceiling, size_
     int rc = check_settable("jb_batch_set_loudness_target: the target is set before the batch's first run");
     if (rc)
         return rc;
-    if (!target || !ceiling || (n != 1 && n != (size_t)b.B)) {
-        set_error("jb_batch_set_loudness_target: give one target, or one per utterance");
+    const char *err = "jb_batch_set_loudness_target: give one target, or one per utterance";
+    std::vector<double> t, c;
+    if (!broadcast(target, n, &t, err) || !broadcast(ceiling, n, &c, err))
         return JB_ERR_INVALID;
-    }
-    std::vector<double> t((size_t)b.B, 0.0), c((size_t)b.B, 0.0);
-    for (size_t u = 0; u < (size_t)b.B; u++) {
-        t[u] = target[n == 1 ? 0 : u];
-        c[u] = ceiling[n == 1 ? 0 : u];
-    }
     if ((rc = check_groups(ln_group_req, t, c, ln_mode, want_hz, "jb_batch_set_loudness_target", nullptr)))
         return rc;
     ln_target = std::move(t);
@@ -185,18 +196,14 @@ int OutputChain::set_peak_mode(const uint32_t *mode, size_t n)
     int rc = check_settable("jb_batch_set_peak_mode: the peak mode is set before the batch's first run");
     if (rc)
         return rc;
-    if (!mode || (n != 1 && n != (size_t)b.B)) {
-        set_error("jb_batch_set_peak_mode: give one mode, or one per utterance");
+    std::vector<uint32_t> m;
+    if (!broadcast(mode, n, &m, "jb_batch_set_peak_mode: give one mode, or one per utterance"))
         return JB_ERR_INVALID;
-    }
-    for (size_t u = 0; u < n; u++)
-        if (mode[u] != JB_PEAK_SAMPLE && mode[u] != JB_PEAK_TRUE) {
+    for (uint32_t v : m)
+        if (v != JB_PEAK_SAMPLE && v != JB_PEAK_TRUE) {
             set_error("jb_batch_set_peak_mode: a mode is JB_PEAK_SAMPLE or JB_PEAK_TRUE");
             return JB_ERR_INVALID;
         }
-    std::vector<uint32_t> m((size_t)b.B, JB_PEAK_SAMPLE);
-    for (size_t u = 0; u < (size_t)b.B; u++)
-        m[u] = mode[n == 1 ? 0 : u];
     if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, m, want_hz, "jb_batch_set_peak_mode", nullptr)))
         return rc;
     ln_mode = std::move(m);
@@ -277,14 +284,10 @@ int OutputChain::check_join(const std::vector<JoinUtt> &req, const std::vector<u
 {
     if (req.empty())
         return JB_OK;
-    const size_t B = (size_t)b.B;
-    std::vector<uint32_t> hz(B, b.voice.sampling_frequency);
-    for (size_t u = 0; u < want.size(); u++)
-        if (want[u])
-            hz[u] = want[u];
-    std::vector<uint64_t> n(B, 0); // (the lengths do not bear on the check)
+    const std::vector<uint32_t> hz = rates_under(want);
+    std::vector<uint64_t> n(hz.size(), 0); // (the lengths do not bear on the check)
     JoinLayout lay;
-    return join_layout_checked(req.data(), n.data(), hz.data(), B, sizeof(double), &lay, who);
+    return join_layout_checked(req.data(), n.data(), hz.data(), hz.size(), sizeof(double), &lay, who);
 }
 
 int OutputChain::set_join(const jb_join_utt *req, size_t n)
@@ -313,12 +316,11 @@ int OutputChain::set_join(const jb_join_utt *req, size_t n)
 // and the field
 int OutputChain::check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const
 {
+    const std::vector<uint32_t> hz = rates_under(want);
     int rc;
-    for (size_t u = 0; u < req.size(); u++) {
-        const uint32_t hz = (u < want.size() && want[u]) ? want[u] : b.voice.sampling_frequency;
-        if ((rc = filter_design_checked(&req[u], hz, u, nullptr, who)))
+    for (size_t u = 0; u < req.size(); u++)
+        if ((rc = filter_design_checked(&req[u], hz[u], u, nullptr, who)))
             return rc;
-    }
     return JB_OK;
 }
 
@@ -333,13 +335,9 @@ int OutputChain::set_filter(const jb_filter *f, size_t n)
         replan();
         return JB_OK;
     }
-    if (!f || (n != 1 && n != (size_t)b.B)) {
-        set_error("jb_batch_set_filter: give one filter, or one per utterance");
+    std::vector<jb_filter> r;
+    if (!broadcast(f, n, &r, "jb_batch_set_filter: give one filter, or one per utterance"))
         return JB_ERR_INVALID;
-    }
-    std::vector<jb_filter> r((size_t)b.B);
-    for (size_t u = 0; u < r.size(); u++)
-        r[u] = f[n == 1 ? 0 : u];
     if ((rc = check_filter(r, want_hz, "jb_batch_set_filter")))
         return rc;
     filt_any.assign(r.size(), 0);
@@ -364,9 +362,135 @@ int OutputChain::filter_coefficients(size_t u, jb_biquad *out, uint32_t *n) cons
     return JB_OK;
 }
 
-// The classes (one table per distinct filter and rate; utterances without sections share the identity), the
-// utterance list sorted by section count and the per-tile state scratch: the f64 of the stage in front in, the
-// filter's slab out
+// At the first run (a second one, or the step done again behind a resident-GV formation timeout, finds it done).
+// The vocoder is pointed at its slab last: a failure leaves the batch as it was created, its blocks the batch's own
+int OutputChain::prepare()
+{
+    if (ready)
+        return JB_OK;
+    frozen = true;
+    int rc;
+    for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
+        if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
+            return rc;
+    if ((rc = prepare_resample()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_join()) ||
+        (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()))
+        return rc;
+    if (plan.active()) {
+        void *voc = slab[(size_t)plan.vocoder.slab];
+        b.vd.pcm = plan.vocoder.i16 ? nullptr : (double *)voc;
+        b.vd.pcm16 = plan.vocoder.i16 ? (int16_t *)voc : nullptr;
+    }
+    ready = true;
+    return JB_OK;
+}
+
+// A run launches every stage of the plan, a redo those that have something to do again: every list of a redo is
+// uploaded (select_X) before its first launch, and one wait ends it
+int OutputChain::enqueue(const std::vector<uint8_t> *only)
+{
+    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || joined()))
+        return JB_OK;
+    const bool redo = only != nullptr;
+    static const LnGroups no_groups;
+    const RedoScope of_redo =
+        redo ? redo_scope(plan.prog_of, plan.units.size(), grouped() ? ln_groups : no_groups, *only) : RedoScope{};
+    const RedoScope *scope = redo ? &of_redo : nullptr;
+    int rc;
+    if ((rc = select_resample(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
+        (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
+        (rc = select_adpcm(scope)))
+        return rc;
+    // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
+    if (redo && !(rs.tiles.n || fil.utts.n || ln.utts.n || ln.apply.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n))
+        return JB_OK;
+    if ((rc = launch_resample(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
+        (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
+        (rc = launch_adpcm(redo)))
+        return rc;
+    hipError_t e;
+    if (redo && (e = hipStreamSynchronize(b.stream_voc)) != hipSuccess)
+        return hip_fail(e, "output chain(redo)");
+    return JB_OK;
+}
+
+static const char *const kRedoLists = "output chain(redo lists)";
+
+// The picked entries of a run's list, each numbered (its field `base`) from the picked ones in front of it
+template <class T> static std::vector<T> renumbered(const std::vector<T> &all, const Picked &p, uint64_t T::*base)
+{
+    std::vector<T> sub;
+    for (size_t i = 0; i < p.index.size(); i++) {
+        sub.push_back(all[p.index[i]]);
+        sub.back().*base = p.base[i];
+    }
+    return sub;
+}
+
+// ---- the converter.  One table per distinct rate (native utterances go through the identity table: a copy, or the
+// 16-bit conversion alone) and the tiles, reading the vocoder's f64 and writing the converter's slab
+int OutputChain::prepare_resample()
+{
+    if (!plan.convert)
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    const uint32_t in = b.voice.sampling_frequency;
+    const double *src = (const double *)slab[(size_t)plan.vocoder.slab];
+    char *dst = (char *)slab[(size_t)plan.converter.slab];
+    const size_t elem = plan.converter.i16 ? sizeof(int16_t) : sizeof(double);
+    std::vector<ResampleTable> tables;
+    std::vector<uint32_t> rate_of_table;
+    std::vector<ResampleTile> &tiles = rs.tiles.host;
+    int rc;
+    tiles.clear();
+    rs.tile_lo.assign(B + 1, 0);
+    for (size_t u = 0; u < B; u++) {
+        const OutUtt &w = plan.utt[u];
+        const size_t t = std::find(rate_of_table.begin(), rate_of_table.end(), w.hz) - rate_of_table.begin();
+        if (t == rate_of_table.size()) {
+            ResampleTable tb{};
+            if ((rc = resample_table(b.device, in, w.hz, &tb)))
+                return rc;
+            rate_of_table.push_back(w.hz);
+            tables.push_back(tb);
+            rs.lds = std::max<size_t>(rs.lds, tb.lds_bytes);
+        }
+        rs.tile_lo[u] = (uint32_t)tiles.size();
+        resample_tiles(tables[t], (uint32_t)t, src + (size_t)b.frame_off[u] * b.voice.fperiod,
+                       (uint64_t)b.T[u] * b.voice.fperiod, dst + w.off * elem, w.n, tiles);
+    }
+    rs.tile_lo[B] = (uint32_t)tiles.size();
+    const size_t nt = std::max<size_t>(tiles.size(), 1);
+    if ((rc = b.dalloc(&rs.tables_dev, tables.size(), false)) || (rc = rs.tiles.alloc(b, nt, nt)) ||
+        (rc = upload_list(rs.tables_dev, tables, "resample work list")))
+        return rc;
+    return rs.tiles.upload("resample work list");
+}
+
+int OutputChain::select_resample(const RedoScope *scope)
+{
+    if (!plan.convert || !scope)
+        return rs.tiles.take_all();
+    const std::vector<uint8_t> &mask = scope->measured; // a tile reads the vocoder's PCM of its own utterance alone
+    std::vector<ResampleTile> sub; // (a tile says where it reads and writes: nothing to renumber)
+    for (size_t u = 0; u < mask.size(); u++)
+        if (mask[u])
+            sub.insert(sub.end(), rs.tiles.host.begin() + rs.tile_lo[u], rs.tiles.host.begin() + rs.tile_lo[u + 1]);
+    return rs.tiles.upload_redo(sub, kRedoLists);
+}
+
+int OutputChain::launch_resample(bool redo)
+{
+    if (!plan.convert || (redo && !rs.tiles.n))
+        return JB_OK;
+    const hipError_t e =
+        jb::launch_resample(rs.tables_dev, rs.tiles.list, rs.tiles.n, plan.converter.i16, rs.lds, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_resample(redo)" : "k_resample");
+}
+
+// ---- the filter: behind the converter (its second pass too), in front of the measurement.  The classes (one table
+// per distinct filter and rate; utterances without sections share the identity), the utterance list sorted by
+// section count and the per-tile state scratch: the f64 of the stage in front in, the filter's slab out
 int OutputChain::prepare_filter()
 {
     if (!plan.filtered())
@@ -381,101 +505,50 @@ int OutputChain::prepare_filter()
     int rc = filter_classes(filt_req.data(), B, hz.data(), B, &fil.classes, &cls_of, "jb_batch_set_filter");
     if (rc)
         return rc;
-    fil.utts.assign(B, FilterUtt{});
+    fil.utts.host.assign(B, FilterUtt{});
     uint64_t tiles = 0;
     for (size_t u = 0; u < B; u++) {
         const OutUtt &o = plan.utt[u];
-        if (filter_tiles(o.n) > kFiltMaxTiles) {
+        const uint64_t nt = filter_tiles(o.n);
+        if (nt > kFiltMaxTiles) {
             set_error("filter: utterance " + std::to_string(u) + " is too long");
             return JB_ERR_UNSUPPORTED;
         }
-        fil.utts[u] = {src + o.off, dst + o.off * elem, o.n, tiles, 0, (uint32_t)filter_tiles(o.n), cls_of[u]};
-        tiles += fil.utts[u].ntiles;
+        fil.utts.host[u] = {src + o.off, dst + o.off * elem, o.n, tiles, 0, (uint32_t)nt, cls_of[u]};
+        tiles += nt;
     }
-    if ((rc = filter_launch_list(fil.classes, fil.utts, nullptr, &fil.all)))
+    if ((rc = filter_launch_list(fil.classes, fil.utts.host, nullptr, &fil.all)) ||
+        (rc = b.dalloc(&fil.classes_dev, fil.classes.size(), false)) || (rc = fil.utts.alloc(b, B, B)) ||
+        (rc = b.dalloc(&fil.st, (size_t)tiles * kFiltMaxD, false)) ||
+        (rc = upload_list(fil.classes_dev, fil.classes, "filter work list")))
         return rc;
-    if ((rc = b.dalloc(&fil.classes_dev, fil.classes.size(), false)) || (rc = b.dalloc(&fil.utts_dev, B, false)) ||
-        (rc = b.dalloc(&fil.redo_dev, B, false)) || (rc = b.dalloc(&fil.st, (size_t)tiles * kFiltMaxD, false)))
-        return rc;
-    hipError_t e;
-    if ((!fil.classes.empty() && (e = hipMemcpy(fil.classes_dev, fil.classes.data(), sizeof(FilterClass) * fil.classes.size(),
-                                               hipMemcpyHostToDevice)) != hipSuccess) ||
-        (B > 0 && (e = hipMemcpy(fil.utts_dev, fil.all.utts.data(), sizeof(FilterUtt) * B, hipMemcpyHostToDevice)) !=
-                      hipSuccess))
-        return hip_fail(e, "filter work list");
-    return JB_OK;
+    return upload_list(fil.utts.dev, fil.all.utts, "filter work list");
 }
 
-// At the first run (a second one, or the step done again behind a resident-GV formation timeout, finds it done).
-// The vocoder is pointed at its slab last: a failure leaves the batch as it was created, its blocks the batch's own
-int OutputChain::prepare()
+int OutputChain::select_filter(const RedoScope *scope)
 {
-    if (ready)
-        return JB_OK;
-    frozen = true;
-    int rc;
-    for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
-        if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
-            return rc;
-    if ((rc = prepare_resample()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_join()) || (rc = prepare_flac()) ||
-        (rc = prepare_format()) || (rc = prepare_adpcm()))
-        return rc;
-    if (plan.active()) {
-        void *voc = slab[(size_t)plan.vocoder.slab];
-        b.vd.pcm = plan.vocoder.i16 ? nullptr : (double *)voc;
-        b.vd.pcm16 = plan.vocoder.i16 ? (int16_t *)voc : nullptr;
-    }
-    ready = true;
-    return JB_OK;
+    fil.take = &fil.all;
+    if (!plan.filtered() || !scope)
+        return fil.utts.take_all();
+    // by filter_launch_list, which also sorts and renumbers: a recursive filter carries a changed sample to the
+    // utterance's end, so every touched utterance whole
+    const std::vector<uint8_t> &mask = scope->measured;
+    const int rc = filter_launch_list(fil.classes, fil.utts.host, &mask, &fil.sub);
+    fil.take = &fil.sub;
+    return rc ? rc : fil.utts.upload_redo(fil.sub.utts, kRedoLists);
 }
 
-// One table per distinct rate (native utterances go through the identity table: a copy, or the 16-bit conversion
-// alone) and the tiles, reading the vocoder's f64 and writing the converter's slab
-int OutputChain::prepare_resample()
+int OutputChain::launch_filter(bool redo)
 {
-    if (!plan.convert)
+    if (!plan.filtered() || (redo && !fil.utts.n))
         return JB_OK;
-    const size_t B = (size_t)b.B;
-    const uint32_t in = b.voice.sampling_frequency;
-    const double *src = (const double *)slab[(size_t)plan.vocoder.slab];
-    char *dst = (char *)slab[(size_t)plan.converter.slab];
-    const size_t elem = plan.converter.i16 ? sizeof(int16_t) : sizeof(double);
-    std::vector<ResampleTable> tables;
-    std::vector<uint32_t> rate_of_table;
-    int rc;
-    rs.tiles.clear();
-    rs.tile_lo.assign(B + 1, 0);
-    for (size_t u = 0; u < B; u++) {
-        const OutUtt &w = plan.utt[u];
-        const size_t t = std::find(rate_of_table.begin(), rate_of_table.end(), w.hz) - rate_of_table.begin();
-        if (t == rate_of_table.size()) {
-            ResampleTable tb{};
-            if ((rc = resample_table(b.device, in, w.hz, &tb)))
-                return rc;
-            rate_of_table.push_back(w.hz);
-            tables.push_back(tb);
-            rs.lds = std::max<size_t>(rs.lds, tb.lds_bytes);
-        }
-        rs.tile_lo[u] = (uint32_t)rs.tiles.size();
-        resample_tiles(tables[t], (uint32_t)t, src + (size_t)b.frame_off[u] * b.voice.fperiod,
-                       (uint64_t)b.T[u] * b.voice.fperiod, dst + w.off * elem, w.n, rs.tiles);
-    }
-    rs.tile_lo[B] = (uint32_t)rs.tiles.size();
-    const size_t nt = std::max<size_t>(rs.tiles.size(), 1);
-    if ((rc = b.dalloc(&rs.tables_dev, tables.size(), false)) || (rc = b.dalloc(&rs.tiles_dev, nt, false)) ||
-        (rc = b.dalloc(&rs.redo_dev, nt, false)))
-        return rc;
-    hipError_t e;
-    if ((e = hipMemcpy(rs.tables_dev, tables.data(), sizeof(ResampleTable) * tables.size(), hipMemcpyHostToDevice)) !=
-            hipSuccess ||
-        (!rs.tiles.empty() && (e = hipMemcpy(rs.tiles_dev, rs.tiles.data(), sizeof(ResampleTile) * rs.tiles.size(),
-                                             hipMemcpyHostToDevice)) != hipSuccess))
-        return hip_fail(e, "resample work list");
-    return JB_OK;
+    const hipError_t e =
+        jb::launch_filter(fil.classes_dev, fil.utts.list, *fil.take, fil.st, plan.filter.i16, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "filter(redo)" : "filter");
 }
 
-// The per-rate tables and the utterance list: the measurement reads the f64 of the stage in front, the apply pass
-// writes x * g to its own slab
+// ---- loudness.  The per-rate tables and the utterance list: the measurement reads the f64 of the stage in front,
+// the apply pass writes x * g to its own slab
 int OutputChain::prepare_loudness()
 {
     if (!plan.normalize())
@@ -485,8 +558,10 @@ int OutputChain::prepare_loudness()
     char *dst = (char *)slab[(size_t)plan.apply.slab];
     const size_t elem = plan.apply.i16 ? sizeof(int16_t) : sizeof(double);
     std::vector<LoudnessRate> rates;
-    ln.utts.assign(B, LoudnessUtt{});
-    uint64_t tiles = 0, atiles = 0;
+    ln.utts.host.assign(B, LoudnessUtt{});
+    ln.ntiles.assign(B, 0);
+    ln.natiles.assign(B, 0);
+    ln.tiles = ln.atiles = 0;
     int rc;
     for (size_t u = 0; u < B; u++) {
         const OutUtt &o = plan.utt[u];
@@ -499,63 +574,113 @@ int OutputChain::prepare_loudness()
                 return rc;
             rates.push_back(lr);
         }
-        LoudnessUtt &w = ln.utts[u];
+        LoudnessUtt &w = ln.utts.host[u];
         w.x = src + o.off;
         w.y = dst + o.off * elem;
         w.n = o.n;
-        w.ntiles = loudness_tiles(rates[r], w.n);
-        w.tile0 = w.lt0 = tiles;
-        w.at0 = atiles;
+        ln.ntiles[u] = w.ntiles = loudness_tiles(rates[r], w.n);
+        ln.natiles[u] = (w.n + kLnApplyTile - 1) / kLnApplyTile;
+        w.tile0 = w.lt0 = ln.tiles;
+        w.at0 = ln.atiles;
         w.rate = (uint32_t)r;
         w.slot = (uint32_t)u;
         w.target = ln_target[u];
         w.ceiling = ln_ceiling[u];
         w.mode = peak_mode(u);
         ln.true_peak = ln.true_peak || w.mode == JB_PEAK_TRUE;
-        tiles += w.ntiles;
-        atiles += (w.n + kLnApplyTile - 1) / kLnApplyTile;
+        ln.tiles += ln.ntiles[u];
+        ln.atiles += ln.natiles[u];
     }
-    const size_t nt = (size_t)std::max<uint64_t>(tiles, 1);
-    if ((rc = b.dalloc(&ln.rates_dev, rates.size(), false)) || (rc = b.dalloc(&ln.utts_dev, B, false)) ||
-        (rc = b.dalloc(&ln.redo_dev, B, false)) || (rc = b.dalloc(&ln.st, 4 * nt, false)) ||
-        (rc = b.dalloc(&ln.pk, nt, false)) || (rc = b.dalloc(&ln.z, nt, false)) ||
-        (rc = b.dalloc(&ln.res, B, false)) || (ln.true_peak && (rc = b.dalloc(&ln.tp, nt, false))))
+    const size_t nt = (size_t)std::max<uint64_t>(ln.tiles, 1);
+    if ((rc = b.dalloc(&ln.rates_dev, rates.size(), false)) || (rc = ln.utts.alloc(b, B, B)) ||
+        (rc = b.dalloc(&ln.st, 4 * nt, false)) || (rc = b.dalloc(&ln.pk, nt, false)) ||
+        (rc = b.dalloc(&ln.z, nt, false)) || (rc = b.dalloc(&ln.res, B, false)) ||
+        (ln.true_peak && (rc = b.dalloc(&ln.tp, nt, false))) ||
+        (rc = upload_list(ln.rates_dev, rates, "loudness work list")) || (rc = ln.utts.upload("loudness work list")))
         return rc;
-    hipError_t e;
-    if ((e = hipMemcpy(ln.rates_dev, rates.data(), sizeof(LoudnessRate) * rates.size(), hipMemcpyHostToDevice)) !=
-            hipSuccess ||
-        (B > 0 && (e = hipMemcpy(ln.utts_dev, ln.utts.data(), sizeof(LoudnessUtt) * B, hipMemcpyHostToDevice)) !=
-                      hipSuccess))
-        return hip_fail(e, "loudness work list");
-    ln.tiles = tiles;
-    ln.atiles = atiles;
     // with a group or a report request: the sets (every utterance, then every group) and what their kernels write
-    const bool grouped = !ln_group_req.empty();
-    if ((!grouped && !ln_report) || B == 0)
-        return JB_OK;
     const size_t G = ln_groups.size();
-    ln.sets.assign(B + G, LoudnessSet{});
-    std::vector<uint32_t> members(grouped ? 2 * B : B);
+    const bool with_groups = !ln_group_req.empty();
+    if ((!with_groups && !ln_report) || B == 0)
+        return JB_OK;
+    ln.sets.host.assign(B + G, LoudnessSet{});
+    std::vector<uint32_t> members(with_groups ? 2 * B : B);
     for (size_t u = 0; u < B; u++) {
-        ln.sets[u] = LoudnessSet{(uint32_t)u, 1, (uint32_t)u, (uint32_t)u};
+        ln.sets.host[u] = LoudnessSet{(uint32_t)u, 1, (uint32_t)u, (uint32_t)u};
         members[u] = (uint32_t)u;
-        if (grouped)
+        if (with_groups)
             members[B + u] = ln_groups.members[u];
     }
     for (size_t g = 0; g < G; g++)
-        ln.sets[B + g] = LoudnessSet{(uint32_t)B + ln_groups.first[g], ln_groups.first[g + 1] - ln_groups.first[g],
-                                     (uint32_t)g, (uint32_t)(B + g)};
-    if ((rc = b.dalloc(&ln.sets_dev, B + G, false)) || (rc = b.dalloc(&ln.sets_redo_dev, B + G, false)) ||
-        (rc = b.dalloc(&ln.members_dev, members.size(), false)) ||
-        (grouped && ((rc = b.dalloc(&ln.gres, G, false)) || (rc = b.dalloc(&ln.apply_redo_dev, B, false)))) ||
+        ln.sets.host[B + g] = LoudnessSet{(uint32_t)B + ln_groups.first[g], ln_groups.first[g + 1] - ln_groups.first[g],
+                                          (uint32_t)g, (uint32_t)(B + g)};
+    if ((rc = ln.sets.alloc(b, B + G, B + G)) || (rc = b.dalloc(&ln.members_dev, members.size(), false)) ||
+        (with_groups && ((rc = b.dalloc(&ln.gres, G, false)) || (rc = b.dalloc(&ln.apply.redo, B, false)))) ||
         (ln_report && ((rc = b.dalloc(&ln.sw, nt, false)) || (rc = b.dalloc(&ln.mm, B, false)) ||
-                       (rc = b.dalloc(&ln.r128, B + G, false)))))
+                       (rc = b.dalloc(&ln.r128, B + G, false)))) ||
+        (rc = ln.sets.upload("loudness group list")))
         return rc;
-    if ((e = hipMemcpy(ln.sets_dev, ln.sets.data(), sizeof(LoudnessSet) * (B + G), hipMemcpyHostToDevice)) !=
-            hipSuccess ||
-        (e = hipMemcpy(ln.members_dev, members.data(), sizeof(uint32_t) * members.size(), hipMemcpyHostToDevice)) !=
-            hipSuccess)
-        return hip_fail(e, "loudness group list");
+    return upload_list(ln.members_dev, members, "loudness group list");
+}
+
+int OutputChain::select_loudness(const RedoScope *scope)
+{
+    const bool report = plan.normalize() && ln.r128;
+    if (!plan.normalize() || !scope) {
+        ln.utts.take_all(ln.tiles);
+        ln.apply.list = ln.utts.dev, ln.apply.n = ln.utts.n, ln.apply.total = ln.atiles;
+        ln.sets.take_all();
+        ln.n_usets = ln.utts.n;
+        return JB_OK;
+    }
+    // The measurement and the utterances' report sets: an utterance's samples in front of the apply pass depend on
+    // nothing but its own.  An utterance of zero samples stays in the list: its result is written like any other.
+    // (This list's at0 is read only where the apply pass takes it too: without groups)
+    const std::vector<uint8_t> &mask = scope->measured;
+    const Picked m = pick_renumbered(mask, ln.ntiles), ma = pick_renumbered(mask, ln.natiles);
+    std::vector<LoudnessUtt> sub = renumbered(ln.utts.host, m, &LoudnessUtt::lt0); // (the scratch, tile0, stays)
+    std::vector<LoudnessSet> set_sub;
+    for (size_t i = 0; i < sub.size(); i++) {
+        sub[i].at0 = ma.base[i];
+        if (report)
+            set_sub.push_back(ln.sets.host[m.index[i]]);
+    }
+    ln.n_usets = (uint32_t)set_sub.size();
+    int rc = ln.utts.upload_redo(sub, kRedoLists, m.total);
+    if (rc)
+        return rc;
+    ln.apply.list = ln.utts.redo, ln.apply.n = ln.utts.n, ln.apply.total = ma.total;
+    if (grouped()) {
+        // the apply pass: a group's gain reaches every member; the groups' sets: those with a measured member
+        const std::vector<uint8_t> &apply_mask = scope->post, &group_mask = scope->touched_groups;
+        const Picked a = pick_renumbered(apply_mask, ln.natiles);
+        for (size_t g = 0; g < group_mask.size(); g++)
+            if (group_mask[g])
+                set_sub.push_back(ln.sets.host[(size_t)b.B + g]);
+        if ((rc = ln.apply.upload_redo(renumbered(ln.utts.host, a, &LoudnessUtt::at0), kRedoLists, a.total)))
+            return rc;
+    }
+    return ln.sets.upload_redo(set_sub, kRedoLists);
+}
+
+// The measurement, the groups' gate over the measured members' scratch, the report, then one gain for every member
+int OutputChain::launch_loudness(bool redo)
+{
+    if (!plan.normalize() || (redo && !ln.utts.n))
+        return JB_OK;
+    hipStream_t st = b.stream_voc;
+    const bool report = ln.r128 != nullptr;
+    hipError_t e;
+    if ((e = launch_loudness_measure(ln.rates_dev, ln.utts.list, ln.utts.n, ln.utts.total, ln.st, ln.pk, ln.tp, ln.z,
+                                     ln.res, ln.true_peak, st)) != hipSuccess ||
+        (grouped() && (e = launch_loudness_groups(ln.rates_dev, ln.utts.dev, ln.sets.list + ln.n_usets,
+                                                  ln.sets.n - ln.n_usets, ln.members_dev, ln.z, ln.res, ln.gres, st)) !=
+                          hipSuccess) ||
+        (report && (e = launch_loudness_range(ln.rates_dev, ln.utts.list, ln.utts.n, ln.utts.dev, ln.sets.list,
+                                              ln.sets.n, ln.members_dev, ln.z, ln.sw, ln.mm, ln.r128, st)) !=
+                       hipSuccess) ||
+        (e = launch_loudness_apply(ln.apply.list, ln.apply.n, ln.apply.total, ln.res, plan.apply.i16, st)) != hipSuccess)
+        return hip_fail(e, redo ? "loudness(redo)" : "loudness");
     return JB_OK;
 }
 
@@ -572,6 +697,18 @@ std::vector<OutputChain::EncUnit> OutputChain::enc_units() const
     return units;
 }
 
+// ---- the join: behind everything that writes the final PCM, in front of everything that encodes it.
+// Samples [k0, k1) of programme p as a span whose tiles follow *tiles
+JoinSpan OutputChain::join_span(size_t p, uint64_t k0, uint64_t k1, uint64_t *tiles) const
+{
+    const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
+    const uint32_t m0 = plan.prog_first[p], m1 = plan.prog_first[p + 1];
+    const JoinSpan w = {(char *)slab[(size_t)plan.join.slab] + plan.units[p].off * elem, plan.units[p].n, k0, k1, *tiles,
+                        m0, m1 - m0};
+    *tiles += join_tiles(k0, k1, plan.join.i16);
+    return w;
+}
+
 // The members in programme order and one span per programme: the final PCM of the plan in, the join slab out
 int OutputChain::prepare_join()
 {
@@ -580,375 +717,226 @@ int OutputChain::prepare_join()
     const size_t B = (size_t)b.B, P = plan.units.size();
     const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
     const char *src = (const char *)slab[(size_t)plan.join_src.slab];
-    char *dst = (char *)slab[(size_t)plan.join.slab];
     jn.members.assign(B, JoinMember{});
     jn.member_at.assign(B, 0);
-    jn.spans.assign(P, JoinSpan{});
+    jn.spans.host.clear();
     jn.tiles = 0;
     for (size_t p = 0; p < P; p++) {
-        const uint32_t m0 = plan.prog_first[p], m1 = plan.prog_first[p + 1];
-        for (uint32_t i = m0; i < m1; i++) {
+        for (uint32_t i = plan.prog_first[p]; i < plan.prog_first[p + 1]; i++) {
             const uint32_t u = plan.prog_members[i];
             jn.member_at[u] = i;
             jn.members[i] = {src + plan.utt[u].off * elem, plan.prog_start[u], plan.utt[u].n, join_req[u].fade_in,
                              join_req[u].fade_out};
         }
-        jn.spans[p] = {dst + plan.units[p].off * elem, plan.units[p].n, 0, plan.units[p].n, jn.tiles, m0, m1 - m0};
-        jn.tiles += join_tiles(0, plan.units[p].n, plan.join.i16);
+        jn.spans.host.push_back(join_span(p, 0, plan.units[p].n, &jn.tiles));
     }
     int rc;
     // (a redo lists at most one span per member)
-    if ((rc = b.dalloc(&jn.members_dev, B, false)) || (rc = b.dalloc(&jn.spans_dev, P, false)) ||
-        (rc = b.dalloc(&jn.redo_dev, B, false)))
+    if ((rc = b.dalloc(&jn.members_dev, B, false)) || (rc = jn.spans.alloc(b, P, B)) ||
+        (rc = upload_list(jn.members_dev, jn.members, "join work list")))
         return rc;
-    hipError_t e;
-    if (B > 0 && ((e = hipMemcpy(jn.members_dev, jn.members.data(), sizeof(JoinMember) * B, hipMemcpyHostToDevice)) !=
-                      hipSuccess ||
-                  (e = hipMemcpy(jn.spans_dev, jn.spans.data(), sizeof(JoinSpan) * P, hipMemcpyHostToDevice)) !=
-                      hipSuccess))
-        return hip_fail(e, "join work list");
-    return JB_OK;
+    return jn.spans.upload("join work list");
 }
 
-// The streams' lists and slabs: one stream per unit (an utterance; behind a join a programme) of the 16-bit slab
-// FLAC reads, at its output rate
+int OutputChain::select_join(const RedoScope *scope)
+{
+    if (!joined() || !scope)
+        return jn.spans.take_all(jn.tiles);
+    const std::vector<uint8_t> &mask = scope->post; // every utterance whose final PCM changed
+    const uint64_t gs = kJoinGroupBytes / (plan.join.i16 ? sizeof(int16_t) : sizeof(double));
+    std::vector<JoinSpan> sub;
+    uint64_t tiles = 0;
+    for (size_t u = 0; u < mask.size(); u++) {
+        if (!mask[u] || !plan.utt[u].n) // a member of zero samples wrote nothing into its programme: no span
+            continue;
+        // not the whole programme: the member's range alone, widened to whole groups of kJoinGroupBytes (the samples
+        // around it are what they were: its neighbours' current ones, and pads)
+        const JoinMember &m = jn.members[jn.member_at[u]];
+        const uint64_t end = plan.units[plan.prog_of[u]].n;
+        sub.push_back(join_span(plan.prog_of[u], m.start / gs * gs,
+                                std::min<uint64_t>((m.start + m.n + gs - 1) / gs * gs, end), &tiles));
+    }
+    return jn.spans.upload_redo(sub, kRedoLists, tiles);
+}
+
+int OutputChain::launch_join(bool redo)
+{
+    if (!joined() || (redo && !jn.spans.n))
+        return JB_OK;
+    const hipError_t e =
+        jb::launch_join(plan.join.i16, jn.spans.list, jn.spans.n, jn.spans.total, jn.members_dev, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_join(redo)" : "k_join");
+}
+
+// ---- FLAC.  The streams' lists and slabs: one stream per unit (an utterance; behind a join a programme) of the
+// 16-bit slab FLAC reads, at its output rate
 int OutputChain::prepare_flac()
 {
     if (!flac_on)
         return JB_OK;
     const std::vector<EncUnit> units = enc_units();
-    const size_t B = units.size();
-    std::vector<const int16_t *> xs(B);
-    std::vector<uint64_t> ns(B);
-    std::vector<uint32_t> hz(B);
-    for (size_t u = 0; u < B; u++) {
+    const size_t U = units.size();
+    std::vector<const int16_t *> xs(U);
+    std::vector<uint64_t> ns(U);
+    std::vector<uint32_t> hz(U);
+    for (size_t u = 0; u < U; u++) {
         xs[u] = (const int16_t *)slab[(size_t)plan.flac] + units[u].off;
         ns[u] = units[u].n;
         hz[u] = units[u].hz;
     }
     std::vector<FlacUtt> utts;
     uint64_t slot_bytes = 0, bound = 0;
-    int rc = flac_plan(flac_p, flac_m, xs.data(), ns.data(), hz.data(), B, &utts, &fl.work, &slot_bytes, &bound);
+    int rc = flac_plan(flac_p, flac_m, xs.data(), ns.data(), hz.data(), U, &utts, &fl.work.host, &slot_bytes, &bound);
     if (rc)
         return rc;
     const bool md5 = (flac_m.flags & kFlacMetaMd5) != 0;
-    std::vector<uint32_t> order;
     if (md5)
-        flac_md5_order(utts, nullptr, &order);
-    fl.n_md5 = (uint32_t)order.size();
+        flac_md5_order(utts, nullptr, &fl.md5.host);
     fl.max_points = 0;
     for (const FlacUtt &w : utts)
         fl.max_points = std::max(fl.max_points, w.n_points);
-    const size_t nf = std::max<size_t>(fl.work.size(), 1);
+    const size_t nf = std::max<size_t>(fl.work.host.size(), 1), nu = std::max<size_t>(U, 1);
     uint8_t *slots = nullptr;
     if ((rc = b.dalloc(&slots, std::max<uint64_t>(slot_bytes, 4), false)) ||
-        (rc = b.dalloc(&fl.out, std::max<uint64_t>(bound, 4), false)) || (rc = b.dalloc(&fl.utts_dev, B, false)) ||
-        (rc = b.dalloc(&fl.work_dev, nf, false)) || (rc = b.dalloc(&fl.redo_dev, nf, false)) ||
-        (rc = b.dalloc(&fl.fsize, nf, false)) || (rc = b.dalloc(&fl.foff, nf, false)) ||
-        (rc = b.dalloc(&fl.res, B, false)) || (rc = b.dalloc(&fl.total, 1, false)) ||
-        (md5 && ((rc = b.dalloc(&fl.md5_order_dev, std::max<size_t>(B, 1), false)) ||
-                 (rc = b.dalloc(&fl.md5_redo_dev, std::max<size_t>(B, 1), false)) ||
-                 (rc = b.dalloc(&fl.digests, 4 * std::max<size_t>(B, 1), false)))))
+        (rc = b.dalloc(&fl.out, std::max<uint64_t>(bound, 4), false)) || (rc = b.dalloc(&fl.utts_dev, U, false)) ||
+        (rc = fl.work.alloc(b, nf, nf)) || (rc = b.dalloc(&fl.fsize, nf, false)) ||
+        (rc = b.dalloc(&fl.foff, nf, false)) || (rc = b.dalloc(&fl.res, U, false)) ||
+        (rc = b.dalloc(&fl.total, 1, false)) ||
+        (md5 && ((rc = fl.md5.alloc(b, nu, nu)) || (rc = b.dalloc(&fl.digests, 4 * nu, false)))))
         return rc;
     flac_bind(&utts, slots);
-    hipError_t e = hipSuccess;
-    if ((B > 0 && (e = hipMemcpy(fl.utts_dev, utts.data(), sizeof(FlacUtt) * B, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (!fl.work.empty() && (e = hipMemcpy(fl.work_dev, fl.work.data(), sizeof(FlacWork) * fl.work.size(),
-                                            hipMemcpyHostToDevice)) != hipSuccess) ||
-        (!order.empty() && (e = hipMemcpy(fl.md5_order_dev, order.data(), sizeof(uint32_t) * order.size(),
-                                          hipMemcpyHostToDevice)) != hipSuccess))
-        return hip_fail(e, "FLAC work list");
+    if ((rc = upload_list(fl.utts_dev, utts, "FLAC work list")) || (rc = fl.work.upload("FLAC work list")) ||
+        (rc = fl.md5.upload("FLAC work list")))
+        return rc;
     if (md5)
         fl.utts = std::move(utts);
     return JB_OK;
 }
 
-// The utterance list: the final f64 of the plan in, each utterance's bytes at its 16-byte aligned place out
+int OutputChain::select_flac(const RedoScope *scope)
+{
+    if (!flac_on || !scope) {
+        fl.md5.take_all();
+        return fl.work.take_all();
+    }
+    const std::vector<uint8_t> &mask = scope->units; // every unit whose final PCM changed
+    // by work item (a block says which frame of which stream it is: nothing to renumber); the digests of the same
+    // units where a block is encoded again (a unit without frames keeps its digest of no samples)
+    std::vector<FlacWork> sub;
+    std::vector<uint32_t> md5_sub;
+    for (const FlacWork &w : fl.work.host)
+        if (mask[w.utt])
+            sub.push_back(w);
+    if (fl.digests && !sub.empty())
+        flac_md5_order(fl.utts, &mask, &md5_sub);
+    const int rc = fl.work.upload_redo(sub, kRedoLists);
+    return rc ? rc : fl.md5.upload_redo(md5_sub, kRedoLists);
+}
+
+// The blocks of the list, the digests of its units' now final PCM (on request), then every stream's offsets, place
+// and header (all of fl.work.dev, redo or not): the pack never sees a digest of replaced PCM
+int OutputChain::launch_flac(bool redo)
+{
+    if (!flac_on || (redo && !fl.work.n))
+        return JB_OK;
+    hipStream_t st = b.stream_voc;
+    hipError_t e;
+    if ((e = launch_flac_encode(flac_p, fl.utts_dev, fl.work.list, fl.work.n, fl.fsize, st)) != hipSuccess ||
+        (fl.digests && (e = launch_flac_md5(fl.utts_dev, fl.md5.list, fl.md5.n, fl.digests, st)) != hipSuccess) ||
+        (e = launch_flac_pack(flac_p, fl.utts_dev, (uint32_t)num_outputs(), fl.work.dev, (uint32_t)fl.work.host.size(),
+                              fl.fsize, fl.foff, fl.res, fl.total, fl.out, st, fl.digests, fl.max_points)) != hipSuccess)
+        return hip_fail(e, redo ? "FLAC(redo)" : "FLAC");
+    return JB_OK;
+}
+
+// ---- the sample format: behind the apply pass, the converter or the hand-off check, whichever wrote last.
+// The unit list: the final f64 of the plan in, each unit's bytes at its 16-byte aligned place out
 int OutputChain::prepare_format()
 {
-    if (plan.fmt_src == OutSlab::None)
+    if (!formatted())
         return JB_OK;
     const std::vector<EncUnit> units = enc_units();
-    const size_t B = units.size();
+    const size_t U = units.size();
     const double *src = (const double *)slab[(size_t)plan.fmt_src];
     uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Fmt];
-    fm.utts.assign(B, FormatUtt{});
+    fm.utts.host.assign(U, FormatUtt{});
+    fm.ntiles.assign(U, 0);
     fm.tiles = 0;
-    for (size_t u = 0; u < B; u++) {
-        FormatUtt &w = fm.utts[u];
+    for (size_t u = 0; u < U; u++) {
+        FormatUtt &w = fm.utts.host[u];
         w.x = src + units[u].off;
         w.y = dst + plan.fmt[u].off;
         w.n = units[u].n;
         w.ft0 = fm.tiles;
-        fm.tiles += (w.n + kFmtTile - 1) / kFmtTile;
+        fm.ntiles[u] = (w.n + kFmtTile - 1) / kFmtTile;
+        fm.tiles += fm.ntiles[u];
     }
-    int rc;
-    if ((rc = b.dalloc(&fm.utts_dev, B, false)) || (rc = b.dalloc(&fm.redo_dev, B, false)))
-        return rc;
-    hipError_t e;
-    if (B > 0 && (e = hipMemcpy(fm.utts_dev, fm.utts.data(), sizeof(FormatUtt) * B, hipMemcpyHostToDevice)) != hipSuccess)
-        return hip_fail(e, "format work list");
-    return JB_OK;
+    const int rc = fm.utts.alloc(b, U, U);
+    return rc ? rc : fm.utts.upload("format work list");
 }
 
-// The utterance list: the final PCM of the plan in (f64 or 16-bit), each utterance's blocks at their 16-byte aligned
-// place out
+int OutputChain::select_format(const RedoScope *scope)
+{
+    if (!formatted() || !scope)
+        return fm.utts.take_all(fm.tiles);
+    // `units`: every unit whose final PCM changed (one of zero samples stays in the list: it has no tile)
+    const Picked p = pick_renumbered(scope->units, fm.ntiles);
+    return fm.utts.upload_redo(renumbered(fm.utts.host, p, &FormatUtt::ft0), kRedoLists, p.total);
+}
+
+int OutputChain::launch_format(bool redo)
+{
+    if (!formatted() || (redo && !fm.utts.n))
+        return JB_OK;
+    const hipError_t e = jb::launch_format(fmt_p.format, fmt_p.dither, fmt_p.seed, fm.utts.list, fm.utts.n,
+                                           fm.utts.total, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_format(redo)" : "k_format");
+}
+
+// ---- IMA ADPCM beside it, of the same final PCM.  The unit list: the final PCM of the plan in (f64 or 16-bit), each
+// unit's blocks at their 16-byte aligned place out
 int OutputChain::prepare_adpcm()
 {
-    if (plan.adpcm_src.slab == OutSlab::None)
+    if (!adpcm())
         return JB_OK;
     const std::vector<EncUnit> units = enc_units();
-    const size_t B = units.size();
+    const size_t U = units.size();
     const char *src = (const char *)slab[(size_t)plan.adpcm_src.slab];
     const size_t elem = plan.adpcm_src.i16 ? sizeof(int16_t) : sizeof(double);
     uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Adpcm];
-    ad.utts.assign(B, AdpcmUtt{});
+    ad.utts.host.assign(U, AdpcmUtt{});
+    ad.ngroups.assign(U, 0);
     ad.groups = 0;
-    for (size_t u = 0; u < B; u++) {
-        AdpcmUtt &w = ad.utts[u];
+    for (size_t u = 0; u < U; u++) {
+        AdpcmUtt &w = ad.utts.host[u];
         w.x = src + units[u].off * elem;
         w.y = dst + plan.adpcm[u].off;
         w.n = units[u].n;
         w.g0 = ad.groups;
         w.A = plan.adpcm[u].A;
         w.spb = adpcm_spb(w.A);
-        ad.groups += (adpcm_blocks(w.n, w.A) + kAdpcmLanes - 1) / kAdpcmLanes;
+        ad.ngroups[u] = (adpcm_blocks(w.n, w.A) + kAdpcmLanes - 1) / kAdpcmLanes;
+        ad.groups += ad.ngroups[u];
     }
-    int rc;
-    if ((rc = b.dalloc(&ad.utts_dev, B, false)) || (rc = b.dalloc(&ad.redo_dev, B, false)))
-        return rc;
-    hipError_t e;
-    if (B > 0 && (e = hipMemcpy(ad.utts_dev, ad.utts.data(), sizeof(AdpcmUtt) * B, hipMemcpyHostToDevice)) != hipSuccess)
-        return hip_fail(e, "ADPCM work list");
-    return JB_OK;
+    const int rc = ad.utts.alloc(b, U, U);
+    return rc ? rc : ad.utts.upload("ADPCM work list");
 }
 
-int OutputChain::enqueue(const std::vector<uint8_t> *only)
+int OutputChain::select_adpcm(const RedoScope *scope)
 {
-    const bool fmt = plan.fmt_src != OutSlab::None;
-    const bool adp = plan.adpcm_src.slab != OutSlab::None;
-    if (!ready || !(plan.active() || flac_on || fmt || adp || joined()))
+    if (!adpcm() || !scope)
+        return ad.utts.take_all(ad.groups);
+    // `units`: every unit whose final PCM changed (one of zero samples stays in the list: it has no block)
+    const Picked p = pick_renumbered(scope->units, ad.ngroups);
+    return ad.utts.upload_redo(renumbered(ad.utts.host, p, &AdpcmUtt::g0), kRedoLists, p.total);
+}
+
+int OutputChain::launch_adpcm(bool redo)
+{
+    if (!adpcm() || (redo && !ad.utts.n))
         return JB_OK;
-    const uint32_t B = (uint32_t)b.B;
-    const uint32_t U = (uint32_t)num_outputs(); // the encoders' units: the programmes behind a join, else B
-    hipStream_t st = b.stream_voc;
-    // the lists of a run: the batch's own
-    const ResampleTile *tiles = rs.tiles_dev;
-    const LoudnessUtt *utts = ln.utts_dev;
-    const FlacWork *work = fl.work_dev;
-    const uint32_t *md5_order = fl.md5_order_dev;
-    uint32_t n_md5 = fl.n_md5;
-    const FormatUtt *futts = fm.utts_dev;
-    uint32_t n_futts = fmt ? U : 0;
-    uint64_t ft = fm.tiles;
-    const AdpcmUtt *autts = ad.utts_dev;
-    uint32_t n_autts = adp ? U : 0;
-    uint64_t ag = ad.groups;
-    const uint32_t n_all_work = (uint32_t)fl.work.size();
-    uint32_t n_tiles = (uint32_t)rs.tiles.size(), n_utts = B, n_work = n_all_work;
-    uint64_t lt = ln.tiles, at = ln.atiles;
-    // loudness groups and the R128 report (with a target only): the utterances the apply pass takes, the groups, the
-    // report's sets
-    const bool grouped = plan.normalize() && ln.gres, report = plan.normalize() && ln.r128;
-    const size_t G = grouped ? ln_groups.size() : 0;
-    const LoudnessUtt *apply_utts = ln.utts_dev;
-    uint32_t n_apply = B, n_gsets = (uint32_t)G, n_rsets = report ? (uint32_t)(B + G) : 0;
-    const LoudnessSet *gsets = grouped ? ln.sets_dev + B : nullptr, *rsets = ln.sets_dev;
-    // behind the apply pass a group's gain reaches every member: the stages there run again for all of them
-    std::vector<uint8_t> touched_groups, group_members;
-    const std::vector<uint8_t> *post = only;
-    // behind the join a member's samples reach its programme: the encoders run again for every programme of `post`
-    std::vector<uint8_t> touched_units;
-    const std::vector<uint8_t> *upost = only; // [U]
-    const JoinSpan *jspans = jn.spans_dev;
-    uint32_t n_jspans = joined() ? U : 0;
-    uint64_t jt = jn.tiles;
-    const bool filt = plan.filtered();
-    FilterLaunch flt_sub;
-    const FilterLaunch *flt = &fil.all;
-    const FilterUtt *flt_utts = fil.utts_dev;
-    hipError_t e = hipSuccess;
-    if (only && grouped) {
-        loudness_groups_closure(ln_groups, *only, &touched_groups, &group_members);
-        post = &group_members;
-    }
-    upost = post;
-    if (only && joined()) {
-        join_closure(plan.prog_of, U, *post, &touched_units);
-        upost = &touched_units;
-    }
-    if (only) {
-        // of a redo: the tiles, the utterances (renumbered: their scratch stays where it is) and the FLAC blocks of
-        // the utterances it rewrote, uploaded before the first launch
-        std::vector<ResampleTile> rs_sub;
-        std::vector<LoudnessUtt> ln_sub;
-        std::vector<FlacWork> fl_sub;
-        std::vector<uint32_t> md5_sub;
-        std::vector<FormatUtt> fm_sub;
-        std::vector<AdpcmUtt> ad_sub;
-        std::vector<LoudnessUtt> ap_sub; // grouped: the apply pass's own list
-        std::vector<LoudnessSet> set_sub;
-        std::vector<JoinSpan> jn_sub;
-        // a recursive filter carries a changed sample to the utterance's end: every touched utterance whole
-        if (filt) {
-            int rc = filter_launch_list(fil.classes, fil.utts, only, &flt_sub);
-            if (rc)
-                return rc;
-            flt = &flt_sub;
-            flt_utts = fil.redo_dev;
-        }
-        lt = at = ft = ag = jt = 0;
-        uint64_t mat = 0; // apply tiles of the measured list (its at0 is not read when the apply pass has its own)
-        for (size_t u = 0; u < B; u++) {
-            if ((*only)[u]) {
-                if (plan.convert)
-                    rs_sub.insert(rs_sub.end(), rs.tiles.begin() + rs.tile_lo[u],
-                                  rs.tiles.begin() + rs.tile_lo[u + 1]);
-                if (plan.normalize()) {
-                    LoudnessUtt w = ln.utts[u];
-                    w.lt0 = lt;
-                    w.at0 = mat;
-                    lt += w.ntiles;
-                    mat += (w.n + kLnApplyTile - 1) / kLnApplyTile;
-                    ln_sub.push_back(w);
-                    if (report)
-                        set_sub.push_back(ln.sets[u]);
-                }
-            }
-            if (!(*post)[u])
-                continue;
-            if (grouped) {
-                LoudnessUtt w = ln.utts[u];
-                w.at0 = at;
-                at += (w.n + kLnApplyTile - 1) / kLnApplyTile;
-                ap_sub.push_back(w);
-            }
-            if (joined() && plan.utt[u].n) {
-                // the member's span alone, widened to whole groups (the samples around it are what they were: its
-                // neighbours' current ones, and pads)
-                const uint64_t gs = kJoinGroupBytes / (plan.join.i16 ? sizeof(int16_t) : sizeof(double));
-                JoinSpan w = jn.spans[plan.prog_of[u]];
-                const JoinMember &m = jn.members[jn.member_at[u]];
-                w.k0 = m.start / gs * gs;
-                w.k1 = std::min<uint64_t>((m.start + m.n + gs - 1) / gs * gs, w.n);
-                w.t0 = jt;
-                jt += join_tiles(w.k0, w.k1, plan.join.i16);
-                jn_sub.push_back(w);
-            }
-        }
-        for (size_t u = 0; u < U; u++) {
-            if (!(*upost)[u])
-                continue;
-            if (fmt) {
-                FormatUtt w = fm.utts[u];
-                w.ft0 = ft;
-                ft += (w.n + kFmtTile - 1) / kFmtTile;
-                fm_sub.push_back(w);
-            }
-            if (adp) {
-                AdpcmUtt w = ad.utts[u];
-                w.g0 = ag;
-                ag += (adpcm_blocks(w.n, w.A) + kAdpcmLanes - 1) / kAdpcmLanes;
-                ad_sub.push_back(w);
-            }
-        }
-        if (!grouped)
-            at = mat;
-        const uint32_t n_usets = (uint32_t)set_sub.size();
-        for (size_t g = 0; g < G; g++)
-            if (touched_groups[g])
-                set_sub.push_back(ln.sets[B + g]);
-        n_gsets = (uint32_t)set_sub.size() - n_usets;
-        n_rsets = report ? (uint32_t)set_sub.size() : 0;
-        rsets = ln.sets_redo_dev;
-        gsets = ln.sets_redo_dev + n_usets;
-        n_apply = grouped ? (uint32_t)ap_sub.size() : (uint32_t)ln_sub.size();
-        apply_utts = grouped ? ln.apply_redo_dev : ln.redo_dev;
-        for (const FlacWork &w : fl.work)
-            if ((*upost)[w.utt])
-                fl_sub.push_back(w);
-        if (fl.digests)
-            flac_md5_order(fl.utts, upost, &md5_sub); // (an utterance without frames keeps its digest of no samples)
-        tiles = rs.redo_dev;
-        utts = ln.redo_dev;
-        work = fl.redo_dev;
-        md5_order = fl.md5_redo_dev;
-        n_md5 = (uint32_t)md5_sub.size();
-        futts = fm.redo_dev;
-        n_futts = (uint32_t)fm_sub.size();
-        autts = ad.redo_dev;
-        n_autts = (uint32_t)ad_sub.size();
-        n_tiles = (uint32_t)rs_sub.size();
-        n_utts = (uint32_t)ln_sub.size();
-        n_work = (uint32_t)fl_sub.size();
-        jspans = jn.redo_dev;
-        n_jspans = (uint32_t)jn_sub.size();
-        if (!n_tiles && !n_utts && !n_work && !n_futts && !n_autts && !n_apply && !n_jspans && flt_sub.utts.empty())
-            return JB_OK;
-        if ((!flt_sub.utts.empty() && (e = hipMemcpy(fil.redo_dev, flt_sub.utts.data(),
-                                                     sizeof(FilterUtt) * flt_sub.utts.size(), hipMemcpyHostToDevice)) !=
-                                          hipSuccess) ||
-            (n_tiles && (e = hipMemcpy(rs.redo_dev, rs_sub.data(), sizeof(ResampleTile) * n_tiles,
-                                       hipMemcpyHostToDevice)) != hipSuccess) ||
-            (n_utts && (e = hipMemcpy(ln.redo_dev, ln_sub.data(), sizeof(LoudnessUtt) * n_utts,
-                                      hipMemcpyHostToDevice)) != hipSuccess) ||
-            (!ap_sub.empty() && (e = hipMemcpy(ln.apply_redo_dev, ap_sub.data(), sizeof(LoudnessUtt) * ap_sub.size(),
-                                               hipMemcpyHostToDevice)) != hipSuccess) ||
-            (!set_sub.empty() && (e = hipMemcpy(ln.sets_redo_dev, set_sub.data(), sizeof(LoudnessSet) * set_sub.size(),
-                                                hipMemcpyHostToDevice)) != hipSuccess) ||
-            (n_jspans && (e = hipMemcpy(jn.redo_dev, jn_sub.data(), sizeof(JoinSpan) * n_jspans,
-                                        hipMemcpyHostToDevice)) != hipSuccess) ||
-            (n_work && (e = hipMemcpy(fl.redo_dev, fl_sub.data(), sizeof(FlacWork) * n_work, hipMemcpyHostToDevice)) !=
-                           hipSuccess) ||
-            (n_md5 && (e = hipMemcpy(fl.md5_redo_dev, md5_sub.data(), sizeof(uint32_t) * n_md5,
-                                     hipMemcpyHostToDevice)) != hipSuccess) ||
-            (n_futts && (e = hipMemcpy(fm.redo_dev, fm_sub.data(), sizeof(FormatUtt) * n_futts,
-                                       hipMemcpyHostToDevice)) != hipSuccess) ||
-            (n_autts && (e = hipMemcpy(ad.redo_dev, ad_sub.data(), sizeof(AdpcmUtt) * n_autts,
-                                       hipMemcpyHostToDevice)) != hipSuccess))
-            return hip_fail(e, "output chain(redo lists)");
-    }
-    // a run launches every stage of the plan; a redo those that have something to do again
-    if (plan.convert && (!only || n_tiles) &&
-        (e = launch_resample(rs.tables_dev, tiles, n_tiles, plan.converter.i16, rs.lds, st)) != hipSuccess)
-        return hip_fail(e, only ? "k_resample(redo)" : "k_resample");
-    // the filter: behind the converter (its second pass too), in front of the measurement
-    if (filt && (!only || !flt->utts.empty()) &&
-        (e = launch_filter(fil.classes_dev, flt_utts, *flt, fil.st, plan.filter.i16, st)) != hipSuccess)
-        return hip_fail(e, only ? "filter(redo)" : "filter");
-    if (plan.normalize() && (!only || n_utts) &&
-        ((e = launch_loudness_measure(ln.rates_dev, utts, n_utts, lt, ln.st, ln.pk, ln.tp, ln.z, ln.res, ln.true_peak,
-                                      st)) != hipSuccess ||
-         // the groups' gate over the measured members' scratch, the report, then one gain for every member
-         (grouped && (e = launch_loudness_groups(ln.rates_dev, ln.utts_dev, gsets, n_gsets, ln.members_dev, ln.z,
-                                                 ln.res, ln.gres, st)) != hipSuccess) ||
-         (report && (e = launch_loudness_range(ln.rates_dev, utts, n_utts, ln.utts_dev, rsets, n_rsets, ln.members_dev,
-                                               ln.z, ln.sw, ln.mm, ln.r128, st)) != hipSuccess) ||
-         (e = launch_loudness_apply(apply_utts, n_apply, at, ln.res, plan.apply.i16, st)) != hipSuccess))
-        return hip_fail(e, only ? "loudness(redo)" : "loudness");
-    // the join: behind everything that writes the final PCM, in front of everything that encodes it
-    if (joined() && (!only || n_jspans) &&
-        (e = launch_join(plan.join.i16, jspans, n_jspans, jt, jn.members_dev, st)) != hipSuccess)
-        return hip_fail(e, only ? "k_join(redo)" : "k_join");
-    // FLAC: the blocks of the list, the digests of its utterances' now final PCM (on request), then every stream's
-    // offsets, place and header (all of fl.work_dev, redo or not): the pack never sees a digest of replaced PCM
-    if (flac_on && (!only || n_work) &&
-        ((e = launch_flac_encode(flac_p, fl.utts_dev, work, n_work, fl.fsize, st)) != hipSuccess ||
-         (fl.digests && (e = launch_flac_md5(fl.utts_dev, md5_order, n_md5, fl.digests, st)) != hipSuccess) ||
-         (e = launch_flac_pack(flac_p, fl.utts_dev, U, fl.work_dev, n_all_work, fl.fsize, fl.foff, fl.res, fl.total,
-                               fl.out, st, fl.digests, fl.max_points)) != hipSuccess))
-        return hip_fail(e, only ? "FLAC(redo)" : "FLAC");
-    // the sample format last: behind the apply pass, the converter or the hand-off check, whichever wrote last
-    if (fmt && (!only || n_futts) &&
-        (e = launch_format(fmt_p.format, fmt_p.dither, fmt_p.seed, futts, n_futts, ft, st)) != hipSuccess)
-        return hip_fail(e, only ? "k_format(redo)" : "k_format");
-    // IMA ADPCM beside it, of the same final PCM
-    if (adp && (!only || n_autts) &&
-        (e = launch_adpcm(plan.adpcm_src.i16, autts, n_autts, ag, st)) != hipSuccess)
-        return hip_fail(e, only ? "k_adpcm(redo)" : "k_adpcm");
-    if (only && (e = hipStreamSynchronize(st)) != hipSuccess)
-        return hip_fail(e, "output chain(redo)");
-    return JB_OK;
+    const hipError_t e = jb::launch_adpcm(plan.adpcm_src.i16, ad.utts.list, ad.utts.n, ad.utts.total, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_adpcm(redo)" : "k_adpcm");
 }
 
 int OutputChain::check_ready(bool requested, const char *not_run, const char *not_set) const
@@ -957,6 +945,26 @@ int OutputChain::check_ready(bool requested, const char *not_run, const char *no
         return JB_OK;
     set_error(requested ? not_run : not_set);
     return JB_ERR_INVALID;
+}
+
+// The end of the last of `places` (each with a byte offset `off` and `bytes`) in their slab
+template <class T> static uint64_t used_bytes(const std::vector<T> &places)
+{
+    uint64_t total = 0;
+    for (const T &w : places)
+        total = std::max<uint64_t>(total, w.off + w.bytes);
+    return total;
+}
+
+// one copy of the used bytes (not zero-filled first)
+int OutputChain::read_used(const void *src, uint64_t bytes, bool wait, std::unique_ptr<uint8_t[]> *host)
+{
+    host->reset(new (std::nothrow) uint8_t[std::max<uint64_t>(bytes, 1)]);
+    if (!*host) {
+        set_error("out of host memory");
+        return JB_ERR_INVALID;
+    }
+    return bytes ? b.read(src, host->get(), (size_t)bytes, wait) : wait ? b.sync() : JB_OK;
 }
 
 int OutputChain::read_loudness(size_t u, LoudnessResult *r)
@@ -1009,16 +1017,7 @@ int OutputChain::read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_
     res->assign(B, FlacOut{});
     if ((rc = B > 0 ? b.read(fl.res, res->data(), sizeof(FlacOut) * B) : b.sync()))
         return rc;
-    uint64_t total = 0;
-    for (const FlacOut &o : *res)
-        total = std::max<uint64_t>(total, o.off + o.bytes);
-    // one copy of the used bytes (not zero-filled first)
-    host->reset(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
-    if (!*host) {
-        set_error("out of host memory");
-        return JB_ERR_INVALID;
-    }
-    return total ? b.read(fl.out, host->get(), (size_t)total, false) : JB_OK;
+    return read_used(fl.out, used_bytes(*res), false, host);
 }
 
 int OutputChain::read_programme(size_t p, bool i16, void *dst)
@@ -1059,16 +1058,7 @@ int OutputChain::read_adpcm_all(std::unique_ptr<uint8_t[]> *host)
     int rc = check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called");
     if (rc)
         return rc;
-    uint64_t total = 0;
-    for (const OutAdpcmUtt &w : plan.adpcm)
-        total = std::max<uint64_t>(total, w.off + w.bytes);
-    // one copy of the used bytes (not zero-filled first)
-    host->reset(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
-    if (!*host) {
-        set_error("out of host memory");
-        return JB_ERR_INVALID;
-    }
-    return total ? b.read(slab[(size_t)OutSlab::Adpcm], host->get(), (size_t)total) : b.sync();
+    return read_used(slab[(size_t)OutSlab::Adpcm], used_bytes(plan.adpcm), true, host);
 }
 
 int OutputChain::format_ready() const
@@ -1100,16 +1090,7 @@ int OutputChain::read_formatted_all(std::unique_ptr<uint8_t[]> *host)
     int rc = format_ready();
     if (rc)
         return rc;
-    uint64_t total = 0;
-    for (const OutFmtUtt &w : plan.fmt)
-        total = std::max<uint64_t>(total, w.off + w.bytes);
-    // one copy of the used bytes (not zero-filled first)
-    host->reset(new (std::nothrow) uint8_t[std::max<uint64_t>(total, 1)]);
-    if (!*host) {
-        set_error("out of host memory");
-        return JB_ERR_INVALID;
-    }
-    return total ? b.read(slab[(size_t)OutSlab::Fmt], host->get(), (size_t)total) : b.sync();
+    return read_used(slab[(size_t)OutSlab::Fmt], used_bytes(plan.fmt), true, host);
 }
 
 } // namespace jb
