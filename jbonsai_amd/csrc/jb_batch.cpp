@@ -2672,23 +2672,32 @@ int jb_batch_read_flac(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
     return b->out.read_flac(o, dst);
 }
 
-int jb_batch_read_flac_all(jb_batch *hb, uint8_t *const *dst)
+// Each output's share of the host copy of a byte sink's slab into dst[u]; no destination of an output with bytes may
+// be NULL (checked before any copy)
+static int scatter_into(uint8_t *const *dst, const std::vector<jb::ByteSpan> &places, const uint8_t *host)
+{
+    for (size_t u = 0; u < places.size(); u++)
+        if (!dst[u] && places[u].bytes)
+            return JB_ERR_INVALID;
+    for (size_t u = 0; u < places.size(); u++)
+        if (places[u].bytes)
+            memcpy(dst[u], host + places[u].off, (size_t)places[u].bytes);
+    return JB_OK;
+}
+
+// jb_batch_read_{flac,formatted,adpcm}_all: the used bytes of the sink's slab in one copy, then every output's share
+static int read_bytes_all(jb_batch *hb, jb::SynthSink sink, uint8_t *const *dst)
 {
     Batch *b = (Batch *)hb;
     if (!b || (!dst && b->B))
         return JB_ERR_INVALID;
-    std::vector<jb::FlacOut> res;
+    std::vector<jb::ByteSpan> places;
     std::unique_ptr<uint8_t[]> host;
-    int rc = b->out.read_flac_all(&res, &host);
-    if (rc)
-        return rc;
-    for (size_t u = 0; u < res.size(); u++)
-        if (!dst[u] && res[u].bytes)
-            return JB_ERR_INVALID;
-    for (size_t u = 0; u < res.size(); u++)
-        memcpy(dst[u], host.get() + res[u].off, (size_t)res[u].bytes);
-    return JB_OK;
+    const int rc = b->out.read_bytes_all(sink, &places, &host);
+    return rc ? rc : scatter_into(dst, places, host.get());
 }
+
+int jb_batch_read_flac_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Flac, dst); }
 
 int jb_batch_set_format(jb_batch *hb, const jb_format_opts *opts)
 {
@@ -2725,22 +2734,7 @@ int jb_batch_read_formatted(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
 
 int jb_batch_read_formatted_all(jb_batch *hb, uint8_t *const *dst)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || (!dst && b->B))
-        return JB_ERR_INVALID;
-    std::unique_ptr<uint8_t[]> host;
-    int rc = b->out.read_formatted_all(&host);
-    if (rc)
-        return rc;
-    for (size_t u = 0; u < b->out.num_outputs(); u++)
-        if (!dst[u] && b->out.format_place(u).bytes)
-            return JB_ERR_INVALID;
-    for (size_t u = 0; u < b->out.num_outputs(); u++) {
-        const jb::OutFmtUtt &w = b->out.format_place(u);
-        if (w.bytes)
-            memcpy(dst[u], host.get() + w.off, (size_t)w.bytes);
-    }
-    return JB_OK;
+    return read_bytes_all(hb, jb::SynthSink::Formatted, dst);
 }
 
 int jb_batch_set_adpcm(jb_batch *hb, const jb_adpcm_opts *opts)
@@ -2791,25 +2785,7 @@ int jb_batch_read_adpcm(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
     return b->out.read_adpcm(utt, dst);
 }
 
-int jb_batch_read_adpcm_all(jb_batch *hb, uint8_t *const *dst)
-{
-    Batch *b = (Batch *)hb;
-    if (!b || (!dst && b->B))
-        return JB_ERR_INVALID;
-    std::unique_ptr<uint8_t[]> host;
-    int rc = b->out.read_adpcm_all(&host);
-    if (rc)
-        return rc;
-    for (size_t u = 0; u < b->out.num_outputs(); u++)
-        if (!dst[u] && b->out.adpcm_place(u)->bytes)
-            return JB_ERR_INVALID;
-    for (size_t u = 0; u < b->out.num_outputs(); u++) {
-        const jb::OutAdpcmUtt *w = b->out.adpcm_place(u);
-        if (w->bytes)
-            memcpy(dst[u], host.get() + w->off, (size_t)w->bytes);
-    }
-    return JB_OK;
-}
+int jb_batch_read_adpcm_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Adpcm, dst); }
 
 int jb_batch_set_join(jb_batch *hb, const jb_join_utt *req, size_t n)
 {

@@ -1420,55 +1420,445 @@ int jb_write_wav_f64(const char *path, const double *pcm, size_t n, uint32_t fs)
 
 } // extern "C"
 
-// elem = 8: f64 PCM (Engine::synthesize's Vec<f64>); elem = 2: the fused 16-bit sink
-int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                              int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads,
-                              const jb_engine *const *each, bool flac, const jb_flac_opts *flac_opts,
-                              const jb_format_opts *fmt_opts, const jb_adpcm_opts *adpcm_opts, size_t *adpcm_samples,
-                              const jb_flac_meta *flac_meta, const jb_join_opts *join, uint64_t *join_starts)
+namespace {
+
+typedef std::chrono::steady_clock::time_point TimePoint;
+TimePoint now() { return std::chrono::steady_clock::now(); }
+double ms(TimePoint a, TimePoint b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+// fn(u) for every u of [lo, hi) on up to nt host threads; the first failure in utterance order, with its message
+template <class F> int each_utt(size_t lo, size_t hi, unsigned nt, F fn)
 {
-    auto eng = [&](size_t u) { return CENG(each ? each[u] : e); }; // the engine of utterance u
-    if (!e || !pcm || !n_samples || (n_utts && !line_off))
-        return JB_ERR_INVALID;
-    // with a join the call hands out ONE output, the programme of all its utterances
-    const size_t n_outs = join ? 1 : n_utts;
-    for (size_t u = 0; u < n_outs; u++) {
-        pcm[u] = nullptr;
-        n_samples[u] = 0;
+    std::vector<int> rcs(hi - lo, JB_OK);
+    std::vector<std::string> errs(hi - lo);
+    std::atomic<size_t> next{lo};
+    auto work = [&]() {
+        for (size_t u; (u = next.fetch_add(1)) < hi;) {
+            rcs[u - lo] = fn(u);
+            if (rcs[u - lo])
+                errs[u - lo] = jb::g_err; // the worker's thread-local message
+        }
+    };
+    const unsigned n = (unsigned)std::min<size_t>(nt, hi - lo);
+    if (n <= 1) {
+        work();
+    } else {
+        std::vector<std::thread> pool;
+        for (unsigned k = 0; k < n; k++)
+            pool.emplace_back(work);
+        for (auto &t : pool)
+            t.join();
     }
-    std::vector<std::unique_ptr<jb::States>> sts(n_utts);
-    for (size_t u = 0; u < n_utts; u++)
-        sts[u].reset(new jb::States());
+    for (size_t u = lo; u < hi; u++)
+        if (rcs[u - lo]) {
+            jb::set_error(errs[u - lo]);
+            return rcs[u - lo];
+        }
+    return JB_OK;
+}
+
+// Each output's share of the host copy of a byte sink's slab into a malloc'ed buffer of its own: out[u] and its byte
+// count n_out[u]
+int hand_out(const std::vector<jb::ByteSpan> &places, const uint8_t *host, void **out, size_t *n_out)
+{
+    for (size_t u = 0; u < places.size(); u++) {
+        if (!(out[u] = malloc(std::max<size_t>((size_t)places[u].bytes, 1)))) {
+            jb::set_error("out of host memory");
+            return JB_ERR_INVALID;
+        }
+        memcpy(out[u], host + places[u].off, (size_t)places[u].bytes);
+        n_out[u] = (size_t)places[u].bytes;
+    }
+    return JB_OK;
+}
+
+// One engine request on its way through: the state its steps share
+struct SynthRun {
+    const jb::SynthRequest &rq;
+    const size_t elem;  // bytes per PCM sample of the batches: 8 (f64, Engine::synthesize's Vec<f64>) or 2 (the fused
+                        // 16-bit sink)
     // JB_E2E_TIMING=1: time spent in the four phases on stderr (tools/e2e_engine.py); with more than
     // one group they overlap, so their sum exceeds the wall time
-    const bool timing = getenv("JB_E2E_TIMING") && atoi(getenv("JB_E2E_TIMING")) != 0;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b2) {
-        return std::chrono::duration<double, std::milli>(b2 - a).count();
-    };
-    const auto t_start = now();
+    const bool timing;
+    unsigned nt = 1;    // host threads of the front half
+    int32_t device;
+    // the engine's pdf tables on the device: the batches are made from pdf rows, not from blended states (null:
+    // JB_HOST_BLEND)
+    const jb_pdf_set *pset = nullptr;
+    bool one_gain = false;            // per-request loudness scope: one loudness group
+    std::vector<std::unique_ptr<jb::States>> sts; // [n_utts]
+    std::vector<size_t> glo;                      // [ngroups + 1] plan_synth_groups
+    std::vector<std::unique_ptr<jb::Batch>> batches; // [ngroups]
+    double t_front = 0, t_create = 0, t_wait = 0, t_d2h = 0;
+
+    explicit SynthRun(const jb::SynthRequest &r)
+        : rq(r), elem(r.i16 ? sizeof(int16_t) : sizeof(double)),
+          timing(getenv("JB_E2E_TIMING") && atoi(getenv("JB_E2E_TIMING")) != 0), device(r.device)
+    {
+    }
+    size_t ngroups() const { return glo.size() - 1; }
+    const jb::Engine *eng(size_t u) const { return CENG(rq.each ? rq.each[u] : rq.e); } // the engine of utterance u
+
+    int resolve_device();
+    int front_half(size_t lo, size_t hi);
+    int create_batch(size_t g);
+    int apply_conditions(jb::OutputChain &out, size_t lo, size_t hi);
+    int request_programme(jb::OutputChain &out, size_t lo, size_t hi);
+    int launch(size_t g);
+    int wait_group(size_t g);
+    int read_group(size_t g);
+    int read_outputs(jb::Batch *b, size_t lo, size_t hi);
+    int finish(size_t g)
+    {
+        const int rc = wait_group(g);
+        return rc ? rc : read_group(g);
+    }
+    int run_pipelined();
+};
+
+// The host threads of the front half, and the device and pdf set of the request
+int SynthRun::resolve_device()
+{
     // The front half (label parse, tree search, pdf blend, durations: label.rs, model/mod.rs:80-156,
     // duration.rs) is independent per utterance and read-only on the engine: host threads, one
     // utterance at a time each (JB_HOST_THREADS, default min(16, cores)).  It is ~13 ms per 128 s
     // utterance and thread against ~0.7 ms of GPU time.
-    unsigned nt = host_threads_default();
-    if (host_threads && !getenv("JB_HOST_THREADS")) // a multi-device call shares the host cores between its device threads
-        nt = host_threads;
+    nt = host_threads_default();
+    if (rq.host_threads && !getenv("JB_HOST_THREADS")) // a multi-device call shares the host cores between its device threads
+        nt = rq.host_threads;
     // device-side gather + blend unless JB_HOST_BLEND=1 (A/B: both produce the same bits)
     const bool host_blend = getenv("JB_HOST_BLEND") && atoi(getenv("JB_HOST_BLEND")) != 0;
-    const jb_pdf_set *pset = nullptr;
     if (!host_blend) {
         int dev = device;
         if (dev < 0 && hipGetDevice(&dev) != hipSuccess) {
             jb::set_error("no HIP device");
             return JB_ERR_DEVICE;
         }
-        int prc = CENG(e)->pdf_set_for(dev, &pset);
+        int prc = CENG(rq.e)->pdf_set_for(dev, &pset);
         if (prc)
             return prc;
         device = dev;
     }
+    return JB_OK;
+}
+
+// The front half of the utterances [lo, hi) on the host threads: labels to states (sts[u])
+int SynthRun::front_half(size_t lo, size_t hi)
+{
+    const auto t0 = now();
+    const jb::Engine &e = *CENG(rq.e);
+    const char *const *lines = rq.lines;
+    const size_t *line_off = rq.line_off;
     const bool indexed = pset != nullptr;
+    // fewer utterances than threads (a single long text through jb_synthesize): the spare threads split
+    // each utterance's labels
+    const unsigned per_utt = (unsigned)std::max<size_t>(1, nt / std::max<size_t>(1, hi - lo));
+    int rc;
+    if (wants_device_search(e, line_off[hi] - line_off[lo])) {
+        // the group's labels through one launch: parse on the host threads, one slab up, the indices back,
+        // finish on the host threads
+        std::vector<jb::FrontUtt> fu(hi - lo);
+        jb::DeviceIndex dix;
+        std::vector<const jb::Engine *> count(hi - lo);
+        for (size_t u = lo; u < hi; u++)
+            count[u - lo] = eng(u);
+        rc = each_utt(lo, hi, nt, [&](size_t u) {
+            return parse_labels(eng(u)->cond, lines + line_off[u], line_off[u + 1] - line_off[u], fu[u - lo].pl);
+        });
+        const auto t1 = now();
+        if (!rc)
+            rc = front_search_device(e, device, fu.data(), fu.size(), count.data(), &dix);
+        const auto t2 = now();
+        if (!rc)
+            rc = each_utt(lo, hi, nt,
+                          [&](size_t u) { return front_finish(*eng(u), fu[u - lo], *sts[u], indexed, per_utt, &e); });
+        if (timing)
+            fprintf(stderr, "front half of %zu utterance(s): parse %.2f ms, device search %.2f ms, finish %.2f ms\n",
+                    hi - lo, ms(t0, t1), ms(t1, t2), ms(t2, now()));
+    } else {
+        rc = each_utt(lo, hi, nt, [&](size_t u) {
+            return build_states(*eng(u), lines + line_off[u], line_off[u + 1] - line_off[u], *sts[u], indexed, per_utt,
+                                &e);
+        });
+    }
+    t_front += ms(t0, now());
+    return rc;
+}
+
+// The batch of group g (batches[g]) from its utterances' states: indexed or state-level
+int SynthRun::create_batch(size_t g)
+{
+    const size_t lo = glo[g], hi = glo[g + 1];
+    const jb::Engine &e = *CENG(rq.e);
+    jb_batch_opts opts{};
+    opts.device = device;
+    opts.flags = (elem == 2 ? JB_BATCH_PCM_I16 : 0) | e.cond.batch_flags();
+    jb::Batch *b = nullptr;
+    int rc;
+    // one engine per utterance: the vocoder conditions of the utterances (a batch whose entries are all the
+    // same runs as one made without them)
+    std::vector<jb_utt_voc> voc(rq.each ? hi - lo : 0);
+    for (size_t u = lo; rq.each && u < hi; u++)
+        voc[u - lo] = jb_utt_voc{eng(u)->cond.alpha, eng(u)->cond.beta, eng(u)->cond.volume};
+    const jb_utt_voc *vp = rq.each ? voc.data() : nullptr;
+    if (pset) {
+        std::vector<jb_index_utt> iu(hi - lo);
+        for (size_t u = lo; u < hi; u++)
+            iu[u - lo] = sts[u]->iutt;
+        rc = jb_batch_create_indexed_voc(&e.desc, pset, iu.data(), hi - lo, vp, &opts, (jb_batch **)&b);
+    } else {
+        std::vector<jb_state_utt> su(hi - lo);
+        for (size_t u = lo; u < hi; u++)
+            su[u - lo] = sts[u]->utt;
+        rc = jb::Batch::create(&e.desc, su.data(), hi - lo, &opts, &b, nullptr, nullptr, vp);
+    }
+    if (!rc)
+        batches[g].reset(b);
+    return rc;
+}
+
+// The output conditions of the utterances [lo, hi), each its engine's own: rate, filter, loudness, peak mode; then the
+// request's one loudness group and its encoder (the setters' refusals depend on this order)
+int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
+{
+    int rc;
+    // output rate: each utterance's engine's own (a batch whose utterances are all native converts nothing)
+    std::vector<uint32_t> rates(hi - lo);
+    bool any_rate = false;
+    for (size_t u = lo; u < hi; u++) {
+        rates[u - lo] = (uint32_t)eng(u)->cond.output_rate;
+        any_rate = any_rate || rates[u - lo];
+    }
+    if (any_rate && (rc = out.set_output_rate(rates.data(), rates.size())))
+        return rc;
+    // the filter: each utterance's engine's own (a batch whose engines all have none filters nothing)
+    std::vector<jb_filter> filters(hi - lo);
+    bool any_filter = false;
+    for (size_t u = lo; u < hi; u++) {
+        filters[u - lo] = eng(u)->cond.filter;
+        any_filter = any_filter || filters[u - lo].n_sections;
+    }
+    if (any_filter && (rc = out.set_filter(filters.data(), filters.size())))
+        return rc;
+    // loudness: each utterance's engine's own target and ceiling; an engine without a target leaves its
+    // utterance as it is (measured, gain 0 dB: bit for bit the same) when another engine of the batch has one
+    std::vector<double> targets(hi - lo), ceilings(hi - lo);
+    std::vector<uint32_t> modes(hi - lo);
+    bool any_target = false, any_true = false;
+    for (size_t u = lo; u < hi; u++) {
+        const bool on = !std::isnan(eng(u)->cond.loudness_target);
+        targets[u - lo] = on ? eng(u)->cond.loudness_target : NAN;
+        ceilings[u - lo] = on ? eng(u)->cond.peak_ceiling : INFINITY;
+        modes[u - lo] = on ? eng(u)->cond.peak_mode : JB_PEAK_SAMPLE;
+        any_target = any_target || on;
+        any_true = any_true || modes[u - lo] == JB_PEAK_TRUE;
+    }
+    if (any_target && (rc = out.set_loudness(targets.data(), ceilings.data(), targets.size())))
+        return rc;
+    if (any_true && (rc = out.set_peak_mode(modes.data(), modes.size())))
+        return rc;
+    if (one_gain) {
+        const std::vector<uint32_t> group(hi - lo, 0u);
+        if ((rc = out.set_loudness_groups(group.data(), group.size())))
+            return rc;
+    }
+    // the request's encoder
+    if (rq.sink == jb::SynthSink::Flac &&
+        ((rc = out.set_flac(rq.flac)) || (rq.flac_meta && (rc = out.set_flac_meta(rq.flac_meta)))))
+        return rc;
+    if (rq.sink == jb::SynthSink::Formatted && (rc = out.set_format(rq.fmt)))
+        return rc;
+    if (rq.sink == jb::SynthSink::Adpcm && (rc = out.set_adpcm(rq.adpcm)))
+        return rc;
+    return JB_OK;
+}
+
+// The utterances [lo, hi) of the batch as one programme, and each member's start to the caller
+int SynthRun::request_programme(jb::OutputChain &out, size_t lo, size_t hi)
+{
+    const jb_join_opts *join = rq.join;
+    // one programme: the lead in front of the first member, the gap behind every member but the last, the
+    // trail behind the last, the fade at both edges of each, in samples at the output rate
+    const uint32_t hz = out.utt(0).hz;
+    std::vector<jb_join_utt> req(hi - lo, jb_join_utt{});
+    for (size_t u = 0; u < req.size(); u++) {
+        req[u].programme = 0;
+        req[u].fade_in = req[u].fade_out = (uint32_t)std::min<uint64_t>(jb::join_ms_to_samples(join->fade_ms, hz),
+                                                                       0xffffffffu);
+        req[u].pad_before = u == 0 ? jb::join_ms_to_samples(join->lead_ms, hz) : 0;
+        req[u].pad_after = jb::join_ms_to_samples(u + 1 == req.size() ? join->trail_ms : join->gap_ms, hz);
+    }
+    const int rc = out.set_join(req.data(), req.size());
+    if (rc)
+        return rc;
+    for (size_t u = 0; rq.join_starts && u < req.size(); u++)
+        rq.join_starts[lo + u] = out.member_start(u);
+    return JB_OK;
+}
+
+// Group g onto the device: its batch, the requests to its output chain, and the run (not waited for)
+int SynthRun::launch(size_t g)
+{
+    const auto t0 = now();
+    const size_t lo = glo[g], hi = glo[g + 1];
+    int rc = create_batch(g);
+    if (rc)
+        return rc;
+    jb::Batch *b = batches[g].get();
+    if ((rc = apply_conditions(b->out, lo, hi)) || (rq.join && (rc = request_programme(b->out, lo, hi))))
+        return rc;
+    rc = b->run(false);
+    t_create += ms(t0, now());
+    return rc;
+}
+
+// Until the device has finished group g
+int SynthRun::wait_group(size_t g)
+{
+    const auto t0 = now();
+    const int rc = batches[g]->sync();
+    t_wait += ms(t0, now());
+    return rc;
+}
+
+// The outputs of group g into buffers of the caller's (malloc), and its batch back to the pools
+int SynthRun::read_group(size_t g)
+{
+    const auto t0 = now();
+    const int rc = read_outputs(batches[g].get(), glo[g], glo[g + 1]);
+    batches[g].reset(); // device memory and streams back to the pools
+    t_d2h += ms(t0, now());
+    return rc;
+}
+
+// read_group: what the request's sink and join hand out for the utterances [lo, hi) of batch b
+int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
+{
+    void **pcm = rq.out;
+    size_t *n_samples = rq.n_out;
+    if (rq.sink != jb::SynthSink::Pcm) {
+        // the used bytes of the sink's slab in one copy (FLAC: behind the streams' sizes and places, one small copy),
+        // then each output's share
+        std::vector<jb::ByteSpan> places;
+        std::unique_ptr<uint8_t[]> host;
+        int rc = b->out.read_bytes_all(rq.sink, &places, &host);
+        if (rc || (rc = hand_out(places, host.get(), pcm + lo, n_samples + lo)))
+            return rc;
+        for (size_t p = 0; rq.sink == jb::SynthSink::Adpcm && rq.adpcm_samples && p < places.size(); p++)
+            rq.adpcm_samples[lo + p] = rq.join ? (size_t)b->out.programme(p).n : b->out.samples(p);
+        return JB_OK;
+    }
+    if (rq.join) {
+        // the programme's PCM in one copy
+        const size_t ns = (size_t)b->out.programme(0).n;
+        if (!(pcm[0] = malloc(std::max<size_t>(ns, 1) * elem))) {
+            jb::set_error("out of host memory");
+            return JB_ERR_INVALID;
+        }
+        n_samples[0] = ns;
+        return b->out.read_programme(0, elem == 2, pcm[0]);
+    }
+    for (size_t u = lo; u < hi; u++) {
+        const size_t ns = b->out.samples(u - lo);
+        n_samples[u] = ns;
+        if (!ns)
+            continue;
+        // 2 MB alignment + MADV_HUGEPAGE: where transparent huge pages are allowed, the first touch of
+        // the buffer (by the scatter threads) takes 512x fewer faults; free() releases it as usual
+        const size_t bytes = ns * elem;
+        if (bytes >= (4u << 20) && posix_memalign(&pcm[u], 2u << 20, bytes) == 0)
+            madvise(pcm[u], bytes, MADV_HUGEPAGE);
+        else
+            pcm[u] = malloc(bytes);
+        if (!pcm[u]) {
+            jb::set_error("out of host memory");
+            return JB_ERR_INVALID;
+        }
+    }
+    // whole slab through the pinned staging ring into the per-utterance buffers
+    return b->read_pcm_split(pcm + lo, elem);
+}
+
+// More than one group: the main thread runs front half and launch of group after group, a finisher thread waits for
+// and reads them
+int SynthRun::run_pipelined()
+{
+    // f64 in groups (JB_SYNTH_GROUPS only): all groups' GPU work first, then the read-backs, so that no
+    // read-back runs beside kernels
+    const bool d2h_last = elem == 8 && rq.sink != jb::SynthSink::Formatted;
+    // finisher thread: groups in order, as soon as they are launched
+    std::mutex mu;
+    std::condition_variable cv;
+    size_t launched = 0;
+    bool stop = false;
+    int frc = JB_OK;
+    std::string ferr;
+    auto failed = [&](int r) {
+        if (r) {
+            std::lock_guard<std::mutex> lk(mu);
+            frc = r;
+            ferr = jb::g_err;
+        }
+        return r != 0;
+    };
+    std::thread finisher([&]() {
+        for (size_t g = 0; g < ngroups(); g++) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return launched > g || stop; });
+                if (launched <= g)
+                    return;
+            }
+            if (failed(d2h_last ? wait_group(g) : finish(g)))
+                return;
+        }
+        for (size_t g = 0; d2h_last && g < ngroups(); g++)
+            if (failed(read_group(g)))
+                return;
+    });
+    int rc = JB_OK;
+    for (size_t g = 0; g < ngroups() && !rc; g++) {
+        if ((rc = front_half(glo[g], glo[g + 1])) || (rc = launch(g)))
+            break;
+        std::lock_guard<std::mutex> lk(mu);
+        launched = g + 1;
+        cv.notify_all();
+        if (frc)
+            break;
+    }
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        stop = true;
+        cv.notify_all();
+    }
+    finisher.join();
+    if (!rc && frc) {
+        rc = frc;
+        jb::set_error(ferr);
+    }
+    return rc;
+}
+
+} // namespace
+
+int jb::synthesize_batch_impl(const SynthRequest &rq)
+{
+    if (!rq.e || !rq.out || !rq.n_out || (rq.n_utts && !rq.line_off))
+        return JB_ERR_INVALID;
+    // with a join the call hands out ONE output, the programme of all its utterances
+    const size_t n_outs = rq.join ? 1 : rq.n_utts;
+    for (size_t u = 0; u < n_outs; u++) {
+        rq.out[u] = nullptr;
+        rq.n_out[u] = 0;
+    }
+    SynthRun run(rq);
+    run.sts.resize(rq.n_utts);
+    for (auto &st : run.sts)
+        st.reset(new jb::States());
+    const auto t_start = now();
+    int rc = run.resolve_device();
+    if (rc)
+        return rc;
 
     // A large request goes through in two groups: while the GPU works on the first, the host threads
     // run the front half of the second.  With the 16-bit sink the read-back of the first group also
@@ -1477,374 +1867,84 @@ int jb::synthesize_batch_impl(const jb_engine *e, const char *const *lines, cons
     // GPU work comes first and the read-backs after it (203-224 -> 183 ms).  More groups lose (three:
     // 220 ms): smaller batches fill the chip less well and their blocks miss the pool.
     // Groups split the utterances by label count; JB_SYNTH_GROUPS overrides.
-    size_t ngroups = 1;
-    const size_t total_lines = n_utts ? line_off[n_utts] - line_off[0] : 0;
-    if (n_utts >= 8 && total_lines >= 16000)
-        ngroups = 2;
-    if (const char *ev = getenv("JB_SYNTH_GROUPS"))
-        ngroups = (size_t)std::max(1, atoi(ev));
+    const char *ev = getenv("JB_SYNTH_GROUPS");
     // per-request loudness scope: the request is one loudness group, and a group lives in one batch
-    const bool one_gain = CENG(e)->cond.loudness_scope == JB_LOUDNESS_PER_REQUEST &&
-                          !std::isnan(CENG(e)->cond.loudness_target);
-    if (one_gain || join) // (a programme lives in one batch too)
-        ngroups = 1;
-    ngroups = std::max<size_t>(1, std::min(ngroups, n_utts));
-    std::vector<size_t> glo(ngroups + 1, n_utts);
-    glo[0] = 0;
-    for (size_t g = 1, u = 0; g < ngroups; g++) {
-        const size_t want = line_off[0] + total_lines * g / ngroups;
-        while (u < n_utts && line_off[u] < want)
-            u++;
-        glo[g] = std::max(u, glo[g - 1]);
-    }
-    std::vector<std::unique_ptr<jb::Batch>> batches(ngroups);
-    double t_front = 0, t_create = 0, t_wait = 0, t_d2h = 0;
+    run.one_gain = CENG(rq.e)->cond.loudness_scope == JB_LOUDNESS_PER_REQUEST &&
+                   !std::isnan(CENG(rq.e)->cond.loudness_target);
+    // (a programme lives in one batch too)
+    run.glo = plan_synth_groups(rq.line_off, rq.n_utts, ev ? std::max(1, atoi(ev)) : 0, run.one_gain || rq.join);
+    run.batches.resize(run.ngroups());
 
-    auto front = [&](size_t lo, size_t hi) -> int {
-        const auto t0 = now();
-        std::vector<int> rcs(hi - lo, JB_OK);
-        std::vector<std::string> errs(hi - lo);
-        // fewer utterances than threads (a single long text through jb_synthesize): the spare threads split
-        // each utterance's labels
-        const unsigned per_utt = (unsigned)std::max<size_t>(1, nt / std::max<size_t>(1, hi - lo));
-        // fn(u) for every utterance of the group on the host threads; the first failure in utterance order
-        auto each_utt = [&](auto fn) -> int {
-            std::atomic<size_t> next{lo};
-            auto work = [&]() {
-                for (size_t u; (u = next.fetch_add(1)) < hi;) {
-                    rcs[u - lo] = fn(u);
-                    if (rcs[u - lo])
-                        errs[u - lo] = jb::g_err; // the worker's thread-local message
-                }
-            };
-            const unsigned n = (unsigned)std::min<size_t>(nt, hi - lo);
-            if (n <= 1) {
-                work();
-            } else {
-                std::vector<std::thread> pool;
-                for (unsigned k = 0; k < n; k++)
-                    pool.emplace_back(work);
-                for (auto &t : pool)
-                    t.join();
-            }
-            for (size_t u = lo; u < hi; u++)
-                if (rcs[u - lo]) {
-                    jb::set_error(errs[u - lo]);
-                    return rcs[u - lo];
-                }
-            return JB_OK;
-        };
-        int rc;
-        if (wants_device_search(*CENG(e), line_off[hi] - line_off[lo])) {
-            // the group's labels through one launch: parse on the host threads, one slab up, the indices back,
-            // finish on the host threads
-            std::vector<jb::FrontUtt> fu(hi - lo);
-            jb::DeviceIndex dix;
-            std::vector<const jb::Engine *> count(hi - lo);
-            for (size_t u = lo; u < hi; u++)
-                count[u - lo] = eng(u);
-            rc = each_utt([&](size_t u) {
-                return parse_labels(eng(u)->cond, lines + line_off[u], line_off[u + 1] - line_off[u], fu[u - lo].pl);
-            });
-            const auto t1 = now();
-            if (!rc)
-                rc = front_search_device(*CENG(e), device, fu.data(), fu.size(), count.data(), &dix);
-            const auto t2 = now();
-            if (!rc)
-                rc = each_utt(
-                    [&](size_t u) { return front_finish(*eng(u), fu[u - lo], *sts[u], indexed, per_utt, CENG(e)); });
-            if (timing)
-                fprintf(stderr, "front half of %zu utterance(s): parse %.2f ms, device search %.2f ms, finish %.2f ms\n",
-                        hi - lo, ms(t0, t1), ms(t1, t2), ms(t2, now()));
-        } else {
-            rc = each_utt([&](size_t u) {
-                return build_states(*eng(u), lines + line_off[u], line_off[u + 1] - line_off[u], *sts[u], indexed, per_utt,
-                                    CENG(e));
-            });
-        }
-        t_front += ms(t0, now());
-        return rc;
-    };
-    auto launch = [&](size_t g) -> int {
-        const auto t0 = now();
-        const size_t lo = glo[g], hi = glo[g + 1];
-        jb_batch_opts opts{};
-        opts.device = device;
-        opts.flags = (elem == 2 ? JB_BATCH_PCM_I16 : 0) | CENG(e)->cond.batch_flags();
-        jb::Batch *b = nullptr;
-        int rc;
-        // one engine per utterance: the vocoder conditions of the utterances (a batch whose entries are all the
-        // same runs as one made without them)
-        std::vector<jb_utt_voc> voc(each ? hi - lo : 0);
-        for (size_t u = lo; each && u < hi; u++)
-            voc[u - lo] = jb_utt_voc{eng(u)->cond.alpha, eng(u)->cond.beta, eng(u)->cond.volume};
-        const jb_utt_voc *vp = each ? voc.data() : nullptr;
-        if (indexed) {
-            std::vector<jb_index_utt> iu(hi - lo);
-            for (size_t u = lo; u < hi; u++)
-                iu[u - lo] = sts[u]->iutt;
-            rc = jb_batch_create_indexed_voc(&CENG(e)->desc, pset, iu.data(), hi - lo, vp, &opts, (jb_batch **)&b);
-        } else {
-            std::vector<jb_state_utt> su(hi - lo);
-            for (size_t u = lo; u < hi; u++)
-                su[u - lo] = sts[u]->utt;
-            rc = jb::Batch::create(&CENG(e)->desc, su.data(), hi - lo, &opts, &b, nullptr, nullptr, vp);
-        }
-        if (rc)
-            return rc;
-        batches[g].reset(b);
-        // output rate: each utterance's engine's own (a batch whose utterances are all native converts nothing)
-        std::vector<uint32_t> rates(hi - lo);
-        bool any_rate = false;
-        for (size_t u = lo; u < hi; u++) {
-            rates[u - lo] = (uint32_t)eng(u)->cond.output_rate;
-            any_rate = any_rate || rates[u - lo];
-        }
-        if (any_rate && (rc = b->out.set_output_rate(rates.data(), rates.size())))
-            return rc;
-        // loudness: each utterance's engine's own target and ceiling; an engine without a target leaves its
-        // utterance as it is (measured, gain 0 dB: bit for bit the same) when another engine of the batch has one
-        std::vector<double> targets(hi - lo), ceilings(hi - lo);
-        std::vector<uint32_t> modes(hi - lo);
-        bool any_target = false, any_true = false;
-        for (size_t u = lo; u < hi; u++) {
-            const bool on = !std::isnan(eng(u)->cond.loudness_target);
-            targets[u - lo] = on ? eng(u)->cond.loudness_target : NAN;
-            ceilings[u - lo] = on ? eng(u)->cond.peak_ceiling : INFINITY;
-            modes[u - lo] = on ? eng(u)->cond.peak_mode : JB_PEAK_SAMPLE;
-            any_target = any_target || on;
-            any_true = any_true || modes[u - lo] == JB_PEAK_TRUE;
-        }
-        // the filter: each utterance's engine's own (a batch whose engines all have none filters nothing)
-        std::vector<jb_filter> filters(hi - lo);
-        bool any_filter = false;
-        for (size_t u = lo; u < hi; u++) {
-            filters[u - lo] = eng(u)->cond.filter;
-            any_filter = any_filter || filters[u - lo].n_sections;
-        }
-        if (any_filter && (rc = b->out.set_filter(filters.data(), filters.size())))
-            return rc;
-        if (any_target && (rc = b->out.set_loudness(targets.data(), ceilings.data(), targets.size())))
-            return rc;
-        if (any_true && (rc = b->out.set_peak_mode(modes.data(), modes.size())))
-            return rc;
-        if (one_gain) {
-            const std::vector<uint32_t> group(hi - lo, 0u);
-            if ((rc = b->out.set_loudness_groups(group.data(), group.size())))
-                return rc;
-        }
-        if (flac && ((rc = b->out.set_flac(flac_opts)) || (flac_meta && (rc = b->out.set_flac_meta(flac_meta)))))
-            return rc;
-        if (fmt_opts && (rc = b->out.set_format(fmt_opts)))
-            return rc;
-        if (adpcm_opts && (rc = b->out.set_adpcm(adpcm_opts)))
-            return rc;
-        if (join) {
-            // one programme: the lead in front of the first member, the gap behind every member but the last, the
-            // trail behind the last, the fade at both edges of each, in samples at the output rate
-            const uint32_t hz = b->out.utt(0).hz;
-            std::vector<jb_join_utt> req(hi - lo, jb_join_utt{});
-            for (size_t u = 0; u < req.size(); u++) {
-                req[u].programme = 0;
-                req[u].fade_in = req[u].fade_out = (uint32_t)std::min<uint64_t>(jb::join_ms_to_samples(join->fade_ms, hz),
-                                                                               0xffffffffu);
-                req[u].pad_before = u == 0 ? jb::join_ms_to_samples(join->lead_ms, hz) : 0;
-                req[u].pad_after = jb::join_ms_to_samples(u + 1 == req.size() ? join->trail_ms : join->gap_ms, hz);
-            }
-            if ((rc = b->out.set_join(req.data(), req.size())))
-                return rc;
-            for (size_t u = 0; join_starts && u < req.size(); u++)
-                join_starts[lo + u] = b->out.member_start(u);
-        }
-        rc = b->run(false);
-        t_create += ms(t0, now());
-        return rc;
-    };
-    auto finish_sync = [&](size_t g) -> int {
-        const auto t0 = now();
-        const int rc = batches[g]->sync();
-        t_wait += ms(t0, now());
-        return rc;
-    };
-    auto finish_read = [&](size_t g) -> int {
-        const size_t lo = glo[g], hi = glo[g + 1];
-        jb::Batch *b = batches[g].get();
-        int rc = JB_OK;
-        const auto t0 = now();
-        if (flac) {
-            // the streams' sizes and places (one small copy), then the used bytes of the compact slab in one copy
-            std::vector<jb::FlacOut> res;
-            std::unique_ptr<uint8_t[]> host;
-            if ((rc = b->out.read_flac_all(&res, &host)))
-                return rc;
-            for (size_t u = lo; u < lo + b->out.num_outputs(); u++) {
-                const jb::FlacOut &o = res[u - lo];
-                if (!(pcm[u] = malloc(std::max<size_t>((size_t)o.bytes, 1)))) {
-                    jb::set_error("out of host memory");
-                    return JB_ERR_INVALID;
-                }
-                memcpy(pcm[u], host.get() + o.off, (size_t)o.bytes);
-                n_samples[u] = (size_t)o.bytes;
-            }
-            batches[g].reset();
-            t_d2h += ms(t0, now());
-            return JB_OK;
-        }
-        if (fmt_opts) {
-            // the used bytes of the format slab in one copy, then each utterance's share
-            std::unique_ptr<uint8_t[]> host;
-            if ((rc = b->out.read_formatted_all(&host)))
-                return rc;
-            for (size_t u = lo; u < lo + b->out.num_outputs(); u++) {
-                const jb::OutFmtUtt &w = b->out.format_place(u - lo);
-                if (!(pcm[u] = malloc(std::max<size_t>((size_t)w.bytes, 1)))) {
-                    jb::set_error("out of host memory");
-                    return JB_ERR_INVALID;
-                }
-                memcpy(pcm[u], host.get() + w.off, (size_t)w.bytes);
-                n_samples[u] = (size_t)w.bytes;
-            }
-            batches[g].reset();
-            t_d2h += ms(t0, now());
-            return JB_OK;
-        }
-        if (adpcm_opts) {
-            // the used bytes of the ADPCM slab in one copy, then each utterance's blocks
-            std::unique_ptr<uint8_t[]> host;
-            if ((rc = b->out.read_adpcm_all(&host)))
-                return rc;
-            for (size_t u = lo; u < lo + b->out.num_outputs(); u++) {
-                const jb::OutAdpcmUtt &w = *b->out.adpcm_place(u - lo);
-                if (!(pcm[u] = malloc(std::max<size_t>((size_t)w.bytes, 1)))) {
-                    jb::set_error("out of host memory");
-                    return JB_ERR_INVALID;
-                }
-                memcpy(pcm[u], host.get() + w.off, (size_t)w.bytes);
-                n_samples[u] = (size_t)w.bytes;
-                if (adpcm_samples)
-                    adpcm_samples[u] = join ? (size_t)b->out.programme(u - lo).n : b->out.samples(u - lo);
-            }
-            batches[g].reset();
-            t_d2h += ms(t0, now());
-            return JB_OK;
-        }
-        if (join) {
-            // the programme's PCM in one copy
-            const size_t ns = (size_t)b->out.programme(0).n;
-            if (!(pcm[0] = malloc(std::max<size_t>(ns, 1) * elem))) {
-                jb::set_error("out of host memory");
-                return JB_ERR_INVALID;
-            }
-            n_samples[0] = ns;
-            rc = b->out.read_programme(0, elem == 2, pcm[0]);
-            batches[g].reset();
-            t_d2h += ms(t0, now());
-            return rc;
-        }
-        for (size_t u = lo; u < hi; u++) {
-            const size_t ns = b->out.samples(u - lo);
-            n_samples[u] = ns;
-            if (!ns)
-                continue;
-            // 2 MB alignment + MADV_HUGEPAGE: where transparent huge pages are allowed, the first touch of
-            // the buffer (by the scatter threads) takes 512x fewer faults; free() releases it as usual
-            const size_t bytes = ns * elem;
-            if (bytes >= (4u << 20) && posix_memalign(&pcm[u], 2u << 20, bytes) == 0)
-                madvise(pcm[u], bytes, MADV_HUGEPAGE);
-            else
-                pcm[u] = malloc(bytes);
-            if (!pcm[u]) {
-                jb::set_error("out of host memory");
-                return JB_ERR_INVALID;
-            }
-        }
-        // whole slab through the pinned staging ring into the per-utterance buffers
-        rc = b->read_pcm_split(pcm + lo, elem);
-        batches[g].reset(); // device memory and streams back to the pools
-        t_d2h += ms(t0, now());
-        return rc;
-    };
-    auto finish = [&](size_t g) -> int {
-        const int rc = finish_sync(g);
-        return rc ? rc : finish_read(g);
-    };
-    // f64 in groups (JB_SYNTH_GROUPS only): all groups' GPU work first, then the read-backs, so that no
-    // read-back runs beside kernels
-    const bool d2h_last = elem == 8 && !fmt_opts;
-
-    int rc = JB_OK;
-    if (ngroups == 1) {
-        if (!(rc = front(0, n_utts)) && !(rc = launch(0)))
-            rc = finish(0);
+    if (run.ngroups() == 1) {
+        if (!(rc = run.front_half(0, rq.n_utts)) && !(rc = run.launch(0)))
+            rc = run.finish(0);
     } else {
-        // finisher thread: groups in order, as soon as they are launched
-        std::mutex mu;
-        std::condition_variable cv;
-        size_t launched = 0;
-        bool stop = false;
-        int frc = JB_OK;
-        std::string ferr;
-        std::thread finisher([&]() {
-            for (size_t g = 0; g < ngroups; g++) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return launched > g || stop; });
-                    if (launched <= g)
-                        return;
-                }
-                const int r = d2h_last ? finish_sync(g) : finish(g);
-                if (r) {
-                    std::lock_guard<std::mutex> lk(mu);
-                    frc = r;
-                    ferr = jb::g_err;
-                    return;
-                }
-            }
-            for (size_t g = 0; d2h_last && g < ngroups; g++) {
-                const int r = finish_read(g);
-                if (r) {
-                    std::lock_guard<std::mutex> lk(mu);
-                    frc = r;
-                    ferr = jb::g_err;
-                    return;
-                }
-            }
-        });
-        for (size_t g = 0; g < ngroups && !rc; g++) {
-            if ((rc = front(glo[g], glo[g + 1])) || (rc = launch(g)))
-                break;
-            std::lock_guard<std::mutex> lk(mu);
-            launched = g + 1;
-            cv.notify_all();
-            if (frc)
-                break;
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            stop = true;
-            cv.notify_all();
-        }
-        finisher.join();
-        if (!rc && frc) {
-            rc = frc;
-            jb::set_error(ferr);
-        }
+        rc = run.run_pipelined();
     }
     if (rc) {
-        batches.clear();
+        run.batches.clear();
         for (size_t u = 0; u < n_outs; u++) {
-            free(pcm[u]);
-            pcm[u] = nullptr;
-            n_samples[u] = 0;
+            free(rq.out[u]);
+            rq.out[u] = nullptr;
+            rq.n_out[u] = 0;
         }
         return rc;
     }
-    if (timing)
+    if (run.timing)
         fprintf(stderr,
                 "jb_synthesize_batch: %zu group(s), wall %.1f ms; front half %.1f ms, upload+create+enqueue %.1f ms, "
                 "wait for the GPU %.1f ms, D2H %.1f ms\n",
-                ngroups, ms(t_start, now()), t_front, t_create, t_wait, t_d2h);
+                run.ngroups(), ms(t_start, now()), run.t_front, run.t_create, run.t_wait, run.t_d2h);
     return JB_OK;
+}
+
+// The request of a single-engine entry for PCM in f64; a byte sink is chosen with one of request_*() below
+static jb::SynthRequest batch_request(const jb_engine *e, const char *const *lines, const size_t *line_off,
+                                      size_t n_utts, int32_t device, void **out, size_t *n_out)
+{
+    jb::SynthRequest rq;
+    rq.e = e;
+    rq.lines = lines;
+    rq.line_off = line_off;
+    rq.n_utts = n_utts;
+    rq.device = device;
+    rq.out = out;
+    rq.n_out = n_out;
+    return rq;
+}
+
+// The sink of a request with the PCM type its encoder reads: FLAC and IMA ADPCM 16 bits, the sample formats f64
+static jb::SynthRequest &request_flac(jb::SynthRequest &rq, const jb_flac_opts *opts, const jb_flac_meta *meta)
+{
+    rq.sink = jb::SynthSink::Flac;
+    rq.i16 = true;
+    rq.flac = opts;
+    rq.flac_meta = meta;
+    return rq;
+}
+
+static jb::SynthRequest &request_formatted(jb::SynthRequest &rq, const jb_format_opts *opts)
+{
+    rq.sink = jb::SynthSink::Formatted;
+    rq.i16 = false;
+    rq.fmt = opts;
+    return rq;
+}
+
+static jb::SynthRequest &request_adpcm(jb::SynthRequest &rq, const jb_adpcm_opts *opts, size_t *n_samples)
+{
+    rq.sink = jb::SynthSink::Adpcm;
+    rq.i16 = true;
+    rq.adpcm = opts;
+    rq.adpcm_samples = n_samples;
+    return rq;
+}
+
+static jb::SynthRequest &request_join(jb::SynthRequest &rq, const jb_join_opts *join, uint64_t *starts)
+{
+    rq.join = join;
+    rq.join_starts = starts;
+    return rq;
 }
 
 extern "C" {
@@ -1852,13 +1952,15 @@ extern "C" {
 int jb_synthesize_batch(const jb_engine *e, const char *const *lines, const size_t *line_off,
                         size_t n_utts, int32_t device, double **pcm, size_t *n_samples)
 {
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(double), (void **)pcm, n_samples);
+    return jb::synthesize_batch_impl(batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples));
 }
 
 int jb_synthesize_batch_i16(const jb_engine *e, const char *const *lines, const size_t *line_off,
                             size_t n_utts, int32_t device, int16_t **pcm, size_t *n_samples)
 {
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)pcm, n_samples);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
+    rq.i16 = true;
+    return jb::synthesize_batch_impl(rq);
 }
 
 void jb_pcm_i16_free(int16_t *p) { free(p); }
@@ -1921,21 +2023,19 @@ static int check_engines(const jb_engine *const *engines, size_t n)
     return JB_OK;
 }
 
-static int synthesize_each(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
-                           size_t n_utts, int32_t device, size_t elem, void **pcm, size_t *n_samples,
-                           bool flac = false, const jb_flac_opts *flac_opts = nullptr,
-                           const jb_format_opts *fmt_opts = nullptr, const jb_adpcm_opts *adpcm_opts = nullptr,
-                           size_t *adpcm_samples = nullptr, const jb_flac_meta *flac_meta = nullptr)
+// rq (its engine fields not yet set) with utterance u under engines[u]
+static int synthesize_each(const jb_engine *const *engines, jb::SynthRequest rq)
 {
-    if (!pcm || !n_samples || (n_utts && !line_off))
+    if (!rq.out || !rq.n_out || (rq.n_utts && !rq.line_off))
         return JB_ERR_INVALID;
-    if (n_utts == 0)
+    if (rq.n_utts == 0)
         return JB_OK;
-    const int rc = check_engines(engines, n_utts);
+    const int rc = check_engines(engines, rq.n_utts);
     if (rc)
         return rc;
-    return jb::synthesize_batch_impl(engines[0], lines, line_off, n_utts, device, elem, pcm, n_samples, 0, engines,
-                                     flac, flac_opts, fmt_opts, adpcm_opts, adpcm_samples, flac_meta);
+    rq.e = engines[0];
+    rq.each = engines;
+    return jb::synthesize_batch_impl(rq);
 }
 
 extern "C" {
@@ -1943,13 +2043,15 @@ extern "C" {
 int jb_synthesize_batch_each(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
                              size_t n_utts, int32_t device, double **pcm, size_t *n_samples)
 {
-    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(double), (void **)pcm, n_samples);
+    return synthesize_each(engines, batch_request(nullptr, lines, line_off, n_utts, device, (void **)pcm, n_samples));
 }
 
 int jb_synthesize_batch_each_i16(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
                                  size_t n_utts, int32_t device, int16_t **pcm, size_t *n_samples)
 {
-    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)pcm, n_samples);
+    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)pcm, n_samples);
+    rq.i16 = true;
+    return synthesize_each(engines, rq);
 }
 
 int jb_synthesize_batch_flac_meta(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
@@ -1959,8 +2061,8 @@ int jb_synthesize_batch_flac_meta(const jb_engine *e, const char *const *lines, 
     int rc = jb::flac_check_opts(opts, nullptr);
     if (rc || (rc = jb::flac_check_meta(meta, nullptr)))
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, 0,
-                                     nullptr, true, opts, nullptr, nullptr, nullptr, meta);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)flac, n_bytes);
+    return jb::synthesize_batch_impl(request_flac(rq, opts, meta));
 }
 
 int jb_synthesize_batch_flac(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
@@ -1976,8 +2078,8 @@ int jb_synthesize_batch_each_flac_meta(const jb_engine *const *engines, const ch
     int rc = jb::flac_check_opts(opts, nullptr);
     if (rc || (rc = jb::flac_check_meta(meta, nullptr)))
         return rc;
-    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, true,
-                           opts, nullptr, nullptr, nullptr, meta);
+    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)flac, n_bytes);
+    return synthesize_each(engines, request_flac(rq, opts, meta));
 }
 
 int jb_synthesize_batch_each_flac(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
@@ -2017,8 +2119,8 @@ int jb_synthesize_batch_formatted(const jb_engine *e, const char *const *lines, 
     int rc = check_format_entry(opts, "jb_synthesize_batch_formatted");
     if (rc)
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(double), (void **)bytes, n_bytes, 0,
-                                     nullptr, false, nullptr, opts);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return jb::synthesize_batch_impl(request_formatted(rq, opts));
 }
 
 int jb_synthesize_batch_each_formatted(const jb_engine *const *engines, const char *const *lines,
@@ -2028,8 +2130,8 @@ int jb_synthesize_batch_each_formatted(const jb_engine *const *engines, const ch
     int rc = check_format_entry(opts, "jb_synthesize_batch_each_formatted");
     if (rc)
         return rc;
-    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(double), (void **)bytes, n_bytes, false,
-                           nullptr, opts);
+    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return synthesize_each(engines, request_formatted(rq, opts));
 }
 
 int jb_synthesize_formatted(const jb_engine *e, const char *const *lines, size_t n, const jb_format_opts *opts,
@@ -2048,8 +2150,8 @@ int jb_synthesize_batch_adpcm(const jb_engine *e, const char *const *lines, cons
     int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_batch_adpcm");
     if (rc)
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)bytes, n_bytes, 0,
-                                     nullptr, false, nullptr, nullptr, opts, n_samples);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return jb::synthesize_batch_impl(request_adpcm(rq, opts, n_samples));
 }
 
 int jb_synthesize_batch_each_adpcm(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
@@ -2059,8 +2161,8 @@ int jb_synthesize_batch_each_adpcm(const jb_engine *const *engines, const char *
     int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_batch_each_adpcm");
     if (rc)
         return rc;
-    return synthesize_each(engines, lines, line_off, n_utts, device, sizeof(int16_t), (void **)bytes, n_bytes, false,
-                           nullptr, nullptr, opts, n_samples);
+    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return synthesize_each(engines, request_adpcm(rq, opts, n_samples));
 }
 
 int jb_synthesize_adpcm(const jb_engine *e, const char *const *lines, size_t n, const jb_adpcm_opts *opts,
@@ -2101,8 +2203,8 @@ int jb_synthesize_programme(const jb_engine *e, const char *const *lines, const 
     int rc = check_join_entry(join, n_utts, "jb_synthesize_programme");
     if (rc)
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(double), (void **)pcm, n_samples, 0,
-                                     nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr, join, starts);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
+    return jb::synthesize_batch_impl(request_join(rq, join, starts));
 }
 
 int jb_synthesize_programme_i16(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
@@ -2112,8 +2214,9 @@ int jb_synthesize_programme_i16(const jb_engine *e, const char *const *lines, co
     int rc = check_join_entry(join, n_utts, "jb_synthesize_programme_i16");
     if (rc)
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)pcm, n_samples, 0,
-                                     nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr, join, starts);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
+    rq.i16 = true;
+    return jb::synthesize_batch_impl(request_join(rq, join, starts));
 }
 
 int jb_synthesize_programme_flac_meta(const jb_engine *e, const char *const *lines, const size_t *line_off,
@@ -2124,8 +2227,8 @@ int jb_synthesize_programme_flac_meta(const jb_engine *e, const char *const *lin
     if (rc || (rc = jb::flac_check_meta(meta, nullptr)) ||
         (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_flac_meta")))
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)flac, n_bytes, 0,
-                                     nullptr, true, opts, nullptr, nullptr, nullptr, meta, join, starts);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)flac, n_bytes);
+    return jb::synthesize_batch_impl(request_join(request_flac(rq, opts, meta), join, starts));
 }
 
 int jb_synthesize_programme_formatted(const jb_engine *e, const char *const *lines, const size_t *line_off,
@@ -2135,8 +2238,8 @@ int jb_synthesize_programme_formatted(const jb_engine *e, const char *const *lin
     int rc = check_format_entry(opts, "jb_synthesize_programme_formatted");
     if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_formatted")))
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(double), (void **)bytes, n_bytes, 0,
-                                     nullptr, false, nullptr, opts, nullptr, nullptr, nullptr, join, starts);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return jb::synthesize_batch_impl(request_join(request_formatted(rq, opts), join, starts));
 }
 
 int jb_synthesize_programme_adpcm(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
@@ -2146,8 +2249,8 @@ int jb_synthesize_programme_adpcm(const jb_engine *e, const char *const *lines, 
     int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_programme_adpcm");
     if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_adpcm")))
         return rc;
-    return jb::synthesize_batch_impl(e, lines, line_off, n_utts, device, sizeof(int16_t), (void **)bytes, n_bytes, 0,
-                                     nullptr, false, nullptr, nullptr, opts, n_samples, nullptr, join, starts);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return jb::synthesize_batch_impl(request_join(request_adpcm(rq, opts, n_samples), join, starts));
 }
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)

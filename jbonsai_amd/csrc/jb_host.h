@@ -34,21 +34,36 @@ struct NoiseDev {
 int noise_table(int device, size_t need, std::shared_ptr<NoiseDev> *out);
 void release_cached_memory(); // empties the per-device pools of finished batches' memory
 void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE_POOL_MB at start)
-// jb_synthesize_batch[_i16] on one device (jb_engine.cpp); host_threads = 0: default front-half thread count;
-// each != null (jb_synthesize_batch_each[_i16], engines checked by the caller): utterance u under each[u]'s Condition,
-// e = each[0] for what the engines share; flac (elem 2): pcm[u] / n_samples[u] receive utterance u's FLAC stream
-// and its byte count instead (jb_synthesize*_flac); fmt_opts (elem 8): its bytes in that sample format and their
-// count (jb_synthesize*_formatted); adpcm_opts (elem 2): its IMA ADPCM blocks and their byte count, the samples they
-// encode in adpcm_samples[u] where that is not null (jb_synthesize*_adpcm); flac_meta: the streams' MD5 / SEEKTABLE
-// request (jb_synthesize*_flac_meta; null: none); join (jb_synthesize_programme*): all utterances are one programme
-// and pcm[0] / n_samples[0] alone receive it, join_starts[u] (may be null) each member's first sample
-int synthesize_batch_impl(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                          int32_t device, size_t elem, void **pcm, size_t *n_samples, unsigned host_threads = 0,
-                          const jb_engine *const *each = nullptr, bool flac = false,
-                          const jb_flac_opts *flac_opts = nullptr, const jb_format_opts *fmt_opts = nullptr,
-                          const jb_adpcm_opts *adpcm_opts = nullptr, size_t *adpcm_samples = nullptr,
-                          const jb_flac_meta *flac_meta = nullptr, const jb_join_opts *join = nullptr,
-                          uint64_t *join_starts = nullptr);
+// What an engine-level call hands out per utterance (or per programme): PCM, or the bytes of one of the encoders
+enum class SynthSink { Pcm, Flac, Formatted, Adpcm };
+struct ByteSpan { // an output's place in the host copy of a byte sink's slab (OutputChain::read_bytes_all)
+    uint64_t off, bytes;
+};
+// One engine request on one device: what the jb_synthesize* entries (jb_engine.cpp, jb_multi.cpp) ask of
+// synthesize_batch_impl.  Exactly one sink; the options of the others stay null
+struct SynthRequest {
+    const jb_engine *e = nullptr;            // the engine; with `each`, each[0]: what the engines share
+    const jb_engine *const *each = nullptr;  // jb_synthesize_batch_each*: utterance u under each[u]'s Condition (the
+                                             // engines checked by the caller); null: e for all
+    const char *const *lines = nullptr;      // utterance u is lines[line_off[u] .. line_off[u + 1])
+    const size_t *line_off = nullptr;
+    size_t n_utts = 0;
+    int32_t device = -1;
+    unsigned host_threads = 0;               // 0: the default front-half thread count
+    SynthSink sink = SynthSink::Pcm;
+    bool i16 = false;                        // the batch's PCM in 16 bits (Pcm: what is handed out; Flac and Adpcm
+                                             // encode it) or in f64 (Formatted reads f64)
+    const jb_flac_opts *flac = nullptr;      // Flac: both may be null (the defaults; no MD5 / SEEKTABLE request)
+    const jb_flac_meta *flac_meta = nullptr;
+    const jb_format_opts *fmt = nullptr;     // Formatted
+    const jb_adpcm_opts *adpcm = nullptr;    // Adpcm; adpcm_samples[u] (may be null): the samples output u's blocks encode
+    size_t *adpcm_samples = nullptr;
+    const jb_join_opts *join = nullptr;      // jb_synthesize_programme*: all utterances are one programme, the one
+    uint64_t *join_starts = nullptr;         // output; join_starts[u] (may be null): each member's first sample
+    void **out = nullptr;                    // [n_utts], or [1] with a join: malloc'ed PCM or bytes of each output
+    size_t *n_out = nullptr;                 // its samples (Pcm) or bytes
+};
+int synthesize_batch_impl(const SynthRequest &rq);
 // A stream / a device block from the per-device pools that batches draw from (jb_batch.cpp), for work outside a
 // batch; *got is the block's pooled size, which pooled_block_free takes back
 hipError_t pooled_stream_acquire(int device, hipStream_t *st);
@@ -452,19 +467,16 @@ struct OutputChain {
     int read_loudness_range(size_t u, bool of_group, LoudnessRange *r);
     int read_flac_index(size_t u, FlacOut *o);
     int read_flac(const FlacOut &o, uint8_t *dst);
-    // every stream's size and place, and the compact slab's used bytes in one copy
-    int read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_t[]> *host);
-    // the formatted bytes: utterance u's count (known once a format is set), its bytes, or the used part of the
-    // slab in one copy (utterance u at host + format_place(u).off)
+    // the formatted bytes: utterance u's count (known once a format is set) and its bytes
     int format_size(size_t u, size_t *n_bytes) const;
     int read_formatted(size_t u, uint8_t *dst);
-    int read_formatted_all(std::unique_ptr<uint8_t[]> *host);
-    const OutFmtUtt &format_place(size_t u) const { return plan.fmt[u]; }
     // the ADPCM blocks: utterance u's place, byte count and block size (known once the request is made; null without
-    // one), its bytes, or the used part of the slab in one copy (utterance u at host + adpcm_place(u)->off)
+    // one) and its bytes
     const OutAdpcmUtt *adpcm_place(size_t u) const;
     int read_adpcm(size_t u, uint8_t *dst);
-    int read_adpcm_all(std::unique_ptr<uint8_t[]> *host);
+    // every output of a byte sink: the used part of its slab in one copy, output u at host + places[u].off (FLAC:
+    // the streams' sizes and places come from the device's index, one small copy first; the others' from the plan)
+    int read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host);
     // the join: what the encoders' entries index (the programmes, or the utterances without a request), an
     // utterance's programme (-1 without a request) and start, a programme's place, members and PCM
     bool joined() const { return plan.join.slab != OutSlab::None; }

@@ -90,7 +90,7 @@ int check_devices(const int32_t *devices, size_t n_devices)
 } // namespace
 
 static int synthesize_multi(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                            const int32_t *devices, size_t n_devices, size_t elem, void **pcm, size_t *n_samples)
+                            const int32_t *devices, size_t n_devices, bool i16, void **pcm, size_t *n_samples)
 {
     if (!e || !pcm || !n_samples || (n_utts && (!line_off || !lines)))
         return JB_ERR_INVALID;
@@ -140,8 +140,17 @@ static int synthesize_multi(const jb_engine *e, const char *const *lines, const 
         Share &s = sh[p];
         if (s.utts.empty())
             return JB_OK;
-        return synthesize_batch_impl(e, s.lines.data(), s.off.data(), s.utts.size(), devices[p], elem, s.pcm.data(),
-                                     s.ns.data(), n_devices > 1 ? per_dev : 0);
+        SynthRequest rq;
+        rq.e = e;
+        rq.lines = s.lines.data();
+        rq.line_off = s.off.data();
+        rq.n_utts = s.utts.size();
+        rq.device = devices[p];
+        rq.host_threads = n_devices > 1 ? per_dev : 0;
+        rq.i16 = i16;
+        rq.out = s.pcm.data();
+        rq.n_out = s.ns.data();
+        return synthesize_batch_impl(rq);
     });
     if (rc) {
         for (Share &s : sh)
@@ -232,16 +241,14 @@ int jb_synthesize_batch_multi(const jb_engine *e, const char *const *label_lines
                               size_t n_utts, const int32_t *devices, size_t n_devices, double **pcm,
                               size_t *n_samples)
 {
-    return jb::synthesize_multi(e, label_lines, line_off, n_utts, devices, n_devices, sizeof(double), (void **)pcm,
-                                n_samples);
+    return jb::synthesize_multi(e, label_lines, line_off, n_utts, devices, n_devices, false, (void **)pcm, n_samples);
 }
 
 int jb_synthesize_batch_i16_multi(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
                                   size_t n_utts, const int32_t *devices, size_t n_devices, int16_t **pcm,
                                   size_t *n_samples)
 {
-    return jb::synthesize_multi(e, label_lines, line_off, n_utts, devices, n_devices, sizeof(int16_t), (void **)pcm,
-                                n_samples);
+    return jb::synthesize_multi(e, label_lines, line_off, n_utts, devices, n_devices, true, (void **)pcm, n_samples);
 }
 
 

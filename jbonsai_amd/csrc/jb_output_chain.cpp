@@ -1008,18 +1008,6 @@ int OutputChain::read_flac_index(size_t u, FlacOut *o)
 
 int OutputChain::read_flac(const FlacOut &o, uint8_t *dst) { return b.read(fl.out + o.off, dst, (size_t)o.bytes, false); }
 
-int OutputChain::read_flac_all(std::vector<FlacOut> *res, std::unique_ptr<uint8_t[]> *host)
-{
-    int rc = flac_ready();
-    if (rc)
-        return rc;
-    const size_t B = num_outputs();
-    res->assign(B, FlacOut{});
-    if ((rc = B > 0 ? b.read(fl.res, res->data(), sizeof(FlacOut) * B) : b.sync()))
-        return rc;
-    return read_used(fl.out, used_bytes(*res), false, host);
-}
-
 int OutputChain::read_programme(size_t p, bool i16, void *dst)
 {
     int rc = check_ready(joined(), "join: the batch has not run", "join: jb_batch_set_join was not called");
@@ -1053,14 +1041,6 @@ int OutputChain::read_adpcm(size_t u, uint8_t *dst)
     return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Adpcm] + w.off, dst, (size_t)w.bytes) : b.sync();
 }
 
-int OutputChain::read_adpcm_all(std::unique_ptr<uint8_t[]> *host)
-{
-    int rc = check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called");
-    if (rc)
-        return rc;
-    return read_used(slab[(size_t)OutSlab::Adpcm], used_bytes(plan.adpcm), true, host);
-}
-
 int OutputChain::format_ready() const
 {
     return check_ready(fmt_on, "format: the batch has not run", "format: jb_batch_set_format was not called");
@@ -1085,12 +1065,29 @@ int OutputChain::read_formatted(size_t u, uint8_t *dst)
     return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Fmt] + w.off, dst, (size_t)w.bytes) : b.sync();
 }
 
-int OutputChain::read_formatted_all(std::unique_ptr<uint8_t[]> *host)
+int OutputChain::read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host)
 {
-    int rc = format_ready();
+    int rc = sink == SynthSink::Flac        ? flac_ready()
+             : sink == SynthSink::Formatted ? format_ready()
+             : sink == SynthSink::Adpcm
+                 ? check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called")
+                 : JB_ERR_INVALID;
     if (rc)
         return rc;
-    return read_used(slab[(size_t)OutSlab::Fmt], used_bytes(plan.fmt), true, host);
+    places->assign(num_outputs(), ByteSpan{});
+    if (sink == SynthSink::Flac) {
+        std::vector<FlacOut> res(places->size());
+        if ((rc = res.empty() ? b.sync() : b.read(fl.res, res.data(), sizeof(FlacOut) * res.size())))
+            return rc;
+        for (size_t u = 0; u < res.size(); u++)
+            (*places)[u] = ByteSpan{res[u].off, res[u].bytes};
+        return read_used(fl.out, used_bytes(*places), false, host);
+    }
+    for (size_t u = 0; u < places->size(); u++)
+        (*places)[u] = sink == SynthSink::Formatted ? ByteSpan{plan.fmt[u].off, plan.fmt[u].bytes}
+                                                    : ByteSpan{plan.adpcm[u].off, plan.adpcm[u].bytes};
+    return read_used(slab[(size_t)(sink == SynthSink::Formatted ? OutSlab::Fmt : OutSlab::Adpcm)], used_bytes(*places),
+                     true, host);
 }
 
 } // namespace jb

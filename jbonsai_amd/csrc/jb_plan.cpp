@@ -323,4 +323,26 @@ StreamMode plan_stream_mode(const jb_stream_desc &s, uint32_t si, uint32_t flags
     return m;
 }
 
+std::vector<size_t> plan_synth_groups(const size_t *line_off, size_t n_utts, int forced, bool one_batch)
+{
+    size_t ngroups = 1;
+    const size_t total_lines = n_utts ? line_off[n_utts] - line_off[0] : 0;
+    if (n_utts >= 8 && total_lines >= 16000)
+        ngroups = 2;
+    if (forced)
+        ngroups = (size_t)std::max(1, forced);
+    if (one_batch)
+        ngroups = 1;
+    ngroups = std::max<size_t>(1, std::min(ngroups, n_utts));
+    std::vector<size_t> glo(ngroups + 1, n_utts);
+    glo[0] = 0;
+    for (size_t g = 1, u = 0; g < ngroups; g++) {
+        const size_t want = line_off[0] + total_lines * g / ngroups;
+        while (u < n_utts && line_off[u] < want)
+            u++;
+        glo[g] = std::max(u, glo[g - 1]);
+    }
+    return glo;
+}
+
 } // namespace jb

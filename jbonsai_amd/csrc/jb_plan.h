@@ -137,4 +137,14 @@ struct StreamMode {
 StreamMode plan_stream_mode(const jb_stream_desc &s, uint32_t si, uint32_t flags, uint32_t stage, bool from_tracks,
                             int mt_max_dim);
 
+// ---- the groups of an engine request (synthesize_batch_impl, jb_engine.cpp) ----
+
+// The boundaries glo[0 .. ngroups] of the groups a request of n_utts utterances is pipelined in: group g is the
+// utterances [glo[g], glo[g + 1]).  Two groups from 8 utterances and 16,000 label lines on, else one; `forced`
+// (JB_SYNTH_GROUPS; 0: none) overrides the count, one_batch (a programme, or one gain for the request: both live in one
+// batch) makes it one, and there are never more groups than utterances.  The groups split the utterances by label
+// count: boundary g is the first utterance whose line_off reaches g / ngroups of the request's lines.
+// line_off: [n_utts + 1], not read for n_utts == 0.  Pure
+std::vector<size_t> plan_synth_groups(const size_t *line_off, size_t n_utts, int forced, bool one_batch);
+
 } // namespace jb

@@ -1,9 +1,12 @@
-// Prints what the shape rules of Batch::create (jbonsai_amd/csrc/jb_plan.h) decide, as JSON; host-only, no GPU.
+// Prints what the shape rules of Batch::create and the group split of an engine request (jbonsai_amd/csrc/jb_plan.h)
+// decide, as JSON; host-only, no GPU.
 // stdin, whitespace-separated, one request:
 //   blocks  f_lo f_hi n_lo n_hi                        -> [[bs, nblk] for fperiod in f_lo..f_hi for nlpf in n_lo..n_hi]
 //   runs    n lf0[0..n)                                -> {"durations": [...], "msd": [...]}
 //   cond    alpha beta volume nmcp stage  nv (alpha beta volume)[0..nv)         (nv: -1 = no per-utterance entries)
 //   stream  L W is_msd use_gv width[0..W) si flags stage from_tracks mt_max_dim
+//   groups  cases (n_utts forced one_batch labels[0..n_utts))[0..cases)   -> [glo of each case]; labels: each
+//           utterance's label lines (line_off starts at 3: the rule reads differences only)
 #include "jb_plan.h"
 
 #include <cstdio>
@@ -98,6 +101,32 @@ int main()
         const jb::StreamMode m = jb::plan_stream_mode(s, si, flags, stage, from_tracks != 0, mt_max_dim);
         printf("{\"W\": %d, \"BW\": %d, \"is_msd\": %d, \"use_gv\": %d, \"mt\": %d, \"defer_out\": %d, \"is_static\": %s}\n",
                m.W, m.BW, m.is_msd, m.use_gv, m.mt, m.defer_out, m.is_static ? "true" : "false");
+    } else if (what == "groups") {
+        size_t cases = 0;
+        std::cin >> cases;
+        printf("[");
+        for (size_t c = 0; c < cases; c++) {
+            size_t n = 0;
+            int forced = 0, one_batch = 0;
+            std::cin >> n >> forced >> one_batch;
+            if (!std::cin || n > 4096)
+                return fail();
+            std::vector<size_t> off(n + 1, 3);
+            for (size_t u = 0; u < n; u++) {
+                size_t labels = 0;
+                std::cin >> labels;
+                off[u + 1] = off[u] + labels;
+            }
+            if (!std::cin)
+                return fail();
+            // (no utterance: line_off is not read)
+            const std::vector<size_t> glo = jb::plan_synth_groups(n ? off.data() : nullptr, n, forced, one_batch != 0);
+            printf("%s[", c ? ",\n " : "");
+            for (size_t g = 0; g < glo.size(); g++)
+                printf("%s%zu", g ? ", " : "", glo[g]);
+            printf("]");
+        }
+        printf("]\n");
     } else
         return fail();
     return 0;
