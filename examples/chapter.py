@@ -2,14 +2,16 @@
 
     python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
-                               [--loudness LUFS [--ceiling DBFS]] [--rate HZ] [--highpass HZ]
+                               [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
 batch and joined on the GPU (Engine.synthesize_programme) in front of the encoder, so a .flac output is one stream whose
 frame numbers, STREAMINFO, MD5 and SEEKTABLE (a point about every second) cover the whole chapter; any other name is
 written as a 16-bit WAV file.  With --loudness the chapter gets ONE gain (per-request loudness scope), so the sentences
 keep their relative levels.  With --highpass a rumble and DC high-pass at that corner runs on the GPU in front of the
-loudness measurement and the encoder (Engine.set_filter).  The cue list -- each sentence's first sample and time within the chapter -- is printed.
+loudness measurement and the encoder (Engine.set_filter).  With --limiter (and --loudness) the chapter's gain may put its
+highest peak that many dB over the ceiling and a look-ahead limiter holds the ceiling on the GPU (Engine.set_limiter), so
+one loud peak no longer holds the whole chapter under its target.  The cue list -- each sentence's first sample and time within the chapter -- is printed.
 Needs an MI355X: the library has no CPU path.
 """
 import argparse
@@ -29,6 +31,8 @@ ap.add_argument("--trail-ms", type=float, default=0.0, help="silence behind the 
 ap.add_argument("--fade-ms", type=float, default=5.0, help="fade at both edges of every sentence")
 ap.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="target loudness of the chapter")
 ap.add_argument("--ceiling", type=float, default=-1.0, metavar="DBFS", help="sample-peak ceiling (with --loudness)")
+ap.add_argument("--limiter", type=float, default=None, metavar="DB",
+                help="look-ahead limiter: the gain may put the highest peak this far over the ceiling (with --loudness)")
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner (50 to 80 Hz removes rumble and DC)")
 args = ap.parse_args()
@@ -46,6 +50,8 @@ if args.highpass is not None:
 if args.loudness is not None:
     engine.condition.set_loudness_target(args.loudness)
     engine.condition.set_peak_ceiling(args.ceiling)
+    if args.limiter is not None:
+        engine.set_limiter(J.limiter(max_reduction_db=args.limiter))
     engine.set_loudness_scope(J.LOUDNESS_PER_REQUEST)
 hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
 join = dict(lead_ms=args.lead_ms, gap_ms=args.gap_ms, trail_ms=args.trail_ms, fade_ms=args.fade_ms)

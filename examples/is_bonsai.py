@@ -1,6 +1,6 @@
 """The reference's `examples/is-bonsai` on the GPU path: full-context labels -> PCM -> 16-bit WAV.
 
-    python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak]]
+    python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak] [--limiter DB]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
                                  [--flac] [--highpass HZ]
 
@@ -20,6 +20,8 @@ With --flac the 16-bit audio is encoded as a FLAC stream on the GPU, with the MD
 SEEKTABLE with a point about every second, and written as it is.
 With --highpass the audio passes a second-order high-pass at that corner on the GPU (Engine.set_filter), behind the
 output rate and in front of the loudness measurement and every encoder above.
+With --limiter (and --loudness) the gain may put the highest peak that many dB over the ceiling and a look-ahead limiter
+on the GPU holds the ceiling (Engine.set_limiter): the target is reached where the peak alone stood in the way.
 """
 import argparse
 import os
@@ -45,6 +47,8 @@ ap.add_argument("--adpcm", action="store_true", help="IMA ADPCM (4-bit) WAV file
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm)")
 ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
+ap.add_argument("--limiter", type=float, default=None, metavar="DB",
+                help="look-ahead limiter on the GPU: dB the gain may put the highest peak over the ceiling (with --loudness)")
 args = ap.parse_args()
 voice, out = args.voice, args.out
 
@@ -54,6 +58,8 @@ if args.highpass is not None:
 if args.loudness is not None:
     engine.condition.set_loudness_target(args.loudness)
     engine.condition.set_peak_ceiling(args.ceiling)
+    if args.limiter is not None:
+        engine.set_limiter(J.limiter(max_reduction_db=args.limiter))
     engine.condition.set_peak_mode(J.PEAK_TRUE if args.true_peak else J.PEAK_SAMPLE)
 if args.programme:
     if args.loudness is None:

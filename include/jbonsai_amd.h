@@ -890,8 +890,8 @@ void jb_join_free(void *p);
  *   16.89 ms.  Against a serial cascade in extended precision the device's largest error is 4.4e-12 of the utterance's
  *   largest sample (a serial f64 cascade: 1.4e-12).
  * Not covered: FIR sections, time-varying filters, more than four sections, one-pole sections, a filter in front of
- * the converter, filters on the native-rate reads, a limiter, serving a generator head early, reading through the
- * pinned ring. */
+ * the converter, filters on the native-rate reads, serving a generator head early, reading through the pinned
+ * ring. */
 /* New (none).  f[0..n): one filter for the batch (n == 1) or one per utterance (n == jb_batch_size); NULL, 0 withdraws
  * the request.  Before the first run only.  Checked against each utterance's output rate, here and again by a later
  * jb_batch_set_output_rate. */
@@ -912,6 +912,88 @@ int jb_filter_pcm_batch(const double *const *in, const size_t *n_in, size_t n, c
 int jb_filter_pcm_batch_i16(const double *const *in, const size_t *n_in, size_t n, const jb_filter *f,
                             const uint32_t *hz, int32_t device, int16_t **out, size_t *n_out);
 void jb_filter_free(void *p);
+
+/* ---- Limiter (new: the reference has no such control) --------------------------------------------------------------
+ * A look-ahead peak limiter in the place of the loudness apply pass: a few peaks are taken down so that the rest can
+ * reach the target.  With a request the static gain of an utterance (or of its loudness group) is
+ * ln_gain_db(T, L, C + max_reduction_db, P): it may put the highest peak up to max_reduction_db over the ceiling C, and
+ * the limiter holds the ceiling.  The rule, for one utterance x[0..N) (f64, 16-bit units) under the gain g, the
+ * ceiling c = 32768 10^(C / 20), the look-ahead L = max(1, round(lookahead_ms hz / 1000)) and the hold
+ * H = round(hold_ms hz / 1000) samples (round: floor(v + 0.5)), FIR only -- no recursion, no iteration, no delay:
+ *   1. u[n] = x[n] g.
+ *   2. the detector: JB_PEAK_SAMPLE d[n] = |u[n]|; JB_PEAK_TRUE d[n] = max(|u[n]|, b[n - 1], b[n]), b[n] the largest
+ *      magnitude of the F - 1 interpolated phases between samples n and n + 1 (jb_true_peak_filter's taps over
+ *      u[n - 5 .. n + 6], u = 0 outside [0, N), one product and eleven FMAs in ascending tap order; b[-1] included).
+ *   3. r[n] = c / d[n] where d[n] > c, else 1; r = 1 outside [0, N).
+ *   4. m[k] = min r[k - H .. k + L], k = -L .. N - 1.
+ *   5. a[n] = w[0] m[n], then fma(w[j], m[n - j], a) for j = 1..L (w: jb_limiter_window); a[n] = 1 where every
+ *      m[n - j] is 1; then a[n] = min(a[n], r[n]).
+ *   6. y[n] = min(max(u[n] a[n], -c), c); a 16-bit output is the 16-bit sink's rule on that y.
+ * Guaranteed: |y[n]| <= c exactly (the sample peak), N samples out, and y[n] = x[n] g bit for bit unless some d[i] > c
+ * lies in i = n - L - H .. n + L: an utterance that stays under the ceiling gets the bytes of the plain apply pass.
+ * Reported only: the true peak of y (in JB_PEAK_TRUE mode the detector bounds the inter-sample peaks of u; those of y
+ * stay near the ceiling, without a guarantee) and the loudness of y, which ends a little under the target (the
+ * limiter is not iterated; jb_batch_loudness* keep reporting the static gain_db).
+ * The device (jb_limiter.hip) limits tiles of 1,024 samples with a halo of L + H samples in front and L behind; the
+ * tiling depends on the utterance alone, every sample follows the rule above exactly, so the output depends on the
+ * utterance's samples, gain and options only and JB_BATCH_INVARIANT output stays invariant.
+ * Not covered: a recursive release, multiband limiting, iteration to the target, a guaranteed true-peak bound, the
+ * _multi entries. */
+#define JB_LIMITER_EXACT 1u /* flags: the three values are taken as given (a hold or a reduction of 0 means 0) */
+#define JB_LIMITER_OFF 2u   /* flags: this utterance is not limited: the plain apply pass.  The values are not read, so
+                               no geometry is formed and no rate is refused for it */
+typedef struct jb_limiter_opts {
+    double lookahead_ms;     /* (0, 10]; 0 without JB_LIMITER_EXACT: 2 ms */
+    double hold_ms;          /* [0, 50]; 0 without JB_LIMITER_EXACT: 8 ms */
+    double max_reduction_db; /* [0, 24]: how far the static gain may put the highest peak over the ceiling; 0 without
+                                JB_LIMITER_EXACT: 6 dB.  Read by the batch and the engine alone, where it enters the gain
+                                rule (there, with JB_LIMITER_EXACT, 0 gives the plain apply pass); jb_limiter_host and
+                                jb_limiter_pcm_batch take the gain as given, check the field's range and do not read
+                                it further: they limit whatever that gain puts over the ceiling */
+    uint32_t flags;          /* JB_LIMITER_EXACT, JB_LIMITER_OFF or 0; any other bit: JB_ERR_INVALID */
+    uint32_t reserved;       /* 0 */
+} jb_limiter_opts;
+typedef struct jb_limiter_report {
+    double max_reduction_db;  /* -20 log10 of the smallest a[n] (0: nothing was limited) */
+    uint64_t limited_samples; /* samples with a[n] < 1 */
+    uint32_t lookahead, hold; /* L and H in samples at the utterance's output rate */
+} jb_limiter_report;
+/* New (none).  opts[0..n): one request for the batch (n == 1) or one per utterance (n == jb_batch_size); NULL, 0
+ * withdraws it.  A value outside its range, a non-finite one, an unknown flag or a non-zero reserved word:
+ * JB_ERR_INVALID before any device is touched (jb_last_error names the utterance and the field).  Only before the
+ * first run and not on a JB_BATCH_MLPG_ONLY batch; in either order with the target, the peak mode, the output rate and
+ * the groups.  The members of one loudness group must agree on the options: this setter and the group setters refuse a
+ * mixed group, naming the group and the field.  Without a target the request has no effect; an utterance without a
+ * finite ceiling is not limited.  2 L + H above 2048 samples at an utterance's output rate fails at the run with
+ * JB_ERR_UNSUPPORTED.  Without the call -- and with a request that limits no utterance (every one JB_LIMITER_OFF,
+ * without depth or without a finite ceiling) -- the apply pass runs as before: nothing is added to a run and nothing is
+ * allocated. */
+int jb_batch_set_limiter(jb_batch *b, const jb_limiter_opts *opts, size_t n);
+/* New (none).  What the last run's limiter did to utterance utt (zeros with the L, H of its request where nothing
+ * reached the ceiling; all zeros for an utterance that is not limited: JB_LIMITER_OFF, no depth, no finite ceiling).
+ * No request, no target or a batch that has not run: JB_ERR_INVALID. */
+int jb_batch_limiter_report(jb_batch *b, size_t utt, jb_limiter_report *out);
+/* New (none).  L and H of opts (NULL: the defaults) at hz and the smoothing window w[0..L]: the interior of a Hann
+ * window of L + 3 points, normalised to sum 1, computed in extended precision and symmetric.  Each pointer may be NULL;
+ * cap below L + 1 with w given: JB_ERR_BUFFER.  2 L + H above 2048: JB_ERR_UNSUPPORTED. */
+int jb_limiter_window(uint32_t hz, const jb_limiter_opts *opts, uint32_t *L, uint32_t *H, double *w, size_t cap);
+/* New (none).  The rule above in plain C++ on the host; no GPU is touched.  x[0..n) at hz under `gain` (linear) and
+ * the ceiling (dBFS or dBTP by peak_mode; +INFINITY: none); y must hold n samples; report may be NULL. */
+int jb_limiter_host(const double *x, uint64_t n, uint32_t hz, double gain, double ceiling_dbfs, uint32_t peak_mode,
+                    const jb_limiter_opts *opts, double *y, jb_limiter_report *report);
+int jb_limiter_host_i16(const double *x, uint64_t n, uint32_t hz, double gain, double ceiling_dbfs,
+                        uint32_t peak_mode, const jb_limiter_opts *opts, int16_t *y, jb_limiter_report *report);
+/* New (none).  The stage on PCM the caller holds, on `device` (-1 = current): the seam of the same kernel.  Utterance
+ * u is n_in[u] f64 samples at hz[u] under gain[u], ceiling_dbfs[u], peak_mode[u] and opts[u]; out[u] = its n_in[u]
+ * limited samples, f64 or by the 16-bit sink's rule, library-owned (jb_limiter_free each); reports (may be NULL): [n].
+ * The same samples and arguments give the same bits from this seam, from jb_limiter_host and from the batch path. */
+int jb_limiter_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz, const double *gain,
+                         const double *ceiling_dbfs, const uint32_t *peak_mode, const jb_limiter_opts *opts,
+                         int32_t device, double **out, jb_limiter_report *reports);
+int jb_limiter_pcm_batch_i16(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                             const double *gain, const double *ceiling_dbfs, const uint32_t *peak_mode,
+                             const jb_limiter_opts *opts, int32_t device, int16_t **out, jb_limiter_report *reports);
+void jb_limiter_free(void *p);
 
 /* ---- multi-GPU (SURVEY 8b "device_ids[] / n_devices", 8e) ----------------------------------
  * Utterances are independent, so a batch shards over the GPUs of a node with no data-path
@@ -1054,6 +1136,14 @@ uint32_t jb_engine_get_loudness_scope(const jb_engine *e);
  * at synthesis.  jb_engine_new copies it with the Condition. */
 int jb_engine_set_filter(jb_engine *e, const jb_filter *f);
 int jb_engine_get_filter(const jb_engine *e, jb_filter *out);
+/* New.  The limiter of the audio the engine's entries return (see "Limiter"): jb_synthesize, every
+ * jb_synthesize_batch* and jb_synthesize_programme* form and _each* (each engine's own request for its utterance: not
+ * among the fields the engines must agree on, except inside a per-request loudness group) ask the batch for it
+ * (jb_batch_set_limiter).  It takes effect with a loudness target and a ceiling.  NULL (the default) = off.  Checked
+ * here; jb_engine_new copies it with the Condition.  jb_engine_get_limiter returns 1 and the request as it was given
+ * in *out, or 0 and zeros where there is none. */
+int jb_engine_set_limiter(jb_engine *e, const jb_limiter_opts *opts);
+int jb_engine_get_limiter(const jb_engine *e, jb_limiter_opts *out);
 /* New.  Where the per-label decision-tree search of the front half runs (Model::get_index for the duration model and
  * every stream model, state and voice, and the GV switch question).  The default is the host, as before: nothing new
  * runs and nothing is allocated.  On the device one wave searches one label (jb_treesearch.hip); label parsing, the
@@ -1356,6 +1446,11 @@ JB_LAYOUT_ASSERT(sizeof(jb_filter_section) == 72 && offsetof(jb_filter_section, 
                  "jb_filter_section");
 JB_LAYOUT_ASSERT(sizeof(jb_filter) == 296 && offsetof(jb_filter, n_sections) == 288, "jb_filter");
 JB_LAYOUT_ASSERT(sizeof(jb_biquad) == 40 && offsetof(jb_biquad, a1) == 24, "jb_biquad");
+JB_LAYOUT_ASSERT(sizeof(jb_limiter_opts) == 32 && offsetof(jb_limiter_opts, max_reduction_db) == 16 &&
+                     offsetof(jb_limiter_opts, flags) == 24, "jb_limiter_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_limiter_report) == 24 && offsetof(jb_limiter_report, limited_samples) == 8 &&
+                     offsetof(jb_limiter_report, lookahead) == 16 && offsetof(jb_limiter_report, hold) == 20,
+                 "jb_limiter_report");
 #undef JB_LAYOUT_ASSERT
 #endif
 #endif /* JBONSAI_AMD_H */

@@ -12,7 +12,9 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    LOUDNESS_NO_GROUP, LOUDNESS_R128, LOUDNESS_PER_UTTERANCE, LOUDNESS_PER_REQUEST,
                    JOIN_NONE, JoinUtt, join_geometry, join_host, join_ms_to_samples, join_pcm,
                    Filter, FilterSection, Biquad, filter_design, filter_sos, filter_pcm, filter_pcm_host, highpass,
-                   lowpass, peaking, lowshelf, highshelf, notch, raw_filter, telephone_band, no_filter)
+                   lowpass, peaking, lowshelf, highshelf, notch, raw_filter, telephone_band, no_filter,
+                   LimiterOpts, LimiterReport, LIMITER_EXACT, LIMITER_OFF, limiter, no_limiter, limiter_window,
+                   limiter_host, limiter_pcm)
 from .batch import (Batch, IndexStreamStates, IndexUtterance, PdfSet, StreamInfo, StreamStates, TrackUtterance,  # noqa: F401
                     Utterance, VoiceInfo, generator_from_tracks, mlpg_batch, paramgen_vocode_batch, vocode_tracks_batch,
                     vocoder_synthesize_batch)
@@ -32,4 +34,5 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "LOUDNESS_PER_REQUEST", "JOIN_NONE", "JoinUtt", "join_geometry", "join_host", "join_ms_to_samples",
            "join_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",
            "filter_pcm_host", "highpass", "lowpass", "peaking", "lowshelf", "highshelf", "notch", "raw_filter",
-           "telephone_band", "no_filter"]
+           "telephone_band", "no_filter", "LimiterOpts", "LimiterReport", "LIMITER_EXACT", "LIMITER_OFF", "limiter",
+           "no_limiter", "limiter_window", "limiter_host", "limiter_pcm"]

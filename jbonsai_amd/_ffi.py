@@ -320,6 +320,46 @@ def filter_array(filters, n=None):
     return arr, len(fs)
 
 
+LIMITER_EXACT, LIMITER_OFF = 1, 2
+
+
+class LimiterOpts(C.Structure):
+    """jb_limiter_opts: look-ahead and hold in ms, how far the static gain may put the highest peak over the ceiling."""
+    _fields_ = [("lookahead_ms", C.c_double), ("hold_ms", C.c_double), ("max_reduction_db", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LimiterReport(C.Structure):
+    """jb_limiter_report: what the limiter did to one utterance."""
+    _fields_ = [("max_reduction_db", C.c_double), ("limited_samples", C.c_uint64), ("lookahead", C.c_uint32),
+                ("hold", C.c_uint32)]
+
+    def as_dict(self):
+        return {"max_reduction_db": self.max_reduction_db, "limited_samples": int(self.limited_samples),
+                "lookahead": int(self.lookahead), "hold": int(self.hold)}
+
+
+def limiter(lookahead_ms: float = 2.0, hold_ms: float = 8.0, max_reduction_db: float = 6.0):
+    """A LimiterOpts with the three values as given (LIMITER_EXACT: a hold or a reduction of 0 means 0)."""
+    return LimiterOpts(float(lookahead_ms), float(hold_ms), float(max_reduction_db), LIMITER_EXACT, 0)
+
+
+def no_limiter():
+    """The LimiterOpts of an utterance that is not limited (LIMITER_OFF)."""
+    return LimiterOpts(0.0, 0.0, 0.0, LIMITER_OFF, 0)
+
+
+def limiter_array(opts, n=None):
+    """A (LimiterOpts * n) array (None: no_limiter()); one entry stands for all n."""
+    os_ = [opts] if isinstance(opts, LimiterOpts) or opts is None else list(opts)
+    if n is not None and len(os_) == 1:
+        os_ = os_ * n
+    arr = (LimiterOpts * max(1, len(os_)))()
+    for i, o in enumerate(os_):
+        C.memmove(C.byref(arr[i]), C.byref(o if o is not None else no_limiter()), C.sizeof(LimiterOpts))
+    return arr, len(os_)
+
+
 class LoudnessReport(C.Structure):
     """jb_loudness_report: what a run measured and applied for one utterance."""
     _fields_ = [("lufs", C.c_double), ("sample_peak_dbfs", C.c_double), ("true_peak_dbtp", C.c_double),
@@ -414,6 +454,9 @@ SYMBOLS = [
     "jb_join_pcm_batch_i16", "jb_join_free",
     "jb_batch_set_filter", "jb_batch_filter_coefficients", "jb_filter_design", "jb_filter_pcm_host",
     "jb_filter_pcm_batch", "jb_filter_pcm_batch_i16", "jb_filter_free", "jb_engine_set_filter", "jb_engine_get_filter",
+    "jb_batch_set_limiter", "jb_batch_limiter_report", "jb_limiter_window", "jb_limiter_host", "jb_limiter_host_i16",
+    "jb_limiter_pcm_batch", "jb_limiter_pcm_batch_i16", "jb_limiter_free", "jb_engine_set_limiter",
+    "jb_engine_get_limiter",
     "jb_synthesize_programme", "jb_synthesize_programme_i16", "jb_synthesize_programme_flac_meta",
     "jb_synthesize_programme_formatted", "jb_synthesize_programme_adpcm",
 ]
@@ -668,6 +711,20 @@ def lib():
     L.jb_filter_free.restype = None
     L.jb_engine_set_filter.argtypes = [vp, flp]
     L.jb_engine_get_filter.argtypes = [vp, flp]
+    lop, lrp = C.POINTER(LimiterOpts), C.POINTER(LimiterReport)
+    L.jb_batch_set_limiter.argtypes = [vp, lop, sz]
+    L.jb_batch_limiter_report.argtypes = [vp, sz, lrp]
+    L.jb_limiter_window.argtypes = [C.c_uint32, lop, u32p, u32p, dp, sz]
+    L.jb_limiter_host.argtypes = [dp, C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.c_uint32, lop, dp, lrp]
+    L.jb_limiter_host_i16.argtypes = [dp, C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.c_uint32, lop,
+                                      C.POINTER(C.c_int16), lrp]
+    L.jb_limiter_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, u32p, dp, dp, u32p, lop, C.c_int32,
+                                       C.POINTER(vp), lrp]
+    L.jb_limiter_pcm_batch_i16.argtypes = L.jb_limiter_pcm_batch.argtypes
+    L.jb_limiter_free.argtypes = [vp]
+    L.jb_limiter_free.restype = None
+    L.jb_engine_set_limiter.argtypes = [vp, lop]
+    L.jb_engine_get_limiter.argtypes = [vp, lop]
     lines, szp = C.POINTER(C.c_char_p), C.POINTER(sz)
     L.jb_synthesize_programme.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
     L.jb_synthesize_programme_i16.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
@@ -1153,6 +1210,66 @@ def filter_pcm(pcms, filters, hz, device: int = -1, i16: bool = False):
         res.append(np.ctypeslib.as_array(buf, shape=(max(int(ns[u]), 1),))[:int(ns[u])].copy())
         L.jb_filter_free(outs[u])
     return res
+
+
+def limiter_window(hz: int, opts=None):
+    """jb_limiter_window: (L, H, w[0..L]) of a LimiterOpts (None: the defaults) at `hz`."""
+    import numpy as np
+    L_, H_ = C.c_uint32(), C.c_uint32()
+    o = None if opts is None else C.byref(opts)
+    check(lib().jb_limiter_window(int(hz), o, C.byref(L_), C.byref(H_), None, 0))
+    w = np.empty(L_.value + 1, dtype=np.float64)
+    check(lib().jb_limiter_window(int(hz), o, None, None, w.ctypes.data_as(C.POINTER(C.c_double)), w.size))
+    return L_.value, H_.value, w
+
+
+def limiter_host(pcm, hz: int, gain: float, ceiling_db: float, peak_mode: int = 0, opts=None, i16: bool = False):
+    """jb_limiter_host / _i16: the limiter's rule on the host (no GPU): (y, report dict) of the f64 samples `pcm`
+    under the linear `gain` and the ceiling in dBFS (dBTP with peak_mode = PEAK_TRUE)."""
+    import numpy as np
+    x = np.ascontiguousarray(pcm, dtype=np.float64)
+    y = np.empty(x.size, dtype=np.int16 if i16 else np.float64)
+    rep = LimiterReport()
+    o = None if opts is None else C.byref(opts)
+    fn = lib().jb_limiter_host_i16 if i16 else lib().jb_limiter_host
+    check(fn(x.ctypes.data_as(C.POINTER(C.c_double)), x.size, int(hz), float(gain), float(ceiling_db), int(peak_mode),
+             o, y.ctypes.data_as(C.POINTER(C.c_int16 if i16 else C.c_double)), C.byref(rep)))
+    return y, rep.as_dict()
+
+
+def limiter_pcm(pcms, hz, gain, ceiling_db, peak_mode=0, opts=None, device: int = -1, i16: bool = False):
+    """jb_limiter_pcm_batch / _i16: the f64 utterances `pcms` limited on the GPU; hz, gain, ceiling_db, peak_mode and
+    opts are one value for all or one per utterance.  Returns ([y], [report dict])."""
+    import numpy as np
+    L = lib()
+    arrs = [np.ascontiguousarray(p, dtype=np.float64) for p in pcms]
+    n = len(arrs)
+
+    def per(v, what):
+        vs = [v] * n if np.isscalar(v) else list(v)
+        if len(vs) != n:
+            raise ValueError("limiter_pcm: one %s, or one per utterance" % what)
+        return vs
+    oarr, no = limiter_array(limiter() if opts is None else opts, n)
+    if no != n and n:
+        raise ValueError("limiter_pcm: one request, or one per utterance")
+    ins = (C.c_void_p * max(1, n))(*[a.ctypes.data for a in arrs])
+    nin = (C.c_size_t * max(1, n))(*[a.size for a in arrs])
+    hzs = (C.c_uint32 * max(1, n))(*[int(h) for h in per(hz, "rate")])
+    gs = (C.c_double * max(1, n))(*[float(g) for g in per(gain, "gain")])
+    cs = (C.c_double * max(1, n))(*[float(c) for c in per(ceiling_db, "ceiling")])
+    ms = (C.c_uint32 * max(1, n))(*[int(m) for m in per(peak_mode, "peak mode")])
+    outs = (C.c_void_p * max(1, n))()
+    reps = (LimiterReport * max(1, n))()
+    check((L.jb_limiter_pcm_batch_i16 if i16 else L.jb_limiter_pcm_batch)(ins, nin, n, hzs, gs, cs, ms, oarr, device,
+                                                                          outs, reps))
+    res = []
+    for u in range(n):
+        ct = C.c_int16 if i16 else C.c_double
+        buf = C.cast(outs[u], C.POINTER(ct))
+        res.append(np.ctypeslib.as_array(buf, shape=(max(arrs[u].size, 1),))[:arrs[u].size].copy())
+        L.jb_limiter_free(outs[u])
+    return res, [reps[u].as_dict() for u in range(n)]
 
 
 def resample(pcms, in_hz: int, out_hz: int, device: int = -1):

@@ -382,6 +382,23 @@ class Batch:
         F.check(self._L.jb_batch_filter_coefficients(self._h, i, out, C.byref(n)))
         return F._biquads(out, n.value)
 
+    def set_limiter(self, opts):
+        """jb_batch_set_limiter: one F.LimiterOpts (J.limiter(...)) for the whole batch or one per utterance (None in a
+        list: that utterance is not limited); None withdraws the request.  Before the first run only.  With a loudness
+        target and a ceiling, the static gain may then put the highest peak max_reduction_db over the ceiling and the
+        limiter holds the ceiling on the device."""
+        if opts is None:
+            F.check(self._L.jb_batch_set_limiter(self._h, None, 0))
+            return
+        arr, n = F.limiter_array(opts)
+        F.check(self._L.jb_batch_set_limiter(self._h, arr, n))
+
+    def limiter_report(self, i) -> dict:
+        """jb_batch_limiter_report: max_reduction_db, limited_samples, lookahead and hold (samples) of utterance i."""
+        rep = F.LimiterReport()
+        F.check(self._L.jb_batch_limiter_report(self._h, i, C.byref(rep)))
+        return rep.as_dict()
+
     def set_loudness_target(self, target_lufs, ceiling_dbfs=float("inf")):
         """jb_batch_set_loudness_target: one target (float) for the whole batch or one per utterance (NaN: measured,
         gain 0 dB unless above the ceiling).  Before the first run only.  The PCM reads then hand out x * gain."""

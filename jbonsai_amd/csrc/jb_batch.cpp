@@ -2513,6 +2513,19 @@ int jb_batch_set_filter(jb_batch *hb, const jb_filter *f, size_t n)
     return hb ? ((Batch *)hb)->out.set_filter(f, n) : JB_ERR_INVALID;
 }
 
+int jb_batch_set_limiter(jb_batch *hb, const jb_limiter_opts *opts, size_t n)
+{
+    return hb ? ((Batch *)hb)->out.set_limiter(opts, n) : JB_ERR_INVALID;
+}
+
+int jb_batch_limiter_report(jb_batch *hb, size_t utt, jb_limiter_report *out)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !out || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    return b->out.read_limiter(utt, out);
+}
+
 int jb_batch_filter_coefficients(const jb_batch *hb, size_t utt, jb_biquad out[JB_FILTER_MAX_SECTIONS], uint32_t *n)
 {
     const Batch *b = (const Batch *)hb;

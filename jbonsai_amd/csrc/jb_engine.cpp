@@ -52,6 +52,8 @@ struct Condition {
     uint32_t peak_mode = JB_PEAK_SAMPLE; // jb_engine_set_peak_mode: what the ceiling bounds, with a target only
     uint32_t loudness_scope = JB_LOUDNESS_PER_UTTERANCE; // jb_engine_set_loudness_scope: what one gain covers
     jb_filter filter{};           // jb_engine_set_filter: n_sections 0 = off
+    bool limiter_on = false;      // jb_engine_set_limiter: a request is set ...
+    jb_limiter_opts limiter{};    // ... and the request as it was given
     uint32_t tree_search = JB_SEARCH_HOST; // jb_engine_set_tree_search: where the per-label tree search runs
     double speed = 1.0;
     size_t stage = 0;
@@ -1115,6 +1117,29 @@ int jb_engine_get_filter(const jb_engine *e, jb_filter *out)
     *out = CENG(e)->cond.filter;
     return JB_OK;
 }
+int jb_engine_set_limiter(jb_engine *e, const jb_limiter_opts *opts)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    if (!opts) {
+        ENG(e)->cond.limiter_on = false;
+        ENG(e)->cond.limiter = jb_limiter_opts{};
+        return JB_OK;
+    }
+    int rc = jb::limiter_check(opts, 0, "jb_engine_set_limiter", nullptr);
+    if (rc)
+        return rc;
+    ENG(e)->cond.limiter_on = true;
+    ENG(e)->cond.limiter = *opts;
+    return JB_OK;
+}
+int jb_engine_get_limiter(const jb_engine *e, jb_limiter_opts *out)
+{
+    if (!e || !out)
+        return JB_ERR_INVALID;
+    *out = CENG(e)->cond.limiter;
+    return CENG(e)->cond.limiter_on ? 1 : 0;
+}
 int jb_engine_set_peak_mode(jb_engine *e, uint32_t mode)
 {
     if (!e || (mode != JB_PEAK_SAMPLE && mode != JB_PEAK_TRUE))
@@ -1617,7 +1642,7 @@ int SynthRun::create_batch(size_t g)
     return rc;
 }
 
-// The output conditions of the utterances [lo, hi), each its engine's own: rate, filter, loudness, peak mode; then the
+// The output conditions of the utterances [lo, hi), each its engine's own: rate, filter, loudness, peak mode, limiter; then the
 // request's one loudness group and its encoder (the setters' refusals depend on this order)
 int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
 {
@@ -1656,6 +1681,17 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
     if (any_target && (rc = out.set_loudness(targets.data(), ceilings.data(), targets.size())))
         return rc;
     if (any_true && (rc = out.set_peak_mode(modes.data(), modes.size())))
+        return rc;
+    // the limiter: each utterance's engine's own (an engine without one leaves its utterance to the plain apply pass;
+    // inside the request's one group the setters refuse engines that disagree)
+    std::vector<jb_limiter_opts> limiters(hi - lo);
+    bool any_limiter = false;
+    for (size_t u = lo; u < hi; u++) {
+        const bool on = eng(u)->cond.limiter_on && !std::isnan(eng(u)->cond.loudness_target);
+        limiters[u - lo] = on ? eng(u)->cond.limiter : jb_limiter_opts{0.0, 0.0, 0.0, JB_LIMITER_OFF, 0};
+        any_limiter = any_limiter || on;
+    }
+    if (any_limiter && (rc = out.set_limiter(limiters.data(), limiters.size())))
         return rc;
     if (one_gain) {
         const std::vector<uint32_t> group(hi - lo, 0u);
@@ -2296,7 +2332,8 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     if (!std::isnan(CENG(e)->cond.loudness_target)) {
         const double t = CENG(e)->cond.loudness_target, c = CENG(e)->cond.peak_ceiling;
         const uint32_t mode = CENG(e)->cond.peak_mode;
-        if ((rc = b->out.set_loudness(&t, &c, 1)) || (rc = b->out.set_peak_mode(&mode, 1)))
+        if ((rc = b->out.set_loudness(&t, &c, 1)) || (rc = b->out.set_peak_mode(&mode, 1)) ||
+            (CENG(e)->cond.limiter_on && (rc = b->out.set_limiter(&CENG(e)->cond.limiter, 1))))
             return rc;
     }
     // Engine::generator runs all three MLPGs before returning (src/engine.rs:333-357); here they are

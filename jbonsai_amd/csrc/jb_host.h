@@ -5,10 +5,12 @@
 #include "jb_adpcm.h"
 #include "jb_filter.h"
 #include "jb_format.h"
+#include "jb_limiter.h"
 #include "jb_loudness_rules.h"
 #include "jb_md5.h"
 #include "jb_output.h"
 
+#include <cmath>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -311,6 +313,26 @@ int filter_launch_list(const std::vector<FilterClass> &classes, const std::vecto
 hipError_t launch_filter(const FilterClass *classes_dev, const FilterUtt *utts_dev, const FilterLaunch &l, double *st,
                          bool i16, hipStream_t stream);
 
+// The limiter stage (jb_limiter.hip; the rules, LimiterClass and LimiterUtt: jb_limiter.h; the host half:
+// jb_limiter.cpp).  opts (null: the defaults) checked and resolved into *out (may be null), or JB_ERR_INVALID with
+// set_error naming the utterance `utt` and the field
+int limiter_check(const jb_limiter_opts *opts, size_t utt, const char *who, LimOpts *out);
+// L and H of a resolved request at hz; JB_ERR_UNSUPPORTED for 2 L + H above kLimMaxSpan
+int limiter_geometry(const LimOpts &r, uint32_t hz, size_t utt, const char *who, uint32_t *L, uint32_t *H);
+void limiter_window(uint32_t L, double *w); // w[0..L]
+int limiter_class_build(uint32_t hz, uint32_t L, uint32_t H, uint32_t mode, LimiterClass *out);
+// The distinct classes of a launch: one table per (L, H) in sample mode, per (rate, L, H) in true-peak mode
+struct LimiterClasses {
+    std::vector<LimiterClass> tables;
+    std::vector<uint32_t> key_hz;
+    int find(uint32_t hz, uint32_t L, uint32_t H, uint32_t mode, uint32_t *cls);
+};
+// utts_dev[0..n) of `tiles` tiles in all: k_ln_limit, then the fold of each listed utterance's tiles (scratch, at the
+// utterance's s0) into out[rslot]; res: the loudness results the gains are read from (null where every g is in the list)
+hipError_t launch_limiter(const LimiterClass *classes_dev, const LimiterUtt *utts_dev, uint32_t n, uint64_t tiles,
+                          const LoudnessResult *res, LimiterTile *scratch, LimiterResult *out, bool i16,
+                          hipStream_t stream);
+
 // Device-resident pdf tables of a voice set (jb_pdf_set) and an indexed batch source
 struct PdfSet {
     int device = -1;
@@ -437,6 +459,9 @@ struct OutputChain {
     // f[0..n): n == 1 or B filters (nullptr, 0: the request is withdrawn), each checked at its utterance's output
     // rate; set_output_rate checks the combined request again
     int set_filter(const jb_filter *f, size_t n);
+    // opts[0..n): n == 1 or B requests (nullptr, 0: the request is withdrawn); with groups, the members must agree
+    int set_limiter(const jb_limiter_opts *opts, size_t n);
+    int read_limiter(size_t u, jb_limiter_report *out); // after sync
     // the coefficients the device runs for utterance u at its output rate (*n = 0 without a filter)
     int filter_coefficients(size_t u, jb_biquad *out, uint32_t *n) const;
     void init();   // Batch::create: the slabs the batch was made with, the plan of no request
@@ -500,6 +525,7 @@ private:
     std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
     std::vector<double> ln_target, ln_ceiling; // [B]
+    std::vector<LimOpts> lim_req;              // [B] the limiter request, resolved; empty: none
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
     std::vector<uint32_t> ln_group_req;        // [B] the caller's ids; empty: no group request
     LnGroups ln_groups;                        // the request planned (empty without one)
@@ -540,6 +566,15 @@ private:
         double *sw = nullptr, *mm = nullptr; // the report's windows (per tile slot) and momentary maxima (per utterance)
         LoudnessRange *r128 = nullptr;       // [B + G]
     } ln;
+    struct Limiter { // follows `post`, in the place of the apply pass
+        DevList<LimiterUtt> utts;     // [B]; total: the tiles
+        std::vector<uint64_t> ntiles; // [B]
+        std::vector<uint32_t> L, H;   // [B] (0, 0: that utterance is not limited)
+        LimiterClass *classes_dev = nullptr;
+        LimiterTile *scratch = nullptr; // per tile
+        LimiterResult *res = nullptr;   // [B]
+        uint64_t tiles = 0;
+    } lim;
     struct Join { // follows `post`
         std::vector<JoinMember> members; // in programme order: programme p owns [prog_first[p], prog_first[p + 1])
         std::vector<uint32_t> member_at; // [B] utterance -> its place in `members`
@@ -576,6 +611,23 @@ private:
     };
     std::vector<EncUnit> enc_units() const;
     bool grouped() const { return plan.normalize() && ln.gres; } // the chain runs loudness groups
+    // the limiter takes the apply pass's place: some utterance is limited (a request that limits none is no request)
+    bool limited() const
+    {
+        if (!plan.normalize())
+            return false;
+        for (size_t u = 0; u < lim_req.size(); u++)
+            if (limits(u))
+                return true;
+        return false;
+    }
+    // utterance u is limited: a request that is not JB_LIMITER_OFF with some depth, a target and a finite ceiling
+    bool limits(size_t u) const
+    {
+        return !lim_req.empty() && !(lim_req[u].flags & kLimOff) && lim_req[u].max_reduction_db > 0.0 &&
+               std::isfinite(ln_ceiling[u]);
+    }
+    int check_limiter_groups(const std::vector<uint32_t> &group, const std::vector<LimOpts> &req, const char *who) const;
     bool formatted() const { return plan.fmt_src != OutSlab::None; }
     bool adpcm() const { return plan.adpcm_src.slab != OutSlab::None; }
     void replan(); // host geometry and routing of the present requests
@@ -594,6 +646,7 @@ private:
     int prepare_resample(), select_resample(const RedoScope *scope), launch_resample(bool redo);
     int prepare_filter(), select_filter(const RedoScope *scope), launch_filter(bool redo);
     int prepare_loudness(), select_loudness(const RedoScope *scope), launch_loudness(bool redo);
+    int prepare_limiter(), select_limiter(const RedoScope *scope), launch_limiter(bool redo);
     int prepare_join(), select_join(const RedoScope *scope), launch_join(bool redo);
     JoinSpan join_span(size_t p, uint64_t k0, uint64_t k1, uint64_t *tiles) const;
     int prepare_flac(), select_flac(const RedoScope *scope), launch_flac(bool redo);

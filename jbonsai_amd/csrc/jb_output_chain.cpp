@@ -1,8 +1,8 @@
 // jb_output_chain.cpp -- OutputChain (jb_host.h): the stages behind the vocoder of one batch.  The setters record a
 // request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() selects what each
 // stage takes (everything, or a redo's part: redo_scope, jb_output.h) and launches, in this order and on the
-// vocoder's stream: the converter (k_resample), the filter, loudness (measurement, groups, report, apply pass), the
-// join, then the encoders of the final PCM: FLAC (blocks, MD5, pack), the sample format and IMA ADPCM.
+// vocoder's stream: the converter (k_resample), the filter, loudness (measurement, groups, report, apply pass; with a
+// limiter request the limiter in the apply pass's place), the join, then the encoders of the final PCM: FLAC (blocks, MD5, pack), the sample format and IMA ADPCM.
 #include "jb_host.h"
 
 #include <algorithm>
@@ -150,7 +150,8 @@ int OutputChain::set_loudness_groups(const uint32_t *group, size_t n)
     }
     std::vector<uint32_t> req(group, group + n);
     LnGroups plan;
-    if ((rc = check_groups(req, ln_target, ln_ceiling, ln_mode, want_hz, "jb_batch_set_loudness_groups", &plan)))
+    if ((rc = check_groups(req, ln_target, ln_ceiling, ln_mode, want_hz, "jb_batch_set_loudness_groups", &plan)) ||
+        (rc = check_limiter_groups(req, lim_req, "jb_batch_set_loudness_groups")))
         return rc;
     if (req.empty()) // (an empty batch: nothing to group)
         return JB_OK;
@@ -348,6 +349,56 @@ int OutputChain::set_filter(const jb_filter *f, size_t n)
     return JB_OK;
 }
 
+// The limiter request `req` ([B], empty: none) under the groups `group` ([B], empty: none): the members of a group
+// agree on the options, else JB_ERR_INVALID naming the group and the field
+int OutputChain::check_limiter_groups(const std::vector<uint32_t> &group, const std::vector<LimOpts> &req,
+                                      const char *who) const
+{
+    if (group.empty() || req.empty())
+        return JB_OK;
+    std::map<uint32_t, size_t> first;
+    for (size_t u = 0; u < group.size(); u++) {
+        if (group[u] == kLnNoGroup)
+            continue;
+        const auto it = first.emplace(group[u], u).first;
+        const LimOpts &a = req[it->second], &c = req[u];
+        const char *field = a.flags != c.flags                         ? "limiter's flags"
+                            : a.lookahead_ms != c.lookahead_ms         ? "limiter's lookahead_ms"
+                            : a.hold_ms != c.hold_ms                   ? "limiter's hold_ms"
+                            : a.max_reduction_db != c.max_reduction_db ? "limiter's max_reduction_db"
+                                                                       : nullptr;
+        if (field) {
+            set_error(std::string(who) + ": the members of loudness group " + std::to_string(group[u]) +
+                      " would disagree on the " + field);
+            return JB_ERR_INVALID;
+        }
+    }
+    return JB_OK;
+}
+
+int OutputChain::set_limiter(const jb_limiter_opts *opts, size_t n)
+{
+    // (the values first: a refused request has touched nothing)
+    const size_t B = (size_t)b.B;
+    std::vector<LimOpts> req;
+    int rc;
+    if (opts || n) {
+        if (!opts || (n != 1 && n != B)) {
+            set_error("jb_batch_set_limiter: give one request, or one per utterance");
+            return JB_ERR_INVALID;
+        }
+        req.resize(B);
+        for (size_t u = 0; u < B; u++)
+            if ((rc = limiter_check(&opts[n == 1 ? 0 : u], u, "jb_batch_set_limiter", &req[u])))
+                return rc;
+    }
+    if ((rc = check_settable("jb_batch_set_limiter: the limiter is set before the batch's first run")) ||
+        (rc = check_limiter_groups(ln_group_req, req, "jb_batch_set_limiter")))
+        return rc;
+    lim_req = std::move(req);
+    return JB_OK;
+}
+
 int OutputChain::filter_coefficients(size_t u, jb_biquad *out, uint32_t *n) const
 {
     *n = 0;
@@ -373,7 +424,8 @@ int OutputChain::prepare()
     for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
-    if ((rc = prepare_resample()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_join()) ||
+    if ((rc = prepare_resample()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
+        (rc = prepare_join()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()))
         return rc;
     if (plan.active()) {
@@ -398,14 +450,14 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const RedoScope *scope = redo ? &of_redo : nullptr;
     int rc;
     if ((rc = select_resample(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
-        (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
+        (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
         (rc = select_adpcm(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fil.utts.n || ln.utts.n || ln.apply.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n))
+    if (redo && !(rs.tiles.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
-        (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
+        (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
         (rc = launch_adpcm(redo)))
         return rc;
     hipError_t e;
@@ -585,7 +637,9 @@ int OutputChain::prepare_loudness()
         w.rate = (uint32_t)r;
         w.slot = (uint32_t)u;
         w.target = ln_target[u];
-        w.ceiling = ln_ceiling[u];
+        // (with a limiter the static gain may put the highest peak max_reduction_db over the ceiling: the gates read
+        // that as their ceiling, the limiter's own list carries the real one)
+        w.ceiling = limits(u) ? ln_ceiling[u] + lim_req[u].max_reduction_db : ln_ceiling[u];
         w.mode = peak_mode(u);
         ln.true_peak = ln.true_peak || w.mode == JB_PEAK_TRUE;
         ln.tiles += ln.ntiles[u];
@@ -679,9 +733,61 @@ int OutputChain::launch_loudness(bool redo)
         (report && (e = launch_loudness_range(ln.rates_dev, ln.utts.list, ln.utts.n, ln.utts.dev, ln.sets.list,
                                               ln.sets.n, ln.members_dev, ln.z, ln.sw, ln.mm, ln.r128, st)) !=
                        hipSuccess) ||
-        (e = launch_loudness_apply(ln.apply.list, ln.apply.n, ln.apply.total, ln.res, plan.apply.i16, st)) != hipSuccess)
+        (!limited() &&
+         (e = launch_loudness_apply(ln.apply.list, ln.apply.n, ln.apply.total, ln.res, plan.apply.i16, st)) != hipSuccess))
         return hip_fail(e, redo ? "loudness(redo)" : "loudness");
     return JB_OK;
+}
+
+// ---- the limiter: with a request, in the place of the apply pass (same input, same slab out, the gain read from the
+// loudness results).  The classes, the utterance list and the per-tile scratch; an utterance without a finite ceiling
+// is listed as the plain apply pass
+int OutputChain::prepare_limiter()
+{
+    if (!limited())
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    LimiterClasses classes;
+    lim.utts.host.assign(B, LimiterUtt{});
+    lim.ntiles.assign(B, 0);
+    lim.L.assign(B, 0);
+    lim.H.assign(B, 0);
+    lim.tiles = 0;
+    int rc;
+    for (size_t u = 0; u < B; u++) {
+        const LoudnessUtt &m = ln.utts.host[u];
+        uint32_t cls = kLimNoSlot;
+        if (limits(u) && ((rc = limiter_geometry(lim_req[u], plan.utt[u].hz, u, "limiter", &lim.L[u], &lim.H[u])) ||
+                          (rc = classes.find(plan.utt[u].hz, lim.L[u], lim.H[u], m.mode, &cls))))
+            return rc;
+        lim.ntiles[u] = limiter_tiles(m.n);
+        lim.utts.host[u] = LimiterUtt{m.x, m.y, m.n, lim.tiles, lim.tiles, limits(u) ? lim_ceiling(ln_ceiling[u]) : 0.0,
+                                      1.0, m.slot, cls, (uint32_t)u, 0};
+        lim.tiles += lim.ntiles[u];
+    }
+    if ((rc = b.dalloc(&lim.classes_dev, classes.tables.size(), false)) || (rc = lim.utts.alloc(b, B, B)) ||
+        (rc = b.dalloc(&lim.scratch, (size_t)lim.tiles, false)) || (rc = b.dalloc(&lim.res, B, false)) ||
+        (rc = upload_list(lim.classes_dev, classes.tables, "limiter work list")))
+        return rc;
+    return lim.utts.upload("limiter work list");
+}
+
+int OutputChain::select_limiter(const RedoScope *scope)
+{
+    if (!limited() || !scope)
+        return lim.utts.take_all(lim.tiles);
+    // `post`: every utterance whose gain or samples changed (the scratch place, s0, stays)
+    const Picked p = pick_renumbered(scope->post, lim.ntiles);
+    return lim.utts.upload_redo(renumbered(lim.utts.host, p, &LimiterUtt::t0), kRedoLists, p.total);
+}
+
+int OutputChain::launch_limiter(bool redo)
+{
+    if (!limited() || (redo && !lim.utts.n))
+        return JB_OK;
+    const hipError_t e = jb::launch_limiter(lim.classes_dev, lim.utts.list, lim.utts.n, lim.utts.total, ln.res,
+                                            lim.scratch, lim.res, plan.apply.i16, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_ln_limit(redo)" : "k_ln_limit");
 }
 
 // The units the encoders take, in the slab each of them reads: the programmes behind a join, else the utterances
@@ -972,6 +1078,23 @@ int OutputChain::read_loudness(size_t u, LoudnessResult *r)
     int rc = check_ready(plan.normalize(), "jb_batch_loudness: the batch has not run",
                          "jb_batch_loudness: no loudness target is set");
     return rc ? rc : b.read(ln.res + u, r, sizeof *r);
+}
+
+int OutputChain::read_limiter(size_t u, jb_limiter_report *out)
+{
+    int rc = check_ready(plan.normalize() && !lim_req.empty(), "jb_batch_limiter_report: the batch has not run",
+                         "jb_batch_limiter_report: needs a loudness target and jb_batch_set_limiter");
+    if (rc)
+        return rc;
+    if (!limited()) { // a request that limits no utterance ran the apply pass
+        *out = jb_limiter_report{0.0, 0, 0, 0};
+        return b.sync();
+    }
+    LimiterResult r{};
+    if ((rc = b.read(lim.res + u, &r, sizeof r)))
+        return rc;
+    *out = jb_limiter_report{lim_reduction_db(r.min_a), r.count, lim.L[u], lim.H[u]};
+    return JB_OK;
 }
 
 uint32_t OutputChain::group_members(size_t u) const

@@ -164,6 +164,16 @@ class _Condition:
         f = F.Filter()
         F.check(self._L().jb_engine_get_filter(self._h(), C.byref(f)))
         return f
+    def set_limiter(self, opts):
+        """The look-ahead peak limiter (an _ffi.LimiterOpts: J.limiter(max_reduction_db=6)) of every entry's output,
+        in effect with a loudness target and a ceiling; None (the default) = off."""
+        F.check(self._L().jb_engine_set_limiter(self._h(), None if opts is None else C.byref(opts)))
+    def get_limiter(self):
+        """The request as it was given, or None."""
+        o = F.LimiterOpts()
+        rc = self._L().jb_engine_get_limiter(self._h(), C.byref(o))
+        F.check(min(rc, 0))
+        return o if rc == 1 else None
     def set_loudness_scope(self, scope):
         """What one gain of the target covers: 0 = each utterance (the default), 1 = the whole request
         (_ffi.LOUDNESS_PER_UTTERANCE / LOUDNESS_PER_REQUEST): the utterances of one synthesize_batch call keep
@@ -255,6 +265,13 @@ class Engine:
 
     def get_filter(self):
         return self.condition.get_filter()
+
+    def set_limiter(self, opts):
+        """jb_engine_set_limiter (the Condition's setter, on the engine): an _ffi.LimiterOpts, or None for none."""
+        self.condition.set_limiter(opts)
+
+    def get_limiter(self):
+        return self.condition.get_limiter()
 
     def close(self):
         if getattr(self, "_h", None):
