@@ -778,16 +778,46 @@ def loudness_filter(hz: int):
     return b.reshape(2, 3), a.reshape(2, 3), hop.value
 
 
+def _pcm_args(pcms, dtype, void: bool = False):
+    """The inputs of a jb_*_pcm_batch call: (arrs, n, ins, nin) -- `pcms` as contiguous arrays of dtype (kept alive by
+    the caller over the call), their count, their pointers (typed, or void * where the entry's argtypes say so) and
+    their lengths."""
+    import numpy as np
+
+    arrs = [np.ascontiguousarray(a, dtype=dtype) for a in pcms]
+    n = len(arrs)
+    pt = C.c_void_p if void else C.POINTER(np.ctypeslib.as_ctypes_type(dtype))
+    ins = (pt * max(n, 1))(*[a.ctypes.data_as(pt) for a in arrs])
+    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    return arrs, n, ins, nin
+
+
+def _take(free, bufs, ns, n, dtype=None):
+    """n library-owned buffers of ns[u] elements copied out -- bytes, or arrays of dtype -- and each released with
+    `free`."""
+    import numpy as np
+
+    out = []
+    for u in range(n):
+        if dtype is None:
+            out.append(C.string_at(bufs[u], ns[u]) if ns[u] else b"")
+        elif ns[u]:
+            ptr = C.cast(bufs[u], C.POINTER(np.ctypeslib.as_ctypes_type(dtype)))
+            out.append(np.ctypeslib.as_array(ptr, shape=(int(ns[u]),)).copy())
+        else:
+            out.append(np.zeros(0, dtype=dtype))
+        if bufs[u]:
+            free(bufs[u])
+    return out
+
+
 def loudness(pcms, hz: int, device: int = -1):
     """jb_loudness_pcm_batch: (lufs, peak_dbfs) of each float64 array of `pcms` (or of one array) at hz, on the GPU."""
     import numpy as np
 
     single = isinstance(pcms, np.ndarray)
-    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
     dp = C.POINTER(C.c_double)
-    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
     lufs, peak = np.zeros(max(n, 1)), np.zeros(max(n, 1))
     check(lib().jb_loudness_pcm_batch(ins, nin, n, hz, device, lufs.ctypes.data_as(dp), peak.ctypes.data_as(dp)))
     res = [(float(lufs[u]), float(peak[u])) for u in range(n)]
@@ -810,11 +840,8 @@ def loudness_groups(pcms, hz: int, group=None, device: int = -1, mode: int = 0, 
     members, flags, r128), r128 (a dict per utterance) and lufs (each utterance's own L)."""
     import numpy as np
 
-    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in pcms]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args(pcms, np.float64)
     dp = C.POINTER(C.c_double)
-    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
     ids = _group_ids(group, n)
     of = (C.c_uint32 * max(n, 1))()
     reps = (LoudnessGroupReport * max(n, 1))()
@@ -867,11 +894,8 @@ def true_peak(pcms, hz: int, device: int = -1):
     import numpy as np
 
     single = isinstance(pcms, np.ndarray)
-    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
     dp = C.POINTER(C.c_double)
-    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
     tp = np.zeros(max(n, 1))
     check(lib().jb_true_peak_pcm_batch(ins, nin, n, hz, device, tp.ctypes.data_as(dp)))
     res = [float(tp[u]) for u in range(n)]
@@ -880,12 +904,7 @@ def true_peak(pcms, hz: int, device: int = -1):
 
 def take_flac(L, bufs, ns, n):
     """bytes of n library-owned FLAC streams, each released with jb_flac_free."""
-    out = []
-    for u in range(n):
-        out.append(C.string_at(bufs[u], ns[u]) if ns[u] else b"")
-        if bufs[u]:
-            L.jb_flac_free(bufs[u])
-    return out
+    return _take(L.jb_flac_free, bufs, ns, n)
 
 
 def flac_encode(pcms, hz: int, block_size: int = 0, max_lpc_order=None, device: int = -1, md5: bool = False,
@@ -894,12 +913,9 @@ def flac_encode(pcms, hz: int, block_size: int = 0, max_lpc_order=None, device: 
     md5: the samples' MD5 in STREAMINFO; seek_interval_ms > 0: a SEEKTABLE with a point about that often."""
     import numpy as np
 
-    arrs = [np.ascontiguousarray(a, dtype=np.int16) for a in pcms]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args(pcms, np.int16)
     L = lib()
-    i16p, u8p = C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
-    ins = (i16p * max(n, 1))(*[a.ctypes.data_as(i16p) for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    u8p = C.POINTER(C.c_uint8)
     bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
     opts, meta = flac_opts(block_size, max_lpc_order), flac_meta(md5, seek_interval_ms)
     if meta is None:
@@ -914,11 +930,7 @@ def flac_md5(pcms, device: int = -1):
     GPU."""
     import numpy as np
 
-    arrs = [np.ascontiguousarray(a, dtype=np.int16) for a in pcms]
-    n = len(arrs)
-    i16p = C.POINTER(C.c_int16)
-    ins = (i16p * max(n, 1))(*[a.ctypes.data_as(i16p) for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    arrs, n, ins, nin = _pcm_args(pcms, np.int16)
     out = C.create_string_buffer(16 * max(n, 1))
     check(lib().jb_flac_md5_pcm_batch(ins, nin, n, device, C.cast(out, C.c_void_p)))
     return [out.raw[16 * u:16 * u + 16] for u in range(n)]
@@ -944,12 +956,7 @@ def flac_seek_geometry(n_samples: int, block_size: int, hz: int, seek_interval_m
 
 def take_formatted(L, bufs, ns, n):
     """bytes of n library-owned formatted outputs, each released with jb_format_free."""
-    out = []
-    for u in range(n):
-        out.append(C.string_at(bufs[u], ns[u]) if ns[u] else b"")
-        if bufs[u]:
-            L.jb_format_free(bufs[u])
-    return out
+    return _take(L.jb_format_free, bufs, ns, n)
 
 
 def format_pcm(pcms, fmt, dither=False, seed: int = 0, device: int = -1):
@@ -958,12 +965,9 @@ def format_pcm(pcms, fmt, dither=False, seed: int = 0, device: int = -1):
     import numpy as np
 
     single = isinstance(pcms, np.ndarray)
-    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
     L = lib()
-    dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
-    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    u8p = C.POINTER(C.c_uint8)
     bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
     opts = format_opts(fmt, dither, seed)
     check(L.jb_format_pcm_batch(ins, nin, n, C.byref(opts), device, bufs, ns))
@@ -1013,12 +1017,7 @@ def adpcm_streams(L, bufs, ns, nsamp, rates, block_align, n):
 
 def take_adpcm(L, bufs, ns, n):
     """bytes of n library-owned ADPCM outputs, each released with jb_adpcm_free."""
-    out = []
-    for u in range(n):
-        out.append(C.string_at(bufs[u], ns[u]) if ns[u] else b"")
-        if bufs[u]:
-            L.jb_adpcm_free(bufs[u])
-    return out
+    return _take(L.jb_adpcm_free, bufs, ns, n)
 
 
 def adpcm_geometry(hz: int, n: int, block_align: int = 0):
@@ -1063,15 +1062,12 @@ def adpcm_encode(pcms, hz, block_align: int = 0, device: int = -1):
     import numpy as np
 
     single = isinstance(pcms, np.ndarray)
-    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
     rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
     if len(rates) != n:
         raise ValueError("give one rate, or one per array")
     L = lib()
-    dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
-    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    u8p = C.POINTER(C.c_uint8)
     hzs = (C.c_uint32 * max(n, 1))(*rates)
     bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
     opts = adpcm_opts(block_align)
@@ -1109,11 +1105,7 @@ def _join_inputs(pcms):
     import numpy as np
 
     i16 = len(pcms) > 0 and all(np.asarray(a).dtype == np.int16 for a in pcms)
-    arrs = [np.ascontiguousarray(a, dtype=np.int16 if i16 else np.float64) for a in pcms]
-    n = len(arrs)
-    ins = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
-    return i16, arrs, n, ins, nin
+    return (i16,) + _pcm_args(pcms, np.int16 if i16 else np.float64, void=True)
 
 
 def join_host(pcms, req):
@@ -1142,15 +1134,7 @@ def join_pcm(pcms, req, device: int = -1):
     outs, ns, P = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), C.c_size_t()
     L = lib()
     check((L.jb_join_pcm_batch_i16 if i16 else L.jb_join_pcm_batch)(ins, nin, n, arr, device, outs, ns, C.byref(P)))
-    res = []
-    ety = C.c_int16 if i16 else C.c_double
-    for p in range(P.value):
-        if ns[p]:
-            res.append(np.frombuffer((ety * ns[p]).from_address(outs[p]), dtype=np.int16 if i16 else np.float64).copy())
-        else:
-            res.append(np.zeros(0, dtype=np.int16 if i16 else np.float64))
-        L.jb_join_free(outs[p])
-    return res
+    return _take(L.jb_join_free, outs, ns, P.value, np.int16 if i16 else np.float64)
 
 
 def _biquads(arr, n):
@@ -1189,27 +1173,18 @@ def filter_pcm(pcms, filters, hz, device: int = -1, i16: bool = False):
     Filter, or None) at hz[u]; one Filter or one rate stands for all.  f64 out, or int16 by the 16-bit sink's rule."""
     import numpy as np
     L = lib()
-    arrs = [np.ascontiguousarray(p, dtype=np.float64) for p in pcms]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args(pcms, np.float64, void=True)
     farr, nf = filter_array(filters, n)
     if nf != n:
         raise ValueError("filter_pcm: one filter, or one per utterance")
     rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
     if len(rates) != n:
         raise ValueError("filter_pcm: one rate, or one per utterance")
-    ins = (C.c_void_p * max(1, n))(*[a.ctypes.data for a in arrs])
-    nin = (C.c_size_t * max(1, n))(*[a.size for a in arrs])
     hzs = (C.c_uint32 * max(1, n))(*rates)
     outs = (C.c_void_p * max(1, n))()
     ns = (C.c_size_t * max(1, n))()
     check((L.jb_filter_pcm_batch_i16 if i16 else L.jb_filter_pcm_batch)(ins, nin, n, farr, hzs, device, outs, ns))
-    res = []
-    for u in range(n):
-        ct = C.c_int16 if i16 else C.c_double
-        buf = C.cast(outs[u], C.POINTER(ct))
-        res.append(np.ctypeslib.as_array(buf, shape=(max(int(ns[u]), 1),))[:int(ns[u])].copy())
-        L.jb_filter_free(outs[u])
-    return res
+    return _take(L.jb_filter_free, outs, ns, n, np.int16 if i16 else np.float64)
 
 
 def limiter_window(hz: int, opts=None):
@@ -1242,8 +1217,7 @@ def limiter_pcm(pcms, hz, gain, ceiling_db, peak_mode=0, opts=None, device: int 
     opts are one value for all or one per utterance.  Returns ([y], [report dict])."""
     import numpy as np
     L = lib()
-    arrs = [np.ascontiguousarray(p, dtype=np.float64) for p in pcms]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args(pcms, np.float64, void=True)
 
     def per(v, what):
         vs = [v] * n if np.isscalar(v) else list(v)
@@ -1253,8 +1227,6 @@ def limiter_pcm(pcms, hz, gain, ceiling_db, peak_mode=0, opts=None, device: int 
     oarr, no = limiter_array(limiter() if opts is None else opts, n)
     if no != n and n:
         raise ValueError("limiter_pcm: one request, or one per utterance")
-    ins = (C.c_void_p * max(1, n))(*[a.ctypes.data for a in arrs])
-    nin = (C.c_size_t * max(1, n))(*[a.size for a in arrs])
     hzs = (C.c_uint32 * max(1, n))(*[int(h) for h in per(hz, "rate")])
     gs = (C.c_double * max(1, n))(*[float(g) for g in per(gain, "gain")])
     cs = (C.c_double * max(1, n))(*[float(c) for c in per(ceiling_db, "ceiling")])
@@ -1263,12 +1235,7 @@ def limiter_pcm(pcms, hz, gain, ceiling_db, peak_mode=0, opts=None, device: int 
     reps = (LimiterReport * max(1, n))()
     check((L.jb_limiter_pcm_batch_i16 if i16 else L.jb_limiter_pcm_batch)(ins, nin, n, hzs, gs, cs, ms, oarr, device,
                                                                           outs, reps))
-    res = []
-    for u in range(n):
-        ct = C.c_int16 if i16 else C.c_double
-        buf = C.cast(outs[u], C.POINTER(ct))
-        res.append(np.ctypeslib.as_array(buf, shape=(max(arrs[u].size, 1),))[:arrs[u].size].copy())
-        L.jb_limiter_free(outs[u])
+    res = _take(L.jb_limiter_free, outs, [a.size for a in arrs], n, np.int16 if i16 else np.float64)
     return res, [reps[u].as_dict() for u in range(n)]
 
 
@@ -1277,19 +1244,12 @@ def resample(pcms, in_hz: int, out_hz: int, device: int = -1):
     import numpy as np
 
     single = isinstance(pcms, np.ndarray)
-    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in ([pcms] if single else pcms)]
-    n = len(arrs)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
     L = lib()
-    dp = C.POINTER(C.c_double)
-    ins = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in arrs])
-    nin = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
-    outs = (dp * max(n, 1))()
+    outs = (C.POINTER(C.c_double) * max(n, 1))()
     nout = (C.c_size_t * max(n, 1))()
     check(L.jb_resample_pcm_batch(ins, nin, n, in_hz, out_hz, device, outs, nout))
-    res = []
-    for u in range(n):
-        res.append(np.ctypeslib.as_array(outs[u], shape=(nout[u],)).copy() if nout[u] else np.zeros(0))
-        L.jb_pcm_free(outs[u])
+    res = _take(L.jb_pcm_free, outs, nout, n, np.float64)
     return res[0] if single else res
 
 

@@ -1482,21 +1482,6 @@ template <class F> int each_utt(size_t lo, size_t hi, unsigned nt, F fn)
     return JB_OK;
 }
 
-// Each output's share of the host copy of a byte sink's slab into a malloc'ed buffer of its own: out[u] and its byte
-// count n_out[u]
-int hand_out(const std::vector<jb::ByteSpan> &places, const uint8_t *host, void **out, size_t *n_out)
-{
-    for (size_t u = 0; u < places.size(); u++) {
-        if (!(out[u] = malloc(std::max<size_t>((size_t)places[u].bytes, 1)))) {
-            jb::set_error("out of host memory");
-            return JB_ERR_INVALID;
-        }
-        memcpy(out[u], host + places[u].off, (size_t)places[u].bytes);
-        n_out[u] = (size_t)places[u].bytes;
-    }
-    return JB_OK;
-}
-
 // One engine request on its way through: the state its steps share
 struct SynthRun {
     const jb::SynthRequest &rq;
@@ -1778,7 +1763,10 @@ int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
         std::vector<jb::ByteSpan> places;
         std::unique_ptr<uint8_t[]> host;
         int rc = b->out.read_bytes_all(rq.sink, &places, &host);
-        if (rc || (rc = hand_out(places, host.get(), pcm + lo, n_samples + lo)))
+        std::vector<jb::PcmShare> shares;
+        for (const jb::ByteSpan &w : places)
+            shares.push_back({w.off, w.bytes});
+        if (rc || (rc = jb::hand_out(host.get(), 1, shares, pcm + lo, n_samples + lo)))
             return rc;
         for (size_t p = 0; rq.sink == jb::SynthSink::Adpcm && rq.adpcm_samples && p < places.size(); p++)
             rq.adpcm_samples[lo + p] = rq.join ? (size_t)b->out.programme(p).n : b->out.samples(p);

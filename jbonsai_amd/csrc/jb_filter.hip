@@ -342,108 +342,49 @@ template <class T>
 int filter_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_filter *f, const uint32_t *hz,
                      int32_t device, T **out, size_t *n_out, const char *who)
 {
-    if (n && (!in || !n_in || !f || !hz || !out || !n_out))
-        return JB_ERR_INVALID;
-    if (n > 0x7fffffffu)
-        return JB_ERR_INVALID;
-    for (size_t u = 0; u < n; u++) {
-        if (n_in[u] && !in[u])
-            return JB_ERR_INVALID;
-        out[u] = nullptr;
-        n_out[u] = 0;
-    }
-    std::vector<FilterClass> classes;
-    std::vector<uint32_t> cls_of;
-    int rc = filter_classes(f, n, hz, n, &classes, &cls_of, who);
+    int rc = pcm_check((const void *const *)in, n_in, n, f && hz && out && n_out, (void **)out, n_out);
     if (rc)
         return rc;
+    std::vector<FilterClass> classes;
+    std::vector<uint32_t> cls_of;
+    if ((rc = filter_classes(f, n, hz, n, &classes, &cls_of, who)))
+        return rc;
     std::vector<FilterUtt> utts(n);
-    uint64_t samples = 0, tiles = 0;
+    uint64_t tiles = 0;
     for (size_t u = 0; u < n; u++) {
         if (filter_tiles(n_in[u]) > kFiltMaxTiles) {
             set_error(std::string(who) + ": utterance " + std::to_string(u) + " is too long");
             return JB_ERR_UNSUPPORTED;
         }
         utts[u] = {nullptr, nullptr, n_in[u], tiles, 0, (uint32_t)filter_tiles(n_in[u]), cls_of[u]};
-        samples += n_in[u];
         tiles += utts[u].ntiles;
     }
-    int dev = device, prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
-        set_error("no HIP device");
-        return JB_ERR_DEVICE;
-    }
-    DeviceScratch scratch;
-    if (scratch.enter(dev) != hipSuccess) {
-        set_error("hipSetDevice failed");
-        return JB_ERR_DEVICE;
-    }
-    double *dx = nullptr, *st = nullptr;
-    T *dy = nullptr;
-    FilterClass *dc = nullptr;
-    FilterUtt *du = nullptr;
-    hipError_t e = scratch.open_stream();
-    hipStream_t s = scratch.stream;
-    if (e == hipSuccess)
-        e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dy, std::max<uint64_t>(samples, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&st, std::max<uint64_t>(tiles * kFiltMaxD, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dc, std::max<size_t>(classes.size(), 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&du, std::max<size_t>(n, 1));
-    FilterLaunch l;
-    std::vector<T> host;
-    if (e == hipSuccess) {
-        uint64_t off = 0;
-        for (size_t u = 0; u < n; u++) {
-            utts[u].x = dx + off;
-            utts[u].y = dy + off;
-            off += n_in[u];
-        }
-        if ((rc = filter_launch_list(classes, utts, nullptr, &l)))
-            return rc;
-    }
-    uint64_t off = 0;
-    for (size_t u = 0; u < n && e == hipSuccess; u++) {
-        if (n_in[u])
-            e = hipMemcpyAsync(dx + off, in[u], sizeof(double) * n_in[u], hipMemcpyHostToDevice, s);
-        off += n_in[u];
-    }
-    if (e == hipSuccess && !classes.empty())
-        e = hipMemcpyAsync(dc, classes.data(), sizeof(FilterClass) * classes.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(du, l.utts.data(), sizeof(FilterUtt) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_filter(dc, du, l, st, sizeof(T) == 2, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    if (e == hipSuccess && samples) {
-        host.resize(samples);
-        e = hipMemcpy(host.data(), dy, sizeof(T) * samples, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess)
-        return hip_fail(e, who);
-    off = 0;
+    DeviceScratch ds;
+    if ((rc = ds.open(device, who)))
+        return rc;
+    std::vector<uint64_t> off;
+    const double *dx = ds.pack(in, n_in, n, &off);
+    T *dy = ds.alloc<T>(off[n]);
+    double *st = ds.alloc<double>(tiles * kFiltMaxD);
     for (size_t u = 0; u < n; u++) {
-        out[u] = (T *)malloc(std::max<size_t>(n_in[u], 1) * sizeof(T));
-        if (!out[u]) {
-            for (size_t k = 0; k < u; k++) {
-                free(out[k]);
-                out[k] = nullptr;
-                n_out[k] = 0;
-            }
-            set_error("out of host memory");
-            return JB_ERR_INVALID;
-        }
-        if (n_in[u])
-            memcpy(out[u], host.data() + off, n_in[u] * sizeof(T));
-        n_out[u] = n_in[u];
-        off += n_in[u];
+        utts[u].x = dx + off[u];
+        utts[u].y = dy + off[u];
     }
-    return JB_OK;
+    FilterLaunch l;
+    if ((rc = filter_launch_list(classes, utts, nullptr, &l)))
+        return rc;
+    const FilterClass *dc = ds.upload(classes);
+    const FilterUtt *du = ds.upload(l.utts);
+    if (ds.ok())
+        ds.err = launch_filter(dc, du, l, st, sizeof(T) == 2, ds.stream);
+    std::vector<T> host;
+    ds.read_back(&host, dy, off[n]);
+    if ((rc = ds.status()))
+        return rc;
+    std::vector<PcmShare> shares(n);
+    for (size_t u = 0; u < n; u++)
+        shares[u] = {off[u], n_in[u]};
+    return hand_out(host.data(), sizeof(T), shares, (void **)out, n_out);
 }
 
 } // namespace

@@ -843,142 +843,66 @@ int jb_flac_encode_pcm_batch_meta(const int16_t *const *in, const size_t *n_in, 
     if (rc || (rc = flac_check_meta(meta, &m)))
         return rc;
     const bool md5 = (m.flags & kFlacMetaMd5) != 0;
-    if (n && (!in || !n_in || !out || !n_out))
-        return JB_ERR_INVALID;
-    if (n > 0x7fffffffu)
-        return JB_ERR_INVALID;
-    for (size_t u = 0; u < n; u++) {
-        if (n_in[u] && !in[u])
-            return JB_ERR_INVALID;
-        out[u] = nullptr;
-        n_out[u] = 0;
-    }
+    if ((rc = pcm_check((const void *const *)in, n_in, n, out && n_out, (void **)out, n_out)))
+        return rc;
     {
         uint32_t c, b, v;
         if ((rc = flac_rate_code(hz, &c, &b, &v)))
             return rc;
     }
-    std::vector<uint64_t> ns(n);
+    DeviceScratch ds;
+    if ((rc = ds.open(device, "jb_flac_encode_pcm_batch")))
+        return rc;
+    std::vector<uint64_t> off;
+    const int16_t *dx = ds.pack(in, n_in, n, &off);
+    std::vector<uint64_t> ns(n_in, n_in + n);
     std::vector<uint32_t> hzs(n, hz);
-    std::vector<const int16_t *> xs(n, nullptr);
-    uint64_t samples = 0;
-    for (size_t u = 0; u < n; u++) {
-        ns[u] = n_in[u];
-        samples += n_in[u];
-    }
-    int dev = device, prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
-        set_error("no HIP device");
-        return JB_ERR_DEVICE;
-    }
-    DeviceScratch scratch;
-    if (scratch.enter(dev) != hipSuccess) {
-        set_error("hipSetDevice failed");
-        return JB_ERR_DEVICE;
-    }
-    int16_t *dx = nullptr;
-    uint8_t *dslots = nullptr, *dout = nullptr;
-    FlacUtt *du = nullptr;
-    FlacWork *dw = nullptr;
-    uint32_t *dfs = nullptr;
-    uint64_t *dfo = nullptr, *dtot = nullptr;
-    uint32_t *dord = nullptr, *ddig = nullptr;
-    FlacOut *dres = nullptr;
-    hipStream_t s = nullptr;
+    std::vector<const int16_t *> xs(n);
+    for (size_t u = 0; u < n; u++)
+        xs[u] = dx + off[u];
     std::vector<FlacUtt> utts;
     std::vector<FlacWork> work;
     std::vector<uint32_t> order;
+    uint64_t slot_bytes = 0, bound = 0;
+    if ((rc = flac_plan(p, m, xs.data(), ns.data(), hzs.data(), n, &utts, &work, &slot_bytes, &bound)))
+        return rc;
     uint32_t max_points = 0;
-    std::vector<FlacOut> res(n);
-    std::vector<uint8_t> host;
-    uint64_t slot_bytes = 0, bound = 0, total = 0;
-    hipError_t e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
-    uint64_t off = 0;
-    for (size_t u = 0; u < n && e == hipSuccess; u++) {
-        xs[u] = dx + off;
-        off += n_in[u];
-    }
-    if (e == hipSuccess &&
-        (rc = flac_plan(p, m, xs.data(), ns.data(), hzs.data(), n, &utts, &work, &slot_bytes, &bound)))
-        e = hipErrorInvalidValue;
     for (const FlacUtt &w : utts)
         max_points = std::max(max_points, w.n_points);
-    if (e == hipSuccess && md5) {
+    uint32_t *dord = nullptr, *ddig = nullptr;
+    if (md5) {
         flac_md5_order(utts, nullptr, &order);
-        if ((e = scratch.alloc(&dord, std::max<size_t>(n, 1))) == hipSuccess)
-            e = scratch.alloc(&ddig, 4 * std::max<size_t>(n, 1));
+        dord = ds.upload(order);
+        ddig = ds.alloc<uint32_t>(4 * n);
     }
-    if (e == hipSuccess) {
-        e = scratch.open_stream();
-        s = scratch.stream;
-    }
-    if (e == hipSuccess)
-        e = scratch.alloc(&dslots, std::max<uint64_t>(slot_bytes, 4));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dout, std::max<uint64_t>(bound, 4));
-    if (e == hipSuccess)
-        e = scratch.alloc(&du, std::max<size_t>(n, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dw, std::max<size_t>(work.size(), 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dfs, std::max<size_t>(work.size(), 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dfo, std::max<size_t>(work.size(), 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dres, std::max<size_t>(n, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dtot, 1);
-    off = 0;
-    for (size_t u = 0; u < n && e == hipSuccess; u++) {
-        if (n_in[u])
-            e = hipMemcpyAsync(dx + off, in[u], sizeof(int16_t) * n_in[u], hipMemcpyHostToDevice, s);
-        off += n_in[u];
-    }
-    if (e == hipSuccess) {
-        flac_bind(&utts, dslots);
-        if (n)
-            e = hipMemcpyAsync(du, utts.data(), sizeof(FlacUtt) * n, hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess && !work.empty())
-        e = hipMemcpyAsync(dw, work.data(), sizeof(FlacWork) * work.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && !order.empty())
-        e = hipMemcpyAsync(dord, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_flac_encode(p, du, dw, (uint32_t)work.size(), dfs, s);
-    if (e == hipSuccess && md5)
-        e = launch_flac_md5(du, dord, (uint32_t)order.size(), ddig, s);
-    if (e == hipSuccess)
-        e = launch_flac_pack(p, du, (uint32_t)n, dw, (uint32_t)work.size(), dfs, dfo, dres, dtot, dout, s,
-                             md5 ? ddig : nullptr, max_points);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(res.data(), dres, sizeof(FlacOut) * n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(&total, dtot, sizeof total, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    if (e == hipSuccess && total) {
-        host.resize(total);
-        e = hipMemcpy(host.data(), dout, total, hipMemcpyDeviceToHost);
-    }
-    if (rc)
+    uint8_t *dslots = ds.alloc<uint8_t>(std::max<uint64_t>(slot_bytes, 4));
+    uint8_t *dout = ds.alloc<uint8_t>(std::max<uint64_t>(bound, 4));
+    flac_bind(&utts, dslots);
+    const FlacUtt *du = ds.upload(utts);
+    const FlacWork *dw = ds.upload(work);
+    uint32_t *dfs = ds.alloc<uint32_t>(work.size());
+    uint64_t *dfo = ds.alloc<uint64_t>(work.size()), *dtot = ds.alloc<uint64_t>(1);
+    FlacOut *dres = ds.alloc<FlacOut>(n);
+    if (ds.ok())
+        ds.err = launch_flac_encode(p, du, dw, (uint32_t)work.size(), dfs, ds.stream);
+    if (ds.ok() && md5)
+        ds.err = launch_flac_md5(du, dord, (uint32_t)order.size(), ddig, ds.stream);
+    if (ds.ok())
+        ds.err = launch_flac_pack(p, du, (uint32_t)n, dw, (uint32_t)work.size(), dfs, dfo, dres, dtot, dout, ds.stream,
+                                  md5 ? ddig : nullptr, max_points);
+    // the streams' sizes and places first, then the used part of the compact slab
+    std::vector<FlacOut> res;
+    std::vector<uint64_t> total;
+    std::vector<uint8_t> host;
+    ds.read_back(&res, dres, n);
+    ds.read_back(&total, dtot, n ? 1 : 0);
+    ds.read_back(&host, dout, total.empty() ? 0 : total[0]);
+    if ((rc = ds.status()))
         return rc;
-    if (e != hipSuccess)
-        return hip_fail(e, "jb_flac_encode_pcm_batch");
-    for (size_t u = 0; u < n; u++) {
-        out[u] = (uint8_t *)malloc(res[u].bytes);
-        if (!out[u]) {
-            for (size_t k = 0; k < u; k++) {
-                free(out[k]);
-                out[k] = nullptr;
-                n_out[k] = 0;
-            }
-            set_error("out of host memory");
-            return JB_ERR_INVALID;
-        }
-        memcpy(out[u], host.data() + res[u].off, res[u].bytes);
-        n_out[u] = res[u].bytes;
-    }
-    return JB_OK;
+    std::vector<PcmShare> shares(n);
+    for (size_t u = 0; u < n; u++)
+        shares[u] = {res[u].off, res[u].bytes};
+    return hand_out(host.data(), 1, shares, (void **)out, n_out);
 }
 
 int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, uint32_t hz,
@@ -989,65 +913,30 @@ int jb_flac_encode_pcm_batch(const int16_t *const *in, const size_t *n_in, size_
 
 int jb_flac_md5_pcm_batch(const int16_t *const *in, const size_t *n_in, size_t n, int32_t device, uint8_t *digests)
 {
-    if (n && (!in || !n_in || !digests))
-        return JB_ERR_INVALID;
-    if (n > 0x7fffffffu)
-        return JB_ERR_INVALID;
-    uint64_t samples = 0;
-    for (size_t u = 0; u < n; u++) {
-        if (n_in[u] && !in[u])
-            return JB_ERR_INVALID;
-        samples += n_in[u];
-    }
-    if (!n)
-        return JB_OK;
-    int dev = device, prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
-        set_error("no HIP device");
-        return JB_ERR_DEVICE;
-    }
-    DeviceScratch scratch;
-    if (scratch.enter(dev) != hipSuccess) {
-        set_error("hipSetDevice failed");
-        return JB_ERR_DEVICE;
-    }
+    int rc = pcm_check((const void *const *)in, n_in, n, digests != nullptr);
+    if (rc || !n)
+        return rc;
+    DeviceScratch ds;
+    if ((rc = ds.open(device, "jb_flac_md5_pcm_batch")))
+        return rc;
     // the inputs packed one after the other, as a batch's 16-bit slab has them: a start is only 2-byte aligned
-    int16_t *dx = nullptr;
-    FlacUtt *du = nullptr;
-    uint32_t *dord = nullptr, *ddig = nullptr;
+    std::vector<uint64_t> off;
+    const int16_t *dx = ds.pack(in, n_in, n, &off);
     std::vector<FlacUtt> utts(n);
-    std::vector<uint32_t> order, dig(4 * n);
-    hipError_t e = scratch.open_stream();
-    hipStream_t s = scratch.stream;
-    if (e == hipSuccess)
-        e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&du, n);
-    if (e == hipSuccess)
-        e = scratch.alloc(&dord, n);
-    if (e == hipSuccess)
-        e = scratch.alloc(&ddig, 4 * n);
-    uint64_t off = 0;
-    for (size_t u = 0; u < n && e == hipSuccess; u++) {
-        utts[u].x = dx + off;
+    for (size_t u = 0; u < n; u++) {
+        utts[u].x = dx + off[u];
         utts[u].n = n_in[u];
-        if (n_in[u])
-            e = hipMemcpyAsync(dx + off, in[u], sizeof(int16_t) * n_in[u], hipMemcpyHostToDevice, s);
-        off += n_in[u];
     }
+    std::vector<uint32_t> order, dig;
     flac_md5_order(utts, nullptr, &order);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(du, utts.data(), sizeof(FlacUtt) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(dord, order.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_flac_md5(du, dord, (uint32_t)n, ddig, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(dig.data(), ddig, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    if (e != hipSuccess)
-        return hip_fail(e, "jb_flac_md5_pcm_batch");
+    const FlacUtt *du = ds.upload(utts);
+    const uint32_t *dord = ds.upload(order);
+    uint32_t *ddig = ds.alloc<uint32_t>(4 * n);
+    if (ds.ok())
+        ds.err = launch_flac_md5(du, dord, (uint32_t)n, ddig, ds.stream);
+    ds.read_back(&dig, ddig, 4 * n);
+    if ((rc = ds.status()))
+        return rc;
     memcpy(digests, dig.data(), 16 * n); // A, B, C, D little-endian: the digest's byte order (a little-endian host)
     return JB_OK;
 }

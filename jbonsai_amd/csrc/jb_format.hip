@@ -162,89 +162,39 @@ int jb_format_pcm_batch(const double *const *in, const size_t *n_in, size_t n, c
     int rc = format_check_opts(opts->format, opts->dither, "jb_format_pcm_batch");
     if (rc)
         return rc;
-    if (n && (!in || !n_in || !out || !n_bytes))
-        return JB_ERR_INVALID;
-    if (n > 0x7fffffffu)
-        return JB_ERR_INVALID;
-    for (size_t u = 0; u < n; u++) {
-        if (n_in[u] && !in[u])
-            return JB_ERR_INVALID;
-        out[u] = nullptr;
-        n_bytes[u] = 0;
-    }
+    if ((rc = pcm_check((const void *const *)in, n_in, n, out && n_bytes, (void **)out, n_bytes)))
+        return rc;
     const size_t nb = format_bytes(opts->format);
-    int dev = device, prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
-        set_error("no HIP device");
-        return JB_ERR_DEVICE;
-    }
-    DeviceScratch scratch;
-    if (scratch.enter(dev) != hipSuccess) {
-        set_error("hipSetDevice failed");
-        return JB_ERR_DEVICE;
-    }
+    DeviceScratch ds;
+    if ((rc = ds.open(device, "jb_format_pcm_batch")))
+        return rc;
     // the inputs packed one after the other (8-byte aligned, as a batch's slab has them), every output on a
     // 16-byte boundary
+    std::vector<uint64_t> xoff;
+    const double *dx = ds.pack(in, n_in, n, &xoff);
     std::vector<FormatUtt> utts(n);
-    std::vector<uint64_t> yoff(n);
-    uint64_t samples = 0, bytes = 0, tiles = 0;
+    std::vector<PcmShare> shares(n);
+    uint64_t bytes = 0, tiles = 0;
     for (size_t u = 0; u < n; u++) {
         utts[u].n = n_in[u];
         utts[u].ft0 = tiles;
-        yoff[u] = bytes;
-        samples += n_in[u];
+        shares[u] = {bytes, n_in[u] * nb};
         bytes += (n_in[u] * nb + 15) & ~(uint64_t)15;
         tiles += (n_in[u] + kFmtTile - 1) / kFmtTile;
     }
-    double *dx = nullptr;
-    uint8_t *dy = nullptr;
-    FormatUtt *du = nullptr;
-    std::vector<uint8_t> host;
-    hipError_t e = scratch.open_stream();
-    hipStream_t s = scratch.stream;
-    if (e == hipSuccess)
-        e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dy, std::max<uint64_t>(bytes, 16));
-    if (e == hipSuccess)
-        e = scratch.alloc(&du, std::max<size_t>(n, 1));
-    uint64_t off = 0;
-    for (size_t u = 0; u < n && e == hipSuccess; u++) {
-        utts[u].x = dx + off;
-        utts[u].y = dy + yoff[u];
-        if (n_in[u])
-            e = hipMemcpyAsync(dx + off, in[u], sizeof(double) * n_in[u], hipMemcpyHostToDevice, s);
-        off += n_in[u];
-    }
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(du, utts.data(), sizeof(FormatUtt) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_format(opts->format, opts->dither, opts->seed, du, (uint32_t)n, tiles, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    if (e == hipSuccess && bytes) {
-        host.resize(bytes);
-        e = hipMemcpy(host.data(), dy, bytes, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess)
-        return hip_fail(e, "jb_format_pcm_batch");
+    uint8_t *dy = ds.alloc<uint8_t>(std::max<uint64_t>(bytes, 16));
     for (size_t u = 0; u < n; u++) {
-        const size_t nby = n_in[u] * nb;
-        out[u] = (uint8_t *)malloc(std::max<size_t>(nby, 1));
-        if (!out[u]) {
-            for (size_t k = 0; k < u; k++) {
-                free(out[k]);
-                out[k] = nullptr;
-                n_bytes[k] = 0;
-            }
-            set_error("out of host memory");
-            return JB_ERR_INVALID;
-        }
-        if (nby)
-            memcpy(out[u], host.data() + yoff[u], nby);
-        n_bytes[u] = nby;
+        utts[u].x = dx + xoff[u];
+        utts[u].y = dy + shares[u].off;
     }
-    return JB_OK;
+    const FormatUtt *du = ds.upload(utts);
+    if (ds.ok())
+        ds.err = launch_format(opts->format, opts->dither, opts->seed, du, (uint32_t)n, tiles, ds.stream);
+    std::vector<uint8_t> host;
+    ds.read_back(&host, dy, bytes);
+    if ((rc = ds.status()))
+        return rc;
+    return hand_out(host.data(), 1, shares, (void **)out, n_bytes);
 }
 
 } // extern "C"

@@ -9,6 +9,7 @@
 #include "jb_loudness_rules.h"
 #include "jb_md5.h"
 #include "jb_output.h"
+#include "jb_pcm_call.h"
 
 #include <cmath>
 #include <map>
@@ -355,31 +356,86 @@ struct TrackSrc {
 };
 
 // What an entry that works on PCM the caller holds needs on the device for the length of the call: makes a device
-// current and gives the caller its own back, owns a non-blocking stream and the device blocks it hands out
+// current and gives the caller its own back, owns a non-blocking stream and the device blocks it hands out.  The
+// jb_*_pcm_batch entries (their host half: jb_pcm_call.h) open it, then allocate, pack, upload and read back through it:
+// it carries the first HIP error of these calls (`err`; every later call is then skipped and returns null), and the
+// entry asks once, with status(), before it hands anything out
 struct DeviceScratch {
-    int prev = -1;
+    int prev = -1, device = -1;
     bool changed = false;
     hipStream_t stream = nullptr;
     std::vector<void *> blocks;
+    hipError_t err = hipSuccess;
+    const char *who = "";
     DeviceScratch() = default;
     DeviceScratch(const DeviceScratch &) = delete;
     DeviceScratch &operator=(const DeviceScratch &) = delete;
-    hipError_t enter(int device)
+    hipError_t enter(int dev) // dev < 0: the caller's current one
     {
         hipError_t e = hipGetDevice(&prev);
+        if (e != hipSuccess)
+            prev = -1;
+        device = dev < 0 ? prev : dev;
         if (e == hipSuccess && prev != device) {
             e = hipSetDevice(device);
             changed = e == hipSuccess;
         }
         return e;
     }
-    hipError_t open_stream() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
-    template <class T> hipError_t alloc(T **p, size_t n)
+    // The device of an entry `name` (dev < 0: the caller's current one) made current, and the stream: JB_ERR_DEVICE
+    // (set_error says which) without a device
+    int open(int dev, const char *name)
     {
-        hipError_t e = hipMalloc((void **)p, sizeof(T) * n);
-        if (e == hipSuccess)
-            blocks.push_back((void *)*p);
-        return e;
+        who = name;
+        const hipError_t e = enter(dev);
+        if (prev < 0) {
+            set_error("no HIP device");
+            return JB_ERR_DEVICE;
+        }
+        if (e != hipSuccess) {
+            set_error("hipSetDevice failed");
+            return JB_ERR_DEVICE;
+        }
+        err = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        return JB_OK;
+    }
+    bool ok() const { return err == hipSuccess; }
+    int status() const { return ok() ? JB_OK : hip_fail(err, who); }
+    template <class T> T *alloc(size_t n) // max(n, 1) elements
+    {
+        T *p = nullptr;
+        if (ok() && (err = hipMalloc((void **)&p, sizeof(T) * (n ? n : 1))) == hipSuccess)
+            blocks.push_back((void *)p);
+        return p;
+    }
+    // A block of max(v.size(), 1) elements and v on its way into it (an empty list: nothing is copied); v lives to the
+    // wait of read_back
+    template <class T> T *upload(const std::vector<T> &v)
+    {
+        T *p = alloc<T>(v.size());
+        if (ok() && !v.empty())
+            err = hipMemcpyAsync(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, stream);
+        return p;
+    }
+    // The inputs one after the other in one slab (*off: pcm_pack), each on its way into it
+    template <class T> T *pack(const T *const *in, const size_t *n_in, size_t n, std::vector<uint64_t> *off)
+    {
+        *off = pcm_pack(n_in, n);
+        T *p = alloc<T>((*off)[n]);
+        for (size_t u = 0; u < n && ok(); u++)
+            if (n_in[u])
+                err = hipMemcpyAsync(p + (*off)[u], in[u], sizeof(T) * n_in[u], hipMemcpyHostToDevice, stream);
+        return p;
+    }
+    // Waits for the stream, then host[0..n) = src[0..n)
+    template <class T> void read_back(std::vector<T> *host, const T *src, size_t n)
+    {
+        if (ok())
+            err = hipStreamSynchronize(stream);
+        if (ok() && n) {
+            host->resize(n);
+            err = hipMemcpy(host->data(), src, sizeof(T) * n, hipMemcpyDeviceToHost);
+        }
     }
     ~DeviceScratch()
     {
@@ -393,6 +449,15 @@ struct DeviceScratch {
             (void)hipSetDevice(prev);
     }
 };
+// pcm_hand_out with the text of a failed allocation in jb_last_error
+inline int hand_out(const void *host, size_t elem, const std::vector<PcmShare> &shares, void **out, size_t *n_out)
+{
+    const char *err = "";
+    const int rc = pcm_hand_out(host, elem, shares, out, n_out, &err);
+    if (rc)
+        set_error(err);
+    return rc;
+}
 
 struct Batch;
 

@@ -137,93 +137,39 @@ int join_pcm_batch(const T *const *in, const size_t *n_in, size_t n, const jb_jo
 {
     if (n_programmes)
         *n_programmes = 0;
-    if (n && (!in || !n_in || !req || !out || !n_out))
-        return JB_ERR_INVALID;
-    if (n > 0x7fffffffu)
-        return JB_ERR_INVALID;
-    for (size_t u = 0; u < n; u++) {
-        if (n_in[u] && !in[u])
-            return JB_ERR_INVALID;
-        out[u] = nullptr;
-        n_out[u] = 0;
-    }
-    std::vector<uint64_t> ns(n_in, n_in + n);
-    JoinLayout lay;
-    int rc = join_layout_checked((const JoinUtt *)req, ns.data(), nullptr, n, sizeof(T), &lay, who);
+    int rc = pcm_check((const void *const *)in, n_in, n, req && out && n_out, (void **)out, n_out);
     if (rc)
         return rc;
+    std::vector<uint64_t> ns(n_in, n_in + n);
+    JoinLayout lay;
+    if ((rc = join_layout_checked((const JoinUtt *)req, ns.data(), nullptr, n, sizeof(T), &lay, who)))
+        return rc;
     const size_t P = lay.progs.size();
-    int dev = device, prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
-        set_error("no HIP device");
-        return JB_ERR_DEVICE;
-    }
-    DeviceScratch scratch;
-    if (scratch.enter(dev) != hipSuccess) {
-        set_error("hipSetDevice failed");
-        return JB_ERR_DEVICE;
-    }
-    std::vector<uint64_t> xoff(n);
-    uint64_t samples = 0;
-    for (size_t u = 0; u < n; u++) {
-        xoff[u] = samples;
-        samples += n_in[u];
-    }
-    T *dx = nullptr, *dy = nullptr;
-    JoinSpan *ds = nullptr;
-    JoinMember *dm = nullptr;
-    std::vector<T> host;
-    hipError_t e = scratch.open_stream();
-    hipStream_t s = scratch.stream;
-    if (e == hipSuccess)
-        e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dy, std::max<uint64_t>(lay.total, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&ds, std::max<size_t>(P, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dm, std::max<size_t>(n, 1));
+    DeviceScratch ds;
+    if ((rc = ds.open(device, who)))
+        return rc;
+    std::vector<uint64_t> xoff;
+    const T *dx = ds.pack(in, n_in, n, &xoff);
+    T *dy = ds.alloc<T>(lay.total);
     std::vector<JoinMember> members;
     std::vector<JoinSpan> spans;
+    join_lists(lay, (const JoinUtt *)req, ns.data(), xoff.data(), dx, dy, sizeof(T), &members, &spans);
     uint64_t tiles = 0;
-    if (e == hipSuccess) {
-        join_lists(lay, (const JoinUtt *)req, ns.data(), xoff.data(), dx, dy, sizeof(T), &members, &spans);
-        for (const JoinSpan &w : spans)
-            tiles += join_tiles(w.k0, w.k1, sizeof(T) == 2);
-    }
-    for (size_t u = 0; u < n && e == hipSuccess; u++)
-        if (n_in[u])
-            e = hipMemcpyAsync(dx + xoff[u], in[u], sizeof(T) * n_in[u], hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(dm, members.data(), sizeof(JoinMember) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && P)
-        e = hipMemcpyAsync(ds, spans.data(), sizeof(JoinSpan) * P, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_join(sizeof(T) == 2, ds, (uint32_t)P, tiles, dm, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    if (e == hipSuccess && lay.total) {
-        host.resize(lay.total);
-        e = hipMemcpy(host.data(), dy, sizeof(T) * lay.total, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess)
-        return hip_fail(e, who);
-    for (size_t p = 0; p < P; p++) {
-        const size_t np = (size_t)lay.units[p].n;
-        out[p] = (T *)malloc(std::max<size_t>(np, 1) * sizeof(T));
-        if (!out[p]) {
-            for (size_t k = 0; k < p; k++) {
-                free(out[k]);
-                out[k] = nullptr;
-                n_out[k] = 0;
-            }
-            set_error("out of host memory");
-            return JB_ERR_INVALID;
-        }
-        if (np)
-            memcpy(out[p], host.data() + lay.units[p].off, np * sizeof(T));
-        n_out[p] = np;
-    }
+    for (const JoinSpan &w : spans)
+        tiles += join_tiles(w.k0, w.k1, sizeof(T) == 2);
+    const JoinMember *dm = ds.upload(members);
+    const JoinSpan *dsp = ds.upload(spans);
+    if (ds.ok())
+        ds.err = launch_join(sizeof(T) == 2, dsp, (uint32_t)P, tiles, dm, ds.stream);
+    std::vector<T> host;
+    ds.read_back(&host, dy, lay.total);
+    if ((rc = ds.status()))
+        return rc;
+    std::vector<PcmShare> shares(P);
+    for (size_t p = 0; p < P; p++)
+        shares[p] = {lay.units[p].off, lay.units[p].n};
+    if ((rc = hand_out(host.data(), sizeof(T), shares, (void **)out, n_out)))
+        return rc;
     if (n_programmes)
         *n_programmes = P;
     return JB_OK;

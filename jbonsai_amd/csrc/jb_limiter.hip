@@ -328,20 +328,14 @@ int limiter_pcm_batch(const double *const *in, const size_t *n_in, size_t n, con
                       const double *ceiling_db, const uint32_t *mode, const jb_limiter_opts *opts, int32_t device,
                       T **out, jb_limiter_report *reports, const char *who)
 {
-    if (n && (!in || !n_in || !hz || !gain || !ceiling_db || !mode || !opts || !out))
-        return JB_ERR_INVALID;
-    if (n > 0x7fffffffu)
-        return JB_ERR_INVALID;
-    for (size_t u = 0; u < n; u++) {
-        if (n_in[u] && !in[u])
-            return JB_ERR_INVALID;
-        out[u] = nullptr;
-    }
+    int rc = pcm_check((const void *const *)in, n_in, n, hz && gain && ceiling_db && mode && opts && out,
+                       (void **)out);
+    if (rc)
+        return rc;
     LimiterClasses classes;
     std::vector<LimiterUtt> utts(n);
     std::vector<uint32_t> Ls(n), Hs(n);
-    uint64_t samples = 0, tiles = 0;
-    int rc;
+    uint64_t tiles = 0;
     for (size_t u = 0; u < n; u++) {
         if (mode[u] != JB_PEAK_SAMPLE && mode[u] != JB_PEAK_TRUE) {
             set_error(std::string(who) + ": a mode is JB_PEAK_SAMPLE or JB_PEAK_TRUE");
@@ -356,81 +350,37 @@ int limiter_pcm_batch(const double *const *in, const size_t *n_in, size_t n, con
             return rc;
         utts[u] = LimiterUtt{nullptr, nullptr,    n_in[u],    tiles, tiles, lim_ceiling(ceiling_db[u]),
                              gain[u], kLimNoSlot, cls,        (uint32_t)u, 0};
-        samples += n_in[u];
         tiles += limiter_tiles(n_in[u]);
     }
-    int dev = device, prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
-        set_error("no HIP device");
-        return JB_ERR_DEVICE;
-    }
-    DeviceScratch scratch;
-    if (scratch.enter(dev) != hipSuccess) {
-        set_error("hipSetDevice failed");
-        return JB_ERR_DEVICE;
-    }
-    double *dx = nullptr;
-    T *dy = nullptr;
-    LimiterClass *dc = nullptr;
-    LimiterUtt *du = nullptr;
-    LimiterTile *dt = nullptr;
-    LimiterResult *dr = nullptr;
-    hipError_t e = scratch.open_stream();
-    hipStream_t s = scratch.stream;
-    if (e == hipSuccess)
-        e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dy, std::max<uint64_t>(samples, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dc, std::max<size_t>(classes.tables.size(), 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&du, std::max<size_t>(n, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dt, std::max<uint64_t>(tiles, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dr, std::max<size_t>(n, 1));
-    uint64_t off = 0;
-    for (size_t u = 0; u < n && e == hipSuccess; u++) {
-        utts[u].x = dx + off;
-        utts[u].y = dy + off;
-        if (n_in[u])
-            e = hipMemcpyAsync(dx + off, in[u], sizeof(double) * n_in[u], hipMemcpyHostToDevice, s);
-        off += n_in[u];
-    }
-    std::vector<T> host(samples);
-    std::vector<LimiterResult> results(n);
-    if (e == hipSuccess && !classes.tables.empty())
-        e = hipMemcpyAsync(dc, classes.tables.data(), sizeof(LimiterClass) * classes.tables.size(),
-                           hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(du, utts.data(), sizeof(LimiterUtt) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_limiter(dc, du, (uint32_t)n, tiles, nullptr, dt, dr, sizeof(T) == 2, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    if (e == hipSuccess && samples)
-        e = hipMemcpy(host.data(), dy, sizeof(T) * samples, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && n)
-        e = hipMemcpy(results.data(), dr, sizeof(LimiterResult) * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return hip_fail(e, who);
-    off = 0;
+    DeviceScratch ds;
+    if ((rc = ds.open(device, who)))
+        return rc;
+    std::vector<uint64_t> off;
+    const double *dx = ds.pack(in, n_in, n, &off);
+    T *dy = ds.alloc<T>(off[n]);
     for (size_t u = 0; u < n; u++) {
-        out[u] = (T *)malloc(std::max<size_t>(n_in[u], 1) * sizeof(T));
-        if (!out[u]) {
-            for (size_t k = 0; k < u; k++) {
-                free(out[k]);
-                out[k] = nullptr;
-            }
-            set_error("out of host memory");
-            return JB_ERR_INVALID;
-        }
-        if (n_in[u])
-            memcpy(out[u], host.data() + off, n_in[u] * sizeof(T));
-        if (reports)
-            reports[u] = jb_limiter_report{lim_reduction_db(results[u].min_a), results[u].count, Ls[u], Hs[u]};
-        off += n_in[u];
+        utts[u].x = dx + off[u];
+        utts[u].y = dy + off[u];
     }
+    const LimiterClass *dc = ds.upload(classes.tables);
+    const LimiterUtt *du = ds.upload(utts);
+    LimiterTile *dt = ds.alloc<LimiterTile>(tiles);
+    LimiterResult *dr = ds.alloc<LimiterResult>(n);
+    if (ds.ok())
+        ds.err = launch_limiter(dc, du, (uint32_t)n, tiles, nullptr, dt, dr, sizeof(T) == 2, ds.stream);
+    std::vector<T> host;
+    std::vector<LimiterResult> results;
+    ds.read_back(&host, dy, off[n]);
+    ds.read_back(&results, dr, n);
+    if ((rc = ds.status()))
+        return rc;
+    std::vector<PcmShare> shares(n);
+    for (size_t u = 0; u < n; u++)
+        shares[u] = {off[u], n_in[u]};
+    if ((rc = hand_out(host.data(), sizeof(T), shares, (void **)out, nullptr)))
+        return rc;
+    for (size_t u = 0; reports && u < n; u++)
+        reports[u] = jb_limiter_report{lim_reduction_db(results[u].min_a), results[u].count, Ls[u], Hs[u]};
     return JB_OK;
 }
 

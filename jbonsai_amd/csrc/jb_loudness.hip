@@ -940,36 +940,27 @@ struct PcmGroups {
 int measure_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
                       uint32_t mode, const char *what, std::vector<LoudnessResult> *res, PcmGroups *gr = nullptr)
 {
-    if (n && (!in || !n_in))
-        return JB_ERR_INVALID;
+    int rc = pcm_check((const void *const *)in, n_in, n);
+    if (rc)
+        return rc;
     if (hz == 0) {
         set_error("loudness: a rate of 0 Hz");
         return JB_ERR_INVALID;
     }
-    if (n > 0x7fffffffu)
-        return JB_ERR_INVALID;
-    for (size_t u = 0; u < n; u++)
-        if (n_in[u] && !in[u])
-            return JB_ERR_INVALID;
     LoudnessRate rate{};
-    int rc = loudness_rate(hz, &rate);
-    if (rc)
+    if ((rc = loudness_rate(hz, &rate)))
         return rc;
-    int dev = device, prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || (dev < 0 && (dev = prev) < 0)) {
-        set_error("no HIP device");
-        return JB_ERR_DEVICE;
-    }
-    DeviceScratch scratch;
-    if (scratch.enter(dev) != hipSuccess) {
-        set_error("hipSetDevice failed");
-        return JB_ERR_DEVICE;
-    }
+    DeviceScratch ds;
+    if ((rc = ds.open(device, what)))
+        return rc;
+    std::vector<uint64_t> off;
+    const double *dx = ds.pack(in, n_in, n, &off);
     std::vector<LoudnessUtt> utts(n);
-    uint64_t tiles = 0, samples = 0;
+    uint64_t tiles = 0;
     for (size_t u = 0; u < n; u++) {
         LoudnessUtt &w = utts[u];
         w = LoudnessUtt{};
+        w.x = dx + off[u];
         w.n = n_in[u];
         w.ntiles = loudness_tiles(rate, w.n);
         w.tile0 = w.lt0 = tiles;
@@ -978,50 +969,25 @@ int measure_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uin
         w.target = gr ? gr->target : NAN;
         w.ceiling = gr ? gr->ceiling : INFINITY;
         tiles += w.ntiles;
-        samples += w.n;
     }
-    double *dx = nullptr, *dst = nullptr, *dpk = nullptr, *dtp = nullptr, *dz = nullptr;
-    LoudnessRate *dr = nullptr;
-    LoudnessUtt *du = nullptr;
-    LoudnessResult *dres = nullptr;
-    std::vector<LoudnessResult> &out = *res;
-    out.assign(n, LoudnessResult{});
-    hipError_t e = scratch.open_stream();
-    hipStream_t s = scratch.stream;
-    if (e == hipSuccess)
-        e = scratch.alloc(&dx, std::max<uint64_t>(samples, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dst, 4 * std::max<uint64_t>(tiles, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dpk, std::max<uint64_t>(tiles, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dtp, std::max<uint64_t>(tiles, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dz, std::max<uint64_t>(tiles, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dr, 1);
-    if (e == hipSuccess)
-        e = scratch.alloc(&du, std::max<size_t>(n, 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dres, std::max<size_t>(n, 1));
-    uint64_t off = 0;
-    for (size_t u = 0; u < n && e == hipSuccess; u++) {
-        utts[u].x = dx + off;
-        if (n_in[u])
-            e = hipMemcpyAsync(dx + off, in[u], sizeof(double) * n_in[u], hipMemcpyHostToDevice, s);
-        off += n_in[u];
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(dr, &rate, sizeof rate, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(du, utts.data(), sizeof(LoudnessUtt) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_loudness_measure(dr, du, (uint32_t)n, tiles, dst, dpk, dtp, dz, dres, mode == JB_PEAK_TRUE, s);
-    if (gr && n && e == hipSuccess) {
-        // the sets: every utterance (members: the identity), then every group
-        const size_t G = gr->plan.size();
-        std::vector<LoudnessSet> sets(n + G);
-        std::vector<uint32_t> members(2 * n);
+    double *dst = ds.alloc<double>(4 * std::max<uint64_t>(tiles, 1)), *dpk = ds.alloc<double>(tiles);
+    double *dtp = ds.alloc<double>(tiles), *dz = ds.alloc<double>(tiles);
+    const std::vector<LoudnessRate> rates(1, rate);
+    const LoudnessRate *dr = ds.upload(rates);
+    const LoudnessUtt *du = ds.upload(utts);
+    LoudnessResult *dres = ds.alloc<LoudnessResult>(n);
+    if (ds.ok())
+        ds.err = launch_loudness_measure(dr, du, (uint32_t)n, tiles, dst, dpk, dtp, dz, dres, mode == JB_PEAK_TRUE,
+                                         ds.stream);
+    // the sets of a group request: every utterance (members: the identity), then every group
+    const size_t G = gr ? gr->plan.size() : 0;
+    std::vector<LoudnessSet> sets;
+    std::vector<uint32_t> members;
+    LoudnessGroupResult *dgres = nullptr;
+    LoudnessRange *dr128 = nullptr;
+    if (gr && n) {
+        sets.resize(n + G);
+        members.resize(2 * n);
         for (size_t u = 0; u < n; u++) {
             sets[u] = LoudnessSet{(uint32_t)u, 1, (uint32_t)u, (uint32_t)u};
             members[u] = (uint32_t)u;
@@ -1030,43 +996,26 @@ int measure_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uin
         for (size_t g = 0; g < G; g++)
             sets[n + g] = LoudnessSet{(uint32_t)n + gr->plan.first[g], gr->plan.first[g + 1] - gr->plan.first[g],
                                       (uint32_t)g, (uint32_t)(n + g)};
-        LoudnessSet *dsets = nullptr;
-        uint32_t *dmem = nullptr;
-        LoudnessGroupResult *dgres = nullptr;
-        LoudnessRange *dr128 = nullptr;
-        double *dsw = nullptr, *dmm = nullptr;
+        const LoudnessSet *dsets = ds.upload(sets);
+        const uint32_t *dmem = ds.upload(members);
+        dgres = ds.alloc<LoudnessGroupResult>(G);
+        dr128 = ds.alloc<LoudnessRange>(n + G);
+        double *dsw = ds.alloc<double>(tiles), *dmm = ds.alloc<double>(n);
+        if (ds.ok())
+            ds.err = launch_loudness_groups(dr, du, dsets + n, (uint32_t)G, dmem, dz, dres, dgres, ds.stream);
+        if (ds.ok())
+            ds.err = launch_loudness_range(dr, du, (uint32_t)n, du, dsets, (uint32_t)(n + G), dmem, dz, dsw, dmm, dr128,
+                                           ds.stream);
+    }
+    res->assign(n, LoudnessResult{});
+    ds.read_back(res, dres, n);
+    if (gr && n) {
         gr->gres.assign(G, LoudnessGroupResult{});
         gr->r128.assign(n + G, LoudnessRange{});
-        if ((e = scratch.alloc(&dsets, n + G)) == hipSuccess && (e = scratch.alloc(&dmem, 2 * n)) == hipSuccess &&
-            (e = scratch.alloc(&dgres, G)) == hipSuccess && (e = scratch.alloc(&dr128, n + G)) == hipSuccess &&
-            (e = scratch.alloc(&dsw, std::max<uint64_t>(tiles, 1))) == hipSuccess &&
-            (e = scratch.alloc(&dmm, n)) == hipSuccess &&
-            (e = hipMemcpyAsync(dsets, sets.data(), sizeof(LoudnessSet) * (n + G), hipMemcpyHostToDevice, s)) ==
-                hipSuccess &&
-            (e = hipMemcpyAsync(dmem, members.data(), sizeof(uint32_t) * 2 * n, hipMemcpyHostToDevice, s)) ==
-                hipSuccess &&
-            (e = launch_loudness_groups(dr, du, dsets + n, (uint32_t)G, dmem, dz, dres, dgres, s)) == hipSuccess &&
-            (e = launch_loudness_range(dr, du, (uint32_t)n, du, dsets, (uint32_t)(n + G), dmem, dz, dsw, dmm, dr128,
-                                       s)) == hipSuccess &&
-            (e = hipMemcpyAsync(gr->gres.data(), dgres, sizeof(LoudnessGroupResult) * G, hipMemcpyDeviceToHost, s)) ==
-                hipSuccess)
-            e = hipMemcpyAsync(gr->r128.data(), dr128, sizeof(LoudnessRange) * (n + G), hipMemcpyDeviceToHost, s);
-        // (the sources of the asynchronous copies live to the wait below)
-        if (e == hipSuccess && n)
-            e = hipMemcpyAsync(out.data(), dres, sizeof(LoudnessResult) * n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(s);
-        if (e != hipSuccess)
-            return hip_fail(e, what);
-        return JB_OK;
+        ds.read_back(&gr->gres, dgres, G);
+        ds.read_back(&gr->r128, dr128, n + G);
     }
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(out.data(), dres, sizeof(LoudnessResult) * n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);
-    if (e != hipSuccess)
-        return hip_fail(e, what);
-    return JB_OK;
+    return ds.status();
 }
 
 } // namespace jb

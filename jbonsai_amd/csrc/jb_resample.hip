@@ -364,89 +364,40 @@ int jb_resample_filter(uint32_t in_hz, uint32_t out_hz, uint32_t *L, uint32_t *M
 int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t in_hz, uint32_t out_hz,
                           int32_t device, double **out, size_t *n_out)
 {
-    if ((n && (!in || !n_in || !out || !n_out)))
-        return JB_ERR_INVALID;
-    for (size_t u = 0; u < n; u++) {
-        out[u] = nullptr;
-        n_out[u] = 0;
-    }
+    int rc = pcm_check((const void *const *)in, n_in, n, out && n_out, (void **)out, n_out);
+    if (rc)
+        return rc;
     if (in_hz == 0 || out_hz == 0) {
         set_error("resample: a rate of 0 Hz");
         return JB_ERR_INVALID;
     }
-    int dev = device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) {
-        set_error("no HIP device");
-        return JB_ERR_DEVICE;
-    }
-    // everything below (stream, allocations, launch) on `dev`, where the table lives; the caller keeps its device
-    DeviceScratch scratch;
-    if (hipError_t se = scratch.enter(dev); se != hipSuccess)
-        return hip_fail(se, "hipSetDevice");
+    // everything below (stream, allocations, launch) on the device where the table lives; the caller keeps its own
+    DeviceScratch ds;
     ResampleTable t{};
-    int rc = resample_table(dev, in_hz, out_hz, &t);
-    if (rc)
+    if ((rc = ds.open(device, "jb_resample_pcm_batch")) || (rc = resample_table(ds.device, in_hz, out_hz, &t)))
         return rc;
-    std::vector<uint64_t> ioff(n + 1, 0), ooff(n + 1, 0);
+    std::vector<uint64_t> ioff;
+    const double *dx = ds.pack(in, n_in, n, &ioff);
+    std::vector<PcmShare> shares(n);
+    uint64_t total = 0;
     for (size_t u = 0; u < n; u++) {
-        if (n_in[u] && !in[u])
-            return JB_ERR_INVALID;
-        ioff[u + 1] = ioff[u] + n_in[u];
-        ooff[u + 1] = ooff[u] + resample_out_len(n_in[u], t.L, t.M);
+        shares[u] = {total, resample_out_len(n_in[u], t.L, t.M)};
+        total += shares[u].n;
     }
-    for (size_t u = 0; u < n; u++) {
-        const size_t no = (size_t)(ooff[u + 1] - ooff[u]);
-        out[u] = (double *)malloc(std::max<size_t>(no, 1) * sizeof(double));
-        if (!out[u]) {
-            for (size_t v = 0; v <= u; v++) {
-                free(out[v]);
-                out[v] = nullptr;
-            }
-            set_error("out of host memory");
-            return JB_ERR_INVALID;
-        }
-        n_out[u] = no;
-    }
-    double *dx = nullptr, *dy = nullptr;
-    ResampleTable *dt = nullptr;
-    ResampleTile *dtl = nullptr;
+    double *dy = ds.alloc<double>(total);
     std::vector<ResampleTile> tiles;
-    hipError_t e = scratch.open_stream();
-    hipStream_t st = scratch.stream;
-    if (e == hipSuccess)
-        e = scratch.alloc(&dx, std::max<uint64_t>(ioff[n], 1));
-    if (e == hipSuccess)
-        e = scratch.alloc(&dy, std::max<uint64_t>(ooff[n], 1));
-    for (size_t u = 0; u < n && e == hipSuccess; u++) {
-        if (n_in[u])
-            e = hipMemcpyAsync(dx + ioff[u], in[u], sizeof(double) * n_in[u], hipMemcpyHostToDevice, st);
-        resample_tiles(t, 0, dx + ioff[u], n_in[u], dy + ooff[u], ooff[u + 1] - ooff[u], tiles);
-    }
-    if (e == hipSuccess)
-        e = scratch.alloc(&dt, 1);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(dt, &t, sizeof t, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && !tiles.empty()) {
-        e = scratch.alloc(&dtl, tiles.size());
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(dtl, tiles.data(), sizeof(ResampleTile) * tiles.size(), hipMemcpyHostToDevice, st);
-    }
-    if (e == hipSuccess)
-        e = launch_resample(dt, dtl, (uint32_t)tiles.size(), false, t.lds_bytes, st);
-    for (size_t u = 0; u < n && e == hipSuccess; u++)
-        if (n_out[u])
-            e = hipMemcpyAsync(out[u], dy + ooff[u], sizeof(double) * n_out[u], hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        for (size_t u = 0; u < n; u++) {
-            free(out[u]);
-            out[u] = nullptr;
-            n_out[u] = 0;
-        }
-        return hip_fail(e, "jb_resample_pcm_batch");
-    }
-    return JB_OK;
+    for (size_t u = 0; u < n; u++)
+        resample_tiles(t, 0, dx + ioff[u], n_in[u], dy + shares[u].off, shares[u].n, tiles);
+    const std::vector<ResampleTable> tables(1, t);
+    const ResampleTable *dt = ds.upload(tables);
+    const ResampleTile *dtl = ds.upload(tiles);
+    if (ds.ok())
+        ds.err = launch_resample(dt, dtl, (uint32_t)tiles.size(), false, t.lds_bytes, ds.stream);
+    std::vector<double> host;
+    ds.read_back(&host, dy, total);
+    if ((rc = ds.status()))
+        return rc;
+    return hand_out(host.data(), sizeof(double), shares, (void **)out, n_out);
 }
 
 } // extern "C"

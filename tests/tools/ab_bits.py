@@ -4,9 +4,11 @@ kernel), and 8 x the 25,546-frame synthetic utterance + 3 distinct ones (lane-tr
 LDS-staged band solve, split excitation: the kernels of BASELINE config 2), f64 and the 16-bit sink.  Then the
 stages behind the vocoder: all eight rows of the output routing table (f64 / 16-bit sink x output
 rate x loudness target; FLAC on the 16-bit rows) on three ragged utterances, with the default geometry and with the
-redo-heavy one of the redo tests, and the three entries on caller-held PCM on seeded input.
+redo-heavy one of the redo tests, and the entries on caller-held PCM on seeded input: three on long inputs, then
+every one of their ten bodies on utterances of 0, 1, 1,025 and 5,000 samples.
 
     python tests/tools/ab_bits.py               every hash (what tools/ab_bits.sh compares between two libraries)
+    python tests/tools/ab_bits.py --seams       the hashes of the entries on caller-held PCM alone
     python tests/tools/ab_bits.py --redo-time N  no hash: run() + sync() of the redo-heavy rows, wall ms, N times each"""
 import hashlib
 import os
@@ -30,6 +32,31 @@ def digest(arrs):
     for a in arrs:
         h.update(a if isinstance(a, bytes) else np.ascontiguousarray(a).tobytes())
     return h.hexdigest()[:16]
+
+
+def pcm_seams():
+    """Every body behind the jb_*_pcm_batch entries (f64 and 16-bit instances) on seeded utterances."""
+    rng = np.random.default_rng(1025)
+    pcm = [9000.0 * rng.standard_normal(n) for n in (0, 1, 1025, 5000)]
+    pcm16 = [np.clip(x, -32768, 32767).astype(np.int16) for x in pcm]
+    print("seam resample", digest(J.resample(pcm, 48000, 16000)), digest(J.resample(pcm, 48000, 48000)))
+    print("seam loudness", digest([np.array(J.loudness(pcm, 48000))]), "true_peak",
+          digest([np.array(J.true_peak(pcm, 48000))]), "groups",
+          digest([repr(J.loudness_groups(pcm, 48000, [1, 1, None, 1], mode=1, target=-23.0, ceiling=-1.0)).encode()]))
+    print("seam flac", digest(J.flac_encode(pcm16, 48000)), "meta",
+          digest(J.flac_encode(pcm16, 22050, block_size=1152, md5=True, seek_interval_ms=10)), "md5",
+          digest(J.flac_md5(pcm16)))
+    print("seam format",
+          *[digest(J.format_pcm(pcm, f, dither=f == "s24", seed=7)) for f in ("alaw", "f32", "s16", "s24", "ulaw")])
+    print("seam adpcm", digest(J.adpcm_encode(pcm, [8000, 16000, 22050, 48000])))
+    req = [(0, 3, 0, 0, 0), (0, 0, 5, 0, 0), (None, 0, 0, 64, 64), (0, 7, 7, 100, 100)]
+    print("seam join", digest(J.join_pcm(pcm, req)), "i16", digest(J.join_pcm(pcm16, req)))
+    filt = [J.highpass(120.0), None, J.telephone_band(), J.highpass(80.0) + J.peaking(2500.0, 3.0)]
+    print("seam filter", digest(J.filter_pcm(pcm, filt, [48000, 48000, 8000, 16000])), "i16",
+          digest(J.filter_pcm(pcm, filt, [48000, 48000, 8000, 16000], i16=True)))
+    for i16 in (False, True):
+        y, rep = J.limiter_pcm(pcm, [48000, 16000, 48000, 22050], 2.0, -1.0, [0, 0, 1, 1], i16=i16)
+        print("seam limiter", "i16" if i16 else "f64", digest(y), digest([repr(rep).encode()]))
 
 
 def output_rows(vi, utts, geometry, label):
@@ -88,12 +115,16 @@ def output_stages():
     pcm16 = [np.clip(x, -32768, 32767).astype(np.int16) for x in pcm]
     print("flac_encode_pcm_batch", digest(J.flac_encode(pcm16, 48000)),
           digest(J.flac_encode(pcm16, 22050, block_size=1152, max_lpc_order=12)))
+    pcm_seams()
 
 
 from jbonsai_amd import synth  # noqa: E402
 
 if redo_time:
     output_stages()
+    sys.exit(0)
+if "--seams" in sys.argv:
+    pcm_seams()
     sys.exit(0)
 
 v = O.Voice(VOICE)
