@@ -1277,10 +1277,11 @@ __global__ __launch_bounds__(256) void k_vocoder(BatchDev bd, VocDev vd, const V
         const int rowstart = lane & ~15, segstart = s * kGroups;
         const bool straddle = active && rowstart > 0 && segstart < rowstart;
         kc.cb = straddle ? ipow(kappa, lane - rowstart + 1) : 0.0;
-        ks.c1 = kc.c1 != 0.0 ? 1.0 : 0.0;
-        ks.c2 = kc.c2 != 0.0 ? 1.0 : 0.0;
-        ks.c4 = kc.c4 != 0.0 ? 1.0 : 0.0;
-        ks.c8 = kc.c8 != 0.0 ? 1.0 : 0.0;
+        // (the unit scan from the lane roles, not from kc != 0: at alpha = 0 kappa is 0 and the sums still run)
+        ks.c1 = ok(1) ? 1.0 : 0.0;
+        ks.c2 = ok(2) ? 1.0 : 0.0;
+        ks.c4 = ok(4) ? 1.0 : 0.0;
+        ks.c8 = ok(8) ? 1.0 : 0.0;
         ks.cb = straddle ? 1.0 : 0.0;
     }
     const double nh = (active && !head) ? 1.0 : 0.0;           // takes carry from lane-1
@@ -1610,10 +1611,11 @@ __global__ __launch_bounds__(128 * ITEMS) void k_vocoder_pair(BatchDev bd, VocDe
         const int rowstart = lane & ~15, segstart = s * kGroups;
         const bool straddle = active && rowstart > 0 && segstart < rowstart;
         kc.cb = straddle ? ipow(kappa, lane - rowstart + 1) : 0.0;
-        ks.c1 = kc.c1 != 0.0 ? 1.0 : 0.0;
-        ks.c2 = kc.c2 != 0.0 ? 1.0 : 0.0;
-        ks.c4 = kc.c4 != 0.0 ? 1.0 : 0.0;
-        ks.c8 = kc.c8 != 0.0 ? 1.0 : 0.0;
+        // (the unit scan from the lane roles, not from kc != 0: at alpha = 0 kappa is 0 and the sums still run)
+        ks.c1 = ok(1) ? 1.0 : 0.0;
+        ks.c2 = ok(2) ? 1.0 : 0.0;
+        ks.c4 = ok(4) ? 1.0 : 0.0;
+        ks.c8 = ok(8) ? 1.0 : 0.0;
         ks.cb = straddle ? 1.0 : 0.0;
     }
     const double nh = (active && !head) ? 1.0 : 0.0;  // takes carry from lane-1
