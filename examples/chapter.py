@@ -3,6 +3,7 @@
     python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
                                [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
+                               [--fbank OUT.npy]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
 batch and joined on the GPU (Engine.synthesize_programme) in front of the encoder, so a .flac output is one stream whose
@@ -11,7 +12,10 @@ written as a 16-bit WAV file.  With --loudness the chapter gets ONE gain (per-re
 keep their relative levels.  With --highpass a rumble and DC high-pass at that corner runs on the GPU in front of the
 loudness measurement and the encoder (Engine.set_filter).  With --limiter (and --loudness) the chapter's gain may put its
 highest peak that many dB over the ceiling and a look-ahead limiter holds the ceiling on the GPU (Engine.set_limiter), so
-one loud peak no longer holds the whole chapter under its target.  The cue list -- each sentence's first sample and time within the chapter -- is printed.
+one loud peak no longer holds the whole chapter under its target.  With --fbank the chapter's log-mel filterbank frames
+(25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are computed on the GPU from the joined programme, frames across
+the pauses and the seams included, and saved as a .npy file INSTEAD of the audio: a request has one sink, so no audio
+file is written (run again without --fbank for it; the cue list is the same).  The cue list -- each sentence's first sample and time within the chapter -- is printed.
 Needs an MI355X: the library has no CPU path.
 """
 import argparse
@@ -35,6 +39,7 @@ ap.add_argument("--limiter", type=float, default=None, metavar="DB",
                 help="look-ahead limiter: the gain may put the highest peak this far over the ceiling (with --loudness)")
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner (50 to 80 Hz removes rumble and DC)")
+ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="the chapter's log-mel filterbank frames from the GPU, instead of the audio")
 args = ap.parse_args()
 
 sentences = []
@@ -55,7 +60,13 @@ if args.loudness is not None:
     engine.set_loudness_scope(J.LOUDNESS_PER_REQUEST)
 hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
 join = dict(lead_ms=args.lead_ms, gap_ms=args.gap_ms, trail_ms=args.trail_ms, fade_ms=args.fade_ms)
-if args.out.endswith(".flac"):
+if args.fbank:
+    import numpy as np
+
+    feats, starts = engine.synthesize_programme(sentences, sink="fbank", **join)
+    np.save(args.fbank, feats)
+    print(f"wrote {args.fbank}: {feats.shape[0]} frames of {feats.shape[1]} log-mel values at {hz} Hz")
+elif args.out.endswith(".flac"):
     data, starts = engine.synthesize_programme(sentences, sink="flac", md5=True, seek_interval_ms=1000, **join)
     with open(args.out, "wb") as f:
         f.write(data)

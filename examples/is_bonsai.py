@@ -2,7 +2,7 @@
 
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak] [--limiter DB]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
-                                 [--flac] [--highpass HZ]
+                                 [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
@@ -20,6 +20,8 @@ With --flac the 16-bit audio is encoded as a FLAC stream on the GPU, with the MD
 SEEKTABLE with a point about every second, and written as it is.
 With --highpass the audio passes a second-order high-pass at that corner on the GPU (Engine.set_filter), behind the
 output rate and in front of the loudness measurement and every encoder above.
+With --fbank the sentence's log-mel filterbank frames (25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are
+computed on the GPU from the final PCM, at --rate if given, and saved as a .npy file; no WAV file is written.
 With --limiter (and --loudness) the gain may put the highest peak that many dB over the ceiling and a look-ahead limiter
 on the GPU holds the ceiling (Engine.set_limiter): the target is reached where the peak alone stood in the way.
 """
@@ -44,7 +46,8 @@ ap.add_argument("--format", choices=["f32", "s16", "s24", "ulaw", "alaw"], defau
                 help="sample format of the WAV file, converted on the GPU")
 ap.add_argument("--dither", action="store_true", help="TPDF dither (with --format s16 or s24)")
 ap.add_argument("--adpcm", action="store_true", help="IMA ADPCM (4-bit) WAV file, encoded on the GPU")
-ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm)")
+ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm or --fbank)")
+ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="log-mel filterbank frames, computed on the GPU")
 ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
 ap.add_argument("--limiter", type=float, default=None, metavar="DB",
@@ -77,6 +80,16 @@ if args.programme:
     print("each sentence alone: " + ", ".join(f"{v:.2f} LUFS" for v in rep["lufs"]))
     J.write_wav(out, np.concatenate(parts), hz)
     print(f"wrote {out}")
+    sys.exit(0)
+if args.fbank:
+    import numpy as np
+
+    if args.rate:
+        engine.condition.set_output_sampling_frequency(args.rate)
+    feats = engine.synthesize_fbank(SAMPLE_SENTENCE_2)
+    np.save(args.fbank, feats)
+    hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
+    print(f"wrote {args.fbank}: {feats.shape[0]} frames of {feats.shape[1]} log-mel values at {hz} Hz")
     sys.exit(0)
 if args.adpcm:
     if args.rate:

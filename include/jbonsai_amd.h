@@ -141,6 +141,25 @@ typedef struct jb_adpcm_opts {
     uint32_t block_align;
     uint32_t reserved[3];
 } jb_adpcm_opts;
+/* New.  Filterbank options (jb_batch_set_fbank, jb_fbank_pcm_batch, jb_fbank_host, jb_synthesize*_fbank; see "Filterbank features" below).
+ * win_us, hop_us: window and hop in microseconds (25000 and 10000 are the usual values); n_fft 0 = the smallest power
+ * of two that holds the window; f_max_hz 0 = half the rate; log_floor 0 = 2^-52; reserved 0.  Anything outside the
+ * limits of that section: JB_ERR_INVALID, naming the field, before any device is touched. */
+#define JB_FBANK_HANN 0u    /* periodic: 0.5 - 0.5 cos(2 pi j / wl) */
+#define JB_FBANK_HAMMING 1u /* symmetric: 0.54 - 0.46 cos(2 pi j / (wl - 1)) */
+#define JB_FBANK_CENTER 1u  /* frame t is centred on sample t hop; samples outside the unit read as 0 */
+#define JB_FBANK_LINEAR 2u  /* the filters' energies themselves, not their logarithms */
+#define JB_FBANK_UNIT 4u    /* samples scaled by 2^-15 (full scale 1.0) instead of the 16-bit scale */
+#define JB_FBANK_F64 8u     /* f64 elements instead of f32 */
+typedef struct jb_fbank_opts {
+    uint32_t win_us, hop_us;
+    uint32_t n_fft, n_mels;
+    double f_min_hz, f_max_hz;
+    double log_floor;
+    uint32_t window; /* JB_FBANK_HANN, JB_FBANK_HAMMING */
+    uint32_t flags;  /* JB_FBANK_CENTER | _LINEAR | _UNIT | _F64 */
+    uint32_t reserved[4];
+} jb_fbank_opts;
 /* The join request of one utterance (see "Join" below): the programme it belongs to, the zero samples before and
  * after it and the lengths of its edge fades.  reserved must be 0. */
 #define JB_JOIN_NONE 0xffffffffu
@@ -516,6 +535,25 @@ int jb_batch_adpcm_block_align(jb_batch *b, size_t utt, uint32_t *block_align);
 int jb_batch_read_adpcm(jb_batch *b, size_t utt, uint8_t *dst, size_t cap);
 /* Every utterance: dst[u] must hold jb_batch_adpcm_size(b, u) bytes (one device-to-host copy for the batch). */
 int jb_batch_read_adpcm_all(jb_batch *b, uint8_t *const *dst);
+/* New (none: no reference counterpart).  Filterbank features (see "Filterbank features" below): the run also turns
+ * each utterance's final f64 PCM -- what jb_batch_read_pcm hands out, after the output rate, the filter and the
+ * loudness target; behind a join each programme -- into [T][n_mels] log-mel frames, on the device.  The options are
+ * checked at every utterance's output rate, here and again by jb_batch_set_output_rate (JB_ERR_INVALID naming the
+ * field).  Only before the batch's first run ("... is set before the batch's first run"), on a batch that is neither
+ * JB_BATCH_PCM_I16 nor JB_BATCH_MLPG_ONLY (JB_ERR_UNSUPPORTED).  opts == NULL withdraws the request.  Independent of
+ * the sample format and IMA ADPCM; the PCM read entries keep working and their bytes do not change.  Without a call
+ * nothing runs and nothing is allocated. */
+int jb_batch_set_fbank(jb_batch *b, const jb_fbank_opts *opts);
+/* Frames, filters and rate of unit `unit` (an utterance; behind a join a programme), known once the request is made;
+ * any out pointer may be NULL.  No request or no such unit: JB_ERR_INVALID. */
+int jb_batch_fbank_shape(jb_batch *b, size_t unit, size_t *T, uint32_t *n_mels, uint32_t *hz);
+/* Its bytes: T x n_mels x 4 (8 with JB_FBANK_F64). */
+int jb_batch_fbank_size(jb_batch *b, size_t unit, size_t *n_bytes);
+/* The frames of unit `unit` into dst, row-major; waits for the run like the read entries; cap below
+ * jb_batch_fbank_size: JB_ERR_BUFFER. */
+int jb_batch_read_fbank(jb_batch *b, size_t unit, uint8_t *dst, size_t cap);
+/* Every unit: dst[u] must hold jb_batch_fbank_size(b, u) bytes (one device-to-host copy for the batch). */
+int jb_batch_read_fbank_all(jb_batch *b, uint8_t *const *dst);
 /* New (none: no reference counterpart).  Join (see "Join" below): the run also gathers the utterances' final PCM --
  * what the PCM read entries hand out, after the output rate and the loudness target -- into programmes, on the
  * device: each programme its members in ascending utterance index, each between its pads and under its fades.  FLAC,
@@ -821,6 +859,57 @@ int jb_adpcm_decode_host(const uint8_t *bytes, size_t n_bytes, uint32_t A, size_
 int jb_adpcm_encode_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
                               const jb_adpcm_opts *opts, int32_t device, uint8_t **out, size_t *n_bytes);
 void jb_adpcm_free(uint8_t *p);
+
+/* ---- Filterbank features (new: the reference hands out samples only; none of these entries has a counterpart) ---------
+ * A bulk consumer (ASR corpora, distillation, alignment, QA) takes log-mel frames, not samples: n_mels numbers per hop.
+ * The stage reads the final f64 PCM on the device and hands out the frames; a programme (jb_batch_set_join) is
+ * analysed whole.
+ * - Geometry, per unit at its own output rate hz, in 64-bit integers: wl = (hz win_us + 500000) / 1000000, hop the
+ *   same from hop_us.  Limits: 2 <= wl <= n_fft, n_fft a power of two in 64..4096 (0: the smallest one >= wl, which
+ *   must lie in that range), hop >= 1, 1 <= n_mels <= 128, 0 <= f_min < f_max <= hz / 2.
+ * - Frames: without JB_FBANK_CENTER T = n >= wl ? 1 + (n - wl) / hop : 0 and frame t is samples [t hop, t hop + wl);
+ *   with it T = ceil(n / hop), frame t starts at t hop - wl / 2 (integer division) and samples outside [0, n) read as
+ *   0: zero padding, not reflection.
+ * - Samples are in 16-bit scale, as jb_batch_read_pcm hands them out; JB_FBANK_UNIT multiplies each by 2^-15 (exact).
+ * - Window: JB_FBANK_HANN is periodic, 0.5 - 0.5 cos(2 pi j / wl); JB_FBANK_HAMMING symmetric, 0.54 - 0.46 cos(2 pi j /
+ *   (wl - 1)); computed on the host in long double and rounded to f64 once (jb_fbank_window).
+ * - Spectrum: X_k = sum_j w_j x_j e^{-2 pi i j k / n_fft}, k = 0..n_fft / 2; P_k = re^2 + im^2.  f64 throughout; the
+ *   twiddles come from a host table (long double, rounded once), never from the device's sincos.
+ * - Filterbank: mel(f) = 1127 ln(1 + f / 700) (the HTK form); n_mels + 2 edges equally spaced in mel from mel(f_min) to
+ *   mel(f_max): edge i = lo + (hi - lo) i / (n_mels + 1); W[m][k] = max(0, min((mu_k - l) / (c - l), (r - mu_k) /
+ *   (r - c))) with mu_k = mel(k hz / n_fft) and l, c, r edges m, m + 1, m + 2; no area normalisation; a filter that
+ *   covers no bin is allowed, its energy is 0.  Built on the host in long double, rounded once (jb_fbank_filterbank).
+ *   E_m = sum_k W[m][k] P_k, summed in ascending k over the filter's support.
+ * - Output: element [t][m], row-major per unit, is E_m under JB_FBANK_LINEAR, else ln(max(E_m, log_floor)); f32 (one
+ *   round-to-nearest from the f64 value) unless JB_FBANK_F64.  A unit starts on a 16-byte boundary of the slab.
+ * - Determinism: a frame's values depend on its own wl samples, hz and the options only; the order of every operation
+ *   is fixed per (n_fft, wl, n_mels).  Hence the seam (jb_fbank_pcm_batch), the batch path, redo rounds and any batch
+ *   give the same bits, and JB_BATCH_INVARIANT output stays invariant.  The host form (jb_fbank_host) follows the same
+ *   rule to the precision of f64 arithmetic; bit equality with the device is not claimed (the logarithm is each
+ *   side's own).
+ * - Cost on 256 x 128 s at 25 / 10 ms and 80 filters (profiles/r20_fbank.txt): 0.667 bytes per sample in f32; the
+ *   kernel takes 43.7 ms of device time at 48 kHz (3.27 million frames of 2048 points) and 11.4 ms at 16 kHz; run + read
+ *   of everything 430 ms (the f64 samples: 353 ms): the read is one pageable copy.  Against the long double model the
+ *   device's error is 1.00 to 1.25 times (3.88 with one filter alone) that of a float64 rfft of the same frames.
+ * Not covered: the Slaney mel scale, reflection padding, pre-emphasis, dither and per-frame DC removal (no Kaldi or
+ * Whisper bit-compatibility is claimed); magnitude instead of power, deltas, MFCC; the generator, the _multi entries
+ * and jb_gather_pcm; 16-bit batches; per-utterance options within one batch;
+ * reading through the pinned ring (the read is one pageable copy). */
+/* wl, hop, n_fft of the options at hz and T and bytes of n samples; any out pointer may be NULL. */
+int jb_fbank_geometry(uint32_t hz, const jb_fbank_opts *opts, size_t n, uint32_t *wl, uint32_t *hop, uint32_t *n_fft,
+                      size_t *T, size_t *n_bytes);
+/* The window (wl doubles) and the filterbank (dense [n_mels][n_fft / 2 + 1]) the options give at hz; cap (in doubles)
+ * below that: JB_ERR_BUFFER. */
+int jb_fbank_window(uint32_t hz, const jb_fbank_opts *opts, double *w, size_t cap);
+int jb_fbank_filterbank(uint32_t hz, const jb_fbank_opts *opts, double *W, size_t cap);
+/* The rule in plain C++ on the host; no GPU is touched.  out must hold the geometry's bytes (cap below that:
+ * JB_ERR_BUFFER). */
+int jb_fbank_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *opts, uint8_t *out, size_t cap);
+/* The stage on PCM the caller holds (jb_format_pcm_batch's twin): out[u] = the frames of in[u] (n_in[u] f64 samples at
+ * hz[u]), n_bytes[u] bytes, library-owned (jb_fbank_free each), on `device` (-1 = current). */
+int jb_fbank_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                       const jb_fbank_opts *opts, int32_t device, uint8_t **out, size_t *n_bytes);
+void jb_fbank_free(uint8_t *p);
 
 /* ---- Join (new: the reference synthesises one utterance into one buffer; none of these entries has a counterpart) ------
  * A programme is "sentence, pause, sentence" as ONE stream: FLAC frame numbers, STREAMINFO, MD5 and SEEKTABLE, ADPCM
@@ -1271,6 +1360,18 @@ int jb_synthesize_batch_adpcm(const jb_engine *e, const char *const *label_lines
 int jb_synthesize_batch_each_adpcm(const jb_engine *const *engines, const char *const *label_lines,
                                    const size_t *line_off, size_t n_utts, int32_t device, const jb_adpcm_opts *opts,
                                    uint8_t **bytes, size_t *n_bytes, size_t *n_samples);
+/* New (none).  Filterbank forms of jb_synthesize (one utterance, current device), jb_synthesize_batch and
+ * jb_synthesize_batch_each (see "Filterbank features"): bytes[u] = the [n_frames[u]][opts->n_mels] frames of utterance
+ * u's final f64 PCM at its engine's output rate, n_bytes[u] bytes, library-owned (jb_fbank_free each); n_frames (may
+ * be NULL).  Options that some utterance's rate refuses: JB_ERR_INVALID naming the field. */
+int jb_synthesize_fbank(const jb_engine *e, const char *const *label_lines, size_t n_lines, const jb_fbank_opts *opts,
+                        uint8_t **bytes, size_t *n_bytes, size_t *n_frames);
+int jb_synthesize_batch_fbank(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                              size_t n_utts, int32_t device, const jb_fbank_opts *opts, uint8_t **bytes,
+                              size_t *n_bytes, size_t *n_frames);
+int jb_synthesize_batch_each_fbank(const jb_engine *const *engines, const char *const *label_lines,
+                                   const size_t *line_off, size_t n_utts, int32_t device, const jb_fbank_opts *opts,
+                                   uint8_t **bytes, size_t *n_bytes, size_t *n_frames);
 /* The same two over a device list: the utterances are split by LPT on their label counts (the frame
  * counts are known only after the front half), one host thread per device runs jb_synthesize_batch's
  * path on its share (front half on that thread's workers, GPU work on that device). */
@@ -1375,6 +1476,11 @@ int jb_synthesize_programme_formatted(const jb_engine *e, const char *const *lab
 int jb_synthesize_programme_adpcm(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
                                   size_t n_utts, int32_t device, const jb_adpcm_opts *opts, const jb_join_opts *join,
                                   uint8_t **bytes, size_t *n_bytes, size_t *n_samples, uint64_t *starts);
+/* New (none).  The programme's filterbank frames: the f64 programme (what jb_synthesize_programme returns) analysed
+ * whole; bytes[0], n_bytes[0], n_frames (may be NULL) as jb_synthesize_fbank's. */
+int jb_synthesize_programme_fbank(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_fbank_opts *opts, const jb_join_opts *join,
+                                  uint8_t **bytes, size_t *n_bytes, size_t *n_frames, uint64_t *starts);
 
 /* ------------------------------------------------------------------------ */
 const char *jb_last_error(void);
@@ -1427,6 +1533,10 @@ JB_LAYOUT_ASSERT(sizeof(jb_flac_meta) == 16 && offsetof(jb_flac_meta, seek_inter
 JB_LAYOUT_ASSERT(sizeof(jb_format_opts) == 16 && offsetof(jb_format_opts, dither) == 4 &&
                      offsetof(jb_format_opts, seed) == 8, "jb_format_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_adpcm_opts) == 16 && offsetof(jb_adpcm_opts, reserved) == 4, "jb_adpcm_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_fbank_opts) == 64 && offsetof(jb_fbank_opts, n_fft) == 8 &&
+                     offsetof(jb_fbank_opts, f_min_hz) == 16 && offsetof(jb_fbank_opts, log_floor) == 32 &&
+                     offsetof(jb_fbank_opts, window) == 40 && offsetof(jb_fbank_opts, reserved) == 48,
+                 "jb_fbank_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_join_utt) == 32 && offsetof(jb_join_utt, fade_out) == 8 &&
                      offsetof(jb_join_utt, pad_before) == 16 && offsetof(jb_join_utt, pad_after) == 24,
                  "jb_join_utt");

@@ -14,13 +14,15 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    Filter, FilterSection, Biquad, filter_design, filter_sos, filter_pcm, filter_pcm_host, highpass,
                    lowpass, peaking, lowshelf, highshelf, notch, raw_filter, telephone_band, no_filter,
                    LimiterOpts, LimiterReport, LIMITER_EXACT, LIMITER_OFF, limiter, no_limiter, limiter_window,
-                   limiter_host, limiter_pcm)
+                   limiter_host, limiter_pcm,
+                   FbankOpts, FBANK_HANN, FBANK_HAMMING, FBANK_CENTER, FBANK_LINEAR, FBANK_UNIT, FBANK_F64, fbank,
+                   fbank_geometry, fbank_window, fbank_filterbank, fbank_host, fbank_pcm)
 from .batch import (Batch, IndexStreamStates, IndexUtterance, PdfSet, StreamInfo, StreamStates, TrackUtterance,  # noqa: F401
                     Utterance, VoiceInfo, generator_from_tracks, mlpg_batch, paramgen_vocode_batch, vocode_tracks_batch,
                     vocoder_synthesize_batch)
 
 from .engine import (Engine, SpeechGenerator, synthesize_batch_each, synthesize_batch_each_flac,  # noqa: F401,E402
-                     synthesize_batch_each_adpcm, synthesize_batch_each_formatted)
+                     synthesize_batch_each_adpcm, synthesize_batch_each_formatted, synthesize_batch_each_fbank)
 from . import comm  # noqa: F401,E402
 
 __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build", "lib", "write_wav", "Batch", "StreamInfo", "StreamStates",
@@ -35,4 +37,7 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "join_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",
            "filter_pcm_host", "highpass", "lowpass", "peaking", "lowshelf", "highshelf", "notch", "raw_filter",
            "telephone_band", "no_filter", "LimiterOpts", "LimiterReport", "LIMITER_EXACT", "LIMITER_OFF", "limiter",
-           "no_limiter", "limiter_window", "limiter_host", "limiter_pcm"]
+           "no_limiter", "limiter_window", "limiter_host", "limiter_pcm",
+           "FbankOpts", "FBANK_HANN", "FBANK_HAMMING", "FBANK_CENTER", "FBANK_LINEAR", "FBANK_UNIT", "FBANK_F64", "fbank",
+           "fbank_geometry", "fbank_window", "fbank_filterbank", "fbank_host", "fbank_pcm",
+           "synthesize_batch_each_fbank"]

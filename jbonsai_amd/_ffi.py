@@ -197,6 +197,41 @@ def adpcm_opts(block_align: int = 0):
     return o
 
 
+FBANK_HANN, FBANK_HAMMING = 0, 1
+FBANK_CENTER, FBANK_LINEAR, FBANK_UNIT, FBANK_F64 = 1, 2, 4, 8
+
+
+class FbankOpts(C.Structure):
+    """jb_fbank_opts: window and hop in microseconds, n_fft (0: by the window), the mel filters and their band, the
+    floor under the logarithm, the window (FBANK_HANN, FBANK_HAMMING) and FBANK_* flags."""
+    _fields_ = [("win_us", C.c_uint32), ("hop_us", C.c_uint32), ("n_fft", C.c_uint32), ("n_mels", C.c_uint32),
+                ("f_min_hz", C.c_double), ("f_max_hz", C.c_double), ("log_floor", C.c_double),
+                ("window", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+    @property
+    def dtype(self):
+        import numpy as np
+
+        return np.dtype(np.float64 if self.flags & FBANK_F64 else np.float32)
+
+
+def fbank(win_ms: float = 25, hop_ms: float = 10, n_mels: int = 80, n_fft: int = 0, f_min: float = 0.0,
+          f_max: float = 0.0, log_floor: float = 0.0, window="hann", center: bool = False, linear: bool = False,
+          unit: bool = False, f64: bool = False):
+    """FbankOpts: log-mel filterbank features of win_ms windows every hop_ms (n_fft 0: the smallest power of two that
+    holds the window; f_max 0: half the rate; log_floor 0: 2^-52); window "hann" (periodic) or "hamming" (symmetric);
+    center: frame t is centred on sample t * hop, zero-padded; linear: energies, not logarithms; unit: samples in
+    +-1.0 instead of the 16-bit scale; f64: float64 elements instead of float32."""
+    o = FbankOpts()
+    o.win_us, o.hop_us = int(round(win_ms * 1000)), int(round(hop_ms * 1000))
+    o.n_fft, o.n_mels = int(n_fft), int(n_mels)
+    o.f_min_hz, o.f_max_hz, o.log_floor = float(f_min), float(f_max), float(log_floor)
+    o.window = {"hann": FBANK_HANN, "hamming": FBANK_HAMMING}[window] if isinstance(window, str) else int(window)
+    o.flags = (FBANK_CENTER * bool(center) | FBANK_LINEAR * bool(linear) | FBANK_UNIT * bool(unit) |
+               FBANK_F64 * bool(f64))
+    return o
+
+
 JOIN_NONE = 0xFFFFFFFF
 
 
@@ -445,6 +480,10 @@ SYMBOLS = [
     "jb_batch_read_adpcm_all", "jb_adpcm_geometry", "jb_adpcm_encode_host", "jb_adpcm_encode_i16_host",
     "jb_adpcm_decode_host", "jb_adpcm_encode_pcm_batch", "jb_adpcm_free", "jb_write_wav_adpcm",
     "jb_synthesize_adpcm", "jb_synthesize_batch_adpcm", "jb_synthesize_batch_each_adpcm",
+    "jb_batch_set_fbank", "jb_batch_fbank_shape", "jb_batch_fbank_size", "jb_batch_read_fbank",
+    "jb_batch_read_fbank_all", "jb_fbank_geometry", "jb_fbank_window", "jb_fbank_filterbank", "jb_fbank_host",
+    "jb_fbank_pcm_batch", "jb_fbank_free", "jb_synthesize_fbank", "jb_synthesize_batch_fbank",
+    "jb_synthesize_batch_each_fbank", "jb_synthesize_programme_fbank",
     "jb_batch_set_loudness_groups", "jb_batch_loudness_group_of", "jb_batch_loudness_group",
     "jb_batch_set_loudness_report", "jb_batch_loudness_r128", "jb_loudness_groups_pcm_batch",
     "jb_loudness_gate_host", "jb_engine_set_loudness_scope", "jb_engine_get_loudness_scope",
@@ -672,6 +711,29 @@ def lib():
                                             C.POINTER(sz)]
     L.jb_adpcm_free.argtypes = [u8p]
     L.jb_adpcm_free.restype = None
+    fop = C.POINTER(FbankOpts)
+    L.jb_batch_set_fbank.argtypes = [vp, fop]
+    L.jb_batch_fbank_shape.argtypes = [vp, sz, C.POINTER(sz), u32p, u32p]
+    L.jb_batch_fbank_size.argtypes = [vp, sz, C.POINTER(sz)]
+    L.jb_batch_read_fbank.argtypes = [vp, sz, vp, sz]
+    L.jb_batch_read_fbank_all.argtypes = [vp, C.POINTER(vp)]
+    L.jb_fbank_geometry.argtypes = [C.c_uint32, fop, sz, u32p, u32p, u32p, C.POINTER(sz), C.POINTER(sz)]
+    L.jb_fbank_window.argtypes = [C.c_uint32, fop, vp, sz]
+    L.jb_fbank_filterbank.argtypes = [C.c_uint32, fop, vp, sz]
+    L.jb_fbank_host.argtypes = [vp, sz, C.c_uint32, fop, vp, sz]
+    L.jb_fbank_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, u32p, fop, C.c_int32, C.POINTER(u8p),
+                                     C.POINTER(sz)]
+    L.jb_fbank_free.argtypes = [u8p]
+    L.jb_fbank_free.restype = None
+    L.jb_synthesize_fbank.argtypes = [vp, C.POINTER(C.c_char_p), sz, fop, C.POINTER(u8p), C.POINTER(sz),
+                                      C.POINTER(sz)]
+    L.jb_synthesize_batch_fbank.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, fop,
+                                            C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_batch_each_fbank.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
+                                                 fop, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_programme_fbank.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, fop,
+                                                C.POINTER(JoinOpts), C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz),
+                                                C.POINTER(C.c_uint64)]
     L.jb_write_wav_adpcm.argtypes = [C.c_char_p, vp, sz, sz, C.c_uint32, C.c_uint32]
     L.jb_synthesize_adpcm.argtypes = [vp, C.POINTER(C.c_char_p), sz, aop, C.POINTER(u8p), C.POINTER(sz),
                                       C.POINTER(sz)]
@@ -1073,6 +1135,74 @@ def adpcm_encode(pcms, hz, block_align: int = 0, device: int = -1):
     opts = adpcm_opts(block_align)
     check(L.jb_adpcm_encode_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, bufs, ns))
     res = take_adpcm(L, bufs, ns, n)
+    return res[0] if single else res
+
+
+def fbank_geometry(hz: int, opts: FbankOpts, n: int = 0):
+    """jb_fbank_geometry: (wl, hop, n_fft, T, bytes) of n samples at hz."""
+    wl, hop, nfft, T, nby = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_size_t(), C.c_size_t()
+    check(lib().jb_fbank_geometry(hz, C.byref(opts), n, C.byref(wl), C.byref(hop), C.byref(nfft), C.byref(T),
+                                  C.byref(nby)))
+    return wl.value, hop.value, nfft.value, T.value, nby.value
+
+
+def fbank_window(hz: int, opts: FbankOpts):
+    """jb_fbank_window: the wl window values the options give at hz."""
+    import numpy as np
+
+    w = np.empty(fbank_geometry(hz, opts)[0], dtype=np.float64)
+    check(lib().jb_fbank_window(hz, C.byref(opts), w.ctypes.data, w.size))
+    return w
+
+
+def fbank_filterbank(hz: int, opts: FbankOpts):
+    """jb_fbank_filterbank: the mel weights [n_mels, n_fft / 2 + 1] the options give at hz."""
+    import numpy as np
+
+    W = np.empty((opts.n_mels, fbank_geometry(hz, opts)[2] // 2 + 1), dtype=np.float64)
+    check(lib().jb_fbank_filterbank(hz, C.byref(opts), W.ctypes.data, W.size))
+    return W
+
+
+def fbank_frames(data: bytes, opts: FbankOpts):
+    """The bytes of a unit's features as an ndarray [T, n_mels]."""
+    import numpy as np
+
+    return np.frombuffer(data, dtype=opts.dtype).reshape(-1, opts.n_mels).copy()
+
+
+def take_fbank(L, bufs, ns, n, opts: FbankOpts):
+    """ndarrays [T, n_mels] of n library-owned outputs, each released with jb_fbank_free."""
+    return [fbank_frames(d, opts) for d in _take(L.jb_fbank_free, bufs, ns, n)]
+
+
+def fbank_host(pcm, hz: int, opts: FbankOpts):
+    """jb_fbank_host: the features [T, n_mels] of float64 samples in 16-bit scale, in plain C++ on the host (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    nby = fbank_geometry(hz, opts, a.size)[4]
+    out = np.empty(max(1, nby), dtype=np.uint8)
+    check(lib().jb_fbank_host(a.ctypes.data, a.size, hz, C.byref(opts), out.ctypes.data, nby))
+    return fbank_frames(out[:nby].tobytes(), opts)
+
+
+def fbank_pcm(pcms, hz, opts: FbankOpts, device: int = -1):
+    """jb_fbank_pcm_batch: the features [T, n_mels] of each float64 array of `pcms` (or of one array) on the GPU; hz:
+    one rate, or one per array."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    L = lib()
+    u8p = C.POINTER(C.c_uint8)
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    check(L.jb_fbank_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, bufs, ns))
+    res = take_fbank(L, bufs, ns, n, opts)
     return res[0] if single else res
 
 

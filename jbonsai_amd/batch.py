@@ -286,6 +286,7 @@ class Batch:
             F.check(L.jb_batch_create(C.byref(vd), arr, len(utts), C.byref(opts), C.byref(h)))
         self._h = h
         self._keep = keep
+        self._fbank = None  # the filterbank request the batch holds (set_fbank)
 
     def __len__(self):
         return self._L.jb_batch_size(self._h)
@@ -558,6 +559,44 @@ class Batch:
         arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
         F.check(self._L.jb_batch_read_adpcm_all(self._h, arr))
         return [b[:n].tobytes() for b, n in zip(bufs, ns)]
+
+    def set_fbank(self, opts=None, **kw):
+        """jb_batch_set_fbank: the run also turns each utterance's (with a join: each programme's) final f64 PCM into
+        log-mel filterbank frames on the GPU.  opts: F.FbankOpts (J.fbank(...)), or the keywords of J.fbank; None
+        without keywords withdraws the request.  An f64 batch (neither pcm_i16 nor mlpg_only), before the first run
+        only."""
+        if opts is None and kw:
+            opts = F.fbank(**kw)
+        F.check(self._L.jb_batch_set_fbank(self._h, C.byref(opts) if opts is not None else None))
+        self._fbank = opts  # (a refused call leaves the batch's request, and this copy of it, as they were)
+
+    def fbank_shape(self, i):
+        """(T, n_mels, hz) of unit i's features (jb_batch_fbank_shape)."""
+        T, m, hz = C.c_size_t(), C.c_uint32(), C.c_uint32()
+        F.check(self._L.jb_batch_fbank_shape(self._h, i, C.byref(T), C.byref(m), C.byref(hz)))
+        return T.value, m.value, hz.value
+
+    def fbank_size(self, i) -> int:
+        n = C.c_size_t()
+        F.check(self._L.jb_batch_fbank_size(self._h, i, C.byref(n)))
+        return n.value
+
+    def read_fbank(self, i):
+        """Unit i's features, an ndarray [T, n_mels] (jb_batch_fbank_size + jb_batch_read_fbank)."""
+        n = self.fbank_size(i)
+        buf = np.empty(max(1, n), dtype=np.uint8)
+        F.check(self._L.jb_batch_read_fbank(self._h, i, buf.ctypes.data, n))
+        return F.fbank_frames(buf[:n].tobytes(), self._fbank)
+
+    def read_fbank_all(self):
+        """Every utterance's (with a join: every programme's) features through one device-to-host copy
+        (jb_batch_read_fbank_all)."""
+        B = self.num_outputs()
+        ns = [self.fbank_size(i) for i in range(B)]
+        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
+        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
+        F.check(self._L.jb_batch_read_fbank_all(self._h, arr))
+        return [F.fbank_frames(b[:n].tobytes(), self._fbank) for b, n in zip(bufs, ns)]
 
     def set_join(self, req):
         """jb_batch_set_join: one request per utterance -- F.JoinUtt entries, or (programme, pad_before, pad_after,

@@ -1691,6 +1691,8 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
         return rc;
     if (rq.sink == jb::SynthSink::Adpcm && (rc = out.set_adpcm(rq.adpcm)))
         return rc;
+    if (rq.sink == jb::SynthSink::Fbank && (rc = out.set_fbank(rq.fbank)))
+        return rc;
     return JB_OK;
 }
 
@@ -1770,6 +1772,8 @@ int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
             return rc;
         for (size_t p = 0; rq.sink == jb::SynthSink::Adpcm && rq.adpcm_samples && p < places.size(); p++)
             rq.adpcm_samples[lo + p] = rq.join ? (size_t)b->out.programme(p).n : b->out.samples(p);
+        for (size_t p = 0; rq.sink == jb::SynthSink::Fbank && rq.fbank_frames && p < places.size(); p++)
+            rq.fbank_frames[lo + p] = (size_t)b->out.fbank_place(p)->T;
         return JB_OK;
     }
     if (rq.join) {
@@ -1961,6 +1965,15 @@ static jb::SynthRequest &request_adpcm(jb::SynthRequest &rq, const jb_adpcm_opts
     rq.i16 = true;
     rq.adpcm = opts;
     rq.adpcm_samples = n_samples;
+    return rq;
+}
+
+static jb::SynthRequest &request_fbank(jb::SynthRequest &rq, const jb_fbank_opts *opts, size_t *n_frames)
+{
+    rq.sink = jb::SynthSink::Fbank;
+    rq.i16 = false;
+    rq.fbank = opts;
+    rq.fbank_frames = n_frames;
     return rq;
 }
 
@@ -2198,6 +2211,37 @@ int jb_synthesize_adpcm(const jb_engine *e, const char *const *lines, size_t n, 
     return jb_synthesize_batch_adpcm(e, lines, off, 1, -1, opts, bytes, n_bytes, n_samples);
 }
 
+int jb_synthesize_batch_fbank(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                              int32_t device, const jb_fbank_opts *opts, uint8_t **bytes, size_t *n_bytes,
+                              size_t *n_frames)
+{
+    int rc = jb::fbank_check_opts((const jb::FbankOpts *)opts, "jb_synthesize_batch_fbank");
+    if (rc)
+        return rc;
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return jb::synthesize_batch_impl(request_fbank(rq, opts, n_frames));
+}
+
+int jb_synthesize_batch_each_fbank(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                                   size_t n_utts, int32_t device, const jb_fbank_opts *opts, uint8_t **bytes,
+                                   size_t *n_bytes, size_t *n_frames)
+{
+    int rc = jb::fbank_check_opts((const jb::FbankOpts *)opts, "jb_synthesize_batch_each_fbank");
+    if (rc)
+        return rc;
+    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return synthesize_each(engines, request_fbank(rq, opts, n_frames));
+}
+
+int jb_synthesize_fbank(const jb_engine *e, const char *const *lines, size_t n, const jb_fbank_opts *opts,
+                        uint8_t **bytes, size_t *n_bytes, size_t *n_frames)
+{
+    if (!bytes || !n_bytes)
+        return JB_ERR_INVALID;
+    size_t off[2] = {0, n};
+    return jb_synthesize_batch_fbank(e, lines, off, 1, -1, opts, bytes, n_bytes, n_frames);
+}
+
 // jb_synthesize_programme*: the options checked before any device is touched
 static int check_join_entry(const jb_join_opts *j, size_t n_utts, const char *who)
 {
@@ -2275,6 +2319,17 @@ int jb_synthesize_programme_adpcm(const jb_engine *e, const char *const *lines, 
         return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
     return jb::synthesize_batch_impl(request_join(request_adpcm(rq, opts, n_samples), join, starts));
+}
+
+int jb_synthesize_programme_fbank(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                  int32_t device, const jb_fbank_opts *opts, const jb_join_opts *join, uint8_t **bytes,
+                                  size_t *n_bytes, size_t *n_frames, uint64_t *starts)
+{
+    int rc = jb::fbank_check_opts((const jb::FbankOpts *)opts, "jb_synthesize_programme_fbank");
+    if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_fbank")))
+        return rc;
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return jb::synthesize_batch_impl(request_join(request_fbank(rq, opts, n_frames), join, starts));
 }
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)

@@ -1,0 +1,267 @@
+// jb_fbank.cpp -- the host half of the filterbank features: the option check, the geometry, the three tables (window,
+// twiddles, mel weights; long double, rounded once) and the rule of jb_fbank.h over PCM the caller holds without a GPU
+// (jb_fbank_host, what the kernel is checked against).
+#include "jb_host.h"
+
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+namespace jb {
+
+static_assert(sizeof(FbankOpts) == sizeof(jb_fbank_opts) && offsetof(FbankOpts, n_mels) == offsetof(jb_fbank_opts, n_mels) &&
+                  offsetof(FbankOpts, f_max_hz) == offsetof(jb_fbank_opts, f_max_hz) &&
+                  offsetof(FbankOpts, log_floor) == offsetof(jb_fbank_opts, log_floor) &&
+                  offsetof(FbankOpts, flags) == offsetof(jb_fbank_opts, flags) &&
+                  offsetof(FbankOpts, reserved) == offsetof(jb_fbank_opts, reserved),
+              "jb_fbank.h restates the header's options");
+static_assert(kFbHann == JB_FBANK_HANN && kFbHamming == JB_FBANK_HAMMING && kFbCenter == JB_FBANK_CENTER &&
+                  kFbLinear == JB_FBANK_LINEAR && kFbUnit == JB_FBANK_UNIT && kFbF64 == JB_FBANK_F64,
+              "jb_fbank.h restates the header's constants");
+
+namespace {
+
+inline long double mel_of(long double f) { return 1127.0L * logl(1.0L + f / 700.0L); }
+
+// One frame by the rule: x[0..wl) windowed (a null sample pointer: zeros) -> E[0..n_mels)
+struct HostFrame {
+    const FbankGeom &g;
+    const FbankTables &t;
+    uint32_t M, log2m;
+    std::vector<double> re, im;
+    HostFrame(const FbankGeom &geom, const FbankTables &tab) : g(geom), t(tab), M(geom.n_fft / 2), log2m(0)
+    {
+        while ((1u << log2m) < M)
+            log2m++;
+        re.assign(M + 1, 0.0);
+        im.assign(M + 1, 0.0);
+    }
+    // sample i of the frame, i < n_fft: x(i) windowed, 0 from wl on
+    template <class X> void run(X x, double *E)
+    {
+        for (uint32_t j = 0; j < M; j++) {
+            uint32_t r = 0;
+            for (uint32_t b = 0; b < log2m; b++)
+                r |= ((j >> b) & 1u) << (log2m - 1 - b);
+            re[r] = 2 * j < g.wl ? t.win[2 * j] * x(2 * j) : 0.0;
+            im[r] = 2 * j + 1 < g.wl ? t.win[2 * j + 1] * x(2 * j + 1) : 0.0;
+        }
+        for (uint32_t s = 0; s < log2m; s++)
+            for (uint32_t j = 0; j < M / 2; j++)
+                fbank_butterfly(re.data(), im.data(), t.tw.data(), log2m, s, j);
+        for (uint32_t k = 0; k <= M / 2; k++)
+            fbank_untangle(re.data(), im.data(), t.tw.data(), M, k);
+        for (uint32_t m = 0; m < g.n_mels; m++) {
+            double e = 0.0;
+            const double *w = t.wts.data() + t.woff[m];
+            for (uint32_t i = 0; i < t.count[m]; i++)
+                e += w[i] * re[t.first[m] + i];
+            E[m] = e;
+        }
+    }
+};
+
+} // namespace
+
+int fbank_check_opts(const FbankOpts *opts, const char *who)
+{
+    if (!opts) {
+        set_error(std::string(who) + ": opts is NULL");
+        return JB_ERR_INVALID;
+    }
+    if (const char *f = fbank_opts_fault(*opts)) {
+        set_error(std::string(who) + ": " + f);
+        return JB_ERR_INVALID;
+    }
+    return JB_OK;
+}
+
+int fbank_geometry(const FbankOpts *opts, uint32_t hz, const char *who, FbankGeom *g)
+{
+    const int rc = fbank_check_opts(opts, who);
+    if (rc)
+        return rc;
+    if (const char *f = fbank_geometry_fault(*opts, hz, g)) {
+        set_error(std::string(who) + ": at " + std::to_string(hz) + " Hz " + f);
+        return JB_ERR_INVALID;
+    }
+    return JB_OK;
+}
+
+void fbank_window(uint32_t window, uint32_t wl, double *w)
+{
+    const long double two_pi = 2.0L * acosl(-1.0L);
+    for (uint32_t j = 0; j < wl; j++)
+        w[j] = window == kFbHamming ? (double)(0.54L - 0.46L * cosl(two_pi * j / (long double)(wl - 1)))
+                                    : (double)(0.5L - 0.5L * cosl(two_pi * j / (long double)wl));
+}
+
+void fbank_filterbank(const FbankGeom &g, uint32_t hz, double *W)
+{
+    const uint32_t K = g.n_fft / 2 + 1;
+    const long double lo = mel_of(g.f_min), hi = mel_of(g.f_max);
+    std::vector<long double> mu(K);
+    for (uint32_t k = 0; k < K; k++)
+        mu[k] = mel_of((long double)k * hz / g.n_fft);
+    for (uint32_t m = 0; m < g.n_mels; m++) {
+        const long double l = lo + (hi - lo) * m / (g.n_mels + 1), c = lo + (hi - lo) * (m + 1) / (g.n_mels + 1),
+                          r = lo + (hi - lo) * (m + 2) / (g.n_mels + 1);
+        for (uint32_t k = 0; k < K; k++) {
+            const long double up = (mu[k] - l) / (c - l), down = (r - mu[k]) / (r - c);
+            const long double v = up < down ? up : down;
+            W[(size_t)m * K + k] = v > 0.0L ? (double)v : 0.0;
+        }
+    }
+}
+
+bool fbank_tables(const FbankGeom &g, uint32_t hz, uint32_t window, FbankTables *t)
+{
+    const uint32_t K = g.n_fft / 2 + 1;
+    t->win.resize(g.wl);
+    fbank_window(window, g.wl, t->win.data());
+    const long double two_pi = 2.0L * acosl(-1.0L);
+    t->tw.resize(2 * (size_t)K);
+    for (uint32_t k = 0; k < K; k++) {
+        t->tw[2 * k] = (double)cosl(two_pi * k / (long double)g.n_fft);
+        t->tw[2 * k + 1] = (double)-sinl(two_pi * k / (long double)g.n_fft);
+    }
+    std::vector<double> W((size_t)g.n_mels * K);
+    fbank_filterbank(g, hz, W.data());
+    t->wts.clear();
+    t->first.assign(g.n_mels, 0);
+    t->count.assign(g.n_mels, 0);
+    t->woff.assign(g.n_mels, 0);
+    t->rise.assign(g.n_mels, 0);
+    t->wr.assign(K, 0.0);
+    t->wf.assign(K, 0.0);
+    // (the centres as fbank_filterbank has them: a bin is on a filter's rising side where mu_k is at or below it)
+    const long double lo = mel_of(g.f_min), hi = mel_of(g.f_max);
+    bool ok = true;
+    for (uint32_t m = 0; m < g.n_mels; m++) {
+        // (the weights rise and fall along mu: the bins above 0 are one run)
+        uint32_t a = 0, b = 0;
+        for (uint32_t k = 0; k < K; k++)
+            if (W[(size_t)m * K + k] > 0.0) {
+                if (a == b)
+                    a = k;
+                b = k + 1;
+            }
+        t->first[m] = a;
+        t->count[m] = b - a;
+        t->woff[m] = (uint32_t)t->wts.size();
+        t->wts.insert(t->wts.end(), W.begin() + (size_t)m * K + a, W.begin() + (size_t)m * K + b);
+        const long double c = lo + (hi - lo) * (m + 1) / (g.n_mels + 1);
+        for (uint32_t k = a; k < b; k++) {
+            const bool rising = mel_of((long double)k * hz / g.n_fft) <= c;
+            std::vector<double> &side = rising ? t->wr : t->wf;
+            ok = ok && side[k] == 0.0 && (rising ? t->rise[m] == k - a : true);
+            side[k] = W[(size_t)m * K + k];
+            t->rise[m] += rising;
+        }
+    }
+    return ok;
+}
+
+} // namespace jb
+
+using namespace jb;
+
+extern "C" {
+
+int jb_fbank_geometry(uint32_t hz, const jb_fbank_opts *opts, size_t n, uint32_t *wl, uint32_t *hop, uint32_t *n_fft,
+                      size_t *T, size_t *n_bytes)
+{
+    FbankGeom g{};
+    const int rc = fbank_geometry((const FbankOpts *)opts, hz, "jb_fbank_geometry", &g);
+    if (rc)
+        return rc;
+    const uint64_t frames = fbank_frames(n, g.wl, g.hop, (opts->flags & kFbCenter) != 0);
+    if (wl)
+        *wl = g.wl;
+    if (hop)
+        *hop = g.hop;
+    if (n_fft)
+        *n_fft = g.n_fft;
+    if (T)
+        *T = (size_t)frames;
+    if (n_bytes)
+        *n_bytes = (size_t)(frames * g.n_mels * fbank_elem(opts->flags));
+    return JB_OK;
+}
+
+int jb_fbank_window(uint32_t hz, const jb_fbank_opts *opts, double *w, size_t cap)
+{
+    FbankGeom g{};
+    const int rc = fbank_geometry((const FbankOpts *)opts, hz, "jb_fbank_window", &g);
+    if (rc)
+        return rc;
+    if (cap < g.wl) {
+        set_error("jb_fbank_window: the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (!w)
+        return JB_ERR_INVALID;
+    fbank_window(opts->window, g.wl, w);
+    return JB_OK;
+}
+
+int jb_fbank_filterbank(uint32_t hz, const jb_fbank_opts *opts, double *W, size_t cap)
+{
+    FbankGeom g{};
+    const int rc = fbank_geometry((const FbankOpts *)opts, hz, "jb_fbank_filterbank", &g);
+    if (rc)
+        return rc;
+    if (cap < (size_t)g.n_mels * (g.n_fft / 2 + 1)) {
+        set_error("jb_fbank_filterbank: the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (!W)
+        return JB_ERR_INVALID;
+    fbank_filterbank(g, hz, W);
+    return JB_OK;
+}
+
+int jb_fbank_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *opts, uint8_t *out, size_t cap)
+{
+    FbankGeom g{};
+    const int rc = fbank_geometry((const FbankOpts *)opts, hz, "jb_fbank_host", &g);
+    if (rc)
+        return rc;
+    const bool center = (opts->flags & kFbCenter) != 0;
+    const uint64_t T = fbank_frames(n, g.wl, g.hop, center);
+    if (cap < T * g.n_mels * fbank_elem(opts->flags)) {
+        set_error("jb_fbank_host: the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (n && (!in || (T && !out)))
+        return JB_ERR_INVALID;
+    FbankTables tab;
+    fbank_tables(g, hz, opts->window, &tab);
+    HostFrame fr(g, tab);
+    std::vector<double> E(g.n_mels);
+    const double scale = (opts->flags & kFbUnit) ? 0x1p-15 : 1.0;
+    for (uint64_t t = 0; t < T; t++) {
+        const int64_t k0 = (int64_t)(t * g.hop) - (center ? (int64_t)(g.wl / 2) : 0);
+        fr.run(
+            [&](uint32_t i) {
+                const int64_t k = k0 + (int64_t)i;
+                return k >= 0 && (uint64_t)k < n ? in[k] * scale : 0.0;
+            },
+            E.data());
+        for (uint32_t m = 0; m < g.n_mels; m++) {
+            const double v = (opts->flags & kFbLinear) ? E[m] : E[m] > g.log_floor ? log(E[m]) : g.ln_floor;
+            const size_t at = (size_t)t * g.n_mels + m;
+            if (opts->flags & kFbF64)
+                memcpy(out + at * 8, &v, 8);
+            else {
+                const float f = (float)v;
+                memcpy(out + at * 4, &f, 4);
+            }
+        }
+    }
+    return JB_OK;
+}
+
+void jb_fbank_free(uint8_t *p) { free(p); }
+
+} // extern "C"

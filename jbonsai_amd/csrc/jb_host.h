@@ -3,6 +3,7 @@
 #include "../../include/jbonsai_amd.h"
 #include "jb_device.h"
 #include "jb_adpcm.h"
+#include "jb_fbank.h"
 #include "jb_filter.h"
 #include "jb_format.h"
 #include "jb_limiter.h"
@@ -38,7 +39,7 @@ int noise_table(int device, size_t need, std::shared_ptr<NoiseDev> *out);
 void release_cached_memory(); // empties the per-device pools of finished batches' memory
 void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE_POOL_MB at start)
 // What an engine-level call hands out per utterance (or per programme): PCM, or the bytes of one of the encoders
-enum class SynthSink { Pcm, Flac, Formatted, Adpcm };
+enum class SynthSink { Pcm, Flac, Formatted, Adpcm, Fbank };
 struct ByteSpan { // an output's place in the host copy of a byte sink's slab (OutputChain::read_bytes_all)
     uint64_t off, bytes;
 };
@@ -55,12 +56,14 @@ struct SynthRequest {
     unsigned host_threads = 0;               // 0: the default front-half thread count
     SynthSink sink = SynthSink::Pcm;
     bool i16 = false;                        // the batch's PCM in 16 bits (Pcm: what is handed out; Flac and Adpcm
-                                             // encode it) or in f64 (Formatted reads f64)
+                                             // encode it) or in f64 (Formatted and Fbank read f64)
     const jb_flac_opts *flac = nullptr;      // Flac: both may be null (the defaults; no MD5 / SEEKTABLE request)
     const jb_flac_meta *flac_meta = nullptr;
     const jb_format_opts *fmt = nullptr;     // Formatted
     const jb_adpcm_opts *adpcm = nullptr;    // Adpcm; adpcm_samples[u] (may be null): the samples output u's blocks encode
     size_t *adpcm_samples = nullptr;
+    const jb_fbank_opts *fbank = nullptr;    // Fbank; fbank_frames[u] (may be null): the frames of output u
+    size_t *fbank_frames = nullptr;
     const jb_join_opts *join = nullptr;      // jb_synthesize_programme*: all utterances are one programme, the one
     uint64_t *join_starts = nullptr;         // output; join_starts[u] (may be null): each member's first sample
     void **out = nullptr;                    // [n_utts], or [1] with a join: malloc'ed PCM or bytes of each output
@@ -278,6 +281,22 @@ hipError_t launch_format(uint32_t format, uint32_t dither, uint64_t seed, const 
 // IMA ADPCM (jb_adpcm.hip; the rules and AdpcmUtt: jb_adpcm.h): utts_dev[0..n) of `groups` workgroups in all, their
 // x f64 or 16-bit samples by i16
 hipError_t launch_adpcm(bool i16, const AdpcmUtt *utts_dev, uint32_t n, uint64_t groups, hipStream_t stream);
+
+// Filterbank features (jb_fbank.hip; the rule, FbankClass and FbankUtt: jb_fbank.h; the host half: jb_fbank.cpp).
+// The distinct geometries of a launch, one per rate: their tables on the host
+struct FbankClasses {
+    std::vector<uint32_t> key_hz;
+    std::vector<FbankGeom> geom;
+    std::vector<FbankTables> tables;
+    // the class of `hz` (made at its first use), or JB_ERR_INVALID naming the field that is out of its limits there
+    int find(const FbankOpts &opts, uint32_t hz, const char *who, uint32_t *cls);
+    size_t words() const; // doubles of the device image of all tables
+    // the image (to be copied to `dev`, words() doubles) and the classes that point into it
+    void bind(const FbankOpts &opts, const double *dev, std::vector<double> *image, std::vector<FbankClass> *out) const;
+};
+// utts_dev[0..n) of `groups` workgroups in all
+hipError_t launch_fbank(const FbankClass *classes_dev, const FbankUtt *utts_dev, uint32_t n, uint64_t groups,
+                        hipStream_t stream);
 
 // The join stage (jb_join.hip; the rules, JoinMember and JoinSpan: jb_join.h; the layout: jb_output.h)
 // join_layout with the request's reserved words checked and set_error naming what is wrong (JB_ERR_INVALID)
@@ -498,7 +517,8 @@ template <class T> struct DevList {
 // The stages behind the vocoder of one batch, in their order -- the converter (jb_batch_set_output_rate), the filter
 // (jb_batch_set_filter), loudness (jb_batch_set_loudness_target, with peak mode, groups and the R128 report), the
 // join (jb_batch_set_join), then the encoders of the final PCM side by side: FLAC (jb_batch_set_flac, _flac_meta),
-// the sample format (jb_batch_set_format) and IMA ADPCM (jb_batch_set_adpcm) -- and all their device state.
+// the sample format (jb_batch_set_format), IMA ADPCM (jb_batch_set_adpcm) and the filterbank features
+// (jb_batch_set_fbank) -- and all their device state.
 // The setters record a request and plan again (jb_output.h); the first run carries the plan out (prepare); every run
 // enqueues the chain once behind the hand-off check, and finish_verify once more for the utterances its redo rounds
 // rewrote.  Each stage has the same three steps: prepare_X (its lists and scratch), select_X (what the next launch
@@ -518,6 +538,9 @@ struct OutputChain {
     int set_flac_meta(const jb_flac_meta *meta); // behind set_flac
     int set_format(const jb_format_opts *opts); // an f64 batch only
     int set_adpcm(const jb_adpcm_opts *opts);   // an f64 or a 16-bit batch
+    // an f64 batch only; checked at every utterance's output rate (NULL: the request is withdrawn); set_output_rate
+    // checks the combined request again
+    int set_fbank(const jb_fbank_opts *opts);
     // req[u]: utterance u's programme, pads and fades, n == B (nullptr, 0: the request is withdrawn); this setter and
     // set_output_rate check that a programme's members agree on the rate
     int set_join(const jb_join_utt *req, size_t n);
@@ -564,6 +587,11 @@ struct OutputChain {
     // one) and its bytes
     const OutAdpcmUtt *adpcm_place(size_t u) const;
     int read_adpcm(size_t u, uint8_t *dst);
+    // the features: unit u's place and geometry (known once the request is made; null without one), its rate, its bytes
+    const OutFbankUtt *fbank_place(size_t u) const;
+    uint32_t fbank_mels() const { return fb_p.n_mels; }
+    uint32_t fbank_hz(size_t u) const { return joined() ? plan.units[u].hz : plan.utt[u].hz; }
+    int read_fbank(size_t u, uint8_t *dst);
     // every output of a byte sink: the used part of its slab in one copy, output u at host + places[u].off (FLAC:
     // the streams' sizes and places come from the device's index, one small copy first; the others' from the plan)
     int read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host);
@@ -586,6 +614,8 @@ private:
     jb_format_opts fmt_p{};
     bool ad_on = false;                        // IMA ADPCM is requested
     uint32_t ad_align = 0;                     // its block_align (0: by the rate)
+    bool fb_on = false;                        // filterbank features are requested
+    FbankOpts fb_p{};
     std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
     std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
@@ -669,6 +699,12 @@ private:
         std::vector<uint64_t> ngroups; // [U] each unit's groups of kAdpcmLanes blocks
         uint64_t groups = 0;
     } ad;
+    struct Fbank { // follows `units`
+        DevList<FbankUtt> utts;
+        std::vector<uint64_t> ngroups; // [U] each unit's workgroups
+        uint64_t groups = 0;
+        FbankClass *classes_dev = nullptr;
+    } fb;
     // the units the encoders take: the programmes in the join slab, or the utterances
     struct EncUnit {
         uint64_t off, n;
@@ -695,6 +731,8 @@ private:
     int check_limiter_groups(const std::vector<uint32_t> &group, const std::vector<LimOpts> &req, const char *who) const;
     bool formatted() const { return plan.fmt_src != OutSlab::None; }
     bool adpcm() const { return plan.adpcm_src.slab != OutSlab::None; }
+    bool fbank() const { return plan.fbank_src != OutSlab::None; }
+    int check_fbank(const FbankOpts &opts, const std::vector<uint32_t> &want, const char *who) const;
     void replan(); // host geometry and routing of the present requests
     // v[0..n), n == 1 or B, as [B] values; false (set_error(err)) for anything else
     template <class T> bool broadcast(const T *v, size_t n, std::vector<T> *out, const char *err) const;
@@ -717,6 +755,7 @@ private:
     int prepare_flac(), select_flac(const RedoScope *scope), launch_flac(bool redo);
     int prepare_format(), select_format(const RedoScope *scope), launch_format(bool redo);
     int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);
+    int prepare_fbank(), select_fbank(const RedoScope *scope), launch_fbank(bool redo);
     int format_ready() const;
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
     int flac_ready() const;

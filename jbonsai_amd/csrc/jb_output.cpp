@@ -126,6 +126,26 @@ OutPlan plan_output(const OutPlanIn &in)
         }
         p.alloc[(size_t)OutSlab::Adpcm] = std::max<uint64_t>(bytes, 16);
     }
+    // the filterbank features beside them: the final f64 to frames of each unit's own geometry (a request that some
+    // rate refuses is no request: the chain has checked it)
+    if (in.fbank && !p.final.i16) {
+        std::vector<OutFbankUtt> f(units.size());
+        uint64_t bytes = 0;
+        bool ok = true;
+        for (size_t u = 0; u < units.size() && ok; u++) {
+            FbankGeom g{};
+            if (!(ok = fbank_geometry_quiet(*in.fbank, units[u].hz, &g)))
+                break;
+            const uint64_t T = fbank_frames(units[u].n, g.wl, g.hop, (in.fbank->flags & kFbCenter) != 0);
+            f[u] = {bytes, T * g.n_mels * fbank_elem(in.fbank->flags), T, g.wl, g.hop, g.n_fft};
+            bytes += (f[u].bytes + 15) & ~(uint64_t)15;
+        }
+        if (ok) {
+            p.fbank_src = enc.slab;
+            p.fbank = std::move(f);
+            p.alloc[(size_t)OutSlab::Feat] = std::max<uint64_t>(bytes, 16);
+        }
+    }
     return p;
 }
 

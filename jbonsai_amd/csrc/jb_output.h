@@ -1,7 +1,7 @@
 #pragma once
 // jb_output.h -- the routing of the stages behind the vocoder, in their order: converter (output rate), filter,
 // loudness (measurement, groups, report, apply pass), join, then the encoders side by side: FLAC, sample format, IMA
-// ADPCM.  plan_output (jb_output.cpp) decides from the batch's shape and the requests alone which slab each stage
+// ADPCM, filterbank features.  plan_output (jb_output.cpp) decides from the batch's shape and the requests alone which slab each stage
 // reads and writes, in f64 or in 16 bits, which slab the read entries hand out, each utterance's output geometry and
 // its place in the encoders' byte slabs, and with a join request (jb_join.h) the programmes: their numbering, each
 // one's place in the join slab, each member's start, and the encoders' geometry by programme instead of by utterance.
@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include <vector>
 
+#include "jb_fbank.h"
 #include "jb_join.h"
 
 namespace jb {
@@ -31,11 +32,12 @@ enum class OutSlab : uint8_t {
     Join64,  // f64 the join stage writes: the programmes
     Join16,  // the same in 16 bits
     Filt64,  // f64 the filter stage writes
+    Feat,    // bytes of the filterbank features
     Count
 };
 constexpr size_t out_slab_elem(OutSlab s) // bytes
 {
-    return s == OutSlab::Fmt || s == OutSlab::Adpcm                            ? 1
+    return s == OutSlab::Fmt || s == OutSlab::Adpcm || s == OutSlab::Feat      ? 1
            : s == OutSlab::S16 || s == OutSlab::New16 || s == OutSlab::Join16 ? 2
                                                                                : 8;
 }
@@ -58,6 +60,7 @@ struct OutPlanIn {
     uint32_t adpcm_align = 0;             // its block_align: 0 = by each utterance's output rate (jb_adpcm.h)
     const JoinUtt *join = nullptr;        // [B] the join request (jb_join.h); nullptr: none
     const uint8_t *filter = nullptr;      // [B] 1 = the utterance's filter has at least one section; nullptr: no request
+    const FbankOpts *fbank = nullptr;     // the filterbank request (jb_fbank.h), checked at every output rate; nullptr: none
 };
 
 struct OutUtt {
@@ -72,6 +75,12 @@ struct OutFmtUtt { // an utterance's place in the format slab
 struct OutAdpcmUtt { // an utterance's blocks in the ADPCM slab
     uint64_t off, bytes; // byte offset (16-byte aligned) and blocks * A
     uint32_t A;          // its block size
+};
+
+struct OutFbankUtt { // a unit's features in the feature slab
+    uint64_t off, bytes;     // byte offset (16-byte aligned) and T * n_mels * bytes per element
+    uint64_t T;              // its frames
+    uint32_t wl, hop, n_fft; // its geometry, by its rate
 };
 
 struct OutUnit { // a programme in the join slab: what the encoders behind a join take for an utterance
@@ -103,8 +112,10 @@ struct OutPlan {
     std::vector<OutFmtUtt> fmt;       // [B] with a format stage, else empty
     OutWrite adpcm_src;               // what the ADPCM stage reads: what `final` names, f64 or 16-bit (None: no ADPCM)
     std::vector<OutAdpcmUtt> adpcm;   // [B] with an ADPCM stage, else empty
+    OutSlab fbank_src = OutSlab::None; // f64 the fbank stage reads: what `final` names (None: no request, or no f64)
+    std::vector<OutFbankUtt> fbank;    // [B] with an fbank stage, else empty
     // With a join request: the stage reads what `final` names and writes the programmes to a slab of its own; flac,
-    // fmt_src and adpcm_src then name that slab, and fmt and adpcm have [P] entries laid out from `units`
+    // fmt_src, adpcm_src and fbank_src then name that slab, and fmt, adpcm and fbank have [P] entries laid out from `units`
     OutWrite join_src, join;          // None: no join
     std::vector<OutUnit> units;       // [P] the programmes
     std::vector<uint32_t> prog_of;    // [B] each utterance's programme

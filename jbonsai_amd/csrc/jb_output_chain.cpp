@@ -2,7 +2,8 @@
 // request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() selects what each
 // stage takes (everything, or a redo's part: redo_scope, jb_output.h) and launches, in this order and on the
 // vocoder's stream: the converter (k_resample), the filter, loudness (measurement, groups, report, apply pass; with a
-// limiter request the limiter in the apply pass's place), the join, then the encoders of the final PCM: FLAC (blocks, MD5, pack), the sample format and IMA ADPCM.
+// limiter request the limiter in the apply pass's place), the join, then the encoders of the final PCM: FLAC (blocks, MD5, pack), the sample format, IMA ADPCM and
+// the filterbank features.
 #include "jb_host.h"
 
 #include <algorithm>
@@ -40,6 +41,7 @@ void OutputChain::replan()
     in.adpcm_align = ad_align;
     in.join = join_req.empty() ? nullptr : join_req.data();
     in.filter = filt_any.empty() ? nullptr : filt_any.data();
+    in.fbank = fb_on ? &fb_p : nullptr;
     plan = plan_output(in);
 }
 
@@ -95,7 +97,8 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
     }
     if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)) ||
         (rc = check_join(join_req, want, "jb_batch_set_output_rate")) ||
-        (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")))
+        (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")) ||
+        (fb_on && (rc = check_fbank(fb_p, want, "jb_batch_set_output_rate"))))
         return rc;
     want_hz = std::move(want);
     replan();
@@ -280,6 +283,40 @@ int OutputChain::set_adpcm(const jb_adpcm_opts *opts)
     return JB_OK;
 }
 
+// The filterbank request under these rates: JB_ERR_INVALID naming the field that is out of its limits at some rate
+int OutputChain::check_fbank(const FbankOpts &opts, const std::vector<uint32_t> &want, const char *who) const
+{
+    int rc;
+    for (uint32_t hz : rates_under(want))
+        if ((rc = fbank_geometry(&opts, hz, who, nullptr)))
+            return rc;
+    return JB_OK;
+}
+
+int OutputChain::set_fbank(const jb_fbank_opts *opts)
+{
+    int rc;
+    if (opts && (rc = fbank_check_opts((const FbankOpts *)opts, "jb_batch_set_fbank")))
+        return rc;
+    if (b.flags & JB_BATCH_MLPG_ONLY) {
+        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_UNSUPPORTED;
+    }
+    if (b.flags & JB_BATCH_PCM_I16) {
+        set_error("jb_batch_set_fbank: the fbank stage reads the f64 output (a batch without JB_BATCH_PCM_I16)");
+        return JB_ERR_UNSUPPORTED;
+    }
+    if ((rc = check_settable("jb_batch_set_fbank: the features are set before the batch's first run")))
+        return rc;
+    if (opts && (rc = check_fbank(*(const FbankOpts *)opts, want_hz, "jb_batch_set_fbank")))
+        return rc;
+    fb_on = opts != nullptr;
+    if (opts)
+        fb_p = *(const FbankOpts *)opts;
+    replan();
+    return JB_OK;
+}
+
 // The join request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming what is wrong
 int OutputChain::check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const
 {
@@ -426,7 +463,8 @@ int OutputChain::prepare()
             return rc;
     if ((rc = prepare_resample()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
         (rc = prepare_join()) ||
-        (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()))
+        (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
+        (rc = prepare_fbank()))
         return rc;
     if (plan.active()) {
         void *voc = slab[(size_t)plan.vocoder.slab];
@@ -441,7 +479,7 @@ int OutputChain::prepare()
 // uploaded (select_X) before its first launch, and one wait ends it
 int OutputChain::enqueue(const std::vector<uint8_t> *only)
 {
-    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || joined()))
+    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || joined()))
         return JB_OK;
     const bool redo = only != nullptr;
     static const LnGroups no_groups;
@@ -451,14 +489,14 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     int rc;
     if ((rc = select_resample(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
         (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
-        (rc = select_adpcm(scope)))
+        (rc = select_adpcm(scope)) || (rc = select_fbank(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n))
+    if (redo && !(rs.tiles.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
         (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
-        (rc = launch_adpcm(redo)))
+        (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)))
         return rc;
     hipError_t e;
     if (redo && (e = hipStreamSynchronize(b.stream_voc)) != hipSuccess)
@@ -1045,6 +1083,64 @@ int OutputChain::launch_adpcm(bool redo)
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_adpcm(redo)" : "k_adpcm");
 }
 
+// ---- the filterbank features beside them, of the same final f64.  The unit list: the final PCM of the plan in, each
+// unit's frames at their 16-byte aligned place out; the tables of every distinct rate in one block
+int OutputChain::prepare_fbank()
+{
+    if (!fbank())
+        return JB_OK;
+    const std::vector<EncUnit> units = enc_units();
+    const size_t U = units.size();
+    const double *src = (const double *)slab[(size_t)plan.fbank_src];
+    uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Feat];
+    FbankClasses cls;
+    fb.utts.host.assign(U, FbankUtt{});
+    fb.ngroups.assign(U, 0);
+    fb.groups = 0;
+    int rc;
+    for (size_t u = 0; u < U; u++) {
+        FbankUtt &w = fb.utts.host[u];
+        if ((rc = cls.find(fb_p, units[u].hz, "jb_batch_set_fbank", &w.cls)))
+            return rc;
+        w.x = src + units[u].off;
+        w.y = dst + plan.fbank[u].off;
+        w.n = units[u].n;
+        w.T = plan.fbank[u].T;
+        w.g0 = fb.groups;
+        const uint32_t per = fbank_wg_frames(plan.fbank[u].n_fft);
+        fb.ngroups[u] = (w.T + per - 1) / per;
+        fb.groups += fb.ngroups[u];
+    }
+    double *tables = nullptr;
+    if ((rc = b.dalloc(&tables, cls.words(), false)))
+        return rc;
+    std::vector<double> image;
+    std::vector<FbankClass> classes;
+    cls.bind(fb_p, tables, &image, &classes);
+    if ((rc = upload_list(tables, image, "fbank tables")) || (rc = b.dalloc(&fb.classes_dev, classes.size(), false)) ||
+        (rc = upload_list(fb.classes_dev, classes, "fbank classes")) || (rc = fb.utts.alloc(b, U, U)))
+        return rc;
+    return fb.utts.upload("fbank work list");
+}
+
+int OutputChain::select_fbank(const RedoScope *scope)
+{
+    if (!fbank() || !scope)
+        return fb.utts.take_all(fb.groups);
+    // `units`: every unit whose final PCM changed, each recomputed whole (one without a frame stays in the list: it
+    // has no workgroup)
+    const Picked p = pick_renumbered(scope->units, fb.ngroups);
+    return fb.utts.upload_redo(renumbered(fb.utts.host, p, &FbankUtt::g0), kRedoLists, p.total);
+}
+
+int OutputChain::launch_fbank(bool redo)
+{
+    if (!fbank() || (redo && !fb.utts.n))
+        return JB_OK;
+    const hipError_t e = jb::launch_fbank(fb.classes_dev, fb.utts.list, fb.utts.n, fb.utts.total, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_fbank(redo)" : "k_fbank");
+}
+
 int OutputChain::check_ready(bool requested, const char *not_run, const char *not_set) const
 {
     if (requested && ready)
@@ -1164,6 +1260,24 @@ int OutputChain::read_adpcm(size_t u, uint8_t *dst)
     return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Adpcm] + w.off, dst, (size_t)w.bytes) : b.sync();
 }
 
+const OutFbankUtt *OutputChain::fbank_place(size_t u) const
+{
+    if (!fb_on) {
+        set_error("fbank: jb_batch_set_fbank was not called");
+        return nullptr;
+    }
+    return &plan.fbank[u];
+}
+
+int OutputChain::read_fbank(size_t u, uint8_t *dst)
+{
+    int rc = check_ready(fb_on, "fbank: the batch has not run", "fbank: jb_batch_set_fbank was not called");
+    if (rc)
+        return rc;
+    const OutFbankUtt &w = plan.fbank[u];
+    return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Feat] + w.off, dst, (size_t)w.bytes) : b.sync();
+}
+
 int OutputChain::format_ready() const
 {
     return check_ready(fmt_on, "format: the batch has not run", "format: jb_batch_set_format was not called");
@@ -1194,6 +1308,8 @@ int OutputChain::read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, s
              : sink == SynthSink::Formatted ? format_ready()
              : sink == SynthSink::Adpcm
                  ? check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called")
+             : sink == SynthSink::Fbank
+                 ? check_ready(fb_on, "fbank: the batch has not run", "fbank: jb_batch_set_fbank was not called")
                  : JB_ERR_INVALID;
     if (rc)
         return rc;
@@ -1208,9 +1324,10 @@ int OutputChain::read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, s
     }
     for (size_t u = 0; u < places->size(); u++)
         (*places)[u] = sink == SynthSink::Formatted ? ByteSpan{plan.fmt[u].off, plan.fmt[u].bytes}
+                       : sink == SynthSink::Fbank   ? ByteSpan{plan.fbank[u].off, plan.fbank[u].bytes}
                                                     : ByteSpan{plan.adpcm[u].off, plan.adpcm[u].bytes};
-    return read_used(slab[(size_t)(sink == SynthSink::Formatted ? OutSlab::Fmt : OutSlab::Adpcm)], used_bytes(*places),
-                     true, host);
+    const OutSlab from = sink == SynthSink::Formatted ? OutSlab::Fmt : sink == SynthSink::Fbank ? OutSlab::Feat : OutSlab::Adpcm;
+    return read_used(slab[(size_t)from], used_bytes(*places), true, host);
 }
 
 } // namespace jb

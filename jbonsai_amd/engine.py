@@ -493,13 +493,35 @@ class Engine:
                                                   nsamp))
         return F.adpcm_streams(self._L, bufs, ns, nsamp, [self._out_hz()] * B, block_align, B)
 
+    def synthesize_fbank(self, labels: Sequence[str], opts=None, **kw) -> np.ndarray:
+        """jb_synthesize_fbank: the log-mel filterbank frames [T, n_mels] of what synthesize(labels) returns, computed
+        on the GPU.  opts: F.FbankOpts, or the keywords of J.fbank."""
+        opts = opts if opts is not None else F.fbank(**kw)
+        buf, n, nf = C.POINTER(C.c_uint8)(), C.c_size_t(), C.c_size_t()
+        F.check(self._L.jb_synthesize_fbank(self._h, _lines(labels), len(labels), C.byref(opts), C.byref(buf),
+                                            C.byref(n), C.byref(nf)))
+        return F.take_fbank(self._L, [buf], [n.value], 1, opts)[0]
+
+    def synthesize_fbank_batch(self, utterances: Sequence[Sequence[str]], opts=None, device: int = -1,
+                               **kw) -> List[np.ndarray]:
+        """jb_synthesize_batch_fbank: each utterance of synthesize_batch(...) as filterbank frames."""
+        opts = opts if opts is not None else F.fbank(**kw)
+        flat = [l for u in utterances for l in u]
+        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+        B = len(utterances)
+        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+        bufs, ns, nf = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
+        F.check(self._L.jb_synthesize_batch_fbank(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns, nf))
+        return F.take_fbank(self._L, bufs, ns, B, opts)
+
     def synthesize_programme(self, utterances: Sequence[Sequence[str]], sink: str = "f64", lead_ms: float = 0.0,
                              gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0, device: int = -1,
                              **sink_opts):
         """jb_synthesize_programme*: the utterances as ONE programme -- lead_ms of zeros, the first utterance, gap_ms,
         the next, ..., trail_ms, a fade of fade_ms at both edges of each -- joined on the GPU in front of the sink.
         sink: "f64" or "i16" (PCM arrays), "flac" (bytes; block_size, max_lpc_order, md5, seek_interval_ms),
-        "formatted" (bytes; fmt, dither, seed) or "adpcm" (an AdpcmStream; block_align).  Returns (output, starts):
+        "formatted" (bytes; fmt, dither, seed), "adpcm" (an AdpcmStream; block_align) or "fbank" (an ndarray
+        [T, n_mels]; opts=F.FbankOpts or the keywords of J.fbank).  Returns (output, starts):
         starts[u] is utterance u's first sample within the programme."""
         flat = [l for u in utterances for l in u]
         off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
@@ -544,7 +566,13 @@ class Engine:
                                                     C.byref(join), C.byref(buf), C.byref(n), C.byref(ns), starts))
             return (F.adpcm_streams(L, [buf], [n.value], [ns.value], [self._out_hz()], block_align, 1)[0],
                     list(starts[:B]))
-        raise ValueError('sink is "f64", "i16", "flac", "formatted" or "adpcm"')
+        if sink == "fbank":
+            opts = sink_opts.pop("opts", None)
+            opts, nf = opts if opts is not None else F.fbank(**sink_opts), C.c_size_t()
+            F.check(L.jb_synthesize_programme_fbank(self._h, _lines(flat), offs, B, device, C.byref(opts),
+                                                    C.byref(join), C.byref(buf), C.byref(n), C.byref(nf), starts))
+            return F.take_fbank(L, [buf], [n.value], 1, opts)[0], list(starts[:B])
+        raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm" or "fbank"')
 
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
@@ -711,3 +739,22 @@ class SpeechGenerator:
             self.close()
         except Exception:
             pass
+
+
+def synthesize_batch_each_fbank(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]], opts=None,
+                                device: int = -1, **kw) -> List[np.ndarray]:
+    """jb_synthesize_batch_each_fbank: synthesize_batch_each(...) as filterbank frames, each utterance at its engine's
+    output rate and that rate's geometry."""
+    if len(engines) != len(utterances):
+        raise ValueError("one engine per utterance")
+    opts = opts if opts is not None else F.fbank(**kw)
+    B = len(utterances)
+    L = engines[0]._L if B and engines[0] is not None else F.lib()
+    _bind(L)
+    flat = [l for u in utterances for l in u]
+    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
+    bufs, ns, nf = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
+    F.check(L.jb_synthesize_batch_each_fbank(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns, nf))
+    return F.take_fbank(L, bufs, ns, B, opts)
