@@ -3,14 +3,16 @@
     python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
                                [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
-                               [--fbank OUT.npy]
+                               [--fbank OUT.npy] [--fir taps.npy [--fir-delay D]]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
 batch and joined on the GPU (Engine.synthesize_programme) in front of the encoder, so a .flac output is one stream whose
 frame numbers, STREAMINFO, MD5 and SEEKTABLE (a point about every second) cover the whole chapter; any other name is
 written as a 16-bit WAV file.  With --loudness the chapter gets ONE gain (per-request loudness scope), so the sentences
 keep their relative levels.  With --highpass a rumble and DC high-pass at that corner runs on the GPU in front of the
-loudness measurement and the encoder (Engine.set_filter).  With --limiter (and --loudness) the chapter's gain may put its
+loudness measurement and the encoder (Engine.set_filter).  With --fir every sentence is convolved on the GPU with the impulse
+response in that .npy file (taps at the output rate; --fir-delay removes its leading latency), in front of --highpass
+(Engine.set_fir).  With --limiter (and --loudness) the chapter's gain may put its
 highest peak that many dB over the ceiling and a look-ahead limiter holds the ceiling on the GPU (Engine.set_limiter), so
 one loud peak no longer holds the whole chapter under its target.  With --fbank the chapter's log-mel filterbank frames
 (25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are computed on the GPU from the joined programme, frames across
@@ -39,6 +41,9 @@ ap.add_argument("--limiter", type=float, default=None, metavar="DB",
                 help="look-ahead limiter: the gain may put the highest peak this far over the ceiling (with --loudness)")
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner (50 to 80 Hz removes rumble and DC)")
+ap.add_argument("--fir", default=None, metavar="taps.npy",
+                help="impulse response at the output rate (a 1-D .npy), convolved with every sentence on the GPU (Engine.set_fir)")
+ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
 ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="the chapter's log-mel filterbank frames from the GPU, instead of the audio")
 args = ap.parse_args()
 
@@ -50,6 +55,10 @@ for path in args.labels:
 engine = J.Engine.load([args.voice])
 if args.rate:
     engine.condition.set_output_sampling_frequency(args.rate)
+if args.fir is not None:
+    import numpy as np
+
+    engine.set_fir(J.fir(np.load(args.fir), args.rate or engine.condition.get_sampling_frequency(), args.fir_delay))
 if args.highpass is not None:
     engine.set_filter(J.highpass(args.highpass))
 if args.loudness is not None:

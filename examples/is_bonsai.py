@@ -3,6 +3,7 @@
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak] [--limiter DB]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
                                  [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]]
+                                 [--fir taps.npy [--fir-delay D]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
@@ -20,6 +21,9 @@ With --flac the 16-bit audio is encoded as a FLAC stream on the GPU, with the MD
 SEEKTABLE with a point about every second, and written as it is.
 With --highpass the audio passes a second-order high-pass at that corner on the GPU (Engine.set_filter), behind the
 output rate and in front of the loudness measurement and every encoder above.
+With --fir the audio is convolved on the GPU with the impulse response in that .npy file (a 1-D array of taps sampled at
+the output rate: the voice's, or --rate), advanced by --fir-delay samples (Engine.set_fir): in front of --highpass, the
+loudness measurement and every encoder above.
 With --fbank the sentence's log-mel filterbank frames (25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are
 computed on the GPU from the final PCM, at --rate if given, and saved as a .npy file; no WAV file is written.
 With --limiter (and --loudness) the gain may put the highest peak that many dB over the ceiling and a look-ahead limiter
@@ -50,12 +54,20 @@ ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rat
 ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="log-mel filterbank frames, computed on the GPU")
 ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
+ap.add_argument("--fir", default=None, metavar="taps.npy", help="impulse response at the output rate, convolved on the GPU")
+ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
 ap.add_argument("--limiter", type=float, default=None, metavar="DB",
                 help="look-ahead limiter on the GPU: dB the gain may put the highest peak over the ceiling (with --loudness)")
 args = ap.parse_args()
 voice, out = args.voice, args.out
 
 engine = J.Engine.load([voice])
+if args.fir is not None:
+    import numpy as np
+
+    if args.rate:
+        engine.condition.set_output_sampling_frequency(args.rate)
+    engine.set_fir(J.fir(np.load(args.fir), args.rate or engine.condition.get_sampling_frequency(), args.fir_delay))
 if args.highpass is not None:
     engine.set_filter(J.highpass(args.highpass))
 if args.loudness is not None:

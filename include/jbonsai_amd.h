@@ -978,7 +978,7 @@ void jb_join_free(void *p);
  *   twice and written once: 37.7 GB), four sections 12.20 ms; the loudness measurement and apply pass of the same batch:
  *   16.89 ms.  Against a serial cascade in extended precision the device's largest error is 4.4e-12 of the utterance's
  *   largest sample (a serial f64 cascade: 1.4e-12).
- * Not covered: FIR sections, time-varying filters, more than four sections, one-pole sections, a filter in front of
+ * Not covered: time-varying filters, more than four sections, one-pole sections, a filter in front of
  * the converter, filters on the native-rate reads, serving a generator head early, reading through the pinned
  * ring. */
 /* New (none).  f[0..n): one filter for the batch (n == 1) or one per utterance (n == jb_batch_size); NULL, 0 withdraws
@@ -1001,6 +1001,81 @@ int jb_filter_pcm_batch(const double *const *in, const size_t *n_in, size_t n, c
 int jb_filter_pcm_batch_i16(const double *const *in, const size_t *n_in, size_t n, const jb_filter *f,
                             const uint32_t *hz, int32_t device, int16_t **out, size_t *n_out);
 void jb_filter_free(void *p);
+
+/* ---- Convolution (new: the reference has no such control) ----------------------------------------------------------
+ * The PCM convolved with a caller-given impulse response (FIR) on the device, at the output rate: a room or a
+ * microphone response, a telephone channel in front of G.711, a linear-phase EQ, a matched or de-emphasis filter.  The
+ * stage is part of the filter stage: behind the converter (or the vocoder at the native rate) and in front of the
+ * filter's sections -- convolution first, then the cascade -- so that the loudness measurement, the ceiling, the
+ * limiter, the groups, the join and every encoder see the convolved audio.
+ * - The rule, for one utterance x[0..N) (f64, 16-bit units), taps h[0..K) and a delay d with 0 <= d < K:
+ *       y[n] = sum over k of h[k] x[n + d - k],   n in [0, N)
+ *   Terms whose index n + d - k lies outside [0, N) are skipped, not multiplied by zero.  The output has the input's
+ *   length: the tail beyond N is dropped and d removes a leading latency (the direct path's index of a room response,
+ *   (K - 1) / 2 of a linear-phase FIR), so the plan's geometry is that of the batch without the request.
+ * - The host rule (jb_fir_host; plain C++, no GPU, O(N K), every K): the in-range terms in ascending k; the first
+ *   starts acc = h[k] x[..], every later one is acc = fma(h[k], x[..], acc); no term in range gives +0.0.  So
+ *   h = [1.0], d = 0 returns the input bit for bit.  A 16-bit batch's output is the 16-bit sink's rule (fmin to 32767,
+ *   fmax to -32768, truncate) on the same y, as the filter's is.
+ * - The request: taps (copied at the call: the caller's buffer may be freed afterwards), hz, the rate the response was
+ *   sampled at -- it must equal the utterance's output rate; a response is never resampled -- the delay, reserved 0.
+ *   taps == NULL with n_taps == 0 is no response for that utterance.
+ * - Refused (JB_ERR_INVALID; jb_last_error names the utterance and the field) before any device is touched: n_taps == 0
+ *   with taps given, n_taps above JB_FIR_MAX_TAPS, a tap that is not finite, delay >= n_taps, hz different from the
+ *   utterance's output rate (at the set call and again at a later jb_batch_set_output_rate), reserved != 0.
+ * - On the device, by K alone (jb_fir_geometry).  JB_FIR_DIRECT, K <= JB_FIR_DIRECT_MAX: every output sample's sum in
+ *   one lane, over tiles of 2,048 outputs staged in LDS with their K - 1 samples in front, in the host rule's order:
+ *   the output equals jb_fir_host bit for bit.  JB_FIR_PARTITIONED above: uniform partitioned overlap-save in f64 with blocks of
+ *   Bk = n_fft / 2 samples, n_fft = 2048 up to K = 4096 and 4096 above, P = ceil(K / Bk) partitions; the partitions'
+ *   spectra and the twiddles are made on the host in long double, once per distinct response (taps, delay, rate: by
+ *   content); block j's spectrum -- of the n_fft samples that end at its end, shifted by d -- is taken once, and
+ *   Y_j = sum over p of X[j - p] H[p] with p ascending from 0 to min(P - 1, j + lead), every bin's sum in one lane.  The
+ *   d samples in front of block 0 are lead = ceil(d / Bk) blocks -lead .. -1 of their own (with d = 0 there are none
+ *   and p stops at min(P - 1, j)).  Blocks are counted from the utterance's own first sample: a sample's
+ *   bits depend on its utterance's samples, the taps, the delay and K only, not on the batch, the position, the entry
+ *   point or redo rounds; JB_BATCH_INVARIANT output stays invariant.  Against the sum in extended precision the
+ *   partitioned mode stays within 8 times the error of a float64 FFT convolution of the whole signal, relative to
+ *   ||h||_1 max|x| (tests/test_gpu_fir.py).
+ * - The spectrum scratch takes 16 (Bk + 1) bytes per block, lead blocks included: about 16 bytes per sample of every
+ *   utterance in partitioned mode.
+ * - jb_batch_read_pcm_native stays the vocoder's PCM.
+ * - Cost on 256 x 128 s at 48 kHz (profiles/r21_fir.txt, written by tools/fir_cost.py): 64 taps take 11.07 ms of device
+ *   time, 4,800 taps 39.24 ms, 24,000 taps 54.12 ms; the loudness measurement and apply pass of the same batch:
+ *   17.42 ms.  Partitioned mode's error is at most 1.72 times the float64 FFT convolution's over the test shapes of more
+ *   than one sample.
+ * Not covered: keeping the tail, resampling a response, time-varying responses, additive noise at an SNR, non-uniform
+ * partitions, serving a generator head early. */
+#define JB_FIR_MAX_TAPS 131072u
+#define JB_FIR_DIRECT_MAX 256u
+#define JB_FIR_DIRECT 0u
+#define JB_FIR_PARTITIONED 1u
+typedef struct jb_fir {
+    const double *taps; /* h[0..n_taps); NULL with n_taps 0: no response */
+    uint32_t n_taps;
+    uint32_t hz;        /* the rate the response was sampled at */
+    uint32_t delay;     /* d < n_taps */
+    uint32_t reserved;  /* 0 */
+} jb_fir;
+/* New (none).  f[0..n): one response for the batch (n == 1) or one per utterance (n == jb_batch_size); NULL, 0
+ * withdraws the request.  Before the first run only. */
+int jb_batch_set_fir(jb_batch *b, const jb_fir *f, size_t n);
+/* New (none).  The geometry of utterance utt's response: JB_FIR_DIRECT or _PARTITIONED, the outputs of a workgroup
+ * (the tile, or Bk) and the partitions (each may be NULL).  JB_ERR_INVALID where the utterance has no response. */
+int jb_batch_fir_geometry(const jb_batch *b, size_t utt, uint32_t *mode, uint32_t *block, uint32_t *partitions);
+/* New (none).  The same for a tap count in 1..JB_FIR_MAX_TAPS; pure. */
+int jb_fir_geometry(uint32_t n_taps, uint32_t *mode, uint32_t *block, uint32_t *partitions);
+/* New (none).  The host rule; no GPU is touched.  f->hz is not looked at beyond the request check; out must hold n
+ * samples (cap below that: JB_ERR_BUFFER) and must not overlap in.  A request without taps returns the input. */
+int jb_fir_host(const double *in, size_t n, const jb_fir *f, double *out, size_t cap);
+/* New (none).  The stage on PCM the caller holds (jb_filter_pcm_batch's twin), on `device` (-1 = current): utterance u
+ * is n_in[u] f64 samples at hz[u] under f[u] (taps NULL: the samples themselves); out[u] = its n_out[u] = n_in[u]
+ * samples, f64 or by the 16-bit sink's rule, library-owned (jb_fir_free each).  The same samples, response and delay
+ * give the same bits from this seam and from the batch path. */
+int jb_fir_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_fir *f, const uint32_t *hz,
+                     int32_t device, double **out, size_t *n_out);
+int jb_fir_pcm_batch_i16(const double *const *in, const size_t *n_in, size_t n, const jb_fir *f, const uint32_t *hz,
+                         int32_t device, int16_t **out, size_t *n_out);
+void jb_fir_free(void *p);
 
 /* ---- Limiter (new: the reference has no such control) --------------------------------------------------------------
  * A look-ahead peak limiter in the place of the loudness apply pass: a few peaks are taken down so that the rest can
@@ -1225,6 +1300,11 @@ uint32_t jb_engine_get_loudness_scope(const jb_engine *e);
  * at synthesis.  jb_engine_new copies it with the Condition. */
 int jb_engine_set_filter(jb_engine *e, const jb_filter *f);
 int jb_engine_get_filter(const jb_engine *e, jb_filter *out);
+/* New.  The impulse response of the audio the engine's entries return (see "Convolution"): wherever the engine's
+ * filter applies, in front of its sections (jb_batch_set_fir).  The taps are copied.  NULL or a request without taps
+ * (the default) = off: the output is unchanged.  Checked here at the engine's present output rate and again at
+ * synthesis.  jb_engine_new copies it with the Condition. */
+int jb_engine_set_fir(jb_engine *e, const jb_fir *f);
 /* New.  The limiter of the audio the engine's entries return (see "Limiter"): jb_synthesize, every
  * jb_synthesize_batch* and jb_synthesize_programme* form and _each* (each engine's own request for its utterance: not
  * among the fields the engines must agree on, except inside a per-request loudness group) ask the batch for it
@@ -1554,6 +1634,9 @@ JB_LAYOUT_ASSERT(sizeof(jb_loudness_group_report) == 96 && offsetof(jb_loudness_
 JB_LAYOUT_ASSERT(sizeof(jb_filter_section) == 72 && offsetof(jb_filter_section, f0_hz) == 8 &&
                      offsetof(jb_filter_section, gain_db) == 24 && offsetof(jb_filter_section, b0) == 32,
                  "jb_filter_section");
+JB_LAYOUT_ASSERT(sizeof(jb_fir) == 24 && offsetof(jb_fir, n_taps) == 8 && offsetof(jb_fir, hz) == 12 &&
+                     offsetof(jb_fir, delay) == 16 && offsetof(jb_fir, reserved) == 20,
+                 "jb_fir");
 JB_LAYOUT_ASSERT(sizeof(jb_filter) == 296 && offsetof(jb_filter, n_sections) == 288, "jb_filter");
 JB_LAYOUT_ASSERT(sizeof(jb_biquad) == 40 && offsetof(jb_biquad, a1) == 24, "jb_biquad");
 JB_LAYOUT_ASSERT(sizeof(jb_limiter_opts) == 32 && offsetof(jb_limiter_opts, max_reduction_db) == 16 &&

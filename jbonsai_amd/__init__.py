@@ -13,6 +13,7 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    JOIN_NONE, JoinUtt, join_geometry, join_host, join_ms_to_samples, join_pcm,
                    Filter, FilterSection, Biquad, filter_design, filter_sos, filter_pcm, filter_pcm_host, highpass,
                    lowpass, peaking, lowshelf, highshelf, notch, raw_filter, telephone_band, no_filter,
+                   Fir, fir, fir_geometry, fir_host, fir_pcm, FIR_MAX_TAPS, FIR_DIRECT_MAX, FIR_DIRECT, FIR_PARTITIONED,
                    LimiterOpts, LimiterReport, LIMITER_EXACT, LIMITER_OFF, limiter, no_limiter, limiter_window,
                    limiter_host, limiter_pcm,
                    FbankOpts, FBANK_HANN, FBANK_HAMMING, FBANK_CENTER, FBANK_LINEAR, FBANK_UNIT, FBANK_F64, fbank,
@@ -36,7 +37,8 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "LOUDNESS_PER_REQUEST", "JOIN_NONE", "JoinUtt", "join_geometry", "join_host", "join_ms_to_samples",
            "join_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",
            "filter_pcm_host", "highpass", "lowpass", "peaking", "lowshelf", "highshelf", "notch", "raw_filter",
-           "telephone_band", "no_filter", "LimiterOpts", "LimiterReport", "LIMITER_EXACT", "LIMITER_OFF", "limiter",
+           "telephone_band", "no_filter", "Fir", "fir", "fir_geometry", "fir_host", "fir_pcm", "FIR_MAX_TAPS",
+           "FIR_DIRECT_MAX", "FIR_DIRECT", "FIR_PARTITIONED", "LimiterOpts", "LimiterReport", "LIMITER_EXACT", "LIMITER_OFF", "limiter",
            "no_limiter", "limiter_window", "limiter_host", "limiter_pcm",
            "FbankOpts", "FBANK_HANN", "FBANK_HAMMING", "FBANK_CENTER", "FBANK_LINEAR", "FBANK_UNIT", "FBANK_F64", "fbank",
            "fbank_geometry", "fbank_window", "fbank_filterbank", "fbank_host", "fbank_pcm",

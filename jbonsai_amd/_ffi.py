@@ -343,6 +343,42 @@ def raw_filter(sos):
     return f
 
 
+FIR_MAX_TAPS, FIR_DIRECT_MAX, FIR_DIRECT, FIR_PARTITIONED = 131072, 256, 0, 1
+
+
+class Fir(C.Structure):
+    """jb_fir: an impulse response of n_taps f64 taps sampled at hz, and the delay d < n_taps its output is advanced by.
+    The object keeps its taps alive (`_taps`); the library copies them at every call that takes one."""
+    _fields_ = [("taps", C.POINTER(C.c_double)), ("n_taps", C.c_uint32), ("hz", C.c_uint32), ("delay", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+def fir(taps, hz: int, delay: int = 0):
+    """A Fir of `taps` (any sequence of floats; None: no response) at `hz`, advanced by `delay` samples."""
+    import numpy as np
+    f = Fir()
+    f.hz, f.delay = int(hz), int(delay)
+    if taps is not None:
+        f._taps = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+        f.taps = f._taps.ctypes.data_as(C.POINTER(C.c_double))
+        f.n_taps = f._taps.size
+    return f
+
+
+def fir_array(firs, n=None):
+    """A (Fir * n) array of Fir entries (None: no response); one entry stands for all n.  The array keeps the entries
+    (and so their taps) alive."""
+    fs = [firs] if isinstance(firs, Fir) or firs is None else list(firs)
+    if n is not None and len(fs) == 1:
+        fs = fs * n
+    arr = (Fir * max(1, len(fs)))()
+    for i, f in enumerate(fs):
+        if f is not None:
+            C.memmove(C.byref(arr[i]), C.byref(f), C.sizeof(Fir))
+    arr._keep = fs
+    return arr, len(fs)
+
+
 def filter_array(filters, n=None):
     """A (Filter * n) array of Filter entries (None: no sections); one entry stands for all n."""
     fs = [filters] if isinstance(filters, Filter) or filters is None else list(filters)
@@ -493,6 +529,8 @@ SYMBOLS = [
     "jb_join_pcm_batch_i16", "jb_join_free",
     "jb_batch_set_filter", "jb_batch_filter_coefficients", "jb_filter_design", "jb_filter_pcm_host",
     "jb_filter_pcm_batch", "jb_filter_pcm_batch_i16", "jb_filter_free", "jb_engine_set_filter", "jb_engine_get_filter",
+    "jb_batch_set_fir", "jb_batch_fir_geometry", "jb_engine_set_fir", "jb_fir_host", "jb_fir_geometry",
+    "jb_fir_pcm_batch", "jb_fir_pcm_batch_i16", "jb_fir_free",
     "jb_batch_set_limiter", "jb_batch_limiter_report", "jb_limiter_window", "jb_limiter_host", "jb_limiter_host_i16",
     "jb_limiter_pcm_batch", "jb_limiter_pcm_batch_i16", "jb_limiter_free", "jb_engine_set_limiter",
     "jb_engine_get_limiter",
@@ -773,6 +811,17 @@ def lib():
     L.jb_filter_free.restype = None
     L.jb_engine_set_filter.argtypes = [vp, flp]
     L.jb_engine_get_filter.argtypes = [vp, flp]
+    frp = C.POINTER(Fir)
+    L.jb_batch_set_fir.argtypes = [vp, frp, sz]
+    L.jb_batch_fir_geometry.argtypes = [vp, sz, u32p, u32p, u32p]
+    L.jb_engine_set_fir.argtypes = [vp, frp]
+    L.jb_fir_host.argtypes = [dp, sz, frp, dp, sz]
+    L.jb_fir_geometry.argtypes = [C.c_uint32, u32p, u32p, u32p]
+    L.jb_fir_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, frp, u32p, C.c_int32, C.POINTER(vp),
+                                   C.POINTER(sz)]
+    L.jb_fir_pcm_batch_i16.argtypes = L.jb_fir_pcm_batch.argtypes
+    L.jb_fir_free.argtypes = [vp]
+    L.jb_fir_free.restype = None
     lop, lrp = C.POINTER(LimiterOpts), C.POINTER(LimiterReport)
     L.jb_batch_set_limiter.argtypes = [vp, lop, sz]
     L.jb_batch_limiter_report.argtypes = [vp, sz, lrp]
@@ -1315,6 +1364,44 @@ def filter_pcm(pcms, filters, hz, device: int = -1, i16: bool = False):
     ns = (C.c_size_t * max(1, n))()
     check((L.jb_filter_pcm_batch_i16 if i16 else L.jb_filter_pcm_batch)(ins, nin, n, farr, hzs, device, outs, ns))
     return _take(L.jb_filter_free, outs, ns, n, np.int16 if i16 else np.float64)
+
+
+def fir_geometry(n_taps: int):
+    """jb_fir_geometry: (mode, block, partitions) of a response of n_taps taps -- FIR_DIRECT with the tile, or
+    FIR_PARTITIONED with Bk = n_fft / 2 and P = ceil(n_taps / Bk)."""
+    m, b, p = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().jb_fir_geometry(int(n_taps), C.byref(m), C.byref(b), C.byref(p)))
+    return m.value, b.value, p.value
+
+
+def fir_host(pcm, f):
+    """jb_fir_host: the host rule (no GPU), f64 in and out; f: a Fir, or None."""
+    import numpy as np
+    x = np.ascontiguousarray(pcm, dtype=np.float64)
+    y = np.empty_like(x)
+    dp = C.POINTER(C.c_double)
+    check(lib().jb_fir_host(x.ctypes.data_as(dp), x.size, C.byref(f if f is not None else Fir()),
+                            y.ctypes.data_as(dp), y.size))
+    return y
+
+
+def fir_pcm(pcms, firs, hz, device: int = -1, i16: bool = False):
+    """jb_fir_pcm_batch / _i16: the f64 utterances `pcms` convolved on the GPU, utterance u with firs[u] (a Fir, or
+    None) at hz[u]; one Fir or one rate stands for all.  f64 out, or int16 by the 16-bit sink's rule."""
+    import numpy as np
+    L = lib()
+    arrs, n, ins, nin = _pcm_args(pcms, np.float64, void=True)
+    farr, nf = fir_array(firs, n)
+    if nf != n:
+        raise ValueError("fir_pcm: one response, or one per utterance")
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("fir_pcm: one rate, or one per utterance")
+    hzs = (C.c_uint32 * max(1, n))(*rates)
+    outs = (C.c_void_p * max(1, n))()
+    ns = (C.c_size_t * max(1, n))()
+    check((L.jb_fir_pcm_batch_i16 if i16 else L.jb_fir_pcm_batch)(ins, nin, n, farr, hzs, device, outs, ns))
+    return _take(L.jb_fir_free, outs, ns, n, np.int16 if i16 else np.float64)
 
 
 def limiter_window(hz: int, opts=None):

@@ -375,6 +375,22 @@ class Batch:
         arr, n = F.filter_array(filters)
         F.check(self._L.jb_batch_set_filter(self._h, arr, n))
 
+    def set_fir(self, firs):
+        """jb_batch_set_fir: one F.Fir (J.fir(taps, hz, delay)) for the whole batch or one per utterance (None in a
+        list: no response); None withdraws the request.  Before the first run.  The convolution runs behind the
+        output rate and in front of the filter's sections; pcm_native stays the vocoder's PCM."""
+        if firs is None:
+            F.check(self._L.jb_batch_set_fir(self._h, None, 0))
+            return
+        arr, n = F.fir_array(firs)
+        F.check(self._L.jb_batch_set_fir(self._h, arr, n))
+
+    def fir_geometry(self, i):
+        """jb_batch_fir_geometry: (mode, block, partitions) of utterance i's response."""
+        m, b, p = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        F.check(self._L.jb_batch_fir_geometry(self._h, i, C.byref(m), C.byref(b), C.byref(p)))
+        return m.value, b.value, p.value
+
     def filter_coefficients(self, i) -> np.ndarray:
         """jb_batch_filter_coefficients: [n_sections, 5] (b0 b1 b2 a1 a2) of what the device runs for utterance i at
         its output rate; [0, 5] without a filter."""

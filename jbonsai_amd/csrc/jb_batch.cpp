@@ -2513,6 +2513,29 @@ int jb_batch_set_filter(jb_batch *hb, const jb_filter *f, size_t n)
     return hb ? ((Batch *)hb)->out.set_filter(f, n) : JB_ERR_INVALID;
 }
 
+int jb_batch_set_fir(jb_batch *hb, const jb_fir *f, size_t n)
+{
+    return hb ? ((Batch *)hb)->out.set_fir(f, n) : JB_ERR_INVALID;
+}
+
+int jb_batch_fir_geometry(const jb_batch *hb, size_t utt, uint32_t *mode, uint32_t *block, uint32_t *partitions)
+{
+    const Batch *b = (const Batch *)hb;
+    if (!b || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    jb::FirGeom g{};
+    const int rc = b->out.fir_geometry_of(utt, &g);
+    if (rc)
+        return rc;
+    if (mode)
+        *mode = g.mode;
+    if (block)
+        *block = g.block;
+    if (partitions)
+        *partitions = g.partitions;
+    return JB_OK;
+}
+
 int jb_batch_set_limiter(jb_batch *hb, const jb_limiter_opts *opts, size_t n)
 {
     return hb ? ((Batch *)hb)->out.set_limiter(opts, n) : JB_ERR_INVALID;

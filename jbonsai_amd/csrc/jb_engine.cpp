@@ -52,6 +52,9 @@ struct Condition {
     uint32_t peak_mode = JB_PEAK_SAMPLE; // jb_engine_set_peak_mode: what the ceiling bounds, with a target only
     uint32_t loudness_scope = JB_LOUDNESS_PER_UTTERANCE; // jb_engine_set_loudness_scope: what one gain covers
     jb_filter filter{};           // jb_engine_set_filter: n_sections 0 = off
+    std::vector<double> fir_taps; // jb_engine_set_fir: the response's taps, copied (empty = off) ...
+    uint32_t fir_hz = 0, fir_delay = 0; // ... its rate and delay
+    jb_fir fir() const { return jb_fir{fir_taps.empty() ? nullptr : fir_taps.data(), (uint32_t)fir_taps.size(), fir_hz, fir_delay, 0}; }
     bool limiter_on = false;      // jb_engine_set_limiter: a request is set ...
     jb_limiter_opts limiter{};    // ... and the request as it was given
     uint32_t tree_search = JB_SEARCH_HOST; // jb_engine_set_tree_search: where the per-label tree search runs
@@ -1110,6 +1113,25 @@ int jb_engine_set_filter(jb_engine *e, const jb_filter *f)
     ENG(e)->cond.filter = *f;
     return JB_OK;
 }
+int jb_engine_set_fir(jb_engine *e, const jb_fir *f)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    jb::Condition &c = ENG(e)->cond;
+    if (!f || (!f->taps && !f->n_taps && !f->reserved)) {
+        c.fir_taps.clear();
+        c.fir_hz = c.fir_delay = 0;
+        return JB_OK;
+    }
+    const size_t hz = c.output_rate ? c.output_rate : c.sampling_frequency;
+    int rc = jb::fir_check(f, (uint32_t)hz, 0, "jb_engine_set_fir");
+    if (rc)
+        return rc;
+    c.fir_taps.assign(f->taps, f->taps + f->n_taps);
+    c.fir_hz = f->hz;
+    c.fir_delay = f->delay;
+    return JB_OK;
+}
 int jb_engine_get_filter(const jb_engine *e, jb_filter *out)
 {
     if (!e || !out)
@@ -1649,6 +1671,15 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
         any_filter = any_filter || filters[u - lo].n_sections;
     }
     if (any_filter && (rc = out.set_filter(filters.data(), filters.size())))
+        return rc;
+    // the impulse response: each utterance's engine's own, the same way
+    std::vector<jb_fir> firs(hi - lo);
+    bool any_fir = false;
+    for (size_t u = lo; u < hi; u++) {
+        firs[u - lo] = eng(u)->cond.fir();
+        any_fir = any_fir || firs[u - lo].taps;
+    }
+    if (any_fir && (rc = out.set_fir(firs.data(), firs.size())))
         return rc;
     // loudness: each utterance's engine's own target and ceiling; an engine without a target leaves its
     // utterance as it is (measured, gain 0 dB: bit for bit the same) when another engine of the batch has one
@@ -2372,6 +2403,11 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     }
     if (CENG(e)->cond.filter.n_sections && (rc = b->out.set_filter(&CENG(e)->cond.filter, 1)))
         return rc;
+    if (!CENG(e)->cond.fir_taps.empty()) {
+        const jb_fir f = CENG(e)->cond.fir();
+        if ((rc = b->out.set_fir(&f, 1)))
+            return rc;
+    }
     if (!std::isnan(CENG(e)->cond.loudness_target)) {
         const double t = CENG(e)->cond.loudness_target, c = CENG(e)->cond.peak_ceiling;
         const uint32_t mode = CENG(e)->cond.peak_mode;

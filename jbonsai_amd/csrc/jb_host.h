@@ -5,6 +5,7 @@
 #include "jb_adpcm.h"
 #include "jb_fbank.h"
 #include "jb_filter.h"
+#include "jb_fir.h"
 #include "jb_format.h"
 #include "jb_limiter.h"
 #include "jb_loudness_rules.h"
@@ -333,6 +334,33 @@ int filter_launch_list(const std::vector<FilterClass> &classes, const std::vecto
 hipError_t launch_filter(const FilterClass *classes_dev, const FilterUtt *utts_dev, const FilterLaunch &l, double *st,
                          bool i16, hipStream_t stream);
 
+// The convolution stage (jb_fir.hip; the rule, FirClass and FirUtt: jb_fir.h; the host half: jb_fir.cpp).
+// f at the output rate `hz`: JB_OK, or JB_ERR_INVALID with set_error naming the utterance `utt` and the field
+int fir_check(const jb_fir *f, uint32_t hz, size_t utt, const char *who);
+// The distinct responses of a launch, by content (taps, delay, rate): their host copies
+struct FirClasses {
+    std::vector<FirResponse> resp;
+    uint32_t find(const FirSpec &f); // the class of an accepted request with taps (made at its first use)
+    size_t words() const;            // doubles of the device image of all tables
+    // the image (to be copied to `dev`, words() doubles) and the classes that point into it
+    void bind(const double *dev, std::vector<double> *image, std::vector<FirClass> *out) const;
+};
+// The partitions' spectra ([P][M + 1][2], scaled by 1 / M) and the twiddles ([M + 1][2]) of a partitioned response
+void fir_spectra(const FirResponse &r, std::vector<double> *H, std::vector<double> *tw);
+// The launch lists of the utterances `has` marks (and `only`, where not null): the direct ones and the partitioned
+// ones, each in utterance order with g0 filled in; tiles / blocks: their workgroups
+struct FirLaunch {
+    std::vector<FirUtt> direct, part;
+    uint64_t tiles = 0, blocks = 0, frames = 0; // frames: the partitioned list's spectra (jb_fir.h: fir_frames)
+};
+void fir_launch_lists(const std::vector<FirResponse> &resp, const std::vector<FirUtt> &utts,
+                      const std::vector<uint8_t> &has, const std::vector<uint8_t> *only, FirLaunch *out);
+// k_fir_direct over direct_dev[0..n_direct), k_fir_spectrum and k_fir_mac over part_dev[0..n_part); spec: the
+// spectrum scratch, 16 bytes per bin
+hipError_t launch_fir(const FirClass *classes_dev, const FirUtt *direct_dev, uint32_t n_direct, uint64_t tiles,
+                      const FirUtt *part_dev, uint32_t n_part, uint64_t blocks, uint64_t frames, double *spec,
+                      hipStream_t stream);
+
 // The limiter stage (jb_limiter.hip; the rules, LimiterClass and LimiterUtt: jb_limiter.h; the host half:
 // jb_limiter.cpp).  opts (null: the defaults) checked and resolved into *out (may be null), or JB_ERR_INVALID with
 // set_error naming the utterance `utt` and the field
@@ -547,6 +575,11 @@ struct OutputChain {
     // f[0..n): n == 1 or B filters (nullptr, 0: the request is withdrawn), each checked at its utterance's output
     // rate; set_output_rate checks the combined request again
     int set_filter(const jb_filter *f, size_t n);
+    // f[0..n): n == 1 or B responses (nullptr, 0: the request is withdrawn; taps == NULL: none for that utterance),
+    // each checked at its utterance's output rate and its taps copied; set_output_rate checks the rates again
+    int set_fir(const jb_fir *f, size_t n);
+    // the geometry of utterance u's response (JB_ERR_INVALID: it has none)
+    int fir_geometry_of(size_t u, FirGeom *g) const;
     // opts[0..n): n == 1 or B requests (nullptr, 0: the request is withdrawn); with groups, the members must agree
     int set_limiter(const jb_limiter_opts *opts, size_t n);
     int read_limiter(size_t u, jb_limiter_report *out); // after sync
@@ -619,6 +652,9 @@ private:
     std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
     std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
+    FirClasses fir_cls;                        // the distinct responses of the convolution request (its copies)
+    std::vector<int32_t> fir_of;               // [B] an utterance's response in fir_cls, -1: none; empty: no request
+    std::vector<uint8_t> stage_any;            // [B] 1 = a section or a response: the plan's filter flag
     std::vector<double> ln_target, ln_ceiling; // [B]
     std::vector<LimOpts> lim_req;              // [B] the limiter request, resolved; empty: none
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
@@ -642,7 +678,19 @@ private:
         const FilterLaunch *take = nullptr;  // of the next launch
         FilterClass *classes_dev = nullptr;
         double *st = nullptr;                // kFiltMaxD doubles per tile
+        std::vector<uint8_t> mine;           // [B] 0 = the convolution writes the stage's output alone; empty: all 1
     } fil;
+    struct Fir { // follows `measured`; in front of the filter's kernels
+        std::vector<FirUtt> host;            // [B] by utterance index
+        std::vector<uint8_t> has;            // [B] 1 = the utterance has a response
+        DevList<FirUtt> direct, part;        // the launch lists
+        FirLaunch all, sub;                  // of a run, of the last redo
+        uint64_t frames = 0;                 // the spectra of the next launch's partitioned list
+        FirClass *classes_dev = nullptr;
+        double *tables = nullptr;            // the classes' image
+        double *spec = nullptr;              // the spectrum scratch of the partitioned utterances
+        double *mid = nullptr;               // f64, the plan's geometry: what the sections read where an utterance has both
+    } fir;
     struct Loudness { // measurement and an utterance's report set: `measured`; the apply pass with groups: `post`
         DevList<LoudnessUtt> utts;             // [B]; total: the measurement's tiles
         DevList<LoudnessUtt> apply;            // what the apply pass takes: `utts`, or on a redo with groups a list
@@ -744,10 +792,13 @@ private:
                      const std::vector<uint32_t> &want, const char *who, LnGroups *out) const;
     int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
     int check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const;
+    int check_fir(const std::vector<uint32_t> &want, const char *who) const; // the responses' rates under `want`
+    void flag_stage(); // stage_any of the two requests
     int check_settable(const char *after_run) const;
     // the stages, in the order enqueue() runs them.  scope null: a full run
     int prepare_resample(), select_resample(const RedoScope *scope), launch_resample(bool redo);
     int prepare_filter(), select_filter(const RedoScope *scope), launch_filter(bool redo);
+    int prepare_fir(), select_fir(const RedoScope *scope), launch_fir(bool redo);
     int prepare_loudness(), select_loudness(const RedoScope *scope), launch_loudness(bool redo);
     int prepare_limiter(), select_limiter(const RedoScope *scope), launch_limiter(bool redo);
     int prepare_join(), select_join(const RedoScope *scope), launch_join(bool redo);

@@ -40,10 +40,14 @@ void OutputChain::replan()
     in.adpcm = ad_on;
     in.adpcm_align = ad_align;
     in.join = join_req.empty() ? nullptr : join_req.data();
-    in.filter = filt_any.empty() ? nullptr : filt_any.data();
+    flag_stage();
+    in.filter = stage_any.empty() ? nullptr : stage_any.data();
     in.fbank = fb_on ? &fb_p : nullptr;
     plan = plan_output(in);
 }
+
+// The plan's filter flag: an utterance has a section or a response (without a convolution request: filt_any itself)
+void OutputChain::flag_stage() { stage_any = fir_stage_flags(filt_any, fir_of); }
 
 // what every setter refuses
 int OutputChain::check_settable(const char *after_run) const
@@ -98,6 +102,7 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
     if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)) ||
         (rc = check_join(join_req, want, "jb_batch_set_output_rate")) ||
         (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")) ||
+        (rc = check_fir(want, "jb_batch_set_output_rate")) ||
         (fb_on && (rc = check_fbank(fb_p, want, "jb_batch_set_output_rate"))))
         return rc;
     want_hz = std::move(want);
@@ -386,6 +391,69 @@ int OutputChain::set_filter(const jb_filter *f, size_t n)
     return JB_OK;
 }
 
+// The convolution request under these rates: a response's rate is its utterance's output rate
+int OutputChain::check_fir(const std::vector<uint32_t> &want, const char *who) const
+{
+    const std::vector<uint32_t> hz = rates_under(want);
+    for (size_t u = 0; u < fir_of.size(); u++)
+        if (fir_of[u] >= 0 && fir_cls.resp[(size_t)fir_of[u]].hz != hz[u]) {
+            set_error(std::string(who) + ": utterance " + std::to_string(u) +
+                      ": hz of its impulse response differs from the utterance's output rate (a response is never "
+                      "resampled): " + std::to_string(fir_cls.resp[(size_t)fir_of[u]].hz) + " Hz against " +
+                      std::to_string(hz[u]) + " Hz");
+            return JB_ERR_INVALID;
+        }
+    return JB_OK;
+}
+
+int OutputChain::set_fir(const jb_fir *f, size_t n)
+{
+    int rc = check_settable("jb_batch_set_fir: the impulse response is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!f && n == 0) {
+        fir_cls = FirClasses{};
+        fir_of.clear();
+        replan();
+        return JB_OK;
+    }
+    const size_t B = (size_t)b.B;
+    if (!f || (n != 1 && n != B)) {
+        set_error("jb_batch_set_fir: give one response, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    const std::vector<uint32_t> hz = rates_under(want_hz);
+    for (size_t u = 0; u < B; u++)
+        if ((rc = fir_check(&f[n == 1 ? 0 : u], hz[u], u, "jb_batch_set_fir")))
+            return rc;
+    FirClasses cls; // (the taps are copied here: the caller's buffers are not read again)
+    std::vector<int32_t> of(B, -1);
+    bool any = false;
+    for (size_t u = 0; u < B; u++) {
+        const jb_fir &fu = f[n == 1 ? 0 : u];
+        if (!fu.taps)
+            continue;
+        of[u] = (int32_t)cls.find(*(const FirSpec *)&fu);
+        any = true;
+    }
+    if (!any)
+        of.clear();
+    fir_cls = std::move(cls);
+    fir_of = std::move(of);
+    replan();
+    return JB_OK;
+}
+
+int OutputChain::fir_geometry_of(size_t u, FirGeom *g) const
+{
+    if (u >= fir_of.size() || fir_of[u] < 0) {
+        set_error("jb_batch_fir_geometry: utterance " + std::to_string(u) + " has no impulse response");
+        return JB_ERR_INVALID;
+    }
+    *g = fir_cls.resp[(size_t)fir_of[u]].g;
+    return JB_OK;
+}
+
 // The limiter request `req` ([B], empty: none) under the groups `group` ([B], empty: none): the members of a group
 // agree on the options, else JB_ERR_INVALID naming the group and the field
 int OutputChain::check_limiter_groups(const std::vector<uint32_t> &group, const std::vector<LimOpts> &req,
@@ -461,7 +529,7 @@ int OutputChain::prepare()
     for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
-    if ((rc = prepare_resample()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
+    if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
         (rc = prepare_join()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
         (rc = prepare_fbank()))
@@ -487,14 +555,14 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         redo ? redo_scope(plan.prog_of, plan.units.size(), grouped() ? ln_groups : no_groups, *only) : RedoScope{};
     const RedoScope *scope = redo ? &of_redo : nullptr;
     int rc;
-    if ((rc = select_resample(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
+    if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
         (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
         (rc = select_adpcm(scope)) || (rc = select_fbank(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n))
         return JB_OK;
-    if ((rc = launch_resample(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
+    if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
         (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
         (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)))
         return rc;
@@ -592,9 +660,19 @@ int OutputChain::prepare_filter()
     std::vector<uint32_t> hz(B), cls_of;
     for (size_t u = 0; u < B; u++)
         hz[u] = plan.utt[u].hz;
-    int rc = filter_classes(filt_req.data(), B, hz.data(), B, &fil.classes, &cls_of, "jb_batch_set_filter");
+    // (with a convolution request alone every utterance is in the identity class)
+    const std::vector<jb_filter> none(filt_req.empty() ? B : 0, jb_filter{});
+    int rc = filter_classes(filt_req.empty() ? none.data() : filt_req.data(), B, hz.data(), B, &fil.classes, &cls_of,
+                            "jb_batch_set_filter");
     if (rc)
         return rc;
+    // behind a response the sections read the convolution's f64 (fir.mid); an utterance with a response and no section
+    // is the convolution's alone
+    if (!fir.has.empty()) {
+        fil.mine.assign(B, 1);
+        for (size_t u = 0; u < B; u++)
+            fil.mine[u] = !(fir.has[u] && fil.classes[cls_of[u]].ns == 0);
+    }
     fil.utts.host.assign(B, FilterUtt{});
     uint64_t tiles = 0;
     for (size_t u = 0; u < B; u++) {
@@ -604,10 +682,11 @@ int OutputChain::prepare_filter()
             set_error("filter: utterance " + std::to_string(u) + " is too long");
             return JB_ERR_UNSUPPORTED;
         }
-        fil.utts.host[u] = {src + o.off, dst + o.off * elem, o.n, tiles, 0, (uint32_t)nt, cls_of[u]};
+        const double *x = !fir.has.empty() && fir.has[u] && fil.mine[u] ? fir.mid : src;
+        fil.utts.host[u] = {x + o.off, dst + o.off * elem, o.n, tiles, 0, (uint32_t)nt, cls_of[u]};
         tiles += nt;
     }
-    if ((rc = filter_launch_list(fil.classes, fil.utts.host, nullptr, &fil.all)) ||
+    if ((rc = filter_launch_list(fil.classes, fil.utts.host, fil.mine.empty() ? nullptr : &fil.mine, &fil.all)) ||
         (rc = b.dalloc(&fil.classes_dev, fil.classes.size(), false)) || (rc = fil.utts.alloc(b, B, B)) ||
         (rc = b.dalloc(&fil.st, (size_t)tiles * kFiltMaxD, false)) ||
         (rc = upload_list(fil.classes_dev, fil.classes, "filter work list")))
@@ -622,7 +701,9 @@ int OutputChain::select_filter(const RedoScope *scope)
         return fil.utts.take_all();
     // by filter_launch_list, which also sorts and renumbers: a recursive filter carries a changed sample to the
     // utterance's end, so every touched utterance whole
-    const std::vector<uint8_t> &mask = scope->measured;
+    std::vector<uint8_t> mask = scope->measured;
+    for (size_t u = 0; u < fil.mine.size(); u++)
+        mask[u] = mask[u] && fil.mine[u];
     const int rc = filter_launch_list(fil.classes, fil.utts.host, &mask, &fil.sub);
     fil.take = &fil.sub;
     return rc ? rc : fil.utts.upload_redo(fil.sub.utts, kRedoLists);
@@ -635,6 +716,87 @@ int OutputChain::launch_filter(bool redo)
     const hipError_t e =
         jb::launch_filter(fil.classes_dev, fil.utts.list, *fil.take, fil.st, plan.filter.i16, b.stream_voc);
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "filter(redo)" : "filter");
+}
+
+// ---- the convolution: in the filter stage's place, in front of its sections.  An utterance with a response and no
+// section: the stage's input in, the stage's slab out; with both: out to an f64 slab of the chain's own, which the
+// sections then read.  The distinct responses' tables, the two launch lists and the spectrum scratch (16 bytes per bin,
+// Bk + 1 bins per block of Bk samples of every partitioned utterance)
+int OutputChain::prepare_fir()
+{
+    if (fir_of.empty() || !plan.filtered())
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    const double *src = (const double *)slab[(size_t)plan.filter_src];
+    char *dst = (char *)slab[(size_t)plan.filter.slab];
+    const size_t elem = plan.filter.i16 ? sizeof(int16_t) : sizeof(double);
+    fir.host.assign(B, FirUtt{});
+    fir.has.assign(B, 0);
+    bool both = false;
+    for (size_t u = 0; u < B; u++) {
+        fir.has[u] = fir_of[u] >= 0;
+        both = both || (fir.has[u] && !filt_any.empty() && filt_any[u]);
+    }
+    int rc;
+    if (both && (rc = b.dalloc(&fir.mid, (size_t)plan.total, false)))
+        return rc;
+    uint64_t bins = 0;
+    for (size_t u = 0; u < B; u++) {
+        if (!fir.has[u])
+            continue;
+        const OutUtt &o = plan.utt[u];
+        const FirGeom &g = fir_cls.resp[(size_t)fir_of[u]].g;
+        const bool mid = !filt_any.empty() && filt_any[u];
+        fir.host[u] = {src + o.off, mid ? (void *)(fir.mid + o.off) : (void *)(dst + o.off * elem), o.n, 0, 0, bins,
+                       (uint32_t)fir_of[u], mid ? 0u : (uint32_t)plan.filter.i16};
+        if (g.mode == kFirPartitioned)
+            bins += fir_frames(o.n, fir_cls.resp[(size_t)fir_of[u]].delay, g.block) * (g.block + 1);
+    }
+    fir_launch_lists(fir_cls.resp, fir.host, fir.has, nullptr, &fir.all);
+    if (fir.all.tiles > 0x7fffffffull || fir.all.frames > 0x7fffffffull) {
+        set_error("convolution: too many blocks for one launch");
+        return JB_ERR_UNSUPPORTED;
+    }
+    fir.direct.host = fir.all.direct;
+    fir.part.host = fir.all.part;
+    if ((rc = b.dalloc(&fir.classes_dev, fir_cls.resp.size(), false)) ||
+        (rc = b.dalloc(&fir.tables, fir_cls.words(), false)) || (bins && (rc = b.dalloc(&fir.spec, (size_t)(2 * bins), false))) ||
+        (rc = fir.direct.alloc(b, fir.direct.host.size(), fir.direct.host.size())) ||
+        (rc = fir.part.alloc(b, fir.part.host.size(), fir.part.host.size())))
+        return rc;
+    std::vector<double> image;
+    std::vector<FirClass> classes;
+    fir_cls.bind(fir.tables, &image, &classes);
+    if ((rc = upload_list(fir.tables, image, "convolution tables")) ||
+        (rc = upload_list(fir.classes_dev, classes, "convolution tables")) ||
+        (rc = fir.direct.upload("convolution work list")))
+        return rc;
+    return fir.part.upload("convolution work list");
+}
+
+int OutputChain::select_fir(const RedoScope *scope)
+{
+    if (fir.has.empty())
+        return JB_OK;
+    if (!scope) {
+        fir.frames = fir.all.frames;
+        fir.direct.take_all(fir.all.tiles);
+        return fir.part.take_all(fir.all.blocks);
+    }
+    // every touched utterance whole: a changed sample reaches K - 1 samples on, and the blocks behind it
+    fir_launch_lists(fir_cls.resp, fir.host, fir.has, &scope->measured, &fir.sub);
+    fir.frames = fir.sub.frames;
+    const int rc = fir.direct.upload_redo(fir.sub.direct, kRedoLists, fir.sub.tiles);
+    return rc ? rc : fir.part.upload_redo(fir.sub.part, kRedoLists, fir.sub.blocks);
+}
+
+int OutputChain::launch_fir(bool redo)
+{
+    if (fir.has.empty() || !(fir.direct.n || fir.part.n))
+        return JB_OK;
+    const hipError_t e = jb::launch_fir(fir.classes_dev, fir.direct.list, fir.direct.n, fir.direct.total, fir.part.list,
+                                        fir.part.n, fir.part.total, fir.frames, fir.spec, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "convolution(redo)" : "convolution");
 }
 
 // ---- loudness.  The per-rate tables and the utterance list: the measurement reads the f64 of the stage in front,

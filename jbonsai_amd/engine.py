@@ -160,6 +160,10 @@ class _Condition:
         """The output filter (an _ffi.Filter: J.highpass(70), J.telephone_band(), ...) of every entry's output, behind
         the output rate and in front of the loudness target; None (the default) = off."""
         F.check(self._L().jb_engine_set_filter(self._h(), None if f is None else C.byref(f)))
+    def set_fir(self, f):
+        """The impulse response (an _ffi.Fir: J.fir(taps, hz, delay)) of every entry's output, in front of the
+        filter's sections; None for none.  The taps are copied."""
+        F.check(self._L().jb_engine_set_fir(self._h(), None if f is None else C.byref(f)))
     def get_filter(self):
         f = F.Filter()
         F.check(self._L().jb_engine_get_filter(self._h(), C.byref(f)))
@@ -262,6 +266,10 @@ class Engine:
     def set_filter(self, f):
         """jb_engine_set_filter (the Condition's setter, on the engine): an _ffi.Filter, or None for none."""
         self.condition.set_filter(f)
+
+    def set_fir(self, f):
+        """jb_engine_set_fir (the Condition's setter, on the engine): an _ffi.Fir, or None for none."""
+        self.condition.set_fir(f)
 
     def get_filter(self):
         return self.condition.get_filter()
