@@ -6,10 +6,13 @@
 //                     generalized.rs:6-38, cepstrum.rs:69-103), mc2b, gnorm, x gamma (mod.rs:92-106,148-156)
 //   k_vocoder_mglsa   per sample: x *= c[0]; `stage` passes of dff (mglsa.rs:15-41); c += cinc (mod.rs:162-172)
 // Off every BASELINE configuration (the nitech voice has no GAMMA option: stage 0) and PARITY
-// UNPINNED -- no reference test reaches this branch; the CPU restatement it is tested against is held
-// by identities only (tests/).  Built for completeness of the drop-in, not
-// for speed: one thread per frame for the coefficients, one wave per time-chunk for the filter,
-// riding the chunk / hand-off check / redo machinery of the Stage::Zero kernels.
+// UNPINNED -- no reference test reaches this branch.  What holds it instead: the filter by
+// its transfer function (tests/test_gpu_mlsa_transfer.py), k_stage_coef by an extended-precision restatement of
+// the conversion checked against its closed forms and 50 digits (tests/coef_ref.py, tests/test_gpu_coef_ref.py:
+// within 1.2 x the CPU restatement's own distance from it at every order up to 35; above, the f64 conversion, the
+// reference's included, runs out of digits: 5e-6 off at n = 48, 2e-3 at 61, 2e-2 at 64).
+// Built for completeness of the drop-in, not for speed: one thread per frame for the coefficients, one wave
+// per time-chunk for the filter, riding the chunk / hand-off check / redo machinery of the Stage::Zero kernels.
 //
 // Filter mapping (lane = tap i, nmcp <= 64).  A dff pass updates d[i] += alpha * (d[i+1] - d[i-1]) in
 // ascending i with d[i-1] already updated: d'[i] = (d[i] + alpha d[i+1]) - alpha d'[i-1], a first-order
@@ -23,7 +26,7 @@
 
 namespace jb {
 
-constexpr int kSgMaxN = 64; // nmcp <= 64 (check_voice: <= 61)
+constexpr int kSgMaxN = 64; // nmcp <= 64 (check_voice: kMaxNmcp)
 
 // ---- per-frame coefficients: the reference's loops, one thread per frame ------------------------
 struct SgScratch {

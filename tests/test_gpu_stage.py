@@ -1,7 +1,11 @@
 """Stage::NonZero (GAMMA != 0 voices -- the spectrum stream holds [gain, LSP...], the
 synthesis filter is the MGLSA cascade; vocoder/mod.rs:90-107,142-176) on the GPU against the oracle's
 restatement.  PARITY UNPINNED: no reference test reaches this branch and no such voice exists here;
-the oracle side is held by the identities of tests/test_oracle_stage.py."""
+the oracle side is held by the identities of tests/test_oracle_stage.py and, for the coefficient
+conversion, by the extended-precision restatement of tests/coef_ref.py (tests/test_coef_ref.py), which
+tests/test_gpu_coef_ref.py holds k_stage_coef to as well: both parities of n, every branch of
+check_lsp_stability, under 4 x the oracle's own error (1e-15 at small orders, 6e-9 at n = 35).  The
+rtol 1e-6 below stays as the end-to-end contract against the oracle."""
 import numpy as np
 import pytest
 
