@@ -3,7 +3,7 @@
     python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
                                [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
-                               [--fbank OUT.npy] [--fir taps.npy [--fir-delay D]]
+                               [--fbank OUT.npy] [--mfcc OUT.npy] [--fir taps.npy [--fir-delay D]]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
 batch and joined on the GPU (Engine.synthesize_programme) in front of the encoder, so a .flac output is one stream whose
@@ -17,7 +17,8 @@ highest peak that many dB over the ceiling and a look-ahead limiter holds the ce
 one loud peak no longer holds the whole chapter under its target.  With --fbank the chapter's log-mel filterbank frames
 (25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are computed on the GPU from the joined programme, frames across
 the pauses and the seams included, and saved as a .npy file INSTEAD of the audio: a request has one sink, so no audio
-file is written (run again without --fbank for it; the cue list is the same).  The cue list -- each sentence's first sample and time within the chapter -- is printed.
+file is written (run again without --fbank for it; the cue list is the same).  --mfcc does the same with 13 liftered
+cepstra, delta and delta-delta rows, normalised in mean and variance over the whole chapter (float32 [T, 39]).  The cue list -- each sentence's first sample and time within the chapter -- is printed.
 Needs an MI355X: the library has no CPU path.
 """
 import argparse
@@ -45,6 +46,7 @@ ap.add_argument("--fir", default=None, metavar="taps.npy",
                 help="impulse response at the output rate (a 1-D .npy), convolved with every sentence on the GPU (Engine.set_fir)")
 ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
 ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="the chapter's log-mel filterbank frames from the GPU, instead of the audio")
+ap.add_argument("--mfcc", default=None, metavar="OUT.npy", help="the chapter's MFCC + deltas + CMVN rows from the GPU, instead of the audio")
 args = ap.parse_args()
 
 sentences = []
@@ -75,6 +77,12 @@ if args.fbank:
     feats, starts = engine.synthesize_programme(sentences, sink="fbank", **join)
     np.save(args.fbank, feats)
     print(f"wrote {args.fbank}: {feats.shape[0]} frames of {feats.shape[1]} log-mel values at {hz} Hz")
+elif args.mfcc:
+    import numpy as np
+
+    feats, starts = engine.synthesize_programme(sentences, sink="mfcc", delta_order=2, cmvn="mean_var", **join)
+    np.save(args.mfcc, feats)
+    print(f"wrote {args.mfcc}: {feats.shape[0]} frames of {feats.shape[1]} cepstral values at {hz} Hz")
 elif args.out.endswith(".flac"):
     data, starts = engine.synthesize_programme(sentences, sink="flac", md5=True, seek_interval_ms=1000, **join)
     with open(args.out, "wb") as f:

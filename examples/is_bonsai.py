@@ -2,7 +2,7 @@
 
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak] [--limiter DB]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
-                                 [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]]
+                                 [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]] [--mfcc OUT.npy [--rate HZ]]
                                  [--fir taps.npy [--fir-delay D]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
@@ -26,6 +26,8 @@ the output rate: the voice's, or --rate), advanced by --fir-delay samples (Engin
 loudness measurement and every encoder above.
 With --fbank the sentence's log-mel filterbank frames (25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are
 computed on the GPU from the final PCM, at --rate if given, and saved as a .npy file; no WAV file is written.
+With --mfcc the same frames go on, still on the GPU, to 13 liftered cepstra with delta and delta-delta rows, mean and
+variance normalised over the sentence (float32 [T, 39]), saved the same way.
 With --limiter (and --loudness) the gain may put the highest peak that many dB over the ceiling and a look-ahead limiter
 on the GPU holds the ceiling (Engine.set_limiter): the target is reached where the peak alone stood in the way.
 """
@@ -50,8 +52,9 @@ ap.add_argument("--format", choices=["f32", "s16", "s24", "ulaw", "alaw"], defau
                 help="sample format of the WAV file, converted on the GPU")
 ap.add_argument("--dither", action="store_true", help="TPDF dither (with --format s16 or s24)")
 ap.add_argument("--adpcm", action="store_true", help="IMA ADPCM (4-bit) WAV file, encoded on the GPU")
-ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm or --fbank)")
+ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm, --fbank or --mfcc)")
 ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="log-mel filterbank frames, computed on the GPU")
+ap.add_argument("--mfcc", default=None, metavar="OUT.npy", help="MFCC + deltas + CMVN rows, computed on the GPU")
 ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
 ap.add_argument("--fir", default=None, metavar="taps.npy", help="impulse response at the output rate, convolved on the GPU")
@@ -102,6 +105,16 @@ if args.fbank:
     np.save(args.fbank, feats)
     hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
     print(f"wrote {args.fbank}: {feats.shape[0]} frames of {feats.shape[1]} log-mel values at {hz} Hz")
+    sys.exit(0)
+if args.mfcc:
+    import numpy as np
+
+    if args.rate:
+        engine.condition.set_output_sampling_frequency(args.rate)
+    feats = engine.synthesize_mfcc(SAMPLE_SENTENCE_2, delta_order=2, cmvn="mean_var")
+    np.save(args.mfcc, feats)
+    hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
+    print(f"wrote {args.mfcc}: {feats.shape[0]} frames of {feats.shape[1]} cepstral values at {hz} Hz")
     sys.exit(0)
 if args.adpcm:
     if args.rate:

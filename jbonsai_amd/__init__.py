@@ -17,7 +17,9 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    LimiterOpts, LimiterReport, LIMITER_EXACT, LIMITER_OFF, limiter, no_limiter, limiter_window,
                    limiter_host, limiter_pcm,
                    FbankOpts, FBANK_HANN, FBANK_HAMMING, FBANK_CENTER, FBANK_LINEAR, FBANK_UNIT, FBANK_F64, fbank,
-                   fbank_geometry, fbank_window, fbank_filterbank, fbank_host, fbank_pcm)
+                   fbank_geometry, fbank_window, fbank_filterbank, fbank_host, fbank_pcm,
+                   MfccOpts, CMVN_NONE, CMVN_MEAN, CMVN_MEAN_VAR, MFCC_F64, mfcc, mfcc_geometry,
+                   mfcc_dct, mfcc_delta_kernel, mfcc_host, mfcc_pcm_host, mfcc_frames, mfcc_pcm)
 from .batch import (Batch, IndexStreamStates, IndexUtterance, PdfSet, StreamInfo, StreamStates, TrackUtterance,  # noqa: F401
                     Utterance, VoiceInfo, generator_from_tracks, mlpg_batch, paramgen_vocode_batch, vocode_tracks_batch,
                     vocoder_synthesize_batch)
@@ -42,4 +44,6 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "no_limiter", "limiter_window", "limiter_host", "limiter_pcm",
            "FbankOpts", "FBANK_HANN", "FBANK_HAMMING", "FBANK_CENTER", "FBANK_LINEAR", "FBANK_UNIT", "FBANK_F64", "fbank",
            "fbank_geometry", "fbank_window", "fbank_filterbank", "fbank_host", "fbank_pcm",
-           "synthesize_batch_each_fbank"]
+           "synthesize_batch_each_fbank",
+           "MfccOpts", "CMVN_NONE", "CMVN_MEAN", "CMVN_MEAN_VAR", "MFCC_F64", "mfcc", "mfcc_geometry",
+           "mfcc_dct", "mfcc_delta_kernel", "mfcc_host", "mfcc_pcm_host", "mfcc_frames", "mfcc_pcm"]

@@ -232,6 +232,42 @@ def fbank(win_ms: float = 25, hop_ms: float = 10, n_mels: int = 80, n_fft: int =
     return o
 
 
+CMVN_NONE, CMVN_MEAN, CMVN_MEAN_VAR = 0, 1, 2
+MFCC_F64 = 1
+
+
+class MfccOpts(C.Structure):
+    """jb_mfcc_opts: the cepstra kept (0: the log-mel energies themselves), the delta order and window, the CMVN mode
+    (CMVN_*), the lifter, the floor under the variance and MFCC_* flags."""
+    _fields_ = [("n_ceps", C.c_uint32), ("delta_order", C.c_uint32), ("delta_window", C.c_uint32),
+                ("cmvn", C.c_uint32), ("lifter", C.c_double), ("var_floor", C.c_double), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+    @property
+    def dtype(self):
+        import numpy as np
+
+        return np.dtype(np.float64 if self.flags & MFCC_F64 else np.float32)
+
+    def width(self, n_mels: int) -> int:
+        """Elements of a row behind a filterbank of n_mels filters."""
+        return (self.n_ceps or n_mels) * (self.delta_order + 1)
+
+
+def mfcc(n_ceps: int = 13, lifter: float = 22, delta_order: int = 0, delta_window: int = 2, cmvn="none",
+         var_floor: float = 0, f64: bool = False):
+    """MfccOpts: n_ceps liftered cepstra of the log-mel energies (0: the energies themselves; lifter 0: none), with
+    delta rows up to delta_order over windows of +-delta_window frames, normalised per unit: cmvn "none", "mean" or
+    "mean_var" (var_floor 0: 2^-52); f64: float64 elements instead of float32."""
+    o = MfccOpts()
+    o.n_ceps, o.delta_order, o.delta_window = int(n_ceps), int(delta_order), int(delta_window)
+    o.cmvn = ({"none": CMVN_NONE, "mean": CMVN_MEAN, "mean_var": CMVN_MEAN_VAR}[cmvn] if isinstance(cmvn, str)
+              else int(cmvn))
+    o.lifter, o.var_floor = float(lifter), float(var_floor)
+    o.flags = MFCC_F64 * bool(f64)
+    return o
+
+
 JOIN_NONE = 0xFFFFFFFF
 
 
@@ -520,6 +556,10 @@ SYMBOLS = [
     "jb_batch_read_fbank_all", "jb_fbank_geometry", "jb_fbank_window", "jb_fbank_filterbank", "jb_fbank_host",
     "jb_fbank_pcm_batch", "jb_fbank_free", "jb_synthesize_fbank", "jb_synthesize_batch_fbank",
     "jb_synthesize_batch_each_fbank", "jb_synthesize_programme_fbank",
+    "jb_mfcc_geometry", "jb_mfcc_dct", "jb_mfcc_delta_kernel", "jb_mfcc_host", "jb_mfcc_pcm_host",
+    "jb_mfcc_frames_batch", "jb_mfcc_pcm_batch", "jb_mfcc_free",
+    "jb_batch_set_mfcc", "jb_batch_mfcc_shape", "jb_batch_mfcc_size", "jb_batch_read_mfcc", "jb_batch_read_mfcc_all",
+    "jb_synthesize_mfcc", "jb_synthesize_batch_mfcc", "jb_synthesize_batch_each_mfcc", "jb_synthesize_programme_mfcc",
     "jb_batch_set_loudness_groups", "jb_batch_loudness_group_of", "jb_batch_loudness_group",
     "jb_batch_set_loudness_report", "jb_batch_loudness_r128", "jb_loudness_groups_pcm_batch",
     "jb_loudness_gate_host", "jb_engine_set_loudness_scope", "jb_engine_get_loudness_scope",
@@ -763,6 +803,32 @@ def lib():
                                      C.POINTER(sz)]
     L.jb_fbank_free.argtypes = [u8p]
     L.jb_fbank_free.restype = None
+    cop = C.POINTER(MfccOpts)
+    L.jb_mfcc_geometry.argtypes = [C.c_uint32, fop, cop, sz, C.POINTER(sz), u32p, C.POINTER(sz)]
+    L.jb_mfcc_dct.argtypes = [C.c_uint32, cop, vp, sz, vp, sz]
+    L.jb_mfcc_delta_kernel.argtypes = [C.c_uint32, C.c_uint32, vp, sz]
+    L.jb_mfcc_host.argtypes = [vp, sz, C.c_uint32, cop, vp, sz]
+    L.jb_mfcc_pcm_host.argtypes = [vp, sz, C.c_uint32, fop, cop, vp, sz]
+    L.jb_mfcc_frames_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, C.c_uint32, cop, C.c_int32, C.POINTER(u8p),
+                                       C.POINTER(sz)]
+    L.jb_mfcc_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, u32p, fop, cop, C.c_int32, C.POINTER(u8p),
+                                    C.POINTER(sz)]
+    L.jb_mfcc_free.argtypes = [u8p]
+    L.jb_mfcc_free.restype = None
+    L.jb_batch_set_mfcc.argtypes = [vp, fop, cop]
+    L.jb_batch_mfcc_shape.argtypes = [vp, sz, C.POINTER(sz), u32p, u32p]
+    L.jb_batch_mfcc_size.argtypes = [vp, sz, C.POINTER(sz)]
+    L.jb_batch_read_mfcc.argtypes = [vp, sz, vp, sz]
+    L.jb_batch_read_mfcc_all.argtypes = [vp, C.POINTER(vp)]
+    L.jb_synthesize_mfcc.argtypes = [vp, C.POINTER(C.c_char_p), sz, fop, cop, C.POINTER(u8p), C.POINTER(sz),
+                                     C.POINTER(sz)]
+    L.jb_synthesize_batch_mfcc.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, fop, cop,
+                                           C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_batch_each_mfcc.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
+                                                fop, cop, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_programme_mfcc.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, fop, cop,
+                                               C.POINTER(JoinOpts), C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz),
+                                               C.POINTER(C.c_uint64)]
     L.jb_synthesize_fbank.argtypes = [vp, C.POINTER(C.c_char_p), sz, fop, C.POINTER(u8p), C.POINTER(sz),
                                       C.POINTER(sz)]
     L.jb_synthesize_batch_fbank.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, fop,
@@ -1252,6 +1318,114 @@ def fbank_pcm(pcms, hz, opts: FbankOpts, device: int = -1):
     bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
     check(L.jb_fbank_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, bufs, ns))
     res = take_fbank(L, bufs, ns, n, opts)
+    return res[0] if single else res
+
+
+def mfcc_geometry(hz: int, fopts: FbankOpts, opts: MfccOpts, n: int = 0):
+    """jb_mfcc_geometry: (T, width, bytes) of n samples at hz."""
+    T, w, nby = C.c_size_t(), C.c_uint32(), C.c_size_t()
+    check(lib().jb_mfcc_geometry(hz, C.byref(fopts), C.byref(opts), n, C.byref(T), C.byref(w), C.byref(nby)))
+    return T.value, w.value, nby.value
+
+
+def mfcc_dct(n_mels: int, opts: MfccOpts):
+    """jb_mfcc_dct: (D [n_ceps, n_mels], lifter [n_ceps]) of the options behind n_mels filters."""
+    import numpy as np
+
+    D, l = np.empty((opts.n_ceps, n_mels), dtype=np.float64), np.empty(opts.n_ceps, dtype=np.float64)
+    check(lib().jb_mfcc_dct(n_mels, C.byref(opts), D.ctypes.data, D.size, l.ctypes.data, l.size))
+    return D, l
+
+
+def mfcc_delta_kernel(order: int, window: int):
+    """jb_mfcc_delta_kernel: s_order[-order * window .. order * window]."""
+    import numpy as np
+
+    s = np.empty(2 * max(order, 0) * max(window, 0) + 1, dtype=np.float64)
+    check(lib().jb_mfcc_delta_kernel(order, window, s.ctypes.data, s.size))
+    return s
+
+
+def mfcc_rows(data: bytes, opts: MfccOpts, n_mels: int):
+    """The bytes of a unit's rows as an ndarray [T, width]."""
+    import numpy as np
+
+    return np.frombuffer(data, dtype=opts.dtype).reshape(-1, opts.width(n_mels)).copy()
+
+
+def take_mfcc(L, bufs, ns, n, opts: MfccOpts, n_mels: int):
+    """ndarrays [T, width] of n library-owned outputs, each released with jb_mfcc_free."""
+    return [mfcc_rows(d, opts, n_mels) for d in _take(L.jb_mfcc_free, bufs, ns, n)]
+
+
+def mfcc_request(opts, fbank_opts, kw):
+    """(FbankOpts, MfccOpts) of a call that takes `opts` (MfccOpts, or None with the keywords of J.mfcc in kw) and
+    `fbank` (FbankOpts, a dict of J.fbank's keywords, or None: the defaults)."""
+    fo = fbank_opts if isinstance(fbank_opts, FbankOpts) else fbank(**(fbank_opts or {}))
+    return fo, (opts if opts is not None else mfcc(**kw))
+
+
+def mfcc_host(logmel, opts: MfccOpts):
+    """jb_mfcc_host: the rows [T, width] of float64 log-mel frames [T, n_mels], in plain C++ on the host (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(logmel, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("log-mel frames are [T, n_mels]")
+    T, n_mels = a.shape
+    nby = T * opts.width(n_mels) * opts.dtype.itemsize
+    out = np.empty(max(1, nby), dtype=np.uint8)
+    check(lib().jb_mfcc_host(a.ctypes.data, T, n_mels, C.byref(opts), out.ctypes.data, nby))
+    return mfcc_rows(out[:nby].tobytes(), opts, n_mels)
+
+
+def mfcc_pcm_host(pcm, hz: int, fopts: FbankOpts, opts: MfccOpts):
+    """jb_mfcc_pcm_host: the rows [T, width] of float64 samples in 16-bit scale, on the host (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    nby = mfcc_geometry(hz, fopts, opts, a.size)[2]
+    out = np.empty(max(1, nby), dtype=np.uint8)
+    check(lib().jb_mfcc_pcm_host(a.ctypes.data, a.size, hz, C.byref(fopts), C.byref(opts), out.ctypes.data, nby))
+    return mfcc_rows(out[:nby].tobytes(), opts, fopts.n_mels)
+
+
+def mfcc_frames(logmels, opts: MfccOpts, device: int = -1):
+    """jb_mfcc_frames_batch: the rows [T, width] of each float64 array [T, n_mels] of `logmels` (or of one array) on
+    the GPU."""
+    import numpy as np
+
+    single = isinstance(logmels, np.ndarray)
+    units = [np.ascontiguousarray(a, dtype=np.float64) for a in ([logmels] if single else logmels)]
+    if any(a.ndim != 2 for a in units) or len({a.shape[1] for a in units}) > 1:
+        raise ValueError("log-mel frames are [T, n_mels], with one n_mels for all")
+    n_mels = units[0].shape[1] if units else 1
+    arrs, n, ins, _ = _pcm_args(units, np.float64)
+    L = lib()
+    u8p = C.POINTER(C.c_uint8)
+    Ts = (C.c_size_t * max(n, 1))(*[a.shape[0] for a in units])
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    check(L.jb_mfcc_frames_batch(ins, Ts, n, n_mels, C.byref(opts), device, bufs, ns))
+    res = [mfcc_rows(d, opts, n_mels) for d in _take(L.jb_mfcc_free, bufs, ns, n)]
+    return res[0] if single else res
+
+
+def mfcc_pcm(pcms, hz, fopts: FbankOpts, opts: MfccOpts, device: int = -1):
+    """jb_mfcc_pcm_batch: the rows [T, width] of each float64 array of `pcms` (or of one array) on the GPU; hz: one
+    rate, or one per array."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    L = lib()
+    u8p = C.POINTER(C.c_uint8)
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    check(L.jb_mfcc_pcm_batch(ins, nin, n, hzs, C.byref(fopts), C.byref(opts), device, bufs, ns))
+    res = [mfcc_rows(d, opts, fopts.n_mels) for d in _take(L.jb_mfcc_free, bufs, ns, n)]
     return res[0] if single else res
 
 

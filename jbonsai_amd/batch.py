@@ -287,6 +287,7 @@ class Batch:
         self._h = h
         self._keep = keep
         self._fbank = None  # the filterbank request the batch holds (set_fbank)
+        self._mfcc = None   # the cepstral request the batch holds (set_mfcc): (FbankOpts, MfccOpts)
 
     def __len__(self):
         return self._L.jb_batch_size(self._h)
@@ -613,6 +614,48 @@ class Batch:
         arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
         F.check(self._L.jb_batch_read_fbank_all(self._h, arr))
         return [F.fbank_frames(b[:n].tobytes(), self._fbank) for b, n in zip(bufs, ns)]
+
+    def set_mfcc(self, opts=None, fbank=None, **kw):
+        """jb_batch_set_mfcc: the run also turns each utterance's (with a join: each programme's) final f64 PCM into
+        cepstral features on the GPU -- cepstra, deltas, CMVN -- behind a filterbank pass of their own.  opts:
+        F.MfccOpts (J.mfcc(...)), or the keywords of J.mfcc; fbank: F.FbankOpts or a dict of J.fbank's keywords (None:
+        the defaults) for the geometry.  None without keywords withdraws the request.  An f64 batch, before the first
+        run only; independent of set_fbank."""
+        if opts is None and not kw and fbank is None:
+            F.check(self._L.jb_batch_set_mfcc(self._h, None, None))
+            self._mfcc = None
+            return
+        fo, mo = F.mfcc_request(opts, fbank, kw)
+        F.check(self._L.jb_batch_set_mfcc(self._h, C.byref(fo), C.byref(mo)))
+        self._mfcc = (fo, mo)
+
+    def mfcc_shape(self, i):
+        """(T, width, hz) of unit i's rows (jb_batch_mfcc_shape)."""
+        T, w, hz = C.c_size_t(), C.c_uint32(), C.c_uint32()
+        F.check(self._L.jb_batch_mfcc_shape(self._h, i, C.byref(T), C.byref(w), C.byref(hz)))
+        return T.value, w.value, hz.value
+
+    def mfcc_size(self, i) -> int:
+        n = C.c_size_t()
+        F.check(self._L.jb_batch_mfcc_size(self._h, i, C.byref(n)))
+        return n.value
+
+    def read_mfcc(self, i):
+        """Unit i's rows, an ndarray [T, width] (jb_batch_mfcc_size + jb_batch_read_mfcc)."""
+        n = self.mfcc_size(i)
+        buf = np.empty(max(1, n), dtype=np.uint8)
+        F.check(self._L.jb_batch_read_mfcc(self._h, i, buf.ctypes.data, n))
+        return F.mfcc_rows(buf[:n].tobytes(), self._mfcc[1], self._mfcc[0].n_mels)
+
+    def read_mfcc_all(self):
+        """Every utterance's (with a join: every programme's) rows through one device-to-host copy
+        (jb_batch_read_mfcc_all)."""
+        B = self.num_outputs()
+        ns = [self.mfcc_size(i) for i in range(B)]
+        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
+        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
+        F.check(self._L.jb_batch_read_mfcc_all(self._h, arr))
+        return [F.mfcc_rows(b[:n].tobytes(), self._mfcc[1], self._mfcc[0].n_mels) for b, n in zip(bufs, ns)]
 
     def set_join(self, req):
         """jb_batch_set_join: one request per utterance -- F.JoinUtt entries, or (programme, pad_before, pad_after,

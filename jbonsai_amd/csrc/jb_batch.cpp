@@ -2721,7 +2721,7 @@ static int scatter_into(uint8_t *const *dst, const std::vector<jb::ByteSpan> &pl
     return JB_OK;
 }
 
-// jb_batch_read_{flac,formatted,adpcm,fbank}_all: the used bytes of the sink's slab in one copy, then every output's share
+// jb_batch_read_{flac,formatted,adpcm,fbank,mfcc}_all: the used bytes of the sink's slab in one copy, then every output's share
 static int read_bytes_all(jb_batch *hb, jb::SynthSink sink, uint8_t *const *dst)
 {
     Batch *b = (Batch *)hb;
@@ -2877,6 +2877,61 @@ int jb_batch_read_fbank(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
 }
 
 int jb_batch_read_fbank_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Fbank, dst); }
+
+int jb_batch_set_mfcc(jb_batch *hb, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts)
+{
+    if (!hb)
+        return JB_ERR_INVALID;
+    return ((Batch *)hb)->out.set_mfcc(fopts, opts);
+}
+
+int jb_batch_mfcc_shape(jb_batch *hb, size_t unit, size_t *T, uint32_t *width, uint32_t *hz)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || unit >= b->out.num_outputs())
+        return JB_ERR_INVALID;
+    const jb::OutMfccUtt *w = b->out.mfcc_place(unit);
+    if (!w)
+        return JB_ERR_INVALID;
+    if (T)
+        *T = (size_t)w->T;
+    if (width)
+        *width = w->width;
+    if (hz)
+        *hz = b->out.fbank_hz(unit);
+    return JB_OK;
+}
+
+int jb_batch_mfcc_size(jb_batch *hb, size_t unit, size_t *n_bytes)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !n_bytes || unit >= b->out.num_outputs())
+        return JB_ERR_INVALID;
+    const jb::OutMfccUtt *w = b->out.mfcc_place(unit);
+    if (!w)
+        return JB_ERR_INVALID;
+    *n_bytes = (size_t)w->bytes;
+    return JB_OK;
+}
+
+int jb_batch_read_mfcc(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || unit >= b->out.num_outputs())
+        return JB_ERR_INVALID;
+    const jb::OutMfccUtt *w = b->out.mfcc_place(unit);
+    if (!w)
+        return JB_ERR_INVALID;
+    if (cap < w->bytes) {
+        jb::set_error("jb_batch_read_mfcc: the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (!dst && w->bytes)
+        return JB_ERR_INVALID;
+    return b->out.read_mfcc(unit, dst);
+}
+
+int jb_batch_read_mfcc_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Mfcc, dst); }
 
 int jb_batch_set_join(jb_batch *hb, const jb_join_utt *req, size_t n)
 {

@@ -1724,6 +1724,8 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
         return rc;
     if (rq.sink == jb::SynthSink::Fbank && (rc = out.set_fbank(rq.fbank)))
         return rc;
+    if (rq.sink == jb::SynthSink::Mfcc && (rc = out.set_mfcc(rq.fbank, rq.mfcc)))
+        return rc;
     return JB_OK;
 }
 
@@ -1805,6 +1807,8 @@ int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
             rq.adpcm_samples[lo + p] = rq.join ? (size_t)b->out.programme(p).n : b->out.samples(p);
         for (size_t p = 0; rq.sink == jb::SynthSink::Fbank && rq.fbank_frames && p < places.size(); p++)
             rq.fbank_frames[lo + p] = (size_t)b->out.fbank_place(p)->T;
+        for (size_t p = 0; rq.sink == jb::SynthSink::Mfcc && rq.fbank_frames && p < places.size(); p++)
+            rq.fbank_frames[lo + p] = (size_t)b->out.mfcc_place(p)->T;
         return JB_OK;
     }
     if (rq.join) {
@@ -2242,6 +2246,55 @@ int jb_synthesize_adpcm(const jb_engine *e, const char *const *lines, size_t n, 
     return jb_synthesize_batch_adpcm(e, lines, off, 1, -1, opts, bytes, n_bytes, n_samples);
 }
 
+static jb::SynthRequest &request_mfcc(jb::SynthRequest &rq, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
+                                      size_t *n_frames)
+{
+    rq.sink = jb::SynthSink::Mfcc;
+    rq.i16 = false;
+    rq.fbank = fopts;
+    rq.mfcc = opts;
+    rq.fbank_frames = n_frames;
+    return rq;
+}
+
+// both option structs of a jb_synthesize*_mfcc call, before any device is touched
+static int check_mfcc_entry(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, const char *who)
+{
+    const int rc = jb::mfcc_check_fbank((const jb::FbankOpts *)fopts, who);
+    return rc ? rc : jb::mfcc_check_opts((const jb::MfccOpts *)opts, fopts->n_mels, who);
+}
+
+int jb_synthesize_batch_mfcc(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                             int32_t device, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, uint8_t **bytes,
+                             size_t *n_bytes, size_t *n_frames)
+{
+    const int rc = check_mfcc_entry(fopts, opts, "jb_synthesize_batch_mfcc");
+    if (rc)
+        return rc;
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return jb::synthesize_batch_impl(request_mfcc(rq, fopts, opts, n_frames));
+}
+
+int jb_synthesize_batch_each_mfcc(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
+                                  uint8_t **bytes, size_t *n_bytes, size_t *n_frames)
+{
+    const int rc = check_mfcc_entry(fopts, opts, "jb_synthesize_batch_each_mfcc");
+    if (rc)
+        return rc;
+    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return synthesize_each(engines, request_mfcc(rq, fopts, opts, n_frames));
+}
+
+int jb_synthesize_mfcc(const jb_engine *e, const char *const *lines, size_t n, const jb_fbank_opts *fopts,
+                       const jb_mfcc_opts *opts, uint8_t **bytes, size_t *n_bytes, size_t *n_frames)
+{
+    if (!bytes || !n_bytes)
+        return JB_ERR_INVALID;
+    size_t off[2] = {0, n};
+    return jb_synthesize_batch_mfcc(e, lines, off, 1, -1, fopts, opts, bytes, n_bytes, n_frames);
+}
+
 int jb_synthesize_batch_fbank(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                               int32_t device, const jb_fbank_opts *opts, uint8_t **bytes, size_t *n_bytes,
                               size_t *n_frames)
@@ -2361,6 +2414,18 @@ int jb_synthesize_programme_fbank(const jb_engine *e, const char *const *lines, 
         return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
     return jb::synthesize_batch_impl(request_join(request_fbank(rq, opts, n_frames), join, starts));
+}
+
+int jb_synthesize_programme_mfcc(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                 int32_t device, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
+                                 const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, size_t *n_frames,
+                                 uint64_t *starts)
+{
+    int rc = check_mfcc_entry(fopts, opts, "jb_synthesize_programme_mfcc");
+    if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_mfcc")))
+        return rc;
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return jb::synthesize_batch_impl(request_join(request_mfcc(rq, fopts, opts, n_frames), join, starts));
 }
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)

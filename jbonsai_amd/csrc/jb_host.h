@@ -10,6 +10,7 @@
 #include "jb_limiter.h"
 #include "jb_loudness_rules.h"
 #include "jb_md5.h"
+#include "jb_mfcc.h"
 #include "jb_output.h"
 #include "jb_pcm_call.h"
 
@@ -40,7 +41,7 @@ int noise_table(int device, size_t need, std::shared_ptr<NoiseDev> *out);
 void release_cached_memory(); // empties the per-device pools of finished batches' memory
 void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE_POOL_MB at start)
 // What an engine-level call hands out per utterance (or per programme): PCM, or the bytes of one of the encoders
-enum class SynthSink { Pcm, Flac, Formatted, Adpcm, Fbank };
+enum class SynthSink { Pcm, Flac, Formatted, Adpcm, Fbank, Mfcc };
 struct ByteSpan { // an output's place in the host copy of a byte sink's slab (OutputChain::read_bytes_all)
     uint64_t off, bytes;
 };
@@ -57,7 +58,7 @@ struct SynthRequest {
     unsigned host_threads = 0;               // 0: the default front-half thread count
     SynthSink sink = SynthSink::Pcm;
     bool i16 = false;                        // the batch's PCM in 16 bits (Pcm: what is handed out; Flac and Adpcm
-                                             // encode it) or in f64 (Formatted and Fbank read f64)
+                                             // encode it) or in f64 (Formatted, Fbank and Mfcc read f64)
     const jb_flac_opts *flac = nullptr;      // Flac: both may be null (the defaults; no MD5 / SEEKTABLE request)
     const jb_flac_meta *flac_meta = nullptr;
     const jb_format_opts *fmt = nullptr;     // Formatted
@@ -65,6 +66,7 @@ struct SynthRequest {
     size_t *adpcm_samples = nullptr;
     const jb_fbank_opts *fbank = nullptr;    // Fbank; fbank_frames[u] (may be null): the frames of output u
     size_t *fbank_frames = nullptr;
+    const jb_mfcc_opts *mfcc = nullptr;      // Mfcc: behind the filterbank options of `fbank`; fbank_frames as Fbank's
     const jb_join_opts *join = nullptr;      // jb_synthesize_programme*: all utterances are one programme, the one
     uint64_t *join_starts = nullptr;         // output; join_starts[u] (may be null): each member's first sample
     void **out = nullptr;                    // [n_utts], or [1] with a join: malloc'ed PCM or bytes of each output
@@ -298,6 +300,12 @@ struct FbankClasses {
 // utts_dev[0..n) of `groups` workgroups in all
 hipError_t launch_fbank(const FbankClass *classes_dev, const FbankUtt *utts_dev, uint32_t n, uint64_t groups,
                         hipStream_t stream);
+
+// Cepstral features (jb_mfcc.hip; the rule, MfccParams and MfccUtt: jb_mfcc.h; the host half: jb_mfcc.cpp):
+// utts_dev[0..n) of `tiles` frame tiles and `blocks` statistics blocks in all; k_ceps (with n_ceps), the statistics'
+// passes (with CMVN) and k_delta, in that order on `stream`
+hipError_t launch_mfcc(const MfccParams &P, const MfccUtt *utts_dev, uint32_t n, uint64_t tiles, uint64_t blocks,
+                       hipStream_t stream);
 
 // The join stage (jb_join.hip; the rules, JoinMember and JoinSpan: jb_join.h; the layout: jb_output.h)
 // join_layout with the request's reserved words checked and set_error naming what is wrong (JB_ERR_INVALID)
@@ -546,7 +554,7 @@ template <class T> struct DevList {
 // (jb_batch_set_filter), loudness (jb_batch_set_loudness_target, with peak mode, groups and the R128 report), the
 // join (jb_batch_set_join), then the encoders of the final PCM side by side: FLAC (jb_batch_set_flac, _flac_meta),
 // the sample format (jb_batch_set_format), IMA ADPCM (jb_batch_set_adpcm) and the filterbank features
-// (jb_batch_set_fbank) -- and all their device state.
+// (jb_batch_set_fbank) and the cepstral features (jb_batch_set_mfcc) -- and all their device state.
 // The setters record a request and plan again (jb_output.h); the first run carries the plan out (prepare); every run
 // enqueues the chain once behind the hand-off check, and finish_verify once more for the utterances its redo rounds
 // rewrote.  Each stage has the same three steps: prepare_X (its lists and scratch), select_X (what the next launch
@@ -572,6 +580,10 @@ struct OutputChain {
     // req[u]: utterance u's programme, pads and fades, n == B (nullptr, 0: the request is withdrawn); this setter and
     // set_output_rate check that a programme's members agree on the rate
     int set_join(const jb_join_utt *req, size_t n);
+    // the cepstral features behind a filterbank pass of their own (jb_mfcc.h): an f64 batch only; the filterbank
+    // options checked at every utterance's output rate (both NULL: the request is withdrawn); set_output_rate checks
+    // the combined request again.  Independent of set_fbank
+    int set_mfcc(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts);
     // f[0..n): n == 1 or B filters (nullptr, 0: the request is withdrawn), each checked at its utterance's output
     // rate; set_output_rate checks the combined request again
     int set_filter(const jb_filter *f, size_t n);
@@ -625,6 +637,9 @@ struct OutputChain {
     uint32_t fbank_mels() const { return fb_p.n_mels; }
     uint32_t fbank_hz(size_t u) const { return joined() ? plan.units[u].hz : plan.utt[u].hz; }
     int read_fbank(size_t u, uint8_t *dst);
+    // the cepstral rows: unit u's place, frames and width (known once the request is made; null without one), its bytes
+    const OutMfccUtt *mfcc_place(size_t u) const;
+    int read_mfcc(size_t u, uint8_t *dst);
     // every output of a byte sink: the used part of its slab in one copy, output u at host + places[u].off (FLAC:
     // the streams' sizes and places come from the device's index, one small copy first; the others' from the plan)
     int read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host);
@@ -649,6 +664,9 @@ private:
     uint32_t ad_align = 0;                     // its block_align (0: by the rate)
     bool fb_on = false;                        // filterbank features are requested
     FbankOpts fb_p{};
+    bool mf_on = false;                        // cepstral features are requested
+    FbankOpts mf_fb{};                         // their filterbank options, as the caller gave them
+    MfccOpts mf_p{};
     std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
     std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
@@ -753,6 +771,15 @@ private:
         uint64_t groups = 0;
         FbankClass *classes_dev = nullptr;
     } fb;
+    struct Mfcc { // follows `units`: the filterbank pass into the log-mel scratch, then the cepstral kernels
+        DevList<FbankUtt> futts;
+        DevList<MfccUtt> utts;                    // total: the frame tiles
+        std::vector<uint64_t> ngroups, ntiles, nblocks; // [U] each unit's filterbank workgroups, frame tiles, blocks
+        uint64_t groups = 0, tiles = 0, blocks = 0;
+        uint64_t take_blocks = 0;                 // the blocks of the next launch's list
+        FbankClass *classes_dev = nullptr;
+        MfccParams P{};
+    } mf;
     // the units the encoders take: the programmes in the join slab, or the utterances
     struct EncUnit {
         uint64_t off, n;
@@ -780,6 +807,8 @@ private:
     bool formatted() const { return plan.fmt_src != OutSlab::None; }
     bool adpcm() const { return plan.adpcm_src.slab != OutSlab::None; }
     bool fbank() const { return plan.fbank_src != OutSlab::None; }
+    bool mfcc() const { return plan.mfcc_src != OutSlab::None; }
+    int check_mfcc(const FbankOpts &fopts, const std::vector<uint32_t> &want, const char *who) const;
     int check_fbank(const FbankOpts &opts, const std::vector<uint32_t> &want, const char *who) const;
     void replan(); // host geometry and routing of the present requests
     // v[0..n), n == 1 or B, as [B] values; false (set_error(err)) for anything else
@@ -807,6 +836,7 @@ private:
     int prepare_format(), select_format(const RedoScope *scope), launch_format(bool redo);
     int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);
     int prepare_fbank(), select_fbank(const RedoScope *scope), launch_fbank(bool redo);
+    int prepare_mfcc(), select_mfcc(const RedoScope *scope), launch_mfcc(bool redo);
     int format_ready() const;
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
     int flac_ready() const;

@@ -146,6 +146,31 @@ OutPlan plan_output(const OutPlanIn &in)
             p.alloc[(size_t)OutSlab::Feat] = std::max<uint64_t>(bytes, 16);
         }
     }
+    // the cepstral features beside them, independent of a plain fbank request: the same final f64 through a filterbank
+    // pass of the stage's own into the f64 log-mel scratch, then rows of each unit's own length
+    if (in.mfcc && in.mfcc_fbank && !p.final.i16 && !mfcc_fbank_fault(*in.mfcc_fbank) &&
+        !mfcc_opts_fault(*in.mfcc, in.mfcc_fbank->n_mels)) {
+        const FbankOpts fo = mfcc_fbank_opts(*in.mfcc_fbank);
+        std::vector<OutMfccUtt> f(units.size());
+        uint64_t bytes = 0, words = 0;
+        bool ok = true;
+        for (size_t u = 0; u < units.size() && ok; u++) {
+            FbankGeom g{};
+            if (!(ok = fbank_geometry_quiet(fo, units[u].hz, &g)))
+                break;
+            const uint64_t T = fbank_frames(units[u].n, g.wl, g.hop, (fo.flags & kFbCenter) != 0);
+            const uint32_t width = mfcc_width(*in.mfcc, g.n_mels);
+            f[u] = {bytes, T * width * mfcc_elem(in.mfcc->flags), T, width, g.n_fft, words};
+            bytes += (f[u].bytes + 15) & ~(uint64_t)15;
+            words += (T * g.n_mels + 1) & ~(uint64_t)1;
+        }
+        if (ok) {
+            p.mfcc_src = enc.slab;
+            p.mfcc = std::move(f);
+            p.alloc[(size_t)OutSlab::MfccL] = std::max<uint64_t>(words, 2);
+            p.alloc[(size_t)OutSlab::Mfcc] = std::max<uint64_t>(bytes, 16);
+        }
+    }
     return p;
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "jb_fbank.h"
+#include "jb_mfcc.h"
 #include "jb_join.h"
 
 namespace jb {
@@ -33,11 +34,13 @@ enum class OutSlab : uint8_t {
     Join16,  // the same in 16 bits
     Filt64,  // f64 the filter stage writes
     Feat,    // bytes of the filterbank features
+    MfccL,   // f64 log-mel frames the cepstral stage makes for itself
+    Mfcc,    // bytes of the cepstral features
     Count
 };
 constexpr size_t out_slab_elem(OutSlab s) // bytes
 {
-    return s == OutSlab::Fmt || s == OutSlab::Adpcm || s == OutSlab::Feat      ? 1
+    return s == OutSlab::Fmt || s == OutSlab::Adpcm || s == OutSlab::Feat || s == OutSlab::Mfcc ? 1
            : s == OutSlab::S16 || s == OutSlab::New16 || s == OutSlab::Join16 ? 2
                                                                                : 8;
 }
@@ -61,6 +64,8 @@ struct OutPlanIn {
     const JoinUtt *join = nullptr;        // [B] the join request (jb_join.h); nullptr: none
     const uint8_t *filter = nullptr;      // [B] 1 = the utterance's filter has at least one section; nullptr: no request
     const FbankOpts *fbank = nullptr;     // the filterbank request (jb_fbank.h), checked at every output rate; nullptr: none
+    const FbankOpts *mfcc_fbank = nullptr; // the cepstral request (jb_mfcc.h): its filterbank's geometry (the stage forces
+    const MfccOpts *mfcc = nullptr;        // f64 logarithms itself) and its options; both or neither
 };
 
 struct OutUtt {
@@ -81,6 +86,14 @@ struct OutFbankUtt { // a unit's features in the feature slab
     uint64_t off, bytes;     // byte offset (16-byte aligned) and T * n_mels * bytes per element
     uint64_t T;              // its frames
     uint32_t wl, hop, n_fft; // its geometry, by its rate
+};
+
+struct OutMfccUtt { // a unit's cepstral rows in the Mfcc slab and its log-mel frames in the MfccL slab
+    uint64_t off, bytes; // byte offset (16-byte aligned) and T * width * bytes per element
+    uint64_t T;          // its frames
+    uint32_t width;      // elements of a row: d (delta_order + 1)
+    uint32_t n_fft;      // of its filterbank geometry, by its rate
+    uint64_t loff;       // its first log-mel value in the MfccL slab, in doubles (a 16-byte boundary)
 };
 
 struct OutUnit { // a programme in the join slab: what the encoders behind a join take for an utterance
@@ -114,8 +127,11 @@ struct OutPlan {
     std::vector<OutAdpcmUtt> adpcm;   // [B] with an ADPCM stage, else empty
     OutSlab fbank_src = OutSlab::None; // f64 the fbank stage reads: what `final` names (None: no request, or no f64)
     std::vector<OutFbankUtt> fbank;    // [B] with an fbank stage, else empty
+    OutSlab mfcc_src = OutSlab::None;  // f64 the cepstral stage reads: what fbank_src would name (None: no request)
+    std::vector<OutMfccUtt> mfcc;      // [B] with a cepstral stage, else empty
     // With a join request: the stage reads what `final` names and writes the programmes to a slab of its own; flac,
-    // fmt_src, adpcm_src and fbank_src then name that slab, and fmt, adpcm and fbank have [P] entries laid out from `units`
+    // fmt_src, adpcm_src, fbank_src and mfcc_src then name that slab, and fmt, adpcm, fbank and mfcc have [P] entries laid
+    // out from `units`
     OutWrite join_src, join;          // None: no join
     std::vector<OutUnit> units;       // [P] the programmes
     std::vector<uint32_t> prog_of;    // [B] each utterance's programme

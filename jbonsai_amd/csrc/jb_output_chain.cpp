@@ -43,6 +43,8 @@ void OutputChain::replan()
     flag_stage();
     in.filter = stage_any.empty() ? nullptr : stage_any.data();
     in.fbank = fb_on ? &fb_p : nullptr;
+    in.mfcc_fbank = mf_on ? &mf_fb : nullptr;
+    in.mfcc = mf_on ? &mf_p : nullptr;
     plan = plan_output(in);
 }
 
@@ -103,7 +105,8 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
         (rc = check_join(join_req, want, "jb_batch_set_output_rate")) ||
         (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")) ||
         (rc = check_fir(want, "jb_batch_set_output_rate")) ||
-        (fb_on && (rc = check_fbank(fb_p, want, "jb_batch_set_output_rate"))))
+        (fb_on && (rc = check_fbank(fb_p, want, "jb_batch_set_output_rate"))) ||
+        (mf_on && (rc = check_mfcc(mf_fb, want, "jb_batch_set_output_rate"))))
         return rc;
     want_hz = std::move(want);
     replan();
@@ -322,6 +325,40 @@ int OutputChain::set_fbank(const jb_fbank_opts *opts)
     return JB_OK;
 }
 
+// The cepstral request's filterbank under these rates, as the stage runs it (f64 logarithms)
+int OutputChain::check_mfcc(const FbankOpts &fopts, const std::vector<uint32_t> &want, const char *who) const
+{
+    return check_fbank(mfcc_fbank_opts(fopts), want, who);
+}
+
+int OutputChain::set_mfcc(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts)
+{
+    int rc;
+    const bool on = fopts || opts;
+    if (on && ((rc = mfcc_check_fbank((const FbankOpts *)fopts, "jb_batch_set_mfcc")) ||
+               (rc = mfcc_check_opts((const MfccOpts *)opts, fopts->n_mels, "jb_batch_set_mfcc"))))
+        return rc;
+    if (b.flags & JB_BATCH_MLPG_ONLY) {
+        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_UNSUPPORTED;
+    }
+    if (b.flags & JB_BATCH_PCM_I16) {
+        set_error("jb_batch_set_mfcc: the cepstral stage reads the f64 output (a batch without JB_BATCH_PCM_I16)");
+        return JB_ERR_UNSUPPORTED;
+    }
+    if ((rc = check_settable("jb_batch_set_mfcc: the features are set before the batch's first run")))
+        return rc;
+    if (on && (rc = check_mfcc(*(const FbankOpts *)fopts, want_hz, "jb_batch_set_mfcc")))
+        return rc;
+    mf_on = on;
+    if (on) {
+        mf_fb = *(const FbankOpts *)fopts;
+        mf_p = *(const MfccOpts *)opts;
+    }
+    replan();
+    return JB_OK;
+}
+
 // The join request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming what is wrong
 int OutputChain::check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const
 {
@@ -532,7 +569,7 @@ int OutputChain::prepare()
     if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
         (rc = prepare_join()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
-        (rc = prepare_fbank()))
+        (rc = prepare_fbank()) || (rc = prepare_mfcc()))
         return rc;
     if (plan.active()) {
         void *voc = slab[(size_t)plan.vocoder.slab];
@@ -547,7 +584,7 @@ int OutputChain::prepare()
 // uploaded (select_X) before its first launch, and one wait ends it
 int OutputChain::enqueue(const std::vector<uint8_t> *only)
 {
-    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || joined()))
+    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || mfcc() || joined()))
         return JB_OK;
     const bool redo = only != nullptr;
     static const LnGroups no_groups;
@@ -557,14 +594,14 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     int rc;
     if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
         (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
-        (rc = select_adpcm(scope)) || (rc = select_fbank(scope)))
+        (rc = select_adpcm(scope)) || (rc = select_fbank(scope)) || (rc = select_mfcc(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n || mf.utts.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
         (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
-        (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)))
+        (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)) || (rc = launch_mfcc(redo)))
         return rc;
     hipError_t e;
     if (redo && (e = hipStreamSynchronize(b.stream_voc)) != hipSuccess)
@@ -1303,6 +1340,114 @@ int OutputChain::launch_fbank(bool redo)
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_fbank(redo)" : "k_fbank");
 }
 
+// ---- the cepstral features beside them, of the same final f64, behind a filterbank pass of their own: k_fbank with
+// f64 logarithms forced into the log-mel scratch, then the cepstral kernels on the same stream.  The statics, the
+// block sums and the statistics are blocks of the stage's own, laid out by the full numbering
+int OutputChain::prepare_mfcc()
+{
+    if (!mfcc())
+        return JB_OK;
+    const std::vector<EncUnit> units = enc_units();
+    const size_t U = units.size();
+    const double *src = (const double *)slab[(size_t)plan.mfcc_src];
+    double *logmel = (double *)slab[(size_t)OutSlab::MfccL];
+    uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Mfcc];
+    const FbankOpts fo = mfcc_fbank_opts(mf_fb);
+    MfccTables tab;
+    mfcc_tables(mf_p, fo.n_mels, &tab);
+    mf.P = mfcc_params(mf_p, fo.n_mels, tab);
+    const uint32_t d = mf.P.d;
+    FbankClasses cls;
+    mf.futts.host.assign(U, FbankUtt{});
+    mf.utts.host.assign(U, MfccUtt{});
+    mf.ngroups.assign(U, 0);
+    mf.ntiles.assign(U, 0);
+    mf.nblocks.assign(U, 0);
+    mf.groups = mf.tiles = mf.blocks = 0;
+    uint64_t frames = 0;
+    int rc;
+    for (size_t u = 0; u < U; u++) {
+        const OutMfccUtt &pl = plan.mfcc[u];
+        FbankUtt &f = mf.futts.host[u];
+        if ((rc = cls.find(fo, units[u].hz, "jb_batch_set_mfcc", &f.cls)))
+            return rc;
+        f.x = src + units[u].off;
+        f.y = (uint8_t *)(logmel + pl.loff);
+        f.n = units[u].n;
+        f.T = pl.T;
+        f.g0 = mf.groups;
+        const uint32_t per = fbank_wg_frames(pl.n_fft);
+        mf.ngroups[u] = (f.T + per - 1) / per;
+        mf.groups += mf.ngroups[u];
+        MfccUtt &w = mf.utts.host[u];
+        w.L = logmel + pl.loff;
+        w.y = dst + pl.off;
+        w.T = pl.T;
+        w.g0 = mf.tiles;
+        w.b0 = mf.blocks;
+        w.r_T = mfcc_r(pl.T);
+        mf.ntiles[u] = mfcc_tiles(pl.T);
+        mf.nblocks[u] = mfcc_blocks(pl.T);
+        mf.tiles += mf.ntiles[u];
+        mf.blocks += mf.nblocks[u];
+        frames += pl.T;
+    }
+    double *tables = nullptr, *statics = nullptr, *bs = nullptr, *stat = nullptr, *dct = nullptr, *lift = nullptr;
+    if ((rc = b.dalloc(&tables, cls.words(), false)) || (rc = b.dalloc(&bs, mf.blocks * d, false)) ||
+        (rc = b.dalloc(&stat, 2 * U * d, false)) || (rc = b.dalloc(&dct, tab.Dt.size(), false)) ||
+        (rc = b.dalloc(&lift, tab.lift.size(), false)) ||
+        (mf_p.n_ceps && (rc = b.dalloc(&statics, frames * d, false))))
+        return rc;
+    uint64_t at = 0;
+    for (size_t u = 0; u < U; u++) {
+        MfccUtt &w = mf.utts.host[u];
+        w.c = mf_p.n_ceps ? statics + at * d : const_cast<double *>(w.L);
+        w.bs = bs + w.b0 * d;
+        w.stat = stat + 2 * u * d;
+        at += w.T;
+    }
+    mf.P.Dt = dct;
+    mf.P.lift = lift;
+    std::vector<double> image;
+    std::vector<FbankClass> classes;
+    cls.bind(fo, tables, &image, &classes);
+    if ((rc = upload_list(tables, image, "mfcc filterbank tables")) || (rc = upload_list(dct, tab.Dt, "mfcc DCT")) ||
+        (rc = upload_list(lift, tab.lift, "mfcc lifter")) || (rc = b.dalloc(&mf.classes_dev, classes.size(), false)) ||
+        (rc = upload_list(mf.classes_dev, classes, "mfcc filterbank classes")) || (rc = mf.futts.alloc(b, U, U)) ||
+        (rc = mf.utts.alloc(b, U, U)) || (rc = mf.futts.upload("mfcc filterbank work list")))
+        return rc;
+    return mf.utts.upload("mfcc work list");
+}
+
+int OutputChain::select_mfcc(const RedoScope *scope)
+{
+    if (!mfcc() || !scope) {
+        mf.take_blocks = mf.blocks;
+        mf.futts.take_all(mf.groups);
+        return mf.utts.take_all(mf.tiles);
+    }
+    // `units`: every unit whose final PCM changed, recomputed whole -- its statistics run over all its frames; the
+    // lists are renumbered, the scratch stays where the full numbering put it (the units' pointers)
+    const Picked pg = pick_renumbered(scope->units, mf.ngroups);
+    const Picked pt = pick_renumbered(scope->units, mf.ntiles), pb = pick_renumbered(scope->units, mf.nblocks);
+    std::vector<MfccUtt> sub = renumbered(mf.utts.host, pt, &MfccUtt::g0);
+    for (size_t i = 0; i < sub.size(); i++)
+        sub[i].b0 = pb.base[i];
+    mf.take_blocks = pb.total;
+    const int rc = mf.futts.upload_redo(renumbered(mf.futts.host, pg, &FbankUtt::g0), kRedoLists, pg.total);
+    return rc ? rc : mf.utts.upload_redo(sub, kRedoLists, pt.total);
+}
+
+int OutputChain::launch_mfcc(bool redo)
+{
+    if (!mfcc() || (redo && !mf.utts.n))
+        return JB_OK;
+    hipError_t e = jb::launch_fbank(mf.classes_dev, mf.futts.list, mf.futts.n, mf.futts.total, b.stream_voc);
+    if (e == hipSuccess)
+        e = jb::launch_mfcc(mf.P, mf.utts.list, mf.utts.n, mf.utts.total, mf.take_blocks, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "mfcc(redo)" : "mfcc");
+}
+
 int OutputChain::check_ready(bool requested, const char *not_run, const char *not_set) const
 {
     if (requested && ready)
@@ -1440,6 +1585,24 @@ int OutputChain::read_fbank(size_t u, uint8_t *dst)
     return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Feat] + w.off, dst, (size_t)w.bytes) : b.sync();
 }
 
+const OutMfccUtt *OutputChain::mfcc_place(size_t u) const
+{
+    if (!mf_on) {
+        set_error("mfcc: jb_batch_set_mfcc was not called");
+        return nullptr;
+    }
+    return &plan.mfcc[u];
+}
+
+int OutputChain::read_mfcc(size_t u, uint8_t *dst)
+{
+    int rc = check_ready(mf_on, "mfcc: the batch has not run", "mfcc: jb_batch_set_mfcc was not called");
+    if (rc)
+        return rc;
+    const OutMfccUtt &w = plan.mfcc[u];
+    return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Mfcc] + w.off, dst, (size_t)w.bytes) : b.sync();
+}
+
 int OutputChain::format_ready() const
 {
     return check_ready(fmt_on, "format: the batch has not run", "format: jb_batch_set_format was not called");
@@ -1472,6 +1635,8 @@ int OutputChain::read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, s
                  ? check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called")
              : sink == SynthSink::Fbank
                  ? check_ready(fb_on, "fbank: the batch has not run", "fbank: jb_batch_set_fbank was not called")
+             : sink == SynthSink::Mfcc
+                 ? check_ready(mf_on, "mfcc: the batch has not run", "mfcc: jb_batch_set_mfcc was not called")
                  : JB_ERR_INVALID;
     if (rc)
         return rc;
@@ -1487,8 +1652,12 @@ int OutputChain::read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, s
     for (size_t u = 0; u < places->size(); u++)
         (*places)[u] = sink == SynthSink::Formatted ? ByteSpan{plan.fmt[u].off, plan.fmt[u].bytes}
                        : sink == SynthSink::Fbank   ? ByteSpan{plan.fbank[u].off, plan.fbank[u].bytes}
+                       : sink == SynthSink::Mfcc    ? ByteSpan{plan.mfcc[u].off, plan.mfcc[u].bytes}
                                                     : ByteSpan{plan.adpcm[u].off, plan.adpcm[u].bytes};
-    const OutSlab from = sink == SynthSink::Formatted ? OutSlab::Fmt : sink == SynthSink::Fbank ? OutSlab::Feat : OutSlab::Adpcm;
+    const OutSlab from = sink == SynthSink::Formatted ? OutSlab::Fmt
+                         : sink == SynthSink::Fbank   ? OutSlab::Feat
+                         : sink == SynthSink::Mfcc    ? OutSlab::Mfcc
+                                                      : OutSlab::Adpcm;
     return read_used(slab[(size_t)from], used_bytes(*places), true, host);
 }
 

@@ -522,14 +522,37 @@ class Engine:
         F.check(self._L.jb_synthesize_batch_fbank(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns, nf))
         return F.take_fbank(self._L, bufs, ns, B, opts)
 
+    def synthesize_mfcc(self, labels: Sequence[str], opts=None, fbank=None, **kw) -> np.ndarray:
+        """jb_synthesize_mfcc: the cepstral features [T, width] of what synthesize(labels) returns, computed on the GPU.
+        opts: F.MfccOpts, or the keywords of J.mfcc; fbank: F.FbankOpts or a dict of J.fbank's keywords."""
+        fo, mo = F.mfcc_request(opts, fbank, kw)
+        buf, n, nf = C.POINTER(C.c_uint8)(), C.c_size_t(), C.c_size_t()
+        F.check(self._L.jb_synthesize_mfcc(self._h, _lines(labels), len(labels), C.byref(fo), C.byref(mo),
+                                           C.byref(buf), C.byref(n), C.byref(nf)))
+        return F.take_mfcc(self._L, [buf], [n.value], 1, mo, fo.n_mels)[0]
+
+    def synthesize_mfcc_batch(self, utterances: Sequence[Sequence[str]], opts=None, fbank=None, device: int = -1,
+                              **kw) -> List[np.ndarray]:
+        """jb_synthesize_batch_mfcc: each utterance of synthesize_batch(...) as cepstral features."""
+        fo, mo = F.mfcc_request(opts, fbank, kw)
+        flat = [l for u in utterances for l in u]
+        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
+        B = len(utterances)
+        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+        bufs, ns, nf = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
+        F.check(self._L.jb_synthesize_batch_mfcc(self._h, _lines(flat), offs, B, device, C.byref(fo), C.byref(mo),
+                                                 bufs, ns, nf))
+        return F.take_mfcc(self._L, bufs, ns, B, mo, fo.n_mels)
+
     def synthesize_programme(self, utterances: Sequence[Sequence[str]], sink: str = "f64", lead_ms: float = 0.0,
                              gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0, device: int = -1,
                              **sink_opts):
         """jb_synthesize_programme*: the utterances as ONE programme -- lead_ms of zeros, the first utterance, gap_ms,
         the next, ..., trail_ms, a fade of fade_ms at both edges of each -- joined on the GPU in front of the sink.
         sink: "f64" or "i16" (PCM arrays), "flac" (bytes; block_size, max_lpc_order, md5, seek_interval_ms),
-        "formatted" (bytes; fmt, dither, seed), "adpcm" (an AdpcmStream; block_align) or "fbank" (an ndarray
-        [T, n_mels]; opts=F.FbankOpts or the keywords of J.fbank).  Returns (output, starts):
+        "formatted" (bytes; fmt, dither, seed), "adpcm" (an AdpcmStream; block_align), "fbank" (an ndarray
+        [T, n_mels]; opts=F.FbankOpts or the keywords of J.fbank) or "mfcc" (an ndarray [T, width]; opts=F.MfccOpts or
+        the keywords of J.mfcc, fbank=F.FbankOpts or a dict of J.fbank's keywords).  Returns (output, starts):
         starts[u] is utterance u's first sample within the programme."""
         flat = [l for u in utterances for l in u]
         off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
@@ -580,7 +603,13 @@ class Engine:
             F.check(L.jb_synthesize_programme_fbank(self._h, _lines(flat), offs, B, device, C.byref(opts),
                                                     C.byref(join), C.byref(buf), C.byref(n), C.byref(nf), starts))
             return F.take_fbank(L, [buf], [n.value], 1, opts)[0], list(starts[:B])
-        raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm" or "fbank"')
+        if sink == "mfcc":
+            fo, mo = F.mfcc_request(sink_opts.pop("opts", None), sink_opts.pop("fbank", None), sink_opts)
+            nf = C.c_size_t()
+            F.check(L.jb_synthesize_programme_mfcc(self._h, _lines(flat), offs, B, device, C.byref(fo), C.byref(mo),
+                                                   C.byref(join), C.byref(buf), C.byref(n), C.byref(nf), starts))
+            return F.take_mfcc(L, [buf], [n.value], 1, mo, fo.n_mels)[0], list(starts[:B])
+        raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm", "fbank" or "mfcc"')
 
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
