@@ -4,6 +4,7 @@
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
                                [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
                                [--fbank OUT.npy] [--mfcc OUT.npy] [--fir taps.npy [--fir-delay D]]
+                               [--noise bed.npy|white --snr DB]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
 batch and joined on the GPU (Engine.synthesize_programme) in front of the encoder, so a .flac output is one stream whose
@@ -12,7 +13,9 @@ written as a 16-bit WAV file.  With --loudness the chapter gets ONE gain (per-re
 keep their relative levels.  With --highpass a rumble and DC high-pass at that corner runs on the GPU in front of the
 loudness measurement and the encoder (Engine.set_filter).  With --fir every sentence is convolved on the GPU with the impulse
 response in that .npy file (taps at the output rate; --fir-delay removes its leading latency), in front of --highpass
-(Engine.set_fir).  With --limiter (and --loudness) the chapter's gain may put its
+(Engine.set_fir).  With --noise every sentence gets background noise at --snr dB on the GPU, behind --fir and in front
+of --highpass: the looped samples of that .npy file (at the output rate) or "white", every sentence from a place of
+its own in the bed (Engine.set_noise with vary=True); the pads between the sentences stay silent.  With --limiter (and --loudness) the chapter's gain may put its
 highest peak that many dB over the ceiling and a look-ahead limiter holds the ceiling on the GPU (Engine.set_limiter), so
 one loud peak no longer holds the whole chapter under its target.  With --fbank the chapter's log-mel filterbank frames
 (25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are computed on the GPU from the joined programme, frames across
@@ -42,6 +45,9 @@ ap.add_argument("--limiter", type=float, default=None, metavar="DB",
                 help="look-ahead limiter: the gain may put the highest peak this far over the ceiling (with --loudness)")
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner (50 to 80 Hz removes rumble and DC)")
+ap.add_argument("--noise", default=None, metavar="bed.npy|white",
+                help="background noise added to every sentence on the GPU at --snr (Engine.set_noise)")
+ap.add_argument("--snr", type=float, default=15.0, metavar="DB", help="speech power over added-noise power")
 ap.add_argument("--fir", default=None, metavar="taps.npy",
                 help="impulse response at the output rate (a 1-D .npy), convolved with every sentence on the GPU (Engine.set_fir)")
 ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
@@ -61,6 +67,11 @@ if args.fir is not None:
     import numpy as np
 
     engine.set_fir(J.fir(np.load(args.fir), args.rate or engine.condition.get_sampling_frequency(), args.fir_delay))
+if args.noise is not None:
+    import numpy as np
+
+    engine.set_noise(J.noise(None if args.noise == "white" else np.load(args.noise),
+                             args.rate or engine.condition.get_sampling_frequency(), args.snr, vary=True))
 if args.highpass is not None:
     engine.set_filter(J.highpass(args.highpass))
 if args.loudness is not None:

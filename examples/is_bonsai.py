@@ -3,7 +3,7 @@
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak] [--limiter DB]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
                                  [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]] [--mfcc OUT.npy [--rate HZ]]
-                                 [--fir taps.npy [--fir-delay D]]
+                                 [--fir taps.npy [--fir-delay D]] [--noise bed.npy|white --snr DB [--snr-active]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
@@ -24,6 +24,10 @@ output rate and in front of the loudness measurement and every encoder above.
 With --fir the audio is convolved on the GPU with the impulse response in that .npy file (a 1-D array of taps sampled at
 the output rate: the voice's, or --rate), advanced by --fir-delay samples (Engine.set_fir): in front of --highpass, the
 loudness measurement and every encoder above.
+With --noise background noise is added on the GPU at --snr dB (Engine.set_noise): the samples of that .npy file (a 1-D
+array at the output rate, 16-bit units, looped) or, with "white", noise generated on the device; --snr-active measures
+the speech over its active tiles (within 20 dB of the mean power), not over the leading and trailing silence.  Behind
+--fir, in front of --highpass, the loudness measurement and every encoder above.
 With --fbank the sentence's log-mel filterbank frames (25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are
 computed on the GPU from the final PCM, at --rate if given, and saved as a .npy file; no WAV file is written.
 With --mfcc the same frames go on, still on the GPU, to 13 liftered cepstra with delta and delta-delta rows, mean and
@@ -59,6 +63,9 @@ ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SE
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
 ap.add_argument("--fir", default=None, metavar="taps.npy", help="impulse response at the output rate, convolved on the GPU")
 ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
+ap.add_argument("--noise", default=None, metavar="bed.npy|white", help="background noise, added on the GPU at --snr")
+ap.add_argument("--snr", type=float, default=15.0, metavar="DB", help="speech power over added-noise power")
+ap.add_argument("--snr-active", action="store_true", help="the speech power of the active tiles, not of the whole signal")
 ap.add_argument("--limiter", type=float, default=None, metavar="DB",
                 help="look-ahead limiter on the GPU: dB the gain may put the highest peak over the ceiling (with --loudness)")
 args = ap.parse_args()
@@ -71,6 +78,14 @@ if args.fir is not None:
     if args.rate:
         engine.condition.set_output_sampling_frequency(args.rate)
     engine.set_fir(J.fir(np.load(args.fir), args.rate or engine.condition.get_sampling_frequency(), args.fir_delay))
+if args.noise is not None:
+    import numpy as np
+
+    if args.rate:
+        engine.condition.set_output_sampling_frequency(args.rate)
+    engine.set_noise(J.noise(None if args.noise == "white" else np.load(args.noise),
+                             args.rate or engine.condition.get_sampling_frequency(), args.snr,
+                             reference="active" if args.snr_active else "whole"))
 if args.highpass is not None:
     engine.set_filter(J.highpass(args.highpass))
 if args.loudness is not None:

@@ -1142,8 +1142,8 @@ void jb_filter_free(void *p);
  *   time, 4,800 taps 39.24 ms, 24,000 taps 54.12 ms; the loudness measurement and apply pass of the same batch:
  *   17.42 ms.  Partitioned mode's error is at most 1.72 times the float64 FFT convolution's over the test shapes of more
  *   than one sample.
- * Not covered: keeping the tail, resampling a response, time-varying responses, additive noise at an SNR, non-uniform
- * partitions, serving a generator head early. */
+ * Not covered: keeping the tail, resampling a response, time-varying responses, non-uniform partitions, serving a
+ * generator head early. */
 #define JB_FIR_MAX_TAPS 131072u
 #define JB_FIR_DIRECT_MAX 256u
 #define JB_FIR_DIRECT 0u
@@ -1175,6 +1175,126 @@ int jb_fir_pcm_batch(const double *const *in, const size_t *n_in, size_t n, cons
 int jb_fir_pcm_batch_i16(const double *const *in, const size_t *n_in, size_t n, const jb_fir *f, const uint32_t *hz,
                          int32_t device, int16_t **out, size_t *n_out);
 void jb_fir_free(void *p);
+
+/* ---- Noise (new: the reference has no such control) ----------------------------------------------------------------
+ * Background noise added to the PCM on the device at a target signal-to-noise ratio: a caller-given noise bed that is
+ * looped, or white noise generated on the device, scaled so that speech power over added-noise power is the requested
+ * SNR.  The stage is part of the filter stage and runs at the output rate, behind the convolution and in front of the
+ * filter's sections -- reverberate, add noise, then the channel filter -- so that the loudness measurement, the
+ * ceiling, the limiter, the groups, the join and every encoder and feature stage see the noisy audio.  The output has
+ * the input's length.  The rule, for one utterance x[0..N) (f64, 16-bit units: the convolution's output where the
+ * utterance has a response, else what the filter stage reads):
+ *   1. The noise sequence w[n], n in [0, N).  JB_NOISE_BED: w[n] = bed[(offset + n) mod Lb], offset < Lb.
+ *      JB_NOISE_WHITE: r = mix(mix(seed) ^ n), mix the splitmix64 finaliser of the format stage's dither; w[n] is the
+ *      sum of the four 16-bit fields of r as integers, minus 131070, as a double: an exact integer in +-131070,
+ *      bell-shaped (Irwin-Hall of four), of zero mean and variance (2^32 - 1) / 3.  Its scale does not matter (the gain
+ *      normalises it); a sample depends on (seed, n) alone.
+ *   2. The power sum S(z) of a sequence z[0..N), in a fixed order that depends on the utterance alone.  Tiles of 1,024
+ *      samples are counted from the utterance's first sample.  A tile has 256 partials: p[l] covers the in-range
+ *      indices l + 256 j, j = 0..3 ascending; the first term is the product z z, every later one fma(z, z, p); a
+ *      partial with no index in range is +0.0.  Then p[l] = p[l] + p[l + h] for l < h, h = 128, 64, .., 1; the tile
+ *      sum is t_i = p[0].  S = t_0, then S = S + t_i in ascending i; N == 0 gives +0.0.
+ *   3. The reference level.  JB_NOISE_REF_WHOLE: A = S(x), C = N (what Kaldi's wav-reverberate and
+ *      torchaudio.functional.add_noise do).  JB_NOISE_REF_ACTIVE (synthesized utterances begin and end with silence,
+ *      which makes the whole-signal power understate the speech): with q = 10^(-gate_db / 10) (host, long double,
+ *      rounded once), tile i of c_i samples is active iff t_i (double)N >= (S(x) q) (double)c_i; A is the sum of the
+ *      active t_i in ascending order (the first starts it), C the sum of their c_i.
+ *   4. The noise power is over all N samples: Bs = S(w).
+ *   5. The gain: with r = 10^(snr_db / 10) (host, long double, rounded once),
+ *      g = sqrt(((A (double)N) / (Bs (double)C)) / r), in that operation order; g = 0 where A == 0, Bs == 0 or
+ *      snr_db == +INFINITY.
+ *   6. y[n] = fma(g, w[n], x[n]).  With g == 0 the utterance is not mixed: y = x bit for bit, signed zeros included.
+ *      A 16-bit output is the 16-bit sink's rule (fmin, fmax, truncate) on that y, as the filter's and the
+ *      convolution's are.
+ * - The request: kind; the bed (copied at the call), its length (at most JB_NOISE_MAX_BED) and hz, the rate it was
+ *   sampled at -- it must equal the utterance's output rate; a bed is never resampled; hz is not read with
+ *   JB_NOISE_WHITE -- the offset into the bed; the generator's seed; snr_db, finite in [-40, 100] or +INFINITY;
+ *   the reference and its gate_db ([1, 60] with JB_NOISE_REF_ACTIVE, else 0); flags; reserved 0.  kind JB_NOISE_BED
+ *   with bed == NULL and bed_len == 0 is no request for that utterance.  The distinct beds of a batch are stored once
+ *   each, by content, and hold at most 2^26 samples (above: JB_ERR_UNSUPPORTED).
+ * - Refused (JB_ERR_INVALID; jb_last_error names the utterance and the field) before any device is touched: an unknown
+ *   kind, reference or flag, a bed sample that is not finite, offset >= bed_len, bed_len == 0 with a bed given, a bed
+ *   with JB_NOISE_WHITE, hz different from the output rate (at the set call and again at a later
+ *   jb_batch_set_output_rate), snr_db or gate_db out of range or NaN, reserved != 0.
+ * - JB_NOISE_VARY, where one request is spread over many utterances (jb_batch_set_noise with n == 1, the engine
+ *   entries): the utterance of index k in the batch or call uses z = mix(mix(seed) ^ k), seed_k = z,
+ *   offset_k = mix(z) mod Lb (the given offset is ignored), so that the utterances of a corpus do not all get the same
+ *   noise (jb_noise_vary).  With one request per utterance the flag is refused.
+ * - On the device (jb_noise.hip): k_noise_sums forms the tile sums of x and w in one pass, one workgroup per tile, the
+ *   partial tree through LDS in the rule's order; k_noise_gain, one wave per utterance, adds the tile sums in ascending
+ *   order, runs the active pass and leaves the gain; k_noise_apply streams y.  No atomics, nothing whose order the
+ *   scheduling sets: A, C and Bs equal jb_noise_host's bit for bit, the gain to an ulp of the division and the square
+ *   root, and y equals jb_noise_host under the device's gain bit for bit.  A sample's bits depend on its utterance's
+ *   samples, the request and the gain alone, not on the batch, the position, the entry point or redo rounds;
+ *   JB_BATCH_INVARIANT output stays invariant.  The sum scratch takes 16 bytes per 1,024 samples.
+ * - jb_batch_read_pcm_native stays the vocoder's PCM.
+ * - Cost on 256 x 128 s at 48 kHz (profiles/r23_noise.txt, written by tools/noise_cost.py): white noise at 15 dB takes
+ *   8.05 ms of device time, a 10 s bed 9.68 ms, a 7-sample bed 8.75 ms, a 10 s bed against the active tiles 10.24 ms;
+ *   the loudness measurement and apply pass of the same batch: 16.96 ms.  By kernel: k_noise_apply 4.63 ms (5.26 ms
+ *   with the long bed) beside k_ln_apply's 4.62 ms on the same samples, k_noise_sums 3.28 to 4.34 ms, k_noise_gain
+ *   0.10 ms (0.65 ms with the active reference).  Over the test shapes the device's gain equals the host's bit for
+ *   bit (largest |g_dev / g_host - 1|: 0; gate 2^-50).
+ * Not covered: noise over a programme's pads (the stage runs per utterance in front of the join), several layers per
+ * utterance and timed foreground events, resampling a bed, coloured generated noise (a bed does that), the _multi
+ * entries (the convolution does not serve them either). */
+#define JB_NOISE_BED 0u
+#define JB_NOISE_WHITE 1u
+#define JB_NOISE_REF_WHOLE 0u
+#define JB_NOISE_REF_ACTIVE 1u
+#define JB_NOISE_VARY 1u
+#define JB_NOISE_MAX_BED 16777216u
+typedef struct jb_noise {
+    const double *bed;  /* bed[0..bed_len), 16-bit units; NULL with JB_NOISE_WHITE, or with bed_len 0: no request */
+    uint64_t seed;      /* JB_NOISE_WHITE's sequence; with JB_NOISE_VARY what the utterances' seeds and offsets come from */
+    double snr_db;      /* [-40, 100], or +INFINITY: the utterance is not mixed */
+    double gate_db;     /* [1, 60] with JB_NOISE_REF_ACTIVE, else 0 */
+    uint32_t kind;      /* JB_NOISE_BED, JB_NOISE_WHITE */
+    uint32_t bed_len;
+    uint32_t hz;        /* the rate the bed was sampled at */
+    uint32_t offset;    /* < bed_len */
+    uint32_t reference; /* JB_NOISE_REF_WHOLE, JB_NOISE_REF_ACTIVE */
+    uint32_t flags;     /* JB_NOISE_VARY */
+    uint32_t reserved;  /* 0 */
+} jb_noise;
+typedef struct jb_noise_report {
+    double speech_power;     /* A / C (0 where C is 0) */
+    double noise_power;      /* Bs / N, of the unscaled noise (0 where N is 0) */
+    double gain;             /* g */
+    double snr_db;           /* as requested */
+    uint64_t active_samples; /* C */
+    uint64_t seed;           /* the seed and ... */
+    uint32_t offset;         /* ... the offset that were used (JB_NOISE_VARY: the utterance's own) */
+    uint32_t reserved;
+} jb_noise_report;
+/* New (none).  req[0..n): one request for the batch (n == 1) or one per utterance (n == jb_batch_size); NULL, 0
+ * withdraws the request.  Before the first run only; not on a JB_BATCH_MLPG_ONLY batch; in either order with the rate,
+ * filter, response, loudness and join setters. */
+int jb_batch_set_noise(jb_batch *b, const jb_noise *req, size_t n);
+/* New (none).  What the stage did to utterance utt, after a run.  JB_ERR_INVALID without a request for that utterance
+ * or before a run. */
+int jb_batch_noise_report(jb_batch *b, size_t utt, jb_noise_report *out);
+/* New (none).  The rule in plain C++; no GPU is touched.  gain == NULL: the rule's gain; otherwise *gain is taken as
+ * given (as jb_limiter_host takes its gain).  req->hz is not looked at beyond the request check, JB_NOISE_VARY is
+ * ignored; y must hold n samples (cap below that: JB_ERR_BUFFER) and must not overlap x; report may be NULL.  No
+ * request returns the input. */
+int jb_noise_host(const double *x, size_t n, const jb_noise *req, const double *gain, double *y, size_t cap,
+                  jb_noise_report *report);
+int jb_noise_host_i16(const double *x, size_t n, const jb_noise *req, const double *gain, int16_t *y, size_t cap,
+                      jb_noise_report *report);
+/* New (none).  Samples first .. first + count of JB_NOISE_WHITE's sequence of `seed`; pure. */
+int jb_noise_white(uint64_t seed, uint64_t first, size_t count, double *out);
+/* New (none).  JB_NOISE_VARY's rule for the utterance of index k (bed_len 0: white, *offset_k = 0); pure. */
+int jb_noise_vary(uint64_t seed, uint64_t k, uint32_t bed_len, uint64_t *seed_k, uint32_t *offset_k);
+/* New (none).  The stage on PCM the caller holds (jb_fir_pcm_batch's twin), on `device` (-1 = current): utterance u is
+ * n_in[u] f64 samples at hz[u] under req[u] (no request: the samples themselves; JB_NOISE_VARY is refused);
+ * out[u] = its n_out[u] = n_in[u] samples, f64 or by the 16-bit sink's rule, library-owned (jb_noise_free each);
+ * reports (may be NULL): [n].  The same samples and request give the same bits from this seam and from the batch
+ * path. */
+int jb_noise_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_noise *req, const uint32_t *hz,
+                       int32_t device, double **out, size_t *n_out, jb_noise_report *reports);
+int jb_noise_pcm_batch_i16(const double *const *in, const size_t *n_in, size_t n, const jb_noise *req,
+                           const uint32_t *hz, int32_t device, int16_t **out, size_t *n_out, jb_noise_report *reports);
+void jb_noise_free(void *p);
 
 /* ---- Limiter (new: the reference has no such control) --------------------------------------------------------------
  * A look-ahead peak limiter in the place of the loudness apply pass: a few peaks are taken down so that the rest can
@@ -1404,6 +1524,16 @@ int jb_engine_get_filter(const jb_engine *e, jb_filter *out);
  * (the default) = off: the output is unchanged.  Checked here at the engine's present output rate and again at
  * synthesis.  jb_engine_new copies it with the Condition. */
 int jb_engine_set_fir(jb_engine *e, const jb_fir *f);
+/* New.  The noise of the audio the engine's entries return (see "Noise"): wherever the engine's impulse response
+ * applies, behind it and in front of the filter's sections (jb_batch_set_noise) -- jb_synthesize, every
+ * jb_synthesize_batch* and jb_synthesize_programme* form, the _each* forms (each engine's own request for its
+ * utterance) and the generator (whose converted utterance is read whole by the first step).  With JB_NOISE_VARY the
+ * utterance of index k in the call uses jb_noise_vary(seed, k, ..).  The bed is copied.  NULL, or no bed with
+ * JB_NOISE_BED (the default) = off: the output is unchanged.  Checked here at the engine's present output rate and
+ * again at synthesis.  jb_engine_new copies it with the Condition; jb_engine_get_noise's bed points into the engine's
+ * copy (valid until the next jb_engine_set_noise). */
+int jb_engine_set_noise(jb_engine *e, const jb_noise *req);
+int jb_engine_get_noise(const jb_engine *e, jb_noise *out);
 /* New.  The limiter of the audio the engine's entries return (see "Limiter"): jb_synthesize, every
  * jb_synthesize_batch* and jb_synthesize_programme* form and _each* (each engine's own request for its utterance: not
  * among the fields the engines must agree on, except inside a per-request loudness group) ask the batch for it
@@ -1756,6 +1886,16 @@ JB_LAYOUT_ASSERT(sizeof(jb_filter_section) == 72 && offsetof(jb_filter_section, 
 JB_LAYOUT_ASSERT(sizeof(jb_fir) == 24 && offsetof(jb_fir, n_taps) == 8 && offsetof(jb_fir, hz) == 12 &&
                      offsetof(jb_fir, delay) == 16 && offsetof(jb_fir, reserved) == 20,
                  "jb_fir");
+JB_LAYOUT_ASSERT(sizeof(jb_noise) == 64 && offsetof(jb_noise, seed) == 8 && offsetof(jb_noise, snr_db) == 16 &&
+                     offsetof(jb_noise, gate_db) == 24 && offsetof(jb_noise, kind) == 32 &&
+                     offsetof(jb_noise, bed_len) == 36 && offsetof(jb_noise, hz) == 40 &&
+                     offsetof(jb_noise, offset) == 44 && offsetof(jb_noise, reference) == 48 &&
+                     offsetof(jb_noise, flags) == 52 && offsetof(jb_noise, reserved) == 56,
+                 "jb_noise");
+JB_LAYOUT_ASSERT(sizeof(jb_noise_report) == 56 && offsetof(jb_noise_report, gain) == 16 &&
+                     offsetof(jb_noise_report, active_samples) == 32 && offsetof(jb_noise_report, seed) == 40 &&
+                     offsetof(jb_noise_report, offset) == 48,
+                 "jb_noise_report");
 JB_LAYOUT_ASSERT(sizeof(jb_filter) == 296 && offsetof(jb_filter, n_sections) == 288, "jb_filter");
 JB_LAYOUT_ASSERT(sizeof(jb_biquad) == 40 && offsetof(jb_biquad, a1) == 24, "jb_biquad");
 JB_LAYOUT_ASSERT(sizeof(jb_limiter_opts) == 32 && offsetof(jb_limiter_opts, max_reduction_db) == 16 &&

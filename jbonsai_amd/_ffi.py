@@ -415,6 +415,62 @@ def fir_array(firs, n=None):
     return arr, len(fs)
 
 
+NOISE_BED, NOISE_WHITE, NOISE_REF_WHOLE, NOISE_REF_ACTIVE, NOISE_VARY, NOISE_MAX_BED = 0, 1, 0, 1, 1, 1 << 24
+
+
+class Noise(C.Structure):
+    """jb_noise: a noise request -- a bed of bed_len f64 samples at hz that is looped from `offset`, or white noise of
+    `seed`, at snr_db against the whole utterance's power or its active tiles' (gate_db below the mean).  The object
+    keeps its bed alive (`_bed`); the library copies it at every call that takes one."""
+    _fields_ = [("bed", C.POINTER(C.c_double)), ("seed", C.c_uint64), ("snr_db", C.c_double), ("gate_db", C.c_double),
+                ("kind", C.c_uint32), ("bed_len", C.c_uint32), ("hz", C.c_uint32), ("offset", C.c_uint32),
+                ("reference", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NoiseReport(C.Structure):
+    """jb_noise_report: speech_power = A / C, noise_power = Bs / N, the gain, and the snr_db, seed and offset used."""
+    _fields_ = [("speech_power", C.c_double), ("noise_power", C.c_double), ("gain", C.c_double),
+                ("snr_db", C.c_double), ("active_samples", C.c_uint64), ("seed", C.c_uint64),
+                ("offset", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def noise(bed=None, hz: int = 0, snr_db: float = 20.0, offset: int = 0, seed: int = 0, reference: str = "whole",
+          gate_db: float = 20.0, vary: bool = False):
+    """A Noise: `bed` (any sequence of floats at `hz`, 16-bit units) looped from `offset`, or white noise of `seed`
+    where bed is None, at `snr_db`; reference "whole" or "active" (tiles within gate_db of the mean power); vary: every
+    utterance of a batch or call gets a seed and an offset of its own (noise_vary)."""
+    import numpy as np
+    if reference not in ("whole", "active"):
+        raise ValueError('noise: reference is "whole" or "active"')
+    r = Noise()
+    r.hz, r.snr_db, r.seed, r.offset = int(hz), float(snr_db), int(seed) & (2**64 - 1), int(offset)
+    r.reference = NOISE_REF_ACTIVE if reference == "active" else NOISE_REF_WHOLE
+    r.gate_db = float(gate_db) if reference == "active" else 0.0
+    r.flags = NOISE_VARY if vary else 0
+    if bed is None:
+        r.kind = NOISE_WHITE
+    else:
+        r.kind = NOISE_BED
+        r._bed = np.ascontiguousarray(bed, dtype=np.float64).reshape(-1)
+        r.bed = r._bed.ctypes.data_as(C.POINTER(C.c_double))
+        r.bed_len = r._bed.size
+    return r
+
+
+def noise_array(reqs, n=None):
+    """A (Noise * n) array of Noise entries (None: no request); one entry stands for all n.  The array keeps the
+    entries (and so their beds) alive."""
+    rs = [reqs] if isinstance(reqs, Noise) or reqs is None else list(reqs)
+    if n is not None and len(rs) == 1:
+        rs = rs * n
+    arr = (Noise * max(1, len(rs)))()
+    for i, r in enumerate(rs):
+        if r is not None:
+            C.memmove(C.byref(arr[i]), C.byref(r), C.sizeof(Noise))
+    arr._keep = rs
+    return arr, len(rs)
+
+
 def filter_array(filters, n=None):
     """A (Filter * n) array of Filter entries (None: no sections); one entry stands for all n."""
     fs = [filters] if isinstance(filters, Filter) or filters is None else list(filters)
@@ -571,6 +627,9 @@ SYMBOLS = [
     "jb_filter_pcm_batch", "jb_filter_pcm_batch_i16", "jb_filter_free", "jb_engine_set_filter", "jb_engine_get_filter",
     "jb_batch_set_fir", "jb_batch_fir_geometry", "jb_engine_set_fir", "jb_fir_host", "jb_fir_geometry",
     "jb_fir_pcm_batch", "jb_fir_pcm_batch_i16", "jb_fir_free",
+    "jb_batch_set_noise", "jb_batch_noise_report", "jb_engine_set_noise", "jb_engine_get_noise", "jb_noise_host",
+    "jb_noise_host_i16", "jb_noise_white", "jb_noise_vary", "jb_noise_pcm_batch", "jb_noise_pcm_batch_i16",
+    "jb_noise_free",
     "jb_batch_set_limiter", "jb_batch_limiter_report", "jb_limiter_window", "jb_limiter_host", "jb_limiter_host_i16",
     "jb_limiter_pcm_batch", "jb_limiter_pcm_batch_i16", "jb_limiter_free", "jb_engine_set_limiter",
     "jb_engine_get_limiter",
@@ -888,6 +947,20 @@ def lib():
     L.jb_fir_pcm_batch_i16.argtypes = L.jb_fir_pcm_batch.argtypes
     L.jb_fir_free.argtypes = [vp]
     L.jb_fir_free.restype = None
+    nzp, nrp = C.POINTER(Noise), C.POINTER(NoiseReport)
+    L.jb_batch_set_noise.argtypes = [vp, nzp, sz]
+    L.jb_batch_noise_report.argtypes = [vp, sz, nrp]
+    L.jb_engine_set_noise.argtypes = [vp, nzp]
+    L.jb_engine_get_noise.argtypes = [vp, nzp]
+    L.jb_noise_host.argtypes = [dp, sz, nzp, dp, dp, sz, nrp]
+    L.jb_noise_host_i16.argtypes = [dp, sz, nzp, dp, C.POINTER(C.c_int16), sz, nrp]
+    L.jb_noise_white.argtypes = [C.c_uint64, C.c_uint64, sz, dp]
+    L.jb_noise_vary.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), u32p]
+    L.jb_noise_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, nzp, u32p, C.c_int32, C.POINTER(vp),
+                                     C.POINTER(sz), nrp]
+    L.jb_noise_pcm_batch_i16.argtypes = L.jb_noise_pcm_batch.argtypes
+    L.jb_noise_free.argtypes = [vp]
+    L.jb_noise_free.restype = None
     lop, lrp = C.POINTER(LimiterOpts), C.POINTER(LimiterReport)
     L.jb_batch_set_limiter.argtypes = [vp, lop, sz]
     L.jb_batch_limiter_report.argtypes = [vp, sz, lrp]
@@ -1576,6 +1649,57 @@ def fir_pcm(pcms, firs, hz, device: int = -1, i16: bool = False):
     ns = (C.c_size_t * max(1, n))()
     check((L.jb_fir_pcm_batch_i16 if i16 else L.jb_fir_pcm_batch)(ins, nin, n, farr, hzs, device, outs, ns))
     return _take(L.jb_fir_free, outs, ns, n, np.int16 if i16 else np.float64)
+
+
+def noise_host(pcm, req, gain=None, i16: bool = False):
+    """jb_noise_host / _i16: the host rule (no GPU) on f64 `pcm` under `req` (a Noise, or None); gain None: the
+    rule's gain, else taken as given.  Returns (y, NoiseReport)."""
+    import numpy as np
+    x = np.ascontiguousarray(pcm, dtype=np.float64)
+    y = np.empty(x.size, dtype=np.int16 if i16 else np.float64)
+    dp = C.POINTER(C.c_double)
+    g = None if gain is None else C.byref(C.c_double(float(gain)))
+    rep = NoiseReport()
+    fn = lib().jb_noise_host_i16 if i16 else lib().jb_noise_host
+    check(fn(x.ctypes.data_as(dp), x.size, C.byref(req if req is not None else Noise()), g,
+             y.ctypes.data_as(C.POINTER(C.c_int16) if i16 else dp), y.size, C.byref(rep)))
+    return y, rep
+
+
+def noise_white(seed: int, first: int, count: int):
+    """jb_noise_white: samples first .. first + count of the white sequence of `seed` (exact integers in +-131070)."""
+    import numpy as np
+    out = np.empty(int(count), dtype=np.float64)
+    check(lib().jb_noise_white(int(seed) & (2**64 - 1), int(first), out.size,
+                               out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def noise_vary(seed: int, k: int, bed_len: int = 0):
+    """jb_noise_vary: (seed_k, offset_k) of the utterance of index k under NOISE_VARY."""
+    s, o = C.c_uint64(), C.c_uint32()
+    check(lib().jb_noise_vary(int(seed) & (2**64 - 1), int(k), int(bed_len), C.byref(s), C.byref(o)))
+    return s.value, o.value
+
+
+def noise_pcm(pcms, reqs, hz, device: int = -1, i16: bool = False):
+    """jb_noise_pcm_batch / _i16: the f64 utterances `pcms` under reqs[u] (a Noise, or None) at hz[u] on the GPU; one
+    Noise or one rate stands for all.  Returns (outs, reports): f64, or int16 by the 16-bit sink's rule."""
+    import numpy as np
+    L = lib()
+    arrs, n, ins, nin = _pcm_args(pcms, np.float64, void=True)
+    rarr, nr = noise_array(reqs, n)
+    if nr != n:
+        raise ValueError("noise_pcm: one request, or one per utterance")
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("noise_pcm: one rate, or one per utterance")
+    hzs = (C.c_uint32 * max(1, n))(*rates)
+    outs = (C.c_void_p * max(1, n))()
+    ns = (C.c_size_t * max(1, n))()
+    reps = (NoiseReport * max(1, n))()
+    check((L.jb_noise_pcm_batch_i16 if i16 else L.jb_noise_pcm_batch)(ins, nin, n, rarr, hzs, device, outs, ns, reps))
+    return _take(L.jb_noise_free, outs, ns, n, np.int16 if i16 else np.float64), list(reps)[:n]
 
 
 def limiter_window(hz: int, opts=None):

@@ -386,6 +386,22 @@ class Batch:
         arr, n = F.fir_array(firs)
         F.check(self._L.jb_batch_set_fir(self._h, arr, n))
 
+    def set_noise(self, reqs):
+        """jb_batch_set_noise: one F.Noise (J.noise(bed, hz, snr_db, ...)) for the whole batch or one per utterance
+        (None in a list: no request); None withdraws the request.  Before the first run.  The noise is added behind
+        the convolution and in front of the filter's sections; pcm_native stays the vocoder's PCM."""
+        if reqs is None:
+            F.check(self._L.jb_batch_set_noise(self._h, None, 0))
+            return
+        arr, n = F.noise_array(reqs)
+        F.check(self._L.jb_batch_set_noise(self._h, arr, n))
+
+    def noise_report(self, i):
+        """jb_batch_noise_report: the F.NoiseReport of utterance i, after a run."""
+        r = F.NoiseReport()
+        F.check(self._L.jb_batch_noise_report(self._h, i, C.byref(r)))
+        return r
+
     def fir_geometry(self, i):
         """jb_batch_fir_geometry: (mode, block, partitions) of utterance i's response."""
         m, b, p = C.c_uint32(), C.c_uint32(), C.c_uint32()

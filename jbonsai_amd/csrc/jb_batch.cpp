@@ -2536,6 +2536,19 @@ int jb_batch_fir_geometry(const jb_batch *hb, size_t utt, uint32_t *mode, uint32
     return JB_OK;
 }
 
+int jb_batch_set_noise(jb_batch *hb, const jb_noise *req, size_t n)
+{
+    return hb ? ((Batch *)hb)->out.set_noise(req, n) : JB_ERR_INVALID;
+}
+
+int jb_batch_noise_report(jb_batch *hb, size_t utt, jb_noise_report *out)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !out || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    return b->out.read_noise(utt, out);
+}
+
 int jb_batch_set_limiter(jb_batch *hb, const jb_limiter_opts *opts, size_t n)
 {
     return hb ? ((Batch *)hb)->out.set_limiter(opts, n) : JB_ERR_INVALID;

@@ -55,6 +55,14 @@ struct Condition {
     std::vector<double> fir_taps; // jb_engine_set_fir: the response's taps, copied (empty = off) ...
     uint32_t fir_hz = 0, fir_delay = 0; // ... its rate and delay
     jb_fir fir() const { return jb_fir{fir_taps.empty() ? nullptr : fir_taps.data(), (uint32_t)fir_taps.size(), fir_hz, fir_delay, 0}; }
+    std::vector<double> noise_bed; // jb_engine_set_noise: the bed's samples, copied ...
+    jb_noise noise_req{};         // ... and the request as it was given (its bed pointer is not kept: noise())
+    jb_noise noise() const
+    {
+        jb_noise r = noise_req;
+        r.bed = noise_bed.empty() ? nullptr : noise_bed.data();
+        return r;
+    }
     bool limiter_on = false;      // jb_engine_set_limiter: a request is set ...
     jb_limiter_opts limiter{};    // ... and the request as it was given
     uint32_t tree_search = JB_SEARCH_HOST; // jb_engine_set_tree_search: where the per-label tree search runs
@@ -1132,6 +1140,32 @@ int jb_engine_set_fir(jb_engine *e, const jb_fir *f)
     c.fir_delay = f->delay;
     return JB_OK;
 }
+int jb_engine_set_noise(jb_engine *e, const jb_noise *req)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    jb::Condition &c = ENG(e)->cond;
+    if (!req) {
+        c.noise_bed.clear();
+        c.noise_req = jb_noise{};
+        return JB_OK;
+    }
+    const size_t hz = c.output_rate ? c.output_rate : c.sampling_frequency;
+    int rc = jb::noise_check(req, (uint32_t)hz, 0, "jb_engine_set_noise");
+    if (rc)
+        return rc;
+    c.noise_bed.assign(req->bed, req->bed + (req->bed ? req->bed_len : 0));
+    c.noise_req = *req;
+    c.noise_req.bed = nullptr;
+    return JB_OK;
+}
+int jb_engine_get_noise(const jb_engine *e, jb_noise *out)
+{
+    if (!e || !out)
+        return JB_ERR_INVALID;
+    *out = CENG(e)->cond.noise();
+    return JB_OK;
+}
 int jb_engine_get_filter(const jb_engine *e, jb_filter *out)
 {
     if (!e || !out)
@@ -1680,6 +1714,17 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
         any_fir = any_fir || firs[u - lo].taps;
     }
     if (any_fir && (rc = out.set_fir(firs.data(), firs.size())))
+        return rc;
+    // the noise: each utterance's engine's own; JB_NOISE_VARY varies by the utterance's index in the call
+    std::vector<jb_noise> noises(hi - lo);
+    std::vector<uint64_t> call_k(hi - lo);
+    bool any_noise = false;
+    for (size_t u = lo; u < hi; u++) {
+        noises[u - lo] = eng(u)->cond.noise();
+        call_k[u - lo] = u;
+        any_noise = any_noise || noises[u - lo].bed || noises[u - lo].kind != JB_NOISE_BED;
+    }
+    if (any_noise && (rc = out.set_noise(noises.data(), noises.size(), call_k.data())))
         return rc;
     // loudness: each utterance's engine's own target and ceiling; an engine without a target leaves its
     // utterance as it is (measured, gain 0 dB: bit for bit the same) when another engine of the batch has one
@@ -2471,6 +2516,11 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     if (!CENG(e)->cond.fir_taps.empty()) {
         const jb_fir f = CENG(e)->cond.fir();
         if ((rc = b->out.set_fir(&f, 1)))
+            return rc;
+    }
+    {
+        const jb_noise nz = CENG(e)->cond.noise();
+        if ((nz.bed || nz.kind != JB_NOISE_BED) && (rc = b->out.set_noise(&nz, 1)))
             return rc;
     }
     if (!std::isnan(CENG(e)->cond.loudness_target)) {

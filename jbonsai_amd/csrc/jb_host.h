@@ -11,6 +11,7 @@
 #include "jb_loudness_rules.h"
 #include "jb_md5.h"
 #include "jb_mfcc.h"
+#include "jb_noise.h"
 #include "jb_output.h"
 #include "jb_pcm_call.h"
 
@@ -369,6 +370,42 @@ hipError_t launch_fir(const FirClass *classes_dev, const FirUtt *direct_dev, uin
                       const FirUtt *part_dev, uint32_t n_part, uint64_t blocks, uint64_t frames, double *spec,
                       hipStream_t stream);
 
+// The noise stage (jb_noise.hip; the rule, NoiseUtt and NoiseRecord: jb_noise.h; the host half: jb_noise.cpp).
+// req at the output rate `hz`: JB_OK, or JB_ERR_INVALID with set_error naming the utterance `utt` and the field
+int noise_check(const jb_noise *req, uint32_t hz, size_t utt, const char *who);
+// An accepted request of one utterance, resolved
+struct NoiseItem {
+    bool on = false;     // the utterance has a request
+    bool active = false; // JB_NOISE_REF_ACTIVE
+    int32_t bed = -1;    // its bed in NoiseBeds, -1: white
+    uint32_t offset = 0;
+    uint64_t seed = 0;
+    double snr_db = 0.0, r = 0.0, q = 0.0; // r = 10^(snr_db / 10), q = 10^(-gate_db / 10) (0 with _WHOLE)
+};
+// `vary`: JB_NOISE_VARY's seed and offset of the utterance of index k
+NoiseItem noise_resolve(const jb_noise &req, bool vary, uint64_t k, int32_t bed);
+// The distinct beds of a launch, by content (samples, rate): their host copies
+struct NoiseBeds {
+    std::vector<std::vector<double>> beds;
+    std::vector<uint32_t> rate;
+    int32_t find(const double *w, uint32_t len, uint32_t hz); // made at its first use
+    uint64_t words() const;                                   // doubles of the device image
+    void bind(const double *dev, std::vector<double> *image, std::vector<NoiseBed> *out) const;
+};
+jb_noise_report noise_report_of(const NoiseItem &it, const NoiseRecord &r, uint64_t n);
+// The launch list of the utterances `has` marks (and `only`, where not null), in utterance order with t0 and a0
+// filled in; tiles / apply: the workgroups of the sums and of the apply pass
+struct NoiseLaunch {
+    std::vector<NoiseUtt> utts;
+    uint64_t tiles = 0, apply = 0;
+};
+void noise_launch_list(const std::vector<NoiseUtt> &utts, const std::vector<uint8_t> &has,
+                       const std::vector<uint8_t> *only, NoiseLaunch *out);
+// k_noise_sums, k_noise_gain and k_noise_apply over utts_dev[0..n); sums: the scratch, two doubles per tile; rec: the
+// records the utterances' `rep` index
+hipError_t launch_noise(const NoiseUtt *utts_dev, uint32_t n, uint64_t tiles, uint64_t apply, double *sums,
+                        NoiseRecord *rec, hipStream_t stream);
+
 // The limiter stage (jb_limiter.hip; the rules, LimiterClass and LimiterUtt: jb_limiter.h; the host half:
 // jb_limiter.cpp).  opts (null: the defaults) checked and resolved into *out (may be null), or JB_ERR_INVALID with
 // set_error naming the utterance `utt` and the field
@@ -592,6 +629,12 @@ struct OutputChain {
     int set_fir(const jb_fir *f, size_t n);
     // the geometry of utterance u's response (JB_ERR_INVALID: it has none)
     int fir_geometry_of(size_t u, FirGeom *g) const;
+    // req[0..n): n == 1 or B requests (nullptr, 0: the request is withdrawn; no bed with JB_NOISE_BED: none for that
+    // utterance), each checked at its utterance's output rate and its bed copied; set_output_rate checks the rates again
+    // call_k (the engine entries; [B] or null): one request per utterance may carry JB_NOISE_VARY, and utterance u
+    // varies by its index call_k[u] in the call
+    int set_noise(const jb_noise *req, size_t n, const uint64_t *call_k = nullptr);
+    int read_noise(size_t u, jb_noise_report *out); // after sync
     // opts[0..n): n == 1 or B requests (nullptr, 0: the request is withdrawn); with groups, the members must agree
     int set_limiter(const jb_limiter_opts *opts, size_t n);
     int read_limiter(size_t u, jb_limiter_report *out); // after sync
@@ -672,7 +715,9 @@ private:
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
     FirClasses fir_cls;                        // the distinct responses of the convolution request (its copies)
     std::vector<int32_t> fir_of;               // [B] an utterance's response in fir_cls, -1: none; empty: no request
-    std::vector<uint8_t> stage_any;            // [B] 1 = a section or a response: the plan's filter flag
+    NoiseBeds noise_beds;                      // the distinct beds of the noise request (its copies)
+    std::vector<NoiseItem> noise_req;          // [B] the noise request, resolved; empty: none
+    std::vector<uint8_t> stage_any;            // [B] 1 = a section, a response or a noise request: the plan's filter flag
     std::vector<double> ln_target, ln_ceiling; // [B]
     std::vector<LimOpts> lim_req;              // [B] the limiter request, resolved; empty: none
     std::vector<uint32_t> ln_mode;             // [B] JB_PEAK_*; empty: sample peak everywhere
@@ -696,7 +741,7 @@ private:
         const FilterLaunch *take = nullptr;  // of the next launch
         FilterClass *classes_dev = nullptr;
         double *st = nullptr;                // kFiltMaxD doubles per tile
-        std::vector<uint8_t> mine;           // [B] 0 = the convolution writes the stage's output alone; empty: all 1
+        std::vector<uint8_t> mine;           // [B] 0 = the convolution or the noise writes the stage's output; empty: all 1
     } fil;
     struct Fir { // follows `measured`; in front of the filter's kernels
         std::vector<FirUtt> host;            // [B] by utterance index
@@ -707,8 +752,18 @@ private:
         FirClass *classes_dev = nullptr;
         double *tables = nullptr;            // the classes' image
         double *spec = nullptr;              // the spectrum scratch of the partitioned utterances
-        double *mid = nullptr;               // f64, the plan's geometry: what the sections read where an utterance has both
+        double *mid = nullptr;               // f64, the plan's geometry: what a sub-stage with another behind it writes
     } fir;
+    struct Noise { // follows `measured`; behind the convolution's kernels, in front of the filter's
+        std::vector<NoiseUtt> host;          // [B] by utterance index
+        std::vector<uint8_t> has;            // [B] 1 = the utterance has a request
+        DevList<NoiseUtt> utts;              // the launch list
+        NoiseLaunch all, sub;                // of a run, of the last redo
+        uint64_t tiles = 0, apply = 0;       // of the next launch
+        double *beds = nullptr;              // the beds' image
+        double *sums = nullptr;              // two doubles per tile of 1,024 samples, by the full run's numbering
+        NoiseRecord *rec = nullptr;          // [B]
+    } noi;
     struct Loudness { // measurement and an utterance's report set: `measured`; the apply pass with groups: `post`
         DevList<LoudnessUtt> utts;             // [B]; total: the measurement's tiles
         DevList<LoudnessUtt> apply;            // what the apply pass takes: `utts`, or on a redo with groups a list
@@ -822,12 +877,14 @@ private:
     int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
     int check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const;
     int check_fir(const std::vector<uint32_t> &want, const char *who) const; // the responses' rates under `want`
-    void flag_stage(); // stage_any of the two requests
+    int check_noise(const std::vector<uint32_t> &want, const char *who) const; // the beds' rates under `want`
+    void flag_stage(); // stage_any of the three requests
     int check_settable(const char *after_run) const;
     // the stages, in the order enqueue() runs them.  scope null: a full run
     int prepare_resample(), select_resample(const RedoScope *scope), launch_resample(bool redo);
     int prepare_filter(), select_filter(const RedoScope *scope), launch_filter(bool redo);
     int prepare_fir(), select_fir(const RedoScope *scope), launch_fir(bool redo);
+    int prepare_noise(), select_noise(const RedoScope *scope), launch_noise(bool redo);
     int prepare_loudness(), select_loudness(const RedoScope *scope), launch_loudness(bool redo);
     int prepare_limiter(), select_limiter(const RedoScope *scope), launch_limiter(bool redo);
     int prepare_join(), select_join(const RedoScope *scope), launch_join(bool redo);

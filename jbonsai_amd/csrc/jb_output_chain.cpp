@@ -48,8 +48,15 @@ void OutputChain::replan()
     plan = plan_output(in);
 }
 
-// The plan's filter flag: an utterance has a section or a response (without a convolution request: filt_any itself)
-void OutputChain::flag_stage() { stage_any = fir_stage_flags(filt_any, fir_of); }
+// The plan's filter flag: an utterance has a section, a response or a noise request (without the latter two:
+// filt_any itself)
+void OutputChain::flag_stage()
+{
+    std::vector<uint8_t> noise_of(noise_req.size());
+    for (size_t u = 0; u < noise_req.size(); u++)
+        noise_of[u] = noise_req[u].on;
+    stage_any = noise_stage_flags(fir_stage_flags(filt_any, fir_of), noise_of);
+}
 
 // what every setter refuses
 int OutputChain::check_settable(const char *after_run) const
@@ -105,6 +112,7 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
         (rc = check_join(join_req, want, "jb_batch_set_output_rate")) ||
         (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")) ||
         (rc = check_fir(want, "jb_batch_set_output_rate")) ||
+        (rc = check_noise(want, "jb_batch_set_output_rate")) ||
         (fb_on && (rc = check_fbank(fb_p, want, "jb_batch_set_output_rate"))) ||
         (mf_on && (rc = check_mfcc(mf_fb, want, "jb_batch_set_output_rate"))))
         return rc;
@@ -491,6 +499,71 @@ int OutputChain::fir_geometry_of(size_t u, FirGeom *g) const
     return JB_OK;
 }
 
+// The noise request under these rates: a bed's rate is its utterance's output rate
+int OutputChain::check_noise(const std::vector<uint32_t> &want, const char *who) const
+{
+    const std::vector<uint32_t> hz = rates_under(want);
+    for (size_t u = 0; u < noise_req.size(); u++)
+        if (noise_req[u].on && noise_req[u].bed >= 0 && noise_beds.rate[(size_t)noise_req[u].bed] != hz[u]) {
+            set_error(std::string(who) + ": utterance " + std::to_string(u) +
+                      ": hz of its noise bed differs from the utterance's output rate (a bed is never resampled): " +
+                      std::to_string(noise_beds.rate[(size_t)noise_req[u].bed]) + " Hz against " +
+                      std::to_string(hz[u]) + " Hz");
+            return JB_ERR_INVALID;
+        }
+    return JB_OK;
+}
+
+int OutputChain::set_noise(const jb_noise *req, size_t n, const uint64_t *call_k)
+{
+    int rc = check_settable("jb_batch_set_noise: the noise is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!req && n == 0) {
+        noise_beds = NoiseBeds{};
+        noise_req.clear();
+        replan();
+        return JB_OK;
+    }
+    const size_t B = (size_t)b.B;
+    if (!req || (n != 1 && n != B)) {
+        set_error("jb_batch_set_noise: give one request, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    const std::vector<uint32_t> hz = rates_under(want_hz);
+    for (size_t u = 0; u < B; u++) {
+        const jb_noise &r = req[n == 1 ? 0 : u];
+        if ((rc = noise_check(&r, hz[u], u, "jb_batch_set_noise")))
+            return rc;
+        if (n != 1 && !call_k && (r.flags & kNoiseVary)) {
+            set_error("jb_batch_set_noise: utterance " + std::to_string(u) +
+                      ": flags: JB_NOISE_VARY needs one request over many utterances");
+            return JB_ERR_INVALID;
+        }
+    }
+    NoiseBeds beds; // (the beds are copied here: the caller's buffers are not read again)
+    std::vector<NoiseItem> items(B);
+    bool any = false;
+    for (size_t u = 0; u < B; u++) {
+        const jb_noise &r = req[n == 1 ? 0 : u];
+        if (noise_none(*(const NoiseSpec *)&r))
+            continue;
+        items[u] = noise_resolve(r, r.flags & kNoiseVary, call_k ? call_k[u] : u,
+                                 r.kind == kNoiseBed ? beds.find(r.bed, r.bed_len, r.hz) : -1);
+        any = true;
+    }
+    if (beds.words() > kNoiseMaxBeds) {
+        set_error("jb_batch_set_noise: the distinct beds hold more than 2^26 samples");
+        return JB_ERR_UNSUPPORTED;
+    }
+    if (!any)
+        items.clear();
+    noise_beds = std::move(beds);
+    noise_req = std::move(items);
+    replan();
+    return JB_OK;
+}
+
 // The limiter request `req` ([B], empty: none) under the groups `group` ([B], empty: none): the members of a group
 // agree on the options, else JB_ERR_INVALID naming the group and the field
 int OutputChain::check_limiter_groups(const std::vector<uint32_t> &group, const std::vector<LimOpts> &req,
@@ -566,7 +639,7 @@ int OutputChain::prepare()
     for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
-    if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
+    if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_noise()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
         (rc = prepare_join()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
         (rc = prepare_fbank()) || (rc = prepare_mfcc()))
@@ -592,14 +665,14 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         redo ? redo_scope(plan.prog_of, plan.units.size(), grouped() ? ln_groups : no_groups, *only) : RedoScope{};
     const RedoScope *scope = redo ? &of_redo : nullptr;
     int rc;
-    if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
+    if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_noise(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
         (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
         (rc = select_adpcm(scope)) || (rc = select_fbank(scope)) || (rc = select_mfcc(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n || mf.utts.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n || mf.utts.n))
         return JB_OK;
-    if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
+    if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_noise(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
         (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
         (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)) || (rc = launch_mfcc(redo)))
         return rc;
@@ -697,18 +770,19 @@ int OutputChain::prepare_filter()
     std::vector<uint32_t> hz(B), cls_of;
     for (size_t u = 0; u < B; u++)
         hz[u] = plan.utt[u].hz;
-    // (with a convolution request alone every utterance is in the identity class)
+    // (with a convolution or a noise request alone every utterance is in the identity class)
     const std::vector<jb_filter> none(filt_req.empty() ? B : 0, jb_filter{});
     int rc = filter_classes(filt_req.empty() ? none.data() : filt_req.data(), B, hz.data(), B, &fil.classes, &cls_of,
                             "jb_batch_set_filter");
     if (rc)
         return rc;
-    // behind a response the sections read the convolution's f64 (fir.mid); an utterance with a response and no section
-    // is the convolution's alone
-    if (!fir.has.empty()) {
+    // behind a response or a noise request the sections read the f64 of the sub-stage in front (fir.mid); an utterance
+    // with one of the two and no section is theirs alone
+    auto fronted = [&](size_t u) { return (!fir.has.empty() && fir.has[u]) || (!noi.has.empty() && noi.has[u]); };
+    if (!fir.has.empty() || !noi.has.empty()) {
         fil.mine.assign(B, 1);
         for (size_t u = 0; u < B; u++)
-            fil.mine[u] = !(fir.has[u] && fil.classes[cls_of[u]].ns == 0);
+            fil.mine[u] = !(fronted(u) && fil.classes[cls_of[u]].ns == 0);
     }
     fil.utts.host.assign(B, FilterUtt{});
     uint64_t tiles = 0;
@@ -719,7 +793,7 @@ int OutputChain::prepare_filter()
             set_error("filter: utterance " + std::to_string(u) + " is too long");
             return JB_ERR_UNSUPPORTED;
         }
-        const double *x = !fir.has.empty() && fir.has[u] && fil.mine[u] ? fir.mid : src;
+        const double *x = fronted(u) && fil.mine[u] ? fir.mid : src;
         fil.utts.host[u] = {x + o.off, dst + o.off * elem, o.n, tiles, 0, (uint32_t)nt, cls_of[u]};
         tiles += nt;
     }
@@ -769,10 +843,14 @@ int OutputChain::prepare_fir()
     const size_t elem = plan.filter.i16 ? sizeof(int16_t) : sizeof(double);
     fir.host.assign(B, FirUtt{});
     fir.has.assign(B, 0);
+    // (something follows the convolution: the noise or a section)
+    auto followed = [&](size_t u) {
+        return (!filt_any.empty() && filt_any[u]) || (!noise_req.empty() && noise_req[u].on);
+    };
     bool both = false;
     for (size_t u = 0; u < B; u++) {
         fir.has[u] = fir_of[u] >= 0;
-        both = both || (fir.has[u] && !filt_any.empty() && filt_any[u]);
+        both = both || (fir.has[u] && followed(u));
     }
     int rc;
     if (both && (rc = b.dalloc(&fir.mid, (size_t)plan.total, false)))
@@ -783,7 +861,7 @@ int OutputChain::prepare_fir()
             continue;
         const OutUtt &o = plan.utt[u];
         const FirGeom &g = fir_cls.resp[(size_t)fir_of[u]].g;
-        const bool mid = !filt_any.empty() && filt_any[u];
+        const bool mid = followed(u);
         fir.host[u] = {src + o.off, mid ? (void *)(fir.mid + o.off) : (void *)(dst + o.off * elem), o.n, 0, 0, bins,
                        (uint32_t)fir_of[u], mid ? 0u : (uint32_t)plan.filter.i16};
         if (g.mode == kFirPartitioned)
@@ -834,6 +912,98 @@ int OutputChain::launch_fir(bool redo)
     const hipError_t e = jb::launch_fir(fir.classes_dev, fir.direct.list, fir.direct.n, fir.direct.total, fir.part.list,
                                         fir.part.n, fir.part.total, fir.frames, fir.spec, b.stream_voc);
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "convolution(redo)" : "convolution");
+}
+
+// ---- the noise: behind the convolution, in front of the sections.  Of an utterance's three sub-stages (response,
+// noise, sections) the last writes the stage's slab, the ones in front write f64 to fir.mid: the noise reads the
+// stage's input, or fir.mid behind a response; it writes the stage's slab, or fir.mid in front of a section -- behind a
+// response and in front of a section the apply pass rewrites fir.mid in place (a sample depends on its own index
+// alone; the sums pass only reads).  The beds' image, the launch list, the sum scratch (16 bytes per 1,024 samples,
+// where the full run's numbering put it) and the records
+int OutputChain::prepare_noise()
+{
+    if (noise_req.empty() || !plan.filtered())
+        return JB_OK;
+    const size_t B = (size_t)b.B;
+    const double *src = (const double *)slab[(size_t)plan.filter_src];
+    char *dst = (char *)slab[(size_t)plan.filter.slab];
+    const size_t elem = plan.filter.i16 ? sizeof(int16_t) : sizeof(double);
+    noi.host.assign(B, NoiseUtt{});
+    noi.has.assign(B, 0);
+    auto followed = [&](size_t u) { return !filt_any.empty() && filt_any[u]; };
+    bool mid_needed = false;
+    for (size_t u = 0; u < B; u++) {
+        noi.has[u] = noise_req[u].on;
+        mid_needed = mid_needed || (noi.has[u] && followed(u));
+    }
+    int rc;
+    if (mid_needed && !fir.mid && (rc = b.dalloc(&fir.mid, (size_t)plan.total, false)))
+        return rc;
+    if ((rc = b.dalloc(&noi.beds, (size_t)noise_beds.words(), false)) || (rc = b.dalloc(&noi.rec, B, false)))
+        return rc;
+    std::vector<double> image;
+    std::vector<NoiseBed> beds;
+    noise_beds.bind(noi.beds, &image, &beds);
+    uint64_t tiles = 0;
+    for (size_t u = 0; u < B; u++) {
+        if (!noi.has[u])
+            continue;
+        const OutUtt &o = plan.utt[u];
+        const NoiseItem &it = noise_req[u];
+        const bool behind = !fir.has.empty() && fir.has[u], mid = followed(u);
+        NoiseUtt w{};
+        w.x = (behind ? fir.mid : src) + o.off;
+        w.y = mid ? (void *)(fir.mid + o.off) : (void *)(dst + o.off * elem);
+        w.bed = it.bed >= 0 ? beds[(size_t)it.bed].w : nullptr;
+        w.n = o.n;
+        w.s0 = tiles;
+        w.mseed = fmt_mix(it.seed);
+        w.r = it.r;
+        w.q = it.q;
+        w.lb = it.bed >= 0 ? beds[(size_t)it.bed].len : 0;
+        w.offset = it.offset;
+        w.active = it.active;
+        w.i16 = mid ? 0u : (uint32_t)plan.filter.i16;
+        w.rep = (uint32_t)u;
+        noi.host[u] = w;
+        tiles += noise_tiles(o.n);
+    }
+    noise_launch_list(noi.host, noi.has, nullptr, &noi.all);
+    if (noi.all.tiles > 0x7fffffffull) {
+        set_error("noise: too many tiles for one launch");
+        return JB_ERR_UNSUPPORTED;
+    }
+    noi.utts.host = noi.all.utts;
+    if ((rc = b.dalloc(&noi.sums, (size_t)(2 * tiles), false)) ||
+        (rc = noi.utts.alloc(b, noi.utts.host.size(), noi.utts.host.size())) ||
+        (rc = upload_list(noi.beds, image, "noise beds")))
+        return rc;
+    return noi.utts.upload("noise work list");
+}
+
+int OutputChain::select_noise(const RedoScope *scope)
+{
+    if (noi.has.empty())
+        return JB_OK;
+    if (!scope) {
+        noi.tiles = noi.all.tiles;
+        noi.apply = noi.all.apply;
+        return noi.utts.take_all();
+    }
+    // every touched utterance whole: one changed sample changes the power, the gain and so every sample
+    noise_launch_list(noi.host, noi.has, &scope->measured, &noi.sub);
+    noi.tiles = noi.sub.tiles;
+    noi.apply = noi.sub.apply;
+    return noi.utts.upload_redo(noi.sub.utts, kRedoLists);
+}
+
+int OutputChain::launch_noise(bool redo)
+{
+    if (noi.has.empty() || !noi.utts.n)
+        return JB_OK;
+    const hipError_t e =
+        jb::launch_noise(noi.utts.list, noi.utts.n, noi.tiles, noi.apply, noi.sums, noi.rec, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "noise(redo)" : "noise");
 }
 
 // ---- loudness.  The per-rate tables and the utterance list: the measurement reads the f64 of the stage in front,
@@ -1481,6 +1651,23 @@ int OutputChain::read_loudness(size_t u, LoudnessResult *r)
     int rc = check_ready(plan.normalize(), "jb_batch_loudness: the batch has not run",
                          "jb_batch_loudness: no loudness target is set");
     return rc ? rc : b.read(ln.res + u, r, sizeof *r);
+}
+
+int OutputChain::read_noise(size_t u, jb_noise_report *out)
+{
+    int rc = check_ready(!noi.has.empty() || !noise_req.empty(), "jb_batch_noise_report: the batch has not run",
+                         "jb_batch_noise_report: jb_batch_set_noise was not called");
+    if (rc)
+        return rc;
+    if (u >= noise_req.size() || !noise_req[u].on) {
+        set_error("jb_batch_noise_report: utterance " + std::to_string(u) + " has no noise request");
+        return JB_ERR_INVALID;
+    }
+    NoiseRecord r{};
+    if ((rc = b.read(noi.rec + u, &r, sizeof r)))
+        return rc;
+    *out = noise_report_of(noise_req[u], r, plan.utt[u].n);
+    return JB_OK;
 }
 
 int OutputChain::read_limiter(size_t u, jb_limiter_report *out)

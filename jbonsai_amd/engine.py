@@ -164,6 +164,10 @@ class _Condition:
         """The impulse response (an _ffi.Fir: J.fir(taps, hz, delay)) of every entry's output, in front of the
         filter's sections; None for none.  The taps are copied."""
         F.check(self._L().jb_engine_set_fir(self._h(), None if f is None else C.byref(f)))
+    def set_noise(self, r):
+        """The noise request (an _ffi.Noise: J.noise(bed, hz, snr_db, ...)) of every entry's output, behind the
+        impulse response and in front of the filter's sections; None for none.  The bed is copied."""
+        F.check(self._L().jb_engine_set_noise(self._h(), None if r is None else C.byref(r)))
     def get_filter(self):
         f = F.Filter()
         F.check(self._L().jb_engine_get_filter(self._h(), C.byref(f)))
@@ -270,6 +274,10 @@ class Engine:
     def set_fir(self, f):
         """jb_engine_set_fir (the Condition's setter, on the engine): an _ffi.Fir, or None for none."""
         self.condition.set_fir(f)
+
+    def set_noise(self, r):
+        """jb_engine_set_noise (the Condition's setter, on the engine): an _ffi.Noise, or None for none."""
+        self.condition.set_noise(r)
 
     def get_filter(self):
         return self.condition.get_filter()
