@@ -506,28 +506,36 @@ class Batch:
         meta = F.flac_meta(md5, seek_interval_ms) or F.FlacMeta()
         F.check(self._L.jb_batch_set_flac_meta(self._h, C.byref(meta)))
 
+    # The byte sinks -- "flac", "formatted", "adpcm", "fbank", "mfcc" -- are read through one path: the C entries are
+    # jb_batch_<name>_size, jb_batch_read_<name> and jb_batch_read_<name>_all
+    def _sink_size(self, name, i) -> int:
+        n = C.c_size_t()
+        F.check(getattr(self._L, f"jb_batch_{name}_size")(self._h, i, C.byref(n)))
+        return n.value
+
+    def _sink_read(self, name, i) -> bytes:
+        n = self._sink_size(name, i)
+        buf = np.empty(max(1, n), dtype=np.uint8)
+        F.check(getattr(self._L, f"jb_batch_read_{name}")(self._h, i, buf.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return buf[:n].tobytes()
+
+    def _sink_read_all(self, name) -> List[bytes]:
+        B = self.num_outputs()
+        ns = [self._sink_size(name, i) for i in range(B)]
+        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
+        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
+        fn = getattr(self._L, f"jb_batch_read_{name}_all")
+        F.check(fn(self._h, C.cast(arr, fn.argtypes[1])))  # (bound as uint8_t ** for FLAC, void ** for the others)
+        return [b[:n].tobytes() for b, n in zip(bufs, ns)]
+
     def flac(self, i) -> bytes:
         """Utterance i's FLAC stream (jb_batch_flac_size + jb_batch_read_flac)."""
-        n = C.c_size_t()
-        F.check(self._L.jb_batch_flac_size(self._h, i, C.byref(n)))
-        buf = bytearray(max(1, n.value))
-        F.check(self._L.jb_batch_read_flac(self._h, i, (C.c_uint8 * len(buf)).from_buffer(buf), n.value))
-        return bytes(buf[:n.value])
+        return self._sink_read("flac", i)
 
     def flac_all(self) -> List[bytes]:
         """Every utterance's (with a join: every programme's) FLAC stream through one device-to-host copy
         (jb_batch_read_flac_all)."""
-        B = self.num_outputs()
-        ns = []
-        for i in range(B):
-            n = C.c_size_t()
-            F.check(self._L.jb_batch_flac_size(self._h, i, C.byref(n)))
-            ns.append(n.value)
-        bufs = [bytearray(max(1, n)) for n in ns]
-        u8p = C.POINTER(C.c_uint8)
-        arr = (u8p * max(1, B))(*[C.cast((C.c_uint8 * len(b)).from_buffer(b), u8p) for b in bufs])
-        F.check(self._L.jb_batch_read_flac_all(self._h, arr))
-        return [bytes(b[:n]) for b, n in zip(bufs, ns)]
+        return self._sink_read_all("flac")
 
     def set_format(self, fmt, dither=False, seed: int = 0):
         """jb_batch_set_format: the run also writes each utterance's final f64 PCM as bytes of a sample format --
@@ -538,25 +546,12 @@ class Batch:
 
     def formatted(self, i) -> bytes:
         """Utterance i's bytes in the batch's sample format (jb_batch_formatted_size + jb_batch_read_formatted)."""
-        n = C.c_size_t()
-        F.check(self._L.jb_batch_formatted_size(self._h, i, C.byref(n)))
-        buf = np.empty(max(1, n.value), dtype=np.uint8)
-        F.check(self._L.jb_batch_read_formatted(self._h, i, buf.ctypes.data, n.value))
-        return buf[:n.value].tobytes()
+        return self._sink_read("formatted", i)
 
     def formatted_all(self) -> List[bytes]:
         """Every utterance's (with a join: every programme's) formatted bytes through one device-to-host copy
         (jb_batch_read_formatted_all)."""
-        B = self.num_outputs()
-        ns = []
-        for i in range(B):
-            n = C.c_size_t()
-            F.check(self._L.jb_batch_formatted_size(self._h, i, C.byref(n)))
-            ns.append(n.value)
-        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
-        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
-        F.check(self._L.jb_batch_read_formatted_all(self._h, arr))
-        return [b[:n].tobytes() for b, n in zip(bufs, ns)]
+        return self._sink_read_all("formatted")
 
     def set_adpcm(self, block_align: int = 0):
         """jb_batch_set_adpcm: the run also encodes each utterance's final PCM as IMA ADPCM blocks (WAV tag 0x11) on
@@ -572,26 +567,16 @@ class Batch:
         return a.value
 
     def adpcm_size(self, i) -> int:
-        n = C.c_size_t()
-        F.check(self._L.jb_batch_adpcm_size(self._h, i, C.byref(n)))
-        return n.value
+        return self._sink_size("adpcm", i)
 
     def read_adpcm(self, i) -> bytes:
         """Utterance i's IMA ADPCM blocks (jb_batch_adpcm_size + jb_batch_read_adpcm)."""
-        n = self.adpcm_size(i)
-        buf = np.empty(max(1, n), dtype=np.uint8)
-        F.check(self._L.jb_batch_read_adpcm(self._h, i, buf.ctypes.data, n))
-        return buf[:n].tobytes()
+        return self._sink_read("adpcm", i)
 
     def read_adpcm_all(self) -> List[bytes]:
         """Every utterance's (with a join: every programme's) blocks through one device-to-host copy
         (jb_batch_read_adpcm_all)."""
-        B = self.num_outputs()
-        ns = [self.adpcm_size(i) for i in range(B)]
-        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
-        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
-        F.check(self._L.jb_batch_read_adpcm_all(self._h, arr))
-        return [b[:n].tobytes() for b, n in zip(bufs, ns)]
+        return self._sink_read_all("adpcm")
 
     def set_fbank(self, opts=None, **kw):
         """jb_batch_set_fbank: the run also turns each utterance's (with a join: each programme's) final f64 PCM into
@@ -610,26 +595,16 @@ class Batch:
         return T.value, m.value, hz.value
 
     def fbank_size(self, i) -> int:
-        n = C.c_size_t()
-        F.check(self._L.jb_batch_fbank_size(self._h, i, C.byref(n)))
-        return n.value
+        return self._sink_size("fbank", i)
 
     def read_fbank(self, i):
         """Unit i's features, an ndarray [T, n_mels] (jb_batch_fbank_size + jb_batch_read_fbank)."""
-        n = self.fbank_size(i)
-        buf = np.empty(max(1, n), dtype=np.uint8)
-        F.check(self._L.jb_batch_read_fbank(self._h, i, buf.ctypes.data, n))
-        return F.fbank_frames(buf[:n].tobytes(), self._fbank)
+        return F.fbank_frames(self._sink_read("fbank", i), self._fbank)
 
     def read_fbank_all(self):
         """Every utterance's (with a join: every programme's) features through one device-to-host copy
         (jb_batch_read_fbank_all)."""
-        B = self.num_outputs()
-        ns = [self.fbank_size(i) for i in range(B)]
-        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
-        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
-        F.check(self._L.jb_batch_read_fbank_all(self._h, arr))
-        return [F.fbank_frames(b[:n].tobytes(), self._fbank) for b, n in zip(bufs, ns)]
+        return [F.fbank_frames(d, self._fbank) for d in self._sink_read_all("fbank")]
 
     def set_mfcc(self, opts=None, fbank=None, **kw):
         """jb_batch_set_mfcc: the run also turns each utterance's (with a join: each programme's) final f64 PCM into
@@ -652,26 +627,16 @@ class Batch:
         return T.value, w.value, hz.value
 
     def mfcc_size(self, i) -> int:
-        n = C.c_size_t()
-        F.check(self._L.jb_batch_mfcc_size(self._h, i, C.byref(n)))
-        return n.value
+        return self._sink_size("mfcc", i)
 
     def read_mfcc(self, i):
         """Unit i's rows, an ndarray [T, width] (jb_batch_mfcc_size + jb_batch_read_mfcc)."""
-        n = self.mfcc_size(i)
-        buf = np.empty(max(1, n), dtype=np.uint8)
-        F.check(self._L.jb_batch_read_mfcc(self._h, i, buf.ctypes.data, n))
-        return F.mfcc_rows(buf[:n].tobytes(), self._mfcc[1], self._mfcc[0].n_mels)
+        return F.mfcc_rows(self._sink_read("mfcc", i), self._mfcc[1], self._mfcc[0].n_mels)
 
     def read_mfcc_all(self):
         """Every utterance's (with a join: every programme's) rows through one device-to-host copy
         (jb_batch_read_mfcc_all)."""
-        B = self.num_outputs()
-        ns = [self.mfcc_size(i) for i in range(B)]
-        bufs = [np.empty(max(1, n), dtype=np.uint8) for n in ns]
-        arr = (C.c_void_p * max(1, B))(*[b.ctypes.data for b in bufs])
-        F.check(self._L.jb_batch_read_mfcc_all(self._h, arr))
-        return [F.mfcc_rows(b[:n].tobytes(), self._mfcc[1], self._mfcc[0].n_mels) for b, n in zip(bufs, ns)]
+        return [F.mfcc_rows(d, self._mfcc[1], self._mfcc[0].n_mels) for d in self._sink_read_all("mfcc")]
 
     def set_join(self, req):
         """jb_batch_set_join: one request per utterance -- F.JoinUtt entries, or (programme, pad_before, pad_after,

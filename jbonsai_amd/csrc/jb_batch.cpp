@@ -2678,47 +2678,39 @@ int jb_batch_loudness_group(jb_batch *hb, size_t utt, jb_loudness_group_report *
     return JB_OK;
 }
 
-int jb_batch_set_flac(jb_batch *hb, const jb_flac_opts *opts)
-{
-    if (!hb)
-        return JB_ERR_INVALID;
-    return ((Batch *)hb)->out.set_flac(opts);
-}
+// The byte sinks' entries (FLAC, sample formats, IMA ADPCM, filterbank, MFCC): a set entry each, and size, read and
+// read_all through the three helpers below, which differ per sink in nothing but the SynthSink
 
-int jb_batch_set_flac_meta(jb_batch *hb, const jb_flac_meta *m)
-{
-    if (!hb)
-        return JB_ERR_INVALID;
-    return ((Batch *)hb)->out.set_flac_meta(m);
-}
-
-int jb_batch_flac_size(jb_batch *hb, size_t utt, size_t *n_bytes)
+// jb_batch_*_size: the bytes of output u -- of a planned sink once its request is made, of FLAC after the run
+static int sink_size(jb_batch *hb, jb::SynthSink sink, size_t u, size_t *n_bytes)
 {
     Batch *b = (Batch *)hb;
-    if (!b || !n_bytes || utt >= b->out.num_outputs())
+    if (!b || !n_bytes || u >= b->out.num_outputs())
         return JB_ERR_INVALID;
-    jb::FlacOut o{};
-    int rc = b->out.read_flac_index(utt, &o);
-    if (rc)
-        return rc;
-    *n_bytes = (size_t)o.bytes;
-    return JB_OK;
+    jb::ByteSpan w{};
+    const int rc = b->out.sink_spans(sink, u, 1, &w);
+    if (!rc)
+        *n_bytes = (size_t)w.bytes;
+    return rc;
 }
 
-int jb_batch_read_flac(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
+// jb_batch_read_*: output u's bytes into dst[0 .. cap)
+static int sink_read(jb_batch *hb, jb::SynthSink sink, size_t u, uint8_t *dst, size_t cap, const char *who)
 {
     Batch *b = (Batch *)hb;
-    if (!b || utt >= b->out.num_outputs())
+    if (!b || u >= b->out.num_outputs())
         return JB_ERR_INVALID;
-    jb::FlacOut o{};
-    int rc = b->out.read_flac_index(utt, &o);
+    jb::ByteSpan w{};
+    const int rc = b->out.sink_spans(sink, u, 1, &w);
     if (rc)
         return rc;
-    if (cap < o.bytes)
+    if (cap < w.bytes) {
+        jb::set_error(std::string(who) + ": the buffer is too small");
         return JB_ERR_BUFFER;
-    if (!dst)
+    }
+    if (!dst && w.bytes)
         return JB_ERR_INVALID;
-    return b->out.read_flac(o, dst);
+    return b->out.sink_read(sink, w, dst);
 }
 
 // Each output's share of the host copy of a byte sink's slab into dst[u]; no destination of an output with bytes may
@@ -2734,7 +2726,7 @@ static int scatter_into(uint8_t *const *dst, const std::vector<jb::ByteSpan> &pl
     return JB_OK;
 }
 
-// jb_batch_read_{flac,formatted,adpcm,fbank,mfcc}_all: the used bytes of the sink's slab in one copy, then every output's share
+// jb_batch_read_*_all: the used bytes of the sink's slab in one copy, then every output's share
 static int read_bytes_all(jb_batch *hb, jb::SynthSink sink, uint8_t *const *dst)
 {
     Batch *b = (Batch *)hb;
@@ -2746,39 +2738,48 @@ static int read_bytes_all(jb_batch *hb, jb::SynthSink sink, uint8_t *const *dst)
     return rc ? rc : scatter_into(dst, places, host.get());
 }
 
+// The plan's entry of output u behind a sink's request (the block size of its ADPCM blocks, the shape of its features)
+static int sink_planned(jb_batch *hb, jb::SynthSink sink, size_t u)
+{
+    const Batch *b = (const Batch *)hb;
+    return b && u < b->out.num_outputs() ? b->out.sink_ready(sink, false) : JB_ERR_INVALID;
+}
+
+int jb_batch_set_flac(jb_batch *hb, const jb_flac_opts *opts)
+{
+    return hb ? ((Batch *)hb)->out.set_flac(opts) : JB_ERR_INVALID;
+}
+
+int jb_batch_set_flac_meta(jb_batch *hb, const jb_flac_meta *m)
+{
+    return hb ? ((Batch *)hb)->out.set_flac_meta(m) : JB_ERR_INVALID;
+}
+
+int jb_batch_flac_size(jb_batch *hb, size_t utt, size_t *n_bytes)
+{
+    return sink_size(hb, jb::SynthSink::Flac, utt, n_bytes);
+}
+
+int jb_batch_read_flac(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
+{
+    return sink_read(hb, jb::SynthSink::Flac, utt, dst, cap, "jb_batch_read_flac");
+}
+
 int jb_batch_read_flac_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Flac, dst); }
 
 int jb_batch_set_format(jb_batch *hb, const jb_format_opts *opts)
 {
-    if (!hb)
-        return JB_ERR_INVALID;
-    return ((Batch *)hb)->out.set_format(opts);
+    return hb ? ((Batch *)hb)->out.set_format(opts) : JB_ERR_INVALID;
 }
 
 int jb_batch_formatted_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || !n_bytes || utt >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    return b->out.format_size(utt, n_bytes);
+    return sink_size(hb, jb::SynthSink::Formatted, utt, n_bytes);
 }
 
 int jb_batch_read_formatted(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || utt >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    size_t nb = 0;
-    int rc = b->out.format_size(utt, &nb);
-    if (rc)
-        return rc;
-    if (cap < nb) {
-        jb::set_error("jb_batch_read_formatted: the buffer is too small");
-        return JB_ERR_BUFFER;
-    }
-    if (!dst && nb)
-        return JB_ERR_INVALID;
-    return b->out.read_formatted(utt, dst);
+    return sink_read(hb, jb::SynthSink::Formatted, utt, dst, cap, "jb_batch_read_formatted");
 }
 
 int jb_batch_read_formatted_all(jb_batch *hb, uint8_t *const *dst)
@@ -2788,160 +2789,89 @@ int jb_batch_read_formatted_all(jb_batch *hb, uint8_t *const *dst)
 
 int jb_batch_set_adpcm(jb_batch *hb, const jb_adpcm_opts *opts)
 {
-    if (!hb)
-        return JB_ERR_INVALID;
-    return ((Batch *)hb)->out.set_adpcm(opts);
+    return hb ? ((Batch *)hb)->out.set_adpcm(opts) : JB_ERR_INVALID;
 }
 
 int jb_batch_adpcm_size(jb_batch *hb, size_t utt, size_t *n_bytes)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || !n_bytes || utt >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
-    if (!w)
-        return JB_ERR_INVALID;
-    *n_bytes = (size_t)w->bytes;
-    return JB_OK;
+    return sink_size(hb, jb::SynthSink::Adpcm, utt, n_bytes);
 }
 
 int jb_batch_adpcm_block_align(jb_batch *hb, size_t utt, uint32_t *block_align)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || !block_align || utt >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
-    if (!w)
-        return JB_ERR_INVALID;
-    *block_align = w->A;
-    return JB_OK;
+    const int rc = block_align ? sink_planned(hb, jb::SynthSink::Adpcm, utt) : JB_ERR_INVALID;
+    if (!rc)
+        *block_align = ((Batch *)hb)->out.adpcm_place(utt).A;
+    return rc;
 }
 
 int jb_batch_read_adpcm(jb_batch *hb, size_t utt, uint8_t *dst, size_t cap)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || utt >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutAdpcmUtt *w = b->out.adpcm_place(utt);
-    if (!w)
-        return JB_ERR_INVALID;
-    if (cap < w->bytes) {
-        jb::set_error("jb_batch_read_adpcm: the buffer is too small");
-        return JB_ERR_BUFFER;
-    }
-    if (!dst && w->bytes)
-        return JB_ERR_INVALID;
-    return b->out.read_adpcm(utt, dst);
+    return sink_read(hb, jb::SynthSink::Adpcm, utt, dst, cap, "jb_batch_read_adpcm");
 }
 
 int jb_batch_read_adpcm_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Adpcm, dst); }
 
 int jb_batch_set_fbank(jb_batch *hb, const jb_fbank_opts *opts)
 {
-    if (!hb)
-        return JB_ERR_INVALID;
-    return ((Batch *)hb)->out.set_fbank(opts);
+    return hb ? ((Batch *)hb)->out.set_fbank(opts) : JB_ERR_INVALID;
 }
 
 int jb_batch_fbank_shape(jb_batch *hb, size_t unit, size_t *T, uint32_t *n_mels, uint32_t *hz)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || unit >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutFbankUtt *w = b->out.fbank_place(unit);
-    if (!w)
-        return JB_ERR_INVALID;
+    const int rc = sink_planned(hb, jb::SynthSink::Fbank, unit);
+    if (rc)
+        return rc;
+    const jb::OutputChain &out = ((Batch *)hb)->out;
     if (T)
-        *T = (size_t)w->T;
+        *T = (size_t)out.fbank_place(unit).T;
     if (n_mels)
-        *n_mels = b->out.fbank_mels();
+        *n_mels = out.fbank_mels();
     if (hz)
-        *hz = b->out.fbank_hz(unit);
+        *hz = out.fbank_hz(unit);
     return JB_OK;
 }
 
 int jb_batch_fbank_size(jb_batch *hb, size_t unit, size_t *n_bytes)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || !n_bytes || unit >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutFbankUtt *w = b->out.fbank_place(unit);
-    if (!w)
-        return JB_ERR_INVALID;
-    *n_bytes = (size_t)w->bytes;
-    return JB_OK;
+    return sink_size(hb, jb::SynthSink::Fbank, unit, n_bytes);
 }
 
 int jb_batch_read_fbank(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || unit >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutFbankUtt *w = b->out.fbank_place(unit);
-    if (!w)
-        return JB_ERR_INVALID;
-    if (cap < w->bytes) {
-        jb::set_error("jb_batch_read_fbank: the buffer is too small");
-        return JB_ERR_BUFFER;
-    }
-    if (!dst && w->bytes)
-        return JB_ERR_INVALID;
-    return b->out.read_fbank(unit, dst);
+    return sink_read(hb, jb::SynthSink::Fbank, unit, dst, cap, "jb_batch_read_fbank");
 }
 
 int jb_batch_read_fbank_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Fbank, dst); }
 
 int jb_batch_set_mfcc(jb_batch *hb, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts)
 {
-    if (!hb)
-        return JB_ERR_INVALID;
-    return ((Batch *)hb)->out.set_mfcc(fopts, opts);
+    return hb ? ((Batch *)hb)->out.set_mfcc(fopts, opts) : JB_ERR_INVALID;
 }
 
 int jb_batch_mfcc_shape(jb_batch *hb, size_t unit, size_t *T, uint32_t *width, uint32_t *hz)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || unit >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutMfccUtt *w = b->out.mfcc_place(unit);
-    if (!w)
-        return JB_ERR_INVALID;
+    const int rc = sink_planned(hb, jb::SynthSink::Mfcc, unit);
+    if (rc)
+        return rc;
+    const jb::OutputChain &out = ((Batch *)hb)->out;
     if (T)
-        *T = (size_t)w->T;
+        *T = (size_t)out.mfcc_place(unit).T;
     if (width)
-        *width = w->width;
+        *width = out.mfcc_place(unit).width;
     if (hz)
-        *hz = b->out.fbank_hz(unit);
+        *hz = out.fbank_hz(unit);
     return JB_OK;
 }
 
 int jb_batch_mfcc_size(jb_batch *hb, size_t unit, size_t *n_bytes)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || !n_bytes || unit >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutMfccUtt *w = b->out.mfcc_place(unit);
-    if (!w)
-        return JB_ERR_INVALID;
-    *n_bytes = (size_t)w->bytes;
-    return JB_OK;
+    return sink_size(hb, jb::SynthSink::Mfcc, unit, n_bytes);
 }
 
 int jb_batch_read_mfcc(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
 {
-    Batch *b = (Batch *)hb;
-    if (!b || unit >= b->out.num_outputs())
-        return JB_ERR_INVALID;
-    const jb::OutMfccUtt *w = b->out.mfcc_place(unit);
-    if (!w)
-        return JB_ERR_INVALID;
-    if (cap < w->bytes) {
-        jb::set_error("jb_batch_read_mfcc: the buffer is too small");
-        return JB_ERR_BUFFER;
-    }
-    if (!dst && w->bytes)
-        return JB_ERR_INVALID;
-    return b->out.read_mfcc(unit, dst);
+    return sink_read(hb, jb::SynthSink::Mfcc, unit, dst, cap, "jb_batch_read_mfcc");
 }
 
 int jb_batch_read_mfcc_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Mfcc, dst); }

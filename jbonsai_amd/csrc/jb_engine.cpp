@@ -1848,12 +1848,12 @@ int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
             shares.push_back({w.off, w.bytes});
         if (rc || (rc = jb::hand_out(host.get(), 1, shares, pcm + lo, n_samples + lo)))
             return rc;
-        for (size_t p = 0; rq.sink == jb::SynthSink::Adpcm && rq.adpcm_samples && p < places.size(); p++)
-            rq.adpcm_samples[lo + p] = rq.join ? (size_t)b->out.programme(p).n : b->out.samples(p);
-        for (size_t p = 0; rq.sink == jb::SynthSink::Fbank && rq.fbank_frames && p < places.size(); p++)
-            rq.fbank_frames[lo + p] = (size_t)b->out.fbank_place(p)->T;
-        for (size_t p = 0; rq.sink == jb::SynthSink::Mfcc && rq.fbank_frames && p < places.size(); p++)
-            rq.fbank_frames[lo + p] = (size_t)b->out.mfcc_place(p)->T;
+        // the request's count of each output: the samples its ADPCM blocks encode, or its frames of features
+        for (size_t p = 0; rq.counts && p < places.size(); p++)
+            rq.counts[lo + p] = rq.sink == jb::SynthSink::Fbank  ? (size_t)b->out.fbank_place(p).T
+                                : rq.sink == jb::SynthSink::Mfcc ? (size_t)b->out.mfcc_place(p).T
+                                : rq.join                        ? (size_t)b->out.programme(p).n
+                                                                 : b->out.samples(p);
         return JB_OK;
     }
     if (rq.join) {
@@ -2044,7 +2044,7 @@ static jb::SynthRequest &request_adpcm(jb::SynthRequest &rq, const jb_adpcm_opts
     rq.sink = jb::SynthSink::Adpcm;
     rq.i16 = true;
     rq.adpcm = opts;
-    rq.adpcm_samples = n_samples;
+    rq.counts = n_samples;
     return rq;
 }
 
@@ -2053,7 +2053,16 @@ static jb::SynthRequest &request_fbank(jb::SynthRequest &rq, const jb_fbank_opts
     rq.sink = jb::SynthSink::Fbank;
     rq.i16 = false;
     rq.fbank = opts;
-    rq.fbank_frames = n_frames;
+    rq.counts = n_frames;
+    return rq;
+}
+
+static jb::SynthRequest &request_mfcc(jb::SynthRequest &rq, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
+                                      size_t *n_frames)
+{
+    request_fbank(rq, fopts, n_frames);
+    rq.sink = jb::SynthSink::Mfcc;
+    rq.mfcc = opts;
     return rq;
 }
 
@@ -2155,6 +2164,68 @@ static int synthesize_each(const jb_engine *const *engines, jb::SynthRequest rq)
     return jb::synthesize_batch_impl(rq);
 }
 
+// The options of the request's sink, under the entry's name (the FLAC checks name their struct instead)
+static int check_sink_opts(const jb::SynthRequest &rq, const char *who)
+{
+    int rc = JB_OK;
+    switch (rq.sink) {
+    case jb::SynthSink::Pcm:
+        return JB_OK;
+    case jb::SynthSink::Flac:
+        rc = jb::flac_check_opts(rq.flac, nullptr);
+        return rc ? rc : jb::flac_check_meta(rq.flac_meta, nullptr);
+    case jb::SynthSink::Formatted:
+        if (!rq.fmt) {
+            jb::set_error(std::string(who) + ": opts is NULL");
+            return JB_ERR_INVALID;
+        }
+        return jb::format_check_opts(rq.fmt->format, rq.fmt->dither, who);
+    case jb::SynthSink::Adpcm:
+        return jb::adpcm_check_opts((const jb::AdpcmOpts *)rq.adpcm, who);
+    case jb::SynthSink::Fbank:
+        return jb::fbank_check_opts((const jb::FbankOpts *)rq.fbank, who);
+    case jb::SynthSink::Mfcc:
+        rc = jb::mfcc_check_fbank((const jb::FbankOpts *)rq.fbank, who);
+        return rc ? rc : jb::mfcc_check_opts((const jb::MfccOpts *)rq.mfcc, rq.fbank->n_mels, who);
+    }
+    return JB_ERR_INVALID;
+}
+
+// jb_synthesize_programme*: the join options
+static int check_join_entry(const jb_join_opts *j, size_t n_utts, const char *who)
+{
+    if (!j) {
+        jb::set_error(std::string(who) + ": join is NULL");
+        return JB_ERR_INVALID;
+    }
+    for (double ms : {j->lead_ms, j->gap_ms, j->trail_ms, j->fade_ms})
+        if (!(ms >= 0.0) || !std::isfinite(ms)) {
+            jb::set_error(std::string(who) + ": lead_ms, gap_ms, trail_ms and fade_ms are finite and not negative");
+            return JB_ERR_INVALID;
+        }
+    if (j->reserved[0] || j->reserved[1]) {
+        jb::set_error(std::string(who) + ": reserved must be 0");
+        return JB_ERR_INVALID;
+    }
+    if (n_utts == 0) {
+        jb::set_error(std::string(who) + ": a programme has at least one utterance");
+        return JB_ERR_INVALID;
+    }
+    return JB_OK;
+}
+
+// What every byte-sink and programme entry does behind its argument marshalling.  rq carries the sink, its options and
+// (programme: a jb_synthesize_programme* entry, which demands one) the join; engines: the _each form, utterance u under
+// engines[u].  The sink's options, then the join's, are checked under the entry's name before any device is touched
+static int synthesize_entry(const char *who, const jb::SynthRequest &rq, const jb_engine *const *engines,
+                            bool programme)
+{
+    int rc = check_sink_opts(rq, who);
+    if (rc || (programme && (rc = check_join_entry(rq.join, rq.n_utts, who))))
+        return rc;
+    return engines ? synthesize_each(engines, rq) : jb::synthesize_batch_impl(rq);
+}
+
 extern "C" {
 
 int jb_synthesize_batch_each(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
@@ -2171,15 +2242,16 @@ int jb_synthesize_batch_each_i16(const jb_engine *const *engines, const char *co
     return synthesize_each(engines, rq);
 }
 
+// The byte sinks' entries: per sink batch, batch_each, single and programme (FLAC: with and without its metadata).
+// Each marshals its arguments into a request and goes through synthesize_entry; a single form is its batch form of one
+// utterance on the current device, and reports under that name
+
 int jb_synthesize_batch_flac_meta(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                                   int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta, uint8_t **flac,
                                   size_t *n_bytes)
 {
-    int rc = jb::flac_check_opts(opts, nullptr);
-    if (rc || (rc = jb::flac_check_meta(meta, nullptr)))
-        return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)flac, n_bytes);
-    return jb::synthesize_batch_impl(request_flac(rq, opts, meta));
+    return synthesize_entry("jb_synthesize_batch_flac_meta", request_flac(rq, opts, meta), nullptr, false);
 }
 
 int jb_synthesize_batch_flac(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
@@ -2192,11 +2264,8 @@ int jb_synthesize_batch_each_flac_meta(const jb_engine *const *engines, const ch
                                        const size_t *line_off, size_t n_utts, int32_t device, const jb_flac_opts *opts,
                                        const jb_flac_meta *meta, uint8_t **flac, size_t *n_bytes)
 {
-    int rc = jb::flac_check_opts(opts, nullptr);
-    if (rc || (rc = jb::flac_check_meta(meta, nullptr)))
-        return rc;
     jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)flac, n_bytes);
-    return synthesize_each(engines, request_flac(rq, opts, meta));
+    return synthesize_entry("jb_synthesize_batch_each_flac_meta", request_flac(rq, opts, meta), engines, false);
 }
 
 int jb_synthesize_batch_each_flac(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
@@ -2221,34 +2290,28 @@ int jb_synthesize_flac(const jb_engine *e, const char *const *lines, size_t n, c
     return jb_synthesize_flac_meta(e, lines, n, opts, nullptr, flac, n_bytes);
 }
 
-static int check_format_entry(const jb_format_opts *opts, const char *who)
+int jb_synthesize_programme_flac_meta(const jb_engine *e, const char *const *lines, const size_t *line_off,
+                                      size_t n_utts, int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta,
+                                      const jb_join_opts *join, uint8_t **flac, size_t *n_bytes, uint64_t *starts)
 {
-    if (!opts) {
-        jb::set_error(std::string(who) + ": opts is NULL");
-        return JB_ERR_INVALID;
-    }
-    return jb::format_check_opts(opts->format, opts->dither, who);
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)flac, n_bytes);
+    request_join(request_flac(rq, opts, meta), join, starts);
+    return synthesize_entry("jb_synthesize_programme_flac_meta", rq, nullptr, true);
 }
 
 int jb_synthesize_batch_formatted(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                                   int32_t device, const jb_format_opts *opts, uint8_t **bytes, size_t *n_bytes)
 {
-    int rc = check_format_entry(opts, "jb_synthesize_batch_formatted");
-    if (rc)
-        return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return jb::synthesize_batch_impl(request_formatted(rq, opts));
+    return synthesize_entry("jb_synthesize_batch_formatted", request_formatted(rq, opts), nullptr, false);
 }
 
 int jb_synthesize_batch_each_formatted(const jb_engine *const *engines, const char *const *lines,
                                        const size_t *line_off, size_t n_utts, int32_t device,
                                        const jb_format_opts *opts, uint8_t **bytes, size_t *n_bytes)
 {
-    int rc = check_format_entry(opts, "jb_synthesize_batch_each_formatted");
-    if (rc)
-        return rc;
     jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return synthesize_each(engines, request_formatted(rq, opts));
+    return synthesize_entry("jb_synthesize_batch_each_formatted", request_formatted(rq, opts), engines, false);
 }
 
 int jb_synthesize_formatted(const jb_engine *e, const char *const *lines, size_t n, const jb_format_opts *opts,
@@ -2260,26 +2323,29 @@ int jb_synthesize_formatted(const jb_engine *e, const char *const *lines, size_t
     return jb_synthesize_batch_formatted(e, lines, off, 1, -1, opts, bytes, n_bytes);
 }
 
+int jb_synthesize_programme_formatted(const jb_engine *e, const char *const *lines, const size_t *line_off,
+                                      size_t n_utts, int32_t device, const jb_format_opts *opts,
+                                      const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, uint64_t *starts)
+{
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    request_join(request_formatted(rq, opts), join, starts);
+    return synthesize_entry("jb_synthesize_programme_formatted", rq, nullptr, true);
+}
+
 int jb_synthesize_batch_adpcm(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                               int32_t device, const jb_adpcm_opts *opts, uint8_t **bytes, size_t *n_bytes,
                               size_t *n_samples)
 {
-    int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_batch_adpcm");
-    if (rc)
-        return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return jb::synthesize_batch_impl(request_adpcm(rq, opts, n_samples));
+    return synthesize_entry("jb_synthesize_batch_adpcm", request_adpcm(rq, opts, n_samples), nullptr, false);
 }
 
 int jb_synthesize_batch_each_adpcm(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
                                    size_t n_utts, int32_t device, const jb_adpcm_opts *opts, uint8_t **bytes,
                                    size_t *n_bytes, size_t *n_samples)
 {
-    int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_batch_each_adpcm");
-    if (rc)
-        return rc;
     jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return synthesize_each(engines, request_adpcm(rq, opts, n_samples));
+    return synthesize_entry("jb_synthesize_batch_each_adpcm", request_adpcm(rq, opts, n_samples), engines, false);
 }
 
 int jb_synthesize_adpcm(const jb_engine *e, const char *const *lines, size_t n, const jb_adpcm_opts *opts,
@@ -2291,75 +2357,29 @@ int jb_synthesize_adpcm(const jb_engine *e, const char *const *lines, size_t n, 
     return jb_synthesize_batch_adpcm(e, lines, off, 1, -1, opts, bytes, n_bytes, n_samples);
 }
 
-static jb::SynthRequest &request_mfcc(jb::SynthRequest &rq, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
-                                      size_t *n_frames)
+int jb_synthesize_programme_adpcm(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                  int32_t device, const jb_adpcm_opts *opts, const jb_join_opts *join, uint8_t **bytes,
+                                  size_t *n_bytes, size_t *n_samples, uint64_t *starts)
 {
-    rq.sink = jb::SynthSink::Mfcc;
-    rq.i16 = false;
-    rq.fbank = fopts;
-    rq.mfcc = opts;
-    rq.fbank_frames = n_frames;
-    return rq;
-}
-
-// both option structs of a jb_synthesize*_mfcc call, before any device is touched
-static int check_mfcc_entry(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, const char *who)
-{
-    const int rc = jb::mfcc_check_fbank((const jb::FbankOpts *)fopts, who);
-    return rc ? rc : jb::mfcc_check_opts((const jb::MfccOpts *)opts, fopts->n_mels, who);
-}
-
-int jb_synthesize_batch_mfcc(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                             int32_t device, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, uint8_t **bytes,
-                             size_t *n_bytes, size_t *n_frames)
-{
-    const int rc = check_mfcc_entry(fopts, opts, "jb_synthesize_batch_mfcc");
-    if (rc)
-        return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return jb::synthesize_batch_impl(request_mfcc(rq, fopts, opts, n_frames));
-}
-
-int jb_synthesize_batch_each_mfcc(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
-                                  size_t n_utts, int32_t device, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
-                                  uint8_t **bytes, size_t *n_bytes, size_t *n_frames)
-{
-    const int rc = check_mfcc_entry(fopts, opts, "jb_synthesize_batch_each_mfcc");
-    if (rc)
-        return rc;
-    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return synthesize_each(engines, request_mfcc(rq, fopts, opts, n_frames));
-}
-
-int jb_synthesize_mfcc(const jb_engine *e, const char *const *lines, size_t n, const jb_fbank_opts *fopts,
-                       const jb_mfcc_opts *opts, uint8_t **bytes, size_t *n_bytes, size_t *n_frames)
-{
-    if (!bytes || !n_bytes)
-        return JB_ERR_INVALID;
-    size_t off[2] = {0, n};
-    return jb_synthesize_batch_mfcc(e, lines, off, 1, -1, fopts, opts, bytes, n_bytes, n_frames);
+    request_join(request_adpcm(rq, opts, n_samples), join, starts);
+    return synthesize_entry("jb_synthesize_programme_adpcm", rq, nullptr, true);
 }
 
 int jb_synthesize_batch_fbank(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                               int32_t device, const jb_fbank_opts *opts, uint8_t **bytes, size_t *n_bytes,
                               size_t *n_frames)
 {
-    int rc = jb::fbank_check_opts((const jb::FbankOpts *)opts, "jb_synthesize_batch_fbank");
-    if (rc)
-        return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return jb::synthesize_batch_impl(request_fbank(rq, opts, n_frames));
+    return synthesize_entry("jb_synthesize_batch_fbank", request_fbank(rq, opts, n_frames), nullptr, false);
 }
 
 int jb_synthesize_batch_each_fbank(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
                                    size_t n_utts, int32_t device, const jb_fbank_opts *opts, uint8_t **bytes,
                                    size_t *n_bytes, size_t *n_frames)
 {
-    int rc = jb::fbank_check_opts((const jb::FbankOpts *)opts, "jb_synthesize_batch_each_fbank");
-    if (rc)
-        return rc;
     jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return synthesize_each(engines, request_fbank(rq, opts, n_frames));
+    return synthesize_entry("jb_synthesize_batch_each_fbank", request_fbank(rq, opts, n_frames), engines, false);
 }
 
 int jb_synthesize_fbank(const jb_engine *e, const char *const *lines, size_t n, const jb_fbank_opts *opts,
@@ -2371,94 +2391,38 @@ int jb_synthesize_fbank(const jb_engine *e, const char *const *lines, size_t n, 
     return jb_synthesize_batch_fbank(e, lines, off, 1, -1, opts, bytes, n_bytes, n_frames);
 }
 
-// jb_synthesize_programme*: the options checked before any device is touched
-static int check_join_entry(const jb_join_opts *j, size_t n_utts, const char *who)
-{
-    if (!j) {
-        jb::set_error(std::string(who) + ": join is NULL");
-        return JB_ERR_INVALID;
-    }
-    for (double ms : {j->lead_ms, j->gap_ms, j->trail_ms, j->fade_ms})
-        if (!(ms >= 0.0) || !std::isfinite(ms)) {
-            jb::set_error(std::string(who) + ": lead_ms, gap_ms, trail_ms and fade_ms are finite and not negative");
-            return JB_ERR_INVALID;
-        }
-    if (j->reserved[0] || j->reserved[1]) {
-        jb::set_error(std::string(who) + ": reserved must be 0");
-        return JB_ERR_INVALID;
-    }
-    if (n_utts == 0) {
-        jb::set_error(std::string(who) + ": a programme has at least one utterance");
-        return JB_ERR_INVALID;
-    }
-    return JB_OK;
-}
-
-int jb_synthesize_programme(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                            int32_t device, const jb_join_opts *join, double **pcm, size_t *n_samples, uint64_t *starts)
-{
-    int rc = check_join_entry(join, n_utts, "jb_synthesize_programme");
-    if (rc)
-        return rc;
-    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
-    return jb::synthesize_batch_impl(request_join(rq, join, starts));
-}
-
-int jb_synthesize_programme_i16(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                                int32_t device, const jb_join_opts *join, int16_t **pcm, size_t *n_samples,
-                                uint64_t *starts)
-{
-    int rc = check_join_entry(join, n_utts, "jb_synthesize_programme_i16");
-    if (rc)
-        return rc;
-    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
-    rq.i16 = true;
-    return jb::synthesize_batch_impl(request_join(rq, join, starts));
-}
-
-int jb_synthesize_programme_flac_meta(const jb_engine *e, const char *const *lines, const size_t *line_off,
-                                      size_t n_utts, int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta,
-                                      const jb_join_opts *join, uint8_t **flac, size_t *n_bytes, uint64_t *starts)
-{
-    int rc = jb::flac_check_opts(opts, nullptr);
-    if (rc || (rc = jb::flac_check_meta(meta, nullptr)) ||
-        (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_flac_meta")))
-        return rc;
-    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)flac, n_bytes);
-    return jb::synthesize_batch_impl(request_join(request_flac(rq, opts, meta), join, starts));
-}
-
-int jb_synthesize_programme_formatted(const jb_engine *e, const char *const *lines, const size_t *line_off,
-                                      size_t n_utts, int32_t device, const jb_format_opts *opts,
-                                      const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, uint64_t *starts)
-{
-    int rc = check_format_entry(opts, "jb_synthesize_programme_formatted");
-    if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_formatted")))
-        return rc;
-    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return jb::synthesize_batch_impl(request_join(request_formatted(rq, opts), join, starts));
-}
-
-int jb_synthesize_programme_adpcm(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
-                                  int32_t device, const jb_adpcm_opts *opts, const jb_join_opts *join, uint8_t **bytes,
-                                  size_t *n_bytes, size_t *n_samples, uint64_t *starts)
-{
-    int rc = jb::adpcm_check_opts((const jb::AdpcmOpts *)opts, "jb_synthesize_programme_adpcm");
-    if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_adpcm")))
-        return rc;
-    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return jb::synthesize_batch_impl(request_join(request_adpcm(rq, opts, n_samples), join, starts));
-}
-
 int jb_synthesize_programme_fbank(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
                                   int32_t device, const jb_fbank_opts *opts, const jb_join_opts *join, uint8_t **bytes,
                                   size_t *n_bytes, size_t *n_frames, uint64_t *starts)
 {
-    int rc = jb::fbank_check_opts((const jb::FbankOpts *)opts, "jb_synthesize_programme_fbank");
-    if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_fbank")))
-        return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return jb::synthesize_batch_impl(request_join(request_fbank(rq, opts, n_frames), join, starts));
+    request_join(request_fbank(rq, opts, n_frames), join, starts);
+    return synthesize_entry("jb_synthesize_programme_fbank", rq, nullptr, true);
+}
+
+int jb_synthesize_batch_mfcc(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                             int32_t device, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, uint8_t **bytes,
+                             size_t *n_bytes, size_t *n_frames)
+{
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return synthesize_entry("jb_synthesize_batch_mfcc", request_mfcc(rq, fopts, opts, n_frames), nullptr, false);
+}
+
+int jb_synthesize_batch_each_mfcc(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
+                                  uint8_t **bytes, size_t *n_bytes, size_t *n_frames)
+{
+    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return synthesize_entry("jb_synthesize_batch_each_mfcc", request_mfcc(rq, fopts, opts, n_frames), engines, false);
+}
+
+int jb_synthesize_mfcc(const jb_engine *e, const char *const *lines, size_t n, const jb_fbank_opts *fopts,
+                       const jb_mfcc_opts *opts, uint8_t **bytes, size_t *n_bytes, size_t *n_frames)
+{
+    if (!bytes || !n_bytes)
+        return JB_ERR_INVALID;
+    size_t off[2] = {0, n};
+    return jb_synthesize_batch_mfcc(e, lines, off, 1, -1, fopts, opts, bytes, n_bytes, n_frames);
 }
 
 int jb_synthesize_programme_mfcc(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
@@ -2466,11 +2430,25 @@ int jb_synthesize_programme_mfcc(const jb_engine *e, const char *const *lines, c
                                  const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, size_t *n_frames,
                                  uint64_t *starts)
 {
-    int rc = check_mfcc_entry(fopts, opts, "jb_synthesize_programme_mfcc");
-    if (rc || (rc = check_join_entry(join, n_utts, "jb_synthesize_programme_mfcc")))
-        return rc;
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
-    return jb::synthesize_batch_impl(request_join(request_mfcc(rq, fopts, opts, n_frames), join, starts));
+    request_join(request_mfcc(rq, fopts, opts, n_frames), join, starts);
+    return synthesize_entry("jb_synthesize_programme_mfcc", rq, nullptr, true);
+}
+
+int jb_synthesize_programme(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                            int32_t device, const jb_join_opts *join, double **pcm, size_t *n_samples, uint64_t *starts)
+{
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
+    return synthesize_entry("jb_synthesize_programme", request_join(rq, join, starts), nullptr, true);
+}
+
+int jb_synthesize_programme_i16(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                int32_t device, const jb_join_opts *join, int16_t **pcm, size_t *n_samples,
+                                uint64_t *starts)
+{
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
+    rq.i16 = true;
+    return synthesize_entry("jb_synthesize_programme_i16", request_join(rq, join, starts), nullptr, true);
 }
 
 int jb_synthesize(const jb_engine *e, const char *const *lines, size_t n, double **pcm, size_t *n_samples)

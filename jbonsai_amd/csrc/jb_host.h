@@ -63,11 +63,11 @@ struct SynthRequest {
     const jb_flac_opts *flac = nullptr;      // Flac: both may be null (the defaults; no MD5 / SEEKTABLE request)
     const jb_flac_meta *flac_meta = nullptr;
     const jb_format_opts *fmt = nullptr;     // Formatted
-    const jb_adpcm_opts *adpcm = nullptr;    // Adpcm; adpcm_samples[u] (may be null): the samples output u's blocks encode
-    size_t *adpcm_samples = nullptr;
-    const jb_fbank_opts *fbank = nullptr;    // Fbank; fbank_frames[u] (may be null): the frames of output u
-    size_t *fbank_frames = nullptr;
-    const jb_mfcc_opts *mfcc = nullptr;      // Mfcc: behind the filterbank options of `fbank`; fbank_frames as Fbank's
+    const jb_adpcm_opts *adpcm = nullptr;    // Adpcm
+    const jb_fbank_opts *fbank = nullptr;    // Fbank
+    const jb_mfcc_opts *mfcc = nullptr;      // Mfcc: behind the filterbank options of `fbank`
+    size_t *counts = nullptr;                // counts[u] (may be null), by the sink: the samples output u's blocks
+                                             // encode (Adpcm), or its frames (Fbank, Mfcc)
     const jb_join_opts *join = nullptr;      // jb_synthesize_programme*: all utterances are one programme, the one
     uint64_t *join_starts = nullptr;         // output; join_starts[u] (may be null): each member's first sample
     void **out = nullptr;                    // [n_utts], or [1] with a join: malloc'ed PCM or bytes of each output
@@ -666,26 +666,23 @@ struct OutputChain {
     int read_loudness_group(size_t u, LoudnessGroupResult *r);
     bool report_on() const { return ln_report != 0; }
     int read_loudness_range(size_t u, bool of_group, LoudnessRange *r);
-    int read_flac_index(size_t u, FlacOut *o);
-    int read_flac(const FlacOut &o, uint8_t *dst);
-    // the formatted bytes: utterance u's count (known once a format is set) and its bytes
-    int format_size(size_t u, size_t *n_bytes) const;
-    int read_formatted(size_t u, uint8_t *dst);
-    // the ADPCM blocks: utterance u's place, byte count and block size (known once the request is made; null without
-    // one) and its bytes
-    const OutAdpcmUtt *adpcm_place(size_t u) const;
-    int read_adpcm(size_t u, uint8_t *dst);
-    // the features: unit u's place and geometry (known once the request is made; null without one), its rate, its bytes
-    const OutFbankUtt *fbank_place(size_t u) const;
+    // The byte sinks (every SynthSink but Pcm) through one path; byte_sink() holds what they differ in.
+    // sink_ready: JB_ERR_INVALID with the sink's message when it was not requested or, with `run`, has not run.
+    // sink_spans: the places of the outputs [u0, u0 + n) in the sink's slab -- from the plan, known once the request
+    // is made; FLAC's from the device's index in one small copy, so after the run only.
+    // sink_read: the bytes of an output at the span sink_spans gave (after the run)
+    int sink_ready(SynthSink sink, bool run) const;
+    int sink_spans(SynthSink sink, size_t u0, size_t n, ByteSpan *w);
+    int sink_read(SynthSink sink, const ByteSpan &w, uint8_t *dst);
+    // every output of a byte sink: the used part of its slab in one copy, output u at host + places[u].off
+    int read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host);
+    // the plan's entry of output u, behind sink_ready(sink, false): the ADPCM block size, the features' frames and
+    // width, and the rate and filters the features are computed at
+    const OutAdpcmUtt &adpcm_place(size_t u) const { return plan.adpcm[u]; }
+    const OutFbankUtt &fbank_place(size_t u) const { return plan.fbank[u]; }
+    const OutMfccUtt &mfcc_place(size_t u) const { return plan.mfcc[u]; }
     uint32_t fbank_mels() const { return fb_p.n_mels; }
     uint32_t fbank_hz(size_t u) const { return joined() ? plan.units[u].hz : plan.utt[u].hz; }
-    int read_fbank(size_t u, uint8_t *dst);
-    // the cepstral rows: unit u's place, frames and width (known once the request is made; null without one), its bytes
-    const OutMfccUtt *mfcc_place(size_t u) const;
-    int read_mfcc(size_t u, uint8_t *dst);
-    // every output of a byte sink: the used part of its slab in one copy, output u at host + places[u].off (FLAC:
-    // the streams' sizes and places come from the device's index, one small copy first; the others' from the plan)
-    int read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host);
     // the join: what the encoders' entries index (the programmes, or the utterances without a request), an
     // utterance's programme (-1 without a request) and start, a programme's place, members and PCM
     bool joined() const { return plan.join.slab != OutSlab::None; }
@@ -894,9 +891,15 @@ private:
     int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);
     int prepare_fbank(), select_fbank(const RedoScope *scope), launch_fbank(bool redo);
     int prepare_mfcc(), select_mfcc(const RedoScope *scope), launch_mfcc(bool redo);
-    int format_ready() const;
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
-    int flac_ready() const;
+    struct ByteSink {
+        bool on;                       // the sink is requested
+        const char *not_run, *not_set; // sink_ready's messages
+        const void *slab;              // its outputs on the device
+        bool planned;                  // the outputs' places come from the plan (FLAC: from the device's index)
+        ByteSpan span;                 // planned: output u's place
+    };
+    ByteSink byte_sink(SynthSink sink, size_t u = 0) const;
     // the used bytes of a byte slab in one copy (wait: for the batch first, as Batch::read does)
     int read_used(const void *src, uint64_t bytes, bool wait, std::unique_ptr<uint8_t[]> *host);
 };

@@ -1708,19 +1708,6 @@ int OutputChain::read_loudness_range(size_t u, bool of_group, LoudnessRange *r)
     return rc ? rc : b.read(ln.r128 + (of_group ? (size_t)b.B + ln_groups.group_of[u] : u), r, sizeof *r);
 }
 
-int OutputChain::flac_ready() const
-{
-    return check_ready(flac_on, "FLAC: the batch has not run", "FLAC: jb_batch_set_flac was not called");
-}
-
-int OutputChain::read_flac_index(size_t u, FlacOut *o)
-{
-    int rc = flac_ready();
-    return rc ? rc : b.read(fl.res + u, o, sizeof *o);
-}
-
-int OutputChain::read_flac(const FlacOut &o, uint8_t *dst) { return b.read(fl.out + o.off, dst, (size_t)o.bytes, false); }
-
 int OutputChain::read_programme(size_t p, bool i16, void *dst)
 {
     int rc = check_ready(joined(), "join: the batch has not run", "join: jb_batch_set_join was not called");
@@ -1736,116 +1723,88 @@ int OutputChain::read_programme(size_t p, bool i16, void *dst)
     return w.n ? b.read((const char *)slab[(size_t)plan.join.slab] + w.off * elem, dst, (size_t)w.n * elem) : b.sync();
 }
 
-const OutAdpcmUtt *OutputChain::adpcm_place(size_t u) const
+// Output u's place among `places` (each with a byte offset `off` and `bytes`); none before the request has planned it
+template <class T> static ByteSpan span_of(const std::vector<T> &places, size_t u)
 {
-    if (!ad_on) {
-        set_error("ADPCM: jb_batch_set_adpcm was not called");
-        return nullptr;
-    }
-    return &plan.adpcm[u];
+    return u < places.size() ? ByteSpan{places[u].off, places[u].bytes} : ByteSpan{};
 }
 
-int OutputChain::read_adpcm(size_t u, uint8_t *dst)
+OutputChain::ByteSink OutputChain::byte_sink(SynthSink sink, size_t u) const
 {
-    int rc = check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called");
+    switch (sink) {
+    case SynthSink::Flac:
+        return {flac_on, "FLAC: the batch has not run", "FLAC: jb_batch_set_flac was not called", fl.out, false, {}};
+    case SynthSink::Formatted:
+        return {fmt_on, "format: the batch has not run", "format: jb_batch_set_format was not called",
+                slab[(size_t)OutSlab::Fmt], true, span_of(plan.fmt, u)};
+    case SynthSink::Adpcm:
+        return {ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called",
+                slab[(size_t)OutSlab::Adpcm], true, span_of(plan.adpcm, u)};
+    case SynthSink::Fbank:
+        return {fb_on, "fbank: the batch has not run", "fbank: jb_batch_set_fbank was not called",
+                slab[(size_t)OutSlab::Feat], true, span_of(plan.fbank, u)};
+    case SynthSink::Mfcc:
+        return {mf_on, "mfcc: the batch has not run", "mfcc: jb_batch_set_mfcc was not called",
+                slab[(size_t)OutSlab::Mfcc], true, span_of(plan.mfcc, u)};
+    case SynthSink::Pcm:
+        break;
+    }
+    return {false, "", "PCM is no byte sink", nullptr, true, {}};
+}
+
+int OutputChain::sink_ready(SynthSink sink, bool run) const
+{
+    const ByteSink s = byte_sink(sink);
+    if (s.on && (ready || !run))
+        return JB_OK;
+    set_error(s.on ? s.not_run : s.not_set);
+    return JB_ERR_INVALID;
+}
+
+int OutputChain::sink_spans(SynthSink sink, size_t u0, size_t n, ByteSpan *w)
+{
+    const bool planned = byte_sink(sink).planned;
+    int rc = sink_ready(sink, !planned);
     if (rc)
         return rc;
-    const OutAdpcmUtt &w = plan.adpcm[u];
-    return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Adpcm] + w.off, dst, (size_t)w.bytes) : b.sync();
-}
-
-const OutFbankUtt *OutputChain::fbank_place(size_t u) const
-{
-    if (!fb_on) {
-        set_error("fbank: jb_batch_set_fbank was not called");
-        return nullptr;
+    if (planned) {
+        for (size_t i = 0; i < n; i++)
+            w[i] = byte_sink(sink, u0 + i).span;
+        return JB_OK;
     }
-    return &plan.fbank[u];
-}
-
-int OutputChain::read_fbank(size_t u, uint8_t *dst)
-{
-    int rc = check_ready(fb_on, "fbank: the batch has not run", "fbank: jb_batch_set_fbank was not called");
-    if (rc)
+    // the streams' sizes and places: the device's index, in one copy
+    FlacOut one{};
+    std::vector<FlacOut> many(n > 1 ? n : 0);
+    FlacOut *res = n > 1 ? many.data() : &one;
+    if ((rc = n ? b.read(fl.res + u0, res, sizeof(FlacOut) * n) : b.sync()))
         return rc;
-    const OutFbankUtt &w = plan.fbank[u];
-    return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Feat] + w.off, dst, (size_t)w.bytes) : b.sync();
-}
-
-const OutMfccUtt *OutputChain::mfcc_place(size_t u) const
-{
-    if (!mf_on) {
-        set_error("mfcc: jb_batch_set_mfcc was not called");
-        return nullptr;
-    }
-    return &plan.mfcc[u];
-}
-
-int OutputChain::read_mfcc(size_t u, uint8_t *dst)
-{
-    int rc = check_ready(mf_on, "mfcc: the batch has not run", "mfcc: jb_batch_set_mfcc was not called");
-    if (rc)
-        return rc;
-    const OutMfccUtt &w = plan.mfcc[u];
-    return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Mfcc] + w.off, dst, (size_t)w.bytes) : b.sync();
-}
-
-int OutputChain::format_ready() const
-{
-    return check_ready(fmt_on, "format: the batch has not run", "format: jb_batch_set_format was not called");
-}
-
-int OutputChain::format_size(size_t u, size_t *n_bytes) const
-{
-    if (!fmt_on) {
-        set_error("format: jb_batch_set_format was not called");
-        return JB_ERR_INVALID;
-    }
-    *n_bytes = (size_t)plan.fmt[u].bytes;
+    for (size_t i = 0; i < n; i++)
+        w[i] = ByteSpan{res[i].off, res[i].bytes};
     return JB_OK;
 }
 
-int OutputChain::read_formatted(size_t u, uint8_t *dst)
+// (the read of a planned sink waits for the batch, an output of no bytes too; FLAC's index read has waited already)
+int OutputChain::sink_read(SynthSink sink, const ByteSpan &w, uint8_t *dst)
 {
-    int rc = format_ready();
+    const ByteSink s = byte_sink(sink);
+    const int rc = sink_ready(sink, true);
     if (rc)
         return rc;
-    const OutFmtUtt &w = plan.fmt[u];
-    return w.bytes ? b.read((const uint8_t *)slab[(size_t)OutSlab::Fmt] + w.off, dst, (size_t)w.bytes) : b.sync();
+    if (w.bytes)
+        return b.read((const uint8_t *)s.slab + w.off, dst, (size_t)w.bytes, s.planned);
+    return s.planned ? b.sync() : JB_OK;
 }
 
 int OutputChain::read_bytes_all(SynthSink sink, std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host)
 {
-    int rc = sink == SynthSink::Flac        ? flac_ready()
-             : sink == SynthSink::Formatted ? format_ready()
-             : sink == SynthSink::Adpcm
-                 ? check_ready(ad_on, "ADPCM: the batch has not run", "ADPCM: jb_batch_set_adpcm was not called")
-             : sink == SynthSink::Fbank
-                 ? check_ready(fb_on, "fbank: the batch has not run", "fbank: jb_batch_set_fbank was not called")
-             : sink == SynthSink::Mfcc
-                 ? check_ready(mf_on, "mfcc: the batch has not run", "mfcc: jb_batch_set_mfcc was not called")
-                 : JB_ERR_INVALID;
+    int rc = sink_ready(sink, true);
     if (rc)
         return rc;
     places->assign(num_outputs(), ByteSpan{});
-    if (sink == SynthSink::Flac) {
-        std::vector<FlacOut> res(places->size());
-        if ((rc = res.empty() ? b.sync() : b.read(fl.res, res.data(), sizeof(FlacOut) * res.size())))
-            return rc;
-        for (size_t u = 0; u < res.size(); u++)
-            (*places)[u] = ByteSpan{res[u].off, res[u].bytes};
-        return read_used(fl.out, used_bytes(*places), false, host);
-    }
-    for (size_t u = 0; u < places->size(); u++)
-        (*places)[u] = sink == SynthSink::Formatted ? ByteSpan{plan.fmt[u].off, plan.fmt[u].bytes}
-                       : sink == SynthSink::Fbank   ? ByteSpan{plan.fbank[u].off, plan.fbank[u].bytes}
-                       : sink == SynthSink::Mfcc    ? ByteSpan{plan.mfcc[u].off, plan.mfcc[u].bytes}
-                                                    : ByteSpan{plan.adpcm[u].off, plan.adpcm[u].bytes};
-    const OutSlab from = sink == SynthSink::Formatted ? OutSlab::Fmt
-                         : sink == SynthSink::Fbank   ? OutSlab::Feat
-                         : sink == SynthSink::Mfcc    ? OutSlab::Mfcc
-                                                      : OutSlab::Adpcm;
-    return read_used(slab[(size_t)from], used_bytes(*places), true, host);
+    if ((rc = sink_spans(sink, 0, places->size(), places->data())))
+        return rc;
+    const ByteSink s = byte_sink(sink);
+    return read_used(s.slab, used_bytes(*places), s.planned, host);
 }
 
 } // namespace jb

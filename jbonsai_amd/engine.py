@@ -111,6 +111,50 @@ def _lines(labels: Sequence[str]):
     return arr
 
 
+def _utt_lines(utterances):
+    """(lines, offs, B) of B utterances: their labels in one array, utterance u's being lines[offs[u]:offs[u + 1]]."""
+    B = len(utterances)
+    offs = (C.c_size_t * (B + 1))(*np.cumsum([0] + [len(u) for u in utterances]).tolist())
+    return _lines([l for u in utterances for l in u]), offs, B
+
+
+def _byte_outs(B, counts=False):
+    """The output arrays of a byte-sink entry of B outputs: (bufs, ns), with counts (bufs, ns, counts)."""
+    sz = C.c_size_t * max(1, B)
+    return ((C.POINTER(C.c_uint8) * max(1, B))(), sz()) + ((sz(),) if counts else ())
+
+
+def _fbank_opts(opts, kw):
+    return opts if opts is not None else F.fbank(**kw)
+
+
+def _drain(kw):
+    """The keywords left in kw, taken out of it."""
+    rest = dict(kw)
+    kw.clear()
+    return rest
+
+
+# synthesize_programme's byte sinks: the option structs a sink builds from the call's keywords (taking out of them what
+# it knows; None: a NULL pointer), its C entry, whether the entry has a per-output count, and the output of
+# (engine, library, buffer, bytes, count, option structs)
+_PROGRAMME_SINKS = {
+    "flac": (lambda kw: (F.flac_opts(kw.pop("block_size", 0), kw.pop("max_lpc_order", None)),
+                         F.flac_meta(kw.pop("md5", False), kw.pop("seek_interval_ms", 0))),
+             "jb_synthesize_programme_flac_meta", False, lambda e, L, buf, n, cnt, o: F.take_flac(L, [buf], [n], 1)[0]),
+    "formatted": (lambda kw: (F.format_opts(kw.pop("fmt"), kw.pop("dither", False), kw.pop("seed", 0)),),
+                  "jb_synthesize_programme_formatted", False,
+                  lambda e, L, buf, n, cnt, o: F.take_formatted(L, [buf], [n], 1)[0]),
+    "adpcm": (lambda kw: (F.adpcm_opts(kw.pop("block_align", 0)),), "jb_synthesize_programme_adpcm", True,
+              lambda e, L, buf, n, cnt, o: F.adpcm_streams(L, [buf], [n], [cnt], [e._out_hz()], o[0].block_align, 1)[0]),
+    "fbank": (lambda kw: (_fbank_opts(kw.pop("opts", None), _drain(kw)),), "jb_synthesize_programme_fbank", True,
+              lambda e, L, buf, n, cnt, o: F.take_fbank(L, [buf], [n], 1, o[0])[0]),
+    "mfcc": (lambda kw: F.mfcc_request(kw.pop("opts", None), kw.pop("fbank", None), _drain(kw)),
+             "jb_synthesize_programme_mfcc", True,
+             lambda e, L, buf, n, cnt, o: F.take_mfcc(L, [buf], [n], 1, o[1], o[0].n_mels)[0]),
+}
+
+
 class _Condition:
     """View of the engine's Condition (src/engine.rs:31-243)."""
 
@@ -415,10 +459,7 @@ class Engine:
         utterances are LPT-split over the listed GPUs, one host thread per device).  The arrays view
         the library-owned buffers (no copy); each is released with jb_pcm_free / jb_pcm_i16_free when
         its array dies."""
-        flat = [l for u in utterances for l in u]
-        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-        B = len(utterances)
-        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+        lines, offs, B = _utt_lines(utterances)
         ety = C.c_int16 if i16 else C.c_double
         pcm = (C.POINTER(ety) * max(1, B))()
         ns = (C.c_size_t * max(1, B))()
@@ -426,10 +467,10 @@ class Engine:
         if devices is not None:
             fn = self._L.jb_synthesize_batch_i16_multi if i16 else self._L.jb_synthesize_batch_multi
             dv = (C.c_int32 * max(1, len(devices)))(*[int(d) for d in devices])
-            F.check(fn(self._h, _lines(flat), offs, B, dv, len(devices), pcm, ns))
+            F.check(fn(self._h, lines, offs, B, dv, len(devices), pcm, ns))
         else:
             fn = self._L.jb_synthesize_batch_i16 if i16 else self._L.jb_synthesize_batch
-            F.check(fn(self._h, _lines(flat), offs, B, device, pcm, ns))
+            F.check(fn(self._h, lines, offs, B, device, pcm, ns))
         return _pcm_arrays(pcm, ns, B, i16, free)
 
     def synthesize_flac(self, labels: Sequence[str], block_size: int = 0, max_lpc_order=None, md5: bool = False,
@@ -449,16 +490,13 @@ class Engine:
     def synthesize_batch_flac(self, utterances: Sequence[Sequence[str]], device: int = -1, block_size: int = 0,
                               max_lpc_order=None, md5: bool = False, seek_interval_ms: int = 0) -> List[bytes]:
         """jb_synthesize_batch_flac[_meta]: one FLAC stream per utterance of synthesize_batch(..., i16=True)."""
-        flat = [l for u in utterances for l in u]
-        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-        B = len(utterances)
-        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-        bufs, ns = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))()
+        lines, offs, B = _utt_lines(utterances)
+        bufs, ns = _byte_outs(B)
         opts, meta = F.flac_opts(block_size, max_lpc_order), F.flac_meta(md5, seek_interval_ms)
         if meta is None:
-            F.check(self._L.jb_synthesize_batch_flac(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
+            F.check(self._L.jb_synthesize_batch_flac(self._h, lines, offs, B, device, C.byref(opts), bufs, ns))
         else:
-            F.check(self._L.jb_synthesize_batch_flac_meta(self._h, _lines(flat), offs, B, device, C.byref(opts),
+            F.check(self._L.jb_synthesize_batch_flac_meta(self._h, lines, offs, B, device, C.byref(opts),
                                                           C.byref(meta), bufs, ns))
         return F.take_flac(self._L, bufs, ns, B)
 
@@ -474,14 +512,10 @@ class Engine:
     def synthesize_batch_formatted(self, utterances: Sequence[Sequence[str]], fmt, dither=False, seed: int = 0,
                                    device: int = -1) -> List[bytes]:
         """jb_synthesize_batch_formatted: the bytes of each utterance of synthesize_batch(...) in the format."""
-        flat = [l for u in utterances for l in u]
-        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-        B = len(utterances)
-        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-        bufs, ns = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))()
+        lines, offs, B = _utt_lines(utterances)
+        bufs, ns = _byte_outs(B)
         opts = F.format_opts(fmt, dither, seed)
-        F.check(self._L.jb_synthesize_batch_formatted(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs,
-                                                      ns))
+        F.check(self._L.jb_synthesize_batch_formatted(self._h, lines, offs, B, device, C.byref(opts), bufs, ns))
         return F.take_formatted(self._L, bufs, ns, B)
 
     def _out_hz(self) -> int:
@@ -499,20 +533,16 @@ class Engine:
     def synthesize_adpcm_batch(self, utterances: Sequence[Sequence[str]], block_align: int = 0,
                                device: int = -1) -> List["F.AdpcmStream"]:
         """jb_synthesize_batch_adpcm: each utterance of synthesize_batch(...) as IMA ADPCM blocks."""
-        flat = [l for u in utterances for l in u]
-        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-        B = len(utterances)
-        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-        bufs, ns, nsamp = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
+        lines, offs, B = _utt_lines(utterances)
+        bufs, ns, nsamp = _byte_outs(B, counts=True)
         opts = F.adpcm_opts(block_align)
-        F.check(self._L.jb_synthesize_batch_adpcm(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns,
-                                                  nsamp))
+        F.check(self._L.jb_synthesize_batch_adpcm(self._h, lines, offs, B, device, C.byref(opts), bufs, ns, nsamp))
         return F.adpcm_streams(self._L, bufs, ns, nsamp, [self._out_hz()] * B, block_align, B)
 
     def synthesize_fbank(self, labels: Sequence[str], opts=None, **kw) -> np.ndarray:
         """jb_synthesize_fbank: the log-mel filterbank frames [T, n_mels] of what synthesize(labels) returns, computed
         on the GPU.  opts: F.FbankOpts, or the keywords of J.fbank."""
-        opts = opts if opts is not None else F.fbank(**kw)
+        opts = _fbank_opts(opts, kw)
         buf, n, nf = C.POINTER(C.c_uint8)(), C.c_size_t(), C.c_size_t()
         F.check(self._L.jb_synthesize_fbank(self._h, _lines(labels), len(labels), C.byref(opts), C.byref(buf),
                                             C.byref(n), C.byref(nf)))
@@ -521,13 +551,10 @@ class Engine:
     def synthesize_fbank_batch(self, utterances: Sequence[Sequence[str]], opts=None, device: int = -1,
                                **kw) -> List[np.ndarray]:
         """jb_synthesize_batch_fbank: each utterance of synthesize_batch(...) as filterbank frames."""
-        opts = opts if opts is not None else F.fbank(**kw)
-        flat = [l for u in utterances for l in u]
-        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-        B = len(utterances)
-        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-        bufs, ns, nf = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
-        F.check(self._L.jb_synthesize_batch_fbank(self._h, _lines(flat), offs, B, device, C.byref(opts), bufs, ns, nf))
+        opts = _fbank_opts(opts, kw)
+        lines, offs, B = _utt_lines(utterances)
+        bufs, ns, nf = _byte_outs(B, counts=True)
+        F.check(self._L.jb_synthesize_batch_fbank(self._h, lines, offs, B, device, C.byref(opts), bufs, ns, nf))
         return F.take_fbank(self._L, bufs, ns, B, opts)
 
     def synthesize_mfcc(self, labels: Sequence[str], opts=None, fbank=None, **kw) -> np.ndarray:
@@ -543,13 +570,10 @@ class Engine:
                               **kw) -> List[np.ndarray]:
         """jb_synthesize_batch_mfcc: each utterance of synthesize_batch(...) as cepstral features."""
         fo, mo = F.mfcc_request(opts, fbank, kw)
-        flat = [l for u in utterances for l in u]
-        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-        B = len(utterances)
-        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-        bufs, ns, nf = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
-        F.check(self._L.jb_synthesize_batch_mfcc(self._h, _lines(flat), offs, B, device, C.byref(fo), C.byref(mo),
-                                                 bufs, ns, nf))
+        lines, offs, B = _utt_lines(utterances)
+        bufs, ns, nf = _byte_outs(B, counts=True)
+        F.check(self._L.jb_synthesize_batch_mfcc(self._h, lines, offs, B, device, C.byref(fo), C.byref(mo), bufs, ns,
+                                                 nf))
         return F.take_mfcc(self._L, bufs, ns, B, mo, fo.n_mels)
 
     def synthesize_programme(self, utterances: Sequence[Sequence[str]], sink: str = "f64", lead_ms: float = 0.0,
@@ -562,10 +586,7 @@ class Engine:
         [T, n_mels]; opts=F.FbankOpts or the keywords of J.fbank) or "mfcc" (an ndarray [T, width]; opts=F.MfccOpts or
         the keywords of J.mfcc, fbank=F.FbankOpts or a dict of J.fbank's keywords).  Returns (output, starts):
         starts[u] is utterance u's first sample within the programme."""
-        flat = [l for u in utterances for l in u]
-        off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-        B = len(utterances)
-        offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
+        lines, offs, B = _utt_lines(utterances)
         join = F.join_opts(lead_ms, gap_ms, trail_ms, fade_ms)
         starts = (C.c_uint64 * max(1, B))()
         out, n = C.c_void_p(), C.c_size_t()
@@ -574,50 +595,22 @@ class Engine:
             if sink_opts:
                 raise TypeError(f"unknown options {sorted(sink_opts)}")
             fn = L.jb_synthesize_programme_i16 if sink == "i16" else L.jb_synthesize_programme
-            F.check(fn(self._h, _lines(flat), offs, B, device, C.byref(join), C.byref(out), C.byref(n), starts))
+            F.check(fn(self._h, lines, offs, B, device, C.byref(join), C.byref(out), C.byref(n), starts))
             ety, dt = (C.c_int16, np.int16) if sink == "i16" else (C.c_double, np.float64)
             res = np.frombuffer((ety * n.value).from_address(out.value), dtype=dt).copy() if n.value else np.zeros(0, dt)
             L.jb_join_free(out)  # (malloc'ed by the library, as every output is)
             return res, list(starts[:B])
-        buf = C.POINTER(C.c_uint8)()
-        if sink == "flac":
-            opts = F.flac_opts(sink_opts.pop("block_size", 0), sink_opts.pop("max_lpc_order", None))
-            meta = F.flac_meta(sink_opts.pop("md5", False), sink_opts.pop("seek_interval_ms", 0))
-            if sink_opts:
-                raise TypeError(f"unknown options {sorted(sink_opts)}")
-            F.check(L.jb_synthesize_programme_flac_meta(self._h, _lines(flat), offs, B, device, C.byref(opts),
-                                                        C.byref(meta) if meta is not None else None, C.byref(join),
-                                                        C.byref(buf), C.byref(n), starts))
-            return F.take_flac(L, [buf], [n.value], 1)[0], list(starts[:B])
-        if sink == "formatted":
-            opts = F.format_opts(sink_opts.pop("fmt"), sink_opts.pop("dither", False), sink_opts.pop("seed", 0))
-            if sink_opts:
-                raise TypeError(f"unknown options {sorted(sink_opts)}")
-            F.check(L.jb_synthesize_programme_formatted(self._h, _lines(flat), offs, B, device, C.byref(opts),
-                                                        C.byref(join), C.byref(buf), C.byref(n), starts))
-            return F.take_formatted(L, [buf], [n.value], 1)[0], list(starts[:B])
-        if sink == "adpcm":
-            block_align = sink_opts.pop("block_align", 0)
-            if sink_opts:
-                raise TypeError(f"unknown options {sorted(sink_opts)}")
-            opts, ns = F.adpcm_opts(block_align), C.c_size_t()
-            F.check(L.jb_synthesize_programme_adpcm(self._h, _lines(flat), offs, B, device, C.byref(opts),
-                                                    C.byref(join), C.byref(buf), C.byref(n), C.byref(ns), starts))
-            return (F.adpcm_streams(L, [buf], [n.value], [ns.value], [self._out_hz()], block_align, 1)[0],
-                    list(starts[:B]))
-        if sink == "fbank":
-            opts = sink_opts.pop("opts", None)
-            opts, nf = opts if opts is not None else F.fbank(**sink_opts), C.c_size_t()
-            F.check(L.jb_synthesize_programme_fbank(self._h, _lines(flat), offs, B, device, C.byref(opts),
-                                                    C.byref(join), C.byref(buf), C.byref(n), C.byref(nf), starts))
-            return F.take_fbank(L, [buf], [n.value], 1, opts)[0], list(starts[:B])
-        if sink == "mfcc":
-            fo, mo = F.mfcc_request(sink_opts.pop("opts", None), sink_opts.pop("fbank", None), sink_opts)
-            nf = C.c_size_t()
-            F.check(L.jb_synthesize_programme_mfcc(self._h, _lines(flat), offs, B, device, C.byref(fo), C.byref(mo),
-                                                   C.byref(join), C.byref(buf), C.byref(n), C.byref(nf), starts))
-            return F.take_mfcc(L, [buf], [n.value], 1, mo, fo.n_mels)[0], list(starts[:B])
-        raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm", "fbank" or "mfcc"')
+        if sink not in _PROGRAMME_SINKS:
+            raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm", "fbank" or "mfcc"')
+        build, entry, counted, take = _PROGRAMME_SINKS[sink]
+        opts = build(sink_opts)
+        if sink_opts:
+            raise TypeError(f"unknown options {sorted(sink_opts)}")
+        buf, count = C.POINTER(C.c_uint8)(), C.c_size_t()
+        F.check(getattr(L, entry)(self._h, lines, offs, B, device, *[o if o is None else C.byref(o) for o in opts],
+                                  C.byref(join), C.byref(buf), C.byref(n), *([C.byref(count)] if counted else []),
+                                  starts))
+        return take(self, L, buf, n.value, count.value, opts), list(starts[:B])
 
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
@@ -641,43 +634,37 @@ def _pcm_arrays(pcm, ns, B, i16, free):
     return out
 
 
+def _each_call(engines, utterances):
+    """(L, engine handles, lines, offs, B) of a synthesize_batch_each* call: one engine per utterance."""
+    if len(engines) != len(utterances):
+        raise ValueError("one engine per utterance")
+    L = engines[0]._L if engines and engines[0] is not None else F.lib()
+    _bind(L)
+    hs = (C.c_void_p * max(1, len(engines)))(*[e._h if e is not None else None for e in engines])
+    return (L, hs) + _utt_lines(utterances)
+
+
 def synthesize_batch_each(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]], i16: bool = False,
                           device: int = -1) -> List[np.ndarray]:
     """jb_synthesize_batch_each[_i16]: utterance u under engines[u]'s Condition, all in one batch.  The engines
     share one voice set (Engine.new / clone of one another) and agree on sampling frequency, fperiod, stage,
     log gain and the batch-invariant flag."""
-    if len(engines) != len(utterances):
-        raise ValueError("one engine per utterance")
-    B = len(utterances)
-    L = engines[0]._L if B and engines[0] is not None else F.lib()
-    _bind(L)
-    flat = [l for u in utterances for l in u]
-    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
+    L, hs, lines, offs, B = _each_call(engines, utterances)
     ety = C.c_int16 if i16 else C.c_double
     pcm = (C.POINTER(ety) * max(1, B))()
     ns = (C.c_size_t * max(1, B))()
     fn = L.jb_synthesize_batch_each_i16 if i16 else L.jb_synthesize_batch_each
-    F.check(fn(hs, _lines(flat), offs, B, device, pcm, ns))
+    F.check(fn(hs, lines, offs, B, device, pcm, ns))
     return _pcm_arrays(pcm, ns, B, i16, L.jb_pcm_i16_free if i16 else L.jb_pcm_free)
 
 
 def synthesize_batch_each_formatted(engines: Sequence["Engine"], utterances: Sequence[Sequence[str]], fmt,
                                     dither=False, seed: int = 0, device: int = -1) -> List[bytes]:
     """jb_synthesize_batch_each_formatted: the bytes of synthesize_batch_each(...) in the sample format."""
-    if len(engines) != len(utterances):
-        raise ValueError("one engine per utterance")
-    B = len(utterances)
-    L = engines[0]._L if B and engines[0] is not None else F.lib()
-    _bind(L)
-    flat = [l for u in utterances for l in u]
-    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
-    bufs, ns = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))()
+    L, hs, lines, offs, B = _each_call(engines, utterances)
+    bufs, ns = _byte_outs(B)
     opts = F.format_opts(fmt, dither, seed)
-    F.check(L.jb_synthesize_batch_each_formatted(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
+    F.check(L.jb_synthesize_batch_each_formatted(hs, lines, offs, B, device, C.byref(opts), bufs, ns))
     return F.take_formatted(L, bufs, ns, B)
 
 
@@ -685,18 +672,10 @@ def synthesize_batch_each_adpcm(engines: Sequence["Engine"], utterances: Sequenc
                                 block_align: int = 0, device: int = -1) -> List["F.AdpcmStream"]:
     """jb_synthesize_batch_each_adpcm: synthesize_batch_each(...) as IMA ADPCM blocks, each utterance at its engine's
     output rate (and, with block_align 0, at that rate's block size)."""
-    if len(engines) != len(utterances):
-        raise ValueError("one engine per utterance")
-    B = len(utterances)
-    L = engines[0]._L if B and engines[0] is not None else F.lib()
-    _bind(L)
-    flat = [l for u in utterances for l in u]
-    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
-    bufs, ns, nsamp = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
+    L, hs, lines, offs, B = _each_call(engines, utterances)
+    bufs, ns, nsamp = _byte_outs(B, counts=True)
     opts = F.adpcm_opts(block_align)
-    F.check(L.jb_synthesize_batch_each_adpcm(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns, nsamp))
+    F.check(L.jb_synthesize_batch_each_adpcm(hs, lines, offs, B, device, C.byref(opts), bufs, ns, nsamp))
     return F.adpcm_streams(L, bufs, ns, nsamp, [e._out_hz() for e in engines], block_align, B)
 
 
@@ -704,22 +683,14 @@ def synthesize_batch_each_flac(engines: Sequence["Engine"], utterances: Sequence
                                block_size: int = 0, max_lpc_order=None, md5: bool = False,
                                seek_interval_ms: int = 0) -> List[bytes]:
     """jb_synthesize_batch_each_flac[_meta]: the FLAC streams of synthesize_batch_each(..., i16=True)."""
-    if len(engines) != len(utterances):
-        raise ValueError("one engine per utterance")
-    B = len(utterances)
-    L = engines[0]._L if B and engines[0] is not None else F.lib()
-    _bind(L)
-    flat = [l for u in utterances for l in u]
-    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
-    bufs, ns = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))()
+    L, hs, lines, offs, B = _each_call(engines, utterances)
+    bufs, ns = _byte_outs(B)
     opts, meta = F.flac_opts(block_size, max_lpc_order), F.flac_meta(md5, seek_interval_ms)
     if meta is None:
-        F.check(L.jb_synthesize_batch_each_flac(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns))
+        F.check(L.jb_synthesize_batch_each_flac(hs, lines, offs, B, device, C.byref(opts), bufs, ns))
     else:
-        F.check(L.jb_synthesize_batch_each_flac_meta(hs, _lines(flat), offs, B, device, C.byref(opts), C.byref(meta),
-                                                     bufs, ns))
+        F.check(L.jb_synthesize_batch_each_flac_meta(hs, lines, offs, B, device, C.byref(opts), C.byref(meta), bufs,
+                                                     ns))
     return F.take_flac(L, bufs, ns, B)
 
 
@@ -790,16 +761,8 @@ def synthesize_batch_each_fbank(engines: Sequence["Engine"], utterances: Sequenc
                                 device: int = -1, **kw) -> List[np.ndarray]:
     """jb_synthesize_batch_each_fbank: synthesize_batch_each(...) as filterbank frames, each utterance at its engine's
     output rate and that rate's geometry."""
-    if len(engines) != len(utterances):
-        raise ValueError("one engine per utterance")
-    opts = opts if opts is not None else F.fbank(**kw)
-    B = len(utterances)
-    L = engines[0]._L if B and engines[0] is not None else F.lib()
-    _bind(L)
-    flat = [l for u in utterances for l in u]
-    off = np.cumsum([0] + [len(u) for u in utterances]).astype(np.uint64)
-    offs = (C.c_size_t * (B + 1))(*[int(x) for x in off])
-    hs = (C.c_void_p * max(1, B))(*[e._h if e is not None else None for e in engines])
-    bufs, ns, nf = (C.POINTER(C.c_uint8) * max(1, B))(), (C.c_size_t * max(1, B))(), (C.c_size_t * max(1, B))()
-    F.check(L.jb_synthesize_batch_each_fbank(hs, _lines(flat), offs, B, device, C.byref(opts), bufs, ns, nf))
+    L, hs, lines, offs, B = _each_call(engines, utterances)
+    opts = _fbank_opts(opts, kw)
+    bufs, ns, nf = _byte_outs(B, counts=True)
+    F.check(L.jb_synthesize_batch_each_fbank(hs, lines, offs, B, device, C.byref(opts), bufs, ns, nf))
     return F.take_fbank(L, bufs, ns, B, opts)

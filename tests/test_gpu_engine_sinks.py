@@ -21,6 +21,19 @@ pytestmark = pytest.mark.gpu
 UTTS = [SAMPLE_SENTENCE_1, SAMPLE_SENTENCE_2, [], list(SAMPLE_SENTENCE_1) * 3, SAMPLE_SENTENCE_1]
 FLAC = dict(md5=True, seek_interval_ms=100)
 FMT = dict(fmt="s24", dither=True, seed=3)
+FB, MF = J.fbank(n_mels=40), J.mfcc(delta_order=1)
+
+
+def each_mfcc(engines, utts):
+    """jb_synthesize_batch_each_mfcc (the package has no wrapper of it)"""
+    L, B = engines[0]._L, len(utts)
+    offs = (C.c_size_t * (B + 1))(*np.cumsum([0] + [len(u) for u in utts]).tolist())
+    hs = (C.c_void_p * B)(*[e._h for e in engines])
+    bufs, ns, nf = (C.POINTER(C.c_uint8) * B)(), (C.c_size_t * B)(), (C.c_size_t * B)()
+    F.check(L.jb_synthesize_batch_each_mfcc(hs, _lines([l for u in utts for l in u]), offs, B, -1, C.byref(FB),
+                                            C.byref(MF), bufs, ns, nf))
+    return F.take_mfcc(L, bufs, ns, B, MF, FB.n_mels)
+
 
 # per sink: the single-engine entry, the _each entry, the programme entry's sink and options, and for the byte sinks
 # the batch-level request and read of every output
@@ -35,9 +48,13 @@ SINKS = {
                   lambda b: b.set_format(FMT["fmt"], FMT["dither"], FMT["seed"]), lambda b: b.formatted_all()),
     "adpcm": (lambda e, u: e.synthesize_adpcm_batch(u), lambda es, u: J.synthesize_batch_each_adpcm(es, u),
               dict(sink="adpcm"), lambda b: b.set_adpcm(), lambda b: b.read_adpcm_all()),
+    "fbank": (lambda e, u: e.synthesize_fbank_batch(u, FB), lambda es, u: J.synthesize_batch_each_fbank(es, u, FB),
+              dict(sink="fbank", opts=FB), lambda b: b.set_fbank(FB), lambda b: b.read_fbank_all()),
+    "mfcc": (lambda e, u: e.synthesize_mfcc_batch(u, MF, fbank=FB), each_mfcc, dict(sink="mfcc", opts=MF, fbank=FB),
+             lambda b: b.set_mfcc(MF, fbank=FB), lambda b: b.read_mfcc_all()),
 }
 I16_BATCH = ("i16", "flac", "adpcm")  # the sinks whose batches are made with the 16-bit PCM
-BYTE_SINKS = ("flac", "formatted", "adpcm")
+BYTE_SINKS = ("flac", "formatted", "adpcm", "fbank", "mfcc")
 
 
 @pytest.fixture(scope="module")
@@ -62,14 +79,28 @@ def data_of(x):
     return x.data if isinstance(x, F.AdpcmStream) else x
 
 
+def n_bytes(x):
+    """The bytes that an output holds, given its bits()"""
+    x = data_of(x)
+    return len(x[1] if type(x) is tuple else x)
+
+
+def empty_bytes(eng, sink):
+    """An output of no samples: nothing, a FLAC stream of its header alone, or the features' geometry for 0 samples"""
+    if sink == "fbank":
+        return J.fbank_geometry(eng._out_hz(), FB, 0)[4]
+    if sink == "mfcc":
+        return J.mfcc_geometry(eng._out_hz(), FB, MF, 0)[2]
+    return 42 if sink == "flac" else 0
+
+
 @pytest.mark.parametrize("sink", list(SINKS))
 def test_groups_each_and_batch_level_agree(eng, states, sink, monkeypatch):
     batch, each = SINKS[sink][:2]
     monkeypatch.setenv("JB_SYNTH_GROUPS", "1")
     one = [bits(x) for x in batch(eng, UTTS)]
-    assert len(one) == len(UTTS) and all(len(data_of(x) if sink in BYTE_SINKS else x[1]) > 0 for x in one[:2] + one[3:])
-    # the empty utterance: nothing, or a FLAC stream of its header alone
-    assert len(data_of(one[2]) if sink in BYTE_SINKS else one[2][1]) == (42 if sink == "flac" else 0)
+    assert len(one) == len(UTTS) and all(n_bytes(x) > 0 for x in one[:2] + one[3:])
+    assert n_bytes(one[2]) == empty_bytes(eng, sink)
     for g in ("2", "5"):
         monkeypatch.setenv("JB_SYNTH_GROUPS", g)
         assert [bits(x) for x in batch(eng, UTTS)] == one, g
@@ -86,7 +117,7 @@ def test_groups_each_and_batch_level_agree(eng, states, sink, monkeypatch):
     with J.Batch(vi, utts, serial=True, serial_gv=True, pcm_i16=sink in I16_BATCH) as b:
         request(b)
         b.run()
-        assert read_all(b) == [data_of(x) for x in one]
+        assert [bits(x) for x in read_all(b)] == [data_of(x) for x in one]
         if sink == "adpcm":
             assert [b.num_samples(u) for u in range(len(b))] == [x.n_samples for x in one]
 
@@ -147,6 +178,10 @@ def test_failure_leaves_no_output(eng, sink, groups, monkeypatch):
     elif sink == "formatted":
         rc = L.jb_synthesize_batch_formatted(*head, C.byref(F.format_opts(FMT["fmt"], FMT["dither"], FMT["seed"])), out,
                                              ns)
+    elif sink == "fbank":
+        rc = L.jb_synthesize_batch_fbank(*head, C.byref(FB), out, ns, nsamp)
+    elif sink == "mfcc":
+        rc = L.jb_synthesize_batch_mfcc(*head, C.byref(FB), C.byref(MF), out, ns, nsamp)
     else:
         rc = L.jb_synthesize_batch_adpcm(*head, C.byref(F.adpcm_opts(0)), out, ns, nsamp)
     assert rc == BAD_CODE and L.jb_last_error().decode() == BAD_MESSAGE
