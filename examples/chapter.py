@@ -3,7 +3,7 @@
     python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
                                [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
-                               [--fbank OUT.npy] [--mfcc OUT.npy] [--fir taps.npy [--fir-delay D]]
+                               [--fbank OUT.npy] [--mfcc OUT.npy] [--melspec OUT.npy [--whisper]] [--fir taps.npy [--fir-delay D]]
                                [--noise bed.npy|white --snr DB]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
@@ -21,7 +21,9 @@ one loud peak no longer holds the whole chapter under its target.  With --fbank 
 (25 ms windows every 10 ms, 80 filters, float32 [T, 80]) are computed on the GPU from the joined programme, frames across
 the pauses and the seams included, and saved as a .npy file INSTEAD of the audio: a request has one sink, so no audio
 file is written (run again without --fbank for it; the cue list is the same).  --mfcc does the same with 13 liftered
-cepstra, delta and delta-delta rows, normalised in mean and variance over the whole chapter (float32 [T, 39]).  The cue list -- each sentence's first sample and time within the chapter -- is printed.
+cepstra, delta and delta-delta rows, normalised in mean and variance over the whole chapter (float32 [T, 39]); --melspec with the chapter's mel spectrogram in
+the librosa / Whisper convention (a centred, reflected 25 ms Hann window every 10 ms, 80 Slaney filters, natural
+logarithm), or with --whisper Whisper's own front end at 16 kHz, its clamp 8 under the whole chapter's maximum.  The cue list -- each sentence's first sample and time within the chapter -- is printed.
 Needs an MI355X: the library has no CPU path.
 """
 import argparse
@@ -53,7 +55,11 @@ ap.add_argument("--fir", default=None, metavar="taps.npy",
 ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
 ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="the chapter's log-mel filterbank frames from the GPU, instead of the audio")
 ap.add_argument("--mfcc", default=None, metavar="OUT.npy", help="the chapter's MFCC + deltas + CMVN rows from the GPU, instead of the audio")
+ap.add_argument("--melspec", default=None, metavar="OUT.npy", help="the chapter's mel spectrogram (librosa / Whisper convention) from the GPU, instead of the audio")
+ap.add_argument("--whisper", action="store_true", help="with --melspec: Whisper's front end; sets the output rate to 16 kHz")
 args = ap.parse_args()
+if args.melspec and args.whisper:
+    args.rate = 16000
 
 sentences = []
 for path in args.labels:
@@ -94,6 +100,13 @@ elif args.mfcc:
     feats, starts = engine.synthesize_programme(sentences, sink="mfcc", delta_order=2, cmvn="mean_var", **join)
     np.save(args.mfcc, feats)
     print(f"wrote {args.mfcc}: {feats.shape[0]} frames of {feats.shape[1]} cepstral values at {hz} Hz")
+elif args.melspec:
+    import numpy as np
+
+    opts = J.whisper_mel(80) if args.whisper else J.melspec(win_ms=25, hop_ms=10, rate=hz)
+    feats, starts = engine.synthesize_programme(sentences, sink="melspec", opts=opts, **join)
+    np.save(args.melspec, feats)
+    print(f"wrote {args.melspec}: {feats.shape[0]} frames of {feats.shape[1]} mel values at {hz} Hz")
 elif args.out.endswith(".flac"):
     data, starts = engine.synthesize_programme(sentences, sink="flac", md5=True, seek_interval_ms=1000, **join)
     with open(args.out, "wb") as f:

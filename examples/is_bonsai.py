@@ -3,6 +3,7 @@
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak] [--limiter DB]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
                                  [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]] [--mfcc OUT.npy [--rate HZ]]
+                                 [--melspec OUT.npy [--whisper | --rate HZ]]
                                  [--fir taps.npy [--fir-delay D]] [--noise bed.npy|white --snr DB [--snr-active]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
@@ -32,6 +33,10 @@ With --fbank the sentence's log-mel filterbank frames (25 ms windows every 10 ms
 computed on the GPU from the final PCM, at --rate if given, and saved as a .npy file; no WAV file is written.
 With --mfcc the same frames go on, still on the GPU, to 13 liftered cepstra with delta and delta-delta rows, mean and
 variance normalised over the sentence (float32 [T, 39]), saved the same way.
+With --melspec the sentence's mel spectrogram in the librosa / Whisper convention -- a centred, reflected 25 ms Hann
+window every 10 ms, 80 Slaney filters, natural logarithm, float32 [T, 80] -- is computed on the GPU from the final PCM,
+at --rate if given; with --whisper it is Whisper's own front end (400 / 160 samples at 16 kHz, log10 clamped 8 under the
+sentence's maximum, (y + 4) / 4: what log_mel_spectrogram gives before its padding to 30 s).  Saved the same way.
 With --limiter (and --loudness) the gain may put the highest peak that many dB over the ceiling and a look-ahead limiter
 on the GPU holds the ceiling (Engine.set_limiter): the target is reached where the peak alone stood in the way.
 """
@@ -56,9 +61,11 @@ ap.add_argument("--format", choices=["f32", "s16", "s24", "ulaw", "alaw"], defau
                 help="sample format of the WAV file, converted on the GPU")
 ap.add_argument("--dither", action="store_true", help="TPDF dither (with --format s16 or s24)")
 ap.add_argument("--adpcm", action="store_true", help="IMA ADPCM (4-bit) WAV file, encoded on the GPU")
-ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm, --fbank or --mfcc)")
+ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm, --fbank, --mfcc or --melspec)")
 ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="log-mel filterbank frames, computed on the GPU")
 ap.add_argument("--mfcc", default=None, metavar="OUT.npy", help="MFCC + deltas + CMVN rows, computed on the GPU")
+ap.add_argument("--melspec", default=None, metavar="OUT.npy", help="mel spectrogram (librosa / Whisper convention), computed on the GPU")
+ap.add_argument("--whisper", action="store_true", help="with --melspec: Whisper's front end at 16 kHz")
 ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
 ap.add_argument("--fir", default=None, metavar="taps.npy", help="impulse response at the output rate, convolved on the GPU")
@@ -130,6 +137,17 @@ if args.mfcc:
     np.save(args.mfcc, feats)
     hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
     print(f"wrote {args.mfcc}: {feats.shape[0]} frames of {feats.shape[1]} cepstral values at {hz} Hz")
+    sys.exit(0)
+if args.melspec:
+    import numpy as np
+
+    if args.whisper or args.rate:
+        engine.condition.set_output_sampling_frequency(16000 if args.whisper else args.rate)
+    hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
+    opts = J.whisper_mel(80) if args.whisper else J.melspec(win_ms=25, hop_ms=10, rate=hz)
+    feats = engine.synthesize_melspec(SAMPLE_SENTENCE_2, opts)
+    np.save(args.melspec, feats)
+    print(f"wrote {args.melspec}: {feats.shape[0]} frames of {feats.shape[1]} mel values at {hz} Hz")
     sys.exit(0)
 if args.adpcm:
     if args.rate:

@@ -178,6 +178,37 @@ typedef struct jb_mfcc_opts {
     uint32_t flags;        /* JB_MFCC_F64 */
     uint32_t reserved[3];
 } jb_mfcc_opts;
+/* New.  Mel spectrogram options (jb_batch_set_melspec, jb_melspec_pcm_batch, jb_melspec_host, jb_synthesize*_melspec;
+ * see "Mel spectrograms" below).  Window and hop in samples at the unit's own rate; win_length 0 = n_fft; f_max_hz 0 =
+ * half the rate; floor 0 = 1e-10; range 0 = no clamp; scale 0 = 1.0; reserved 0.  Anything outside the limits of that
+ * section: JB_ERR_INVALID, naming the field, before any device is touched.  jb_melspec_whisper fills in Whisper's. */
+#define JB_MEL_HTK 0u         /* mel(f) = 2595 log10(1 + f / 700) */
+#define JB_MEL_SLANEY 1u      /* 3 f / 200 below 1 kHz, 15 + ln(f / 1000) / (ln 6.4 / 27) above */
+#define JB_MEL_NORM_NONE 0u   /* triangles of height 1 */
+#define JB_MEL_NORM_SLANEY 1u /* each filter times 2 / (f_{m+2} - f_m): unit area */
+#define JB_MEL_PAD_REFLECT 0u /* frame t centred on sample t hop, the unit reflected about its edge samples */
+#define JB_MEL_PAD_ZERO 1u    /* centred, zeros outside the unit */
+#define JB_MEL_PAD_NONE 2u    /* frame t starts at sample t hop; whole frames only */
+#define JB_MEL_LOG_NONE 0u    /* the filters' sums themselves */
+#define JB_MEL_LOG_LN 1u      /* ln(max(E, floor)) */
+#define JB_MEL_LOG_LOG10 2u   /* log10(max(E, floor)) */
+#define JB_MEL_LOG_DB 3u      /* 10 log10(max(E, floor)) */
+#define JB_MEL_MAGNITUDE 1u   /* |X_k| instead of |X_k|^2 */
+#define JB_MEL_DROP_LAST 2u   /* without the last frame (reflect and zero padding only) */
+#define JB_MEL_F64 4u         /* f64 elements instead of f32 */
+typedef struct jb_melspec_opts {
+    uint32_t n_fft, win_length, hop_length, n_mels;
+    double f_min_hz, f_max_hz; /* f_max 0: half the rate */
+    double floor;              /* clamp in front of the logarithm; 0: 1e-10 */
+    double range;              /* 0: none; else y = max(y, Ymax - range), Ymax over the unit */
+    double offset, scale;      /* out = (y + offset) * scale; scale 0: 1.0 */
+    uint32_t mel_scale;        /* JB_MEL_HTK, JB_MEL_SLANEY */
+    uint32_t norm;             /* JB_MEL_NORM_NONE, JB_MEL_NORM_SLANEY */
+    uint32_t pad;              /* JB_MEL_PAD_REFLECT, _ZERO, _NONE */
+    uint32_t log;              /* JB_MEL_LOG_NONE, _LN, _LOG10, _DB */
+    uint32_t flags;            /* JB_MEL_MAGNITUDE | _DROP_LAST | _F64 */
+    uint32_t reserved[3];      /* 0 */
+} jb_melspec_opts;
 /* The join request of one utterance (see "Join" below): the programme it belongs to, the zero samples before and
  * after it and the lengths of its edge fades.  reserved must be 0. */
 #define JB_JOIN_NONE 0xffffffffu
@@ -588,6 +619,21 @@ int jb_batch_mfcc_size(jb_batch *b, size_t unit, size_t *n_bytes);
 int jb_batch_read_mfcc(jb_batch *b, size_t unit, uint8_t *dst, size_t cap);
 /* Every unit: dst[u] must hold jb_batch_mfcc_size(b, u) bytes (one device-to-host copy for the batch). */
 int jb_batch_read_mfcc_all(jb_batch *b, uint8_t *const *dst);
+/* New.  Mel spectrograms of every unit's final PCM (see "Mel spectrograms" below), on the device.  Preconditions as
+ * jb_batch_set_fbank's: an f64 batch (JB_BATCH_PCM_I16, JB_BATCH_MLPG_ONLY: JB_ERR_UNSUPPORTED), before the first run;
+ * checked at every unit's output rate, and again by jb_batch_set_output_rate.  opts == NULL withdraws the request.
+ * Independent of jb_batch_set_fbank and jb_batch_set_mfcc, which keep their slabs and bytes; behind a join the units
+ * are the programmes, and the range clamp runs under the whole programme's maximum.  Without a call nothing runs and
+ * nothing is allocated. */
+int jb_batch_set_melspec(jb_batch *b, const jb_melspec_opts *opts);
+/* Unit `unit`'s frames, filters and rate, known once the request is made; any out pointer may be NULL. */
+int jb_batch_melspec_shape(jb_batch *b, size_t unit, size_t *T, uint32_t *n_mels, uint32_t *hz);
+/* Its bytes: T x n_mels x 4 (8 with JB_MEL_F64). */
+int jb_batch_melspec_size(jb_batch *b, size_t unit, size_t *n_bytes);
+/* Its frames after a run, row-major (waits for the batch); cap below jb_batch_melspec_size: JB_ERR_BUFFER. */
+int jb_batch_read_melspec(jb_batch *b, size_t unit, uint8_t *dst, size_t cap);
+/* Every unit: dst[u] must hold jb_batch_melspec_size(b, u) bytes (one device-to-host copy for the batch). */
+int jb_batch_read_melspec_all(jb_batch *b, uint8_t *const *dst);
 /* New (none: no reference counterpart).  Join (see "Join" below): the run also gathers the utterances' final PCM --
  * what the PCM read entries hand out, after the output rate and the loudness target -- into programmes, on the
  * device: each programme its members in ascending utterance index, each between its pads and under its fades.  FLAC,
@@ -925,8 +971,8 @@ void jb_adpcm_free(uint8_t *p);
  *   kernel takes 43.7 ms of device time at 48 kHz (3.27 million frames of 2048 points) and 11.4 ms at 16 kHz; run + read
  *   of everything 430 ms (the f64 samples: 353 ms): the read is one pageable copy.  Against the long double model the
  *   device's error is 1.00 to 1.25 times (3.88 with one filter alone) that of a float64 rfft of the same frames.
- * Not covered: the Slaney mel scale, reflection padding, pre-emphasis, dither and per-frame DC removal (no Kaldi or
- * Whisper bit-compatibility is claimed); magnitude instead of power; the generator, the _multi entries
+ * Not covered: the Slaney mel scale, reflection padding and magnitude instead of power (these are the "Mel
+ * spectrograms" stage below); pre-emphasis, dither and per-frame DC removal (no Kaldi bit-compatibility is claimed); the generator, the _multi entries
  * and jb_gather_pcm; 16-bit batches; per-utterance options within one batch;
  * reading through the pinned ring (the read is one pageable copy). */
 /* wl, hop, n_fft of the options at hz and T and bytes of n samples; any out pointer may be NULL. */
@@ -1009,6 +1055,68 @@ int jb_mfcc_pcm_batch(const double *const *in, const size_t *n_in, size_t n, con
                       const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, int32_t device, uint8_t **out,
                       size_t *n_bytes);
 void jb_mfcc_free(uint8_t *p);
+
+/* ---- Mel spectrograms (new: the reference hands out samples only; none of these entries has a counterpart) ------------
+ * The filterbank stage above speaks Kaldi / HTK.  Everything neural reads the other dialect -- what librosa's
+ * melspectrogram, torchaudio's MelSpectrogram and Whisper's log_mel_spectrogram compute: a centred, reflected
+ * short-time transform of any 5-smooth length with window and hop in samples, triangles that are linear in Hz between
+ * mel-spaced edges, Slaney's scale and area normalisation, log10 or dB, and a clamp against the unit's own maximum.
+ * For a unit of n samples x (16-bit scale, as jb_batch_read_pcm hands them out) at rate hz:
+ * 1. Scale.  s[i] = x[i] * 2^-15 (exact); this stage has no 16-bit scale.
+ * 2. Sizes.  N = n_fft is even, in 64..4096, without a prime factor above 5 (400, 480, 600, 800, 1024, 1200, 2048,
+ *    4000, ...); W = win_length is 0 (N) or in 2..N; H = hop_length >= 1; all in samples at the unit's own rate.
+ * 3. Frames.  With p = N / 2: under JB_MEL_PAD_REFLECT and _ZERO T = 1 + n / H (integer division) and frame t is
+ *    s~[t H - p + j], j < N; _ZERO: s~ is 0 outside the unit; _REFLECT: s~[-j] = s[j], s~[n - 1 + j] = s[n - 1 - j] (the
+ *    edge sample is not repeated), which needs n > p: a shorter unit has T = 0.  Under _NONE frame t is s[t H + j] and
+ *    T = n >= N ? 1 + (n - N) / H : 0.  JB_MEL_DROP_LAST drops the last frame under _REFLECT and _ZERO (T one less, not
+ *    below 0); with _NONE it is refused.
+ * 4. Window.  Periodic Hann of W points, 0.5 - 0.5 cos(2 pi j / W), at (N - W) / 2 inside the frame with zeros around
+ *    it (torch.stft's placement); made on the host in long double and rounded once (jb_melspec_window).
+ * 5. Spectrum.  X_k, k = 0..N / 2, of the windowed frame; S_k = |X_k|^2, or |X_k| with JB_MEL_MAGNITUDE.  f64
+ *    throughout; the twiddles come from host tables (long double, rounded once).
+ * 6. Filters.  n_mels + 2 points equally spaced on the mel scale between mel(f_min) and mel(f_max) -- JB_MEL_HTK:
+ *    2595 log10(1 + f / 700); JB_MEL_SLANEY: 3 f / 200 below 1 kHz, 15 + ln(f / 1000) / (ln 6.4 / 27) above -- and
+ *    converted back to Hz: f_0 .. f_{n_mels+1}.  With nu_k = k hz / N, W[m][k] = max(0, min((nu_k - f_m) / (f_{m+1} -
+ *    f_m), (f_{m+2} - nu_k) / (f_{m+2} - f_{m+1}))); JB_MEL_NORM_SLANEY multiplies it by 2 / (f_{m+2} - f_m).  Made on
+ *    the host in long double, rounded once (jb_melspec_filterbank).  E[t][m] = sum_k W[m][k] S_k in ascending k; a
+ *    filter that covers no bin gives 0.  1 <= n_mels <= 128, 0 <= f_min < f_max <= hz / 2.
+ * 7. Logarithm.  _NONE: y = E; _LN: ln(max(E, floor)); _LOG10: log10(max(E, floor)); _DB: 10 log10(max(E, floor)).  An
+ *    E at or below the floor gives the floor's logarithm as made on the host in long double and rounded once.
+ * 8. Range.  If range > 0: y = max(y, Ymax - range), Ymax the largest y of the whole unit (behind a join: of the whole
+ *    programme), in f64.
+ * 9. Affine and element.  out = (y + offset) * scale, one f64 add and one f64 multiply without contraction; the
+ *    element is f32 by one rounding, or f64 with JB_MEL_F64.  Row-major [T][n_mels] per unit.
+ * Whisper's front end (jb_melspec_whisper): 400 / 400 / 160, reflect padding, drop-last, power spectrum, Slaney scale
+ * and norm, 0..8000 Hz, log10, floor 1e-10, range 8, offset 4, scale 0.25; the caller sets the output rate to 16 kHz.
+ * Determinism: a frame's operations and their order are a function of (N, W, n_mels, options) alone; the maximum of
+ * step 8 has no order.  Hence the seam (jb_melspec_pcm_batch), the batch path, redo rounds and any batch give the same
+ * bits, and JB_BATCH_INVARIANT output stays invariant.  The host form (jb_melspec_host) follows the same rule with the
+ * same butterflies; bit equality with the device is not claimed (the logarithm is each side's own).
+ * Cost on 256 x 128 s with 80 filters (profiles/r24_melspec.txt): N = 1200, H = 480 at 48 kHz takes 58.7 ms of device
+ * time (3.27 million frames; 63.1 ms with a range), k_fbank's 2048-point pass on the same frames 43.9 ms; Whisper's front
+ * end behind the converter at 16 kHz 24.4 ms; 0.667 bytes per sample in f32 at 48 kHz; run + read of everything 444 ms
+ * (the f64 samples: 353 ms).  Against the long double model the device's error is 0.66 to 1.92 times that of a float64
+ * rfft of the same frames.
+ * Not covered: HiFi-GAN's own (N - H) / 2 padding; windows other than Hann; pre-emphasis and dither; Whisper's padding
+ * or trimming to 30 s; the generator, the _multi entries and jb_gather_pcm; 16-bit batches; per-utterance options
+ * within a batch; reading through the pinned ring (the read is one pageable copy). */
+/* Whisper's options with n_mels filters (80 or 128 in its models; any 1..128 is taken) into *opts. */
+int jb_melspec_whisper(uint32_t n_mels, jb_melspec_opts *opts);
+/* N, W, H of the options at hz and T and bytes of n samples; any out pointer may be NULL. */
+int jb_melspec_geometry(uint32_t hz, const jb_melspec_opts *opts, size_t n, uint32_t *n_fft, uint32_t *win_length,
+                        uint32_t *hop_length, size_t *T, size_t *n_bytes);
+/* The window as the frame sees it (N doubles: the W Hann values at (N - W) / 2, zeros around them) and the filterbank
+ * (dense [n_mels][N / 2 + 1]) the options give at hz; cap (in doubles) below that: JB_ERR_BUFFER. */
+int jb_melspec_window(uint32_t hz, const jb_melspec_opts *opts, double *w, size_t cap);
+int jb_melspec_filterbank(uint32_t hz, const jb_melspec_opts *opts, double *W, size_t cap);
+/* The rule in plain C++ on the host; no GPU is touched.  out must hold the geometry's bytes (cap below that:
+ * JB_ERR_BUFFER). */
+int jb_melspec_host(const double *in, size_t n, uint32_t hz, const jb_melspec_opts *opts, uint8_t *out, size_t cap);
+/* The stage on PCM the caller holds (jb_fbank_pcm_batch's twin): out[u] = the frames of in[u] (n_in[u] f64 samples at
+ * hz[u]), n_bytes[u] bytes, library-owned (jb_melspec_free each), on `device` (-1 = current). */
+int jb_melspec_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                         const jb_melspec_opts *opts, int32_t device, uint8_t **out, size_t *n_bytes);
+void jb_melspec_free(uint8_t *p);
 
 /* ---- Join (new: the reference synthesises one utterance into one buffer; none of these entries has a counterpart) ------
  * A programme is "sentence, pause, sentence" as ONE stream: FLAC frame numbers, STREAMINFO, MD5 and SEEKTABLE, ADPCM
@@ -1691,6 +1799,18 @@ int jb_synthesize_batch_each_mfcc(const jb_engine *const *engines, const char *c
 int jb_synthesize_batch_each_fbank(const jb_engine *const *engines, const char *const *label_lines,
                                    const size_t *line_off, size_t n_utts, int32_t device, const jb_fbank_opts *opts,
                                    uint8_t **bytes, size_t *n_bytes, size_t *n_frames);
+/* New.  Mel spectrograms (see "Mel spectrograms") straight from the engine, as the _fbank entries above: bytes[u] = the
+ * [n_frames[u]][opts->n_mels] frames of utterance u's final f64 PCM at its engine's output rate, n_bytes[u] bytes,
+ * library-owned (jb_melspec_free each); n_frames may be NULL.  For Whisper's front end set the engines' output rate
+ * to 16 kHz. */
+int jb_synthesize_melspec(const jb_engine *e, const char *const *label_lines, size_t n_lines,
+                          const jb_melspec_opts *opts, uint8_t **bytes, size_t *n_bytes, size_t *n_frames);
+int jb_synthesize_batch_melspec(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                size_t n_utts, int32_t device, const jb_melspec_opts *opts, uint8_t **bytes,
+                                size_t *n_bytes, size_t *n_frames);
+int jb_synthesize_batch_each_melspec(const jb_engine *const *engines, const char *const *label_lines,
+                                     const size_t *line_off, size_t n_utts, int32_t device,
+                                     const jb_melspec_opts *opts, uint8_t **bytes, size_t *n_bytes, size_t *n_frames);
 /* The same two over a device list: the utterances are split by LPT on their label counts (the frame
  * counts are known only after the front half), one host thread per device runs jb_synthesize_batch's
  * path on its share (front half on that thread's workers, GPU work on that device). */
@@ -1806,6 +1926,12 @@ int jb_synthesize_programme_mfcc(const jb_engine *e, const char *const *label_li
                                  size_t n_utts, int32_t device, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
                                  const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, size_t *n_frames,
                                  uint64_t *starts);
+/* New.  The programme's mel spectrogram, the range clamp under the whole programme's maximum; bytes[0], n_bytes[0],
+ * n_frames (may be NULL) as jb_synthesize_melspec's. */
+int jb_synthesize_programme_melspec(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                    size_t n_utts, int32_t device, const jb_melspec_opts *opts,
+                                    const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, size_t *n_frames,
+                                    uint64_t *starts);
 
 /* ------------------------------------------------------------------------ */
 const char *jb_last_error(void);
@@ -1866,6 +1992,11 @@ JB_LAYOUT_ASSERT(sizeof(jb_fbank_opts) == 64 && offsetof(jb_fbank_opts, n_fft) =
                      offsetof(jb_fbank_opts, f_min_hz) == 16 && offsetof(jb_fbank_opts, log_floor) == 32 &&
                      offsetof(jb_fbank_opts, window) == 40 && offsetof(jb_fbank_opts, reserved) == 48,
                  "jb_fbank_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_melspec_opts) == 96 && offsetof(jb_melspec_opts, f_min_hz) == 16 &&
+                     offsetof(jb_melspec_opts, floor) == 32 && offsetof(jb_melspec_opts, range) == 40 &&
+                     offsetof(jb_melspec_opts, offset) == 48 && offsetof(jb_melspec_opts, mel_scale) == 64 &&
+                     offsetof(jb_melspec_opts, flags) == 80 && offsetof(jb_melspec_opts, reserved) == 84,
+                 "jb_melspec_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_join_utt) == 32 && offsetof(jb_join_utt, fade_out) == 8 &&
                      offsetof(jb_join_utt, pad_before) == 16 && offsetof(jb_join_utt, pad_after) == 24,
                  "jb_join_utt");

@@ -21,7 +21,11 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    FbankOpts, FBANK_HANN, FBANK_HAMMING, FBANK_CENTER, FBANK_LINEAR, FBANK_UNIT, FBANK_F64, fbank,
                    fbank_geometry, fbank_window, fbank_filterbank, fbank_host, fbank_pcm,
                    MfccOpts, CMVN_NONE, CMVN_MEAN, CMVN_MEAN_VAR, MFCC_F64, mfcc, mfcc_geometry,
-                   mfcc_dct, mfcc_delta_kernel, mfcc_host, mfcc_pcm_host, mfcc_frames, mfcc_pcm)
+                   mfcc_dct, mfcc_delta_kernel, mfcc_host, mfcc_pcm_host, mfcc_frames, mfcc_pcm,
+                   MelspecOpts, MEL_HTK, MEL_SLANEY, MEL_NORM_NONE, MEL_NORM_SLANEY, MEL_PAD_REFLECT, MEL_PAD_ZERO,
+                   MEL_PAD_NONE, MEL_LOG_NONE, MEL_LOG_LN, MEL_LOG_LOG10, MEL_LOG_DB, MEL_MAGNITUDE, MEL_DROP_LAST,
+                   MEL_F64, melspec, whisper_mel, melspec_geometry, melspec_window, melspec_filterbank, melspec_host,
+                   melspec_pcm)
 from .batch import (Batch, IndexStreamStates, IndexUtterance, PdfSet, StreamInfo, StreamStates, TrackUtterance,  # noqa: F401
                     Utterance, VoiceInfo, generator_from_tracks, mlpg_batch, paramgen_vocode_batch, vocode_tracks_batch,
                     vocoder_synthesize_batch)
@@ -50,4 +54,8 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "fbank_geometry", "fbank_window", "fbank_filterbank", "fbank_host", "fbank_pcm",
            "synthesize_batch_each_fbank",
            "MfccOpts", "CMVN_NONE", "CMVN_MEAN", "CMVN_MEAN_VAR", "MFCC_F64", "mfcc", "mfcc_geometry",
-           "mfcc_dct", "mfcc_delta_kernel", "mfcc_host", "mfcc_pcm_host", "mfcc_frames", "mfcc_pcm"]
+           "mfcc_dct", "mfcc_delta_kernel", "mfcc_host", "mfcc_pcm_host", "mfcc_frames", "mfcc_pcm",
+           "MelspecOpts", "MEL_HTK", "MEL_SLANEY", "MEL_NORM_NONE", "MEL_NORM_SLANEY", "MEL_PAD_REFLECT", "MEL_PAD_ZERO",
+           "MEL_PAD_NONE", "MEL_LOG_NONE", "MEL_LOG_LN", "MEL_LOG_LOG10", "MEL_LOG_DB", "MEL_MAGNITUDE", "MEL_DROP_LAST",
+           "MEL_F64", "melspec", "whisper_mel", "melspec_geometry", "melspec_window", "melspec_filterbank",
+           "melspec_host", "melspec_pcm"]

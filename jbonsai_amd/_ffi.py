@@ -268,6 +268,85 @@ def mfcc(n_ceps: int = 13, lifter: float = 22, delta_order: int = 0, delta_windo
     return o
 
 
+MEL_HTK, MEL_SLANEY = 0, 1
+MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1
+MEL_PAD_REFLECT, MEL_PAD_ZERO, MEL_PAD_NONE = 0, 1, 2
+MEL_LOG_NONE, MEL_LOG_LN, MEL_LOG_LOG10, MEL_LOG_DB = 0, 1, 2, 3
+MEL_MAGNITUDE, MEL_DROP_LAST, MEL_F64 = 1, 2, 4
+
+
+class MelspecOpts(C.Structure):
+    """jb_melspec_opts: transform, window and hop in samples, the mel filters, their band, scale (MEL_HTK, MEL_SLANEY)
+    and normalisation (MEL_NORM_*), the padding (MEL_PAD_*), the logarithm (MEL_LOG_*) with its floor, the range clamp
+    under the unit's maximum, the affine step and MEL_* flags."""
+    _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop_length", C.c_uint32), ("n_mels", C.c_uint32),
+                ("f_min_hz", C.c_double), ("f_max_hz", C.c_double), ("floor", C.c_double), ("range", C.c_double),
+                ("offset", C.c_double), ("scale", C.c_double), ("mel_scale", C.c_uint32), ("norm", C.c_uint32),
+                ("pad", C.c_uint32), ("log", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    @property
+    def dtype(self):
+        import numpy as np
+
+        return np.dtype(np.float64 if self.flags & MEL_F64 else np.float32)
+
+
+def _choice(value, names):
+    return names[value] if isinstance(value, str) else int(value)
+
+
+def melspec_next_fft(win: int) -> int:
+    """The smallest transform length the stage takes that holds a window of `win` samples: even, at least 64, no prime
+    factor above 5."""
+    n = max(64, win + (win & 1))
+    while True:
+        r = n
+        for p in (2, 3, 5):
+            while r % p == 0:
+                r //= p
+        if r == 1:
+            return n
+        n += 2
+
+
+def melspec(n_fft: int = 0, hop: int = 0, win: int = 0, n_mels: int = 80, f_min: float = 0.0, f_max: float = 0.0,
+            mel_scale="slaney", norm="slaney", pad="reflect", log="ln", floor: float = 0.0, range: float = 0.0,
+            offset: float = 0.0, scale: float = 0.0, magnitude: bool = False, drop_last: bool = False,
+            f64: bool = False, win_ms: float = 0.0, hop_ms: float = 0.0, rate: int = 0):
+    """MelspecOpts: mel spectrograms in the librosa / Whisper convention: an n_fft-point transform (even, 64..4096, no
+    prime factor above 5) every `hop` samples under a periodic Hann window of `win` samples (0: n_fft); win_ms / hop_ms
+    with `rate` give win and hop in samples instead (n_fft 0 then: the smallest length the stage takes that holds win).  mel_scale "htk" or "slaney"; norm "none" or
+    "slaney"; pad "reflect", "zero" or "none"; log "none", "ln", "log10" or "db" above `floor` (0: 1e-10); range > 0
+    clamps at the unit's maximum minus range; then (y + offset) * scale (scale 0: 1.0).  magnitude: |X| instead of
+    |X|^2; drop_last: without the last frame; f64: float64 elements instead of float32."""
+    if win_ms or hop_ms:
+        if not rate:
+            raise ValueError("win_ms / hop_ms need the rate")
+        win = int(win_ms * rate / 1000.0 + 0.5) if win_ms else win  # (half a sample rounds up, as the fbank stage's)
+        hop = int(hop_ms * rate / 1000.0 + 0.5) if hop_ms else hop
+    o = MelspecOpts()
+    n_fft = n_fft or (melspec_next_fft(int(win)) if win_ms else win)
+    o.n_fft, o.win_length, o.hop_length, o.n_mels = int(n_fft), int(win), int(hop), int(n_mels)
+    o.f_min_hz, o.f_max_hz = float(f_min), float(f_max)
+    o.floor, o.range, o.offset, o.scale = float(floor), float(range), float(offset), float(scale)
+    o.mel_scale = _choice(mel_scale, {"htk": MEL_HTK, "slaney": MEL_SLANEY})
+    o.norm = _choice("none" if norm is None else norm, {"none": MEL_NORM_NONE, "slaney": MEL_NORM_SLANEY})
+    o.pad = _choice(pad, {"reflect": MEL_PAD_REFLECT, "zero": MEL_PAD_ZERO, "none": MEL_PAD_NONE})
+    o.log = _choice("none" if log is None else log,
+                    {"none": MEL_LOG_NONE, "ln": MEL_LOG_LN, "log10": MEL_LOG_LOG10, "db": MEL_LOG_DB})
+    o.flags = MEL_MAGNITUDE * bool(magnitude) | MEL_DROP_LAST * bool(drop_last) | MEL_F64 * bool(f64)
+    return o
+
+
+def whisper_mel(n_mels: int = 80, f64: bool = False):
+    """jb_melspec_whisper: Whisper's front end (400 / 400 / 160 at 16 kHz, reflect padding without the last frame, Slaney
+    filters, log10 clamped 8 under the maximum, (y + 4) / 4); the caller sets the output rate to 16 kHz."""
+    o = MelspecOpts()
+    check(lib().jb_melspec_whisper(n_mels, C.byref(o)))
+    o.flags |= MEL_F64 * bool(f64)
+    return o
+
+
 JOIN_NONE = 0xFFFFFFFF
 
 
@@ -616,6 +695,11 @@ SYMBOLS = [
     "jb_mfcc_frames_batch", "jb_mfcc_pcm_batch", "jb_mfcc_free",
     "jb_batch_set_mfcc", "jb_batch_mfcc_shape", "jb_batch_mfcc_size", "jb_batch_read_mfcc", "jb_batch_read_mfcc_all",
     "jb_synthesize_mfcc", "jb_synthesize_batch_mfcc", "jb_synthesize_batch_each_mfcc", "jb_synthesize_programme_mfcc",
+    "jb_melspec_whisper", "jb_melspec_geometry", "jb_melspec_window", "jb_melspec_filterbank", "jb_melspec_host",
+    "jb_melspec_pcm_batch", "jb_melspec_free",
+    "jb_batch_set_melspec", "jb_batch_melspec_shape", "jb_batch_melspec_size", "jb_batch_read_melspec",
+    "jb_batch_read_melspec_all", "jb_synthesize_melspec", "jb_synthesize_batch_melspec",
+    "jb_synthesize_batch_each_melspec", "jb_synthesize_programme_melspec",
     "jb_batch_set_loudness_groups", "jb_batch_loudness_group_of", "jb_batch_loudness_group",
     "jb_batch_set_loudness_report", "jb_batch_loudness_r128", "jb_loudness_groups_pcm_batch",
     "jb_loudness_gate_host", "jb_engine_set_loudness_scope", "jb_engine_get_loudness_scope",
@@ -862,6 +946,21 @@ def lib():
                                      C.POINTER(sz)]
     L.jb_fbank_free.argtypes = [u8p]
     L.jb_fbank_free.restype = None
+    msop = C.POINTER(MelspecOpts)
+    L.jb_melspec_whisper.argtypes = [C.c_uint32, msop]
+    L.jb_melspec_geometry.argtypes = [C.c_uint32, msop, sz, u32p, u32p, u32p, C.POINTER(sz), C.POINTER(sz)]
+    L.jb_melspec_window.argtypes = [C.c_uint32, msop, vp, sz]
+    L.jb_melspec_filterbank.argtypes = [C.c_uint32, msop, vp, sz]
+    L.jb_melspec_host.argtypes = [vp, sz, C.c_uint32, msop, vp, sz]
+    L.jb_melspec_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, u32p, msop, C.c_int32, C.POINTER(u8p),
+                                       C.POINTER(sz)]
+    L.jb_batch_set_melspec.argtypes = [vp, msop]
+    L.jb_batch_melspec_shape.argtypes = [vp, sz, C.POINTER(sz), u32p, u32p]
+    L.jb_batch_melspec_size.argtypes = [vp, sz, C.POINTER(sz)]
+    L.jb_batch_read_melspec.argtypes = [vp, sz, vp, sz]
+    L.jb_batch_read_melspec_all.argtypes = [vp, C.POINTER(vp)]
+    L.jb_melspec_free.argtypes = [u8p]
+    L.jb_melspec_free.restype = None
     cop = C.POINTER(MfccOpts)
     L.jb_mfcc_geometry.argtypes = [C.c_uint32, fop, cop, sz, C.POINTER(sz), u32p, C.POINTER(sz)]
     L.jb_mfcc_dct.argtypes = [C.c_uint32, cop, vp, sz, vp, sz]
@@ -897,6 +996,15 @@ def lib():
     L.jb_synthesize_programme_fbank.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, fop,
                                                 C.POINTER(JoinOpts), C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz),
                                                 C.POINTER(C.c_uint64)]
+    L.jb_synthesize_melspec.argtypes = [vp, C.POINTER(C.c_char_p), sz, msop, C.POINTER(u8p), C.POINTER(sz),
+                                        C.POINTER(sz)]
+    L.jb_synthesize_batch_melspec.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, msop,
+                                              C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_batch_each_melspec.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
+                                                   msop, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_programme_melspec.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, msop,
+                                                  C.POINTER(JoinOpts), C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz),
+                                                  C.POINTER(C.c_uint64)]
     L.jb_write_wav_adpcm.argtypes = [C.c_char_p, vp, sz, sz, C.c_uint32, C.c_uint32]
     L.jb_synthesize_adpcm.argtypes = [vp, C.POINTER(C.c_char_p), sz, aop, C.POINTER(u8p), C.POINTER(sz),
                                       C.POINTER(sz)]
@@ -1391,6 +1499,75 @@ def fbank_pcm(pcms, hz, opts: FbankOpts, device: int = -1):
     bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
     check(L.jb_fbank_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, bufs, ns))
     res = take_fbank(L, bufs, ns, n, opts)
+    return res[0] if single else res
+
+
+def melspec_geometry(hz: int, opts: MelspecOpts, n: int = 0):
+    """jb_melspec_geometry: (n_fft, win_length, hop_length, T, bytes) of n samples at hz."""
+    nfft, wl, hop, T, nby = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_size_t(), C.c_size_t()
+    check(lib().jb_melspec_geometry(hz, C.byref(opts), n, C.byref(nfft), C.byref(wl), C.byref(hop), C.byref(T),
+                                    C.byref(nby)))
+    return nfft.value, wl.value, hop.value, T.value, nby.value
+
+
+def melspec_window(hz: int, opts: MelspecOpts):
+    """jb_melspec_window: the n_fft window values a frame is multiplied by (the Hann window centred, zeros around it)."""
+    import numpy as np
+
+    w = np.empty(melspec_geometry(hz, opts)[0], dtype=np.float64)
+    check(lib().jb_melspec_window(hz, C.byref(opts), w.ctypes.data, w.size))
+    return w
+
+
+def melspec_filterbank(hz: int, opts: MelspecOpts):
+    """jb_melspec_filterbank: the mel weights [n_mels, n_fft / 2 + 1] the options give at hz."""
+    import numpy as np
+
+    W = np.empty((opts.n_mels, melspec_geometry(hz, opts)[0] // 2 + 1), dtype=np.float64)
+    check(lib().jb_melspec_filterbank(hz, C.byref(opts), W.ctypes.data, W.size))
+    return W
+
+
+def melspec_frames(data: bytes, opts: MelspecOpts):
+    """The bytes of a unit's mel spectrogram as an ndarray [T, n_mels]."""
+    import numpy as np
+
+    return np.frombuffer(data, dtype=opts.dtype).reshape(-1, opts.n_mels).copy()
+
+
+def take_melspec(L, bufs, ns, n, opts: MelspecOpts):
+    """ndarrays [T, n_mels] of n library-owned outputs, each released with jb_melspec_free."""
+    return [melspec_frames(d, opts) for d in _take(L.jb_melspec_free, bufs, ns, n)]
+
+
+def melspec_host(pcm, hz: int, opts: MelspecOpts):
+    """jb_melspec_host: the mel spectrogram [T, n_mels] of float64 samples in 16-bit scale, in plain C++ on the host
+    (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    nby = melspec_geometry(hz, opts, a.size)[4]
+    out = np.empty(max(1, nby), dtype=np.uint8)
+    check(lib().jb_melspec_host(a.ctypes.data, a.size, hz, C.byref(opts), out.ctypes.data, nby))
+    return melspec_frames(out[:nby].tobytes(), opts)
+
+
+def melspec_pcm(pcms, hz, opts: MelspecOpts, device: int = -1):
+    """jb_melspec_pcm_batch: the mel spectrogram [T, n_mels] of each float64 array of `pcms` (or of one array) on the
+    GPU; hz: one rate, or one per array."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    L = lib()
+    u8p = C.POINTER(C.c_uint8)
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    check(L.jb_melspec_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, bufs, ns))
+    res = take_melspec(L, bufs, ns, n, opts)
     return res[0] if single else res
 
 

@@ -288,6 +288,7 @@ class Batch:
         self._keep = keep
         self._fbank = None  # the filterbank request the batch holds (set_fbank)
         self._mfcc = None   # the cepstral request the batch holds (set_mfcc): (FbankOpts, MfccOpts)
+        self._melspec = None  # the mel spectrogram request the batch holds (set_melspec)
 
     def __len__(self):
         return self._L.jb_batch_size(self._h)
@@ -506,7 +507,7 @@ class Batch:
         meta = F.flac_meta(md5, seek_interval_ms) or F.FlacMeta()
         F.check(self._L.jb_batch_set_flac_meta(self._h, C.byref(meta)))
 
-    # The byte sinks -- "flac", "formatted", "adpcm", "fbank", "mfcc" -- are read through one path: the C entries are
+    # The byte sinks -- "flac", "formatted", "adpcm", "fbank", "mfcc", "melspec" -- are read through one path: the C entries are
     # jb_batch_<name>_size, jb_batch_read_<name> and jb_batch_read_<name>_all
     def _sink_size(self, name, i) -> int:
         n = C.c_size_t()
@@ -637,6 +638,34 @@ class Batch:
         """Every utterance's (with a join: every programme's) rows through one device-to-host copy
         (jb_batch_read_mfcc_all)."""
         return [F.mfcc_rows(d, self._mfcc[1], self._mfcc[0].n_mels) for d in self._sink_read_all("mfcc")]
+
+    def set_melspec(self, opts=None, **kw):
+        """jb_batch_set_melspec: the run also turns each utterance's (with a join: each programme's) final f64 PCM into
+        a mel spectrogram in the librosa / Whisper convention on the GPU.  opts: F.MelspecOpts (J.melspec(...),
+        J.whisper_mel(...)), or the keywords of J.melspec; None without keywords withdraws the request.  An f64 batch
+        (neither pcm_i16 nor mlpg_only), before the first run only; independent of set_fbank and set_mfcc."""
+        if opts is None and kw:
+            opts = F.melspec(**kw)
+        F.check(self._L.jb_batch_set_melspec(self._h, C.byref(opts) if opts is not None else None))
+        self._melspec = opts  # (a refused call leaves the batch's request, and this copy of it, as they were)
+
+    def melspec_shape(self, i):
+        """(T, n_mels, hz) of unit i's mel spectrogram (jb_batch_melspec_shape)."""
+        T, m, hz = C.c_size_t(), C.c_uint32(), C.c_uint32()
+        F.check(self._L.jb_batch_melspec_shape(self._h, i, C.byref(T), C.byref(m), C.byref(hz)))
+        return T.value, m.value, hz.value
+
+    def melspec_size(self, i) -> int:
+        return self._sink_size("melspec", i)
+
+    def read_melspec(self, i):
+        """Unit i's mel spectrogram, an ndarray [T, n_mels] (jb_batch_melspec_size + jb_batch_read_melspec)."""
+        return F.melspec_frames(self._sink_read("melspec", i), self._melspec)
+
+    def read_melspec_all(self):
+        """Every utterance's (with a join: every programme's) mel spectrogram through one device-to-host copy
+        (jb_batch_read_melspec_all)."""
+        return [F.melspec_frames(d, self._melspec) for d in self._sink_read_all("melspec")]
 
     def set_join(self, req):
         """jb_batch_set_join: one request per utterance -- F.JoinUtt entries, or (programme, pad_before, pad_after,

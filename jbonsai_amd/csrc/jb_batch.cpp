@@ -2876,6 +2876,41 @@ int jb_batch_read_mfcc(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
 
 int jb_batch_read_mfcc_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Mfcc, dst); }
 
+int jb_batch_set_melspec(jb_batch *hb, const jb_melspec_opts *opts)
+{
+    return hb ? ((Batch *)hb)->out.set_melspec(opts) : JB_ERR_INVALID;
+}
+
+int jb_batch_melspec_shape(jb_batch *hb, size_t unit, size_t *T, uint32_t *n_mels, uint32_t *hz)
+{
+    const int rc = sink_planned(hb, jb::SynthSink::Melspec, unit);
+    if (rc)
+        return rc;
+    const jb::OutputChain &out = ((Batch *)hb)->out;
+    if (T)
+        *T = (size_t)out.melspec_place(unit).T;
+    if (n_mels)
+        *n_mels = out.melspec_mels();
+    if (hz)
+        *hz = out.fbank_hz(unit);
+    return JB_OK;
+}
+
+int jb_batch_melspec_size(jb_batch *hb, size_t unit, size_t *n_bytes)
+{
+    return sink_size(hb, jb::SynthSink::Melspec, unit, n_bytes);
+}
+
+int jb_batch_read_melspec(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
+{
+    return sink_read(hb, jb::SynthSink::Melspec, unit, dst, cap, "jb_batch_read_melspec");
+}
+
+int jb_batch_read_melspec_all(jb_batch *hb, uint8_t *const *dst)
+{
+    return read_bytes_all(hb, jb::SynthSink::Melspec, dst);
+}
+
 int jb_batch_set_join(jb_batch *hb, const jb_join_utt *req, size_t n)
 {
     return hb ? ((Batch *)hb)->out.set_join(req, n) : JB_ERR_INVALID;

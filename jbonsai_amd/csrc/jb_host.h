@@ -10,6 +10,7 @@
 #include "jb_limiter.h"
 #include "jb_loudness_rules.h"
 #include "jb_md5.h"
+#include "jb_melspec.h"
 #include "jb_mfcc.h"
 #include "jb_noise.h"
 #include "jb_output.h"
@@ -42,7 +43,7 @@ int noise_table(int device, size_t need, std::shared_ptr<NoiseDev> *out);
 void release_cached_memory(); // empties the per-device pools of finished batches' memory
 void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE_POOL_MB at start)
 // What an engine-level call hands out per utterance (or per programme): PCM, or the bytes of one of the encoders
-enum class SynthSink { Pcm, Flac, Formatted, Adpcm, Fbank, Mfcc };
+enum class SynthSink { Pcm, Flac, Formatted, Adpcm, Fbank, Mfcc, Melspec };
 struct ByteSpan { // an output's place in the host copy of a byte sink's slab (OutputChain::read_bytes_all)
     uint64_t off, bytes;
 };
@@ -59,15 +60,16 @@ struct SynthRequest {
     unsigned host_threads = 0;               // 0: the default front-half thread count
     SynthSink sink = SynthSink::Pcm;
     bool i16 = false;                        // the batch's PCM in 16 bits (Pcm: what is handed out; Flac and Adpcm
-                                             // encode it) or in f64 (Formatted, Fbank and Mfcc read f64)
+                                             // encode it) or in f64 (Formatted, Fbank, Mfcc and Melspec read f64)
     const jb_flac_opts *flac = nullptr;      // Flac: both may be null (the defaults; no MD5 / SEEKTABLE request)
     const jb_flac_meta *flac_meta = nullptr;
     const jb_format_opts *fmt = nullptr;     // Formatted
     const jb_adpcm_opts *adpcm = nullptr;    // Adpcm
     const jb_fbank_opts *fbank = nullptr;    // Fbank
     const jb_mfcc_opts *mfcc = nullptr;      // Mfcc: behind the filterbank options of `fbank`
+    const jb_melspec_opts *melspec = nullptr; // Melspec
     size_t *counts = nullptr;                // counts[u] (may be null), by the sink: the samples output u's blocks
-                                             // encode (Adpcm), or its frames (Fbank, Mfcc)
+                                             // encode (Adpcm), or its frames (Fbank, Mfcc, Melspec)
     const jb_join_opts *join = nullptr;      // jb_synthesize_programme*: all utterances are one programme, the one
     uint64_t *join_starts = nullptr;         // output; join_starts[u] (may be null): each member's first sample
     void **out = nullptr;                    // [n_utts], or [1] with a join: malloc'ed PCM or bytes of each output
@@ -301,6 +303,23 @@ struct FbankClasses {
 // utts_dev[0..n) of `groups` workgroups in all
 hipError_t launch_fbank(const FbankClass *classes_dev, const FbankUtt *utts_dev, uint32_t n, uint64_t groups,
                         hipStream_t stream);
+
+// Mel spectrograms (jb_melspec.hip; the rule, MelClass and MelUtt: jb_melspec.h; the host half: jb_melspec.cpp).
+// The distinct geometries of a launch, one per rate: their tables on the host
+struct MelClasses {
+    std::vector<uint32_t> key_hz;
+    std::vector<MelGeom> geom;
+    std::vector<MelTables> tables;
+    // the class of `hz` (made at its first use), or JB_ERR_INVALID naming the field that is out of its limits there
+    int find(const MelOpts &opts, uint32_t hz, const char *who, uint32_t *cls);
+    size_t words() const; // doubles of the device image of all tables
+    // the image (to be copied to `dev`, words() doubles) and the classes that point into it
+    void bind(const MelOpts &opts, const double *dev, std::vector<double> *image, std::vector<MelClass> *out) const;
+};
+// utts_dev[0..n) of `groups` workgroups in all; with `ranged` (the options' range above 0) k_melspec_max and
+// k_melspec_finish behind k_melspec: gmax one double per workgroup, umax one per unit (scratch; else unused)
+hipError_t launch_melspec(const MelClass *classes_dev, const MelUtt *utts_dev, uint32_t n, uint64_t groups, bool ranged,
+                          double *gmax, double *umax, hipStream_t stream);
 
 // Cepstral features (jb_mfcc.hip; the rule, MfccParams and MfccUtt: jb_mfcc.h; the host half: jb_mfcc.cpp):
 // utts_dev[0..n) of `tiles` frame tiles and `blocks` statistics blocks in all; k_ceps (with n_ceps), the statistics'
@@ -591,7 +610,8 @@ template <class T> struct DevList {
 // (jb_batch_set_filter), loudness (jb_batch_set_loudness_target, with peak mode, groups and the R128 report), the
 // join (jb_batch_set_join), then the encoders of the final PCM side by side: FLAC (jb_batch_set_flac, _flac_meta),
 // the sample format (jb_batch_set_format), IMA ADPCM (jb_batch_set_adpcm) and the filterbank features
-// (jb_batch_set_fbank) and the cepstral features (jb_batch_set_mfcc) -- and all their device state.
+// (jb_batch_set_fbank), the cepstral features (jb_batch_set_mfcc) and the mel spectrograms (jb_batch_set_melspec) --
+// and all their device state.
 // The setters record a request and plan again (jb_output.h); the first run carries the plan out (prepare); every run
 // enqueues the chain once behind the hand-off check, and finish_verify once more for the utterances its redo rounds
 // rewrote.  Each stage has the same three steps: prepare_X (its lists and scratch), select_X (what the next launch
@@ -621,6 +641,9 @@ struct OutputChain {
     // options checked at every utterance's output rate (both NULL: the request is withdrawn); set_output_rate checks
     // the combined request again.  Independent of set_fbank
     int set_mfcc(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts);
+    // the mel spectrograms (jb_melspec.h): an f64 batch only; checked at every utterance's output rate (NULL: the
+    // request is withdrawn); set_output_rate checks the combined request again.  Independent of set_fbank and set_mfcc
+    int set_melspec(const jb_melspec_opts *opts);
     // f[0..n): n == 1 or B filters (nullptr, 0: the request is withdrawn), each checked at its utterance's output
     // rate; set_output_rate checks the combined request again
     int set_filter(const jb_filter *f, size_t n);
@@ -681,6 +704,8 @@ struct OutputChain {
     const OutAdpcmUtt &adpcm_place(size_t u) const { return plan.adpcm[u]; }
     const OutFbankUtt &fbank_place(size_t u) const { return plan.fbank[u]; }
     const OutMfccUtt &mfcc_place(size_t u) const { return plan.mfcc[u]; }
+    const OutMelUtt &melspec_place(size_t u) const { return plan.melspec[u]; }
+    uint32_t melspec_mels() const { return ml_p.n_mels; }
     uint32_t fbank_mels() const { return fb_p.n_mels; }
     uint32_t fbank_hz(size_t u) const { return joined() ? plan.units[u].hz : plan.utt[u].hz; }
     // the join: what the encoders' entries index (the programmes, or the utterances without a request), an
@@ -707,6 +732,8 @@ private:
     bool mf_on = false;                        // cepstral features are requested
     FbankOpts mf_fb{};                         // their filterbank options, as the caller gave them
     MfccOpts mf_p{};
+    bool ml_on = false;                        // mel spectrograms are requested
+    MelOpts ml_p{};
     std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
     std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
@@ -832,6 +859,13 @@ private:
         FbankClass *classes_dev = nullptr;
         MfccParams P{};
     } mf;
+    struct Melspec { // follows `units`: k_melspec, and with a range the fold of the maxima and the finish pass
+        DevList<MelUtt> utts;
+        std::vector<uint64_t> ngroups; // [U] each unit's workgroups
+        uint64_t groups = 0;
+        MelClass *classes_dev = nullptr;
+        double *gmax = nullptr, *umax = nullptr; // with a range: one double per workgroup, one per unit
+    } ml;
     // the units the encoders take: the programmes in the join slab, or the utterances
     struct EncUnit {
         uint64_t off, n;
@@ -860,6 +894,8 @@ private:
     bool adpcm() const { return plan.adpcm_src.slab != OutSlab::None; }
     bool fbank() const { return plan.fbank_src != OutSlab::None; }
     bool mfcc() const { return plan.mfcc_src != OutSlab::None; }
+    bool melspec() const { return plan.melspec_src != OutSlab::None; }
+    int check_melspec(const MelOpts &opts, const std::vector<uint32_t> &want, const char *who) const;
     int check_mfcc(const FbankOpts &fopts, const std::vector<uint32_t> &want, const char *who) const;
     int check_fbank(const FbankOpts &opts, const std::vector<uint32_t> &want, const char *who) const;
     void replan(); // host geometry and routing of the present requests
@@ -891,6 +927,7 @@ private:
     int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);
     int prepare_fbank(), select_fbank(const RedoScope *scope), launch_fbank(bool redo);
     int prepare_mfcc(), select_mfcc(const RedoScope *scope), launch_mfcc(bool redo);
+    int prepare_melspec(), select_melspec(const RedoScope *scope), launch_melspec(bool redo);
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
     struct ByteSink {
         bool on;                       // the sink is requested

@@ -1,0 +1,392 @@
+// jb_melspec.hip -- mel spectrograms on the device: the chain's final f64 PCM as [T][n_mels] frames, by the rule of
+// jb_melspec.h.
+//
+//   k_melspec         a workgroup takes mel_wg_frames(n_fft) consecutive frames of one unit (workgroups never cross
+//                     units), a frame mel_frame_lanes(n_fft) lanes: a wave up to n_fft 1024, two up to 2048, all four
+//                     above, so that a workgroup holds at most kMelPoints complex points (33 KB of LDS in f64 with the
+//                     pads) beside the 32 KB of the passes' twiddles W_M^p, p < M (the whole circle: a radix-5 pass
+//                     asks for four fifths of it), staged once per workgroup: two workgroups to a CU.
+//                     A frame's n_fft real samples are windowed on the way in -- predicated: the reflection is an index
+//                     map (mel_sample_at), nothing outside the unit or the window is read -- and packed two to a
+//                     complex point, stored at its digit-reversed place (a table: M entries).  The in-place passes of
+//                     the factors 5, 3 and 2 of M follow, one to a barrier; a lane takes butterflies l, l + fl, ... of
+//                     the pass's M / r and holds one butterfly's r points in registers (mel_butterfly, the host's
+//                     text); no two passes are fused.  Each lane then untangles pairs (k, M - k) into |X_k|^2 in place
+//                     (fbank_power; the square root under JB_MEL_MAGNITUDE), every bin is multiplied by its weight in
+//                     its rising and in its falling filter, and one lane per filter adds its products in ascending
+//                     order, takes the logarithm and, without a range, the affine step and writes the element.  The
+//                     spectrum never leaves LDS.
+//                     LDS places: one pad double behind every 32 (mel_at, as k_fbank).  The passes of 5 and 3 come
+//                     first, where the span is odd: a half-wave's reads of one operand step by r doubles (pass 0) or
+//                     by one double with a jump of (r - 1) L at a block's end: conflict-free but for those jumps.  The
+//                     passes of 2 that follow have spans of a multiple of the odd part: consecutive lanes read
+//                     consecutive doubles.  For a power of two the first pass steps by two doubles (two-way), the
+//                     digit-reversed stores of the load are spread by the pad.
+//                     Every operation of a frame is its own butterfly, pair, bin or filter: its order does not depend
+//                     on the lanes that share the frame, on the frame's place in the workgroup or on the batch.
+//   with range > 0    k_melspec writes the f64 values in front of the clamp to the unit's scratch and the largest of its
+//                     workgroup to gmax[blockIdx] (a tree in LDS; a maximum has no order);
+//   k_melspec_max     a workgroup per unit folds the unit's entries of gmax into umax[unit];
+//   k_melspec_finish  the grid of k_melspec again: each workgroup streams its frames' elements through the clamp, the
+//                     affine step and the element conversion.
+#include "jb_host.h"
+
+#include <algorithm>
+#include <stdlib.h>
+#include <string.h>
+
+namespace jb {
+
+namespace {
+
+__host__ __device__ __forceinline__ constexpr uint32_t mel_at(uint32_t i) { return i + (i >> 5); }
+// the frames of a workgroup: 4 x (mel_at(512) + 1), 2 x (mel_at(1024) + 1) or mel_at(2048) + 1 slots
+constexpr uint32_t kMelSlots = 4 * (mel_at(kMelPoints / 4) + 1) + 4;
+
+__device__ __forceinline__ uint32_t mel_find(const MelUtt *utts, uint32_t n, uint64_t idx)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (utts[mid].g0 <= idx)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kMelLanes) void k_melspec(const MelClass *__restrict__ classes,
+                                                       const MelUtt *__restrict__ utts, uint32_t n_utts,
+                                                       double *__restrict__ gmax)
+{
+    // (a frame's arrays hold M + 1 values, the untangling leaves S_M in the last one, at the padded places of mel_at)
+    __shared__ double s_re[kMelSlots], s_im[kMelSlots];
+    __shared__ double s_twc[kMelPoints], s_tws[kMelPoints];
+    __shared__ double s_max[kMelLanes];
+    const uint32_t u = mel_find(utts, n_utts, blockIdx.x);
+    const MelUtt U = utts[u];
+    const MelClass &C = classes[U.cls];
+    const uint32_t N = C.n_fft, M = N / 2;
+    const uint32_t fl = mel_frame_lanes(N), nf = kMelLanes / fl;
+    const uint32_t f = threadIdx.x / fl, l = threadIdx.x % fl;
+    const uint64_t t = (blockIdx.x - U.g0) * (uint64_t)nf + f;
+    const bool live = t < U.T; // (a workgroup's last frames may lie behind the unit's: they load, store and sum nothing)
+    double *re = s_re + f * (mel_at(M) + 1), *im = s_im + f * (mel_at(M) + 1);
+    const uint32_t pad = C.pad, wl = C.wl, woff = C.woff;
+    const int64_t k0 = (int64_t)(t * C.hop) - (pad == kMelPadNone ? 0 : (int64_t)M);
+    for (uint32_t p = threadIdx.x; p < M; p += kMelLanes) {
+        s_twc[p] = C.twc[p];
+        s_tws[p] = C.tws[p];
+    }
+    if (live)
+        for (uint32_t j = l; j < M; j += fl) {
+            double v[2];
+#pragma unroll
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint32_t i = 2 * j + h; // (i < n_fft; the window lies at [woff, woff + wl))
+                const int64_t k = mel_sample_at(k0 + (int64_t)i, U.n, pad);
+                const bool in = i >= woff && i < woff + wl && k >= 0;
+                v[h] = in ? C.win[i - woff] * (U.x[k] * 0x1p-15) : 0.0;
+            }
+            const uint32_t r = mel_at(C.rev[j]);
+            re[r] = v[0];
+            im[r] = v[1];
+        }
+    const uint32_t n_pass = C.n_pass;
+    for (uint32_t s = 0; s < n_pass; s++) {
+        __syncthreads();
+        const uint32_t r = C.r[s], L = C.L[s], inv = C.inv[s];
+        if (live)
+            for (uint32_t j = l; j < M / r; j += fl)
+                mel_butterfly(re, im, s_twc, s_tws, M, r, L, inv, j, [](uint32_t i) { return mel_at(i); });
+    }
+    __syncthreads();
+    const bool magnitude = (C.flags & kMelMagnitude) != 0;
+    if (live)
+        for (uint32_t k = l; k <= M / 2; k += fl) { // fbank_untangle at the padded places
+            const uint32_t kk = M - k, ik = mel_at(k), iz = mel_at(kk == M ? 0 : kk);
+            const double ar = re[ik], ai = im[ik], zr = re[iz], zi = im[iz];
+            const double p0 = fbank_power(ar, ai, zr, zi, C.tw[2 * k], C.tw[2 * k + 1]);
+            re[ik] = magnitude ? sqrt(p0) : p0;
+            if (kk != k) {
+                const double p1 = fbank_power(zr, zi, ar, ai, C.tw[2 * kk], C.tw[2 * kk + 1]);
+                re[mel_at(kk)] = magnitude ? sqrt(p1) : p1;
+            }
+        }
+    __syncthreads();
+    // every bin's two products: rising into im, falling in place
+    if (live)
+        for (uint32_t k = l; k <= M; k += fl) {
+            const double p = re[mel_at(k)];
+            im[mel_at(k)] = C.wr[k] * p;
+            re[mel_at(k)] = C.wf[k] * p;
+        }
+    __syncthreads();
+    const bool ranged = C.range > 0.0;
+    double top = -HUGE_VAL;
+    if (live) {
+        const uint64_t row = t * C.n_mels;
+        for (uint32_t m = l; m < C.n_mels; m += fl) {
+            const uint32_t k0m = C.first[m], k1m = k0m + C.rise[m], k2m = k0m + C.count[m];
+            double e = 0.0;
+#pragma unroll 4
+            for (uint32_t k = k0m; k < k1m; k++)
+                e += im[mel_at(k)];
+#pragma unroll 4
+            for (uint32_t k = k1m; k < k2m; k++)
+                e += re[mel_at(k)];
+            const double y = mel_log(e, C.log, C.floor, C.y_floor);
+            if (ranged) {
+                U.s[row + m] = y;
+                top = y > top ? y : top;
+            } else {
+                const double v = mel_affine(y, C.offset, C.scale);
+                if (C.flags & kMelF64)
+                    ((double *)U.y)[row + m] = v;
+                else
+                    ((float *)U.y)[row + m] = (float)v;
+            }
+        }
+    }
+    if (!ranged) // (uniform over the workgroup)
+        return;
+    s_max[threadIdx.x] = top;
+    for (uint32_t h = kMelLanes / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (threadIdx.x < h) {
+            const double o = s_max[threadIdx.x + h];
+            s_max[threadIdx.x] = o > s_max[threadIdx.x] ? o : s_max[threadIdx.x];
+        }
+    }
+    if (threadIdx.x == 0)
+        gmax[blockIdx.x] = s_max[0];
+}
+
+// Unit blockIdx.x: the largest of its workgroups' maxima (its entries of gmax follow one another from g0)
+__global__ __launch_bounds__(kMelLanes) void k_melspec_max(const MelClass *__restrict__ classes,
+                                                           const MelUtt *__restrict__ utts,
+                                                           const double *__restrict__ gmax, double *__restrict__ umax)
+{
+    __shared__ double s_max[kMelLanes];
+    const MelUtt U = utts[blockIdx.x];
+    const uint32_t nf = mel_wg_frames(classes[U.cls].n_fft);
+    const uint64_t groups = (U.T + nf - 1) / nf;
+    double top = -HUGE_VAL;
+    for (uint64_t g = threadIdx.x; g < groups; g += kMelLanes) {
+        const double o = gmax[U.g0 + g];
+        top = o > top ? o : top;
+    }
+    s_max[threadIdx.x] = top;
+    for (uint32_t h = kMelLanes / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (threadIdx.x < h) {
+            const double o = s_max[threadIdx.x + h];
+            s_max[threadIdx.x] = o > s_max[threadIdx.x] ? o : s_max[threadIdx.x];
+        }
+    }
+    if (threadIdx.x == 0)
+        umax[blockIdx.x] = s_max[0];
+}
+
+// The grid of k_melspec: a workgroup's frames' elements from the scratch through the clamp, the affine step and the
+// element conversion
+__global__ __launch_bounds__(kMelLanes) void k_melspec_finish(const MelClass *__restrict__ classes,
+                                                              const MelUtt *__restrict__ utts, uint32_t n_utts,
+                                                              const double *__restrict__ umax)
+{
+    const uint32_t u = mel_find(utts, n_utts, blockIdx.x);
+    const MelUtt U = utts[u];
+    const MelClass &C = classes[U.cls];
+    const uint32_t nf = mel_wg_frames(C.n_fft);
+    const uint64_t t0 = (blockIdx.x - U.g0) * (uint64_t)nf;
+    const uint64_t t1 = t0 + nf < U.T ? t0 + nf : U.T;
+    const double low = umax[u] - C.range, offset = C.offset, scale = C.scale;
+    const bool f64 = (C.flags & kMelF64) != 0;
+    for (uint64_t i = t0 * C.n_mels + threadIdx.x; i < t1 * C.n_mels; i += kMelLanes) {
+        const double y = U.s[i];
+        const double v = mel_affine(y > low ? y : low, offset, scale);
+        if (f64)
+            ((double *)U.y)[i] = v;
+        else
+            ((float *)U.y)[i] = (float)v;
+    }
+}
+
+} // namespace
+
+hipError_t launch_melspec(const MelClass *classes_dev, const MelUtt *utts_dev, uint32_t n, uint64_t groups, bool ranged,
+                          double *gmax, double *umax, hipStream_t stream)
+{
+    if (n == 0 || groups == 0)
+        return hipSuccess;
+    if (groups > 0x7fffffffull)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_melspec, dim3((uint32_t)groups), dim3(kMelLanes), 0, stream, classes_dev, utts_dev, n, gmax);
+    if (ranged) {
+        hipLaunchKernelGGL(k_melspec_max, dim3(n), dim3(kMelLanes), 0, stream, classes_dev, utts_dev, gmax, umax);
+        hipLaunchKernelGGL(k_melspec_finish, dim3((uint32_t)groups), dim3(kMelLanes), 0, stream, classes_dev, utts_dev,
+                           n, umax);
+    }
+    return hipGetLastError();
+}
+
+int MelClasses::find(const MelOpts &opts, uint32_t hz, const char *who, uint32_t *cls)
+{
+    for (size_t i = 0; i < key_hz.size(); i++)
+        if (key_hz[i] == hz) {
+            *cls = (uint32_t)i;
+            return JB_OK;
+        }
+    MelGeom g{};
+    const int rc = mel_geometry(&opts, hz, who, &g);
+    if (rc)
+        return rc;
+    MelTables t; // (a class is listed once its tables stand)
+    if (!mel_tables(g, hz, opts, &t)) {
+        set_error(std::string(who) + ": the filterbank at " + std::to_string(hz) + " Hz has no by-bin form");
+        return JB_ERR_INVALID;
+    }
+    *cls = (uint32_t)key_hz.size();
+    key_hz.push_back(hz);
+    geom.push_back(g);
+    tables.push_back(std::move(t));
+    return JB_OK;
+}
+
+size_t MelClasses::words() const
+{
+    size_t w = 0;
+    for (const MelTables &t : tables)
+        w += t.win.size() + t.tw.size() + t.twc.size() + t.tws.size() + t.wr.size() + t.wf.size() +
+             (t.rev.size() + 3 * t.first.size() + 1) / 2;
+    return w;
+}
+
+void MelClasses::bind(const MelOpts &opts, const double *dev, std::vector<double> *image,
+                      std::vector<MelClass> *out) const
+{
+    image->clear();
+    out->clear();
+    for (size_t i = 0; i < tables.size(); i++) {
+        const MelTables &t = tables[i];
+        const MelGeom &g = geom[i];
+        MelClass c{};
+        auto put = [&](const std::vector<double> &v) {
+            const double *at = dev + image->size();
+            image->insert(image->end(), v.begin(), v.end());
+            return at;
+        };
+        c.win = put(t.win);
+        c.tw = put(t.tw);
+        c.twc = put(t.twc);
+        c.tws = put(t.tws);
+        c.wr = put(t.wr);
+        c.wf = put(t.wf);
+        // the four lists of uint32 behind them, in whole doubles
+        const size_t nm = t.first.size(), nr = t.rev.size();
+        std::vector<double> ints((nr + 3 * nm + 1) / 2, 0.0);
+        uint32_t *ip = (uint32_t *)ints.data();
+        memcpy(ip, t.rev.data(), 4 * nr);
+        memcpy(ip + nr, t.first.data(), 4 * nm);
+        memcpy(ip + nr + nm, t.count.data(), 4 * nm);
+        memcpy(ip + nr + 2 * nm, t.rise.data(), 4 * nm);
+        const uint32_t *di = (const uint32_t *)put(ints);
+        c.rev = di;
+        c.first = di + nr;
+        c.count = di + nr + nm;
+        c.rise = di + nr + 2 * nm;
+        c.n_fft = g.n_fft;
+        c.wl = g.wl;
+        c.woff = g.woff;
+        c.hop = g.hop;
+        c.n_mels = g.n_mels;
+        c.flags = opts.flags;
+        c.pad = opts.pad;
+        c.log = opts.log;
+        c.n_pass = t.sched.n;
+        for (uint32_t s = 0; s < t.sched.n; s++) {
+            c.r[s] = t.sched.r[s];
+            c.L[s] = t.sched.L[s];
+            c.inv[s] = t.sched.inv[s];
+        }
+        c.floor = g.floor;
+        c.y_floor = g.y_floor;
+        c.range = opts.range;
+        c.offset = opts.offset;
+        c.scale = g.scale;
+        out->push_back(c);
+    }
+}
+
+} // namespace jb
+
+using namespace jb;
+
+extern "C" {
+
+int jb_melspec_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                         const jb_melspec_opts *opts, int32_t device, uint8_t **out, size_t *n_bytes)
+{
+    const MelOpts *o = (const MelOpts *)opts;
+    int rc = mel_check_opts(o, "jb_melspec_pcm_batch");
+    if (rc)
+        return rc;
+    if ((rc = pcm_check((const void *const *)in, n_in, n, hz && out && n_bytes, (void **)out, n_bytes)))
+        return rc;
+    // (every rate's geometry before a device is touched)
+    MelClasses cls;
+    std::vector<MelUtt> utts(n);
+    for (size_t u = 0; u < n; u++)
+        if ((rc = cls.find(*o, hz[u], "jb_melspec_pcm_batch", &utts[u].cls)))
+            return rc;
+    DeviceScratch ds;
+    if ((rc = ds.open(device, "jb_melspec_pcm_batch")))
+        return rc;
+    // the inputs packed one after the other (8-byte aligned, as a batch's slab has them), every output on a
+    // 16-byte boundary; with a range the f64 values in front of the clamp in a scratch of their own
+    const bool ranged = o->range > 0.0;
+    std::vector<uint64_t> xoff;
+    const double *dx = ds.pack(in, n_in, n, &xoff);
+    std::vector<PcmShare> shares(n);
+    std::vector<uint64_t> soff(n);
+    uint64_t bytes = 0, groups = 0, values = 0;
+    for (size_t u = 0; u < n; u++) {
+        MelUtt &w = utts[u];
+        const MelGeom &g = cls.geom[w.cls];
+        w.n = n_in[u];
+        w.T = mel_frames(w.n, g.n_fft, g.hop, o->pad, o->flags);
+        w.g0 = groups;
+        shares[u] = {bytes, w.T * g.n_mels * mel_elem(o->flags)};
+        soff[u] = values;
+        bytes += (shares[u].n + 15) & ~(uint64_t)15;
+        values += w.T * g.n_mels;
+        groups += (w.T + mel_wg_frames(g.n_fft) - 1) / mel_wg_frames(g.n_fft);
+    }
+    uint8_t *dy = ds.alloc<uint8_t>(std::max<uint64_t>(bytes, 16));
+    double *dsc = ranged ? ds.alloc<double>(values) : nullptr;
+    double *gmax = ranged ? ds.alloc<double>(groups) : nullptr;
+    double *umax = ranged ? ds.alloc<double>(n) : nullptr;
+    for (size_t u = 0; u < n; u++) {
+        utts[u].x = dx + xoff[u];
+        utts[u].y = dy + shares[u].off;
+        utts[u].s = ranged ? dsc + soff[u] : nullptr;
+    }
+    double *dt = ds.alloc<double>(cls.words());
+    std::vector<double> image;
+    std::vector<MelClass> classes;
+    cls.bind(*o, dt, &image, &classes);
+    if (ds.ok() && !image.empty())
+        ds.err = hipMemcpyAsync(dt, image.data(), sizeof(double) * image.size(), hipMemcpyHostToDevice, ds.stream);
+    const MelClass *dc = ds.upload(classes);
+    const MelUtt *du = ds.upload(utts);
+    if (ds.ok())
+        ds.err = launch_melspec(dc, du, (uint32_t)n, groups, ranged, gmax, umax, ds.stream);
+    std::vector<uint8_t> host;
+    ds.read_back(&host, dy, bytes);
+    if ((rc = ds.status()))
+        return rc;
+    return hand_out(host.data(), 1, shares, (void **)out, n_bytes);
+}
+
+} // extern "C"

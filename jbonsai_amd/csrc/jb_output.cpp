@@ -171,6 +171,30 @@ OutPlan plan_output(const OutPlanIn &in)
             p.alloc[(size_t)OutSlab::Mfcc] = std::max<uint64_t>(bytes, 16);
         }
     }
+    // the mel spectrograms beside them, independent of both: the same final f64 to frames of each unit's own length;
+    // with a range the f64 values in front of the clamp in a scratch of the stage
+    if (in.melspec && !p.final.i16) {
+        const MelOpts &mo = *in.melspec;
+        std::vector<OutMelUtt> f(units.size());
+        uint64_t bytes = 0, words = 0;
+        bool ok = true;
+        for (size_t u = 0; u < units.size() && ok; u++) {
+            MelGeom g{};
+            if (!(ok = mel_geometry_quiet(mo, units[u].hz, &g)))
+                break;
+            const uint64_t T = mel_frames(units[u].n, g.n_fft, g.hop, mo.pad, mo.flags);
+            f[u] = {bytes, T * g.n_mels * mel_elem(mo.flags), T, g.n_fft, g.hop, mo.range > 0.0 ? words : 0};
+            bytes += (f[u].bytes + 15) & ~(uint64_t)15;
+            words += (T * g.n_mels + 1) & ~(uint64_t)1;
+        }
+        if (ok) {
+            p.melspec_src = enc.slab;
+            p.melspec = std::move(f);
+            p.alloc[(size_t)OutSlab::Mel] = std::max<uint64_t>(bytes, 16);
+            if (mo.range > 0.0)
+                p.alloc[(size_t)OutSlab::MelY] = std::max<uint64_t>(words, 2);
+        }
+    }
     return p;
 }
 

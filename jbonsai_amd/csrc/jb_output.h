@@ -1,7 +1,7 @@
 #pragma once
 // jb_output.h -- the routing of the stages behind the vocoder, in their order: converter (output rate), filter,
 // loudness (measurement, groups, report, apply pass), join, then the encoders side by side: FLAC, sample format, IMA
-// ADPCM, filterbank features.  plan_output (jb_output.cpp) decides from the batch's shape and the requests alone which slab each stage
+// ADPCM, filterbank features, cepstral features, mel spectrograms.  plan_output (jb_output.cpp) decides from the batch's shape and the requests alone which slab each stage
 // reads and writes, in f64 or in 16 bits, which slab the read entries hand out, each utterance's output geometry and
 // its place in the encoders' byte slabs, and with a join request (jb_join.h) the programmes: their numbering, each
 // one's place in the join slab, each member's start, and the encoders' geometry by programme instead of by utterance.
@@ -14,6 +14,7 @@
 
 #include "jb_fbank.h"
 #include "jb_mfcc.h"
+#include "jb_melspec.h"
 #include "jb_join.h"
 
 namespace jb {
@@ -36,11 +37,13 @@ enum class OutSlab : uint8_t {
     Feat,    // bytes of the filterbank features
     MfccL,   // f64 log-mel frames the cepstral stage makes for itself
     Mfcc,    // bytes of the cepstral features
+    Mel,     // bytes of the mel spectrograms
+    MelY,    // f64 values the mel stage holds in front of its range clamp (with a range only)
     Count
 };
 constexpr size_t out_slab_elem(OutSlab s) // bytes
 {
-    return s == OutSlab::Fmt || s == OutSlab::Adpcm || s == OutSlab::Feat || s == OutSlab::Mfcc ? 1
+    return s == OutSlab::Fmt || s == OutSlab::Adpcm || s == OutSlab::Feat || s == OutSlab::Mfcc || s == OutSlab::Mel ? 1
            : s == OutSlab::S16 || s == OutSlab::New16 || s == OutSlab::Join16 ? 2
                                                                                : 8;
 }
@@ -66,6 +69,7 @@ struct OutPlanIn {
     const FbankOpts *fbank = nullptr;     // the filterbank request (jb_fbank.h), checked at every output rate; nullptr: none
     const FbankOpts *mfcc_fbank = nullptr; // the cepstral request (jb_mfcc.h): its filterbank's geometry (the stage forces
     const MfccOpts *mfcc = nullptr;        // f64 logarithms itself) and its options; both or neither
+    const MelOpts *melspec = nullptr;      // the mel spectrogram request (jb_melspec.h), checked at every output rate; nullptr: none
 };
 
 struct OutUtt {
@@ -94,6 +98,13 @@ struct OutMfccUtt { // a unit's cepstral rows in the Mfcc slab and its log-mel f
     uint32_t width;      // elements of a row: d (delta_order + 1)
     uint32_t n_fft;      // of its filterbank geometry, by its rate
     uint64_t loff;       // its first log-mel value in the MfccL slab, in doubles (a 16-byte boundary)
+};
+
+struct OutMelUtt { // a unit's mel spectrogram in the Mel slab and, with a range, its f64 values in the MelY slab
+    uint64_t off, bytes; // byte offset (16-byte aligned) and T * n_mels * bytes per element
+    uint64_t T;          // its frames
+    uint32_t n_fft, hop; // its geometry (in samples: the same at every rate)
+    uint64_t yoff;       // its first value in the MelY slab, in doubles (a 16-byte boundary); 0 without a range
 };
 
 struct OutUnit { // a programme in the join slab: what the encoders behind a join take for an utterance
@@ -129,8 +140,10 @@ struct OutPlan {
     std::vector<OutFbankUtt> fbank;    // [B] with an fbank stage, else empty
     OutSlab mfcc_src = OutSlab::None;  // f64 the cepstral stage reads: what fbank_src would name (None: no request)
     std::vector<OutMfccUtt> mfcc;      // [B] with a cepstral stage, else empty
+    OutSlab melspec_src = OutSlab::None; // f64 the mel stage reads: what fbank_src would name (None: no request)
+    std::vector<OutMelUtt> melspec;      // [B] with a mel stage, else empty
     // With a join request: the stage reads what `final` names and writes the programmes to a slab of its own; flac,
-    // fmt_src, adpcm_src, fbank_src and mfcc_src then name that slab, and fmt, adpcm, fbank and mfcc have [P] entries laid
+    // fmt_src, adpcm_src, fbank_src, mfcc_src and melspec_src then name that slab, and fmt, adpcm, fbank, mfcc and melspec have [P] entries laid
     // out from `units`
     OutWrite join_src, join;          // None: no join
     std::vector<OutUnit> units;       // [P] the programmes

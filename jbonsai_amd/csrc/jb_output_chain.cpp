@@ -45,6 +45,7 @@ void OutputChain::replan()
     in.fbank = fb_on ? &fb_p : nullptr;
     in.mfcc_fbank = mf_on ? &mf_fb : nullptr;
     in.mfcc = mf_on ? &mf_p : nullptr;
+    in.melspec = ml_on ? &ml_p : nullptr;
     plan = plan_output(in);
 }
 
@@ -114,7 +115,8 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
         (rc = check_fir(want, "jb_batch_set_output_rate")) ||
         (rc = check_noise(want, "jb_batch_set_output_rate")) ||
         (fb_on && (rc = check_fbank(fb_p, want, "jb_batch_set_output_rate"))) ||
-        (mf_on && (rc = check_mfcc(mf_fb, want, "jb_batch_set_output_rate"))))
+        (mf_on && (rc = check_mfcc(mf_fb, want, "jb_batch_set_output_rate"))) ||
+        (ml_on && (rc = check_melspec(ml_p, want, "jb_batch_set_output_rate"))))
         return rc;
     want_hz = std::move(want);
     replan();
@@ -363,6 +365,40 @@ int OutputChain::set_mfcc(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts)
         mf_fb = *(const FbankOpts *)fopts;
         mf_p = *(const MfccOpts *)opts;
     }
+    replan();
+    return JB_OK;
+}
+
+// The mel spectrogram request under these rates: JB_ERR_INVALID naming the field that is out of its limits at some rate
+int OutputChain::check_melspec(const MelOpts &opts, const std::vector<uint32_t> &want, const char *who) const
+{
+    int rc;
+    for (uint32_t hz : rates_under(want))
+        if ((rc = mel_geometry(&opts, hz, who, nullptr)))
+            return rc;
+    return JB_OK;
+}
+
+int OutputChain::set_melspec(const jb_melspec_opts *opts)
+{
+    int rc;
+    if (opts && (rc = mel_check_opts((const MelOpts *)opts, "jb_batch_set_melspec")))
+        return rc;
+    if (b.flags & JB_BATCH_MLPG_ONLY) {
+        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_UNSUPPORTED;
+    }
+    if (b.flags & JB_BATCH_PCM_I16) {
+        set_error("jb_batch_set_melspec: the mel stage reads the f64 output (a batch without JB_BATCH_PCM_I16)");
+        return JB_ERR_UNSUPPORTED;
+    }
+    if ((rc = check_settable("jb_batch_set_melspec: the features are set before the batch's first run")))
+        return rc;
+    if (opts && (rc = check_melspec(*(const MelOpts *)opts, want_hz, "jb_batch_set_melspec")))
+        return rc;
+    ml_on = opts != nullptr;
+    if (opts)
+        ml_p = *(const MelOpts *)opts;
     replan();
     return JB_OK;
 }
@@ -642,7 +678,7 @@ int OutputChain::prepare()
     if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_noise()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
         (rc = prepare_join()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
-        (rc = prepare_fbank()) || (rc = prepare_mfcc()))
+        (rc = prepare_fbank()) || (rc = prepare_mfcc()) || (rc = prepare_melspec()))
         return rc;
     if (plan.active()) {
         void *voc = slab[(size_t)plan.vocoder.slab];
@@ -657,7 +693,7 @@ int OutputChain::prepare()
 // uploaded (select_X) before its first launch, and one wait ends it
 int OutputChain::enqueue(const std::vector<uint8_t> *only)
 {
-    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || mfcc() || joined()))
+    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || mfcc() || melspec() || joined()))
         return JB_OK;
     const bool redo = only != nullptr;
     static const LnGroups no_groups;
@@ -667,14 +703,16 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     int rc;
     if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_noise(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
         (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
-        (rc = select_adpcm(scope)) || (rc = select_fbank(scope)) || (rc = select_mfcc(scope)))
+        (rc = select_adpcm(scope)) || (rc = select_fbank(scope)) || (rc = select_mfcc(scope)) ||
+        (rc = select_melspec(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n || mf.utts.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n || mf.utts.n || ml.utts.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_noise(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
         (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
-        (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)) || (rc = launch_mfcc(redo)))
+        (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)) || (rc = launch_mfcc(redo)) ||
+        (rc = launch_melspec(redo)))
         return rc;
     hipError_t e;
     if (redo && (e = hipStreamSynchronize(b.stream_voc)) != hipSuccess)
@@ -1618,6 +1656,71 @@ int OutputChain::launch_mfcc(bool redo)
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "mfcc(redo)" : "mfcc");
 }
 
+// ---- the mel spectrograms beside them, of the same final f64: k_melspec, and with a range the fold of each unit's
+// maxima and the finish pass on the same stream.  The f64 values in front of the clamp lie in the MelY slab at the
+// plan's places; the workgroups' maxima are numbered by the launch list, the units' by their place in it
+int OutputChain::prepare_melspec()
+{
+    if (!melspec())
+        return JB_OK;
+    const std::vector<EncUnit> units = enc_units();
+    const size_t U = units.size();
+    const double *src = (const double *)slab[(size_t)plan.melspec_src];
+    uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Mel];
+    double *vals = (double *)slab[(size_t)OutSlab::MelY];
+    const bool ranged = ml_p.range > 0.0;
+    MelClasses cls;
+    ml.utts.host.assign(U, MelUtt{});
+    ml.ngroups.assign(U, 0);
+    ml.groups = 0;
+    int rc;
+    for (size_t u = 0; u < U; u++) {
+        const OutMelUtt &pl = plan.melspec[u];
+        MelUtt &w = ml.utts.host[u];
+        if ((rc = cls.find(ml_p, units[u].hz, "jb_batch_set_melspec", &w.cls)))
+            return rc;
+        w.x = src + units[u].off;
+        w.y = dst + pl.off;
+        w.s = ranged ? vals + pl.yoff : nullptr;
+        w.n = units[u].n;
+        w.T = pl.T;
+        w.g0 = ml.groups;
+        const uint32_t per = mel_wg_frames(pl.n_fft);
+        ml.ngroups[u] = (w.T + per - 1) / per;
+        ml.groups += ml.ngroups[u];
+    }
+    double *tables = nullptr;
+    if ((rc = b.dalloc(&tables, cls.words(), false)) ||
+        (ranged && ((rc = b.dalloc(&ml.gmax, ml.groups, false)) || (rc = b.dalloc(&ml.umax, U, false)))))
+        return rc;
+    std::vector<double> image;
+    std::vector<MelClass> classes;
+    cls.bind(ml_p, tables, &image, &classes);
+    if ((rc = upload_list(tables, image, "melspec tables")) || (rc = b.dalloc(&ml.classes_dev, classes.size(), false)) ||
+        (rc = upload_list(ml.classes_dev, classes, "melspec classes")) || (rc = ml.utts.alloc(b, U, U)))
+        return rc;
+    return ml.utts.upload("melspec work list");
+}
+
+int OutputChain::select_melspec(const RedoScope *scope)
+{
+    if (!melspec() || !scope)
+        return ml.utts.take_all(ml.groups);
+    // `units`: every unit whose final PCM changed, each recomputed whole -- its maximum runs over all its frames (one
+    // without a frame stays in the list: it has no workgroup)
+    const Picked p = pick_renumbered(scope->units, ml.ngroups);
+    return ml.utts.upload_redo(renumbered(ml.utts.host, p, &MelUtt::g0), kRedoLists, p.total);
+}
+
+int OutputChain::launch_melspec(bool redo)
+{
+    if (!melspec() || (redo && !ml.utts.n))
+        return JB_OK;
+    const hipError_t e = jb::launch_melspec(ml.classes_dev, ml.utts.list, ml.utts.n, ml.utts.total, ml_p.range > 0.0,
+                                            ml.gmax, ml.umax, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_melspec(redo)" : "k_melspec");
+}
+
 int OutputChain::check_ready(bool requested, const char *not_run, const char *not_set) const
 {
     if (requested && ready)
@@ -1746,6 +1849,9 @@ OutputChain::ByteSink OutputChain::byte_sink(SynthSink sink, size_t u) const
     case SynthSink::Mfcc:
         return {mf_on, "mfcc: the batch has not run", "mfcc: jb_batch_set_mfcc was not called",
                 slab[(size_t)OutSlab::Mfcc], true, span_of(plan.mfcc, u)};
+    case SynthSink::Melspec:
+        return {ml_on, "melspec: the batch has not run", "melspec: jb_batch_set_melspec was not called",
+                slab[(size_t)OutSlab::Mel], true, span_of(plan.melspec, u)};
     case SynthSink::Pcm:
         break;
     }

@@ -128,6 +128,10 @@ def _fbank_opts(opts, kw):
     return opts if opts is not None else F.fbank(**kw)
 
 
+def _melspec_opts(opts, kw):
+    return opts if opts is not None else F.melspec(**kw)
+
+
 def _drain(kw):
     """The keywords left in kw, taken out of it."""
     rest = dict(kw)
@@ -152,6 +156,8 @@ _PROGRAMME_SINKS = {
     "mfcc": (lambda kw: F.mfcc_request(kw.pop("opts", None), kw.pop("fbank", None), _drain(kw)),
              "jb_synthesize_programme_mfcc", True,
              lambda e, L, buf, n, cnt, o: F.take_mfcc(L, [buf], [n], 1, o[1], o[0].n_mels)[0]),
+    "melspec": (lambda kw: (_melspec_opts(kw.pop("opts", None), _drain(kw)),), "jb_synthesize_programme_melspec", True,
+                lambda e, L, buf, n, cnt, o: F.take_melspec(L, [buf], [n], 1, o[0])[0]),
 }
 
 
@@ -576,6 +582,24 @@ class Engine:
                                                  nf))
         return F.take_mfcc(self._L, bufs, ns, B, mo, fo.n_mels)
 
+    def synthesize_melspec(self, labels: Sequence[str], opts=None, **kw) -> np.ndarray:
+        """jb_synthesize_melspec: the mel spectrogram [T, n_mels] of what synthesize(labels) returns, computed on the
+        GPU.  opts: F.MelspecOpts (J.melspec(...), J.whisper_mel(...)), or the keywords of J.melspec."""
+        opts = _melspec_opts(opts, kw)
+        buf, n, nf = C.POINTER(C.c_uint8)(), C.c_size_t(), C.c_size_t()
+        F.check(self._L.jb_synthesize_melspec(self._h, _lines(labels), len(labels), C.byref(opts), C.byref(buf),
+                                              C.byref(n), C.byref(nf)))
+        return F.take_melspec(self._L, [buf], [n.value], 1, opts)[0]
+
+    def synthesize_melspec_batch(self, utterances: Sequence[Sequence[str]], opts=None, device: int = -1,
+                                 **kw) -> List[np.ndarray]:
+        """jb_synthesize_batch_melspec: each utterance of synthesize_batch(...) as a mel spectrogram."""
+        opts = _melspec_opts(opts, kw)
+        lines, offs, B = _utt_lines(utterances)
+        bufs, ns, nf = _byte_outs(B, counts=True)
+        F.check(self._L.jb_synthesize_batch_melspec(self._h, lines, offs, B, device, C.byref(opts), bufs, ns, nf))
+        return F.take_melspec(self._L, bufs, ns, B, opts)
+
     def synthesize_programme(self, utterances: Sequence[Sequence[str]], sink: str = "f64", lead_ms: float = 0.0,
                              gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0, device: int = -1,
                              **sink_opts):
@@ -583,8 +607,9 @@ class Engine:
         the next, ..., trail_ms, a fade of fade_ms at both edges of each -- joined on the GPU in front of the sink.
         sink: "f64" or "i16" (PCM arrays), "flac" (bytes; block_size, max_lpc_order, md5, seek_interval_ms),
         "formatted" (bytes; fmt, dither, seed), "adpcm" (an AdpcmStream; block_align), "fbank" (an ndarray
-        [T, n_mels]; opts=F.FbankOpts or the keywords of J.fbank) or "mfcc" (an ndarray [T, width]; opts=F.MfccOpts or
-        the keywords of J.mfcc, fbank=F.FbankOpts or a dict of J.fbank's keywords).  Returns (output, starts):
+        [T, n_mels]; opts=F.FbankOpts or the keywords of J.fbank), "mfcc" (an ndarray [T, width]; opts=F.MfccOpts or
+        the keywords of J.mfcc, fbank=F.FbankOpts or a dict of J.fbank's keywords) or "melspec" (an ndarray
+        [T, n_mels]; opts=F.MelspecOpts or the keywords of J.melspec).  Returns (output, starts):
         starts[u] is utterance u's first sample within the programme."""
         lines, offs, B = _utt_lines(utterances)
         join = F.join_opts(lead_ms, gap_ms, trail_ms, fade_ms)
@@ -601,7 +626,7 @@ class Engine:
             L.jb_join_free(out)  # (malloc'ed by the library, as every output is)
             return res, list(starts[:B])
         if sink not in _PROGRAMME_SINKS:
-            raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm", "fbank" or "mfcc"')
+            raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm", "fbank", "mfcc" or "melspec"')
         build, entry, counted, take = _PROGRAMME_SINKS[sink]
         opts = build(sink_opts)
         if sink_opts:
