@@ -29,19 +29,6 @@ constexpr uint32_t kRowDw = kAdpcmSub / 2 + 1; // a block's sub-tile, two sample
 constexpr uint32_t kOutDw = kAdpcmSub / 8 + 1; // its packed codes, padded
 constexpr uint32_t kWaves = kAdpcmLanes / 64;
 
-__device__ __forceinline__ uint32_t adpcm_find(const AdpcmUtt *utts, uint32_t n, uint64_t idx)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].g0 <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ int32_t ad_sample(double v) { return fmt_quant<false>(v, -32768.0, 32767.0, 0, 0); }
 __device__ __forceinline__ int32_t ad_sample(int16_t v) { return v; }
 __device__ __forceinline__ uint32_t ad_pack(int32_t a, int32_t b) { return ((uint32_t)a & 0xffffu) | ((uint32_t)b << 16); }
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(kAdpcmLanes) void k_adpcm(const AdpcmUtt *__restric
     __shared__ int32_t steps[kAdpcmSteps + 7];
     __shared__ uint32_t tiles[kWaves][64 * kRowDw];
     __shared__ uint32_t outs[kWaves][64 * kOutDw];
-    const uint32_t u = adpcm_find(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x);
     const AdpcmUtt U = utts[u];
     const uint32_t A = U.A, spb = U.spb;
     const uint64_t n = U.n;

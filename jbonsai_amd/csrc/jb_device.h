@@ -251,6 +251,23 @@ __device__ __forceinline__ double wave_uniform(double v)
 }
 __device__ __forceinline__ uint32_t wave_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
+// The unit of workgroup (tile, block, spectrum) `idx` of an output stage's launch list: the largest u with
+// utts[u].*base <= idx.  Lists are in unit order and `base` is the prefix sum of their counts, so units without any share
+// their successor's
+template <class U>
+__device__ __forceinline__ uint32_t find_unit(const U *utts, uint32_t n, uint64_t idx, uint64_t U::*base = &U::g0)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (utts[mid].*base <= idx)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
 // The row of LPF taps of frame f (index in the concatenated arrays), NL taps per row
 __device__ __forceinline__ const double *lpf_row(const VocDev &vd, uint64_t f, int NL)
 {

@@ -27,37 +27,17 @@ inline long double mel_of(long double f) { return 1127.0L * logl(1.0L + f / 700.
 struct HostFrame {
     const FbankGeom &g;
     const FbankTables &t;
-    uint32_t M, log2m;
     std::vector<double> re, im;
-    HostFrame(const FbankGeom &geom, const FbankTables &tab) : g(geom), t(tab), M(geom.n_fft / 2), log2m(0)
+    HostFrame(const FbankGeom &geom, const FbankTables &tab)
+        : g(geom), t(tab), re(geom.n_fft / 2 + 1, 0.0), im(geom.n_fft / 2 + 1, 0.0)
     {
-        while ((1u << log2m) < M)
-            log2m++;
-        re.assign(M + 1, 0.0);
-        im.assign(M + 1, 0.0);
     }
     // sample i of the frame, i < n_fft: x(i) windowed, 0 from wl on
     template <class X> void run(X x, double *E)
     {
-        for (uint32_t j = 0; j < M; j++) {
-            uint32_t r = 0;
-            for (uint32_t b = 0; b < log2m; b++)
-                r |= ((j >> b) & 1u) << (log2m - 1 - b);
-            re[r] = 2 * j < g.wl ? t.win[2 * j] * x(2 * j) : 0.0;
-            im[r] = 2 * j + 1 < g.wl ? t.win[2 * j + 1] * x(2 * j + 1) : 0.0;
-        }
-        for (uint32_t s = 0; s < log2m; s++)
-            for (uint32_t j = 0; j < M / 2; j++)
-                fbank_butterfly(re.data(), im.data(), t.tw.data(), log2m, s, j);
-        for (uint32_t k = 0; k <= M / 2; k++)
-            fbank_untangle(re.data(), im.data(), t.tw.data(), M, k);
-        for (uint32_t m = 0; m < g.n_mels; m++) {
-            double e = 0.0;
-            const double *w = t.wts.data() + t.woff[m];
-            for (uint32_t i = 0; i < t.count[m]; i++)
-                e += w[i] * re[t.first[m] + i];
-            E[m] = e;
-        }
+        rfft_frame_power(t.fft, [&](uint32_t i) { return i < g.wl ? t.win[i] * x(i) : 0.0; }, re.data(), im.data());
+        for (uint32_t m = 0; m < g.n_mels; m++)
+            E[m] = mel_bank_energy(t.bank, m, re.data());
     }
 };
 
@@ -119,47 +99,17 @@ bool fbank_tables(const FbankGeom &g, uint32_t hz, uint32_t window, FbankTables 
     const uint32_t K = g.n_fft / 2 + 1;
     t->win.resize(g.wl);
     fbank_window(window, g.wl, t->win.data());
-    const long double two_pi = 2.0L * acosl(-1.0L);
-    t->tw.resize(2 * (size_t)K);
-    for (uint32_t k = 0; k < K; k++) {
-        t->tw[2 * k] = (double)cosl(two_pi * k / (long double)g.n_fft);
-        t->tw[2 * k + 1] = (double)-sinl(two_pi * k / (long double)g.n_fft);
-    }
+    t->fft = rfft_plan(g.n_fft);
     std::vector<double> W((size_t)g.n_mels * K);
     fbank_filterbank(g, hz, W.data());
-    t->wts.clear();
-    t->first.assign(g.n_mels, 0);
-    t->count.assign(g.n_mels, 0);
-    t->woff.assign(g.n_mels, 0);
-    t->rise.assign(g.n_mels, 0);
-    t->wr.assign(K, 0.0);
-    t->wf.assign(K, 0.0);
     // (the centres as fbank_filterbank has them: a bin is on a filter's rising side where mu_k is at or below it)
     const long double lo = mel_of(g.f_min), hi = mel_of(g.f_max);
-    bool ok = true;
-    for (uint32_t m = 0; m < g.n_mels; m++) {
-        // (the weights rise and fall along mu: the bins above 0 are one run)
-        uint32_t a = 0, b = 0;
-        for (uint32_t k = 0; k < K; k++)
-            if (W[(size_t)m * K + k] > 0.0) {
-                if (a == b)
-                    a = k;
-                b = k + 1;
-            }
-        t->first[m] = a;
-        t->count[m] = b - a;
-        t->woff[m] = (uint32_t)t->wts.size();
-        t->wts.insert(t->wts.end(), W.begin() + (size_t)m * K + a, W.begin() + (size_t)m * K + b);
-        const long double c = lo + (hi - lo) * (m + 1) / (g.n_mels + 1);
-        for (uint32_t k = a; k < b; k++) {
-            const bool rising = mel_of((long double)k * hz / g.n_fft) <= c;
-            std::vector<double> &side = rising ? t->wr : t->wf;
-            ok = ok && side[k] == 0.0 && (rising ? t->rise[m] == k - a : true);
-            side[k] = W[(size_t)m * K + k];
-            t->rise[m] += rising;
-        }
-    }
-    return ok;
+    return mel_bank_split(
+        W.data(), g.n_mels, K,
+        [&](uint32_t m, uint32_t k) {
+            return mel_of((long double)k * hz / g.n_fft) <= lo + (hi - lo) * (m + 1) / (g.n_mels + 1);
+        },
+        &t->bank);
 }
 
 } // namespace jb

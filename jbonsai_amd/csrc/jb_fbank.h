@@ -1,19 +1,9 @@
 #pragma once
 // jb_fbank.h -- log-mel filterbank features (include/jbonsai_amd.h "Filterbank features"): the geometry of a unit, the
-// tables of one (rate, options) pair, the butterfly and the untangling of one frame's transform, stated once for the
-// kernel (jb_fbank.hip), for the host half (jb_fbank.cpp) and for the output plan (jb_output.cpp), and the stage's work
-// list.  Plain C++17; under hipcc the rules compile for the host and the device alike.
-#include <cmath>
-#include <stddef.h>
-#include <stdint.h>
-#include <vector>
-
-#ifdef __HIPCC__
-// (spelt without the HIP runtime header: jb_output.cpp includes this file without it)
-#define JB_FBANK_HD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
-#else
-#define JB_FBANK_HD inline
-#endif
+// tables of one (rate, options) pair, stated once for the kernel (jb_fbank.hip), for the host half (jb_fbank.cpp) and
+// for the output plan (jb_output.cpp), and the stage's work list.  The transform of a frame is jb_rfft.h's, the bank of
+// filters jb_melbank.h's.  Plain C++17.
+#include "jb_melbank.h"
 
 namespace jb {
 
@@ -126,17 +116,9 @@ int fbank_geometry(const FbankOpts *opts, uint32_t hz, const char *who, FbankGeo
 
 // The tables of one geometry, built in long double and rounded once
 struct FbankTables {
-    std::vector<double> win;      // [wl]
-    std::vector<double> tw;       // [n_fft / 2 + 1][2]: cos, -sin of 2 pi k / n_fft
-    std::vector<double> wts;      // the filters' weights over their supports, filter after filter
-    std::vector<uint32_t> first;  // [n_mels] a filter's first bin with a weight above 0
-    std::vector<uint32_t> count;  // [n_mels] its bins (0: it covers none)
-    std::vector<uint32_t> woff;   // [n_mels] its first weight in wts
-    // The same weights by bin, for the kernel.  A bin lies on the rising side of at most one filter (mu_k at or below
-    // its centre) and on the falling side of at most one; a filter's support is its `rise` rising bins, then its
-    // falling ones
-    std::vector<uint32_t> rise;   // [n_mels]
-    std::vector<double> wr, wf;   // [n_fft / 2 + 1] the bin's weight in its rising / falling filter (0: none)
+    std::vector<double> win; // [wl]
+    RfftPlan fft;            // of n_fft (passes of 2 alone)
+    MelBank bank;            // over the n_fft / 2 + 1 bins
 };
 void fbank_window(uint32_t window, uint32_t wl, double *w);
 // dense [n_mels][n_fft / 2 + 1]
@@ -161,53 +143,5 @@ struct FbankUtt {
     uint64_t n, T, g0;
     uint32_t cls, pad;
 };
-
-// One butterfly of stage s (spans of 2^s) of the in-place decimation-in-time transform of M = 2^log2m points whose
-// input was stored in bit-reversed order: butterfly j of M / 2.  tw: the n_fft = 2 M table
-// (a, b) <- (a + w b, a - w b), w = c + i sn
-JB_FBANK_HD void fbank_bfly(double &ar, double &ai, double &br, double &bi, double c, double sn)
-{
-    const double tr = c * br - sn * bi, ti = c * bi + sn * br;
-    br = ar - tr;
-    bi = ai - ti;
-    ar = ar + tr;
-    ai = ai + ti;
-}
-JB_FBANK_HD void fbank_butterfly(double *re, double *im, const double *tw, uint32_t log2m, uint32_t s, uint32_t j)
-{
-    const uint32_t half = 1u << s, pos = j & (half - 1);
-    const uint32_t i0 = ((j >> s) << (s + 1)) | pos, i1 = i0 + half;
-    const uint32_t k = pos << (log2m - s); // pos n_fft / (2 half): always even
-    fbank_bfly(re[i0], im[i0], re[i1], im[i1], tw[2 * k], tw[2 * k + 1]);
-}
-
-// |X_k|^2 of the real transform from the packed one, Z in (re, im)[0..M): X_k = Fe + w_k Fo with Fe = (Z_k +
-// conj Z_{M-k}) / 2 and Fo = -i (Z_k - conj Z_{M-k}) / 2 (Z_M = Z_0)
-JB_FBANK_HD double fbank_power(double ar, double ai, double zr, double zi, double c, double sn)
-{
-    const double br = zr, bi = -zi;
-    const double fer = 0.5 * (ar + br), fei = 0.5 * (ai + bi);
-    const double fr = 0.5 * (ai - bi), fi = -0.5 * (ar - br);
-    const double xr = fer + (c * fr - sn * fi), xi = fei + (c * fi + sn * fr);
-    return xr * xr + xi * xi;
-}
-// The pair k, M - k (k in 0..M/2) of the M + 1 powers, in place: P_k into re[k], P_{M-k} into re[M - k] (re has a
-// slot M); nothing else of the arrays is read
-// (c0, s0), (c1, s1): entries k and M - k of the n_fft table
-JB_FBANK_HD void fbank_untangle(double *re, double *im, uint32_t M, uint32_t k, double c0, double s0, double c1,
-                                double s1)
-{
-    const uint32_t kk = M - k, kz = kk == M ? 0 : kk;
-    const double ar = re[k], ai = im[k], zr = re[kz], zi = im[kz];
-    const double p0 = fbank_power(ar, ai, zr, zi, c0, s0);
-    const double p1 = fbank_power(zr, zi, ar, ai, c1, s1);
-    re[k] = p0;
-    if (kk != k)
-        re[kk] = p1;
-}
-JB_FBANK_HD void fbank_untangle(double *re, double *im, const double *tw, uint32_t M, uint32_t k)
-{
-    fbank_untangle(re, im, M, k, tw[2 * k], tw[2 * k + 1], tw[2 * (M - k)], tw[2 * (M - k) + 1]);
-}
 
 } // namespace jb

@@ -19,6 +19,7 @@
 //             Every operation of a frame is its own butterfly, pair, bin or filter: its order does not depend on the
 //             lanes that share the frame, on the frame's place in the workgroup or on the batch.
 #include "jb_host.h"
+#include "jb_rfft_dev.h"
 
 #include <algorithm>
 #include <map>
@@ -33,32 +34,16 @@ namespace {
 // bins to weigh ((M + 1) / fl, rounded up); fl is 64 up to M = 512, then M / 8
 constexpr uint32_t kLoadIts = 8, kPairIts = 5, kBinIts = 9;
 
-// Where value i of a frame lies in its LDS arrays: one pad double behind every 32.  The bit-reversed stores of the load
-// (a wave's addresses differ in their high bits only: without the pad all 64 on one bank) and the spans of 4, 16, ... of
-// the early passes then spread over the banks
-__host__ __device__ __forceinline__ constexpr uint32_t fb_at(uint32_t i) { return i + (i >> 5); }
-constexpr uint32_t kFbSlots = 4 * (fb_at(kFbPoints / 4) + 1) + 4; // the frames of a workgroup: 4 x 529, 2 x 1057, 2113
-
-__device__ __forceinline__ uint32_t fbank_find(const FbankUtt *utts, uint32_t n, uint64_t idx)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].g0 <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
+// the frames of a workgroup at the padded places of rfft_at: 4 x 529, 2 x 1057, 2113
+constexpr uint32_t kFbSlots = 4 * (rfft_at(kFbPoints / 4) + 1) + 4;
 
 __global__ __launch_bounds__(kFbLanes) void k_fbank(const FbankClass *__restrict__ classes,
                                                     const FbankUtt *__restrict__ utts, uint32_t n_utts)
 {
-    // (a frame's arrays hold M + 1 values, the untangling leaves P_M in the last one, at the padded places of fb_at)
+    // (a frame's arrays hold M + 1 values, the untangling leaves P_M in the last one, at the padded places of rfft_at)
     __shared__ double s_re[kFbSlots], s_im[kFbSlots];
     __shared__ double s_twc[kFbPoints / 2], s_tws[kFbPoints / 2];
-    const uint32_t u = fbank_find(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x);
     const FbankUtt U = utts[u];
     const FbankClass C = classes[U.cls];
     const uint32_t M = C.n_fft / 2, log2m = C.log2m;
@@ -66,7 +51,7 @@ __global__ __launch_bounds__(kFbLanes) void k_fbank(const FbankClass *__restrict
     const uint32_t f = threadIdx.x / fl, l = threadIdx.x % fl;
     const uint64_t t = (blockIdx.x - U.g0) * (uint64_t)nf + f;
     const bool live = t < U.T; // (a workgroup's last frames may lie behind the unit's: they load, store and sum nothing)
-    double *re = s_re + f * (fb_at(M) + 1), *im = s_im + f * (fb_at(M) + 1);
+    double *re = s_re + f * (rfft_at(M) + 1), *im = s_im + f * (rfft_at(M) + 1);
     const bool center = (C.flags & kFbCenter) != 0;
     const double scale = (C.flags & kFbUnit) ? 0x1p-15 : 1.0;
     const int64_t k0 = (int64_t)(t * C.hop) - (center ? (int64_t)(C.wl / 2) : 0);
@@ -93,42 +78,12 @@ __global__ __launch_bounds__(kFbLanes) void k_fbank(const FbankClass *__restrict
             const uint32_t j = l + it * fl;
             if (j < M) {
                 const uint32_t r = __brev(j) >> (32 - log2m);
-                re[fb_at(r)] = wv[2 * it] * (xv[2 * it] * scale);
-                im[fb_at(r)] = wv[2 * it + 1] * (xv[2 * it + 1] * scale);
+                re[rfft_at(r)] = wv[2 * it] * (xv[2 * it] * scale);
+                im[rfft_at(r)] = wv[2 * it + 1] * (xv[2 * it + 1] * scale);
             }
         }
     }
-    uint32_t s = 0;
-    for (; s + 1 < log2m; s += 2) { // passes s and s + 1
-        __syncthreads();
-        if (live) {
-            const uint32_t h = 1u << s;
-#pragma unroll 2
-            for (uint32_t q = l; q < M / 4; q += fl) {
-                const uint32_t pos = q & (h - 1);
-                const uint32_t i0 = ((q >> s) << (s + 2)) | pos;
-                const uint32_t ia = fb_at(i0), ib = fb_at(i0 + h), ic = fb_at(i0 + 2 * h), id = fb_at(i0 + 3 * h);
-                double ar = re[ia], ai = im[ia], br = re[ib], bi = im[ib];
-                double cr = re[ic], ci = im[ic], dr = re[id], di = im[id];
-                const uint32_t p0 = pos << (log2m - s - 1), p1 = pos << (log2m - s - 2), p2 = (pos + h) << (log2m - s - 2);
-                fbank_bfly(ar, ai, br, bi, s_twc[p0], s_tws[p0]);
-                fbank_bfly(cr, ci, dr, di, s_twc[p0], s_tws[p0]);
-                fbank_bfly(ar, ai, cr, ci, s_twc[p1], s_tws[p1]);
-                fbank_bfly(br, bi, dr, di, s_twc[p2], s_tws[p2]);
-                re[ia] = ar, im[ia] = ai, re[ib] = br, im[ib] = bi;
-                re[ic] = cr, im[ic] = ci, re[id] = dr, im[id] = di;
-            }
-        }
-    }
-    if (s < log2m) { // log2(M) is odd: the last pass alone, spans of M / 2 and twiddles W_M^j
-        __syncthreads();
-        if (live)
-            for (uint32_t j = l; j < M / 2; j += fl) {
-                const uint32_t ia = fb_at(j), ib = fb_at(j + M / 2);
-                fbank_bfly(re[ia], im[ia], re[ib], im[ib], s_twc[j], s_tws[j]);
-            }
-    }
-    __syncthreads();
+    rfft_passes(re, im, s_twc, s_tws, M, log2m, l, fl, live);
     // (the pairs' twiddles, then the bins' weights, loaded the same way: all of a lane's at once)
     if (live) {
         double tw[4 * kPairIts];
@@ -141,12 +96,12 @@ __global__ __launch_bounds__(kFbLanes) void k_fbank(const FbankClass *__restrict
 #pragma unroll
         for (uint32_t it = 0; it < kPairIts; it++) {
             const uint32_t k = l + it * fl;
-            if (k <= M / 2) { // fbank_untangle at the padded places
-                const uint32_t kk = M - k, ik = fb_at(k), iz = fb_at(kk == M ? 0 : kk);
+            if (k <= M / 2) { // rfft_untangle at the padded places
+                const uint32_t kk = M - k, ik = rfft_at(k), iz = rfft_at(kk == M ? 0 : kk);
                 const double ar = re[ik], ai = im[ik], zr = re[iz], zi = im[iz];
-                re[ik] = fbank_power(ar, ai, zr, zi, tw[4 * it], tw[4 * it + 1]);
+                re[ik] = rfft_power(ar, ai, zr, zi, tw[4 * it], tw[4 * it + 1]);
                 if (kk != k)
-                    re[fb_at(kk)] = fbank_power(zr, zi, ar, ai, tw[4 * it + 2], tw[4 * it + 3]);
+                    re[rfft_at(kk)] = rfft_power(zr, zi, ar, ai, tw[4 * it + 2], tw[4 * it + 3]);
             }
         }
     }
@@ -163,9 +118,9 @@ __global__ __launch_bounds__(kFbLanes) void k_fbank(const FbankClass *__restrict
         for (uint32_t it = 0; it < kBinIts; it++) {
             const uint32_t k = l + it * fl;
             if (k <= M) {
-                const double p = re[fb_at(k)];
-                im[fb_at(k)] = wr[it] * p;
-                re[fb_at(k)] = wf[it] * p;
+                const double p = re[rfft_at(k)];
+                im[rfft_at(k)] = wr[it] * p;
+                re[rfft_at(k)] = wf[it] * p;
             }
         }
     }
@@ -175,13 +130,7 @@ __global__ __launch_bounds__(kFbLanes) void k_fbank(const FbankClass *__restrict
     uint8_t *row = U.y + t * C.n_mels * fbank_elem(C.flags);
     for (uint32_t m = l; m < C.n_mels; m += fl) {
         const uint32_t k0m = C.first[m], k1m = k0m + C.rise[m], k2m = k0m + C.count[m];
-        double e = 0.0;
-#pragma unroll 4
-        for (uint32_t k = k0m; k < k1m; k++)
-            e += im[fb_at(k)];
-#pragma unroll 4
-        for (uint32_t k = k1m; k < k2m; k++)
-            e += re[fb_at(k)];
+        const double e = mel_bank_sum(re, im, k0m, k1m, k2m);
         const double v = (C.flags & kFbLinear) ? e : e > C.log_floor ? log(e) : C.ln_floor;
         if (C.flags & kFbF64)
             ((double *)row)[m] = v;
@@ -203,66 +152,23 @@ hipError_t launch_fbank(const FbankClass *classes_dev, const FbankUtt *utts_dev,
     return hipGetLastError();
 }
 
-int FbankClasses::find(const FbankOpts &opts, uint32_t hz, const char *who, uint32_t *cls)
-{
-    for (size_t i = 0; i < key_hz.size(); i++)
-        if (key_hz[i] == hz) {
-            *cls = (uint32_t)i;
-            return JB_OK;
-        }
-    FbankGeom g{};
-    const int rc = fbank_geometry(&opts, hz, who, &g);
-    if (rc)
-        return rc;
-    FbankTables t; // (a class is listed once its tables stand)
-    if (!fbank_tables(g, hz, opts.window, &t)) {
-        set_error(std::string(who) + ": the filterbank at " + std::to_string(hz) + " Hz has no by-bin form");
-        return JB_ERR_INVALID;
-    }
-    *cls = (uint32_t)key_hz.size();
-    key_hz.push_back(hz);
-    geom.push_back(g);
-    tables.push_back(std::move(t));
-    return JB_OK;
-}
-
-size_t FbankClasses::words() const
-{
-    size_t w = 0;
-    for (const FbankTables &t : tables)
-        w += t.win.size() + t.tw.size() + t.wr.size() + t.wf.size() + (3 * t.first.size() + 1) / 2;
-    return w;
-}
-
+template <>
 void FbankClasses::bind(const FbankOpts &opts, const double *dev, std::vector<double> *image,
                         std::vector<FbankClass> *out) const
 {
-    image->clear();
+    TableImage img(dev);
     out->clear();
     for (size_t i = 0; i < tables.size(); i++) {
         const FbankTables &t = tables[i];
         const FbankGeom &g = geom[i];
         FbankClass c{};
-        auto put = [&](const std::vector<double> &v) {
-            const double *at = dev + image->size();
-            image->insert(image->end(), v.begin(), v.end());
-            return at;
-        };
-        c.win = put(t.win);
-        c.tw = put(t.tw);
-        c.wr = put(t.wr);
-        c.wf = put(t.wf);
-        // the three lists of uint32 behind them, in whole doubles
-        const size_t nm = t.first.size();
-        std::vector<double> ints((3 * nm + 1) / 2, 0.0);
-        uint32_t *ip = (uint32_t *)ints.data();
-        memcpy(ip, t.first.data(), 4 * nm);
-        memcpy(ip + nm, t.count.data(), 4 * nm);
-        memcpy(ip + 2 * nm, t.rise.data(), 4 * nm);
-        const uint32_t *di = (const uint32_t *)put(ints);
-        c.first = di;
-        c.count = di + nm;
-        c.rise = di + 2 * nm;
+        c.win = img.put(t.win);
+        c.tw = img.put(t.fft.tw);
+        c.wr = img.put(t.bank.wr);
+        c.wf = img.put(t.bank.wf);
+        c.first = img.put(t.bank.first);
+        c.count = img.put(t.bank.count);
+        c.rise = img.put(t.bank.rise);
         c.wl = g.wl;
         c.hop = g.hop;
         c.n_fft = g.n_fft;
@@ -274,6 +180,7 @@ void FbankClasses::bind(const FbankOpts &opts, const double *dev, std::vector<do
         c.ln_floor = g.ln_floor;
         out->push_back(c);
     }
+    *image = std::move(img.words);
 }
 
 } // namespace jb

@@ -59,20 +59,6 @@ template <uint32_t D> __device__ __forceinline__ void filt_mv_add(cdouble *P, co
     }
 }
 
-// largest u with utts[u].t0 <= idx; utterances without tiles share their successor's prefix
-__device__ __forceinline__ uint32_t filt_find(const FilterUtt *utts, uint32_t n, uint64_t idx)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].t0 <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 // A tile of `len` values out of `src` (src(e): value e of the tile) to gy[0 .. len): the elements in front of gy's
 // first 16-byte boundary one by one, whole aligned 16-byte groups behind them, the last partial group one by one
 template <class T, class Src> __device__ __forceinline__ void filt_store_tile(T *y, uint32_t len, uint32_t tid, Src src)
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(kFiltLanes) void k_filter_tiles(const FilterClass *
     __shared__ double xs[kFiltLanes * Sp]; // lane l's segment at l * Sp: odd strides, no bank conflict
     __shared__ double sc[D * kFiltLanes];  // component i of lane l at i * 256 + l
     const uint32_t tid = threadIdx.x;
-    const FilterUtt U = utts[filt_find(utts, n_utts, blockIdx.x)];
+    const FilterUtt U = utts[find_unit(utts, n_utts, blockIdx.x, &FilterUtt::t0)];
     const uint64_t t = blockIdx.x - U.t0;
     const uint64_t start = t * kFiltTile;
     if (t >= U.ntiles || start >= U.n)
@@ -267,7 +253,7 @@ __global__ __launch_bounds__(64) void k_filter_scan(const FilterClass *__restric
 template <class T>
 __global__ __launch_bounds__(kFiltLanes) void k_filter_copy(const FilterUtt *__restrict__ utts, uint32_t n_utts)
 {
-    const FilterUtt U = utts[filt_find(utts, n_utts, blockIdx.x)];
+    const FilterUtt U = utts[find_unit(utts, n_utts, blockIdx.x, &FilterUtt::t0)];
     const uint64_t t = blockIdx.x - U.t0;
     const uint64_t start = t * kFiltTile;
     if (t >= U.ntiles || start >= U.n)

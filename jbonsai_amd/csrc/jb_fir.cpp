@@ -45,19 +45,10 @@ uint32_t FirClasses::find(const FirSpec &f)
     r.hz = f.hz;
     r.delay = f.delay;
     r.g = fir_geometry(f.n_taps);
+    if (r.g.mode == kFirPartitioned)
+        fir_spectra(r, &r.H, &r.tw);
     resp.push_back(std::move(r));
     return (uint32_t)resp.size() - 1;
-}
-
-size_t FirClasses::words() const
-{
-    size_t w = 0;
-    for (const FirResponse &r : resp) {
-        w += r.taps.size();
-        if (r.g.mode == kFirPartitioned)
-            w += (size_t)(r.g.partitions + 1) * (r.g.n_fft / 2 + 1) * 2;
-    }
-    return w;
 }
 
 namespace {
@@ -102,11 +93,7 @@ void fir_spectra(const FirResponse &r, std::vector<double> *H, std::vector<doubl
         c[k] = cosl(two_pi * k / (long double)n_fft);
         s[k] = sinl(two_pi * k / (long double)n_fft);
     }
-    tw->resize(2 * (size_t)(M + 1));
-    for (uint32_t k = 0; k <= M; k++) {
-        (*tw)[2 * k] = (double)cosl(two_pi * k / (long double)n_fft);
-        (*tw)[2 * k + 1] = (double)-sinl(two_pi * k / (long double)n_fft);
-    }
+    *tw = rfft_twiddles(n_fft);
     H->assign((size_t)P * (M + 1) * 2, 0.0);
     std::vector<long double> re(n_fft), im(n_fft);
     const size_t K = r.taps.size();
@@ -127,16 +114,11 @@ void fir_spectra(const FirResponse &r, std::vector<double> *H, std::vector<doubl
 
 void FirClasses::bind(const double *dev, std::vector<double> *image, std::vector<FirClass> *out) const
 {
-    image->clear();
+    TableImage img(dev);
     out->clear();
     for (const FirResponse &r : resp) {
         FirClass c{};
-        auto put = [&](const std::vector<double> &v) {
-            const double *at = dev + image->size();
-            image->insert(image->end(), v.begin(), v.end());
-            return at;
-        };
-        c.h = put(r.taps);
+        c.h = img.put(r.taps);
         c.K = (uint32_t)r.taps.size();
         c.delay = r.delay;
         c.mode = r.g.mode;
@@ -144,16 +126,15 @@ void FirClasses::bind(const double *dev, std::vector<double> *image, std::vector
         c.partitions = r.g.partitions;
         c.n_fft = r.g.n_fft;
         if (r.g.mode == kFirPartitioned) {
-            std::vector<double> H, tw;
-            fir_spectra(r, &H, &tw);
-            c.H = put(H);
-            c.tw = put(tw);
+            c.H = img.put(r.H);
+            c.tw = img.put(r.tw);
             for (c.log2m = 0; (2u << c.log2m) < r.g.n_fft;)
                 c.log2m++;
             c.lead = fir_lead(r.delay, r.g.block);
         }
         out->push_back(c);
     }
+    *image = std::move(img.words);
 }
 
 } // namespace jb

@@ -4,16 +4,10 @@
 // rule of one sample, stated once for the direct kernel (jb_fir.hip) and for the host rule (jb_fir.cpp); the geometry
 // of a tap count (mode, block, partitions: from K alone); the stage's device tables and work list.
 // Plain C++17; under hipcc the rule compiles for the host and the device alike.
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <vector>
+// Partitioned mode takes the packed real transform of jb_rfft.h.
+#include "jb_rfft.h"
 
-#ifdef __HIPCC__
-#define JB_FIR_HD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
-#else
-#define JB_FIR_HD inline
-#endif
+#include <math.h>
 
 namespace jb {
 
@@ -77,7 +71,7 @@ inline const char *fir_fault(const FirSpec &f, uint32_t hz)
 
 // y[n] of x[0..N) under h[0..K) and the delay d < K: the terms h[k] x[n + d - k] whose index lies in [0, N), in
 // ascending k; the first starts the sum, every later one is fused onto it; none: +0.0.  at(i): sample i of x
-template <class X> JB_FIR_HD double fir_sample(const double *h, uint32_t K, uint32_t d, uint64_t N, uint64_t n, X at)
+template <class X> JB_RFFT_HD double fir_sample(const double *h, uint32_t K, uint32_t d, uint64_t N, uint64_t n, X at)
 {
     const uint64_t top = n + d; // the index of the term k = 0
     const uint64_t klo = top >= N ? top - (N - 1) : 0, khi = top < K - 1 ? top : K - 1;
@@ -102,11 +96,13 @@ inline std::vector<uint8_t> fir_stage_flags(const std::vector<uint8_t> &sections
     return flags;
 }
 
-// One distinct response (taps, delay, rate) on the host, with its geometry
+// One distinct response (taps, delay, rate) on the host, with its geometry and, in partitioned mode, its tables
+// (fir_spectra)
 struct FirResponse {
     std::vector<double> taps;
     uint32_t hz = 0, delay = 0;
     FirGeom g{};
+    std::vector<double> H, tw;
 };
 
 // The device's view of one response.  Direct: h alone.  Partitioned: H[p][k] = (re, im) of bin k <= M of partition
@@ -126,15 +122,5 @@ struct FirUtt {
     uint64_t n, g0, f0, s0;
     uint32_t cls, i16;
 };
-
-// (a, b) <- (a + w b, a - w b), w = c + i sn: the butterfly of jb_fbank.h, operation for operation
-JB_FIR_HD void fir_bfly(double &ar, double &ai, double &br, double &bi, double c, double sn)
-{
-    const double tr = c * br - sn * bi, ti = c * bi + sn * br;
-    br = ar - tr;
-    bi = ai - ti;
-    ar = ar + tr;
-    ai = ai + ti;
-}
 
 } // namespace jb

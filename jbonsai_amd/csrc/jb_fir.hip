@@ -13,9 +13,9 @@
 //   k_fir_spectrum  K > 256, uniform partitioned overlap-save in f64.  Per (utterance, block j): the real transform of
 //                   the n_fft samples that end at the end of block j, shifted by the delay (j from -lead: the delay's
 //                   samples in front of block 0 are lead = ceil(d / Bk) blocks of their own), out-of-range samples
-//                   predicated to zero, packed two to a complex point; k_fbank's pass structure and LDS padding (two
-//                   radix-2 passes to a barrier, re and im apart, a pad double behind every 32); the untangled Bk + 1
-//                   bins go to the spectrum scratch.
+//                   predicated to zero, packed two to a complex point; k_fbank's pass structure and LDS padding
+//                   (rfft_passes: two radix-2 passes to a barrier, re and im apart, a pad double behind every 32); the
+//                   untangled Bk + 1 bins go to the spectrum scratch.
 //   k_fir_mac       Per (utterance, block j): Y = sum over p of X[j - p] H[p], p ascending from 0 to min(P - 1, j + lead),
 //                   every bin's sum in one lane; the untangling inverted, the inverse transform as the forward one of
 //                   the conjugate (1 / M is in H), the last Bk samples kept: f64 in whole 16-byte stores, or the
@@ -23,6 +23,7 @@
 // Blocks and tiles are counted from the utterance's own first sample, and every operation of a block is its own
 // butterfly, pair or bin: a sample's bits depend on its utterance's samples, the taps, the delay and K only.
 #include "jb_host.h"
+#include "jb_rfft_dev.h"
 
 #include <algorithm>
 #include <stdlib.h>
@@ -50,25 +51,9 @@ __device__ __forceinline__ void fir_out(double v, int16_t *o)
     *o = (int16_t)fmt_quant<false>(v, -32768.0, 32767.0, 0, 0);
 }
 
-// Where value i of a block lies in its LDS arrays: one pad double behind every 32 (k_fbank's fb_at)
-__host__ __device__ __forceinline__ constexpr uint32_t fir_at(uint32_t i) { return i + (i >> 5); }
-constexpr uint32_t kFirSlots = fir_at(kFirPoints) + 1;
+constexpr uint32_t kFirSlots = rfft_at(kFirPoints) + 1; // a block at the padded places of rfft_at
 constexpr uint32_t kFirLoadIts = kFirPoints / kFirLanes;              // points a lane loads, at most
 constexpr uint32_t kFirPairIts = (kFirPoints / 2 + kFirLanes) / kFirLanes; // pairs (k, M - k), k <= M / 2, of a lane
-
-// largest u with utts[u].*base <= idx; utterances without workgroups share their successor's prefix
-__device__ __forceinline__ uint32_t fir_find(const FirUtt *utts, uint32_t n, uint64_t idx, uint64_t FirUtt::*base = &FirUtt::g0)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].*base <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
 
 // `len` values out of `src` (src(e): value e) to y[0 .. len): the elements in front of y's first 16-byte boundary one
 // by one, whole aligned 16-byte groups behind them, the last partial group one by one (k_join's and the filter's form)
@@ -121,7 +106,7 @@ __global__ __launch_bounds__(kFirLanes) void k_fir_direct(const FirClass *__rest
     __shared__ double hs[kFirDirectMax];
     __shared__ double ys[fir_pad(kFirTile)];
     const uint32_t tid = threadIdx.x;
-    const FirUtt U = utts[fir_find(utts, n_utts, blockIdx.x)];
+    const FirUtt U = utts[find_unit(utts, n_utts, blockIdx.x)];
     const uint64_t start = (blockIdx.x - U.g0) * (uint64_t)kFirTile;
     if (start >= U.n)
         return;
@@ -170,50 +155,14 @@ __global__ __launch_bounds__(kFirLanes) void k_fir_direct(const FirClass *__rest
     fir_store_utt(U, start, len, tid, [&](uint32_t e) { return ys[fir_pad(e)]; });
 }
 
-// The log2(M) in-place radix-2 passes over points stored in bit-reversed order, two to a barrier and a last single one
-// where log2(M) is odd: k_fbank's passes with the whole workgroup on one block.  Ends behind a barrier
-__device__ __forceinline__ void fir_passes(double *re, double *im, const double *twc, const double *tws, uint32_t M,
-                                           uint32_t log2m, uint32_t l)
-{
-    uint32_t s = 0;
-    for (; s + 1 < log2m; s += 2) { // passes s and s + 1
-        __syncthreads();
-        const uint32_t h = 1u << s;
-#pragma unroll 2
-        for (uint32_t q = l; q < M / 4; q += kFirLanes) {
-            const uint32_t pos = q & (h - 1);
-            const uint32_t i0 = ((q >> s) << (s + 2)) | pos;
-            const uint32_t ia = fir_at(i0), ib = fir_at(i0 + h), ic = fir_at(i0 + 2 * h), id = fir_at(i0 + 3 * h);
-            double ar = re[ia], ai = im[ia], br = re[ib], bi = im[ib];
-            double cr = re[ic], ci = im[ic], dr = re[id], di = im[id];
-            const uint32_t p0 = pos << (log2m - s - 1), p1 = pos << (log2m - s - 2), p2 = (pos + h) << (log2m - s - 2);
-            fir_bfly(ar, ai, br, bi, twc[p0], tws[p0]);
-            fir_bfly(cr, ci, dr, di, twc[p0], tws[p0]);
-            fir_bfly(ar, ai, cr, ci, twc[p1], tws[p1]);
-            fir_bfly(br, bi, dr, di, twc[p2], tws[p2]);
-            re[ia] = ar, im[ia] = ai, re[ib] = br, im[ib] = bi;
-            re[ic] = cr, im[ic] = ci, re[id] = dr, im[id] = di;
-        }
-    }
-    if (s < log2m) { // spans of M / 2 and twiddles W_M^j
-        __syncthreads();
-        for (uint32_t j = l; j < M / 2; j += kFirLanes) {
-            const uint32_t ia = fir_at(j), ib = fir_at(j + M / 2);
-            fir_bfly(re[ia], im[ia], re[ib], im[ib], twc[j], tws[j]);
-        }
-    }
-    __syncthreads();
-}
-
-// X_k of the real transform from the packed one: a = Z_k, z = Z_(M - k) (Z_M = Z_0), w_k = c + i sn
+// X_k of the real transform from the packed one (rfft_bin) as the spectrum scratch holds it
 __device__ __forceinline__ FirD2 fir_untangle(double ar, double ai, double zr, double zi, double c, double sn)
 {
-    const double br = zr, bi = -zi;
-    const double fer = 0.5 * (ar + br), fei = 0.5 * (ai + bi);
-    const double fr = 0.5 * (ai - bi), fi = -0.5 * (ar - br);
+    double xr, xi;
+    rfft_bin(ar, ai, zr, zi, c, sn, &xr, &xi);
     FirD2 x;
-    x[0] = fer + (c * fr - sn * fi);
-    x[1] = fei + (c * fi + sn * fr);
+    x[0] = xr;
+    x[1] = xi;
     return x;
 }
 // The inverse: conj Z_k of the packed transform from a = Y_k and y = Y_(M - k)
@@ -236,7 +185,7 @@ __global__ __launch_bounds__(kFirLanes) void k_fir_spectrum(const FirClass *__re
     __shared__ double s_re[kFirSlots], s_im[kFirSlots];
     __shared__ double s_twc[kFirPoints / 2], s_tws[kFirPoints / 2];
     const uint32_t l = threadIdx.x;
-    const FirUtt U = utts[fir_find(utts, n_utts, blockIdx.x, &FirUtt::f0)];
+    const FirUtt U = utts[find_unit(utts, n_utts, blockIdx.x, &FirUtt::f0)];
     const FirClass C = classes[U.cls];
     const uint32_t M = std::min<uint32_t>(C.n_fft / 2, kFirPoints + 0u), log2m = C.log2m, Bk = M;
     const uint64_t f = blockIdx.x - U.f0; // spectrum f is block j = f - lead
@@ -264,18 +213,18 @@ __global__ __launch_bounds__(kFirLanes) void k_fir_spectrum(const FirClass *__re
             const uint32_t q = l + it * kFirLanes;
             if (q < M) {
                 const uint32_t r = __brev(q) >> (32 - log2m);
-                s_re[fir_at(r)] = xv[2 * it];
-                s_im[fir_at(r)] = xv[2 * it + 1];
+                s_re[rfft_at(r)] = xv[2 * it];
+                s_im[rfft_at(r)] = xv[2 * it + 1];
             }
         }
     }
-    fir_passes(s_re, s_im, s_twc, s_tws, M, log2m, l);
+    rfft_passes(s_re, s_im, s_twc, s_tws, M, log2m, l, kFirLanes, true);
     JB_FIR_GLOBAL FirD2 *X = (JB_FIR_GLOBAL FirD2 *)spec + (U.s0 + f * (uint64_t)(M + 1));
 #pragma unroll
     for (uint32_t it = 0; it < kFirPairIts; it++) {
         const uint32_t k = l + it * kFirLanes;
         if (k <= M / 2) {
-            const uint32_t kk = M - k, ik = fir_at(k), iz = fir_at(kk == M ? 0 : kk);
+            const uint32_t kk = M - k, ik = rfft_at(k), iz = rfft_at(kk == M ? 0 : kk);
             const double ar = s_re[ik], ai = s_im[ik], zr = s_re[iz], zi = s_im[iz];
             X[k] = fir_untangle(ar, ai, zr, zi, C.tw[2 * k], C.tw[2 * k + 1]);
             if (kk != k)
@@ -291,7 +240,7 @@ __global__ __launch_bounds__(kFirLanes) void k_fir_mac(const FirClass *__restric
     __shared__ double s_re[kFirSlots], s_im[kFirSlots];
     __shared__ double s_twc[kFirPoints / 2], s_tws[kFirPoints / 2];
     const uint32_t l = threadIdx.x;
-    const FirUtt U = utts[fir_find(utts, n_utts, blockIdx.x)];
+    const FirUtt U = utts[find_unit(utts, n_utts, blockIdx.x)];
     const FirClass C = classes[U.cls];
     const uint32_t M = std::min<uint32_t>(C.n_fft / 2, kFirPoints + 0u), log2m = C.log2m, Bk = M;
     const uint64_t j = blockIdx.x - U.g0;
@@ -322,21 +271,21 @@ __global__ __launch_bounds__(kFirLanes) void k_fir_mac(const FirClass *__restric
         }
         const FirD2 zk = fir_tangle(ar, ai, br, bi, C.tw[2 * k], C.tw[2 * k + 1]);
         const uint32_t rk = __brev(k) >> (32 - log2m);
-        s_re[fir_at(rk)] = zk[0];
-        s_im[fir_at(rk)] = zk[1];
+        s_re[rfft_at(rk)] = zk[0];
+        s_im[rfft_at(rk)] = zk[1];
         if (kk != k && kk != M) {
             const FirD2 zz = fir_tangle(br, bi, ar, ai, C.tw[2 * kk], C.tw[2 * kk + 1]);
             const uint32_t rz = __brev(kk) >> (32 - log2m);
-            s_re[fir_at(rz)] = zz[0];
-            s_im[fir_at(rz)] = zz[1];
+            s_re[rfft_at(rz)] = zz[0];
+            s_im[rfft_at(rz)] = zz[1];
         }
     }
-    fir_passes(s_re, s_im, s_twc, s_tws, M, log2m, l);
+    rfft_passes(s_re, s_im, s_twc, s_tws, M, log2m, l, kFirLanes, true);
     // z = conj of what the passes left; samples Bk .. 2 Bk of the block's window are points M / 2 .. M
     const uint64_t start = j * (uint64_t)Bk;
     const uint32_t len = (uint32_t)std::min<uint64_t>(Bk, U.n - start);
     fir_store_utt(U, start, len, l, [&](uint32_t e) {
-        const uint32_t q = fir_at(M / 2 + (e >> 1));
+        const uint32_t q = rfft_at(M / 2 + (e >> 1));
         return (e & 1u) ? -s_im[q] : s_re[q];
     });
 }

@@ -31,19 +31,6 @@ constexpr uint32_t fmt_group(uint32_t fmt)
     return fmt == kFmtS16 ? 8 : (fmt == kFmtUlaw || fmt == kFmtAlaw) ? 16 : 4;
 }
 
-__device__ __forceinline__ uint32_t fmt_find(const FormatUtt *utts, uint32_t n, uint64_t idx)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].ft0 <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 template <uint32_t kFmt, bool kDither>
 __global__ __launch_bounds__(kFmtLanes) void k_format(const FormatUtt *__restrict__ utts, uint32_t n_utts,
                                                       uint64_t mseed)
@@ -51,7 +38,7 @@ __global__ __launch_bounds__(kFmtLanes) void k_format(const FormatUtt *__restric
     constexpr uint32_t G = fmt_group(kFmt);
     constexpr uint32_t NB = (uint32_t)format_bytes(kFmt);
     static_assert(kFmtTile % (kFmtLanes * G) == 0 && kFmtTile % 16 == 0, "a tile is whole groups of every lane");
-    const uint32_t u = fmt_find(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x, &FormatUtt::ft0);
     const FormatUtt U = utts[u];
     const uint64_t k0 = (blockIdx.x - U.ft0) * (uint64_t)kFmtTile;
     if (k0 >= U.n)

@@ -288,34 +288,73 @@ hipError_t launch_format(uint32_t format, uint32_t dither, uint64_t seed, const 
 // x f64 or 16-bit samples by i16
 hipError_t launch_adpcm(bool i16, const AdpcmUtt *utts_dev, uint32_t n, uint64_t groups, hipStream_t stream);
 
-// Filterbank features (jb_fbank.hip; the rule, FbankClass and FbankUtt: jb_fbank.h; the host half: jb_fbank.cpp).
-// The distinct geometries of a launch, one per rate: their tables on the host
-struct FbankClasses {
+// The distinct geometries of a launch of the filterbank features or the mel spectrograms, one per rate: their tables
+// on the host.  A stage states its geometry and its tables (rate_geometry, rate_tables) and the body of bind
+template <class Opts, class Geom, class Tables, class Class> struct RateClasses {
     std::vector<uint32_t> key_hz;
-    std::vector<FbankGeom> geom;
-    std::vector<FbankTables> tables;
+    std::vector<Geom> geom;
+    std::vector<Tables> tables;
     // the class of `hz` (made at its first use), or JB_ERR_INVALID naming the field that is out of its limits there
-    int find(const FbankOpts &opts, uint32_t hz, const char *who, uint32_t *cls);
-    size_t words() const; // doubles of the device image of all tables
-    // the image (to be copied to `dev`, words() doubles) and the classes that point into it
-    void bind(const FbankOpts &opts, const double *dev, std::vector<double> *image, std::vector<FbankClass> *out) const;
+    int find(const Opts &opts, uint32_t hz, const char *who, uint32_t *cls)
+    {
+        for (size_t i = 0; i < key_hz.size(); i++)
+            if (key_hz[i] == hz) {
+                *cls = (uint32_t)i;
+                return JB_OK;
+            }
+        Geom g{};
+        const int rc = rate_geometry(&opts, hz, who, &g);
+        if (rc)
+            return rc;
+        Tables t; // (a class is listed once its tables stand)
+        if (!rate_tables(g, hz, opts, &t)) {
+            set_error(std::string(who) + ": the filterbank at " + std::to_string(hz) + " Hz has no by-bin form");
+            return JB_ERR_INVALID;
+        }
+        *cls = (uint32_t)key_hz.size();
+        key_hz.push_back(hz);
+        geom.push_back(g);
+        tables.push_back(std::move(t));
+        return JB_OK;
+    }
+    // the image (to be copied to `dev`) and the classes that point into it
+    void bind(const Opts &opts, const double *dev, std::vector<double> *image, std::vector<Class> *out) const;
+    size_t words() const // doubles of the image: of the one bind makes
+    {
+        std::vector<double> image;
+        std::vector<Class> classes;
+        bind(Opts{}, nullptr, &image, &classes);
+        return image.size();
+    }
 };
+
+// Filterbank features (jb_fbank.hip; the rule, FbankClass and FbankUtt: jb_fbank.h; the host half: jb_fbank.cpp)
+inline int rate_geometry(const FbankOpts *o, uint32_t hz, const char *who, FbankGeom *g)
+{
+    return fbank_geometry(o, hz, who, g);
+}
+inline bool rate_tables(const FbankGeom &g, uint32_t hz, const FbankOpts &o, FbankTables *t)
+{
+    return fbank_tables(g, hz, o.window, t);
+}
+typedef RateClasses<FbankOpts, FbankGeom, FbankTables, FbankClass> FbankClasses;
+template <>
+void FbankClasses::bind(const FbankOpts &opts, const double *dev, std::vector<double> *image,
+                        std::vector<FbankClass> *out) const;
 // utts_dev[0..n) of `groups` workgroups in all
 hipError_t launch_fbank(const FbankClass *classes_dev, const FbankUtt *utts_dev, uint32_t n, uint64_t groups,
                         hipStream_t stream);
 
-// Mel spectrograms (jb_melspec.hip; the rule, MelClass and MelUtt: jb_melspec.h; the host half: jb_melspec.cpp).
-// The distinct geometries of a launch, one per rate: their tables on the host
-struct MelClasses {
-    std::vector<uint32_t> key_hz;
-    std::vector<MelGeom> geom;
-    std::vector<MelTables> tables;
-    // the class of `hz` (made at its first use), or JB_ERR_INVALID naming the field that is out of its limits there
-    int find(const MelOpts &opts, uint32_t hz, const char *who, uint32_t *cls);
-    size_t words() const; // doubles of the device image of all tables
-    // the image (to be copied to `dev`, words() doubles) and the classes that point into it
-    void bind(const MelOpts &opts, const double *dev, std::vector<double> *image, std::vector<MelClass> *out) const;
-};
+// Mel spectrograms (jb_melspec.hip; the rule, MelClass and MelUtt: jb_melspec.h; the host half: jb_melspec.cpp)
+inline int rate_geometry(const MelOpts *o, uint32_t hz, const char *who, MelGeom *g)
+{
+    return mel_geometry(o, hz, who, g);
+}
+inline bool rate_tables(const MelGeom &g, uint32_t hz, const MelOpts &o, MelTables *t) { return mel_tables(g, hz, o, t); }
+typedef RateClasses<MelOpts, MelGeom, MelTables, MelClass> MelClasses;
+template <>
+void MelClasses::bind(const MelOpts &opts, const double *dev, std::vector<double> *image,
+                      std::vector<MelClass> *out) const;
 // utts_dev[0..n) of `groups` workgroups in all; with `ranged` (the options' range above 0) k_melspec_max and
 // k_melspec_finish behind k_melspec: gmax one double per workgroup, umax one per unit (scratch; else unused)
 hipError_t launch_melspec(const MelClass *classes_dev, const MelUtt *utts_dev, uint32_t n, uint64_t groups, bool ranged,
@@ -369,9 +408,15 @@ int fir_check(const jb_fir *f, uint32_t hz, size_t utt, const char *who);
 struct FirClasses {
     std::vector<FirResponse> resp;
     uint32_t find(const FirSpec &f); // the class of an accepted request with taps (made at its first use)
-    size_t words() const;            // doubles of the device image of all tables
-    // the image (to be copied to `dev`, words() doubles) and the classes that point into it
+    // the image (to be copied to `dev`) and the classes that point into it
     void bind(const double *dev, std::vector<double> *image, std::vector<FirClass> *out) const;
+    size_t words() const // doubles of the image: of the one bind makes
+    {
+        std::vector<double> image;
+        std::vector<FirClass> classes;
+        bind(nullptr, &image, &classes);
+        return image.size();
+    }
 };
 // The partitions' spectra ([P][M + 1][2], scaled by 1 / M) and the twiddles ([M + 1][2]) of a partitioned response
 void fir_spectra(const FirResponse &r, std::vector<double> *H, std::vector<double> *tw);
@@ -925,6 +970,11 @@ private:
     int prepare_flac(), select_flac(const RedoScope *scope), launch_flac(bool redo);
     int prepare_format(), select_format(const RedoScope *scope), launch_format(bool redo);
     int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);
+    // The tables of a class cache on the device: their image in a block of its own, then the classes that point into
+    // it at *classes_dev (what_tables, what_classes: their names in a failure's text)
+    template <class Classes, class Opts, class Class>
+    int upload_classes(const Classes &cls, const Opts &opts, const char *what_tables, const char *what_classes,
+                       Class **classes_dev);
     int prepare_fbank(), select_fbank(const RedoScope *scope), launch_fbank(bool redo);
     int prepare_mfcc(), select_mfcc(const RedoScope *scope), launch_mfcc(bool redo);
     int prepare_melspec(), select_melspec(const RedoScope *scope), launch_melspec(bool redo);

@@ -48,20 +48,6 @@ __device__ __forceinline__ void lim_put(double v, int16_t *o)
     *o = (int16_t)fmt_quant<false>(v, -32768.0, 32767.0, 0, 0);
 }
 
-// largest u with utts[u].t0 <= idx; utterances without tiles share their successor's prefix
-__device__ __forceinline__ uint32_t lim_find(const LimiterUtt *utts, uint32_t n, uint64_t idx)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].t0 <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 // A tile of `len` values out of `src` (src(e): value e of the tile) to y[0 .. len): the elements in front of y's first
 // 16-byte boundary one by one, whole aligned 16-byte groups behind them, the last partial group one by one
 template <class T, class Src> __device__ __forceinline__ void lim_store_tile(T *y, uint32_t len, uint32_t tid, Src src)
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(kLimLanes) void k_ln_limit(const LimiterClass *__re
     __shared__ double rs[kLimR + 1]; // b, then r, its windowed minima, m; at last the lanes' partial results
     __shared__ uint32_t cs[kLimLanes];
     const uint32_t tid = threadIdx.x;
-    const LimiterUtt U = utts[lim_find(utts, n_utts, blockIdx.x)];
+    const LimiterUtt U = utts[find_unit(utts, n_utts, blockIdx.x, &LimiterUtt::t0)];
     const uint64_t t = blockIdx.x - U.t0;
     const uint64_t start = t * kLimTile;
     if (start >= U.n || !U.y)

@@ -230,21 +230,6 @@ __device__ __forceinline__ void ln_mv_add(cdouble *P, const double *w, double *v
     }
 }
 
-// largest u with utts[u].lt0 (kApply: at0) <= idx; utterances without tiles share their successor's prefix
-template <bool kApply>
-__device__ __forceinline__ uint32_t ln_find(const LoudnessUtt *utts, uint32_t n, uint64_t idx)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((kApply ? utts[mid].at0 : utts[mid].lt0) <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ void ln_coefs(const LoudnessRate *R, double *c)
 {
     cdouble *b = (cdouble *)R->b, *a = (cdouble *)R->a;
@@ -262,7 +247,7 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_tiles(const LoudnessRate *__res
     __shared__ double sc[kLnLanes * 4];
     __shared__ double red[kLnLanes];
     const uint32_t tid = threadIdx.x;
-    const uint32_t u = ln_find<false>(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x, &LoudnessUtt::lt0);
     const LoudnessUtt U = utts[u];
     const LoudnessRate *R = rates + U.rate;
     const uint32_t H = R->H, S = R->S, G = R->G, tph = R->tph;
@@ -475,7 +460,7 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_true_peak(const LoudnessRate *_
     __shared__ double xs[kLnLanes * kLnMaxS + kTpBefore + kTpAfter]; // slot i: sample start - 5 + i
     __shared__ double red[kLnLanes];
     const uint32_t tid = threadIdx.x;
-    const uint32_t u = ln_find<false>(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x, &LoudnessUtt::lt0);
     const LoudnessUtt U = utts[u];
     if (U.mode != JB_PEAK_TRUE)
         return;
@@ -850,7 +835,7 @@ template <class T>
 __global__ __launch_bounds__(kLnLanes) void k_ln_apply(const LoudnessUtt *__restrict__ utts, uint32_t n_utts,
                                                        const LoudnessResult *__restrict__ res)
 {
-    const uint32_t u = ln_find<true>(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x, &LoudnessUtt::at0);
     const LoudnessUtt U = utts[u];
     const uint64_t k0 = (blockIdx.x - U.at0) * (uint64_t)kLnApplyTile;
     if (k0 >= U.n || !U.y)

@@ -65,30 +65,15 @@ struct HostFrame {
     }
     template <class X> void run(X x, double *y)
     {
-        auto w = [&](uint32_t i) {
-            return i >= g.woff && i < g.woff + g.wl ? t.win[i - g.woff] * (x(i) * 0x1p-15) : 0.0;
-        };
-        for (uint32_t j = 0; j < M; j++) {
-            re[t.rev[j]] = w(2 * j);
-            im[t.rev[j]] = w(2 * j + 1);
-        }
-        const MelSchedule &s = t.sched;
-        for (uint32_t p = 0; p < s.n; p++)
-            for (uint32_t j = 0; j < M / s.r[p]; j++)
-                mel_butterfly(re.data(), im.data(), t.twc.data(), t.tws.data(), M, s.r[p], s.L[p], s.inv[p], j,
-                              [](uint32_t i) { return i; });
-        for (uint32_t k = 0; k <= M / 2; k++)
-            fbank_untangle(re.data(), im.data(), t.tw.data(), M, k);
+        rfft_frame_power(
+            t.fft,
+            [&](uint32_t i) { return i >= g.woff && i < g.woff + g.wl ? t.win[i - g.woff] * (x(i) * 0x1p-15) : 0.0; },
+            re.data(), im.data());
         if (o.flags & kMelMagnitude)
             for (uint32_t k = 0; k <= M; k++)
                 re[k] = sqrt(re[k]);
-        for (uint32_t m = 0; m < g.n_mels; m++) {
-            double e = 0.0;
-            const double *wt = t.wts.data() + t.woff[m];
-            for (uint32_t i = 0; i < t.count[m]; i++)
-                e += wt[i] * re[t.first[m] + i];
-            y[m] = mel_log(e, o.log, g.floor, g.y_floor);
-        }
+        for (uint32_t m = 0; m < g.n_mels; m++)
+            y[m] = mel_log(mel_bank_energy(t.bank, m, re.data()), o.log, g.floor, g.y_floor);
     }
 };
 
@@ -153,61 +138,20 @@ void mel_filterbank(const MelGeom &g, uint32_t hz, uint32_t mel_scale, uint32_t 
 
 bool mel_tables(const MelGeom &g, uint32_t hz, const MelOpts &o, MelTables *t)
 {
-    const uint32_t K = g.n_fft / 2 + 1, M = g.n_fft / 2;
+    const uint32_t K = g.n_fft / 2 + 1;
     t->win.resize(g.wl);
     mel_window(g.wl, t->win.data());
-    const long double two_pi = 2.0L * acosl(-1.0L);
-    t->tw.resize(2 * (size_t)K);
-    for (uint32_t k = 0; k < K; k++) {
-        t->tw[2 * k] = (double)cosl(two_pi * k / (long double)g.n_fft);
-        t->tw[2 * k + 1] = (double)-sinl(two_pi * k / (long double)g.n_fft);
-    }
-    t->twc.resize(M);
-    t->tws.resize(M);
-    for (uint32_t p = 0; p < M; p++) {
-        t->twc[p] = (double)cosl(two_pi * p / (long double)M);
-        t->tws[p] = (double)-sinl(two_pi * p / (long double)M);
-    }
-    t->sched = mel_schedule(M);
-    t->rev.resize(M);
-    for (uint32_t j = 0; j < M; j++)
-        t->rev[j] = mel_digit_reverse(t->sched, j);
+    t->fft = rfft_plan(g.n_fft);
     std::vector<double> W((size_t)g.n_mels * K);
     mel_filterbank(g, hz, o.mel_scale, o.norm, W.data());
-    t->wts.clear();
-    t->first.assign(g.n_mels, 0);
-    t->count.assign(g.n_mels, 0);
-    t->woff.assign(g.n_mels, 0);
-    t->rise.assign(g.n_mels, 0);
-    t->wr.assign(K, 0.0);
-    t->wf.assign(K, 0.0);
     t->wmax = 0.0;
+    for (double w : W)
+        t->wmax = std::max(t->wmax, w);
     // (the centres as mel_filterbank has them: a bin is on a filter's rising side where nu_k is at or below it)
     const std::vector<long double> f = mel_edges(g, o.mel_scale);
-    bool ok = true;
-    for (uint32_t m = 0; m < g.n_mels; m++) {
-        // (the weights rise and fall along nu: the bins above 0 are one run)
-        uint32_t a = 0, b = 0;
-        for (uint32_t k = 0; k < K; k++)
-            if (W[(size_t)m * K + k] > 0.0) {
-                if (a == b)
-                    a = k;
-                b = k + 1;
-                t->wmax = std::max(t->wmax, W[(size_t)m * K + k]);
-            }
-        t->first[m] = a;
-        t->count[m] = b - a;
-        t->woff[m] = (uint32_t)t->wts.size();
-        t->wts.insert(t->wts.end(), W.begin() + (size_t)m * K + a, W.begin() + (size_t)m * K + b);
-        for (uint32_t k = a; k < b; k++) {
-            const bool rising = (long double)k * hz / g.n_fft <= f[m + 1];
-            std::vector<double> &side = rising ? t->wr : t->wf;
-            ok = ok && side[k] == 0.0 && (rising ? t->rise[m] == k - a : true);
-            side[k] = W[(size_t)m * K + k];
-            t->rise[m] += rising;
-        }
-    }
-    return ok;
+    return mel_bank_split(
+        W.data(), g.n_mels, K, [&](uint32_t m, uint32_t k) { return (long double)k * hz / g.n_fft <= f[m + 1]; },
+        &t->bank);
 }
 
 } // namespace jb

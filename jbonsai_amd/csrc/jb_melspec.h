@@ -1,12 +1,9 @@
 #pragma once
 // jb_melspec.h -- mel spectrograms in the librosa / Whisper convention (include/jbonsai_amd.h "Mel spectrograms"): the
-// geometry of a unit, the tables of one (rate, options) pair, the pass schedule and the butterflies of radix 2, 3 and 5
-// of one frame's mixed-radix transform, stated once for the kernel (jb_melspec.hip) and for the host half
-// (jb_melspec.cpp), and the stage's work list.  Plain C++17; under hipcc the rules compile for the host and the device
-// alike.  The radix-2 butterfly and the untangling of the packed transform are jb_fbank.h's (they hold for any even N).
-#include "jb_fbank.h"
-
-#define JB_MEL_HD JB_FBANK_HD
+// geometry of a unit, the tables of one (rate, options) pair, stated once for the kernel (jb_melspec.hip) and for the
+// host half (jb_melspec.cpp), and the stage's work list.  The mixed-radix transform of a frame is jb_rfft.h's, the bank
+// of filters jb_melbank.h's.  Plain C++17; under hipcc the rules compile for the host and the device alike.
+#include "jb_melbank.h"
 
 namespace jb {
 
@@ -31,7 +28,7 @@ constexpr uint32_t kMelMagnitude = 1, kMelDropLast = 2, kMelF64 = 4;   // JB_MEL
 constexpr uint32_t kMelMinFft = 64, kMelMaxFft = 4096, kMelMaxMels = 128;
 constexpr uint32_t kMelLanes = 256;             // threads of a workgroup
 constexpr uint32_t kMelPoints = kMelMaxFft / 2; // complex points of the largest packed transform
-constexpr uint32_t kMelMaxPasses = 11;          // 2048 = 2^11
+constexpr uint32_t kMelMaxPasses = kRfftMaxPasses;
 
 // Lanes that share a frame and frames a workgroup takes, by n_fft alone: a wave up to 1024, two up to 2048, four above
 constexpr uint32_t mel_frame_lanes(uint32_t n_fft) { return n_fft <= 1024 ? 64 : n_fft <= 2048 ? 128 : 256; }
@@ -61,7 +58,7 @@ constexpr uint64_t mel_frames(uint64_t n, uint32_t n_fft, uint32_t hop, uint32_t
 }
 // Sample `idx` of the padded unit (idx may lie outside [0, n)) as an index into the unit, or -1: it reads as 0.
 // Reflection does not repeat the edge sample; with n > n_fft / 2 one reflection reaches every sample a frame asks for
-JB_MEL_HD int64_t mel_sample_at(int64_t idx, uint64_t n, uint32_t pad)
+JB_RFFT_HD int64_t mel_sample_at(int64_t idx, uint64_t n, uint32_t pad)
 {
     if (pad == kMelPadReflect) {
         if (idx < 0)
@@ -153,128 +150,12 @@ inline bool mel_geometry_quiet(const MelOpts &opts, uint32_t hz, MelGeom *g)
 int mel_check_opts(const MelOpts *opts, const char *who);
 int mel_geometry(const MelOpts *opts, uint32_t hz, const char *who, MelGeom *g);
 
-// The passes of the packed transform of M = n_fft / 2 points: the factors 5, then 3, then 2 of M.  Pass s has radix
-// r[s] and span L[s] = r[0] ... r[s - 1]; inv[s] = floor(2^32 / L[s]) + 1 divides a butterfly's index by the span
-// (mel_div: exact for indices below 2^16; L = 1 is spelt out)
-struct MelSchedule {
-    uint32_t n = 0;
-    uint32_t r[kMelMaxPasses] = {}, L[kMelMaxPasses] = {}, inv[kMelMaxPasses] = {};
-};
-inline MelSchedule mel_schedule(uint32_t M)
-{
-    MelSchedule s;
-    uint32_t span = 1;
-    for (uint32_t p : {5u, 3u, 2u})
-        while (M % p == 0 && s.n < kMelMaxPasses) {
-            s.r[s.n] = p;
-            s.L[s.n] = span;
-            s.inv[s.n] = span > 1 ? (uint32_t)(0x100000000ull / span) + 1 : 0;
-            s.n++;
-            span *= p;
-            M /= p;
-        }
-    return s;
-}
-// Where input point j of the transform is stored: its digits in the schedule's radices, reversed
-inline uint32_t mel_digit_reverse(const MelSchedule &s, uint32_t j)
-{
-    uint32_t at = 0;
-    for (uint32_t p = s.n; p-- > 0;) {
-        at += (j % s.r[p]) * s.L[p];
-        j /= s.r[p];
-    }
-    return at;
-}
-JB_MEL_HD uint32_t mel_div(uint32_t j, uint32_t L, uint32_t inv)
-{
-    return L == 1 ? j : (uint32_t)(((uint64_t)j * inv) >> 32);
-}
-
-// The butterflies, decimation in time: the inputs behind the first are multiplied by their twiddles (c + i sn: powers of
-// W_{rL}), then the r-point transform is taken with W_r = e^{-2 pi i / r}; written product by product and sum by sum
-// (no contraction: the translation units are built with it off)
-JB_MEL_HD void mel_twiddle(double &r, double &i, double c, double sn)
-{
-    const double tr = c * r - sn * i, ti = c * i + sn * r;
-    r = tr;
-    i = ti;
-}
-JB_MEL_HD void mel_bfly3(double &ar, double &ai, double &br, double &bi, double &cr, double &ci, double c1, double s1,
-                         double c2, double s2)
-{
-    constexpr double kS3 = 0.86602540378443864676; // sin(2 pi / 3)
-    mel_twiddle(br, bi, c1, s1);
-    mel_twiddle(cr, ci, c2, s2);
-    const double tr = br + cr, ti = bi + ci;
-    const double dr = kS3 * (br - cr), di = kS3 * (bi - ci);
-    const double mr = ar - 0.5 * tr, mi = ai - 0.5 * ti;
-    ar = ar + tr;
-    ai = ai + ti;
-    br = mr + di; // m - i d
-    bi = mi - dr;
-    cr = mr - di; // m + i d
-    ci = mi + dr;
-}
-JB_MEL_HD void mel_bfly5(double &ar, double &ai, double &br, double &bi, double &cr, double &ci, double &dr, double &di,
-                         double &er, double &ei, const double *c, const double *s)
-{
-    constexpr double kC1 = 0.30901699437494742410, kC2 = -0.80901699437494742410; // cos(2 pi / 5), cos(4 pi / 5)
-    constexpr double kS1 = 0.95105651629515357212, kS2 = 0.58778525229247312917;  // sin(2 pi / 5), sin(4 pi / 5)
-    mel_twiddle(br, bi, c[0], s[0]);
-    mel_twiddle(cr, ci, c[1], s[1]);
-    mel_twiddle(dr, di, c[2], s[2]);
-    mel_twiddle(er, ei, c[3], s[3]);
-    const double s1r = br + er, s1i = bi + ei, s2r = cr + dr, s2i = ci + di;
-    const double d1r = br - er, d1i = bi - ei, d2r = cr - dr, d2i = ci - di;
-    const double m1r = (ar + kC1 * s1r) + kC2 * s2r, m1i = (ai + kC1 * s1i) + kC2 * s2i;
-    const double m2r = (ar + kC2 * s1r) + kC1 * s2r, m2i = (ai + kC2 * s1i) + kC1 * s2i;
-    const double n1r = kS1 * d1r + kS2 * d2r, n1i = kS1 * d1i + kS2 * d2i;
-    const double n2r = kS2 * d1r - kS1 * d2r, n2i = kS2 * d1i - kS1 * d2i;
-    ar = (ar + s1r) + s2r;
-    ai = (ai + s1i) + s2i;
-    br = m1r + n1i; // m1 - i n1
-    bi = m1i - n1r;
-    er = m1r - n1i; // m1 + i n1
-    ei = m1i + n1r;
-    cr = m2r + n2i; // m2 - i n2
-    ci = m2i - n2r;
-    dr = m2r - n2i; // m2 + i n2
-    di = m2i + n2r;
-}
-// Butterfly j (of M / r) of a pass of radix r and span L of the in-place transform of M points whose input was stored
-// in digit-reversed order.  twc, tws: cos and -sin of 2 pi p / M, p < M; at(i): where point i lies in re and im
-template <class At>
-JB_MEL_HD void mel_butterfly(double *re, double *im, const double *twc, const double *tws, uint32_t M, uint32_t r,
-                             uint32_t L, uint32_t inv, uint32_t j, At at)
-{
-    const uint32_t blk = mel_div(j, L, inv), pos = j - blk * L;
-    const uint32_t i0 = blk * L * r + pos;
-    const uint32_t p = (M / (L * r)) * pos; // W_{rL}^pos = W_M^p; q p < M for q < r
-    const uint32_t a = at(i0), b = at(i0 + L);
-    if (r == 2) {
-        fbank_bfly(re[a], im[a], re[b], im[b], twc[p], tws[p]);
-    } else if (r == 3) {
-        const uint32_t c = at(i0 + 2 * L);
-        mel_bfly3(re[a], im[a], re[b], im[b], re[c], im[c], twc[p], tws[p], twc[2 * p], tws[2 * p]);
-    } else {
-        const uint32_t c = at(i0 + 2 * L), d = at(i0 + 3 * L), e = at(i0 + 4 * L);
-        const double tc[4] = {twc[p], twc[2 * p], twc[3 * p], twc[4 * p]};
-        const double ts[4] = {tws[p], tws[2 * p], tws[3 * p], tws[4 * p]};
-        mel_bfly5(re[a], im[a], re[b], im[b], re[c], im[c], re[d], im[d], re[e], im[e], tc, ts);
-    }
-}
-
 // The tables of one geometry, built in long double and rounded once
 struct MelTables {
-    std::vector<double> win;      // [wl]
-    std::vector<double> tw;       // [n_fft / 2 + 1][2]: cos, -sin of 2 pi k / n_fft (the untangling)
-    std::vector<double> twc, tws; // [n_fft / 2]: cos, -sin of 2 pi p / (n_fft / 2) (the passes)
-    std::vector<uint32_t> rev;    // [n_fft / 2]: mel_digit_reverse
-    MelSchedule sched;
-    std::vector<double> wts;      // the filters' weights over their supports, filter after filter
-    std::vector<uint32_t> first, count, woff, rise; // [n_mels], as FbankTables has them
-    std::vector<double> wr, wf;   // [n_fft / 2 + 1] the bin's weight in its rising / falling filter (0: none)
-    double wmax = 0.0;
+    std::vector<double> win; // [wl]
+    RfftPlan fft;            // of n_fft
+    MelBank bank;            // over the n_fft / 2 + 1 bins
+    double wmax = 0.0;       // the largest weight
 };
 void mel_window(uint32_t wl, double *w);
 // dense [n_mels][n_fft / 2 + 1]
@@ -283,7 +164,7 @@ void mel_filterbank(const MelGeom &g, uint32_t hz, uint32_t mel_scale, uint32_t 
 bool mel_tables(const MelGeom &g, uint32_t hz, const MelOpts &o, MelTables *t);
 
 // The logarithm of step 7 and the affine step of step 9, one text for both sides
-JB_MEL_HD double mel_log(double e, uint32_t log, double floor, double y_floor)
+JB_RFFT_HD double mel_log(double e, uint32_t log, double floor, double y_floor)
 {
     if (log == kMelLogNone)
         return e;
@@ -291,7 +172,7 @@ JB_MEL_HD double mel_log(double e, uint32_t log, double floor, double y_floor)
         return y_floor;
     return log == kMelLogLn ? ::log(e) : log == kMelLog10 ? ::log10(e) : 10.0 * ::log10(e);
 }
-JB_MEL_HD double mel_affine(double y, double offset, double scale) { return (y + offset) * scale; }
+JB_RFFT_HD double mel_affine(double y, double offset, double scale) { return (y + offset) * scale; }
 
 // The device's view of one geometry's tables
 struct MelClass {

@@ -10,13 +10,13 @@
 //                     map (mel_sample_at), nothing outside the unit or the window is read -- and packed two to a
 //                     complex point, stored at its digit-reversed place (a table: M entries).  The in-place passes of
 //                     the factors 5, 3 and 2 of M follow, one to a barrier; a lane takes butterflies l, l + fl, ... of
-//                     the pass's M / r and holds one butterfly's r points in registers (mel_butterfly, the host's
+//                     the pass's M / r and holds one butterfly's r points in registers (rfft_butterfly, the host's
 //                     text); no two passes are fused.  Each lane then untangles pairs (k, M - k) into |X_k|^2 in place
-//                     (fbank_power; the square root under JB_MEL_MAGNITUDE), every bin is multiplied by its weight in
+//                     (rfft_power; the square root under JB_MEL_MAGNITUDE), every bin is multiplied by its weight in
 //                     its rising and in its falling filter, and one lane per filter adds its products in ascending
 //                     order, takes the logarithm and, without a range, the affine step and writes the element.  The
 //                     spectrum never leaves LDS.
-//                     LDS places: one pad double behind every 32 (mel_at, as k_fbank).  The passes of 5 and 3 come
+//                     LDS places: one pad double behind every 32 (rfft_at, as k_fbank).  The passes of 5 and 3 come
 //                     first, where the span is odd: a half-wave's reads of one operand step by r doubles (pass 0) or
 //                     by one double with a jump of (r - 1) L at a block's end: conflict-free but for those jumps.  The
 //                     passes of 2 that follow have spans of a multiple of the odd part: consecutive lanes read
@@ -30,6 +30,7 @@
 //   k_melspec_finish  the grid of k_melspec again: each workgroup streams its frames' elements through the clamp, the
 //                     affine step and the element conversion.
 #include "jb_host.h"
+#include "jb_rfft_dev.h"
 
 #include <algorithm>
 #include <stdlib.h>
@@ -39,32 +40,19 @@ namespace jb {
 
 namespace {
 
-__host__ __device__ __forceinline__ constexpr uint32_t mel_at(uint32_t i) { return i + (i >> 5); }
-// the frames of a workgroup: 4 x (mel_at(512) + 1), 2 x (mel_at(1024) + 1) or mel_at(2048) + 1 slots
-constexpr uint32_t kMelSlots = 4 * (mel_at(kMelPoints / 4) + 1) + 4;
-
-__device__ __forceinline__ uint32_t mel_find(const MelUtt *utts, uint32_t n, uint64_t idx)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].g0 <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
+// the frames of a workgroup at the padded places of rfft_at: 4 x (rfft_at(512) + 1), 2 x (rfft_at(1024) + 1) or
+// rfft_at(2048) + 1 slots
+constexpr uint32_t kMelSlots = 4 * (rfft_at(kMelPoints / 4) + 1) + 4;
 
 __global__ __launch_bounds__(kMelLanes) void k_melspec(const MelClass *__restrict__ classes,
                                                        const MelUtt *__restrict__ utts, uint32_t n_utts,
                                                        double *__restrict__ gmax)
 {
-    // (a frame's arrays hold M + 1 values, the untangling leaves S_M in the last one, at the padded places of mel_at)
+    // (a frame's arrays hold M + 1 values, the untangling leaves S_M in the last one, at the padded places of rfft_at)
     __shared__ double s_re[kMelSlots], s_im[kMelSlots];
     __shared__ double s_twc[kMelPoints], s_tws[kMelPoints];
     __shared__ double s_max[kMelLanes];
-    const uint32_t u = mel_find(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x);
     const MelUtt U = utts[u];
     const MelClass &C = classes[U.cls];
     const uint32_t N = C.n_fft, M = N / 2;
@@ -72,7 +60,7 @@ __global__ __launch_bounds__(kMelLanes) void k_melspec(const MelClass *__restric
     const uint32_t f = threadIdx.x / fl, l = threadIdx.x % fl;
     const uint64_t t = (blockIdx.x - U.g0) * (uint64_t)nf + f;
     const bool live = t < U.T; // (a workgroup's last frames may lie behind the unit's: they load, store and sum nothing)
-    double *re = s_re + f * (mel_at(M) + 1), *im = s_im + f * (mel_at(M) + 1);
+    double *re = s_re + f * (rfft_at(M) + 1), *im = s_im + f * (rfft_at(M) + 1);
     const uint32_t pad = C.pad, wl = C.wl, woff = C.woff;
     const int64_t k0 = (int64_t)(t * C.hop) - (pad == kMelPadNone ? 0 : (int64_t)M);
     for (uint32_t p = threadIdx.x; p < M; p += kMelLanes) {
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(kMelLanes) void k_melspec(const MelClass *__restric
                 const bool in = i >= woff && i < woff + wl && k >= 0;
                 v[h] = in ? C.win[i - woff] * (U.x[k] * 0x1p-15) : 0.0;
             }
-            const uint32_t r = mel_at(C.rev[j]);
+            const uint32_t r = rfft_at(C.rev[j]);
             re[r] = v[0];
             im[r] = v[1];
         }
@@ -99,28 +87,28 @@ __global__ __launch_bounds__(kMelLanes) void k_melspec(const MelClass *__restric
         const uint32_t r = C.r[s], L = C.L[s], inv = C.inv[s];
         if (live)
             for (uint32_t j = l; j < M / r; j += fl)
-                mel_butterfly(re, im, s_twc, s_tws, M, r, L, inv, j, [](uint32_t i) { return mel_at(i); });
+                rfft_butterfly(re, im, s_twc, s_tws, M, r, L, inv, j, [](uint32_t i) { return rfft_at(i); });
     }
     __syncthreads();
     const bool magnitude = (C.flags & kMelMagnitude) != 0;
     if (live)
-        for (uint32_t k = l; k <= M / 2; k += fl) { // fbank_untangle at the padded places
-            const uint32_t kk = M - k, ik = mel_at(k), iz = mel_at(kk == M ? 0 : kk);
+        for (uint32_t k = l; k <= M / 2; k += fl) { // rfft_untangle at the padded places
+            const uint32_t kk = M - k, ik = rfft_at(k), iz = rfft_at(kk == M ? 0 : kk);
             const double ar = re[ik], ai = im[ik], zr = re[iz], zi = im[iz];
-            const double p0 = fbank_power(ar, ai, zr, zi, C.tw[2 * k], C.tw[2 * k + 1]);
+            const double p0 = rfft_power(ar, ai, zr, zi, C.tw[2 * k], C.tw[2 * k + 1]);
             re[ik] = magnitude ? sqrt(p0) : p0;
             if (kk != k) {
-                const double p1 = fbank_power(zr, zi, ar, ai, C.tw[2 * kk], C.tw[2 * kk + 1]);
-                re[mel_at(kk)] = magnitude ? sqrt(p1) : p1;
+                const double p1 = rfft_power(zr, zi, ar, ai, C.tw[2 * kk], C.tw[2 * kk + 1]);
+                re[rfft_at(kk)] = magnitude ? sqrt(p1) : p1;
             }
         }
     __syncthreads();
     // every bin's two products: rising into im, falling in place
     if (live)
         for (uint32_t k = l; k <= M; k += fl) {
-            const double p = re[mel_at(k)];
-            im[mel_at(k)] = C.wr[k] * p;
-            re[mel_at(k)] = C.wf[k] * p;
+            const double p = re[rfft_at(k)];
+            im[rfft_at(k)] = C.wr[k] * p;
+            re[rfft_at(k)] = C.wf[k] * p;
         }
     __syncthreads();
     const bool ranged = C.range > 0.0;
@@ -129,13 +117,7 @@ __global__ __launch_bounds__(kMelLanes) void k_melspec(const MelClass *__restric
         const uint64_t row = t * C.n_mels;
         for (uint32_t m = l; m < C.n_mels; m += fl) {
             const uint32_t k0m = C.first[m], k1m = k0m + C.rise[m], k2m = k0m + C.count[m];
-            double e = 0.0;
-#pragma unroll 4
-            for (uint32_t k = k0m; k < k1m; k++)
-                e += im[mel_at(k)];
-#pragma unroll 4
-            for (uint32_t k = k1m; k < k2m; k++)
-                e += re[mel_at(k)];
+            const double e = mel_bank_sum(re, im, k0m, k1m, k2m);
             const double y = mel_log(e, C.log, C.floor, C.y_floor);
             if (ranged) {
                 U.s[row + m] = y;
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(kMelLanes) void k_melspec_finish(const MelClass *__
                                                               const MelUtt *__restrict__ utts, uint32_t n_utts,
                                                               const double *__restrict__ umax)
 {
-    const uint32_t u = mel_find(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x);
     const MelUtt U = utts[u];
     const MelClass &C = classes[U.cls];
     const uint32_t nf = mel_wg_frames(C.n_fft);
@@ -231,71 +213,26 @@ hipError_t launch_melspec(const MelClass *classes_dev, const MelUtt *utts_dev, u
     return hipGetLastError();
 }
 
-int MelClasses::find(const MelOpts &opts, uint32_t hz, const char *who, uint32_t *cls)
-{
-    for (size_t i = 0; i < key_hz.size(); i++)
-        if (key_hz[i] == hz) {
-            *cls = (uint32_t)i;
-            return JB_OK;
-        }
-    MelGeom g{};
-    const int rc = mel_geometry(&opts, hz, who, &g);
-    if (rc)
-        return rc;
-    MelTables t; // (a class is listed once its tables stand)
-    if (!mel_tables(g, hz, opts, &t)) {
-        set_error(std::string(who) + ": the filterbank at " + std::to_string(hz) + " Hz has no by-bin form");
-        return JB_ERR_INVALID;
-    }
-    *cls = (uint32_t)key_hz.size();
-    key_hz.push_back(hz);
-    geom.push_back(g);
-    tables.push_back(std::move(t));
-    return JB_OK;
-}
-
-size_t MelClasses::words() const
-{
-    size_t w = 0;
-    for (const MelTables &t : tables)
-        w += t.win.size() + t.tw.size() + t.twc.size() + t.tws.size() + t.wr.size() + t.wf.size() +
-             (t.rev.size() + 3 * t.first.size() + 1) / 2;
-    return w;
-}
-
+template <>
 void MelClasses::bind(const MelOpts &opts, const double *dev, std::vector<double> *image,
                       std::vector<MelClass> *out) const
 {
-    image->clear();
+    TableImage img(dev);
     out->clear();
     for (size_t i = 0; i < tables.size(); i++) {
         const MelTables &t = tables[i];
         const MelGeom &g = geom[i];
         MelClass c{};
-        auto put = [&](const std::vector<double> &v) {
-            const double *at = dev + image->size();
-            image->insert(image->end(), v.begin(), v.end());
-            return at;
-        };
-        c.win = put(t.win);
-        c.tw = put(t.tw);
-        c.twc = put(t.twc);
-        c.tws = put(t.tws);
-        c.wr = put(t.wr);
-        c.wf = put(t.wf);
-        // the four lists of uint32 behind them, in whole doubles
-        const size_t nm = t.first.size(), nr = t.rev.size();
-        std::vector<double> ints((nr + 3 * nm + 1) / 2, 0.0);
-        uint32_t *ip = (uint32_t *)ints.data();
-        memcpy(ip, t.rev.data(), 4 * nr);
-        memcpy(ip + nr, t.first.data(), 4 * nm);
-        memcpy(ip + nr + nm, t.count.data(), 4 * nm);
-        memcpy(ip + nr + 2 * nm, t.rise.data(), 4 * nm);
-        const uint32_t *di = (const uint32_t *)put(ints);
-        c.rev = di;
-        c.first = di + nr;
-        c.count = di + nr + nm;
-        c.rise = di + nr + 2 * nm;
+        c.win = img.put(t.win);
+        c.tw = img.put(t.fft.tw);
+        c.twc = img.put(t.fft.twc);
+        c.tws = img.put(t.fft.tws);
+        c.wr = img.put(t.bank.wr);
+        c.wf = img.put(t.bank.wf);
+        c.rev = img.put(t.fft.rev);
+        c.first = img.put(t.bank.first);
+        c.count = img.put(t.bank.count);
+        c.rise = img.put(t.bank.rise);
         c.n_fft = g.n_fft;
         c.wl = g.wl;
         c.woff = g.woff;
@@ -304,11 +241,11 @@ void MelClasses::bind(const MelOpts &opts, const double *dev, std::vector<double
         c.flags = opts.flags;
         c.pad = opts.pad;
         c.log = opts.log;
-        c.n_pass = t.sched.n;
-        for (uint32_t s = 0; s < t.sched.n; s++) {
-            c.r[s] = t.sched.r[s];
-            c.L[s] = t.sched.L[s];
-            c.inv[s] = t.sched.inv[s];
+        c.n_pass = t.fft.sched.n;
+        for (uint32_t s = 0; s < t.fft.sched.n; s++) {
+            c.r[s] = t.fft.sched.r[s];
+            c.L[s] = t.fft.sched.L[s];
+            c.inv[s] = t.fft.sched.inv[s];
         }
         c.floor = g.floor;
         c.y_floor = g.y_floor;
@@ -317,6 +254,7 @@ void MelClasses::bind(const MelOpts &opts, const double *dev, std::vector<double
         c.scale = g.scale;
         out->push_back(c);
     }
+    *image = std::move(img.words);
 }
 
 } // namespace jb

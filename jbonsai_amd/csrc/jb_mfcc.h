@@ -128,7 +128,7 @@ struct MfccUtt {
 // ---- the rule, operation for operation (every product and sum on its own: the build has -ffp-contract=off) ----
 
 // c[t][i]: the cepstrum i of one frame.  Lrow: the frame's n_mels logarithms; Dcol: D[i][0], stride ds to D[i][1]
-JB_FBANK_HD double mfcc_cep(const double *Lrow, const double *Dcol, uint32_t ds, uint32_t n_mels, double lift)
+JB_RFFT_HD double mfcc_cep(const double *Lrow, const double *Dcol, uint32_t ds, uint32_t n_mels, double lift)
 {
     double acc = 0.0;
     for (uint32_t m = 0; m < n_mels; m++)
@@ -136,19 +136,19 @@ JB_FBANK_HD double mfcc_cep(const double *Lrow, const double *Dcol, uint32_t ds,
     return lift * acc;
 }
 // One value of the statistics' passes: c (the mean's pass), or (c - mu)^2 (the variance's)
-JB_FBANK_HD double mfcc_stat_term(double c, double mu, bool var)
+JB_RFFT_HD double mfcc_stat_term(double c, double mu, bool var)
 {
     const double dv = c - mu;
     return var ? dv * dv : c;
 }
 // The normalised static
-JB_FBANK_HD double mfcc_norm(double c, double mu, double sd, uint32_t cmvn)
+JB_RFFT_HD double mfcc_norm(double c, double mu, double sd, uint32_t cmvn)
 {
     return cmvn == kMfCmvnNone ? c : cmvn == kMfCmvnMean ? c - mu : (c - mu) / sd;
 }
-JB_FBANK_HD double mfcc_sd(double var, double floor) { return sqrt(var > floor ? var : floor); }
+JB_RFFT_HD double mfcc_sd(double var, double floor) { return sqrt(var > floor ? var : floor); }
 // out_q of one element: v(j) is c'[clamp(t + j)][i] for j in -qN..qN; s: s_q[-qN..qN]
-template <class V> JB_FBANK_HD double mfcc_delta(const double *s, int32_t qN, V v)
+template <class V> JB_RFFT_HD double mfcc_delta(const double *s, int32_t qN, V v)
 {
     double acc = 0.0;
     for (int32_t j = -qN; j <= qN; j++)

@@ -30,24 +30,10 @@ constexpr uint32_t kMfRowMax = kFbMaxMels | 1u;                     // an L row 
 constexpr uint32_t kMfHaloMax = kMfMaxOrder * kMfMaxWindow;         // frames on each side of a k_delta tile
 constexpr uint32_t kMfStage = (kMfTile + 2 * kMfHaloMax) * kMfCols; // doubles of a k_delta tile
 
-// the unit of item idx of a list numbered by `key` (g0 or b0)
-template <uint64_t MfccUtt::*key> __device__ __forceinline__ uint32_t mfcc_find(const MfccUtt *utts, uint32_t n, uint64_t idx)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].*key <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kMfLanes) void k_ceps(MfccParams P, const MfccUtt *__restrict__ utts, uint32_t n_utts)
 {
     __shared__ double s_L[kMfTile * kMfRowMax];
-    const uint32_t u = mfcc_find<&MfccUtt::g0>(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x);
     const MfccUtt U = utts[u];
     const uint64_t t0 = (blockIdx.x - U.g0) * (uint64_t)kMfTile;
     if (t0 >= U.T) // (not reached: a unit's tiles cover its frames)
@@ -73,7 +59,7 @@ __global__ __launch_bounds__(kMfLanes) void k_mfcc_block(MfccParams P, const Mfc
         return;
     const uint64_t gb = item / P.d;
     const uint32_t i = (uint32_t)(item % P.d);
-    const uint32_t u = mfcc_find<&MfccUtt::b0>(utts, n_utts, gb);
+    const uint32_t u = find_unit(utts, n_utts, gb, &MfccUtt::b0);
     const MfccUtt U = utts[u];
     const uint64_t blk = gb - U.b0, t0 = blk * kMfBlock;
     if (t0 >= U.T)
@@ -110,7 +96,7 @@ __global__ __launch_bounds__(kMfLanes) void k_mfcc_fold(MfccParams P, const Mfcc
 __global__ __launch_bounds__(kMfLanes) void k_delta(MfccParams P, const MfccUtt *__restrict__ utts, uint32_t n_utts)
 {
     __shared__ double s_c[kMfStage];
-    const uint32_t u = mfcc_find<&MfccUtt::g0>(utts, n_utts, blockIdx.x);
+    const uint32_t u = find_unit(utts, n_utts, blockIdx.x);
     const MfccUtt U = utts[u];
     const uint64_t t0 = (blockIdx.x - U.g0) * (uint64_t)kMfTile;
     if (t0 >= U.T)

@@ -51,25 +51,11 @@ __device__ __forceinline__ void noise_out(double v, int16_t *o)
     *o = (int16_t)fmt_quant<false>(v, -32768.0, 32767.0, 0, 0);
 }
 
-// largest u with utts[u].*base <= idx; utterances without workgroups share their successor's prefix
-__device__ __forceinline__ uint32_t noise_find(const NoiseUtt *utts, uint32_t n, uint64_t idx, uint64_t NoiseUtt::*base)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (utts[mid].*base <= idx)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kNoiseLanes) void k_noise_sums(const NoiseUtt *__restrict__ utts, uint32_t n_utts,
                                                             double *__restrict__ sums)
 {
     __shared__ double s_x[kNoiseLanes], s_w[kNoiseLanes];
-    const NoiseUtt U = utts[noise_find(utts, n_utts, blockIdx.x, &NoiseUtt::t0)];
+    const NoiseUtt U = utts[find_unit(utts, n_utts, blockIdx.x, &NoiseUtt::t0)];
     const uint64_t i = blockIdx.x - U.t0;
     if (i * kNoiseTile >= U.n)
         return;
@@ -249,7 +235,7 @@ template <class T> __device__ __forceinline__ void noise_apply_tile(const NoiseU
 __global__ __launch_bounds__(kNoiseLanes) void k_noise_apply(const NoiseUtt *utts, uint32_t n_utts,
                                                              const NoiseRecord *rec)
 {
-    const NoiseUtt U = utts[noise_find(utts, n_utts, blockIdx.x, &NoiseUtt::a0)];
+    const NoiseUtt U = utts[find_unit(utts, n_utts, blockIdx.x, &NoiseUtt::a0)];
     const uint64_t k0 = (blockIdx.x - U.a0) * (uint64_t)kNoiseApplyTile;
     if (k0 >= U.n)
         return;

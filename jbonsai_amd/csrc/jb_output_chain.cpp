@@ -1490,6 +1490,22 @@ int OutputChain::launch_adpcm(bool redo)
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_adpcm(redo)" : "k_adpcm");
 }
 
+template <class Classes, class Opts, class Class>
+int OutputChain::upload_classes(const Classes &cls, const Opts &opts, const char *what_tables, const char *what_classes,
+                                Class **classes_dev)
+{
+    double *tables = nullptr;
+    int rc = b.dalloc(&tables, cls.words(), false);
+    if (rc)
+        return rc;
+    std::vector<double> image;
+    std::vector<Class> classes;
+    cls.bind(opts, tables, &image, &classes);
+    if ((rc = upload_list(tables, image, what_tables)) || (rc = b.dalloc(classes_dev, classes.size(), false)))
+        return rc;
+    return upload_list(*classes_dev, classes, what_classes);
+}
+
 // ---- the filterbank features beside them, of the same final f64.  The unit list: the final PCM of the plan in, each
 // unit's frames at their 16-byte aligned place out; the tables of every distinct rate in one block
 int OutputChain::prepare_fbank()
@@ -1518,14 +1534,8 @@ int OutputChain::prepare_fbank()
         fb.ngroups[u] = (w.T + per - 1) / per;
         fb.groups += fb.ngroups[u];
     }
-    double *tables = nullptr;
-    if ((rc = b.dalloc(&tables, cls.words(), false)))
-        return rc;
-    std::vector<double> image;
-    std::vector<FbankClass> classes;
-    cls.bind(fb_p, tables, &image, &classes);
-    if ((rc = upload_list(tables, image, "fbank tables")) || (rc = b.dalloc(&fb.classes_dev, classes.size(), false)) ||
-        (rc = upload_list(fb.classes_dev, classes, "fbank classes")) || (rc = fb.utts.alloc(b, U, U)))
+    if ((rc = upload_classes(cls, fb_p, "fbank tables", "fbank classes", &fb.classes_dev)) ||
+        (rc = fb.utts.alloc(b, U, U)))
         return rc;
     return fb.utts.upload("fbank work list");
 }
@@ -1600,8 +1610,8 @@ int OutputChain::prepare_mfcc()
         mf.blocks += mf.nblocks[u];
         frames += pl.T;
     }
-    double *tables = nullptr, *statics = nullptr, *bs = nullptr, *stat = nullptr, *dct = nullptr, *lift = nullptr;
-    if ((rc = b.dalloc(&tables, cls.words(), false)) || (rc = b.dalloc(&bs, mf.blocks * d, false)) ||
+    double *statics = nullptr, *bs = nullptr, *stat = nullptr, *dct = nullptr, *lift = nullptr;
+    if ((rc = b.dalloc(&bs, mf.blocks * d, false)) ||
         (rc = b.dalloc(&stat, 2 * U * d, false)) || (rc = b.dalloc(&dct, tab.Dt.size(), false)) ||
         (rc = b.dalloc(&lift, tab.lift.size(), false)) ||
         (mf_p.n_ceps && (rc = b.dalloc(&statics, frames * d, false))))
@@ -1616,12 +1626,9 @@ int OutputChain::prepare_mfcc()
     }
     mf.P.Dt = dct;
     mf.P.lift = lift;
-    std::vector<double> image;
-    std::vector<FbankClass> classes;
-    cls.bind(fo, tables, &image, &classes);
-    if ((rc = upload_list(tables, image, "mfcc filterbank tables")) || (rc = upload_list(dct, tab.Dt, "mfcc DCT")) ||
-        (rc = upload_list(lift, tab.lift, "mfcc lifter")) || (rc = b.dalloc(&mf.classes_dev, classes.size(), false)) ||
-        (rc = upload_list(mf.classes_dev, classes, "mfcc filterbank classes")) || (rc = mf.futts.alloc(b, U, U)) ||
+    if ((rc = upload_classes(cls, fo, "mfcc filterbank tables", "mfcc filterbank classes", &mf.classes_dev)) ||
+        (rc = upload_list(dct, tab.Dt, "mfcc DCT")) || (rc = upload_list(lift, tab.lift, "mfcc lifter")) ||
+        (rc = mf.futts.alloc(b, U, U)) ||
         (rc = mf.utts.alloc(b, U, U)) || (rc = mf.futts.upload("mfcc filterbank work list")))
         return rc;
     return mf.utts.upload("mfcc work list");
@@ -1689,15 +1696,9 @@ int OutputChain::prepare_melspec()
         ml.ngroups[u] = (w.T + per - 1) / per;
         ml.groups += ml.ngroups[u];
     }
-    double *tables = nullptr;
-    if ((rc = b.dalloc(&tables, cls.words(), false)) ||
-        (ranged && ((rc = b.dalloc(&ml.gmax, ml.groups, false)) || (rc = b.dalloc(&ml.umax, U, false)))))
-        return rc;
-    std::vector<double> image;
-    std::vector<MelClass> classes;
-    cls.bind(ml_p, tables, &image, &classes);
-    if ((rc = upload_list(tables, image, "melspec tables")) || (rc = b.dalloc(&ml.classes_dev, classes.size(), false)) ||
-        (rc = upload_list(ml.classes_dev, classes, "melspec classes")) || (rc = ml.utts.alloc(b, U, U)))
+    if ((ranged && ((rc = b.dalloc(&ml.gmax, ml.groups, false)) || (rc = b.dalloc(&ml.umax, U, false)))) ||
+        (rc = upload_classes(cls, ml_p, "melspec tables", "melspec classes", &ml.classes_dev)) ||
+        (rc = ml.utts.alloc(b, U, U)))
         return rc;
     return ml.utts.upload("melspec work list");
 }

@@ -52,15 +52,14 @@ def close_to_host(got, x, hz, o):
 GEOMETRIES = list(R.SHAPES)
 
 
-@pytest.mark.parametrize("hz,n_mels,n_fft", GEOMETRIES)
-@pytest.mark.parametrize("center", [False, True])
-def test_seam_over_workgroup_boundaries_and_odd_offsets(eng, hz, n_mels, n_fft, center):
+def seam_boundaries(hz, n_mels, n_fft, center, win_ms=25, hop_ms=10):
     """One call of many short inputs: T = 0, 1 and one less than, equal to and one more than a multiple of the frames a
     workgroup takes; odd sample counts, so that the inputs start on odd offsets of the packed slab; every frame of
     every input (the first and the last among them) against the host form, and against the same input run alone."""
-    wl, hop, nf = R.geometry(hz, n_fft=n_fft)
+    wl, hop, nf = R.geometry(hz, 1000 * win_ms, 1000 * hop_ms, n_fft)
     per = 4 if nf <= 1024 else 2 if nf == 2048 else 1
-    o = J.fbank(n_mels=n_mels, n_fft=n_fft, center=center, linear=True, f64=True, window="hamming")
+    o = J.fbank(win_ms=win_ms, hop_ms=hop_ms, n_mels=n_mels, n_fft=n_fft, center=center, linear=True, f64=True,
+                window="hamming")
 
     def length(T):  # an odd count of samples that gives T frames
         if center:
@@ -82,6 +81,19 @@ def test_seam_over_workgroup_boundaries_and_odd_offsets(eng, hz, n_mels, n_fft, 
     # deterministic: the same input alone and among the others, as the 5th of 9
     assert np.array_equal(J.fbank_pcm(xs[4], hz, o), got[4])
     assert np.array_equal(J.fbank_pcm([xs[4]], hz, o)[0], got[4])
+
+
+@pytest.mark.parametrize("hz,n_mels,n_fft", GEOMETRIES)
+@pytest.mark.parametrize("center", [False, True])
+def test_seam_over_workgroup_boundaries_and_odd_offsets(eng, hz, n_mels, n_fft, center):
+    seam_boundaries(hz, n_mels, n_fft, center)
+
+
+# The smallest transforms: fewer groups of four points (M / 4 = 8, 16) than the 64 lanes of a frame, log2(M) 5 and 6
+@pytest.mark.parametrize("n_fft,win_ms,hop_ms", [(64, 8, 4), (128, 16, 8)])
+@pytest.mark.parametrize("center", [False, True])
+def test_seam_over_workgroup_boundaries_at_the_smallest_transforms(eng, n_fft, win_ms, hop_ms, center):
+    seam_boundaries(8000, 10, n_fft, center, win_ms, hop_ms)
 
 
 def test_seam_rates_in_one_call_and_the_f32_rows(eng):

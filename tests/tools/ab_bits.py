@@ -5,10 +5,13 @@ LDS-staged band solve, split excitation: the kernels of BASELINE config 2), f64 
 stages behind the vocoder: all eight rows of the output routing table (f64 / 16-bit sink x output
 rate x loudness target; FLAC on the 16-bit rows) on three ragged utterances, with the default geometry and with the
 redo-heavy one of the redo tests, and the entries on caller-held PCM on seeded input: three on long inputs, then
-every one of their ten bodies on utterances of 0, 1, 1,025 and 5,000 samples.
+every one of their bodies on utterances of 0, 1, 1,025 and 5,000 samples -- the spectral stages (filterbank, cepstra,
+mel spectrogram) at every transform size class and both element types, the convolution in direct mode and at both
+partitioned transform sizes, the noise stage -- and the host halves of the spectral stages, which need no device.
 
     python tests/tools/ab_bits.py               every hash (what tools/ab_bits.sh compares between two libraries)
     python tests/tools/ab_bits.py --seams       the hashes of the entries on caller-held PCM alone
+    python tests/tools/ab_bits.py --host        the hashes of the spectral stages' host halves alone (no device)
     python tests/tools/ab_bits.py --redo-time N  no hash: run() + sync() of the redo-heavy rows, wall ms, N times each"""
 import hashlib
 import os
@@ -34,6 +37,56 @@ def digest(arrs):
     return h.hexdigest()[:16]
 
 
+FB_FFT = (64, 128, 512, 2048, 4096)
+ML_FFT = (64, 96, 400, 1024, 1200, 4000)
+SPEC_HZ = 16000
+
+
+def fbank_opts(N, f64):
+    """A window of N samples at SPEC_HZ every N / 4, transformed at n_fft = N."""
+    return J.fbank(win_ms=1e3 * N / SPEC_HZ, hop_ms=250.0 * N / SPEC_HZ, n_fft=N, n_mels=10 if N < 256 else 40, f64=f64)
+
+
+def melspec_cases(f64):
+    for N in ML_FFT:
+        for scale, norm in (("htk", "none"), ("slaney", "slaney")):
+            for rng in (0.0, 8.0):
+                yield (N, scale, rng), J.melspec(n_fft=N, hop=N // 4, n_mels=10 if N < 256 else 40, mel_scale=scale,
+                                                 norm=norm, range=rng, f64=f64)
+
+
+def host_bits():
+    """The host halves of the spectral stages on seeded input: windows, dense filterbanks and frames."""
+    x = 9000.0 * np.random.default_rng(64).standard_normal(3 * 4096 + 17)
+    for N in FB_FFT:
+        o = fbank_opts(N, True)
+        print("host fbank", N, digest([J.fbank_window(SPEC_HZ, o)]), digest([J.fbank_filterbank(SPEC_HZ, o)]),
+              digest([J.fbank_host(x, SPEC_HZ, o)]), digest([J.fbank_host(x, SPEC_HZ, fbank_opts(N, False))]))
+    for key, o in melspec_cases(True):
+        print("host melspec", *key, digest([J.melspec_window(SPEC_HZ, o)]), digest([J.melspec_filterbank(SPEC_HZ, o)]),
+              digest([J.melspec_host(x, SPEC_HZ, o)]))
+    print("host mfcc", digest([J.mfcc_pcm_host(x, SPEC_HZ, J.fbank(), J.mfcc())]))
+
+
+def spectral_seams(pcm):
+    """fbank_pcm, mfcc_pcm and melspec_pcm at every transform size, f32 and f64 elements; fir_pcm in direct mode and at
+    both partitioned transform sizes, f64 and the 16-bit sink; noise_pcm."""
+    rng = np.random.default_rng(950)
+    pcm = pcm + [9000.0 * rng.standard_normal(48000)]  # (several workgroups at every transform size)
+    for f64 in (False, True):
+        for N in FB_FFT:
+            o = fbank_opts(N, f64)
+            print("seam fbank", N, "f64" if f64 else "f32", digest(J.fbank_pcm(pcm, SPEC_HZ, o)), "mfcc",
+                  digest(J.mfcc_pcm(pcm, SPEC_HZ, fbank_opts(N, False), J.mfcc(n_ceps=8, delta_order=1, cmvn="mean_var", f64=f64))))
+        for key, o in melspec_cases(f64):
+            print("seam melspec", *key, "f64" if f64 else "f32", digest(J.melspec_pcm(pcm, SPEC_HZ, o)))
+    for K in (256, 257, 2049, 5000):
+        f = J.fir(rng.standard_normal(K) / np.sqrt(K), SPEC_HZ, delay=K // 3)
+        print("seam fir", K, digest(J.fir_pcm(pcm, f, SPEC_HZ)), "i16", digest(J.fir_pcm(pcm, f, SPEC_HZ, i16=True)))
+    y, rep = J.noise_pcm(pcm, J.noise(snr_db=15.0, seed=3), SPEC_HZ)
+    print("seam noise", digest(y), digest([bytes(r) for r in rep]))
+
+
 def pcm_seams():
     """Every body behind the jb_*_pcm_batch entries (f64 and 16-bit instances) on seeded utterances."""
     rng = np.random.default_rng(1025)
@@ -57,6 +110,7 @@ def pcm_seams():
     for i16 in (False, True):
         y, rep = J.limiter_pcm(pcm, [48000, 16000, 48000, 22050], 2.0, -1.0, [0, 0, 1, 1], i16=i16)
         print("seam limiter", "i16" if i16 else "f64", digest(y), digest([repr(rep).encode()]))
+    spectral_seams(pcm)
 
 
 def output_rows(vi, utts, geometry, label):
@@ -116,6 +170,7 @@ def output_stages():
     print("flac_encode_pcm_batch", digest(J.flac_encode(pcm16, 48000)),
           digest(J.flac_encode(pcm16, 22050, block_size=1152, max_lpc_order=12)))
     pcm_seams()
+    host_bits()
 
 
 from jbonsai_amd import synth  # noqa: E402
@@ -125,6 +180,9 @@ if redo_time:
     sys.exit(0)
 if "--seams" in sys.argv:
     pcm_seams()
+    sys.exit(0)
+if "--host" in sys.argv:
+    host_bits()
     sys.exit(0)
 
 v = O.Voice(VOICE)
