@@ -1716,6 +1716,10 @@ int Batch::enqueue_paramgen()
     return JB_OK;
 }
 
+// The taps of a carried state that the hand-off check compares (launch_voc_verify, launch_voc_verify_pairs): the
+// nmcp - 1 live ones, or with -1 every slot of the state (Stage::NonZero)
+static int voc_verify_taps(const VocDev &vd) { return vd.stage > 0 ? -1 : vd.nmcp - 1; }
+
 int Batch::run(bool timed)
 {
     hipError_t e = hipSetDevice(device);
@@ -1758,8 +1762,8 @@ int Batch::run(bool timed)
         hipEventRecord(ev2, stream_voc);
     if (chunk_frames != 0 && n_items > 0) {
         hipMemsetAsync(nbad_dev, 0, sizeof(uint32_t), stream_voc);
-        if ((e = launch_voc_verify(work_dev, n_items, vd.state_stride, vd.stage > 0 ? -1 : vd.nmcp - 1, verify_tol, bad_dev,
-                                   nbad_dev, stream_voc)) != hipSuccess)
+        if ((e = launch_voc_verify(work_dev, n_items, vd.state_stride, voc_verify_taps(vd), verify_tol, bad_dev, nbad_dev,
+                                   stream_voc)) != hipSuccess)
             return hip_fail(e, "k_voc_verify");
         verify_pending = true;
     }
@@ -1773,274 +1777,365 @@ int Batch::run(bool timed)
     return JB_OK;
 }
 
+namespace {
+
+// What the steps of Batch::finish_verify share: the batch, the flags the round rules (jb_plan.h) read and write, and
+// what one step of a round leaves for the next.  Lives for the call alone.
+struct RedoCtx {
+    Batch &b;
+    std::vector<VocPlanItem> items; // b.work as the rules read it: utt and the kSave* bits of the non-null dumps
+    std::vector<uint8_t> pending;   // [n_items] failed its hand-off check and not final yet
+    std::vector<uint8_t> touched;   // [B] utterances a redo round rewrote PCM of: converted again at the end
+    // one round
+    RedoPick pick;
+    RedoStageA a;
+    std::vector<uint8_t> unsettled, at2; // [n_items] the last comparison failed / it was at the second checkpoint
+    RedoSettled s;
+    const bool trace = getenv("JB_REDO_TRACE") != nullptr; // debugging aid: one line per redo round on stderr
+    const std::chrono::steady_clock::time_point tv0 = std::chrono::steady_clock::now();
+    double since() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tv0).count(); }
+    double *tmp(uint32_t k) const { return b.tmp_state + (size_t)k * b.state_stride; }
+    double *tmp2(uint32_t k) const { return b.tmp2_state + (size_t)k * b.state_stride; }
+};
+
+// The failed hand-offs of the run: b.n_redo, and where there are any, c.pending and the items the rules read
+int read_failed_handoffs(RedoCtx &c)
+{
+    Batch &b = c.b;
+    uint32_t nbad = 0;
+    hipError_t e = hipMemcpy(&nbad, b.nbad_dev, sizeof nbad, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipMemcpy(n_bad)");
+    b.n_redo = nbad;
+    if (nbad == 0)
+        return JB_OK;
+    c.pending.resize(b.n_items);
+    if ((e = hipMemcpy(c.pending.data(), b.bad_dev, b.n_items, hipMemcpyDeviceToHost)) != hipSuccess)
+        return hip_fail(e, "hipMemcpy(bad)");
+    c.pending[0] = 0;
+    c.touched.assign((size_t)b.B, 0);
+    c.items.resize(b.n_items);
+    for (uint32_t k = 0; k < b.n_items; k++) {
+        const VocWork &w = b.work[k];
+        c.items[k] = VocPlanItem{w.utt, w.t_start, w.t_out, w.t_end,
+                                 (uint8_t)((w.save_end ? kSaveEnd : 0) | (w.save_warm ? kSaveWarm : 0) |
+                                           (w.save_ckpt ? kSaveCkpt : 0) | (w.save_ckpt2 ? kSaveCkpt2 : 0))};
+    }
+    return JB_OK;
+}
+
+// The work list of a redo launch, the recomputed states and the pair list: allocated by the first run that needs them
+int ensure_redo_scratch(RedoCtx &c)
+{
+    Batch &b = c.b;
+    int rc;
+    if (!b.redo_dev && (rc = b.dalloc(&b.redo_dev, b.n_items, false)))
+        return rc;
+    if (!b.tmp_state && ((rc = b.dalloc(&b.tmp_state, (size_t)b.n_items * b.state_stride, true)) ||
+                         (rc = b.dalloc(&b.pairs_dev, 2 * (size_t)b.n_items, false)) || (rc = b.flush_zero())))
+        return rc;
+    return JB_OK;
+}
+
+// One launch of k_vocoder over `round`, waited for
+int run_redo_items(RedoCtx &c, const std::vector<VocWork> &round)
+{
+    Batch &b = c.b;
+    if (round.empty())
+        return JB_OK;
+    hipError_t he;
+    const double t_a = c.since();
+    if ((he = hipMemcpy(b.redo_dev, round.data(), sizeof(VocWork) * round.size(), hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_fail(he, "hipMemcpy(redo)");
+    const double t_b = c.since();
+    if ((he = launch_vocoder(b.bd, b.vd, b.redo_dev, (uint32_t)round.size(), b.stream_voc, b.invariant)) != hipSuccess)
+        return hip_fail(he, "k_vocoder(redo)");
+    const double t_c = c.since();
+    if ((he = hipStreamSynchronize(b.stream_voc)) != hipSuccess)
+        return hip_fail(he, "redo sync");
+    if (c.trace)
+        fprintf(stderr, "  {copy %.3f launch %.3f wait %.3f} ", t_b - t_a, t_c - t_b, c.since() - t_c);
+    return JB_OK;
+}
+
+// The hand-off comparison of pairs of states (pairs[2q], pairs[2q + 1]) -> bad[q], waited for.  what_launch, what_read:
+// the names of the launch and of the read-back in a failure's text
+int compare_pairs(RedoCtx &c, const std::vector<const double *> &pairs, const char *what_launch, const char *what_read,
+                  std::vector<uint8_t> *bad)
+{
+    Batch &b = c.b;
+    const size_t n = pairs.size() / 2;
+    bad->resize(n);
+    hipError_t e;
+    if ((e = hipMemcpy(b.pairs_dev, pairs.data(), sizeof(double *) * pairs.size(), hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_fail(e, "hipMemcpy(pairs)");
+    if ((e = hipMemsetAsync(b.nbad_dev, 0, sizeof(uint32_t), b.stream_voc)) != hipSuccess)
+        return hip_fail(e, "hipMemset(n_bad)");
+    if ((e = launch_voc_verify_pairs(b.pairs_dev, (uint32_t)n, b.vd.state_stride, voc_verify_taps(b.vd), b.verify_tol, b.bad_dev,
+                                     b.nbad_dev, b.stream_voc)) != hipSuccess)
+        return hip_fail(e, what_launch);
+    if ((e = hipMemcpyAsync(bad->data(), b.bad_dev, n, hipMemcpyDeviceToHost, b.stream_voc)) != hipSuccess ||
+        (e = hipStreamSynchronize(b.stream_voc)) != hipSuccess)
+        return hip_fail(e, what_read);
+    return JB_OK;
+}
+
+// Chunk k again from the end state of its predecessor: to its checkpoint where it has one, else to its end -- into the
+// scratch dump where the state is compared first (redo_stage_a), else over the first pass's end state
+VocWork stage_a_item(const RedoCtx &c, uint32_t k)
+{
+    VocWork w = c.b.work[k];
+    w.t_start = w.t_out;
+    w.load_state = c.b.work[k - 1].save_end;
+    w.save_warm = nullptr;
+    if (w.save_ckpt)
+        w.t_end = w.t_out + c.b.vd.ckpt_frames;
+    if (w.save_ckpt || c.a.spec_end[k])
+        w.save_end = c.tmp(k);
+    w.save_ckpt = w.save_ckpt2 = nullptr;
+    return w;
+}
+
+// Chunk k on from the state recomputed at its first checkpoint to the second
+VocWork second_checkpoint_item(const RedoCtx &c, uint32_t k)
+{
+    VocWork w = c.b.work[k];
+    w.t_start = w.t_out = c.b.work[k].t_out + c.b.vd.ckpt_frames;
+    w.t_end = c.b.work[k].t_out + c.b.vd.ckpt2_frames;
+    w.load_state = c.tmp(k);
+    w.save_end = c.tmp2(k);
+    w.save_warm = w.save_ckpt = w.save_ckpt2 = nullptr;
+    return w;
+}
+
+// Chunk k on from the state recomputed at the checkpoint it was last compared at, to its end
+VocWork stage_b_item(const RedoCtx &c, uint32_t k)
+{
+    VocWork w = c.b.work[k];
+    w.t_start = w.t_out = c.b.work[k].t_out + (c.at2[k] ? c.b.vd.ckpt2_frames : c.b.vd.ckpt_frames);
+    w.load_state = c.at2[k] ? c.tmp2(k) : c.tmp(k);
+    w.save_warm = nullptr;
+    w.save_ckpt = w.save_ckpt2 = nullptr;
+    return w;
+}
+
+// stage A: up to the checkpoint (or the whole chunk where there is none)
+int run_stage_a(RedoCtx &c)
+{
+    c.a = redo_stage_a(c.items, c.pick);
+    std::vector<VocWork> round;
+    for (uint32_t k : c.pick.ids) {
+        c.touched[c.b.work[k].utt] = 1;
+        round.push_back(stage_a_item(c, k));
+    }
+    const double tr0 = c.since();
+    int rc = run_redo_items(c, round);
+    if (rc)
+        return rc;
+    if (c.trace)
+        fprintf(stderr, "  [stage A: built by %.3f, ran until %.3f ms] ", tr0, c.since());
+    return JB_OK;
+}
+
+// does the recomputed state meet the checkpoint (spec_end: the end state the first pass left)?
+int compare_at_checkpoint(RedoCtx &c)
+{
+    const std::vector<uint32_t> &ids = c.pick.ids, &part = c.a.part;
+    c.unsettled.assign(c.b.n_items, 0);
+    c.at2.assign(c.b.n_items, 0);
+    if (part.empty())
+        return JB_OK;
+    std::vector<const double *> pairs(2 * part.size());
+    for (size_t q = 0; q < part.size(); q++) {
+        const uint32_t k = ids[part[q]];
+        pairs[2 * q] = c.tmp(k);
+        pairs[2 * q + 1] = c.a.spec_end[k] ? c.b.work[k].save_end : c.b.work[k].save_ckpt;
+    }
+    std::vector<uint8_t> bad2;
+    int rc = compare_pairs(c, pairs, "k_voc_verify_pairs", "hipMemcpy(bad2)", &bad2);
+    for (size_t q = 0; !rc && q < part.size(); q++)
+        c.unsettled[ids[part[q]]] = bad2[q];
+    return rc;
+}
+
+// second checkpoint: a chunk that had not converged at the first one goes on to it and is compared again
+int second_checkpoint(RedoCtx &c)
+{
+    Batch &b = c.b;
+    const std::vector<uint32_t> mid_ids = redo_second_checkpoint(c.items, c.pick.ids, c.unsettled, b.vd.ckpt2_frames != 0);
+    if (mid_ids.empty())
+        return JB_OK;
+    int rc;
+    if (!b.tmp2_state && ((rc = b.dalloc(&b.tmp2_state, (size_t)b.n_items * b.state_stride, true)) || (rc = b.flush_zero())))
+        return rc;
+    std::vector<VocWork> mid;
+    std::vector<const double *> pairs;
+    for (uint32_t k : mid_ids) {
+        mid.push_back(second_checkpoint_item(c, k));
+        pairs.push_back(c.tmp2(k));
+        pairs.push_back(b.work[k].save_ckpt2);
+    }
+    std::vector<uint8_t> badm;
+    if ((rc = run_redo_items(c, mid)) || (rc = compare_pairs(c, pairs, "k_voc_verify_pairs(second checkpoint)",
+                                                             "hipMemcpy(bad, second checkpoint)", &badm)))
+        return rc;
+    for (size_t q = 0; q < mid_ids.size(); q++) {
+        c.at2[mid_ids[q]] = 1;
+        c.unsettled[mid_ids[q]] = badm[q];
+    }
+    if (c.trace)
+        fprintf(stderr, "  second checkpoint: %zu chunks, %zu still not converged\n", mid_ids.size(),
+                (size_t)std::count_if(badm.begin(), badm.end(), [](uint8_t x) { return x != 0; }));
+    return JB_OK;
+}
+
+// What the round's recomputations are worth (redo_settle), then: the exact end state of a VALID chunk recomputed to its
+// end goes where the first pass left its own (an invalid one started from a state that is being replaced: its dump
+// keeps the first pass's state, the better start for its successor's next attempt); stage B, the rest of the valid
+// chunks that had not converged at their checkpoint; and the valid chunks are final
+int settle_and_finish(RedoCtx &c)
+{
+    Batch &b = c.b;
+    c.s = redo_settle(c.items, c.pick, c.pending, c.a.spec_end, c.unsettled);
+    b.n_redo_partial += c.s.n_partial;
+    b.n_redo_full += c.s.n_full;
+    hipError_t e;
+    for (uint32_t k : c.pick.ids)
+        if (c.s.final_now[k] && c.a.spec_end[k] &&
+            (e = hipMemcpyAsync(b.work[k].save_end, c.tmp(k), sizeof(double) * b.state_stride, hipMemcpyDeviceToDevice,
+                                b.stream_voc)) != hipSuccess)
+            return hip_fail(e, "hipMemcpy(end state)");
+    std::vector<VocWork> rest;
+    for (uint32_t k : c.s.rest)
+        rest.push_back(stage_b_item(c, k));
+    int rc = run_redo_items(c, rest);
+    if (rc)
+        return rc;
+    for (uint32_t k : c.pick.ids)
+        if (c.s.final_now[k])
+            c.pending[k] = 0;
+    if (c.trace)
+        fprintf(stderr, "  (%.3f ms since the check was read) redo round: %zu items (%zu to a checkpoint), %zu continue past it, "
+                        "%u settled so far, %u to the end so far\n",
+                c.since(), c.pick.ids.size(), c.a.part.size(), rest.size(), b.n_redo_partial, b.n_redo_full);
+    return JB_OK;
+}
+
+// Re-certification (redo_recertify): the hand-offs behind the chunks recomputed to their end, compared again; a
+// successor that fails is pending from here on
+int recertify(RedoCtx &c)
+{
+    Batch &b = c.b;
+    const std::vector<uint32_t> succ = redo_recertify(c.items, c.s.full_ids, c.pick.in_round, c.pending);
+    if (succ.empty())
+        return JB_OK;
+    std::vector<const double *> pairs(2 * succ.size());
+    for (size_t q = 0; q < succ.size(); q++) {
+        pairs[2 * q] = b.work[succ[q]].save_warm;
+        pairs[2 * q + 1] = b.work[succ[q] - 1].save_end;
+    }
+    std::vector<uint8_t> bad3;
+    int rc = compare_pairs(c, pairs, "k_voc_verify_pairs(successors)", "hipMemcpy(bad3)", &bad3);
+    if (rc)
+        return rc;
+    if (c.trace)
+        fprintf(stderr, "  re-certified %zu successors: %zu fail\n", succ.size(),
+                (size_t)std::count_if(bad3.begin(), bad3.end(), [](uint8_t x) { return x != 0; }));
+    for (size_t q = 0; q < succ.size(); q++)
+        if (bad3[q]) {
+            c.pending[succ[q]] = 1;
+            b.n_redo++;
+            b.n_recert_failed++;
+        }
+    return JB_OK;
+}
+
+} // namespace
+
 // After the stream has drained: act on the chunk hand-off check.  Chunks whose
 // warmed-up state disagrees with the predecessor's end state are recomputed from that
 // end state (exact continuation), in increasing order so that each re-do starts from
 // a final state.
+// A chunk with a checkpoint is first recomputed only up to it (vd.ckpt_frames frames): if the
+// recomputed state meets the checkpoint the original chunk left there, the rest of that chunk
+// was computed from a trajectory that had already converged and stands; otherwise the
+// recomputation continues from there to the end of the chunk.  Which chunks a round takes and what
+// its comparisons are worth are the rules of jb_plan.h (redo_pick_round .. redo_recertify); the
+// steps above do the device's part.
 int Batch::finish_verify()
 {
     if (!verify_pending)
         return JB_OK;
     verify_pending = false;
-    const auto tv0 = std::chrono::steady_clock::now();
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tv0).count(); };
-    uint32_t nbad = 0;
-    hipError_t e = hipMemcpy(&nbad, nbad_dev, sizeof nbad, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return hip_fail(e, "hipMemcpy(n_bad)");
-    n_redo = nbad;
-    if (nbad == 0)
-        return JB_OK;
-    std::vector<uint8_t> bad(n_items);
-    if ((e = hipMemcpy(bad.data(), bad_dev, n_items, hipMemcpyDeviceToHost)) != hipSuccess)
-        return hip_fail(e, "hipMemcpy(bad)");
-    // rounds: every failing chunk whose predecessor is final (not itself pending) is
-    // recomputed in the same launch; runs of consecutive failures take one round each.
-    // A chunk with a checkpoint is first recomputed only up to it (vd.ckpt_frames frames): if the
-    // recomputed state meets the checkpoint the original chunk left there, the rest of that chunk
-    // was computed from a trajectory that had already converged and stands; otherwise the
-    // recomputation continues from there to the end of the chunk.
+    RedoCtx c{*this};
+    int rc = read_failed_handoffs(c);
+    if (rc || n_redo == 0)
+        return rc;
     n_redo_partial = n_redo_full = n_recert_failed = 0;
-    const size_t stride = state_stride;
-    int rc;
-    if (!redo_dev && (rc = dalloc(&redo_dev, n_items, false)))
+    if ((rc = ensure_redo_scratch(c)))
         return rc;
-    if (!tmp_state && ((rc = dalloc(&tmp_state, (size_t)n_items * stride, true)) ||
-                       (rc = dalloc(&pairs_dev, 2 * (size_t)n_items, false)) || (rc = flush_zero())))
-        return rc;
-    auto run_round = [&](const std::vector<VocWork> &round) -> int {
-        if (round.empty())
-            return JB_OK;
-        hipError_t he;
-        const double t_a = since();
-
-        if ((he = hipMemcpy(redo_dev, round.data(), sizeof(VocWork) * round.size(), hipMemcpyHostToDevice)) !=
-            hipSuccess)
-            return hip_fail(he, "hipMemcpy(redo)");
-        const double t_b = since();
-        if ((he = launch_vocoder(bd, vd, redo_dev, (uint32_t)round.size(), stream_voc, invariant)) != hipSuccess)
-            return hip_fail(he, "k_vocoder(redo)");
-        const double t_c = since();
-        if ((he = hipStreamSynchronize(stream_voc)) != hipSuccess)
-            return hip_fail(he, "redo sync");
-        if (getenv("JB_REDO_TRACE"))
-            fprintf(stderr, "  {copy %.3f launch %.3f wait %.3f} ", t_b - t_a, t_c - t_b, since() - t_c);
-        return JB_OK;
-    };
-    std::vector<uint8_t> pending(bad);
-    pending[0] = 0;
-    std::vector<uint8_t> touched((size_t)B, 0); // utterances a redo round rewrote PCM of: converted again at the end
-    const bool redo_trace = getenv("JB_REDO_TRACE") != nullptr; // debugging aid: one line per redo round on stderr
-    if (redo_trace)
-        fprintf(stderr, "redo: lists and scratch ready after %.3f ms\n", since());
+    if (c.trace)
+        fprintf(stderr, "redo: lists and scratch ready after %.3f ms\n", c.since());
     for (;;) {
-        // This round: every failing chunk whose predecessor is final, AND -- speculatively -- a failing chunk
-        // behind a failing chunk: it starts from the end state its predecessor left in the FIRST pass.  That state
-        // stands if the predecessor settles at its checkpoint (295 of 297 do; stage A of a chunk with a checkpoint
-        // does not touch the dump), or, for a chunk without a checkpoint, if the end state of its recomputation
-        // -- written to a scratch dump, compared after the launch, then copied over -- meets it to the hand-off
-        // tolerance (the trajectory that started wrong has had warm-up + chunk frames to converge: every one of
-        // 156 did in a batch of 16 x 25,546 frames).  Where it does not stand, the successor's recomputation
-        // started from a state that is being replaced: it stays pending for the next round.  (Before, a run of
-        // consecutive failures cost one round per chunk: 3 ms each with checkpoints, 1.2 ms each for 20-frame
-        // chunks, two or three rounds per step in small batches.)
-        std::vector<uint32_t> ids;
-        std::vector<uint8_t> in_round(n_items, 0);
-        for (uint32_t k = 1; k < n_items; k++) {
-            if (!pending[k])
-                continue;
-            if (!pending[k - 1] || (in_round[k - 1] && work[k - 1].save_end && work[k - 1].utt == work[k].utt)) {
-                ids.push_back(k);
-                in_round[k] = 1;
-            }
-        }
-        if (ids.empty())
+        c.pick = redo_pick_round(c.items, c.pending);
+        if (c.pick.ids.empty())
             break;
-        for (uint32_t k : ids)
-            touched[work[k].utt] = 1;
-        // stage A: up to the checkpoint (or the whole chunk where there is none)
-        std::vector<VocWork> round;
-        std::vector<uint32_t> part; // positions in ids whose recomputed state is compared: with a checkpoint, or
-                                    // (spec_end) recomputed to the end with a successor in this round
-        std::vector<uint8_t> spec_end(n_items, 0);
-        for (size_t j = 0; j < ids.size(); j++) {
-            const uint32_t k = ids[j];
-            VocWork w = work[k];
-            w.t_start = w.t_out;
-            w.load_state = work[k - 1].save_end;
-            w.save_warm = nullptr;
-            if (w.save_ckpt) {
-                w.t_end = w.t_out + vd.ckpt_frames;
-                w.save_end = tmp_state + (size_t)k * stride;
-                part.push_back((uint32_t)j);
-            } else if (k + 1 < n_items && in_round[k + 1] && work[k + 1].utt == w.utt && w.save_end) {
-                spec_end[k] = 1;
-                w.save_end = tmp_state + (size_t)k * stride;
-                part.push_back((uint32_t)j);
-            }
-            w.save_ckpt = w.save_ckpt2 = nullptr;
-            round.push_back(w);
-        }
-        const double tr0 = since();
-        if ((rc = run_round(round)))
+        if ((rc = run_stage_a(c)) || (rc = compare_at_checkpoint(c)) || (rc = second_checkpoint(c)) ||
+            (rc = settle_and_finish(c)) || (rc = recertify(c)))
             return rc;
-        if (redo_trace)
-            fprintf(stderr, "  [stage A: built by %.3f, ran until %.3f ms] ", tr0, since());
-        // does the recomputed state meet the checkpoint?
-        std::vector<uint8_t> unsettled(n_items, 0);
-        if (!part.empty()) {
-            std::vector<const double *> pairs(2 * part.size());
-            for (size_t q = 0; q < part.size(); q++) {
-                const uint32_t k = ids[part[q]];
-                pairs[2 * q] = tmp_state + (size_t)k * stride;
-                pairs[2 * q + 1] = spec_end[k] ? work[k].save_end : work[k].save_ckpt;
-            }
-            hipMemcpy(pairs_dev, pairs.data(), sizeof(double *) * pairs.size(), hipMemcpyHostToDevice);
-            hipMemsetAsync(nbad_dev, 0, sizeof(uint32_t), stream_voc);
-            if ((e = launch_voc_verify_pairs(pairs_dev, (uint32_t)part.size(), vd.state_stride, vd.stage > 0 ? -1 : vd.nmcp - 1, verify_tol, bad_dev,
-                                             nbad_dev, stream_voc)) != hipSuccess)
-                return hip_fail(e, "k_voc_verify_pairs");
-            std::vector<uint8_t> bad2(part.size());
-            if ((e = hipMemcpyAsync(bad2.data(), bad_dev, part.size(), hipMemcpyDeviceToHost, stream_voc)) !=
-                    hipSuccess ||
-                (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
-                return hip_fail(e, "hipMemcpy(bad2)");
-            for (size_t q = 0; q < part.size(); q++)
-                unsettled[ids[part[q]]] = bad2[q];
-        }
-        // second checkpoint: a chunk that had not converged at the first one goes on to it and is compared again
-        std::vector<uint8_t> at2(n_items, 0);
-        if (vd.ckpt2_frames) {
-            std::vector<VocWork> mid;
-            std::vector<uint32_t> mid_ids;
-            for (uint32_t k : ids)
-                if (work[k].save_ckpt && work[k].save_ckpt2 && unsettled[k]) {
-                    if (!tmp2_state && ((rc = dalloc(&tmp2_state, (size_t)n_items * stride, true)) || (rc = flush_zero())))
-                        return rc;
-                    VocWork w = work[k];
-                    w.t_start = w.t_out = work[k].t_out + vd.ckpt_frames;
-                    w.t_end = work[k].t_out + vd.ckpt2_frames;
-                    w.load_state = tmp_state + (size_t)k * stride;
-                    w.save_end = tmp2_state + (size_t)k * stride;
-                    w.save_warm = w.save_ckpt = w.save_ckpt2 = nullptr;
-                    mid.push_back(w);
-                    mid_ids.push_back(k);
-                }
-            if (!mid.empty()) {
-                if ((rc = run_round(mid)))
-                    return rc;
-                std::vector<const double *> pairs(2 * mid_ids.size());
-                for (size_t q = 0; q < mid_ids.size(); q++) {
-                    pairs[2 * q] = tmp2_state + (size_t)mid_ids[q] * stride;
-                    pairs[2 * q + 1] = work[mid_ids[q]].save_ckpt2;
-                }
-                hipMemcpy(pairs_dev, pairs.data(), sizeof(double *) * pairs.size(), hipMemcpyHostToDevice);
-                hipMemsetAsync(nbad_dev, 0, sizeof(uint32_t), stream_voc);
-                if ((e = launch_voc_verify_pairs(pairs_dev, (uint32_t)mid_ids.size(), vd.state_stride, vd.stage > 0 ? -1 : vd.nmcp - 1,
-                                                 verify_tol, bad_dev, nbad_dev, stream_voc)) != hipSuccess)
-                    return hip_fail(e, "k_voc_verify_pairs(second checkpoint)");
-                std::vector<uint8_t> badm(mid_ids.size());
-                if ((e = hipMemcpyAsync(badm.data(), bad_dev, mid_ids.size(), hipMemcpyDeviceToHost, stream_voc)) != hipSuccess ||
-                    (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
-                    return hip_fail(e, "hipMemcpy(bad, second checkpoint)");
-                for (size_t q = 0; q < mid_ids.size(); q++) {
-                    at2[mid_ids[q]] = 1;
-                    unsettled[mid_ids[q]] = badm[q];
-                }
-                if (redo_trace)
-                    fprintf(stderr, "  second checkpoint: %zu chunks, %zu still not converged\n", mid_ids.size(),
-                            (size_t)std::count_if(badm.begin(), badm.end(), [](uint8_t x) { return x != 0; }));
-            }
-        }
-        // in chunk order: what this round's recomputations are worth
-        std::vector<VocWork> rest;      // stage B: the rest of valid chunks that had not converged at their checkpoint
-        std::vector<uint32_t> full_ids; // chunks recomputed to their end in this round
-        std::vector<uint8_t> final_now(n_items, 0);
-        for (uint32_t k : ids) {
-            // valid: started from a final state -- the predecessor was final before the round, or it was in the
-            // round, valid itself, and its first-pass end state stands (settled at its checkpoint / met by the end
-            // state of its recomputation)
-            const bool pred_in = in_round[k - 1] && pending[k - 1];
-            const bool valid = !pred_in || (final_now[k - 1] && (work[k - 1].save_ckpt || spec_end[k - 1]) && !unsettled[k - 1]);
-            if (!valid)
-                continue; // stays pending: next round, from the state its predecessor is getting now
-            final_now[k] = 1;
-            if (!work[k].save_ckpt) {
-                n_redo_full++;
-                full_ids.push_back(k);
-            } else if (!unsettled[k]) {
-                n_redo_partial++;
-            } else {
-                n_redo_full++;
-                full_ids.push_back(k);
-                VocWork w = work[k];
-                w.t_start = w.t_out = work[k].t_out + (at2[k] ? vd.ckpt2_frames : vd.ckpt_frames);
-                w.load_state = (at2[k] ? tmp2_state : tmp_state) + (size_t)k * stride;
-                w.save_warm = nullptr;
-                w.save_ckpt = w.save_ckpt2 = nullptr;
-                rest.push_back(w);
-            }
-        }
-        // the exact end state of a VALID chunk recomputed to its end goes where the first pass left its own (an
-        // invalid one started from a state that is being replaced: its dump keeps the first pass's state, the better
-        // start for its successor's next attempt)
-        for (uint32_t k : ids)
-            if (final_now[k] && spec_end[k] &&
-                (e = hipMemcpyAsync(work[k].save_end, tmp_state + (size_t)k * stride, sizeof(double) * stride,
-                                    hipMemcpyDeviceToDevice, stream_voc)) != hipSuccess)
-                return hip_fail(e, "hipMemcpy(end state)");
-        if ((rc = run_round(rest)))
-            return rc;
-        for (uint32_t k : ids)
-            if (final_now[k])
-                pending[k] = 0;
-        if (redo_trace)
-            fprintf(stderr, "  (%.3f ms since the check was read) ", since());
-        if (redo_trace)
-            fprintf(stderr, "redo round: %zu items (%zu to a checkpoint), %zu continue past it, %u settled so far, %u to the end so far\n",
-                    ids.size(), part.size(), rest.size(), n_redo_partial, n_redo_full);
-        // Re-certification.  Chunk k+1 was checked against the end state chunk k left in the first
-        // pass -- the end of a trajectory now known to have started wrong.  Where chunk k has been
-        // recomputed to its end, that dump now holds the exact state: compare it with the warm state of
-        // chunk k+1 again and put k+1 on the list if it fails.  (A chunk settled at its checkpoint kept
-        // its first-pass end state, whose trajectory was certified at the checkpoint: nothing to re-check.)
-        std::vector<uint32_t> succ;
-        for (uint32_t k : full_ids)
-            // (a successor that was recomputed in this round started from this chunk's end state: nothing to re-check
-            // if that was valid, and it is still pending if not)
-            if (k + 1 < n_items && work[k + 1].utt == work[k].utt && work[k + 1].save_warm && !pending[k + 1] &&
-                !in_round[k + 1] && work[k].save_end)
-                succ.push_back(k + 1);
-        if (!succ.empty()) {
-            std::vector<const double *> pairs(2 * succ.size());
-            for (size_t q = 0; q < succ.size(); q++) {
-                pairs[2 * q] = work[succ[q]].save_warm;
-                pairs[2 * q + 1] = work[succ[q] - 1].save_end;
-            }
-            hipMemcpy(pairs_dev, pairs.data(), sizeof(double *) * pairs.size(), hipMemcpyHostToDevice);
-            hipMemsetAsync(nbad_dev, 0, sizeof(uint32_t), stream_voc);
-            if ((e = launch_voc_verify_pairs(pairs_dev, (uint32_t)succ.size(), vd.state_stride, vd.stage > 0 ? -1 : vd.nmcp - 1, verify_tol,
-                                             bad_dev, nbad_dev, stream_voc)) != hipSuccess)
-                return hip_fail(e, "k_voc_verify_pairs(successors)");
-            std::vector<uint8_t> bad3(succ.size());
-            if ((e = hipMemcpyAsync(bad3.data(), bad_dev, succ.size(), hipMemcpyDeviceToHost, stream_voc)) !=
-                    hipSuccess ||
-                (e = hipStreamSynchronize(stream_voc)) != hipSuccess)
-                return hip_fail(e, "hipMemcpy(bad3)");
-            if (redo_trace)
-                fprintf(stderr, "  re-certified %zu successors: %zu fail\n", succ.size(),
-                        (size_t)std::count_if(bad3.begin(), bad3.end(), [](uint8_t x) { return x != 0; }));
-            for (size_t q = 0; q < succ.size(); q++)
-                if (bad3[q]) {
-                    pending[succ[q]] = 1;
-                    n_redo++;
-                    n_recert_failed++;
-                }
-        }
     }
     // what run() converted, measured and encoded behind the check came in part from PCM these rounds replaced (the
     // gain is a function of an utterance's final PCM; the FLAC pack places every stream again)
-    return out.enqueue(&touched);
+    return out.enqueue(&c.touched);
+}
+
+// The error flag of a stream's resident GV kernel (s.gv_gang_ctl is set): a blocking 4-byte copy
+static int read_gang_err(const StreamDev &s, uint32_t *err)
+{
+    hipError_t e = hipMemcpy(err, &((GvGangCtl *)s.gv_gang_ctl)->err, sizeof *err, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? JB_OK : hip_fail(e, "hipMemcpy(gv gang err)");
+}
+
+// JB_GG_PROFILE_PRINT: what the resident GV kernel of a library built with -DJB_GG_PROFILE recorded, on stderr
+static void print_gang_profile(const StreamDev &s)
+{
+    GvGangCtl c;
+    hipMemcpy(&c, s.gv_gang_ctl, sizeof c, hipMemcpyDeviceToHost);
+    const double nb = (double)s.gv_gang_n * s.gv_gang_tiles;
+    fprintf(stderr,
+            "k_mlpg_gv_gang ticks per workgroup: load %.0f stats %.0f blocksum %.0f exchange %.0f (hand-off alone "
+            "%.0f) step %.0f store %.0f\n",
+            c.prof[0] / nb, c.prof[1] / nb, c.prof[2] / nb, c.prof[3] / nb, c.prof[6] / nb, c.prof[4] / nb, c.prof[5] / nb);
+#if JB_GG_PROFILE
+    // who a gang waits for: per exchange of gangs 0, 9, 18 the arrival of each tile (its sums ready) behind the
+    // gang's first arrival, and how long after the LAST arrival the last tile had the exchange over (100 MHz clock)
+    const int nt = std::min(s.gv_gang_tiles, 8);
+    for (int gi : {0, 9, 18}) {
+        if (gi >= s.gv_gang_n)
+            continue;
+        GvGang gg;
+        hipMemcpy(&gg, (const uint8_t *)s.gv_gang_ctl + sizeof(GvGangCtl) + sizeof(GvGang) * (size_t)gi, sizeof gg,
+                  hipMemcpyDeviceToHost);
+        fprintf(stderr, "gang %d: exchange | arrival of tiles 0..%d behind the first, us | last arrival -> all done, us | since previous exchange, us\n", gi, nt - 1);
+        unsigned long long prev_first = 0;
+        for (int e = 0; e < 96; e++) {
+            unsigned long long first = ~0ull, last = 0, done = 0;
+            for (int t = 0; t < nt; t++) {
+                first = std::min(first, gg.stamp[0][t][e]);
+                last = std::max(last, gg.stamp[0][t][e]);
+                done = std::max(done, gg.stamp[1][t][e]);
+            }
+            if (first == 0)
+                break;
+            fprintf(stderr, "  %2d |", e);
+            for (int t = 0; t < nt; t++)
+                fprintf(stderr, " %5.2f", (double)(gg.stamp[0][t][e] - first) / 100.0);
+            fprintf(stderr, " | %5.2f | %6.2f\n", (double)(done - last) / 100.0,
+                    prev_first ? (double)(first - prev_first) / 100.0 : 0.0);
+            prev_first = first;
+        }
+    }
+#endif
 }
 
 int Batch::sync()
@@ -2059,56 +2154,19 @@ int Batch::sync()
     for (int si = 0; gang_check_pending && si < kMaxStream; si++)
         if (sd[si].gv_gang_ctl) {
             uint32_t err = 0;
-            uint32_t *derr = &((GvGangCtl *)sd[si].gv_gang_ctl)->err;
-            if ((e = hipMemcpy(&err, derr, sizeof err, hipMemcpyDeviceToHost)) != hipSuccess)
-                return hip_fail(e, "hipMemcpy(gv gang err)");
+            int rc = read_gang_err(sd[si], &err);
+            if (rc)
+                return rc;
             if (err) {
                 // Formation timed out: with several resident launches on one device each can hold CUs with
                 // incomplete gangs while none owns all its members.  This batch's GV runs as the multi-launch
                 // sweeps from now on (their workspace is allocated either way) and the step is done again.
-                (void)hipMemset(derr, 0, sizeof err);
+                (void)hipMemset(&((GvGangCtl *)sd[si].gv_gang_ctl)->err, 0, sizeof err);
                 sd[si].gv_gang_ctl = nullptr;
                 gang_timed_out = true;
                 gang_fallbacks++;
             } else if (getenv("JB_GG_PROFILE_PRINT")) { // library built with -DJB_GG_PROFILE
-                GvGangCtl c;
-                hipMemcpy(&c, sd[si].gv_gang_ctl, sizeof c, hipMemcpyDeviceToHost);
-                const double nb = (double)sd[si].gv_gang_n * sd[si].gv_gang_tiles;
-                fprintf(stderr,
-                        "k_mlpg_gv_gang ticks per workgroup: load %.0f stats %.0f blocksum %.0f exchange %.0f (hand-off alone "
-                        "%.0f) step %.0f store %.0f\n",
-                        c.prof[0] / nb, c.prof[1] / nb, c.prof[2] / nb, c.prof[3] / nb, c.prof[6] / nb, c.prof[4] / nb,
-                        c.prof[5] / nb);
-#if JB_GG_PROFILE
-                // who a gang waits for: per exchange of gangs 0, 9, 18 the arrival of each tile (its sums ready) behind the
-                // gang's first arrival, and how long after the LAST arrival the last tile had the exchange over (100 MHz clock)
-                const int nt = std::min(sd[si].gv_gang_tiles, 8);
-                for (int gi : {0, 9, 18}) {
-                    if (gi >= sd[si].gv_gang_n)
-                        continue;
-                    GvGang gg;
-                    hipMemcpy(&gg, (const uint8_t *)sd[si].gv_gang_ctl + sizeof(GvGangCtl) + sizeof(GvGang) * (size_t)gi, sizeof gg,
-                              hipMemcpyDeviceToHost);
-                    fprintf(stderr, "gang %d: exchange | arrival of tiles 0..%d behind the first, us | last arrival -> all done, us | since previous exchange, us\n", gi, nt - 1);
-                    unsigned long long prev_first = 0;
-                    for (int e = 0; e < 96; e++) {
-                        unsigned long long first = ~0ull, last = 0, done = 0;
-                        for (int t = 0; t < nt; t++) {
-                            first = std::min(first, gg.stamp[0][t][e]);
-                            last = std::max(last, gg.stamp[0][t][e]);
-                            done = std::max(done, gg.stamp[1][t][e]);
-                        }
-                        if (first == 0)
-                            break;
-                        fprintf(stderr, "  %2d |", e);
-                        for (int t = 0; t < nt; t++)
-                            fprintf(stderr, " %5.2f", (double)(gg.stamp[0][t][e] - first) / 100.0);
-                        fprintf(stderr, " | %5.2f | %6.2f\n", (double)(done - last) / 100.0,
-                                prev_first ? (double)(first - prev_first) / 100.0 : 0.0);
-                        prev_first = first;
-                    }
-                }
-#endif
+                print_gang_profile(sd[si]);
             }
         }
     gang_check_pending = false;
@@ -2126,9 +2184,9 @@ int Batch::gang_timeout_seen(bool *seen)
     for (int si = 0; gang_check_pending && si < kMaxStream; si++)
         if (sd[si].gv_gang_ctl) {
             uint32_t err = 0;
-            hipError_t e = hipMemcpy(&err, &((GvGangCtl *)sd[si].gv_gang_ctl)->err, sizeof err, hipMemcpyDeviceToHost);
-            if (e != hipSuccess)
-                return hip_fail(e, "hipMemcpy(gv gang err)");
+            int rc = read_gang_err(sd[si], &err);
+            if (rc)
+                return rc;
             if (err)
                 *seen = true;
         }

@@ -1,6 +1,6 @@
 // jb_plan.cpp -- the vocoder's work list (jb_plan.h): serial = one item per utterance; chunked = items of
 // chunk_frames output frames that start warmup_frames early from zero state.  Batch::build_work allocates and
-// uploads what this decides.  Behind it, the shape rules of Batch::create.
+// uploads what this decides.  Behind it, the rules of the redo rounds and the shape rules of Batch::create.
 #include "jb_plan.h"
 
 #include <algorithm>
@@ -229,6 +229,105 @@ VocPlan plan_vocoder_work(const VocPlanIn &in)
         }
     }
     return p;
+}
+
+RedoPick redo_pick_round(const std::vector<VocPlanItem> &items, const std::vector<uint8_t> &pending)
+{
+    // This round: every failing chunk whose predecessor is final, AND -- speculatively -- a failing chunk
+    // behind a failing chunk: it starts from the end state its predecessor left in the FIRST pass.  That state
+    // stands if the predecessor settles at its checkpoint (295 of 297 do; stage A of a chunk with a checkpoint
+    // does not touch the dump), or, for a chunk without a checkpoint, if the end state of its recomputation
+    // -- written to a scratch dump, compared after the launch, then copied over -- meets it to the hand-off
+    // tolerance (the trajectory that started wrong has had warm-up + chunk frames to converge: every one of
+    // 156 did in a batch of 16 x 25,546 frames).  Where it does not stand, the successor's recomputation
+    // started from a state that is being replaced: it stays pending for the next round.  (Before, a run of
+    // consecutive failures cost one round per chunk: 3 ms each with checkpoints, 1.2 ms each for 20-frame
+    // chunks, two or three rounds per step in small batches.)
+    const uint32_t n = (uint32_t)items.size();
+    RedoPick p;
+    p.in_round.assign(n, 0);
+    for (uint32_t k = 1; k < n; k++) {
+        if (!pending[k])
+            continue;
+        if (!pending[k - 1] || (p.in_round[k - 1] && (items[k - 1].saves & kSaveEnd) && items[k - 1].utt == items[k].utt)) {
+            p.ids.push_back(k);
+            p.in_round[k] = 1;
+        }
+    }
+    return p;
+}
+
+RedoStageA redo_stage_a(const std::vector<VocPlanItem> &items, const RedoPick &pick)
+{
+    const uint32_t n = (uint32_t)items.size();
+    RedoStageA a;
+    a.spec_end.assign(n, 0);
+    for (size_t j = 0; j < pick.ids.size(); j++) {
+        const uint32_t k = pick.ids[j];
+        if (items[k].saves & kSaveCkpt) {
+            a.part.push_back((uint32_t)j);
+        } else if (k + 1 < n && pick.in_round[k + 1] && items[k + 1].utt == items[k].utt && (items[k].saves & kSaveEnd)) {
+            a.spec_end[k] = 1;
+            a.part.push_back((uint32_t)j);
+        }
+    }
+    return a;
+}
+
+std::vector<uint32_t> redo_second_checkpoint(const std::vector<VocPlanItem> &items, const std::vector<uint32_t> &ids,
+                                             const std::vector<uint8_t> &unsettled, bool ckpt2)
+{
+    std::vector<uint32_t> mid_ids;
+    for (uint32_t k : ids)
+        if (ckpt2 && (items[k].saves & kSaveCkpt) && (items[k].saves & kSaveCkpt2) && unsettled[k])
+            mid_ids.push_back(k);
+    return mid_ids;
+}
+
+RedoSettled redo_settle(const std::vector<VocPlanItem> &items, const RedoPick &pick, const std::vector<uint8_t> &pending,
+                        const std::vector<uint8_t> &spec_end, const std::vector<uint8_t> &unsettled)
+{
+    RedoSettled s;
+    s.final_now.assign(items.size(), 0);
+    for (uint32_t k : pick.ids) {
+        // valid: started from a final state -- the predecessor was final before the round, or it was in the
+        // round, valid itself, and its first-pass end state stands (settled at its checkpoint / met by the end
+        // state of its recomputation)
+        const bool pred_in = pick.in_round[k - 1] && pending[k - 1];
+        const bool valid = !pred_in || (s.final_now[k - 1] && ((items[k - 1].saves & kSaveCkpt) || spec_end[k - 1]) && !unsettled[k - 1]);
+        if (!valid)
+            continue; // stays pending: next round, from the state its predecessor is getting now
+        s.final_now[k] = 1;
+        if (!(items[k].saves & kSaveCkpt)) {
+            s.n_full++;
+            s.full_ids.push_back(k);
+        } else if (!unsettled[k]) {
+            s.n_partial++;
+        } else {
+            s.n_full++;
+            s.full_ids.push_back(k);
+            s.rest.push_back(k);
+        }
+    }
+    return s;
+}
+
+std::vector<uint32_t> redo_recertify(const std::vector<VocPlanItem> &items, const std::vector<uint32_t> &full_ids,
+                                     const std::vector<uint8_t> &in_round, const std::vector<uint8_t> &pending)
+{
+    // Re-certification.  Chunk k+1 was checked against the end state chunk k left in the first
+    // pass -- the end of a trajectory now known to have started wrong.  Where chunk k has been
+    // recomputed to its end, that dump now holds the exact state: compare it with the warm state of
+    // chunk k+1 again and put k+1 on the list if it fails.  (A chunk settled at its checkpoint kept
+    // its first-pass end state, whose trajectory was certified at the checkpoint: nothing to re-check.)
+    std::vector<uint32_t> succ;
+    for (uint32_t k : full_ids)
+        // (a successor that was recomputed in this round started from this chunk's end state: nothing to re-check
+        // if that was valid, and it is still pending if not)
+        if (k + 1 < items.size() && items[k + 1].utt == items[k].utt && (items[k + 1].saves & kSaveWarm) && !pending[k + 1] &&
+            !in_round[k + 1] && (items[k].saves & kSaveEnd))
+            succ.push_back(k + 1);
+    return succ;
 }
 
 FrameBlocks plan_frame_blocks(int fperiod, int nlpf)

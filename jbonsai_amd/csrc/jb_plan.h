@@ -1,7 +1,8 @@
 #pragma once
 // jb_plan.h -- the vocoder's work geometry: chunk length, warm-up, checkpoints, kernel and waves per SIMD, the work
 // items and the lane kernel's launch order, decided from the batch's shape alone (plan_vocoder_work, jb_plan.cpp).
-// Below it, the shape rules of Batch::create: frame blocks, the voiced runs of an LF0 track, the vocoder conditions and
+// Below it, the rules of the redo rounds that follow a failed hand-off check (Batch::finish_verify) and the shape
+// rules of Batch::create: frame blocks, the voiced runs of an LF0 track, the vocoder conditions and
 // each stream's MLPG mode.  Plain C++17 without HIP: the planners run and are tested on any host; the kernels read the
 // constants below too.
 #include "../../include/jbonsai_amd.h"
@@ -71,6 +72,46 @@ struct VocPlan {
 
 // Pure: no globals, no environment.
 VocPlan plan_vocoder_work(const VocPlanIn &in);
+
+// ---- the redo rounds of the hand-off check (Batch::finish_verify) ----
+// Which failing chunks a round recomputes, how far, and what the recomputations are worth once their states have been
+// compared: rules over chunk indices alone.  They read each item's utt and kSave* bits, the flags below ([n items]
+// each, 0 / 1) and nothing else; the driver does the device round trips between them.  Each pure.
+
+// This round: `ids` (increasing) and the same as flags.  pending[0] must be 0: chunk 0 has no hand-off
+struct RedoPick {
+    std::vector<uint32_t> ids;
+    std::vector<uint8_t> in_round;
+};
+RedoPick redo_pick_round(const std::vector<VocPlanItem> &items, const std::vector<uint8_t> &pending);
+
+// Stage A: a chunk with a checkpoint goes up to it, every other one to its end -- speculatively (spec_end) where its
+// successor is in the round too, of the same utterance, and starts from the end state this chunk leaves
+struct RedoStageA {
+    std::vector<uint32_t> part;    // positions in ids whose recomputed state is compared: with a checkpoint, or spec_end
+    std::vector<uint8_t> spec_end; // recomputed to the end into a scratch dump, compared with the first pass's end state
+};
+RedoStageA redo_stage_a(const std::vector<VocPlanItem> &items, const RedoPick &pick);
+
+// Second checkpoint: the chunks of the round that had not converged at the first one and have a second to go on to
+std::vector<uint32_t> redo_second_checkpoint(const std::vector<VocPlanItem> &items, const std::vector<uint32_t> &ids,
+                                             const std::vector<uint8_t> &unsettled, bool ckpt2);
+
+// In chunk order: what the round's recomputations are worth.  unsettled: the chunk's last comparison failed (at the
+// second checkpoint for those that went on to it); pending: as the round was picked from
+struct RedoSettled {
+    std::vector<uint8_t> final_now; // valid recomputations: no longer pending after this round
+    std::vector<uint32_t> rest;     // stage B: final chunks that go on to their end from the checkpoint they were last
+                                    // compared at
+    std::vector<uint32_t> full_ids; // final chunks recomputed to their end in this round
+    uint32_t n_partial = 0, n_full = 0; // final chunks settled at a checkpoint / recomputed to the end
+};
+RedoSettled redo_settle(const std::vector<VocPlanItem> &items, const RedoPick &pick, const std::vector<uint8_t> &pending,
+                        const std::vector<uint8_t> &spec_end, const std::vector<uint8_t> &unsettled);
+
+// Re-certification: the successors of full_ids whose hand-off is compared again.  pending: after the round
+std::vector<uint32_t> redo_recertify(const std::vector<VocPlanItem> &items, const std::vector<uint32_t> &full_ids,
+                                     const std::vector<uint8_t> &in_round, const std::vector<uint8_t> &pending);
 
 // ---- the shape rules of Batch::create (each pure: plain values in, no globals, no environment) ----
 

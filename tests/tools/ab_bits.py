@@ -4,7 +4,7 @@ kernel), and 8 x the 25,546-frame synthetic utterance + 3 distinct ones (lane-tr
 LDS-staged band solve, split excitation: the kernels of BASELINE config 2), f64 and the 16-bit sink.  Then the
 stages behind the vocoder: all eight rows of the output routing table (f64 / 16-bit sink x output
 rate x loudness target; FLAC on the 16-bit rows) on three ragged utterances, with the default geometry and with the
-redo-heavy one of the redo tests, and the entries on caller-held PCM on seeded input: three on long inputs, then
+redo-heavy one of the redo tests (each row with the run's redo counters), and the entries on caller-held PCM on seeded input: three on long inputs, then
 every one of their bodies on utterances of 0, 1, 1,025 and 5,000 samples -- the spectral stages (filterbank, cepstra,
 mel spectrogram) at every transform size class and both element types, the convolution in direct mode and at both
 partitioned transform sizes, the noise stage -- and the host halves of the spectral stages, which need no device.
@@ -135,12 +135,14 @@ def output_rows(vi, utts, geometry, label):
                             b.run()
                             b.sync()
                             ms.append(1e3 * (time.perf_counter() - t0))
-                        print(name, "n_redo", b.info()["n_redo"], "run+sync ms", " ".join(f"{x:.3f}" for x in ms))
+                        print(name, "n_redo", b.info()["n_redo"], "redo_stats", b.redo_stats(), "run+sync ms",
+                              " ".join(f"{x:.3f}" for x in ms))
                         continue
                     b.run()
                     b.sync()
                     read = b.pcm_i16 if i16 else b.pcm
-                    out = [name, "n_redo", b.info()["n_redo"], "n", [b.num_samples(i) for i in range(B)],
+                    out = [name, "n_redo", b.info()["n_redo"], "redo_stats", b.redo_stats(),
+                           "n", [b.num_samples(i) for i in range(B)],
                            "hz", [b.output_rate(i) for i in range(B)], "off", [b.pcm_offset(i) for i in range(B + 1)],
                            "pcm", digest([read(i) for i in range(B)]), "all", digest(b.pcm_all())]
                     if not i16 or rates or target:
