@@ -4,7 +4,7 @@
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
                                [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
                                [--fbank OUT.npy] [--mfcc OUT.npy] [--melspec OUT.npy [--whisper]] [--fir taps.npy [--fir-delay D]]
-                               [--noise bed.npy|white --snr DB]
+                               [--noise bed.npy|white --snr DB] [--room LX,LY,LZ --rt60 S [--room-taps K]]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
 batch and joined on the GPU (Engine.synthesize_programme) in front of the encoder, so a .flac output is one stream whose
@@ -13,7 +13,9 @@ written as a 16-bit WAV file.  With --loudness the chapter gets ONE gain (per-re
 keep their relative levels.  With --highpass a rumble and DC high-pass at that corner runs on the GPU in front of the
 loudness measurement and the encoder (Engine.set_filter).  With --fir every sentence is convolved on the GPU with the impulse
 response in that .npy file (taps at the output rate; --fir-delay removes its leading latency), in front of --highpass
-(Engine.set_fir).  With --noise every sentence gets background noise at --snr dB on the GPU, behind --fir and in front
+(Engine.set_fir).  With --room every sentence is reverberated on the GPU by a simulated shoebox room of those edges in
+metres with the reverberation time --rt60, in --fir's place, every sentence from positions of its own (Engine.set_room
+with vary=True, seed 0: jb_room_vary).  With --noise every sentence gets background noise at --snr dB on the GPU, behind --fir and in front
 of --highpass: the looped samples of that .npy file (at the output rate) or "white", every sentence from a place of
 its own in the bed (Engine.set_noise with vary=True); the pads between the sentences stay silent.  With --limiter (and --loudness) the chapter's gain may put its
 highest peak that many dB over the ceiling and a look-ahead limiter holds the ceiling on the GPU (Engine.set_limiter), so
@@ -50,6 +52,10 @@ ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high
 ap.add_argument("--noise", default=None, metavar="bed.npy|white",
                 help="background noise added to every sentence on the GPU at --snr (Engine.set_noise)")
 ap.add_argument("--snr", type=float, default=15.0, metavar="DB", help="speech power over added-noise power")
+ap.add_argument("--room", default=None, metavar="LX,LY,LZ",
+                help="edges of a simulated room in metres: every sentence reverberated on the GPU (Engine.set_room)")
+ap.add_argument("--rt60", type=float, default=0.5, metavar="S", help="reverberation time of --room")
+ap.add_argument("--room-taps", type=int, default=0, metavar="K", help="taps of --room's response (0: 1.2 rt60)")
 ap.add_argument("--fir", default=None, metavar="taps.npy",
                 help="impulse response at the output rate (a 1-D .npy), convolved with every sentence on the GPU (Engine.set_fir)")
 ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
@@ -73,6 +79,12 @@ if args.fir is not None:
     import numpy as np
 
     engine.set_fir(J.fir(np.load(args.fir), args.rate or engine.condition.get_sampling_frequency(), args.fir_delay))
+if args.room is not None:
+    hz = args.rate or engine.condition.get_sampling_frequency()
+    size = [float(v) for v in args.room.split(",")]
+    src, mic = J.room_vary(0, 0, size, 0.5)
+    engine.set_room(J.room(size, src, mic, rt60=args.rt60, hz=hz, n_taps=args.room_taps or int(1.2 * args.rt60 * hz)),
+                    vary=True, seed=0)
 if args.noise is not None:
     import numpy as np
 

@@ -5,6 +5,7 @@
                                  [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]] [--mfcc OUT.npy [--rate HZ]]
                                  [--melspec OUT.npy [--whisper | --rate HZ]]
                                  [--fir taps.npy [--fir-delay D]] [--noise bed.npy|white --snr DB [--snr-active]]
+                                 [--room LX,LY,LZ --rt60 S [--room-taps K]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
@@ -25,6 +26,9 @@ output rate and in front of the loudness measurement and every encoder above.
 With --fir the audio is convolved on the GPU with the impulse response in that .npy file (a 1-D array of taps sampled at
 the output rate: the voice's, or --rate), advanced by --fir-delay samples (Engine.set_fir): in front of --highpass, the
 loudness measurement and every encoder above.
+With --room the audio is reverberated on the GPU by a simulated shoebox room of those edges in metres with the
+reverberation time --rt60 (Engine.set_room: the image-source method, Eyring's coefficients; source and microphone from
+jb_room_vary with seed 0; --room-taps taps at the output rate, by default 1.2 rt60), in --fir's place.
 With --noise background noise is added on the GPU at --snr dB (Engine.set_noise): the samples of that .npy file (a 1-D
 array at the output rate, 16-bit units, looped) or, with "white", noise generated on the device; --snr-active measures
 the speech over its active tiles (within 20 dB of the mean power), not over the leading and trailing silence.  Behind
@@ -70,6 +74,9 @@ ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SE
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
 ap.add_argument("--fir", default=None, metavar="taps.npy", help="impulse response at the output rate, convolved on the GPU")
 ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
+ap.add_argument("--room", default=None, metavar="LX,LY,LZ", help="edges of a simulated room in metres, reverberated on the GPU")
+ap.add_argument("--rt60", type=float, default=0.4, metavar="S", help="reverberation time of --room")
+ap.add_argument("--room-taps", type=int, default=0, metavar="K", help="taps of --room's response (0: 1.2 rt60)")
 ap.add_argument("--noise", default=None, metavar="bed.npy|white", help="background noise, added on the GPU at --snr")
 ap.add_argument("--snr", type=float, default=15.0, metavar="DB", help="speech power over added-noise power")
 ap.add_argument("--snr-active", action="store_true", help="the speech power of the active tiles, not of the whole signal")
@@ -85,6 +92,13 @@ if args.fir is not None:
     if args.rate:
         engine.condition.set_output_sampling_frequency(args.rate)
     engine.set_fir(J.fir(np.load(args.fir), args.rate or engine.condition.get_sampling_frequency(), args.fir_delay))
+if args.room is not None:
+    if args.rate:
+        engine.condition.set_output_sampling_frequency(args.rate)
+    hz = args.rate or engine.condition.get_sampling_frequency()
+    size = [float(v) for v in args.room.split(",")]
+    src, mic = J.room_vary(0, 0, size, 0.5)
+    engine.set_room(J.room(size, src, mic, rt60=args.rt60, hz=hz, n_taps=args.room_taps or int(1.2 * args.rt60 * hz)))
 if args.noise is not None:
     import numpy as np
 

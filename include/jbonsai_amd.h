@@ -1284,6 +1284,110 @@ int jb_fir_pcm_batch_i16(const double *const *in, const size_t *n_in, size_t n, 
                          int32_t device, int16_t **out, size_t *n_out);
 void jb_fir_free(void *p);
 
+/* ---- Room responses (new: the reference has no such control) -------------------------------------------------------
+ * The impulse response of a shoebox room by the image-source method (Allen and Berkley, 1979), made on the device and
+ * installed as the convolution stage's request: "a different simulated room per utterance" without a second tool, a
+ * directory of responses or a host loop.  Everything behind the generator is the convolution stage, unchanged.
+ * - The room: edges size[3] in metres; source[3] and mic[3], strictly inside; reflection coefficients beta[6] in
+ *   (-1, 1), in the order x = 0, x = Lx, y = 0, y = Ly, z = 0, z = Lz; the speed of sound c (0: 343 m/s); the rate hz;
+ *   n_taps = K in 1..JB_FIR_MAX_TAPS; flags; reserved 0.  A room whose bytes are all zero is "no room for this
+ *   utterance" where one is given per utterance.
+ * - Constants: the low-pass interpolator's half-width Wh = JB_ROOM_WH = 32 samples, Q = JB_ROOM_Q = 128 table points
+ *   per sample.  The table (jb_room_lowpass) is F[q] = sinc(q / Q) w(q) for q = 0 .. Q Wh, with the Hann window
+ *   w(q) = (1 + cos(pi q / (Q Wh))) / 2, and 0 for the two entries above: Q Wh + 3 entries, made on the host in long
+ *   double and rounded once.  It is evaluated in the well-conditioned forms sinc(n + r) = (-1)^n sin(pi r) / (pi (n + r))
+ *   for q = n Q + r Q (exactly 0 where r = 0 < n, 1 at q = 0) and w(q) = sin^2(pi (Q Wh - q) / (2 Q Wh)).
+ * - Axis tables (host, long double, rounded once).  For the axis of length L, source s, microphone r and walls b0, b1:
+ *   n runs over -Na .. Na, Na = ceil(Rmax / 2L) + 1, Rmax = c (K + Wh) / hz, and p over {0, 1}; the coordinate is
+ *   D = ((1 - 2p) s + 2 n L) - r and the weight g = b0^|n - p| b1^|n| (x^0 = 1).  Entries whose g rounds to 0 are left
+ *   out; the rest are sorted by |D| ascending, ties by (n, p), and stored as the doubles D2 = D^2 and g.  More than
+ *   JB_ROOM_MAX_AXIS = 1024 entries on an axis: JB_ERR_UNSUPPORTED (three tables and F are staged in LDS together:
+ *   80 KiB of a CU's 160 KiB at the bound; a launch takes what its largest room needs).
+ * - Lookup: lp(t): u = |t| Q, i0 = floor(u), f = u - i0, lp = fma(f, F[i0 + 1] - F[i0], F[i0]).
+ * - Tap k, in one lane, in this order: acc = +0.0; then i ascends over the x table, inside it j over the y table,
+ *   inside it m over the z table: s2 = (D2x[i] + D2y[j]) + D2z[m], d = sqrt(s2), tau = d kappa (kappa = hz / c, long
+ *   double, rounded once), t = (double)k - tau; if |t| < Wh: A = ((gx[i] gy[j]) gz[m]) / (fourpi d) and
+ *   acc = fma(A, lp(t), acc).  With JB_ROOM_UNIT_DIRECT the divisor is d / d0 instead, d0 the same expression for the
+ *   three (n = 0, p = 0) entries: the direct path then has amplitude about 1 and a batch without a loudness target
+ *   keeps its level.  The direct index is floor(d0 kappa + 0.5).
+ * - A response's bits depend on the room alone: not on the call, the other rooms of a call, or the device's
+ *   scheduling.  jb_room_host visits every (i, j, m); the kernel skips entries only where the test |t| < Wh fails for
+ *   every tap of the workgroup (below).
+ * - Refused (JB_ERR_INVALID; jb_last_error names the room and the field) before any device is touched: an edge outside
+ *   [0.5, 1000] m, a position not strictly inside, |beta| >= 1 or a value that is not finite, c neither 0 nor in
+ *   [50, 5000], source and microphone closer than 1 cm, hz outside 1000..768000, K of 0 or above the cap, a direct
+ *   index >= K, an unknown flag, reserved != 0.  entries_x entries_y K above 2^32 for one room: JB_ERR_UNSUPPORTED
+ *   (a bound on the work of one room, to protect a shared card).
+ * - On the device (jb_room.hip, k_room): one lane per tap, workgroups of 256 consecutive taps of one room, a grid over
+ *   (tap tiles, distinct rooms); rooms equal by content are generated once.  The three tables and F are staged in
+ *   LDS.  A workgroup's taps k0 .. k0 + 255 reach d in ((k0 - Wh) / kappa, (k0 + 255 + Wh) / kappa); that band, as
+ *   squared distances and widened by 2^-30 of itself, ends the i and j loops at the first entry beyond it (the tables
+ *   are sorted) and, per (i, j), bounds the window of z entries by bisection on D2z, widened by one entry on either
+ *   side; inside the window every lane applies the exact test.  f64 throughout, explicit fma, no atomics.  A call
+ *   whose rooms together exceed a launch budget of 2^35 pair visits (entries_x entries_y K) is cut into several
+ *   launches by room: at the 3.3e10 to 9.0e10 pair visits a second of whole calls of 256 rooms
+ *   (profiles/r25_room.txt, written by tools/room_cost.py) a launch stays around a second at most.
+ * - jb_room_vary: the positions of the utterance of index k, uniform at least `margin` from every wall.  With mix the
+ *   splitmix64 finaliser of the noise and dither stages: z = mix(mix(seed) ^ k); attempt a = 0, 1, ..: coordinate j
+ *   (0..2: the source's x, y, z; 3..5: the microphone's) is margin + u (L - 2 margin) -- the product rounded, then the
+ *   sum -- with u = (mix(z + 6 a + j + 1) >> 11) 2^-53 and L its axis' edge; the first attempt whose source and
+ *   microphone are at least 1 cm apart is taken (64 attempts without one: JB_ERR_INVALID).  margin > 0 and
+ *   2 margin < every edge.
+ * Not covered: frequency-dependent absorption, directivity, rooms that are not shoeboxes, randomised image positions
+ * (Lehmann's fix of sweeping echoes), responses that stay on the device instead of passing through the host on their
+ * way to the convolution's spectra, more than one microphone per room. */
+#define JB_ROOM_UNIT_DIRECT 1u  /* flags: amplitudes relative to the direct path's */
+#define JB_ROOM_KEEP_LATENCY 2u /* flags: jb_batch_set_room installs the response with delay 0 */
+#define JB_ROOM_VARY 1u         /* jb_engine_set_room's flags: positions by jb_room_vary */
+#define JB_ROOM_WH 32u
+#define JB_ROOM_Q 128u
+#define JB_ROOM_MAX_AXIS 1024u
+typedef struct jb_room {
+    double size[3], source[3], mic[3], beta[6], c;
+    uint32_t hz, n_taps, flags, reserved;
+} jb_room;
+typedef struct jb_room_info {
+    double direct_distance; /* d0, metres */
+    uint64_t pair_visits;   /* entries_x entries_y K */
+    uint64_t workgroups;    /* ceil(K / 256) */
+    uint32_t entries[3];    /* of the x, y and z tables */
+    uint32_t direct_index;  /* floor(d0 kappa + 0.5) */
+} jb_room_info;
+typedef struct jb_room_report {
+    double energy;         /* sum of h[k]^2, ascending k, fused */
+    double drr_db;         /* 10 log10 of the energy within +-Wh of the direct index over the rest (+INFINITY: no rest) */
+    uint32_t direct_index;
+    uint32_t delay;        /* what the convolution was given: the direct index, or 0 with JB_ROOM_KEEP_LATENCY */
+} jb_room_report;
+/* New (none).  The rule on the host; no GPU is touched.  h must hold r->n_taps taps (cap below that: JB_ERR_BUFFER). */
+int jb_room_host(const jb_room *r, double *h, size_t cap);
+/* New (none).  The device seam: the responses of r[0..n) generated on `device` (-1 = current); h[u] = room u's
+ * n_h[u] = n_taps taps, library-owned (jb_room_free each).  Rooms equal by content are generated once and give the
+ * same bits. */
+int jb_room_rir_batch(const jb_room *r, size_t n, int32_t device, double **h, size_t *n_h);
+void jb_room_free(void *p);
+/* New (none).  Entries per axis, direct distance and index, pair visits and workgroups of a room; pure. */
+int jb_room_geometry(const jb_room *r, jb_room_info *out);
+/* New (none).  The table F (cap below Q Wh + 3 with F given: JB_ERR_BUFFER) and the two constants; each pointer may be
+ * NULL. */
+int jb_room_lowpass(double *F, size_t cap, uint32_t *Wh, uint32_t *Q);
+/* New (none).  Eyring's formula: alpha = 1 - exp(-(24 ln 10 / c) V / (S rt60)) with the volume V and the surface S,
+ * beta = sqrt(1 - alpha) on all six walls (long double, rounded once).  c 0: 343 m/s.  rt60 <= 0 or not finite, or an
+ * edge outside [0.5, 1000] m: JB_ERR_INVALID. */
+int jb_room_design(const double size[3], double rt60, double c, double beta[6]);
+/* New (none).  The positions of the utterance of index k (the rule above); pure. */
+int jb_room_vary(uint64_t seed, uint64_t k, const double size[3], double margin, double source[3], double mic[3]);
+/* New (none).  r[0..n): one room for the batch (n == 1) or one per utterance (n == jb_batch_size; all bytes zero: none
+ * for that utterance); NULL, 0 withdraws the request.  Before the first run only.  Each room's hz must equal its
+ * utterance's output rate (the convolution's check, made again by a later jb_batch_set_output_rate).  The distinct
+ * rooms are generated on the batch's device in this call and installed as the batch's convolution request with
+ * delay = the direct index (0 with JB_ROOM_KEEP_LATENCY).  The room request and jb_batch_set_fir share one slot: the
+ * later call replaces the earlier.  The same room gives the bits of jb_batch_set_fir with jb_room_rir_batch's taps. */
+int jb_batch_set_room(jb_batch *b, const jb_room *r, size_t n);
+/* New (none).  The response of utterance utt, from the taps jb_batch_set_room read back (host).  JB_ERR_INVALID where
+ * the utterance has no room. */
+int jb_batch_room_report(const jb_batch *b, size_t utt, jb_room_report *out);
+
 /* ---- Noise (new: the reference has no such control) ----------------------------------------------------------------
  * Background noise added to the PCM on the device at a target signal-to-noise ratio: a caller-given noise bed that is
  * looped, or white noise generated on the device, scaled so that speech power over added-noise power is the requested
@@ -1632,6 +1736,14 @@ int jb_engine_get_filter(const jb_engine *e, jb_filter *out);
  * (the default) = off: the output is unchanged.  Checked here at the engine's present output rate and again at
  * synthesis.  jb_engine_new copies it with the Condition. */
 int jb_engine_set_fir(jb_engine *e, const jb_fir *f);
+/* New.  The room of the audio the engine's entries return (see "Room responses"): wherever the engine's impulse
+ * response applies, in its place (jb_batch_set_room) -- the room and jb_engine_set_fir share one slot, the later call
+ * replaces the earlier.  flags: JB_ROOM_VARY or 0.  With JB_ROOM_VARY the utterance of index k in the call gets the
+ * positions jb_room_vary(seed, k, r->size, margin, ..) in the one room (r's own source and mic are not read; the
+ * generator's utterance has index 0); without it seed and margin are not read.  NULL (the default) = off: the output
+ * is unchanged.  Checked here at the engine's present output rate (with JB_ROOM_VARY: for index 0) and again at
+ * synthesis, where the rooms are generated on the batch's device.  jb_engine_new copies it with the Condition. */
+int jb_engine_set_room(jb_engine *e, const jb_room *r, uint32_t flags, uint64_t seed, double margin);
 /* New.  The noise of the audio the engine's entries return (see "Noise"): wherever the engine's impulse response
  * applies, behind it and in front of the filter's sections (jb_batch_set_noise) -- jb_synthesize, every
  * jb_synthesize_batch* and jb_synthesize_programme* form, the _each* forms (each engine's own request for its
@@ -2017,6 +2129,17 @@ JB_LAYOUT_ASSERT(sizeof(jb_filter_section) == 72 && offsetof(jb_filter_section, 
 JB_LAYOUT_ASSERT(sizeof(jb_fir) == 24 && offsetof(jb_fir, n_taps) == 8 && offsetof(jb_fir, hz) == 12 &&
                      offsetof(jb_fir, delay) == 16 && offsetof(jb_fir, reserved) == 20,
                  "jb_fir");
+JB_LAYOUT_ASSERT(sizeof(jb_room) == 144 && offsetof(jb_room, source) == 24 && offsetof(jb_room, mic) == 48 &&
+                     offsetof(jb_room, beta) == 72 && offsetof(jb_room, c) == 120 && offsetof(jb_room, hz) == 128 &&
+                     offsetof(jb_room, n_taps) == 132 && offsetof(jb_room, flags) == 136 &&
+                     offsetof(jb_room, reserved) == 140,
+                 "jb_room");
+JB_LAYOUT_ASSERT(sizeof(jb_room_info) == 40 && offsetof(jb_room_info, pair_visits) == 8 &&
+                     offsetof(jb_room_info, entries) == 24 && offsetof(jb_room_info, direct_index) == 36,
+                 "jb_room_info");
+JB_LAYOUT_ASSERT(sizeof(jb_room_report) == 24 && offsetof(jb_room_report, drr_db) == 8 &&
+                     offsetof(jb_room_report, direct_index) == 16 && offsetof(jb_room_report, delay) == 20,
+                 "jb_room_report");
 JB_LAYOUT_ASSERT(sizeof(jb_noise) == 64 && offsetof(jb_noise, seed) == 8 && offsetof(jb_noise, snr_db) == 16 &&
                      offsetof(jb_noise, gate_db) == 24 && offsetof(jb_noise, kind) == 32 &&
                      offsetof(jb_noise, bed_len) == 36 && offsetof(jb_noise, hz) == 40 &&

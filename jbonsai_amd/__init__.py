@@ -16,6 +16,8 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    Fir, fir, fir_geometry, fir_host, fir_pcm, FIR_MAX_TAPS, FIR_DIRECT_MAX, FIR_DIRECT, FIR_PARTITIONED,
                    Noise, NoiseReport, noise, noise_host, noise_white, noise_vary, noise_pcm, NOISE_BED, NOISE_WHITE,
                    NOISE_REF_WHOLE, NOISE_REF_ACTIVE, NOISE_VARY, NOISE_MAX_BED,
+                   Room, RoomInfo, RoomReport, room, room_host, room_rir, room_geometry, room_lowpass, room_design,
+                   room_vary, ROOM_UNIT_DIRECT, ROOM_KEEP_LATENCY, ROOM_VARY, ROOM_WH, ROOM_Q, ROOM_MAX_AXIS,
                    LimiterOpts, LimiterReport, LIMITER_EXACT, LIMITER_OFF, limiter, no_limiter, limiter_window,
                    limiter_host, limiter_pcm,
                    FbankOpts, FBANK_HANN, FBANK_HAMMING, FBANK_CENTER, FBANK_LINEAR, FBANK_UNIT, FBANK_F64, fbank,
@@ -48,7 +50,9 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "telephone_band", "no_filter", "Fir", "fir", "fir_geometry", "fir_host", "fir_pcm", "FIR_MAX_TAPS",
            "FIR_DIRECT_MAX", "FIR_DIRECT", "FIR_PARTITIONED", "Noise", "NoiseReport", "noise", "noise_host",
            "noise_white", "noise_vary", "noise_pcm", "NOISE_BED", "NOISE_WHITE", "NOISE_REF_WHOLE", "NOISE_REF_ACTIVE",
-           "NOISE_VARY", "NOISE_MAX_BED", "LimiterOpts", "LimiterReport", "LIMITER_EXACT", "LIMITER_OFF", "limiter",
+           "NOISE_VARY", "NOISE_MAX_BED", "Room", "RoomInfo", "RoomReport", "room", "room_host", "room_rir",
+           "room_geometry", "room_lowpass", "room_design", "room_vary", "ROOM_UNIT_DIRECT", "ROOM_KEEP_LATENCY",
+           "ROOM_VARY", "ROOM_WH", "ROOM_Q", "ROOM_MAX_AXIS", "LimiterOpts", "LimiterReport", "LIMITER_EXACT", "LIMITER_OFF", "limiter",
            "no_limiter", "limiter_window", "limiter_host", "limiter_pcm",
            "FbankOpts", "FBANK_HANN", "FBANK_HAMMING", "FBANK_CENTER", "FBANK_LINEAR", "FBANK_UNIT", "FBANK_F64", "fbank",
            "fbank_geometry", "fbank_window", "fbank_filterbank", "fbank_host", "fbank_pcm",

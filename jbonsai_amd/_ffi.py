@@ -494,6 +494,60 @@ def fir_array(firs, n=None):
     return arr, len(fs)
 
 
+ROOM_UNIT_DIRECT, ROOM_KEEP_LATENCY, ROOM_VARY, ROOM_WH, ROOM_Q, ROOM_MAX_AXIS = 1, 2, 1, 32, 128, 1024
+
+
+class Room(C.Structure):
+    """jb_room: a shoebox room -- edges, source and microphone in metres, the six walls' reflection coefficients (x = 0,
+    x = Lx, y = 0, y = Ly, z = 0, z = Lz), the speed of sound (0: 343 m/s), the rate and the number of taps."""
+    _fields_ = [("size", C.c_double * 3), ("source", C.c_double * 3), ("mic", C.c_double * 3),
+                ("beta", C.c_double * 6), ("c", C.c_double), ("hz", C.c_uint32), ("n_taps", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RoomInfo(C.Structure):
+    """jb_room_info: the direct distance and index, entries per axis, pair visits and workgroups of a room."""
+    _fields_ = [("direct_distance", C.c_double), ("pair_visits", C.c_uint64), ("workgroups", C.c_uint64),
+                ("entries", C.c_uint32 * 3), ("direct_index", C.c_uint32)]
+
+
+class RoomReport(C.Structure):
+    """jb_room_report: the taps' energy, the direct-to-reverberant ratio in dB, the direct index and the delay used."""
+    _fields_ = [("energy", C.c_double), ("drr_db", C.c_double), ("direct_index", C.c_uint32), ("delay", C.c_uint32)]
+
+
+def room(size, source, mic, beta=None, rt60=None, hz: int = 0, n_taps: int = 0, c: float = 343.0,
+         unit_direct: bool = True, keep_latency: bool = False):
+    """A Room of edges `size` with `source` and `mic` inside (metres).  Give exactly one of `beta` (one coefficient
+    for all six walls, or six) and `rt60` (seconds: Eyring's formula, room_design)."""
+    if (beta is None) == (rt60 is None):
+        raise ValueError("room: give exactly one of beta and rt60")
+    r = Room()
+    r.size[:], r.source[:], r.mic[:] = [float(v) for v in size], [float(v) for v in source], [float(v) for v in mic]
+    if rt60 is not None:
+        r.beta[:] = room_design(size, rt60, c)
+    else:
+        try:
+            r.beta[:] = [float(v) for v in beta]
+        except TypeError:
+            r.beta[:] = [float(beta)] * 6
+    r.c, r.hz, r.n_taps = float(c), int(hz), int(n_taps)
+    r.flags = (ROOM_UNIT_DIRECT if unit_direct else 0) | (ROOM_KEEP_LATENCY if keep_latency else 0)
+    return r
+
+
+def room_array(rooms, n=None):
+    """A (Room * n) array of Room entries (None: no room, all bytes zero); one entry stands for all n."""
+    rs = [rooms] if isinstance(rooms, Room) or rooms is None else list(rooms)
+    if n is not None and len(rs) == 1:
+        rs = rs * n
+    arr = (Room * max(1, len(rs)))()
+    for i, r in enumerate(rs):
+        if r is not None:
+            C.memmove(C.byref(arr[i]), C.byref(r), C.sizeof(Room))
+    return arr, len(rs)
+
+
 NOISE_BED, NOISE_WHITE, NOISE_REF_WHOLE, NOISE_REF_ACTIVE, NOISE_VARY, NOISE_MAX_BED = 0, 1, 0, 1, 1, 1 << 24
 
 
@@ -711,6 +765,8 @@ SYMBOLS = [
     "jb_filter_pcm_batch", "jb_filter_pcm_batch_i16", "jb_filter_free", "jb_engine_set_filter", "jb_engine_get_filter",
     "jb_batch_set_fir", "jb_batch_fir_geometry", "jb_engine_set_fir", "jb_fir_host", "jb_fir_geometry",
     "jb_fir_pcm_batch", "jb_fir_pcm_batch_i16", "jb_fir_free",
+    "jb_room_host", "jb_room_rir_batch", "jb_room_free", "jb_room_geometry", "jb_room_lowpass", "jb_room_design",
+    "jb_room_vary", "jb_batch_set_room", "jb_batch_room_report", "jb_engine_set_room",
     "jb_batch_set_noise", "jb_batch_noise_report", "jb_engine_set_noise", "jb_engine_get_noise", "jb_noise_host",
     "jb_noise_host_i16", "jb_noise_white", "jb_noise_vary", "jb_noise_pcm_batch", "jb_noise_pcm_batch_i16",
     "jb_noise_free",
@@ -1055,6 +1111,18 @@ def lib():
     L.jb_fir_pcm_batch_i16.argtypes = L.jb_fir_pcm_batch.argtypes
     L.jb_fir_free.argtypes = [vp]
     L.jb_fir_free.restype = None
+    rmp, d3 = C.POINTER(Room), C.POINTER(C.c_double)
+    L.jb_room_host.argtypes = [rmp, dp, sz]
+    L.jb_room_rir_batch.argtypes = [rmp, sz, C.c_int32, C.POINTER(vp), C.POINTER(sz)]
+    L.jb_room_free.argtypes = [vp]
+    L.jb_room_free.restype = None
+    L.jb_room_geometry.argtypes = [rmp, C.POINTER(RoomInfo)]
+    L.jb_room_lowpass.argtypes = [dp, sz, u32p, u32p]
+    L.jb_room_design.argtypes = [d3, C.c_double, C.c_double, d3]
+    L.jb_room_vary.argtypes = [C.c_uint64, C.c_uint64, d3, C.c_double, d3, d3]
+    L.jb_batch_set_room.argtypes = [vp, rmp, sz]
+    L.jb_batch_room_report.argtypes = [vp, sz, C.POINTER(RoomReport)]
+    L.jb_engine_set_room.argtypes = [vp, rmp, C.c_uint32, C.c_uint64, C.c_double]
     nzp, nrp = C.POINTER(Noise), C.POINTER(NoiseReport)
     L.jb_batch_set_noise.argtypes = [vp, nzp, sz]
     L.jb_batch_noise_report.argtypes = [vp, sz, nrp]
@@ -1826,6 +1894,61 @@ def fir_pcm(pcms, firs, hz, device: int = -1, i16: bool = False):
     ns = (C.c_size_t * max(1, n))()
     check((L.jb_fir_pcm_batch_i16 if i16 else L.jb_fir_pcm_batch)(ins, nin, n, farr, hzs, device, outs, ns))
     return _take(L.jb_fir_free, outs, ns, n, np.int16 if i16 else np.float64)
+
+
+def room_host(r):
+    """jb_room_host: the taps of Room r by the rule on the host (no GPU)."""
+    import numpy as np
+    h = np.empty(int(r.n_taps), dtype=np.float64)
+    check(lib().jb_room_host(C.byref(r), h.ctypes.data_as(C.POINTER(C.c_double)), h.size))
+    return h
+
+
+def room_rir(rooms, device: int = -1):
+    """jb_room_rir_batch: the taps of every Room of `rooms`, generated on the GPU; equal rooms are generated once."""
+    import numpy as np
+    L = lib()
+    rs = list(rooms)
+    arr, n = room_array(rs)
+    n = len(rs)
+    outs = (C.c_void_p * max(1, n))()
+    ns = (C.c_size_t * max(1, n))()
+    check(L.jb_room_rir_batch(arr, n, device, outs, ns))
+    return _take(L.jb_room_free, outs, ns, n, np.float64)
+
+
+def room_geometry(r):
+    """jb_room_geometry: the RoomInfo of Room r (pure)."""
+    info = RoomInfo()
+    check(lib().jb_room_geometry(C.byref(r), C.byref(info)))
+    return info
+
+
+def room_lowpass():
+    """jb_room_lowpass: (F, Wh, Q) -- the low-pass interpolator's table of Q Wh + 3 entries and its constants."""
+    import numpy as np
+    wh, q = C.c_uint32(), C.c_uint32()
+    check(lib().jb_room_lowpass(None, 0, C.byref(wh), C.byref(q)))
+    F = np.empty(wh.value * q.value + 3, dtype=np.float64)
+    check(lib().jb_room_lowpass(F.ctypes.data_as(C.POINTER(C.c_double)), F.size, None, None))
+    return F, wh.value, q.value
+
+
+def room_design(size, rt60: float, c: float = 343.0):
+    """jb_room_design: the six reflection coefficients of a room of edges `size` with the reverberation time rt60
+    (Eyring's formula)."""
+    s = (C.c_double * 3)(*[float(v) for v in size])
+    b = (C.c_double * 6)()
+    check(lib().jb_room_design(s, float(rt60), float(c), b))
+    return list(b)
+
+
+def room_vary(seed: int, k: int, size, margin: float = 0.5):
+    """jb_room_vary: (source, mic) of the utterance of index k, at least `margin` from every wall."""
+    s = (C.c_double * 3)(*[float(v) for v in size])
+    src, mic = (C.c_double * 3)(), (C.c_double * 3)()
+    check(lib().jb_room_vary(int(seed) & (2**64 - 1), int(k), s, float(margin), src, mic))
+    return list(src), list(mic)
 
 
 def noise_host(pcm, req, gain=None, i16: bool = False):

@@ -387,6 +387,23 @@ class Batch:
         arr, n = F.fir_array(firs)
         F.check(self._L.jb_batch_set_fir(self._h, arr, n))
 
+    def set_room(self, rooms):
+        """jb_batch_set_room: one F.Room (J.room(size, source, mic, rt60=..., hz=..., n_taps=...)) for the whole batch
+        or one per utterance (None in a list: no room); None withdraws the request.  Before the first run.  The rooms'
+        responses are generated on the batch's device in this call and installed in set_fir's place, advanced by the
+        direct path's index; the later of set_room and set_fir replaces the earlier."""
+        if rooms is None:
+            F.check(self._L.jb_batch_set_room(self._h, None, 0))
+            return
+        arr, n = F.room_array(rooms)
+        F.check(self._L.jb_batch_set_room(self._h, arr, n))
+
+    def room_report(self, i):
+        """jb_batch_room_report: the F.RoomReport of utterance i's room (direct index, delay, energy, DRR in dB)."""
+        r = F.RoomReport()
+        F.check(self._L.jb_batch_room_report(self._h, i, C.byref(r)))
+        return r
+
     def set_noise(self, reqs):
         """jb_batch_set_noise: one F.Noise (J.noise(bed, hz, snr_db, ...)) for the whole batch or one per utterance
         (None in a list: no request); None withdraws the request.  Before the first run.  The noise is added behind

@@ -2594,6 +2594,19 @@ int jb_batch_fir_geometry(const jb_batch *hb, size_t utt, uint32_t *mode, uint32
     return JB_OK;
 }
 
+int jb_batch_set_room(jb_batch *hb, const jb_room *r, size_t n)
+{
+    return hb ? ((Batch *)hb)->out.set_room(r, n) : JB_ERR_INVALID;
+}
+
+int jb_batch_room_report(const jb_batch *hb, size_t utt, jb_room_report *out)
+{
+    const Batch *b = (const Batch *)hb;
+    if (!b || !out || utt >= (size_t)b->B)
+        return JB_ERR_INVALID;
+    return b->out.read_room(utt, out);
+}
+
 int jb_batch_set_noise(jb_batch *hb, const jb_noise *req, size_t n)
 {
     return hb ? ((Batch *)hb)->out.set_noise(req, n) : JB_ERR_INVALID;

@@ -55,6 +55,22 @@ struct Condition {
     std::vector<double> fir_taps; // jb_engine_set_fir: the response's taps, copied (empty = off) ...
     uint32_t fir_hz = 0, fir_delay = 0; // ... its rate and delay
     jb_fir fir() const { return jb_fir{fir_taps.empty() ? nullptr : fir_taps.data(), (uint32_t)fir_taps.size(), fir_hz, fir_delay, 0}; }
+    bool room_on = false;         // jb_engine_set_room: a room is set (in the impulse response's slot) ...
+    jb_room room_req{};           // ... as it was given, with its flags, seed and margin
+    uint32_t room_flags = 0;
+    uint64_t room_seed = 0;
+    double room_margin = 0.0;
+    // the room of the utterance of index k in a call (all bytes zero: none); JB_ERR_INVALID from the varied positions
+    int room(uint64_t k, jb_room *out) const
+    {
+        *out = jb_room{};
+        if (!room_on)
+            return JB_OK;
+        *out = room_req;
+        if (room_flags & JB_ROOM_VARY)
+            return jb::room_vary(room_seed, k, room_req.size, room_margin, out->source, out->mic, "jb_engine_set_room");
+        return JB_OK;
+    }
     std::vector<double> noise_bed; // jb_engine_set_noise: the bed's samples, copied ...
     jb_noise noise_req{};         // ... and the request as it was given (its bed pointer is not kept: noise())
     jb_noise noise() const
@@ -1138,6 +1154,42 @@ int jb_engine_set_fir(jb_engine *e, const jb_fir *f)
     c.fir_taps.assign(f->taps, f->taps + f->n_taps);
     c.fir_hz = f->hz;
     c.fir_delay = f->delay;
+    c.room_on = false; // (one slot: the later call replaces the earlier)
+    return JB_OK;
+}
+int jb_engine_set_room(jb_engine *e, const jb_room *r, uint32_t flags, uint64_t seed, double margin)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    jb::Condition &c = ENG(e)->cond;
+    if (!r) {
+        c.room_on = false;
+        return JB_OK;
+    }
+    if (flags & ~JB_ROOM_VARY) {
+        jb::set_error("jb_engine_set_room: flags holds an unknown flag");
+        return JB_ERR_INVALID;
+    }
+    jb_room r0 = *r; // the room of index 0
+    int rc;
+    if ((flags & JB_ROOM_VARY) &&
+        (rc = jb::room_vary(seed, 0, r->size, margin, r0.source, r0.mic, "jb_engine_set_room")))
+        return rc;
+    if ((rc = jb::room_check(&r0, 0, "jb_engine_set_room", nullptr)))
+        return rc;
+    const size_t hz = c.output_rate ? c.output_rate : c.sampling_frequency;
+    if (r0.hz != (uint32_t)hz) {
+        jb::set_error("jb_engine_set_room: hz differs from the engine's output rate (a response is never resampled): " +
+                      std::to_string(r0.hz) + " Hz against " + std::to_string(hz) + " Hz");
+        return JB_ERR_INVALID;
+    }
+    c.room_on = true;
+    c.room_req = *r;
+    c.room_flags = flags;
+    c.room_seed = seed;
+    c.room_margin = margin;
+    c.fir_taps.clear(); // (one slot: the later call replaces the earlier)
+    c.fir_hz = c.fir_delay = 0;
     return JB_OK;
 }
 int jb_engine_set_noise(jb_engine *e, const jb_noise *req)
@@ -1713,7 +1765,17 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
         firs[u - lo] = eng(u)->cond.fir();
         any_fir = any_fir || firs[u - lo].taps;
     }
-    if (any_fir && (rc = out.set_fir(firs.data(), firs.size())))
+    // the room: each utterance's engine's own, in the response's slot; JB_ROOM_VARY varies the positions by the
+    // utterance's index in the call
+    std::vector<jb_room> rooms(hi - lo);
+    bool any_room = false;
+    for (size_t u = lo; u < hi; u++) {
+        if ((rc = eng(u)->cond.room(u, &rooms[u - lo])))
+            return rc;
+        any_room = any_room || eng(u)->cond.room_on;
+    }
+    if (any_room ? (rc = out.set_room(rooms.data(), rooms.size(), firs.data()))
+                 : (any_fir && (rc = out.set_fir(firs.data(), firs.size()))))
         return rc;
     // the noise: each utterance's engine's own; JB_NOISE_VARY varies by the utterance's index in the call
     std::vector<jb_noise> noises(hi - lo);
@@ -2542,6 +2604,11 @@ int jb_generator_new(const jb_engine *e, const char *const *lines, size_t n, jb_
     if (!CENG(e)->cond.fir_taps.empty()) {
         const jb_fir f = CENG(e)->cond.fir();
         if ((rc = b->out.set_fir(&f, 1)))
+            return rc;
+    }
+    if (CENG(e)->cond.room_on) {
+        jb_room rm;
+        if ((rc = CENG(e)->cond.room(0, &rm)) || (rc = b->out.set_room(&rm, 1)))
             return rc;
     }
     {

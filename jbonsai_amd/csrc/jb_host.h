@@ -15,6 +15,7 @@
 #include "jb_noise.h"
 #include "jb_output.h"
 #include "jb_pcm_call.h"
+#include "jb_room.h"
 
 #include <cmath>
 #include <map>
@@ -434,6 +435,25 @@ hipError_t launch_fir(const FirClass *classes_dev, const FirUtt *direct_dev, uin
                       const FirUtt *part_dev, uint32_t n_part, uint64_t blocks, uint64_t frames, double *spec,
                       hipStream_t stream);
 
+// Room responses (jb_room.hip; the rule, RoomTables and RoomDev: jb_room.h; the host half: jb_room.cpp).
+// The room `idx` of a call checked and its tables made (t may be null): JB_OK, JB_ERR_INVALID (set_error names the
+// room and the field) or JB_ERR_UNSUPPORTED (an axis table or the work above its bound); touches no device
+int room_check(const jb_room *r, size_t idx, const char *who, RoomTables *t);
+const std::vector<double> &room_lowpass(); // F: kRoomTable entries, made at the first call
+void room_host_taps(const RoomTables &t, double *h); // the rule on the host: h[0..K)
+jb_room_report room_report_of(const double *h, uint32_t K, uint32_t direct, uint32_t delay);
+// JB_ROOM_VARY's positions of the utterance of index k (JB_ERR_INVALID names what is wrong)
+int room_vary(uint64_t seed, uint64_t k, const double size[3], double margin, double source[3], double mic[3],
+              const char *who);
+// The responses of r[0..n) (room_none entries: left empty) generated on `device` (< 0: the current one): h[u] and,
+// where not null, tabs[u]; rooms equal by content are generated once
+int room_rirs(const jb_room *r, size_t n, int device, std::vector<std::vector<double>> *h,
+              std::vector<RoomTables> *tabs, const char *who);
+// k_room over rooms_dev[0..n) (their tables in `image`), `tiles` workgroups of taps per room at most; table_words:
+// the doubles of the largest room's three tables
+hipError_t launch_room(const RoomDev *rooms_dev, uint32_t n, uint32_t tiles, uint32_t table_words, const double *image,
+                       const double *F, double *out, hipStream_t stream);
+
 // The noise stage (jb_noise.hip; the rule, NoiseUtt and NoiseRecord: jb_noise.h; the host half: jb_noise.cpp).
 // req at the output rate `hz`: JB_OK, or JB_ERR_INVALID with set_error naming the utterance `utt` and the field
 int noise_check(const jb_noise *req, uint32_t hz, size_t utt, const char *who);
@@ -695,6 +715,11 @@ struct OutputChain {
     // f[0..n): n == 1 or B responses (nullptr, 0: the request is withdrawn; taps == NULL: none for that utterance),
     // each checked at its utterance's output rate and its taps copied; set_output_rate checks the rates again
     int set_fir(const jb_fir *f, size_t n);
+    // r[0..n): n == 1 or B rooms (nullptr, 0: the request is withdrawn; all bytes zero: none for that utterance, which
+    // then takes others[u] where `others` ([B], the engine entries) is given): generated on the batch's device here
+    // and installed in set_fir's slot, the later of the two calls replacing the earlier
+    int set_room(const jb_room *r, size_t n, const jb_fir *others = nullptr);
+    int read_room(size_t u, jb_room_report *out) const;
     // the geometry of utterance u's response (JB_ERR_INVALID: it has none)
     int fir_geometry_of(size_t u, FirGeom *g) const;
     // req[0..n): n == 1 or B requests (nullptr, 0: the request is withdrawn; no bed with JB_NOISE_BED: none for that
@@ -784,6 +809,8 @@ private:
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
     FirClasses fir_cls;                        // the distinct responses of the convolution request (its copies)
     std::vector<int32_t> fir_of;               // [B] an utterance's response in fir_cls, -1: none; empty: no request
+    std::vector<jb_room_report> room_rep;      // [B] what set_room read back; empty: no room made the slot's responses
+    std::vector<uint8_t> room_has;             // [B] 1 = that utterance's response is a room's
     NoiseBeds noise_beds;                      // the distinct beds of the noise request (its copies)
     std::vector<NoiseItem> noise_req;          // [B] the noise request, resolved; empty: none
     std::vector<uint8_t> stage_any;            // [B] 1 = a section, a response or a noise request: the plan's filter flag
@@ -955,6 +982,7 @@ private:
     int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
     int check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const;
     int check_fir(const std::vector<uint32_t> &want, const char *who) const; // the responses' rates under `want`
+    int install_fir(const jb_fir *f, size_t n, const char *who);             // set_fir's and set_room's common half
     int check_noise(const std::vector<uint32_t> &want, const char *who) const; // the beds' rates under `want`
     void flag_stage(); // stage_any of the three requests
     int check_settable(const char *after_run) const;

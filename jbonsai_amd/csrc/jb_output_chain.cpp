@@ -495,6 +495,7 @@ int OutputChain::set_fir(const jb_fir *f, size_t n)
     if (!f && n == 0) {
         fir_cls = FirClasses{};
         fir_of.clear();
+        room_rep.clear();
         replan();
         return JB_OK;
     }
@@ -503,9 +504,20 @@ int OutputChain::set_fir(const jb_fir *f, size_t n)
         set_error("jb_batch_set_fir: give one response, or one per utterance");
         return JB_ERR_INVALID;
     }
+    if ((rc = install_fir(f, n, "jb_batch_set_fir")))
+        return rc;
+    room_rep.clear(); // (the slot now holds a response that no room made)
+    return JB_OK;
+}
+
+// The convolution slot filled from f[0..n), n == 1 or B: checked at every utterance's output rate, the taps copied
+int OutputChain::install_fir(const jb_fir *f, size_t n, const char *who)
+{
+    int rc;
+    const size_t B = (size_t)b.B;
     const std::vector<uint32_t> hz = rates_under(want_hz);
     for (size_t u = 0; u < B; u++)
-        if ((rc = fir_check(&f[n == 1 ? 0 : u], hz[u], u, "jb_batch_set_fir")))
+        if ((rc = fir_check(&f[n == 1 ? 0 : u], hz[u], u, who)))
             return rc;
     FirClasses cls; // (the taps are copied here: the caller's buffers are not read again)
     std::vector<int32_t> of(B, -1);
@@ -532,6 +544,69 @@ int OutputChain::fir_geometry_of(size_t u, FirGeom *g) const
         return JB_ERR_INVALID;
     }
     *g = fir_cls.resp[(size_t)fir_of[u]].g;
+    return JB_OK;
+}
+
+int OutputChain::set_room(const jb_room *r, size_t n, const jb_fir *others)
+{
+    int rc = check_settable("jb_batch_set_room: the room is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!r && n == 0)
+        return set_fir(nullptr, 0);
+    const size_t B = (size_t)b.B;
+    if (!r || (n != 1 && n != B)) {
+        set_error("jb_batch_set_room: give one room, or one per utterance");
+        return JB_ERR_INVALID;
+    }
+    // every room and its rate first: a refused request has touched no device
+    const std::vector<uint32_t> hz = rates_under(want_hz);
+    std::vector<jb_room> rooms(B);
+    for (size_t u = 0; u < B; u++) {
+        rooms[u] = r[n == 1 ? 0 : u];
+        if (room_none(*(const RoomSpec *)&rooms[u]))
+            continue;
+        if ((rc = room_check(&rooms[u], u, "jb_batch_set_room", nullptr)))
+            return rc;
+        if (rooms[u].hz != hz[u]) {
+            set_error("jb_batch_set_room: utterance " + std::to_string(u) +
+                      ": hz differs from the utterance's output rate (a response is never resampled): " +
+                      std::to_string(rooms[u].hz) + " Hz against " + std::to_string(hz[u]) + " Hz");
+            return JB_ERR_INVALID;
+        }
+    }
+    std::vector<std::vector<double>> taps;
+    std::vector<RoomTables> tabs;
+    if ((rc = room_rirs(rooms.data(), B, b.device, &taps, &tabs, "jb_batch_set_room")))
+        return rc;
+    std::vector<jb_fir> firs(B, jb_fir{});
+    std::vector<jb_room_report> rep(B, jb_room_report{});
+    std::vector<uint8_t> has(B, 0);
+    for (size_t u = 0; u < B; u++) {
+        if (taps[u].empty()) {
+            if (others)
+                firs[u] = others[u];
+            continue;
+        }
+        const uint32_t delay = (rooms[u].flags & kRoomKeepLatency) ? 0u : tabs[u].direct;
+        firs[u] = jb_fir{taps[u].data(), (uint32_t)taps[u].size(), rooms[u].hz, delay, 0};
+        rep[u] = room_report_of(taps[u].data(), tabs[u].K, tabs[u].direct, delay);
+        has[u] = 1;
+    }
+    if ((rc = install_fir(firs.data(), B, "jb_batch_set_room")))
+        return rc;
+    room_rep = std::move(rep);
+    room_has = std::move(has);
+    return JB_OK;
+}
+
+int OutputChain::read_room(size_t u, jb_room_report *out) const
+{
+    if (u >= room_rep.size() || !room_has[u]) {
+        set_error("jb_batch_room_report: utterance " + std::to_string(u) + " has no room");
+        return JB_ERR_INVALID;
+    }
+    *out = room_rep[u];
     return JB_OK;
 }
 

@@ -214,6 +214,12 @@ class _Condition:
         """The impulse response (an _ffi.Fir: J.fir(taps, hz, delay)) of every entry's output, in front of the
         filter's sections; None for none.  The taps are copied."""
         F.check(self._L().jb_engine_set_fir(self._h(), None if f is None else C.byref(f)))
+    def set_room(self, room, vary=False, seed=0, margin=0.5):
+        """The room (an _ffi.Room: J.room(size, source, mic, rt60=..., hz=..., n_taps=...)) of every entry's output,
+        in the impulse response's place (the later of set_room and set_fir replaces the earlier); None for none.
+        vary: the utterance of index k in a call gets the positions J.room_vary(seed, k, size, margin)."""
+        F.check(self._L().jb_engine_set_room(self._h(), None if room is None else C.byref(room),
+                                             F.ROOM_VARY if vary else 0, int(seed) & (2**64 - 1), float(margin)))
     def set_noise(self, r):
         """The noise request (an _ffi.Noise: J.noise(bed, hz, snr_db, ...)) of every entry's output, behind the
         impulse response and in front of the filter's sections; None for none.  The bed is copied."""
@@ -324,6 +330,11 @@ class Engine:
     def set_fir(self, f):
         """jb_engine_set_fir (the Condition's setter, on the engine): an _ffi.Fir, or None for none."""
         self.condition.set_fir(f)
+
+    def set_room(self, room, vary=False, seed=0, margin=0.5):
+        """jb_engine_set_room (the Condition's setter, on the engine): an _ffi.Room, or None for none; vary: positions
+        of each utterance's own by J.room_vary(seed, k, size, margin)."""
+        self.condition.set_room(room, vary=vary, seed=seed, margin=margin)
 
     def set_noise(self, r):
         """jb_engine_set_noise (the Condition's setter, on the engine): an _ffi.Noise, or None for none."""
