@@ -3,7 +3,7 @@
     python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
                                [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
-                               [--fbank OUT.npy] [--mfcc OUT.npy] [--melspec OUT.npy [--whisper]] [--fir taps.npy [--fir-delay D]]
+                               [--fbank OUT.npy] [--mfcc OUT.npy] [--kaldi] [--melspec OUT.npy [--whisper]] [--fir taps.npy [--fir-delay D]]
                                [--noise bed.npy|white --snr DB] [--room LX,LY,LZ --rt60 S [--room-taps K]]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
@@ -61,6 +61,7 @@ ap.add_argument("--fir", default=None, metavar="taps.npy",
 ap.add_argument("--fir-delay", type=int, default=0, metavar="D", help="samples the convolved output is advanced by")
 ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="the chapter's log-mel filterbank frames from the GPU, instead of the audio")
 ap.add_argument("--mfcc", default=None, metavar="OUT.npy", help="the chapter's MFCC + deltas + CMVN rows from the GPU, instead of the audio")
+ap.add_argument("--kaldi", action="store_true", help="with --fbank or --mfcc: Kaldi's frame conditioning and defaults (J.kaldi_frame)")
 ap.add_argument("--melspec", default=None, metavar="OUT.npy", help="the chapter's mel spectrogram (librosa / Whisper convention) from the GPU, instead of the audio")
 ap.add_argument("--whisper", action="store_true", help="with --melspec: Whisper's front end; sets the output rate to 16 kHz")
 args = ap.parse_args()
@@ -103,13 +104,22 @@ join = dict(lead_ms=args.lead_ms, gap_ms=args.gap_ms, trail_ms=args.trail_ms, fa
 if args.fbank:
     import numpy as np
 
-    feats, starts = engine.synthesize_programme(sentences, sink="fbank", **join)
+    kaldi = {}
+    if args.kaldi:  # DC removal, pre-emphasis 0.97, the Povey window, 23 filters from 20 Hz
+        kaldi["opts"], fr = J.kaldi_frame()
+        engine.set_frame(fr)
+    feats, starts = engine.synthesize_programme(sentences, sink="fbank", **kaldi, **join)
     np.save(args.fbank, feats)
     print(f"wrote {args.fbank}: {feats.shape[0]} frames of {feats.shape[1]} log-mel values at {hz} Hz")
 elif args.mfcc:
     import numpy as np
 
-    feats, starts = engine.synthesize_programme(sentences, sink="mfcc", delta_order=2, cmvn="mean_var", **join)
+    kaldi = {}
+    if args.kaldi:  # ... and the frame's log energy as c0
+        kaldi["fbank"], fr = J.kaldi_frame()
+        fr.flags |= J.FRAME_ENERGY
+        engine.set_frame(fr)
+    feats, starts = engine.synthesize_programme(sentences, sink="mfcc", delta_order=2, cmvn="mean_var", **kaldi, **join)
     np.save(args.mfcc, feats)
     print(f"wrote {args.mfcc}: {feats.shape[0]} frames of {feats.shape[1]} cepstral values at {hz} Hz")
 elif args.melspec:

@@ -2,7 +2,7 @@
 
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak] [--limiter DB]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
-                                 [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]] [--mfcc OUT.npy [--rate HZ]]
+                                 [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]] [--mfcc OUT.npy [--rate HZ]] [--kaldi]
                                  [--melspec OUT.npy [--whisper | --rate HZ]]
                                  [--fir taps.npy [--fir-delay D]] [--noise bed.npy|white --snr DB [--snr-active]]
                                  [--room LX,LY,LZ --rt60 S [--room-taps K]]
@@ -37,6 +37,9 @@ With --fbank the sentence's log-mel filterbank frames (25 ms windows every 10 ms
 computed on the GPU from the final PCM, at --rate if given, and saved as a .npy file; no WAV file is written.
 With --mfcc the same frames go on, still on the GPU, to 13 liftered cepstra with delta and delta-delta rows, mean and
 variance normalised over the sentence (float32 [T, 39]), saved the same way.
+With --kaldi beside --fbank or --mfcc the frames are conditioned as Kaldi's compute-fbank-feats does it, still on the GPU
+(Engine.set_frame, J.kaldi_frame): per-frame DC removal, pre-emphasis 0.97, the Povey window, 20 Hz to half the rate,
+23 filters; the cepstra then carry the frame's log energy as c0.
 With --melspec the sentence's mel spectrogram in the librosa / Whisper convention -- a centred, reflected 25 ms Hann
 window every 10 ms, 80 Slaney filters, natural logarithm, float32 [T, 80] -- is computed on the GPU from the final PCM,
 at --rate if given; with --whisper it is Whisper's own front end (400 / 160 samples at 16 kHz, log10 clamped 8 under the
@@ -68,6 +71,7 @@ ap.add_argument("--adpcm", action="store_true", help="IMA ADPCM (4-bit) WAV file
 ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate (with --adpcm, --fbank, --mfcc or --melspec)")
 ap.add_argument("--fbank", default=None, metavar="OUT.npy", help="log-mel filterbank frames, computed on the GPU")
 ap.add_argument("--mfcc", default=None, metavar="OUT.npy", help="MFCC + deltas + CMVN rows, computed on the GPU")
+ap.add_argument("--kaldi", action="store_true", help="with --fbank or --mfcc: Kaldi's frame conditioning and defaults")
 ap.add_argument("--melspec", default=None, metavar="OUT.npy", help="mel spectrogram (librosa / Whisper convention), computed on the GPU")
 ap.add_argument("--whisper", action="store_true", help="with --melspec: Whisper's front end at 16 kHz")
 ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
@@ -137,7 +141,12 @@ if args.fbank:
 
     if args.rate:
         engine.condition.set_output_sampling_frequency(args.rate)
-    feats = engine.synthesize_fbank(SAMPLE_SENTENCE_2)
+    if args.kaldi:
+        fopts, fr = J.kaldi_frame()
+        engine.set_frame(fr)
+        feats = engine.synthesize_fbank(SAMPLE_SENTENCE_2, fopts)
+    else:
+        feats = engine.synthesize_fbank(SAMPLE_SENTENCE_2)
     np.save(args.fbank, feats)
     hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
     print(f"wrote {args.fbank}: {feats.shape[0]} frames of {feats.shape[1]} log-mel values at {hz} Hz")
@@ -147,7 +156,13 @@ if args.mfcc:
 
     if args.rate:
         engine.condition.set_output_sampling_frequency(args.rate)
-    feats = engine.synthesize_mfcc(SAMPLE_SENTENCE_2, delta_order=2, cmvn="mean_var")
+    if args.kaldi:
+        fopts, fr = J.kaldi_frame()
+        fr.flags |= J.FRAME_ENERGY
+        engine.set_frame(fr)
+        feats = engine.synthesize_mfcc(SAMPLE_SENTENCE_2, fbank=fopts, delta_order=2, cmvn="mean_var")
+    else:
+        feats = engine.synthesize_mfcc(SAMPLE_SENTENCE_2, delta_order=2, cmvn="mean_var")
     np.save(args.mfcc, feats)
     hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
     print(f"wrote {args.mfcc}: {feats.shape[0]} frames of {feats.shape[1]} cepstral values at {hz} Hz")

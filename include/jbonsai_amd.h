@@ -178,6 +178,24 @@ typedef struct jb_mfcc_opts {
     uint32_t flags;        /* JB_MFCC_F64 */
     uint32_t reserved[3];
 } jb_mfcc_opts;
+/* New.  Frame conditioning (jb_batch_set_frame_opts, jb_engine_set_frame_opts, the _framed entries; see "Frame
+ * conditioning" below): what makes a frame of the filterbank and cepstral stages Kaldi's.  It stands beside a
+ * jb_fbank_opts (and a jb_mfcc_opts), as the cepstral options stand beside the filterbank's.  All zero = the identity;
+ * reserved 0.  Anything outside the limits of that section: JB_ERR_INVALID, naming the field, before any device is
+ * touched.  jb_frame_kaldi fills in compute-fbank-feats' defaults. */
+#define JB_FRAME_WINDOW_OPTS 0u /* the window of the jb_fbank_opts, unchanged */
+#define JB_FRAME_POVEY 1u       /* (0.5 - 0.5 cos(a j))^0.85,  a = 2 pi / (wl - 1) */
+#define JB_FRAME_HANN_SYM 2u    /* 0.5 - 0.5 cos(a j)   (Kaldi's "hanning") */
+#define JB_FRAME_RECT 3u        /* 1 */
+#define JB_FRAME_BLACKMAN 4u    /* 0.42 - 0.5 cos(a j) + 0.08 cos(2 a j) */
+#define JB_FRAME_REMOVE_DC 1u   /* flags */
+#define JB_FRAME_REFLECT 2u     /* flags: Kaldi's snip_edges = false */
+#define JB_FRAME_ENERGY 4u      /* flags: behind an mfcc request with n_ceps >= 1, c0 is the frame's log energy */
+typedef struct jb_frame_opts {
+    double preemph; /* c in [0, 1]; 0: none */
+    uint32_t window, flags;
+    uint32_t reserved[4]; /* 0 */
+} jb_frame_opts;
 /* New.  Mel spectrogram options (jb_batch_set_melspec, jb_melspec_pcm_batch, jb_melspec_host, jb_synthesize*_melspec;
  * see "Mel spectrograms" below).  Window and hop in samples at the unit's own rate; win_length 0 = n_fft; f_max_hz 0 =
  * half the rate; floor 0 = 1e-10; range 0 = no clamp; scale 0 = 1.0; reserved 0.  Anything outside the limits of that
@@ -610,6 +628,12 @@ int jb_batch_read_fbank_all(jb_batch *b, uint8_t *const *dst);
  * request.  Independent of jb_batch_set_fbank, which keeps its own slab and bytes; behind a join the units are the
  * programmes, and the CMVN runs over the whole programme. */
 int jb_batch_set_mfcc(jb_batch *b, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts);
+/* New.  The frame request beside jb_batch_set_fbank's and jb_batch_set_mfcc's (see "Frame conditioning" below): both
+ * stages condition their frames by it.  Before the first run, in either order with the two; the pair is checked when
+ * both are present and again at the first run, where a request without an fbank or mfcc request is JB_ERR_INVALID.
+ * NULL withdraws the request.  jb_batch_fbank_shape, jb_batch_mfcc_shape and the byte sinks' sizes report the reflected
+ * T under JB_FRAME_REFLECT. */
+int jb_batch_set_frame_opts(jb_batch *b, const jb_frame_opts *fr);
 /* Unit `unit`'s frames, row width d (delta_order + 1) and rate, known once the request is made; any out pointer may be
  * NULL. */
 int jb_batch_mfcc_shape(jb_batch *b, size_t unit, size_t *T, uint32_t *width, uint32_t *hz);
@@ -972,8 +996,8 @@ void jb_adpcm_free(uint8_t *p);
  *   of everything 430 ms (the f64 samples: 353 ms): the read is one pageable copy.  Against the long double model the
  *   device's error is 1.00 to 1.25 times (3.88 with one filter alone) that of a float64 rfft of the same frames.
  * Not covered: the Slaney mel scale, reflection padding and magnitude instead of power (these are the "Mel
- * spectrograms" stage below); pre-emphasis, dither and per-frame DC removal (no Kaldi bit-compatibility is claimed); the generator, the _multi entries
- * and jb_gather_pcm; 16-bit batches; per-utterance options within one batch;
+ * spectrograms" stage below); dither (pre-emphasis, per-frame DC removal, the symmetric windows and reflected edges are
+ * the "Frame conditioning" section below); the generator, the _multi entries and jb_gather_pcm; 16-bit batches; per-utterance options within one batch;
  * reading through the pinned ring (the read is one pageable copy). */
 /* wl, hop, n_fft of the options at hz and T and bytes of n samples; any out pointer may be NULL. */
 int jb_fbank_geometry(uint32_t hz, const jb_fbank_opts *opts, size_t n, uint32_t *wl, uint32_t *hop, uint32_t *n_fft,
@@ -1027,10 +1051,9 @@ void jb_fbank_free(uint8_t *p);
  * feature slab.  A redo round recomputes every unit it touched whole, statistics included, so the rows are the seam's
  * on the final PCM, and JB_BATCH_INVARIANT output stays invariant.
  * Not covered: sharing one filterbank pass between an fbank and an mfcc request; 16-bit batches; reading through the
- * pinned ring (the read is one pageable copy); frame energy in
- * place of c0; HTK's unnormalised DCT; sliding-window or global (corpus) CMVN; pre-emphasis, DC removal and the Povey
- * window (no Kaldi bit-compatibility is claimed; a whole-signal pre-emphasis is a two-tap jb_batch_set_fir); fusing the
- * DCT into the filterbank kernel; the generator, the _multi entries and jb_gather_pcm. */
+ * pinned ring (the read is one pageable copy); HTK's unnormalised DCT; sliding-window or global (corpus) CMVN; fusing
+ * the DCT into the filterbank kernel (frame energy in place of c0, pre-emphasis, DC removal and the Povey window are
+ * the "Frame conditioning" section below); the generator, the _multi entries and jb_gather_pcm. */
 /* T (the filterbank's), the row width d (delta_order + 1) and the bytes of n samples at hz; any out pointer may be
  * NULL. */
 int jb_mfcc_geometry(uint32_t hz, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, size_t n, size_t *T,
@@ -1055,6 +1078,68 @@ int jb_mfcc_pcm_batch(const double *const *in, const size_t *n_in, size_t n, con
                       const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, int32_t device, uint8_t **out,
                       size_t *n_bytes);
 void jb_mfcc_free(uint8_t *p);
+
+/* ---- Frame conditioning (new: the reference hands out samples only; none of these entries has a counterpart) ----------
+ * What a Kaldi, lhotse or WeNet recipe does to a frame in front of the transform (Kaldi's ExtractWindow / ProcessWindow,
+ * without dither), as a request (jb_frame_opts) beside the filterbank and cepstral options.  For one frame of wl values
+ * of a unit of n samples, in this order:
+ * 1. Samples.  v_i = x[k(i)] * scale; the scale is JB_FBANK_UNIT's, applied first.  Without JB_FRAME_REFLECT the frame
+ *    starts, T and the zeros outside the unit are the filterbank stage's (snip, or JB_FBANK_CENTER).  With it T =
+ *    (n + hop / 2) / hop, frame t starts at t hop + hop / 2 - wl / 2 (integer divisions), and an index k outside [0, n)
+ *    is mapped by k < 0 ? -k - 1 : 2 n - 1 - k, repeated until it lies inside (a unit shorter than half a window
+ *    reflects more than once).  JB_FRAME_REFLECT together with JB_FBANK_CENTER is refused, naming `flags`.
+ * 2. DC (JB_FRAME_REMOVE_DC).  p_j (j = 0..63) is the sum of v_i over i = j (mod 64), from 0.0 in ascending i; then for
+ *    w = 32, 16, .., 1: p_j = p_j + p_{j+w} for j < w; mean = p_0 / (double)wl (a division: a constant integer-valued
+ *    frame gives exactly its value); v_i -= mean.  In JB_FBANK_CENTER mode the padded zeros belong to the frame.  The
+ *    order is a function of wl alone, not of n_fft or of the lanes that share the frame.
+ * 3. Energy (JB_FRAME_ENERGY).  e = sum v_i^2 in the order of step 2, each square rounded on its own: the "raw" energy,
+ *    after DC removal, before pre-emphasis and the window.
+ * 4. Pre-emphasis (preemph = c > 0).  y_0 = v_0 - c v_0, y_i = v_i - c v_{i-1}, from the values of step 2; the product
+ *    is rounded, then the difference (no contraction).
+ * 5. Window.  z_i = w_i y_i; the table is made on the host in long double and rounded once (jb_frame_window).
+ *    JB_FRAME_WINDOW_OPTS gives the jb_fbank_opts window's table bit for bit.
+ * Spectrum, filterbank, floor, logarithm and element type follow unchanged ("Filterbank features").  With
+ * JB_FRAME_ENERGY, c[t][0] = ln(max(e, log_floor)) replaces the DCT's row 0 in front of CMVN and the deltas; the
+ * lifter's l_0 is 1.
+ * Refused, naming the field, before any device is touched: JB_FRAME_ENERGY with an fbank request or with n_ceps = 0
+ * (`flags`); an unknown window or flag; a reserved word that is not 0; preemph outside [0, 1] or not finite.
+ * An all-zero jb_frame_opts is the identity: every entry that takes one then returns the bytes of its counterpart
+ * without it.  Determinism is the filterbank stage's: a frame's values depend on its own samples, hz and the options
+ * only, so the seams, the batch path, redo rounds and any batch give the same bits.
+ * Cost on 256 x 128 s at 25 / 10 ms and 80 filters (profiles/r27_frame.txt), Povey window, DC removal and pre-emphasis
+ * 0.97: k_fbank takes 55.3 ms of device time at 48 kHz against 43.9 ms without the request (3.27 million frames of 2048
+ * points, two waves a frame: 16.9 against 13.4 ns a frame, 1.26 times) and 15.1 against 11.4 ms behind the converter at
+ * 16 kHz (n_fft 512: 1.32 times); the cepstral stage with the energy 62.3 against 46.5 ms.  What it pays for: two more
+ * barriers and one more LDS round trip per frame.  Without a request the kernel is the one it was (43.9 ms; the default
+ * step 77.63 ms against the parent's 77.60 ms, medians of three alternating runs, 77.55 .. 77.77 ms in all).  Against the
+ * long double model the device's error is 0.59 to 3.04 times that of a float64 numpy model of the same frames (the host
+ * form's: at most 3.61; gate 8).
+ * Not claimed: bit-compatibility with Kaldi (Kaldi works in f32 and truncates the window length where this stage rounds
+ * it); dither (the noise stage adds white noise to the whole signal instead); an energy column on the fbank sink;
+ * raw_energy = false; the melspec stage does not read the request. */
+/* compute-fbank-feats' defaults with n_mels filters (23 there) into *f and *fr: 25 / 10 ms, the Povey window, DC
+ * removal, pre-emphasis 0.97, f_min 20 Hz, floor 2^-23, snip framing, no energy. */
+int jb_frame_kaldi(uint32_t n_mels, jb_fbank_opts *f, jb_frame_opts *fr);
+/* The request beside the options it conditions: fopts, and mopts for an mfcc request (NULL: an fbank request). */
+int jb_frame_check(const jb_fbank_opts *fopts, const jb_mfcc_opts *mopts, const jb_frame_opts *fr);
+/* jb_fbank_geometry with the request: T and the bytes are the reflected ones under JB_FRAME_REFLECT. */
+int jb_fbank_framed_geometry(uint32_t hz, const jb_fbank_opts *opts, const jb_frame_opts *fr, size_t n, uint32_t *wl,
+                             uint32_t *hop, uint32_t *n_fft, size_t *T, size_t *n_bytes);
+/* The window of step 5 (wl doubles; cap below that: JB_ERR_BUFFER). */
+int jb_frame_window(uint32_t hz, const jb_fbank_opts *opts, const jb_frame_opts *fr, double *w, size_t cap);
+/* The rule on the host (jb_fbank_host's and jb_mfcc_pcm_host's twins); no GPU is touched. */
+int jb_fbank_framed_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *opts, const jb_frame_opts *fr,
+                         uint8_t *out, size_t cap);
+int jb_mfcc_framed_pcm_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *fopts,
+                            const jb_mfcc_opts *opts, const jb_frame_opts *fr, uint8_t *out, size_t cap);
+/* The stages on PCM the caller holds (jb_fbank_pcm_batch's and jb_mfcc_pcm_batch's twins); out[u] is library-owned
+ * (jb_fbank_free, jb_mfcc_free). */
+int jb_fbank_framed_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                              const jb_fbank_opts *opts, const jb_frame_opts *fr, int32_t device, uint8_t **out,
+                              size_t *n_bytes);
+int jb_mfcc_framed_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                             const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, const jb_frame_opts *fr,
+                             int32_t device, uint8_t **out, size_t *n_bytes);
 
 /* ---- Mel spectrograms (new: the reference hands out samples only; none of these entries has a counterpart) ------------
  * The filterbank stage above speaks Kaldi / HTK.  Everything neural reads the other dialect -- what librosa's
@@ -1736,6 +1821,11 @@ int jb_engine_get_filter(const jb_engine *e, jb_filter *out);
  * (the default) = off: the output is unchanged.  Checked here at the engine's present output rate and again at
  * synthesis.  jb_engine_new copies it with the Condition. */
 int jb_engine_set_fir(jb_engine *e, const jb_fir *f);
+/* New.  The frame request of the features the engine's entries return (see "Frame conditioning"): read by every later
+ * *_fbank and *_mfcc synthesis entry, _batch, _each and _programme included (the engines of one _each call must agree).
+ * Checked here on its own and beside the entry's options at synthesis.  NULL (the default) = none.  jb_engine_new copies
+ * it with the Condition. */
+int jb_engine_set_frame_opts(jb_engine *e, const jb_frame_opts *fr);
 /* New.  The room of the audio the engine's entries return (see "Room responses"): wherever the engine's impulse
  * response applies, in its place (jb_batch_set_room) -- the room and jb_engine_set_fir share one slot, the later call
  * replaces the earlier.  flags: JB_ROOM_VARY or 0.  With JB_ROOM_VARY the utterance of index k in the call gets the
@@ -2104,6 +2194,9 @@ JB_LAYOUT_ASSERT(sizeof(jb_fbank_opts) == 64 && offsetof(jb_fbank_opts, n_fft) =
                      offsetof(jb_fbank_opts, f_min_hz) == 16 && offsetof(jb_fbank_opts, log_floor) == 32 &&
                      offsetof(jb_fbank_opts, window) == 40 && offsetof(jb_fbank_opts, reserved) == 48,
                  "jb_fbank_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_frame_opts) == 32 && offsetof(jb_frame_opts, window) == 8 &&
+                     offsetof(jb_frame_opts, flags) == 12 && offsetof(jb_frame_opts, reserved) == 16,
+                 "jb_frame_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_melspec_opts) == 96 && offsetof(jb_melspec_opts, f_min_hz) == 16 &&
                      offsetof(jb_melspec_opts, floor) == 32 && offsetof(jb_melspec_opts, range) == 40 &&
                      offsetof(jb_melspec_opts, offset) == 48 && offsetof(jb_melspec_opts, mel_scale) == 64 &&

@@ -24,6 +24,9 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    fbank_geometry, fbank_window, fbank_filterbank, fbank_host, fbank_pcm,
                    MfccOpts, CMVN_NONE, CMVN_MEAN, CMVN_MEAN_VAR, MFCC_F64, mfcc, mfcc_geometry,
                    mfcc_dct, mfcc_delta_kernel, mfcc_host, mfcc_pcm_host, mfcc_frames, mfcc_pcm,
+                   FrameOpts, FRAME_WINDOW_OPTS, FRAME_POVEY, FRAME_HANN_SYM, FRAME_RECT, FRAME_BLACKMAN,
+                   FRAME_REMOVE_DC, FRAME_REFLECT, FRAME_ENERGY, frame, kaldi_frame, fbank_framed_geometry,
+                   frame_window, fbank_framed_host, fbank_framed_pcm, mfcc_framed_pcm_host, mfcc_framed_pcm,
                    MelspecOpts, MEL_HTK, MEL_SLANEY, MEL_NORM_NONE, MEL_NORM_SLANEY, MEL_PAD_REFLECT, MEL_PAD_ZERO,
                    MEL_PAD_NONE, MEL_LOG_NONE, MEL_LOG_LN, MEL_LOG_LOG10, MEL_LOG_DB, MEL_MAGNITUDE, MEL_DROP_LAST,
                    MEL_F64, melspec, whisper_mel, melspec_geometry, melspec_window, melspec_filterbank, melspec_host,
@@ -56,6 +59,9 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "no_limiter", "limiter_window", "limiter_host", "limiter_pcm",
            "FbankOpts", "FBANK_HANN", "FBANK_HAMMING", "FBANK_CENTER", "FBANK_LINEAR", "FBANK_UNIT", "FBANK_F64", "fbank",
            "fbank_geometry", "fbank_window", "fbank_filterbank", "fbank_host", "fbank_pcm",
+           "FrameOpts", "FRAME_WINDOW_OPTS", "FRAME_POVEY", "FRAME_HANN_SYM", "FRAME_RECT", "FRAME_BLACKMAN",
+           "FRAME_REMOVE_DC", "FRAME_REFLECT", "FRAME_ENERGY", "frame", "kaldi_frame", "fbank_framed_geometry",
+           "frame_window", "fbank_framed_host", "fbank_framed_pcm", "mfcc_framed_pcm_host", "mfcc_framed_pcm",
            "synthesize_batch_each_fbank",
            "MfccOpts", "CMVN_NONE", "CMVN_MEAN", "CMVN_MEAN_VAR", "MFCC_F64", "mfcc", "mfcc_geometry",
            "mfcc_dct", "mfcc_delta_kernel", "mfcc_host", "mfcc_pcm_host", "mfcc_frames", "mfcc_pcm",

@@ -232,6 +232,36 @@ def fbank(win_ms: float = 25, hop_ms: float = 10, n_mels: int = 80, n_fft: int =
     return o
 
 
+FRAME_WINDOW_OPTS, FRAME_POVEY, FRAME_HANN_SYM, FRAME_RECT, FRAME_BLACKMAN = 0, 1, 2, 3, 4
+FRAME_REMOVE_DC, FRAME_REFLECT, FRAME_ENERGY = 1, 2, 4
+
+
+class FrameOpts(C.Structure):
+    """jb_frame_opts: Kaldi-style conditioning of each frame in front of the transform -- the pre-emphasis coefficient,
+    the window (FRAME_WINDOW_OPTS: the FbankOpts' own) and FRAME_* flags.  All zero: the identity."""
+    _fields_ = [("preemph", C.c_double), ("window", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+def frame(preemph: float = 0.0, window=None, remove_dc: bool = False, reflect: bool = False, energy: bool = False):
+    """FrameOpts: per-frame DC removal, pre-emphasis y_i = v_i - preemph * v_{i-1} and the window "povey", "hann_sym",
+    "rect" or "blackman" (None: the FbankOpts' own); reflect: Kaldi's snip_edges = false; energy: behind an mfcc
+    request, c0 is the frame's log energy."""
+    o = FrameOpts()
+    o.preemph = float(preemph)
+    names = {None: FRAME_WINDOW_OPTS, "povey": FRAME_POVEY, "hann_sym": FRAME_HANN_SYM, "rect": FRAME_RECT,
+             "blackman": FRAME_BLACKMAN}
+    o.window = names[window] if window is None or isinstance(window, str) else int(window)
+    o.flags = FRAME_REMOVE_DC * bool(remove_dc) | FRAME_REFLECT * bool(reflect) | FRAME_ENERGY * bool(energy)
+    return o
+
+
+def kaldi_frame(n_mels: int = 23):
+    """jb_frame_kaldi: (FbankOpts, FrameOpts) of compute-fbank-feats' defaults with n_mels filters."""
+    f, fr = FbankOpts(), FrameOpts()
+    check(lib().jb_frame_kaldi(int(n_mels), C.byref(f), C.byref(fr)))
+    return f, fr
+
+
 CMVN_NONE, CMVN_MEAN, CMVN_MEAN_VAR = 0, 1, 2
 MFCC_F64 = 1
 
@@ -747,6 +777,9 @@ SYMBOLS = [
     "jb_synthesize_batch_each_fbank", "jb_synthesize_programme_fbank",
     "jb_mfcc_geometry", "jb_mfcc_dct", "jb_mfcc_delta_kernel", "jb_mfcc_host", "jb_mfcc_pcm_host",
     "jb_mfcc_frames_batch", "jb_mfcc_pcm_batch", "jb_mfcc_free",
+    "jb_frame_kaldi", "jb_frame_check", "jb_fbank_framed_geometry", "jb_frame_window", "jb_fbank_framed_host",
+    "jb_mfcc_framed_pcm_host", "jb_fbank_framed_pcm_batch", "jb_mfcc_framed_pcm_batch",
+    "jb_batch_set_frame_opts", "jb_engine_set_frame_opts",
     "jb_batch_set_mfcc", "jb_batch_mfcc_shape", "jb_batch_mfcc_size", "jb_batch_read_mfcc", "jb_batch_read_mfcc_all",
     "jb_synthesize_mfcc", "jb_synthesize_batch_mfcc", "jb_synthesize_batch_each_mfcc", "jb_synthesize_programme_mfcc",
     "jb_melspec_whisper", "jb_melspec_geometry", "jb_melspec_window", "jb_melspec_filterbank", "jb_melspec_host",
@@ -1029,6 +1062,19 @@ def lib():
                                     C.POINTER(sz)]
     L.jb_mfcc_free.argtypes = [u8p]
     L.jb_mfcc_free.restype = None
+    frp = C.POINTER(FrameOpts)
+    L.jb_frame_kaldi.argtypes = [C.c_uint32, fop, frp]
+    L.jb_frame_check.argtypes = [fop, cop, frp]
+    L.jb_fbank_framed_geometry.argtypes = [C.c_uint32, fop, frp, sz, u32p, u32p, u32p, C.POINTER(sz), C.POINTER(sz)]
+    L.jb_frame_window.argtypes = [C.c_uint32, fop, frp, vp, sz]
+    L.jb_fbank_framed_host.argtypes = [vp, sz, C.c_uint32, fop, frp, vp, sz]
+    L.jb_mfcc_framed_pcm_host.argtypes = [vp, sz, C.c_uint32, fop, cop, frp, vp, sz]
+    L.jb_fbank_framed_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, u32p, fop, frp, C.c_int32,
+                                            C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_mfcc_framed_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, u32p, fop, cop, frp, C.c_int32,
+                                           C.POINTER(u8p), C.POINTER(sz)]
+    L.jb_batch_set_frame_opts.argtypes = [vp, frp]
+    L.jb_engine_set_frame_opts.argtypes = [vp, frp]
     L.jb_batch_set_mfcc.argtypes = [vp, fop, cop]
     L.jb_batch_mfcc_shape.argtypes = [vp, sz, C.POINTER(sz), u32p, u32p]
     L.jb_batch_mfcc_size.argtypes = [vp, sz, C.POINTER(sz)]
@@ -1570,6 +1616,52 @@ def fbank_pcm(pcms, hz, opts: FbankOpts, device: int = -1):
     return res[0] if single else res
 
 
+def fbank_framed_geometry(hz: int, opts: FbankOpts, fr: FrameOpts, n: int = 0):
+    """jb_fbank_framed_geometry: (wl, hop, n_fft, T, bytes) of n samples at hz under the frame request."""
+    wl, hop, nfft, T, nby = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_size_t(), C.c_size_t()
+    check(lib().jb_fbank_framed_geometry(hz, C.byref(opts), C.byref(fr), n, C.byref(wl), C.byref(hop), C.byref(nfft),
+                                         C.byref(T), C.byref(nby)))
+    return wl.value, hop.value, nfft.value, T.value, nby.value
+
+
+def frame_window(hz: int, opts: FbankOpts, fr: FrameOpts):
+    """jb_frame_window: the wl window values of a conditioned frame at hz."""
+    import numpy as np
+
+    w = np.empty(fbank_geometry(hz, opts)[0], dtype=np.float64)
+    check(lib().jb_frame_window(hz, C.byref(opts), C.byref(fr), w.ctypes.data, w.size))
+    return w
+
+
+def fbank_framed_host(pcm, hz: int, opts: FbankOpts, fr: FrameOpts):
+    """jb_fbank_framed_host: fbank_host under the frame request (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    nby = fbank_framed_geometry(hz, opts, fr, a.size)[4]
+    out = np.empty(max(1, nby), dtype=np.uint8)
+    check(lib().jb_fbank_framed_host(a.ctypes.data, a.size, hz, C.byref(opts), C.byref(fr), out.ctypes.data, nby))
+    return fbank_frames(out[:nby].tobytes(), opts)
+
+
+def fbank_framed_pcm(pcms, hz, opts: FbankOpts, fr: FrameOpts, device: int = -1):
+    """jb_fbank_framed_pcm_batch: fbank_pcm under the frame request, on the GPU."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    L = lib()
+    u8p = C.POINTER(C.c_uint8)
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    check(L.jb_fbank_framed_pcm_batch(ins, nin, n, hzs, C.byref(opts), C.byref(fr), device, bufs, ns))
+    res = take_fbank(L, bufs, ns, n, opts)
+    return res[0] if single else res
+
+
 def melspec_geometry(hz: int, opts: MelspecOpts, n: int = 0):
     """jb_melspec_geometry: (n_fft, win_length, hop_length, T, bytes) of n samples at hz."""
     nfft, wl, hop, T, nby = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_size_t(), C.c_size_t()
@@ -1743,6 +1835,37 @@ def mfcc_pcm(pcms, hz, fopts: FbankOpts, opts: MfccOpts, device: int = -1):
     hzs = (C.c_uint32 * max(n, 1))(*rates)
     bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
     check(L.jb_mfcc_pcm_batch(ins, nin, n, hzs, C.byref(fopts), C.byref(opts), device, bufs, ns))
+    res = [mfcc_rows(d, opts, fopts.n_mels) for d in _take(L.jb_mfcc_free, bufs, ns, n)]
+    return res[0] if single else res
+
+
+def mfcc_framed_pcm_host(pcm, hz: int, fopts: FbankOpts, opts: MfccOpts, fr: FrameOpts):
+    """jb_mfcc_framed_pcm_host: mfcc_pcm_host under the frame request (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    T = fbank_framed_geometry(hz, fopts, fr, a.size)[3]
+    nby = T * opts.width(fopts.n_mels) * opts.dtype.itemsize
+    out = np.empty(max(1, nby), dtype=np.uint8)
+    check(lib().jb_mfcc_framed_pcm_host(a.ctypes.data, a.size, hz, C.byref(fopts), C.byref(opts), C.byref(fr),
+                                        out.ctypes.data, nby))
+    return mfcc_rows(out[:nby].tobytes(), opts, fopts.n_mels)
+
+
+def mfcc_framed_pcm(pcms, hz, fopts: FbankOpts, opts: MfccOpts, fr: FrameOpts, device: int = -1):
+    """jb_mfcc_framed_pcm_batch: mfcc_pcm under the frame request, on the GPU."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    L = lib()
+    u8p = C.POINTER(C.c_uint8)
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    check(L.jb_mfcc_framed_pcm_batch(ins, nin, n, hzs, C.byref(fopts), C.byref(opts), C.byref(fr), device, bufs, ns))
     res = [mfcc_rows(d, opts, fopts.n_mels) for d in _take(L.jb_mfcc_free, bufs, ns, n)]
     return res[0] if single else res
 

@@ -638,6 +638,15 @@ class Batch:
         F.check(self._L.jb_batch_set_mfcc(self._h, C.byref(fo), C.byref(mo)))
         self._mfcc = (fo, mo)
 
+    def set_frame(self, fr=None, **kw):
+        """jb_batch_set_frame_opts: Kaldi-style frame conditioning (DC removal, pre-emphasis, the Povey and the other
+        symmetric windows, reflected edges, the frame's log energy as c0) for set_fbank's and set_mfcc's features.
+        fr: F.FrameOpts (J.frame(...)), or the keywords of J.frame; None without keywords withdraws the request.
+        Before the first run, in either order with set_fbank / set_mfcc."""
+        if fr is None and kw:
+            fr = F.frame(**kw)
+        F.check(self._L.jb_batch_set_frame_opts(self._h, C.byref(fr) if fr is not None else None))
+
     def mfcc_shape(self, i):
         """(T, width, hz) of unit i's rows (jb_batch_mfcc_shape)."""
         T, w, hz = C.c_size_t(), C.c_uint32(), C.c_uint32()

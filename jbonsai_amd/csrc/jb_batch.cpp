@@ -2915,6 +2915,11 @@ int jb_batch_read_fbank(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
 
 int jb_batch_read_fbank_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Fbank, dst); }
 
+int jb_batch_set_frame_opts(jb_batch *hb, const jb_frame_opts *fr)
+{
+    return hb ? ((Batch *)hb)->out.set_frame_opts(fr) : JB_ERR_INVALID;
+}
+
 int jb_batch_set_mfcc(jb_batch *hb, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts)
 {
     return hb ? ((Batch *)hb)->out.set_mfcc(fopts, opts) : JB_ERR_INVALID;

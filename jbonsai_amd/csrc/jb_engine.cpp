@@ -55,6 +55,8 @@ struct Condition {
     std::vector<double> fir_taps; // jb_engine_set_fir: the response's taps, copied (empty = off) ...
     uint32_t fir_hz = 0, fir_delay = 0; // ... its rate and delay
     jb_fir fir() const { return jb_fir{fir_taps.empty() ? nullptr : fir_taps.data(), (uint32_t)fir_taps.size(), fir_hz, fir_delay, 0}; }
+    bool frame_on = false;        // jb_engine_set_frame_opts: a frame request for the *_fbank and *_mfcc entries ...
+    jb_frame_opts frame{};        // ... as it was given
     bool room_on = false;         // jb_engine_set_room: a room is set (in the impulse response's slot) ...
     jb_room room_req{};           // ... as it was given, with its flags, seed and margin
     uint32_t room_flags = 0;
@@ -1157,6 +1159,20 @@ int jb_engine_set_fir(jb_engine *e, const jb_fir *f)
     c.room_on = false; // (one slot: the later call replaces the earlier)
     return JB_OK;
 }
+int jb_engine_set_frame_opts(jb_engine *e, const jb_frame_opts *fr)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    jb::Condition &c = ENG(e)->cond;
+    if (fr)
+        if (const char *f = jb::frame_opts_fault(*(const jb::FrameOpts *)fr)) {
+            jb::set_error(std::string("jb_engine_set_frame_opts: ") + f);
+            return JB_ERR_INVALID;
+        }
+    c.frame_on = fr != nullptr;
+    c.frame = fr ? *fr : jb_frame_opts{};
+    return JB_OK;
+}
 int jb_engine_set_room(jb_engine *e, const jb_room *r, uint32_t flags, uint64_t seed, double margin)
 {
     if (!e)
@@ -1829,6 +1845,17 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
         return rc;
     if (rq.sink == jb::SynthSink::Adpcm && (rc = out.set_adpcm(rq.adpcm)))
         return rc;
+    // the frame request beside the two feature encoders: the engines' own, which must agree (one per batch)
+    if (rq.sink == jb::SynthSink::Fbank || rq.sink == jb::SynthSink::Mfcc) {
+        const jb::Condition &c0 = eng(lo)->cond;
+        for (size_t u = lo; u < hi; u++)
+            if (eng(u)->cond.frame_on != c0.frame_on || memcmp(&eng(u)->cond.frame, &c0.frame, sizeof c0.frame)) {
+                jb::set_error("jb_engine_set_frame_opts: the engines of one call must agree on the frame request");
+                return JB_ERR_INVALID;
+            }
+        if (c0.frame_on && (rc = out.set_frame_opts(&c0.frame)))
+            return rc;
+    }
     if (rq.sink == jb::SynthSink::Fbank && (rc = out.set_fbank(rq.fbank)))
         return rc;
     if (rq.sink == jb::SynthSink::Mfcc && (rc = out.set_mfcc(rq.fbank, rq.mfcc)))

@@ -1,7 +1,9 @@
-// jb_fbank.cpp -- the host half of the filterbank features: the option check, the geometry, the three tables (window,
+// jb_fbank.cpp -- the host half of the filterbank features and of their frame conditioning (jb_fbank_framed_host, the
+// request's window, check and Kaldi defaults): the option check, the geometry, the three tables (window,
 // twiddles, mel weights; long double, rounded once) and the rule of jb_fbank.h over PCM the caller holds without a GPU
 // (jb_fbank_host, what the kernel is checked against).
 #include "jb_host.h"
+#include "jb_mfcc.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -18,6 +20,14 @@ static_assert(sizeof(FbankOpts) == sizeof(jb_fbank_opts) && offsetof(FbankOpts, 
 static_assert(kFbHann == JB_FBANK_HANN && kFbHamming == JB_FBANK_HAMMING && kFbCenter == JB_FBANK_CENTER &&
                   kFbLinear == JB_FBANK_LINEAR && kFbUnit == JB_FBANK_UNIT && kFbF64 == JB_FBANK_F64,
               "jb_fbank.h restates the header's constants");
+static_assert(sizeof(FrameOpts) == sizeof(jb_frame_opts) && offsetof(FrameOpts, window) == offsetof(jb_frame_opts, window) &&
+                  offsetof(FrameOpts, flags) == offsetof(jb_frame_opts, flags) &&
+                  offsetof(FrameOpts, reserved) == offsetof(jb_frame_opts, reserved),
+              "jb_fbank.h restates the header's frame request");
+static_assert(kFrWindowOpts == JB_FRAME_WINDOW_OPTS && kFrPovey == JB_FRAME_POVEY && kFrHannSym == JB_FRAME_HANN_SYM &&
+                  kFrRect == JB_FRAME_RECT && kFrBlackman == JB_FRAME_BLACKMAN && kFrRemoveDc == JB_FRAME_REMOVE_DC &&
+                  kFrReflect == JB_FRAME_REFLECT && kFrEnergy == JB_FRAME_ENERGY,
+              "jb_fbank.h restates the header's frame constants");
 
 namespace {
 
@@ -39,7 +49,26 @@ struct HostFrame {
         for (uint32_t m = 0; m < g.n_mels; m++)
             E[m] = mel_bank_energy(t.bank, m, re.data());
     }
+    // ... of a frame that is windowed already: z[0..wl)
+    void run_windowed(const double *z, double *E)
+    {
+        rfft_frame_power(t.fft, [&](uint32_t i) { return i < g.wl ? z[i] : 0.0; }, re.data(), im.data());
+        for (uint32_t m = 0; m < g.n_mels; m++)
+            E[m] = mel_bank_energy(t.bank, m, re.data());
+    }
 };
+
+// Element [t][m] of the output from the filter's energy
+void put_element(const FbankOpts &o, const FbankGeom &g, double E, uint8_t *out, size_t at)
+{
+    const double v = (o.flags & kFbLinear) ? E : E > g.log_floor ? log(E) : g.ln_floor;
+    if (o.flags & kFbF64)
+        memcpy(out + at * 8, &v, 8);
+    else {
+        const float f = (float)v;
+        memcpy(out + at * 4, &f, 4);
+    }
+}
 
 } // namespace
 
@@ -74,6 +103,78 @@ void fbank_window(uint32_t window, uint32_t wl, double *w)
     for (uint32_t j = 0; j < wl; j++)
         w[j] = window == kFbHamming ? (double)(0.54L - 0.46L * cosl(two_pi * j / (long double)(wl - 1)))
                                     : (double)(0.5L - 0.5L * cosl(two_pi * j / (long double)wl));
+}
+
+void frame_window(uint32_t fbank_win, uint32_t frame_win, uint32_t wl, double *w)
+{
+    if (frame_win == kFrWindowOpts) {
+        fbank_window(fbank_win, wl, w);
+        return;
+    }
+    const long double a = 2.0L * acosl(-1.0L) / (long double)(wl - 1);
+    for (uint32_t j = 0; j < wl; j++) {
+        const long double h = 0.5L - 0.5L * cosl(a * j);
+        w[j] = frame_win == kFrPovey      ? (double)powl(h, 0.85L)
+               : frame_win == kFrHannSym  ? (double)h
+               : frame_win == kFrBlackman ? (double)(0.42L - 0.5L * cosl(a * j) + 0.08L * cosl(2.0L * a * j))
+                                          : 1.0;
+    }
+}
+
+int frame_check(const FbankOpts *opts, const FrameOpts *fr, bool cepstra, const char *who)
+{
+    const int rc = fbank_check_opts(opts, who);
+    if (rc)
+        return rc;
+    if (!fr) {
+        set_error(std::string(who) + ": the frame request is NULL");
+        return JB_ERR_INVALID;
+    }
+    const char *f = frame_opts_fault(*fr);
+    if (!f)
+        f = frame_pair_fault(*opts, *fr, cepstra);
+    if (f) {
+        set_error(std::string(who) + ": jb_frame_opts: " + f);
+        return JB_ERR_INVALID;
+    }
+    return JB_OK;
+}
+
+int fbank_framed_host(const double *in, size_t n, uint32_t hz, const FbankOpts &o, const FrameOpts &fr, uint8_t *out,
+                      size_t cap, const char *who, std::vector<double> *energy)
+{
+    FbankGeom g{};
+    const int rc = fbank_geometry(&o, hz, who, &g);
+    if (rc)
+        return rc;
+    const bool center = (o.flags & kFbCenter) != 0, reflect = (fr.flags & kFrReflect) != 0;
+    const uint64_t T = frame_count(n, g.wl, g.hop, center, reflect);
+    if (cap < T * g.n_mels * fbank_elem(o.flags)) {
+        set_error(std::string(who) + ": the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (n && (!in || (T && !out)))
+        return JB_ERR_INVALID;
+    FbankTables tab;
+    fbank_tables(g, hz, o.window, &tab);
+    frame_window(o.window, fr.window, g.wl, tab.win.data());
+    HostFrame hf(g, tab);
+    std::vector<double> E(g.n_mels), v(g.wl);
+    const double scale = (o.flags & kFbUnit) ? 0x1p-15 : 1.0;
+    if (energy)
+        energy->assign(T, 0.0);
+    for (uint64_t t = 0; t < T; t++) {
+        const int64_t k0 = frame_start(t, g.wl, g.hop, center, reflect);
+        for (uint32_t i = 0; i < g.wl; i++) {
+            const int64_t k = k0 + (int64_t)i;
+            v[i] = reflect ? in[frame_reflect(k, n)] * scale : k >= 0 && (uint64_t)k < n ? in[k] * scale : 0.0;
+        }
+        frame_condition(fr, tab.win.data(), g.wl, v.data(), energy ? &(*energy)[t] : nullptr);
+        hf.run_windowed(v.data(), E.data());
+        for (uint32_t m = 0; m < g.n_mels; m++)
+            put_element(o, g, E[m], out, (size_t)t * g.n_mels + m);
+    }
+    return JB_OK;
 }
 
 void fbank_filterbank(const FbankGeom &g, uint32_t hz, double *W)
@@ -210,6 +311,78 @@ int jb_fbank_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *
         }
     }
     return JB_OK;
+}
+
+int jb_frame_kaldi(uint32_t n_mels, jb_fbank_opts *f, jb_frame_opts *fr)
+{
+    if (!f || !fr) {
+        set_error("jb_frame_kaldi: an out pointer is NULL");
+        return JB_ERR_INVALID;
+    }
+    if (n_mels < 1 || n_mels > kFbMaxMels) {
+        set_error("jb_frame_kaldi: n_mels is in 1..128");
+        return JB_ERR_INVALID;
+    }
+    memset(f, 0, sizeof *f);
+    memset(fr, 0, sizeof *fr);
+    f->win_us = 25000;
+    f->hop_us = 10000;
+    f->n_mels = n_mels;
+    f->f_min_hz = 20.0;
+    f->log_floor = 0x1p-23;
+    fr->preemph = 0.97;
+    fr->window = JB_FRAME_POVEY;
+    fr->flags = JB_FRAME_REMOVE_DC;
+    return JB_OK;
+}
+
+int jb_frame_check(const jb_fbank_opts *fopts, const jb_mfcc_opts *mopts, const jb_frame_opts *fr)
+{
+    const FbankOpts *f = (const FbankOpts *)fopts;
+    const MfccOpts *m = (const MfccOpts *)mopts;
+    int rc = fbank_check_opts(f, "jb_frame_check");
+    if (!rc && m && !(rc = mfcc_check_fbank(f, "jb_frame_check")))
+        rc = mfcc_check_opts(m, f->n_mels, "jb_frame_check");
+    return rc ? rc : frame_check(f, (const FrameOpts *)fr, m && m->n_ceps >= 1, "jb_frame_check");
+}
+
+int jb_fbank_framed_geometry(uint32_t hz, const jb_fbank_opts *opts, const jb_frame_opts *fr, size_t n, uint32_t *wl,
+                             uint32_t *hop, uint32_t *n_fft, size_t *T, size_t *n_bytes)
+{
+    int rc = frame_check((const FbankOpts *)opts, (const FrameOpts *)fr, true, "jb_fbank_framed_geometry");
+    if (rc || (rc = jb_fbank_geometry(hz, opts, n, wl, hop, n_fft, T, n_bytes)) || !(fr->flags & kFrReflect))
+        return rc;
+    FbankGeom g{};
+    fbank_geometry_fault(*(const FbankOpts *)opts, hz, &g);
+    const uint64_t frames = frame_count(n, g.wl, g.hop, false, true);
+    if (T)
+        *T = (size_t)frames;
+    if (n_bytes)
+        *n_bytes = (size_t)(frames * g.n_mels * fbank_elem(opts->flags));
+    return JB_OK;
+}
+
+int jb_frame_window(uint32_t hz, const jb_fbank_opts *opts, const jb_frame_opts *fr, double *w, size_t cap)
+{
+    int rc = frame_check((const FbankOpts *)opts, (const FrameOpts *)fr, true, "jb_frame_window");
+    if (rc || (rc = jb_fbank_window(hz, opts, w, cap)))
+        return rc;
+    FbankGeom g{};
+    fbank_geometry_fault(*(const FbankOpts *)opts, hz, &g);
+    frame_window(opts->window, fr->window, g.wl, w);
+    return JB_OK;
+}
+
+int jb_fbank_framed_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *opts, const jb_frame_opts *fr,
+                         uint8_t *out, size_t cap)
+{
+    const int rc = frame_check((const FbankOpts *)opts, (const FrameOpts *)fr, false, "jb_fbank_framed_host");
+    if (rc)
+        return rc;
+    if (frame_is_identity(*(const FrameOpts *)fr))
+        return jb_fbank_host(in, n, hz, opts, out, cap);
+    return fbank_framed_host(in, n, hz, *(const FbankOpts *)opts, *(const FrameOpts *)fr, out, cap,
+                             "jb_fbank_framed_host", nullptr);
 }
 
 void jb_fbank_free(uint8_t *p) { free(p); }

@@ -114,6 +114,105 @@ inline bool fbank_geometry_quiet(const FbankOpts &opts, uint32_t hz, FbankGeom *
 int fbank_check_opts(const FbankOpts *opts, const char *who);
 int fbank_geometry(const FbankOpts *opts, uint32_t hz, const char *who, FbankGeom *g);
 
+// Frame conditioning (include/jbonsai_amd.h "Frame conditioning"): jb_frame_opts restated, and the rule's pieces that
+// the kernel, the host form and the plan share
+struct FrameOpts {
+    double preemph;
+    uint32_t window, flags;
+    uint32_t reserved[4];
+};
+static_assert(sizeof(FrameOpts) == 32 && offsetof(FrameOpts, window) == 8 && offsetof(FrameOpts, reserved) == 16,
+              "jb_frame_opts is 32 bytes");
+constexpr uint32_t kFrWindowOpts = 0, kFrPovey = 1, kFrHannSym = 2, kFrRect = 3, kFrBlackman = 4; // JB_FRAME_POVEY, ..
+constexpr uint32_t kFrRemoveDc = 1, kFrReflect = 2, kFrEnergy = 4; // JB_FRAME_REMOVE_DC, _REFLECT, _ENERGY
+
+// The zero request is the identity: the stage then runs as without one
+inline bool frame_is_identity(const FrameOpts &f)
+{
+    return f.preemph == 0.0 && f.window == kFrWindowOpts && f.flags == 0;
+}
+// What is wrong with the request on its own, naming the field; null: nothing
+inline const char *frame_opts_fault(const FrameOpts &f)
+{
+    if (f.window > kFrBlackman)
+        return "window is JB_FRAME_WINDOW_OPTS, _POVEY, _HANN_SYM, _RECT or _BLACKMAN";
+    if (f.flags & ~(kFrRemoveDc | kFrReflect | kFrEnergy))
+        return "flags has an unknown bit";
+    if (f.reserved[0] || f.reserved[1] || f.reserved[2] || f.reserved[3])
+        return "reserved must be 0";
+    if (!(f.preemph >= 0.0 && f.preemph <= 1.0))
+        return "preemph is in 0..1";
+    return nullptr;
+}
+// ... and beside the filterbank options it conditions; cepstra: the request is an mfcc one with n_ceps >= 1
+inline const char *frame_pair_fault(const FbankOpts &o, const FrameOpts &f, bool cepstra)
+{
+    if ((f.flags & kFrReflect) && (o.flags & kFbCenter))
+        return "flags: JB_FRAME_REFLECT does not go with JB_FBANK_CENTER";
+    if ((f.flags & kFrEnergy) && !cepstra)
+        return "flags: JB_FRAME_ENERGY needs an mfcc request with n_ceps >= 1";
+    return nullptr;
+}
+// T of n samples and the first sample of frame t (below 0 or behind n: outside the unit), with and without
+// JB_FRAME_REFLECT
+constexpr uint64_t frame_count(uint64_t n, uint32_t wl, uint32_t hop, bool center, bool reflect)
+{
+    return reflect ? (n + hop / 2) / hop : fbank_frames(n, wl, hop, center);
+}
+JB_RFFT_HD constexpr int64_t frame_start(uint64_t t, uint32_t wl, uint32_t hop, bool center, bool reflect)
+{
+    return (int64_t)(t * hop) + (reflect ? (int64_t)(hop / 2) - (int64_t)(wl / 2) : center ? -(int64_t)(wl / 2) : 0);
+}
+// Sample k of a unit of n >= 1 samples under JB_FRAME_REFLECT: mirrored at the edges (the edge sample repeats) until
+// it lies inside
+JB_RFFT_HD constexpr uint64_t frame_reflect(int64_t k, uint64_t n)
+{
+    while (k < 0 || (uint64_t)k >= n)
+        k = k < 0 ? -k - 1 : 2 * (int64_t)n - 1 - k;
+    return (uint64_t)k;
+}
+// The sum of step 2: f(i), i < wl, into 64 partial sums p_j (i = j mod 64, from 0.0 in ascending i), folded p_j +=
+// p_{j + w} for w = 32, 16, .., 1.  A function of wl alone; the kernel's 64 lanes do the same additions
+template <class F> inline double frame_sum(uint32_t wl, F f)
+{
+    double p[64];
+    for (uint32_t j = 0; j < 64; j++) {
+        p[j] = 0.0;
+        for (uint32_t i = j; i < wl; i += 64)
+            p[j] = p[j] + f(i);
+    }
+    for (uint32_t w = 32; w; w >>= 1)
+        for (uint32_t j = 0; j < w; j++)
+            p[j] = p[j] + p[j + w];
+    return p[0];
+}
+// Steps 2 to 5 on the host, in place: v[0..wl) the samples of step 1 -> the windowed frame; the energy of step 3 into
+// *energy (may be null)
+inline void frame_condition(const FrameOpts &f, const double *win, uint32_t wl, double *v, double *energy)
+{
+    if (f.flags & kFrRemoveDc) {
+        const double mean = frame_sum(wl, [&](uint32_t i) { return v[i]; }) / (double)wl;
+        for (uint32_t i = 0; i < wl; i++)
+            v[i] = v[i] - mean;
+    }
+    if (energy)
+        *energy = frame_sum(wl, [&](uint32_t i) { return v[i] * v[i]; });
+    const double c = f.preemph;
+    double prev = v[0];
+    for (uint32_t i = 0; i < wl; i++) {
+        const double cur = v[i], cp = c * prev;
+        v[i] = win[i] * (c > 0.0 ? cur - cp : cur);
+        prev = cur;
+    }
+}
+// The window of a conditioned frame: the request's, or with JB_FRAME_WINDOW_OPTS the filterbank options' (jb_fbank.cpp)
+void frame_window(uint32_t fbank_window, uint32_t frame_window, uint32_t wl, double *w);
+// JB_OK, or JB_ERR_INVALID with set_error naming the field: the filterbank options, the request and the pair
+int frame_check(const FbankOpts *opts, const FrameOpts *fr, bool cepstra, const char *who);
+// The conditioned rule on the host (jb_fbank_framed_host's body); energy: the frames' energies of step 3 (may be null)
+int fbank_framed_host(const double *in, size_t n, uint32_t hz, const FbankOpts &o, const FrameOpts &fr, uint8_t *out,
+                      size_t cap, const char *who, std::vector<double> *energy);
+
 // The tables of one geometry, built in long double and rounded once
 struct FbankTables {
     std::vector<double> win; // [wl]
@@ -133,6 +232,8 @@ struct FbankClass {
     uint32_t wl, hop, n_fft, log2m;
     uint32_t n_mels, flags;
     double log_floor, ln_floor;
+    double preemph;         // the frame request (win is its window already); all zero: none
+    uint32_t fr_flags, pad; // JB_FRAME_REMOVE_DC | _REFLECT
 };
 
 // One unit of a launch.  Launch lists are in unit order; g0 is the prefix sum of the list's workgroups
@@ -140,6 +241,7 @@ struct FbankClass {
 struct FbankUtt {
     const double *x; // the chain's final f64 PCM, in 16-bit scale
     uint8_t *y;      // its [T][n_mels] elements, 16-byte aligned
+    double *e;       // [T] the frames' energies (step 3 of the frame request); null: none
     uint64_t n, T, g0;
     uint32_t cls, pad;
 };

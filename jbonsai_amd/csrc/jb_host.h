@@ -291,7 +291,9 @@ hipError_t launch_adpcm(bool i16, const AdpcmUtt *utts_dev, uint32_t n, uint64_t
 
 // The distinct geometries of a launch of the filterbank features or the mel spectrograms, one per rate: their tables
 // on the host.  A stage states its geometry and its tables (rate_geometry, rate_tables) and the body of bind
-template <class Opts, class Geom, class Tables, class Class> struct RateClasses {
+struct RateNoCond {};
+template <class Opts, class Geom, class Tables, class Class, class Cond = RateNoCond> struct RateClasses {
+    Cond cond{}; // what conditions every class of the launch beside the options (set before the first find)
     std::vector<uint32_t> key_hz;
     std::vector<Geom> geom;
     std::vector<Tables> tables;
@@ -308,7 +310,7 @@ template <class Opts, class Geom, class Tables, class Class> struct RateClasses 
         if (rc)
             return rc;
         Tables t; // (a class is listed once its tables stand)
-        if (!rate_tables(g, hz, opts, &t)) {
+        if (!rate_tables(g, hz, opts, cond, &t)) {
             set_error(std::string(who) + ": the filterbank at " + std::to_string(hz) + " Hz has no by-bin form");
             return JB_ERR_INVALID;
         }
@@ -334,24 +336,31 @@ inline int rate_geometry(const FbankOpts *o, uint32_t hz, const char *who, Fbank
 {
     return fbank_geometry(o, hz, who, g);
 }
-inline bool rate_tables(const FbankGeom &g, uint32_t hz, const FbankOpts &o, FbankTables *t)
+inline bool rate_tables(const FbankGeom &g, uint32_t hz, const FbankOpts &o, const FrameOpts &fr, FbankTables *t)
 {
-    return fbank_tables(g, hz, o.window, t);
+    if (!fbank_tables(g, hz, o.window, t))
+        return false;
+    frame_window(o.window, fr.window, g.wl, t->win.data());
+    return true;
 }
-typedef RateClasses<FbankOpts, FbankGeom, FbankTables, FbankClass> FbankClasses;
+// (the class key: the rate, under the one FrameOpts of the launch)
+typedef RateClasses<FbankOpts, FbankGeom, FbankTables, FbankClass, FrameOpts> FbankClasses;
 template <>
 void FbankClasses::bind(const FbankOpts &opts, const double *dev, std::vector<double> *image,
                         std::vector<FbankClass> *out) const;
-// utts_dev[0..n) of `groups` workgroups in all
+// utts_dev[0..n) of `groups` workgroups in all; framed: the classes carry a frame request (the conditioned loader)
 hipError_t launch_fbank(const FbankClass *classes_dev, const FbankUtt *utts_dev, uint32_t n, uint64_t groups,
-                        hipStream_t stream);
+                        hipStream_t stream, bool framed = false);
 
 // Mel spectrograms (jb_melspec.hip; the rule, MelClass and MelUtt: jb_melspec.h; the host half: jb_melspec.cpp)
 inline int rate_geometry(const MelOpts *o, uint32_t hz, const char *who, MelGeom *g)
 {
     return mel_geometry(o, hz, who, g);
 }
-inline bool rate_tables(const MelGeom &g, uint32_t hz, const MelOpts &o, MelTables *t) { return mel_tables(g, hz, o, t); }
+inline bool rate_tables(const MelGeom &g, uint32_t hz, const MelOpts &o, const RateNoCond &, MelTables *t)
+{
+    return mel_tables(g, hz, o, t);
+}
 typedef RateClasses<MelOpts, MelGeom, MelTables, MelClass> MelClasses;
 template <>
 void MelClasses::bind(const MelOpts &opts, const double *dev, std::vector<double> *image,
@@ -709,6 +718,10 @@ struct OutputChain {
     // the mel spectrograms (jb_melspec.h): an f64 batch only; checked at every utterance's output rate (NULL: the
     // request is withdrawn); set_output_rate checks the combined request again.  Independent of set_fbank and set_mfcc
     int set_melspec(const jb_melspec_opts *opts);
+    // the frame request beside set_fbank's and set_mfcc's (jb_fbank.h "Frame conditioning"; NULL: withdrawn), in either
+    // order with them: the pair is checked when both are present and again at the first run, where a request without
+    // either is an error
+    int set_frame_opts(const jb_frame_opts *fr);
     // f[0..n): n == 1 or B filters (nullptr, 0: the request is withdrawn), each checked at its utterance's output
     // rate; set_output_rate checks the combined request again
     int set_filter(const jb_filter *f, size_t n);
@@ -802,6 +815,8 @@ private:
     bool mf_on = false;                        // cepstral features are requested
     FbankOpts mf_fb{};                         // their filterbank options, as the caller gave them
     MfccOpts mf_p{};
+    bool fr_on = false;                        // a frame request stands beside the two above
+    FrameOpts fr_p{};
     bool ml_on = false;                        // mel spectrograms are requested
     MelOpts ml_p{};
     std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
@@ -969,6 +984,9 @@ private:
     bool melspec() const { return plan.melspec_src != OutSlab::None; }
     int check_melspec(const MelOpts &opts, const std::vector<uint32_t> &want, const char *who) const;
     int check_mfcc(const FbankOpts &fopts, const std::vector<uint32_t> &want, const char *who) const;
+    // the frame request fr (null: none) beside an fbank request fb and an mfcc request (mfb, mp), each null: none
+    int check_frame(const FrameOpts *fr, const FbankOpts *fb, const FbankOpts *mfb, const MfccOpts *mp,
+                    const char *who) const;
     int check_fbank(const FbankOpts &opts, const std::vector<uint32_t> &want, const char *who) const;
     void replan(); // host geometry and routing of the present requests
     // v[0..n), n == 1 or B, as [B] values; false (set_error(err)) for anything else

@@ -115,8 +115,10 @@ template <class F> double blocked_mean(uint64_t T, double r_T, F term)
     return total * r_T;
 }
 
-// The rule from the cepstra on: L [T][n_mels] -> out
-void mfcc_rule(const double *L, uint64_t T, uint32_t n_mels, const MfccOpts &o, uint8_t *out)
+// The rule from the cepstra on: L [T][n_mels] -> out; energy (null: none): the frames' energies of JB_FRAME_ENERGY,
+// held to the geometry's floor
+void mfcc_rule(const double *L, uint64_t T, uint32_t n_mels, const MfccOpts &o, uint8_t *out,
+               const double *energy = nullptr, const FbankGeom *g = nullptr)
 {
     if (!T)
         return;
@@ -127,8 +129,10 @@ void mfcc_rule(const double *L, uint64_t T, uint32_t n_mels, const MfccOpts &o, 
     std::vector<double> c((size_t)T * d);
     for (uint64_t t = 0; t < T; t++)
         for (uint32_t i = 0; i < d; i++)
-            c[t * d + i] = o.n_ceps ? mfcc_cep(L + t * n_mels, tab.D.data() + (size_t)i * n_mels, 1, n_mels, tab.lift[i])
-                                    : L[t * n_mels + i];
+            c[t * d + i] = !o.n_ceps          ? L[t * n_mels + i]
+                           : i == 0 && energy ? mfcc_c0(energy[t], g->log_floor, g->ln_floor)
+                                              : mfcc_cep(L + t * n_mels, tab.D.data() + (size_t)i * n_mels, 1, n_mels,
+                                                         tab.lift[i]);
     if (o.cmvn != kMfCmvnNone) {
         const double r_T = mfcc_r(T);
         for (uint32_t i = 0; i < d; i++) {
@@ -258,6 +262,38 @@ int jb_mfcc_pcm_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opt
     if ((rc = jb_fbank_host(in, n, hz, (const jb_fbank_opts *)&f, (uint8_t *)L.data(), sizeof(double) * T * f.n_mels)))
         return rc;
     mfcc_rule(L.data(), T, f.n_mels, *(const MfccOpts *)opts, out);
+    return JB_OK;
+}
+
+int jb_mfcc_framed_pcm_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *fopts,
+                            const jb_mfcc_opts *opts, const jb_frame_opts *fr, uint8_t *out, size_t cap)
+{
+    const char *who = "jb_mfcc_framed_pcm_host";
+    const FbankOpts *fo = (const FbankOpts *)fopts;
+    const MfccOpts *o = (const MfccOpts *)opts;
+    const FrameOpts *q = (const FrameOpts *)fr;
+    int rc = mfcc_check_fbank(fo, who);
+    if (rc || (rc = mfcc_check_opts(o, fo->n_mels, who)) || (rc = frame_check(fo, q, o->n_ceps >= 1, who)))
+        return rc;
+    if (frame_is_identity(*q))
+        return jb_mfcc_pcm_host(in, n, hz, fopts, opts, out, cap);
+    const FbankOpts f = mfcc_fbank_opts(*fo);
+    FbankGeom g{};
+    if ((rc = fbank_geometry(&f, hz, who, &g)))
+        return rc;
+    const uint64_t T = frame_count(n, g.wl, g.hop, (f.flags & kFbCenter) != 0, (q->flags & kFrReflect) != 0);
+    if (cap < T * mfcc_width(*o, g.n_mels) * mfcc_elem(o->flags)) {
+        set_error(std::string(who) + ": the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (n && (!in || (T && !out)))
+        return JB_ERR_INVALID;
+    std::vector<double> L((size_t)T * f.n_mels + 1), energy;
+    const bool e = (q->flags & kFrEnergy) != 0;
+    if ((rc = fbank_framed_host(in, n, hz, f, *q, (uint8_t *)L.data(), sizeof(double) * T * f.n_mels, who,
+                                e ? &energy : nullptr)))
+        return rc;
+    mfcc_rule(L.data(), T, f.n_mels, *o, out, e ? energy.data() : nullptr, &g);
     return JB_OK;
 }
 

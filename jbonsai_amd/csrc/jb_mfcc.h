@@ -94,6 +94,7 @@ struct MfccParams {
     uint32_t n_mels, n_ceps, d, order, N, cmvn, flags, pad;
     double floor; // var_floor, or 2^-52
     double s1[kMfMaxS1], s2[kMfMaxS2];
+    double e_floor, e_ln_floor; // the filterbank's log_floor and its logarithm: what c0 of JB_FRAME_ENERGY is held to
 };
 inline MfccParams mfcc_params(const MfccOpts &o, uint32_t n_mels, const MfccTables &t)
 {
@@ -123,6 +124,7 @@ struct MfccUtt {
     uint8_t *y;      // [T][d (order + 1)] elements, 16-byte aligned
     uint64_t T, g0, b0;
     double r_T;
+    const double *e; // [T] the frames' energies (JB_FRAME_ENERGY: c[t][0] is their logarithm); null: none
 };
 
 // ---- the rule, operation for operation (every product and sum on its own: the build has -ffp-contract=off) ----
@@ -135,6 +137,8 @@ JB_RFFT_HD double mfcc_cep(const double *Lrow, const double *Dcol, uint32_t ds, 
         acc = acc + Dcol[(size_t)m * ds] * Lrow[m];
     return lift * acc;
 }
+// c[t][0] under JB_FRAME_ENERGY: ln(max(e, log_floor)), the floor's logarithm from the host; the lifter's l_0 is 1
+JB_RFFT_HD double mfcc_c0(double e, double floor, double ln_floor) { return e > floor ? log(e) : ln_floor; }
 // One value of the statistics' passes: c (the mean's pass), or (c - mu)^2 (the variance's)
 JB_RFFT_HD double mfcc_stat_term(double c, double mu, bool var)
 {

@@ -7,6 +7,7 @@
 //                 lane per (frame, coefficient) walks m ascending: L from LDS (the lanes of a frame read one address: a
 //                 broadcast), D from the transposed [m][i] table, so lanes that follow one another read doubles that
 //                 follow one another.  The f64 statics go to scratch.  Not launched with n_ceps = 0: the statics are L.
+//                 With the frames' energies (JB_FRAME_ENERGY: k_fbank wrote them) column 0 is their logarithm.
 //   k_mfcc_block  one lane per (unit, block of kMfBlock frames, dimension): the block's sum from 0.0 in ascending t,
 //                 of c in the mean's pass and of (c - mu)^2 in the variance's.
 //   k_mfcc_fold   one lane per (unit, dimension): the block sums from 0.0 in ascending order, times r_T; the mean's pass
@@ -47,7 +48,8 @@ __global__ __launch_bounds__(kMfLanes) void k_ceps(MfccParams P, const MfccUtt *
     double *dst = U.c + t0 * nc;
     for (uint32_t e = threadIdx.x; e < nf * nc; e += kMfLanes) {
         const uint32_t f = e / nc, i = e % nc;
-        dst[e] = mfcc_cep(s_L + f * rs, P.Dt + i, nc, nm, P.lift[i]);
+        dst[e] = i == 0 && U.e ? mfcc_c0(U.e[t0 + f], P.e_floor, P.e_ln_floor)
+                               : mfcc_cep(s_L + f * rs, P.Dt + i, nc, nm, P.lift[i]);
     }
 }
 
@@ -163,12 +165,15 @@ namespace {
 // The stage behind log-mel frames that stand on the device (unit u: T[u] frames at dL + loff[u] doubles), through ds;
 // the outputs are handed out
 int mfcc_run(DeviceScratch &ds, const MfccOpts &o, uint32_t n_mels, const double *dL, const std::vector<uint64_t> &loff,
-             const std::vector<uint64_t> &T, uint8_t **out, size_t *n_bytes)
+             const std::vector<uint64_t> &T, uint8_t **out, size_t *n_bytes, const double *de = nullptr,
+             const std::vector<uint64_t> *eoff = nullptr, const FbankGeom *g = nullptr)
 {
     const size_t n = T.size();
     MfccTables tab;
     mfcc_tables(o, n_mels, &tab);
     MfccParams P = mfcc_params(o, n_mels, tab);
+    if (g) // (the frames' energies at de + eoff[u], held to the filterbank's floor)
+        P.e_floor = g->log_floor, P.e_ln_floor = g->ln_floor;
     const uint32_t d = P.d, width = mfcc_width(o, n_mels);
     std::vector<MfccUtt> utts(n);
     std::vector<PcmShare> shares(n);
@@ -200,6 +205,7 @@ int mfcc_run(DeviceScratch &ds, const MfccOpts &o, uint32_t n_mels, const double
         w.bs = dbs + w.b0 * d;
         w.stat = dst + 2 * u * d;
         w.y = dy + shares[u].off;
+        w.e = de ? de + (*eoff)[u] : nullptr;
     }
     const MfccUtt *du = ds.upload(utts);
     if (ds.ok())
@@ -209,6 +215,69 @@ int mfcc_run(DeviceScratch &ds, const MfccOpts &o, uint32_t n_mels, const double
     if (const int rc = ds.status())
         return rc;
     return hand_out(host.data(), 1, shares, (void **)out, n_bytes);
+}
+
+// The whole stage on PCM the caller holds: fopts and o with the frame request fr (all zero: none), under the entry's name
+int mfcc_pcm_run(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz, const FbankOpts *fopts,
+                 const MfccOpts *o, const FrameOpts &fr, int32_t device, uint8_t **out, size_t *n_bytes, const char *who)
+{
+    int rc = mfcc_check_fbank(fopts, who);
+    if (rc)
+        return rc;
+    const FbankOpts f = mfcc_fbank_opts(*fopts);
+    if ((rc = mfcc_check_opts(o, f.n_mels, who)) || (rc = frame_check(&f, &fr, o->n_ceps >= 1, who)))
+        return rc;
+    if ((rc = pcm_check((const void *const *)in, n_in, n, hz && out && n_bytes, (void **)out, n_bytes)))
+        return rc;
+    // (every rate's geometry before a device is touched)
+    FbankClasses cls;
+    cls.cond = fr;
+    std::vector<FbankUtt> futts(n);
+    for (size_t u = 0; u < n; u++)
+        if ((rc = cls.find(f, hz[u], who, &futts[u].cls)))
+            return rc;
+    DeviceScratch ds;
+    if ((rc = ds.open(device, who)))
+        return rc;
+    // the filterbank stage as jb_fbank_pcm_batch runs it, its f64 logarithms into a slab of the call (a unit's frames
+    // on a 16-byte boundary), then the cepstral kernels behind it on the same stream
+    std::vector<uint64_t> xoff;
+    const double *dx = ds.pack(in, n_in, n, &xoff);
+    const bool center = (f.flags & kFbCenter) != 0, reflect = (fr.flags & kFrReflect) != 0;
+    const bool energy = (fr.flags & kFrEnergy) != 0;
+    std::vector<uint64_t> loff(n), eoff(n), T(n);
+    uint64_t words = 0, groups = 0, frames = 0;
+    for (size_t u = 0; u < n; u++) {
+        FbankUtt &w = futts[u];
+        const FbankGeom &g = cls.geom[w.cls];
+        w.n = n_in[u];
+        w.T = T[u] = frame_count(w.n, g.wl, g.hop, center, reflect);
+        w.g0 = groups;
+        loff[u] = words;
+        eoff[u] = frames;
+        words += (w.T * g.n_mels + 1) & ~(uint64_t)1;
+        frames += w.T;
+        groups += (w.T + fbank_wg_frames(g.n_fft) - 1) / fbank_wg_frames(g.n_fft);
+    }
+    double *dL = ds.alloc<double>(std::max<uint64_t>(words, 2));
+    double *de = energy ? ds.alloc<double>(std::max<uint64_t>(frames, 1)) : nullptr;
+    for (size_t u = 0; u < n; u++) {
+        futts[u].x = dx + xoff[u];
+        futts[u].y = (uint8_t *)(dL + loff[u]);
+        futts[u].e = de ? de + eoff[u] : nullptr;
+    }
+    double *dt = ds.alloc<double>(cls.words());
+    std::vector<double> image;
+    std::vector<FbankClass> classes;
+    cls.bind(f, dt, &image, &classes);
+    if (ds.ok() && !image.empty())
+        ds.err = hipMemcpyAsync(dt, image.data(), sizeof(double) * image.size(), hipMemcpyHostToDevice, ds.stream);
+    const FbankClass *dcl = ds.upload(classes);
+    const FbankUtt *du = ds.upload(futts);
+    if (ds.ok())
+        ds.err = launch_fbank(dcl, du, (uint32_t)n, groups, ds.stream, !frame_is_identity(fr));
+    // (image, classes and futts live to the wait inside mfcc_run)
+    return mfcc_run(ds, *o, f.n_mels, dL, loff, T, out, n_bytes, de, &eoff, n && de ? &cls.geom[0] : nullptr);
 }
 
 } // namespace
@@ -248,58 +317,20 @@ int jb_mfcc_pcm_batch(const double *const *in, const size_t *n_in, size_t n, con
                       const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, int32_t device, uint8_t **out,
                       size_t *n_bytes)
 {
-    int rc = mfcc_check_fbank((const FbankOpts *)fopts, "jb_mfcc_pcm_batch");
-    if (rc)
-        return rc;
-    const FbankOpts f = mfcc_fbank_opts(*(const FbankOpts *)fopts);
-    const MfccOpts *o = (const MfccOpts *)opts;
-    if ((rc = mfcc_check_opts(o, f.n_mels, "jb_mfcc_pcm_batch")))
-        return rc;
-    if ((rc = pcm_check((const void *const *)in, n_in, n, hz && out && n_bytes, (void **)out, n_bytes)))
-        return rc;
-    // (every rate's geometry before a device is touched)
-    FbankClasses cls;
-    std::vector<FbankUtt> futts(n);
-    for (size_t u = 0; u < n; u++)
-        if ((rc = cls.find(f, hz[u], "jb_mfcc_pcm_batch", &futts[u].cls)))
-            return rc;
-    DeviceScratch ds;
-    if ((rc = ds.open(device, "jb_mfcc_pcm_batch")))
-        return rc;
-    // the filterbank stage as jb_fbank_pcm_batch runs it, its f64 logarithms into a slab of the call (a unit's frames
-    // on a 16-byte boundary), then the cepstral kernels behind it on the same stream
-    std::vector<uint64_t> xoff;
-    const double *dx = ds.pack(in, n_in, n, &xoff);
-    const bool center = (f.flags & kFbCenter) != 0;
-    std::vector<uint64_t> loff(n), T(n);
-    uint64_t words = 0, groups = 0;
-    for (size_t u = 0; u < n; u++) {
-        FbankUtt &w = futts[u];
-        const FbankGeom &g = cls.geom[w.cls];
-        w.n = n_in[u];
-        w.T = T[u] = fbank_frames(w.n, g.wl, g.hop, center);
-        w.g0 = groups;
-        loff[u] = words;
-        words += (w.T * g.n_mels + 1) & ~(uint64_t)1;
-        groups += (w.T + fbank_wg_frames(g.n_fft) - 1) / fbank_wg_frames(g.n_fft);
+    return mfcc_pcm_run(in, n_in, n, hz, (const FbankOpts *)fopts, (const MfccOpts *)opts, FrameOpts{}, device, out,
+                        n_bytes, "jb_mfcc_pcm_batch");
+}
+
+int jb_mfcc_framed_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                             const jb_fbank_opts *fopts, const jb_mfcc_opts *opts, const jb_frame_opts *fr,
+                             int32_t device, uint8_t **out, size_t *n_bytes)
+{
+    if (!fr) {
+        set_error("jb_mfcc_framed_pcm_batch: the frame request is NULL");
+        return JB_ERR_INVALID;
     }
-    double *dL = ds.alloc<double>(std::max<uint64_t>(words, 2));
-    for (size_t u = 0; u < n; u++) {
-        futts[u].x = dx + xoff[u];
-        futts[u].y = (uint8_t *)(dL + loff[u]);
-    }
-    double *dt = ds.alloc<double>(cls.words());
-    std::vector<double> image;
-    std::vector<FbankClass> classes;
-    cls.bind(f, dt, &image, &classes);
-    if (ds.ok() && !image.empty())
-        ds.err = hipMemcpyAsync(dt, image.data(), sizeof(double) * image.size(), hipMemcpyHostToDevice, ds.stream);
-    const FbankClass *dcl = ds.upload(classes);
-    const FbankUtt *du = ds.upload(futts);
-    if (ds.ok())
-        ds.err = launch_fbank(dcl, du, (uint32_t)n, groups, ds.stream);
-    // (image, classes and futts live to the wait inside mfcc_run)
-    return mfcc_run(ds, *o, f.n_mels, dL, loff, T, out, n_bytes);
+    return mfcc_pcm_run(in, n_in, n, hz, (const FbankOpts *)fopts, (const MfccOpts *)opts, *(const FrameOpts *)fr,
+                        device, out, n_bytes, "jb_mfcc_framed_pcm_batch");
 }
 
 } // extern "C"

@@ -128,6 +128,7 @@ OutPlan plan_output(const OutPlanIn &in)
     }
     // the filterbank features beside them: the final f64 to frames of each unit's own geometry (a request that some
     // rate refuses is no request: the chain has checked it)
+    const bool reflect = in.frame && (in.frame->flags & kFrReflect); // (the frame request: T of both feature stages)
     if (in.fbank && !p.final.i16) {
         std::vector<OutFbankUtt> f(units.size());
         uint64_t bytes = 0;
@@ -136,7 +137,7 @@ OutPlan plan_output(const OutPlanIn &in)
             FbankGeom g{};
             if (!(ok = fbank_geometry_quiet(*in.fbank, units[u].hz, &g)))
                 break;
-            const uint64_t T = fbank_frames(units[u].n, g.wl, g.hop, (in.fbank->flags & kFbCenter) != 0);
+            const uint64_t T = frame_count(units[u].n, g.wl, g.hop, (in.fbank->flags & kFbCenter) != 0, reflect);
             f[u] = {bytes, T * g.n_mels * fbank_elem(in.fbank->flags), T, g.wl, g.hop, g.n_fft};
             bytes += (f[u].bytes + 15) & ~(uint64_t)15;
         }
@@ -158,7 +159,7 @@ OutPlan plan_output(const OutPlanIn &in)
             FbankGeom g{};
             if (!(ok = fbank_geometry_quiet(fo, units[u].hz, &g)))
                 break;
-            const uint64_t T = fbank_frames(units[u].n, g.wl, g.hop, (fo.flags & kFbCenter) != 0);
+            const uint64_t T = frame_count(units[u].n, g.wl, g.hop, (fo.flags & kFbCenter) != 0, reflect);
             const uint32_t width = mfcc_width(*in.mfcc, g.n_mels);
             f[u] = {bytes, T * width * mfcc_elem(in.mfcc->flags), T, width, g.n_fft, words};
             bytes += (f[u].bytes + 15) & ~(uint64_t)15;

@@ -69,6 +69,7 @@ struct OutPlanIn {
     const FbankOpts *fbank = nullptr;     // the filterbank request (jb_fbank.h), checked at every output rate; nullptr: none
     const FbankOpts *mfcc_fbank = nullptr; // the cepstral request (jb_mfcc.h): its filterbank's geometry (the stage forces
     const MfccOpts *mfcc = nullptr;        // f64 logarithms itself) and its options; both or neither
+    const FrameOpts *frame = nullptr;      // the frame request beside the fbank and mfcc ones (JB_FRAME_REFLECT: their T); nullptr: none
     const MelOpts *melspec = nullptr;      // the mel spectrogram request (jb_melspec.h), checked at every output rate; nullptr: none
 };
 

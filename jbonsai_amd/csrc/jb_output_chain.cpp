@@ -45,6 +45,7 @@ void OutputChain::replan()
     in.fbank = fb_on ? &fb_p : nullptr;
     in.mfcc_fbank = mf_on ? &mf_fb : nullptr;
     in.mfcc = mf_on ? &mf_p : nullptr;
+    in.frame = fr_on ? &fr_p : nullptr;
     in.melspec = ml_on ? &ml_p : nullptr;
     plan = plan_output(in);
 }
@@ -326,7 +327,9 @@ int OutputChain::set_fbank(const jb_fbank_opts *opts)
     }
     if ((rc = check_settable("jb_batch_set_fbank: the features are set before the batch's first run")))
         return rc;
-    if (opts && (rc = check_fbank(*(const FbankOpts *)opts, want_hz, "jb_batch_set_fbank")))
+    if (opts && ((rc = check_fbank(*(const FbankOpts *)opts, want_hz, "jb_batch_set_fbank")) ||
+                 (rc = check_frame(fr_on ? &fr_p : nullptr, (const FbankOpts *)opts, nullptr, nullptr,
+                                   "jb_batch_set_fbank"))))
         return rc;
     fb_on = opts != nullptr;
     if (opts)
@@ -358,13 +361,50 @@ int OutputChain::set_mfcc(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts)
     }
     if ((rc = check_settable("jb_batch_set_mfcc: the features are set before the batch's first run")))
         return rc;
-    if (on && (rc = check_mfcc(*(const FbankOpts *)fopts, want_hz, "jb_batch_set_mfcc")))
+    if (on && ((rc = check_mfcc(*(const FbankOpts *)fopts, want_hz, "jb_batch_set_mfcc")) ||
+               (rc = check_frame(fr_on ? &fr_p : nullptr, nullptr, (const FbankOpts *)fopts, (const MfccOpts *)opts,
+                                 "jb_batch_set_mfcc"))))
         return rc;
     mf_on = on;
     if (on) {
         mf_fb = *(const FbankOpts *)fopts;
         mf_p = *(const MfccOpts *)opts;
     }
+    replan();
+    return JB_OK;
+}
+
+// The frame request beside the feature requests it conditions: JB_ERR_INVALID naming the field
+int OutputChain::check_frame(const FrameOpts *fr, const FbankOpts *fb, const FbankOpts *mfb, const MfccOpts *mp,
+                             const char *who) const
+{
+    if (!fr)
+        return JB_OK;
+    const char *f = fb ? frame_pair_fault(*fb, *fr, false) : nullptr;
+    if (!f && mfb)
+        f = frame_pair_fault(*mfb, *fr, mp->n_ceps >= 1);
+    if (f) {
+        set_error(std::string(who) + ": jb_frame_opts: " + f);
+        return JB_ERR_INVALID;
+    }
+    return JB_OK;
+}
+
+int OutputChain::set_frame_opts(const jb_frame_opts *fr)
+{
+    const FrameOpts *q = (const FrameOpts *)fr;
+    int rc;
+    if (q)
+        if (const char *f = frame_opts_fault(*q)) {
+            set_error(std::string("jb_batch_set_frame_opts: ") + f);
+            return JB_ERR_INVALID;
+        }
+    if ((rc = check_settable("jb_batch_set_frame_opts: the frame request is set before the batch's first run")) ||
+        (rc = check_frame(q, fb_on ? &fb_p : nullptr, mf_on ? &mf_fb : nullptr, &mf_p, "jb_batch_set_frame_opts")))
+        return rc;
+    fr_on = q != nullptr;
+    if (q)
+        fr_p = *q;
     replan();
     return JB_OK;
 }
@@ -745,8 +785,15 @@ int OutputChain::prepare()
 {
     if (ready)
         return JB_OK;
-    frozen = true;
     int rc;
+    if (fr_on && !fb_on && !mf_on) {
+        set_error("jb_batch_set_frame_opts: the frame request stands beside jb_batch_set_fbank or jb_batch_set_mfcc");
+        return JB_ERR_INVALID;
+    }
+    if ((rc = check_frame(fr_on ? &fr_p : nullptr, fb_on ? &fb_p : nullptr, mf_on ? &mf_fb : nullptr, &mf_p,
+                          "jb_batch_set_frame_opts")))
+        return rc;
+    frozen = true;
     for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
@@ -1592,6 +1639,8 @@ int OutputChain::prepare_fbank()
     const double *src = (const double *)slab[(size_t)plan.fbank_src];
     uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Feat];
     FbankClasses cls;
+    if (fr_on)
+        cls.cond = fr_p;
     fb.utts.host.assign(U, FbankUtt{});
     fb.ngroups.assign(U, 0);
     fb.groups = 0;
@@ -1629,7 +1678,8 @@ int OutputChain::launch_fbank(bool redo)
 {
     if (!fbank() || (redo && !fb.utts.n))
         return JB_OK;
-    const hipError_t e = jb::launch_fbank(fb.classes_dev, fb.utts.list, fb.utts.n, fb.utts.total, b.stream_voc);
+    const hipError_t e = jb::launch_fbank(fb.classes_dev, fb.utts.list, fb.utts.n, fb.utts.total, b.stream_voc,
+                                          fr_on && !frame_is_identity(fr_p));
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_fbank(redo)" : "k_fbank");
 }
 
@@ -1651,6 +1701,9 @@ int OutputChain::prepare_mfcc()
     mf.P = mfcc_params(mf_p, fo.n_mels, tab);
     const uint32_t d = mf.P.d;
     FbankClasses cls;
+    if (fr_on)
+        cls.cond = fr_p;
+    const bool energy = fr_on && (fr_p.flags & kFrEnergy);
     mf.futts.host.assign(U, FbankUtt{});
     mf.utts.host.assign(U, MfccUtt{});
     mf.ngroups.assign(U, 0);
@@ -1685,8 +1738,9 @@ int OutputChain::prepare_mfcc()
         mf.blocks += mf.nblocks[u];
         frames += pl.T;
     }
-    double *statics = nullptr, *bs = nullptr, *stat = nullptr, *dct = nullptr, *lift = nullptr;
-    if ((rc = b.dalloc(&bs, mf.blocks * d, false)) ||
+    double *statics = nullptr, *bs = nullptr, *stat = nullptr, *dct = nullptr, *lift = nullptr, *en = nullptr;
+    if ((energy && (rc = b.dalloc(&en, std::max<uint64_t>(frames, 1), false))) ||
+        (rc = b.dalloc(&bs, mf.blocks * d, false)) ||
         (rc = b.dalloc(&stat, 2 * U * d, false)) || (rc = b.dalloc(&dct, tab.Dt.size(), false)) ||
         (rc = b.dalloc(&lift, tab.lift.size(), false)) ||
         (mf_p.n_ceps && (rc = b.dalloc(&statics, frames * d, false))))
@@ -1697,8 +1751,12 @@ int OutputChain::prepare_mfcc()
         w.c = mf_p.n_ceps ? statics + at * d : const_cast<double *>(w.L);
         w.bs = bs + w.b0 * d;
         w.stat = stat + 2 * u * d;
+        // (the frames' energies of JB_FRAME_ENERGY: k_fbank writes them, k_ceps reads them, numbered as the statics)
+        w.e = mf.futts.host[u].e = energy ? en + at : nullptr;
         at += w.T;
     }
+    if (energy && !cls.geom.empty())
+        mf.P.e_floor = cls.geom[0].log_floor, mf.P.e_ln_floor = cls.geom[0].ln_floor;
     mf.P.Dt = dct;
     mf.P.lift = lift;
     if ((rc = upload_classes(cls, fo, "mfcc filterbank tables", "mfcc filterbank classes", &mf.classes_dev)) ||
@@ -1732,7 +1790,8 @@ int OutputChain::launch_mfcc(bool redo)
 {
     if (!mfcc() || (redo && !mf.utts.n))
         return JB_OK;
-    hipError_t e = jb::launch_fbank(mf.classes_dev, mf.futts.list, mf.futts.n, mf.futts.total, b.stream_voc);
+    hipError_t e = jb::launch_fbank(mf.classes_dev, mf.futts.list, mf.futts.n, mf.futts.total, b.stream_voc,
+                                    fr_on && !frame_is_identity(fr_p));
     if (e == hipSuccess)
         e = jb::launch_mfcc(mf.P, mf.utts.list, mf.utts.n, mf.utts.total, mf.take_blocks, b.stream_voc);
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "mfcc(redo)" : "mfcc");

@@ -214,6 +214,12 @@ class _Condition:
         """The impulse response (an _ffi.Fir: J.fir(taps, hz, delay)) of every entry's output, in front of the
         filter's sections; None for none.  The taps are copied."""
         F.check(self._L().jb_engine_set_fir(self._h(), None if f is None else C.byref(f)))
+    def set_frame(self, fr=None, **kw):
+        """The frame request (an _ffi.FrameOpts: J.frame(...), or its keywords) of every *_fbank and *_mfcc entry's
+        features; None without keywords for none."""
+        if fr is None and kw:
+            fr = F.frame(**kw)
+        F.check(self._L().jb_engine_set_frame_opts(self._h(), None if fr is None else C.byref(fr)))
     def set_room(self, room, vary=False, seed=0, margin=0.5):
         """The room (an _ffi.Room: J.room(size, source, mic, rt60=..., hz=..., n_taps=...)) of every entry's output,
         in the impulse response's place (the later of set_room and set_fir replaces the earlier); None for none.
@@ -330,6 +336,11 @@ class Engine:
     def set_fir(self, f):
         """jb_engine_set_fir (the Condition's setter, on the engine): an _ffi.Fir, or None for none."""
         self.condition.set_fir(f)
+
+    def set_frame(self, fr=None, **kw):
+        """jb_engine_set_frame_opts (the Condition's setter, on the engine): an _ffi.FrameOpts or the keywords of
+        J.frame, or None for none."""
+        self.condition.set_frame(fr, **kw)
 
     def set_room(self, room, vary=False, seed=0, margin=0.5):
         """jb_engine_set_room (the Condition's setter, on the engine): an _ffi.Room, or None for none; vary: positions
