@@ -1283,6 +1283,37 @@ def _take(free, bufs, ns, n, dtype=None):
     return out
 
 
+def _feature_pcm(entry: str, free: str, pcms, hz, opts, device: int, rows):
+    """A feature entry on caller-held PCM: `entry`(ins, nin, n, hzs, *opts, device, bufs, ns) over the float64 arrays
+    of `pcms` (or one array) at hz (one rate, or one per array), every output through rows(bytes) and released with
+    `free`.  A single array in gives a single array out."""
+    import numpy as np
+
+    single = isinstance(pcms, np.ndarray)
+    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    L = lib()
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    bufs, ns = (C.POINTER(C.c_uint8) * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    check(getattr(L, entry)(ins, nin, n, hzs, *[C.byref(o) for o in opts], device, bufs, ns))
+    res = [rows(d) for d in _take(getattr(L, free), bufs, ns, n)]
+    return res[0] if single else res
+
+
+def _feature_host(entry: str, pcm, hz: int, opts, size):
+    """A host entry into a sized byte buffer: `entry`(pcm, n, hz, *opts, out, size(n)) over float64 samples; the
+    bytes."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    nby = size(a.size)
+    out = np.empty(max(1, nby), dtype=np.uint8)
+    check(getattr(lib(), entry)(a.ctypes.data, a.size, hz, *[C.byref(o) for o in opts], out.ctypes.data, nby))
+    return out[:nby].tobytes()
+
+
 def loudness(pcms, hz: int, device: int = -1):
     """jb_loudness_pcm_batch: (lufs, peak_dbfs) of each float64 array of `pcms` (or of one array) at hz, on the GPU."""
     import numpy as np
@@ -1588,32 +1619,17 @@ def take_fbank(L, bufs, ns, n, opts: FbankOpts):
 
 def fbank_host(pcm, hz: int, opts: FbankOpts):
     """jb_fbank_host: the features [T, n_mels] of float64 samples in 16-bit scale, in plain C++ on the host (no GPU)."""
-    import numpy as np
+    return fbank_frames(_feature_host("jb_fbank_host", pcm, hz, (opts,), lambda n: fbank_geometry(hz, opts, n)[4]),
+                        opts)
 
-    a = np.ascontiguousarray(pcm, dtype=np.float64)
-    nby = fbank_geometry(hz, opts, a.size)[4]
-    out = np.empty(max(1, nby), dtype=np.uint8)
-    check(lib().jb_fbank_host(a.ctypes.data, a.size, hz, C.byref(opts), out.ctypes.data, nby))
-    return fbank_frames(out[:nby].tobytes(), opts)
 
 
 def fbank_pcm(pcms, hz, opts: FbankOpts, device: int = -1):
     """jb_fbank_pcm_batch: the features [T, n_mels] of each float64 array of `pcms` (or of one array) on the GPU; hz:
     one rate, or one per array."""
-    import numpy as np
+    return _feature_pcm("jb_fbank_pcm_batch", "jb_fbank_free", pcms, hz, (opts,), device,
+                        lambda d: fbank_frames(d, opts))
 
-    single = isinstance(pcms, np.ndarray)
-    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
-    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
-    if len(rates) != n:
-        raise ValueError("give one rate, or one per array")
-    L = lib()
-    u8p = C.POINTER(C.c_uint8)
-    hzs = (C.c_uint32 * max(n, 1))(*rates)
-    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-    check(L.jb_fbank_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, bufs, ns))
-    res = take_fbank(L, bufs, ns, n, opts)
-    return res[0] if single else res
 
 
 def fbank_framed_geometry(hz: int, opts: FbankOpts, fr: FrameOpts, n: int = 0):
@@ -1635,31 +1651,16 @@ def frame_window(hz: int, opts: FbankOpts, fr: FrameOpts):
 
 def fbank_framed_host(pcm, hz: int, opts: FbankOpts, fr: FrameOpts):
     """jb_fbank_framed_host: fbank_host under the frame request (no GPU)."""
-    import numpy as np
+    return fbank_frames(_feature_host("jb_fbank_framed_host", pcm, hz, (opts, fr),
+                                      lambda n: fbank_framed_geometry(hz, opts, fr, n)[4]), opts)
 
-    a = np.ascontiguousarray(pcm, dtype=np.float64)
-    nby = fbank_framed_geometry(hz, opts, fr, a.size)[4]
-    out = np.empty(max(1, nby), dtype=np.uint8)
-    check(lib().jb_fbank_framed_host(a.ctypes.data, a.size, hz, C.byref(opts), C.byref(fr), out.ctypes.data, nby))
-    return fbank_frames(out[:nby].tobytes(), opts)
 
 
 def fbank_framed_pcm(pcms, hz, opts: FbankOpts, fr: FrameOpts, device: int = -1):
     """jb_fbank_framed_pcm_batch: fbank_pcm under the frame request, on the GPU."""
-    import numpy as np
+    return _feature_pcm("jb_fbank_framed_pcm_batch", "jb_fbank_free", pcms, hz, (opts, fr), device,
+                        lambda d: fbank_frames(d, opts))
 
-    single = isinstance(pcms, np.ndarray)
-    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
-    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
-    if len(rates) != n:
-        raise ValueError("give one rate, or one per array")
-    L = lib()
-    u8p = C.POINTER(C.c_uint8)
-    hzs = (C.c_uint32 * max(n, 1))(*rates)
-    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-    check(L.jb_fbank_framed_pcm_batch(ins, nin, n, hzs, C.byref(opts), C.byref(fr), device, bufs, ns))
-    res = take_fbank(L, bufs, ns, n, opts)
-    return res[0] if single else res
 
 
 def melspec_geometry(hz: int, opts: MelspecOpts, n: int = 0):
@@ -1703,32 +1704,17 @@ def take_melspec(L, bufs, ns, n, opts: MelspecOpts):
 def melspec_host(pcm, hz: int, opts: MelspecOpts):
     """jb_melspec_host: the mel spectrogram [T, n_mels] of float64 samples in 16-bit scale, in plain C++ on the host
     (no GPU)."""
-    import numpy as np
+    return melspec_frames(_feature_host("jb_melspec_host", pcm, hz, (opts,),
+                                        lambda n: melspec_geometry(hz, opts, n)[4]), opts)
 
-    a = np.ascontiguousarray(pcm, dtype=np.float64)
-    nby = melspec_geometry(hz, opts, a.size)[4]
-    out = np.empty(max(1, nby), dtype=np.uint8)
-    check(lib().jb_melspec_host(a.ctypes.data, a.size, hz, C.byref(opts), out.ctypes.data, nby))
-    return melspec_frames(out[:nby].tobytes(), opts)
 
 
 def melspec_pcm(pcms, hz, opts: MelspecOpts, device: int = -1):
     """jb_melspec_pcm_batch: the mel spectrogram [T, n_mels] of each float64 array of `pcms` (or of one array) on the
     GPU; hz: one rate, or one per array."""
-    import numpy as np
+    return _feature_pcm("jb_melspec_pcm_batch", "jb_melspec_free", pcms, hz, (opts,), device,
+                        lambda d: melspec_frames(d, opts))
 
-    single = isinstance(pcms, np.ndarray)
-    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
-    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
-    if len(rates) != n:
-        raise ValueError("give one rate, or one per array")
-    L = lib()
-    u8p = C.POINTER(C.c_uint8)
-    hzs = (C.c_uint32 * max(n, 1))(*rates)
-    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-    check(L.jb_melspec_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, bufs, ns))
-    res = take_melspec(L, bufs, ns, n, opts)
-    return res[0] if single else res
 
 
 def mfcc_geometry(hz: int, fopts: FbankOpts, opts: MfccOpts, n: int = 0):
@@ -1791,13 +1777,9 @@ def mfcc_host(logmel, opts: MfccOpts):
 
 def mfcc_pcm_host(pcm, hz: int, fopts: FbankOpts, opts: MfccOpts):
     """jb_mfcc_pcm_host: the rows [T, width] of float64 samples in 16-bit scale, on the host (no GPU)."""
-    import numpy as np
+    return mfcc_rows(_feature_host("jb_mfcc_pcm_host", pcm, hz, (fopts, opts),
+                                   lambda n: mfcc_geometry(hz, fopts, opts, n)[2]), opts, fopts.n_mels)
 
-    a = np.ascontiguousarray(pcm, dtype=np.float64)
-    nby = mfcc_geometry(hz, fopts, opts, a.size)[2]
-    out = np.empty(max(1, nby), dtype=np.uint8)
-    check(lib().jb_mfcc_pcm_host(a.ctypes.data, a.size, hz, C.byref(fopts), C.byref(opts), out.ctypes.data, nby))
-    return mfcc_rows(out[:nby].tobytes(), opts, fopts.n_mels)
 
 
 def mfcc_frames(logmels, opts: MfccOpts, device: int = -1):
@@ -1823,51 +1805,25 @@ def mfcc_frames(logmels, opts: MfccOpts, device: int = -1):
 def mfcc_pcm(pcms, hz, fopts: FbankOpts, opts: MfccOpts, device: int = -1):
     """jb_mfcc_pcm_batch: the rows [T, width] of each float64 array of `pcms` (or of one array) on the GPU; hz: one
     rate, or one per array."""
-    import numpy as np
+    return _feature_pcm("jb_mfcc_pcm_batch", "jb_mfcc_free", pcms, hz, (fopts, opts), device,
+                        lambda d: mfcc_rows(d, opts, fopts.n_mels))
 
-    single = isinstance(pcms, np.ndarray)
-    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
-    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
-    if len(rates) != n:
-        raise ValueError("give one rate, or one per array")
-    L = lib()
-    u8p = C.POINTER(C.c_uint8)
-    hzs = (C.c_uint32 * max(n, 1))(*rates)
-    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-    check(L.jb_mfcc_pcm_batch(ins, nin, n, hzs, C.byref(fopts), C.byref(opts), device, bufs, ns))
-    res = [mfcc_rows(d, opts, fopts.n_mels) for d in _take(L.jb_mfcc_free, bufs, ns, n)]
-    return res[0] if single else res
 
 
 def mfcc_framed_pcm_host(pcm, hz: int, fopts: FbankOpts, opts: MfccOpts, fr: FrameOpts):
     """jb_mfcc_framed_pcm_host: mfcc_pcm_host under the frame request (no GPU)."""
-    import numpy as np
+    def size(n):
+        return fbank_framed_geometry(hz, fopts, fr, n)[3] * opts.width(fopts.n_mels) * opts.dtype.itemsize
 
-    a = np.ascontiguousarray(pcm, dtype=np.float64)
-    T = fbank_framed_geometry(hz, fopts, fr, a.size)[3]
-    nby = T * opts.width(fopts.n_mels) * opts.dtype.itemsize
-    out = np.empty(max(1, nby), dtype=np.uint8)
-    check(lib().jb_mfcc_framed_pcm_host(a.ctypes.data, a.size, hz, C.byref(fopts), C.byref(opts), C.byref(fr),
-                                        out.ctypes.data, nby))
-    return mfcc_rows(out[:nby].tobytes(), opts, fopts.n_mels)
+    return mfcc_rows(_feature_host("jb_mfcc_framed_pcm_host", pcm, hz, (fopts, opts, fr), size), opts, fopts.n_mels)
+
 
 
 def mfcc_framed_pcm(pcms, hz, fopts: FbankOpts, opts: MfccOpts, fr: FrameOpts, device: int = -1):
     """jb_mfcc_framed_pcm_batch: mfcc_pcm under the frame request, on the GPU."""
-    import numpy as np
+    return _feature_pcm("jb_mfcc_framed_pcm_batch", "jb_mfcc_free", pcms, hz, (fopts, opts, fr), device,
+                        lambda d: mfcc_rows(d, opts, fopts.n_mels))
 
-    single = isinstance(pcms, np.ndarray)
-    arrs, n, ins, nin = _pcm_args([pcms] if single else pcms, np.float64)
-    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
-    if len(rates) != n:
-        raise ValueError("give one rate, or one per array")
-    L = lib()
-    u8p = C.POINTER(C.c_uint8)
-    hzs = (C.c_uint32 * max(n, 1))(*rates)
-    bufs, ns = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-    check(L.jb_mfcc_framed_pcm_batch(ins, nin, n, hzs, C.byref(fopts), C.byref(opts), C.byref(fr), device, bufs, ns))
-    res = [mfcc_rows(d, opts, fopts.n_mels) for d in _take(L.jb_mfcc_free, bufs, ns, n)]
-    return res[0] if single else res
 
 
 def write_wav_adpcm(path, data: bytes, n_samples: int, sampling_frequency: int, block_align: int) -> None:

@@ -1,7 +1,8 @@
-// jb_fbank.cpp -- the host half of the filterbank features and of their frame conditioning (jb_fbank_framed_host, the
-// request's window, check and Kaldi defaults): the option check, the geometry, the three tables (window,
-// twiddles, mel weights; long double, rounded once) and the rule of jb_fbank.h over PCM the caller holds without a GPU
-// (jb_fbank_host, what the kernel is checked against).
+// jb_fbank.cpp -- the host half of the filterbank features and of their frame conditioning (the request's window, check
+// and Kaldi defaults): the option check, the geometry, the three tables (window, twiddles, mel weights; long double,
+// rounded once) and the rule of jb_fbank.h over PCM the caller holds without a GPU, what the kernel is checked against:
+// one body, fbank_framed_host, under jb_fbank_framed_host and -- with the all-zero request (jb_fbank.h "Frame
+// conditioning") -- under jb_fbank_host; the two geometry entries share geometry_out the same way.
 #include "jb_host.h"
 #include "jb_mfcc.h"
 
@@ -33,7 +34,7 @@ namespace {
 
 inline long double mel_of(long double f) { return 1127.0L * logl(1.0L + f / 700.0L); }
 
-// One frame by the rule: x[0..wl) windowed (a null sample pointer: zeros) -> E[0..n_mels)
+// One frame by the rule: z[0..wl) windowed already -> E[0..n_mels)
 struct HostFrame {
     const FbankGeom &g;
     const FbankTables &t;
@@ -42,15 +43,7 @@ struct HostFrame {
         : g(geom), t(tab), re(geom.n_fft / 2 + 1, 0.0), im(geom.n_fft / 2 + 1, 0.0)
     {
     }
-    // sample i of the frame, i < n_fft: x(i) windowed, 0 from wl on
-    template <class X> void run(X x, double *E)
-    {
-        rfft_frame_power(t.fft, [&](uint32_t i) { return i < g.wl ? t.win[i] * x(i) : 0.0; }, re.data(), im.data());
-        for (uint32_t m = 0; m < g.n_mels; m++)
-            E[m] = mel_bank_energy(t.bank, m, re.data());
-    }
-    // ... of a frame that is windowed already: z[0..wl)
-    void run_windowed(const double *z, double *E)
+    void run(const double *z, double *E)
     {
         rfft_frame_power(t.fft, [&](uint32_t i) { return i < g.wl ? z[i] : 0.0; }, re.data(), im.data());
         for (uint32_t m = 0; m < g.n_mels; m++)
@@ -58,16 +51,26 @@ struct HostFrame {
     }
 };
 
-// Element [t][m] of the output from the filter's energy
-void put_element(const FbankOpts &o, const FbankGeom &g, double E, uint8_t *out, size_t at)
+// jb_fbank_geometry's body under the frame request fr (none: FrameOpts{}), the refusals under `who`
+int geometry_out(uint32_t hz, const FbankOpts *o, const FrameOpts &fr, size_t n, uint32_t *wl, uint32_t *hop,
+                 uint32_t *n_fft, size_t *T, size_t *n_bytes, const char *who)
 {
-    const double v = (o.flags & kFbLinear) ? E : E > g.log_floor ? log(E) : g.ln_floor;
-    if (o.flags & kFbF64)
-        memcpy(out + at * 8, &v, 8);
-    else {
-        const float f = (float)v;
-        memcpy(out + at * 4, &f, 4);
-    }
+    FbankGeom g{};
+    const int rc = fbank_geometry(o, hz, who, &g);
+    if (rc)
+        return rc;
+    const uint64_t frames = frame_count(n, g, *o, fr);
+    if (wl)
+        *wl = g.wl;
+    if (hop)
+        *hop = g.hop;
+    if (n_fft)
+        *n_fft = g.n_fft;
+    if (T)
+        *T = (size_t)frames;
+    if (n_bytes)
+        *n_bytes = (size_t)(frames * g.n_mels * fbank_elem(o->flags));
+    return JB_OK;
 }
 
 } // namespace
@@ -140,15 +143,16 @@ int frame_check(const FbankOpts *opts, const FrameOpts *fr, bool cepstra, const 
     return JB_OK;
 }
 
-int fbank_framed_host(const double *in, size_t n, uint32_t hz, const FbankOpts &o, const FrameOpts &fr, uint8_t *out,
+int fbank_framed_host(const double *in, size_t n, uint32_t hz, const FbankOpts *opts, const FrameOpts &fr, uint8_t *out,
                       size_t cap, const char *who, std::vector<double> *energy)
 {
     FbankGeom g{};
-    const int rc = fbank_geometry(&o, hz, who, &g);
+    const int rc = fbank_geometry(opts, hz, who, &g);
     if (rc)
         return rc;
+    const FbankOpts &o = *opts;
     const bool center = (o.flags & kFbCenter) != 0, reflect = (fr.flags & kFrReflect) != 0;
-    const uint64_t T = frame_count(n, g.wl, g.hop, center, reflect);
+    const uint64_t T = frame_count(n, g, o, fr);
     if (cap < T * g.n_mels * fbank_elem(o.flags)) {
         set_error(std::string(who) + ": the buffer is too small");
         return JB_ERR_BUFFER;
@@ -170,9 +174,11 @@ int fbank_framed_host(const double *in, size_t n, uint32_t hz, const FbankOpts &
             v[i] = reflect ? in[frame_reflect(k, n)] * scale : k >= 0 && (uint64_t)k < n ? in[k] * scale : 0.0;
         }
         frame_condition(fr, tab.win.data(), g.wl, v.data(), energy ? &(*energy)[t] : nullptr);
-        hf.run_windowed(v.data(), E.data());
-        for (uint32_t m = 0; m < g.n_mels; m++)
-            put_element(o, g, E[m], out, (size_t)t * g.n_mels + m);
+        hf.run(v.data(), E.data());
+        for (uint32_t m = 0; m < g.n_mels; m++) {
+            const double y = (o.flags & kFbLinear) ? E[m] : E[m] > g.log_floor ? log(E[m]) : g.ln_floor;
+            put_elem(out, (size_t)t * g.n_mels + m, y, (o.flags & kFbF64) != 0);
+        }
     }
     return JB_OK;
 }
@@ -222,22 +228,7 @@ extern "C" {
 int jb_fbank_geometry(uint32_t hz, const jb_fbank_opts *opts, size_t n, uint32_t *wl, uint32_t *hop, uint32_t *n_fft,
                       size_t *T, size_t *n_bytes)
 {
-    FbankGeom g{};
-    const int rc = fbank_geometry((const FbankOpts *)opts, hz, "jb_fbank_geometry", &g);
-    if (rc)
-        return rc;
-    const uint64_t frames = fbank_frames(n, g.wl, g.hop, (opts->flags & kFbCenter) != 0);
-    if (wl)
-        *wl = g.wl;
-    if (hop)
-        *hop = g.hop;
-    if (n_fft)
-        *n_fft = g.n_fft;
-    if (T)
-        *T = (size_t)frames;
-    if (n_bytes)
-        *n_bytes = (size_t)(frames * g.n_mels * fbank_elem(opts->flags));
-    return JB_OK;
+    return geometry_out(hz, (const FbankOpts *)opts, FrameOpts{}, n, wl, hop, n_fft, T, n_bytes, "jb_fbank_geometry");
 }
 
 int jb_fbank_window(uint32_t hz, const jb_fbank_opts *opts, double *w, size_t cap)
@@ -274,43 +265,7 @@ int jb_fbank_filterbank(uint32_t hz, const jb_fbank_opts *opts, double *W, size_
 
 int jb_fbank_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *opts, uint8_t *out, size_t cap)
 {
-    FbankGeom g{};
-    const int rc = fbank_geometry((const FbankOpts *)opts, hz, "jb_fbank_host", &g);
-    if (rc)
-        return rc;
-    const bool center = (opts->flags & kFbCenter) != 0;
-    const uint64_t T = fbank_frames(n, g.wl, g.hop, center);
-    if (cap < T * g.n_mels * fbank_elem(opts->flags)) {
-        set_error("jb_fbank_host: the buffer is too small");
-        return JB_ERR_BUFFER;
-    }
-    if (n && (!in || (T && !out)))
-        return JB_ERR_INVALID;
-    FbankTables tab;
-    fbank_tables(g, hz, opts->window, &tab);
-    HostFrame fr(g, tab);
-    std::vector<double> E(g.n_mels);
-    const double scale = (opts->flags & kFbUnit) ? 0x1p-15 : 1.0;
-    for (uint64_t t = 0; t < T; t++) {
-        const int64_t k0 = (int64_t)(t * g.hop) - (center ? (int64_t)(g.wl / 2) : 0);
-        fr.run(
-            [&](uint32_t i) {
-                const int64_t k = k0 + (int64_t)i;
-                return k >= 0 && (uint64_t)k < n ? in[k] * scale : 0.0;
-            },
-            E.data());
-        for (uint32_t m = 0; m < g.n_mels; m++) {
-            const double v = (opts->flags & kFbLinear) ? E[m] : E[m] > g.log_floor ? log(E[m]) : g.ln_floor;
-            const size_t at = (size_t)t * g.n_mels + m;
-            if (opts->flags & kFbF64)
-                memcpy(out + at * 8, &v, 8);
-            else {
-                const float f = (float)v;
-                memcpy(out + at * 4, &f, 4);
-            }
-        }
-    }
-    return JB_OK;
+    return fbank_framed_host(in, n, hz, (const FbankOpts *)opts, FrameOpts{}, out, cap, "jb_fbank_host", nullptr);
 }
 
 int jb_frame_kaldi(uint32_t n_mels, jb_fbank_opts *f, jb_frame_opts *fr)
@@ -349,17 +304,11 @@ int jb_frame_check(const jb_fbank_opts *fopts, const jb_mfcc_opts *mopts, const 
 int jb_fbank_framed_geometry(uint32_t hz, const jb_fbank_opts *opts, const jb_frame_opts *fr, size_t n, uint32_t *wl,
                              uint32_t *hop, uint32_t *n_fft, size_t *T, size_t *n_bytes)
 {
-    int rc = frame_check((const FbankOpts *)opts, (const FrameOpts *)fr, true, "jb_fbank_framed_geometry");
-    if (rc || (rc = jb_fbank_geometry(hz, opts, n, wl, hop, n_fft, T, n_bytes)) || !(fr->flags & kFrReflect))
-        return rc;
-    FbankGeom g{};
-    fbank_geometry_fault(*(const FbankOpts *)opts, hz, &g);
-    const uint64_t frames = frame_count(n, g.wl, g.hop, false, true);
-    if (T)
-        *T = (size_t)frames;
-    if (n_bytes)
-        *n_bytes = (size_t)(frames * g.n_mels * fbank_elem(opts->flags));
-    return JB_OK;
+    const int rc = frame_check((const FbankOpts *)opts, (const FrameOpts *)fr, true, "jb_fbank_framed_geometry");
+    // (what the rate refuses keeps jb_fbank_geometry's name, as it always had)
+    return rc ? rc
+              : geometry_out(hz, (const FbankOpts *)opts, *(const FrameOpts *)fr, n, wl, hop, n_fft, T, n_bytes,
+                             "jb_fbank_geometry");
 }
 
 int jb_frame_window(uint32_t hz, const jb_fbank_opts *opts, const jb_frame_opts *fr, double *w, size_t cap)
@@ -379,9 +328,7 @@ int jb_fbank_framed_host(const double *in, size_t n, uint32_t hz, const jb_fbank
     const int rc = frame_check((const FbankOpts *)opts, (const FrameOpts *)fr, false, "jb_fbank_framed_host");
     if (rc)
         return rc;
-    if (frame_is_identity(*(const FrameOpts *)fr))
-        return jb_fbank_host(in, n, hz, opts, out, cap);
-    return fbank_framed_host(in, n, hz, *(const FbankOpts *)opts, *(const FrameOpts *)fr, out, cap,
+    return fbank_framed_host(in, n, hz, (const FbankOpts *)opts, *(const FrameOpts *)fr, out, cap,
                              "jb_fbank_framed_host", nullptr);
 }
 

@@ -38,11 +38,6 @@ struct FbankGeom {
     double ln_floor; // ln(log_floor) in long double, rounded once: what an energy at or below the floor gives
 };
 constexpr uint64_t fbank_round_us(uint32_t hz, uint32_t us) { return ((uint64_t)hz * us + 500000) / 1000000; }
-// T of n samples
-constexpr uint64_t fbank_frames(uint64_t n, uint32_t wl, uint32_t hop, bool center)
-{
-    return center ? (n + hop - 1) / hop : n >= wl ? 1 + (n - wl) / hop : 0;
-}
 constexpr uint64_t fbank_elem(uint32_t flags) { return (flags & kFbF64) ? 8 : 4; }
 
 // What is wrong with the options whatever the rate (a bad window, flag or reserved word, a log_floor that is no
@@ -115,7 +110,10 @@ int fbank_check_opts(const FbankOpts *opts, const char *who);
 int fbank_geometry(const FbankOpts *opts, uint32_t hz, const char *who, FbankGeom *g);
 
 // Frame conditioning (include/jbonsai_amd.h "Frame conditioning"): jb_frame_opts restated, and the rule's pieces that
-// the kernel, the host form and the plan share
+// the kernel, the host form and the plan share.
+// A plain request is the all-zero frame request: under FrameOpts{} frame_count and frame_start are the plain stage's
+// and frame_condition leaves win[i] * v_i, so the host holds one rule and the entries without a request run it with
+// FrameOpts{}.  Only the device asks frame_is_identity, to pick the loader without the conditioning's two barriers
 struct FrameOpts {
     double preemph;
     uint32_t window, flags;
@@ -126,7 +124,7 @@ static_assert(sizeof(FrameOpts) == 32 && offsetof(FrameOpts, window) == 8 && off
 constexpr uint32_t kFrWindowOpts = 0, kFrPovey = 1, kFrHannSym = 2, kFrRect = 3, kFrBlackman = 4; // JB_FRAME_POVEY, ..
 constexpr uint32_t kFrRemoveDc = 1, kFrReflect = 2, kFrEnergy = 4; // JB_FRAME_REMOVE_DC, _REFLECT, _ENERGY
 
-// The zero request is the identity: the stage then runs as without one
+// The zero request is the identity: the device then runs k_fbank<false> (rate_launch, jb_host.h)
 inline bool frame_is_identity(const FrameOpts &f)
 {
     return f.preemph == 0.0 && f.window == kFrWindowOpts && f.flags == 0;
@@ -157,7 +155,11 @@ inline const char *frame_pair_fault(const FbankOpts &o, const FrameOpts &f, bool
 // JB_FRAME_REFLECT
 constexpr uint64_t frame_count(uint64_t n, uint32_t wl, uint32_t hop, bool center, bool reflect)
 {
-    return reflect ? (n + hop / 2) / hop : fbank_frames(n, wl, hop, center);
+    return reflect ? (n + hop / 2) / hop : center ? (n + hop - 1) / hop : n >= wl ? 1 + (n - wl) / hop : 0;
+}
+constexpr uint64_t frame_count(uint64_t n, const FbankGeom &g, const FbankOpts &o, const FrameOpts &f)
+{
+    return frame_count(n, g.wl, g.hop, (o.flags & kFbCenter) != 0, (f.flags & kFrReflect) != 0);
 }
 JB_RFFT_HD constexpr int64_t frame_start(uint64_t t, uint32_t wl, uint32_t hop, bool center, bool reflect)
 {
@@ -209,8 +211,9 @@ inline void frame_condition(const FrameOpts &f, const double *win, uint32_t wl, 
 void frame_window(uint32_t fbank_window, uint32_t frame_window, uint32_t wl, double *w);
 // JB_OK, or JB_ERR_INVALID with set_error naming the field: the filterbank options, the request and the pair
 int frame_check(const FbankOpts *opts, const FrameOpts *fr, bool cepstra, const char *who);
-// The conditioned rule on the host (jb_fbank_framed_host's body); energy: the frames' energies of step 3 (may be null)
-int fbank_framed_host(const double *in, size_t n, uint32_t hz, const FbankOpts &o, const FrameOpts &fr, uint8_t *out,
+// The rule on the host under the name of the entry `who` (jb_fbank_host's body with FrameOpts{}, jb_fbank_framed_host's
+// with its request); o is checked here (null: refused); energy: the frames' energies of step 3 (may be null)
+int fbank_framed_host(const double *in, size_t n, uint32_t hz, const FbankOpts *o, const FrameOpts &fr, uint8_t *out,
                       size_t cap, const char *who, std::vector<double> *energy);
 
 // The tables of one geometry, built in long double and rounded once

@@ -20,6 +20,8 @@
 //             DC removal, the frame's energy, pre-emphasis and the request's window in front of the same transform.
 //             Every operation of a frame is its own butterfly, pair, bin or filter: its order does not depend on the
 //             lanes that share the frame, on the frame's place in the workgroup or on the batch.
+// The launch list -- classes, units, g0, the workgroup count and the choice of loader -- is RatePass's (jb_host.h), for
+// the entries below and for a batch's output chain alike.
 #include "jb_host.h"
 #include "jb_rfft_dev.h"
 
@@ -325,19 +327,19 @@ void FbankClasses::bind(const FbankOpts &opts, const double *dev, std::vector<do
 
 namespace {
 
-// The seam's body: opts with the frame request fr (all zero: none), under the entry's name
+// The seam's body: opts with the frame request fr (all zero: none), under the entry's name -- check, put the pass
+// together (RatePass, jb_host.h), attach the units' pointers, launch, hand out
 int fbank_pcm_run(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz, const FbankOpts *o,
                   const FrameOpts &fr, int32_t device, uint8_t **out, size_t *n_bytes, const char *who)
 {
     int rc = pcm_check((const void *const *)in, n_in, n, hz && out && n_bytes, (void **)out, n_bytes);
     if (rc)
         return rc;
-    // (every rate's geometry before a device is touched)
-    FbankClasses cls;
-    cls.cond = fr;
-    std::vector<FbankUtt> utts(n);
+    // (every rate's geometry and every unit's frames before a device is touched)
+    FbankPass pass;
+    pass.start(*o, fr);
     for (size_t u = 0; u < n; u++)
-        if ((rc = cls.find(*o, hz[u], who, &utts[u].cls)))
+        if ((rc = pass.add(hz[u], n_in[u], who)))
             return rc;
     DeviceScratch ds;
     if ((rc = ds.open(device, who)))
@@ -347,33 +349,19 @@ int fbank_pcm_run(const double *const *in, const size_t *n_in, size_t n, const u
     std::vector<uint64_t> xoff;
     const double *dx = ds.pack(in, n_in, n, &xoff);
     std::vector<PcmShare> shares(n);
-    const bool center = (o->flags & kFbCenter) != 0, reflect = (fr.flags & kFrReflect) != 0;
-    uint64_t bytes = 0, groups = 0;
+    uint64_t bytes = 0;
     for (size_t u = 0; u < n; u++) {
-        FbankUtt &w = utts[u];
-        const FbankGeom &g = cls.geom[w.cls];
-        w.n = n_in[u];
-        w.T = frame_count(w.n, g.wl, g.hop, center, reflect);
-        w.g0 = groups;
-        shares[u] = {bytes, w.T * g.n_mels * fbank_elem(o->flags)};
+        shares[u] = {bytes, pass.list.host[u].T * o->n_mels * fbank_elem(o->flags)};
         bytes += (shares[u].n + 15) & ~(uint64_t)15;
-        groups += (w.T + fbank_wg_frames(g.n_fft) - 1) / fbank_wg_frames(g.n_fft);
     }
     uint8_t *dy = ds.alloc<uint8_t>(std::max<uint64_t>(bytes, 16));
     for (size_t u = 0; u < n; u++) {
-        utts[u].x = dx + xoff[u];
-        utts[u].y = dy + shares[u].off;
+        pass.list.host[u].x = dx + xoff[u];
+        pass.list.host[u].y = dy + shares[u].off;
     }
-    double *dt = ds.alloc<double>(cls.words());
-    std::vector<double> image;
-    std::vector<FbankClass> classes;
-    cls.bind(*o, dt, &image, &classes);
-    if (ds.ok() && !image.empty())
-        ds.err = hipMemcpyAsync(dt, image.data(), sizeof(double) * image.size(), hipMemcpyHostToDevice, ds.stream);
-    const FbankClass *dc = ds.upload(classes);
-    const FbankUtt *du = ds.upload(utts);
+    pass.bind(ds, who);
     if (ds.ok())
-        ds.err = launch_fbank(dc, du, (uint32_t)n, groups, ds.stream, !frame_is_identity(fr));
+        ds.err = pass.launch(ds.stream);
     std::vector<uint8_t> host;
     ds.read_back(&host, dy, bytes);
     if ((rc = ds.status()))

@@ -290,10 +290,15 @@ hipError_t launch_format(uint32_t format, uint32_t dither, uint64_t seed, const 
 hipError_t launch_adpcm(bool i16, const AdpcmUtt *utts_dev, uint32_t n, uint64_t groups, hipStream_t stream);
 
 // The distinct geometries of a launch of the filterbank features or the mel spectrograms, one per rate: their tables
-// on the host.  A stage states its geometry and its tables (rate_geometry, rate_tables) and the body of bind
+// on the host.  A stage states its geometry and its tables (rate_geometry, rate_tables), the body of bind and, for the
+// pass that RatePass below puts together, a unit's frames, the frames of a workgroup and the launch (rate_frames,
+// rate_wg_frames, rate_launch)
 struct RateNoCond {};
 template <class Opts, class Geom, class Tables, class Class, class Cond = RateNoCond> struct RateClasses {
-    Cond cond{}; // what conditions every class of the launch beside the options (set before the first find)
+    typedef Opts opts_type;
+    typedef Class class_type;
+    typedef Cond cond_type;
+    Cond cond{}; // what conditions every class of the launch beside the options (RatePass::start sets it)
     std::vector<uint32_t> key_hz;
     std::vector<Geom> geom;
     std::vector<Tables> tables;
@@ -350,7 +355,18 @@ void FbankClasses::bind(const FbankOpts &opts, const double *dev, std::vector<do
                         std::vector<FbankClass> *out) const;
 // utts_dev[0..n) of `groups` workgroups in all; framed: the classes carry a frame request (the conditioned loader)
 hipError_t launch_fbank(const FbankClass *classes_dev, const FbankUtt *utts_dev, uint32_t n, uint64_t groups,
-                        hipStream_t stream, bool framed = false);
+                        hipStream_t stream, bool framed);
+inline uint64_t rate_frames(const FbankOpts &o, const FrameOpts &fr, const FbankGeom &g, uint64_t n)
+{
+    return frame_count(n, g, o, fr);
+}
+inline uint32_t rate_wg_frames(const FbankGeom &g) { return fbank_wg_frames(g.n_fft); }
+// (the one place that decides between k_fbank<false> and k_fbank<true>: jb_fbank.h "Frame conditioning")
+inline hipError_t rate_launch(const FbankOpts &, const FrameOpts &fr, const FbankClass *classes_dev,
+                              const FbankUtt *utts_dev, uint32_t n, uint64_t groups, hipStream_t stream)
+{
+    return launch_fbank(classes_dev, utts_dev, n, groups, stream, !frame_is_identity(fr));
+}
 
 // Mel spectrograms (jb_melspec.hip; the rule, MelClass and MelUtt: jb_melspec.h; the host half: jb_melspec.cpp)
 inline int rate_geometry(const MelOpts *o, uint32_t hz, const char *who, MelGeom *g)
@@ -369,6 +385,16 @@ void MelClasses::bind(const MelOpts &opts, const double *dev, std::vector<double
 // k_melspec_finish behind k_melspec: gmax one double per workgroup, umax one per unit (scratch; else unused)
 hipError_t launch_melspec(const MelClass *classes_dev, const MelUtt *utts_dev, uint32_t n, uint64_t groups, bool ranged,
                           double *gmax, double *umax, hipStream_t stream);
+inline uint64_t rate_frames(const MelOpts &o, const RateNoCond &, const MelGeom &g, uint64_t n)
+{
+    return mel_frames(n, g.n_fft, g.hop, o.pad, o.flags);
+}
+inline uint32_t rate_wg_frames(const MelGeom &g) { return mel_wg_frames(g.n_fft); }
+inline hipError_t rate_launch(const MelOpts &o, const RateNoCond &, const MelClass *classes_dev, const MelUtt *utts_dev,
+                              uint32_t n, uint64_t groups, hipStream_t stream, double *gmax, double *umax)
+{
+    return launch_melspec(classes_dev, utts_dev, n, groups, o.range > 0.0, gmax, umax, stream);
+}
 
 // Cepstral features (jb_mfcc.hip; the rule, MfccParams and MfccUtt: jb_mfcc.h; the host half: jb_mfcc.cpp):
 // utts_dev[0..n) of `tiles` frame tiles and `blocks` statistics blocks in all; k_ceps (with n_ceps), the statistics'
@@ -598,9 +624,21 @@ struct DeviceScratch {
     template <class T> T *upload(const std::vector<T> &v)
     {
         T *p = alloc<T>(v.size());
-        if (ok() && !v.empty())
-            err = hipMemcpyAsync(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, stream);
+        put(p, v, who);
         return p;
+    }
+    // alloc and the copy of upload as a Batch spells them (dalloc, put): what RatePass::bind stores through.  JB_OK
+    // always: the error waits in `err`
+    template <class T> int dalloc(T **p, size_t n, bool)
+    {
+        *p = alloc<T>(n);
+        return JB_OK;
+    }
+    template <class T> int put(T *dst, const std::vector<T> &v, const char *)
+    {
+        if (ok() && !v.empty())
+            err = hipMemcpyAsync(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, stream);
+        return JB_OK;
     }
     // The inputs one after the other in one slab (*off: pcm_pack), each on its way into it
     template <class T> T *pack(const T *const *in, const size_t *n_in, size_t n, std::vector<uint64_t> *off)
@@ -679,6 +717,74 @@ template <class T> struct DevList {
         return upload_list(redo, v, what);
     }
 };
+
+// One pass of a rate-classed stage (the filterbank features, the mel spectrograms) put together on the host, for the
+// entries on caller-held PCM and for a batch's output chain alike: the classes under the launch's condition, the unit
+// list (class, n, T and g0, the prefix sum of the workgroups), each unit's workgroups -- what a redo renumbers from --
+// and their sum.  start, add per unit, attach the units' pointers (list.host[u]), bind, launch
+template <class Classes, class Utt> struct RatePass {
+    typedef typename Classes::opts_type Opts;
+    typedef typename Classes::class_type Class;
+    typedef Utt Unit;
+    static constexpr uint64_t kByRule = ~0ull;
+    Opts opts{};
+    Classes cls;
+    DevList<Utt> list;             // host: the units in their order
+    std::vector<uint64_t> ngroups; // each unit's workgroups
+    uint64_t groups = 0;
+    const Class *classes_dev = nullptr;
+    std::vector<double> image; // the tables and the classes as bind sent them: they live to the wait of a store
+    std::vector<Class> classes; // that copies behind the call
+    void start(const Opts &o, const typename Classes::cond_type &cond = {})
+    {
+        *this = RatePass{};
+        opts = o;
+        cls.cond = cond;
+    }
+    // A unit of n samples at hz behind those added so far; T: its frames where the caller's plan holds them.
+    // JB_ERR_INVALID naming the field that is out of its limits at hz; touches no device
+    int add(uint32_t hz, uint64_t n, const char *who, uint64_t T = kByRule)
+    {
+        Utt w{};
+        const int rc = cls.find(opts, hz, who, &w.cls);
+        if (rc)
+            return rc;
+        const auto &g = cls.geom[w.cls];
+        w.n = n;
+        w.T = T == kByRule ? rate_frames(opts, cls.cond, g, n) : T;
+        w.g0 = groups;
+        ngroups.push_back((w.T + rate_wg_frames(g) - 1) / rate_wg_frames(g));
+        groups += ngroups.back();
+        list.host.push_back(w);
+        return JB_OK;
+    }
+    // The classes' tables in a block of their own, the classes that point into it and the unit list, through `st` (a
+    // DeviceScratch or a Batch: dalloc and put; what: the stage's name in a failure's text); the next launch takes the
+    // whole list
+    template <class Store> int bind(Store &st, const std::string &what)
+    {
+        double *tables = nullptr;
+        Class *cd = nullptr;
+        int rc = st.dalloc(&tables, cls.words(), false);
+        if (rc)
+            return rc;
+        cls.bind(opts, tables, &image, &classes);
+        if ((rc = st.put(tables, image, (what + " tables").c_str())) ||
+            (rc = st.dalloc(&cd, classes.size(), false)) || (rc = st.put(cd, classes, (what + " classes").c_str())) ||
+            (rc = st.dalloc(&list.dev, list.host.size(), false)) ||
+            (rc = st.put(list.dev, list.host, (what + " work list").c_str())))
+            return rc;
+        classes_dev = cd;
+        return list.take_all(groups);
+    }
+    // what list.take_all or list.upload_redo chose; extra: what the stage's launch takes beside the lists
+    template <class... Extra> hipError_t launch(hipStream_t stream, Extra... extra) const
+    {
+        return rate_launch(opts, cls.cond, classes_dev, list.list, list.n, list.total, stream, extra...);
+    }
+};
+typedef RatePass<FbankClasses, FbankUtt> FbankPass;
+typedef RatePass<MelClasses, MelUtt> MelPass;
 
 // The stages behind the vocoder of one batch, in their order -- the converter (jb_batch_set_output_rate), the filter
 // (jb_batch_set_filter), loudness (jb_batch_set_loudness_target, with peak mode, groups and the R128 report), the
@@ -931,26 +1037,17 @@ private:
         std::vector<uint64_t> ngroups; // [U] each unit's groups of kAdpcmLanes blocks
         uint64_t groups = 0;
     } ad;
-    struct Fbank { // follows `units`
-        DevList<FbankUtt> utts;
-        std::vector<uint64_t> ngroups; // [U] each unit's workgroups
-        uint64_t groups = 0;
-        FbankClass *classes_dev = nullptr;
-    } fb;
+    FbankPass fb; // follows `units`
     struct Mfcc { // follows `units`: the filterbank pass into the log-mel scratch, then the cepstral kernels
-        DevList<FbankUtt> futts;
-        DevList<MfccUtt> utts;                    // total: the frame tiles
-        std::vector<uint64_t> ngroups, ntiles, nblocks; // [U] each unit's filterbank workgroups, frame tiles, blocks
-        uint64_t groups = 0, tiles = 0, blocks = 0;
-        uint64_t take_blocks = 0;                 // the blocks of the next launch's list
-        FbankClass *classes_dev = nullptr;
+        FbankPass fbank;
+        DevList<MfccUtt> utts;                  // total: the frame tiles
+        std::vector<uint64_t> ntiles, nblocks;  // [U] each unit's frame tiles, blocks
+        uint64_t tiles = 0, blocks = 0;
+        uint64_t take_blocks = 0;               // the blocks of the next launch's list
         MfccParams P{};
     } mf;
     struct Melspec { // follows `units`: k_melspec, and with a range the fold of the maxima and the finish pass
-        DevList<MelUtt> utts;
-        std::vector<uint64_t> ngroups; // [U] each unit's workgroups
-        uint64_t groups = 0;
-        MelClass *classes_dev = nullptr;
+        MelPass pass;
         double *gmax = nullptr, *umax = nullptr; // with a range: one double per workgroup, one per unit
     } ml;
     // the units the encoders take: the programmes in the join slab, or the utterances
@@ -982,12 +1079,16 @@ private:
     bool fbank() const { return plan.fbank_src != OutSlab::None; }
     bool mfcc() const { return plan.mfcc_src != OutSlab::None; }
     bool melspec() const { return plan.melspec_src != OutSlab::None; }
-    int check_melspec(const MelOpts &opts, const std::vector<uint32_t> &want, const char *who) const;
+    // a feature request (FbankOpts, MelOpts) under these rates: JB_ERR_INVALID naming the field that is out of its
+    // limits at some rate
+    template <class Opts> int check_rates(const Opts &opts, const std::vector<uint32_t> &want, const char *who) const;
     int check_mfcc(const FbankOpts &fopts, const std::vector<uint32_t> &want, const char *who) const;
+    // what the three feature setters refuse alike: a batch without PCM, a 16-bit one (`noun` stage reads the f64
+    // output), a batch that has run
+    int check_feature_settable(const char *entry, const char *noun) const;
     // the frame request fr (null: none) beside an fbank request fb and an mfcc request (mfb, mp), each null: none
     int check_frame(const FrameOpts *fr, const FbankOpts *fb, const FbankOpts *mfb, const MfccOpts *mp,
                     const char *who) const;
-    int check_fbank(const FbankOpts &opts, const std::vector<uint32_t> &want, const char *who) const;
     void replan(); // host geometry and routing of the present requests
     // v[0..n), n == 1 or B, as [B] values; false (set_error(err)) for anything else
     template <class T> bool broadcast(const T *v, size_t n, std::vector<T> *out, const char *err) const;
@@ -1016,11 +1117,6 @@ private:
     int prepare_flac(), select_flac(const RedoScope *scope), launch_flac(bool redo);
     int prepare_format(), select_format(const RedoScope *scope), launch_format(bool redo);
     int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);
-    // The tables of a class cache on the device: their image in a block of its own, then the classes that point into
-    // it at *classes_dev (what_tables, what_classes: their names in a failure's text)
-    template <class Classes, class Opts, class Class>
-    int upload_classes(const Classes &cls, const Opts &opts, const char *what_tables, const char *what_classes,
-                       Class **classes_dev);
     int prepare_fbank(), select_fbank(const RedoScope *scope), launch_fbank(bool redo);
     int prepare_mfcc(), select_mfcc(const RedoScope *scope), launch_mfcc(bool redo);
     int prepare_melspec(), select_melspec(const RedoScope *scope), launch_melspec(bool redo);
@@ -1129,6 +1225,8 @@ struct Batch {
         *p = (T *)v;
         return rc;
     }
+    // v into a block of the batch, synchronously (beside dalloc: what RatePass::bind stores through)
+    template <class T> int put(T *dst, const std::vector<T> &v, const char *what) { return upload_list(dst, v, what); }
     // blocks that must start out zeroed: cleared by ONE launch when the batch has been put together (flush_zero),
     // not by a fill of its own each -- two dozen 5 us launches were 0.13 ms of the 2.4 ms of a one-sentence request
     std::vector<std::pair<void *, size_t>> zero_list;

@@ -1,8 +1,10 @@
 #pragma once
 // jb_melbank.h -- a bank of triangular filters over the n_fft / 2 + 1 bins of a frame's transform, as the filterbank
 // features and the mel spectrograms hold it: each filter's weights over its support for the host, the same weights by
-// bin for the kernels, and the host's sum of one filter.  Plain C++17.
+// bin for the kernels, the host's sum of one filter and the write of one output element.  Plain C++17.
 #include "jb_rfft.h"
+
+#include <string.h>
 
 namespace jb {
 
@@ -53,6 +55,17 @@ template <class Rising> bool mel_bank_split(const double *W, uint32_t n_mels, ui
         }
     }
     return ok;
+}
+
+// Element `at` of a host form's output: v as it stands (f64), or rounded once to f32
+inline void put_elem(uint8_t *out, size_t at, double v, bool f64)
+{
+    if (f64)
+        memcpy(out + at * 8, &v, 8);
+    else {
+        const float f = (float)v;
+        memcpy(out + at * 4, &f, 4);
+    }
 }
 
 // Filter m over the bins' values P[0..K): its products added in ascending order

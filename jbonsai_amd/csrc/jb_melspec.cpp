@@ -77,16 +77,6 @@ struct HostFrame {
     }
 };
 
-void put_elem(uint8_t *out, size_t at, double v, uint32_t flags)
-{
-    if (flags & kMelF64)
-        memcpy(out + at * 8, &v, 8);
-    else {
-        const float f = (float)v;
-        memcpy(out + at * 4, &f, 4);
-    }
-}
-
 } // namespace
 
 int mel_check_opts(const MelOpts *opts, const char *who)
@@ -279,7 +269,7 @@ int jb_melspec_host(const double *in, size_t n, uint32_t hz, const jb_melspec_op
         double v = y[i];
         if (o->range > 0.0)
             v = v > ymax - o->range ? v : ymax - o->range;
-        put_elem(out, i, mel_affine(v, o->offset, g.scale), o->flags);
+        put_elem(out, i, mel_affine(v, o->offset, g.scale), (o->flags & kMelF64) != 0);
     }
     return JB_OK;
 }

@@ -29,6 +29,8 @@
 //   k_melspec_max     a workgroup per unit folds the unit's entries of gmax into umax[unit];
 //   k_melspec_finish  the grid of k_melspec again: each workgroup streams its frames' elements through the clamp, the
 //                     affine step and the element conversion.
+// The launch list -- classes, units, g0 and the workgroup count that gmax is numbered by -- is RatePass's (jb_host.h),
+// for jb_melspec_pcm_batch below (check, build, attach the pointers, launch, hand out) and for a batch's output chain.
 #include "jb_host.h"
 #include "jb_rfft_dev.h"
 
@@ -272,11 +274,11 @@ int jb_melspec_pcm_batch(const double *const *in, const size_t *n_in, size_t n, 
         return rc;
     if ((rc = pcm_check((const void *const *)in, n_in, n, hz && out && n_bytes, (void **)out, n_bytes)))
         return rc;
-    // (every rate's geometry before a device is touched)
-    MelClasses cls;
-    std::vector<MelUtt> utts(n);
+    // (every rate's geometry and every unit's frames before a device is touched: RatePass, jb_host.h)
+    MelPass pass;
+    pass.start(*o);
     for (size_t u = 0; u < n; u++)
-        if ((rc = cls.find(*o, hz[u], "jb_melspec_pcm_batch", &utts[u].cls)))
+        if ((rc = pass.add(hz[u], n_in[u], "jb_melspec_pcm_batch")))
             return rc;
     DeviceScratch ds;
     if ((rc = ds.open(device, "jb_melspec_pcm_batch")))
@@ -288,38 +290,26 @@ int jb_melspec_pcm_batch(const double *const *in, const size_t *n_in, size_t n, 
     const double *dx = ds.pack(in, n_in, n, &xoff);
     std::vector<PcmShare> shares(n);
     std::vector<uint64_t> soff(n);
-    uint64_t bytes = 0, groups = 0, values = 0;
+    uint64_t bytes = 0, values = 0;
     for (size_t u = 0; u < n; u++) {
-        MelUtt &w = utts[u];
-        const MelGeom &g = cls.geom[w.cls];
-        w.n = n_in[u];
-        w.T = mel_frames(w.n, g.n_fft, g.hop, o->pad, o->flags);
-        w.g0 = groups;
-        shares[u] = {bytes, w.T * g.n_mels * mel_elem(o->flags)};
+        const uint64_t elems = pass.list.host[u].T * o->n_mels;
+        shares[u] = {bytes, elems * mel_elem(o->flags)};
         soff[u] = values;
         bytes += (shares[u].n + 15) & ~(uint64_t)15;
-        values += w.T * g.n_mels;
-        groups += (w.T + mel_wg_frames(g.n_fft) - 1) / mel_wg_frames(g.n_fft);
+        values += elems;
     }
     uint8_t *dy = ds.alloc<uint8_t>(std::max<uint64_t>(bytes, 16));
     double *dsc = ranged ? ds.alloc<double>(values) : nullptr;
-    double *gmax = ranged ? ds.alloc<double>(groups) : nullptr;
+    double *gmax = ranged ? ds.alloc<double>(pass.groups) : nullptr;
     double *umax = ranged ? ds.alloc<double>(n) : nullptr;
     for (size_t u = 0; u < n; u++) {
-        utts[u].x = dx + xoff[u];
-        utts[u].y = dy + shares[u].off;
-        utts[u].s = ranged ? dsc + soff[u] : nullptr;
+        pass.list.host[u].x = dx + xoff[u];
+        pass.list.host[u].y = dy + shares[u].off;
+        pass.list.host[u].s = ranged ? dsc + soff[u] : nullptr;
     }
-    double *dt = ds.alloc<double>(cls.words());
-    std::vector<double> image;
-    std::vector<MelClass> classes;
-    cls.bind(*o, dt, &image, &classes);
-    if (ds.ok() && !image.empty())
-        ds.err = hipMemcpyAsync(dt, image.data(), sizeof(double) * image.size(), hipMemcpyHostToDevice, ds.stream);
-    const MelClass *dc = ds.upload(classes);
-    const MelUtt *du = ds.upload(utts);
+    pass.bind(ds, "jb_melspec_pcm_batch");
     if (ds.ok())
-        ds.err = launch_melspec(dc, du, (uint32_t)n, groups, ranged, gmax, umax, ds.stream);
+        ds.err = pass.launch(ds.stream, gmax, umax);
     std::vector<uint8_t> host;
     ds.read_back(&host, dy, bytes);
     if ((rc = ds.status()))

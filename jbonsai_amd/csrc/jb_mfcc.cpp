@@ -154,14 +154,36 @@ void mfcc_rule(const double *L, uint64_t T, uint32_t n_mels, const MfccOpts &o, 
                     return c[(size_t)(g < 0 ? 0 : g >= (int64_t)T ? (int64_t)T - 1 : g) * d + i];
                 };
                 const double v = q == 0 ? c[t * d + i] : mfcc_delta(q == 1 ? p.s1 : p.s2, (int32_t)q * N, at);
-                const size_t e = (size_t)t * width + (size_t)q * d + i;
-                if (o.flags & kMfF64)
-                    memcpy(out + e * 8, &v, 8);
-                else {
-                    const float f = (float)v;
-                    memcpy(out + e * 4, &f, 4);
-                }
+                put_elem(out, (size_t)t * width + (size_t)q * d + i, v, (o.flags & kMfF64) != 0);
             }
+}
+
+// The whole rule over PCM under the frame request *q and the entry's name `who`: jb_mfcc_framed_pcm_host's body, and
+// with the all-zero request (jb_fbank.h "Frame conditioning") jb_mfcc_pcm_host's
+int mfcc_pcm_host(const double *in, size_t n, uint32_t hz, const FbankOpts *fo, const MfccOpts *o, const FrameOpts *q,
+                  uint8_t *out, size_t cap, const char *who)
+{
+    int rc = mfcc_check_fbank(fo, who);
+    if (rc || (rc = mfcc_check_opts(o, fo->n_mels, who)) || (rc = frame_check(fo, q, o->n_ceps >= 1, who)))
+        return rc;
+    const FbankOpts f = mfcc_fbank_opts(*fo);
+    FbankGeom g{};
+    if ((rc = fbank_geometry(&f, hz, who, &g)))
+        return rc;
+    const uint64_t T = frame_count(n, g, f, *q);
+    if (cap < T * mfcc_width(*o, g.n_mels) * mfcc_elem(o->flags)) {
+        set_error(std::string(who) + ": the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (n && (!in || (T && !out)))
+        return JB_ERR_INVALID;
+    std::vector<double> L((size_t)T * f.n_mels + 1), energy;
+    const bool e = (q->flags & kFrEnergy) != 0;
+    if ((rc = fbank_framed_host(in, n, hz, &f, *q, (uint8_t *)L.data(), sizeof(double) * T * f.n_mels, who,
+                                e ? &energy : nullptr)))
+        return rc;
+    mfcc_rule(L.data(), T, f.n_mels, *o, out, e ? energy.data() : nullptr, &g);
+    return JB_OK;
 }
 
 } // namespace
@@ -184,7 +206,7 @@ int jb_mfcc_geometry(uint32_t hz, const jb_fbank_opts *fopts, const jb_mfcc_opts
     FbankGeom g{};
     if ((rc = fbank_geometry(f, hz, "jb_mfcc_geometry", &g)))
         return rc;
-    const uint64_t frames = fbank_frames(n, g.wl, g.hop, (f->flags & kFbCenter) != 0);
+    const uint64_t frames = frame_count(n, g, *f, FrameOpts{});
     const uint32_t w = mfcc_width(*(const MfccOpts *)opts, g.n_mels);
     if (T)
         *T = (size_t)frames;
@@ -247,54 +269,19 @@ int jb_mfcc_host(const double *L, size_t T, uint32_t n_mels, const jb_mfcc_opts 
 int jb_mfcc_pcm_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *fopts, const jb_mfcc_opts *opts,
                      uint8_t *out, size_t cap)
 {
-    size_t T = 0, bytes = 0;
-    int rc = jb_mfcc_geometry(hz, fopts, opts, n, &T, nullptr, &bytes);
-    if (rc)
-        return rc;
-    if (cap < bytes) {
-        set_error("jb_mfcc_pcm_host: the buffer is too small");
-        return JB_ERR_BUFFER;
-    }
-    if (n && (!in || (T && !out)))
-        return JB_ERR_INVALID;
-    const FbankOpts f = mfcc_fbank_opts(*(const FbankOpts *)fopts);
-    std::vector<double> L((size_t)T * f.n_mels + 1);
-    if ((rc = jb_fbank_host(in, n, hz, (const jb_fbank_opts *)&f, (uint8_t *)L.data(), sizeof(double) * T * f.n_mels)))
-        return rc;
-    mfcc_rule(L.data(), T, f.n_mels, *(const MfccOpts *)opts, out);
-    return JB_OK;
+    // (what the options and the rate refuse keeps jb_mfcc_geometry's name, as it always had)
+    const int rc = jb_mfcc_geometry(hz, fopts, opts, n, nullptr, nullptr, nullptr);
+    const FrameOpts none{};
+    return rc ? rc
+              : mfcc_pcm_host(in, n, hz, (const FbankOpts *)fopts, (const MfccOpts *)opts, &none, out, cap,
+                              "jb_mfcc_pcm_host");
 }
 
 int jb_mfcc_framed_pcm_host(const double *in, size_t n, uint32_t hz, const jb_fbank_opts *fopts,
                             const jb_mfcc_opts *opts, const jb_frame_opts *fr, uint8_t *out, size_t cap)
 {
-    const char *who = "jb_mfcc_framed_pcm_host";
-    const FbankOpts *fo = (const FbankOpts *)fopts;
-    const MfccOpts *o = (const MfccOpts *)opts;
-    const FrameOpts *q = (const FrameOpts *)fr;
-    int rc = mfcc_check_fbank(fo, who);
-    if (rc || (rc = mfcc_check_opts(o, fo->n_mels, who)) || (rc = frame_check(fo, q, o->n_ceps >= 1, who)))
-        return rc;
-    if (frame_is_identity(*q))
-        return jb_mfcc_pcm_host(in, n, hz, fopts, opts, out, cap);
-    const FbankOpts f = mfcc_fbank_opts(*fo);
-    FbankGeom g{};
-    if ((rc = fbank_geometry(&f, hz, who, &g)))
-        return rc;
-    const uint64_t T = frame_count(n, g.wl, g.hop, (f.flags & kFbCenter) != 0, (q->flags & kFrReflect) != 0);
-    if (cap < T * mfcc_width(*o, g.n_mels) * mfcc_elem(o->flags)) {
-        set_error(std::string(who) + ": the buffer is too small");
-        return JB_ERR_BUFFER;
-    }
-    if (n && (!in || (T && !out)))
-        return JB_ERR_INVALID;
-    std::vector<double> L((size_t)T * f.n_mels + 1), energy;
-    const bool e = (q->flags & kFrEnergy) != 0;
-    if ((rc = fbank_framed_host(in, n, hz, f, *q, (uint8_t *)L.data(), sizeof(double) * T * f.n_mels, who,
-                                e ? &energy : nullptr)))
-        return rc;
-    mfcc_rule(L.data(), T, f.n_mels, *o, out, e ? energy.data() : nullptr, &g);
-    return JB_OK;
+    return mfcc_pcm_host(in, n, hz, (const FbankOpts *)fopts, (const MfccOpts *)opts, (const FrameOpts *)fr, out, cap,
+                         "jb_mfcc_framed_pcm_host");
 }
 
 void jb_mfcc_free(uint8_t *p) { free(p); }

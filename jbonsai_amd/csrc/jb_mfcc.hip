@@ -16,6 +16,8 @@
 //                 delta_order N frames on both sides (clamped at the unit's ends) in LDS, normalised on the way in,
 //                 and writes every row's share of [c' | out_1 | out_2] with whole-dword (f32) or whole-qword stores.
 // The launch count does not depend on the batch: the lists are laid out like FbankUtt's (prefix sums, a binary search).
+// The filterbank pass in front (mfcc_pcm_run here, the output chain's prepare_mfcc) is a RatePass of jb_host.h, as the
+// filterbank stage's own; only the cepstral lists are put together here.
 #include "jb_host.h"
 #include "jb_mfcc.h"
 
@@ -229,55 +231,41 @@ int mfcc_pcm_run(const double *const *in, const size_t *n_in, size_t n, const ui
         return rc;
     if ((rc = pcm_check((const void *const *)in, n_in, n, hz && out && n_bytes, (void **)out, n_bytes)))
         return rc;
-    // (every rate's geometry before a device is touched)
-    FbankClasses cls;
-    cls.cond = fr;
-    std::vector<FbankUtt> futts(n);
+    // (every rate's geometry and every unit's frames before a device is touched)
+    FbankPass pass;
+    pass.start(f, fr);
     for (size_t u = 0; u < n; u++)
-        if ((rc = cls.find(f, hz[u], who, &futts[u].cls)))
+        if ((rc = pass.add(hz[u], n_in[u], who)))
             return rc;
     DeviceScratch ds;
     if ((rc = ds.open(device, who)))
         return rc;
-    // the filterbank stage as jb_fbank_pcm_batch runs it, its f64 logarithms into a slab of the call (a unit's frames
-    // on a 16-byte boundary), then the cepstral kernels behind it on the same stream
+    // the filterbank pass as jb_fbank_pcm_batch runs it (RatePass, jb_host.h), its f64 logarithms into a slab of the
+    // call (a unit's frames on a 16-byte boundary), then the cepstral kernels behind it on the same stream
     std::vector<uint64_t> xoff;
     const double *dx = ds.pack(in, n_in, n, &xoff);
-    const bool center = (f.flags & kFbCenter) != 0, reflect = (fr.flags & kFrReflect) != 0;
     const bool energy = (fr.flags & kFrEnergy) != 0;
     std::vector<uint64_t> loff(n), eoff(n), T(n);
-    uint64_t words = 0, groups = 0, frames = 0;
+    uint64_t words = 0, frames = 0;
     for (size_t u = 0; u < n; u++) {
-        FbankUtt &w = futts[u];
-        const FbankGeom &g = cls.geom[w.cls];
-        w.n = n_in[u];
-        w.T = T[u] = frame_count(w.n, g.wl, g.hop, center, reflect);
-        w.g0 = groups;
+        T[u] = pass.list.host[u].T;
         loff[u] = words;
         eoff[u] = frames;
-        words += (w.T * g.n_mels + 1) & ~(uint64_t)1;
-        frames += w.T;
-        groups += (w.T + fbank_wg_frames(g.n_fft) - 1) / fbank_wg_frames(g.n_fft);
+        words += (T[u] * f.n_mels + 1) & ~(uint64_t)1;
+        frames += T[u];
     }
     double *dL = ds.alloc<double>(std::max<uint64_t>(words, 2));
     double *de = energy ? ds.alloc<double>(std::max<uint64_t>(frames, 1)) : nullptr;
     for (size_t u = 0; u < n; u++) {
-        futts[u].x = dx + xoff[u];
-        futts[u].y = (uint8_t *)(dL + loff[u]);
-        futts[u].e = de ? de + eoff[u] : nullptr;
+        pass.list.host[u].x = dx + xoff[u];
+        pass.list.host[u].y = (uint8_t *)(dL + loff[u]);
+        pass.list.host[u].e = de ? de + eoff[u] : nullptr;
     }
-    double *dt = ds.alloc<double>(cls.words());
-    std::vector<double> image;
-    std::vector<FbankClass> classes;
-    cls.bind(f, dt, &image, &classes);
-    if (ds.ok() && !image.empty())
-        ds.err = hipMemcpyAsync(dt, image.data(), sizeof(double) * image.size(), hipMemcpyHostToDevice, ds.stream);
-    const FbankClass *dcl = ds.upload(classes);
-    const FbankUtt *du = ds.upload(futts);
+    pass.bind(ds, who);
     if (ds.ok())
-        ds.err = launch_fbank(dcl, du, (uint32_t)n, groups, ds.stream, !frame_is_identity(fr));
-    // (image, classes and futts live to the wait inside mfcc_run)
-    return mfcc_run(ds, *o, f.n_mels, dL, loff, T, out, n_bytes, de, &eoff, n && de ? &cls.geom[0] : nullptr);
+        ds.err = pass.launch(ds.stream);
+    // (the pass lives to the wait inside mfcc_run)
+    return mfcc_run(ds, *o, f.n_mels, dL, loff, T, out, n_bytes, de, &eoff, n && de ? &pass.cls.geom[0] : nullptr);
 }
 
 } // namespace

@@ -115,9 +115,9 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
         (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")) ||
         (rc = check_fir(want, "jb_batch_set_output_rate")) ||
         (rc = check_noise(want, "jb_batch_set_output_rate")) ||
-        (fb_on && (rc = check_fbank(fb_p, want, "jb_batch_set_output_rate"))) ||
+        (fb_on && (rc = check_rates(fb_p, want, "jb_batch_set_output_rate"))) ||
         (mf_on && (rc = check_mfcc(mf_fb, want, "jb_batch_set_output_rate"))) ||
-        (ml_on && (rc = check_melspec(ml_p, want, "jb_batch_set_output_rate"))))
+        (ml_on && (rc = check_rates(ml_p, want, "jb_batch_set_output_rate"))))
         return rc;
     want_hz = std::move(want);
     replan();
@@ -302,14 +302,28 @@ int OutputChain::set_adpcm(const jb_adpcm_opts *opts)
     return JB_OK;
 }
 
-// The filterbank request under these rates: JB_ERR_INVALID naming the field that is out of its limits at some rate
-int OutputChain::check_fbank(const FbankOpts &opts, const std::vector<uint32_t> &want, const char *who) const
+template <class Opts>
+int OutputChain::check_rates(const Opts &opts, const std::vector<uint32_t> &want, const char *who) const
 {
     int rc;
     for (uint32_t hz : rates_under(want))
-        if ((rc = fbank_geometry(&opts, hz, who, nullptr)))
+        if ((rc = rate_geometry(&opts, hz, who, nullptr)))
             return rc;
     return JB_OK;
+}
+
+int OutputChain::check_feature_settable(const char *entry, const char *noun) const
+{
+    if (b.flags & JB_BATCH_MLPG_ONLY) {
+        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
+        return JB_ERR_UNSUPPORTED;
+    }
+    if (b.flags & JB_BATCH_PCM_I16) {
+        set_error(std::string(entry) + ": the " + noun +
+                  " stage reads the f64 output (a batch without JB_BATCH_PCM_I16)");
+        return JB_ERR_UNSUPPORTED;
+    }
+    return check_settable((std::string(entry) + ": the features are set before the batch's first run").c_str());
 }
 
 int OutputChain::set_fbank(const jb_fbank_opts *opts)
@@ -317,17 +331,9 @@ int OutputChain::set_fbank(const jb_fbank_opts *opts)
     int rc;
     if (opts && (rc = fbank_check_opts((const FbankOpts *)opts, "jb_batch_set_fbank")))
         return rc;
-    if (b.flags & JB_BATCH_MLPG_ONLY) {
-        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
-        return JB_ERR_UNSUPPORTED;
-    }
-    if (b.flags & JB_BATCH_PCM_I16) {
-        set_error("jb_batch_set_fbank: the fbank stage reads the f64 output (a batch without JB_BATCH_PCM_I16)");
-        return JB_ERR_UNSUPPORTED;
-    }
-    if ((rc = check_settable("jb_batch_set_fbank: the features are set before the batch's first run")))
+    if ((rc = check_feature_settable("jb_batch_set_fbank", "fbank")))
         return rc;
-    if (opts && ((rc = check_fbank(*(const FbankOpts *)opts, want_hz, "jb_batch_set_fbank")) ||
+    if (opts && ((rc = check_rates(*(const FbankOpts *)opts, want_hz, "jb_batch_set_fbank")) ||
                  (rc = check_frame(fr_on ? &fr_p : nullptr, (const FbankOpts *)opts, nullptr, nullptr,
                                    "jb_batch_set_fbank"))))
         return rc;
@@ -341,7 +347,7 @@ int OutputChain::set_fbank(const jb_fbank_opts *opts)
 // The cepstral request's filterbank under these rates, as the stage runs it (f64 logarithms)
 int OutputChain::check_mfcc(const FbankOpts &fopts, const std::vector<uint32_t> &want, const char *who) const
 {
-    return check_fbank(mfcc_fbank_opts(fopts), want, who);
+    return check_rates(mfcc_fbank_opts(fopts), want, who);
 }
 
 int OutputChain::set_mfcc(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts)
@@ -351,15 +357,7 @@ int OutputChain::set_mfcc(const jb_fbank_opts *fopts, const jb_mfcc_opts *opts)
     if (on && ((rc = mfcc_check_fbank((const FbankOpts *)fopts, "jb_batch_set_mfcc")) ||
                (rc = mfcc_check_opts((const MfccOpts *)opts, fopts->n_mels, "jb_batch_set_mfcc"))))
         return rc;
-    if (b.flags & JB_BATCH_MLPG_ONLY) {
-        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
-        return JB_ERR_UNSUPPORTED;
-    }
-    if (b.flags & JB_BATCH_PCM_I16) {
-        set_error("jb_batch_set_mfcc: the cepstral stage reads the f64 output (a batch without JB_BATCH_PCM_I16)");
-        return JB_ERR_UNSUPPORTED;
-    }
-    if ((rc = check_settable("jb_batch_set_mfcc: the features are set before the batch's first run")))
+    if ((rc = check_feature_settable("jb_batch_set_mfcc", "cepstral")))
         return rc;
     if (on && ((rc = check_mfcc(*(const FbankOpts *)fopts, want_hz, "jb_batch_set_mfcc")) ||
                (rc = check_frame(fr_on ? &fr_p : nullptr, nullptr, (const FbankOpts *)fopts, (const MfccOpts *)opts,
@@ -409,32 +407,14 @@ int OutputChain::set_frame_opts(const jb_frame_opts *fr)
     return JB_OK;
 }
 
-// The mel spectrogram request under these rates: JB_ERR_INVALID naming the field that is out of its limits at some rate
-int OutputChain::check_melspec(const MelOpts &opts, const std::vector<uint32_t> &want, const char *who) const
-{
-    int rc;
-    for (uint32_t hz : rates_under(want))
-        if ((rc = mel_geometry(&opts, hz, who, nullptr)))
-            return rc;
-    return JB_OK;
-}
-
 int OutputChain::set_melspec(const jb_melspec_opts *opts)
 {
     int rc;
     if (opts && (rc = mel_check_opts((const MelOpts *)opts, "jb_batch_set_melspec")))
         return rc;
-    if (b.flags & JB_BATCH_MLPG_ONLY) {
-        set_error("a JB_BATCH_MLPG_ONLY batch has no PCM");
-        return JB_ERR_UNSUPPORTED;
-    }
-    if (b.flags & JB_BATCH_PCM_I16) {
-        set_error("jb_batch_set_melspec: the mel stage reads the f64 output (a batch without JB_BATCH_PCM_I16)");
-        return JB_ERR_UNSUPPORTED;
-    }
-    if ((rc = check_settable("jb_batch_set_melspec: the features are set before the batch's first run")))
+    if ((rc = check_feature_settable("jb_batch_set_melspec", "mel")))
         return rc;
-    if (opts && (rc = check_melspec(*(const MelOpts *)opts, want_hz, "jb_batch_set_melspec")))
+    if (opts && (rc = check_rates(*(const MelOpts *)opts, want_hz, "jb_batch_set_melspec")))
         return rc;
     ml_on = opts != nullptr;
     if (opts)
@@ -829,7 +809,7 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
         (rc = select_melspec(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.utts.n || mf.utts.n || ml.utts.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_noise(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
         (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
@@ -1612,24 +1592,8 @@ int OutputChain::launch_adpcm(bool redo)
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_adpcm(redo)" : "k_adpcm");
 }
 
-template <class Classes, class Opts, class Class>
-int OutputChain::upload_classes(const Classes &cls, const Opts &opts, const char *what_tables, const char *what_classes,
-                                Class **classes_dev)
-{
-    double *tables = nullptr;
-    int rc = b.dalloc(&tables, cls.words(), false);
-    if (rc)
-        return rc;
-    std::vector<double> image;
-    std::vector<Class> classes;
-    cls.bind(opts, tables, &image, &classes);
-    if ((rc = upload_list(tables, image, what_tables)) || (rc = b.dalloc(classes_dev, classes.size(), false)))
-        return rc;
-    return upload_list(*classes_dev, classes, what_classes);
-}
-
-// ---- the filterbank features beside them, of the same final f64.  The unit list: the final PCM of the plan in, each
-// unit's frames at their 16-byte aligned place out; the tables of every distinct rate in one block
+// ---- the filterbank features beside them, of the same final f64: a RatePass (jb_host.h) over the units, with the
+// plan's frames.  The final PCM of the plan in, each unit's frames at their 16-byte aligned place out
 int OutputChain::prepare_fbank()
 {
     if (!fbank())
@@ -1638,48 +1602,37 @@ int OutputChain::prepare_fbank()
     const size_t U = units.size();
     const double *src = (const double *)slab[(size_t)plan.fbank_src];
     uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Feat];
-    FbankClasses cls;
-    if (fr_on)
-        cls.cond = fr_p;
-    fb.utts.host.assign(U, FbankUtt{});
-    fb.ngroups.assign(U, 0);
-    fb.groups = 0;
+    fb.start(fb_p, fr_on ? fr_p : FrameOpts{});
     int rc;
     for (size_t u = 0; u < U; u++) {
-        FbankUtt &w = fb.utts.host[u];
-        if ((rc = cls.find(fb_p, units[u].hz, "jb_batch_set_fbank", &w.cls)))
+        if ((rc = fb.add(units[u].hz, units[u].n, "jb_batch_set_fbank", plan.fbank[u].T)))
             return rc;
-        w.x = src + units[u].off;
-        w.y = dst + plan.fbank[u].off;
-        w.n = units[u].n;
-        w.T = plan.fbank[u].T;
-        w.g0 = fb.groups;
-        const uint32_t per = fbank_wg_frames(plan.fbank[u].n_fft);
-        fb.ngroups[u] = (w.T + per - 1) / per;
-        fb.groups += fb.ngroups[u];
+        fb.list.host[u].x = src + units[u].off;
+        fb.list.host[u].y = dst + plan.fbank[u].off;
     }
-    if ((rc = upload_classes(cls, fb_p, "fbank tables", "fbank classes", &fb.classes_dev)) ||
-        (rc = fb.utts.alloc(b, U, U)))
+    if ((rc = fb.bind(b, "fbank")))
         return rc;
-    return fb.utts.upload("fbank work list");
+    return b.dalloc(&fb.list.redo, U, false);
 }
 
-int OutputChain::select_fbank(const RedoScope *scope)
+// A pass's lists of a redo.  `units`: every unit whose final PCM changed, each recomputed whole (one without a frame
+// stays in the list: it has no workgroup); the list is renumbered, what a unit points at stays where the full
+// numbering put it
+template <class Pass> static int select_pass(Pass &p, const RedoScope *scope)
 {
-    if (!fbank() || !scope)
-        return fb.utts.take_all(fb.groups);
-    // `units`: every unit whose final PCM changed, each recomputed whole (one without a frame stays in the list: it
-    // has no workgroup)
-    const Picked p = pick_renumbered(scope->units, fb.ngroups);
-    return fb.utts.upload_redo(renumbered(fb.utts.host, p, &FbankUtt::g0), kRedoLists, p.total);
+    if (!scope)
+        return p.list.take_all(p.groups);
+    const Picked k = pick_renumbered(scope->units, p.ngroups);
+    return p.list.upload_redo(renumbered(p.list.host, k, &Pass::Unit::g0), kRedoLists, k.total);
 }
+
+int OutputChain::select_fbank(const RedoScope *scope) { return select_pass(fb, fbank() ? scope : nullptr); }
 
 int OutputChain::launch_fbank(bool redo)
 {
-    if (!fbank() || (redo && !fb.utts.n))
+    if (!fbank() || (redo && !fb.list.n))
         return JB_OK;
-    const hipError_t e = jb::launch_fbank(fb.classes_dev, fb.utts.list, fb.utts.n, fb.utts.total, b.stream_voc,
-                                          fr_on && !frame_is_identity(fr_p));
+    const hipError_t e = fb.launch(b.stream_voc);
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_fbank(redo)" : "k_fbank");
 }
 
@@ -1700,31 +1653,20 @@ int OutputChain::prepare_mfcc()
     mfcc_tables(mf_p, fo.n_mels, &tab);
     mf.P = mfcc_params(mf_p, fo.n_mels, tab);
     const uint32_t d = mf.P.d;
-    FbankClasses cls;
-    if (fr_on)
-        cls.cond = fr_p;
     const bool energy = fr_on && (fr_p.flags & kFrEnergy);
-    mf.futts.host.assign(U, FbankUtt{});
+    mf.fbank.start(fo, fr_on ? fr_p : FrameOpts{});
     mf.utts.host.assign(U, MfccUtt{});
-    mf.ngroups.assign(U, 0);
     mf.ntiles.assign(U, 0);
     mf.nblocks.assign(U, 0);
-    mf.groups = mf.tiles = mf.blocks = 0;
+    mf.tiles = mf.blocks = 0;
     uint64_t frames = 0;
     int rc;
     for (size_t u = 0; u < U; u++) {
         const OutMfccUtt &pl = plan.mfcc[u];
-        FbankUtt &f = mf.futts.host[u];
-        if ((rc = cls.find(fo, units[u].hz, "jb_batch_set_mfcc", &f.cls)))
+        if ((rc = mf.fbank.add(units[u].hz, units[u].n, "jb_batch_set_mfcc", pl.T)))
             return rc;
-        f.x = src + units[u].off;
-        f.y = (uint8_t *)(logmel + pl.loff);
-        f.n = units[u].n;
-        f.T = pl.T;
-        f.g0 = mf.groups;
-        const uint32_t per = fbank_wg_frames(pl.n_fft);
-        mf.ngroups[u] = (f.T + per - 1) / per;
-        mf.groups += mf.ngroups[u];
+        mf.fbank.list.host[u].x = src + units[u].off;
+        mf.fbank.list.host[u].y = (uint8_t *)(logmel + pl.loff);
         MfccUtt &w = mf.utts.host[u];
         w.L = logmel + pl.loff;
         w.y = dst + pl.off;
@@ -1752,17 +1694,16 @@ int OutputChain::prepare_mfcc()
         w.bs = bs + w.b0 * d;
         w.stat = stat + 2 * u * d;
         // (the frames' energies of JB_FRAME_ENERGY: k_fbank writes them, k_ceps reads them, numbered as the statics)
-        w.e = mf.futts.host[u].e = energy ? en + at : nullptr;
+        w.e = mf.fbank.list.host[u].e = energy ? en + at : nullptr;
         at += w.T;
     }
-    if (energy && !cls.geom.empty())
-        mf.P.e_floor = cls.geom[0].log_floor, mf.P.e_ln_floor = cls.geom[0].ln_floor;
+    if (energy && !mf.fbank.cls.geom.empty())
+        mf.P.e_floor = mf.fbank.cls.geom[0].log_floor, mf.P.e_ln_floor = mf.fbank.cls.geom[0].ln_floor;
     mf.P.Dt = dct;
     mf.P.lift = lift;
-    if ((rc = upload_classes(cls, fo, "mfcc filterbank tables", "mfcc filterbank classes", &mf.classes_dev)) ||
-        (rc = upload_list(dct, tab.Dt, "mfcc DCT")) || (rc = upload_list(lift, tab.lift, "mfcc lifter")) ||
-        (rc = mf.futts.alloc(b, U, U)) ||
-        (rc = mf.utts.alloc(b, U, U)) || (rc = mf.futts.upload("mfcc filterbank work list")))
+    if ((rc = mf.fbank.bind(b, "mfcc filterbank")) ||
+        (rc = b.dalloc(&mf.fbank.list.redo, U, false)) || (rc = upload_list(dct, tab.Dt, "mfcc DCT")) ||
+        (rc = upload_list(lift, tab.lift, "mfcc lifter")) || (rc = mf.utts.alloc(b, U, U)))
         return rc;
     return mf.utts.upload("mfcc work list");
 }
@@ -1771,18 +1712,17 @@ int OutputChain::select_mfcc(const RedoScope *scope)
 {
     if (!mfcc() || !scope) {
         mf.take_blocks = mf.blocks;
-        mf.futts.take_all(mf.groups);
+        mf.fbank.list.take_all(mf.fbank.groups);
         return mf.utts.take_all(mf.tiles);
     }
     // `units`: every unit whose final PCM changed, recomputed whole -- its statistics run over all its frames; the
     // lists are renumbered, the scratch stays where the full numbering put it (the units' pointers)
-    const Picked pg = pick_renumbered(scope->units, mf.ngroups);
     const Picked pt = pick_renumbered(scope->units, mf.ntiles), pb = pick_renumbered(scope->units, mf.nblocks);
     std::vector<MfccUtt> sub = renumbered(mf.utts.host, pt, &MfccUtt::g0);
     for (size_t i = 0; i < sub.size(); i++)
         sub[i].b0 = pb.base[i];
     mf.take_blocks = pb.total;
-    const int rc = mf.futts.upload_redo(renumbered(mf.futts.host, pg, &FbankUtt::g0), kRedoLists, pg.total);
+    const int rc = select_pass(mf.fbank, scope);
     return rc ? rc : mf.utts.upload_redo(sub, kRedoLists, pt.total);
 }
 
@@ -1790,8 +1730,7 @@ int OutputChain::launch_mfcc(bool redo)
 {
     if (!mfcc() || (redo && !mf.utts.n))
         return JB_OK;
-    hipError_t e = jb::launch_fbank(mf.classes_dev, mf.futts.list, mf.futts.n, mf.futts.total, b.stream_voc,
-                                    fr_on && !frame_is_identity(fr_p));
+    hipError_t e = mf.fbank.launch(b.stream_voc);
     if (e == hipSuccess)
         e = jb::launch_mfcc(mf.P, mf.utts.list, mf.utts.n, mf.utts.total, mf.take_blocks, b.stream_voc);
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "mfcc(redo)" : "mfcc");
@@ -1810,49 +1749,31 @@ int OutputChain::prepare_melspec()
     uint8_t *dst = (uint8_t *)slab[(size_t)OutSlab::Mel];
     double *vals = (double *)slab[(size_t)OutSlab::MelY];
     const bool ranged = ml_p.range > 0.0;
-    MelClasses cls;
-    ml.utts.host.assign(U, MelUtt{});
-    ml.ngroups.assign(U, 0);
-    ml.groups = 0;
+    ml.pass.start(ml_p);
     int rc;
     for (size_t u = 0; u < U; u++) {
         const OutMelUtt &pl = plan.melspec[u];
-        MelUtt &w = ml.utts.host[u];
-        if ((rc = cls.find(ml_p, units[u].hz, "jb_batch_set_melspec", &w.cls)))
+        if ((rc = ml.pass.add(units[u].hz, units[u].n, "jb_batch_set_melspec", pl.T)))
             return rc;
+        MelUtt &w = ml.pass.list.host[u];
         w.x = src + units[u].off;
         w.y = dst + pl.off;
         w.s = ranged ? vals + pl.yoff : nullptr;
-        w.n = units[u].n;
-        w.T = pl.T;
-        w.g0 = ml.groups;
-        const uint32_t per = mel_wg_frames(pl.n_fft);
-        ml.ngroups[u] = (w.T + per - 1) / per;
-        ml.groups += ml.ngroups[u];
     }
-    if ((ranged && ((rc = b.dalloc(&ml.gmax, ml.groups, false)) || (rc = b.dalloc(&ml.umax, U, false)))) ||
-        (rc = upload_classes(cls, ml_p, "melspec tables", "melspec classes", &ml.classes_dev)) ||
-        (rc = ml.utts.alloc(b, U, U)))
+    if ((ranged && ((rc = b.dalloc(&ml.gmax, ml.pass.groups, false)) || (rc = b.dalloc(&ml.umax, U, false)))) ||
+        (rc = ml.pass.bind(b, "melspec")))
         return rc;
-    return ml.utts.upload("melspec work list");
+    return b.dalloc(&ml.pass.list.redo, U, false);
 }
 
-int OutputChain::select_melspec(const RedoScope *scope)
-{
-    if (!melspec() || !scope)
-        return ml.utts.take_all(ml.groups);
-    // `units`: every unit whose final PCM changed, each recomputed whole -- its maximum runs over all its frames (one
-    // without a frame stays in the list: it has no workgroup)
-    const Picked p = pick_renumbered(scope->units, ml.ngroups);
-    return ml.utts.upload_redo(renumbered(ml.utts.host, p, &MelUtt::g0), kRedoLists, p.total);
-}
+// (a redone unit's maximum runs over all its frames)
+int OutputChain::select_melspec(const RedoScope *scope) { return select_pass(ml.pass, melspec() ? scope : nullptr); }
 
 int OutputChain::launch_melspec(bool redo)
 {
-    if (!melspec() || (redo && !ml.utts.n))
+    if (!melspec() || (redo && !ml.pass.list.n))
         return JB_OK;
-    const hipError_t e = jb::launch_melspec(ml.classes_dev, ml.utts.list, ml.utts.n, ml.utts.total, ml_p.range > 0.0,
-                                            ml.gmax, ml.umax, b.stream_voc);
+    const hipError_t e = ml.pass.launch(b.stream_voc, ml.gmax, ml.umax);
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_melspec(redo)" : "k_melspec");
 }
 

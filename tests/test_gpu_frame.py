@@ -144,6 +144,33 @@ def test_the_zero_request_gives_the_plain_seams_bytes(eng):
         J.mfcc_framed_pcm(xs, rates, fo, mo, J.frame(preemph=2.0))
 
 
+@pytest.mark.parametrize("reflect", [False, True])
+def test_seam_rates_and_workgroup_edges_in_one_call(eng, reflect):
+    """What the pass builder numbers (class, T, g0, the workgroup count), as tests/test_gpu_fbank.py's
+    test_seam_rates_in_one_call_and_the_f32_rows has it for the plain seam: eight units at 16 and 48 kHz interleaved,
+    n_fft 512 (four frames to a workgroup), of 0, 1, wl - 1, wl, wl + 4 hop (five frames: one past a workgroup) and
+    wl + 3 hop (exactly one workgroup) samples -- the last two at both rates.  Each unit of the one call has the bytes
+    of its own call, for the filterbank and for the cepstra with the frames' energies."""
+    rng = np.random.default_rng(512)
+    f = J.fbank(win_ms=10, hop_ms=5, n_fft=512, n_mels=23)
+    rates = [16000, 48000] * 4
+    xs = []
+    for u, hz in enumerate(rates):
+        wl, hop, nf = R.geometry(hz, 10000, 5000, 512)
+        assert nf == 512
+        n = (0, 1, wl - 1, wl, wl + 4 * hop, wl + 3 * hop, wl + 3 * hop, wl + 4 * hop)[u]
+        xs.append(rng.normal(0, 3000, n) + 500.0)
+    fr = J.frame(preemph=0.97, window="povey", remove_dc=True, reflect=reflect)
+    fre, mo = J.frame(preemph=0.97, window="povey", remove_dc=True, reflect=reflect, energy=True), J.mfcc()
+    got, gotm = J.fbank_framed_pcm(xs, rates, f, fr), J.mfcc_framed_pcm(xs, rates, f, mo, fre)
+    if not reflect:
+        assert [g.shape[0] for g in got] == [0, 0, 0, 1, 5, 4, 4, 5]
+    for x, hz, g, gm in zip(xs, rates, got, gotm):
+        assert g.shape == (J.fbank_framed_geometry(hz, f, fr, x.size)[3], 23) and gm.shape == (g.shape[0], 13)
+        assert g.tobytes() == J.fbank_framed_pcm(x, hz, f, fr).tobytes()
+        assert gm.tobytes() == J.mfcc_framed_pcm(x, hz, f, mo, fre).tobytes()
+
+
 @needs_ld
 @pytest.mark.parametrize("hz", [16000, 48000])
 def test_energy_replaces_c0(eng, hz):

@@ -120,6 +120,28 @@ def test_seam_rates_in_one_call(eng):
         J.melspec_pcm(xs, rates, J.melspec(n_fft=400, hop=160, f_max=8000.0))
 
 
+@pytest.mark.parametrize("pad", ["none", "reflect"])
+def test_seam_rates_and_workgroup_edges_in_one_call_with_a_range(eng, pad):
+    """What the pass builder numbers (class, T, g0, the workgroup count) under range = 8.0, whose maxima per workgroup
+    and per unit lie at g0 and at the unit's place: eight units at 16 and 48 kHz interleaved, n_fft 512 (four frames to
+    a workgroup), of 0, 1, n_fft - 1, n_fft, n_fft + 4 hop (one frame past a workgroup without padding) and n_fft + 3 hop
+    (exactly one workgroup) samples -- the last two at both rates.  Each unit of the one call has the bytes of its own
+    call.  (test_seam_rates_in_one_call compares the same way at ordinary lengths.)"""
+    rng = np.random.default_rng(512)
+    N, hop = 512, 128
+    o = J.melspec(n_fft=N, hop=hop, n_mels=23, pad=pad, range=8.0)
+    rates = [16000, 48000] * 4
+    xs = [rng.normal(0, 3000, n) * np.where(np.arange(n) < n // 2, 1e-3, 1.0)  # (60 dB under the rest: 13.8 > 8)
+          for n in (0, 1, N - 1, N, N + 4 * hop, N + 3 * hop, N + 3 * hop, N + 4 * hop)]
+    got = J.melspec_pcm(xs, rates, o)
+    if pad == "none":
+        assert [g.shape[0] for g in got] == [0, 0, 0, 1, 5, 4, 4, 5]
+    for x, hz, g in zip(xs, rates, got):
+        assert g.shape == (J.melspec_geometry(hz, o, x.size)[3], 23)
+        assert g.tobytes() == J.melspec_pcm(x, hz, o).tobytes()
+    assert any(np.sum(g == g.min()) > 1 for g in got if g.size)  # (the range bites: a unit's quiet head is clamped)
+
+
 def _utts(eng, frames, seed):
     tab = synth.VoiceTables(eng)
     return eng.voice_info(), [synth.synth_utterance(tab, t, seed + t) for t in frames]

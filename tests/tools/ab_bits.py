@@ -6,8 +6,10 @@ stages behind the vocoder: all eight rows of the output routing table (DESIGN.md
 rate x loudness target; FLAC on the 16-bit rows) on three ragged utterances, with the default geometry and with the
 redo-heavy one of the redo tests (each row with the run's redo counters), and the entries on caller-held PCM on seeded input: three on long inputs, then
 every one of their bodies on utterances of 0, 1, 1,025 and 5,000 samples -- the spectral stages (filterbank, cepstra,
-mel spectrogram) at every transform size class and both element types, the convolution in direct mode and at both
-partitioned transform sizes, the noise stage -- and the host halves of the spectral stages, which need no device.
+mel spectrogram) at every transform size class and both element types, the framed filterbank and cepstral entries
+(the all-zero frame request, every option alone, the Kaldi preset) at one small and one large class, the convolution
+in direct mode and at both partitioned transform sizes, the noise stage -- and the host halves of the spectral stages,
+the framed ones included, which need no device.
 
     python tests/tools/ab_bits.py               every hash (what tools/ab_bits.sh compares between two libraries)
     python tests/tools/ab_bits.py --seams       the hashes of the entries on caller-held PCM alone
@@ -55,8 +57,62 @@ def melspec_cases(f64):
                                                  norm=norm, range=rng, f64=f64)
 
 
+FR_FFT = (64, 2048)  # the framed entries: one small and one large transform class
+SEAM_LENGTHS = (0, 1, 1025, 5000)
+
+
+def frame_cases(cepstra):
+    """The frame requests of the framed entries: the all-zero one, every option alone and the Kaldi preset's
+    (JB_FRAME_ENERGY stands behind a cepstral request only)."""
+    yield "zero", J.frame()
+    yield "remove_dc", J.frame(remove_dc=True)
+    yield "preemph", J.frame(preemph=0.97)
+    yield "povey", J.frame(window="povey")
+    yield "reflect", J.frame(reflect=True)
+    if cepstra:
+        yield "energy", J.frame(energy=True)
+    yield "kaldi", J.kaldi_frame()[1]
+
+
+def seam_mfcc(f64):
+    return J.mfcc(n_ceps=8, delta_order=1, cmvn="mean_var", f64=f64)
+
+
+def host_framed_bits():
+    """jb_fbank_framed_host and jb_mfcc_framed_pcm_host at the seams' lengths, both element types."""
+    rng = np.random.default_rng(1025)
+    pcm = [9000.0 * rng.standard_normal(n) for n in SEAM_LENGTHS]
+    for N in FR_FFT:
+        for f64 in (False, True):
+            for name, fr in frame_cases(True):
+                row = ["host framed", N, "f64" if f64 else "f32", name]
+                if name != "energy":
+                    row += [digest([J.fbank_framed_host(x, SPEC_HZ, fbank_opts(N, f64), fr) for x in pcm])]
+                row += ["mfcc", digest([J.mfcc_framed_pcm_host(x, SPEC_HZ, fbank_opts(N, False), seam_mfcc(f64), fr)
+                                        for x in pcm])]
+                print(*row)
+    kf, kfr = J.kaldi_frame()
+    print("host framed kaldi preset", digest([J.fbank_framed_host(x, SPEC_HZ, kf, kfr) for x in pcm]), "mfcc",
+          digest([J.mfcc_framed_pcm_host(x, SPEC_HZ, kf, J.mfcc(), kfr) for x in pcm]))
+
+
+def framed_seams(pcm):
+    """fbank_framed_pcm and mfcc_framed_pcm under every frame request, both element types."""
+    for N in FR_FFT:
+        for f64 in (False, True):
+            for name, fr in frame_cases(True):
+                row = ["seam framed", N, "f64" if f64 else "f32", name]
+                if name != "energy":
+                    row += [digest(J.fbank_framed_pcm(pcm, SPEC_HZ, fbank_opts(N, f64), fr))]
+                print(*row, "mfcc", digest(J.mfcc_framed_pcm(pcm, SPEC_HZ, fbank_opts(N, False), seam_mfcc(f64), fr)))
+    kf, kfr = J.kaldi_frame()
+    print("seam framed kaldi preset", digest(J.fbank_framed_pcm(pcm, SPEC_HZ, kf, kfr)), "mfcc",
+          digest(J.mfcc_framed_pcm(pcm, SPEC_HZ, kf, J.mfcc(), kfr)))
+
+
 def host_bits():
     """The host halves of the spectral stages on seeded input: windows, dense filterbanks and frames."""
+    host_framed_bits()
     x = 9000.0 * np.random.default_rng(64).standard_normal(3 * 4096 + 17)
     for N in FB_FFT:
         o = fbank_opts(N, True)
@@ -77,9 +133,10 @@ def spectral_seams(pcm):
         for N in FB_FFT:
             o = fbank_opts(N, f64)
             print("seam fbank", N, "f64" if f64 else "f32", digest(J.fbank_pcm(pcm, SPEC_HZ, o)), "mfcc",
-                  digest(J.mfcc_pcm(pcm, SPEC_HZ, fbank_opts(N, False), J.mfcc(n_ceps=8, delta_order=1, cmvn="mean_var", f64=f64))))
+                  digest(J.mfcc_pcm(pcm, SPEC_HZ, fbank_opts(N, False), seam_mfcc(f64))))
         for key, o in melspec_cases(f64):
             print("seam melspec", *key, "f64" if f64 else "f32", digest(J.melspec_pcm(pcm, SPEC_HZ, o)))
+    framed_seams(pcm)
     for K in (256, 257, 2049, 5000):
         f = J.fir(rng.standard_normal(K) / np.sqrt(K), SPEC_HZ, delay=K // 3)
         print("seam fir", K, digest(J.fir_pcm(pcm, f, SPEC_HZ)), "i16", digest(J.fir_pcm(pcm, f, SPEC_HZ, i16=True)))
@@ -90,7 +147,7 @@ def spectral_seams(pcm):
 def pcm_seams():
     """Every body behind the jb_*_pcm_batch entries (f64 and 16-bit instances) on seeded utterances."""
     rng = np.random.default_rng(1025)
-    pcm = [9000.0 * rng.standard_normal(n) for n in (0, 1, 1025, 5000)]
+    pcm = [9000.0 * rng.standard_normal(n) for n in SEAM_LENGTHS]
     pcm16 = [np.clip(x, -32768, 32767).astype(np.int16) for x in pcm]
     print("seam resample", digest(J.resample(pcm, 48000, 16000)), digest(J.resample(pcm, 48000, 48000)))
     print("seam loudness", digest([np.array(J.loudness(pcm, 48000))]), "true_peak",
