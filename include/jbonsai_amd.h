@@ -749,6 +749,30 @@ int jb_vocoder_synthesize_batch(const jb_voice_desc *voice, const jb_track_utt *
  * formula; the batch entries never filter it. */
 int jb_resample_filter(uint32_t in_hz, uint32_t out_hz, uint32_t *L, uint32_t *M, uint32_t *ntaps, double *taps,
                        size_t cap);
+/* The path k_resample takes for a pair, by (L, M, ntaps) alone; pure, no GPU is touched.  A workgroup of four waves
+ * computes a tile of `rows` output rows (row m holds outputs m L .. m L + L - 1) of one utterance.  pad: the shift s
+ * that spreads a half-wave's LDS reads, rows M apart, over the most bank pairs -- one pad double per 2^s window slots,
+ * s in {4, 5, 6, 7}, or 0 for none.  cap: the window samples that 8,192 LDS doubles (64 KiB) hold beside the pad
+ * doubles of that shift; fit = floor((cap - ntaps) / M), or 0 where ntaps + M > cap.  By fit:
+ *   fit >= 256          lds 1, rows 256, row_waves 4: a wave holds 64 rows and walks all L phases
+ *   128 <= fit < 256    lds 1, rows 128, row_waves 2: two waves hold the rows, the two pairs split the phases
+ *   1 <= fit < 128      lds 1, rows min(fit, 64), row_waves 1: one wave's lanes hold the rows, the four waves split
+ *                       the phases (with L < 4 the waves beyond L idle)
+ *   fit == 0            lds 0, pad 0, rows 256, row_waves 4: every lane reads the utterance from global memory behind a
+ *                       bounds predicate (cap and fit keep the figures of the shift that was picked)
+ * lds_bytes is the window of a full tile, rows M + ntaps samples and their pad doubles (0 without LDS; never above
+ * 65,536).  in_hz == out_hz is the identity table of the batch entries, not the pair L = M = 1 of the formula:
+ * identity 1, ntaps 1, lds 0, pad 0, tiles of rows = 16,384 samples copied.  Every path sums in the order above, so
+ * the path changes the speed of a pair and never its bits (tests/test_gpu_resample_paths.py holds each to a host
+ * evaluation with std::fma, bit for bit).  Errors as jb_resample_filter's; out NULL: JB_ERR_INVALID. */
+typedef struct jb_resample_geometry_t {
+    uint32_t L, M, ntaps;
+    uint32_t pad, cap, fit;
+    uint32_t lds, rows, row_waves, lds_bytes;
+    uint32_t identity;
+    uint32_t reserved; /* 0 */
+} jb_resample_geometry_t;
+int jb_resample_geometry(uint32_t in_hz, uint32_t out_hz, jb_resample_geometry_t *out);
 /* The converter on PCM the caller holds (the seam of jb_vocoder_synthesize_batch's kind): in[u] of n_in[u] samples at
  * in_hz -> out[u] of n_out[u] = ceil(n_in[u] L / M) samples at out_hz, library-owned (jb_pcm_free each), on `device`
  * (-1 = current). */
@@ -2230,6 +2254,9 @@ JB_LAYOUT_ASSERT(sizeof(jb_room) == 144 && offsetof(jb_room, source) == 24 && of
 JB_LAYOUT_ASSERT(sizeof(jb_room_info) == 40 && offsetof(jb_room_info, pair_visits) == 8 &&
                      offsetof(jb_room_info, entries) == 24 && offsetof(jb_room_info, direct_index) == 36,
                  "jb_room_info");
+JB_LAYOUT_ASSERT(sizeof(jb_resample_geometry_t) == 48 && offsetof(jb_resample_geometry_t, pad) == 12 &&
+                     offsetof(jb_resample_geometry_t, lds) == 24 && offsetof(jb_resample_geometry_t, identity) == 40,
+                 "jb_resample_geometry_t");
 JB_LAYOUT_ASSERT(sizeof(jb_room_report) == 24 && offsetof(jb_room_report, drr_db) == 8 &&
                      offsetof(jb_room_report, direct_index) == 16 && offsetof(jb_room_report, delay) == 20,
                  "jb_room_report");

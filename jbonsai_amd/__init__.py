@@ -6,7 +6,8 @@ thin host-side mirror of the reference's API used by tests and the benchmark.
 """
 from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, build, flac_encode, flac_md5, flac_seek_geometry, lib, loudness,  # noqa: F401
                    md5_host,
-                   loudness_filter, resample, resample_filter, true_peak, true_peak_filter, write_wav,
+                   loudness_filter, resample, resample_filter, resample_geometry, ResampleGeometry, true_peak,
+                   true_peak_filter, write_wav,
                    format_pcm, format_pcm_host, write_wav_formatted, AdpcmStream, adpcm_decode_host, adpcm_encode,
                    adpcm_encode_host, adpcm_geometry, write_wav_adpcm, loudness_groups, loudness_gate_host,
                    LOUDNESS_NO_GROUP, LOUDNESS_R128, LOUDNESS_PER_UTTERANCE, LOUDNESS_PER_REQUEST,
@@ -41,7 +42,7 @@ from . import comm  # noqa: F401,E402
 
 __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build", "lib", "write_wav", "Batch", "StreamInfo", "StreamStates",
            "Utterance", "VoiceInfo", "paramgen_vocode_batch", "mlpg_batch", "vocode_tracks_batch", "vocoder_synthesize_batch", "generator_from_tracks", "TrackUtterance", "PdfSet", "IndexUtterance", "IndexStreamStates",
-           "UttVoc", "synthesize_batch_each", "resample", "resample_filter",
+           "UttVoc", "synthesize_batch_each", "resample", "resample_filter", "resample_geometry", "ResampleGeometry",
            "loudness", "loudness_filter", "flac_encode", "synthesize_batch_each_flac", "flac_md5", "flac_seek_geometry", "md5_host",
            "true_peak", "true_peak_filter", "PEAK_SAMPLE", "PEAK_TRUE",
            "format_pcm", "format_pcm_host", "write_wav_formatted", "synthesize_batch_each_formatted",

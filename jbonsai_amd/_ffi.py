@@ -541,6 +541,14 @@ class RoomInfo(C.Structure):
                 ("entries", C.c_uint32 * 3), ("direct_index", C.c_uint32)]
 
 
+class ResampleGeometry(C.Structure):
+    """jb_resample_geometry_t: the path k_resample takes for a pair -- L, M, ntaps, the pad shift, the LDS cap and the
+    rows that fit it, whether the window is staged in LDS, rows per tile, waves per row block, LDS bytes, identity."""
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("ntaps", C.c_uint32), ("pad", C.c_uint32), ("cap", C.c_uint32),
+                ("fit", C.c_uint32), ("lds", C.c_uint32), ("rows", C.c_uint32), ("row_waves", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("identity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class RoomReport(C.Structure):
     """jb_room_report: the taps' energy, the direct-to-reverberant ratio in dB, the direct index and the delay used."""
     _fields_ = [("energy", C.c_double), ("drr_db", C.c_double), ("direct_index", C.c_uint32), ("delay", C.c_uint32)]
@@ -750,6 +758,7 @@ SYMBOLS = [
     "jb_batch_create_voc", "jb_batch_create_indexed_voc", "jb_synthesize_batch_each", "jb_synthesize_batch_each_i16",
     "jb_batch_set_output_rate", "jb_batch_output_rate", "jb_batch_read_pcm_native", "jb_resample_filter",
     "jb_resample_pcm_batch", "jb_engine_set_output_sampling_frequency", "jb_engine_get_output_sampling_frequency",
+    "jb_resample_geometry",
     "jb_batch_set_loudness_target", "jb_batch_loudness", "jb_loudness_filter", "jb_loudness_pcm_batch",
     "jb_engine_set_loudness_target", "jb_engine_get_loudness_target", "jb_engine_set_peak_ceiling",
     "jb_engine_get_peak_ceiling",
@@ -922,6 +931,7 @@ def lib():
                                      C.POINTER(C.c_uint32), dp, sz]
     L.jb_resample_pcm_batch.argtypes = [C.POINTER(dp), C.POINTER(sz), sz, C.c_uint32, C.c_uint32, C.c_int32,
                                         C.POINTER(dp), C.POINTER(sz)]
+    L.jb_resample_geometry.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(ResampleGeometry)]
     L.jb_engine_set_output_sampling_frequency.argtypes = [vp, sz]
     L.jb_engine_get_output_sampling_frequency.argtypes = [vp]
     L.jb_engine_get_output_sampling_frequency.restype = sz
@@ -1237,6 +1247,13 @@ def resample_filter(in_hz: int, out_hz: int):
     check(L.jb_resample_filter(in_hz, out_hz, C.byref(l_), C.byref(m_), C.byref(nt),
                                taps.ctypes.data_as(C.POINTER(C.c_double)), taps.size))
     return l_.value, m_.value, taps
+
+
+def resample_geometry(in_hz: int, out_hz: int):
+    """jb_resample_geometry: the ResampleGeometry of in_hz -> out_hz (pure; no GPU needed)."""
+    g = ResampleGeometry()
+    check(lib().jb_resample_geometry(int(in_hz), int(out_hz), C.byref(g)))
+    return g
 
 
 def loudness_filter(hz: int):

@@ -122,6 +122,16 @@ struct ResampleTile {
     uint32_t rows;
     uint32_t table;  // index into the launch's table list
 };
+// The path of a pair, by (L, M, ntaps) alone -- no device is touched (jb_resample_geometry hands it out): the fields of
+// ResampleTable of the same names, and the two figures they follow from
+struct ResampleGeom {
+    uint32_t L, M, C, ntaps;
+    uint32_t cap;       // LDS slots left for a window's samples once the pad doubles of shift `pad` are set aside
+    uint32_t fit;       // rows whose window (rows M + ntaps samples) fits cap; 0: the global-memory path
+    uint32_t rows, row_waves, lds, pad, lds_bytes, identity;
+};
+// taps (may be null): the pair's table, [L][ntaps], or the identity's one tap 1.0
+int resample_geometry(uint32_t in_hz, uint32_t out_hz, ResampleGeom *out, std::vector<double> *taps);
 int resample_table(int device, uint32_t in_hz, uint32_t out_hz, ResampleTable *out);
 void resample_tiles(const ResampleTable &t, uint32_t table, const double *x, uint64_t n_in, void *y, uint64_t n_out,
                     std::vector<ResampleTile> &tiles);

@@ -117,6 +117,66 @@ int resample_design(uint32_t in_hz, uint32_t out_hz, ResampleSpec *spec, std::ve
     return JB_OK;
 }
 
+// The path of a pair: which mapping k_resample runs and with what tile, from (L, M, ntaps) alone -- no device
+int resample_geometry(uint32_t in_hz, uint32_t out_hz, ResampleGeom *out, std::vector<double> *taps)
+{
+    ResampleSpec s{};
+    const bool identity = in_hz == out_hz; // what a native-rate utterance of a converting batch goes through
+    if (identity) {
+        s = ResampleSpec{1, 1, 1, 1};
+        if (taps)
+            taps->assign(1, 1.0);
+    } else {
+        int rc = resample_design(in_hz, out_hz, &s, taps);
+        if (rc)
+            return rc;
+    }
+    ResampleGeom g{};
+    g.L = s.L;
+    g.M = s.M;
+    g.C = s.C;
+    g.ntaps = s.ntaps;
+    // pad doubles where a half-wave's lane stride M hits few bank pairs (a double's pair is its index mod 32: rows M
+    // apart take 32 / gcd(M, 32) of them)
+    g.pad = pick_pad_shift(s.M);
+    // rows per tile: the window (rows M + ntaps samples, and its pad) within the LDS budget, 64 rows per wave at most
+    const uint64_t cap = g.pad ? ((uint64_t)(kRsLdsDoubles - 1) << g.pad) / ((1u << g.pad) + 1) : kRsLdsDoubles;
+    const uint64_t fit = s.ntaps + (uint64_t)s.M <= cap ? (cap - s.ntaps) / s.M : 0;
+    g.cap = (uint32_t)cap;
+    g.fit = (uint32_t)fit;
+    if (identity) {
+        // a copy (or the 16-bit conversion alone): y[k] = x[k], large tiles straight from global memory
+        g.identity = 1;
+        g.lds = 0;
+        g.pad = 0;
+        g.rows = kRsCopyRows;
+        g.row_waves = 4;
+    } else if (fit == 0) {
+        g.lds = 0;
+        g.pad = 0;
+        g.rows = 256;
+        g.row_waves = 4;
+    } else {
+        g.lds = 1;
+        if (fit >= 256) {
+            g.rows = 256;
+            g.row_waves = 4;
+        } else if (fit >= 128) {
+            g.rows = 128;
+            g.row_waves = 2;
+        } else {
+            g.rows = (uint32_t)std::min<uint64_t>(fit, 64);
+            g.row_waves = 1;
+        }
+        // a launch allocates only what its tiles' windows take (16 kHz from 48 kHz: 8 KB), so that up to eight
+        // workgroups share a CU and hide the latency of each lane's chain of dependent FMAs
+        const uint32_t wlen = g.rows * s.M + s.ntaps;
+        g.lds_bytes = (uint32_t)(sizeof(double) * (g.pad ? wlen + (wlen >> g.pad) + 1 : wlen));
+    }
+    *out = g;
+    return JB_OK;
+}
+
 // Device tables, one per (device, in_hz, out_hz), kept for the process (the largest of the common pairs is 179 KB)
 namespace {
 struct TableKey {
@@ -139,57 +199,22 @@ int resample_table(int device, uint32_t in_hz, uint32_t out_hz, ResampleTable *o
         *out = it->second;
         return JB_OK;
     }
-    ResampleSpec s{};
+    ResampleGeom g{};
     std::vector<double> taps;
-    const bool identity = in_hz == out_hz; // what a native-rate utterance of a converting batch goes through
-    if (identity) {
-        s = ResampleSpec{1, 1, 1, 1};
-        taps.assign(1, 1.0);
-    } else {
-        int rc = resample_design(in_hz, out_hz, &s, &taps);
-        if (rc)
-            return rc;
-    }
+    int rc = resample_geometry(in_hz, out_hz, &g, &taps);
+    if (rc)
+        return rc;
     ResampleTable t{};
-    t.L = s.L;
-    t.M = s.M;
-    t.C = s.C;
-    t.ntaps = s.ntaps;
-    // pad doubles where a half-wave's lane stride M hits few bank pairs (a double's pair is its index mod 32: rows M
-    // apart take 32 / gcd(M, 32) of them)
-    t.pad = pick_pad_shift(s.M);
-    // rows per tile: the window (rows M + ntaps samples, and its pad) within the LDS budget, 64 rows per wave at most
-    const uint64_t cap = t.pad ? ((uint64_t)(kRsLdsDoubles - 1) << t.pad) / ((1u << t.pad) + 1) : kRsLdsDoubles;
-    const uint64_t fit = s.ntaps + (uint64_t)s.M <= cap ? (cap - s.ntaps) / s.M : 0;
-    if (identity) {
-        // a copy (or the 16-bit conversion alone): y[k] = x[k], large tiles straight from global memory
-        t.identity = 1;
-        t.lds = 0;
-        t.pad = 0;
-        t.rows = kRsCopyRows;
-        t.row_waves = 4;
-    } else if (fit == 0) {
-        t.lds = 0;
-        t.pad = 0;
-        t.rows = 256;
-        t.row_waves = 4;
-    } else {
-        t.lds = 1;
-        if (fit >= 256) {
-            t.rows = 256;
-            t.row_waves = 4;
-        } else if (fit >= 128) {
-            t.rows = 128;
-            t.row_waves = 2;
-        } else {
-            t.rows = (uint32_t)std::min<uint64_t>(fit, 64);
-            t.row_waves = 1;
-        }
-        // a launch allocates only what its tiles' windows take (16 kHz from 48 kHz: 8 KB), so that up to eight
-        // workgroups share a CU and hide the latency of each lane's chain of dependent FMAs
-        const uint32_t wlen = t.rows * s.M + s.ntaps;
-        t.lds_bytes = (uint32_t)(sizeof(double) * (t.pad ? wlen + (wlen >> t.pad) + 1 : wlen));
-    }
+    t.L = g.L;
+    t.M = g.M;
+    t.C = g.C;
+    t.ntaps = g.ntaps;
+    t.rows = g.rows;
+    t.row_waves = g.row_waves;
+    t.lds = g.lds;
+    t.pad = g.pad;
+    t.lds_bytes = g.lds_bytes;
+    t.identity = g.identity;
     // on `device`, whatever the calling thread has current (and that stays current afterwards)
     DeviceScratch scope;
     hipError_t e = scope.enter(device);
@@ -358,6 +383,25 @@ int jb_resample_filter(uint32_t in_hz, uint32_t out_hz, uint32_t *L, uint32_t *M
         }
         std::copy(h.begin(), h.end(), taps);
     }
+    return JB_OK;
+}
+
+int jb_resample_geometry(uint32_t in_hz, uint32_t out_hz, jb_resample_geometry_t *out)
+{
+    if (!out) {
+        set_error("jb_resample_geometry: out is NULL");
+        return JB_ERR_INVALID;
+    }
+    if (in_hz == 0 || out_hz == 0) {
+        set_error("resample: a rate of 0 Hz");
+        return JB_ERR_INVALID;
+    }
+    ResampleGeom g{};
+    int rc = resample_geometry(in_hz, out_hz, &g, nullptr);
+    if (rc)
+        return rc;
+    *out = jb_resample_geometry_t{g.L, g.M, g.ntaps, g.pad, g.cap, g.fit, g.lds, g.rows, g.row_waves, g.lds_bytes,
+                                  g.identity, 0};
     return JB_OK;
 }
 

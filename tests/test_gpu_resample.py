@@ -209,8 +209,10 @@ def test_mixed_rates_fast_invariant(eng):
     assert np.asarray(batch[0]).size == 66480 and np.asarray(batch[3]).size == 33240
 
 
-@pytest.mark.parametrize("out_hz", [22050, 24000])
+@pytest.mark.parametrize("out_hz", [22050, 24000, 96000, 11025, 400])
 def test_generator_steps(eng, out_hz):
+    """96 kHz: an upsampling step of 2 F; 11.025 kHz: a 1-wave padded table, steps of 55 and 56; 400 Hz: the
+    global-memory path, two samples per frame."""
     L, M, _ = J.resample_filter(IN, out_hz)
     e = with_rate(eng, out_hz)
     want = e.synthesize(SAMPLE_SENTENCE_1)
@@ -231,6 +233,8 @@ def test_generator_steps(eng, out_hz):
     assert k == g.total_frames()
     if out_hz == 22050:
         assert {p.size for p in parts} == {110, 111}
+    if out_hz in (96000, 11025, 400):
+        assert {p.size for p in parts} == {96000: {2 * F}, 11025: {55, 56}, 400: {2}}[out_hz]
     same_bits(np.concatenate(parts), want)
     # steps of several frames at once: the same samples
     g2 = e.generator(SAMPLE_SENTENCE_1)

@@ -20,7 +20,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 UNSUPPORTED = -2
 NEW_SYMBOLS = ["jb_batch_set_output_rate", "jb_batch_output_rate", "jb_batch_read_pcm_native", "jb_resample_filter",
                "jb_resample_pcm_batch", "jb_engine_set_output_sampling_frequency",
-               "jb_engine_get_output_sampling_frequency"]
+               "jb_engine_get_output_sampling_frequency", "jb_resample_geometry"]
 
 # (in, out, L, M, ntaps)
 PAIRS = [
@@ -33,6 +33,19 @@ PAIRS = [
     (22050, 48000, 320, 147, 72),
     (16000, 44100, 441, 160, 72),
     (44100, 8000, 80, 441, 392),
+    # the pairs of tests/resample_ref.py that are not above: every path of k_resample, the largest L, M and ntaps
+    (48000, 32000, 2, 3, 108),
+    (16000, 48000, 3, 1, 72),
+    (48000, 25000, 25, 48, 138),
+    (48000, 1500, 1, 32, 2276),
+    (48000, 11025, 147, 640, 310),
+    (44100, 48000, 160, 147, 72),
+    (8000, 44100, 441, 80, 72),
+    (48000, 1000, 1, 48, 3414),
+    (48000, 400, 1, 120, 8534),
+    (2048, 1, 1, 2048, 145636),
+    (1, 2048, 2048, 1, 72),
+    (2048, 2047, 2047, 2048, 72),
 ]
 
 
@@ -72,6 +85,12 @@ def test_filter_table(pair):
     assert np.max(np.abs(taps.sum(axis=1) - 1.0)) <= 1e-5
 
 
+def test_pairs_hold_every_case_of_the_path_tests():
+    from tests import resample_ref as R
+
+    assert {(c.in_hz, c.out_hz, c.L, c.M, c.ntaps) for c in R.CASES} <= set(PAIRS)
+
+
 def test_filter_buffer_and_counts_only():
     l_, m_, nt = C.c_uint32(), C.c_uint32(), C.c_uint32()
     L = J.lib()
@@ -82,7 +101,7 @@ def test_filter_buffer_and_counts_only():
                                 small.size) == -8
 
 
-@pytest.mark.parametrize("pair", PAIRS[:6], ids=[f"{a}-{b}" for a, b, *_ in PAIRS[:6]])
+@pytest.mark.parametrize("pair", PAIRS, ids=[f"{a}-{b}" for a, b, *_ in PAIRS])
 def test_prototype_quality(pair):
     """The prototype's response on the input-rate axis: flat to +-0.001 dB up to 0.8 of the output Nyquist, at most
     -95 dB from the output Nyquist up (what the device's sine test then sees through the polyphase)."""
