@@ -1,0 +1,91 @@
+"""Overlapping talkers as one file: several label files in, ONE FLAC stream or WAV file out -- every sentence at a
+start of its own and under a gain of its own, summed on the GPU.
+
+    python examples/mixture.py voice.htsvoice first.lab second.lab ... -o mixture.flac
+                               --start-ms MS,MS,... [--gain-db DB,DB,...] [--fit [--ceiling DBFS]]
+                               [--lead-ms MS] [--trail-ms MS] [--fade-ms MS] [--rate HZ]
+                               [--room LX,LY,LZ --rt60 S [--vary]] [--stems DIR]
+
+Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
+batch and mixed on the GPU (Engine.set_programme_mix, then Engine.synthesize_programme) in front of the encoder, so a
+.flac output is one stream whose frame numbers, STREAMINFO, MD5 and SEEKTABLE cover the mixture; any other name is
+written as a 16-bit WAV file.  --start-ms and --gain-db take one value per sentence (a gain of 0 dB by default).  With
+--fit a mixture whose peak passes --ceiling is scaled down to it on the GPU; without it the 16-bit sink clamps.  With
+--room every sentence is reverberated by a simulated shoebox room of those edges in metres, with --vary every talker
+from a position of their own (Engine.set_room with vary=True).  With --stems the members' own 16-bit PCM, as it went into
+the sum, is written beside the mixture (s0.wav, s1.wav, ...).  The cue list -- each sentence's first sample and time
+within the mixture -- and the stage's report (the host rule over the stems: the same numbers) are printed.
+Needs an MI355X: the library has no CPU path.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import jbonsai_amd as J  # noqa: E402
+
+
+def floats(s):
+    return [float(v) for v in s.split(",")]
+
+
+ap = argparse.ArgumentParser()
+ap.add_argument("voice")
+ap.add_argument("labels", nargs="+", help="one label file per sentence")
+ap.add_argument("-o", "--out", default="mixture.flac")
+ap.add_argument("--start-ms", type=floats, required=True, metavar="MS,MS,...", help="each sentence's start")
+ap.add_argument("--gain-db", type=floats, default=None, metavar="DB,DB,...", help="each sentence's gain (0 dB)")
+ap.add_argument("--fit", action="store_true", help="scale a mixture over the ceiling down to it")
+ap.add_argument("--ceiling", type=float, default=-1.0, metavar="DBFS", help="the ceiling of --fit")
+ap.add_argument("--lead-ms", type=float, default=0.0, help="silence in front of every start")
+ap.add_argument("--trail-ms", type=float, default=0.0, help="silence every sentence claims behind its end")
+ap.add_argument("--fade-ms", type=float, default=5.0, help="fade at both edges of every sentence")
+ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rate")
+ap.add_argument("--room", default=None, metavar="LX,LY,LZ", help="edges of a simulated room in metres (Engine.set_room)")
+ap.add_argument("--rt60", type=float, default=0.5, metavar="S", help="reverberation time of --room")
+ap.add_argument("--vary", action="store_true", help="with --room: every talker at a position of their own")
+ap.add_argument("--stems", default=None, metavar="DIR", help="write the members' 16-bit PCM there")
+args = ap.parse_args()
+gains = args.gain_db or [0.0] * len(args.labels)
+if len(args.start_ms) != len(args.labels) or len(gains) != len(args.labels):
+    ap.error("--start-ms and --gain-db take one value per label file")
+
+sentences = []
+for path in args.labels:
+    with open(path) as f:
+        sentences.append([ln for ln in f.read().split("\n") if ln and not ln.startswith("#")])
+
+engine = J.Engine.load([args.voice])
+if args.rate:
+    engine.condition.set_output_sampling_frequency(args.rate)
+hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
+if args.room is not None:
+    size = floats(args.room)
+    src, mic = J.room_vary(0, 0, size, 0.5)
+    engine.set_room(J.room(size, src, mic, rt60=args.rt60, hz=hz, n_taps=int(1.2 * args.rt60 * hz)), vary=args.vary,
+                    seed=0)
+place = list(zip(args.start_ms, gains))
+opts = dict(lead_ms=args.lead_ms, trail_ms=args.trail_ms, fade_ms=args.fade_ms, mix=place, fit=args.fit,
+            ceiling_db=args.ceiling)
+if args.out.endswith(".flac"):
+    data, starts = engine.synthesize_programme(sentences, sink="flac", md5=True, seek_interval_ms=1000, **opts)
+    with open(args.out, "wb") as f:
+        f.write(data)
+    print(f"wrote {args.out}: {len(data)} bytes of FLAC at {hz} Hz, MD5 {data[26:42].hex()}")
+else:
+    pcm, starts = engine.synthesize_programme(sentences, sink="i16", **opts)
+    J.write_wav(args.out, pcm, hz)
+    print(f"wrote {args.out}: {pcm.size} samples at {hz} Hz")
+for k, (s, path) in enumerate(zip(starts, args.labels)):
+    print(f"cue {k} {s} {s / hz:.3f} {path}")
+# the stems, and the stage's report from them by the host rule
+stems = engine.synthesize_batch(sentences, i16=True)
+fade, trail = J.join_ms_to_samples(args.fade_ms, hz), J.join_ms_to_samples(args.trail_ms, hz)
+req = [(0, s, g, trail, fade, fade) for s, g in zip(starts, gains)]
+_, (rep,) = J.mix_host(stems, req, J.mix_opts(args.fit, args.ceiling))
+print(f"report peak {rep.peak:.1f} scale {rep.scale:.6f} depth {rep.depth} overlap {rep.overlap} samples "
+      f"({rep.overlap / hz:.3f} s)")
+if args.stems:
+    os.makedirs(args.stems, exist_ok=True)
+    for k, x in enumerate(stems):
+        J.write_wav(os.path.join(args.stems, f"s{k}.wav"), x, hz)

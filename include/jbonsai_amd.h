@@ -243,6 +243,38 @@ typedef struct jb_join_opts {
     double lead_ms, gap_ms, trail_ms, fade_ms;
     uint32_t reserved[2];
 } jb_join_opts;
+/* The mix request of one utterance (see "Mix" below): the programme it belongs to, where it starts within it, the zero
+ * samples it claims behind its end, its edge fades (the join's) and its gain.  reserved and reserved2 must be 0. */
+#define JB_MIX_NONE 0xffffffffu
+typedef struct jb_mix_utt {
+    uint32_t programme;         /* id below jb_batch_size(b), or JB_MIX_NONE: a programme of its own */
+    uint32_t fade_in, fade_out; /* samples at the output rate; 0: none */
+    uint32_t reserved;          /* 0 */
+    uint64_t start;             /* the member's first sample within the programme, at the output rate */
+    uint64_t pad_after;         /* zero samples behind its last one that count for the programme's length */
+    double gain_db;             /* finite in [-120, 40], or -INFINITY: muted, the member counts for the length alone */
+    uint64_t reserved2;         /* 0 */
+} jb_mix_utt;
+/* The options of a whole mix request.  JB_MIX_FIT: a programme whose peak lies above the ceiling is scaled down to
+ * it; ceiling_db in dBFS (finite, in [-120, 0]; 0 dBFS = 32768), read with the flag only.  reserved 0. */
+#define JB_MIX_FIT 1u
+typedef struct jb_mix_opts {
+    uint32_t flags;
+    uint32_t reserved;
+    double ceiling_db;
+} jb_mix_opts;
+/* What the mix stage did to one programme. */
+typedef struct jb_mix_report {
+    double peak;       /* M_p: the largest |sum| in f64 in front of the fit and the sink (a NaN sample is passed over) */
+    double scale;      /* s_p: what JB_MIX_FIT multiplied the sum by; 1 without the flag or under the ceiling */
+    uint32_t depth;    /* the largest number of unmuted members over one sample */
+    uint32_t reserved; /* 0 */
+    uint64_t overlap;  /* samples under two or more unmuted members */
+} jb_mix_report;
+/* A member's place in jb_engine_set_programme_mix: its start behind the lead, and its gain. */
+typedef struct jb_mix_place {
+    double start_ms, gain_db;
+} jb_mix_place;
 
 /* The output filter (see "Filter" below): a cascade of up to JB_FILTER_MAX_SECTIONS second-order sections at the
  * output rate, applied in order.  A section is a kind with f0_hz, q and gain_db (gain_db: peaking and the shelves
@@ -687,6 +719,20 @@ int jb_batch_member_start(const jb_batch *b, size_t utt, uint64_t *start_sample)
  * run like the read entries; cap below the programme's samples: JB_ERR_BUFFER. */
 int jb_batch_read_programme_pcm(jb_batch *b, size_t p, double *dst, size_t cap);
 int jb_batch_read_programme_pcm_i16(jb_batch *b, size_t p, int16_t *dst, size_t cap);
+/* New (none: no reference counterpart).  Mix (see "Mix" below), the join's sibling in the join's place: the run also
+ * sums the utterances' final PCM into programmes, on the device, each member at its start and under its gain.  All
+ * that jb_batch_set_join says of the encoders' indices, of jb_batch_num_outputs, _programme_of, _programme_layout,
+ * _member_start and _read_programme_pcm / _i16, of the output rate and of when the call is allowed holds here too.
+ * n == jb_batch_size(b); opts may be NULL (no flags); req == NULL with n == 0 withdraws the request.  A batch holds a
+ * join request or a mix request, never both: the second setter is refused with JB_ERR_INVALID and changes nothing;
+ * withdrawing the one frees the way for the other.  Refused with JB_ERR_INVALID (jb_last_error names the utterance or
+ * programme and the field): a bad programme id, members of mixed rates, a gain_db outside [-120, 40] that is not
+ * -INFINITY, non-zero reserved words, an unknown flag, a ceiling_db outside [-120, 0] with JB_MIX_FIT.  Work lists of
+ * more than 2^24 entries: JB_ERR_UNSUPPORTED. */
+int jb_batch_set_mix(jb_batch *b, const jb_mix_utt *req, size_t n, const jb_mix_opts *opts);
+/* New (none).  What the stage did to programme p, after a run (peak and scale are the device's).  JB_ERR_INVALID
+ * without a mix request, before a run or for no such programme. */
+int jb_batch_mix_report(jb_batch *b, size_t p, jb_mix_report *out);
 void jb_batch_free(jb_batch *b);
 
 /* One-shot convenience: create + run + read + free.  pcm[i] must hold
@@ -1245,9 +1291,9 @@ void jb_melspec_free(uint8_t *p);
  * - Loudness is measured on the members, in front of the pads; with jb_batch_set_loudness_groups over the same
  *   members the programme has one gain.
  * - Cost: not measured yet.
- * Not covered: the generator, the _multi entries and jb_gather_pcm, the _each forms at engine level, overlapping members (a
- * crossfade, i.e. negative pads), a caller-chosen member order, FLAC CUESHEET / VORBIS_COMMENT blocks and seek points
- * at member starts, loudness measured over the joined programme, reading through the pinned ring. */
+ * Not covered: the generator, the _multi entries and jb_gather_pcm, the _each forms at engine level, a caller-chosen
+ * member order, FLAC CUESHEET / VORBIS_COMMENT blocks and seek points at member starts, loudness measured over the
+ * joined programme, reading through the pinned ring.  (Overlapping members, a crossfade: "Mix" below.) */
 /* New (none).  floor(ms * hz / 1000.0 + 0.5): a duration in samples at hz (0 for a negative or NaN duration). */
 uint64_t jb_join_ms_to_samples(double ms, uint32_t hz);
 /* New (none).  The geometry of a request over n members of n_in[u] samples at hz[u] (hz NULL: not compared):
@@ -1272,6 +1318,67 @@ int jb_join_pcm_batch(const double *const *in, const size_t *n_in, size_t n, con
 int jb_join_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n, const jb_join_utt *req,
                           int32_t device, int16_t **out, size_t *n_out, size_t *n_programmes);
 void jb_join_free(void *p);
+
+/* ---- Mix (new: the reference synthesises one utterance into one buffer; none of these entries has a counterpart) -------
+ * A programme is the SUM of its members, each at a start of its own and under a gain of its own: two talkers at once
+ * (the members' PCM stays readable, so the stems come with the mixture), a crossfade between sentences, a timed event
+ * over a sentence.  The stage stands in the join's place and feeds the same encoders and feature stages, which then
+ * run over the mixture whole.  The rule (jbonsai_amd/csrc/jb_mix.h states it once for the host, the device and the
+ * plan):
+ * - Numbering and rate: as the join's.  Length: the largest start + n + pad_after over a programme's members.  Each
+ *   programme starts on a 16-byte boundary of its slab.
+ * - Gain: g = 10^(gain_db / 20), formed on the host in long double and rounded once (jb_mix_gain); 0 dB is exactly 1,
+ *   -INFINITY exactly 0.
+ * - Sample k: over the members in ascending utterance index, whatever their starts, each one with g != 0 and
+ *   start <= k < start + n gives t = the join's faded sample of x[k - start] in f64 (a 16-bit sample enters as its
+ *   (double); nothing is truncated per member), times g where g != 1.  The first term starts the sum, each later one
+ *   is acc = acc + t (no fma).  Under no member the sample is +0.0.  An f64 programme stores acc, a 16-bit one the
+ *   16-bit sink's rule of acc (clamp, then truncate toward zero).  So a sample under one member at 0 dB outside its
+ *   fades keeps its bits, and a mix whose starts are a join's, at 0 dB, is that join's programme bit for bit.
+ * - Fit (JB_MIX_FIT): M_p = the largest |acc| of the programme (fmax: a NaN is passed over), c the ceiling in sample
+ *   units (32768 * 10^(ceiling_db / 20)), s_p = M_p > c ? c / M_p : 1.  Where s_p != 1 every sample is
+ *   fmin(fmax(acc * s_p, -c), c) in front of the sink, so |y| <= c holds exactly; where s_p == 1 no bit changes.
+ *   Without the flag nothing is scaled and the 16-bit sink clamps as it always does.  The peak is measured either way.
+ * - Report: M_p, s_p, the largest number of unmuted members over one sample, the samples under two or more.
+ * - Independence: a programme's bits depend on its members' samples and the request alone, not on the batch, its
+ *   position, redo rounds (a touched programme runs again whole, the peak included) or the entry point;
+ *   JB_BATCH_INVARIANT output stays invariant.
+ * - Loudness, the ceiling and the limiter stay per utterance in front of the mix, as with the join.  The recipe for
+ *   talkers at a level difference: per-utterance loudness targets set the difference (BS.1770 gating), JB_MIX_FIT
+ *   keeps the sum under the ceiling.
+ * - On the device (jb_mix.hip): the host cuts each programme at every member start and end into segments under a
+ *   constant set of members; k_mix, one workgroup per 16 KiB destination tile, loads each covering member's 16-byte
+ *   group at whatever alignment it has and adds in list order, so the work per sample follows the depth at that
+ *   sample; k_mix_peak folds the tiles' maxima per programme; with JB_MIX_FIT k_mix runs again over the programmes
+ *   with s_p != 1, from the members.  No LDS, no atomics.
+ * - Cost: not measured.
+ * Not covered: loudness measured over the mixture, the generator, the _multi entries, a member in two programmes,
+ * stems materialised in programme coordinates. */
+/* New (none).  g of gain_db by the rule above; pure (a NaN or a value outside the setter's range is not refused here). */
+double jb_mix_gain(double gain_db);
+/* New (none).  The geometry of a request, as jb_join_geometry, plus depth[p] and overlap[p] of the report ([n] each,
+ * the first P written); any out pointer may be NULL; opts may be NULL. */
+int jb_mix_geometry(const jb_mix_utt *req, const size_t *n_in, const uint32_t *hz, size_t n, const jb_mix_opts *opts,
+                    uint32_t *programme_of, uint64_t *member_start, size_t *n_programmes, uint64_t *programme_samples,
+                    uint32_t *depth, uint64_t *overlap);
+/* New (none).  The rule in plain C++ on the host; no GPU is touched.  out[p] must hold programme p's samples (cap[p]
+ * below that: JB_ERR_BUFFER).  scale == NULL: the rule's s_p; otherwise scale[p] is taken as given (as jb_noise_host
+ * takes a gain) and reported.  reports (may be NULL): [P]. */
+int jb_mix_host(const double *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req, const jb_mix_opts *opts,
+                const double *scale, double *const *out, const size_t *cap, jb_mix_report *reports);
+int jb_mix_i16_host(const int16_t *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                    const jb_mix_opts *opts, const double *scale, int16_t *const *out, const size_t *cap,
+                    jb_mix_report *reports);
+/* New (none).  The stage on PCM the caller holds (jb_join_pcm_batch's twin), on `device` (-1 = current).  out and
+ * n_out have n entries; the first *n_programmes are written: out[p] = programme p, library-owned (jb_mix_free each).
+ * reports (may be NULL): [n], the first P written, peak and scale the device's. */
+int jb_mix_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                     const jb_mix_opts *opts, int32_t device, double **out, size_t *n_out, size_t *n_programmes,
+                     jb_mix_report *reports);
+int jb_mix_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                         const jb_mix_opts *opts, int32_t device, int16_t **out, size_t *n_out, size_t *n_programmes,
+                         jb_mix_report *reports);
+void jb_mix_free(void *p);
 
 /* ---- Filter (new: the reference has no such control) ---------------------------------------------------------------
  * A caller-chosen cascade of up to four second-order sections shapes the PCM on the device, at the output rate: behind
@@ -1867,6 +1974,15 @@ int jb_engine_set_room(jb_engine *e, const jb_room *r, uint32_t flags, uint64_t 
  * again at synthesis.  jb_engine_new copies it with the Condition; jb_engine_get_noise's bed points into the engine's
  * copy (valid until the next jb_engine_set_noise). */
 int jb_engine_set_noise(jb_engine *e, const jb_noise *req);
+/* New (none).  While set, every jb_synthesize_programme* entry called with n utterances MIXES them instead of joining
+ * them ("Mix" below), whatever its sink: utterance u starts at jb_join_ms_to_samples(lead_ms + place[u].start_ms) under
+ * place[u].gain_db, trail_ms is every member's pad_after, fade_ms every member's fades, and gap_ms must be 0.  starts
+ * receives the members' starts as with a join.  A call with another utterance count or a non-zero gap: JB_ERR_INVALID
+ * before any device is touched.  Here: a negative or non-finite start_ms, a gain_db or options jb_batch_set_mix would
+ * refuse: JB_ERR_INVALID.  opts may be NULL (no flags); NULL, 0 withdraws the setting.  The getter writes *n, *opts and,
+ * where place is given, the n places (cap below n: JB_ERR_BUFFER); any out pointer may be NULL. */
+int jb_engine_set_programme_mix(jb_engine *e, const jb_mix_place *place, size_t n, const jb_mix_opts *opts);
+int jb_engine_get_programme_mix(const jb_engine *e, jb_mix_place *place, size_t cap, size_t *n, jb_mix_opts *opts);
 int jb_engine_get_noise(const jb_engine *e, jb_noise *out);
 /* New.  The limiter of the audio the engine's entries return (see "Limiter"): jb_synthesize, every
  * jb_synthesize_batch* and jb_synthesize_programme* form and _each* (each engine's own request for its utterance: not
@@ -2229,6 +2345,15 @@ JB_LAYOUT_ASSERT(sizeof(jb_melspec_opts) == 96 && offsetof(jb_melspec_opts, f_mi
 JB_LAYOUT_ASSERT(sizeof(jb_join_utt) == 32 && offsetof(jb_join_utt, fade_out) == 8 &&
                      offsetof(jb_join_utt, pad_before) == 16 && offsetof(jb_join_utt, pad_after) == 24,
                  "jb_join_utt");
+JB_LAYOUT_ASSERT(sizeof(jb_mix_utt) == 48 && offsetof(jb_mix_utt, fade_out) == 8 && offsetof(jb_mix_utt, start) == 16 &&
+                     offsetof(jb_mix_utt, pad_after) == 24 && offsetof(jb_mix_utt, gain_db) == 32 &&
+                     offsetof(jb_mix_utt, reserved2) == 40,
+                 "jb_mix_utt");
+JB_LAYOUT_ASSERT(sizeof(jb_mix_opts) == 16 && offsetof(jb_mix_opts, ceiling_db) == 8, "jb_mix_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_mix_report) == 32 && offsetof(jb_mix_report, scale) == 8 &&
+                     offsetof(jb_mix_report, depth) == 16 && offsetof(jb_mix_report, overlap) == 24,
+                 "jb_mix_report");
+JB_LAYOUT_ASSERT(sizeof(jb_mix_place) == 16 && offsetof(jb_mix_place, gain_db) == 8, "jb_mix_place");
 JB_LAYOUT_ASSERT(sizeof(jb_join_opts) == 40 && offsetof(jb_join_opts, fade_ms) == 24 &&
                      offsetof(jb_join_opts, reserved) == 32, "jb_join_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_loudness_report) == 40 && offsetof(jb_loudness_report, gain_db) == 24 &&

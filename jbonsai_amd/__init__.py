@@ -12,6 +12,8 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    adpcm_encode_host, adpcm_geometry, write_wav_adpcm, loudness_groups, loudness_gate_host,
                    LOUDNESS_NO_GROUP, LOUDNESS_R128, LOUDNESS_PER_UTTERANCE, LOUDNESS_PER_REQUEST,
                    JOIN_NONE, JoinUtt, join_geometry, join_host, join_ms_to_samples, join_pcm,
+                   MIX_NONE, MIX_FIT, MixUtt, MixOpts, MixReport, MixPlace, mix_opts, mix_geometry, mix_gain, mix_host,
+                   mix_pcm,
                    Filter, FilterSection, Biquad, filter_design, filter_sos, filter_pcm, filter_pcm_host, highpass,
                    lowpass, peaking, lowshelf, highshelf, notch, raw_filter, telephone_band, no_filter,
                    Fir, fir, fir_geometry, fir_host, fir_pcm, FIR_MAX_TAPS, FIR_DIRECT_MAX, FIR_DIRECT, FIR_PARTITIONED,
@@ -49,7 +51,8 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "AdpcmStream", "adpcm_decode_host", "adpcm_encode", "adpcm_encode_host", "adpcm_geometry", "write_wav_adpcm",
            "synthesize_batch_each_adpcm", "loudness_groups", "loudness_gate_host", "LOUDNESS_NO_GROUP", "LOUDNESS_R128", "LOUDNESS_PER_UTTERANCE",
            "LOUDNESS_PER_REQUEST", "JOIN_NONE", "JoinUtt", "join_geometry", "join_host", "join_ms_to_samples",
-           "join_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",
+           "join_pcm", "MIX_NONE", "MIX_FIT", "MixUtt", "MixOpts", "MixReport", "MixPlace", "mix_opts", "mix_geometry",
+           "mix_gain", "mix_host", "mix_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",
            "filter_pcm_host", "highpass", "lowpass", "peaking", "lowshelf", "highshelf", "notch", "raw_filter",
            "telephone_band", "no_filter", "Fir", "fir", "fir_geometry", "fir_host", "fir_pcm", "FIR_MAX_TAPS",
            "FIR_DIRECT_MAX", "FIR_DIRECT", "FIR_PARTITIONED", "Noise", "NoiseReport", "noise", "noise_host",

@@ -415,6 +415,56 @@ def join_request(req):
     return arr
 
 
+MIX_NONE = 0xFFFFFFFF
+MIX_FIT = 1
+
+
+class MixUtt(C.Structure):
+    """jb_mix_utt: an utterance's programme, its start within it, its pad behind, its edge fades and its gain."""
+    _fields_ = [("programme", C.c_uint32), ("fade_in", C.c_uint32), ("fade_out", C.c_uint32), ("reserved", C.c_uint32),
+                ("start", C.c_uint64), ("pad_after", C.c_uint64), ("gain_db", C.c_double), ("reserved2", C.c_uint64)]
+
+
+class MixOpts(C.Structure):
+    """jb_mix_opts: MIX_FIT and its ceiling in dBFS."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("ceiling_db", C.c_double)]
+
+
+class MixReport(C.Structure):
+    """jb_mix_report: a programme's peak, its scale, its depth and its samples under two or more members."""
+    _fields_ = [("peak", C.c_double), ("scale", C.c_double), ("depth", C.c_uint32), ("reserved", C.c_uint32),
+                ("overlap", C.c_uint64)]
+
+
+class MixPlace(C.Structure):
+    """jb_mix_place: a member's start behind the lead in milliseconds, and its gain."""
+    _fields_ = [("start_ms", C.c_double), ("gain_db", C.c_double)]
+
+
+def mix_opts(fit: bool = False, ceiling_db: float = 0.0):
+    o = MixOpts()
+    o.flags, o.ceiling_db = MIX_FIT * bool(fit), float(ceiling_db)
+    return o
+
+
+def mix_request(req):
+    """A (MixUtt * n) array of `req`: MixUtt entries, or tuples / dicts of (programme, start, gain_db, pad_after,
+    fade_in, fade_out) with programme None for an utterance of its own and the rest 0 by default."""
+    arr = (MixUtt * max(1, len(req)))()
+    for i, r in enumerate(req):
+        if isinstance(r, MixUtt):
+            arr[i] = r
+            continue
+        if isinstance(r, dict):
+            r = (r.get("programme"), r.get("start", 0), r.get("gain_db", 0.0), r.get("pad_after", 0),
+                 r.get("fade_in", 0), r.get("fade_out", 0))
+        r = tuple(r) + (0,) * (6 - len(r))
+        arr[i].programme = MIX_NONE if r[0] is None else int(r[0])
+        arr[i].start, arr[i].gain_db, arr[i].pad_after = int(r[1]), float(r[2]), int(r[3])
+        arr[i].fade_in, arr[i].fade_out = int(r[4]), int(r[5])
+    return arr
+
+
 FILTER_MAX_SECTIONS = 4
 FILTER_HIGHPASS, FILTER_LOWPASS, FILTER_PEAKING, FILTER_LOWSHELF, FILTER_HIGHSHELF, FILTER_NOTCH, FILTER_RAW = range(1, 8)
 
@@ -803,6 +853,9 @@ SYMBOLS = [
     "jb_batch_member_start", "jb_batch_read_programme_pcm", "jb_batch_read_programme_pcm_i16",
     "jb_join_ms_to_samples", "jb_join_geometry", "jb_join_host", "jb_join_i16_host", "jb_join_pcm_batch",
     "jb_join_pcm_batch_i16", "jb_join_free",
+    "jb_batch_set_mix", "jb_batch_mix_report", "jb_mix_gain", "jb_mix_geometry", "jb_mix_host", "jb_mix_i16_host",
+    "jb_mix_pcm_batch", "jb_mix_pcm_batch_i16", "jb_mix_free", "jb_engine_set_programme_mix",
+    "jb_engine_get_programme_mix",
     "jb_batch_set_filter", "jb_batch_filter_coefficients", "jb_filter_design", "jb_filter_pcm_host",
     "jb_filter_pcm_batch", "jb_filter_pcm_batch_i16", "jb_filter_free", "jb_engine_set_filter", "jb_engine_get_filter",
     "jb_batch_set_fir", "jb_batch_fir_geometry", "jb_engine_set_fir", "jb_fir_host", "jb_fir_geometry",
@@ -1144,6 +1197,22 @@ def lib():
     L.jb_join_pcm_batch_i16.argtypes = L.jb_join_pcm_batch.argtypes
     L.jb_join_free.argtypes = [vp]
     L.jb_join_free.restype = None
+    mxup, mxop, mxrp = C.POINTER(MixUtt), C.POINTER(MixOpts), C.POINTER(MixReport)
+    L.jb_batch_set_mix.argtypes = [vp, mxup, sz, mxop]
+    L.jb_batch_mix_report.argtypes = [vp, sz, mxrp]
+    L.jb_mix_gain.argtypes = [C.c_double]
+    L.jb_mix_gain.restype = C.c_double
+    L.jb_mix_geometry.argtypes = [mxup, C.POINTER(sz), u32p, sz, mxop, u32p, u64p, C.POINTER(sz), u64p, u32p, u64p]
+    L.jb_mix_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, mxup, mxop, C.POINTER(C.c_double), C.POINTER(vp),
+                              C.POINTER(sz), mxrp]
+    L.jb_mix_i16_host.argtypes = L.jb_mix_host.argtypes
+    L.jb_mix_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, mxup, mxop, C.c_int32, C.POINTER(vp), C.POINTER(sz),
+                                   C.POINTER(sz), mxrp]
+    L.jb_mix_pcm_batch_i16.argtypes = L.jb_mix_pcm_batch.argtypes
+    L.jb_mix_free.argtypes = [vp]
+    L.jb_mix_free.restype = None
+    L.jb_engine_set_programme_mix.argtypes = [vp, C.POINTER(MixPlace), sz, mxop]
+    L.jb_engine_get_programme_mix.argtypes = [vp, C.POINTER(MixPlace), sz, C.POINTER(sz), mxop]
     flp, bqp = C.POINTER(Filter), C.POINTER(Biquad)
     L.jb_batch_set_filter.argtypes = [vp, flp, sz]
     L.jb_batch_filter_coefficients.argtypes = [vp, sz, bqp, u32p]
@@ -1902,6 +1971,61 @@ def join_pcm(pcms, req, device: int = -1):
     L = lib()
     check((L.jb_join_pcm_batch_i16 if i16 else L.jb_join_pcm_batch)(ins, nin, n, arr, device, outs, ns, C.byref(P)))
     return _take(L.jb_join_free, outs, ns, P.value, np.int16 if i16 else np.float64)
+
+
+def mix_gain(gain_db: float) -> float:
+    """jb_mix_gain: 10^(gain_db / 20) formed in long double and rounded once; exactly 1 at 0 dB, 0 at -inf."""
+    return float(lib().jb_mix_gain(float(gain_db)))
+
+
+def mix_geometry(req, lengths, hz=None, opts=None):
+    """jb_mix_geometry: (programme_of [n], member_start [n], programme_samples [P], depth [P], overlap [P]) of a
+    request (mix_request's forms) over members of `lengths` samples; hz: one rate per member to compare, or None."""
+    n = len(lengths)
+    arr = mix_request(req)
+    nin = (C.c_size_t * max(n, 1))(*[int(x) for x in lengths])
+    hzs = None if hz is None else (C.c_uint32 * max(n, 1))(*[int(h) for h in hz])
+    po, ms = (C.c_uint32 * max(n, 1))(), (C.c_uint64 * max(n, 1))()
+    P, ps = C.c_size_t(), (C.c_uint64 * max(n, 1))()
+    dp, ov = (C.c_uint32 * max(n, 1))(), (C.c_uint64 * max(n, 1))()
+    check(lib().jb_mix_geometry(arr, nin, hzs, n, None if opts is None else C.byref(opts), po, ms, C.byref(P), ps,
+                                dp, ov))
+    return list(po[:n]), list(ms[:n]), list(ps[:P.value]), list(dp[:P.value]), list(ov[:P.value])
+
+
+def mix_host(pcms, req, opts=None, scale=None):
+    """jb_mix_host / jb_mix_i16_host (by the arrays' dtype): (programmes, reports) of the members `pcms` under the
+    request `req` and the MixOpts `opts`, in plain C++ on the host (no GPU); scale: one given s per programme."""
+    import numpy as np
+
+    i16, arrs, n, ins, nin = _join_inputs(pcms)
+    arr = mix_request(req)
+    ps = mix_geometry(arr[:n], [a.size for a in arrs])[2]
+    outs = [np.empty(int(k), dtype=np.int16 if i16 else np.float64) for k in ps]
+    P = len(outs)
+    optr = (C.c_void_p * max(P, 1))(*[o.ctypes.data if o.size else None for o in outs])
+    caps = (C.c_size_t * max(P, 1))(*[o.size for o in outs])
+    reps = (MixReport * max(P, 1))()
+    sc = None if scale is None else (C.c_double * max(P, 1))(*[float(v) for v in scale])
+    L = lib()
+    check((L.jb_mix_i16_host if i16 else L.jb_mix_host)(ins, nin, n, arr, None if opts is None else C.byref(opts), sc,
+                                                        optr, caps, reps))
+    return outs, list(reps[:P])
+
+
+def mix_pcm(pcms, req, opts=None, device: int = -1):
+    """jb_mix_pcm_batch / _i16 (by the arrays' dtype): the same (programmes, reports), mixed on the GPU."""
+    import numpy as np
+
+    i16, arrs, n, ins, nin = _join_inputs(pcms)
+    arr = mix_request(req)
+    outs, ns, P = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), C.c_size_t()
+    reps = (MixReport * max(n, 1))()
+    L = lib()
+    check((L.jb_mix_pcm_batch_i16 if i16 else L.jb_mix_pcm_batch)(ins, nin, n, arr,
+                                                                  None if opts is None else C.byref(opts), device, outs,
+                                                                  ns, C.byref(P), reps))
+    return _take(L.jb_mix_free, outs, ns, P.value, np.int16 if i16 else np.float64), list(reps[:P.value])
 
 
 def _biquads(arr, n):

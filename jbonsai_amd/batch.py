@@ -703,6 +703,23 @@ class Batch:
             return
         F.check(self._L.jb_batch_set_join(self._h, F.join_request(req), len(req)))
 
+    def set_mix(self, req, fit: bool = False, ceiling_db: float = 0.0):
+        """jb_batch_set_mix: one request per utterance -- F.MixUtt entries, or (programme, start, gain_db, pad_after,
+        fade_in, fade_out) tuples with programme None for an utterance of its own, in samples at the output rate; None
+        withdraws the request.  The run then sums the final PCM into programmes on the GPU, in the join's place: a
+        batch holds a join or a mix request.  fit: a programme over ceiling_db (dBFS) is scaled down to it."""
+        if req is None:
+            F.check(self._L.jb_batch_set_mix(self._h, None, 0, None))
+            return
+        o = F.mix_opts(fit, ceiling_db)
+        F.check(self._L.jb_batch_set_mix(self._h, F.mix_request(req), len(req), C.byref(o)))
+
+    def mix_report(self, p):
+        """jb_batch_mix_report: the F.MixReport of programme p, after a run."""
+        r = F.MixReport()
+        F.check(self._L.jb_batch_mix_report(self._h, p, C.byref(r)))
+        return r
+
     def num_outputs(self) -> int:
         """What the encoders' entries index: the programmes with a join request, else the utterances."""
         return self._L.jb_batch_num_outputs(self._h)

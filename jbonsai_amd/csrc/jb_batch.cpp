@@ -2992,6 +2992,19 @@ int jb_batch_set_join(jb_batch *hb, const jb_join_utt *req, size_t n)
     return hb ? ((Batch *)hb)->out.set_join(req, n) : JB_ERR_INVALID;
 }
 
+int jb_batch_set_mix(jb_batch *hb, const jb_mix_utt *req, size_t n, const jb_mix_opts *opts)
+{
+    return hb ? ((Batch *)hb)->out.set_mix(req, n, opts) : JB_ERR_INVALID;
+}
+
+int jb_batch_mix_report(jb_batch *hb, size_t p, jb_mix_report *out)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !out)
+        return JB_ERR_INVALID;
+    return b->out.read_mix(p, out);
+}
+
 size_t jb_batch_num_outputs(const jb_batch *hb) { return hb ? ((const Batch *)hb)->out.num_outputs() : 0; }
 
 int32_t jb_batch_programme_of(const jb_batch *hb, size_t utt)

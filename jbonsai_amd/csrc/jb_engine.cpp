@@ -83,6 +83,8 @@ struct Condition {
     }
     bool limiter_on = false;      // jb_engine_set_limiter: a request is set ...
     jb_limiter_opts limiter{};    // ... and the request as it was given
+    std::vector<jb_mix_place> mix_place; // jb_engine_set_programme_mix: each member's start and gain (empty = off) ...
+    jb_mix_opts mix_opts{};              // ... and the request's options
     uint32_t tree_search = JB_SEARCH_HOST; // jb_engine_set_tree_search: where the per-label tree search runs
     double speed = 1.0;
     size_t stage = 0;
@@ -1227,6 +1229,58 @@ int jb_engine_set_noise(jb_engine *e, const jb_noise *req)
     c.noise_req.bed = nullptr;
     return JB_OK;
 }
+int jb_engine_set_programme_mix(jb_engine *e, const jb_mix_place *place, size_t n, const jb_mix_opts *opts)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    jb::Condition &c = ENG(e)->cond;
+    if (!place && n == 0) {
+        c.mix_place.clear();
+        c.mix_opts = jb_mix_opts{};
+        return JB_OK;
+    }
+    if (!place || n == 0) {
+        jb::set_error("jb_engine_set_programme_mix: give one place per utterance (NULL, 0 withdraws the setting)");
+        return JB_ERR_INVALID;
+    }
+    // the request's fields through the stage's own check (the starts are set when the rate is known)
+    std::vector<jb_mix_utt> req(n, jb_mix_utt{});
+    std::vector<uint64_t> len(n, 0);
+    for (size_t u = 0; u < n; u++) {
+        if (!(place[u].start_ms >= 0.0) || !std::isfinite(place[u].start_ms)) {
+            jb::set_error("jb_engine_set_programme_mix: start_ms is finite and not negative (utterance " +
+                          std::to_string(u) + ")");
+            return JB_ERR_INVALID;
+        }
+        req[u].gain_db = place[u].gain_db;
+    }
+    jb::MixLayout lay;
+    int rc = jb::mix_layout_checked((const jb::MixUtt *)req.data(), len.data(), nullptr, n, sizeof(double),
+                                    (const jb::MixOpts *)opts, &lay, "jb_engine_set_programme_mix");
+    if (rc)
+        return rc;
+    c.mix_place.assign(place, place + n);
+    c.mix_opts = opts ? *opts : jb_mix_opts{};
+    return JB_OK;
+}
+int jb_engine_get_programme_mix(const jb_engine *e, jb_mix_place *place, size_t cap, size_t *n, jb_mix_opts *opts)
+{
+    if (!e)
+        return JB_ERR_INVALID;
+    const jb::Condition &c = CENG(e)->cond;
+    if (n)
+        *n = c.mix_place.size();
+    if (opts)
+        *opts = c.mix_opts;
+    if (place) {
+        if (cap < c.mix_place.size()) {
+            jb::set_error("jb_engine_get_programme_mix: the buffer is too small");
+            return JB_ERR_BUFFER;
+        }
+        std::copy(c.mix_place.begin(), c.mix_place.end(), place);
+    }
+    return JB_OK;
+}
 int jb_engine_get_noise(const jb_engine *e, jb_noise *out)
 {
     if (!e || !out)
@@ -1869,6 +1923,27 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
 int SynthRun::request_programme(jb::OutputChain &out, size_t lo, size_t hi)
 {
     const jb_join_opts *join = rq.join;
+    // with jb_engine_set_programme_mix the programme is a mix: member u starts at lead + start_ms[u] under its gain,
+    // the trail is every member's pad behind it, the fade every member's fades (the entry has checked count and gap)
+    const Condition &c0 = eng(lo)->cond;
+    if (!c0.mix_place.empty()) {
+        const uint32_t mhz = out.utt(0).hz;
+        std::vector<jb_mix_utt> mreq(hi - lo, jb_mix_utt{});
+        for (size_t u = 0; u < mreq.size(); u++) {
+            mreq[u].programme = 0;
+            mreq[u].fade_in = mreq[u].fade_out =
+                (uint32_t)std::min<uint64_t>(jb::join_ms_to_samples(join->fade_ms, mhz), 0xffffffffu);
+            mreq[u].start = jb::join_ms_to_samples(join->lead_ms + c0.mix_place[u].start_ms, mhz);
+            mreq[u].pad_after = jb::join_ms_to_samples(join->trail_ms, mhz);
+            mreq[u].gain_db = c0.mix_place[u].gain_db;
+        }
+        const int mrc = out.set_mix(mreq.data(), mreq.size(), &c0.mix_opts);
+        if (mrc)
+            return mrc;
+        for (size_t u = 0; rq.join_starts && u < mreq.size(); u++)
+            rq.join_starts[lo + u] = out.member_start(u);
+        return JB_OK;
+    }
     // one programme: the lead in front of the first member, the gap behind every member but the last, the
     // trail behind the last, the fade at both edges of each, in samples at the output rate
     const uint32_t hz = out.utt(0).hz;
@@ -2295,7 +2370,7 @@ static int check_sink_opts(const jb::SynthRequest &rq, const char *who)
 }
 
 // jb_synthesize_programme*: the join options
-static int check_join_entry(const jb_join_opts *j, size_t n_utts, const char *who)
+static int check_join_entry(const jb_engine *e, const jb_join_opts *j, size_t n_utts, const char *who)
 {
     if (!j) {
         jb::set_error(std::string(who) + ": join is NULL");
@@ -2314,6 +2389,17 @@ static int check_join_entry(const jb_join_opts *j, size_t n_utts, const char *wh
         jb::set_error(std::string(who) + ": a programme has at least one utterance");
         return JB_ERR_INVALID;
     }
+    // while jb_engine_set_programme_mix is set the call mixes: one place per utterance, and no gap
+    const size_t n_mix = e ? CENG(e)->cond.mix_place.size() : 0;
+    if (n_mix && n_mix != n_utts) {
+        jb::set_error(std::string(who) + ": jb_engine_set_programme_mix places " + std::to_string(n_mix) +
+                      " utterances, the call has " + std::to_string(n_utts));
+        return JB_ERR_INVALID;
+    }
+    if (n_mix && j->gap_ms != 0.0) {
+        jb::set_error(std::string(who) + ": gap_ms must be 0 while jb_engine_set_programme_mix is set");
+        return JB_ERR_INVALID;
+    }
     return JB_OK;
 }
 
@@ -2324,7 +2410,7 @@ static int synthesize_entry(const char *who, const jb::SynthRequest &rq, const j
                             bool programme)
 {
     int rc = check_sink_opts(rq, who);
-    if (rc || (programme && (rc = check_join_entry(rq.join, rq.n_utts, who))))
+    if (rc || (programme && (rc = check_join_entry(rq.e, rq.join, rq.n_utts, who))))
         return rc;
     return engines ? synthesize_each(engines, rq) : jb::synthesize_batch_impl(rq);
 }

@@ -424,6 +424,29 @@ void join_lists(const JoinLayout &lay, const JoinUtt *req, const uint64_t *n, co
 hipError_t launch_join(bool i16, const JoinSpan *spans_dev, uint32_t n, uint64_t tiles, const JoinMember *members_dev,
                        hipStream_t stream);
 
+// The mix stage (jb_mix.hip; the rules and the work lists' entries: jb_mix.h; the layout: jb_output.h; the host half:
+// jb_mix.cpp).  mix_layout with the request's and the options' fields checked and set_error naming what is wrong
+// (JB_ERR_INVALID; lists past kMixMaxList entries: JB_ERR_UNSUPPORTED).  opts may be null
+int mix_layout_checked(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
+                       const MixOpts *opts, MixLayout *out, const char *who);
+// The lists of a run: members[i] for the layout's members[i] (utterance u's samples at x + xoff[u] elements) and one
+// span per programme (programme p at y + units[p].off elements); *tiles their tiles, the peak scratch's slots / kMixWaves
+void mix_lists(const MixLayout &lay, const MixUtt *req, const uint64_t *n, const uint64_t *xoff, const void *x, void *y,
+               size_t elem, std::vector<MixMember> *members, std::vector<MixSpan> *spans, uint64_t *tiles);
+// What a launch reads on the device beside its spans
+struct MixLaunch {
+    const MixMember *members;
+    const MixSeg *segs;
+    const uint32_t *lists;
+    double *tile_peak; // kMixWaves per tile, by the spans' pk0
+    MixResult *res;    // by the spans' prog
+    bool fit;          // kMixFit: the second pass follows
+    double ceiling;    // in sample units, with fit
+};
+// spans_dev[0..n) of `tiles` tiles in all: k_mix, k_mix_peak and with fit k_mix again over the programmes of s != 1
+hipError_t launch_mix(bool i16, const MixSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L,
+                      hipStream_t stream);
+
 // The filter stage (jb_filter.hip; the rules, FilterClass and FilterUtt: jb_filter.h; the host half: jb_filter.cpp)
 // f at `hz`: its coefficients into c ([n_sections][5], may be null), or JB_ERR_INVALID with set_error naming the
 // utterance `utt`, the section and the field
@@ -827,6 +850,10 @@ struct OutputChain {
     // req[u]: utterance u's programme, pads and fades, n == B (nullptr, 0: the request is withdrawn); this setter and
     // set_output_rate check that a programme's members agree on the rate
     int set_join(const jb_join_utt *req, size_t n);
+    // req[u]: utterance u's programme, start, pad, fades and gain, n == B, under opts (may be null); nullptr, 0: the
+    // request is withdrawn.  Checked as set_join's; a batch holds a join or a mix request, the second setter is refused
+    int set_mix(const jb_mix_utt *req, size_t n, const jb_mix_opts *opts);
+    int read_mix(size_t p, jb_mix_report *out); // after sync
     // the cepstral features behind a filterbank pass of their own (jb_mfcc.h): an f64 batch only; the filterbank
     // options checked at every utterance's output rate (both NULL: the request is withdrawn); set_output_rate checks
     // the combined request again.  Independent of set_fbank
@@ -909,7 +936,8 @@ struct OutputChain {
     uint32_t fbank_hz(size_t u) const { return joined() ? plan.units[u].hz : plan.utt[u].hz; }
     // the join: what the encoders' entries index (the programmes, or the utterances without a request), an
     // utterance's programme (-1 without a request) and start, a programme's place, members and PCM
-    bool joined() const { return plan.join.slab != OutSlab::None; }
+    bool joined() const { return plan.join.slab != OutSlab::None; } // a join or a mix request
+    bool mixed() const { return plan.mixed; }                        // the programmes are a mix request's
     size_t num_outputs() const { return joined() ? plan.units.size() : plan.utt.size(); }
     int32_t programme_of(size_t u) const { return joined() ? (int32_t)plan.prog_of[u] : -1; }
     uint64_t member_start(size_t u) const { return plan.prog_start[u]; }
@@ -936,6 +964,8 @@ private:
     bool ml_on = false;                        // mel spectrograms are requested
     MelOpts ml_p{};
     std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
+    std::vector<MixUtt> mix_req;               // [B] the mix request; empty: none (never beside join_req)
+    MixOpts mix_opts{};                        // its options
     std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
     FirClasses fir_cls;                        // the distinct responses of the convolution request (its copies)
@@ -1025,6 +1055,11 @@ private:
         JoinMember *members_dev = nullptr;
         uint64_t tiles = 0;
     } jn;
+    struct Mix { // in the join's place; follows `units`: a touched programme runs again whole
+        DevList<MixSpan> spans; // [P] every programme
+        MixLaunch L{};          // the members, the segments and their lists, the peak scratch, the results
+        uint64_t tiles = 0;
+    } mx;
     struct Flac { // follows `units`, by work item; the pack takes every stream
         DevList<FlacWork> work;
         DevList<uint32_t> md5;     // with an MD5 request: the units in launch order
@@ -1109,6 +1144,8 @@ private:
                      const std::vector<double> &ceiling, const std::vector<uint32_t> &mode,
                      const std::vector<uint32_t> &want, const char *who, LnGroups *out) const;
     int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
+    int check_mix(const std::vector<MixUtt> &req, const MixOpts &opts, const std::vector<uint32_t> &want,
+                  const char *who) const;
     int check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const;
     int check_fir(const std::vector<uint32_t> &want, const char *who) const; // the responses' rates under `want`
     int install_fir(const jb_fir *f, size_t n, const char *who);             // set_fir's and set_room's common half
@@ -1124,6 +1161,7 @@ private:
     int prepare_limiter(), select_limiter(const RedoScope *scope), launch_limiter(bool redo);
     int prepare_join(), select_join(const RedoScope *scope), launch_join(bool redo);
     JoinSpan join_span(size_t p, uint64_t k0, uint64_t k1, uint64_t *tiles) const;
+    int prepare_mix(), select_mix(const RedoScope *scope), launch_mix(bool redo);
     int prepare_flac(), select_flac(const RedoScope *scope), launch_flac(bool redo);
     int prepare_format(), select_format(const RedoScope *scope), launch_format(bool redo);
     int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);

@@ -96,6 +96,31 @@ OutPlan plan_output(const OutPlanIn &in)
                 p.flac = p.join.slab;
         }
     }
+    // a mix request goes exactly where the join goes: the same slab, the same fields, the programmes its sums
+    if (in.mix && !in.join) {
+        std::vector<uint64_t> n(in.B);
+        for (size_t u = 0; u < in.B; u++)
+            n[u] = p.utt[u].n;
+        MixLayout lay;
+        if (mix_layout(in.mix, n.data(), nullptr, in.B, p.final.i16 ? 2 : 8, &lay, nullptr, nullptr)) {
+            p.join_src = p.final;
+            p.join = {p.final.i16 ? OutSlab::Join16 : OutSlab::Join64, p.final.i16};
+            p.mixed = true;
+            for (size_t g = 0; g < lay.units.size(); g++)
+                lay.units[g].hz = p.utt[lay.progs.members[lay.progs.first[g]]].hz;
+            p.units = lay.units;
+            p.prog_of = std::move(lay.progs.group_of);
+            p.prog_first = std::move(lay.progs.first);
+            p.prog_members = std::move(lay.progs.members);
+            p.prog_start = std::move(lay.start);
+            p.mix_depth = std::move(lay.depth);
+            p.mix_overlap = std::move(lay.overlap);
+            p.alloc[(size_t)p.join.slab] = std::max<uint64_t>(lay.total, 1);
+            enc = p.join;
+            if (p.flac != OutSlab::None)
+                p.flac = p.join.slab;
+        }
+    }
     const bool joined = p.join.slab != OutSlab::None;
     if (joined)
         units = p.units;
@@ -232,6 +257,100 @@ bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size
         }
         w.hz = hz ? hz[lay.progs.members[lay.progs.first[g]]] : 0;
         lay.total = (w.off + w.n + align - 1) / align * align;
+    }
+    *out = std::move(lay);
+    return true;
+}
+
+bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, MixLayout *out,
+                uint32_t *bad, const char **field)
+{
+    static_assert(kMixNone == kLnNoGroup, "one numbering for groups and programmes");
+    auto refuse = [&](uint32_t id, const char *f) {
+        if (bad)
+            *bad = id;
+        if (field)
+            *field = f;
+        return false;
+    };
+    std::vector<uint32_t> ids(B);
+    for (size_t u = 0; u < B; u++)
+        ids[u] = req[u].programme;
+    LnGroupsIn gi;
+    gi.B = B;
+    gi.group = ids.data();
+    gi.hz = hz;
+    MixLayout lay;
+    uint32_t id = 0;
+    const char *f = "";
+    if (!plan_loudness_groups(gi, &lay.progs, &id, &f))
+        return refuse(id, f[0] == 'g' ? "programme id" : f); // ("group id")
+    const size_t P = lay.progs.size();
+    const uint64_t align = kMixGroupBytes / elem;
+    constexpr uint64_t kMaxLen = 1ull << 63;
+    lay.units.assign(P, OutUnit{});
+    lay.start.assign(B, 0);
+    lay.gain.assign(B, 0.0);
+    lay.seg_first.assign(P + 1, 0);
+    lay.depth.assign(P, 0);
+    lay.overlap.assign(P, 0);
+    struct Event {
+        uint64_t k;
+        uint32_t at; // the member's place in progs.members
+        bool add;
+    };
+    std::vector<Event> ev;
+    std::vector<uint32_t> cover; // ascending places: ascending utterance indices
+    for (size_t g = 0; g < P; g++) {
+        OutUnit &w = lay.units[g];
+        w.off = lay.total;
+        ev.clear();
+        for (uint32_t i = lay.progs.first[g]; i < lay.progs.first[g + 1]; i++) {
+            const uint32_t u = lay.progs.members[i];
+            if (req[u].start >= kMaxLen || n[u] >= kMaxLen || req[u].pad_after >= kMaxLen ||
+                req[u].start + n[u] + req[u].pad_after >= kMaxLen)
+                return refuse(u, "length");
+            lay.start[u] = req[u].start;
+            lay.gain[u] = mix_gain(req[u].gain_db);
+            w.n = std::max(w.n, req[u].start + n[u] + req[u].pad_after);
+            if (lay.gain[u] != 0.0 && n[u]) {
+                ev.push_back({req[u].start, i, true});
+                ev.push_back({req[u].start + n[u], i, false});
+            }
+        }
+        w.hz = hz ? hz[lay.progs.members[lay.progs.first[g]]] : 0;
+        if (lay.total >= kMaxLen || w.n + align >= kMaxLen - lay.total)
+            return refuse((uint32_t)g, "length");
+        lay.total = (w.off + w.n + align - 1) / align * align;
+        // the sweep: a segment ends at every event; between two the cover stands
+        std::stable_sort(ev.begin(), ev.end(), [](const Event &a, const Event &b) { return a.k < b.k; });
+        cover.clear();
+        uint64_t k = 0;
+        auto emit = [&](uint64_t to) {
+            if (to <= k)
+                return true;
+            if (lay.lists.size() + cover.size() > kMixMaxList)
+                return false;
+            lay.segs.push_back({k, to, (uint32_t)lay.lists.size(), (uint32_t)cover.size()});
+            lay.lists.insert(lay.lists.end(), cover.begin(), cover.end());
+            lay.depth[g] = std::max<uint32_t>(lay.depth[g], (uint32_t)cover.size());
+            if (cover.size() >= 2)
+                lay.overlap[g] += to - k;
+            k = to;
+            return true;
+        };
+        for (const Event &e : ev) {
+            if (!emit(e.k))
+                return refuse((uint32_t)g, "work lists");
+            const auto it = std::lower_bound(cover.begin(), cover.end(), e.at);
+            if (e.add)
+                cover.insert(it, e.at);
+            else
+                cover.erase(it);
+        }
+        if (!emit(w.n)) // (the pads behind the last member's end: silence)
+            return refuse((uint32_t)g, "work lists");
+        lay.seg_first[g + 1] = (uint32_t)lay.segs.size();
     }
     *out = std::move(lay);
     return true;

@@ -3,8 +3,9 @@
 // loudness (measurement, groups, report, apply pass), join, then the encoders side by side: FLAC, sample format, IMA
 // ADPCM, filterbank features, cepstral features, mel spectrograms.  plan_output (jb_output.cpp) decides from the batch's shape and the requests alone which slab each stage
 // reads and writes, in f64 or in 16 bits, which slab the read entries hand out, each utterance's output geometry and
-// its place in the encoders' byte slabs, and with a join request (jb_join.h) the programmes: their numbering, each
-// one's place in the join slab, each member's start, and the encoders' geometry by programme instead of by utterance.
+// its place in the encoders' byte slabs, and with a join request (jb_join.h) or a mix request (jb_mix.h) the programmes:
+// their numbering, each one's place in the join slab, each member's start, and the encoders' geometry by programme
+// instead of by utterance.
 // The loudness groups' bookkeeping is here too, and what a redo round runs again: the three masks the stages follow
 // (redo_scope) and the renumbering of the items a mask picks (pick_renumbered).
 // Plain C++17 without HIP: all of it is made and tested on any host; OutputChain (jb_host.h) carries it out.
@@ -16,6 +17,7 @@
 #include "jb_mfcc.h"
 #include "jb_melspec.h"
 #include "jb_join.h"
+#include "jb_mix.h"
 
 namespace jb {
 
@@ -65,6 +67,7 @@ struct OutPlanIn {
     bool adpcm = false;                   // IMA ADPCM is requested
     uint32_t adpcm_align = 0;             // its block_align: 0 = by each utterance's output rate (jb_adpcm.h)
     const JoinUtt *join = nullptr;        // [B] the join request (jb_join.h); nullptr: none
+    const MixUtt *mix = nullptr;          // [B] the mix request (jb_mix.h) in the join's place; nullptr: none (never both)
     const uint8_t *filter = nullptr;      // [B] 1 = the utterance's filter has at least one section; nullptr: no request
     const FbankOpts *fbank = nullptr;     // the filterbank request (jb_fbank.h), checked at every output rate; nullptr: none
     const FbankOpts *mfcc_fbank = nullptr; // the cepstral request (jb_mfcc.h): its filterbank's geometry (the stage forces
@@ -146,7 +149,10 @@ struct OutPlan {
     // With a join request: the stage reads what `final` names and writes the programmes to a slab of its own; flac,
     // fmt_src, adpcm_src, fbank_src, mfcc_src and melspec_src then name that slab, and fmt, adpcm, fbank, mfcc and melspec have [P] entries laid
     // out from `units`
-    OutWrite join_src, join;          // None: no join
+    OutWrite join_src, join;          // None: neither a join nor a mix
+    bool mixed = false;               // the programmes are a mix request's: sums of their members (jb_mix.h)
+    std::vector<uint32_t> mix_depth;  // [P] with a mix: the largest number of unmuted members over one sample
+    std::vector<uint64_t> mix_overlap; // [P] with a mix: the samples under two or more unmuted members
     std::vector<OutUnit> units;       // [P] the programmes
     std::vector<uint32_t> prog_of;    // [B] each utterance's programme
     std::vector<uint64_t> prog_start; // [B] its first sample within it
@@ -206,6 +212,29 @@ struct JoinLayout {
 // for an id of B or above, or "output rate" where its members disagree
 bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, JoinLayout *out,
                  uint32_t *bad, const char **field);
+
+// The mix request laid out (jb_mix.h): programmes numbered as the join numbers them; a member starts where its request
+// says, a programme's length is the largest start + n + pad_after of its members, and each programme starts on a
+// 16-byte boundary of a slab of `elem`-byte samples.  The work lists follow from the geometry alone: each programme cut
+// at every start and end of an unmuted member (gain[u] != 0) of at least one sample into segments under a constant
+// set of members, each segment's set listed once in ascending utterance index
+struct MixLayout {
+    LnGroups progs;              // as JoinLayout's
+    std::vector<OutUnit> units;  // [P]
+    std::vector<uint64_t> start; // [B] each member's first sample within its programme
+    uint64_t total = 0;          // samples of the slab
+    std::vector<double> gain;    // [B] mix_gain of each request
+    std::vector<uint32_t> seg_first; // [P + 1] programme p owns segs[seg_first[p] .. seg_first[p + 1])
+    std::vector<MixSeg> segs;        // (a programme of no samples: none)
+    std::vector<uint32_t> lists;     // the segments' members: places in progs.members
+    std::vector<uint32_t> depth;     // [P] the longest list of the programme
+    std::vector<uint64_t> overlap;   // [P] its samples in segments of two or more
+};
+// Pure.  n, hz: as join_layout's.  false: the request is refused; *bad is the caller's id of the offending programme
+// (for "length" and "work lists": the utterance or the dense programme) and *field says "programme id", "output
+// rate", "length" where start + n + pad_after passes 2^63, or "work lists" where the lists pass kMixMaxList entries
+bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, MixLayout *out,
+                uint32_t *bad, const char **field);
 
 // The redo closure behind the join.  post: [B] 1 = an utterance whose final PCM changed (behind
 // loudness_groups_closure); programmes: [P] 1 = a programme with such a member

@@ -2,7 +2,7 @@
 // request and plan again (plan_output, jb_output.h); prepare() carries the plan out once; enqueue() selects what each
 // stage takes (everything, or a redo's part: redo_scope, jb_output.h) and launches, in this order and on the
 // vocoder's stream: the converter (k_resample), the filter, loudness (measurement, groups, report, apply pass; with a
-// limiter request the limiter in the apply pass's place), the join, then the encoders of the final PCM: FLAC (blocks, MD5, pack), the sample format, IMA ADPCM and
+// limiter request the limiter in the apply pass's place), the join (or the mix in its place), then the encoders of the final PCM: FLAC (blocks, MD5, pack), the sample format, IMA ADPCM and
 // the filterbank features.
 #include "jb_host.h"
 
@@ -40,6 +40,7 @@ void OutputChain::replan()
     in.adpcm = ad_on;
     in.adpcm_align = ad_align;
     in.join = join_req.empty() ? nullptr : join_req.data();
+    in.mix = mix_req.empty() ? nullptr : mix_req.data();
     flag_stage();
     in.filter = stage_any.empty() ? nullptr : stage_any.data();
     in.fbank = fb_on ? &fb_p : nullptr;
@@ -112,6 +113,7 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
     }
     if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)) ||
         (rc = check_join(join_req, want, "jb_batch_set_output_rate")) ||
+        (rc = check_mix(mix_req, mix_opts, want, "jb_batch_set_output_rate")) ||
         (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")) ||
         (rc = check_fir(want, "jb_batch_set_output_rate")) ||
         (rc = check_noise(want, "jb_batch_set_output_rate")) ||
@@ -448,10 +450,64 @@ int OutputChain::set_join(const jb_join_utt *req, size_t n)
         set_error("jb_batch_set_join: give one request per utterance");
         return JB_ERR_INVALID;
     }
+    if (!mix_req.empty()) {
+        set_error("jb_batch_set_join: the batch holds a mix request (a batch holds a join or a mix request; withdraw "
+                  "the one first)");
+        return JB_ERR_INVALID;
+    }
     std::vector<JoinUtt> r((const JoinUtt *)req, (const JoinUtt *)req + n);
     if ((rc = check_join(r, want_hz, "jb_batch_set_join")))
         return rc;
     join_req = std::move(r);
+    replan();
+    return JB_OK;
+}
+
+// The mix request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming what is wrong
+int OutputChain::check_mix(const std::vector<MixUtt> &req, const MixOpts &opts, const std::vector<uint32_t> &want,
+                           const char *who) const
+{
+    if (req.empty())
+        return JB_OK;
+    const std::vector<uint32_t> hz = rates_under(want);
+    // (the lengths at these rates, as plan_output forms them: they decide who lies over whom, so the lists' size)
+    std::vector<uint64_t> n(hz.size(), 0);
+    for (size_t u = 0; u < n.size(); u++) {
+        uint64_t L = 1, M = 1;
+        if (hz[u] != b.voice.sampling_frequency)
+            resample_ratio(b.voice.sampling_frequency, hz[u], &L, &M);
+        n[u] = resample_out_len((uint64_t)b.T[u] * b.voice.fperiod, L, M);
+    }
+    MixLayout lay;
+    return mix_layout_checked(req.data(), n.data(), hz.data(), hz.size(), sizeof(double), &opts, &lay, who);
+}
+
+int OutputChain::set_mix(const jb_mix_utt *req, size_t n, const jb_mix_opts *opts)
+{
+    int rc = check_settable("jb_batch_set_mix: the mix is set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!req && n == 0) {
+        mix_req.clear();
+        mix_opts = MixOpts{};
+        replan();
+        return JB_OK;
+    }
+    if (!req || n != (size_t)b.B) {
+        set_error("jb_batch_set_mix: give one request per utterance");
+        return JB_ERR_INVALID;
+    }
+    if (!join_req.empty()) {
+        set_error("jb_batch_set_mix: the batch holds a join request (a batch holds a join or a mix request; withdraw "
+                  "the one first)");
+        return JB_ERR_INVALID;
+    }
+    std::vector<MixUtt> r((const MixUtt *)req, (const MixUtt *)req + n);
+    const MixOpts o = opts ? *(const MixOpts *)opts : MixOpts{};
+    if ((rc = check_mix(r, o, want_hz, "jb_batch_set_mix")))
+        return rc;
+    mix_req = std::move(r);
+    mix_opts = o;
     replan();
     return JB_OK;
 }
@@ -778,7 +834,7 @@ int OutputChain::prepare()
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
     if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_noise()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
-        (rc = prepare_join()) ||
+        (rc = prepare_join()) || (rc = prepare_mix()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
         (rc = prepare_fbank()) || (rc = prepare_mfcc()) || (rc = prepare_melspec()))
         return rc;
@@ -804,15 +860,15 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const RedoScope *scope = redo ? &of_redo : nullptr;
     int rc;
     if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_noise(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
-        (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
+        (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_mix(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
         (rc = select_adpcm(scope)) || (rc = select_fbank(scope)) || (rc = select_mfcc(scope)) ||
         (rc = select_melspec(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || mx.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_noise(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
-        (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
+        (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_mix(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
         (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)) || (rc = launch_mfcc(redo)) ||
         (rc = launch_melspec(redo)))
         return rc;
@@ -1365,7 +1421,7 @@ JoinSpan OutputChain::join_span(size_t p, uint64_t k0, uint64_t k1, uint64_t *ti
 // The members in programme order and one span per programme: the final PCM of the plan in, the join slab out
 int OutputChain::prepare_join()
 {
-    if (!joined())
+    if (!joined() || mixed())
         return JB_OK;
     const size_t B = (size_t)b.B, P = plan.units.size();
     const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
@@ -1393,7 +1449,7 @@ int OutputChain::prepare_join()
 
 int OutputChain::select_join(const RedoScope *scope)
 {
-    if (!joined() || !scope)
+    if (!joined() || mixed() || !scope)
         return jn.spans.take_all(jn.tiles);
     const std::vector<uint8_t> &mask = scope->post; // every utterance whose final PCM changed
     const uint64_t gs = kJoinGroupBytes / (plan.join.i16 ? sizeof(int16_t) : sizeof(double));
@@ -1414,11 +1470,73 @@ int OutputChain::select_join(const RedoScope *scope)
 
 int OutputChain::launch_join(bool redo)
 {
-    if (!joined() || (redo && !jn.spans.n))
+    if (!joined() || mixed() || (redo && !jn.spans.n))
         return JB_OK;
     const hipError_t e =
         jb::launch_join(plan.join.i16, jn.spans.list, jn.spans.n, jn.spans.total, jn.members_dev, b.stream_voc);
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_join(redo)" : "k_join");
+}
+
+// ---- the mix, in the join's place: the members, the segments and their lists from the layout (mix_layout, as the
+// plan formed it), one span per programme, the peak scratch and the results
+int OutputChain::prepare_mix()
+{
+    if (!mixed())
+        return JB_OK;
+    const size_t B = (size_t)b.B, P = plan.units.size();
+    const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
+    std::vector<uint64_t> n(B), xoff(B);
+    for (size_t u = 0; u < B; u++) {
+        n[u] = plan.utt[u].n;
+        xoff[u] = plan.utt[u].off;
+    }
+    MixLayout lay;
+    int rc = mix_layout_checked(mix_req.data(), n.data(), nullptr, B, elem, &mix_opts, &lay, "jb_batch_set_mix");
+    if (rc)
+        return rc;
+    std::vector<MixMember> members;
+    mix_lists(lay, mix_req.data(), n.data(), xoff.data(), slab[(size_t)plan.join_src.slab], slab[(size_t)plan.join.slab],
+              elem, &members, &mx.spans.host, &mx.tiles);
+    MixMember *md = nullptr;
+    MixSeg *sd = nullptr;
+    uint32_t *ld = nullptr;
+    if ((rc = b.dalloc(&md, B, false)) || (rc = b.dalloc(&sd, lay.segs.size(), false)) ||
+        (rc = b.dalloc(&ld, lay.lists.size(), false)) || (rc = b.dalloc(&mx.L.tile_peak, mx.tiles * kMixWaves, false)) ||
+        (rc = b.dalloc(&mx.L.res, P, false)) || (rc = mx.spans.alloc(b, P, P)) ||
+        (rc = upload_list(md, members, "mix work list")) || (rc = upload_list(sd, lay.segs, "mix work list")) ||
+        (rc = upload_list(ld, lay.lists, "mix work list")))
+        return rc;
+    mx.L.members = md;
+    mx.L.segs = sd;
+    mx.L.lists = ld;
+    mx.L.fit = (mix_opts.flags & kMixFit) != 0;
+    mx.L.ceiling = mx.L.fit ? mix_ceiling(mix_opts.ceiling_db) : 0.0;
+    return mx.spans.upload("mix work list");
+}
+
+// A redo runs every programme with a member whose final PCM changed again, whole: the sum, the peak and the fit
+int OutputChain::select_mix(const RedoScope *scope)
+{
+    if (!mixed() || !scope)
+        return mx.spans.take_all(mx.tiles);
+    std::vector<MixSpan> sub;
+    uint64_t tiles = 0;
+    for (size_t p = 0; p < scope->units.size(); p++) {
+        if (!scope->units[p])
+            continue;
+        sub.push_back(mx.spans.host[p]);
+        sub.back().t0 = tiles; // (pk0 stays: the programme's tiles in the peak scratch)
+        tiles += join_tiles(0, plan.units[p].n, plan.join.i16);
+    }
+    return mx.spans.upload_redo(sub, kRedoLists, tiles);
+}
+
+int OutputChain::launch_mix(bool redo)
+{
+    if (!mixed() || (redo && !mx.spans.n))
+        return JB_OK;
+    const hipError_t e = jb::launch_mix(plan.join.i16, mx.spans.list, mx.spans.n, mx.spans.total, mx.L, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_mix(redo)" : "k_mix");
 }
 
 // ---- FLAC.  The streams' lists and slabs: one stream per unit (an utterance; behind a join a programme) of the
@@ -1826,6 +1944,23 @@ int OutputChain::read_noise(size_t u, jb_noise_report *out)
     if ((rc = b.read(noi.rec + u, &r, sizeof r)))
         return rc;
     *out = noise_report_of(noise_req[u], r, plan.utt[u].n);
+    return JB_OK;
+}
+
+int OutputChain::read_mix(size_t p, jb_mix_report *out)
+{
+    int rc = check_ready(mixed(), "jb_batch_mix_report: the batch has not run",
+                         "jb_batch_mix_report: jb_batch_set_mix was not called");
+    if (rc)
+        return rc;
+    if (p >= plan.units.size()) {
+        set_error("jb_batch_mix_report: no such programme");
+        return JB_ERR_INVALID;
+    }
+    MixResult r{};
+    if ((rc = b.read(mx.L.res + p, &r, sizeof r)))
+        return rc;
+    *out = jb_mix_report{r.peak, r.scale, plan.mix_depth[p], 0, plan.mix_overlap[p]};
     return JB_OK;
 }
 

@@ -351,6 +351,30 @@ class Engine:
         """jb_engine_set_noise (the Condition's setter, on the engine): an _ffi.Noise, or None for none."""
         self.condition.set_noise(r)
 
+    def set_programme_mix(self, place, fit: bool = False, ceiling_db: float = 0.0):
+        """jb_engine_set_programme_mix: place = [(start_ms, gain_db), ...], one per utterance of the
+        synthesize_programme calls to come, which then MIX their utterances (utterance u starts lead_ms + start_ms[u]
+        into the programme, under gain_db[u]) instead of joining them; fit: a programme over ceiling_db (dBFS) is
+        scaled down to it.  None withdraws the setting."""
+        if place is None:
+            F.check(self._L.jb_engine_set_programme_mix(self._h, None, 0, None))
+            return
+        arr = (F.MixPlace * max(1, len(place)))()
+        for u, (start_ms, gain_db) in enumerate(place):
+            arr[u].start_ms, arr[u].gain_db = float(start_ms), float(gain_db)
+        o = F.mix_opts(fit, ceiling_db)
+        F.check(self._L.jb_engine_set_programme_mix(self._h, arr, len(place), C.byref(o)))
+
+    def get_programme_mix(self):
+        """(place, fit, ceiling_db) as set_programme_mix took them; place None without a setting."""
+        n, o = C.c_size_t(), F.MixOpts()
+        F.check(self._L.jb_engine_get_programme_mix(self._h, None, 0, C.byref(n), C.byref(o)))
+        if not n.value:
+            return None, False, 0.0
+        arr = (F.MixPlace * n.value)()
+        F.check(self._L.jb_engine_get_programme_mix(self._h, arr, n.value, None, None))
+        return [(a.start_ms, a.gain_db) for a in arr], bool(o.flags & F.MIX_FIT), o.ceiling_db
+
     def get_filter(self):
         return self.condition.get_filter()
 
@@ -624,7 +648,7 @@ class Engine:
 
     def synthesize_programme(self, utterances: Sequence[Sequence[str]], sink: str = "f64", lead_ms: float = 0.0,
                              gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0, device: int = -1,
-                             **sink_opts):
+                             mix=None, fit: bool = False, ceiling_db: float = 0.0, **sink_opts):
         """jb_synthesize_programme*: the utterances as ONE programme -- lead_ms of zeros, the first utterance, gap_ms,
         the next, ..., trail_ms, a fade of fade_ms at both edges of each -- joined on the GPU in front of the sink.
         sink: "f64" or "i16" (PCM arrays), "flac" (bytes; block_size, max_lpc_order, md5, seek_interval_ms),
@@ -632,7 +656,17 @@ class Engine:
         [T, n_mels]; opts=F.FbankOpts or the keywords of J.fbank), "mfcc" (an ndarray [T, width]; opts=F.MfccOpts or
         the keywords of J.mfcc, fbank=F.FbankOpts or a dict of J.fbank's keywords) or "melspec" (an ndarray
         [T, n_mels]; opts=F.MelspecOpts or the keywords of J.melspec).  Returns (output, starts):
-        starts[u] is utterance u's first sample within the programme."""
+        starts[u] is utterance u's first sample within the programme.
+        mix=[(start_ms, gain_db), ...] (a convenience: set_programme_mix for this call alone, the engine's setting put
+        back behind it) sums the utterances instead, each at its start and under its gain; fit and ceiling_db as there."""
+        if mix is not None:
+            was = self.get_programme_mix()
+            self.set_programme_mix(mix, fit, ceiling_db)
+            try:
+                return self.synthesize_programme(utterances, sink, lead_ms, gap_ms, trail_ms, fade_ms, device,
+                                                 **sink_opts)
+            finally:
+                self.set_programme_mix(*was)
         lines, offs, B = _utt_lines(utterances)
         join = F.join_opts(lead_ms, gap_ms, trail_ms, fade_ms)
         starts = (C.c_uint64 * max(1, B))()
