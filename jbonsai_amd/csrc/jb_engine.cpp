@@ -1255,7 +1255,7 @@ int jb_engine_set_programme_mix(jb_engine *e, const jb_mix_place *place, size_t 
         req[u].gain_db = place[u].gain_db;
     }
     jb::MixLayout lay;
-    int rc = jb::mix_layout_checked((const jb::MixUtt *)req.data(), len.data(), nullptr, n, sizeof(double),
+    int rc = jb::mix_layout_checked((const jb::MixUtt *)req.data(), false, len.data(), nullptr, n, sizeof(double),
                                     (const jb::MixOpts *)opts, &lay, "jb_engine_set_programme_mix");
     if (rc)
         return rc;
@@ -1923,42 +1923,34 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
 int SynthRun::request_programme(jb::OutputChain &out, size_t lo, size_t hi)
 {
     const jb_join_opts *join = rq.join;
-    // with jb_engine_set_programme_mix the programme is a mix: member u starts at lead + start_ms[u] under its gain,
-    // the trail is every member's pad behind it, the fade every member's fades (the entry has checked count and gap)
+    // One programme, every member under the fade at both its edges, in samples at the output rate.  A join: the lead in
+    // front of the first member, the gap behind every member but the last, the trail behind the last.  With
+    // jb_engine_set_programme_mix a mix: member u starts at lead + start_ms[u] under its gain, and the trail is every
+    // member's pad behind it (the entry has checked count and gap)
     const Condition &c0 = eng(lo)->cond;
-    if (!c0.mix_place.empty()) {
-        const uint32_t mhz = out.utt(0).hz;
-        std::vector<jb_mix_utt> mreq(hi - lo, jb_mix_utt{});
-        for (size_t u = 0; u < mreq.size(); u++) {
-            mreq[u].programme = 0;
-            mreq[u].fade_in = mreq[u].fade_out =
-                (uint32_t)std::min<uint64_t>(jb::join_ms_to_samples(join->fade_ms, mhz), 0xffffffffu);
-            mreq[u].start = jb::join_ms_to_samples(join->lead_ms + c0.mix_place[u].start_ms, mhz);
-            mreq[u].pad_after = jb::join_ms_to_samples(join->trail_ms, mhz);
-            mreq[u].gain_db = c0.mix_place[u].gain_db;
-        }
-        const int mrc = out.set_mix(mreq.data(), mreq.size(), &c0.mix_opts);
-        if (mrc)
-            return mrc;
-        for (size_t u = 0; rq.join_starts && u < mreq.size(); u++)
-            rq.join_starts[lo + u] = out.member_start(u);
-        return JB_OK;
-    }
-    // one programme: the lead in front of the first member, the gap behind every member but the last, the
-    // trail behind the last, the fade at both edges of each, in samples at the output rate
+    const bool mix = !c0.mix_place.empty();
     const uint32_t hz = out.utt(0).hz;
-    std::vector<jb_join_utt> req(hi - lo, jb_join_utt{});
-    for (size_t u = 0; u < req.size(); u++) {
-        req[u].programme = 0;
-        req[u].fade_in = req[u].fade_out = (uint32_t)std::min<uint64_t>(jb::join_ms_to_samples(join->fade_ms, hz),
-                                                                       0xffffffffu);
-        req[u].pad_before = u == 0 ? jb::join_ms_to_samples(join->lead_ms, hz) : 0;
-        req[u].pad_after = jb::join_ms_to_samples(u + 1 == req.size() ? join->trail_ms : join->gap_ms, hz);
+    const size_t n = hi - lo;
+    const uint32_t fade = (uint32_t)std::min<uint64_t>(jb::join_ms_to_samples(join->fade_ms, hz), 0xffffffffu);
+    // one request, in the words of its kind: the two differ in where a member's place and its gain come from
+    std::vector<jb_join_utt> jreq(mix ? 0 : n, jb_join_utt{});
+    std::vector<jb_mix_utt> mreq(mix ? n : 0, jb_mix_utt{});
+    for (size_t u = 0; u < n; u++) {
+        if (mix) {
+            mreq[u].fade_in = mreq[u].fade_out = fade;
+            mreq[u].start = jb::join_ms_to_samples(join->lead_ms + c0.mix_place[u].start_ms, hz);
+            mreq[u].pad_after = jb::join_ms_to_samples(join->trail_ms, hz);
+            mreq[u].gain_db = c0.mix_place[u].gain_db;
+        } else {
+            jreq[u].fade_in = jreq[u].fade_out = fade;
+            jreq[u].pad_before = u == 0 ? jb::join_ms_to_samples(join->lead_ms, hz) : 0;
+            jreq[u].pad_after = jb::join_ms_to_samples(u + 1 == n ? join->trail_ms : join->gap_ms, hz);
+        }
     }
-    const int rc = out.set_join(req.data(), req.size());
+    const int rc = mix ? out.set_mix(mreq.data(), n, &c0.mix_opts) : out.set_join(jreq.data(), n);
     if (rc)
         return rc;
-    for (size_t u = 0; rq.join_starts && u < req.size(); u++)
+    for (size_t u = 0; rq.join_starts && u < n; u++)
         rq.join_starts[lo + u] = out.member_start(u);
     return JB_OK;
 }

@@ -412,30 +412,28 @@ inline hipError_t rate_launch(const MelOpts &o, const RateNoCond &, const MelCla
 hipError_t launch_mfcc(const MfccParams &P, const MfccUtt *utts_dev, uint32_t n, uint64_t tiles, uint64_t blocks,
                        hipStream_t stream);
 
-// The join stage (jb_join.hip; the rules, JoinMember and JoinSpan: jb_join.h; the layout: jb_output.h)
-// join_layout with the request's reserved words checked and set_error naming what is wrong (JB_ERR_INVALID)
-int join_layout_checked(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
-                        JoinLayout *out, const char *who);
-// The lists of a run: members[i] for the layout's members[i] (utterance u's samples at x + xoff[u] elements), one
-// span per programme (programme p at y + units[p].off elements)
-void join_lists(const JoinLayout &lay, const JoinUtt *req, const uint64_t *n, const uint64_t *xoff, const void *x,
-                void *y, size_t elem, std::vector<JoinMember> *members, std::vector<JoinSpan> *spans);
-// spans_dev[0..n) of `tiles` tiles in all, their samples f64 or 16-bit by i16
-hipError_t launch_join(bool i16, const JoinSpan *spans_dev, uint32_t n, uint64_t tiles, const JoinMember *members_dev,
-                       hipStream_t stream);
-
-// The mix stage (jb_mix.hip; the rules and the work lists' entries: jb_mix.h; the layout: jb_output.h; the host half:
-// jb_mix.cpp).  mix_layout with the request's and the options' fields checked and set_error naming what is wrong
-// (JB_ERR_INVALID; lists past kMixMaxList entries: JB_ERR_UNSUPPORTED).  opts may be null
-int mix_layout_checked(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
+// The programme stage: the join (jb_join.hip; the rules, ProgMember and ProgSpan: jb_join.h) and the mix (jb_mix.hip;
+// the rules and MixSeg: jb_mix.h; the host half: jb_mix.cpp) over one layout (jb_output.h mix_layout).
+// mix_layout with the request's and the options' fields checked and set_error naming what is wrong (JB_ERR_INVALID;
+// lists past kMixMaxList entries: JB_ERR_UNSUPPORTED).  opts may be null.  `chained`: req is a join's (join_as_mix),
+// and the refusals are worded for the join
+int mix_layout_checked(const MixUtt *req, bool chained, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
                        const MixOpts *opts, MixLayout *out, const char *who);
+// The same from the join's own request
+int join_layout_checked(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
+                        MixLayout *out, const char *who);
 // The lists of a run: members[i] for the layout's members[i] (utterance u's samples at x + xoff[u] elements) and one
-// span per programme (programme p at y + units[p].off elements); *tiles their tiles, the peak scratch's slots / kMixWaves
+// span per programme, whole (programme p at y + units[p].off elements); *tiles their tiles, the peak scratch's slots /
+// kMixWaves
 void mix_lists(const MixLayout &lay, const MixUtt *req, const uint64_t *n, const uint64_t *xoff, const void *x, void *y,
-               size_t elem, std::vector<MixMember> *members, std::vector<MixSpan> *spans, uint64_t *tiles);
+               size_t elem, std::vector<ProgMember> *members, std::vector<ProgSpan> *spans, uint64_t *tiles);
+// The join's launch over the same members and spans (k_join reads neither the segments nor the gains): spans_dev[0..n)
+// of `tiles` tiles in all, their samples f64 or 16-bit by i16
+hipError_t launch_join(bool i16, const ProgSpan *spans_dev, uint32_t n, uint64_t tiles, const ProgMember *members_dev,
+                       hipStream_t stream);
 // What a launch reads on the device beside its spans
 struct MixLaunch {
-    const MixMember *members;
+    const ProgMember *members;
     const MixSeg *segs;
     const uint32_t *lists;
     double *tile_peak; // kMixWaves per tile, by the spans' pk0
@@ -444,7 +442,7 @@ struct MixLaunch {
     double ceiling;    // in sample units, with fit
 };
 // spans_dev[0..n) of `tiles` tiles in all: k_mix, k_mix_peak and with fit k_mix again over the programmes of s != 1
-hipError_t launch_mix(bool i16, const MixSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L,
+hipError_t launch_mix(bool i16, const ProgSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L,
                       hipStream_t stream);
 
 // The filter stage (jb_filter.hip; the rules, FilterClass and FilterUtt: jb_filter.h; the host half: jb_filter.cpp)
@@ -963,9 +961,9 @@ private:
     FrameOpts fr_p{};
     bool ml_on = false;                        // mel spectrograms are requested
     MelOpts ml_p{};
-    std::vector<JoinUtt> join_req;             // [B] the join request; empty: none
-    std::vector<MixUtt> mix_req;               // [B] the mix request; empty: none (never beside join_req)
-    MixOpts mix_opts{};                        // its options
+    std::vector<MixUtt> prog_req;              // [B] the programme request, a join's (join_as_mix) or a mix's; empty: none
+    bool prog_chained = false;                 // it is a join's: its starts count from the member in front
+    MixOpts mix_opts{};                        // a mix's options
     std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
     FirClasses fir_cls;                        // the distinct responses of the convolution request (its copies)
@@ -1048,18 +1046,14 @@ private:
         LimiterResult *res = nullptr;   // [B]
         uint64_t tiles = 0;
     } lim;
-    struct Join { // follows `post`
-        std::vector<JoinMember> members; // in programme order: programme p owns [prog_first[p], prog_first[p + 1])
+    struct Programme { // the join or the mix.  A join follows `post`: each changed member's own range runs again;
+                       // a mix follows `units`: a touched programme runs again whole
+        std::vector<ProgMember> members; // in programme order: programme p owns [prog_first[p], prog_first[p + 1])
         std::vector<uint32_t> member_at; // [B] utterance -> its place in `members`
-        DevList<JoinSpan> spans;         // [P] every programme whole (a redo: one span per member)
-        JoinMember *members_dev = nullptr;
+        DevList<ProgSpan> spans;         // [P] every programme whole (a join's redo: one span per member)
+        MixLaunch L{};                   // the members; with a mix the segments and their lists, the peak scratch, the results
         uint64_t tiles = 0;
-    } jn;
-    struct Mix { // in the join's place; follows `units`: a touched programme runs again whole
-        DevList<MixSpan> spans; // [P] every programme
-        MixLaunch L{};          // the members, the segments and their lists, the peak scratch, the results
-        uint64_t tiles = 0;
-    } mx;
+    } pg;
     struct Flac { // follows `units`, by work item; the pack takes every stream
         DevList<FlacWork> work;
         DevList<uint32_t> md5;     // with an MD5 request: the units in launch order
@@ -1143,9 +1137,11 @@ private:
     int check_groups(const std::vector<uint32_t> &group, const std::vector<double> &target,
                      const std::vector<double> &ceiling, const std::vector<uint32_t> &mode,
                      const std::vector<uint32_t> &want, const char *who, LnGroups *out) const;
-    int check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const;
-    int check_mix(const std::vector<MixUtt> &req, const MixOpts &opts, const std::vector<uint32_t> &want,
-                  const char *who) const;
+    int check_programme(const std::vector<MixUtt> &req, bool chained, const MixOpts &opts,
+                        const std::vector<uint32_t> &want, const char *who) const;
+    // the one slot of set_join and set_mix: the checks in front of the request, and the request stored
+    int open_programme(bool chained, bool given, size_t n, bool *store);
+    int store_programme(bool chained, std::vector<MixUtt> req, const MixOpts &opts);
     int check_filter(const std::vector<jb_filter> &req, const std::vector<uint32_t> &want, const char *who) const;
     int check_fir(const std::vector<uint32_t> &want, const char *who) const; // the responses' rates under `want`
     int install_fir(const jb_fir *f, size_t n, const char *who);             // set_fir's and set_room's common half
@@ -1159,9 +1155,7 @@ private:
     int prepare_noise(), select_noise(const RedoScope *scope), launch_noise(bool redo);
     int prepare_loudness(), select_loudness(const RedoScope *scope), launch_loudness(bool redo);
     int prepare_limiter(), select_limiter(const RedoScope *scope), launch_limiter(bool redo);
-    int prepare_join(), select_join(const RedoScope *scope), launch_join(bool redo);
-    JoinSpan join_span(size_t p, uint64_t k0, uint64_t k1, uint64_t *tiles) const;
-    int prepare_mix(), select_mix(const RedoScope *scope), launch_mix(bool redo);
+    int prepare_programme(), select_programme(const RedoScope *scope), launch_programme(bool redo);
     int prepare_flac(), select_flac(const RedoScope *scope), launch_flac(bool redo);
     int prepare_format(), select_format(const RedoScope *scope), launch_format(bool redo);
     int prepare_adpcm(), select_adpcm(const RedoScope *scope), launch_adpcm(bool redo);

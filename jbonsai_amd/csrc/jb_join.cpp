@@ -1,4 +1,4 @@
-// jb_join.cpp -- the host half of the join stage: the request check, the geometry, the work lists of a launch and
+// jb_join.cpp -- the host half of the join stage: the request check and the geometry (both the one layout's) and
 // the rules of jb_join.h over PCM the caller holds without a GPU (jb_join_host, what the kernel is checked against).
 #include "jb_host.h"
 
@@ -16,43 +16,9 @@ static_assert(sizeof(JoinUtt) == sizeof(jb_join_utt) && offsetof(JoinUtt, progra
               "jb_join.h restates the header's request");
 
 int join_layout_checked(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
-                        JoinLayout *out, const char *who)
+                        MixLayout *out, const char *who)
 {
-    for (size_t u = 0; u < B; u++)
-        if (req[u].reserved) {
-            set_error(std::string(who) + ": reserved must be 0 (utterance " + std::to_string(u) + ")");
-            return JB_ERR_INVALID;
-        }
-    uint32_t bad = 0;
-    const char *field = "";
-    if (!join_layout(req, n, hz, B, elem, out, &bad, &field)) {
-        if (std::string(field) == "programme id")
-            set_error(std::string(who) + ": programme id " + std::to_string(bad) +
-                      " (an id is below the batch size, or JB_JOIN_NONE)");
-        else
-            set_error(std::string(who) + ": the members of programme " + std::to_string(bad) +
-                      " would disagree on the " + field);
-        return JB_ERR_INVALID;
-    }
-    return JB_OK;
-}
-
-void join_lists(const JoinLayout &lay, const JoinUtt *req, const uint64_t *n, const uint64_t *xoff, const void *x,
-                void *y, size_t elem, std::vector<JoinMember> *members, std::vector<JoinSpan> *spans)
-{
-    const size_t B = lay.start.size(), P = lay.units.size();
-    members->assign(B, JoinMember{});
-    spans->assign(P, JoinSpan{});
-    uint64_t tiles = 0;
-    for (size_t p = 0; p < P; p++) {
-        const uint32_t m0 = lay.progs.first[p], m1 = lay.progs.first[p + 1];
-        for (uint32_t i = m0; i < m1; i++) {
-            const uint32_t u = lay.progs.members[i];
-            (*members)[i] = {(const char *)x + xoff[u] * elem, lay.start[u], n[u], req[u].fade_in, req[u].fade_out};
-        }
-        (*spans)[p] = {(char *)y + lay.units[p].off * elem, lay.units[p].n, 0, lay.units[p].n, tiles, m0, m1 - m0};
-        tiles += join_tiles(0, lay.units[p].n, elem == 2);
-    }
+    return mix_layout_checked(join_as_mix(req, B).data(), true, n, hz, B, elem, nullptr, out, who);
 }
 
 namespace {
@@ -67,7 +33,7 @@ int join_host(const T *const *in, const size_t *n_in, size_t n, const jb_join_ut
         if (n_in[u] && !in[u])
             return JB_ERR_INVALID;
     std::vector<uint64_t> ns(n_in, n_in + n);
-    JoinLayout lay;
+    MixLayout lay;
     int rc = join_layout_checked((const JoinUtt *)req, ns.data(), nullptr, n, sizeof(T), &lay, who);
     if (rc)
         return rc;
@@ -111,7 +77,7 @@ int jb_join_geometry(const jb_join_utt *req, const size_t *n_in, const uint32_t 
     if (n && (!req || !n_in))
         return JB_ERR_INVALID;
     std::vector<uint64_t> ns(n_in, n_in + n);
-    JoinLayout lay;
+    MixLayout lay;
     int rc = join_layout_checked((const JoinUtt *)req, ns.data(), hz, n, sizeof(double), &lay, "jb_join_geometry");
     if (rc)
         return rc;

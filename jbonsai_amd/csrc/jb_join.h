@@ -2,7 +2,7 @@
 // jb_join.h -- the join stage (include/jbonsai_amd.h "Join"): a programme's PCM is its members one after the other, each
 // between its own pads of zero samples and under its own edge fades.  The rules of one sample and of the geometry,
 // stated once for the kernel (jb_join.hip), for the host seam (jb_join.cpp) and for the output plan (jb_output.cpp),
-// and the stage's work lists.
+// and the work lists' entries of the programme stage, which the mix (jb_mix.h) shares.
 // Plain C++17 and header-only; under hipcc the rules compile for the host and the device alike.
 #include <stddef.h>
 #include <stdint.h>
@@ -26,32 +26,39 @@ struct JoinUtt {
 static_assert(sizeof(JoinUtt) == 32 && offsetof(JoinUtt, pad_before) == 16, "jb_join_utt is 32 bytes");
 constexpr uint32_t kJoinNone = 0xffffffffu; // JB_JOIN_NONE: the utterance is a programme of its own
 
-constexpr uint32_t kJoinLanes = 256;
-constexpr uint32_t kJoinTileBytes = 16384; // destination bytes per workgroup: four 16-byte groups per lane
-constexpr uint32_t kJoinGroupBytes = 16;   // what one store writes; programmes start on such a boundary in their slab
+// The programme stage's launch shape, the join's and the mix's alike
+constexpr uint32_t kProgLanes = 256;
+constexpr uint32_t kProgTileBytes = 16384; // destination bytes per workgroup: four 16-byte groups per lane
+constexpr uint32_t kProgGroupBytes = 16;   // what one store writes; programmes start on such a boundary in their slab
 
-// One member of a join launch, in the order of its programme
-struct JoinMember {
+// One member of a programme launch, in the order of its programme (ascending utterance index; in a join that is
+// ascending by start)
+struct ProgMember {
     const void *x;  // its final PCM: f64 or 16-bit samples (by the launch)
-    uint64_t start; // its first sample within the programme (behind its pad_before)
+    uint64_t start; // its first sample within the programme (in a join: behind its pad_before)
     uint64_t n;
     uint32_t fade_in, fade_out;
+    double g; // mix_gain of its gain_db (a join: 1, and not read)
 };
 
-// One span of a join launch: samples [k0, k1) of one programme, k0 a multiple of a group's samples, k1 one too or the
-// programme's end.  A run lists every programme whole; a redo the spans of the members that changed.  t0 is the
-// prefix sum of the list's tiles (tiles never cross spans); the programme owns members[m0 .. m0 + nm), nm >= 1
-struct JoinSpan {
-    void *y;    // the programme's first sample in the join slab, 16-byte aligned
+// One span of a programme launch: samples [k0, k1) of one programme, k0 a multiple of a group's samples, k1 one too or
+// the programme's end.  A run lists every programme whole, and so does a mix's redo; a join's redo lists the spans of
+// the members that changed.  t0 is the prefix sum of the list's tiles (tiles never cross spans), pk0 the programme's
+// first tile in the mix's peak scratch (the full run's numbering: a redo keeps it); the programme owns
+// members[m0 .. m0 + nm), nm >= 1, and segs[s0 .. s0 + ns) (jb_mix.h)
+struct ProgSpan {
+    void *y;    // the programme's first sample in its slab, 16-byte aligned
     uint64_t n; // the programme's samples
-    uint64_t k0, k1, t0;
+    uint64_t k0, k1, t0, pk0;
     uint32_t m0, nm;
+    uint32_t s0, ns;
+    uint32_t prog, reserved;
 };
 
 // tiles of a span [k0, k1) of 16-bit or f64 samples
-constexpr uint64_t join_tiles(uint64_t k0, uint64_t k1, bool i16)
+constexpr uint64_t prog_tiles(uint64_t k0, uint64_t k1, bool i16)
 {
-    return k1 > k0 ? (k1 - k0 + kJoinTileBytes / (i16 ? 2 : 8) - 1) / (kJoinTileBytes / (i16 ? 2 : 8)) : 0;
+    return k1 > k0 ? (k1 - k0 + kProgTileBytes / (i16 ? 2 : 8) - 1) / (kProgTileBytes / (i16 ? 2 : 8)) : 0;
 }
 
 // floor(ms hz / 1000 + 0.5); 0 for a negative or NaN duration
@@ -98,7 +105,7 @@ JB_JOIN_HD int16_t join_sample(int16_t x, uint64_t k, uint64_t n, uint32_t fade_
 // The member that holds sample k of a programme, among members[0 .. nm) ascending by start: the last one with
 // start <= k searched in [lo, hi], or -1 where k lies in front of the first.  *inside: k is one of its samples (else
 // k lies in a pad)
-JB_JOIN_HD int32_t join_find(const JoinMember *members, int32_t lo, int32_t hi, uint64_t k, bool *inside)
+JB_JOIN_HD int32_t join_find(const ProgMember *members, int32_t lo, int32_t hi, uint64_t k, bool *inside)
 {
     if (members[lo].start > k) {
         *inside = false;
@@ -116,13 +123,13 @@ JB_JOIN_HD int32_t join_find(const JoinMember *members, int32_t lo, int32_t hi, 
 }
 
 // Sample k of a programme by the rules above: a member's sample, or the zero of a pad
-template <class T> JB_JOIN_HD T join_value(const JoinMember *members, int32_t lo, int32_t hi, uint64_t k)
+template <class T> JB_JOIN_HD T join_value(const ProgMember *members, int32_t lo, int32_t hi, uint64_t k)
 {
     bool inside;
     const int32_t j = join_find(members, lo, hi, k, &inside);
     if (!inside)
         return (T)0;
-    const JoinMember m = members[j];
+    const ProgMember m = members[j];
     return join_sample(((const T *)m.x)[k - m.start], k - m.start, m.n, m.fade_in, m.fade_out);
 }
 

@@ -24,7 +24,7 @@ static_assert(sizeof(MixReport) == sizeof(jb_mix_report) && offsetof(MixReport, 
                   offsetof(MixReport, overlap) == offsetof(jb_mix_report, overlap),
               "jb_mix.h restates the header's report");
 
-int mix_layout_checked(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
+int mix_layout_checked(const MixUtt *req, bool chained, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
                        const MixOpts *opts, MixLayout *out, const char *who)
 {
     auto refuse = [&](const std::string &what) {
@@ -48,12 +48,16 @@ int mix_layout_checked(const MixUtt *req, const uint64_t *n, const uint32_t *hz,
     }
     uint32_t bad = 0;
     const char *field = "";
-    if (!mix_layout(req, n, hz, B, elem, out, &bad, &field)) {
+    if (!mix_layout(req, n, hz, B, elem, out, &bad, &field, chained)) {
         const std::string f = field;
         if (f == "programme id")
-            return refuse("programme id " + std::to_string(bad) + " (an id is below the batch size, or JB_MIX_NONE)");
+            return refuse("programme id " + std::to_string(bad) + " (an id is below the batch size, or " +
+                          (chained ? "JB_JOIN_NONE)" : "JB_MIX_NONE)"));
         if (f == "length")
-            return refuse("start + samples + pad_after is too long (utterance " + std::to_string(bad) + ")");
+            return refuse(std::string(chained ? "the members in front + pad_before + " : "start + ") +
+                          "samples + pad_after is too long (utterance " + std::to_string(bad) + ")");
+        if (f == "slab length")
+            return refuse("the programmes up to programme " + std::to_string(bad) + " are too long together");
         if (f == "work lists") {
             set_error(std::string(who) + ": the segments' member lists pass 2^24 entries (programme " +
                       std::to_string(bad) + ")");
@@ -65,21 +69,29 @@ int mix_layout_checked(const MixUtt *req, const uint64_t *n, const uint32_t *hz,
 }
 
 void mix_lists(const MixLayout &lay, const MixUtt *req, const uint64_t *n, const uint64_t *xoff, const void *x, void *y,
-               size_t elem, std::vector<MixMember> *members, std::vector<MixSpan> *spans, uint64_t *tiles)
+               size_t elem, std::vector<ProgMember> *members, std::vector<ProgSpan> *spans, uint64_t *tiles)
 {
     const size_t B = lay.start.size(), P = lay.units.size();
-    members->assign(B, MixMember{});
-    spans->assign(P, MixSpan{});
+    members->assign(B, ProgMember{});
+    spans->assign(P, ProgSpan{});
     *tiles = 0;
     for (size_t p = 0; p < P; p++) {
-        for (uint32_t i = lay.progs.first[p]; i < lay.progs.first[p + 1]; i++) {
+        const uint32_t m0 = lay.progs.first[p], m1 = lay.progs.first[p + 1];
+        for (uint32_t i = m0; i < m1; i++) {
             const uint32_t u = lay.progs.members[i];
             (*members)[i] = {(const char *)x + xoff[u] * elem, lay.start[u], n[u], req[u].fade_in, req[u].fade_out,
                              lay.gain[u]};
         }
-        (*spans)[p] = {(char *)y + lay.units[p].off * elem, lay.units[p].n,           *tiles, *tiles,
-                       lay.seg_first[p],                   lay.seg_first[p + 1] - lay.seg_first[p], (uint32_t)p, 0};
-        *tiles += join_tiles(0, lay.units[p].n, elem == 2);
+        ProgSpan &w = (*spans)[p];
+        w.y = (char *)y + lay.units[p].off * elem;
+        w.n = w.k1 = lay.units[p].n;
+        w.t0 = w.pk0 = *tiles;
+        w.m0 = m0;
+        w.nm = m1 - m0;
+        w.s0 = lay.seg_first[p];
+        w.ns = lay.seg_first[p + 1] - lay.seg_first[p];
+        w.prog = (uint32_t)p;
+        *tiles += prog_tiles(0, w.n, elem == 2);
     }
 }
 
@@ -96,7 +108,8 @@ int mix_host(const T *const *in, const size_t *n_in, size_t n, const jb_mix_utt 
             return JB_ERR_INVALID;
     std::vector<uint64_t> ns(n_in, n_in + n);
     MixLayout lay;
-    int rc = mix_layout_checked((const MixUtt *)req, ns.data(), nullptr, n, sizeof(T), (const MixOpts *)opts, &lay, who);
+    int rc = mix_layout_checked((const MixUtt *)req, false, ns.data(), nullptr, n, sizeof(T), (const MixOpts *)opts, &lay,
+                                who);
     if (rc)
         return rc;
     const size_t P = lay.units.size();
@@ -159,8 +172,8 @@ int jb_mix_geometry(const jb_mix_utt *req, const size_t *n_in, const uint32_t *h
         return JB_ERR_INVALID;
     std::vector<uint64_t> ns(n_in, n_in + n);
     MixLayout lay;
-    int rc = mix_layout_checked((const MixUtt *)req, ns.data(), hz, n, sizeof(double), (const MixOpts *)opts, &lay,
-                                "jb_mix_geometry");
+    int rc = mix_layout_checked((const MixUtt *)req, false, ns.data(), hz, n, sizeof(double), (const MixOpts *)opts,
+                                &lay, "jb_mix_geometry");
     if (rc)
         return rc;
     for (size_t u = 0; u < n; u++) {

@@ -2,7 +2,7 @@
 // jb_mix.h -- the mix stage (include/jbonsai_amd.h "Mix"), the join's sibling: a programme's PCM is the sum of its
 // members, each at a start of its own, under its own edge fades (jb_join.h's, not restated) and a gain of its own.
 // The rules of one sample, of the gain and of the fit, stated once for the kernel (jb_mix.hip), for the host seam
-// (jb_mix.cpp) and for the output plan (jb_output.cpp), and the stage's work lists.
+// (jb_mix.cpp) and for the output plan (jb_output.cpp), and the segments of the work lists (members and spans: jb_join.h).
 // Plain C++17 and header-only; under hipcc the rules compile for the host and the device alike.
 #include <math.h>
 #include <stddef.h>
@@ -39,17 +39,7 @@ constexpr uint32_t kMixFit = 1u;         // JB_MIX_FIT
 constexpr double kMixMinDb = -120.0, kMixMaxDb = 40.0, kMixMinCeilingDb = -120.0;
 constexpr uint64_t kMixMaxList = 1ull << 24; // entries of the segments' member lists
 
-constexpr uint32_t kMixLanes = kJoinLanes, kMixTileBytes = kJoinTileBytes, kMixGroupBytes = kJoinGroupBytes;
-constexpr uint32_t kMixWaves = kMixLanes / 64; // a tile leaves one |acc| maximum per wave
-
-// One member of a mix launch, in the order of its programme (ascending utterance index)
-struct MixMember {
-    const void *x;  // its final PCM: f64 or 16-bit samples (by the launch)
-    uint64_t start; // its first sample within the programme
-    uint64_t n;
-    uint32_t fade_in, fade_out;
-    double g; // mix_gain of its gain_db
-};
+constexpr uint32_t kMixWaves = kProgLanes / 64; // a tile leaves one |acc| maximum per wave
 
 // One segment of a programme: samples [k0, k1) lie under the same unmuted members, lists[l0 .. l0 + nl) in ascending
 // utterance index (entries: places in the members' list).  A programme's segments follow each other from 0 to its
@@ -57,16 +47,6 @@ struct MixMember {
 struct MixSeg {
     uint64_t k0, k1;
     uint32_t l0, nl;
-};
-
-// One programme of a mix launch, always whole.  t0 is the prefix sum of the list's tiles, pk0 the programme's first
-// tile in the peak scratch (the full run's numbering: a redo keeps it); the programme owns segs[s0 .. s0 + ns)
-struct MixSpan {
-    void *y;    // the programme's first sample in its slab, 16-byte aligned
-    uint64_t n; // the programme's samples
-    uint64_t t0, pk0;
-    uint32_t s0, ns;
-    uint32_t prog, reserved;
 };
 
 // What k_mix_peak leaves per programme
@@ -97,11 +77,11 @@ JB_JOIN_HD double mix_term(double x, uint64_t k, uint64_t n, uint32_t fade_in, u
 
 // The sum at sample k of a programme under the members list[0 .. nl): the first term starts it, the others are added
 // in list order; +0.0 under no member
-template <class T> JB_JOIN_HD double mix_acc(const MixMember *members, const uint32_t *list, uint32_t nl, uint64_t k)
+template <class T> JB_JOIN_HD double mix_acc(const ProgMember *members, const uint32_t *list, uint32_t nl, uint64_t k)
 {
     double acc = 0.0;
     for (uint32_t i = 0; i < nl; i++) {
-        const MixMember m = members[list[i]];
+        const ProgMember m = members[list[i]];
         const uint64_t ka = k - m.start;
         const double t = mix_term((double)((const T *)m.x)[ka], ka, m.n, m.fade_in, m.fade_out, m.g);
         acc = i ? acc + t : t;

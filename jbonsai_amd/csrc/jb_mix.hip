@@ -1,7 +1,7 @@
 // jb_mix.hip -- the mix stage on the device: the chain's final PCM, f64 or 16-bit, summed into programmes (each member
 // at its start, under its fades and its gain) by the rules of jb_mix.h.
 //
-//   k_mix<T, kFit>   one workgroup per tile of kMixTileBytes of one programme (every programme starts on a 16-byte
+//   k_mix<T, kFit>   one workgroup per tile of kProgTileBytes of one programme (every programme starts on a 16-byte
 //               boundary of its slab and is listed whole).  A lane takes groups of 16 destination bytes -- 2 f64 or 8
 //               16-bit samples -- and stores each as one dwordx4.  A group inside one segment loads each covering
 //               member's samples in one load at whatever alignment they have (as k_join does; nothing in front of a
@@ -42,7 +42,7 @@ template <> struct MixVec<int16_t> {
     typedef MixS8u U;
 };
 
-__device__ __forceinline__ uint32_t mix_span_of(const MixSpan *spans, uint32_t n, uint64_t idx)
+__device__ __forceinline__ uint32_t mix_span_of(const ProgSpan *spans, uint32_t n, uint64_t idx)
 {
     uint32_t lo = 0, hi = n;
     while (hi - lo > 1) {
@@ -65,7 +65,7 @@ __device__ __forceinline__ double mix_wave_max(double v)
 
 // the sum at sample k of the programme whose segments are segs[lo .. hi]
 template <class T>
-__device__ __forceinline__ double mix_value(const MixSeg *segs, uint32_t lo, uint32_t hi, const MixMember *members,
+__device__ __forceinline__ double mix_value(const MixSeg *segs, uint32_t lo, uint32_t hi, const ProgMember *members,
                                             const uint32_t *lists, uint64_t k)
 {
     const MixSeg g = segs[mix_find(segs, lo, hi, k)];
@@ -73,18 +73,18 @@ __device__ __forceinline__ double mix_value(const MixSeg *segs, uint32_t lo, uin
 }
 
 template <class T, bool kFit>
-__global__ __launch_bounds__(kMixLanes) void k_mix(const MixSpan *__restrict__ spans, uint32_t n_spans,
-                                                   const MixMember *__restrict__ members,
+__global__ __launch_bounds__(kProgLanes) void k_mix(const ProgSpan *__restrict__ spans, uint32_t n_spans,
+                                                   const ProgMember *__restrict__ members,
                                                    const MixSeg *__restrict__ segs_all,
                                                    const uint32_t *__restrict__ lists, double *__restrict__ tile_peak,
                                                    const MixResult *__restrict__ res, double c)
 {
-    constexpr uint32_t G = kMixGroupBytes / sizeof(T);
-    constexpr uint32_t kTile = kMixTileBytes / sizeof(T);
-    static_assert(kTile % (kMixLanes * G) == 0, "a tile is whole groups of every lane");
+    constexpr uint32_t G = kProgGroupBytes / sizeof(T);
+    constexpr uint32_t kTile = kProgTileBytes / sizeof(T);
+    static_assert(kTile % (kProgLanes * G) == 0, "a tile is whole groups of every lane");
     typedef typename MixVec<T>::V V;
     typedef typename MixVec<T>::U U;
-    const MixSpan S = spans[mix_span_of(spans, n_spans, blockIdx.x)];
+    const ProgSpan S = spans[mix_span_of(spans, n_spans, blockIdx.x)];
     double s = 1.0;
     if (kFit) {
         s = res[S.prog].scale;
@@ -111,8 +111,8 @@ __global__ __launch_bounds__(kMixLanes) void k_mix(const MixSpan *__restrict__ s
         return o;
     };
 #pragma unroll
-    for (uint32_t i = 0; i < kTile / (kMixLanes * G); i++) {
-        const uint64_t ks = k0 + (uint64_t)(i * kMixLanes + threadIdx.x) * G;
+    for (uint32_t i = 0; i < kTile / (kProgLanes * G); i++) {
+        const uint64_t ks = k0 + (uint64_t)(i * kProgLanes + threadIdx.x) * G;
         if (ks + G <= k1) {
             const MixSeg g = segs[mix_find(segs, slo, shi, ks)];
             V v = (V)(T)0;
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kMixLanes) void k_mix(const MixSpan *__restrict__ s
                 double acc[G];
                 bool copied = false;
                 for (uint32_t j = 0; j < g.nl; j++) {
-                    const MixMember m = members[list[j]];
+                    const ProgMember m = members[list[j]];
                     const uint64_t ka = ks - m.start;
                     const V x = *(const JB_MIX_GLOBAL U *)((const JB_MIX_GLOBAL T *)m.x + ka);
                     const bool plain = join_plain(ka, ka + G - 1, m.n, m.fade_in, m.fade_out);
@@ -172,12 +172,12 @@ __global__ __launch_bounds__(kMixLanes) void k_mix(const MixSpan *__restrict__ s
     }
 }
 
-// One wave per programme of the list: M over its tiles' maxima (tile_samples: kMixTileBytes in samples), and s
-__global__ __launch_bounds__(64) void k_mix_peak(const MixSpan *__restrict__ spans, uint32_t tile_samples,
+// One wave per programme of the list: M over its tiles' maxima (tile_samples: kProgTileBytes in samples), and s
+__global__ __launch_bounds__(64) void k_mix_peak(const ProgSpan *__restrict__ spans, uint32_t tile_samples,
                                                  const double *__restrict__ tile_peak, MixResult *__restrict__ res,
                                                  bool fit, double c)
 {
-    const MixSpan S = spans[blockIdx.x];
+    const ProgSpan S = spans[blockIdx.x];
     const uint64_t slots = (S.n + tile_samples - 1) / tile_samples * kMixWaves;
     const double *pk = tile_peak + S.pk0 * kMixWaves;
     double m = 0.0;
@@ -189,21 +189,21 @@ __global__ __launch_bounds__(64) void k_mix_peak(const MixSpan *__restrict__ spa
 }
 
 template <class T>
-void mix_launch(const MixSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L, hipStream_t stream)
+void mix_launch(const ProgSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L, hipStream_t stream)
 {
     if (tiles)
-        hipLaunchKernelGGL((k_mix<T, false>), dim3((uint32_t)tiles), dim3(kMixLanes), 0, stream, spans_dev, n, L.members,
+        hipLaunchKernelGGL((k_mix<T, false>), dim3((uint32_t)tiles), dim3(kProgLanes), 0, stream, spans_dev, n, L.members,
                            L.segs, L.lists, L.tile_peak, (const MixResult *)L.res, L.ceiling);
-    hipLaunchKernelGGL(k_mix_peak, dim3(n), dim3(64), 0, stream, spans_dev, (uint32_t)(kMixTileBytes / sizeof(T)),
+    hipLaunchKernelGGL(k_mix_peak, dim3(n), dim3(64), 0, stream, spans_dev, (uint32_t)(kProgTileBytes / sizeof(T)),
                        (const double *)L.tile_peak, L.res, L.fit, L.ceiling);
     if (tiles && L.fit)
-        hipLaunchKernelGGL((k_mix<T, true>), dim3((uint32_t)tiles), dim3(kMixLanes), 0, stream, spans_dev, n, L.members,
+        hipLaunchKernelGGL((k_mix<T, true>), dim3((uint32_t)tiles), dim3(kProgLanes), 0, stream, spans_dev, n, L.members,
                            L.segs, L.lists, L.tile_peak, (const MixResult *)L.res, L.ceiling);
 }
 
 } // namespace
 
-hipError_t launch_mix(bool i16, const MixSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L,
+hipError_t launch_mix(bool i16, const ProgSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L,
                       hipStream_t stream)
 {
     if (n == 0)
@@ -219,21 +219,24 @@ hipError_t launch_mix(bool i16, const MixSpan *spans_dev, uint32_t n, uint64_t t
 
 namespace {
 
-// jb_mix_pcm_batch / _i16: the inputs packed one after the other on the device (as a batch's slab has them), the
-// programmes of the geometry each on a 16-byte boundary
+// jb_join_pcm_batch, jb_mix_pcm_batch and their _i16 forms: the inputs packed one after the other on the device (as a
+// batch's slab has them), the programmes of the geometry each on a 16-byte boundary.  `chained`: request is a join's
+// (jb_join_utt[n]; else jb_mix_utt[n]), without options and reports, and the launch is the join's
 template <class T>
-int mix_pcm_batch(const T *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req, const jb_mix_opts *opts,
-                  int32_t device, T **out, size_t *n_out, size_t *n_programmes, jb_mix_report *reports, const char *who)
+int programme_pcm_batch(const T *const *in, const size_t *n_in, size_t n, const void *request, bool chained,
+                        const MixOpts *opts, int32_t device, T **out, size_t *n_out, size_t *n_programmes,
+                        jb_mix_report *reports, const char *who)
 {
     if (n_programmes)
         *n_programmes = 0;
-    int rc = pcm_check((const void *const *)in, n_in, n, req && out && n_out, (void **)out, n_out);
+    int rc = pcm_check((const void *const *)in, n_in, n, request && out && n_out, (void **)out, n_out);
     if (rc)
         return rc;
+    const std::vector<MixUtt> as_mix = chained ? join_as_mix((const JoinUtt *)request, n) : std::vector<MixUtt>();
+    const MixUtt *req = chained ? as_mix.data() : (const MixUtt *)request;
     std::vector<uint64_t> ns(n_in, n_in + n);
     MixLayout lay;
-    if ((rc = mix_layout_checked((const MixUtt *)req, ns.data(), nullptr, n, sizeof(T), (const MixOpts *)opts, &lay,
-                                 who)))
+    if ((rc = mix_layout_checked(req, chained, ns.data(), nullptr, n, sizeof(T), opts, &lay, who)))
         return rc;
     const size_t P = lay.units.size();
     DeviceScratch ds;
@@ -242,25 +245,29 @@ int mix_pcm_batch(const T *const *in, const size_t *n_in, size_t n, const jb_mix
     std::vector<uint64_t> xoff;
     const T *dx = ds.pack(in, n_in, n, &xoff);
     T *dy = ds.alloc<T>(lay.total);
-    std::vector<MixMember> members;
-    std::vector<MixSpan> spans;
+    std::vector<ProgMember> members;
+    std::vector<ProgSpan> spans;
     uint64_t tiles = 0;
-    mix_lists(lay, (const MixUtt *)req, ns.data(), xoff.data(), dx, dy, sizeof(T), &members, &spans, &tiles);
+    mix_lists(lay, req, ns.data(), xoff.data(), dx, dy, sizeof(T), &members, &spans, &tiles);
     MixLaunch L{};
     L.members = ds.upload(members);
-    L.segs = ds.upload(lay.segs);
-    L.lists = ds.upload(lay.lists);
-    L.tile_peak = ds.alloc<double>(tiles * kMixWaves);
-    L.res = ds.alloc<MixResult>(P);
-    L.fit = opts && (opts->flags & kMixFit);
-    L.ceiling = L.fit ? mix_ceiling(opts->ceiling_db) : 0.0;
-    const MixSpan *dsp = ds.upload(spans);
+    if (!chained) { // (the join's kernel reads the members alone)
+        L.segs = ds.upload(lay.segs);
+        L.lists = ds.upload(lay.lists);
+        L.tile_peak = ds.alloc<double>(tiles * kMixWaves);
+        L.res = ds.alloc<MixResult>(P);
+        L.fit = opts && (opts->flags & kMixFit);
+        L.ceiling = L.fit ? mix_ceiling(opts->ceiling_db) : 0.0;
+    }
+    const ProgSpan *dsp = ds.upload(spans);
     if (ds.ok())
-        ds.err = launch_mix(sizeof(T) == 2, dsp, (uint32_t)P, tiles, L, ds.stream);
+        ds.err = chained ? launch_join(sizeof(T) == 2, dsp, (uint32_t)P, tiles, L.members, ds.stream)
+                         : launch_mix(sizeof(T) == 2, dsp, (uint32_t)P, tiles, L, ds.stream);
     std::vector<T> host;
     std::vector<MixResult> res;
     ds.read_back(&host, dy, lay.total);
-    ds.read_back(&res, (const MixResult *)L.res, P);
+    if (!chained)
+        ds.read_back(&res, (const MixResult *)L.res, P);
     if ((rc = ds.status()))
         return rc;
     std::vector<PcmShare> shares(P);
@@ -268,7 +275,7 @@ int mix_pcm_batch(const T *const *in, const size_t *n_in, size_t n, const jb_mix
         shares[p] = {lay.units[p].off, lay.units[p].n};
     if ((rc = hand_out(host.data(), sizeof(T), shares, (void **)out, n_out)))
         return rc;
-    for (size_t p = 0; reports && p < P; p++)
+    for (size_t p = 0; reports && !chained && p < P; p++)
         reports[p] = {res[p].peak, res[p].scale, lay.depth[p], 0, lay.overlap[p]};
     if (n_programmes)
         *n_programmes = P;
@@ -283,18 +290,34 @@ using namespace jb;
 
 extern "C" {
 
+int jb_join_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_join_utt *req, int32_t device,
+                      double **out, size_t *n_out, size_t *n_programmes)
+{
+    return programme_pcm_batch(in, n_in, n, req, true, nullptr, device, out, n_out, n_programmes, nullptr,
+                               "jb_join_pcm_batch");
+}
+
+int jb_join_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n, const jb_join_utt *req,
+                          int32_t device, int16_t **out, size_t *n_out, size_t *n_programmes)
+{
+    return programme_pcm_batch(in, n_in, n, req, true, nullptr, device, out, n_out, n_programmes, nullptr,
+                               "jb_join_pcm_batch_i16");
+}
+
 int jb_mix_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
                      const jb_mix_opts *opts, int32_t device, double **out, size_t *n_out, size_t *n_programmes,
                      jb_mix_report *reports)
 {
-    return mix_pcm_batch(in, n_in, n, req, opts, device, out, n_out, n_programmes, reports, "jb_mix_pcm_batch");
+    return programme_pcm_batch(in, n_in, n, req, false, (const MixOpts *)opts, device, out, n_out, n_programmes, reports,
+                               "jb_mix_pcm_batch");
 }
 
 int jb_mix_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
                          const jb_mix_opts *opts, int32_t device, int16_t **out, size_t *n_out, size_t *n_programmes,
                          jb_mix_report *reports)
 {
-    return mix_pcm_batch(in, n_in, n, req, opts, device, out, n_out, n_programmes, reports, "jb_mix_pcm_batch_i16");
+    return programme_pcm_batch(in, n_in, n, req, false, (const MixOpts *)opts, device, out, n_out, n_programmes, reports,
+                               "jb_mix_pcm_batch_i16");
 }
 
 } // extern "C"

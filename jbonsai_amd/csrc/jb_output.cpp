@@ -75,37 +75,22 @@ OutPlan plan_output(const OutPlanIn &in)
     // then read; their units are the programmes (a request the chain has checked; one that does not lay out: no join)
     std::vector<OutUnit> units;
     OutWrite enc = p.final; // what the encoders read
-    if (in.join) {
-        std::vector<uint64_t> n(in.B);
-        for (size_t u = 0; u < in.B; u++)
-            n[u] = p.utt[u].n;
-        JoinLayout lay;
-        if (join_layout(in.join, n.data(), nullptr, in.B, p.final.i16 ? 2 : 8, &lay, nullptr, nullptr)) {
-            p.join_src = p.final;
-            p.join = {p.final.i16 ? OutSlab::Join16 : OutSlab::Join64, p.final.i16};
-            for (size_t g = 0; g < lay.units.size(); g++)
-                lay.units[g].hz = p.utt[lay.progs.members[lay.progs.first[g]]].hz;
-            p.units = lay.units;
-            p.prog_of = std::move(lay.progs.group_of);
-            p.prog_first = std::move(lay.progs.first);
-            p.prog_members = std::move(lay.progs.members);
-            p.prog_start = std::move(lay.start);
-            p.alloc[(size_t)p.join.slab] = std::max<uint64_t>(lay.total, 1);
-            enc = p.join;
-            if (p.flac != OutSlab::None)
-                p.flac = p.join.slab;
-        }
-    }
-    // a mix request goes exactly where the join goes: the same slab, the same fields, the programmes its sums
-    if (in.mix && !in.join) {
+    // (a join's request and a mix's go the same way: the same slab, the same fields; only what the report and the redo
+    // rule read tells them apart; a join given in its own words is worded as the mix it means first, in front of `mix`)
+    std::vector<MixUtt> worded;
+    if (in.join)
+        worded = join_as_mix(in.join, in.B);
+    const MixUtt *request = in.join ? worded.data() : in.mix;
+    const bool chained = in.join || in.chained;
+    if (request) {
         std::vector<uint64_t> n(in.B);
         for (size_t u = 0; u < in.B; u++)
             n[u] = p.utt[u].n;
         MixLayout lay;
-        if (mix_layout(in.mix, n.data(), nullptr, in.B, p.final.i16 ? 2 : 8, &lay, nullptr, nullptr)) {
+        if (mix_layout(request, n.data(), nullptr, in.B, p.final.i16 ? 2 : 8, &lay, nullptr, nullptr, chained)) {
             p.join_src = p.final;
             p.join = {p.final.i16 ? OutSlab::Join16 : OutSlab::Join64, p.final.i16};
-            p.mixed = true;
+            p.mixed = !chained;
             for (size_t g = 0; g < lay.units.size(); g++)
                 lay.units[g].hz = p.utt[lay.progs.members[lay.progs.first[g]]].hz;
             p.units = lay.units;
@@ -113,8 +98,10 @@ OutPlan plan_output(const OutPlanIn &in)
             p.prog_first = std::move(lay.progs.first);
             p.prog_members = std::move(lay.progs.members);
             p.prog_start = std::move(lay.start);
-            p.mix_depth = std::move(lay.depth);
-            p.mix_overlap = std::move(lay.overlap);
+            if (p.mixed) {
+                p.mix_depth = std::move(lay.depth);
+                p.mix_overlap = std::move(lay.overlap);
+            }
             p.alloc[(size_t)p.join.slab] = std::max<uint64_t>(lay.total, 1);
             enc = p.join;
             if (p.flac != OutSlab::None)
@@ -224,48 +211,31 @@ OutPlan plan_output(const OutPlanIn &in)
     return p;
 }
 
+std::vector<MixUtt> join_as_mix(const JoinUtt *req, size_t B)
+{
+    std::vector<MixUtt> m(B, MixUtt{});
+    for (size_t u = 0; u < B; u++) {
+        m[u].programme = req[u].programme;
+        m[u].fade_in = req[u].fade_in;
+        m[u].fade_out = req[u].fade_out;
+        m[u].reserved = req[u].reserved;
+        m[u].start = req[u].pad_before;
+        m[u].pad_after = req[u].pad_after;
+    }
+    return m;
+}
+
 bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, JoinLayout *out,
                  uint32_t *bad, const char **field)
 {
-    // the numbering and the agreement on the rate are the loudness groups' (kJoinNone == kLnNoGroup)
-    static_assert(kJoinNone == kLnNoGroup, "one numbering for groups and programmes");
-    std::vector<uint32_t> ids(B);
-    for (size_t u = 0; u < B; u++)
-        ids[u] = req[u].programme;
-    LnGroupsIn gi;
-    gi.B = B;
-    gi.group = ids.data();
-    gi.hz = hz;
-    JoinLayout lay;
-    const char *f = "";
-    if (!plan_loudness_groups(gi, &lay.progs, bad, &f)) {
-        if (field)
-            *field = f[0] == 'g' ? "programme id" : f; // ("group id")
-        return false;
-    }
-    const size_t P = lay.progs.size();
-    const uint64_t align = kJoinGroupBytes / elem;
-    lay.units.assign(P, OutUnit{});
-    lay.start.assign(B, 0);
-    for (size_t g = 0; g < P; g++) {
-        OutUnit &w = lay.units[g];
-        w.off = lay.total;
-        for (uint32_t i = lay.progs.first[g]; i < lay.progs.first[g + 1]; i++) {
-            const uint32_t u = lay.progs.members[i];
-            lay.start[u] = w.n + req[u].pad_before;
-            w.n = lay.start[u] + n[u] + req[u].pad_after;
-        }
-        w.hz = hz ? hz[lay.progs.members[lay.progs.first[g]]] : 0;
-        lay.total = (w.off + w.n + align - 1) / align * align;
-    }
-    *out = std::move(lay);
-    return true;
+    return mix_layout(join_as_mix(req, B).data(), n, hz, B, elem, out, bad, field, true);
 }
 
 bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, MixLayout *out,
-                uint32_t *bad, const char **field)
+                uint32_t *bad, const char **field, bool chained)
 {
-    static_assert(kMixNone == kLnNoGroup, "one numbering for groups and programmes");
+    // the numbering and the agreement on the rate are the loudness groups'
+    static_assert(kMixNone == kLnNoGroup && kJoinNone == kLnNoGroup, "one numbering for groups and programmes");
     auto refuse = [&](uint32_t id, const char *f) {
         if (bad)
             *bad = id;
@@ -286,7 +256,7 @@ bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t
     if (!plan_loudness_groups(gi, &lay.progs, &id, &f))
         return refuse(id, f[0] == 'g' ? "programme id" : f); // ("group id")
     const size_t P = lay.progs.size();
-    const uint64_t align = kMixGroupBytes / elem;
+    const uint64_t align = kProgGroupBytes / elem;
     constexpr uint64_t kMaxLen = 1ull << 63;
     lay.units.assign(P, OutUnit{});
     lay.start.assign(B, 0);
@@ -307,20 +277,23 @@ bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t
         ev.clear();
         for (uint32_t i = lay.progs.first[g]; i < lay.progs.first[g + 1]; i++) {
             const uint32_t u = lay.progs.members[i];
-            if (req[u].start >= kMaxLen || n[u] >= kMaxLen || req[u].pad_after >= kMaxLen ||
-                req[u].start + n[u] + req[u].pad_after >= kMaxLen)
+            // (each term below 2^63 and each partial sum checked: no sum wraps)
+            if (req[u].start >= kMaxLen || n[u] >= kMaxLen || req[u].pad_after >= kMaxLen)
                 return refuse(u, "length");
-            lay.start[u] = req[u].start;
+            const uint64_t start = chained ? w.n + req[u].start : req[u].start; // (w.n: where the member in front ends)
+            if (start >= kMaxLen || start + n[u] >= kMaxLen || start + n[u] + req[u].pad_after >= kMaxLen)
+                return refuse(u, "length");
+            lay.start[u] = start;
             lay.gain[u] = mix_gain(req[u].gain_db);
-            w.n = std::max(w.n, req[u].start + n[u] + req[u].pad_after);
+            w.n = std::max(w.n, start + n[u] + req[u].pad_after);
             if (lay.gain[u] != 0.0 && n[u]) {
-                ev.push_back({req[u].start, i, true});
-                ev.push_back({req[u].start + n[u], i, false});
+                ev.push_back({start, i, true});
+                ev.push_back({start + n[u], i, false});
             }
         }
         w.hz = hz ? hz[lay.progs.members[lay.progs.first[g]]] : 0;
         if (lay.total >= kMaxLen || w.n + align >= kMaxLen - lay.total)
-            return refuse((uint32_t)g, "length");
+            return refuse((uint32_t)g, "slab length");
         lay.total = (w.off + w.n + align - 1) / align * align;
         // the sweep: a segment ends at every event; between two the cover stands
         std::stable_sort(ev.begin(), ev.end(), [](const Event &a, const Event &b) { return a.k < b.k; });

@@ -66,8 +66,10 @@ struct OutPlanIn {
     uint32_t fmt_bytes = 0;               // bytes per sample of the requested sample format; 0: none requested
     bool adpcm = false;                   // IMA ADPCM is requested
     uint32_t adpcm_align = 0;             // its block_align: 0 = by each utterance's output rate (jb_adpcm.h)
-    const JoinUtt *join = nullptr;        // [B] the join request (jb_join.h); nullptr: none
-    const MixUtt *mix = nullptr;          // [B] the mix request (jb_mix.h) in the join's place; nullptr: none (never both)
+    const MixUtt *mix = nullptr;          // [B] the programme request in the mix's words (jb_mix.h): a mix's, or with
+    bool chained = false;                 // `chained` a join's as join_as_mix words it; nullptr: none
+    const JoinUtt *join = nullptr;        // [B] a join request in its own words (jb_join.h), as the host probes give
+                                          // it: the plan words it with join_as_mix itself, in front of `mix`
     const uint8_t *filter = nullptr;      // [B] 1 = the utterance's filter has at least one section; nullptr: no request
     const FbankOpts *fbank = nullptr;     // the filterbank request (jb_fbank.h), checked at every output rate; nullptr: none
     const FbankOpts *mfcc_fbank = nullptr; // the cepstral request (jb_mfcc.h): its filterbank's geometry (the stage forces
@@ -198,28 +200,21 @@ bool plan_loudness_groups(const LnGroupsIn &in, LnGroups *out, uint32_t *bad_gro
 void loudness_groups_closure(const LnGroups &g, const std::vector<uint8_t> &touched, std::vector<uint8_t> *groups,
                              std::vector<uint8_t> *members);
 
-// The join request laid out (jb_join.h): programmes numbered densely in the order of their first member, as the
-// loudness groups are (an utterance of kJoinNone: a programme of one); programme p is its members in ascending
-// utterance index, each between its pads, and starts on a 16-byte boundary of a slab of `elem`-byte samples
-struct JoinLayout {
-    LnGroups progs;              // group_of: [B] the programme of each utterance; first / members: [P + 1] / [B]
-    std::vector<OutUnit> units;  // [P]
-    std::vector<uint64_t> start; // [B] each member's first sample within its programme
-    uint64_t total = 0;          // samples of the slab
-};
-// Pure.  n: [B] each utterance's samples; hz: [B] its output rate (nullptr: not compared, the units' rate is 0).
-// false: the request is refused; *bad is the caller's id of the offending programme and *field says "programme id"
-// for an id of B or above, or "output rate" where its members disagree
-bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, JoinLayout *out,
-                 uint32_t *bad, const char **field);
+// A join request (jb_join.h) in the mix's words, all but the starts: 0 dB, the fades, pad_after and the reserved word
+// carried over, and `start` holding pad_before -- counted from where the member in front ends with its pad_after,
+// which the layout alone knows.  mix_layout takes it with `chained` and leaves in `start` the starts the request means:
+// a join is the mix whose members follow each other, so its depth is at most 1 and its overlap 0
+std::vector<MixUtt> join_as_mix(const JoinUtt *req, size_t B);
 
-// The mix request laid out (jb_mix.h): programmes numbered as the join numbers them; a member starts where its request
-// says, a programme's length is the largest start + n + pad_after of its members, and each programme starts on a
-// 16-byte boundary of a slab of `elem`-byte samples.  The work lists follow from the geometry alone: each programme cut
-// at every start and end of an unmuted member (gain[u] != 0) of at least one sample into segments under a constant
-// set of members, each segment's set listed once in ascending utterance index
+// The programme request laid out, a mix's (jb_mix.h) or a join's (join_as_mix, `chained`): programmes numbered densely
+// in the order of their first member, as the loudness groups are (an utterance of kMixNone: a programme of one), their
+// members in ascending utterance index; a member starts where its request says (`chained`: that far behind the end of
+// the member in front), a programme's length is the largest start + n + pad_after of its members, and each programme
+// starts on a 16-byte boundary of a slab of `elem`-byte samples.  The work lists follow from the geometry alone: each
+// programme cut at every start and end of an unmuted member (gain[u] != 0) of at least one sample into segments under
+// a constant set of members, each segment's set listed once in ascending utterance index
 struct MixLayout {
-    LnGroups progs;              // as JoinLayout's
+    LnGroups progs;              // group_of: [B] the programme of each utterance; first / members: [P + 1] / [B]
     std::vector<OutUnit> units;  // [P]
     std::vector<uint64_t> start; // [B] each member's first sample within its programme
     uint64_t total = 0;          // samples of the slab
@@ -230,11 +225,17 @@ struct MixLayout {
     std::vector<uint32_t> depth;     // [P] the longest list of the programme
     std::vector<uint64_t> overlap;   // [P] its samples in segments of two or more
 };
-// Pure.  n, hz: as join_layout's.  false: the request is refused; *bad is the caller's id of the offending programme
-// (for "length" and "work lists": the utterance or the dense programme) and *field says "programme id", "output
-// rate", "length" where start + n + pad_after passes 2^63, or "work lists" where the lists pass kMixMaxList entries
+// Pure.  n: [B] each utterance's samples; hz: [B] its output rate (nullptr: not compared, the units' rate is 0).
+// false: the request is refused; *bad is the caller's id of the offending programme (for "length" and "work lists":
+// the utterance or the dense programme) and *field says "programme id" for an id of B or above, "output rate" where
+// its members disagree, "length" where an utterance's start + n + pad_after passes 2^63, "slab length" where the
+// programmes up to the dense programme *bad pass it together, or "work lists" where the lists pass kMixMaxList entries
 bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, MixLayout *out,
-                uint32_t *bad, const char **field);
+                uint32_t *bad, const char **field, bool chained = false);
+// The same from a join request in its own words (the host probes' way in): mix_layout of join_as_mix, chained
+using JoinLayout = MixLayout;
+bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, JoinLayout *out,
+                 uint32_t *bad, const char **field);
 
 // The redo closure behind the join.  post: [B] 1 = an utterance whose final PCM changed (behind
 // loudness_groups_closure); programmes: [P] 1 = a programme with such a member

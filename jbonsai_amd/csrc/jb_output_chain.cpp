@@ -39,8 +39,8 @@ void OutputChain::replan()
     in.fmt_bytes = fmt_on ? (uint32_t)format_bytes(fmt_p.format) : 0;
     in.adpcm = ad_on;
     in.adpcm_align = ad_align;
-    in.join = join_req.empty() ? nullptr : join_req.data();
-    in.mix = mix_req.empty() ? nullptr : mix_req.data();
+    in.mix = prog_req.empty() ? nullptr : prog_req.data();
+    in.chained = prog_chained;
     flag_stage();
     in.filter = stage_any.empty() ? nullptr : stage_any.data();
     in.fbank = fb_on ? &fb_p : nullptr;
@@ -112,8 +112,7 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
             return rc;
     }
     if ((rc = check_groups(ln_group_req, ln_target, ln_ceiling, ln_mode, want, "jb_batch_set_output_rate", nullptr)) ||
-        (rc = check_join(join_req, want, "jb_batch_set_output_rate")) ||
-        (rc = check_mix(mix_req, mix_opts, want, "jb_batch_set_output_rate")) ||
+        (rc = check_programme(prog_req, prog_chained, mix_opts, want, "jb_batch_set_output_rate")) ||
         (rc = check_filter(filt_req, want, "jb_batch_set_output_rate")) ||
         (rc = check_fir(want, "jb_batch_set_output_rate")) ||
         (rc = check_noise(want, "jb_batch_set_output_rate")) ||
@@ -425,47 +424,10 @@ int OutputChain::set_melspec(const jb_melspec_opts *opts)
     return JB_OK;
 }
 
-// The join request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming what is wrong
-int OutputChain::check_join(const std::vector<JoinUtt> &req, const std::vector<uint32_t> &want, const char *who) const
-{
-    if (req.empty())
-        return JB_OK;
-    const std::vector<uint32_t> hz = rates_under(want);
-    std::vector<uint64_t> n(hz.size(), 0); // (the lengths do not bear on the check)
-    JoinLayout lay;
-    return join_layout_checked(req.data(), n.data(), hz.data(), hz.size(), sizeof(double), &lay, who);
-}
-
-int OutputChain::set_join(const jb_join_utt *req, size_t n)
-{
-    int rc = check_settable("jb_batch_set_join: the join is set before the batch's first run");
-    if (rc)
-        return rc;
-    if (!req && n == 0) {
-        join_req.clear();
-        replan();
-        return JB_OK;
-    }
-    if (!req || n != (size_t)b.B) {
-        set_error("jb_batch_set_join: give one request per utterance");
-        return JB_ERR_INVALID;
-    }
-    if (!mix_req.empty()) {
-        set_error("jb_batch_set_join: the batch holds a mix request (a batch holds a join or a mix request; withdraw "
-                  "the one first)");
-        return JB_ERR_INVALID;
-    }
-    std::vector<JoinUtt> r((const JoinUtt *)req, (const JoinUtt *)req + n);
-    if ((rc = check_join(r, want_hz, "jb_batch_set_join")))
-        return rc;
-    join_req = std::move(r);
-    replan();
-    return JB_OK;
-}
-
-// The mix request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming what is wrong
-int OutputChain::check_mix(const std::vector<MixUtt> &req, const MixOpts &opts, const std::vector<uint32_t> &want,
-                           const char *who) const
+// The programme request `req` ([B], empty: none), a join's (`chained`) or a mix's, under these rates: JB_ERR_INVALID
+// naming what is wrong
+int OutputChain::check_programme(const std::vector<MixUtt> &req, bool chained, const MixOpts &opts,
+                                 const std::vector<uint32_t> &want, const char *who) const
 {
     if (req.empty())
         return JB_OK;
@@ -479,37 +441,70 @@ int OutputChain::check_mix(const std::vector<MixUtt> &req, const MixOpts &opts, 
         n[u] = resample_out_len((uint64_t)b.T[u] * b.voice.fperiod, L, M);
     }
     MixLayout lay;
-    return mix_layout_checked(req.data(), n.data(), hz.data(), hz.size(), sizeof(double), &opts, &lay, who);
+    return mix_layout_checked(req.data(), chained, n.data(), hz.data(), hz.size(), sizeof(double),
+                              chained ? nullptr : &opts, &lay, who);
+}
+
+// The one slot for a programme request, a join's (`chained`) or a mix's: what either setter checks before it reads its
+// request.  *store: a request of one entry per utterance is given and the slot is free for it; else the call is over
+// (refused, or a withdrawal, which leaves a request of the other kind alone)
+int OutputChain::open_programme(bool chained, bool given, size_t n, bool *store)
+{
+    *store = false;
+    const std::string kind = chained ? "join" : "mix", who = "jb_batch_set_" + kind;
+    int rc = check_settable((who + ": the " + kind + " is set before the batch's first run").c_str());
+    if (rc)
+        return rc;
+    const bool taken = !prog_req.empty() && prog_chained != chained; // the slot holds a request of the other kind
+    if (!given && n == 0) {
+        if (!taken) {
+            prog_req.clear();
+            mix_opts = MixOpts{};
+            replan();
+        }
+        return JB_OK;
+    }
+    if (!given || n != (size_t)b.B) {
+        set_error(who + ": give one request per utterance");
+        return JB_ERR_INVALID;
+    }
+    if (taken) {
+        set_error(who + ": the batch holds a " + (chained ? "mix" : "join") +
+                  " request (a batch holds a join or a mix request; withdraw the one first)");
+        return JB_ERR_INVALID;
+    }
+    *store = true;
+    return JB_OK;
+}
+
+// The request in the mix's words into the slot, checked under the present rates
+int OutputChain::store_programme(bool chained, std::vector<MixUtt> req, const MixOpts &opts)
+{
+    int rc = check_programme(req, chained, opts, want_hz, chained ? "jb_batch_set_join" : "jb_batch_set_mix");
+    if (rc)
+        return rc;
+    prog_req = std::move(req);
+    prog_chained = chained;
+    mix_opts = opts;
+    replan();
+    return JB_OK;
+}
+
+int OutputChain::set_join(const jb_join_utt *req, size_t n)
+{
+    bool store;
+    const int rc = open_programme(true, req != nullptr, n, &store);
+    return rc || !store ? rc : store_programme(true, join_as_mix((const JoinUtt *)req, n), MixOpts{});
 }
 
 int OutputChain::set_mix(const jb_mix_utt *req, size_t n, const jb_mix_opts *opts)
 {
-    int rc = check_settable("jb_batch_set_mix: the mix is set before the batch's first run");
-    if (rc)
+    bool store;
+    const int rc = open_programme(false, req != nullptr, n, &store);
+    if (rc || !store)
         return rc;
-    if (!req && n == 0) {
-        mix_req.clear();
-        mix_opts = MixOpts{};
-        replan();
-        return JB_OK;
-    }
-    if (!req || n != (size_t)b.B) {
-        set_error("jb_batch_set_mix: give one request per utterance");
-        return JB_ERR_INVALID;
-    }
-    if (!join_req.empty()) {
-        set_error("jb_batch_set_mix: the batch holds a join request (a batch holds a join or a mix request; withdraw "
-                  "the one first)");
-        return JB_ERR_INVALID;
-    }
-    std::vector<MixUtt> r((const MixUtt *)req, (const MixUtt *)req + n);
-    const MixOpts o = opts ? *(const MixOpts *)opts : MixOpts{};
-    if ((rc = check_mix(r, o, want_hz, "jb_batch_set_mix")))
-        return rc;
-    mix_req = std::move(r);
-    mix_opts = o;
-    replan();
-    return JB_OK;
+    const MixUtt *r = (const MixUtt *)req;
+    return store_programme(false, std::vector<MixUtt>(r, r + n), opts ? *(const MixOpts *)opts : MixOpts{});
 }
 
 // The filter request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming the utterance, the section
@@ -834,7 +829,7 @@ int OutputChain::prepare()
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
             return rc;
     if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_noise()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
-        (rc = prepare_join()) || (rc = prepare_mix()) ||
+        (rc = prepare_programme()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
         (rc = prepare_fbank()) || (rc = prepare_mfcc()) || (rc = prepare_melspec()))
         return rc;
@@ -860,15 +855,15 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const RedoScope *scope = redo ? &of_redo : nullptr;
     int rc;
     if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_noise(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
-        (rc = select_limiter(scope)) || (rc = select_join(scope)) || (rc = select_mix(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
+        (rc = select_limiter(scope)) || (rc = select_programme(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
         (rc = select_adpcm(scope)) || (rc = select_fbank(scope)) || (rc = select_mfcc(scope)) ||
         (rc = select_melspec(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || jn.spans.n || mx.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || pg.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_noise(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
-        (rc = launch_limiter(redo)) || (rc = launch_join(redo)) || (rc = launch_mix(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
+        (rc = launch_limiter(redo)) || (rc = launch_programme(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
         (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)) || (rc = launch_mfcc(redo)) ||
         (rc = launch_melspec(redo)))
         return rc;
@@ -1406,82 +1401,12 @@ std::vector<OutputChain::EncUnit> OutputChain::enc_units() const
     return units;
 }
 
-// ---- the join: behind everything that writes the final PCM, in front of everything that encodes it.
-// Samples [k0, k1) of programme p as a span whose tiles follow *tiles
-JoinSpan OutputChain::join_span(size_t p, uint64_t k0, uint64_t k1, uint64_t *tiles) const
+// ---- the programmes, a join's or a mix's: behind everything that writes the final PCM, in front of everything that
+// encodes it.  The members, the segments and their lists from the layout (mix_layout, as the plan formed it) and one
+// span per programme; with a mix the peak scratch and the results
+int OutputChain::prepare_programme()
 {
-    const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
-    const uint32_t m0 = plan.prog_first[p], m1 = plan.prog_first[p + 1];
-    const JoinSpan w = {(char *)slab[(size_t)plan.join.slab] + plan.units[p].off * elem, plan.units[p].n, k0, k1, *tiles,
-                        m0, m1 - m0};
-    *tiles += join_tiles(k0, k1, plan.join.i16);
-    return w;
-}
-
-// The members in programme order and one span per programme: the final PCM of the plan in, the join slab out
-int OutputChain::prepare_join()
-{
-    if (!joined() || mixed())
-        return JB_OK;
-    const size_t B = (size_t)b.B, P = plan.units.size();
-    const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
-    const char *src = (const char *)slab[(size_t)plan.join_src.slab];
-    jn.members.assign(B, JoinMember{});
-    jn.member_at.assign(B, 0);
-    jn.spans.host.clear();
-    jn.tiles = 0;
-    for (size_t p = 0; p < P; p++) {
-        for (uint32_t i = plan.prog_first[p]; i < plan.prog_first[p + 1]; i++) {
-            const uint32_t u = plan.prog_members[i];
-            jn.member_at[u] = i;
-            jn.members[i] = {src + plan.utt[u].off * elem, plan.prog_start[u], plan.utt[u].n, join_req[u].fade_in,
-                             join_req[u].fade_out};
-        }
-        jn.spans.host.push_back(join_span(p, 0, plan.units[p].n, &jn.tiles));
-    }
-    int rc;
-    // (a redo lists at most one span per member)
-    if ((rc = b.dalloc(&jn.members_dev, B, false)) || (rc = jn.spans.alloc(b, P, B)) ||
-        (rc = upload_list(jn.members_dev, jn.members, "join work list")))
-        return rc;
-    return jn.spans.upload("join work list");
-}
-
-int OutputChain::select_join(const RedoScope *scope)
-{
-    if (!joined() || mixed() || !scope)
-        return jn.spans.take_all(jn.tiles);
-    const std::vector<uint8_t> &mask = scope->post; // every utterance whose final PCM changed
-    const uint64_t gs = kJoinGroupBytes / (plan.join.i16 ? sizeof(int16_t) : sizeof(double));
-    std::vector<JoinSpan> sub;
-    uint64_t tiles = 0;
-    for (size_t u = 0; u < mask.size(); u++) {
-        if (!mask[u] || !plan.utt[u].n) // a member of zero samples wrote nothing into its programme: no span
-            continue;
-        // not the whole programme: the member's range alone, widened to whole groups of kJoinGroupBytes (the samples
-        // around it are what they were: its neighbours' current ones, and pads)
-        const JoinMember &m = jn.members[jn.member_at[u]];
-        const uint64_t end = plan.units[plan.prog_of[u]].n;
-        sub.push_back(join_span(plan.prog_of[u], m.start / gs * gs,
-                                std::min<uint64_t>((m.start + m.n + gs - 1) / gs * gs, end), &tiles));
-    }
-    return jn.spans.upload_redo(sub, kRedoLists, tiles);
-}
-
-int OutputChain::launch_join(bool redo)
-{
-    if (!joined() || mixed() || (redo && !jn.spans.n))
-        return JB_OK;
-    const hipError_t e =
-        jb::launch_join(plan.join.i16, jn.spans.list, jn.spans.n, jn.spans.total, jn.members_dev, b.stream_voc);
-    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_join(redo)" : "k_join");
-}
-
-// ---- the mix, in the join's place: the members, the segments and their lists from the layout (mix_layout, as the
-// plan formed it), one span per programme, the peak scratch and the results
-int OutputChain::prepare_mix()
-{
-    if (!mixed())
+    if (!joined())
         return JB_OK;
     const size_t B = (size_t)b.B, P = plan.units.size();
     const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
@@ -1491,52 +1416,80 @@ int OutputChain::prepare_mix()
         xoff[u] = plan.utt[u].off;
     }
     MixLayout lay;
-    int rc = mix_layout_checked(mix_req.data(), n.data(), nullptr, B, elem, &mix_opts, &lay, "jb_batch_set_mix");
+    int rc = mix_layout_checked(prog_req.data(), prog_chained, n.data(), nullptr, B, elem, mixed() ? &mix_opts : nullptr,
+                                &lay, mixed() ? "jb_batch_set_mix" : "jb_batch_set_join");
     if (rc)
         return rc;
-    std::vector<MixMember> members;
-    mix_lists(lay, mix_req.data(), n.data(), xoff.data(), slab[(size_t)plan.join_src.slab], slab[(size_t)plan.join.slab],
-              elem, &members, &mx.spans.host, &mx.tiles);
-    MixMember *md = nullptr;
-    MixSeg *sd = nullptr;
-    uint32_t *ld = nullptr;
-    if ((rc = b.dalloc(&md, B, false)) || (rc = b.dalloc(&sd, lay.segs.size(), false)) ||
-        (rc = b.dalloc(&ld, lay.lists.size(), false)) || (rc = b.dalloc(&mx.L.tile_peak, mx.tiles * kMixWaves, false)) ||
-        (rc = b.dalloc(&mx.L.res, P, false)) || (rc = mx.spans.alloc(b, P, P)) ||
-        (rc = upload_list(md, members, "mix work list")) || (rc = upload_list(sd, lay.segs, "mix work list")) ||
-        (rc = upload_list(ld, lay.lists, "mix work list")))
+    mix_lists(lay, prog_req.data(), n.data(), xoff.data(), slab[(size_t)plan.join_src.slab], slab[(size_t)plan.join.slab],
+              elem, &pg.members, &pg.spans.host, &pg.tiles);
+    pg.member_at.assign(B, 0);
+    for (size_t i = 0; i < B; i++)
+        pg.member_at[lay.progs.members[i]] = (uint32_t)i;
+    ProgMember *md = nullptr;
+    // (a join's redo lists at most one span per member, a mix's one per programme)
+    if ((rc = b.dalloc(&md, B, false)) || (rc = pg.spans.alloc(b, P, mixed() ? P : B)) ||
+        (rc = upload_list(md, pg.members, mixed() ? "mix work list" : "join work list")))
         return rc;
-    mx.L.members = md;
-    mx.L.segs = sd;
-    mx.L.lists = ld;
-    mx.L.fit = (mix_opts.flags & kMixFit) != 0;
-    mx.L.ceiling = mx.L.fit ? mix_ceiling(mix_opts.ceiling_db) : 0.0;
-    return mx.spans.upload("mix work list");
-}
-
-// A redo runs every programme with a member whose final PCM changed again, whole: the sum, the peak and the fit
-int OutputChain::select_mix(const RedoScope *scope)
-{
-    if (!mixed() || !scope)
-        return mx.spans.take_all(mx.tiles);
-    std::vector<MixSpan> sub;
-    uint64_t tiles = 0;
-    for (size_t p = 0; p < scope->units.size(); p++) {
-        if (!scope->units[p])
-            continue;
-        sub.push_back(mx.spans.host[p]);
-        sub.back().t0 = tiles; // (pk0 stays: the programme's tiles in the peak scratch)
-        tiles += join_tiles(0, plan.units[p].n, plan.join.i16);
+    pg.L.members = md;
+    if (mixed()) { // (the join's kernel reads the members alone)
+        MixSeg *sd = nullptr;
+        uint32_t *ld = nullptr;
+        if ((rc = b.dalloc(&sd, lay.segs.size(), false)) || (rc = b.dalloc(&ld, lay.lists.size(), false)) ||
+            (rc = b.dalloc(&pg.L.tile_peak, pg.tiles * kMixWaves, false)) || (rc = b.dalloc(&pg.L.res, P, false)) ||
+            (rc = upload_list(sd, lay.segs, "mix work list")) || (rc = upload_list(ld, lay.lists, "mix work list")))
+            return rc;
+        pg.L.segs = sd;
+        pg.L.lists = ld;
+        pg.L.fit = (mix_opts.flags & kMixFit) != 0;
+        pg.L.ceiling = pg.L.fit ? mix_ceiling(mix_opts.ceiling_db) : 0.0;
     }
-    return mx.spans.upload_redo(sub, kRedoLists, tiles);
+    return pg.spans.upload(mixed() ? "mix work list" : "join work list");
 }
 
-int OutputChain::launch_mix(bool redo)
+// A redo of a mix runs every programme with a member whose final PCM changed again, whole: the sum, the peak and the
+// fit.  A redo of a join runs each changed member's own range alone, widened to whole groups of kProgGroupBytes (the
+// samples around it are what they were: its neighbours' current ones, and pads)
+int OutputChain::select_programme(const RedoScope *scope)
 {
-    if (!mixed() || (redo && !mx.spans.n))
+    if (!joined() || !scope)
+        return pg.spans.take_all(pg.tiles);
+    std::vector<ProgSpan> sub;
+    uint64_t tiles = 0;
+    auto take = [&](size_t p, uint64_t k0, uint64_t k1) {
+        sub.push_back(pg.spans.host[p]);
+        sub.back().k0 = k0;
+        sub.back().k1 = k1;
+        sub.back().t0 = tiles; // (pk0 stays: the programme's tiles in the peak scratch)
+        tiles += prog_tiles(k0, k1, plan.join.i16);
+    };
+    if (mixed()) {
+        for (size_t p = 0; p < scope->units.size(); p++)
+            if (scope->units[p])
+                take(p, 0, plan.units[p].n);
+    } else {
+        const std::vector<uint8_t> &mask = scope->post; // every utterance whose final PCM changed
+        const uint64_t gs = kProgGroupBytes / (plan.join.i16 ? sizeof(int16_t) : sizeof(double));
+        for (size_t u = 0; u < mask.size(); u++) {
+            if (!mask[u] || !plan.utt[u].n) // a member of zero samples wrote nothing into its programme: no span
+                continue;
+            const ProgMember &m = pg.members[pg.member_at[u]];
+            take(plan.prog_of[u], m.start / gs * gs,
+                 std::min<uint64_t>((m.start + m.n + gs - 1) / gs * gs, plan.units[plan.prog_of[u]].n));
+        }
+    }
+    return pg.spans.upload_redo(sub, kRedoLists, tiles);
+}
+
+int OutputChain::launch_programme(bool redo)
+{
+    if (!joined() || (redo && !pg.spans.n))
         return JB_OK;
-    const hipError_t e = jb::launch_mix(plan.join.i16, mx.spans.list, mx.spans.n, mx.spans.total, mx.L, b.stream_voc);
-    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_mix(redo)" : "k_mix");
+    const hipError_t e =
+        mixed() ? jb::launch_mix(plan.join.i16, pg.spans.list, pg.spans.n, pg.spans.total, pg.L, b.stream_voc)
+                : jb::launch_join(plan.join.i16, pg.spans.list, pg.spans.n, pg.spans.total, pg.L.members, b.stream_voc);
+    if (e == hipSuccess)
+        return JB_OK;
+    return mixed() ? hip_fail(e, redo ? "k_mix(redo)" : "k_mix") : hip_fail(e, redo ? "k_join(redo)" : "k_join");
 }
 
 // ---- FLAC.  The streams' lists and slabs: one stream per unit (an utterance; behind a join a programme) of the
@@ -1958,7 +1911,7 @@ int OutputChain::read_mix(size_t p, jb_mix_report *out)
         return JB_ERR_INVALID;
     }
     MixResult r{};
-    if ((rc = b.read(mx.L.res + p, &r, sizeof r)))
+    if ((rc = b.read(pg.L.res + p, &r, sizeof r)))
         return rc;
     *out = jb_mix_report{r.peak, r.scale, plan.mix_depth[p], 0, plan.mix_overlap[p]};
     return JB_OK;

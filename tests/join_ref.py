@@ -5,6 +5,10 @@ import numpy as np
 
 NONE = None  # an utterance of its own
 
+# member lengths around the 16-byte group and the tile, and pads: what the device tests join and the host tests lay out
+LENGTHS = [0, 1, 7, 8, 63, 64, 65, 4095, 4096, 4097]
+PADS = [0, 1, 3, 4097]
+
 
 def ms_to_samples(ms, hz):
     """floor(ms * hz / 1000.0 + 0.5); 0 for a negative duration"""

@@ -5,7 +5,9 @@
 //            the fields of tests/plan/adpcm_probe.cpp under the same names, then join_src, join, units (hz, n, off),
 //            prog_of, prog_start, prog_first, prog_members
 //   layout   elem B request[0..B) n[0..B) nh hz[0..nh)        (nh: 0 = rates not compared, or B)
-//            ok, bad, field, prog_of, start, units, total
+//            ok, bad, field, prog_of, start, units, total of the one layout (mix_layout over join_as_mix), the mix
+//            request the join means as `converted` (programme, start, gain_db, pad_after, fade_in, fade_out), and the
+//            work lists: seg_first, segs (k0, k1, l0, nl), lists (as utterance indices), depth, overlap
 //   closure  B request[0..B) ng group[0..ng) touched[0..B)   (ng: 0 = no loudness groups, or B; -1 = no group)
 //            post (the touched set behind loudness_groups_closure) and programmes (join_closure of it)
 // A request entry is: programme (-1 = none) pad_before pad_after fade_in fade_out.
@@ -143,15 +145,36 @@ static int layout()
         fprintf(stderr, "bad input\n");
         return 2;
     }
-    jb::JoinLayout lay;
+    // the join in the mix's words, through the one layout; `converted` is the mix request it means: the layout's starts
+    // in the place of the pads in front
+    std::vector<jb::MixUtt> mix = jb::join_as_mix(req.data(), B);
+    jb::MixLayout lay;
     uint32_t bad = 0;
     const char *field = "";
-    const bool ok = jb::join_layout(req.data(), n.data(), nh ? hz.data() : nullptr, B, elem, &lay, &bad, &field);
+    const bool ok = jb::mix_layout(mix.data(), n.data(), nh ? hz.data() : nullptr, B, elem, &lay, &bad, &field, true);
     printf("{\"ok\": %s, \"bad\": %lld, \"field\": \"%s\",", ok ? "true" : "false",
            bad == jb::kJoinNone ? -1ll : (long long)bad, field);
     list_of("prog_of", lay.progs.group_of, ",");
     list_of("start", lay.start, ",");
     units_of(lay.units, ",");
+    printf(" \"converted\": [");
+    for (size_t u = 0; ok && u < B; u++)
+        printf("%s[%lld, %llu, %.17g, %llu, %u, %u]", u ? ", " : "",
+               mix[u].programme == jb::kMixNone ? -1ll : (long long)mix[u].programme, (unsigned long long)lay.start[u],
+               mix[u].gain_db, (unsigned long long)mix[u].pad_after, mix[u].fade_in, mix[u].fade_out);
+    printf("],");
+    list_of("seg_first", lay.seg_first, ",");
+    printf(" \"segs\": [");
+    for (size_t i = 0; i < lay.segs.size(); i++)
+        printf("%s[%llu, %llu, %u, %u]", i ? ", " : "", (unsigned long long)lay.segs[i].k0,
+               (unsigned long long)lay.segs[i].k1, lay.segs[i].l0, lay.segs[i].nl);
+    printf("],");
+    std::vector<uint32_t> who;
+    for (uint32_t at : lay.lists)
+        who.push_back(lay.progs.members[at]);
+    list_of("lists", who, ",");
+    list_of("depth", lay.depth, ",");
+    list_of("overlap", lay.overlap, ",");
     printf(" \"total\": %llu}\n", (unsigned long long)lay.total);
     return 0;
 }

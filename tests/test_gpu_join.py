@@ -59,8 +59,7 @@ def check_seam(pcms, req):
     return got
 
 
-LENGTHS = [0, 1, 7, 8, 63, 64, 65, 4095, 4096, 4097]
-PADS = [0, 1, 3, 4097]
+LENGTHS, PADS = R.LENGTHS, R.PADS
 
 
 # ---- 1. the seam ----------------------------------------------------------------------------------------------------

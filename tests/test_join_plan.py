@@ -1,4 +1,4 @@
-"""The join stage in the output plan (jbonsai_amd/csrc/jb_output.h: plan_output, join_layout, join_closure) on the host,
+"""The join stage in the output plan (jbonsai_amd/csrc/jb_output.h: plan_output, mix_layout over join_as_mix, join_closure) on the host,
 without a GPU: over every row of the routing table the slab the stage reads and writes, the programmes (`units`), the
 members' starts, and the format and ADPCM geometry by programme; the numbering; the refusals; the redo closure; and,
 without a request, the plan as it was.  A probe of its own (tests/plan/join_probe.cpp), built the way
@@ -174,3 +174,105 @@ def test_empty_batch(probes):
     assert p["join"] == ["none", "-"] and p["units"] == []
     lay = run_layout(probes[0], [], [])
     assert lay["ok"] and lay["units"] == [] and lay["total"] == 0
+
+
+# ---- the join as the mix it means: one layout serves both (join_as_mix, then mix_layout with the starts chained) ------
+def fades_of(n):
+    return [0, 1, 2, n, n + 5]
+
+
+def conversion_cases():
+    """(name, request, lengths, elem): every row of the routing table (REQ6 over the lengths and the sample size of that
+    row), the LENGTHS x PADS list tests/test_gpu_join.py joins, members of no samples, and no programme ids at all."""
+    LENGTHS, PADS = R.LENGTHS, R.PADS
+    cases = []
+    for i16, rate, loudness in sorted(ROWS):
+        n = [ceil_div(k * 147, 160) for k in N6] if rate else list(N6)
+        cases.append((f"row-{int(i16)}{int(rate)}{int(loudness)}", REQ6, n, 2 if i16 else 8))
+    lengths = LENGTHS + LENGTHS[::-1]
+    grid = [(0, PADS[u % 4], PADS[(u // 4) % 4], fades_of(n)[u % 5], fades_of(n)[(u + 2) % 5])
+            for u, n in enumerate(lengths)]
+    for elem in (8, 2):
+        cases.append((f"lengths-pads-{elem}", grid, lengths, elem))
+        cases.append((f"lengths-pads-two-{elem}", [(u % 2,) + r[1:] for u, r in enumerate(grid)], lengths, elem))
+    cases.append(("empty-members", REQ6, [0] * 6, 8))
+    cases.append(("empty-members-no-pads", [(0,), (0,), (1,), (1,)], [0] * 4, 2))
+    cases.append(("all-none", [(None,) + r[1:] for r in REQ6], N6, 8))
+    cases.append(("all-none-grid", [(None,) + r[1:] for r in grid], lengths, 2))
+    return cases
+
+
+CASES = conversion_cases()
+
+
+@pytest.fixture(scope="module")
+def layouts(probes):
+    """Each case through the probe once: the layout, the converted request and the work lists"""
+    return {name: run_layout(probes[0], req, n, elem=elem) for name, req, n, elem in CASES}
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_a_join_is_the_mix_its_conversion_names(layouts, case):
+    """The converted request against the numpy statement (tests/join_ref.py): start = running end + pad_before in
+    programme order, 0 dB, fades and pad_after carried over.  jb_mix_geometry of it answers what jb_join_geometry
+    answers of the join, with depth at most 1 and no overlap.  (The starts of the converted request are the chained
+    layout's own: the conversion has no second loop to disagree with it, so this holds the layout's starts to the numpy
+    statement and everything else of the request to the join's fields.)"""
+    import jbonsai_amd as J
+
+    name, req, n, elem = case
+    lay = layouts[name]
+    assert lay["ok"]
+    full = [tuple(r) + (0,) * (5 - len(r)) for r in req]
+    progs, prog_of, start = R.join([[0] * k for k in n], req)
+    conv = [tuple(c) for c in lay["converted"]]
+    assert conv == [(-1 if r[0] is None else r[0], start[u], 0.0, r[2], r[3], r[4]) for u, r in enumerate(full)]
+    assert lay["prog_of"] == prog_of and [u[1] for u in lay["units"]] == [len(x) for x in progs]
+    as_mix = [(None if c[0] < 0 else c[0],) + c[1:] for c in conv]
+    jp, js, jn = J.join_geometry(req, n)
+    mp, ms, mn, depth, overlap = J.mix_geometry(as_mix, n)
+    assert (mp, ms, mn) == (jp, js, jn) == (prog_of, start, [len(x) for x in progs])
+    assert all(d <= 1 for d in depth) and overlap == [0] * len(progs)
+    assert depth == lay["depth"] and overlap == lay["overlap"]
+    assert depth == [int(any(n[u] for u in range(len(n)) if prog_of[u] == p)) for p in range(len(progs))]
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_segments_of_a_join_alternate_pad_member_pad(layouts, case):
+    """A programme's segments cover [0, n) without a hole; each is one member's own range or the silence between two;
+    a member of no samples and a pad of none leave no segment, and never two silences in a row."""
+    name, req, n, elem = case
+    lay = layouts[name]
+    first, segs, lists = lay["seg_first"], lay["segs"], lay["lists"]
+    assert len(first) == len(lay["units"]) + 1 and first[0] == 0 and first[-1] == len(segs)
+    listed = []
+    for p, (_, length, _) in enumerate(lay["units"]):
+        mine = segs[first[p]:first[p + 1]]
+        members = [u for u in range(len(n)) if lay["prog_of"][u] == p and n[u]]
+        k, want = 0, []  # the segments the members' ranges leave, in order
+        for u in members:
+            if lay["start"][u] > k:
+                want.append((k, lay["start"][u], None))
+            want.append((lay["start"][u], lay["start"][u] + n[u], u))
+            k = lay["start"][u] + n[u]
+        if length > k:
+            want.append((k, length, None))
+        got = []
+        for k0, k1, l0, nl in mine:
+            assert k0 < k1 and nl <= 1 and l0 + nl <= len(lists)
+            got.append((k0, k1, lists[l0] if nl else None))
+        assert got == want
+        assert not any(a[2] is None and b[2] is None for a, b in zip(got, got[1:]))
+        assert (got[0][0], got[-1][1]) == (0, length) if length else got == []
+        listed += members
+    assert lists == listed
+
+
+def test_a_join_too_long_to_lay_out_is_refused_by_the_layout(probes):
+    """What the one layout adds to the join: pads that carry a programme's length to 2^63 are a refusal naming the
+    utterance, not a wrapped length"""
+    lay = run_layout(probes[0], [(0, 2 ** 62, 2 ** 62), (0, 0, 0)], [10, 10])
+    assert (lay["ok"], lay["bad"], lay["field"]) == (False, 0, "length")
+    lay = run_layout(probes[0], [(0, 2 ** 62, 0), (0, 2 ** 62 - 20, 0)], [10, 10])
+    assert (lay["ok"], lay["bad"], lay["field"]) == (False, 1, "length")
+    assert run_layout(probes[0], [(0, 2 ** 62, 0), (0, 2 ** 62 - 40, 0)], [10, 10])["ok"]  # (the slab rounds up to 16 bytes)

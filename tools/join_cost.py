@@ -5,8 +5,9 @@
    a stage's own time is its step minus the plain step of the same source, medians over the rounds, modes alternating
    within a round (the stages run last on the vocoder's stream, nothing overlaps them).
 2. With --kernels DIR (the output directory of a `rocprofv3 --kernel-trace` run of `tools/join_cost.py --trace-run`, a
-   run of its own: one f64 batch with a loudness target, the join and k_format<S16>): the kernel times of k_join,
-   k_ln_apply and k_format on the same samples, and the ratio of k_join to k_ln_apply.
+   run of its own: one f64 batch with a loudness target, the join and k_format<S16>, then one 16-bit batch with the
+   join): the kernel times of the join's kernel by sample type, k_ln_apply and k_format on the same samples, and the
+   ratio of the join's kernel to k_ln_apply.
 3. With --bench-before / --bench-after (the JSON lines of plain bench.py runs, parent and this tree, alternating;
    several lines per file: the repeats): the step times side by side.
 
@@ -59,7 +60,22 @@ if args.trace_run:
         b.set_format("s16")
         for _ in range(3):
             b.run_timed()
+    with J.Batch(vi, utts, pdf_set=pset, pcm_i16=True) as b:
+        b.set_join(REQ)
+        for _ in range(3):
+            b.run_timed()
     sys.exit(0)
+
+
+def kernel_key(name):
+    """The kernels this tool compares, in a trace: k_join by sample type, k_ln_apply and k_format by name"""
+    if "k_join" in name:
+        return f"join kernel <{'f64' if '<double' in name else 'i16'}>"
+    for key in ("k_ln_apply", "k_format"):
+        if key in name:
+            return key
+    return None
+
 
 # name -> (16-bit sink, stage)
 MODES = {
@@ -112,19 +128,19 @@ for k, width in (("k_join<f64>", 8), ("k_join<i16>", 2)):
 if args.kernels:
     say()
     say("== kernel times (rocprofv3 --kernel-trace, a run of its own: one f64 batch with a loudness target, the join "
-        "and k_format<S16>; three steps) ==")
+        "and k_format<S16>, then one 16-bit batch with the join; three steps each) ==")
     f = glob.glob(os.path.join(args.kernels, "**", "*kernel_trace.csv"), recursive=True)[0]
     tot, cnt = {}, {}
     for r in csv.DictReader(open(f)):
-        k = r["Kernel_Name"]
-        for key in ("k_join", "k_ln_apply", "k_format"):
-            if key in k:
-                tot[key] = tot.get(key, 0.0) + (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
-                cnt[key] = cnt.get(key, 0) + 1
+        key = kernel_key(r["Kernel_Name"])
+        if key:
+            tot[key] = tot.get(key, 0.0) + (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
+            cnt[key] = cnt.get(key, 0) + 1
     for key in sorted(tot):
-        say(f"  {key:>12}: {tot[key] / cnt[key]:8.3f} ms per launch ({cnt[key]} launches)")
-    if "k_join" in tot and "k_ln_apply" in tot:
-        say(f"k_join<f64> / k_ln_apply<f64> = {(tot['k_join'] / cnt['k_join']) / (tot['k_ln_apply'] / cnt['k_ln_apply']):.2f}")
+        say(f"  {key:>18}: {tot[key] / cnt[key]:8.3f} ms per launch ({cnt[key]} launches)")
+    jk = "join kernel <f64>"
+    if jk in tot and "k_ln_apply" in tot:
+        say(f"join kernel <f64> / k_ln_apply<f64> = {(tot[jk] / cnt[jk]) / (tot['k_ln_apply'] / cnt['k_ln_apply']):.2f}")
 
 
 def bench_steps(path):

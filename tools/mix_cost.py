@@ -6,8 +6,9 @@
    second pass), and with k_format<S16>; a stage's own time is its step minus the plain step, medians over the rounds,
    modes alternating within a round (the stages run last on the vocoder's stream, nothing overlaps them).  The
    two-talker rates count the members read once per cover and the programme written once.
-2. With --kernels DIR (the output directory of a `rocprofv3 --kernel-trace --stats` run of `tools/mix_cost.py
-   --trace-run`, a run of its own): the kernel times of k_join, k_mix (both passes), k_mix_peak and k_format.
+2. With --kernels DIR (the output directory of a `rocprofv3 --kernel-trace` run of `tools/mix_cost.py
+   --trace-run`, a run of its own): the kernel times of the join's kernel, k_mix's sum pass
+   (by request) and fit pass, k_mix_peak and k_format.
 3. With --bench-before / --bench-after (the JSON lines of plain bench.py runs, parent and this tree, alternating): the
    step times side by side.
 
@@ -71,6 +72,20 @@ if args.trace_run:
                 b.run_timed()
     sys.exit(0)
 
+
+def kernel_key(name):
+    """The stage kernels of a trace by instantiation: k_join by sample type, k_mix's sum and fit passes by sample type,
+    and the others by name"""
+    ty = "f64" if "<double" in name else "i16" if "<short" in name else "?"
+    if "k_join" in name:
+        return f"join kernel <{ty}>"
+    if "k_mix_peak" in name:
+        return "k_mix_peak"
+    if "k_mix" in name:
+        return f"k_mix {'fit' if 'true>' in name else 'sum'} <{ty}>"
+    return "k_format" if "k_format" in name else None
+
+
 # name -> (stage, request, fit)
 MODES = {
     "f64 plain": (None, None, False),
@@ -108,7 +123,7 @@ own = {k: med[k] - med["f64 plain"] for k in MODES}
 say()
 if own["join 16 x 16"] > 0:
     ratio = own["mix, the join's geometry"] / own["join 16 x 16"]
-    say(f"k_mix on the join's geometry / k_join on the same members: {ratio:.2f} (the same bytes)")
+    say(f"the mix on the join's geometry / the join on the same members: {ratio:.2f} (the same bytes)")
 total = args.copies * n
 traffic = {
     "mix 128 x 2, half overlap": (total + (args.copies // 2) * (n + n // 2)) * 8,
@@ -122,19 +137,20 @@ say(f"the second pass that fit adds: {own['mix 128 x 2, full overlap, fit'] - ow
 
 if args.kernels:
     say()
-    say("== kernel times (rocprofv3 --kernel-trace --stats, a run of its own: the join with k_format<S16>, then the mix "
+    say("== kernel times (rocprofv3 --kernel-trace, a run of its own: the join with k_format<S16>, then the mix "
         "of the join's geometry, half overlap, full overlap with fit; two steps each) ==")
     f = glob.glob(os.path.join(args.kernels, "**", "*kernel_trace.csv"), recursive=True)[0]
-    tot, cnt = {}, {}
-    for r in csv.DictReader(open(f)):
-        k = r["Kernel_Name"]
-        for key in ("k_join", "k_mix_peak", "k_mix", "k_format"):
-            if key in k:
-                tot[key] = tot.get(key, 0.0) + (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
-                cnt[key] = cnt.get(key, 0) + 1
-                break
-    for key in sorted(tot):
-        say(f"  {key:>12}: {tot[key] / cnt[key]:8.3f} ms per launch ({cnt[key]} launches)")
+    runs = {}
+    for r in sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"])):
+        key = kernel_key(r["Kernel_Name"])
+        if key:
+            runs.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
+    for key in sorted(runs):
+        t = runs[key]
+        say(f"  {key:>18}: {sum(t) / len(t):8.3f} ms per launch ({len(t)} launches)")
+        if key.startswith("k_mix sum") and len(t) == 6:  # (in the order of the trace run, two steps each)
+            for i, shape in enumerate(("the join's geometry", "half overlap", "full overlap")):
+                say(f"  {'':>18}  {shape:>20}: {sum(t[2 * i:2 * i + 2]) / 2:8.3f} ms per launch")
 
 
 def bench_steps(path):
