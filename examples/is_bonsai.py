@@ -5,7 +5,7 @@
                                  [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]] [--mfcc OUT.npy [--rate HZ]] [--kaldi]
                                  [--melspec OUT.npy [--whisper | --rate HZ]]
                                  [--fir taps.npy [--fir-delay D]] [--noise bed.npy|white --snr DB [--snr-active]]
-                                 [--room LX,LY,LZ --rt60 S [--room-taps K]]
+                                 [--room LX,LY,LZ --rt60 S [--room-taps K]] [--activity OUT.npy [--rate HZ]]
 
 Mirrors examples/is-bonsai/main.rs of jbonsai: Engine::load, Engine::synthesize, then the 16-bit mono
 WAV the example writes with hound (clamp to i16, truncate).  Needs an MI355X: the library has no CPU path.
@@ -46,6 +46,10 @@ at --rate if given; with --whisper it is Whisper's own front end (400 / 160 samp
 sentence's maximum, (y + 4) / 4: what log_mel_spectrogram gives before its padding to 30 s).  Saved the same way.
 With --limiter (and --loudness) the gain may put the highest peak that many dB over the ceiling and a look-ahead limiter
 on the GPU holds the ceiling (Engine.set_limiter): the target is reached where the peak alone stood in the way.
+With --activity the sentence's per-frame speech-activity labels on --fbank's frame grid (25 ms windows every 10 ms; 1 =
+the frame's energy lies within 40 dB of the loudest frame's, pauses of up to 200 ms closed) are measured on the GPU in
+the run that makes the PCM (Engine.synthesize_programme_activity), at --rate if given, and saved as a .npy file of uint8
+[T, 1]: the mask that says which of --fbank's frames hold speech.  The WAV file is written as usual.
 """
 import argparse
 import os
@@ -84,6 +88,7 @@ ap.add_argument("--room-taps", type=int, default=0, metavar="K", help="taps of -
 ap.add_argument("--noise", default=None, metavar="bed.npy|white", help="background noise, added on the GPU at --snr")
 ap.add_argument("--snr", type=float, default=15.0, metavar="DB", help="speech power over added-noise power")
 ap.add_argument("--snr-active", action="store_true", help="the speech power of the active tiles, not of the whole signal")
+ap.add_argument("--activity", default=None, metavar="OUT.npy", help="per-frame speech-activity labels, measured on the GPU")
 ap.add_argument("--limiter", type=float, default=None, metavar="DB",
                 help="look-ahead limiter on the GPU: dB the gain may put the highest peak over the ceiling (with --loudness)")
 args = ap.parse_args()
@@ -135,6 +140,20 @@ if args.programme:
     print("each sentence alone: " + ", ".join(f"{v:.2f} LUFS" for v in rep["lufs"]))
     J.write_wav(out, np.concatenate(parts), hz)
     print(f"wrote {out}")
+    sys.exit(0)
+if args.activity:
+    import numpy as np
+
+    if args.rate:
+        engine.condition.set_output_sampling_frequency(args.rate)
+    hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
+    pcm, labels, _ = engine.synthesize_programme_activity([SAMPLE_SENTENCE_2], J.activity(25, 10, gate_db=40, min_gap=20))
+    np.save(args.activity, labels)
+    on = np.flatnonzero(labels[:, 0])
+    print(f"wrote {args.activity}: {labels.shape[0]} frames, {on.size} active, the first {on[0] if on.size else '-'} and "
+          f"the last {on[-1] if on.size else '-'}")
+    J.write_wav(out, pcm, hz)
+    print(f"wrote {out}: {pcm.size} samples at {hz} Hz")
     sys.exit(0)
 if args.fbank:
     import numpy as np

@@ -5,6 +5,7 @@ start of its own and under a gain of its own, summed on the GPU.
                                --start-ms MS,MS,... [--gain-db DB,DB,...] [--fit [--ceiling DBFS]]
                                [--lead-ms MS] [--trail-ms MS] [--fade-ms MS] [--rate HZ]
                                [--room LX,LY,LZ --rt60 S [--vary]] [--stems DIR]
+                               [--activity labels.npy] [--rttm out.rttm] [--gate-db DB]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
 batch and mixed on the GPU (Engine.set_programme_mix, then Engine.synthesize_programme) in front of the encoder, so a
@@ -15,6 +16,10 @@ written as a 16-bit WAV file.  --start-ms and --gain-db take one value per sente
 from a position of their own (Engine.set_room with vary=True).  With --stems the members' own 16-bit PCM, as it went into
 the sum, is written beside the mixture (s0.wav, s1.wav, ...).  The cue list -- each sentence's first sample and time
 within the mixture -- and the stage's report (the host rule over the stems: the same numbers) are printed.
+With --activity the per-frame speech-activity labels of the talkers, a uint8 matrix [frames][talkers] at 25 / 10 ms
+measured on the GPU in a run of the same mixture (Engine.synthesize_programme_activity: a gate --gate-db under each
+talker's loudest frame, pauses of up to 200 ms closed, 20 ms of hang at both ends), are saved as a .npy file; with --rttm
+the runs of each column are written as RTTM lines, `SPEAKER <name> 1 <start> <dur> <NA> <NA> spk<j> <NA> <NA>`.
 Needs an MI355X: the library has no CPU path.
 """
 import argparse
@@ -45,6 +50,9 @@ ap.add_argument("--room", default=None, metavar="LX,LY,LZ", help="edges of a sim
 ap.add_argument("--rt60", type=float, default=0.5, metavar="S", help="reverberation time of --room")
 ap.add_argument("--vary", action="store_true", help="with --room: every talker at a position of their own")
 ap.add_argument("--stems", default=None, metavar="DIR", help="write the members' 16-bit PCM there")
+ap.add_argument("--activity", default=None, metavar="NPY", help="save the talkers' per-frame activity labels there")
+ap.add_argument("--rttm", default=None, metavar="RTTM", help="write the talkers' active runs there as RTTM lines")
+ap.add_argument("--gate-db", type=float, default=40.0, help="the activity gate under each talker's loudest frame")
 args = ap.parse_args()
 gains = args.gain_db or [0.0] * len(args.labels)
 if len(args.start_ms) != len(args.labels) or len(gains) != len(args.labels):
@@ -89,3 +97,24 @@ if args.stems:
     os.makedirs(args.stems, exist_ok=True)
     for k, x in enumerate(stems):
         J.write_wav(os.path.join(args.stems, f"s{k}.wav"), x, hz)
+if args.activity or args.rttm:
+    import numpy as np
+
+    hop_ms = 10.0
+    _, labels, _ = engine.synthesize_programme_activity(
+        sentences, J.activity(25, hop_ms, gate_db=args.gate_db, grid="center", min_gap=20, hang_before=2, hang_after=2),
+        lead_ms=args.lead_ms, trail_ms=args.trail_ms, fade_ms=args.fade_ms, mix=place, fit=args.fit,
+        ceiling_db=args.ceiling)
+    k = labels.sum(axis=1)
+    print(f"activity {labels.shape[0]} frames by {labels.shape[1]} talkers: {int((k == 0).sum())} silent, "
+          f"{int((k == 1).sum())} under one talker, {int((k >= 2).sum())} overlapped")
+    if args.activity:
+        np.save(args.activity, labels)
+    if args.rttm:
+        name = os.path.splitext(os.path.basename(args.out))[0]
+        with open(args.rttm, "w") as f:
+            for j in range(labels.shape[1]):
+                edges = np.flatnonzero(np.diff(np.concatenate(([0], labels[:, j], [0]))))
+                for a, b in zip(edges[::2], edges[1::2]):  # frames [a, b) are active
+                    f.write(f"SPEAKER {name} 1 {a * hop_ms / 1000:.3f} {(b - a) * hop_ms / 1000:.3f} <NA> <NA> spk{j} "
+                            "<NA> <NA>\n")

@@ -1380,6 +1380,128 @@ int jb_mix_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n,
                          jb_mix_report *reports);
 void jb_mix_free(void *p);
 
+/* ---- Speech activity (new: the reference has no such output) ---------------------------------------------------------
+ * Per-frame 0/1 labels on the frame grid of the feature stages, one column per talker: what an RTTM file or an
+ * EEND-style [T][speakers] target holds, measured on the device so that the stems need not cross the link.  The rule
+ * (jbonsai_amd/csrc/jb_activity.h states it once for the host and the device):
+ * - A unit is an utterance, or a programme of a join or mix request.  Each unit gets a row-major uint8 matrix [T][C].
+ * - Columns.  JB_ACTIVITY_MEMBERS: C = the programme's members in ascending utterance index; column j is measured on
+ *   member j's own PCM before fade and gain (the gate is relative), placed at its start, reading 0 outside
+ *   [start_j, start_j + n_j); a muted member (gain_db == -INFINITY) keeps its column, all zeros.  JB_ACTIVITY_UNIT:
+ *   C = 1, measured on the unit's own PCM (the programme, or the utterance).  Without a programme the two are the same.
+ * - Grid.  wl and hop are win_us and hop_us rounded at the unit's rate as the filterbank stage rounds them
+ *   (floor(hz us / 10^6 + 1/2)); with JB_ACTIVITY_SAMPLES they are samples as given.  wl in 2..4096, hop >= 1.  For a
+ *   unit of n >= 1 samples frame t starts at s_t:
+ *     JB_ACTIVITY_SNIP    T = n >= wl ? 1 + (n - wl) / hop : 0   s_t = t hop                     (plain fbank)
+ *     JB_ACTIVITY_CENTER  T = ceil(n / hop)                      s_t = t hop - wl / 2            (JB_FBANK_CENTER)
+ *     JB_ACTIVITY_KALDI   T = (n + hop / 2) / hop                s_t = t hop + hop / 2 - wl / 2  (JB_FRAME_REFLECT)
+ *     JB_ACTIVITY_STFT    T = 1 + n / hop                        s_t = t hop - wl / 2            (melspec, no drop-last)
+ *   Samples outside the unit read as 0 (no reflection: a mirrored edge would invent energy).  n == 0: T = 0.
+ * - Energy.  E[j][t] = sum over i < wl of v_i v_i, v_i column j's sample at s_t + i (16 bits enter as their (double)),
+ *   summed as the frame conditioning's step 2 sums: 64 strided partials from 0.0, folded 32, 16, .., 1; products are
+ *   rounded, then added (no fma).  A zero term leaves a partial's bits alone, so a frame that touches no sample of the
+ *   member is exactly +0.0 and the result does not depend on how samples outside a member are skipped.
+ * - Gate.  A frame is raw-active iff E > 0 and E >= thr.  JB_ACTIVITY_REF_PEAK: thr = q max_t E[j][t] with
+ *   q = 10^(-gate_db / 10) formed in long double and rounded once.  JB_ACTIVITY_REF_ABS: thr = wl 32768^2
+ *   10^(-gate_db / 10), rounded once from long double: a level in dBFS, the mode for stems that carry noise.
+ *   gate_db in [1, 120].
+ * - Smoothing, three integer steps on a column's raw bits in this order, lengths in frames, each in 0..65535.
+ *   Close (min_gap): an inactive frame becomes active iff the nearest raw-active frames a in front and b behind exist
+ *   with b - a - 1 <= min_gap (gaps at the head and the tail of the unit are never closed).  Open (min_speech): every
+ *   run of active frames shorter than min_speech is cleared (a run cut by the unit's edge counts as long as is
+ *   visible).  Hang: frame t is active iff a surviving frame s has s - hang_before <= t <= s + hang_after.  All four
+ *   at 0: the raw bits.
+ * - On the device (jb_activity.hip): k_act_energy stages a run of frames' samples in LDS once and sums each frame on
+ *   one wave, storing per member only the frames that touch it and an integer atomic maximum of the bit patterns per
+ *   column; k_act_label, one wave per column, packs the raw bits 64 to a word by ballot, runs the smoothing steps on the
+ *   words with a wave scan across them, stores the bytes and the column's report; k_act_unit counts the rows.
+ * Not covered: measuring in front of the noise stage (with a noise request the stems carry the noise: take
+ * JB_ACTIVITY_REF_ABS or a gate above the floor), trimming, labels from the HMM alignment, packed-bit output, and any
+ * claim of equality with Kaldi's or WebRTC's detectors. */
+#define JB_ACTIVITY_SNIP 0u
+#define JB_ACTIVITY_CENTER 1u
+#define JB_ACTIVITY_KALDI 2u
+#define JB_ACTIVITY_STFT 3u
+#define JB_ACTIVITY_REF_PEAK 0u
+#define JB_ACTIVITY_REF_ABS 1u
+#define JB_ACTIVITY_MEMBERS 0u
+#define JB_ACTIVITY_UNIT 1u
+#define JB_ACTIVITY_SAMPLES 1u
+/* T * C of a unit and the label bytes of a call may not pass this (JB_ERR_UNSUPPORTED): 256 members by 3.27 million
+ * frames pass.  A chapter of hundreds of members takes JB_ACTIVITY_UNIT. */
+#define JB_ACTIVITY_MAX_CELLS (1ull << 30)
+typedef struct jb_activity_opts {
+    uint32_t win_us, hop_us; /* microseconds; samples with JB_ACTIVITY_SAMPLES */
+    double gate_db;          /* [1, 120] */
+    uint32_t grid;           /* JB_ACTIVITY_SNIP, _CENTER, _KALDI, _STFT */
+    uint32_t reference;      /* JB_ACTIVITY_REF_PEAK, _REF_ABS */
+    uint32_t columns;        /* JB_ACTIVITY_MEMBERS, _UNIT */
+    uint32_t flags;          /* JB_ACTIVITY_SAMPLES or 0 */
+    uint32_t min_speech, min_gap, hang_before, hang_after; /* frames, 0..65535 */
+    uint32_t reserved[4];
+} jb_activity_opts;
+/* A column's report. */
+typedef struct jb_activity_report {
+    uint64_t active;      /* active frames */
+    uint64_t first, last; /* the first and the last active frame; T where there is none */
+    double peak;          /* the largest energy of the column */
+    double thr;           /* the threshold its frames were held to */
+} jb_activity_report;
+/* A unit's report. */
+typedef struct jb_activity_unit_report {
+    uint64_t frames;          /* T */
+    uint64_t none, one, many; /* frames under 0, exactly 1, and 2 or more active columns */
+} jb_activity_unit_report;
+/* New (none).  The window, the hop and T of a unit of n samples at hz under opts (each out pointer may be NULL).
+ * Refused with JB_ERR_INVALID naming the field: an unknown grid, reference, columns or flag, a non-zero reserved
+ * word, a gate_db or a length outside its range, a window or hop outside its limits at hz. */
+int jb_activity_geometry(const jb_activity_opts *opts, uint32_t hz, size_t n, uint32_t *wl, uint32_t *hop, uint64_t *T);
+/* New (none).  The rule over one column in plain C++ on the host: x[0..n) is the unit, out[T] its labels (cap below T:
+ * JB_ERR_BUFFER); report may be NULL.  `columns` is not read. */
+int jb_activity_host(const double *x, size_t n, uint32_t hz, const jb_activity_opts *opts, uint8_t *out, size_t cap,
+                     jb_activity_report *report);
+/* New (none).  The rule over one unit of n_unit samples from its m members, on the host: member j holds in[j][0..n_in[j])
+ * at start[j] (start[j] + n_in[j] above n_unit: JB_ERR_INVALID), muted where gain_db (may be NULL) has -INFINITY.
+ * out: [T][m] (cap below T m: JB_ERR_BUFFER); cols (may be NULL): [m]; unit may be NULL.  opts->columns must be
+ * JB_ACTIVITY_MEMBERS. */
+int jb_activity_members_host(const double *const *in, const size_t *n_in, const uint64_t *start, const double *gain_db,
+                             size_t m, uint64_t n_unit, uint32_t hz, const jb_activity_opts *opts, uint8_t *out,
+                             size_t cap, jb_activity_report *cols, jb_activity_unit_report *unit);
+/* New (none).  The stage on PCM the caller holds, on `device` (-1 = current).  Members, starts and programmes are given
+ * as for jb_mix_pcm_batch; req == NULL: every utterance is a unit of its own.  hz: [n] each utterance's rate (a
+ * programme's members must agree; may be NULL with JB_ACTIVITY_SAMPLES).  With JB_ACTIVITY_UNIT a programme is mixed
+ * first (under mix_opts, may be NULL) and its column measured on the mixture.  out, T and C have n entries, the first
+ * *n_units written: out[p] = unit p's [T[p]][C[p]] matrix, library-owned (jb_activity_free each).  cols (may be NULL):
+ * [n], the columns' reports unit after unit; units (may be NULL): [n], the first *n_units written. */
+int jb_activity_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                          const jb_mix_opts *mix_opts, const uint32_t *hz, const jb_activity_opts *opts, int32_t device,
+                          uint8_t **out, uint64_t *T, uint32_t *C, size_t *n_units, jb_activity_report *cols,
+                          jb_activity_unit_report *units);
+int jb_activity_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                              const jb_mix_opts *mix_opts, const uint32_t *hz, const jb_activity_opts *opts,
+                              int32_t device, uint8_t **out, uint64_t *T, uint32_t *C, size_t *n_units,
+                              jb_activity_report *cols, jb_activity_unit_report *units);
+void jb_activity_free(void *p);
+/* New (none).  The stage in a batch: a side output beside whatever sinks the batch has, f64 or JB_BATCH_PCM_I16.  The
+ * units are the batch's outputs (jb_batch_num_outputs): the programmes of a join or mix request, or the utterances.
+ * Column j of a programme is its j-th member in ascending utterance index, measured on the PCM jb_batch_read_pcm hands
+ * out, at jb_batch_member_start; JB_ACTIVITY_UNIT measures what jb_batch_read_programme_pcm hands out.  Checked at
+ * every unit's rate and against JB_ACTIVITY_MAX_CELLS under the present requests (JB_ERR_INVALID naming the unit and
+ * the field, JB_ERR_UNSUPPORTED past the cap), and again at the first run where a rate or a programme request came
+ * behind it.  opts == NULL withdraws the request.  Only before the batch's first run.  A redo round measures every
+ * unit with a rewritten member again, whole.  Without the request no kernel, list or allocation is added. */
+int jb_batch_set_activity(jb_batch *b, const jb_activity_opts *opts);
+/* New (none).  T, C and the rate of unit `unit` (each may be NULL), known once the request is made; its bytes T * C. */
+int jb_batch_activity_shape(jb_batch *b, size_t unit, uint64_t *T, uint32_t *C, uint32_t *hz);
+int jb_batch_activity_size(jb_batch *b, size_t unit, size_t *n_bytes);
+/* New (none).  After the run: unit `unit`'s [T][C] labels into dst[0 .. cap) (JB_ERR_BUFFER if cap is below T * C); and
+ * every unit's labels, dst[u] sized by jb_batch_activity_size, in one device-to-host copy for the batch. */
+int jb_batch_read_activity(jb_batch *b, size_t unit, uint8_t *dst, size_t cap);
+int jb_batch_read_activity_all(jb_batch *b, uint8_t *const *dst);
+/* New (none).  After the run: the report of column `col` of unit `unit`, and the unit's. */
+int jb_batch_activity_report(jb_batch *b, size_t unit, size_t col, jb_activity_report *out);
+int jb_batch_activity_unit_report(jb_batch *b, size_t unit, jb_activity_unit_report *out);
+
 /* ---- Filter (new: the reference has no such control) ---------------------------------------------------------------
  * A caller-chosen cascade of up to four second-order sections shapes the PCM on the device, at the output rate: behind
  * the converter (or the vocoder at the native rate) and in front of the loudness measurement, so that the target, the
@@ -2248,6 +2370,14 @@ int jb_synthesize_programme(const jb_engine *e, const char *const *label_lines, 
 int jb_synthesize_programme_i16(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
                                 size_t n_utts, int32_t device, const jb_join_opts *join, int16_t **pcm,
                                 size_t *n_samples, uint64_t *starts);
+/* New (none).  jb_synthesize_programme with the programme's speech-activity labels ("Speech activity" above) beside its
+ * f64 PCM, from the same run: *labels is the [*T][*C] matrix (library-owned: jb_activity_free), with
+ * JB_ACTIVITY_MEMBERS one column per utterance of the call, placed at starts[u].  While jb_engine_set_programme_mix is
+ * set the programme is a mix, as in every programme entry.  opts is checked before any device is touched. */
+int jb_synthesize_programme_activity(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                     size_t n_utts, int32_t device, const jb_join_opts *join,
+                                     const jb_activity_opts *opts, double **pcm, size_t *n_samples, uint8_t **labels,
+                                     uint64_t *T, uint32_t *C, uint64_t *starts);
 int jb_synthesize_programme_flac_meta(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
                                       size_t n_utts, int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta,
                                       const jb_join_opts *join, uint8_t **flac, size_t *n_bytes, uint64_t *starts);
@@ -2354,6 +2484,16 @@ JB_LAYOUT_ASSERT(sizeof(jb_mix_report) == 32 && offsetof(jb_mix_report, scale) =
                      offsetof(jb_mix_report, depth) == 16 && offsetof(jb_mix_report, overlap) == 24,
                  "jb_mix_report");
 JB_LAYOUT_ASSERT(sizeof(jb_mix_place) == 16 && offsetof(jb_mix_place, gain_db) == 8, "jb_mix_place");
+JB_LAYOUT_ASSERT(sizeof(jb_activity_opts) == 64 && offsetof(jb_activity_opts, gate_db) == 8 &&
+                     offsetof(jb_activity_opts, grid) == 16 && offsetof(jb_activity_opts, flags) == 28 &&
+                     offsetof(jb_activity_opts, min_speech) == 32 && offsetof(jb_activity_opts, reserved) == 48,
+                 "jb_activity_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_activity_report) == 40 && offsetof(jb_activity_report, first) == 8 &&
+                     offsetof(jb_activity_report, peak) == 24 && offsetof(jb_activity_report, thr) == 32,
+                 "jb_activity_report");
+JB_LAYOUT_ASSERT(sizeof(jb_activity_unit_report) == 32 && offsetof(jb_activity_unit_report, none) == 8 &&
+                     offsetof(jb_activity_unit_report, many) == 24,
+                 "jb_activity_unit_report");
 JB_LAYOUT_ASSERT(sizeof(jb_join_opts) == 40 && offsetof(jb_join_opts, fade_ms) == 24 &&
                      offsetof(jb_join_opts, reserved) == 32, "jb_join_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_loudness_report) == 40 && offsetof(jb_loudness_report, gain_db) == 24 &&

@@ -14,6 +14,9 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    JOIN_NONE, JoinUtt, join_geometry, join_host, join_ms_to_samples, join_pcm,
                    MIX_NONE, MIX_FIT, MixUtt, MixOpts, MixReport, MixPlace, mix_opts, mix_geometry, mix_gain, mix_host,
                    mix_pcm,
+                   ACTIVITY_SNIP, ACTIVITY_CENTER, ACTIVITY_KALDI, ACTIVITY_STFT, ACTIVITY_REF_PEAK, ACTIVITY_REF_ABS,
+                   ACTIVITY_MEMBERS, ACTIVITY_UNIT, ACTIVITY_SAMPLES, ACTIVITY_MAX_CELLS, ActivityOpts, ActivityReport,
+                   ActivityUnitReport, activity, activity_geometry, activity_host, activity_members_host, activity_pcm,
                    Filter, FilterSection, Biquad, filter_design, filter_sos, filter_pcm, filter_pcm_host, highpass,
                    lowpass, peaking, lowshelf, highshelf, notch, raw_filter, telephone_band, no_filter,
                    Fir, fir, fir_geometry, fir_host, fir_pcm, FIR_MAX_TAPS, FIR_DIRECT_MAX, FIR_DIRECT, FIR_PARTITIONED,
@@ -52,7 +55,10 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "synthesize_batch_each_adpcm", "loudness_groups", "loudness_gate_host", "LOUDNESS_NO_GROUP", "LOUDNESS_R128", "LOUDNESS_PER_UTTERANCE",
            "LOUDNESS_PER_REQUEST", "JOIN_NONE", "JoinUtt", "join_geometry", "join_host", "join_ms_to_samples",
            "join_pcm", "MIX_NONE", "MIX_FIT", "MixUtt", "MixOpts", "MixReport", "MixPlace", "mix_opts", "mix_geometry",
-           "mix_gain", "mix_host", "mix_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",
+           "mix_gain", "mix_host", "mix_pcm", "ACTIVITY_SNIP", "ACTIVITY_CENTER", "ACTIVITY_KALDI", "ACTIVITY_STFT",
+           "ACTIVITY_REF_PEAK", "ACTIVITY_REF_ABS", "ACTIVITY_MEMBERS", "ACTIVITY_UNIT", "ACTIVITY_SAMPLES",
+           "ACTIVITY_MAX_CELLS", "ActivityOpts", "ActivityReport", "ActivityUnitReport", "activity", "activity_geometry",
+           "activity_host", "activity_members_host", "activity_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",
            "filter_pcm_host", "highpass", "lowpass", "peaking", "lowshelf", "highshelf", "notch", "raw_filter",
            "telephone_band", "no_filter", "Fir", "fir", "fir_geometry", "fir_host", "fir_pcm", "FIR_MAX_TAPS",
            "FIR_DIRECT_MAX", "FIR_DIRECT", "FIR_PARTITIONED", "Noise", "NoiseReport", "noise", "noise_host",

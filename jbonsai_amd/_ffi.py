@@ -465,6 +465,53 @@ def mix_request(req):
     return arr
 
 
+ACTIVITY_SNIP, ACTIVITY_CENTER, ACTIVITY_KALDI, ACTIVITY_STFT = range(4)
+ACTIVITY_REF_PEAK, ACTIVITY_REF_ABS = 0, 1
+ACTIVITY_MEMBERS, ACTIVITY_UNIT = 0, 1
+ACTIVITY_SAMPLES = 1
+ACTIVITY_MAX_CELLS = 1 << 30
+_ACTIVITY_GRIDS = {"snip": ACTIVITY_SNIP, "center": ACTIVITY_CENTER, "kaldi": ACTIVITY_KALDI, "stft": ACTIVITY_STFT}
+_ACTIVITY_REFS = {"peak": ACTIVITY_REF_PEAK, "abs": ACTIVITY_REF_ABS}
+_ACTIVITY_COLUMNS = {"members": ACTIVITY_MEMBERS, "unit": ACTIVITY_UNIT}
+
+
+class ActivityOpts(C.Structure):
+    """jb_activity_opts: the frame grid, the gate and the smoothing lengths of a speech-activity request."""
+    _fields_ = [("win_us", C.c_uint32), ("hop_us", C.c_uint32), ("gate_db", C.c_double), ("grid", C.c_uint32),
+                ("reference", C.c_uint32), ("columns", C.c_uint32), ("flags", C.c_uint32), ("min_speech", C.c_uint32),
+                ("min_gap", C.c_uint32), ("hang_before", C.c_uint32), ("hang_after", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class ActivityReport(C.Structure):
+    """jb_activity_report: a column's active frames, its first and last one (T: none), its largest energy, its thr."""
+    _fields_ = [("active", C.c_uint64), ("first", C.c_uint64), ("last", C.c_uint64), ("peak", C.c_double),
+                ("thr", C.c_double)]
+
+
+class ActivityUnitReport(C.Structure):
+    """jb_activity_unit_report: T and the frames under 0, exactly 1, and 2 or more active columns."""
+    _fields_ = [("frames", C.c_uint64), ("none", C.c_uint64), ("one", C.c_uint64), ("many", C.c_uint64)]
+
+
+def activity(win_ms=25, hop_ms=10, gate_db=40, grid="snip", reference="peak", columns="members", min_speech=0, min_gap=0,
+             hang_before=0, hang_after=0, samples=False):
+    """An ActivityOpts: window and hop in milliseconds (samples=True: in samples, as melspec takes them), the gate in dB
+    under the column's largest frame energy (reference="peak") or under full scale (reference="abs"), the grid by name
+    ("snip", "center", "kaldi", "stft") or constant, and the smoothing lengths in frames."""
+    o = ActivityOpts()
+    if samples:
+        o.win_us, o.hop_us, o.flags = int(win_ms), int(hop_ms), ACTIVITY_SAMPLES
+    else:
+        o.win_us, o.hop_us = int(round(win_ms * 1000)), int(round(hop_ms * 1000))
+    o.gate_db = float(gate_db)
+    o.grid = _ACTIVITY_GRIDS.get(grid, grid)
+    o.reference = _ACTIVITY_REFS.get(reference, reference)
+    o.columns = _ACTIVITY_COLUMNS.get(columns, columns)
+    o.min_speech, o.min_gap, o.hang_before, o.hang_after = int(min_speech), int(min_gap), int(hang_before), int(hang_after)
+    return o
+
+
 FILTER_MAX_SECTIONS = 4
 FILTER_HIGHPASS, FILTER_LOWPASS, FILTER_PEAKING, FILTER_LOWSHELF, FILTER_HIGHSHELF, FILTER_NOTCH, FILTER_RAW = range(1, 8)
 
@@ -856,6 +903,10 @@ SYMBOLS = [
     "jb_batch_set_mix", "jb_batch_mix_report", "jb_mix_gain", "jb_mix_geometry", "jb_mix_host", "jb_mix_i16_host",
     "jb_mix_pcm_batch", "jb_mix_pcm_batch_i16", "jb_mix_free", "jb_engine_set_programme_mix",
     "jb_engine_get_programme_mix",
+    "jb_activity_geometry", "jb_activity_host", "jb_activity_members_host", "jb_activity_pcm_batch",
+    "jb_activity_pcm_batch_i16", "jb_activity_free", "jb_batch_set_activity", "jb_batch_activity_shape",
+    "jb_batch_activity_size", "jb_batch_read_activity", "jb_batch_read_activity_all", "jb_batch_activity_report",
+    "jb_batch_activity_unit_report", "jb_synthesize_programme_activity",
     "jb_batch_set_filter", "jb_batch_filter_coefficients", "jb_filter_design", "jb_filter_pcm_host",
     "jb_filter_pcm_batch", "jb_filter_pcm_batch_i16", "jb_filter_free", "jb_engine_set_filter", "jb_engine_get_filter",
     "jb_batch_set_fir", "jb_batch_fir_geometry", "jb_engine_set_fir", "jb_fir_host", "jb_fir_geometry",
@@ -1213,6 +1264,23 @@ def lib():
     L.jb_mix_free.restype = None
     L.jb_engine_set_programme_mix.argtypes = [vp, C.POINTER(MixPlace), sz, mxop]
     L.jb_engine_get_programme_mix.argtypes = [vp, C.POINTER(MixPlace), sz, C.POINTER(sz), mxop]
+    acop, acrp, acup = C.POINTER(ActivityOpts), C.POINTER(ActivityReport), C.POINTER(ActivityUnitReport)
+    L.jb_activity_geometry.argtypes = [acop, C.c_uint32, sz, u32p, u32p, u64p]
+    L.jb_activity_host.argtypes = [vp, sz, C.c_uint32, acop, vp, sz, acrp]
+    L.jb_activity_members_host.argtypes = [C.POINTER(vp), C.POINTER(sz), u64p, C.POINTER(C.c_double), sz, C.c_uint64,
+                                           C.c_uint32, acop, vp, sz, acrp, acup]
+    L.jb_activity_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, mxup, mxop, u32p, acop, C.c_int32,
+                                        C.POINTER(vp), u64p, u32p, C.POINTER(sz), acrp, acup]
+    L.jb_activity_pcm_batch_i16.argtypes = L.jb_activity_pcm_batch.argtypes
+    L.jb_activity_free.argtypes = [vp]
+    L.jb_activity_free.restype = None
+    L.jb_batch_set_activity.argtypes = [vp, acop]
+    L.jb_batch_activity_shape.argtypes = [vp, sz, u64p, u32p, u32p]
+    L.jb_batch_activity_size.argtypes = [vp, sz, C.POINTER(sz)]
+    L.jb_batch_read_activity.argtypes = [vp, sz, vp, sz]
+    L.jb_batch_read_activity_all.argtypes = [vp, C.POINTER(vp)]
+    L.jb_batch_activity_report.argtypes = [vp, sz, sz, acrp]
+    L.jb_batch_activity_unit_report.argtypes = [vp, sz, acup]
     flp, bqp = C.POINTER(Filter), C.POINTER(Biquad)
     L.jb_batch_set_filter.argtypes = [vp, flp, sz]
     L.jb_batch_filter_coefficients.argtypes = [vp, sz, bqp, u32p]
@@ -1279,6 +1347,8 @@ def lib():
     lines, szp = C.POINTER(C.c_char_p), C.POINTER(sz)
     L.jb_synthesize_programme.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
     L.jb_synthesize_programme_i16.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
+    L.jb_synthesize_programme_activity.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(ActivityOpts),
+                                                   C.POINTER(vp), szp, C.POINTER(vp), u64p, u32p, u64p]
     L.jb_synthesize_programme_flac_meta.argtypes = [vp, lines, szp, sz, C.c_int32, C.POINTER(FlacOpts),
                                                     C.POINTER(FlacMeta), jop, C.POINTER(u8p), szp, u64p]
     L.jb_synthesize_programme_formatted.argtypes = [vp, lines, szp, sz, C.c_int32, mop, jop, C.POINTER(u8p), szp,
@@ -2026,6 +2096,71 @@ def mix_pcm(pcms, req, opts=None, device: int = -1):
                                                                   None if opts is None else C.byref(opts), device, outs,
                                                                   ns, C.byref(P), reps))
     return _take(L.jb_mix_free, outs, ns, P.value, np.int16 if i16 else np.float64), list(reps[:P.value])
+
+
+def activity_geometry(opts, hz: int, n: int):
+    """jb_activity_geometry: (wl, hop, T) of a unit of n samples at hz under the ActivityOpts `opts`."""
+    wl, hop, T = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    check(lib().jb_activity_geometry(C.byref(opts), int(hz), int(n), C.byref(wl), C.byref(hop), C.byref(T)))
+    return wl.value, hop.value, T.value
+
+
+def activity_host(pcm, hz: int, opts):
+    """jb_activity_host: (labels [T] uint8, ActivityReport) of one column over the float64 samples `pcm`, in plain C++
+    on the host (no GPU)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    T = activity_geometry(opts, hz, a.size)[2]
+    out = np.zeros(max(T, 1), dtype=np.uint8)
+    rep = ActivityReport()
+    check(lib().jb_activity_host(a.ctypes.data, a.size, int(hz), C.byref(opts), out.ctypes.data, T, C.byref(rep)))
+    return out[:T].copy(), rep
+
+
+def activity_members_host(pcms, starts, n_unit: int, hz: int, opts, gain_db=None):
+    """jb_activity_members_host: (labels [T][m] uint8, [ActivityReport] * m, ActivityUnitReport) of a unit of n_unit
+    samples from its members `pcms` (float64) at `starts`; gain_db: one per member, -inf mutes."""
+    import numpy as np
+
+    arrs, m, ins, nin = _pcm_args(pcms, np.float64, void=True)
+    st = (C.c_uint64 * max(m, 1))(*[int(v) for v in starts])
+    gd = None if gain_db is None else (C.c_double * max(m, 1))(*[float(g) for g in gain_db])
+    T = activity_geometry(opts, hz, int(n_unit))[2]
+    out = np.zeros(max(T * m, 1), dtype=np.uint8)
+    reps, unit = (ActivityReport * max(m, 1))(), ActivityUnitReport()
+    check(lib().jb_activity_members_host(ins, nin, st, gd, m, int(n_unit), int(hz), C.byref(opts), out.ctypes.data, T * m,
+                                         reps, C.byref(unit)))
+    return out[:T * m].reshape(T, m).copy(), list(reps[:m]), unit
+
+
+def activity_pcm(pcms, hz, opts, req=None, mix=None, device: int = -1):
+    """jb_activity_pcm_batch / _i16 (by the arrays' dtype): the labels of caller-held PCM, measured on the GPU.  req: a
+    mix request (mix_request's forms) that makes programmes of the utterances, or None: every utterance a unit of its
+    own; mix: the MixOpts of the mixture that columns="unit" is measured on; hz: one rate, or one per array.
+    ([labels [T][C] uint8 per unit], [[ActivityReport] * C per unit], [ActivityUnitReport per unit])."""
+    import numpy as np
+
+    i16, arrs, n, ins, nin = _join_inputs(pcms)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    arr = None if req is None else mix_request(req)
+    outs, Ts, Cs, P = (C.c_void_p * max(n, 1))(), (C.c_uint64 * max(n, 1))(), (C.c_uint32 * max(n, 1))(), C.c_size_t()
+    reps, units = (ActivityReport * max(n, 1))(), (ActivityUnitReport * max(n, 1))()
+    L = lib()
+    check((L.jb_activity_pcm_batch_i16 if i16 else L.jb_activity_pcm_batch)(
+        ins, nin, n, arr, None if mix is None else C.byref(mix), hzs, C.byref(opts), device, outs, Ts, Cs, C.byref(P),
+        reps, units))
+    sizes = [int(Ts[p]) * int(Cs[p]) for p in range(P.value)]
+    flat = _take(L.jb_activity_free, outs, sizes, P.value, np.uint8)
+    labels, cols, k = [], [], 0
+    for p in range(P.value):
+        labels.append(flat[p].reshape(int(Ts[p]), int(Cs[p])))
+        cols.append(list(reps[k:k + int(Cs[p])]))
+        k += int(Cs[p])
+    return labels, cols, list(units[:P.value])
 
 
 def _biquads(arr, n):

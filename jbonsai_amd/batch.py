@@ -693,6 +693,51 @@ class Batch:
         (jb_batch_read_melspec_all)."""
         return [F.melspec_frames(d, self._melspec) for d in self._sink_read_all("melspec")]
 
+    def set_activity(self, opts=None, **kw):
+        """jb_batch_set_activity: the run also measures per-frame speech-activity labels on the GPU, a uint8 [T, C]
+        matrix per unit (an utterance; with a join or mix request a programme), one column per member
+        (columns="members") or one for the unit (columns="unit"): a side output beside whatever sinks the batch has.
+        opts: F.ActivityOpts (J.activity(...)), or the keywords of J.activity; None without keywords withdraws the
+        request.  Before the first run only."""
+        if opts is None and kw:
+            opts = F.activity(**kw)
+        F.check(self._L.jb_batch_set_activity(self._h, C.byref(opts) if opts is not None else None))
+
+    def activity_shape(self, i):
+        """(T, C, hz) of unit i's label matrix (jb_batch_activity_shape)."""
+        T, c, hz = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        F.check(self._L.jb_batch_activity_shape(self._h, i, C.byref(T), C.byref(c), C.byref(hz)))
+        return T.value, c.value, hz.value
+
+    def read_activity(self, i) -> np.ndarray:
+        """Unit i's labels, uint8 [T, C] (jb_batch_activity_size + jb_batch_read_activity)."""
+        T, c, _ = self.activity_shape(i)
+        n = C.c_size_t()
+        F.check(self._L.jb_batch_activity_size(self._h, i, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        F.check(self._L.jb_batch_read_activity(self._h, i, out.ctypes.data, n.value))
+        return out[:n.value].reshape(T, c)
+
+    def read_activity_all(self):
+        """Every unit's labels through one device-to-host copy (jb_batch_read_activity_all)."""
+        shapes = [self.activity_shape(i)[:2] for i in range(self.num_outputs())]
+        outs = [np.zeros(max(T * c, 1), dtype=np.uint8) for T, c in shapes]
+        ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+        F.check(self._L.jb_batch_read_activity_all(self._h, ptrs))
+        return [o[:T * c].reshape(T, c) for o, (T, c) in zip(outs, shapes)]
+
+    def activity_report(self, i, col=0):
+        """jb_batch_activity_report: the F.ActivityReport of column col of unit i, after a run."""
+        r = F.ActivityReport()
+        F.check(self._L.jb_batch_activity_report(self._h, i, col, C.byref(r)))
+        return r
+
+    def activity_unit_report(self, i):
+        """jb_batch_activity_unit_report: the F.ActivityUnitReport of unit i, after a run."""
+        r = F.ActivityUnitReport()
+        F.check(self._L.jb_batch_activity_unit_report(self._h, i, C.byref(r)))
+        return r
+
     def set_join(self, req):
         """jb_batch_set_join: one request per utterance -- F.JoinUtt entries, or (programme, pad_before, pad_after,
         fade_in, fade_out) tuples with programme None for an utterance of its own, in samples at the output rate; None

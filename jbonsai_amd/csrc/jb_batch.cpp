@@ -2987,6 +2987,76 @@ int jb_batch_read_melspec_all(jb_batch *hb, uint8_t *const *dst)
     return read_bytes_all(hb, jb::SynthSink::Melspec, dst);
 }
 
+int jb_batch_set_activity(jb_batch *hb, const jb_activity_opts *opts)
+{
+    return hb ? ((Batch *)hb)->out.set_activity(opts) : JB_ERR_INVALID;
+}
+
+int jb_batch_activity_shape(jb_batch *hb, size_t unit, uint64_t *T, uint32_t *C, uint32_t *hz)
+{
+    const Batch *b = (const Batch *)hb;
+    jb::ActLayUnit w{};
+    const int rc = b ? b->out.activity_place(unit, false, "jb_batch_activity_shape", &w) : JB_ERR_INVALID;
+    if (rc)
+        return rc;
+    if (T)
+        *T = w.T;
+    if (C)
+        *C = w.C;
+    if (hz)
+        *hz = b->out.fbank_hz(unit);
+    return JB_OK;
+}
+
+int jb_batch_activity_size(jb_batch *hb, size_t unit, size_t *n_bytes)
+{
+    const Batch *b = (const Batch *)hb;
+    jb::ActLayUnit w{};
+    const int rc = b && n_bytes ? b->out.activity_place(unit, false, "jb_batch_activity_size", &w) : JB_ERR_INVALID;
+    if (!rc)
+        *n_bytes = (size_t)(w.T * w.C);
+    return rc;
+}
+
+int jb_batch_read_activity(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
+{
+    Batch *b = (Batch *)hb;
+    jb::ActLayUnit w{};
+    const int rc = b ? b->out.activity_place(unit, true, "jb_batch_read_activity", &w) : JB_ERR_INVALID;
+    if (rc)
+        return rc;
+    if (cap < w.T * w.C) {
+        jb::set_error("jb_batch_read_activity: the buffer is too small");
+        return JB_ERR_BUFFER;
+    }
+    if (!dst && w.T * w.C)
+        return JB_ERR_INVALID;
+    return b->out.read_activity(unit, dst);
+}
+
+int jb_batch_read_activity_all(jb_batch *hb, uint8_t *const *dst)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || (!dst && b->B))
+        return JB_ERR_INVALID;
+    std::vector<jb::ByteSpan> places;
+    std::unique_ptr<uint8_t[]> host;
+    const int rc = b->out.read_activity_all(&places, &host);
+    return rc ? rc : scatter_into(dst, places, host.get());
+}
+
+int jb_batch_activity_report(jb_batch *hb, size_t unit, size_t col, jb_activity_report *out)
+{
+    Batch *b = (Batch *)hb;
+    return b && out ? b->out.read_activity_report(unit, col, out) : JB_ERR_INVALID;
+}
+
+int jb_batch_activity_unit_report(jb_batch *hb, size_t unit, jb_activity_unit_report *out)
+{
+    Batch *b = (Batch *)hb;
+    return b && out ? b->out.read_activity_unit_report(unit, out) : JB_ERR_INVALID;
+}
+
 int jb_batch_set_join(jb_batch *hb, const jb_join_utt *req, size_t n)
 {
     return hb ? ((Batch *)hb)->out.set_join(req, n) : JB_ERR_INVALID;

@@ -1964,7 +1964,8 @@ int SynthRun::launch(size_t g)
     if (rc)
         return rc;
     jb::Batch *b = batches[g].get();
-    if ((rc = apply_conditions(b->out, lo, hi)) || (rq.join && (rc = request_programme(b->out, lo, hi))))
+    if ((rc = apply_conditions(b->out, lo, hi)) || (rq.join && (rc = request_programme(b->out, lo, hi))) ||
+        (rq.activity && (rc = b->out.set_activity(rq.activity))))
         return rc;
     rc = b->run(false);
     t_create += ms(t0, now());
@@ -2023,7 +2024,20 @@ int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
             return JB_ERR_INVALID;
         }
         n_samples[0] = ns;
-        return b->out.read_programme(0, elem == 2, pcm[0]);
+        int rc = b->out.read_programme(0, elem == 2, pcm[0]);
+        if (rc || !rq.activity)
+            return rc;
+        // the programme's labels beside it
+        jb::ActLayUnit w{};
+        if ((rc = b->out.activity_place(0, true, "jb_synthesize_programme_activity", &w)))
+            return rc;
+        if (!(rq.act_out[0] = (uint8_t *)malloc(std::max<size_t>((size_t)(w.T * w.C), 1)))) {
+            jb::set_error("out of host memory");
+            return JB_ERR_INVALID;
+        }
+        rq.act_T[0] = w.T;
+        rq.act_C[0] = w.C;
+        return b->out.read_activity(0, rq.act_out[0]);
     }
     for (size_t u = lo; u < hi; u++) {
         const size_t ns = b->out.samples(u - lo);
@@ -2655,6 +2669,27 @@ int jb_synthesize_programme(const jb_engine *e, const char *const *lines, const 
 {
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
     return synthesize_entry("jb_synthesize_programme", request_join(rq, join, starts), nullptr, true);
+}
+
+int jb_synthesize_programme_activity(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                     int32_t device, const jb_join_opts *join, const jb_activity_opts *opts, double **pcm,
+                                     size_t *n_samples, uint8_t **labels, uint64_t *T, uint32_t *C, uint64_t *starts)
+{
+    const char *who = "jb_synthesize_programme_activity";
+    if (!labels || !T || !C || !pcm || !n_samples)
+        return JB_ERR_INVALID;
+    *labels = nullptr;
+    *T = 0;
+    *C = 0;
+    const int rc = jb::act_check_opts((const jb::ActOpts *)opts, who);
+    if (rc)
+        return rc;
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
+    rq.activity = opts;
+    rq.act_out = labels;
+    rq.act_T = T;
+    rq.act_C = C;
+    return synthesize_entry(who, request_join(rq, join, starts), nullptr, true);
 }
 
 int jb_synthesize_programme_i16(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,

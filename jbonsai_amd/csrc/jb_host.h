@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/jbonsai_amd.h"
 #include "jb_device.h"
+#include "jb_activity.h"
 #include "jb_adpcm.h"
 #include "jb_fbank.h"
 #include "jb_filter.h"
@@ -73,6 +74,10 @@ struct SynthRequest {
                                              // encode (Adpcm), or its frames (Fbank, Mfcc, Melspec)
     const jb_join_opts *join = nullptr;      // jb_synthesize_programme*: all utterances are one programme, the one
     uint64_t *join_starts = nullptr;         // output; join_starts[u] (may be null): each member's first sample
+    const jb_activity_opts *activity = nullptr; // beside a Pcm sink with a join: the programme's speech-activity labels
+    uint8_t **act_out = nullptr;             // into act_out[0] (malloc'ed), their frames and columns into act_T[0]
+    uint64_t *act_T = nullptr;               // and act_C[0]
+    uint32_t *act_C = nullptr;
     void **out = nullptr;                    // [n_utts], or [1] with a join: malloc'ed PCM or bytes of each output
     size_t *n_out = nullptr;                 // its samples (Pcm) or bytes
 };
@@ -444,6 +449,21 @@ struct MixLaunch {
 // spans_dev[0..n) of `tiles` tiles in all: k_mix, k_mix_peak and with fit k_mix again over the programmes of s != 1
 hipError_t launch_mix(bool i16, const ProgSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L,
                       hipStream_t stream);
+
+// The speech-activity stage (jb_activity.hip; the rules, ActCol and ActUnit: jb_activity.h; the host half:
+// jb_activity.cpp).  opts checked with set_error naming the field under the entry `who` (null: refused)
+int act_check_opts(const ActOpts *opts, const char *who);
+// act_layout with set_error naming the unit and the field: JB_ERR_INVALID, or JB_ERR_UNSUPPORTED past a cap
+int act_layout_checked(const ActOpts &o, size_t P, const uint64_t *unit_n, const uint32_t *unit_hz, const uint32_t *first,
+                       const uint32_t *members, const uint64_t *start, const uint64_t *n, const double *gain,
+                       ActLayout *out, const char *who);
+// cols_dev[0..n_cols) of `energy_wgs` workgroups in all, their sources f64 or 16-bit by i16: the columns' maxima
+// (col_max[n_cols], scratch by list position) cleared, k_act_energy, k_act_label (reports[slot] of each column; a
+// unit's first column clears unit_reports[unit]), then units_dev[0..n_units) of `unit_wgs` workgroups: k_act_unit.
+// A list holds every column of each of its units
+hipError_t launch_activity(bool i16, const ActCol *cols_dev, uint32_t n_cols, uint64_t energy_wgs,
+                           const ActUnit *units_dev, uint32_t n_units, uint64_t unit_wgs, uint64_t *col_max,
+                           ActReport *reports, ActUnitReport *unit_reports, const ActLaunch &L, hipStream_t stream);
 
 // The filter stage (jb_filter.hip; the rules, FilterClass and FilterUtt: jb_filter.h; the host half: jb_filter.cpp)
 // f at `hz`: its coefficients into c ([n_sections][5], may be null), or JB_ERR_INVALID with set_error naming the
@@ -859,6 +879,17 @@ struct OutputChain {
     // the mel spectrograms (jb_melspec.h): an f64 batch only; checked at every utterance's output rate (NULL: the
     // request is withdrawn); set_output_rate checks the combined request again.  Independent of set_fbank and set_mfcc
     int set_melspec(const jb_melspec_opts *opts);
+    // the speech-activity labels (jb_activity.h), a side output beside whatever sinks the batch has, f64 or 16-bit:
+    // checked at every unit's rate and against the caps under the present requests (NULL: the request is withdrawn),
+    // and again at the first run, since the rates and the programmes may be set behind it
+    int set_activity(const jb_activity_opts *opts);
+    // unit u's place (JB_ERR_INVALID without a request or for no such unit; `run`: or before the run), its labels, the
+    // labels of every unit in one copy (unit u at host + places[u].off), and the reports (after sync)
+    int activity_place(size_t u, bool run, const char *who, ActLayUnit *out) const;
+    int read_activity(size_t u, uint8_t *dst);
+    int read_activity_all(std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host);
+    int read_activity_report(size_t u, size_t col, jb_activity_report *out);
+    int read_activity_unit_report(size_t u, jb_activity_unit_report *out);
     // the frame request beside set_fbank's and set_mfcc's (jb_fbank.h "Frame conditioning"; NULL: withdrawn), in either
     // order with them: the pair is checked when both are present and again at the first run, where a request without
     // either is an error
@@ -961,6 +992,8 @@ private:
     FrameOpts fr_p{};
     bool ml_on = false;                        // mel spectrograms are requested
     MelOpts ml_p{};
+    bool act_on = false;                       // speech-activity labels are requested
+    ActOpts act_p{};
     std::vector<MixUtt> prog_req;              // [B] the programme request, a join's (join_as_mix) or a mix's; empty: none
     bool prog_chained = false;                 // it is a join's: its starts count from the member in front
     MixOpts mix_opts{};                        // a mix's options
@@ -1089,6 +1122,17 @@ private:
         MelPass pass;
         double *gmax = nullptr, *umax = nullptr; // with a range: one double per workgroup, one per unit
     } ml;
+    struct Activity { // follows `units`: a unit with a rewritten member is measured again, whole
+        DevList<ActCol> cols;        // every column, unit after unit; total: the energy kernel's workgroups
+        DevList<ActUnit> units;      // [U]; total: the counting kernel's workgroups
+        uint8_t *lab = nullptr;      // the label bytes, unit after unit on 16-byte boundaries (plan.act.bytes)
+        double *en = nullptr;        // the compact energies (plan.act.energies)
+        uint64_t *wd = nullptr;      // the word scratch (plan.act.words; with a smoothing length only)
+        uint64_t *col_max = nullptr; // one per column of a launch list
+        ActReport *rep = nullptr;    // one per column
+        ActUnitReport *urep = nullptr; // [U]
+        ActLaunch L{};
+    } act;
     // the units the encoders take: the programmes in the join slab, or the utterances
     struct EncUnit {
         uint64_t off, n;
@@ -1118,6 +1162,10 @@ private:
     bool fbank() const { return plan.fbank_src != OutSlab::None; }
     bool mfcc() const { return plan.mfcc_src != OutSlab::None; }
     bool melspec() const { return plan.melspec_src != OutSlab::None; }
+    bool activity() const { return plan.act_src.slab != OutSlab::None; }
+    // why the plan holds no activity stage for the request (JB_ERR_INVALID naming the unit and the field, or
+    // JB_ERR_UNSUPPORTED past a cap)
+    int activity_fault(const char *who) const;
     // a feature request (FbankOpts, MelOpts) under these rates: JB_ERR_INVALID naming the field that is out of its
     // limits at some rate
     template <class Opts> int check_rates(const Opts &opts, const std::vector<uint32_t> &want, const char *who) const;
@@ -1162,6 +1210,7 @@ private:
     int prepare_fbank(), select_fbank(const RedoScope *scope), launch_fbank(bool redo);
     int prepare_mfcc(), select_mfcc(const RedoScope *scope), launch_mfcc(bool redo);
     int prepare_melspec(), select_melspec(const RedoScope *scope), launch_melspec(bool redo);
+    int prepare_activity(), select_activity(const RedoScope *scope), launch_activity(bool redo);
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
     struct ByteSink {
         bool on;                       // the sink is requested

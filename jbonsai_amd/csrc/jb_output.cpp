@@ -99,6 +99,7 @@ OutPlan plan_output(const OutPlanIn &in)
             p.prog_members = std::move(lay.progs.members);
             p.prog_start = std::move(lay.start);
             if (p.mixed) {
+                p.prog_gain = std::move(lay.gain);
                 p.mix_depth = std::move(lay.depth);
                 p.mix_overlap = std::move(lay.overlap);
             }
@@ -206,6 +207,39 @@ OutPlan plan_output(const OutPlanIn &in)
             p.alloc[(size_t)OutSlab::Mel] = std::max<uint64_t>(bytes, 16);
             if (mo.range > 0.0)
                 p.alloc[(size_t)OutSlab::MelY] = std::max<uint64_t>(words, 2);
+        }
+    }
+    // the speech-activity labels, a side output beside all of them: a column per member of each unit measured on the
+    // member's own final PCM at its start, or one column on the unit's PCM (a request that some unit refuses is no
+    // request: the chain has checked it)
+    if (in.activity) {
+        const size_t U = units.size();
+        std::vector<uint64_t> unit_n(U), n(in.B), start(in.B, 0);
+        std::vector<uint32_t> unit_hz(U), first(U + 1), members(in.B);
+        std::vector<double> gain(in.B, 1.0);
+        for (size_t u = 0; u < U; u++) {
+            unit_n[u] = units[u].n;
+            unit_hz[u] = units[u].hz;
+        }
+        for (size_t u = 0; u < in.B; u++) {
+            n[u] = p.utt[u].n;
+            members[u] = (uint32_t)u;
+        }
+        for (size_t u = 0; u <= U; u++)
+            first[u] = (uint32_t)u;
+        if (joined) {
+            first = p.prog_first;
+            members = p.prog_members;
+            start = p.prog_start;
+            if (p.mixed)
+                gain = p.prog_gain;
+        }
+        ActLayout lay;
+        p.act_fault = act_layout(*in.activity, U, unit_n.data(), unit_hz.data(), first.data(), members.data(),
+                                 start.data(), n.data(), gain.data(), &lay, &p.act_fault_unit, &p.act_unsupported);
+        if (!p.act_fault) {
+            p.act_src = in.activity->columns == kActUnit ? enc : p.final;
+            p.act = std::move(lay);
         }
     }
     return p;

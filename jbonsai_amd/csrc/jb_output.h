@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include <vector>
 
+#include "jb_activity.h"
 #include "jb_fbank.h"
 #include "jb_mfcc.h"
 #include "jb_melspec.h"
@@ -76,6 +77,7 @@ struct OutPlanIn {
     const MfccOpts *mfcc = nullptr;        // f64 logarithms itself) and its options; both or neither
     const FrameOpts *frame = nullptr;      // the frame request beside the fbank and mfcc ones (JB_FRAME_REFLECT: their T); nullptr: none
     const MelOpts *melspec = nullptr;      // the mel spectrogram request (jb_melspec.h), checked at every output rate; nullptr: none
+    const ActOpts *activity = nullptr;     // the speech-activity request (jb_activity.h), checked at every unit's rate; nullptr: none
 };
 
 struct OutUtt {
@@ -159,6 +161,17 @@ struct OutPlan {
     std::vector<uint32_t> prog_of;    // [B] each utterance's programme
     std::vector<uint64_t> prog_start; // [B] its first sample within it
     std::vector<uint32_t> prog_first, prog_members; // programme p owns prog_members[prog_first[p] .. prog_first[p + 1])
+    // With a speech-activity request (jb_activity.h), a side output beside the encoders: with JB_ACTIVITY_MEMBERS the
+    // stage reads the members where the join reads them (join_src: what `final` names), with JB_ACTIVITY_UNIT the
+    // units where the encoders read them (the join slab, or `final`); f64 or 16 bits.  act: each unit's place in the
+    // label bytes with its T, C, wl and hop, each column's source, frames and place in the compact energy scratch, and
+    // the three blocks' sizes (act.bytes, act.energies, act.words: the stage's own blocks, not slabs of `alloc`)
+    OutWrite act_src;                 // None: no request (or one that some unit refuses: the chain has checked it)
+    ActLayout act;
+    const char *act_fault = nullptr;  // what act_layout refused of the request, its unit and whether a cap was passed
+    size_t act_fault_unit = 0;
+    bool act_unsupported = false;
+    std::vector<double> prog_gain;    // [B] with a mix: mix_gain of each member (0: muted)
     uint64_t alloc[(size_t)OutSlab::Count] = {}; // elements to allocate of each slab, at least 1 (0: none; V64 / S16 exist)
     bool normalize() const { return apply.slab != OutSlab::None; }
     bool filtered() const { return filter.slab != OutSlab::None; }

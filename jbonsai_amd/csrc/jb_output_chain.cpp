@@ -48,6 +48,7 @@ void OutputChain::replan()
     in.mfcc = mf_on ? &mf_p : nullptr;
     in.frame = fr_on ? &fr_p : nullptr;
     in.melspec = ml_on ? &ml_p : nullptr;
+    in.activity = act_on ? &act_p : nullptr;
     plan = plan_output(in);
 }
 
@@ -422,6 +423,38 @@ int OutputChain::set_melspec(const jb_melspec_opts *opts)
         ml_p = *(const MelOpts *)opts;
     replan();
     return JB_OK;
+}
+
+// The speech-activity request: tried on the plan of the present requests, and put back where some unit refuses it
+int OutputChain::set_activity(const jb_activity_opts *opts)
+{
+    int rc;
+    if (opts && (rc = act_check_opts((const ActOpts *)opts, "jb_batch_set_activity")))
+        return rc;
+    if ((rc = check_settable("jb_batch_set_activity: the activity request is set before the batch's first run")))
+        return rc;
+    const bool was_on = act_on;
+    const ActOpts was = act_p;
+    act_on = opts != nullptr;
+    if (opts)
+        act_p = *(const ActOpts *)opts;
+    replan();
+    if (act_on && !activity()) {
+        rc = activity_fault("jb_batch_set_activity");
+        act_on = was_on;
+        act_p = was;
+        replan();
+        return rc;
+    }
+    return JB_OK;
+}
+
+int OutputChain::activity_fault(const char *who) const
+{
+    const bool whole = act_opts_fault(act_p) != nullptr; // the options on their own: no unit to name
+    set_error(std::string(who) + ": " + (plan.act_fault ? plan.act_fault : "the request was not planned") +
+              (whole ? "" : " (unit " + std::to_string(plan.act_fault_unit) + ")"));
+    return plan.act_unsupported ? JB_ERR_UNSUPPORTED : JB_ERR_INVALID;
 }
 
 // The programme request `req` ([B], empty: none), a join's (`chained`) or a mix's, under these rates: JB_ERR_INVALID
@@ -824,6 +857,8 @@ int OutputChain::prepare()
     if ((rc = check_frame(fr_on ? &fr_p : nullptr, fb_on ? &fb_p : nullptr, mf_on ? &mf_fb : nullptr, &mf_p,
                           "jb_batch_set_frame_opts")))
         return rc;
+    if (act_on && !activity()) // (a rate or a programme request set behind the activity request)
+        return activity_fault("jb_batch_set_activity");
     frozen = true;
     for (size_t s = 0; s < (size_t)OutSlab::Count; s++)
         if (plan.alloc[s] && (rc = b.dalloc_bytes(&slab[s], (size_t)plan.alloc[s] * out_slab_elem((OutSlab)s), false)))
@@ -831,7 +866,7 @@ int OutputChain::prepare()
     if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_noise()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
         (rc = prepare_programme()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
-        (rc = prepare_fbank()) || (rc = prepare_mfcc()) || (rc = prepare_melspec()))
+        (rc = prepare_fbank()) || (rc = prepare_mfcc()) || (rc = prepare_melspec()) || (rc = prepare_activity()))
         return rc;
     if (plan.active()) {
         void *voc = slab[(size_t)plan.vocoder.slab];
@@ -846,7 +881,7 @@ int OutputChain::prepare()
 // uploaded (select_X) before its first launch, and one wait ends it
 int OutputChain::enqueue(const std::vector<uint8_t> *only)
 {
-    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || mfcc() || melspec() || joined()))
+    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || mfcc() || melspec() || joined() || activity()))
         return JB_OK;
     const bool redo = only != nullptr;
     static const LnGroups no_groups;
@@ -855,15 +890,15 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const RedoScope *scope = redo ? &of_redo : nullptr;
     int rc;
     if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_noise(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
-        (rc = select_limiter(scope)) || (rc = select_programme(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
+        (rc = select_limiter(scope)) || (rc = select_programme(scope)) || (rc = select_activity(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
         (rc = select_adpcm(scope)) || (rc = select_fbank(scope)) || (rc = select_mfcc(scope)) ||
         (rc = select_melspec(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || pg.spans.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || pg.spans.n || act.cols.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_noise(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
-        (rc = launch_limiter(redo)) || (rc = launch_programme(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
+        (rc = launch_limiter(redo)) || (rc = launch_programme(redo)) || (rc = launch_activity(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
         (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)) || (rc = launch_mfcc(redo)) ||
         (rc = launch_melspec(redo)))
         return rc;
@@ -1492,6 +1527,114 @@ int OutputChain::launch_programme(bool redo)
     return mixed() ? hip_fail(e, redo ? "k_mix(redo)" : "k_mix") : hip_fail(e, redo ? "k_join(redo)" : "k_join");
 }
 
+// ---- the speech-activity labels: behind the programmes, beside the encoders.  One column per member on the member's
+// own final PCM (what the join reads), or one per unit on the unit's PCM (what the encoders read); the places from the
+// plan (act_layout)
+int OutputChain::prepare_activity()
+{
+    if (!activity())
+        return JB_OK;
+    const ActLayout &lay = plan.act;
+    const size_t U = lay.units.size(), NC = lay.cols.size();
+    const size_t elem = plan.act_src.i16 ? sizeof(int16_t) : sizeof(double);
+    const bool whole = act_p.columns == kActUnit;
+    const char *src = (const char *)slab[(size_t)plan.act_src.slab];
+    int rc;
+    if ((rc = b.dalloc(&act.lab, std::max<uint64_t>(lay.bytes, 16), false)) ||
+        (rc = b.dalloc(&act.en, std::max<uint64_t>(lay.energies, 1), false)) ||
+        (lay.words && (rc = b.dalloc(&act.wd, lay.words, false))))
+        return rc;
+    uint8_t *lab = act.lab;
+    double *en = act.en;
+    uint64_t *wd = act.wd;
+    const std::vector<EncUnit> units = enc_units();
+    act.L = ActLaunch{act_p.grid, act_p.reference == kActRefAbs, act_p.min_speech, act_p.min_gap, act_p.hang_before,
+                      act_p.hang_after};
+    const double q = act_ratio(act_p.gate_db);
+    act.cols.host.assign(NC, ActCol{});
+    act.units.host.assign(U, ActUnit{});
+    uint64_t energy_wgs = 0, unit_wgs = 0;
+    for (size_t p = 0; p < U; p++) {
+        const ActLayUnit &W = lay.units[p];
+        act.units.host[p] = ActUnit{lab + W.off, W.T, unit_wgs, W.C, (uint32_t)p};
+        unit_wgs += act_unit_wgs(W.T);
+        for (uint32_t j = 0; j < W.C; j++) {
+            const ActLayCol &a = lay.cols[W.col0 + j];
+            ActCol &c = act.cols.host[W.col0 + j];
+            c.x = src + (whole ? units[p].off : plan.utt[a.utt].off) * elem;
+            c.y = lab + W.off + j;
+            c.e = en + a.e0;
+            c.words = act.L.smooth() ? wd + a.w0 : nullptr;
+            c.start = a.start;
+            c.n = a.n;
+            c.T = W.T;
+            c.f0 = a.f0;
+            c.nf = a.nf;
+            c.g0 = energy_wgs;
+            c.nw = (W.T + 63) / 64;
+            c.q = q;
+            c.thr_abs = act_abs_threshold(act_p.gate_db, W.wl);
+            c.C = W.C;
+            c.wl = W.wl;
+            c.hop = W.hop;
+            c.col = j;
+            c.slot = W.col0 + j;
+            c.unit = (uint32_t)p;
+            energy_wgs += act_energy_wgs(a.nf, W.wl, W.hop);
+        }
+    }
+    act.cols.total = energy_wgs;
+    act.units.total = unit_wgs;
+    if ((rc = b.dalloc(&act.col_max, NC, false)) || (rc = b.dalloc(&act.rep, NC, false)) ||
+        (rc = b.dalloc(&act.urep, U, false)) || (rc = act.cols.alloc(b, NC, NC)) || (rc = act.units.alloc(b, U, U)) ||
+        (rc = act.cols.upload("activity work list")))
+        return rc;
+    return act.units.upload("activity work list");
+}
+
+// A redo measures every unit with a member whose final PCM changed again, whole: the energies, the maxima, the labels
+// and the reports of all its columns
+int OutputChain::select_activity(const RedoScope *scope)
+{
+    if (!activity() || !scope) {
+        uint64_t energy_wgs = 0, unit_wgs = 0;
+        for (const ActCol &c : act.cols.host)
+            energy_wgs += act_energy_wgs(c.nf, c.wl, c.hop);
+        for (const ActUnit &w : act.units.host)
+            unit_wgs += act_unit_wgs(w.T);
+        act.units.take_all(unit_wgs);
+        return act.cols.take_all(energy_wgs);
+    }
+    std::vector<ActCol> cols;
+    std::vector<ActUnit> us;
+    uint64_t energy_wgs = 0, unit_wgs = 0;
+    for (size_t p = 0; p < act.units.host.size() && p < scope->units.size(); p++) {
+        if (!scope->units[p])
+            continue;
+        us.push_back(act.units.host[p]);
+        us.back().g0 = unit_wgs;
+        unit_wgs += act_unit_wgs(us.back().T);
+        const ActLayUnit &W = plan.act.units[p];
+        for (uint32_t j = 0; j < W.C; j++) {
+            cols.push_back(act.cols.host[W.col0 + j]);
+            cols.back().g0 = energy_wgs;
+            energy_wgs += act_energy_wgs(cols.back().nf, W.wl, W.hop);
+        }
+    }
+    const int rc = act.units.upload_redo(us, kRedoLists, unit_wgs);
+    return rc ? rc : act.cols.upload_redo(cols, kRedoLists, energy_wgs);
+}
+
+int OutputChain::launch_activity(bool redo)
+{
+    if (!activity() || (redo && !act.cols.n))
+        return JB_OK;
+    const hipError_t e =
+        jb::launch_activity(plan.act_src.i16, act.cols.list, act.cols.n, act.cols.total, act.units.list, act.units.n,
+                            act.units.total, act.col_max, act.rep, act.urep, act.L, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_act(redo)" : "k_act");
+}
+
 // ---- FLAC.  The streams' lists and slabs: one stream per unit (an utterance; behind a join a programme) of the
 // 16-bit slab FLAC reads, at its output rate
 int OutputChain::prepare_flac()
@@ -1874,6 +2017,60 @@ int OutputChain::read_used(const void *src, uint64_t bytes, bool wait, std::uniq
         return JB_ERR_INVALID;
     }
     return bytes ? b.read(src, host->get(), (size_t)bytes, wait) : wait ? b.sync() : JB_OK;
+}
+
+int OutputChain::activity_place(size_t u, bool run, const char *who, ActLayUnit *out) const
+{
+    if (!act_on || !activity() || (run && !ready) || u >= plan.act.units.size()) {
+        set_error(std::string(who) + (!act_on || !activity() ? ": jb_batch_set_activity was not called"
+                                      : run && !ready        ? ": the batch has not run"
+                                                             : ": no such unit"));
+        return JB_ERR_INVALID;
+    }
+    *out = plan.act.units[u];
+    return JB_OK;
+}
+
+int OutputChain::read_activity(size_t u, uint8_t *dst)
+{
+    ActLayUnit w{};
+    const int rc = activity_place(u, true, "jb_batch_read_activity", &w);
+    if (rc)
+        return rc;
+    const uint64_t bytes = w.T * w.C;
+    return bytes ? b.read(act.lab + w.off, dst, (size_t)bytes) : b.sync();
+}
+
+int OutputChain::read_activity_all(std::vector<ByteSpan> *places, std::unique_ptr<uint8_t[]> *host)
+{
+    ActLayUnit w{};
+    int rc = activity_place(0, true, "jb_batch_read_activity_all", &w);
+    if (rc)
+        return rc;
+    places->clear();
+    for (const ActLayUnit &v : plan.act.units)
+        places->push_back(ByteSpan{v.off, v.T * v.C});
+    return read_used(act.lab, used_bytes(*places), true, host);
+}
+
+int OutputChain::read_activity_report(size_t u, size_t col, jb_activity_report *out)
+{
+    ActLayUnit w{};
+    const int rc = activity_place(u, true, "jb_batch_activity_report", &w);
+    if (rc)
+        return rc;
+    if (col >= w.C) {
+        set_error("jb_batch_activity_report: no such column");
+        return JB_ERR_INVALID;
+    }
+    return b.read(act.rep + w.col0 + col, out, sizeof *out);
+}
+
+int OutputChain::read_activity_unit_report(size_t u, jb_activity_unit_report *out)
+{
+    ActLayUnit w{};
+    const int rc = activity_place(u, true, "jb_batch_activity_unit_report", &w);
+    return rc ? rc : b.read(act.urep + u, out, sizeof *out);
 }
 
 int OutputChain::read_loudness(size_t u, LoudnessResult *r)

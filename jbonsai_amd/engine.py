@@ -693,6 +693,42 @@ class Engine:
                                   starts))
         return take(self, L, buf, n.value, count.value, opts), list(starts[:B])
 
+    def synthesize_programme_activity(self, utterances: Sequence[Sequence[str]], opts=None, lead_ms: float = 0.0,
+                                      gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0,
+                                      device: int = -1, mix=None, fit: bool = False, ceiling_db: float = 0.0, **kw):
+        """jb_synthesize_programme_activity: synthesize_programme(..., sink="f64") with the programme's speech-activity
+        labels from the same run.  opts: F.ActivityOpts, or the keywords of J.activity.  Returns (pcm, labels, starts):
+        labels is uint8 [T, C], with columns="members" one column per utterance, placed at starts[u].  mix, fit and
+        ceiling_db as in synthesize_programme."""
+        if mix is not None:
+            was = self.get_programme_mix()
+            self.set_programme_mix(mix, fit, ceiling_db)
+            try:
+                return self.synthesize_programme_activity(utterances, opts, lead_ms, gap_ms, trail_ms, fade_ms, device,
+                                                          **kw)
+            finally:
+                self.set_programme_mix(*was)
+        if opts is None:
+            opts = F.activity(**kw)
+        elif kw:
+            raise TypeError(f"unknown options {sorted(kw)}")
+        lines, offs, B = _utt_lines(utterances)
+        join = F.join_opts(lead_ms, gap_ms, trail_ms, fade_ms)
+        starts = (C.c_uint64 * max(1, B))()
+        out, n, lab, T, Cc = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_uint64(), C.c_uint32()
+        L = self._L
+        F.check(L.jb_synthesize_programme_activity(self._h, lines, offs, B, device, C.byref(join), C.byref(opts),
+                                                   C.byref(out), C.byref(n), C.byref(lab), C.byref(T), C.byref(Cc),
+                                                   starts))
+        pcm = np.frombuffer((C.c_double * n.value).from_address(out.value), dtype=np.float64).copy() if n.value \
+            else np.zeros(0, np.float64)
+        L.jb_join_free(out)
+        cells = T.value * Cc.value
+        labels = np.frombuffer((C.c_uint8 * cells).from_address(lab.value), dtype=np.uint8).copy() if cells \
+            else np.zeros(0, np.uint8)
+        L.jb_activity_free(lab)
+        return pcm, labels.reshape(T.value, Cc.value), list(starts[:B])
+
     def generator(self, labels: Sequence[str]) -> "SpeechGenerator":
         h = C.c_void_p()
         F.check(self._L.jb_generator_new(self._h, _lines(labels), len(labels), C.byref(h)))
