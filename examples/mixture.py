@@ -4,7 +4,8 @@ start of its own and under a gain of its own, summed on the GPU.
     python examples/mixture.py voice.htsvoice first.lab second.lab ... -o mixture.flac
                                --start-ms MS,MS,... [--gain-db DB,DB,...] [--fit [--ceiling DBFS]]
                                [--lead-ms MS] [--trail-ms MS] [--fade-ms MS] [--rate HZ]
-                               [--room LX,LY,LZ --rt60 S [--vary]] [--stems DIR]
+                               [--room LX,LY,LZ --rt60 S [--vary]]
+                               [--stems DIR [--talker ID ...] [--levels levels.csv]]
                                [--activity labels.npy] [--rttm out.rttm] [--gate-db DB]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
@@ -13,9 +14,14 @@ batch and mixed on the GPU (Engine.set_programme_mix, then Engine.synthesize_pro
 written as a 16-bit WAV file.  --start-ms and --gain-db take one value per sentence (a gain of 0 dB by default).  With
 --fit a mixture whose peak passes --ceiling is scaled down to it on the GPU; without it the 16-bit sink clamps.  With
 --room every sentence is reverberated by a simulated shoebox room of those edges in metres, with --vary every talker
-from a position of their own (Engine.set_room with vary=True).  With --stems the members' own 16-bit PCM, as it went into
-the sum, is written beside the mixture (s0.wav, s1.wav, ...).  The cue list -- each sentence's first sample and time
-within the mixture -- and the stage's report (the host rule over the stems: the same numbers) are printed.
+from a position of their own (Engine.set_room with vary=True).  With --stems the mixture and its stems in programme
+coordinates -- each source exactly as it entered the sum, at its start, under its fades, its gain and the fit's scale,
+zero elsewhere and as long as the mixture -- come from one more run (Engine.synthesize_programme(..., stems=)) and are
+written to DIR as mix and s<id>, FLAC or 16-bit WAV as the output is; --talker gives one id per sentence (sentences of
+one id form one stem; by default every sentence is a stem of its own), and --levels writes one CSV row per stem: its
+peak, the mixture's scale, the three sums E_s, D and E_p measured on the GPU and level_db, sir_db and si_sdr_db (the
+input SI-SDR of the corpus metadata).  The cue list -- each sentence's first sample and time within the mixture -- and
+the stage's report (the host rule over the members: the same numbers) are printed.
 With --activity the per-frame speech-activity labels of the talkers, a uint8 matrix [frames][talkers] at 25 / 10 ms
 measured on the GPU in a run of the same mixture (Engine.synthesize_programme_activity: a gate --gate-db under each
 talker's loudest frame, pauses of up to 200 ms closed, 20 ms of hang at both ends), are saved as a .npy file; with --rttm
@@ -49,7 +55,9 @@ ap.add_argument("--rate", type=int, default=None, metavar="HZ", help="output rat
 ap.add_argument("--room", default=None, metavar="LX,LY,LZ", help="edges of a simulated room in metres (Engine.set_room)")
 ap.add_argument("--rt60", type=float, default=0.5, metavar="S", help="reverberation time of --room")
 ap.add_argument("--vary", action="store_true", help="with --room: every talker at a position of their own")
-ap.add_argument("--stems", default=None, metavar="DIR", help="write the members' 16-bit PCM there")
+ap.add_argument("--stems", default=None, metavar="DIR", help="write the mixture and its stems there (mix, s<id>)")
+ap.add_argument("--talker", type=int, nargs="*", default=None, metavar="ID", help="with --stems: each sentence's stem id")
+ap.add_argument("--levels", default=None, metavar="CSV", help="with --stems: each stem's level against the mixture")
 ap.add_argument("--activity", default=None, metavar="NPY", help="save the talkers' per-frame activity labels there")
 ap.add_argument("--rttm", default=None, metavar="RTTM", help="write the talkers' active runs there as RTTM lines")
 ap.add_argument("--gate-db", type=float, default=40.0, help="the activity gate under each talker's loudest frame")
@@ -57,6 +65,9 @@ args = ap.parse_args()
 gains = args.gain_db or [0.0] * len(args.labels)
 if len(args.start_ms) != len(args.labels) or len(gains) != len(args.labels):
     ap.error("--start-ms and --gain-db take one value per label file")
+talkers = args.talker if args.talker else list(range(len(args.labels)))
+if len(talkers) != len(args.labels) or ((args.talker or args.levels) and not args.stems):
+    ap.error("--talker takes one id per label file; --talker and --levels go with --stems")
 
 sentences = []
 for path in args.labels:
@@ -86,7 +97,7 @@ else:
     print(f"wrote {args.out}: {pcm.size} samples at {hz} Hz")
 for k, (s, path) in enumerate(zip(starts, args.labels)):
     print(f"cue {k} {s} {s / hz:.3f} {path}")
-# the stems, and the stage's report from them by the host rule
+# the members, and the stage's report from them by the host rule
 stems = engine.synthesize_batch(sentences, i16=True)
 fade, trail = J.join_ms_to_samples(args.fade_ms, hz), J.join_ms_to_samples(args.trail_ms, hz)
 req = [(0, s, g, trail, fade, fade) for s, g in zip(starts, gains)]
@@ -94,9 +105,29 @@ _, (rep,) = J.mix_host(stems, req, J.mix_opts(args.fit, args.ceiling))
 print(f"report peak {rep.peak:.1f} scale {rep.scale:.6f} depth {rep.depth} overlap {rep.overlap} samples "
       f"({rep.overlap / hz:.3f} s)")
 if args.stems:
+    import numpy as np
+
     os.makedirs(args.stems, exist_ok=True)
-    for k, x in enumerate(stems):
-        J.write_wav(os.path.join(args.stems, f"s{k}.wav"), x, hz)
+    flac = args.out.endswith(".flac")
+    kw = dict(md5=True, seek_interval_ms=1000) if flac else {}
+    ids = list(dict.fromkeys(talkers))  # the stems' order: by the first sentence of each id
+    # (the library's stem ids lie below the number of sentences: the caller's ids are numbered in that order)
+    units, _, reports = engine.synthesize_programme(sentences, sink="flac" if flac else "f64",
+                                                    stems=[ids.index(t) for t in talkers], levels=True, **kw, **opts)
+    for name, x in zip(["mix"] + [f"s{i}" for i in ids], units):
+        path = os.path.join(args.stems, name + (".flac" if flac else ".wav"))
+        if flac:
+            with open(path, "wb") as f:
+                f.write(x)
+        else:  # the 16-bit sink's rule: clamp, then truncate toward zero
+            J.write_wav(path, np.trunc(np.clip(x, -32768.0, 32767.0)).astype(np.int16), hz)
+        print(f"stem {name} {path}")
+    if args.levels:
+        with open(args.levels, "w") as f:
+            f.write("stem,peak,scale,e_s,d,e_p,level_db,sir_db,si_sdr_db\n")
+            for i, r in zip(ids, reports):
+                f.write(f"s{i},{r.peak!r},{r.scale!r},{r.e_s!r},{r.d!r},{r.e_p!r},{r.level_db!r},{r.sir_db!r},"
+                        f"{r.si_sdr_db!r}\n")
 if args.activity or args.rttm:
     import numpy as np
 

@@ -1321,10 +1321,10 @@ void jb_join_free(void *p);
 
 /* ---- Mix (new: the reference synthesises one utterance into one buffer; none of these entries has a counterpart) -------
  * A programme is the SUM of its members, each at a start of its own and under a gain of its own: two talkers at once
- * (the members' PCM stays readable, so the stems come with the mixture), a crossfade between sentences, a timed event
- * over a sentence.  The stage stands in the join's place and feeds the same encoders and feature stages, which then
- * run over the mixture whole.  The rule (jbonsai_amd/csrc/jb_mix.h states it once for the host, the device and the
- * plan):
+ * (the members' PCM stays readable; the stems in programme coordinates: "Stems" below), a crossfade between
+ * sentences, a timed event over a sentence.  The stage stands in the join's place and feeds the same encoders and
+ * feature stages, which then run over the mixture whole.  The rule (jbonsai_amd/csrc/jb_mix.h states it once for the
+ * host, the device and the plan):
  * - Numbering and rate: as the join's.  Length: the largest start + n + pad_after over a programme's members.  Each
  *   programme starts on a 16-byte boundary of its slab.
  * - Gain: g = 10^(gain_db / 20), formed on the host in long double and rounded once (jb_mix_gain); 0 dB is exactly 1,
@@ -1352,8 +1352,8 @@ void jb_join_free(void *p);
  *   sample; k_mix_peak folds the tiles' maxima per programme; with JB_MIX_FIT k_mix runs again over the programmes
  *   with s_p != 1, from the members.  No LDS, no atomics.
  * - Cost: not measured.
- * Not covered: loudness measured over the mixture, the generator, the _multi entries, a member in two programmes,
- * stems materialised in programme coordinates. */
+ * Not covered: loudness measured over the mixture, the generator, the _multi entries, a member in two programmes
+ * (the stems below are what that was asked for). */
 /* New (none).  g of gain_db by the rule above; pure (a NaN or a value outside the setter's range is not refused here). */
 double jb_mix_gain(double gain_db);
 /* New (none).  The geometry of a request, as jb_join_geometry, plus depth[p] and overlap[p] of the report ([n] each,
@@ -1379,6 +1379,106 @@ int jb_mix_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n,
                          const jb_mix_opts *opts, int32_t device, int16_t **out, size_t *n_out, size_t *n_programmes,
                          jb_mix_report *reports);
 void jb_mix_free(void *p);
+
+/* ---- Stems of a mix (new: none of these entries has a counterpart) -------------------------------------------------------
+ * What a separation or diarisation corpus stores beside the mixture: each source exactly as it entered the sum -- at its
+ * start, under its fades, its gain and the fit's scale, zero elsewhere, as long as the mixture -- and its level
+ * against the mixture.  The members of one programme that carry the same stem id form one stem (one id per talker:
+ * a talker's five sentences are one stem).  The rule (jbonsai_amd/csrc/jb_mix.h states it once):
+ * - Stem s of programme p has the programme's length and rate.  Sample k is the mix rule over the stem's own members
+ *   alone: ascending utterance index, the first term starts the sum, acc = acc + t behind it (no fma), +0.0 under
+ *   none.  With JB_MIX_FIT and s_p != 1 the stored value is acc * s_p, s_p the PROGRAMME's scale: a stem has no scale
+ *   of its own and is NOT clamped to the ceiling (a stem may peak above its mixture; a clamp would break additivity).
+ *   The 16-bit sink clamps and truncates as it always does.
+ * - Numbering: units 0 .. P-1 stay the programmes; the stems follow, by programme in dense order and within one by the
+ *   ascending utterance index of each stem's first member.  Each stem starts on a 16-byte boundary of the programmes'
+ *   slab, behind them, and is a unit like any other to FLAC, the sample formats, ADPCM, fbank, mfcc and melspec (the
+ *   mfcc CMVN and the melspec range clamp are per unit, hence per stem).  The activity stage keeps reading members and
+ *   keeps the P programmes as its units.  A muted member may carry an id and contributes nothing; a stem without an
+ *   unmuted member of at least one sample exists and is all +0.0.
+ * - Additivity: in f64 with s_p == 1 and every unmuted member under an id, at a sample under at most two members the
+ *   stems added in unit order equal the mixture (==); under a depth d only the association differs:
+ *   |sum - mix| <= (d - 1) 2^-52 sum |t|.  In 16 bits, where no term and no sum leaves [-32768, 32767], the stems' sum
+ *   is within d counts of the mixture.  A stem that is one member at 0 dB keeps that member's bits outside its fades.
+ * - Independence: a stem's bits depend on its members' samples, the request and s_p alone; a redo round runs a
+ *   touched programme again whole, with its stems and their levels.
+ * - Levels (JB_MIX_STEM_LEVELS): E_s = sum s[k]^2 and D = sum s[k] m[k] over the programme's 1,024-sample tiles that
+ *   touch the stem's extent [first_sample, end_sample), E_p = sum m[k]^2 over all of the programme's tiles, of the
+ *   units AS STORED (a 16-bit sample enters as its (double)), so a caller reproduces them from what they read back.
+ *   The order is the noise stage's: 256 strided partials per tile, a partial's first term the product and each later
+ *   one fused on (fma), the partials folded by the tree h = 128 .. 1, the tile sums added in ascending order.  The
+ *   device's three sums are jb_mix_levels_host's bit for bit.  From them, on the host in long double:
+ *   level_db = 10 log10(E_s / E_p), sir_db = 10 log10(E_s / (E_p - 2 D + E_s)), si_sdr_db = 10 log10(a / (E_p - a))
+ *   with a = D^2 / E_s; +INFINITY where a denominator is not above 0, -INFINITY where E_s == 0.
+ * - On the device (jb_mix.hip): the stems go through k_mix as units (the fit pass of a stem reads its programme's
+ *   scale and does not clamp); k_mix_levels, one workgroup per tile, and a fold of one wave per unit.  No atomics.
+ * - Cost: not measured.
+ * - At engine level: jb_synthesize_programme_stems and jb_synthesize_programme_stems_flac_meta, behind
+ *   jb_engine_set_programme_mix.
+ * Not covered: activity columns per stem, loudness measured per stem, the generator, the _multi entries, a member in
+ * two programmes. */
+#define JB_MIX_NO_STEM 0xffffffffu
+#define JB_MIX_STEM_LEVELS 1u
+typedef struct jb_stem_report {
+    double peak;  /* the largest |acc| of the stem, in front of the scale */
+    double scale; /* s_p of its programme */
+    double e_s, d, e_p; /* with JB_MIX_STEM_LEVELS, else 0 */
+    double level_db, sir_db, si_sdr_db; /* with JB_MIX_STEM_LEVELS, else NaN */
+} jb_stem_report;
+/* New (none).  The stems request behind jb_batch_set_mix, before the first run: stem_of[u] is utterance u's stem id
+ * within its programme (below jb_batch_size(b)) or JB_MIX_NO_STEM; flags: JB_MIX_STEM_LEVELS or 0.  NULL, 0, 0
+ * withdraws it; withdrawing the mix withdraws it too.  JB_ERR_INVALID with jb_last_error naming the utterance and the
+ * field: an id of jb_batch_size(b) or above, a request without a mix or over a join, an unknown flag, a slab too long.
+ * jb_batch_num_outputs is P + S while it stands, and every encoder index and jb_batch_read_programme_pcm / _i16 take a
+ * stem's unit. */
+int jb_batch_set_mix_stems(jb_batch *b, const uint32_t *stem_of, size_t n, uint32_t flags);
+size_t jb_batch_num_programmes(const jb_batch *b); /* P (without a join or mix request: the batch size) */
+int64_t jb_batch_stem_unit(const jb_batch *b, size_t utt); /* the unit of the utterance's stem, or -1 */
+/* New (none).  A stem's place: its dense programme, the caller's id, its members (muted ones included) and its extent
+ * (0, 0 without an unmuted member of at least one sample); any out pointer may be NULL; unit below P or not below
+ * P + S: JB_ERR_INVALID. */
+int jb_batch_stem_layout(const jb_batch *b, size_t unit, uint32_t *programme, uint32_t *stem_id, uint32_t *n_members,
+                         uint64_t *first_sample, uint64_t *end_sample);
+/* New (none).  After a run: the stem's peak, its programme's scale and, with JB_MIX_STEM_LEVELS, the sums and the dB
+ * values. */
+int jb_batch_stem_report(jb_batch *b, size_t unit, jb_stem_report *out);
+/* New (none).  The geometry of a mix request with stems: P, the units P + S, each utterance's stem unit (-1: none) and
+ * per unit ([2 n] each, the first P + S written) its samples, its dense programme, the caller's stem id
+ * (JB_MIX_NO_STEM for a programme), its members, its extent (a programme: 0 and its length) and its depth.  Any out
+ * pointer may be NULL. */
+int jb_mix_stems_geometry(const jb_mix_utt *req, const uint32_t *stem_of, const size_t *n_in, const uint32_t *hz, size_t n,
+                          const jb_mix_opts *opts, size_t *n_programmes, size_t *n_units, int64_t *stem_unit,
+                          uint64_t *unit_samples, uint32_t *unit_programme, uint32_t *unit_stem_id,
+                          uint32_t *unit_members, uint64_t *unit_first, uint64_t *unit_end, uint32_t *unit_depth);
+/* New (none).  The rule on the host: out and cap have P + S entries, the programmes first; scale as jb_mix_host's
+ * ([P]; a stem takes its programme's).  reports (may be NULL): [P]; stem_reports (may be NULL): [S], the levels with
+ * JB_MIX_STEM_LEVELS in flags taken from out as stored. */
+int jb_mix_stems_host(const double *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                      const uint32_t *stem_of, uint32_t flags, const jb_mix_opts *opts, const double *scale,
+                      double *const *out, const size_t *cap, jb_mix_report *reports, jb_stem_report *stem_reports);
+int jb_mix_stems_i16_host(const int16_t *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                          const uint32_t *stem_of, uint32_t flags, const jb_mix_opts *opts, const double *scale,
+                          int16_t *const *out, const size_t *cap, jb_mix_report *reports, jb_stem_report *stem_reports);
+/* New (none).  The three sums of a stem and its mixture of n samples each by the order above, on the host; the extent
+ * with first_sample <= end_sample <= n.  Any out pointer may be NULL. */
+int jb_mix_levels_host(const double *stem, const double *mix, size_t n, uint64_t first_sample, uint64_t end_sample,
+                       double *e_s, double *d, double *e_p);
+int jb_mix_levels_i16_host(const int16_t *stem, const int16_t *mix, size_t n, uint64_t first_sample,
+                           uint64_t end_sample, double *e_s, double *d, double *e_p);
+/* New (none).  The three dB values of a report from its three sums (long double on the host); pure. */
+void jb_mix_levels_db(double e_s, double d, double e_p, double *level_db, double *sir_db, double *si_sdr_db);
+/* New (none).  The stage with stems on PCM the caller holds, on `device` (-1 = current).  out and n_out have 2 n
+ * entries; the first *n_units are written, the *n_programmes programmes first, library-owned (jb_mix_free each).
+ * reports (may be NULL): [n], the first P written; stem_reports (may be NULL): [n], the first S written, the sums the
+ * device's. */
+int jb_mix_stems_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                           const uint32_t *stem_of, uint32_t flags, const jb_mix_opts *opts, int32_t device,
+                           double **out, size_t *n_out, size_t *n_programmes, size_t *n_units, jb_mix_report *reports,
+                           jb_stem_report *stem_reports);
+int jb_mix_stems_pcm_batch_i16(const int16_t *const *in, const size_t *n_in, size_t n, const jb_mix_utt *req,
+                               const uint32_t *stem_of, uint32_t flags, const jb_mix_opts *opts, int32_t device,
+                               int16_t **out, size_t *n_out, size_t *n_programmes, size_t *n_units,
+                               jb_mix_report *reports, jb_stem_report *stem_reports);
 
 /* ---- Speech activity (new: the reference has no such output) ---------------------------------------------------------
  * Per-frame 0/1 labels on the frame grid of the feature stages, one column per talker: what an RTTM file or an
@@ -2381,6 +2481,22 @@ int jb_synthesize_programme_activity(const jb_engine *e, const char *const *labe
 int jb_synthesize_programme_flac_meta(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
                                       size_t n_utts, int32_t device, const jb_flac_opts *opts, const jb_flac_meta *meta,
                                       const jb_join_opts *join, uint8_t **flac, size_t *n_bytes, uint64_t *starts);
+/* New (none).  jb_synthesize_programme and jb_synthesize_programme_flac_meta with the stems of the mixture ("Stems of a
+ * mix" above) from the same run: stem_of[u] is utterance u's stem id (below n_utts) or JB_MIX_NO_STEM, flags
+ * JB_MIX_STEM_LEVELS or 0.  The outputs are the mixture first and the S stems behind it, *n_outputs = 1 + S of them:
+ * pcm / flac and n_samples / n_bytes have 1 + n_utts entries, each written output library-owned (jb_join_free /
+ * jb_flac_free); reports (may be NULL) has n_utts entries, the first S written, one per stem in output order.  Valid
+ * only while jb_engine_set_programme_mix is set: otherwise, and for a NULL stem_of, an unknown flag or an id of n_utts
+ * or above, JB_ERR_INVALID before any device is touched.  Any other sink with stems is reached at batch level. */
+int jb_synthesize_programme_stems(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_join_opts *join, const uint32_t *stem_of,
+                                  uint32_t flags, double **pcm, size_t *n_samples, size_t *n_outputs,
+                                  jb_stem_report *reports, uint64_t *starts);
+int jb_synthesize_programme_stems_flac_meta(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                            size_t n_utts, int32_t device, const jb_flac_opts *opts,
+                                            const jb_flac_meta *meta, const jb_join_opts *join, const uint32_t *stem_of,
+                                            uint32_t flags, uint8_t **flac, size_t *n_bytes, size_t *n_outputs,
+                                            jb_stem_report *reports, uint64_t *starts);
 int jb_synthesize_programme_formatted(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
                                       size_t n_utts, int32_t device, const jb_format_opts *opts,
                                       const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, uint64_t *starts);
@@ -2483,6 +2599,9 @@ JB_LAYOUT_ASSERT(sizeof(jb_mix_opts) == 16 && offsetof(jb_mix_opts, ceiling_db) 
 JB_LAYOUT_ASSERT(sizeof(jb_mix_report) == 32 && offsetof(jb_mix_report, scale) == 8 &&
                      offsetof(jb_mix_report, depth) == 16 && offsetof(jb_mix_report, overlap) == 24,
                  "jb_mix_report");
+JB_LAYOUT_ASSERT(sizeof(jb_stem_report) == 64 && offsetof(jb_stem_report, e_s) == 16 &&
+                     offsetof(jb_stem_report, level_db) == 40,
+                 "jb_stem_report");
 JB_LAYOUT_ASSERT(sizeof(jb_mix_place) == 16 && offsetof(jb_mix_place, gain_db) == 8, "jb_mix_place");
 JB_LAYOUT_ASSERT(sizeof(jb_activity_opts) == 64 && offsetof(jb_activity_opts, gate_db) == 8 &&
                      offsetof(jb_activity_opts, grid) == 16 && offsetof(jb_activity_opts, flags) == 28 &&

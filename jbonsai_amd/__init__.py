@@ -13,7 +13,8 @@ from ._ffi import (JbError, LIB_PATH, NODATA, PEAK_SAMPLE, PEAK_TRUE, UttVoc, bu
                    LOUDNESS_NO_GROUP, LOUDNESS_R128, LOUDNESS_PER_UTTERANCE, LOUDNESS_PER_REQUEST,
                    JOIN_NONE, JoinUtt, join_geometry, join_host, join_ms_to_samples, join_pcm,
                    MIX_NONE, MIX_FIT, MixUtt, MixOpts, MixReport, MixPlace, mix_opts, mix_geometry, mix_gain, mix_host,
-                   mix_pcm,
+                   mix_pcm, MIX_NO_STEM, MIX_STEM_LEVELS, StemReport, mix_stems_geometry, mix_stems_host,
+                   mix_stems_pcm, mix_levels_host, mix_levels_db,
                    ACTIVITY_SNIP, ACTIVITY_CENTER, ACTIVITY_KALDI, ACTIVITY_STFT, ACTIVITY_REF_PEAK, ACTIVITY_REF_ABS,
                    ACTIVITY_MEMBERS, ACTIVITY_UNIT, ACTIVITY_SAMPLES, ACTIVITY_MAX_CELLS, ActivityOpts, ActivityReport,
                    ActivityUnitReport, activity, activity_geometry, activity_host, activity_members_host, activity_pcm,
@@ -55,7 +56,9 @@ __all__ = ["Engine", "SpeechGenerator", "JbError", "LIB_PATH", "NODATA", "build"
            "synthesize_batch_each_adpcm", "loudness_groups", "loudness_gate_host", "LOUDNESS_NO_GROUP", "LOUDNESS_R128", "LOUDNESS_PER_UTTERANCE",
            "LOUDNESS_PER_REQUEST", "JOIN_NONE", "JoinUtt", "join_geometry", "join_host", "join_ms_to_samples",
            "join_pcm", "MIX_NONE", "MIX_FIT", "MixUtt", "MixOpts", "MixReport", "MixPlace", "mix_opts", "mix_geometry",
-           "mix_gain", "mix_host", "mix_pcm", "ACTIVITY_SNIP", "ACTIVITY_CENTER", "ACTIVITY_KALDI", "ACTIVITY_STFT",
+           "mix_gain", "mix_host", "mix_pcm", "MIX_NO_STEM", "MIX_STEM_LEVELS", "StemReport", "mix_stems_geometry",
+           "mix_stems_host", "mix_stems_pcm", "mix_levels_host", "mix_levels_db", "ACTIVITY_SNIP", "ACTIVITY_CENTER",
+           "ACTIVITY_KALDI", "ACTIVITY_STFT",
            "ACTIVITY_REF_PEAK", "ACTIVITY_REF_ABS", "ACTIVITY_MEMBERS", "ACTIVITY_UNIT", "ACTIVITY_SAMPLES",
            "ACTIVITY_MAX_CELLS", "ActivityOpts", "ActivityReport", "ActivityUnitReport", "activity", "activity_geometry",
            "activity_host", "activity_members_host", "activity_pcm", "Filter", "FilterSection", "Biquad", "filter_design", "filter_sos", "filter_pcm",

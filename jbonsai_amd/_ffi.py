@@ -436,6 +436,21 @@ class MixReport(C.Structure):
                 ("overlap", C.c_uint64)]
 
 
+MIX_NO_STEM = 0xFFFFFFFF
+MIX_STEM_LEVELS = 1
+
+
+class StemReport(C.Structure):
+    """jb_stem_report: a stem's peak, its programme's scale and, with levels, the three sums and the dB values."""
+    _fields_ = [("peak", C.c_double), ("scale", C.c_double), ("e_s", C.c_double), ("d", C.c_double),
+                ("e_p", C.c_double), ("level_db", C.c_double), ("sir_db", C.c_double), ("si_sdr_db", C.c_double)]
+
+
+def stem_ids(stem_of):
+    """A (uint32 * n) array of stem ids; None: MIX_NO_STEM."""
+    return (C.c_uint32 * max(1, len(stem_of)))(*[MIX_NO_STEM if s is None else int(s) for s in stem_of])
+
+
 class MixPlace(C.Structure):
     """jb_mix_place: a member's start behind the lead in milliseconds, and its gain."""
     _fields_ = [("start_ms", C.c_double), ("gain_db", C.c_double)]
@@ -903,6 +918,10 @@ SYMBOLS = [
     "jb_batch_set_mix", "jb_batch_mix_report", "jb_mix_gain", "jb_mix_geometry", "jb_mix_host", "jb_mix_i16_host",
     "jb_mix_pcm_batch", "jb_mix_pcm_batch_i16", "jb_mix_free", "jb_engine_set_programme_mix",
     "jb_engine_get_programme_mix",
+    "jb_batch_set_mix_stems", "jb_batch_num_programmes", "jb_batch_stem_unit", "jb_batch_stem_layout",
+    "jb_batch_stem_report", "jb_mix_stems_geometry", "jb_mix_stems_host", "jb_mix_stems_i16_host",
+    "jb_mix_levels_host", "jb_mix_levels_i16_host", "jb_mix_levels_db", "jb_mix_stems_pcm_batch",
+    "jb_mix_stems_pcm_batch_i16", "jb_synthesize_programme_stems", "jb_synthesize_programme_stems_flac_meta",
     "jb_activity_geometry", "jb_activity_host", "jb_activity_members_host", "jb_activity_pcm_batch",
     "jb_activity_pcm_batch_i16", "jb_activity_free", "jb_batch_set_activity", "jb_batch_activity_shape",
     "jb_batch_activity_size", "jb_batch_read_activity", "jb_batch_read_activity_all", "jb_batch_activity_report",
@@ -1262,6 +1281,26 @@ def lib():
     L.jb_mix_pcm_batch_i16.argtypes = L.jb_mix_pcm_batch.argtypes
     L.jb_mix_free.argtypes = [vp]
     L.jb_mix_free.restype = None
+    strp, dbp, i64p = C.POINTER(StemReport), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    L.jb_batch_set_mix_stems.argtypes = [vp, u32p, sz, C.c_uint32]
+    L.jb_batch_num_programmes.argtypes = [vp]
+    L.jb_batch_num_programmes.restype = sz
+    L.jb_batch_stem_unit.argtypes = [vp, sz]
+    L.jb_batch_stem_unit.restype = C.c_int64
+    L.jb_batch_stem_layout.argtypes = [vp, sz, u32p, u32p, u32p, u64p, u64p]
+    L.jb_batch_stem_report.argtypes = [vp, sz, strp]
+    L.jb_mix_stems_geometry.argtypes = [mxup, u32p, C.POINTER(sz), u32p, sz, mxop, C.POINTER(sz), C.POINTER(sz), i64p,
+                                        u64p, u32p, u32p, u32p, u64p, u64p, u32p]
+    L.jb_mix_stems_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, mxup, u32p, C.c_uint32, mxop, dbp, C.POINTER(vp),
+                                    C.POINTER(sz), mxrp, strp]
+    L.jb_mix_stems_i16_host.argtypes = L.jb_mix_stems_host.argtypes
+    L.jb_mix_levels_host.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, dbp, dbp, dbp]
+    L.jb_mix_levels_i16_host.argtypes = L.jb_mix_levels_host.argtypes
+    L.jb_mix_levels_db.argtypes = [C.c_double, C.c_double, C.c_double, dbp, dbp, dbp]
+    L.jb_mix_levels_db.restype = None
+    L.jb_mix_stems_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, mxup, u32p, C.c_uint32, mxop, C.c_int32,
+                                         C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), mxrp, strp]
+    L.jb_mix_stems_pcm_batch_i16.argtypes = L.jb_mix_stems_pcm_batch.argtypes
     L.jb_engine_set_programme_mix.argtypes = [vp, C.POINTER(MixPlace), sz, mxop]
     L.jb_engine_get_programme_mix.argtypes = [vp, C.POINTER(MixPlace), sz, C.POINTER(sz), mxop]
     acop, acrp, acup = C.POINTER(ActivityOpts), C.POINTER(ActivityReport), C.POINTER(ActivityUnitReport)
@@ -1347,6 +1386,11 @@ def lib():
     lines, szp = C.POINTER(C.c_char_p), C.POINTER(sz)
     L.jb_synthesize_programme.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
     L.jb_synthesize_programme_i16.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(vp), szp, u64p]
+    L.jb_synthesize_programme_stems.argtypes = [vp, lines, szp, sz, C.c_int32, jop, u32p, C.c_uint32, C.POINTER(vp), szp,
+                                                szp, C.POINTER(StemReport), u64p]
+    L.jb_synthesize_programme_stems_flac_meta.argtypes = [vp, lines, szp, sz, C.c_int32, C.POINTER(FlacOpts),
+                                                          C.POINTER(FlacMeta), jop, u32p, C.c_uint32, C.POINTER(u8p),
+                                                          szp, szp, C.POINTER(StemReport), u64p]
     L.jb_synthesize_programme_activity.argtypes = [vp, lines, szp, sz, C.c_int32, jop, C.POINTER(ActivityOpts),
                                                    C.POINTER(vp), szp, C.POINTER(vp), u64p, u32p, u64p]
     L.jb_synthesize_programme_flac_meta.argtypes = [vp, lines, szp, sz, C.c_int32, C.POINTER(FlacOpts),
@@ -2096,6 +2140,88 @@ def mix_pcm(pcms, req, opts=None, device: int = -1):
                                                                   None if opts is None else C.byref(opts), device, outs,
                                                                   ns, C.byref(P), reps))
     return _take(L.jb_mix_free, outs, ns, P.value, np.int16 if i16 else np.float64), list(reps[:P.value])
+
+
+def mix_stems_geometry(req, stem_of, lengths, hz=None, opts=None):
+    """jb_mix_stems_geometry: a dict of P, the units' number U = P + S, stem_unit [n] (-1: none) and per unit
+    samples, programme, stem_id (MIX_NO_STEM for a programme), members, first, end and depth."""
+    n = len(lengths)
+    arr, ids = mix_request(req), stem_ids(stem_of)
+    nin = (C.c_size_t * max(n, 1))(*[int(x) for x in lengths])
+    hzs = None if hz is None else (C.c_uint32 * max(n, 1))(*[int(h) for h in hz])
+    m = max(2 * n, 1)
+    P, U, su = C.c_size_t(), C.c_size_t(), (C.c_int64 * max(n, 1))()
+    ns, fi, en = (C.c_uint64 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * m)()
+    pr, si, me, de = (C.c_uint32 * m)(), (C.c_uint32 * m)(), (C.c_uint32 * m)(), (C.c_uint32 * m)()
+    check(lib().jb_mix_stems_geometry(arr, ids, nin, hzs, n, None if opts is None else C.byref(opts), C.byref(P),
+                                      C.byref(U), su, ns, pr, si, me, fi, en, de))
+    u = U.value
+    return {"P": P.value, "U": u, "stem_unit": list(su[:n]), "samples": list(ns[:u]), "programme": list(pr[:u]),
+            "stem_id": list(si[:u]), "members": list(me[:u]), "first": list(fi[:u]), "end": list(en[:u]),
+            "depth": list(de[:u])}
+
+
+def mix_stems_host(pcms, req, stem_of, opts=None, scale=None, levels: bool = False):
+    """jb_mix_stems_host / _i16_host (by the arrays' dtype): (units, reports, stem_reports) -- the P programmes and the
+    S stems behind them, the MixReports [P] and the StemReports [S] -- by the rule in plain C++ on the host."""
+    import numpy as np
+
+    i16, arrs, n, ins, nin = _join_inputs(pcms)
+    arr, ids = mix_request(req), stem_ids(stem_of)
+    g = mix_stems_geometry(arr[:n], stem_of, [a.size for a in arrs])
+    outs = [np.empty(int(k), dtype=np.int16 if i16 else np.float64) for k in g["samples"]]
+    U, P = len(outs), g["P"]
+    optr = (C.c_void_p * max(U, 1))(*[o.ctypes.data if o.size else None for o in outs])
+    caps = (C.c_size_t * max(U, 1))(*[o.size for o in outs])
+    reps, sreps = (MixReport * max(P, 1))(), (StemReport * max(U - P, 1))()
+    sc = None if scale is None else (C.c_double * max(P, 1))(*[float(v) for v in scale])
+    L = lib()
+    check((L.jb_mix_stems_i16_host if i16 else L.jb_mix_stems_host)(
+        ins, nin, n, arr, ids, MIX_STEM_LEVELS * bool(levels), None if opts is None else C.byref(opts), sc, optr, caps,
+        reps, sreps))
+    return outs, list(reps[:P]), list(sreps[:U - P])
+
+
+def mix_stems_pcm(pcms, req, stem_of, opts=None, levels: bool = False, device: int = -1):
+    """jb_mix_stems_pcm_batch / _i16 (by the arrays' dtype): the same (units, reports, stem_reports), on the GPU."""
+    import numpy as np
+
+    i16, arrs, n, ins, nin = _join_inputs(pcms)
+    arr, ids = mix_request(req), stem_ids(stem_of)
+    m = max(2 * n, 1)
+    outs, ns, P, U = (C.c_void_p * m)(), (C.c_size_t * m)(), C.c_size_t(), C.c_size_t()
+    reps, sreps = (MixReport * max(n, 1))(), (StemReport * max(n, 1))()
+    L = lib()
+    check((L.jb_mix_stems_pcm_batch_i16 if i16 else L.jb_mix_stems_pcm_batch)(
+        ins, nin, n, arr, ids, MIX_STEM_LEVELS * bool(levels), None if opts is None else C.byref(opts), device, outs, ns,
+        C.byref(P), C.byref(U), reps, sreps))
+    return (_take(L.jb_mix_free, outs, ns, U.value, np.int16 if i16 else np.float64), list(reps[:P.value]),
+            list(sreps[:U.value - P.value]))
+
+
+def mix_levels_host(stem, mix, first: int = 0, end=None):
+    """jb_mix_levels_host / _i16_host (by the arrays' dtype): (E_s, D, E_p) of a stem and its mixture by the stage's
+    summation order; [first, end): the stem's extent (default: the whole length)."""
+    import numpy as np
+
+    i16 = np.asarray(stem).dtype == np.int16
+    a = np.ascontiguousarray(stem, dtype=np.int16 if i16 else np.float64)
+    m = np.ascontiguousarray(mix, dtype=a.dtype)
+    if a.size != m.size:
+        raise ValueError("the stem and the mixture have one length")
+    e, d, p = C.c_double(), C.c_double(), C.c_double()
+    L = lib()
+    check((L.jb_mix_levels_i16_host if i16 else L.jb_mix_levels_host)(
+        a.ctypes.data if a.size else None, m.ctypes.data if m.size else None, a.size, int(first),
+        a.size if end is None else int(end), C.byref(e), C.byref(d), C.byref(p)))
+    return e.value, d.value, p.value
+
+
+def mix_levels_db(e_s: float, d: float, e_p: float):
+    """jb_mix_levels_db: (level_db, sir_db, si_sdr_db) of the three sums, formed in long double."""
+    a, b, c = C.c_double(), C.c_double(), C.c_double()
+    lib().jb_mix_levels_db(float(e_s), float(d), float(e_p), C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
 
 
 def activity_geometry(opts, hz: int, n: int):

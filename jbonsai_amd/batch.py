@@ -720,7 +720,8 @@ class Batch:
 
     def read_activity_all(self):
         """Every unit's labels through one device-to-host copy (jb_batch_read_activity_all)."""
-        shapes = [self.activity_shape(i)[:2] for i in range(self.num_outputs())]
+        # (the stems of a mix are no units of this stage: it keeps the programmes)
+        shapes = [self.activity_shape(i)[:2] for i in range(self.num_programmes())]
         outs = [np.zeros(max(T * c, 1), dtype=np.uint8) for T, c in shapes]
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
         F.check(self._L.jb_batch_read_activity_all(self._h, ptrs))
@@ -765,8 +766,41 @@ class Batch:
         F.check(self._L.jb_batch_mix_report(self._h, p, C.byref(r)))
         return r
 
+    def set_mix_stems(self, stem_of, levels: bool = False):
+        """jb_batch_set_mix_stems, behind set_mix and before the first run: stem_of[u] is utterance u's stem id within
+        its programme, or None for no stem; members of one programme with the same id form one stem, a unit behind the
+        programmes (num_outputs is then P + S).  levels: the three sums and the dB values of stem_report.  None
+        withdraws the request."""
+        if stem_of is None:
+            F.check(self._L.jb_batch_set_mix_stems(self._h, None, 0, 0))
+            return
+        F.check(self._L.jb_batch_set_mix_stems(self._h, F.stem_ids(stem_of), len(stem_of),
+                                               F.MIX_STEM_LEVELS * bool(levels)))
+
+    def num_programmes(self) -> int:
+        """P: the programmes among the outputs (jb_batch_num_programmes); the stems follow them."""
+        return self._L.jb_batch_num_programmes(self._h)
+
+    def stem_unit(self, u) -> int:
+        """The unit of utterance u's stem, or -1 (jb_batch_stem_unit)."""
+        return int(self._L.jb_batch_stem_unit(self._h, u))
+
+    def stem_layout(self, unit):
+        """(programme, stem_id, members, first_sample, end_sample) of a stem's unit (jb_batch_stem_layout)."""
+        p, i, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        a, e = C.c_uint64(), C.c_uint64()
+        F.check(self._L.jb_batch_stem_layout(self._h, unit, C.byref(p), C.byref(i), C.byref(m), C.byref(a), C.byref(e)))
+        return p.value, i.value, m.value, a.value, e.value
+
+    def stem_report(self, unit):
+        """jb_batch_stem_report: the F.StemReport of a stem's unit, after a run."""
+        r = F.StemReport()
+        F.check(self._L.jb_batch_stem_report(self._h, unit, C.byref(r)))
+        return r
+
     def num_outputs(self) -> int:
-        """What the encoders' entries index: the programmes with a join request, else the utterances."""
+        """What the encoders' entries index: the utterances; with a join or mix request the P programmes, and with
+        a stems request behind a mix the P programmes and the S stems behind them (P + S)."""
         return self._L.jb_batch_num_outputs(self._h)
 
     def programme_of(self, i) -> int:

@@ -3075,6 +3075,51 @@ int jb_batch_mix_report(jb_batch *hb, size_t p, jb_mix_report *out)
     return b->out.read_mix(p, out);
 }
 
+int jb_batch_set_mix_stems(jb_batch *hb, const uint32_t *stem_of, size_t n, uint32_t flags)
+{
+    return hb ? ((Batch *)hb)->out.set_mix_stems(stem_of, n, flags) : JB_ERR_INVALID;
+}
+
+size_t jb_batch_num_programmes(const jb_batch *hb) { return hb ? ((const Batch *)hb)->out.num_programmes() : 0; }
+
+int64_t jb_batch_stem_unit(const jb_batch *hb, size_t utt)
+{
+    const Batch *b = (const Batch *)hb;
+    return (b && utt < (size_t)b->B) ? b->out.stem_unit(utt) : -1;
+}
+
+int jb_batch_stem_layout(const jb_batch *hb, size_t unit, uint32_t *programme, uint32_t *stem_id, uint32_t *n_members,
+                         uint64_t *first_sample, uint64_t *end_sample)
+{
+    const Batch *b = (const Batch *)hb;
+    if (!b)
+        return JB_ERR_INVALID;
+    const jb::MixStem *st = b->out.stem(unit);
+    if (!st) {
+        jb::set_error("jb_batch_stem_layout: no such stem (unit " + std::to_string(unit) + ")");
+        return JB_ERR_INVALID;
+    }
+    if (programme)
+        *programme = st->programme;
+    if (stem_id)
+        *stem_id = st->id;
+    if (n_members)
+        *n_members = st->n_members;
+    if (first_sample)
+        *first_sample = st->first;
+    if (end_sample)
+        *end_sample = st->end;
+    return JB_OK;
+}
+
+int jb_batch_stem_report(jb_batch *hb, size_t unit, jb_stem_report *out)
+{
+    Batch *b = (Batch *)hb;
+    if (!b || !out)
+        return JB_ERR_INVALID;
+    return b->out.read_stem(unit, out);
+}
+
 size_t jb_batch_num_outputs(const jb_batch *hb) { return hb ? ((const Batch *)hb)->out.num_outputs() : 0; }
 
 int32_t jb_batch_programme_of(const jb_batch *hb, size_t utt)

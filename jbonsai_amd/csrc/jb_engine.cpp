@@ -1692,6 +1692,7 @@ struct SynthRun {
     int create_batch(size_t g);
     int apply_conditions(jb::OutputChain &out, size_t lo, size_t hi);
     int request_programme(jb::OutputChain &out, size_t lo, size_t hi);
+    int read_stem_reports(jb::Batch *b);
     int launch(size_t g);
     int wait_group(size_t g);
     int read_group(size_t g);
@@ -1947,7 +1948,9 @@ int SynthRun::request_programme(jb::OutputChain &out, size_t lo, size_t hi)
             jreq[u].pad_after = jb::join_ms_to_samples(u + 1 == n ? join->trail_ms : join->gap_ms, hz);
         }
     }
-    const int rc = mix ? out.set_mix(mreq.data(), n, &c0.mix_opts) : out.set_join(jreq.data(), n);
+    int rc = mix ? out.set_mix(mreq.data(), n, &c0.mix_opts) : out.set_join(jreq.data(), n);
+    if (!rc && rq.stem_of) // (the entry has checked that the engine holds a mix)
+        rc = out.set_mix_stems(rq.stem_of + lo, n, rq.stem_flags);
     if (rc)
         return rc;
     for (size_t u = 0; rq.join_starts && u < n; u++)
@@ -1991,6 +1994,22 @@ int SynthRun::read_group(size_t g)
     return rc;
 }
 
+// With a stems request: the number of outputs and each stem's report to the caller
+int SynthRun::read_stem_reports(jb::Batch *b)
+{
+    if (!rq.stem_of)
+        return JB_OK;
+    const size_t U = b->out.num_outputs(), P = b->out.num_programmes();
+    for (size_t p = P; rq.stem_reports && p < U; p++) {
+        const int rc = b->out.read_stem(p, rq.stem_reports + (p - P));
+        if (rc)
+            return rc;
+    }
+    if (rq.n_outputs) // (last: a call that fails hands out nothing and says so)
+        *rq.n_outputs = U;
+    return JB_OK;
+}
+
 // read_group: what the request's sink and join hand out for the utterances [lo, hi) of batch b
 int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
 {
@@ -2014,7 +2033,22 @@ int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
                                 : rq.sink == jb::SynthSink::Melspec ? (size_t)b->out.melspec_place(p).T
                                 : rq.join                        ? (size_t)b->out.programme(p).n
                                                                  : b->out.samples(p);
-        return JB_OK;
+        return read_stem_reports(b);
+    }
+    if (rq.join && rq.stem_of) {
+        // the mixture and the stems behind it, unit after unit
+        for (size_t p = 0; p < b->out.num_outputs(); p++) {
+            const size_t ns = (size_t)b->out.programme(p).n;
+            if (!(pcm[p] = malloc(std::max<size_t>(ns, 1) * elem))) {
+                jb::set_error("out of host memory");
+                return JB_ERR_INVALID;
+            }
+            n_samples[p] = ns;
+            const int rc = b->out.read_programme(p, elem == 2, pcm[p]);
+            if (rc)
+                return rc;
+        }
+        return read_stem_reports(b);
     }
     if (rq.join) {
         // the programme's PCM in one copy
@@ -2127,7 +2161,10 @@ int jb::synthesize_batch_impl(const SynthRequest &rq)
     if (!rq.e || !rq.out || !rq.n_out || (rq.n_utts && !rq.line_off))
         return JB_ERR_INVALID;
     // with a join the call hands out ONE output, the programme of all its utterances
-    const size_t n_outs = rq.join ? 1 : rq.n_utts;
+    // (with a stems request the mixture and at most one stem per utterance behind it)
+    const size_t n_outs = rq.join ? (rq.stem_of ? 1 + rq.n_utts : 1) : rq.n_utts;
+    if (rq.n_outputs)
+        *rq.n_outputs = 0;
     for (size_t u = 0; u < n_outs; u++) {
         rq.out[u] = nullptr;
         rq.n_out[u] = 0;
@@ -2164,6 +2201,8 @@ int jb::synthesize_batch_impl(const SynthRequest &rq)
     }
     if (rc) {
         run.batches.clear();
+        if (rq.n_outputs)
+            *rq.n_outputs = 0;
         for (size_t u = 0; u < n_outs; u++) {
             free(rq.out[u]);
             rq.out[u] = nullptr;
@@ -2669,6 +2708,57 @@ int jb_synthesize_programme(const jb_engine *e, const char *const *lines, const 
 {
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
     return synthesize_entry("jb_synthesize_programme", request_join(rq, join, starts), nullptr, true);
+}
+
+// The stems' entries: the engine's mix with a stems request behind it.  Refused before any device is touched without a
+// mix (jb_engine_set_programme_mix), without ids, with an unknown flag or an id of n_utts or above
+static int stems_entry(const char *who, jb::SynthRequest &rq, const uint32_t *stem_of, uint32_t flags, size_t *n_outputs,
+                       jb_stem_report *reports)
+{
+    auto refuse = [&](const std::string &what) {
+        jb::set_error(std::string(who) + ": " + what);
+        return JB_ERR_INVALID;
+    };
+    if (n_outputs)
+        *n_outputs = 0;
+    if (!rq.e || !n_outputs)
+        return JB_ERR_INVALID;
+    if (CENG(rq.e)->cond.mix_place.empty())
+        return refuse("the engine holds no mix (jb_engine_set_programme_mix comes first)");
+    if (!stem_of)
+        return refuse("give one stem id per utterance");
+    if (flags & ~JB_MIX_STEM_LEVELS)
+        return refuse("flags holds an unknown flag");
+    for (size_t u = 0; u < rq.n_utts; u++)
+        if (stem_of[u] != JB_MIX_NO_STEM && stem_of[u] >= rq.n_utts)
+            return refuse("stem_of of utterance " + std::to_string(u) + " (" + std::to_string(stem_of[u]) +
+                          "): a stem id is below the number of utterances, or JB_MIX_NO_STEM");
+    rq.stem_of = stem_of;
+    rq.stem_flags = flags;
+    rq.n_outputs = n_outputs;
+    rq.stem_reports = reports;
+    return synthesize_entry(who, rq, nullptr, true);
+}
+
+int jb_synthesize_programme_stems(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                  int32_t device, const jb_join_opts *join, const uint32_t *stem_of, uint32_t flags,
+                                  double **pcm, size_t *n_samples, size_t *n_outputs, jb_stem_report *reports,
+                                  uint64_t *starts)
+{
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)pcm, n_samples);
+    return stems_entry("jb_synthesize_programme_stems", request_join(rq, join, starts), stem_of, flags, n_outputs,
+                       reports);
+}
+
+int jb_synthesize_programme_stems_flac_meta(const jb_engine *e, const char *const *lines, const size_t *line_off,
+                                            size_t n_utts, int32_t device, const jb_flac_opts *opts,
+                                            const jb_flac_meta *meta, const jb_join_opts *join, const uint32_t *stem_of,
+                                            uint32_t flags, uint8_t **flac, size_t *n_bytes, size_t *n_outputs,
+                                            jb_stem_report *reports, uint64_t *starts)
+{
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)flac, n_bytes);
+    request_join(request_flac(rq, opts, meta), join, starts);
+    return stems_entry("jb_synthesize_programme_stems_flac_meta", rq, stem_of, flags, n_outputs, reports);
 }
 
 int jb_synthesize_programme_activity(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,

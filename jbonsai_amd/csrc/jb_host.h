@@ -78,7 +78,12 @@ struct SynthRequest {
     uint8_t **act_out = nullptr;             // into act_out[0] (malloc'ed), their frames and columns into act_T[0]
     uint64_t *act_T = nullptr;               // and act_C[0]
     uint32_t *act_C = nullptr;
-    void **out = nullptr;                    // [n_utts], or [1] with a join: malloc'ed PCM or bytes of each output
+    const uint32_t *stem_of = nullptr;       // jb_synthesize_programme_stems*: [n_utts] the stems request behind the
+    uint32_t stem_flags = 0;                 // engine's mix (JB_MIX_STEM_LEVELS); the outputs are then the mixture and
+    size_t *n_outputs = nullptr;             // the S stems behind it, *n_outputs = 1 + S, and stem_reports[0 .. S)
+    jb_stem_report *stem_reports = nullptr;  // ([n_utts], may be null) each stem's report
+    void **out = nullptr;                    // [n_utts], or [1] with a join ([1 + n_utts] with stems): malloc'ed PCM or
+                                             // bytes of each output
     size_t *n_out = nullptr;                 // its samples (Pcm) or bytes
 };
 int synthesize_batch_impl(const SynthRequest &rq);
@@ -422,14 +427,15 @@ hipError_t launch_mfcc(const MfccParams &P, const MfccUtt *utts_dev, uint32_t n,
 // mix_layout with the request's and the options' fields checked and set_error naming what is wrong (JB_ERR_INVALID;
 // lists past kMixMaxList entries: JB_ERR_UNSUPPORTED).  opts may be null.  `chained`: req is a join's (join_as_mix),
 // and the refusals are worded for the join
+// stem_of: [B] the stems request behind a mix's (jb_mix.h "Stems"; with `chained`: refused), nullptr: none
 int mix_layout_checked(const MixUtt *req, bool chained, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
-                       const MixOpts *opts, MixLayout *out, const char *who);
+                       const MixOpts *opts, MixLayout *out, const char *who, const uint32_t *stem_of = nullptr);
 // The same from the join's own request
 int join_layout_checked(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem,
                         MixLayout *out, const char *who);
 // The lists of a run: members[i] for the layout's members[i] (utterance u's samples at x + xoff[u] elements) and one
-// span per programme, whole (programme p at y + units[p].off elements); *tiles their tiles, the peak scratch's slots /
-// kMixWaves
+// span per unit, whole (unit p at y + units[p].off elements; the stems behind the programmes); *tiles their tiles, the
+// peak scratch's slots / kMixWaves
 void mix_lists(const MixLayout &lay, const MixUtt *req, const uint64_t *n, const uint64_t *xoff, const void *x, void *y,
                size_t elem, std::vector<ProgMember> *members, std::vector<ProgSpan> *spans, uint64_t *tiles);
 // The join's launch over the same members and spans (k_join reads neither the segments nor the gains): spans_dev[0..n)
@@ -445,10 +451,39 @@ struct MixLaunch {
     MixResult *res;    // by the spans' prog
     bool fit;          // kMixFit: the second pass follows
     double ceiling;    // in sample units, with fit
+    uint32_t stems;      // the last `stems` spans of the list are stems (they stand behind the programmes), of
+    uint64_t stem_tiles; // `stem_tiles` tiles: with fit they take their programme's scale and are not clamped
 };
 // spans_dev[0..n) of `tiles` tiles in all: k_mix, k_mix_peak and with fit k_mix again over the programmes of s != 1
+// and the stems of such programmes
 hipError_t launch_mix(bool i16, const ProgSpan *spans_dev, uint32_t n, uint64_t tiles, const MixLaunch &L,
                       hipStream_t stream);
+// The level items of the units picked by mask ([P + S]; empty: all): one per stem over the tiles of its extent, one
+// per programme that has a stem over all of its tiles (unit p at y + units[p].off elements); t0 counted from 0 over
+// the list, s0 the full numbering's (a redo keeps it); *tiles: the list's tiles.  scratch (may be null): the full
+// numbering's tiles
+void mix_level_items(const MixLayout &lay, const void *y, size_t elem, const std::vector<uint8_t> &mask,
+                     std::vector<LevelItem> *items, uint64_t *tiles, uint64_t *scratch);
+// A stem's report from what the device left: its peak, its programme's scale and, with levels, the sums (its own pair
+// and its programme's E_p) and the dB values the host derives from them
+inline jb_stem_report stem_report_of(double peak, double scale, bool levels, MixSums own, double e_p)
+{
+    jb_stem_report r{};
+    r.peak = peak;
+    r.scale = scale;
+    r.level_db = r.sir_db = r.si_sdr_db = NAN;
+    if (levels) {
+        r.e_s = own.e;
+        r.d = own.d;
+        r.e_p = e_p;
+        level_db_of(r.e_s, r.d, r.e_p, &r.level_db, &r.sir_db, &r.si_sdr_db);
+    }
+    return r;
+}
+// k_mix_levels over the `tiles` tiles of items_dev[0..n) and the fold: tile_sums two doubles per tile by the items'
+// s0, sums by the items' unit
+hipError_t launch_mix_levels(bool i16, const LevelItem *items_dev, uint32_t n, uint64_t tiles, double *tile_sums,
+                             MixSums *sums, hipStream_t stream);
 
 // The speech-activity stage (jb_activity.hip; the rules, ActCol and ActUnit: jb_activity.h; the host half:
 // jb_activity.cpp).  opts checked with set_error naming the field under the entry `who` (null: refused)
@@ -872,6 +907,19 @@ struct OutputChain {
     // request is withdrawn.  Checked as set_join's; a batch holds a join or a mix request, the second setter is refused
     int set_mix(const jb_mix_utt *req, size_t n, const jb_mix_opts *opts);
     int read_mix(size_t p, jb_mix_report *out); // after sync
+    // The stems request behind a mix's (jb_mix.h "Stems"): one id per utterance, or JB_MIX_NO_STEM; flags:
+    // JB_MIX_STEM_LEVELS.  Null and 0 withdraw it, and so does withdrawing the mix.  Checked with the mix under the
+    // present rates; refused without a mix request (or over a join)
+    int set_mix_stems(const uint32_t *stem_of, size_t n, uint32_t flags);
+    int read_stem(size_t unit, jb_stem_report *out); // after sync
+    size_t num_programmes() const { return joined() ? plan.n_progs : plan.utt.size(); }
+    int64_t stem_unit(size_t u) const { return plan.stem_unit.empty() ? -1 : plan.stem_unit[u]; }
+    const MixStem *stem(size_t unit) const // null: the unit is no stem
+    {
+        return joined() && unit >= plan.n_progs && unit - plan.n_progs < plan.stems.size()
+                   ? &plan.stems[unit - plan.n_progs]
+                   : nullptr;
+    }
     // the cepstral features behind a filterbank pass of their own (jb_mfcc.h): an f64 batch only; the filterbank
     // options checked at every utterance's output rate (both NULL: the request is withdrawn); set_output_rate checks
     // the combined request again.  Independent of set_fbank
@@ -971,7 +1019,10 @@ struct OutputChain {
     int32_t programme_of(size_t u) const { return joined() ? (int32_t)plan.prog_of[u] : -1; }
     uint64_t member_start(size_t u) const { return plan.prog_start[u]; }
     const OutUnit &programme(size_t p) const { return plan.units[p]; }
-    size_t programme_members(size_t p) const { return plan.prog_first[p + 1] - plan.prog_first[p]; }
+    size_t programme_members(size_t p) const // (a stem's unit: the members under its id)
+    {
+        return p < plan.n_progs ? plan.prog_first[p + 1] - plan.prog_first[p] : plan.stems[p - plan.n_progs].n_members;
+    }
     int read_programme(size_t p, bool i16, void *dst);
 
 private:
@@ -997,6 +1048,8 @@ private:
     std::vector<MixUtt> prog_req;              // [B] the programme request, a join's (join_as_mix) or a mix's; empty: none
     bool prog_chained = false;                 // it is a join's: its starts count from the member in front
     MixOpts mix_opts{};                        // a mix's options
+    std::vector<uint32_t> stem_req;            // [B] the stems request behind a mix's; empty: none
+    uint32_t stem_flags = 0;                   // kMixStemLevels
     std::vector<jb_filter> filt_req;           // [B] the filter request; empty: none
     std::vector<uint8_t> filt_any;             // [B] 1 = that utterance's filter has a section
     FirClasses fir_cls;                        // the distinct responses of the convolution request (its copies)
@@ -1086,6 +1139,14 @@ private:
         DevList<ProgSpan> spans;         // [P] every programme whole (a join's redo: one span per member)
         MixLaunch L{};                   // the members; with a mix the segments and their lists, the peak scratch, the results
         uint64_t tiles = 0;
+        // with a stems request and its levels: the items of a full run (a redo: those of the touched units), the
+        // tile sums by the full numbering and the sums per unit; lay: the layout's units, stems and programme count
+        // alone (what mix_level_items reads), empty without levels
+        MixLayout lay;
+        DevList<LevelItem> items;
+        uint64_t level_tiles = 0;
+        double *tile_sums = nullptr;
+        MixSums *sums = nullptr;
     } pg;
     struct Flac { // follows `units`, by work item; the pack takes every stream
         DevList<FlacWork> work;
@@ -1185,8 +1246,10 @@ private:
     int check_groups(const std::vector<uint32_t> &group, const std::vector<double> &target,
                      const std::vector<double> &ceiling, const std::vector<uint32_t> &mode,
                      const std::vector<uint32_t> &want, const char *who, LnGroups *out) const;
+    // (stems: the stems request to check with it; null: the one the chain holds)
     int check_programme(const std::vector<MixUtt> &req, bool chained, const MixOpts &opts,
-                        const std::vector<uint32_t> &want, const char *who) const;
+                        const std::vector<uint32_t> &want, const char *who,
+                        const std::vector<uint32_t> *stems = nullptr) const;
     // the one slot of set_join and set_mix: the checks in front of the request, and the request stored
     int open_programme(bool chained, bool given, size_t n, bool *store);
     int store_programme(bool chained, std::vector<MixUtt> req, const MixOpts &opts);

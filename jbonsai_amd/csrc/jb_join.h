@@ -45,14 +45,15 @@ struct ProgMember {
 // the programme's end.  A run lists every programme whole, and so does a mix's redo; a join's redo lists the spans of
 // the members that changed.  t0 is the prefix sum of the list's tiles (tiles never cross spans), pk0 the programme's
 // first tile in the mix's peak scratch (the full run's numbering: a redo keeps it); the programme owns
-// members[m0 .. m0 + nm), nm >= 1, and segs[s0 .. s0 + ns) (jb_mix.h)
+// members[m0 .. m0 + nm), nm >= 1, and segs[s0 .. s0 + ns) (jb_mix.h).  A stem of a mix (jb_mix.h) is a span like any
+// other, with its programme's members, segments of its own and `parent` naming the programme whose scale it takes
 struct ProgSpan {
     void *y;    // the programme's first sample in its slab, 16-byte aligned
     uint64_t n; // the programme's samples
     uint64_t k0, k1, t0, pk0;
     uint32_t m0, nm;
     uint32_t s0, ns;
-    uint32_t prog, reserved;
+    uint32_t prog, parent; // (a programme: parent == prog)
 };
 
 // tiles of a span [k0, k1) of 16-bit or f64 samples

@@ -119,4 +119,104 @@ JB_JOIN_HD void mix_store(double v, int16_t *o)
     *o = (int16_t)(int32_t)v;
 }
 
+// ---- Stems (jb_batch_set_mix_stems): the members of one programme that carry the same stem id form one stem, a unit
+// of the programme's length and rate behind the programmes.  Sample k of a stem is mix_acc over the stem's own members
+// alone -- ascending utterance index, the first term starts the sum, acc + t behind it, +0.0 under none: the mix rule
+// over a subset.  With kMixFit and s_p != 1 the stored value is acc * s_p, s_p the PROGRAMME's scale; a stem has no
+// scale of its own and is not held under the ceiling (a stem may peak above its mixture; a clamp would break
+// additivity).  The 16-bit sink clamps and truncates as it always does.
+// So, in f64 with s_p == 1 and every unmuted member under an id: at a sample under at most two members the stems added
+// in unit order equal the mixture (==); under a depth d only the association differs, |sum - mix| <= (d - 1) 2^-52
+// sum |t|; in 16 bits, where no term and no sum leaves [-32768, 32767], the stems' sum is within d counts.
+constexpr uint32_t kMixNoStem = 0xffffffffu; // JB_MIX_NO_STEM: the utterance belongs to no stem
+constexpr uint32_t kMixStemLevels = 1u;      // JB_MIX_STEM_LEVELS
+JB_JOIN_HD double mix_stem_fit(double acc, double s) { return acc * s; }
+
+// One stem of a layout (unit P + its index)
+struct MixStem {
+    uint32_t programme, id; // the dense programme, the caller's id
+    uint32_t n_members, reserved; // members that carry the id, muted ones and those of no samples included
+    uint64_t first, end;    // [first, end): from the first sample to behind the last one of its unmuted members of at
+                            // least one sample; 0, 0 without one
+};
+
+// ---- Levels (kMixStemLevels): E_s = sum s[k]^2, D = sum s[k] m[k] over the programme's tiles that touch the stem's
+// extent, E_p = sum m[k]^2 over all of the programme's tiles, of the units as stored (a 16-bit sample enters as its
+// (double)).  The order is the noise stage's (jb_noise.h), stated again here (this header is compiled where that one is
+// not): tiles of kLevelTile samples in programme coordinates; partial l of tile i takes the samples
+// i kLevelTile + l + kLevelLanes j, j = 0, 1, ... below the programme's length: the first product starts it, each later
+// one is fused on (fma), a partial without a sample is +0.0; the partials fold by p[l] = p[l] + p[l + h], h = 128 ... 1;
+// the tile sums are added in ascending order, the first tile starts the sum (no tile: +0.0)
+constexpr uint32_t kLevelTile = 1024, kLevelLanes = 256, kLevelWave = 64;
+constexpr uint64_t level_tiles(uint64_t n) { return (n + kLevelTile - 1) / kLevelTile; }
+// the tiles [*t0, *t0 + count) of a programme of n samples that touch [first, end)
+JB_JOIN_HD uint64_t level_extent_tiles(uint64_t first, uint64_t end, uint64_t *t0)
+{
+    *t0 = first / kLevelTile;
+    return end > first ? (end + kLevelTile - 1) / kLevelTile - *t0 : 0;
+}
+// at(k, &a, &b): the two factors of sample k
+template <class Z> JB_JOIN_HD double level_partial(uint64_t N, uint64_t i, uint32_t l, Z at)
+{
+    double p = 0.0;
+    bool first = true;
+    for (uint32_t j = 0; j < kLevelTile / kLevelLanes; j++) {
+        const uint64_t k = i * kLevelTile + l + (uint64_t)kLevelLanes * j;
+        if (k >= N)
+            break;
+        double a, b;
+        at(k, &a, &b);
+        p = first ? a * b : __builtin_fma(a, b, p);
+        first = false;
+    }
+    return p;
+}
+// What the fold leaves of one unit: a stem's E_s and D, a programme's E_p (twice)
+struct MixSums {
+    double e, d;
+};
+// One item of a level launch: the sums of unit `unit` (a of N samples) against its programme m over the tiles
+// [tile0, tile0 + nt) in programme coordinates; a programme's own item has a == m.  t0: the prefix sum of the list's
+// tiles, s0: the item's first tile in the tile-sum scratch
+struct LevelItem {
+    const void *a, *m;
+    uint64_t n, tile0, nt, t0, s0;
+    uint32_t unit, self;
+};
+// The host's statement of the whole order: sum a[k] b[k] over the tiles [t0, t0 + nt) of units of N samples
+template <class T> inline double level_sum_host(const T *a, const T *b, uint64_t N, uint64_t t0, uint64_t nt)
+{
+    double S = 0.0;
+    for (uint64_t i = t0; i < t0 + nt; i++) {
+        double p[kLevelLanes];
+        for (uint32_t l = 0; l < kLevelLanes; l++)
+            p[l] = level_partial(N, i, l, [&](uint64_t k, double *x, double *y) {
+                *x = (double)a[k];
+                *y = (double)b[k];
+            });
+        for (uint32_t h = kLevelLanes / 2; h; h >>= 1)
+            for (uint32_t l = 0; l < h; l++)
+                p[l] = p[l] + p[l + h];
+        S = i == t0 ? p[0] : S + p[0];
+    }
+    return S;
+}
+// The three dB values of a stem report, from the three sums, in long double: +INFINITY where a denominator is not above
+// 0, -INFINITY where E_s == 0 (a host function)
+inline void level_db_of(double e_s, double d, double e_p, double *level, double *sir, double *si_sdr)
+{
+    const long double Es = e_s, D = d, Ep = e_p;
+    auto db = [&](long double num, long double den) {
+        if (e_s == 0.0)
+            return -(double)INFINITY;
+        if (!(den > 0.0L))
+            return (double)INFINITY;
+        return (double)(10.0L * log10l(num / den));
+    };
+    *level = db(Es, Ep);
+    *sir = db(Es, Ep - 2.0L * D + Es);
+    const long double a = e_s == 0.0 ? 0.0L : D * D / Es;
+    *si_sdr = db(a, Ep - a);
+}
+
 } // namespace jb

@@ -87,12 +87,20 @@ OutPlan plan_output(const OutPlanIn &in)
         for (size_t u = 0; u < in.B; u++)
             n[u] = p.utt[u].n;
         MixLayout lay;
-        if (mix_layout(request, n.data(), nullptr, in.B, p.final.i16 ? 2 : 8, &lay, nullptr, nullptr, chained)) {
+        if (mix_layout(request, n.data(), nullptr, in.B, p.final.i16 ? 2 : 8, &lay, nullptr, nullptr, chained,
+                       chained ? nullptr : in.stem_of)) {
             p.join_src = p.final;
             p.join = {p.final.i16 ? OutSlab::Join16 : OutSlab::Join64, p.final.i16};
             p.mixed = !chained;
-            for (size_t g = 0; g < lay.units.size(); g++)
+            p.n_progs = lay.programmes();
+            for (size_t g = 0; g < p.n_progs; g++)
                 lay.units[g].hz = p.utt[lay.progs.members[lay.progs.first[g]]].hz;
+            for (size_t s = 0; s < lay.stems.size(); s++) { // a stem has its programme's rate
+                lay.units[p.n_progs + s].hz = lay.units[lay.stems[s].programme].hz;
+                p.unit_parent.push_back(lay.stems[s].programme);
+            }
+            p.stems = std::move(lay.stems);
+            p.stem_unit = std::move(lay.stem_unit);
             p.units = lay.units;
             p.prog_of = std::move(lay.progs.group_of);
             p.prog_first = std::move(lay.progs.first);
@@ -213,7 +221,7 @@ OutPlan plan_output(const OutPlanIn &in)
     // member's own final PCM at its start, or one column on the unit's PCM (a request that some unit refuses is no
     // request: the chain has checked it)
     if (in.activity) {
-        const size_t U = units.size();
+        const size_t U = joined ? p.n_progs : units.size(); // (a mix's stems are no units of this stage: it reads members)
         std::vector<uint64_t> unit_n(U), n(in.B), start(in.B, 0);
         std::vector<uint32_t> unit_hz(U), first(U + 1), members(in.B);
         std::vector<double> gain(in.B, 1.0);
@@ -266,7 +274,7 @@ bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size
 }
 
 bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, MixLayout *out,
-                uint32_t *bad, const char **field, bool chained)
+                uint32_t *bad, const char **field, bool chained, const uint32_t *stem_of)
 {
     // the numbering and the agreement on the rate are the loudness groups'
     static_assert(kMixNone == kLnNoGroup && kJoinNone == kLnNoGroup, "one numbering for groups and programmes");
@@ -305,6 +313,38 @@ bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t
     };
     std::vector<Event> ev;
     std::vector<uint32_t> cover; // ascending places: ascending utterance indices
+    // the sweep over the events of unit g of `len` samples: a segment ends at every event; between two the cover stands
+    auto sweep = [&](size_t g, uint64_t len) {
+        std::stable_sort(ev.begin(), ev.end(), [](const Event &a, const Event &b) { return a.k < b.k; });
+        cover.clear();
+        uint64_t k = 0;
+        auto emit = [&](uint64_t to) {
+            if (to <= k)
+                return true;
+            if (lay.lists.size() + cover.size() > kMixMaxList)
+                return false;
+            lay.segs.push_back({k, to, (uint32_t)lay.lists.size(), (uint32_t)cover.size()});
+            lay.lists.insert(lay.lists.end(), cover.begin(), cover.end());
+            lay.depth[g] = std::max<uint32_t>(lay.depth[g], (uint32_t)cover.size());
+            if (cover.size() >= 2)
+                lay.overlap[g] += to - k;
+            k = to;
+            return true;
+        };
+        for (const Event &e : ev) {
+            if (!emit(e.k))
+                return false;
+            const auto it = std::lower_bound(cover.begin(), cover.end(), e.at);
+            if (e.add)
+                cover.insert(it, e.at);
+            else
+                cover.erase(it);
+        }
+        if (!emit(len)) // (the pads behind the last member's end: silence)
+            return false;
+        lay.seg_first[g + 1] = (uint32_t)lay.segs.size();
+        return true;
+    };
     for (size_t g = 0; g < P; g++) {
         OutUnit &w = lay.units[g];
         w.off = lay.total;
@@ -329,47 +369,72 @@ bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t
         if (lay.total >= kMaxLen || w.n + align >= kMaxLen - lay.total)
             return refuse((uint32_t)g, "slab length");
         lay.total = (w.off + w.n + align - 1) / align * align;
-        // the sweep: a segment ends at every event; between two the cover stands
-        std::stable_sort(ev.begin(), ev.end(), [](const Event &a, const Event &b) { return a.k < b.k; });
-        cover.clear();
-        uint64_t k = 0;
-        auto emit = [&](uint64_t to) {
-            if (to <= k)
-                return true;
-            if (lay.lists.size() + cover.size() > kMixMaxList)
-                return false;
-            lay.segs.push_back({k, to, (uint32_t)lay.lists.size(), (uint32_t)cover.size()});
-            lay.lists.insert(lay.lists.end(), cover.begin(), cover.end());
-            lay.depth[g] = std::max<uint32_t>(lay.depth[g], (uint32_t)cover.size());
-            if (cover.size() >= 2)
-                lay.overlap[g] += to - k;
-            k = to;
-            return true;
-        };
-        for (const Event &e : ev) {
-            if (!emit(e.k))
-                return refuse((uint32_t)g, "work lists");
-            const auto it = std::lower_bound(cover.begin(), cover.end(), e.at);
-            if (e.add)
-                cover.insert(it, e.at);
-            else
-                cover.erase(it);
-        }
-        if (!emit(w.n)) // (the pads behind the last member's end: silence)
+        if (!sweep(g, w.n))
             return refuse((uint32_t)g, "work lists");
-        lay.seg_first[g + 1] = (uint32_t)lay.segs.size();
+    }
+    // the stems behind the programmes: by programme, within one by each stem's first member
+    if (stem_of) {
+        for (size_t u = 0; u < B; u++)
+            if (stem_of[u] != kMixNoStem && stem_of[u] >= B)
+                return refuse((uint32_t)u, "stem id");
+        lay.stem_unit.assign(B, -1);
+        std::vector<uint32_t> stem_at(B, kMixNoStem); // caller's id -> the stem, within the programme at hand
+        for (size_t g = 0; g < P; g++) {
+            const size_t s0 = lay.stems.size();
+            for (uint32_t i = lay.progs.first[g]; i < lay.progs.first[g + 1]; i++) {
+                const uint32_t u = lay.progs.members[i], id = stem_of[u];
+                if (id == kMixNoStem)
+                    continue;
+                if (stem_at[id] == kMixNoStem) {
+                    stem_at[id] = (uint32_t)lay.stems.size();
+                    lay.stems.push_back(MixStem{(uint32_t)g, id, 0, 0, 0, 0});
+                }
+                const size_t s = stem_at[id];
+                lay.stems[s].n_members++;
+                lay.stem_unit[u] = (int32_t)(P + s);
+            }
+            for (size_t s = s0; s < lay.stems.size(); s++) {
+                const size_t unit = P + s;
+                stem_at[lay.stems[s].id] = kMixNoStem; // (the next programme counts its ids anew)
+                lay.units.push_back(OutUnit{lay.units[g].hz, lay.units[g].n, lay.total});
+                lay.seg_first.push_back(lay.seg_first.back());
+                lay.depth.push_back(0);
+                lay.overlap.push_back(0);
+                const OutUnit &w = lay.units[unit];
+                if (lay.total >= kMaxLen || w.n + align >= kMaxLen - lay.total)
+                    return refuse((uint32_t)unit, "slab length");
+                lay.total = (w.off + w.n + align - 1) / align * align;
+                ev.clear();
+                MixStem &st = lay.stems[s];
+                bool any = false;
+                for (uint32_t i = lay.progs.first[g]; i < lay.progs.first[g + 1]; i++) {
+                    const uint32_t u = lay.progs.members[i];
+                    if (stem_of[u] != st.id || lay.gain[u] == 0.0 || !n[u])
+                        continue;
+                    ev.push_back({lay.start[u], i, true});
+                    ev.push_back({lay.start[u] + n[u], i, false});
+                    st.first = any ? std::min(st.first, lay.start[u]) : lay.start[u];
+                    st.end = any ? std::max(st.end, lay.start[u] + n[u]) : lay.start[u] + n[u];
+                    any = true;
+                }
+                if (!sweep(unit, w.n))
+                    return refuse((uint32_t)unit, "work lists");
+            }
+        }
     }
     *out = std::move(lay);
     return true;
 }
 
 void join_closure(const std::vector<uint32_t> &prog_of, size_t P, const std::vector<uint8_t> &post,
-                  std::vector<uint8_t> *programmes)
+                  std::vector<uint8_t> *programmes, const std::vector<uint32_t> &unit_parent)
 {
-    programmes->assign(P, 0);
+    programmes->assign(P + unit_parent.size(), 0);
     for (size_t u = 0; u < prog_of.size(); u++)
         if (post[u])
             (*programmes)[prog_of[u]] = 1;
+    for (size_t s = 0; s < unit_parent.size(); s++)
+        (*programmes)[P + s] = (*programmes)[unit_parent[s]];
 }
 
 bool plan_loudness_groups(const LnGroupsIn &in, LnGroups *out, uint32_t *bad_group, const char **bad_field)
@@ -442,7 +507,7 @@ void loudness_groups_closure(const LnGroups &g, const std::vector<uint8_t> &touc
 }
 
 RedoScope redo_scope(const std::vector<uint32_t> &prog_of, size_t P, const LnGroups &groups,
-                     const std::vector<uint8_t> &only)
+                     const std::vector<uint8_t> &only, const std::vector<uint32_t> &unit_parent)
 {
     RedoScope s;
     s.measured = s.post = only;
@@ -450,7 +515,7 @@ RedoScope redo_scope(const std::vector<uint32_t> &prog_of, size_t P, const LnGro
         loudness_groups_closure(groups, only, &s.touched_groups, &s.post);
     s.units = s.post;
     if (!prog_of.empty())
-        join_closure(prog_of, P, s.post, &s.units);
+        join_closure(prog_of, P, s.post, &s.units, unit_parent);
     return s;
 }
 

@@ -67,6 +67,7 @@ struct OutPlanIn {
     uint32_t fmt_bytes = 0;               // bytes per sample of the requested sample format; 0: none requested
     bool adpcm = false;                   // IMA ADPCM is requested
     uint32_t adpcm_align = 0;             // its block_align: 0 = by each utterance's output rate (jb_adpcm.h)
+    const uint32_t *stem_of = nullptr;    // [B] the stems request behind a mix's (jb_mix.h "Stems"); nullptr: none
     const MixUtt *mix = nullptr;          // [B] the programme request in the mix's words (jb_mix.h): a mix's, or with
     bool chained = false;                 // `chained` a join's as join_as_mix words it; nullptr: none
     const JoinUtt *join = nullptr;        // [B] a join request in its own words (jb_join.h), as the host probes give
@@ -157,7 +158,12 @@ struct OutPlan {
     bool mixed = false;               // the programmes are a mix request's: sums of their members (jb_mix.h)
     std::vector<uint32_t> mix_depth;  // [P] with a mix: the largest number of unmuted members over one sample
     std::vector<uint64_t> mix_overlap; // [P] with a mix: the samples under two or more unmuted members
-    std::vector<OutUnit> units;       // [P] the programmes
+    std::vector<OutUnit> units;       // [P] the programmes; with a stems request [P + S]: the stems behind them, units
+                                      // like any other to the encoders (mix_depth and mix_overlap run over them too)
+    size_t n_progs = 0;               // P
+    std::vector<MixStem> stems;       // [S] with a stems request
+    std::vector<int32_t> stem_unit;   // [B] with a stems request: the unit of each utterance's stem, or -1
+    std::vector<uint32_t> unit_parent; // [S] the programme of each stem (redo_scope's)
     std::vector<uint32_t> prog_of;    // [B] each utterance's programme
     std::vector<uint64_t> prog_start; // [B] its first sample within it
     std::vector<uint32_t> prog_first, prog_members; // programme p owns prog_members[prog_first[p] .. prog_first[p + 1])
@@ -237,23 +243,35 @@ struct MixLayout {
     std::vector<uint32_t> lists;     // the segments' members: places in progs.members
     std::vector<uint32_t> depth;     // [P] the longest list of the programme
     std::vector<uint64_t> overlap;   // [P] its samples in segments of two or more
+    // With a stems request (stem_of; jb_mix.h "Stems"): the stems are units P .. P + S - 1 behind the programmes, by
+    // programme in dense order and within one by the ascending utterance index of each stem's first member; a stem is
+    // laid out as what it is, a unit of its programme's length and rate on a 16-byte boundary of the same slab with
+    // segments and lists of its own over its subset (places in progs.members, as the programmes').  units, seg_first,
+    // depth and overlap then run over the P + S units; progs stays the programmes'.  Without a request: all empty
+    std::vector<MixStem> stems;     // [S]
+    std::vector<int32_t> stem_unit; // [B] the unit of each utterance's stem, -1: none; empty without a request
+    size_t programmes() const { return progs.size(); }
 };
 // Pure.  n: [B] each utterance's samples; hz: [B] its output rate (nullptr: not compared, the units' rate is 0).
 // false: the request is refused; *bad is the caller's id of the offending programme (for "length" and "work lists":
 // the utterance or the dense programme) and *field says "programme id" for an id of B or above, "output rate" where
 // its members disagree, "length" where an utterance's start + n + pad_after passes 2^63, "slab length" where the
-// programmes up to the dense programme *bad pass it together, or "work lists" where the lists pass kMixMaxList entries
+// programmes up to the dense programme *bad pass it together, or "work lists" where the lists pass kMixMaxList entries.
+// stem_of: [B] each utterance's stem id within its programme, or kMixNoStem; nullptr: no stems.  "stem id": the
+// utterance *bad carries an id of B or above; "slab length" and "work lists" then name a unit, programme or stem
 bool mix_layout(const MixUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, MixLayout *out,
-                uint32_t *bad, const char **field, bool chained = false);
+                uint32_t *bad, const char **field, bool chained = false, const uint32_t *stem_of = nullptr);
 // The same from a join request in its own words (the host probes' way in): mix_layout of join_as_mix, chained
 using JoinLayout = MixLayout;
 bool join_layout(const JoinUtt *req, const uint64_t *n, const uint32_t *hz, size_t B, size_t elem, JoinLayout *out,
                  uint32_t *bad, const char **field);
 
 // The redo closure behind the join.  post: [B] 1 = an utterance whose final PCM changed (behind
-// loudness_groups_closure); programmes: [P] 1 = a programme with such a member
+// loudness_groups_closure); programmes: [P] 1 = a programme with such a member.  unit_parent: the programme of every
+// unit behind the P programmes (a mix's stems; empty: none): programmes then has P + S entries, and a touched
+// programme touches its stems (they and their levels run again whole)
 void join_closure(const std::vector<uint32_t> &prog_of, size_t P, const std::vector<uint8_t> &post,
-                  std::vector<uint8_t> *programmes);
+                  std::vector<uint8_t> *programmes, const std::vector<uint32_t> &unit_parent = {});
 
 // What a redo round runs again, from the utterances it rewrote.  Each stage of the chain follows one of the masks
 struct RedoScope {
@@ -266,7 +284,7 @@ struct RedoScope {
 // Pure: loudness_groups_closure, then join_closure.  prog_of: [B] each utterance's programme of P (empty: no join);
 // groups: the loudness groups the chain runs (empty: none); only: [B] 1 = an utterance the round rewrote
 RedoScope redo_scope(const std::vector<uint32_t> &prog_of, size_t P, const LnGroups &groups,
-                     const std::vector<uint8_t> &only);
+                     const std::vector<uint8_t> &only, const std::vector<uint32_t> &unit_parent = {});
 
 // The items a mask picks, renumbered: a redo launch packs their tiles (or groups, or blocks) from 0, while their
 // scratch stays where the full run's numbering put it.  An item of count 0 is picked like any other

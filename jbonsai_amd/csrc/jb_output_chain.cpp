@@ -41,6 +41,7 @@ void OutputChain::replan()
     in.adpcm_align = ad_align;
     in.mix = prog_req.empty() ? nullptr : prog_req.data();
     in.chained = prog_chained;
+    in.stem_of = stem_req.empty() || prog_req.empty() || prog_chained ? nullptr : stem_req.data();
     flag_stage();
     in.filter = stage_any.empty() ? nullptr : stage_any.data();
     in.fbank = fb_on ? &fb_p : nullptr;
@@ -460,10 +461,13 @@ int OutputChain::activity_fault(const char *who) const
 // The programme request `req` ([B], empty: none), a join's (`chained`) or a mix's, under these rates: JB_ERR_INVALID
 // naming what is wrong
 int OutputChain::check_programme(const std::vector<MixUtt> &req, bool chained, const MixOpts &opts,
-                                 const std::vector<uint32_t> &want, const char *who) const
+                                 const std::vector<uint32_t> &want, const char *who,
+                                 const std::vector<uint32_t> *stems) const
 {
     if (req.empty())
         return JB_OK;
+    if (!stems)
+        stems = &stem_req;
     const std::vector<uint32_t> hz = rates_under(want);
     // (the lengths at these rates, as plan_output forms them: they decide who lies over whom, so the lists' size)
     std::vector<uint64_t> n(hz.size(), 0);
@@ -475,7 +479,7 @@ int OutputChain::check_programme(const std::vector<MixUtt> &req, bool chained, c
     }
     MixLayout lay;
     return mix_layout_checked(req.data(), chained, n.data(), hz.data(), hz.size(), sizeof(double),
-                              chained ? nullptr : &opts, &lay, who);
+                              chained ? nullptr : &opts, &lay, who, stems->empty() ? nullptr : stems->data());
 }
 
 // The one slot for a programme request, a join's (`chained`) or a mix's: what either setter checks before it reads its
@@ -493,6 +497,8 @@ int OutputChain::open_programme(bool chained, bool given, size_t n, bool *store)
         if (!taken) {
             prog_req.clear();
             mix_opts = MixOpts{};
+            stem_req.clear(); // (the stems stand behind a mix: they leave with it)
+            stem_flags = 0;
             replan();
         }
         return JB_OK;
@@ -538,6 +544,38 @@ int OutputChain::set_mix(const jb_mix_utt *req, size_t n, const jb_mix_opts *opt
         return rc;
     const MixUtt *r = (const MixUtt *)req;
     return store_programme(false, std::vector<MixUtt>(r, r + n), opts ? *(const MixOpts *)opts : MixOpts{});
+}
+
+int OutputChain::set_mix_stems(const uint32_t *stem_of, size_t n, uint32_t flags)
+{
+    const char *who = "jb_batch_set_mix_stems";
+    int rc = check_settable("jb_batch_set_mix_stems: the stems are set before the batch's first run");
+    if (rc)
+        return rc;
+    if (!stem_of && n == 0 && flags == 0) {
+        stem_req.clear();
+        stem_flags = 0;
+        replan();
+        return JB_OK;
+    }
+    auto refuse = [&](const std::string &what) {
+        set_error(std::string(who) + ": " + what);
+        return JB_ERR_INVALID;
+    };
+    if (!stem_of || n != (size_t)b.B)
+        return refuse("give one stem id per utterance");
+    if (flags & ~kMixStemLevels)
+        return refuse("flags holds an unknown flag");
+    if (prog_req.empty() || prog_chained)
+        return refuse(prog_req.empty() ? "the batch holds no mix request (jb_batch_set_mix comes first)"
+                                       : "the batch holds a join request: stems stand behind a mix");
+    const std::vector<uint32_t> req(stem_of, stem_of + n);
+    if ((rc = check_programme(prog_req, false, mix_opts, want_hz, who, &req)))
+        return rc;
+    stem_req = req;
+    stem_flags = flags;
+    replan();
+    return JB_OK;
 }
 
 // The filter request `req` ([B], empty: none) under these rates: JB_ERR_INVALID naming the utterance, the section
@@ -886,7 +924,8 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     const bool redo = only != nullptr;
     static const LnGroups no_groups;
     const RedoScope of_redo =
-        redo ? redo_scope(plan.prog_of, plan.units.size(), grouped() ? ln_groups : no_groups, *only) : RedoScope{};
+        redo ? redo_scope(plan.prog_of, plan.n_progs, grouped() ? ln_groups : no_groups, *only, plan.unit_parent)
+             : RedoScope{};
     const RedoScope *scope = redo ? &of_redo : nullptr;
     int rc;
     if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_noise(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
@@ -1443,7 +1482,7 @@ int OutputChain::prepare_programme()
 {
     if (!joined())
         return JB_OK;
-    const size_t B = (size_t)b.B, P = plan.units.size();
+    const size_t B = (size_t)b.B, U = plan.units.size(); // the units: the programmes, and a mix's stems behind them
     const size_t elem = plan.join.i16 ? sizeof(int16_t) : sizeof(double);
     std::vector<uint64_t> n(B), xoff(B);
     for (size_t u = 0; u < B; u++) {
@@ -1451,10 +1490,16 @@ int OutputChain::prepare_programme()
         xoff[u] = plan.utt[u].off;
     }
     MixLayout lay;
+    const bool stems = mixed() && !stem_req.empty();
     int rc = mix_layout_checked(prog_req.data(), prog_chained, n.data(), nullptr, B, elem, mixed() ? &mix_opts : nullptr,
-                                &lay, mixed() ? "jb_batch_set_mix" : "jb_batch_set_join");
+                                &lay, mixed() ? "jb_batch_set_mix" : "jb_batch_set_join",
+                                stems ? stem_req.data() : nullptr);
     if (rc)
         return rc;
+    if (lay.units.size() != U) {
+        set_error("programmes: the plan and the layout disagree");
+        return JB_ERR_INVALID;
+    }
     mix_lists(lay, prog_req.data(), n.data(), xoff.data(), slab[(size_t)plan.join_src.slab], slab[(size_t)plan.join.slab],
               elem, &pg.members, &pg.spans.host, &pg.tiles);
     pg.member_at.assign(B, 0);
@@ -1462,7 +1507,7 @@ int OutputChain::prepare_programme()
         pg.member_at[lay.progs.members[i]] = (uint32_t)i;
     ProgMember *md = nullptr;
     // (a join's redo lists at most one span per member, a mix's one per programme)
-    if ((rc = b.dalloc(&md, B, false)) || (rc = pg.spans.alloc(b, P, mixed() ? P : B)) ||
+    if ((rc = b.dalloc(&md, B, false)) || (rc = pg.spans.alloc(b, U, mixed() ? U : B)) ||
         (rc = upload_list(md, pg.members, mixed() ? "mix work list" : "join work list")))
         return rc;
     pg.L.members = md;
@@ -1470,13 +1515,26 @@ int OutputChain::prepare_programme()
         MixSeg *sd = nullptr;
         uint32_t *ld = nullptr;
         if ((rc = b.dalloc(&sd, lay.segs.size(), false)) || (rc = b.dalloc(&ld, lay.lists.size(), false)) ||
-            (rc = b.dalloc(&pg.L.tile_peak, pg.tiles * kMixWaves, false)) || (rc = b.dalloc(&pg.L.res, P, false)) ||
+            (rc = b.dalloc(&pg.L.tile_peak, pg.tiles * kMixWaves, false)) || (rc = b.dalloc(&pg.L.res, U, false)) ||
             (rc = upload_list(sd, lay.segs, "mix work list")) || (rc = upload_list(ld, lay.lists, "mix work list")))
             return rc;
         pg.L.segs = sd;
         pg.L.lists = ld;
         pg.L.fit = (mix_opts.flags & kMixFit) != 0;
         pg.L.ceiling = pg.L.fit ? mix_ceiling(mix_opts.ceiling_db) : 0.0;
+    }
+    if (stems && (stem_flags & kMixStemLevels)) {
+        uint64_t scratch = 0;
+        // (what a redo's items are built from: the units, the stems and the programmes' count; the segments and their
+        // lists are on the device and not kept)
+        pg.lay = MixLayout{};
+        pg.lay.progs.first = lay.progs.first;
+        pg.lay.units = lay.units;
+        pg.lay.stems = lay.stems;
+        mix_level_items(lay, slab[(size_t)plan.join.slab], elem, {}, &pg.items.host, &pg.level_tiles, &scratch);
+        if ((rc = pg.items.alloc(b, U, U)) || (rc = b.dalloc(&pg.tile_sums, 2 * scratch, false)) ||
+            (rc = b.dalloc(&pg.sums, U, false)) || (rc = pg.items.upload("mix level list")))
+            return rc;
     }
     return pg.spans.upload(mixed() ? "mix work list" : "join work list");
 }
@@ -1486,8 +1544,24 @@ int OutputChain::prepare_programme()
 // samples around it are what they were: its neighbours' current ones, and pads)
 int OutputChain::select_programme(const RedoScope *scope)
 {
-    if (!joined() || !scope)
+    // (the stems stand behind the programmes in every list, a redo's too: the launch counts them from its end)
+    const size_t NP = plan.n_progs;
+    auto count_stems = [&](const std::vector<ProgSpan> &list) {
+        pg.L.stems = 0;
+        pg.L.stem_tiles = 0;
+        for (const ProgSpan &w : list)
+            if (w.prog >= NP) {
+                pg.L.stems++;
+                pg.L.stem_tiles += prog_tiles(w.k0, w.k1, plan.join.i16);
+            }
+    };
+    if (!joined() || !scope) {
+        if (joined() && mixed()) {
+            count_stems(pg.spans.host);
+            pg.items.take_all(pg.level_tiles);
+        }
         return pg.spans.take_all(pg.tiles);
+    }
     std::vector<ProgSpan> sub;
     uint64_t tiles = 0;
     auto take = [&](size_t p, uint64_t k0, uint64_t k1) {
@@ -1501,6 +1575,16 @@ int OutputChain::select_programme(const RedoScope *scope)
         for (size_t p = 0; p < scope->units.size(); p++)
             if (scope->units[p])
                 take(p, 0, plan.units[p].n);
+        count_stems(sub);
+        if (pg.sums) { // the levels of the touched programmes and of their stems, again
+            std::vector<LevelItem> items;
+            uint64_t lt = 0;
+            mix_level_items(pg.lay, slab[(size_t)plan.join.slab], plan.join.i16 ? sizeof(int16_t) : sizeof(double),
+                            scope->units, &items, &lt, nullptr);
+            const int rc = pg.items.upload_redo(items, kRedoLists, lt);
+            if (rc)
+                return rc;
+        }
     } else {
         const std::vector<uint8_t> &mask = scope->post; // every utterance whose final PCM changed
         const uint64_t gs = kProgGroupBytes / (plan.join.i16 ? sizeof(int16_t) : sizeof(double));
@@ -1522,6 +1606,12 @@ int OutputChain::launch_programme(bool redo)
     const hipError_t e =
         mixed() ? jb::launch_mix(plan.join.i16, pg.spans.list, pg.spans.n, pg.spans.total, pg.L, b.stream_voc)
                 : jb::launch_join(plan.join.i16, pg.spans.list, pg.spans.n, pg.spans.total, pg.L.members, b.stream_voc);
+    if (e == hipSuccess && mixed() && pg.sums) {
+        const hipError_t el = jb::launch_mix_levels(plan.join.i16, pg.items.list, pg.items.n, pg.items.total,
+                                                    pg.tile_sums, pg.sums, b.stream_voc);
+        if (el != hipSuccess)
+            return hip_fail(el, redo ? "k_mix_levels(redo)" : "k_mix_levels");
+    }
     if (e == hipSuccess)
         return JB_OK;
     return mixed() ? hip_fail(e, redo ? "k_mix(redo)" : "k_mix") : hip_fail(e, redo ? "k_join(redo)" : "k_join");
@@ -2103,7 +2193,7 @@ int OutputChain::read_mix(size_t p, jb_mix_report *out)
                          "jb_batch_mix_report: jb_batch_set_mix was not called");
     if (rc)
         return rc;
-    if (p >= plan.units.size()) {
+    if (p >= plan.n_progs) {
         set_error("jb_batch_mix_report: no such programme");
         return JB_ERR_INVALID;
     }
@@ -2111,6 +2201,27 @@ int OutputChain::read_mix(size_t p, jb_mix_report *out)
     if ((rc = b.read(pg.L.res + p, &r, sizeof r)))
         return rc;
     *out = jb_mix_report{r.peak, r.scale, plan.mix_depth[p], 0, plan.mix_overlap[p]};
+    return JB_OK;
+}
+
+int OutputChain::read_stem(size_t unit, jb_stem_report *out)
+{
+    int rc = check_ready(mixed() && !plan.stems.empty(), "jb_batch_stem_report: the batch has not run",
+                         "jb_batch_stem_report: jb_batch_set_mix_stems was not called");
+    if (rc)
+        return rc;
+    const MixStem *st = stem(unit);
+    if (!st) {
+        set_error("jb_batch_stem_report: no such stem (unit " + std::to_string(unit) + ")");
+        return JB_ERR_INVALID;
+    }
+    MixResult own{}, par{};
+    MixSums so{}, sp{};
+    if ((rc = b.read(pg.L.res + unit, &own, sizeof own)) || (rc = b.read(pg.L.res + st->programme, &par, sizeof par)))
+        return rc;
+    if (pg.sums && ((rc = b.read(pg.sums + unit, &so, sizeof so)) || (rc = b.read(pg.sums + st->programme, &sp, sizeof sp))))
+        return rc;
+    *out = stem_report_of(own.peak, par.scale, pg.sums != nullptr, so, sp.e);
     return JB_OK;
 }
 

@@ -648,7 +648,8 @@ class Engine:
 
     def synthesize_programme(self, utterances: Sequence[Sequence[str]], sink: str = "f64", lead_ms: float = 0.0,
                              gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0, device: int = -1,
-                             mix=None, fit: bool = False, ceiling_db: float = 0.0, **sink_opts):
+                             mix=None, fit: bool = False, ceiling_db: float = 0.0, stems=None, levels: bool = False,
+                             **sink_opts):
         """jb_synthesize_programme*: the utterances as ONE programme -- lead_ms of zeros, the first utterance, gap_ms,
         the next, ..., trail_ms, a fade of fade_ms at both edges of each -- joined on the GPU in front of the sink.
         sink: "f64" or "i16" (PCM arrays), "flac" (bytes; block_size, max_lpc_order, md5, seek_interval_ms),
@@ -658,13 +659,19 @@ class Engine:
         [T, n_mels]; opts=F.MelspecOpts or the keywords of J.melspec).  Returns (output, starts):
         starts[u] is utterance u's first sample within the programme.
         mix=[(start_ms, gain_db), ...] (a convenience: set_programme_mix for this call alone, the engine's setting put
-        back behind it) sums the utterances instead, each at its start and under its gain; fit and ceiling_db as there."""
+        back behind it) sums the utterances instead, each at its start and under its gain; fit and ceiling_db as there.
+        stems=[id or None, ...] (behind a mix, sink "f64" or "flac"; another sink: ValueError; at batch level every
+        sink takes stems): jb_synthesize_programme_stems*, one stem id per utterance.  The output is then a list, the
+        mixture first and the S stems behind it, and the return (outputs, starts, reports) with one F.StemReport per
+        stem; levels: the reports' three sums and dB values."""
+        if stems is not None and sink not in ("f64", "flac"):
+            raise ValueError('stems= goes with sink "f64" or "flac" (any other sink with stems: Batch.set_mix_stems)')
         if mix is not None:
             was = self.get_programme_mix()
             self.set_programme_mix(mix, fit, ceiling_db)
             try:
                 return self.synthesize_programme(utterances, sink, lead_ms, gap_ms, trail_ms, fade_ms, device,
-                                                 **sink_opts)
+                                                 stems=stems, levels=levels, **sink_opts)
             finally:
                 self.set_programme_mix(*was)
         lines, offs, B = _utt_lines(utterances)
@@ -672,6 +679,28 @@ class Engine:
         starts = (C.c_uint64 * max(1, B))()
         out, n = C.c_void_p(), C.c_size_t()
         L = self._L
+        if stems is not None:
+            if len(stems) != B:
+                raise ValueError("one stem id (or None) per utterance")
+            ids, flags = F.stem_ids(stems), F.MIX_STEM_LEVELS * bool(levels)
+            ns, U, reps = (C.c_size_t * (B + 1))(), C.c_size_t(), (F.StemReport * max(1, B))()
+            if sink == "f64":
+                if sink_opts:
+                    raise TypeError(f"unknown options {sorted(sink_opts)}")
+                outs = (C.c_void_p * (B + 1))()
+                F.check(L.jb_synthesize_programme_stems(self._h, lines, offs, B, device, C.byref(join), ids, flags, outs,
+                                                        ns, C.byref(U), reps, starts))
+                res = F._take(L.jb_join_free, outs, ns, U.value, np.float64)
+            else:
+                opts = _PROGRAMME_SINKS["flac"][0](sink_opts)
+                if sink_opts:
+                    raise TypeError(f"unknown options {sorted(sink_opts)}")
+                bufs = (C.POINTER(C.c_uint8) * (B + 1))()
+                refs = [o if o is None else C.byref(o) for o in opts]
+                F.check(L.jb_synthesize_programme_stems_flac_meta(self._h, lines, offs, B, device, *refs, C.byref(join),
+                                                                  ids, flags, bufs, ns, C.byref(U), reps, starts))
+                res = F.take_flac(L, bufs, ns, U.value)
+            return res, list(starts[:B]), list(reps[:max(U.value, 1) - 1])
         if sink in ("f64", "i16"):
             if sink_opts:
                 raise TypeError(f"unknown options {sorted(sink_opts)}")
