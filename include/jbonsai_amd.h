@@ -834,6 +834,12 @@ int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
  *    shelf: fc = 1681.974450955533, Q = 0.7071752369554196, Vh = 10^(3.999843853973347 / 20),
  *    Vb = Vh^0.4996667741545416, b = [(Vh + Vb K/Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K/Q + K^2) / a0];
  *    high-pass: fc = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1].
+ *    The shelf's centre has to lie below Nyquist: at fs <= 3363 Hz K is not positive and the shelf's poles leave the
+ *    unit circle (a2 = 1.00125 at 3363 Hz, 0.99993 at 3364 Hz).  No loudness value (L, the momentary and short-term
+ *    maxima, LRA) is defined there: jb_loudness_pcm_batch, jb_loudness_groups_pcm_batch and a batch with a loudness
+ *    target or an R128 report at such an output rate return JB_ERR_UNSUPPORTED, naming the rate; 3364 Hz and up are
+ *    measured.  jb_loudness_filter stays the formula at any rate, and the true peak (step 5), which reads no
+ *    K-weighted sample, is measured below the limit as well.
  * 2. Hop H = (fs + 5) / 10 (integer division); z_j = sum of y^2 over [jH, (j + 1)H); block i (hops i..i+3, counted
  *    only when (i + 4)H <= N) has l_i = -0.691 + 10 log10((z_i + ... + z_(i+3)) / 4H).
  * 3. Gates: keep l_i > -70; G = -0.691 + 10 log10(mean of their block mean squares) - 10; keep l_i > G as well;
@@ -880,7 +886,8 @@ int jb_resample_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
  * (a[0] = a[3] = 1), and *hop = H; each pointer may be NULL.  hz == 0: JB_ERR_INVALID. */
 int jb_loudness_filter(uint32_t hz, double *b, double *a, uint32_t *hop);
 /* The measurement on PCM the caller holds (jb_resample_pcm_batch's twin): lufs[u] = L and peak_dbfs[u] = P of in[u]
- * (n_in[u] samples at hz), on `device` (-1 = current).  A hop outside 1..61439 samples: JB_ERR_UNSUPPORTED. */
+ * (n_in[u] samples at hz), on `device` (-1 = current).  A hop outside 1..61439 samples (hz >= 614395) or a rate of
+ * 3363 Hz or less (step 1): JB_ERR_UNSUPPORTED, before any device is opened. */
 int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
                           double *lufs, double *peak_dbfs);
 /* The group measurement on PCM the caller holds (jb_loudness_pcm_batch's twin for steps 6 to 8): in[u] (n_in[u]
@@ -888,7 +895,8 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
  * measured on `device` (-1 = current) in peak mode `mode` against target_lufs and ceiling_db.  group_of[u] (may be
  * NULL) = the dense group of utterance u, numbered by first member; groups[g] for g < *n_groups (at most groups_cap
  * are written; JB_ERR_BUFFER if there are more), each with its R128 fields; utt_r128[u] (may be NULL) = each
- * utterance's own R128 fields; utt_lufs[u] (may be NULL) = its own L.  No sample is changed. */
+ * utterance's own R128 fields; utt_lufs[u] (may be NULL) = its own L.  No sample is changed.  The rates of
+ * jb_loudness_pcm_batch. */
 int jb_loudness_groups_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *group,
                                  uint32_t hz, int32_t device, uint32_t mode, double target_lufs, double ceiling_db,
                                  uint32_t *group_of, jb_loudness_group_report *groups, size_t groups_cap,
@@ -905,7 +913,8 @@ int jb_loudness_gate_host(const double *const *z, const size_t *n_hops, size_t n
  * the [F - 1][12] taps h[p][j] of phases p = 1..F-1 (JB_ERR_BUFFER if cap < (F - 1) * 12).  hz == 0: JB_ERR_INVALID. */
 int jb_true_peak_filter(uint32_t hz, uint32_t *F, uint32_t *ntaps, double *taps, size_t cap);
 /* jb_loudness_pcm_batch's twin for step 5: true_peak_dbtp[u] = TP of in[u] (n_in[u] samples at hz), on `device`
- * (-1 = current).  The tiling is the measurement's: a hop outside 1..61439 samples is JB_ERR_UNSUPPORTED. */
+ * (-1 = current).  The tiling is the measurement's: a hop outside 1..61439 samples is JB_ERR_UNSUPPORTED; the lower
+ * limit of the loudness values (step 1) does not apply. */
 int jb_true_peak_pcm_batch(const double *const *in, const size_t *n_in, size_t n, uint32_t hz, int32_t device,
                            double *true_peak_dbtp);
 

@@ -157,7 +157,7 @@ struct LoudnessRate {
     double b[6], a[6];     // stage 1 (shelf) then stage 2 (high-pass): b0 b1 b2 / 1 a1 a2
     double P[8][16];       // A^(S 2^k), k = 0..7: the state transition over 2^k segments (4x4, row-major)
     double Pt[16], Pr[16]; // A^G (a hop's tiles but its last), A^(H - (tph - 1) G) (a hop's last tile)
-    double Ph[16];         // A^H (a hop)
+    double Ph[16];         // A^H (a hop).  A is in the coordinates states are carried in (jb_loudness.hip ln_to_scan)
     uint32_t hz, H, S, G, tph;
     uint32_t F;                                  // true-peak oversampling factor, 1..64 (true_peak_table)
     double tp[(kTpMaxF - 1) * kTpTaps];          // its phases 1..F-1, [F - 1][12]
@@ -184,6 +184,10 @@ int loudness_filter(uint32_t hz, double b[6], double a[6], uint32_t *hop);
 int true_peak_table(uint32_t hz, uint32_t *F, double *taps);
 // The device table of one rate (host-built); JB_ERR_UNSUPPORTED where the tiling does not reach (H == 0, H > 61439)
 int loudness_rate(uint32_t hz, LoudnessRate *out);
+// Whether a loudness value (L, the momentary and short-term maxima, LRA) is defined at `hz`: JB_ERR_UNSUPPORTED at
+// 3363 Hz and below, where the shelf's centre is not below Nyquist and the K-weighting diverges.  Asked wherever such
+// a value is produced; the true peak reads no hop energy and is measured at any rate the tiling reaches
+int loudness_measurable(uint32_t hz);
 uint32_t loudness_tiles(const LoudnessRate &r, uint64_t n); // measure tiles of an utterance of n samples
 // measure: utts_dev[0..n) of total tiles; st: 4 doubles per tile, pk / tp / z: one; res[slot] of each utterance.
 // true_peak: some utterance of the list is in JB_PEAK_TRUE mode (without one the oversampled pass is not launched)

@@ -7,7 +7,9 @@
 //
 // The filter is linear and time-invariant, so a recursion cut into pieces is exact up to rounding: a piece filtered
 // from zero state ends in e, and the state s at its start carries over as s -> A^len s + e (A: the 4x4 transition of
-// one sample with x = 0, len: the piece's length).  Five kernels measure, one applies:
+// one sample with x = 0, len: the piece's length).  Between pieces a state travels in the coordinates of ln_to_scan
+// and the powers of A are made on the host in extended precision (mat_pow): both for the same reason, a DC offset
+// that the high-pass holds as two large states of opposite sign.  Five kernels measure, one applies:
 //   k_ln_tiles<false>  one workgroup per tile (<= 256 segments of S <= 16 samples, inside one hop): the tile is staged
 //                      through LDS with coalesced loads (the sample peak on the way), every lane filters its segment
 //                      from zero, a Hillis-Steele scan of the affine maps across the 256 lanes (matrices A^(S 2^k),
@@ -42,6 +44,7 @@ namespace jb {
 namespace {
 constexpr uint32_t kLnMaxS = 16; // samples per segment at most (tiles of at most 4096 samples)
 constexpr uint32_t kLnMaxHop = 61439; // tph = ceil(H / 4096) <= 15: the hop's last tile is never empty
+constexpr double kLnShelfHz = 1681.974450955533; // the shelf's centre: K = tan(pi fc / fs) > 0 only below Nyquist
 using M4 = double[16];
 
 // One sample through both stages (transposed direct form II); c: b0 b1 b2 a1 a2 of stage 1, then of stage 2
@@ -56,12 +59,12 @@ inline double host_step(const double *c, double *s, double x)
     return y;
 }
 
-void mat_mul(const double *a, const double *b, double *out)
+void mat_mul(const long double *a, const long double *b, long double *out)
 {
-    double t[16];
+    long double t[16];
     for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++) {
-            double acc = 0.0;
+            long double acc = 0.0L;
             for (int k = 0; k < 4; k++)
                 acc += a[i * 4 + k] * b[k * 4 + j];
             t[i * 4 + j] = acc;
@@ -69,16 +72,23 @@ void mat_mul(const double *a, const double *b, double *out)
     std::copy(t, t + 16, out);
 }
 
+// A^n by squaring in extended precision, rounded once (as jb_filter.cpp's tables).  The high-pass has a nearly double
+// pole at 1: what one entry of A^n is off by is carried for another 1 / (1 - r) samples, times a state of the size of
+// x, into an output several hundred times smaller than that state.  Squared in f64 the powers cost 1e-9 LU on a DC
+// offset at 48 kHz, 50 times what a serial f64 recursion loses (tests/test_gpu_loudness_ld.py,
+// profiles/loudness_ld.txt)
 void mat_pow(const double *a, uint64_t n, double *out)
 {
-    double r[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, p[16];
+    long double r[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, p[16];
     std::copy(a, a + 16, p);
     for (; n; n >>= 1) {
         if (n & 1)
             mat_mul(r, p, r);
-        mat_mul(p, p, p);
+        if (n > 1)
+            mat_mul(p, p, p);
     }
-    std::copy(r, r + 16, out);
+    for (int i = 0; i < 16; i++)
+        out[i] = (double)r[i];
 }
 
 double tp_bessel_i0(double x)
@@ -142,7 +152,7 @@ int loudness_filter(uint32_t hz, double b[6], double a[6], uint32_t *hop)
         aa[2] = (1.0 - K / Q + K * K) / a0;
     };
     double bb[6], aa[6];
-    stage(1681.974450955533, 0.7071752369554196, bb, aa, true);
+    stage(kLnShelfHz, 0.7071752369554196, bb, aa, true);
     stage(38.13547087602444, 0.5003270373238773, bb + 3, aa + 3, false);
     if (b)
         std::copy(bb, bb + 6, b);
@@ -151,6 +161,16 @@ int loudness_filter(uint32_t hz, double b[6], double a[6], uint32_t *hop)
     if (hop)
         *hop = (hz + 5) / 10;
     return JB_OK;
+}
+
+int loudness_measurable(uint32_t hz)
+{
+    if (hz == 0 || 2.0 * kLnShelfHz < (double)hz)
+        return JB_OK;
+    set_error("loudness: at " + std::to_string(hz) + " Hz the shelf's centre (1681.97 Hz) is not below Nyquist (" +
+              std::to_string(hz / 2) + (hz % 2 ? ".5" : "") + " Hz): the K-weighting is unstable; 3364 Hz and up are "
+              "measured");
+    return JB_ERR_UNSUPPORTED;
 }
 
 int loudness_rate(uint32_t hz, LoudnessRate *out)
@@ -177,13 +197,17 @@ int loudness_rate(uint32_t hz, LoudnessRate *out)
         set_error("loudness: no tiling for a hop of " + std::to_string(H));
         return JB_ERR_UNSUPPORTED;
     }
-    // A: one sample with x = 0, column j from the unit state e_j -- the device's recursion, term for term
+    // A: one sample with x = 0, column j from the unit state e_j -- the device's recursion, term for term -- in the
+    // scan's coordinates (ln_to_scan): e_3 there is (t0, t1) = (-1, 1), and the image's pair is summed again
     const double c[10] = {r.b[0], r.b[1], r.b[2], r.a[1], r.a[2], r.b[3], r.b[4], r.b[5], r.a[4], r.a[5]};
     double A[16];
     for (int j = 0; j < 4; j++) {
         double s[4] = {0, 0, 0, 0};
         s[j] = 1.0;
+        if (j == 3)
+            s[2] = -1.0;
         host_step(c, s, 0.0);
+        s[2] += s[3];
         for (int i = 0; i < 4; i++)
             A[i * 4 + j] = s[i];
     }
@@ -218,6 +242,15 @@ __device__ __forceinline__ double ln_step(const double *c, double *s, double x)
     s[3] = __builtin_fma(c[7], w, -c[9] * y);
     return y;
 }
+
+// The coordinates in which states are carried between pieces (sc, st, every matrix of LoudnessRate): the high-pass
+// pair (t0, t1) as (t0 + t1, t1).  The high-pass has a nearly double pole at 1 and a DC offset c in its input sits in
+// the pair as (-c, c).  In the recursion's own coordinates A^n has entries of size n that map that state by a
+// difference of products n c, rounded at eps n c, and what is lost there lives on for another 1 / (1 - r) samples of
+// an output that is several hundred times smaller than c.  In these coordinates the sum is 0 for the offset (exact:
+// the two are within a factor of 2), the entries that meet t1 are small, and no product is larger than its result
+__device__ __forceinline__ void ln_to_scan(double *s) { s[2] += s[3]; }
+__device__ __forceinline__ void ln_from_scan(double *s) { s[2] -= s[3]; }
 
 // v += P w (P wave-uniform: scalar operands)
 __device__ __forceinline__ void ln_mv_add(cdouble *P, const double *w, double *v)
@@ -301,6 +334,7 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_tiles(const LoudnessRate *__res
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     for (uint32_t i = 0; i < sl; i++)
         ln_step(c, v, xl[i] * inv);
+    ln_to_scan(v);
     for (int i = 0; i < 4; i++)
         sc[tid * 4 + i] = v[i];
     __syncthreads();
@@ -325,7 +359,8 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_tiles(const LoudnessRate *__res
             ln_mv_add((cdouble *)R->P[kk], w, v);
         }
     }
-    // v: the state at the start of this lane's segment
+    // v: the state at the start of this lane's segment, back in the recursion's coordinates
+    ln_from_scan(v);
     double acc = 0.0;
     if (kZ) {
         for (uint32_t i = 0; i < sl; i++) {
@@ -336,6 +371,7 @@ __global__ __launch_bounds__(kLnLanes) void k_ln_tiles(const LoudnessRate *__res
         if (tid == nact - 1) {
             for (uint32_t i = 0; i < sl; i++)
                 ln_step(c, v, xl[i] * inv);
+            ln_to_scan(v);
             for (int i = 0; i < 4; i++)
                 st[(U.tile0 + t) * 4 + i] = v[i];
         }
@@ -1016,9 +1052,11 @@ int jb_loudness_pcm_batch(const double *const *in, const size_t *n_in, size_t n,
 {
     if (n && (!lufs || !peak_dbfs))
         return JB_ERR_INVALID;
-    std::vector<LoudnessResult> out;
-    int rc = measure_pcm_batch(in, n_in, n, hz, device, JB_PEAK_SAMPLE, "jb_loudness_pcm_batch", &out);
+    int rc = loudness_measurable(hz);
     if (rc)
+        return rc;
+    std::vector<LoudnessResult> out;
+    if ((rc = measure_pcm_batch(in, n_in, n, hz, device, JB_PEAK_SAMPLE, "jb_loudness_pcm_batch", &out)))
         return rc;
     for (size_t u = 0; u < n; u++) {
         lufs[u] = out[u].lufs;
@@ -1060,9 +1098,11 @@ int jb_loudness_groups_pcm_batch(const double *const *in, const size_t *n_in, si
                   std::to_string(groups_cap));
         return JB_ERR_BUFFER;
     }
-    std::vector<LoudnessResult> out;
-    int rc = measure_pcm_batch(in, n_in, n, hz, device, mode, "jb_loudness_groups_pcm_batch", &out, &gr);
+    int rc = loudness_measurable(hz);
     if (rc)
+        return rc;
+    std::vector<LoudnessResult> out;
+    if ((rc = measure_pcm_batch(in, n_in, n, hz, device, mode, "jb_loudness_groups_pcm_batch", &out, &gr)))
         return rc;
     uint32_t F = 1;
     if ((rc = true_peak_table(hz, &F, nullptr)))

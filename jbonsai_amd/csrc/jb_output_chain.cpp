@@ -1294,7 +1294,7 @@ int OutputChain::prepare_loudness()
             r++;
         if (r == rates.size()) {
             LoudnessRate lr{};
-            if ((rc = loudness_rate(o.hz, &lr)))
+            if ((rc = loudness_measurable(o.hz)) || (rc = loudness_rate(o.hz, &lr)))
                 return rc;
             rates.push_back(lr);
         }

@@ -72,3 +72,47 @@ def test_engine_target_and_ceiling_setter_getter_and_copy():
     assert math.isnan(c.get_loudness_target())
     # other fields stay as they were
     assert c.get_output_sampling_frequency() == 0 and c.get_sampling_frequency() == 48000
+
+
+# ---- the two refusals of the measurement: both return before any device is opened -------------------------------------
+def _raises(fn):
+    try:
+        fn()
+    except J.JbError as e:
+        return e
+    return None
+
+
+def _seams(hz):
+    x = [np.zeros(8)]
+    return [lambda: J.loudness(x, hz), lambda: J.loudness_groups(x, hz)]
+
+
+def test_a_hop_above_61439_samples_is_refused_and_named():
+    for seam in _seams(614395):
+        e = _raises(seam)
+        assert e is not None and e.code == -2, e
+        assert "614395 Hz" in str(e) and "hop of 61440" in str(e), str(e)
+    for seam in _seams(614394):  # accepted: a hop of 61439; without a device what is left is the device's own error
+        e = _raises(seam)
+        assert e is None or e.code == -3, e
+
+
+def test_a_rate_whose_nyquist_is_not_above_the_shelf_is_refused_and_named():
+    """At 3363 Hz and below K = tan(pi 1681.97 / fs) is not positive and the shelf is unstable (a2 = 1.00125 at
+    3363 Hz, 0.99993 at 3364 Hz by the formula)."""
+    assert k_filter(3363)[1][0][2] > 1.0 > k_filter(3364)[1][0][2] > 0.9999
+    for hz in (3363, 3000, 400, 1):
+        for seam in _seams(hz):
+            e = _raises(seam)
+            assert e is not None and e.code == -2, (hz, e)
+            assert "%d Hz" % hz in str(e) and "shelf" in str(e) and "Nyquist" in str(e), str(e)
+    for seam in _seams(3364):
+        e = _raises(seam)
+        assert e is None or e.code == -3, e
+    # the coefficients stay a pure function of the rate, and the true peak reads no hop energy: neither refuses
+    assert J.loudness_filter(3000)[2] == 300
+    e = _raises(lambda: J.true_peak([np.zeros(8)], 3000))
+    assert e is None or e.code == -3, e
+    e = _raises(lambda: J.loudness([np.zeros(8)], 0))
+    assert e is not None and e.code == -1
