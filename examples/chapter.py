@@ -3,7 +3,7 @@
     python examples/chapter.py voice.htsvoice first.lab second.lab ... -o chapter.flac
                                [--lead-ms MS] [--gap-ms MS] [--trail-ms MS] [--fade-ms MS]
                                [--loudness LUFS [--ceiling DBFS] [--limiter DB]] [--rate HZ] [--highpass HZ]
-                               [--fbank OUT.npy] [--mfcc OUT.npy] [--kaldi] [--melspec OUT.npy [--whisper]] [--fir taps.npy [--fir-delay D]]
+                               [--fbank OUT.npy] [--mfcc OUT.npy] [--kaldi] [--melspec OUT.npy [--whisper]] [--pitch OUT.npy] [--fir taps.npy [--fir-delay D]]
                                [--noise bed.npy|white --snr DB] [--room LX,LY,LZ --rt60 S [--room-taps K]]
 
 Each label file holds the full-context labels of one sentence, one per line.  The sentences are synthesized in one
@@ -64,6 +64,7 @@ ap.add_argument("--mfcc", default=None, metavar="OUT.npy", help="the chapter's M
 ap.add_argument("--kaldi", action="store_true", help="with --fbank or --mfcc: Kaldi's frame conditioning and defaults (J.kaldi_frame)")
 ap.add_argument("--melspec", default=None, metavar="OUT.npy", help="the chapter's mel spectrogram (librosa / Whisper convention) from the GPU, instead of the audio")
 ap.add_argument("--whisper", action="store_true", help="with --melspec: Whisper's front end; sets the output rate to 16 kHz")
+ap.add_argument("--pitch", default=None, metavar="OUT.npy", help="the chapter's Kaldi-style pitch features [T, 3] from the GPU, the log-pitch normalised over the whole chapter, instead of the audio")
 args = ap.parse_args()
 if args.melspec and args.whisper:
     args.rate = 16000
@@ -122,6 +123,12 @@ elif args.mfcc:
     feats, starts = engine.synthesize_programme(sentences, sink="mfcc", delta_order=2, cmvn="mean_var", **kaldi, **join)
     np.save(args.mfcc, feats)
     print(f"wrote {args.mfcc}: {feats.shape[0]} frames of {feats.shape[1]} cepstral values at {hz} Hz")
+elif args.pitch:
+    import numpy as np
+
+    feats, starts = engine.synthesize_programme(sentences, sink="pitch", opts=J.kaldi_pitch(), **join)
+    np.save(args.pitch, feats)
+    print(f"wrote {args.pitch}: {feats.shape[0]} frames of {feats.shape[1]} pitch columns at {hz} Hz")
 elif args.melspec:
     import numpy as np
 

@@ -3,7 +3,7 @@
     python examples/is_bonsai.py [voice.htsvoice] [out.wav] [--loudness LUFS [--ceiling DBFS] [--true-peak] [--limiter DB]]
                                  [--programme] [--format f32|s16|s24|ulaw|alaw [--dither]] [--adpcm [--rate HZ]]
                                  [--flac] [--highpass HZ] [--fbank OUT.npy [--rate HZ]] [--mfcc OUT.npy [--rate HZ]] [--kaldi]
-                                 [--melspec OUT.npy [--whisper | --rate HZ]]
+                                 [--melspec OUT.npy [--whisper | --rate HZ]] [--pitch OUT.npy [--rate HZ]]
                                  [--fir taps.npy [--fir-delay D]] [--noise bed.npy|white --snr DB [--snr-active]]
                                  [--room LX,LY,LZ --rt60 S [--room-taps K]] [--activity OUT.npy [--rate HZ]]
 
@@ -78,6 +78,7 @@ ap.add_argument("--mfcc", default=None, metavar="OUT.npy", help="MFCC + deltas +
 ap.add_argument("--kaldi", action="store_true", help="with --fbank or --mfcc: Kaldi's frame conditioning and defaults")
 ap.add_argument("--melspec", default=None, metavar="OUT.npy", help="mel spectrogram (librosa / Whisper convention), computed on the GPU")
 ap.add_argument("--whisper", action="store_true", help="with --melspec: Whisper's front end at 16 kHz")
+ap.add_argument("--pitch", default=None, metavar="OUT.npy", help="Kaldi-style pitch features [T, 3] (POV, normalised log-pitch, delta), tracked on the GPU; --rate applies")
 ap.add_argument("--flac", action="store_true", help="FLAC file with MD5 and a SEEKTABLE, encoded on the GPU")
 ap.add_argument("--highpass", type=float, default=None, metavar="HZ", help="high-pass corner, filtered on the GPU")
 ap.add_argument("--fir", default=None, metavar="taps.npy", help="impulse response at the output rate, convolved on the GPU")
@@ -185,6 +186,16 @@ if args.mfcc:
     np.save(args.mfcc, feats)
     hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
     print(f"wrote {args.mfcc}: {feats.shape[0]} frames of {feats.shape[1]} cepstral values at {hz} Hz")
+    sys.exit(0)
+if args.pitch:
+    import numpy as np
+
+    if args.rate:
+        engine.condition.set_output_sampling_frequency(args.rate)
+    hz = engine.condition.get_output_sampling_frequency() or engine.condition.get_sampling_frequency()
+    feats = engine.synthesize_pitch(SAMPLE_SENTENCE_2, J.kaldi_pitch())
+    np.save(args.pitch, feats)
+    print(f"wrote {args.pitch}: {feats.shape[0]} frames of {feats.shape[1]} pitch columns at {hz} Hz")
     sys.exit(0)
 if args.melspec:
     import numpy as np

@@ -1611,6 +1611,122 @@ int jb_batch_read_activity_all(jb_batch *b, uint8_t *const *dst);
 int jb_batch_activity_report(jb_batch *b, size_t unit, size_t col, jb_activity_report *out);
 int jb_batch_activity_unit_report(jb_batch *b, size_t unit, jb_activity_unit_report *out);
 
+/* ---- Pitch features (new: the reference has no such output) ----------------------------------------------------------
+ * The pitch columns that the Kaldi/ESPnet recipes for tonal and pitch-accent languages read beside the filterbank rows
+ * (compute-kaldi-pitch-feats | process-kaldi-pitch-feats; Ghahremani et al., ICASSP 2014), tracked on the PCM the
+ * caller holds.  The rule (jbonsai_amd/csrc/jb_pitch.h states it once for the host and the device) is f64 throughout;
+ * its tables come from the host in long double, rounded once; every sum has a fixed order; products are rounded before
+ * they are added (no fma).  hz: the unit's rate, n its samples, r = JB_PITCH_RATE = 4000 Hz.
+ * 1. Decimate.  y[m] = (1 / hz) sum_k x[k] f(k / hz - m / r), m < n4 = ceil(n r / hz), with
+ *    f(t) = 2c sinc(2ct) (1 + cos(2 pi c t / w)) / 2 inside |t| < w / (2c) and 0 elsewhere, c = 1000 Hz, w = 1; from
+ *    +0.0 over ascending k inside [0, n).  The weights come from a table of r / gcd(hz, r) phases (1 at 8, 16 and
+ *    48 kHz, 40 at 44.1 kHz) of 2 ceil(hz / 2000) + 1 weights; a table above JB_PITCH_MAX_DOWN weights is
+ *    JB_ERR_UNSUPPORTED, hz < r JB_ERR_INVALID.  S1 = sum y and S2 = sum y^2 are taken in the noise stage's order (tiles
+ *    of 1,024 samples, 256 strided partials, the tree 128 .. 1, the tiles in ascending order) without its fused
+ *    multiply-add; sigma^2 = S2 / n4 - (S1 / n4)^2.
+ * 2. Frames.  wl and hop at the unit's rate are win_us and hop_us rounded as the filterbank stage rounds them, and
+ *    T = n >= wl ? 1 + (n - wl) / hop : 0 (JB_PITCH_SNIP) or (n + hop / 2) / hop (JB_PITCH_KALDI): the filterbank
+ *    stage's T under the same window, hop and grid (plain, or JB_FRAME_REFLECT), so the rows concatenate.  At 4 kHz
+ *    wl4 = win_us / 250 (8..512) and sh4 = hop_us / 250, whole numbers: win_us and hop_us are multiples of 250.  Frame t
+ *    starts at t sh4 (JB_PITCH_KALDI: t sh4 + sh4 / 2 - wl4 / 2); samples outside [0, n4) read as 0.  A stated
+ *    deviation: Kaldi's snip mode drops the last frames whose longest lag runs past the end; they are kept here over
+ *    zeros.
+ * 3. Lags.  lag_0 = 1 / max_f0 and lag_{i+1} = lag_i (1 + delta_pitch), each one long double operation, while
+ *    lag_i <= 1 / min_f0 (S lags, at most 1024; 417 at the defaults).  The integer lags run over a .. b,
+ *    a = max(0, floor(r / max_f0 - 5/2)), b = ceil(r / min_f0 + 5/2) (at most 255; 7..83 at the defaults).
+ * 4. NCCF.  v: the wl4 + b samples from the frame's start less the mean of the first wl4 (every sum of a frame in the
+ *    frame conditioning's order: 64 strided partials from 0.0, folded 32 .. 1).  inner_L = sum_{i<wl4} v_i v_{i+L},
+ *    e_L = sum v_{i+L}^2; q_L = inner_L / sqrt(e_0 e_L + B), B = nccf_ballast (sigma^2 wl4)^2, and
+ *    p_L = inner_L / sqrt(e_0 e_L); +0.0 where the denominator is 0.  Both go to the lag grid:
+ *    Q_i = sum_L q_L g_i[L] from +0.0 over ascending L, g_i[L] = f(L / r - lag_i) / r with c = r / 2 and w = 5.
+ * 5. Track.  local_i = (1 - Q_i) + (soft_min_f0 lag_i) Q_i; F_t[i] = min_j (F_{t-1}[j] + kappa (i - j)^2) + local_i,
+ *    kappa = penalty_factor ln(1 + delta_pitch)^2, (i - j)^2 an exact integer, the minimum exact over all j with ties
+ *    to the smallest j; then F_t -= min_i F_t.  F_{-1} = 0.  The last state is the smallest index of the minimum; the
+ *    stored choices are traced back.  The raw pair of a frame is (p at the chosen lag, 1 / lag).
+ * 6. Process, the default output [T][3]: pov_scale ((1.0001 - clamp(p, -1, 1))^0.15 - 1); pitch_scale (l_t -
+ *    sum pi_j l_j / sum pi_j) over j in [t - norm_left, t + norm_right] within [0, T), ascending, with l = ln(1 / lag)
+ *    and pi = 1 / (1 + e^-rho), rho = -5.2 + 5.4 e^{7.5(a-1)} + 4.8 a - 2 e^{-10 a} + 4.2 e^{20(a-1)}, a = min(|p|, 1);
+ *    delta_scale sum_{k=-2..2} k l_{clamp(t+k)} / 10.  JB_PITCH_RAW_LOG adds l_t as a fourth column; JB_PITCH_RAW gives
+ *    the two columns of step 5 instead.  Elements are f32, or f64 with JB_PITCH_F64.
+ * On the device (jb_pitch.hip): k_pitch_down, a workgroup per tile of the sums with the rate's phase table in LDS;
+ * k_pitch_track, one workgroup per unit, serial over its frames and parallel over the lags (a call of one long unit
+ * runs on one workgroup), storing a 16-bit choice per frame and lag: 2 S bytes per frame of scratch, 834 at the
+ * defaults, over a call at most JB_PITCH_MAX_SCRATCH (JB_ERR_UNSUPPORTED); k_pitch_post, a wave per frame, for p at the
+ * chosen lag; k_pitch_cols, a lane per frame, for step 6.  Steps 1 to 5 use + - * / sqrt and tables alone.
+ * Not claimed: Kaldi's bits (no Kaldi binary was at hand to compare with), its online modes and its random delta
+ * noise, a fused fbank + pitch sink (the equal T lets a caller concatenate), the generator, the _multi
+ * entries, and the voice's own LF0 as ground truth. */
+#define JB_PITCH_SNIP 0u
+#define JB_PITCH_KALDI 1u
+#define JB_PITCH_F64 1u
+#define JB_PITCH_RAW 2u
+#define JB_PITCH_RAW_LOG 4u
+#define JB_PITCH_RATE 4000u
+#define JB_PITCH_MAX_DOWN 4096u
+#define JB_PITCH_MAX_SCRATCH (1ull << 32)
+typedef struct jb_pitch_opts {
+    uint32_t win_us, hop_us;        /* microseconds, multiples of 250 */
+    double min_f0, max_f0;          /* Hz */
+    double delta_pitch;             /* the lag grid's step, [0.0001, 1] */
+    double penalty_factor;
+    double soft_min_f0;
+    double nccf_ballast;
+    double pov_scale, pitch_scale, delta_scale;
+    uint32_t norm_left, norm_right; /* frames, 0..4096 */
+    uint32_t grid;                  /* JB_PITCH_SNIP, _KALDI */
+    uint32_t flags;                 /* JB_PITCH_F64 | JB_PITCH_RAW | JB_PITCH_RAW_LOG */
+    uint32_t reserved[4];
+} jb_pitch_opts;
+typedef struct jb_pitch_geometry_t {
+    uint64_t T, n4;               /* frames, and samples at 4 kHz */
+    uint32_t wl, hop;             /* at the unit's rate */
+    uint32_t wl4, sh4;            /* at 4 kHz */
+    uint32_t S, lag_first, lag_last; /* lags of the grid; a and b */
+    uint32_t width, elem;         /* columns of a row, bytes of an element */
+    uint32_t choice_bytes;        /* the tracker's scratch per frame */
+} jb_pitch_geometry_t;
+/* New (none).  Kaldi's defaults as PitchExtractionOptions and ProcessPitchOptions have them: 25 / 10 ms, 50..400 Hz,
+ * delta_pitch 0.005, penalty_factor 0.1, soft_min_f0 10, nccf_ballast 7000, the three scales 2, 2, 10, 75 frames on
+ * either side, JB_PITCH_KALDI (snip_edges = false), f32, three columns. */
+int jb_pitch_kaldi(jb_pitch_opts *opts);
+/* New (none).  The geometry of a unit of n samples at hz under opts (out may be NULL).  Refused with JB_ERR_INVALID
+ * naming the field: an unknown grid or flag, a non-zero reserved word, a window or hop that is no multiple of 250 us
+ * or outside its limits, a bound, step or scale outside its range, more than 1024 lags, an integer lag above 255,
+ * hz below 4000; JB_ERR_UNSUPPORTED for a rate whose phase table passes JB_PITCH_MAX_DOWN. */
+int jb_pitch_geometry(const jb_pitch_opts *opts, uint32_t hz, size_t n, jb_pitch_geometry_t *out);
+/* New (none).  The lags of step 3 in seconds: *S (may be NULL) their count, lags (may be NULL) [cap] receives them
+ * (JB_ERR_BUFFER if cap is below S). */
+int jb_pitch_lags(const jb_pitch_opts *opts, double *lags, size_t cap, size_t *S);
+/* New (none).  The rule in plain C++ on the host: x[0..n) is the unit, out its [T][width] elements (cap in bytes;
+ * below T width elem: JB_ERR_BUFFER).  Each of lag_index [T] (the chosen lag of every frame), grid_q and grid_p
+ * ([T][S]: Q and p over the lag grid) may be NULL. */
+int jb_pitch_host(const double *x, size_t n, uint32_t hz, const jb_pitch_opts *opts, void *out, size_t cap,
+                  uint32_t *lag_index, double *grid_q, double *grid_p);
+/* New (none).  The stage on PCM the caller holds, on `device` (-1 = current): every utterance is a unit, hz[u] its
+ * rate.  out[u] = its [T[u]][width] elements, library-owned (jb_pitch_free); lag_index (may be NULL): [n], each the
+ * unit's [T[u]] chosen lags, library-owned.  T and width (may be NULL) have n entries. */
+int jb_pitch_pcm_batch(const double *const *in, const size_t *n_in, size_t n, const uint32_t *hz,
+                       const jb_pitch_opts *opts, int32_t device, void **out, uint64_t *T, uint32_t *width,
+                       uint32_t **lag_index);
+void jb_pitch_free(void *p);
+/* New (none).  The stage in a batch: a byte sink beside whatever else the batch has, of an f64 batch (with
+ * JB_BATCH_PCM_I16: JB_ERR_UNSUPPORTED).  The units are the batch's outputs (jb_batch_num_outputs): the utterances, or
+ * behind a join or mix the programmes (and the stems behind them), so that the normalisation of the log-pitch runs over
+ * the whole programme.  It reads the final f64 PCM that the filterbank stage would read, at each unit's output rate.
+ * Checked at every unit's rate when set and when a rate is set behind it; the tracker's choices are allocated at the
+ * first run, and past JB_PITCH_MAX_SCRATCH that run is refused with JB_ERR_UNSUPPORTED.  opts == NULL withdraws the
+ * request.  Only before the batch's first run.  A redo round tracks every unit whose PCM changed again, whole.  Without
+ * the request no kernel, list or allocation is added. */
+int jb_batch_set_pitch(jb_batch *b, const jb_pitch_opts *opts);
+/* New (none).  T, the row's width and the rate of unit `unit` (each may be NULL), known once the request is made; its
+ * bytes T * width * element bytes. */
+int jb_batch_pitch_shape(jb_batch *b, size_t unit, size_t *T, uint32_t *width, uint32_t *hz);
+int jb_batch_pitch_size(jb_batch *b, size_t unit, size_t *n_bytes);
+/* New (none).  After the run: unit `unit`'s rows into dst[0 .. cap) (JB_ERR_BUFFER if cap is too small); and every
+ * unit's rows, dst[u] sized by jb_batch_pitch_size, in one device-to-host copy for the batch. */
+int jb_batch_read_pitch(jb_batch *b, size_t unit, uint8_t *dst, size_t cap);
+int jb_batch_read_pitch_all(jb_batch *b, uint8_t *const *dst);
+
 /* ---- Filter (new: the reference has no such control) ---------------------------------------------------------------
  * A caller-chosen cascade of up to four second-order sections shapes the PCM on the device, at the output rate: behind
  * the converter (or the vocoder at the native rate) and in front of the loudness measurement, so that the target, the
@@ -2529,6 +2645,22 @@ int jb_synthesize_programme_melspec(const jb_engine *e, const char *const *label
                                     size_t n_utts, int32_t device, const jb_melspec_opts *opts,
                                     const jb_join_opts *join, uint8_t **bytes, size_t *n_bytes, size_t *n_frames,
                                     uint64_t *starts);
+/* New (none).  The pitch features ("Pitch features" above) of what jb_synthesize, jb_synthesize_batch and
+ * jb_synthesize_batch_each return, and of a programme (the normalisation of the log-pitch over the whole programme),
+ * tracked on the device from the final f64 PCM of the same run: bytes[u] = output u's [T][width] elements,
+ * library-owned (jb_pitch_free), n_bytes[u] their bytes, n_frames[u] (may be NULL) = T; starts as
+ * jb_synthesize_programme's.  Options that are refused: JB_ERR_INVALID naming the field, before any device is touched. */
+int jb_synthesize_pitch(const jb_engine *e, const char *const *label_lines, size_t n, const jb_pitch_opts *opts,
+                        uint8_t **bytes, size_t *n_bytes, size_t *n_frames);
+int jb_synthesize_batch_pitch(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                              size_t n_utts, int32_t device, const jb_pitch_opts *opts, uint8_t **bytes,
+                              size_t *n_bytes, size_t *n_frames);
+int jb_synthesize_batch_each_pitch(const jb_engine *const *engines, const char *const *label_lines,
+                                   const size_t *line_off, size_t n_utts, int32_t device, const jb_pitch_opts *opts,
+                                   uint8_t **bytes, size_t *n_bytes, size_t *n_frames);
+int jb_synthesize_programme_pitch(const jb_engine *e, const char *const *label_lines, const size_t *line_off,
+                                  size_t n_utts, int32_t device, const jb_pitch_opts *opts, const jb_join_opts *join,
+                                  uint8_t **bytes, size_t *n_bytes, size_t *n_frames, uint64_t *starts);
 
 /* ------------------------------------------------------------------------ */
 const char *jb_last_error(void);
@@ -2622,6 +2754,13 @@ JB_LAYOUT_ASSERT(sizeof(jb_activity_report) == 40 && offsetof(jb_activity_report
 JB_LAYOUT_ASSERT(sizeof(jb_activity_unit_report) == 32 && offsetof(jb_activity_unit_report, none) == 8 &&
                      offsetof(jb_activity_unit_report, many) == 24,
                  "jb_activity_unit_report");
+JB_LAYOUT_ASSERT(sizeof(jb_pitch_opts) == 112 && offsetof(jb_pitch_opts, min_f0) == 8 &&
+                     offsetof(jb_pitch_opts, pov_scale) == 56 && offsetof(jb_pitch_opts, norm_left) == 80 &&
+                     offsetof(jb_pitch_opts, grid) == 88 && offsetof(jb_pitch_opts, reserved) == 96,
+                 "jb_pitch_opts");
+JB_LAYOUT_ASSERT(sizeof(jb_pitch_geometry_t) == 56 && offsetof(jb_pitch_geometry_t, wl) == 16 &&
+                     offsetof(jb_pitch_geometry_t, S) == 32 && offsetof(jb_pitch_geometry_t, choice_bytes) == 52,
+                 "jb_pitch_geometry_t");
 JB_LAYOUT_ASSERT(sizeof(jb_join_opts) == 40 && offsetof(jb_join_opts, fade_ms) == 24 &&
                      offsetof(jb_join_opts, reserved) == 32, "jb_join_opts");
 JB_LAYOUT_ASSERT(sizeof(jb_loudness_report) == 40 && offsetof(jb_loudness_report, gain_db) == 24 &&

@@ -527,6 +527,54 @@ def activity(win_ms=25, hop_ms=10, gate_db=40, grid="snip", reference="peak", co
     return o
 
 
+PITCH_SNIP, PITCH_KALDI = 0, 1
+PITCH_F64, PITCH_RAW, PITCH_RAW_LOG = 1, 2, 4
+PITCH_RATE = 4000
+PITCH_MAX_DOWN = 4096
+PITCH_MAX_SCRATCH = 1 << 32
+_PITCH_GRIDS = {"snip": PITCH_SNIP, "kaldi": PITCH_KALDI}
+
+
+class PitchOpts(C.Structure):
+    """jb_pitch_opts: the frame grid, the lag grid, the tracker's costs and the post-processing of a pitch request."""
+    _fields_ = [("win_us", C.c_uint32), ("hop_us", C.c_uint32), ("min_f0", C.c_double), ("max_f0", C.c_double),
+                ("delta_pitch", C.c_double), ("penalty_factor", C.c_double), ("soft_min_f0", C.c_double),
+                ("nccf_ballast", C.c_double), ("pov_scale", C.c_double), ("pitch_scale", C.c_double),
+                ("delta_scale", C.c_double), ("norm_left", C.c_uint32), ("norm_right", C.c_uint32),
+                ("grid", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class PitchGeometry(C.Structure):
+    """jb_pitch_geometry_t: T and n4, the window and hop at the unit's rate and at 4 kHz, the lag grid's size and the
+    integer lags' range, a row's columns and element bytes, and the tracker's scratch bytes per frame."""
+    _fields_ = [("T", C.c_uint64), ("n4", C.c_uint64), ("wl", C.c_uint32), ("hop", C.c_uint32), ("wl4", C.c_uint32),
+                ("sh4", C.c_uint32), ("S", C.c_uint32), ("lag_first", C.c_uint32), ("lag_last", C.c_uint32),
+                ("width", C.c_uint32), ("elem", C.c_uint32), ("choice_bytes", C.c_uint32)]
+
+
+def kaldi_pitch():
+    """jb_pitch_kaldi: a PitchOpts with Kaldi's defaults (25 / 10 ms, 50..400 Hz, the Kaldi grid, f32, 3 columns)."""
+    o = PitchOpts()
+    check(lib().jb_pitch_kaldi(C.byref(o)))
+    return o
+
+
+def pitch(win_ms=25, hop_ms=10, grid="kaldi", raw=False, raw_log=False, f64=False, **fields):
+    """A PitchOpts: Kaldi's defaults with the window and hop in milliseconds, the grid by name ("snip", "kaldi") or
+    constant, raw=True for the tracker's two columns (p, Hz), raw_log=True for the fourth column, f64=True for float64
+    elements, and any other field of jb_pitch_opts by name (min_f0, max_f0, delta_pitch, ...)."""
+    o = kaldi_pitch()
+    o.win_us, o.hop_us = int(round(win_ms * 1000)), int(round(hop_ms * 1000))
+    o.grid = _PITCH_GRIDS.get(grid, grid)
+    o.flags = PITCH_F64 * bool(f64) | PITCH_RAW * bool(raw) | PITCH_RAW_LOG * bool(raw_log)
+    names = {f[0] for f in PitchOpts._fields_} - {"reserved"}
+    for k, v in fields.items():
+        if k not in names:
+            raise TypeError(f"jb_pitch_opts has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
 FILTER_MAX_SECTIONS = 4
 FILTER_HIGHPASS, FILTER_LOWPASS, FILTER_PEAKING, FILTER_LOWSHELF, FILTER_HIGHSHELF, FILTER_NOTCH, FILTER_RAW = range(1, 8)
 
@@ -926,6 +974,9 @@ SYMBOLS = [
     "jb_activity_pcm_batch_i16", "jb_activity_free", "jb_batch_set_activity", "jb_batch_activity_shape",
     "jb_batch_activity_size", "jb_batch_read_activity", "jb_batch_read_activity_all", "jb_batch_activity_report",
     "jb_batch_activity_unit_report", "jb_synthesize_programme_activity",
+    "jb_pitch_kaldi", "jb_pitch_geometry", "jb_pitch_lags", "jb_pitch_host", "jb_pitch_pcm_batch", "jb_pitch_free",
+    "jb_batch_set_pitch", "jb_batch_pitch_shape", "jb_batch_pitch_size", "jb_batch_read_pitch", "jb_batch_read_pitch_all",
+    "jb_synthesize_pitch", "jb_synthesize_batch_pitch", "jb_synthesize_batch_each_pitch", "jb_synthesize_programme_pitch",
     "jb_batch_set_filter", "jb_batch_filter_coefficients", "jb_filter_design", "jb_filter_pcm_host",
     "jb_filter_pcm_batch", "jb_filter_pcm_batch_i16", "jb_filter_free", "jb_engine_set_filter", "jb_engine_get_filter",
     "jb_batch_set_fir", "jb_batch_fir_geometry", "jb_engine_set_fir", "jb_fir_host", "jb_fir_geometry",
@@ -1320,6 +1371,28 @@ def lib():
     L.jb_batch_read_activity_all.argtypes = [vp, C.POINTER(vp)]
     L.jb_batch_activity_report.argtypes = [vp, sz, sz, acrp]
     L.jb_batch_activity_unit_report.argtypes = [vp, sz, acup]
+    ptop = C.POINTER(PitchOpts)
+    L.jb_pitch_kaldi.argtypes = [ptop]
+    L.jb_pitch_geometry.argtypes = [ptop, C.c_uint32, sz, C.POINTER(PitchGeometry)]
+    L.jb_pitch_lags.argtypes = [ptop, vp, sz, C.POINTER(sz)]
+    L.jb_pitch_host.argtypes = [vp, sz, C.c_uint32, ptop, vp, sz, vp, vp, vp]
+    L.jb_pitch_pcm_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, u32p, ptop, C.c_int32, C.POINTER(vp), u64p, u32p,
+                                     C.POINTER(vp)]
+    L.jb_pitch_free.argtypes = [vp]
+    L.jb_pitch_free.restype = None
+    L.jb_batch_set_pitch.argtypes = [vp, ptop]
+    L.jb_batch_pitch_shape.argtypes = [vp, sz, C.POINTER(sz), u32p, u32p]
+    L.jb_batch_pitch_size.argtypes = [vp, sz, C.POINTER(sz)]
+    L.jb_batch_read_pitch.argtypes = [vp, sz, vp, sz]
+    L.jb_batch_read_pitch_all.argtypes = [vp, C.POINTER(vp)]
+    L.jb_synthesize_pitch.argtypes = [vp, C.POINTER(C.c_char_p), sz, ptop, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_batch_pitch.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, ptop,
+                                            C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_batch_each_pitch.argtypes = [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32,
+                                                 ptop, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz)]
+    L.jb_synthesize_programme_pitch.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int32, ptop,
+                                                C.POINTER(JoinOpts), C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz),
+                                                C.POINTER(C.c_uint64)]
     flp, bqp = C.POINTER(Filter), C.POINTER(Biquad)
     L.jb_batch_set_filter.argtypes = [vp, flp, sz]
     L.jb_batch_filter_coefficients.argtypes = [vp, sz, bqp, u32p]
@@ -2287,6 +2360,75 @@ def activity_pcm(pcms, hz, opts, req=None, mix=None, device: int = -1):
         cols.append(list(reps[k:k + int(Cs[p])]))
         k += int(Cs[p])
     return labels, cols, list(units[:P.value])
+
+
+def pitch_frames(data: bytes, opts):
+    """The rows [T][width] of a pitch sink's bytes under the PitchOpts `opts`."""
+    import numpy as np
+
+    width = 2 if opts.flags & PITCH_RAW else 4 if opts.flags & PITCH_RAW_LOG else 3
+    return np.frombuffer(data, dtype=np.float64 if opts.flags & PITCH_F64 else np.float32).reshape(-1, width).copy()
+
+
+def take_pitch(L, bufs, ns, n, opts):
+    """ndarrays [T, width] of n library-owned outputs, each released with jb_pitch_free."""
+    return [pitch_frames(d, opts) for d in _take(L.jb_pitch_free, bufs, ns, n)]
+
+
+def pitch_geometry(opts, hz: int, n: int):
+    """jb_pitch_geometry: the PitchGeometry of a unit of n samples at hz under the PitchOpts `opts`."""
+    g = PitchGeometry()
+    check(lib().jb_pitch_geometry(C.byref(opts), int(hz), int(n), C.byref(g)))
+    return g
+
+
+def pitch_lags(opts):
+    """jb_pitch_lags: the lags of the grid in seconds, a float64 array [S]."""
+    import numpy as np
+
+    S = C.c_size_t()
+    check(lib().jb_pitch_lags(C.byref(opts), None, 0, C.byref(S)))
+    out = np.zeros(S.value, dtype=np.float64)
+    check(lib().jb_pitch_lags(C.byref(opts), out.ctypes.data, out.size, None))
+    return out
+
+
+def pitch_host(pcm, hz: int, opts, grid: bool = False):
+    """jb_pitch_host: (rows [T][width], lag_index [T] uint32) of the float64 samples `pcm`, in plain C++ on the host (no
+    GPU); with grid=True also (Q, p), each [T][S]: the two NCCFs over the lag grid."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pcm, dtype=np.float64)
+    g = pitch_geometry(opts, hz, a.size)
+    T = int(g.T)
+    out = np.zeros((T, g.width), dtype=np.float64 if g.elem == 8 else np.float32)
+    idx = np.zeros(T, dtype=np.uint32)
+    Q = np.zeros((T, g.S) if grid else (0, g.S), dtype=np.float64)
+    P = np.zeros_like(Q)
+    check(lib().jb_pitch_host(a.ctypes.data if a.size else None, a.size, int(hz), C.byref(opts),
+                              out.ctypes.data if T else None, out.nbytes, idx.ctypes.data if T else None,
+                              Q.ctypes.data if grid and T else None, P.ctypes.data if grid and T else None))
+    return (out, idx, Q, P) if grid else (out, idx)
+
+
+def pitch_pcm(pcms, hz, opts, device: int = -1):
+    """jb_pitch_pcm_batch: the pitch rows of caller-held float64 PCM, tracked on the GPU; hz: one rate, or one per array.
+    ([rows [T][width] per unit], [lag_index [T] uint32 per unit])."""
+    import numpy as np
+
+    arrs, n, ins, nin = _pcm_args(pcms, np.float64, void=True)
+    rates = [int(hz)] * n if np.isscalar(hz) else [int(h) for h in hz]
+    if len(rates) != n:
+        raise ValueError("give one rate, or one per array")
+    hzs = (C.c_uint32 * max(n, 1))(*rates)
+    outs, lags = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+    Ts, Ws = (C.c_uint64 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+    L = lib()
+    check(L.jb_pitch_pcm_batch(ins, nin, n, hzs, C.byref(opts), device, outs, Ts, Ws, lags))
+    dtype = np.float64 if opts.flags & PITCH_F64 else np.float32
+    flat = _take(L.jb_pitch_free, outs, [int(Ts[u]) * int(Ws[u]) for u in range(n)], n, dtype)
+    idx = _take(L.jb_pitch_free, lags, [int(Ts[u]) for u in range(n)], n, np.uint32)
+    return [flat[u].reshape(int(Ts[u]), int(Ws[u])) for u in range(n)], idx
 
 
 def _biquads(arr, n):

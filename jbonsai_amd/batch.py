@@ -289,6 +289,7 @@ class Batch:
         self._fbank = None  # the filterbank request the batch holds (set_fbank)
         self._mfcc = None   # the cepstral request the batch holds (set_mfcc): (FbankOpts, MfccOpts)
         self._melspec = None  # the mel spectrogram request the batch holds (set_melspec)
+        self._pitch = None  # the pitch request the batch holds (set_pitch)
 
     def __len__(self):
         return self._L.jb_batch_size(self._h)
@@ -674,6 +675,32 @@ class Batch:
             opts = F.melspec(**kw)
         F.check(self._L.jb_batch_set_melspec(self._h, C.byref(opts) if opts is not None else None))
         self._melspec = opts  # (a refused call leaves the batch's request, and this copy of it, as they were)
+
+    def set_pitch(self, opts=None, **kw):
+        """jb_batch_set_pitch: the run also tracks the pitch features of each utterance's (behind a join or mix: each
+        programme's and stem's) final f64 PCM on the GPU.  opts: F.PitchOpts (J.kaldi_pitch(), J.pitch(...)), or the
+        keywords of J.pitch; None without keywords withdraws the request.  An f64 batch only; before the first run."""
+        if opts is None and kw:
+            opts = F.pitch(**kw)
+        F.check(self._L.jb_batch_set_pitch(self._h, C.byref(opts) if opts is not None else None))
+        self._pitch = opts  # (a refused call leaves the batch's request, and this copy of it, as they were)
+
+    def pitch_shape(self, i):
+        """(T, width, hz) of unit i's pitch features (jb_batch_pitch_shape)."""
+        T, w, hz = C.c_size_t(), C.c_uint32(), C.c_uint32()
+        F.check(self._L.jb_batch_pitch_shape(self._h, i, C.byref(T), C.byref(w), C.byref(hz)))
+        return T.value, w.value, hz.value
+
+    def pitch_size(self, i) -> int:
+        return self._sink_size("pitch", i)
+
+    def read_pitch(self, i):
+        """Unit i's pitch features, an ndarray [T, width] (jb_batch_pitch_size + jb_batch_read_pitch)."""
+        return F.pitch_frames(self._sink_read("pitch", i), self._pitch)
+
+    def read_pitch_all(self):
+        """Every unit's pitch features through one device-to-host copy (jb_batch_read_pitch_all)."""
+        return [F.pitch_frames(d, self._pitch) for d in self._sink_read_all("pitch")]
 
     def melspec_shape(self, i):
         """(T, n_mels, hz) of unit i's mel spectrogram (jb_batch_melspec_shape)."""

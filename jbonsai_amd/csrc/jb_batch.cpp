@@ -2987,6 +2987,38 @@ int jb_batch_read_melspec_all(jb_batch *hb, uint8_t *const *dst)
     return read_bytes_all(hb, jb::SynthSink::Melspec, dst);
 }
 
+int jb_batch_set_pitch(jb_batch *hb, const jb_pitch_opts *opts)
+{
+    return hb ? ((Batch *)hb)->out.set_pitch(opts) : JB_ERR_INVALID;
+}
+
+int jb_batch_pitch_shape(jb_batch *hb, size_t unit, size_t *T, uint32_t *width, uint32_t *hz)
+{
+    const int rc = sink_planned(hb, jb::SynthSink::Pitch, unit);
+    if (rc)
+        return rc;
+    const jb::OutputChain &out = ((Batch *)hb)->out;
+    if (T)
+        *T = (size_t)out.pitch_place(unit).T;
+    if (width)
+        *width = out.pitch_place(unit).width;
+    if (hz)
+        *hz = out.fbank_hz(unit);
+    return JB_OK;
+}
+
+int jb_batch_pitch_size(jb_batch *hb, size_t unit, size_t *n_bytes)
+{
+    return sink_size(hb, jb::SynthSink::Pitch, unit, n_bytes);
+}
+
+int jb_batch_read_pitch(jb_batch *hb, size_t unit, uint8_t *dst, size_t cap)
+{
+    return sink_read(hb, jb::SynthSink::Pitch, unit, dst, cap, "jb_batch_read_pitch");
+}
+
+int jb_batch_read_pitch_all(jb_batch *hb, uint8_t *const *dst) { return read_bytes_all(hb, jb::SynthSink::Pitch, dst); }
+
 int jb_batch_set_activity(jb_batch *hb, const jb_activity_opts *opts)
 {
     return hb ? ((Batch *)hb)->out.set_activity(opts) : JB_ERR_INVALID;

@@ -1917,6 +1917,8 @@ int SynthRun::apply_conditions(jb::OutputChain &out, size_t lo, size_t hi)
         return rc;
     if (rq.sink == jb::SynthSink::Melspec && (rc = out.set_melspec(rq.melspec)))
         return rc;
+    if (rq.sink == jb::SynthSink::Pitch && (rc = out.set_pitch(rq.pitch)))
+        return rc;
     return JB_OK;
 }
 
@@ -2031,6 +2033,7 @@ int SynthRun::read_outputs(jb::Batch *b, size_t lo, size_t hi)
             rq.counts[lo + p] = rq.sink == jb::SynthSink::Fbank  ? (size_t)b->out.fbank_place(p).T
                                 : rq.sink == jb::SynthSink::Mfcc ? (size_t)b->out.mfcc_place(p).T
                                 : rq.sink == jb::SynthSink::Melspec ? (size_t)b->out.melspec_place(p).T
+                                : rq.sink == jb::SynthSink::Pitch ? (size_t)b->out.pitch_place(p).T
                                 : rq.join                        ? (size_t)b->out.programme(p).n
                                                                  : b->out.samples(p);
         return read_stem_reports(b);
@@ -2287,6 +2290,15 @@ static jb::SynthRequest &request_melspec(jb::SynthRequest &rq, const jb_melspec_
     return rq;
 }
 
+static jb::SynthRequest &request_pitch(jb::SynthRequest &rq, const jb_pitch_opts *opts, size_t *n_frames)
+{
+    rq.sink = jb::SynthSink::Pitch;
+    rq.i16 = false;
+    rq.pitch = opts;
+    rq.counts = n_frames;
+    return rq;
+}
+
 static jb::SynthRequest &request_join(jb::SynthRequest &rq, const jb_join_opts *join, uint64_t *starts)
 {
     rq.join = join;
@@ -2410,6 +2422,8 @@ static int check_sink_opts(const jb::SynthRequest &rq, const char *who)
         return rc ? rc : jb::mfcc_check_opts((const jb::MfccOpts *)rq.mfcc, rq.fbank->n_mels, who);
     case jb::SynthSink::Melspec:
         return jb::mel_check_opts((const jb::MelOpts *)rq.melspec, who);
+    case jb::SynthSink::Pitch:
+        return jb::pitch_check_opts((const jb::PitchOpts *)rq.pitch, who, nullptr);
     }
     return JB_ERR_INVALID;
 }
@@ -2701,6 +2715,40 @@ int jb_synthesize_programme_melspec(const jb_engine *e, const char *const *lines
     jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
     request_join(request_melspec(rq, opts, n_frames), join, starts);
     return synthesize_entry("jb_synthesize_programme_melspec", rq, nullptr, true);
+}
+
+int jb_synthesize_batch_pitch(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                              int32_t device, const jb_pitch_opts *opts, uint8_t **bytes, size_t *n_bytes,
+                              size_t *n_frames)
+{
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return synthesize_entry("jb_synthesize_batch_pitch", request_pitch(rq, opts, n_frames), nullptr, false);
+}
+
+int jb_synthesize_batch_each_pitch(const jb_engine *const *engines, const char *const *lines, const size_t *line_off,
+                                   size_t n_utts, int32_t device, const jb_pitch_opts *opts, uint8_t **bytes,
+                                   size_t *n_bytes, size_t *n_frames)
+{
+    jb::SynthRequest rq = batch_request(nullptr, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    return synthesize_entry("jb_synthesize_batch_each_pitch", request_pitch(rq, opts, n_frames), engines, false);
+}
+
+int jb_synthesize_pitch(const jb_engine *e, const char *const *lines, size_t n, const jb_pitch_opts *opts,
+                        uint8_t **bytes, size_t *n_bytes, size_t *n_frames)
+{
+    if (!bytes || !n_bytes)
+        return JB_ERR_INVALID;
+    size_t off[2] = {0, n};
+    return jb_synthesize_batch_pitch(e, lines, off, 1, -1, opts, bytes, n_bytes, n_frames);
+}
+
+int jb_synthesize_programme_pitch(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,
+                                  int32_t device, const jb_pitch_opts *opts, const jb_join_opts *join,
+                                  uint8_t **bytes, size_t *n_bytes, size_t *n_frames, uint64_t *starts)
+{
+    jb::SynthRequest rq = batch_request(e, lines, line_off, n_utts, device, (void **)bytes, n_bytes);
+    request_join(request_pitch(rq, opts, n_frames), join, starts);
+    return synthesize_entry("jb_synthesize_programme_pitch", rq, nullptr, true);
 }
 
 int jb_synthesize_programme(const jb_engine *e, const char *const *lines, const size_t *line_off, size_t n_utts,

@@ -16,6 +16,7 @@
 #include "jb_noise.h"
 #include "jb_output.h"
 #include "jb_pcm_call.h"
+#include "jb_pitch.h"
 #include "jb_room.h"
 
 #include <cmath>
@@ -45,7 +46,7 @@ int noise_table(int device, size_t need, std::shared_ptr<NoiseDev> *out);
 void release_cached_memory(); // empties the per-device pools of finished batches' memory
 void set_cached_memory_limit(size_t bytes); // cap of a device's pool (JB_DEVICE_POOL_MB at start)
 // What an engine-level call hands out per utterance (or per programme): PCM, or the bytes of one of the encoders
-enum class SynthSink { Pcm, Flac, Formatted, Adpcm, Fbank, Mfcc, Melspec };
+enum class SynthSink { Pcm, Flac, Formatted, Adpcm, Fbank, Mfcc, Melspec, Pitch };
 struct ByteSpan { // an output's place in the host copy of a byte sink's slab (OutputChain::read_bytes_all)
     uint64_t off, bytes;
 };
@@ -70,6 +71,7 @@ struct SynthRequest {
     const jb_fbank_opts *fbank = nullptr;    // Fbank
     const jb_mfcc_opts *mfcc = nullptr;      // Mfcc: behind the filterbank options of `fbank`
     const jb_melspec_opts *melspec = nullptr; // Melspec
+    const jb_pitch_opts *pitch = nullptr;     // Pitch
     size_t *counts = nullptr;                // counts[u] (may be null), by the sink: the samples output u's blocks
                                              // encode (Adpcm), or its frames (Fbank, Mfcc, Melspec)
     const jb_join_opts *join = nullptr;      // jb_synthesize_programme*: all utterances are one programme, the one
@@ -504,6 +506,17 @@ hipError_t launch_activity(bool i16, const ActCol *cols_dev, uint32_t n_cols, ui
                            const ActUnit *units_dev, uint32_t n_units, uint64_t unit_wgs, uint64_t *col_max,
                            ActReport *reports, ActUnitReport *unit_reports, const ActLaunch &L, hipStream_t stream);
 
+// The pitch stage (jb_pitch.hip; the rules, PitchClass and PitchUtt: jb_pitch.h; the host half: jb_pitch.cpp).  opts
+// checked with set_error naming the field under the entry `who` (null: refused), the lag grid into *grid (may be null);
+// a unit's rate checked (JB_ERR_UNSUPPORTED past the phase table's cap), its phase table into *down (may be null)
+int pitch_check_opts(const PitchOpts *opts, const char *who, PitchGrid *grid);
+int pitch_check_rate(uint32_t hz, size_t unit, const char *who, PitchDown *down);
+jb_pitch_geometry_t pitch_geometry_of(const PitchOpts &o, const PitchGrid &g, uint32_t hz, uint64_t n);
+// utts_dev[0..n_utts) in unit order with `tiles`, `post_wgs` and `cols_wgs` workgroups in all: k_pitch_down,
+// k_pitch_track (a workgroup per unit), k_pitch_post and, without JB_PITCH_RAW, k_pitch_cols
+hipError_t launch_pitch(const PitchUtt *utts_dev, uint32_t n_utts, uint64_t tiles, uint64_t post_wgs, uint64_t cols_wgs,
+                        const PitchClass &cls, hipStream_t stream);
+
 // The filter stage (jb_filter.hip; the rules, FilterClass and FilterUtt: jb_filter.h; the host half: jb_filter.cpp)
 // f at `hz`: its coefficients into c ([n_sections][5], may be null), or JB_ERR_INVALID with set_error naming the
 // utterance `utt`, the section and the field
@@ -931,6 +944,9 @@ struct OutputChain {
     // the mel spectrograms (jb_melspec.h): an f64 batch only; checked at every utterance's output rate (NULL: the
     // request is withdrawn); set_output_rate checks the combined request again.  Independent of set_fbank and set_mfcc
     int set_melspec(const jb_melspec_opts *opts);
+    // the pitch features (jb_pitch.h): an f64 batch only; checked at every utterance's output rate and against
+    // JB_PITCH_MAX_SCRATCH at the first run (NULL: the request is withdrawn)
+    int set_pitch(const jb_pitch_opts *opts);
     // the speech-activity labels (jb_activity.h), a side output beside whatever sinks the batch has, f64 or 16-bit:
     // checked at every unit's rate and against the caps under the present requests (NULL: the request is withdrawn),
     // and again at the first run, since the rates and the programmes may be set behind it
@@ -1013,6 +1029,7 @@ struct OutputChain {
     const OutMfccUtt &mfcc_place(size_t u) const { return plan.mfcc[u]; }
     const OutMelUtt &melspec_place(size_t u) const { return plan.melspec[u]; }
     uint32_t melspec_mels() const { return ml_p.n_mels; }
+    const OutPitchUtt &pitch_place(size_t u) const { return plan.pitch[u]; }
     uint32_t fbank_mels() const { return fb_p.n_mels; }
     uint32_t fbank_hz(size_t u) const { return joined() ? plan.units[u].hz : plan.utt[u].hz; }
     // the join: what the encoders' entries index (the programmes, or the utterances without a request), an
@@ -1047,6 +1064,8 @@ private:
     FrameOpts fr_p{};
     bool ml_on = false;                        // mel spectrograms are requested
     MelOpts ml_p{};
+    bool pt_on = false;                        // pitch features are requested
+    PitchOpts pt_p{};
     bool act_on = false;                       // speech-activity labels are requested
     ActOpts act_p{};
     std::vector<MixUtt> prog_req;              // [B] the programme request, a join's (join_as_mix) or a mix's; empty: none
@@ -1187,6 +1206,18 @@ private:
         MelPass pass;
         double *gmax = nullptr, *umax = nullptr; // with a range: one double per workgroup, one per unit
     } ml;
+    struct Pitch { // follows `units`: a unit whose final PCM changed is tracked again, whole
+        DevList<PitchUtt> utts;        // [U]; a launch's entries carry its own three prefix sums
+        PitchClass cls{};              // the tables of the request on the device
+        uint8_t *out = nullptr;        // the rows' bytes, unit after unit on 16-byte boundaries (plan.pitch_bytes)
+        double *y4 = nullptr;          // the 4 kHz signals (plan.pitch_words)
+        double *tables = nullptr, *down = nullptr; // the grid's tables, and the distinct rates' phase tables
+        uint32_t *tap = nullptr;
+        double *tile = nullptr, *pv = nullptr, *pw = nullptr; // the tiles' sums; p and pi of every frame
+        uint16_t *choice = nullptr;    // 2 S bytes a frame: allocated at the first run that needs it
+        uint32_t *idx = nullptr;       // the chosen lag of every frame
+        uint64_t tiles = 0, post = 0, cols = 0; // of the next launch
+    } pt;
     struct Activity { // follows `units`: a unit with a rewritten member is measured again, whole
         DevList<ActCol> cols;        // every column, unit after unit; total: the energy kernel's workgroups
         DevList<ActUnit> units;      // [U]; total: the counting kernel's workgroups
@@ -1227,6 +1258,7 @@ private:
     bool fbank() const { return plan.fbank_src != OutSlab::None; }
     bool mfcc() const { return plan.mfcc_src != OutSlab::None; }
     bool melspec() const { return plan.melspec_src != OutSlab::None; }
+    bool pitch() const { return plan.pitch_src != OutSlab::None; }
     bool activity() const { return plan.act_src.slab != OutSlab::None; }
     // why the plan holds no activity stage for the request (JB_ERR_INVALID naming the unit and the field, or
     // JB_ERR_UNSUPPORTED past a cap)
@@ -1235,6 +1267,7 @@ private:
     // limits at some rate
     template <class Opts> int check_rates(const Opts &opts, const std::vector<uint32_t> &want, const char *who) const;
     int check_mfcc(const FbankOpts &fopts, const std::vector<uint32_t> &want, const char *who) const;
+    int check_pitch(const std::vector<uint32_t> &want, const char *who) const; // every rate's phase table under `want`
     // what the three feature setters refuse alike: a batch without PCM, a 16-bit one (`noun` stage reads the f64
     // output), a batch that has run
     int check_feature_settable(const char *entry, const char *noun) const;
@@ -1277,6 +1310,7 @@ private:
     int prepare_fbank(), select_fbank(const RedoScope *scope), launch_fbank(bool redo);
     int prepare_mfcc(), select_mfcc(const RedoScope *scope), launch_mfcc(bool redo);
     int prepare_melspec(), select_melspec(const RedoScope *scope), launch_melspec(bool redo);
+    int prepare_pitch(), select_pitch(const RedoScope *scope), launch_pitch(bool redo);
     int prepare_activity(), select_activity(const RedoScope *scope), launch_activity(bool redo);
     int check_ready(bool requested, const char *not_run, const char *not_set) const;
     struct ByteSink {

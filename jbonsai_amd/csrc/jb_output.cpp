@@ -217,6 +217,33 @@ OutPlan plan_output(const OutPlanIn &in)
                 p.alloc[(size_t)OutSlab::MelY] = std::max<uint64_t>(words, 2);
         }
     }
+    // the pitch features beside them, independent of the three: the same final f64 to a 4 kHz signal of the stage's
+    // own, then rows of each unit's own length (a request that some rate refuses is no request: the chain has checked it)
+    if (in.pitch && !p.final.i16 && !pitch_opts_fault(*in.pitch)) {
+        const PitchOpts &po = *in.pitch;
+        std::vector<OutPitchUtt> f(units.size());
+        uint64_t bytes = 0, words = 0;
+        bool ok = true;
+        for (size_t u = 0; u < units.size() && ok; u++) {
+            const uint32_t hz = units[u].hz;
+            PitchDown down;
+            bool cap = false;
+            if (!(ok = !pitch_down_fault(hz, &down, &cap)))
+                break;
+            const uint64_t T = pitch_frames(po.grid, units[u].n, (uint32_t)fbank_round_us(hz, po.win_us),
+                                            (uint32_t)fbank_round_us(hz, po.hop_us));
+            const uint32_t width = pitch_width(po.flags), elem = (uint32_t)pitch_elem(po.flags);
+            f[u] = {bytes, T * width * elem, T, width, elem, pitch_n4(units[u].n, hz), words};
+            bytes += (f[u].bytes + 15) & ~(uint64_t)15;
+            words += (f[u].n4 + 1) & ~(uint64_t)1;
+        }
+        if (ok) {
+            p.pitch_src = enc.slab;
+            p.pitch = std::move(f);
+            p.pitch_bytes = std::max<uint64_t>(bytes, 16);
+            p.pitch_words = std::max<uint64_t>(words, 2);
+        }
+    }
     // the speech-activity labels, a side output beside all of them: a column per member of each unit measured on the
     // member's own final PCM at its start, or one column on the unit's PCM (a request that some unit refuses is no
     // request: the chain has checked it)

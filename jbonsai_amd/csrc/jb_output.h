@@ -17,6 +17,7 @@
 #include "jb_fbank.h"
 #include "jb_mfcc.h"
 #include "jb_melspec.h"
+#include "jb_pitch.h"
 #include "jb_join.h"
 #include "jb_mix.h"
 
@@ -78,6 +79,7 @@ struct OutPlanIn {
     const MfccOpts *mfcc = nullptr;        // f64 logarithms itself) and its options; both or neither
     const FrameOpts *frame = nullptr;      // the frame request beside the fbank and mfcc ones (JB_FRAME_REFLECT: their T); nullptr: none
     const MelOpts *melspec = nullptr;      // the mel spectrogram request (jb_melspec.h), checked at every output rate; nullptr: none
+    const PitchOpts *pitch = nullptr;      // the pitch request (jb_pitch.h), checked at every output rate; nullptr: none
     const ActOpts *activity = nullptr;     // the speech-activity request (jb_activity.h), checked at every unit's rate; nullptr: none
 };
 
@@ -116,6 +118,13 @@ struct OutMelUtt { // a unit's mel spectrogram in the Mel slab and, with a range
     uint64_t yoff;       // its first value in the MelY slab, in doubles (a 16-byte boundary); 0 without a range
 };
 
+struct OutPitchUtt { // a unit's pitch rows in the stage's byte block and its 4 kHz signal in its f64 block
+    uint64_t off, bytes; // byte offset (16-byte aligned) and T * width * bytes per element
+    uint64_t T;          // its frames: the fbank stage's under the same window, hop and grid
+    uint32_t width, elem; // elements of a row and bytes of an element
+    uint64_t n4, yoff;   // its samples at 4 kHz and the first one's place in the f64 block, in doubles (a 16-byte boundary)
+};
+
 struct OutUnit { // a programme in the join slab: what the encoders behind a join take for an utterance
     uint32_t hz;
     uint64_t n, off; // samples and first sample in the join slab (a 16-byte boundary)
@@ -151,6 +160,10 @@ struct OutPlan {
     std::vector<OutMfccUtt> mfcc;      // [B] with a cepstral stage, else empty
     OutSlab melspec_src = OutSlab::None; // f64 the mel stage reads: what fbank_src would name (None: no request)
     std::vector<OutMelUtt> melspec;      // [B] with a mel stage, else empty
+    OutSlab pitch_src = OutSlab::None;   // f64 the pitch stage reads: what fbank_src would name (None: no request)
+    std::vector<OutPitchUtt> pitch;      // [B] with a pitch stage, else empty ([P], or [P + S] with stems, behind a join or mix)
+    uint64_t pitch_bytes = 0, pitch_words = 0; // the stage's two blocks: the rows' bytes and the 4 kHz signals' doubles
+                                         // (blocks of the stage's own, as the activity stage's are: not slabs of `alloc`)
     // With a join request: the stage reads what `final` names and writes the programmes to a slab of its own; flac,
     // fmt_src, adpcm_src, fbank_src, mfcc_src and melspec_src then name that slab, and fmt, adpcm, fbank, mfcc and melspec have [P] entries laid
     // out from `units`

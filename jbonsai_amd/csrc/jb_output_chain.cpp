@@ -49,6 +49,7 @@ void OutputChain::replan()
     in.mfcc = mf_on ? &mf_p : nullptr;
     in.frame = fr_on ? &fr_p : nullptr;
     in.melspec = ml_on ? &ml_p : nullptr;
+    in.pitch = pt_on ? &pt_p : nullptr;
     in.activity = act_on ? &act_p : nullptr;
     plan = plan_output(in);
 }
@@ -120,7 +121,8 @@ int OutputChain::set_output_rate(const uint32_t *hz, size_t n)
         (rc = check_noise(want, "jb_batch_set_output_rate")) ||
         (fb_on && (rc = check_rates(fb_p, want, "jb_batch_set_output_rate"))) ||
         (mf_on && (rc = check_mfcc(mf_fb, want, "jb_batch_set_output_rate"))) ||
-        (ml_on && (rc = check_rates(ml_p, want, "jb_batch_set_output_rate"))))
+        (ml_on && (rc = check_rates(ml_p, want, "jb_batch_set_output_rate"))) ||
+        (pt_on && (rc = check_pitch(want, "jb_batch_set_output_rate"))))
         return rc;
     want_hz = std::move(want);
     replan();
@@ -422,6 +424,32 @@ int OutputChain::set_melspec(const jb_melspec_opts *opts)
     ml_on = opts != nullptr;
     if (opts)
         ml_p = *(const MelOpts *)opts;
+    replan();
+    return JB_OK;
+}
+
+int OutputChain::check_pitch(const std::vector<uint32_t> &want, const char *who) const
+{
+    int rc;
+    size_t u = 0;
+    for (uint32_t hz : rates_under(want))
+        if ((rc = pitch_check_rate(hz, u++, who, nullptr)))
+            return rc;
+    return JB_OK;
+}
+
+int OutputChain::set_pitch(const jb_pitch_opts *opts)
+{
+    int rc;
+    if (opts && (rc = pitch_check_opts((const PitchOpts *)opts, "jb_batch_set_pitch", nullptr)))
+        return rc;
+    if ((rc = check_feature_settable("jb_batch_set_pitch", "pitch")))
+        return rc;
+    if (opts && (rc = check_pitch(want_hz, "jb_batch_set_pitch")))
+        return rc;
+    pt_on = opts != nullptr;
+    if (opts)
+        pt_p = *(const PitchOpts *)opts;
     replan();
     return JB_OK;
 }
@@ -904,7 +932,7 @@ int OutputChain::prepare()
     if ((rc = prepare_resample()) || (rc = prepare_fir()) || (rc = prepare_noise()) || (rc = prepare_filter()) || (rc = prepare_loudness()) || (rc = prepare_limiter()) ||
         (rc = prepare_programme()) ||
         (rc = prepare_flac()) || (rc = prepare_format()) || (rc = prepare_adpcm()) ||
-        (rc = prepare_fbank()) || (rc = prepare_mfcc()) || (rc = prepare_melspec()) || (rc = prepare_activity()))
+        (rc = prepare_fbank()) || (rc = prepare_mfcc()) || (rc = prepare_melspec()) || (rc = prepare_pitch()) || (rc = prepare_activity()))
         return rc;
     if (plan.active()) {
         void *voc = slab[(size_t)plan.vocoder.slab];
@@ -919,7 +947,7 @@ int OutputChain::prepare()
 // uploaded (select_X) before its first launch, and one wait ends it
 int OutputChain::enqueue(const std::vector<uint8_t> *only)
 {
-    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || mfcc() || melspec() || joined() || activity()))
+    if (!ready || !(plan.active() || flac_on || formatted() || adpcm() || fbank() || mfcc() || melspec() || pitch() || joined() || activity()))
         return JB_OK;
     const bool redo = only != nullptr;
     static const LnGroups no_groups;
@@ -931,15 +959,15 @@ int OutputChain::enqueue(const std::vector<uint8_t> *only)
     if ((rc = select_resample(scope)) || (rc = select_fir(scope)) || (rc = select_noise(scope)) || (rc = select_filter(scope)) || (rc = select_loudness(scope)) ||
         (rc = select_limiter(scope)) || (rc = select_programme(scope)) || (rc = select_activity(scope)) || (rc = select_flac(scope)) || (rc = select_format(scope)) ||
         (rc = select_adpcm(scope)) || (rc = select_fbank(scope)) || (rc = select_mfcc(scope)) ||
-        (rc = select_melspec(scope)))
+        (rc = select_melspec(scope)) || (rc = select_pitch(scope)))
         return rc;
     // (an empty list is not uploaded: a redo that selects nothing has not touched the device)
-    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || pg.spans.n || act.cols.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n))
+    if (redo && !(rs.tiles.n || fir.direct.n || fir.part.n || noi.utts.n || fil.utts.n || ln.utts.n || ln.apply.n || lim.utts.n || pg.spans.n || act.cols.n || fl.work.n || fm.utts.n || ad.utts.n || fb.list.n || mf.utts.n || ml.pass.list.n || pt.utts.n))
         return JB_OK;
     if ((rc = launch_resample(redo)) || (rc = launch_fir(redo)) || (rc = launch_noise(redo)) || (rc = launch_filter(redo)) || (rc = launch_loudness(redo)) ||
         (rc = launch_limiter(redo)) || (rc = launch_programme(redo)) || (rc = launch_activity(redo)) || (rc = launch_flac(redo)) || (rc = launch_format(redo)) ||
         (rc = launch_adpcm(redo)) || (rc = launch_fbank(redo)) || (rc = launch_mfcc(redo)) ||
-        (rc = launch_melspec(redo)))
+        (rc = launch_melspec(redo)) || (rc = launch_pitch(redo)))
         return rc;
     hipError_t e;
     if (redo && (e = hipStreamSynchronize(b.stream_voc)) != hipSuccess)
@@ -2081,6 +2109,140 @@ int OutputChain::launch_melspec(bool redo)
     return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "k_melspec(redo)" : "k_melspec");
 }
 
+// ---- the pitch features beside them, of the same final f64: the decimator into the stage's f64 block, the tracker (one
+// workgroup per listed unit), the post pass and the columns on the same stream.  The tracker's choices, 2 S bytes a
+// frame, and the frames' lags, p and pi are blocks of the stage's own, allocated here: at the first run
+int OutputChain::prepare_pitch()
+{
+    if (!pitch())
+        return JB_OK;
+    const char *who = "jb_batch_set_pitch";
+    PitchGrid g;
+    int rc = pitch_check_opts(&pt_p, who, &g);
+    if (rc)
+        return rc;
+    const std::vector<EncUnit> units = enc_units();
+    const size_t U = units.size();
+    const double *src = (const double *)slab[(size_t)plan.pitch_src];
+    if ((rc = b.dalloc(&pt.out, plan.pitch_bytes, false)) || (rc = b.dalloc(&pt.y4, plan.pitch_words, false)))
+        return rc;
+    uint8_t *dst = pt.out;
+    double *y4 = pt.y4;
+    std::vector<uint64_t> fr0(U + 1, 0), tl0(U + 1, 0);
+    for (size_t u = 0; u < U; u++) {
+        fr0[u + 1] = fr0[u] + plan.pitch[u].T;
+        tl0[u + 1] = tl0[u] + pitch_tiles(plan.pitch[u].n4);
+    }
+    if (fr0[U] > kPitchMaxScratch / pitch_choice_bytes(g.S)) {
+        set_error(std::string(who) + ": the tracker's choices (" + std::to_string(pitch_choice_bytes(g.S)) +
+                  " bytes per frame) pass JB_PITCH_MAX_SCRATCH");
+        return JB_ERR_UNSUPPORTED;
+    }
+    // the grid's tables in one block (G, soft, 1 / lag, ln(1 / lag)), and the distinct rates' phase tables in another
+    std::vector<double> tab(g.G);
+    const size_t o_soft = tab.size();
+    tab.insert(tab.end(), g.soft.begin(), g.soft.end());
+    const size_t o_inv = tab.size();
+    tab.insert(tab.end(), g.inv_lag.begin(), g.inv_lag.end());
+    const size_t o_log = tab.size();
+    tab.insert(tab.end(), g.log_pitch.begin(), g.log_pitch.end());
+    std::vector<double> downs;
+    std::vector<uint32_t> seen;
+    std::vector<size_t> first;
+    std::vector<PitchDown> dn(U);
+    std::vector<size_t> w_of(U);
+    for (size_t u = 0; u < U; u++) {
+        if ((rc = pitch_check_rate(units[u].hz, u, who, &dn[u])))
+            return rc;
+        size_t k = 0;
+        while (k < seen.size() && seen[k] != units[u].hz)
+            k++;
+        if (k == seen.size()) {
+            seen.push_back(units[u].hz);
+            first.push_back(downs.size());
+            downs.insert(downs.end(), dn[u].W.begin(), dn[u].W.end());
+        }
+        w_of[u] = first[k];
+    }
+    if ((rc = b.dalloc(&pt.tables, tab.size(), false)) || (rc = upload_list(pt.tables, tab, "pitch tables")) ||
+        (rc = b.dalloc(&pt.down, downs.size(), false)) || (rc = upload_list(pt.down, downs, "pitch phase tables")) ||
+        (rc = b.dalloc(&pt.tap, g.tap.size(), false)) || (rc = upload_list(pt.tap, g.tap, "pitch taps")) ||
+        (rc = b.dalloc(&pt.tile, std::max<uint64_t>(2 * tl0[U], 2), false)) ||
+        (rc = b.dalloc(&pt.choice, std::max<uint64_t>(fr0[U] * g.S, 1), false)) ||
+        (rc = b.dalloc(&pt.idx, std::max<uint64_t>(fr0[U], 1), false)) ||
+        (rc = b.dalloc(&pt.pv, std::max<uint64_t>(fr0[U], 1), false)) ||
+        (rc = b.dalloc(&pt.pw, std::max<uint64_t>(fr0[U], 1), false)))
+        return rc;
+    PitchClass &C = pt.cls;
+    C = PitchClass{};
+    C.G = pt.tables;
+    C.soft = pt.tables + o_soft;
+    C.inv_lag = pt.tables + o_inv;
+    C.log_pitch = pt.tables + o_log;
+    C.tap = pt.tap;
+    C.kappa = g.kappa;
+    C.ballast = pt_p.nccf_ballast;
+    C.pov_scale = pt_p.pov_scale;
+    C.pitch_scale = pt_p.pitch_scale;
+    C.delta_scale = pt_p.delta_scale;
+    C.S = g.S;
+    C.a = g.a;
+    C.b = g.b;
+    C.wl4 = g.wl4;
+    C.sh4 = g.sh4;
+    C.grid = pt_p.grid;
+    C.flags = pt_p.flags;
+    C.left = pt_p.norm_left;
+    C.right = pt_p.norm_right;
+    pt.utts.host.assign(U, PitchUtt{});
+    for (size_t u = 0; u < U; u++) {
+        const OutPitchUtt &pl = plan.pitch[u];
+        PitchUtt &w = pt.utts.host[u];
+        w.x = src + units[u].off;
+        w.W = pt.down + w_of[u];
+        w.y4 = y4 + pl.yoff;
+        w.tile = pt.tile + 2 * tl0[u];
+        w.choice = pt.choice + fr0[u] * g.S;
+        w.idx = pt.idx + fr0[u];
+        w.pv = pt.pv + fr0[u];
+        w.pw = pt.pw + fr0[u];
+        w.out = dst + pl.off;
+        w.n = units[u].n;
+        w.n4 = pl.n4;
+        w.T = pl.T;
+        w.hzp = dn[u].hzp;
+        w.P = dn[u].P;
+        w.D = dn[u].D;
+    }
+    pitch_number(&pt.utts.host, &pt.tiles, &pt.post, &pt.cols);
+    if ((rc = pt.utts.alloc(b, U, U)))
+        return rc;
+    return pt.utts.upload("pitch work list");
+}
+
+// `units`: every unit whose final PCM changed, numbered among themselves
+int OutputChain::select_pitch(const RedoScope *scope)
+{
+    if (!pitch() || !scope) {
+        pitch_number(&pt.utts.host, &pt.tiles, &pt.post, &pt.cols);
+        return pt.utts.take_all();
+    }
+    std::vector<PitchUtt> sub;
+    for (size_t u = 0; u < pt.utts.host.size(); u++)
+        if (scope->units[u])
+            sub.push_back(pt.utts.host[u]);
+    pitch_number(&sub, &pt.tiles, &pt.post, &pt.cols);
+    return pt.utts.upload_redo(sub, kRedoLists);
+}
+
+int OutputChain::launch_pitch(bool redo)
+{
+    if (!pitch() || (redo && !pt.utts.n))
+        return JB_OK;
+    const hipError_t e = jb::launch_pitch(pt.utts.list, pt.utts.n, pt.tiles, pt.post, pt.cols, pt.cls, b.stream_voc);
+    return e == hipSuccess ? JB_OK : hip_fail(e, redo ? "pitch(redo)" : "pitch");
+}
+
 int OutputChain::check_ready(bool requested, const char *not_run, const char *not_set) const
 {
     if (requested && ready)
@@ -2304,6 +2466,9 @@ OutputChain::ByteSink OutputChain::byte_sink(SynthSink sink, size_t u) const
     case SynthSink::Melspec:
         return {ml_on, "melspec: the batch has not run", "melspec: jb_batch_set_melspec was not called",
                 slab[(size_t)OutSlab::Mel], true, span_of(plan.melspec, u)};
+    case SynthSink::Pitch:
+        return {pt_on, "pitch: the batch has not run", "pitch: jb_batch_set_pitch was not called",
+                pt.out, true, span_of(plan.pitch, u)};
     case SynthSink::Pcm:
         break;
     }

@@ -132,6 +132,10 @@ def _melspec_opts(opts, kw):
     return opts if opts is not None else F.melspec(**kw)
 
 
+def _pitch_opts(opts, kw):
+    return opts if opts is not None else F.pitch(**kw)
+
+
 def _drain(kw):
     """The keywords left in kw, taken out of it."""
     rest = dict(kw)
@@ -158,6 +162,8 @@ _PROGRAMME_SINKS = {
              lambda e, L, buf, n, cnt, o: F.take_mfcc(L, [buf], [n], 1, o[1], o[0].n_mels)[0]),
     "melspec": (lambda kw: (_melspec_opts(kw.pop("opts", None), _drain(kw)),), "jb_synthesize_programme_melspec", True,
                 lambda e, L, buf, n, cnt, o: F.take_melspec(L, [buf], [n], 1, o[0])[0]),
+    "pitch": (lambda kw: (_pitch_opts(kw.pop("opts", None), _drain(kw)),), "jb_synthesize_programme_pitch", True,
+              lambda e, L, buf, n, cnt, o: F.take_pitch(L, [buf], [n], 1, o[0])[0]),
 }
 
 
@@ -646,6 +652,24 @@ class Engine:
         F.check(self._L.jb_synthesize_batch_melspec(self._h, lines, offs, B, device, C.byref(opts), bufs, ns, nf))
         return F.take_melspec(self._L, bufs, ns, B, opts)
 
+    def synthesize_pitch(self, labels: Sequence[str], opts=None, **kw) -> np.ndarray:
+        """jb_synthesize_pitch: the pitch features [T, width] of what synthesize(labels) returns, tracked on the GPU.
+        opts: F.PitchOpts (J.kaldi_pitch(), J.pitch(...)), or the keywords of J.pitch."""
+        opts = _pitch_opts(opts, kw)
+        buf, n, nf = C.POINTER(C.c_uint8)(), C.c_size_t(), C.c_size_t()
+        F.check(self._L.jb_synthesize_pitch(self._h, _lines(labels), len(labels), C.byref(opts), C.byref(buf),
+                                            C.byref(n), C.byref(nf)))
+        return F.take_pitch(self._L, [buf], [n.value], 1, opts)[0]
+
+    def synthesize_pitch_batch(self, utterances: Sequence[Sequence[str]], opts=None, device: int = -1,
+                               **kw) -> List[np.ndarray]:
+        """jb_synthesize_batch_pitch: each utterance of synthesize_batch(...) as pitch features."""
+        opts = _pitch_opts(opts, kw)
+        lines, offs, B = _utt_lines(utterances)
+        bufs, ns, nf = _byte_outs(B, counts=True)
+        F.check(self._L.jb_synthesize_batch_pitch(self._h, lines, offs, B, device, C.byref(opts), bufs, ns, nf))
+        return F.take_pitch(self._L, bufs, ns, B, opts)
+
     def synthesize_programme(self, utterances: Sequence[Sequence[str]], sink: str = "f64", lead_ms: float = 0.0,
                              gap_ms: float = 0.0, trail_ms: float = 0.0, fade_ms: float = 0.0, device: int = -1,
                              mix=None, fit: bool = False, ceiling_db: float = 0.0, stems=None, levels: bool = False,
@@ -711,7 +735,7 @@ class Engine:
             L.jb_join_free(out)  # (malloc'ed by the library, as every output is)
             return res, list(starts[:B])
         if sink not in _PROGRAMME_SINKS:
-            raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm", "fbank", "mfcc" or "melspec"')
+            raise ValueError('sink is "f64", "i16", "flac", "formatted", "adpcm", "fbank", "mfcc", "melspec" or "pitch"')
         build, entry, counted, take = _PROGRAMME_SINKS[sink]
         opts = build(sink_opts)
         if sink_opts:
